@@ -11,15 +11,27 @@ runs the same steps on its own camera batches (cameras shard one per GPU, no dat
 weak scaling, value = frames all ranks processed / max-over-ranks time.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]        N > 1 without a launcher: bench.py starts its N ranks itself
+    python bench.py ... --dump-outputs DIR                                 also write the last timed step's outputs as DIR/*.npy
+    python bench.py ... --full                                             everything listed below as well
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus 2 --workload stereo [--exchange native|rccl]    config 4
     python bench.py --gpus N --workload loop_closure [--exchange ...]      config 5
 
-Timing: R rounds of EXACTLY K steps, each bracketed by barrier + torch.cuda.synchronize() on both sides and max-reduced
-over the ranks; rounds are added until they together time >= 0.5 s whatever K is (at least 3 rounds).
-value = units all ranks processed in a round / the MEDIAN round's time; value_spread = min / median / max over the rounds.
+Timing of the metric workload: a plain run times ONE region of EXACTLY K steps, bracketed by barrier +
+torch.cuda.synchronize() on both sides and max-reduced over the ranks; value = frames all ranks processed / its time,
+ms_per_step = its time / K.  Nothing else runs: set-up, warm-up (W steps, and more until it has lasted 0.5 s), the K
+steps, the outputs (--dump-outputs) and the line.
+With --full: R rounds of EXACTLY K steps, each bracketed the same way, added until they together time >= 0.5 s whatever K
+is (at least 3 rounds); value = units all ranks processed in a round / the MEDIAN round's time; value_spread = min /
+median / max over the rounds.  The stereo and loop-closure workloads always time their steps in such rounds.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+--dump-outputs DIR (metric workload, rank 0): what the last timed step returned to its caller, the frames of its batch
+concatenated in order, as float32 .npy: n_keypoints [F], level_counts [F, 8], keypoints [n, 6] (x, y, size, angle,
+response, octave), descriptors [n, 32] (byte values), match_idx / match_d1 / match_d2 [n], frames [F] (the batch indices
+of the F frames written: the whole batch, or a fixed sample of it where the whole would exceed 64 MB).  The frames are
+seeded and every round of timed steps runs the same steps, so the same arguments give the same inputs on every run.
+
+Rank 0 prints ONE JSON line.  With --full, besides the contract fields it carries
   sustained              (K < 500) one region of 1000 steps, the rate of a pipeline that stays full, with the rate of each 1/25th
   ranks_reported_by_backend  N > 1 (and forced world-1 groups): world size and an all-reduce of ones through the backend
   single_gpu_exchange    N = 1: configs 4 and 5 as child processes at world size 1 -- through a real "nccl" (RCCL) process
@@ -64,14 +76,22 @@ CACHE_BYTES = 256 << 20  # Infinity Cache: the rotating device batches must exce
 
 def make_frames(rank, n_sets, batch, w, h):
     """n_sets x batch DISTINCT frames: set s = scene (rank, s) at time steps 0 .. batch-1 (consecutive frames move
-    by (3,-2) px and carry fresh noise)."""
+    by (3,-2) px and carry fresh noise).  Every frame has its own seeded generator, so host threads make the same bytes
+    as one thread would; the pool is gone before anything forks."""
+    from concurrent.futures import ThreadPoolExecutor
     from send_slam_amd import synth
     out = np.empty((n_sets, batch, h, w), np.uint8)
-    for s in range(n_sets):
-        seed = 1000 * rank + s
-        sc = synth.scene(seed, w, h)
-        for t in range(batch):
-            out[s, t] = synth.frame_from_scene(sc, seed, w, h, t)
+    scenes = [None] * n_sets
+
+    def one_scene(s):
+        scenes[s] = synth.scene(1000 * rank + s, w, h)
+
+    def one_frame(st):
+        s, t = st
+        out[s, t] = synth.frame_from_scene(scenes[s], 1000 * rank + s, w, h, t)
+    with ThreadPoolExecutor(max(1, min(16, usable_cores()))) as pool:
+        list(pool.map(one_scene, range(n_sets)))
+        list(pool.map(one_frame, [(s, t) for s in range(n_sets) for t in range(batch)]))
     return out
 
 
@@ -210,12 +230,13 @@ def max_over_ranks(elapsed, world, dev, backend):
 
 
 MIN_REGION_S = 0.5  # whatever --steps is, the rounds together time at least this long
+MIN_WARMUP_S = 0.5  # a plain run's warm-up lasts at least this long: its ONE region then starts on a GPU at speed
 
 
-def timed_rounds(run_steps, steps, drain, world, dev, backend, max_rounds=400):
+def timed_rounds(run_steps, steps, drain, world, dev, backend, max_rounds=400, rounds=0):
     """R rounds of EXACTLY `steps` steps.  Every round is bracketed by barrier + torch.cuda.synchronize() on both sides and
-    its time is the MAX over ranks; rounds are added until they together last >= MIN_REGION_S, at least 3.  Returns the
-    list of round times in seconds."""
+    its time is the MAX over ranks; rounds are added until they together last >= MIN_REGION_S, at least 3, or exactly
+    `rounds` of them when it is given.  Returns the list of round times in seconds."""
     import torch
     import torch.distributed as dist
     d = use_dist(world)
@@ -232,7 +253,7 @@ def timed_rounds(run_steps, steps, drain, world, dev, backend, max_rounds=400):
             dist.barrier()
         return max_over_ranks(time.perf_counter() - t0, world, dev, backend)
     # every time in `times` is max-reduced, so every rank sees the same numbers and stops after the same round
-    fixed = int(os.environ.get("SENDSLAM_BENCH_ROUNDS", "0"))
+    fixed = rounds or int(os.environ.get("SENDSLAM_BENCH_ROUNDS", "0"))
     times = []
     while len(times) < max_rounds:
         times.append(one())
@@ -696,6 +717,38 @@ def exchange_legs(timeout_s=240):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much
+
+
+def dump_outputs(path, ctx, match_out, batch):
+    """--dump-outputs: the results of the context's last step as its caller receives them (ss_fetch_frame per frame and the
+    step's match arrays), the frames of the batch concatenated in order, as float32 DIR/<name>.npy.  Where the whole batch
+    could exceed DUMP_LIMIT_BYTES, a fixed seeded sample of its frames (bounded by the keypoint capacity, not by the
+    outputs, so two builds pick the same frames)."""
+    from send_slam_amd import binding
+    kcap = ctx.batch_view().kp_capacity
+    per_frame = kcap * (len(binding.KP_DTYPE.names) + 32 + 3) * 4 + (2 + ctx.params.n_levels) * 4
+    n_frames = min(batch, max(1, DUMP_LIMIT_BYTES // per_frame))
+    frames = np.arange(batch) if n_frames == batch else np.sort(np.random.default_rng(0).choice(batch, n_frames, replace=False))
+    m_idx, m_d1, m_d2 = (t.cpu().numpy() for t in match_out)
+    parts = {k: [] for k in ("n_keypoints", "level_counts", "keypoints", "descriptors", "match_idx", "match_d1", "match_d2")}
+    for b in frames:
+        kps, desc, levels = ctx.fetch_frame(int(b))
+        n = len(kps)
+        parts["n_keypoints"].append(n)
+        parts["level_counts"].append(levels)
+        parts["keypoints"].append(np.stack([kps[f].astype(np.float32) for f in binding.KP_DTYPE.names], axis=1))
+        parts["descriptors"].append(desc)
+        parts["match_idx"].append(m_idx[b, :n])
+        parts["match_d1"].append(m_d1[b, :n])
+        parts["match_d2"].append(m_d2[b, :n])
+    arrays = {"frames": frames, "n_keypoints": np.array(parts.pop("n_keypoints")), "level_counts": np.stack(parts.pop("level_counts"))}
+    arrays.update({k: np.concatenate(v) for k, v in parts.items()})
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def self_launch(n):
     import signal
     import socket
@@ -741,9 +794,14 @@ def main():
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--features", type=int, default=2000)
     ap.add_argument("--contexts", type=int, default=4, help="camera batches in flight per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="metric workload: time rounds of K steps (value = median round) and add everything beside the headline: "
+                         "per-kernel events, rooflines, parity against the oracle, the CPU baseline and the other legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="metric workload: write the outputs of the last timed step as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--timed-only", action="store_true",
-                    help="only warm-up + timed steps: no isolated pass, database-streaming, host-pipeline, latency or tracking "
+                    help="with --full: only warm-up + timed rounds: no isolated pass, database-streaming, host-pipeline, latency or tracking "
                          "extras (what the rocprofv3 --stats runs use, so every launch they average is a launch of the timed loop)")
     ap.add_argument("--profile-extra", default="", choices=["", "match_stream"],
                     help="run ONLY that extra leg (for rocprofv3 of the database-streaming kernel)")
@@ -787,9 +845,10 @@ def main():
         return
 
     frames = make_frames(rank, n_sets, B, w, h)
+    extras = a.full and not a.timed_only  # the legs beside the timed steps
 
     cpu_obj, cpu_outs = None, []
-    if rank == 0 and a.gpus == 1 and not a.no_cpu_baseline and not a.profile_extra:
+    if rank == 0 and a.gpus == 1 and a.full and not a.no_cpu_baseline and not a.profile_extra:
         cpu_obj, cpu_outs = cpu_baseline(frames[0], nf)  # before any HIP call in this process
 
     import torch
@@ -819,32 +878,51 @@ def main():
         c.extract_batch_device(d_sets[i % n_sets].data_ptr(), B, w, h)
         c.match_batch_device(0, o_idx.data_ptr(), o_d1.data_ptr(), o_d2.data_ptr())
 
+    t_warm = time.perf_counter()
     for i in range(max(a.warmup, n_ctx)):
         step(i)
     for c in ctxs:
         c.synchronize()
+    # A plain run times one region, so a short one would otherwise start while the GPU still ramps up (measured at
+    # --steps 20 --warmup 5: 2 % below the same region after 0.5 s of steps); --full's median round is past that ramp.
+    # The extra steps are warm-up only: the timed steps below are the same steps whatever it took.
+    i = max(a.warmup, n_ctx)
+    while not a.full and time.perf_counter() - t_warm < MIN_WARMUP_S:
+        for _ in range(8 * n_ctx):
+            step(i)
+            i += 1
+        for c in ctxs:
+            c.synchronize()
 
-    # per-kernel HIP events on each context's own stream, live over the timed rounds (SENDSLAM_BENCH_NO_EVENTS=1
+    # --full: per-kernel HIP events on each context's own stream, live over the timed rounds (SENDSLAM_BENCH_NO_EVENTS=1
     # switches them off to measure what they cost)
-    live_events = os.environ.get("SENDSLAM_BENCH_NO_EVENTS") != "1"
+    live_events = a.full and os.environ.get("SENDSLAM_BENCH_NO_EVENTS") != "1"
     for c in ctxs:
         c.profile(live_events)
         c.profile_reset()
-    next_step = [max(a.warmup, n_ctx)]  # the step counter runs on over the rounds: contexts and frame sets keep rotating
+    first_timed = max(a.warmup, n_ctx)
+    next_step = [first_timed]  # the step counter runs on after the rounds: contexts and frame sets keep rotating
 
     def run_steps(k):
         for i in range(next_step[0], next_step[0] + k):
             step(i)
         next_step[0] += k
 
+    def run_round(k):
+        next_step[0] = first_timed  # every round runs the same steps: the last one's inputs do not depend on the round count
+        run_steps(k)
+
     def drain():
         for c in ctxs:
             c.synchronize()  # drains the context's stream and checks the per-frame error words
-    # R rounds of exactly `steps` steps, each bracketed by barrier + synchronize and max-reduced over the ranks; together
-    # >= 0.5 s whatever --steps is.  value = the median round.
-    times = timed_rounds(run_steps, steps, drain, world, dev, backend)
+    # A plain run: ONE region of exactly `steps` steps.  --full: R rounds of exactly `steps` steps, together >= 0.5 s
+    # whatever --steps is, value = the median round.  Either way bracketed by barrier + synchronize, max-reduced over the ranks.
+    times = timed_rounds(run_round, steps, drain, world, dev, backend, rounds=0 if a.full else 1)
     elapsed, spread = round_summary(times, B * steps * world, "frames/s")
-    reported = backend_world(world, dev, backend)
+    if a.dump_outputs and rank == 0:
+        k_last = (first_timed + steps - 1) % n_ctx  # the context of the last timed step: its buffers hold that step's results
+        dump_outputs(a.dump_outputs, ctxs[k_last], outs[k_last], B)
+    reported = backend_world(world, dev, backend) if a.full else None
 
     # per-kernel HIP-event statistics of the timed loop (summed over the contexts)
     def merged_stats(cs):
@@ -868,7 +946,7 @@ def main():
     # bracketed like a round, with the rate of each 1/25th of it from events recorded on the contexts' streams (no drain
     # in between).  Reported next to `value`, never instead.
     sustained = None
-    if not a.timed_only and steps < 500:
+    if extras and steps < 500:
         s_steps, n_chunks = 1000, 25
         ext = [torch.cuda.ExternalStream(c.stream(), device=dev) for c in ctxs]
         chunk_ev = []
@@ -911,7 +989,7 @@ def main():
     # parity of the measured configuration: EVERY context's last timed batch against the oracle (frame 1 + its own
     # index of that batch: the oracle costs 0.1 s per frame), then all frames of the baseline leg on context 0
     parity = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         from oracle import orb_oracle as O
         parity = True
         p = O.default_params(n_features=nf)
@@ -942,7 +1020,7 @@ def main():
     # when it has the GPU to itself -- the number rocprofv3's kernel trace reports for the same kernel -- reported next
     # to the live number, never instead.
     iso = {}
-    if not a.timed_only:
+    if extras:
         ctx.profile(True)
         ctx.profile_reset()
         for i in range(2 * n_sets):
@@ -957,7 +1035,7 @@ def main():
     # steps of one scene: SURVEY.md section 8(d) asks for "frame t vs t + 1" beside the self-match), four batches in
     # flight like the timed region; two pairs checked against the oracle.  Never `value`.
     consecutive = None
-    if not a.timed_only:
+    if extras:
         def step_prev(i):
             k = i % n_ctx
             c, (o_idx, o_d1, o_d2) = ctxs[k], outs[k]
@@ -997,7 +1075,7 @@ def main():
     # Latency path of the drop-in boundary (what the NIF / front door call per camera frame):
     # host pixels in, host keypoints + descriptors out, PCIe copies included.  Never `value`.
     lat = []
-    for i in range(0 if a.timed_only else 12):
+    for i in range(12 if extras else 0):
         t1 = time.perf_counter()
         ctx.extract(frames[0, i % B])
         lat.append(time.perf_counter() - t1)
@@ -1007,7 +1085,7 @@ def main():
     # Same boundary one step further (ss_track: extraction + match on the GPU, pose geometry on the
     # host) on a parallax sequence, rank 0 only: per-frame time in tracking state OK.  Never `value`.
     track_ms = track_ok = None
-    if rank == 0 and not a.timed_only:
+    if rank == 0 and extras:
         from send_slam_amd import synth
         cam = binding.Camera(type=b"PinHole", fx=800.0, fy=800.0, cx=w / 2.0, cy=h / 2.0, width=w, height=h, fps=30.0,
                              rgb=1, th_depth=40.0, baseline=0.0, depth_map_factor=1000.0)
@@ -1031,7 +1109,7 @@ def main():
     del d_sets, outs
 
     match_stream = host_pipe = frontdoor = None
-    if rank == 0 and not a.timed_only:
+    if rank == 0 and extras:
         torch.cuda.empty_cache()
         match_stream = bench_match_stream(binding, torch, dev, local_rank)
         torch.cuda.empty_cache()
@@ -1052,7 +1130,7 @@ def main():
     # "nccl" process group: the all_gather / broadcast of their steps go through RCCL, so that branch has executed on the
     # hardware the line was measured on; then the same steps over the C ABI's own exchange.  Never `value`.
     single_gpu_exchange = None
-    if world == 1 and not a.timed_only and os.environ.get("SENDSLAM_BENCH_NO_EXCHANGE_LEGS") != "1":
+    if world == 1 and extras and os.environ.get("SENDSLAM_BENCH_NO_EXCHANGE_LEGS") != "1":
         single_gpu_exchange = exchange_legs()
 
     kernels = []
@@ -1145,7 +1223,13 @@ def main():
                    "n_features": nf, "n_levels": 8, "scale_factor": 1.2,
                    "match": "self-match all-pairs, j==i excluded, TH 50, ratio 9/10",
                    "parallelism": f"one camera batch per GPU x {world}, no collective"},
-        "rounds": len(times), "timed_region_s": round(sum(times), 4), "value_spread": spread, "sustained": sustained,
+        "rounds": len(times), "timed_region_s": round(sum(times), 4),
+    }
+    if not a.full:
+        print(json.dumps(out))
+        return
+    out.update({
+        "value_spread": spread, "sustained": sustained,
         "ranks_reported_by_backend": reported, "single_gpu_exchange": single_gpu_exchange,
         "roofline": roofline, "valu_roofline": valu_roofline, "match_roofline": match_roofline,
         "match_stream_roofline": match_stream, "consecutive_frames": consecutive, "host_pipeline": host_pipe, "frontdoor": frontdoor, "kernels": kernels, "cpu_baseline": cpu_obj,
@@ -1153,7 +1237,7 @@ def main():
         "parity_note": "oracle = the committed CPU restatement; parity with the real ORB-SLAM3 binary is unpinned (DESIGN.md section 3)",
         "single_frame_host_to_host_ms": None if single_frame_ms is None else round(single_frame_ms, 3),
         "track_frame_host_to_host_ms": None if track_ms is None else round(track_ms, 3), "track_ok_frames_of_14": track_ok,
-    }
+    })
     print(json.dumps(out))
 
 

@@ -6,7 +6,7 @@ TAG=${1:-r03}
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py"
+B="python3 $R/bench.py --full"
 $B > $O/${TAG}_bench_final.json 2> $O/${TAG}_bench_final.err && echo "bench ok" &&
 $B --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_steps20.json 2> $O/${TAG}_bench_steps20.err && echo "bench steps20 ok" &&
 export SENDSLAM_BENCH_ROUNDS=1 &&

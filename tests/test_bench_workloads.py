@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,7 +57,7 @@ def test_loop_closure_workload_two_ranks_one_card():
 
 
 def test_metric_workload_two_ranks_one_card_carries_rooflines():
-    j = run_bench(2, "--steps", "8", "--warmup", "4", "--batch", "8", "--contexts", "2", "--no-cpu-baseline")
+    j = run_bench(2, "--steps", "8", "--warmup", "4", "--batch", "8", "--contexts", "2", "--no-cpu-baseline", "--full")
     check_contract(j, 2)
     assert j["scaling"] == "weak" and j["config"]["frames_per_step_per_gpu"] == 8 and j["rounds"] >= 3 and j["value_spread"]
     assert j["match_roofline"] and j["match_stream_roofline"]["frac"] > 0.3
@@ -76,9 +77,9 @@ def run_plain(n, *args, env_extra=None):
 
 
 def test_plain_invocation_gpus_2_launches_its_own_ranks():
-    """the driver's command shape with N = 2 and --steps 20: no launcher, rounds of exactly 20 steps that together time
-    >= 0.5 s, value_spread filled, rooflines on the N > 1 line, the rank count the backend itself reports"""
-    j = run_plain(2, "--steps", "20", "--warmup", "5", "--no-cpu-baseline")
+    """the driver's command shape with N = 2 and --steps 20 (--full): no launcher, rounds of exactly 20 steps that together
+    time >= 0.5 s, value_spread filled, rooflines on the N > 1 line, the rank count the backend itself reports"""
+    j = run_plain(2, "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--full")
     check_contract(j, 2)
     assert j["steps"] == 20 and j["rounds"] >= 3 and j["timed_region_s"] >= 0.5
     sp = j["value_spread"]
@@ -87,6 +88,53 @@ def test_plain_invocation_gpus_2_launches_its_own_ranks():
     assert j["sustained"] and j["sustained"]["steps"] >= 1000 and j["sustained"]["chunks"]["n"] >= 20
     assert j["valu_roofline"]["frac_of_architectural_peak"] < j["valu_roofline"]["frac"]
     assert j["cpu_baseline"] is None  # rank 0 at N = 1 only
+
+
+def test_plain_run_times_exactly_its_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: ONE region of exactly K steps, the contract fields and
+    nothing measured beside them; DIR holds the last timed step's outputs, two of its frames checked against the oracle"""
+    from oracle import orb_oracle as O
+    from send_slam_amd import synth
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
+        env.pop(k, None)
+    steps, warmup = 6, 2
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["steps"] == steps and j["rounds"] == 1 and j["unit"] == "frames/s" and j["higher_is_better"] is True
+    assert abs(j["ms_per_step"] * steps - j["timed_region_s"] * 1e3) <= 0.1  # timed_region_s carries 0.1 ms
+    assert abs(j["value"] - j["config"]["frames_per_step_per_gpu"] * 1e3 / j["ms_per_step"]) <= 1e-3 * j["value"]
+    for k in ("roofline", "cpu_baseline", "parity_checked_vs_oracle", "value_spread", "kernels", "host_pipeline"):
+        assert k not in j, k  # --full only
+
+    names = ("frames", "n_keypoints", "level_counts", "keypoints", "descriptors", "match_idx", "match_d1", "match_d2")
+    d = {n: np.load(str(tmp_path / (n + ".npy"))) for n in names}
+    assert all(a.dtype == np.float32 for a in d.values())
+    assert sum(os.path.getsize(str(tmp_path / (n + ".npy"))) for n in names) <= 64 * 10 ** 6
+    cfg = j["config"]
+    B, w, h, nf = cfg["frames_per_step_per_gpu"], 1280, 720, cfg["n_features"]
+    assert d["frames"].tolist() == list(range(B))
+    n = d["n_keypoints"].astype(np.int64)
+    assert int(n.sum()) == len(d["keypoints"]) == len(d["descriptors"]) == len(d["match_idx"]) == len(d["match_d2"])
+    # the last timed step ran on frame set (max(W, contexts) + K - 1) % sets of rank 0
+    s = (max(warmup, cfg["batches_in_flight_per_gpu"]) + steps - 1) % cfg["distinct_device_batches_rotated"]
+    sc = synth.scene(s, w, h)
+    off = np.concatenate([[0], np.cumsum(n)])
+    p = O.default_params(n_features=nf)
+    for b in (0, B - 1):
+        okps, odesc, ocounts = O.extract(synth.frame_from_scene(sc, s, w, h, b), p)
+        oidx, od1, od2 = O.match(odesc, odesc, 50, 9, 10, exclude_self=True)
+        r = slice(off[b], off[b + 1])
+        assert n[b] == len(okps) and np.array_equal(d["level_counts"][b], ocounts)
+        assert np.array_equal(d["keypoints"][r, 0], okps["x"]) and np.array_equal(d["keypoints"][r, 3], okps["angle"])
+        assert np.array_equal(d["keypoints"][r, 5], okps["octave"]) and np.array_equal(d["descriptors"][r], odesc)
+        assert np.array_equal(d["match_idx"][r], oidx) and np.array_equal(d["match_d1"][r], od1) and np.array_equal(d["match_d2"][r], od2)
 
 
 def test_native_exchange_stereo_and_loop_closure_two_ranks_one_card():

@@ -1,7 +1,8 @@
 """Pins that are possible in this image without the reference's third-party code:
 
   (a) the recalled rBRIEF table against the copy of OpenCV's bit_pattern_31_ that scikit-image ships as a DATA
-      file (read as text, nothing imported); skipped where that file is absent;
+      file (skimage/feature/orb_descriptor_positions.txt, scikit-image 0.18.3), stored as integers in
+      tests/golden/orb_descriptor_positions.txt (read as text, nothing imported);
   (b) the 7x7 sigma-2 Gaussian taps derived from exp(-d^2 / 8) and OpenCV's error-diffusion rule for the 8-bit
       fixed-point kernel instead of trusting the literal {18, 34, 48, 56, ...};
   (c) the loader of tests/golden/ref_dump/ (README there): the day a maintainer drops a dump of the real
@@ -9,7 +10,6 @@
       is exercised on a dump written from the oracle into a temporary directory, so an empty ref_dump/ does not
       mean an untested loader.  Until a real dump exists parity with ORB-SLAM3 stays UNPINNED.
 """
-import glob
 import os
 
 import numpy as np
@@ -20,15 +20,11 @@ import ref_dump
 from send_slam_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SKIMAGE_PATTERN = [p for pat in ("/opt/conda/lib/python3*/site-packages/skimage/feature/orb_descriptor_positions.txt",
-                                 "/usr/lib/python3*/site-packages/skimage/feature/orb_descriptor_positions.txt",
-                                 "/usr/local/lib/python3*/*-packages/skimage/feature/orb_descriptor_positions.txt")
-                   for p in glob.glob(pat)]
+SKIMAGE_PATTERN = os.path.join(ROOT, "tests", "golden", "orb_descriptor_positions.txt")
 
 
-@pytest.mark.skipif(not SKIMAGE_PATTERN, reason="scikit-image's orb_descriptor_positions.txt is not on this image")
 def test_bit_pattern_equals_the_opencv_table_scikit_image_ships():
-    want = np.loadtxt(SKIMAGE_PATTERN[0]).astype(np.int64)
+    want = np.loadtxt(SKIMAGE_PATTERN).astype(np.int64)
     assert want.shape == (256, 4)
     orc = pyref.parse_c_int_table(os.path.join(ROOT, "oracle/orb_constants.h"), "ORC_BIT_PATTERN_31")
     assert orc == want.reshape(-1).tolist()

@@ -54,6 +54,7 @@ extern "C" {
 
 #define SS_ABI_VERSION 5
 #define SS_MAX_LEVELS 16
+#define SS_MAX_CAMERAS 8 /* cameras one context tracks (ss_track*), each with its own state */
 #define SS_DESC_BYTES 32
 
 typedef enum {
@@ -186,6 +187,20 @@ int ss_match_device(ss_ctx *ctx, const void *d_query, int n_query, const void *d
  * device arrays [n_frames][kp_capacity]; rows >= n_keypoints[b] are idx -1. */
 int ss_match_batch_device(ss_ctx *ctx, int mode, int th, int ratio_num, int ratio_den,
                           void *d_idx, void *d_d1, void *d_d2);
+/* Matches every frame of the last batch against a train frame named per frame by a table (the table form of
+ * ss_match_batch_device, e.g. each frame against the previous frame of its own camera).  train_src is a HOST array
+ * [n_frames]; for query frame b, t = train_src[b]:
+ *   t >= 0   frame t of the batch (0 <= t < n_frames, earlier or later); the pair j == i is excluded iff t == b;
+ *   t == -1  no train: rows < n_keypoints[b] get idx -1 and d1 = d2 = 0xFFFF;
+ *   t <= -2  carry frame c = -2 - t (0 <= c < n_carry): d_carry is a device array [n_carry][kp_capacity][32] of packed
+ *            descriptors (kp_capacity of ss_get_batch_view) and d_carry_n a device int32 [n_carry] of their row counts
+ *            (<= kp_capacity); no self-exclusion.
+ * Any other value is SS_ERR_INVALID_ARG.  d_carry / d_carry_n may be NULL when n_carry == 0.  th / ratio and the outputs
+ * are those of ss_match_batch_device.  Asynchronous on the context's stream; the table is copied before the call returns,
+ * the carry is read by the device (on the matrix-core path it is first expanded into a context buffer). */
+int ss_match_batch_sources_device(ss_ctx *ctx, const int32_t *train_src, const void *d_carry, const void *d_carry_n,
+                                  int n_carry, int th, int ratio_num, int ratio_den, void *d_idx, void *d_d1,
+                                  void *d_d2);
 
 /* n_frames independent (query frame, train frame) pairs in one launch, e.g. the frames of this GPU's eye against the
  * all-gathered frames of the peer eye.  Both sides are device arrays
@@ -217,7 +232,16 @@ typedef struct {
  * No keyframes, local mapping, loop closing or relocalisation. */
 int ss_track(ss_ctx *ctx, int camera_id, const uint8_t *pix, int width, int height, int channels,
              int row_stride, double timestamp, ss_pose *out);
-/* back to NO_IMAGES_YET (System::Reset / the "terminate" message :462-469) */
+/* Several cameras on one context: every camera id gets its own tracker state (reference, previous frame, motion model)
+ * and descriptor buffers, up to SS_MAX_CAMERAS ids in the order they first appear; a further id is SS_ERR_INVALID_ARG.
+ * ss_set_calibration(camera_id) gives that camera its own calibration (intrinsics, distortion, and for ss_track the
+ * RGB order of colour frames) and resets that camera only; a camera that was never sent a calibration uses the
+ * calibration set last.  An id takes its slot with its calibration or its first successful pose-step call (a frame
+ * that fails extraction takes none).  One camera's frames must arrive in order; frames of different cameras may
+ * interleave.  Batch extraction (ss_extract_batch_device, ss_pipe) has no camera ids: its colour frames use the RGB
+ * order of the calibration set last, so the cameras of one pipe share one RGB order.
+ * ss_track_reset: every camera back to NO_IMAGES_YET (System::Reset / the "terminate" message :462-469); cameras
+ * without a calibration of their own give their slots back. */
 int ss_track_reset(ss_ctx *ctx);
 
 /* The matrix-core matcher reads descriptors as rows of 256 FP4 values (one per bit, +1 / -1: 128 bytes).  The frames of a
@@ -242,16 +266,24 @@ int ss_track_features(ss_ctx *ctx, int camera_id, double timestamp, const void *
 
 /* ss_track_features for a caller that has matched the frames of a batch against each other already (ss_pipe match_mode 1,
  * ss_match_batch_device mode 1, with th 50 and ratio 9 / 10 -- the pose step's own rule): match_idx / match_d1 are host
- * arrays of n_keypoints entries, this frame's matches against the frame of the PREVIOUS pose-step call on this context
- * that returned SS_OK (NULL, NULL: none -- also the thing to pass after a call that failed).  They are used when that
+ * arrays of n_keypoints entries, this frame's matches against the frame of the PREVIOUS pose-step call FOR THE SAME CAMERA
+ * on this context that returned SS_OK (NULL, NULL: none -- also the thing to pass after a call that failed).  They are used when that
  * frame is the one the tracker is about to match against (tracking, or the frame right after a new reference); in every
  * other case the tracker runs its own device match, as ss_track_features does, so the poses are the same either way.  flags: SS_TRACK_DESC_STAYS_VALID = d_descriptors stays valid and unchanged
  * until the next pose-step call on this context has returned (the rows of a pipe slot that is released after its last
- * frame): the tracker then refers to them instead of copying them.  With both, a tracked frame costs no device work. */
+ * frame): the tracker then refers to them instead of copying them, and never reads them after that next call has
+ * returned (it copies them first where it still needs them, see ss_track_detach).  With both, a tracked frame costs
+ * no device work. */
 #define SS_TRACK_DESC_STAYS_VALID 1
 int ss_track_features_matched(ss_ctx *ctx, int camera_id, double timestamp, const void *d_descriptors,
                               const ss_keypoint *keypoints, int n_keypoints, const int32_t *match_idx,
                               const uint16_t *match_d1, int flags, ss_pose *out);
+/* The rows a camera's tracker refers to under SS_TRACK_DESC_STAYS_VALID are copied into the context ("detached") by the
+ * next pose-step call for ANOTHER camera (before it returns), dropped by the next call for the SAME camera (which either
+ * replaces them or leaves the camera without a previous frame), and copied by ss_track_detach for every camera at once: call it
+ * before the memory of those rows is reused or freed (e.g. before releasing a pipe slot whose frames were tracked, even
+ * when its last frames were skipped), after which the caller owes nothing.  Poses do not depend on where the rows live. */
+int ss_track_detach(ss_ctx *ctx);
 
 /* ---- a database partitioned over GPUs ------------------------------------
  * A shard reports, per query descriptor, ss_match_part = (best distance, second-best distance, GLOBAL row of the
@@ -351,7 +383,8 @@ typedef struct {
     int32_t width, height, channels; /* every frame of the pipe has this shape */
     int32_t batch;                   /* frames per slot, 1..256 */
     int32_t depth;                   /* slots, 2..16 */
-    int32_t match_mode;              /* -1 none; 0 self-match; 1 frame b against frame b-1 of the batch (ss_match_batch_device) */
+    int32_t match_mode;              /* -1 none; 0 self-match; 1 frame b against frame b-1 of the batch (ss_match_batch_device);
+                                      * 2 each frame against the previous frame of its own camera (below) */
     int32_t match_th, ratio_num, ratio_den; /* 0 0 0 = the defaults 50, 9, 10 */
     int32_t copy_threads;            /* host threads of ss_pipe_submit_frames; 0 = 4 */
 } ss_pipe_config;
@@ -400,6 +433,18 @@ int ss_pipe_poll(ss_pipe *pipe, ss_pipe_result *out);
 int ss_pipe_release(ss_pipe *pipe, int slot);
 /* batches submitted and not yet returned by wait / poll */
 int ss_pipe_in_flight(const ss_pipe *pipe);
+/* match_mode 2 (several cameras in one stream): a frame's train is the latest earlier frame, in submission order across
+ * batches, with the same camera_id and a producer-side status of SS_OK (a NULL frame, camera id 0).  The train table is
+ * built at submission (ss_match_batch_sources_device).  A train in an earlier batch comes from the pipe's carry: the last
+ * such frame of up to SS_MAX_CAMERAS cameras, updated on the device after each batch's match by one gather launch; a
+ * batch's match waits for the previous batch's carry update, extractions of different slots still overlap.  Frames of
+ * further cameras get trains inside their batch only.  A submission that fails half-way empties the carry: the next
+ * batch's first frame of each camera then has no train.  A frame whose train turns out bad on the device (SS_ERR_OVERFLOW)
+ * gets match_idx -1, as in mode 1.
+ * ss_pipe_match_sources: for each frame of a returned, unreleased slot of a mode-2 pipe, the (sequence, index in its batch)
+ * of the frame it was matched against, or -1 / -1 (no train, or its matches were voided); arrays of n_frames entries.
+ * SS_ERR_STATE for another mode or slot state. */
+int ss_pipe_match_sources(const ss_pipe *pipe, int slot, int64_t *train_sequence, int32_t *train_frame);
 /* Test hook: the next submission fails (SS_ERR_HIP, "injected failure ...") after `after_operations` of its enqueues have
  * been issued.  A submission that fails half-way drains its streams before it returns, leaves the slot ACQUIRED (release or
  * resubmit it) and the pipe usable; ss_pipe_submit_frames frees its slot itself. */

@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Kernel-by-kernel comparison of the gfx950 instruction streams of two builds of csrc/ss_kernels.hip.
+
+    hipcc --offload-arch=gfx950 <Makefile CXXFLAGS> --cuda-device-only -c csrc/ss_kernels.hip -o before.co   (parent commit)
+    hipcc ... -o after.co                                                                                   (this tree)
+    python3 profiles/tools/isa_diff.py before.co after.co
+
+Runs on a machine without a GPU.  The batch matchers gained a table form through a trailing
+template parameter pack (`typename... TAB`, empty in the existing forms): an instantiation with the empty pack is compared
+with the kernel of the same name and template arguments before; kernels only the new build has are listed.  Branch targets are compared as
+offsets inside their function, so code that moved inside the object still compares equal.  Exit status 1 when an
+instruction stream differs."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+
+
+def disassemble(bundle):
+    with tempfile.TemporaryDirectory() as d:
+        elf = os.path.join(d, "k.elf")
+        subprocess.check_call([f"{ROCM}/llvm/bin/clang-offload-bundler", "--unbundle", "--type=o", f"--input={bundle}",
+                               f"--targets={TARGET}", f"--output={elf}"])
+        text = subprocess.check_output([f"{ROCM}/llvm/bin/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", elf], text=True)
+    funcs, name = {}, None
+    for line in text.splitlines():
+        m = re.match(r"^<(\S+)>:$", line)
+        if m:
+            name = m.group(1)
+            funcs[name] = []
+            continue
+        if name is None or not line.strip():
+            continue
+        # "op args  // ADDR: ENC <sym+0xoff>" -> "op args <sym+0xoff>"; branch immediates are relative already
+        ins = line.split("//")[0].strip()
+        tgt = re.search(r"<[^>]*(\+0x[0-9a-f]+)>", line)
+        body = funcs[name]
+        if body and body[-1].startswith("s_getpc_b64") and ins.startswith("s_add_u32"):
+            ins = re.sub(r"0x[0-9a-f]+$", "<pc-relative>", ins)  # address of a constant table: where the linker put it
+        body.append(ins + (f" <{tgt.group(1)}>" if tgt else ""))
+    return funcs
+
+
+def demangle(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines()
+    return dict(zip(names, out))
+
+
+def old_name(dem):
+    """the name the kernel had before the table form: the table is a trailing parameter pack, empty in the forms without it
+    (k_match<>(...) was the plain function k_match(...), whose demangled name has no return type)"""
+    return re.sub(r"^void (.*)<>\(", r"\1(", dem)
+
+
+def main():
+    before, after = disassemble(sys.argv[1]), disassemble(sys.argv[2])
+    db, da = demangle(list(before)), demangle(list(after))
+    by_old = {db[n]: n for n in before}
+    same = differ = 0
+    matched = set()
+    for n in after:
+        o = old_name(da[n])
+        if o not in by_old:
+            print(f"new   {da[n][:140]}")
+            continue
+        matched.add(o)
+        if before[by_old[o]] == after[n]:
+            same += 1
+        else:
+            differ += 1
+            print(f"DIFF  {o[:140]}  ({len(before[by_old[o]])} -> {len(after[n])} instructions)")
+    for o in by_old:
+        if o not in matched:
+            print(f"gone  {o[:140]}")
+            differ += 1
+    print(f"{same} kernels identical, {differ} differ or are gone")
+    return 1 if differ else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -43,6 +43,32 @@ template <typename T> void dev_free(T *&p)
 
 } // namespace
 
+/* ss_track state of one camera: the tracker, the descriptors of its initialisation reference / previous frame, its own
+ * calibration (if it has been sent one) */
+struct cam_track {
+    int camera_id = 0; /* 0: a free slot */
+    bool has_cam = false;
+    ss_camera cam{};
+    sst_tracker tracker;
+    uint8_t *d_ref_desc = nullptr, *d_prev_desc = nullptr;
+    size_t d_ref_desc_bytes = 0, d_prev_desc_bytes = 0;
+    uint8_t *d_ref_desc_x = nullptr, *d_prev_desc_x = nullptr; /* the same rows as matrix-core operands (128 B each) */
+    size_t d_ref_desc_x_bytes = 0, d_prev_desc_x_bytes = 0;
+    /* this camera's pose-step calls are numbered: which call's frame the tracker holds as its previous / reference frame, and
+     * whether the previous frame's descriptors are still the caller's rows (ss_track_features_matched, prev_ext_n of them) */
+    int64_t serial = 0, prev_serial = -1, ref_serial = -1;
+    const uint8_t *d_prev_ext = nullptr;
+    int prev_ext_n = 0;
+
+    void reset()
+    {
+        tracker.reset();
+        prev_serial = ref_serial = -1;
+        d_prev_ext = nullptr;
+        prev_ext_n = 0;
+    }
+};
+
 struct ss_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -91,6 +117,13 @@ struct ss_ctx {
     size_t d_mq_bytes = 0, d_mt_bytes = 0, d_mout_bytes = 0, d_part_tmp_bytes = 0;
     uint8_t *d_qx = nullptr, *d_tx = nullptr; /* caller descriptors expanded to the matrix-core matcher's operand rows */
     size_t d_qx_bytes = 0, d_tx_bytes = 0;
+    int32_t *d_train_src = nullptr; /* ss_match_batch_sources_device: the train table on the device */
+    size_t d_train_src_bytes = 0;
+    int32_t *h_train_src = nullptr; /* ... staged in pinned memory; the event marks the end of its last copy */
+    int h_train_src_n = 0;
+    hipEvent_t train_src_copied = nullptr;
+    uint8_t *d_carry_x = nullptr; /* its carry frames expanded to operand rows */
+    size_t d_carry_x_bytes = 0;
 
     /* host results of ss_extract */
     std::vector<ss_keypoint> h_kps;
@@ -100,12 +133,9 @@ struct ss_ctx {
     int last_n_frames = 0;
     ss_lvl0 last_lvl0; /* where level 0 of the last batch lives (ptr == NULL: in the pyramid block) */
 
-    /* ss_track: descriptors of the initialisation reference / the previous frame, host geometry */
-    uint8_t *d_ref_desc = nullptr, *d_prev_desc = nullptr;
-    size_t d_ref_desc_bytes = 0, d_prev_desc_bytes = 0;
-    uint8_t *d_ref_desc_x = nullptr, *d_prev_desc_x = nullptr; /* the same rows as matrix-core operands (128 B each) */
-    size_t d_ref_desc_x_bytes = 0, d_prev_desc_x_bytes = 0;
-    sst_tracker tracker;
+    /* ss_track: one state per camera id, slots taken in the order the ids first appear; host geometry buffers */
+    cam_track cams[SS_MAX_CAMERAS];
+    int n_cams = 0;
     std::vector<float> h_xy;
     std::vector<int32_t> h_oct, h_midx;
     std::vector<uint16_t> h_md1;
@@ -114,10 +144,6 @@ struct ss_ctx {
      * geometry = sst_tracker::step, keep = copies of the descriptors the next frame matches against) */
     bool track_timing = false;
     double t_match = 0, t_geom = 0, t_keep = 0;
-    /* calls of the pose step are numbered: which call's frame the tracker holds as its previous / reference frame, and
-     * whether the previous frame's descriptors are still the caller's rows (ss_track_features_matched) */
-    int64_t track_serial = 0, prev_serial = -1, ref_serial = -1;
-    const uint8_t *d_prev_ext = nullptr;
     int64_t n_tracked = 0;
     bool profile = false;
     std::vector<stage_rec> stages;
@@ -299,7 +325,7 @@ int ensure_geometry(ss_ctx *c, int w, int h)
 int64_t level_px(const ss_geom &g, int l) { return (int64_t)g.lv[l].w * g.lv[l].h; }
 
 /* the per-batch kernel sequence; d_pix is device memory */
-int run_extract(ss_ctx *c, const void *d_pix, int n, int channels, int64_t row_stride, int64_t frame_stride)
+int run_extract(ss_ctx *c, const void *d_pix, int n, int channels, int64_t row_stride, int64_t frame_stride, int rgb_flag = -1)
 {
     const ss_geom &g = c->hg;
     hipStream_t s = c->stream;
@@ -327,7 +353,8 @@ int run_extract(ss_ctx *c, const void *d_pix, int n, int channels, int64_t row_s
     if (!l0.ptr) {
         int c0 = 0, c1 = 0, c2 = 0;
         if (channels != 1) { /* Camera.RGB: 1 -> byte 0 weighs as R */
-            const bool rgb = c->calibrated ? c->cam.rgb != 0 : false;
+            /* rgb_flag: the frame's camera's own Camera.RGB (ss_extract), or -1: the calibration set last */
+            const bool rgb = rgb_flag >= 0 ? rgb_flag != 0 : c->calibrated ? c->cam.rgb != 0 : false;
             c0 = rgb ? SS_GRAY_RY : SS_GRAY_BY;
             c1 = SS_GRAY_GY;
             c2 = rgb ? SS_GRAY_BY : SS_GRAY_RY;
@@ -409,6 +436,52 @@ static int match_expanded(ss_ctx *c, const void *d_query_x, int n_query, const v
 
 extern "C" {
 
+/* the ss_track state of camera_id, or NULL when the camera has none yet */
+static cam_track *find_camera(ss_ctx *c, int camera_id)
+{
+    for (int i = 0; i < c->n_cams; i++)
+        if (c->cams[i].camera_id == camera_id) return &c->cams[i];
+    return nullptr;
+}
+
+/* the ss_track state of camera_id: its slot, or a new one while fewer than SS_MAX_CAMERAS ids have been seen */
+static int camera_slot(ss_ctx *c, int camera_id, cam_track **out)
+{
+    for (int i = 0; i < c->n_cams; i++)
+        if (c->cams[i].camera_id == camera_id) {
+            *out = &c->cams[i];
+            return SS_OK;
+        }
+    if (c->n_cams == SS_MAX_CAMERAS)
+        return fail(c, SS_ERR_INVALID_ARG, "camera " + std::to_string(camera_id) + ": this context tracks " + std::to_string(SS_MAX_CAMERAS) +
+                                               " cameras already (SS_MAX_CAMERAS)");
+    cam_track &ct = c->cams[c->n_cams++];
+    ct.camera_id = camera_id;
+    *out = &ct;
+    return SS_OK;
+}
+
+/* the previous frame's rows of a camera are still the caller's (SS_TRACK_DESC_STAYS_VALID): copy them into the camera's own
+ * buffers (and their operand form), so that the caller may reuse its rows once this has returned */
+static int detach_rows(ss_ctx *c, cam_track &ct)
+{
+    if (!ct.d_prev_ext) return SS_OK;
+    const int n = ct.prev_ext_n;
+    int rc = grow(c, ct.d_prev_desc, ct.d_prev_desc_bytes, (size_t)n * SS_DESC_BYTES);
+    if (rc != SS_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(ct.d_prev_desc, ct.d_prev_ext, (size_t)n * SS_DESC_BYTES, hipMemcpyDeviceToDevice, c->stream));
+    if (!c->no_desc_x) {
+        rc = grow(c, ct.d_prev_desc_x, ct.d_prev_desc_x_bytes, (size_t)SS_EXPANDED_BYTES(n));
+        if (rc != SS_OK) return rc;
+        ssk_expand_desc(c->stream, ct.d_prev_ext, n, ct.d_prev_desc_x);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    ct.d_prev_ext = nullptr;
+    ct.prev_ext_n = 0;
+    return SS_OK;
+}
+
 int ss_abi_version(void) { return SS_ABI_VERSION; }
 
 int ss_orb_params_default(ss_orb_params *p)
@@ -488,10 +561,16 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_part_tmp);
     dev_free(c->d_qx);
     dev_free(c->d_tx);
-    dev_free(c->d_ref_desc);
-    dev_free(c->d_prev_desc);
-    dev_free(c->d_ref_desc_x);
-    dev_free(c->d_prev_desc_x);
+    dev_free(c->d_train_src);
+    dev_free(c->d_carry_x);
+    if (c->h_train_src) (void)hipHostFree(c->h_train_src);
+    if (c->train_src_copied) (void)hipEventDestroy(c->train_src_copied);
+    for (cam_track &ct : c->cams) {
+        dev_free(ct.d_ref_desc);
+        dev_free(ct.d_prev_desc);
+        dev_free(ct.d_ref_desc_x);
+        dev_free(ct.d_prev_desc_x);
+    }
     (void)hipStreamDestroy(c->stream);
     delete c;
     return SS_OK;
@@ -504,15 +583,18 @@ int ss_set_calibration(ss_ctx *c, int camera_id, const ss_camera *cam)
     if (!c) return SS_ERR_INVALID_ARG;
     if (camera_id == 0) return fail(c, SS_ERR_INVALID_ARG, "Calibration message missing camera identifier.");
     if (!cam) return fail(c, SS_ERR_INVALID_ARG, "Calibration message missing structured parameter payload.");
+    cam_track *ct = nullptr;
+    const int rc = camera_slot(c, camera_id, &ct);
+    if (rc != SS_OK) return rc;
     c->cam = *cam;
     c->cam.type[sizeof(c->cam.type) - 1] = 0;
     c->cam_id = camera_id;
     c->calibrated = true;
     /* the reference rebuilds the whole ORB_SLAM3::System on every calibration message (:491-518): the map, the
-     * reference frame and the motion model do not survive it */
-    c->tracker.reset();
-    c->prev_serial = c->ref_serial = -1;
-    c->d_prev_ext = nullptr;
+     * reference frame and the motion model do not survive it -- of this camera; the others keep tracking */
+    ct->cam = c->cam;
+    ct->has_cam = true;
+    ct->reset();
     return SS_OK;
 }
 
@@ -536,7 +618,8 @@ int ss_extract(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int heig
     if (rc != SS_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_in, pix, bytes, hipMemcpyHostToDevice, c->stream));
     /* the caller keeps ownership of pix: it is consumed before we return */
-    rc = run_extract(c, c->d_in, 1, channels, row_stride, (int64_t)alloc);
+    const cam_track *own = find_camera(c, camera_id);
+    rc = run_extract(c, c->d_in, 1, channels, row_stride, (int64_t)alloc, own && own->has_cam ? (own->cam.rgb != 0) : -1);
     if (rc != SS_OK) return rc;
     int32_t nk = 0;
     HIP_TRY(c, hipMemcpyAsync(&nk, c->n_kp, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -735,6 +818,67 @@ int ss_match_batch_device(ss_ctx *c, int mode, int th, int ratio_num, int ratio_
     return SS_OK;
 }
 
+int ss_match_batch_sources_device(ss_ctx *c, const int32_t *train_src, const void *d_carry, const void *d_carry_n, int n_carry, int th,
+                                  int ratio_num, int ratio_den, void *d_idx, void *d_d1, void *d_d2)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->have_geom || c->last_n_frames <= 0) return fail(c, SS_ERR_STATE, "no batch has been extracted");
+    if (!train_src || !d_idx || !d_d1 || !d_d2 || ratio_den <= 0 || n_carry < 0 || (n_carry > 0 && (!d_carry || !d_carry_n)))
+        return fail(c, SS_ERR_INVALID_ARG, "bad match arguments");
+    const int n = c->last_n_frames, kcap = c->hg.kcap;
+    for (int b = 0; b < n; b++) {
+        const int t = train_src[b];
+        if (t >= n || t < -1 - n_carry)
+            return fail(c, SS_ERR_INVALID_ARG, "train_src[" + std::to_string(b) + "] = " + std::to_string(t) + " names no frame of the batch (" +
+                                                   std::to_string(n) + ") or of the carry (" + std::to_string(n_carry) + ")");
+    }
+    int rc = grow(c, c->d_train_src, c->d_train_src_bytes, (size_t)n * sizeof(int32_t));
+    if (rc != SS_OK) return rc;
+    /* the table travels through pinned memory, so the copy is asynchronous and the caller's array is free when this returns;
+     * the previous call's copy has left the staging buffer before it is rewritten */
+    if (c->train_src_copied) HIP_TRY(c, hipEventSynchronize(c->train_src_copied));
+    else HIP_TRY(c, hipEventCreateWithFlags(&c->train_src_copied, hipEventDisableTiming));
+    if (c->h_train_src_n < n) {
+        if (c->h_train_src) (void)hipHostFree(c->h_train_src);
+        c->h_train_src = nullptr;
+        c->h_train_src_n = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_train_src, (size_t)n * sizeof(int32_t), hipHostMallocDefault));
+        c->h_train_src_n = n;
+    }
+    memcpy(c->h_train_src, train_src, (size_t)n * sizeof(int32_t));
+    HIP_TRY(c, hipMemcpyAsync(c->d_train_src, c->h_train_src, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->train_src_copied, c->stream));
+    int chunk_len = 4;
+    int n_chunks = ssk_match_chunks(kcap, kcap, n, &chunk_len);
+    if (c->desc_x) n_chunks = ssk_match_x_batch_chunks(kcap, kcap, n, &chunk_len);
+    if (n_chunks > 1 || c->desc_x) {
+        rc = grow(c, c->match_partial, c->match_partial_bytes, (size_t)n * n_chunks * kcap * SSK_MATCH_PARTIAL_BYTES);
+        if (rc != SS_OK) return rc;
+    }
+    ssk_table tab{c->d_train_src, d_carry, nullptr, (const int32_t *)d_carry_n};
+    if (c->desc_x && n_carry > 0) { /* the carry as operand rows, at the batch's frame stride */
+        rc = grow(c, c->d_carry_x, c->d_carry_x_bytes, (size_t)n_carry * kcap * SSK_X_ROW);
+        if (rc != SS_OK) return rc;
+        stage_timer t(c, "expand", (int64_t)n_carry * kcap * (32 + SSK_X_ROW));
+        ssk_expand_desc_frames(c->stream, d_carry, kcap, n_carry, c->d_carry_x);
+        tab.carry_x = c->d_carry_x;
+    }
+    {
+        const int64_t nf = c->hg.n_features;
+        stage_timer t(c, "match", (int64_t)n * (nf * 32 * 2 + nf * 8));
+        if (c->desc_x)
+            ssk_match_x_table(c->stream, c->desc_x, c->desc_x, c->n_kp, c->n_kp, (int64_t)kcap * SSK_X_ROW, (int64_t)kcap * SSK_X_ROW, chunk_len,
+                              n_chunks, th, ratio_num, ratio_den, kcap, c->match_partial, (int32_t *)d_idx, (uint16_t *)d_d1, (uint16_t *)d_d2, n,
+                              c->desc, c->desc, (int64_t)kcap * SS_DESC_BYTES, (int64_t)kcap * SS_DESC_BYTES, tab);
+        else
+            ssk_match_table(c->stream, c->desc, c->desc, c->n_kp, c->n_kp, (int64_t)kcap * 8, (int64_t)kcap * 8, chunk_len, n_chunks, th, ratio_num,
+                            ratio_den, kcap, c->match_partial, (int32_t *)d_idx, (uint16_t *)d_d1, (uint16_t *)d_d2, n, tab);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
 int ss_match_pairs_device(ss_ctx *c, const void *d_query, const void *d_n_query, const void *d_train, const void *d_n_train,
                           int n_frames, int rows_per_frame, int th, int ratio_num, int ratio_den, void *d_idx, void *d_d1,
                           void *d_d2)
@@ -789,7 +933,7 @@ int ss_match_pairs_device(ss_ctx *c, const void *d_query, const void *d_n_query,
 
 /* the pose half of the frame branch: device match against the initial / previous frame's descriptors, then the host
  * geometry (csrc/ss_track.cpp).  d_desc: n rows of 32 bytes in device memory, written on c->stream or complete. */
-static int track_step(ss_ctx *c, int camera_id, double timestamp, const uint8_t *d_desc, const uint8_t *d_desc_x, const ss_keypoint *kps,
+static int track_step(ss_ctx *c, cam_track &ct, double timestamp, const uint8_t *d_desc, const uint8_t *d_desc_x, const ss_keypoint *kps,
                       int n, ss_pose *out, const int32_t *given_idx = nullptr, const uint16_t *given_d1 = nullptr, int flags = 0)
 {
     /* d_desc_x: the same n rows already expanded (the extraction's desc_x), or NULL: expanded here when the matrix-core matcher
@@ -798,7 +942,8 @@ static int track_step(ss_ctx *c, int camera_id, double timestamp, const uint8_t 
      * the caller's batch matcher; used when that frame is the one the tracker is about to match against, and then nothing
      * is enqueued on the device for this frame. */
     const bool use_x = !c->no_desc_x && n > 0;
-    const int64_t serial = ++c->track_serial;
+    const int camera_id = ct.camera_id;
+    const int64_t serial = ++ct.serial;
     auto expanded = [&]() -> int {
         if (!use_x || d_desc_x) return SS_OK;
         int rcx = grow(c, c->d_qx, c->d_qx_bytes, (size_t)SS_EXPANDED_BYTES(n));
@@ -808,8 +953,9 @@ static int track_step(ss_ctx *c, int camera_id, double timestamp, const uint8_t 
         d_desc_x = c->d_qx;
         return SS_OK;
     };
-    sst_tracker &tr = c->tracker;
-    tr.cam = sst_camera{c->cam.fx, c->cam.fy, c->cam.cx, c->cam.cy, c->cam.k1, c->cam.k2, c->cam.p1, c->cam.p2};
+    sst_tracker &tr = ct.tracker;
+    const ss_camera &cal = ct.has_cam ? ct.cam : c->cam; /* a camera never calibrated: the calibration set last */
+    tr.cam = sst_camera{cal.fx, cal.fy, cal.cx, cal.cy, cal.k1, cal.k2, cal.p1, cal.p2};
     tr.scale_factor = c->params.scale_factor;
     c->h_xy.resize((size_t)2 * std::max(n, 1));
     c->h_oct.resize((size_t)std::max(n, 1));
@@ -826,15 +972,15 @@ static int track_step(ss_ctx *c, int camera_id, double timestamp, const uint8_t 
     const int32_t *m_idx = c->h_midx.data();
     const uint16_t *m_d1 = c->h_md1.data();
     if (want != SST_MATCH_NONE && n > 0) {
-        const int64_t train_serial = want == SST_MATCH_REF ? c->ref_serial : c->prev_serial;
+        const int64_t train_serial = want == SST_MATCH_REF ? ct.ref_serial : ct.prev_serial;
         if (given_idx && given_d1 && train_serial == serial - 1 && tr.n_train() > 0) {
             m_idx = given_idx;
             m_d1 = given_d1;
         } else {
             /* the previous frame's descriptors may still be the caller's (SS_TRACK_DESC_STAYS_VALID): packed rows only */
-            const bool prev_ext = want == SST_MATCH_PREV && c->d_prev_ext != nullptr;
-            const uint8_t *train = want == SST_MATCH_REF ? c->d_ref_desc : prev_ext ? c->d_prev_ext : c->d_prev_desc;
-            const uint8_t *train_x = want == SST_MATCH_REF ? c->d_ref_desc_x : prev_ext ? nullptr : c->d_prev_desc_x;
+            const bool prev_ext = want == SST_MATCH_PREV && ct.d_prev_ext != nullptr;
+            const uint8_t *train = want == SST_MATCH_REF ? ct.d_ref_desc : prev_ext ? ct.d_prev_ext : ct.d_prev_desc;
+            const uint8_t *train_x = want == SST_MATCH_REF ? ct.d_ref_desc_x : prev_ext ? nullptr : ct.d_prev_desc_x;
             rc = grow(c, c->d_mout, c->d_mout_bytes, (size_t)n * 8);
             if (rc != SS_OK) return rc;
             int32_t *di = (int32_t *)c->d_mout;
@@ -868,25 +1014,30 @@ static int track_step(ss_ctx *c, int camera_id, double timestamp, const uint8_t 
             c->n_tracked++;
         }
     } tguard{c, tm0, tg0, tk0};
+    /* the caller's rows of the previous frame are never read after this call: a frame kept as the previous one replaces
+     * them, and every other outcome leaves the tracker without a previous frame to match against (it matches only in
+     * state OK, which is entered through a frame kept as the previous one) */
+    ct.d_prev_ext = nullptr;
+    ct.prev_ext_n = 0;
     if (keep == SST_KEEP_AS_PREV) {
-        c->prev_serial = serial;
-        c->d_prev_ext = nullptr;
+        ct.prev_serial = serial;
     } else if (keep == SST_KEEP_AS_REF) {
-        c->ref_serial = serial;
+        ct.ref_serial = serial;
     }
     if (keep == SST_KEEP_AS_PREV && n > 0 && (flags & SS_TRACK_DESC_STAYS_VALID)) {
-        c->d_prev_ext = d_desc; /* the caller keeps the rows alive until the next call has returned: nothing to copy */
+        ct.d_prev_ext = d_desc; /* the caller keeps the rows alive until the next call has returned: nothing to copy */
+        ct.prev_ext_n = n;
     } else if (keep != SST_KEEP_NONE && n > 0) {
-        uint8_t *&dst = keep == SST_KEEP_AS_REF ? c->d_ref_desc : c->d_prev_desc;
-        size_t &dst_bytes = keep == SST_KEEP_AS_REF ? c->d_ref_desc_bytes : c->d_prev_desc_bytes;
+        uint8_t *&dst = keep == SST_KEEP_AS_REF ? ct.d_ref_desc : ct.d_prev_desc;
+        size_t &dst_bytes = keep == SST_KEEP_AS_REF ? ct.d_ref_desc_bytes : ct.d_prev_desc_bytes;
         rc = grow(c, dst, dst_bytes, (size_t)n * SS_DESC_BYTES);
         if (rc != SS_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(dst, d_desc, (size_t)n * SS_DESC_BYTES, hipMemcpyDeviceToDevice, c->stream));
         if (use_x) {
             rc = expanded();
             if (rc != SS_OK) return rc;
-            uint8_t *&dst_x = keep == SST_KEEP_AS_REF ? c->d_ref_desc_x : c->d_prev_desc_x;
-            size_t &dst_x_bytes = keep == SST_KEEP_AS_REF ? c->d_ref_desc_x_bytes : c->d_prev_desc_x_bytes;
+            uint8_t *&dst_x = keep == SST_KEEP_AS_REF ? ct.d_ref_desc_x : ct.d_prev_desc_x;
+            size_t &dst_x_bytes = keep == SST_KEEP_AS_REF ? ct.d_ref_desc_x_bytes : ct.d_prev_desc_x_bytes;
             rc = grow(c, dst_x, dst_x_bytes, (size_t)SS_EXPANDED_BYTES(n));
             if (rc != SS_OK) return rc;
             HIP_TRY(c, hipMemcpyAsync(dst_x, d_desc_x, (size_t)SS_EXPANDED_BYTES(n), hipMemcpyDeviceToDevice, c->stream));
@@ -905,40 +1056,101 @@ static int track_step(ss_ctx *c, int camera_id, double timestamp, const uint8_t 
     return SS_OK;
 }
 
+static int track_impl(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int height, int channels, int row_stride, double timestamp,
+                      ss_pose *out);
+static int track_features_impl(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
+                               int n_keypoints, ss_pose *out);
+static int track_features_matched_impl(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
+                                       int n_keypoints, const int32_t *match_idx, const uint16_t *match_d1, int flags, ss_pose *out);
+
+/* SS_TRACK_DESC_STAYS_VALID: the rows a camera refers to are valid until the next pose-step call on the context has
+ * returned, whatever its outcome.  Every pose-step entry point therefore copies the rows of the other cameras first, and
+ * those of its own camera when it fails (a call that reaches the tracker drops or replaces them, track_step). */
+extern "C++" template <typename F> static int pose_call(ss_ctx *c, int camera_id, F &&body)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    for (int i = 0; i < c->n_cams; i++)
+        if (c->cams[i].camera_id != camera_id) {
+            const int rcd = detach_rows(c, c->cams[i]);
+            if (rcd != SS_OK) return rcd;
+        }
+    const int rc = body();
+    if (rc != SS_OK)
+        if (cam_track *own = find_camera(c, camera_id)) {
+            const std::string why = c->err; /* the call's own error is what the caller sees */
+            (void)detach_rows(c, *own);
+            c->err = why;
+        }
+    return rc;
+}
+
 int ss_track(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int height, int channels, int row_stride,
              double timestamp, ss_pose *out)
 {
-    if (!c || !out) return SS_ERR_INVALID_ARG;
-    if (!c->calibrated) return fail(c, SS_ERR_NOT_CALIBRATED, "Received frame before calibration. Ignoring.");
-    ss_frame_result res;
-    int rc = ss_extract(c, camera_id, pix, width, height, channels, row_stride, timestamp, &res);
-    if (rc != SS_OK) return rc;
-    /* this frame's descriptors are still in HBM (frame 0 of the batch arrays) */
-    return track_step(c, camera_id, timestamp, c->desc, c->desc_x, res.keypoints, res.n_keypoints, out);
+    return pose_call(c, camera_id, [&]() { return track_impl(c, camera_id, pix, width, height, channels, row_stride, timestamp, out); });
 }
 
 int ss_track_features(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
                       int n_keypoints, ss_pose *out)
 {
-    if (!c || !out || n_keypoints < 0) return SS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    if (!c->calibrated) return fail(c, SS_ERR_NOT_CALIBRATED, "Received frame before calibration. Ignoring.");
-    if (camera_id == 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing camera identifier.");
-    if (n_keypoints > 0 && (!d_descriptors || !keypoints)) return fail(c, SS_ERR_INVALID_ARG, "ss_track_features: NULL feature arrays");
-    return track_step(c, camera_id, timestamp, (const uint8_t *)d_descriptors, nullptr, keypoints, n_keypoints, out);
+    return pose_call(c, camera_id, [&]() { return track_features_impl(c, camera_id, timestamp, d_descriptors, keypoints, n_keypoints, out); });
 }
 
 int ss_track_features_matched(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
                               int n_keypoints, const int32_t *match_idx, const uint16_t *match_d1, int flags, ss_pose *out)
 {
-    if (!c || !out || n_keypoints < 0) return SS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
+    return pose_call(c, camera_id, [&]() {
+        return track_features_matched_impl(c, camera_id, timestamp, d_descriptors, keypoints, n_keypoints, match_idx, match_d1, flags, out);
+    });
+}
+static int track_impl(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int height, int channels, int row_stride, double timestamp,
+                      ss_pose *out)
+{
+    if (!out) return SS_ERR_INVALID_ARG;
+    if (!c->calibrated) return fail(c, SS_ERR_NOT_CALIBRATED, "Received frame before calibration. Ignoring.");
+    /* a new camera is refused before any work when the context has no slot left, and gets its slot only once its frame has
+     * been extracted (a frame that fails does not take one) */
+    if (camera_id != 0 && !find_camera(c, camera_id) && c->n_cams == SS_MAX_CAMERAS) {
+        cam_track *none = nullptr;
+        return camera_slot(c, camera_id, &none);
+    }
+    ss_frame_result res;
+    int rc = ss_extract(c, camera_id, pix, width, height, channels, row_stride, timestamp, &res);
+    if (rc != SS_OK) return rc;
+    cam_track *ct = nullptr;
+    rc = camera_slot(c, camera_id, &ct);
+    if (rc != SS_OK) return rc;
+    /* this frame's descriptors are still in HBM (frame 0 of the batch arrays) */
+    return track_step(c, *ct, timestamp, c->desc, c->desc_x, res.keypoints, res.n_keypoints, out);
+}
+
+static int track_features_impl(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
+                               int n_keypoints, ss_pose *out)
+{
+    if (!out || n_keypoints < 0) return SS_ERR_INVALID_ARG;
+    if (!c->calibrated) return fail(c, SS_ERR_NOT_CALIBRATED, "Received frame before calibration. Ignoring.");
+    if (camera_id == 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing camera identifier.");
+    if (n_keypoints > 0 && (!d_descriptors || !keypoints)) return fail(c, SS_ERR_INVALID_ARG, "ss_track_features: NULL feature arrays");
+    cam_track *ct = nullptr;
+    const int rc = camera_slot(c, camera_id, &ct);
+    if (rc != SS_OK) return rc;
+    return track_step(c, *ct, timestamp, (const uint8_t *)d_descriptors, nullptr, keypoints, n_keypoints, out);
+}
+
+static int track_features_matched_impl(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
+                                       int n_keypoints, const int32_t *match_idx, const uint16_t *match_d1, int flags, ss_pose *out)
+{
+    if (!out || n_keypoints < 0) return SS_ERR_INVALID_ARG;
     if (!c->calibrated) return fail(c, SS_ERR_NOT_CALIBRATED, "Received frame before calibration. Ignoring.");
     if (camera_id == 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing camera identifier.");
     if (n_keypoints > 0 && (!d_descriptors || !keypoints)) return fail(c, SS_ERR_INVALID_ARG, "ss_track_features_matched: NULL feature arrays");
     if ((match_idx == nullptr) != (match_d1 == nullptr)) return fail(c, SS_ERR_INVALID_ARG, "ss_track_features_matched: match_idx and match_d1 go together");
     if (flags & ~SS_TRACK_DESC_STAYS_VALID) return fail(c, SS_ERR_INVALID_ARG, "ss_track_features_matched: unknown flag");
-    return track_step(c, camera_id, timestamp, (const uint8_t *)d_descriptors, nullptr, keypoints, n_keypoints, out, match_idx, match_d1, flags);
+    cam_track *ct = nullptr;
+    const int rc = camera_slot(c, camera_id, &ct);
+    if (rc != SS_OK) return rc;
+    return track_step(c, *ct, timestamp, (const uint8_t *)d_descriptors, nullptr, keypoints, n_keypoints, out, match_idx, match_d1, flags);
 }
 
 int ss_expand_descriptors_device(ss_ctx *c, const void *d_packed, int n, void *d_expanded)
@@ -1100,9 +1312,35 @@ int ss_wait_stream(ss_ctx *c, void *hip_stream)
 int ss_track_reset(ss_ctx *c)
 {
     if (!c) return SS_ERR_INVALID_ARG;
-    c->tracker.reset();
-    c->prev_serial = c->ref_serial = -1;
-    c->d_prev_ext = nullptr;
+    /* every camera back to NO_IMAGES_YET; a camera without a calibration of its own gives its slot back */
+    int kept = 0;
+    for (int i = 0; i < c->n_cams; i++) {
+        c->cams[i].reset();
+        if (c->cams[i].has_cam) {
+            if (kept != i) std::swap(c->cams[kept], c->cams[i]);
+            kept++;
+        }
+    }
+    for (int i = kept; i < c->n_cams; i++) {
+        cam_track &ct = c->cams[i];
+        dev_free(ct.d_ref_desc);
+        dev_free(ct.d_prev_desc);
+        dev_free(ct.d_ref_desc_x);
+        dev_free(ct.d_prev_desc_x);
+        ct = cam_track();
+    }
+    c->n_cams = kept;
+    return SS_OK;
+}
+
+int ss_track_detach(ss_ctx *c)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    for (int i = 0; i < c->n_cams; i++) {
+        const int rc = detach_rows(c, c->cams[i]);
+        if (rc != SS_OK) return rc;
+    }
     return SS_OK;
 }
 

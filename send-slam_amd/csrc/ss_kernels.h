@@ -70,6 +70,27 @@ void ssk_match_x(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, 
                  int64_t qp_frame_stride = 0, int64_t tp_frame_stride = 0);
 /* (query_p / train_p: the same rows as packed 32-byte descriptors where the caller has them, frame strides in bytes: the second
  * launch, which recomputes 15 distances per query, then reads a quarter of the bytes) */
+/* Table form of the two batch matchers above (ss_match_batch_sources_device): query frame b is matched against src[b] (device
+ * int32 [n_frames]) instead of b + shift.  src[b] >= 0: frame src[b] of the batch, the self pair excluded iff src[b] == b;
+ * -1: no train (idx -1, d1 / d2 0xFFFF); <= -2: carry frame -2 - src[b], with carry_n[c] rows, at the train's frame stride
+ * (carry_p packed 32-byte rows; carry_x expanded rows, needed by ssk_match_x_table only).  Always the compact kernel forms. */
+struct ssk_table {
+    const int32_t *src;
+    const void *carry_p, *carry_x;
+    const int32_t *carry_n;
+};
+void ssk_match_table(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr,
+                     int64_t q_frame_stride_words, int64_t t_frame_stride_words, int chunk_len, int n_chunks, int th, int rnum, int rden,
+                     int out_stride, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames, const ssk_table &tab);
+void ssk_match_x_table(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
+                       int64_t q_frame_stride, int64_t t_frame_stride, int chunk_len, int n_chunks, int th, int rnum, int rden, int out_stride,
+                       void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p,
+                       int64_t qp_frame_stride, int64_t tp_frame_stride, const ssk_table &tab);
+/* pipe match_mode 2: carry frame dst[i] <- batch frame src[i] (packed rows [kcap][32], row count clamped to kcap), i < n <=
+ * SSK_CARRY_MAX, one launch */
+#define SSK_CARRY_MAX 8
+void ssk_carry_gather(hipStream_t s, const void *desc, const int32_t *n_kp, int kcap, const int32_t *dst, const int32_t *src, int n, void *carry,
+                      int32_t *carry_n);
 /* packed 32-B descriptors -> expanded SSK_X_ROW-byte rows; `out` holds n rounded up to 32 rows */
 void ssk_expand_desc(hipStream_t s, const void *packed, int n, void *out);
 /* [n_frames][rows][32] packed -> [n_frames][rows rounded up to 32][SSK_X_ROW] */

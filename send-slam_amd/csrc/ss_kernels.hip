@@ -2151,24 +2151,56 @@ __device__ __forceinline__ void merge_partial(int &d1, int &j1, int &d2, int e1,
     }
 }
 
+/* Table form of the batch matchers (TABLE = true): the train frame of query frame b is src[b] instead of b + shift.
+ * t >= 0: frame t of the batch (self pair excluded, in exclude mode 2, iff t == b); t == -1: no train (nt = 0: idx -1,
+ * d1 / d2 0xFFFF); t <= -2: carry frame -2 - t, read from `carry` at the train's frame stride with carry_n rows.  Every value
+ * is read per block (frame is uniform): scalar loads.  The forms without the table compile as before. */
+struct mt_table {
+    const int32_t *src;     /* device [n_frames] */
+    const uint8_t *carry;   /* carry frames in the row format this launch reads (packed or expanded) */
+    const uint8_t *carry_p; /* the same frames as packed 32-byte rows (the fused epilogue of k_match_mfma_x) */
+    const int32_t *carry_n; /* device [n_carry] row counts */
+};
+
+/* the table argument of a kernel: a trailing parameter pack that is empty in the forms without the table, so that their
+ * parameter lists (and with them the offsets of the hidden arguments) are those of the kernels before the table form */
+__device__ __forceinline__ mt_table mt_of() { return mt_table{}; }
+__device__ __forceinline__ mt_table mt_of(const mt_table &t) { return t; }
+
+/* the table value of query frame `frame`, the frame index inside the base it names, and that frame's row count */
+__device__ __forceinline__ int mt_src(const mt_table &tab, int frame) { return tab.src[frame]; }
+__device__ __forceinline__ int mt_slot(int t) { return t >= 0 ? t : (t <= -2 ? -2 - t : 0); }
+__device__ __forceinline__ int mt_count(const mt_table &tab, int t, int tframe, const int32_t *nt_arr, int nt_fixed)
+{
+    if (t < 0) return t == -1 ? 0 : tab.carry_n[tframe];
+    return nt_arr ? nt_arr[tframe] : nt_fixed;
+}
+/* Each kernel resolves its train frame with `TABLE ? table rule : shift rule` on a constant condition, which the compiler
+ * reduces to one arm before any optimisation: the forms without the table are the statements they were before. */
+
+template <typename... TAB>
 __global__ __launch_bounds__(256) void k_match(const uint32_t *__restrict__ query, const uint32_t *__restrict__ train,
                                                const int32_t *__restrict__ nq_arr, const int32_t *__restrict__ nt_arr,
                                                int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride,
                                                int train_frame_shift, int chunk_len, int n_chunks, int exclude_self_mode,
                                                int th, int rnum, int rden, int out_stride,
                                                match_partial *__restrict__ partial, int32_t *__restrict__ idx_out,
-                                               uint16_t *__restrict__ d1_out, uint16_t *__restrict__ d2_out)
+                                               uint16_t *__restrict__ d1_out, uint16_t *__restrict__ d2_out, TAB... tab_arg)
 {
+    constexpr bool TABLE = sizeof...(TAB) > 0;
+    const mt_table tab = mt_of(tab_arg...);
     __shared__ int s_d1[4][64], s_j1[4][64], s_d2[4][64];
     const int frame = blockIdx.z, chunk = blockIdx.y;
-    /* batch mode: train = frame + shift (clamped to 0); exclude j == i when train == query frame */
-    int tframe = frame + train_frame_shift;
+    /* exclude j == i when train == query frame */
+    const int tsel = TABLE ? mt_src(tab, frame) : 0; /* table value */
+    int tframe = TABLE ? mt_slot(tsel) : frame + train_frame_shift;
     if (tframe < 0) tframe = 0;
     const int nq = nq_arr ? nq_arr[frame] : nq_fixed;
-    const int nt = nt_arr ? nt_arr[tframe] : nt_fixed;
-    const bool excl = exclude_self_mode == 1 || (exclude_self_mode == 2 && tframe == frame);
+    const int nt = TABLE ? mt_count(tab, tsel, tframe, nt_arr, nt_fixed) : nt_arr ? nt_arr[tframe] : nt_fixed;
+    const bool excl = exclude_self_mode == 1 || (exclude_self_mode == 2 && (TABLE ? tsel : tframe) == frame);
+    const bool from_carry = TABLE ? tsel <= -2 : false;
     const uint32_t *qf = query + (size_t)frame * q_frame_stride;
-    const uint32_t *tf = train + (size_t)tframe * t_frame_stride;
+    const uint32_t *tf = (from_carry ? (const uint32_t *)tab.carry : train) + (size_t)tframe * t_frame_stride;
     const int lane = lane_id();
     const int wave = rfl((int)(threadIdx.x >> 6));
     const int qi = blockIdx.x * 64 + lane;
@@ -2285,25 +2317,29 @@ __device__ __forceinline__ void mm_select(const v16i &acc, uint32_t kb0, uint32_
     }
 }
 
-template <int NU>
+template <int NU, typename... TAB>
 __global__ __launch_bounds__(64 * MM_WAVES, NU == 2 ? 2 : 4) void k_match_mfma(const uint32_t *__restrict__ query, const uint32_t *__restrict__ train,
                                                     const int32_t *__restrict__ nq_arr, const int32_t *__restrict__ nt_arr,
                                                     int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride,
                                                     int train_frame_shift, int chunk_len, int n_chunks, int exclude_self_mode,
                                                     int th, int rnum, int rden, int out_stride,
                                                     match_partial *__restrict__ partial, int32_t *__restrict__ idx_out,
-                                                    uint16_t *__restrict__ d1_out, uint16_t *__restrict__ d2_out)
+                                                    uint16_t *__restrict__ d1_out, uint16_t *__restrict__ d2_out, TAB... tab_arg)
 {
+    constexpr bool TABLE = sizeof...(TAB) > 0;
+    const mt_table tab = mt_of(tab_arg...);
     __shared__ uint2 lut[256];
     __shared__ __attribute__((aligned(16))) uint8_t tiles[2][MM_TILE * MM_ROW_BYTES];
     const int frame = blockIdx.z, chunk = blockIdx.y;
-    int tframe = frame + train_frame_shift;
+    const int tsel = TABLE ? mt_src(tab, frame) : 0; /* table value */
+    int tframe = TABLE ? mt_slot(tsel) : frame + train_frame_shift;
     if (tframe < 0) tframe = 0;
     const int nq = nq_arr ? nq_arr[frame] : nq_fixed;
-    const int nt = nt_arr ? nt_arr[tframe] : nt_fixed;
-    const bool excl = exclude_self_mode == 1 || (exclude_self_mode == 2 && tframe == frame);
+    const int nt = TABLE ? mt_count(tab, tsel, tframe, nt_arr, nt_fixed) : nt_arr ? nt_arr[tframe] : nt_fixed;
+    const bool excl = exclude_self_mode == 1 || (exclude_self_mode == 2 && (TABLE ? tsel : tframe) == frame);
+    const bool from_carry = TABLE ? tsel <= -2 : false;
     const uint32_t *qf = query + (size_t)frame * q_frame_stride;
-    const uint32_t *tf = train + (size_t)tframe * t_frame_stride;
+    const uint32_t *tf = (from_carry ? (const uint32_t *)tab.carry : train) + (size_t)tframe * t_frame_stride;
     const int lane = lane_id(), col = lane & 31, half = lane >> 5;
     const int wave = rfl((int)(threadIdx.x >> 6));
     const int qbase = blockIdx.x * MM_QBLOCK(NU) + wave * (32 * NU); /* this wave's queries: NU 32-column B tiles */
@@ -2580,13 +2616,15 @@ struct mx_finish {
     uint16_t *d1_out, *d2_out;
 };
 
-template <bool FUSED, int MX_QT, bool PIPE> /* FUSED: one chunk covers the train set, the kernel finishes its queries itself */
+template <bool FUSED, int MX_QT, bool PIPE, typename... TAB> /* FUSED: one chunk covers the train set, the kernel finishes its queries itself */
 __global__ __launch_bounds__(256, PIPE ? 2 : 5) void k_match_mfma_x(const uint8_t *__restrict__ query_x, const uint8_t *__restrict__ train_x,
                                                        const int32_t *__restrict__ nq_arr, const int32_t *__restrict__ nt_arr,
                                                        int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride,
                                                        int train_frame_shift, int chunk_len, int n_chunks, int exclude_self_mode,
-                                                       int out_stride, match_partial *__restrict__ partial, mx_finish fin)
+                                                       int out_stride, match_partial *__restrict__ partial, mx_finish fin, TAB... tab_arg)
 {
+    constexpr bool TABLE = sizeof...(TAB) > 0;
+    const mt_table tab = mt_of(tab_arg...);
     constexpr int MX_NBUF = MX_NBUF_OF(PIPE), MX_QBLOCK = MX_QBLOCK_OF(MX_QT);
     __shared__ __attribute__((aligned(16))) uint8_t tiles[MX_NBUF][MX_BUF];
     /* 1-D grid, XCD-aware: every XCD gets a contiguous run of (frame, chunk, query block) triples, so the blocks that
@@ -2595,13 +2633,15 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 5) void k_match_mfma_x(const uint8_
     const int n_qblocks = (out_stride + MX_QBLOCK - 1) / MX_QBLOCK;
     const int logical = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int qblock = logical % n_qblocks, chunk = (logical / n_qblocks) % n_chunks, frame = logical / (n_qblocks * n_chunks);
-    int tframe = frame + train_frame_shift;
+    const int tsel = TABLE ? mt_src(tab, frame) : 0; /* table value */
+    int tframe = TABLE ? mt_slot(tsel) : frame + train_frame_shift;
     if (tframe < 0) tframe = 0;
     const int nq = nq_arr ? nq_arr[frame] : nq_fixed;
-    const int nt = nt_arr ? nt_arr[tframe] : nt_fixed;
-    const bool excl = exclude_self_mode == 1 || (exclude_self_mode == 2 && tframe == frame);
+    const int nt = TABLE ? mt_count(tab, tsel, tframe, nt_arr, nt_fixed) : nt_arr ? nt_arr[tframe] : nt_fixed;
+    const bool excl = exclude_self_mode == 1 || (exclude_self_mode == 2 && (TABLE ? tsel : tframe) == frame);
+    const bool from_carry = TABLE ? tsel <= -2 : false;
     const uint8_t *qf = query_x + (size_t)frame * q_frame_stride; /* strides in bytes: rows of SS_X_ROW */
-    const uint8_t *tf = train_x + (size_t)tframe * t_frame_stride;
+    const uint8_t *tf = (from_carry ? tab.carry : train_x) + (size_t)tframe * t_frame_stride;
     const int lane = lane_id(), col = lane & 31, half = lane >> 5;
     const int wave = rfl((int)(threadIdx.x >> 6));
     const int qbase = qblock * MX_QBLOCK + wave * (32 * MX_QT); /* this wave's 64 queries: two B tiles */
@@ -2859,7 +2899,7 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 5) void k_match_mfma_x(const uint8_
      * query row, and the minimum over the group's other rows completes the second best.  Lane 8 s writes the query's outputs. */
     const int g = lane & 7, slot = lane >> 3;
     const uint8_t *qp = fin.query_p + (size_t)frame * fin.qp_frame_stride;
-    const uint8_t *tp = fin.train_p + (size_t)tframe * fin.tp_frame_stride;
+    const uint8_t *tp = (from_carry ? tab.carry_p : fin.train_p) + (size_t)tframe * fin.tp_frame_stride;
     /* a round of four passes per query tile: the loads of a round are issued together (one memory round trip per round, not per pass) */
 #pragma unroll
     for (int round = 0; round < MX_QT; round++) {
@@ -2917,22 +2957,26 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 5) void k_match_mfma_x(const uint8_
  * Four lanes per query, lane g < MX_RUNS with run g of the group (4 ROWB contiguous bytes).  The rows are read
  * as packed descriptors where the caller has them (32 bytes: a quarter of the traffic), else as the matcher's operand rows:
  * 128 bytes of FP4 +1 (0x2) / -1 (0xA) nibbles, two rows differ in a bit where the nibbles' sign bits differ. */
-template <int ROWB>
+template <int ROWB, typename... TAB>
 __global__ __launch_bounds__(256) void k_match_finish_x(const uint8_t *__restrict__ query_x, const uint8_t *__restrict__ train_x,
                                                         const int32_t *__restrict__ nq_arr, const int32_t *__restrict__ nt_arr, int nq_fixed,
                                                         int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift,
                                                         int exclude_self_mode, const match_partial *__restrict__ partial, int n_chunks, int th,
                                                         int rnum, int rden, int out_stride, int32_t *__restrict__ idx_out,
-                                                        uint16_t *__restrict__ d1_out, uint16_t *__restrict__ d2_out)
+                                                        uint16_t *__restrict__ d1_out, uint16_t *__restrict__ d2_out, TAB... tab_arg)
 {
+    constexpr bool TABLE = sizeof...(TAB) > 0;
+    const mt_table tab = mt_of(tab_arg...);
     const int frame = blockIdx.y, g = threadIdx.x & 3;
     const int qi = blockIdx.x * 64 + (threadIdx.x >> 2);
     if (qi >= out_stride) return; /* a whole quad leaves together */
-    int tframe = frame + train_frame_shift;
+    const int tsel = TABLE ? mt_src(tab, frame) : 0; /* table value */
+    int tframe = TABLE ? mt_slot(tsel) : frame + train_frame_shift;
     if (tframe < 0) tframe = 0;
     const int nq = nq_arr ? nq_arr[frame] : nq_fixed;
-    const int nt = nt_arr ? nt_arr[tframe] : nt_fixed;
-    const bool excl = exclude_self_mode == 1 || (exclude_self_mode == 2 && tframe == frame);
+    const int nt = TABLE ? mt_count(tab, tsel, tframe, nt_arr, nt_fixed) : nt_arr ? nt_arr[tframe] : nt_fixed;
+    const bool excl = exclude_self_mode == 1 || (exclude_self_mode == 2 && (TABLE ? tsel : tframe) == frame);
+    const bool from_carry = TABLE ? tsel <= -2 : false;
     const size_t o = (size_t)frame * out_stride + qi;
     int d1 = 0xFFFF, d2 = 0xFFFF, j1 = -1;
     if (n_chunks == 0) {
@@ -2950,7 +2994,7 @@ __global__ __launch_bounds__(256) void k_match_finish_x(const uint8_t *__restric
     if (qvalid && j1 >= 0) {
         const int base = mx_group_base(j1) + 8 * g; /* rows base .. base + 3: this lane's run (lanes g >= MX_RUNS have none) */
         const uint4 *q = (const uint4 *)(query_x + (size_t)frame * q_frame_stride + (size_t)qi * ROWB);
-        const uint4 *t = (const uint4 *)(train_x + (size_t)tframe * t_frame_stride + (size_t)base * ROWB);
+        const uint4 *t = (const uint4 *)((from_carry ? tab.carry : train_x) + (size_t)tframe * t_frame_stride + (size_t)base * ROWB);
         const uint32_t mask = ROWB == SS_X_ROW ? 0x88888888u : 0xFFFFFFFFu;
         uint4 qa[ROWB / 16];
 #pragma unroll
@@ -3020,6 +3064,23 @@ __global__ __launch_bounds__(256) void k_expand_desc(const uint32_t *__restrict_
         v = fp4_of_4bits((w >> (4 * (lane & 7))) & 15u);
     }
     *(uint16_t *)(out + (size_t)row * SS_X_ROW + 2 * lane) = (uint16_t)v;
+}
+
+/* pipe match_mode 2: the last frame of each camera of a batch -> the pipe's carry, one launch.  Block row y copies pair y:
+ * the packed rows of batch frame src[y] ([kcap][32] bytes) to carry frame dst[y], and its row count, clamped to kcap (a frame
+ * the kernels flagged may report more). */
+static_assert(SSK_CARRY_MAX == SS_MAX_CAMERAS, "one carry gather moves a frame of every camera the pipe's carry holds");
+struct carry_pairs {
+    int32_t dst[SSK_CARRY_MAX], src[SSK_CARRY_MAX];
+};
+__global__ __launch_bounds__(256) void k_carry_gather(const uint4 *__restrict__ desc, const int32_t *__restrict__ n_kp, int kcap, carry_pairs pr,
+                                                      uint4 *__restrict__ carry, int32_t *__restrict__ carry_n)
+{
+    const int y = blockIdx.y, units = kcap * (SS_DESC_BYTES / 16);
+    const uint4 *from = desc + (size_t)pr.src[y] * units;
+    uint4 *to = carry + (size_t)pr.dst[y] * units;
+    for (int u = (int)(blockIdx.x * 256 + threadIdx.x); u < units; u += (int)(gridDim.x * 256)) to[u] = from[u];
+    if (blockIdx.x == 0 && threadIdx.x == 0) carry_n[pr.dst[y]] = imin(imax(n_kp[pr.src[y]], 0), kcap);
 }
 
 /* raw local match of a database shard -> the 8-byte records ranks exchange (include/sendslam_orb.h ss_match_part) */
@@ -3343,33 +3404,45 @@ static bool mx_pipelined(int n_frames, int rows_t)
     return n_frames == 1 && rows_t >= 65536;
 }
 
-template <bool FUSED, int QT, bool PIPE>
+template <bool FUSED, int QT, bool PIPE, bool TABLE>
 static void mx_launch(hipStream_t s, dim3 grid, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr, int nq_fixed,
                       int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift, int chunk_len, int n_chunks,
-                      int exclude_self_mode, int out_stride, void *partial, const mx_finish &fin)
+                      int exclude_self_mode, int out_stride, void *partial, const mx_finish &fin, const mt_table &tab)
 {
-    hipLaunchKernelGGL((k_match_mfma_x<FUSED, QT, PIPE>), grid, dim3(256), 0, s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride,
-                       t_frame_stride, train_frame_shift, chunk_len, n_chunks, exclude_self_mode, out_stride, (match_partial *)partial, fin);
+    if constexpr (TABLE)
+        hipLaunchKernelGGL((k_match_mfma_x<FUSED, QT, PIPE, mt_table>), grid, dim3(256), 0, s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed,
+                           q_frame_stride, t_frame_stride, train_frame_shift, chunk_len, n_chunks, exclude_self_mode, out_stride,
+                           (match_partial *)partial, fin, tab);
+    else
+        hipLaunchKernelGGL((k_match_mfma_x<FUSED, QT, PIPE>), grid, dim3(256), 0, s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed,
+                           q_frame_stride, t_frame_stride, train_frame_shift, chunk_len, n_chunks, exclude_self_mode, out_stride,
+                           (match_partial *)partial, fin);
 }
 
-/* the matcher's first launch (or only one, when fused); returns true when the outputs are final */
+/* the matcher's first launch (or only one, when fused); returns true when the outputs are final.  The table form has the
+ * compact kernel only (pipelined is ignored). */
+template <bool TABLE = false>
 static bool mx_match(hipStream_t s, bool pipelined, int n_frames, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr,
                      const int32_t *nt_arr, int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift,
-                     int chunk_len, int n_chunks, int exclude_self_mode, int out_stride, void *partial, const mx_finish &fin)
+                     int chunk_len, int n_chunks, int exclude_self_mode, int out_stride, void *partial, const mx_finish &fin,
+                     const mt_table &tab = mt_table{})
 {
+    if (TABLE) pipelined = false;
     const int qblock = pipelined ? MX_QBLOCK_OF(2) : MX_QBLOCK_OF(1);
     dim3 grid(((out_stride + qblock - 1) / qblock) * n_chunks * n_frames);
     const bool fused = n_chunks == 1 && fin.query_p && fin.train_p; /* one launch: the kernel finishes its queries itself */
 #define MX_GO(F, Q, P)                                                                                                                      \
-    mx_launch<F, Q, P>(s, grid, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride, t_frame_stride, train_frame_shift, chunk_len, \
-                       n_chunks, exclude_self_mode, out_stride, partial, fin)
-    if (pipelined) {
-        if (fused) MX_GO(true, 2, true);
-        else MX_GO(false, 2, true);
-    } else {
-        if (fused) MX_GO(true, 1, false);
-        else MX_GO(false, 1, false);
+    mx_launch<F, Q, P, TABLE>(s, grid, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride, t_frame_stride, train_frame_shift, \
+                              chunk_len, n_chunks, exclude_self_mode, out_stride, partial, fin, tab)
+    if constexpr (!TABLE) {
+        if (pipelined) {
+            if (fused) MX_GO(true, 2, true);
+            else MX_GO(false, 2, true);
+            return fused;
+        }
     }
+    if (fused) MX_GO(true, 1, false);
+    else MX_GO(false, 1, false);
 #undef MX_GO
     return fused;
 }
@@ -3377,18 +3450,33 @@ static bool mx_match(hipStream_t s, bool pipelined, int n_frames, const uint8_t 
 /* batch form on expanded descriptors (desc_x of the extraction): same arguments as ssk_match, strides in BYTES.  With several
  * chunks two launches: k_match_mfma_x writes one partial per (query, chunk), k_match_finish_x folds them, adds the second best
  * inside the best row's group and applies the acceptance test. */
-void ssk_match_x(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
-                 int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift, int chunk_len,
-                 int n_chunks, int exclude_self_mode, int th, int rnum, int rden, int out_stride, void *partial, int32_t *idx,
-                 uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p, int64_t qp_frame_stride,
-                 int64_t tp_frame_stride)
+template <bool TABLE>
+static void match_x_batch(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
+                          int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift, int chunk_len,
+                          int n_chunks, int exclude_self_mode, int th, int rnum, int rden, int out_stride, void *partial, int32_t *idx,
+                          uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p, int64_t qp_frame_stride,
+                          int64_t tp_frame_stride, const ssk_table *tab)
 {
     mx_finish fin{query_p, train_p, qp_frame_stride, tp_frame_stride, th, rnum, rden, idx, d1, d2};
-    if (mx_match(s, mx_pipelined(n_frames, out_stride), n_frames, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride, t_frame_stride,
-                 train_frame_shift, chunk_len, n_chunks, exclude_self_mode, out_stride, partial, fin))
+    /* the carry in the row format each launch reads */
+    mt_table tx{}, tp{};
+    if (tab) {
+        tx = mt_table{tab->src, (const uint8_t *)tab->carry_x, (const uint8_t *)tab->carry_p, tab->carry_n};
+        tp = mt_table{tab->src, (const uint8_t *)tab->carry_p, (const uint8_t *)tab->carry_p, tab->carry_n};
+    }
+    if (mx_match<TABLE>(s, mx_pipelined(n_frames, out_stride), n_frames, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride,
+                        t_frame_stride, train_frame_shift, chunk_len, n_chunks, exclude_self_mode, out_stride, partial, fin, tx))
         return;
     dim3 g2((out_stride + 63) / 64, n_frames);
-    if (query_p && train_p) /* the same rows as packed descriptors: the finish reads those */
+    if (TABLE && query_p && train_p) /* the same rows as packed descriptors: the finish reads those */
+        hipLaunchKernelGGL((k_match_finish_x<32, mt_table>), g2, dim3(256), 0, s, query_p, train_p, nq_arr, nt_arr, nq_fixed, nt_fixed, qp_frame_stride,
+                           tp_frame_stride, train_frame_shift, exclude_self_mode, (const match_partial *)partial, n_chunks, th, rnum, rden, out_stride,
+                           idx, d1, d2, tp);
+    else if (TABLE)
+        hipLaunchKernelGGL((k_match_finish_x<SS_X_ROW, mt_table>), g2, dim3(256), 0, s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed,
+                           q_frame_stride, t_frame_stride, train_frame_shift, exclude_self_mode, (const match_partial *)partial, n_chunks, th, rnum,
+                           rden, out_stride, idx, d1, d2, tx);
+    else if (query_p && train_p)
         hipLaunchKernelGGL(k_match_finish_x<32>, g2, dim3(256), 0, s, query_p, train_p, nq_arr, nt_arr, nq_fixed, nt_fixed, qp_frame_stride,
                            tp_frame_stride, train_frame_shift, exclude_self_mode, (const match_partial *)partial, n_chunks, th, rnum, rden, out_stride,
                            idx, d1, d2);
@@ -3396,6 +3484,26 @@ void ssk_match_x(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, 
         hipLaunchKernelGGL(k_match_finish_x<SS_X_ROW>, g2, dim3(256), 0, s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride,
                            t_frame_stride, train_frame_shift, exclude_self_mode, (const match_partial *)partial, n_chunks, th, rnum, rden, out_stride,
                            idx, d1, d2);
+}
+
+void ssk_match_x(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
+                 int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift, int chunk_len,
+                 int n_chunks, int exclude_self_mode, int th, int rnum, int rden, int out_stride, void *partial, int32_t *idx,
+                 uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p, int64_t qp_frame_stride,
+                 int64_t tp_frame_stride)
+{
+    match_x_batch<false>(s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride, t_frame_stride, train_frame_shift, chunk_len,
+                         n_chunks, exclude_self_mode, th, rnum, rden, out_stride, partial, idx, d1, d2, n_frames, query_p, train_p, qp_frame_stride,
+                         tp_frame_stride, nullptr);
+}
+
+void ssk_match_x_table(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
+                       int64_t q_frame_stride, int64_t t_frame_stride, int chunk_len, int n_chunks, int th, int rnum, int rden, int out_stride,
+                       void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p,
+                       int64_t qp_frame_stride, int64_t tp_frame_stride, const ssk_table &tab)
+{
+    match_x_batch<true>(s, query_x, train_x, nq_arr, nt_arr, 0, 0, q_frame_stride, t_frame_stride, 0, chunk_len, n_chunks, 2, th, rnum, rden,
+                        out_stride, partial, idx, d1, d2, n_frames, query_p, train_p, qp_frame_stride, tp_frame_stride, &tab);
 }
 
 /* chunk plan: rows_q query rows and rows_t train rows per frame.  Once the query blocks alone fill the chip, one chunk per
@@ -3462,16 +3570,21 @@ void ssk_match_x_single(hipStream_t s, const uint8_t *query_x, int nq, const uin
                            fin_chunks, th, rnum, rden, nq, idx, d1, d2);
 }
 
-void ssk_match(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr,
-               int nq_fixed, int nt_fixed, int64_t q_frame_stride_words, int64_t t_frame_stride_words,
-               int train_frame_shift, int chunk_len, int n_chunks, int exclude_self_mode, int th, int rnum, int rden,
-               int out_stride, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames)
+template <bool TABLE>
+static void match_batch(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr, int nq_fixed,
+                        int nt_fixed, int64_t q_frame_stride_words, int64_t t_frame_stride_words, int train_frame_shift, int chunk_len,
+                        int n_chunks, int exclude_self_mode, int th, int rnum, int rden, int out_stride, void *partial, int32_t *idx,
+                        uint16_t *d1, uint16_t *d2, int n_frames, const mt_table &tab)
 {
     if (out_stride >= SSK_MATCH_MFMA_MIN_QUERIES) {
-        /* many queries: the matrix-core form */
-        const int nu = mm_tiles_per_wave(nt_fixed, n_frames);
+        /* many queries: the matrix-core form (the table form: NU = 1 only) */
+        const int nu = TABLE ? 1 : mm_tiles_per_wave(nt_fixed, n_frames);
         dim3 grid((out_stride + MM_QBLOCK(nu) - 1) / MM_QBLOCK(nu), n_chunks, n_frames);
-        if (nu == 2)
+        if (TABLE)
+            hipLaunchKernelGGL((k_match_mfma<1, mt_table>), grid, dim3(64 * MM_WAVES), 0, s, (const uint32_t *)query, (const uint32_t *)train, nq_arr,
+                               nt_arr, nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift, chunk_len,
+                               n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2, tab);
+        else if (nu == 2)
             hipLaunchKernelGGL(k_match_mfma<2>, grid, dim3(64 * MM_WAVES), 0, s, (const uint32_t *)query, (const uint32_t *)train, nq_arr,
                                nt_arr, nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift, chunk_len,
                                n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2);
@@ -3481,9 +3594,14 @@ void ssk_match(hipStream_t s, const void *query, const void *train, const int32_
                                n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2);
     } else {
         dim3 grid((out_stride + 63) / 64, n_chunks, n_frames);
-        hipLaunchKernelGGL(k_match, grid, dim3(256), 0, s, (const uint32_t *)query, (const uint32_t *)train, nq_arr, nt_arr,
-                           nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift, chunk_len,
-                           n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2);
+        if (TABLE)
+            hipLaunchKernelGGL(k_match<mt_table>, grid, dim3(256), 0, s, (const uint32_t *)query, (const uint32_t *)train, nq_arr, nt_arr,
+                               nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift, chunk_len,
+                               n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2, tab);
+        else
+            hipLaunchKernelGGL(k_match<>, grid, dim3(256), 0, s, (const uint32_t *)query, (const uint32_t *)train, nq_arr, nt_arr,
+                               nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift, chunk_len,
+                               n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2);
     }
     if (n_chunks >= 32 && n_frames == 1 && !nq_arr) {
         hipLaunchKernelGGL(k_match_merge_wide, dim3(out_stride), dim3(64), 0, s, (const match_partial *)partial, nq_fixed, n_chunks,
@@ -3493,6 +3611,24 @@ void ssk_match(hipStream_t s, const void *query, const void *train, const int32_
         hipLaunchKernelGGL(k_match_merge, g2, dim3(256), 0, s, (const match_partial *)partial, nq_arr, nq_fixed,
                            n_chunks, th, rnum, rden, out_stride, idx, d1, d2);
     }
+}
+
+void ssk_match(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr,
+               int nq_fixed, int nt_fixed, int64_t q_frame_stride_words, int64_t t_frame_stride_words,
+               int train_frame_shift, int chunk_len, int n_chunks, int exclude_self_mode, int th, int rnum, int rden,
+               int out_stride, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames)
+{
+    match_batch<false>(s, query, train, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift,
+                       chunk_len, n_chunks, exclude_self_mode, th, rnum, rden, out_stride, partial, idx, d1, d2, n_frames, mt_table{});
+}
+
+void ssk_match_table(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr,
+                     int64_t q_frame_stride_words, int64_t t_frame_stride_words, int chunk_len, int n_chunks, int th, int rnum, int rden,
+                     int out_stride, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames, const ssk_table &tab)
+{
+    const mt_table t{tab.src, (const uint8_t *)tab.carry_p, (const uint8_t *)tab.carry_p, tab.carry_n};
+    match_batch<true>(s, query, train, nq_arr, nt_arr, 0, 0, q_frame_stride_words, t_frame_stride_words, 0, chunk_len, n_chunks, 2, th, rnum,
+                      rden, out_stride, partial, idx, d1, d2, n_frames, t);
 }
 
 /* database-streaming match for n_query <= 8 (see k_match_stream): plan (false = not applicable), kernel launch, merge
@@ -3528,6 +3664,20 @@ void ssk_match_stream_merge(hipStream_t s, const void *partial, int nq, int n_ch
 {
     hipLaunchKernelGGL(k_match_merge_wide, dim3(nq), dim3(64), 0, s, (const match_partial *)partial, nq, n_chunks, th, rnum, rden, nq,
                        idx, d1, d2);
+}
+
+void ssk_carry_gather(hipStream_t s, const void *desc, const int32_t *n_kp, int kcap, const int32_t *dst, const int32_t *src, int n, void *carry,
+                      int32_t *carry_n)
+{
+    if (n <= 0) return;
+    carry_pairs pr{};
+    for (int i = 0; i < n && i < SSK_CARRY_MAX; i++) {
+        pr.dst[i] = dst[i];
+        pr.src[i] = src[i];
+    }
+    const int units = kcap * (SS_DESC_BYTES / 16);
+    hipLaunchKernelGGL(k_carry_gather, dim3(std::min((units + 255) / 256, 64), std::min(n, SSK_CARRY_MAX)), dim3(256), 0, s, (const uint4 *)desc,
+                       n_kp, kcap, pr, (uint4 *)carry, carry_n);
 }
 
 void ssk_pack_partial(hipStream_t s, const int32_t *idx, const uint16_t *d1, const uint16_t *d2, int n, int32_t row_offset,

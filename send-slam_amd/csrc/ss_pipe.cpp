@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <functional>
@@ -31,6 +32,9 @@
 #include <vector>
 
 #include "../../include/sendslam_orb.h"
+#include "ss_kernels.h"
+
+static_assert(SSK_CARRY_MAX == SS_MAX_CAMERAS, "one carry gather moves a frame of every camera the carry holds");
 
 namespace {
 
@@ -124,6 +128,11 @@ struct pipe_slot {
     uint64_t sequence = 0;
     std::vector<int32_t> status, camera_id;
     std::vector<double> timestamp;
+    /* match_mode 2: each frame's train (the table of ss_match_batch_sources_device), which frame that is (sequence, index;
+     * -1 -1 none), and the frames this batch left in the carry (carry slot, frame) */
+    std::vector<int32_t> train_src, src_frame;
+    std::vector<int64_t> src_seq;
+    std::vector<std::pair<int, int>> carried;
     /* device result arrays of the slot's context */
     ss_batch_view view{};
     /* carved host result arrays */
@@ -150,6 +159,27 @@ struct ss_pipe {
     std::string err_producer, err_consumer;
     std::atomic<int> err_side{0}; /* 0 none, 1 producer, 2 consumer */
     bool broken = false;        /* a submission failed half-way and its streams could not be drained */
+    /* match_mode 2: the carry = the last producer-OK frame of up to SS_MAX_CAMERAS cameras from earlier batches: packed rows
+     * [SS_MAX_CAMERAS][kcap][32] and counts on the device, per carry slot its camera (0 = empty) and which frame it holds.
+     * Written by the carry update of every batch; the next batch's match waits for it (carry_done). */
+    uint8_t *d_carry = nullptr;
+    int32_t *d_carry_n = nullptr;
+    int32_t carry_cam[SS_MAX_CAMERAS] = {};
+    int64_t carry_seq[SS_MAX_CAMERAS] = {};
+    int32_t carry_frame[SS_MAX_CAMERAS] = {};
+    hipEvent_t carry_done = nullptr;
+    bool carry_recorded = false;
+    /* per carry slot, the frame it received from the last RETURNED batch and whether the kernels flagged that frame.  Results
+     * come back in submission order, and between a carried frame and a later frame matched against it no batch holds that
+     * camera (else the later frame's train would be newer), so when a batch is filled this is its carry trains' record. */
+    struct carry_record {
+        int64_t seq = -1;
+        int frame = -1;
+        bool bad = false;
+    } carry_fill[SS_MAX_CAMERAS];
+    /* test hook, SENDSLAM_TEST_FLAG_FRAMES=seq:frame,...: those frames come back as if the kernels had flagged them
+     * (frame_error != 0 -> SS_ERR_OVERFLOW), the only way to reach the bad-train rules without overflowing a capacity */
+    std::vector<std::pair<int64_t, int>> test_flagged;
     int inject_fail_after = -1; /* test hook (ss_pipe_debug_inject_failure): the next submission fails after this many enqueued operations */
     copy_pool *pool = nullptr;
 };
@@ -207,6 +237,8 @@ void free_slot(pipe_slot &s)
 
 void fill_result(ss_pipe *p, pipe_slot &s, int id, ss_pipe_result *out)
 {
+    for (const auto &f : p->test_flagged)
+        if (f.first == (int64_t)s.sequence && f.second >= 0 && f.second < s.n_frames) s.h_err[f.second] = 1;
     /* a frame's own status: what the producer flagged, else what the kernels reported */
     for (int i = 0; i < s.n_frames; i++) {
         if (s.status[i] == SS_OK && s.h_err[i] != 0) s.status[i] = SS_ERR_OVERFLOW;
@@ -222,6 +254,23 @@ void fill_result(ss_pipe *p, pipe_slot &s, int id, ss_pipe_result *out)
         for (int i = 1; i < s.n_frames; i++)
             if (s.status[i - 1] != SS_OK)
                 for (int k = 0; k < p->kcap; k++) s.h_midx[(size_t)i * p->kcap + k] = -1;
+    /* match_mode 2: the same for a train in the batch or in the carry that the kernels flagged; such a frame has no source */
+    if (p->cfg.match_mode == 2) {
+        for (int i = 0; i < s.n_frames; i++) {
+            const int t = s.train_src[i];
+            bool bad = s.status[i] != SS_OK || (t >= 0 && s.status[t] != SS_OK);
+            if (t <= -2) {
+                const auto &rec = p->carry_fill[-2 - t];
+                bad = bad || (rec.bad && rec.seq == s.src_seq[i] && rec.frame == s.src_frame[i]);
+            }
+            if (!bad) continue;
+            for (int k = 0; k < p->kcap; k++) s.h_midx[(size_t)i * p->kcap + k] = -1;
+            s.src_seq[i] = -1;
+            s.src_frame[i] = -1;
+        }
+        /* after this batch's own trains were checked: what it left in the carry, for the batches after it */
+        for (const auto &cf : s.carried) p->carry_fill[cf.first] = {(int64_t)s.sequence, cf.second, s.status[cf.second] != SS_OK};
+    }
     out->slot = id;
     out->n_frames = s.n_frames;
     out->kp_capacity = p->kcap;
@@ -263,6 +312,9 @@ int ss_pipe_destroy(ss_pipe *p)
     delete p->pool;
     for (auto &s : p->slots) free_slot(s);
     if (p->upload) (void)hipStreamDestroy(p->upload);
+    if (p->d_carry) (void)hipFree(p->d_carry);
+    if (p->d_carry_n) (void)hipFree(p->d_carry_n);
+    if (p->carry_done) (void)hipEventDestroy(p->carry_done);
     delete p;
     return SS_OK;
 }
@@ -278,7 +330,7 @@ int ss_pipe_create(int device_ordinal, const ss_orb_params *params, const ss_cam
         return pfail(nullptr, SS_ERR_INVALID_ARG, "ss_pipe_create: bad frame shape");
     if (c.batch < 1 || c.batch > 256) return pfail(nullptr, SS_ERR_INVALID_ARG, "ss_pipe_create: batch out of range (1..256)");
     if (c.depth < 2 || c.depth > 16) return pfail(nullptr, SS_ERR_INVALID_ARG, "ss_pipe_create: depth out of range (2..16)");
-    if (c.match_mode < -1 || c.match_mode > 1) return pfail(nullptr, SS_ERR_INVALID_ARG, "ss_pipe_create: bad match_mode");
+    if (c.match_mode < -1 || c.match_mode > 2) return pfail(nullptr, SS_ERR_INVALID_ARG, "ss_pipe_create: bad match_mode");
     if (c.channels != 1 && !cam) return pfail(nullptr, SS_ERR_NOT_CALIBRATED, "ss_pipe_create: colour frames need the calibration (rgb flag)");
     if (c.match_th == 0 && c.ratio_num == 0 && c.ratio_den == 0) {
         c.match_th = 50;
@@ -349,6 +401,17 @@ int ss_pipe_create(int device_ordinal, const ss_orb_params *params, const ss_cam
         }
         p->kcap = s.view.kp_capacity;
         const size_t B = (size_t)c.batch, K = (size_t)p->kcap;
+        if (c.match_mode == 2 && !p->d_carry) {
+            e = hipMalloc((void **)&p->d_carry, (size_t)SS_MAX_CAMERAS * K * SS_DESC_BYTES);
+            if (e == hipSuccess) e = hipMalloc((void **)&p->d_carry_n, SS_MAX_CAMERAS * sizeof(int32_t));
+            if (e == hipSuccess) e = hipMemsetAsync(p->d_carry, 0, (size_t)SS_MAX_CAMERAS * K * SS_DESC_BYTES, s.stream);
+            if (e == hipSuccess) e = hipMemsetAsync(p->d_carry_n, 0, SS_MAX_CAMERAS * sizeof(int32_t), s.stream);
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&p->carry_done, hipEventDisableTiming);
+            if (e != hipSuccess) {
+                p->err_producer = std::string("ss_pipe_create: ") + hipGetErrorString(e);
+                return bail(e == hipErrorOutOfMemory ? SS_ERR_NO_MEMORY : SS_ERR_HIP);
+            }
+        }
         /* pinned result block */
         size_t off = 0;
         auto carve = [&](size_t bytes) {
@@ -377,8 +440,14 @@ int ss_pipe_create(int device_ordinal, const ss_orb_params *params, const ss_cam
             s.h_md2 = (uint16_t *)(s.h_res + o_m2);
             /* one match of the blank batch: the context allocates its chunk-partial buffer now, not inside the first
              * real submission */
-            rc = ss_match_batch_device(s.ctx, c.match_mode, c.match_th, c.ratio_num, c.ratio_den, s.d_match, s.d_match + B * K * 4,
-                                       s.d_match + B * K * 6);
+            if (c.match_mode == 2) { /* also sizes the context's buffer of the expanded carry */
+                const std::vector<int32_t> none(B, -1);
+                rc = ss_match_batch_sources_device(s.ctx, none.data(), p->d_carry, p->d_carry_n, SS_MAX_CAMERAS, c.match_th, c.ratio_num,
+                                                   c.ratio_den, s.d_match, s.d_match + B * K * 4, s.d_match + B * K * 6);
+            } else {
+                rc = ss_match_batch_device(s.ctx, c.match_mode, c.match_th, c.ratio_num, c.ratio_den, s.d_match, s.d_match + B * K * 4,
+                                           s.d_match + B * K * 6);
+            }
             if (rc == SS_OK) rc = ss_synchronize(s.ctx);
             if (rc != SS_OK) {
                 p->err_producer = ss_last_error(s.ctx);
@@ -388,7 +457,22 @@ int ss_pipe_create(int device_ordinal, const ss_orb_params *params, const ss_cam
         s.status.assign(B, SS_OK);
         s.camera_id.assign(B, 1);
         s.timestamp.assign(B, 0.0);
+        s.train_src.assign(B, -1);
+        s.src_frame.assign(B, -1);
+        s.src_seq.assign(B, -1);
     }
+    if (const char *e = getenv("SENDSLAM_TEST_FLAG_FRAMES"))
+        for (const char *q = e; *q;) {
+            char *end = nullptr;
+            const long long sq = strtoll(q, &end, 10);
+            if (end == q || *end != ':') break;
+            q = end + 1;
+            const long fr = strtol(q, &end, 10);
+            if (end == q) break;
+            p->test_flagged.emplace_back((int64_t)sq, (int)fr);
+            q = *end == ',' ? end + 1 : end;
+            if (*end != ',') break;
+        }
     p->pool = new copy_pool(c.copy_threads - 1); /* the submitting thread copies too */
     *out = p;
     return SS_OK;
@@ -412,6 +496,80 @@ int ss_pipe_acquire(ss_pipe *p, ss_pipe_slot *out)
     return p->broken ? pfail(p, SS_ERR_STATE, "ss_pipe: a failed submission could not be drained; destroy the pipe") : SS_ERR_BUSY;
 }
 
+/* match_mode 2, after the extraction: the train table from the camera ids (host), the match against it once the previous
+ * batch's carry update is done, then this batch's carry update.  The host side of the carry is committed only when every
+ * enqueue succeeded; a failed submission empties it (submit_locked). */
+static int enqueue_carry_match(ss_pipe *p, pipe_slot &s, int n)
+{
+    const ss_pipe_config &c = p->cfg;
+    const size_t K = (size_t)p->kcap, B = (size_t)c.batch;
+    const int64_t seq = (int64_t)p->next_sequence; /* this batch's sequence if the submission succeeds (one producer thread) */
+    int32_t cam[SS_MAX_CAMERAS];
+    int64_t cseq[SS_MAX_CAMERAS];
+    int32_t cframe[SS_MAX_CAMERAS];
+    std::copy(p->carry_cam, p->carry_cam + SS_MAX_CAMERAS, cam);
+    std::copy(p->carry_seq, p->carry_seq + SS_MAX_CAMERAS, cseq);
+    std::copy(p->carry_frame, p->carry_frame + SS_MAX_CAMERAS, cframe);
+    s.carried.clear();
+    for (int i = 0; i < n; i++) {
+        s.train_src[i] = -1;
+        s.src_seq[i] = -1;
+        s.src_frame[i] = -1;
+        if (s.status[i] != SS_OK) continue; /* a bad frame neither has a train nor is one */
+        const int id = s.camera_id[i];
+        int t = -1;
+        for (int j = i - 1; j >= 0 && t < 0; j--)
+            if (s.status[j] == SS_OK && s.camera_id[j] == id) t = j;
+        if (t >= 0) {
+            s.train_src[i] = t;
+            s.src_seq[i] = seq;
+            s.src_frame[i] = t;
+        } else {
+            for (int k = 0; k < SS_MAX_CAMERAS; k++)
+                if (cam[k] == id) {
+                    s.train_src[i] = -2 - k;
+                    s.src_seq[i] = cseq[k];
+                    s.src_frame[i] = cframe[k];
+                }
+        }
+    }
+    /* each camera's last OK frame of the batch goes to the camera's carry slot, or to a free one */
+    int32_t dst[SS_MAX_CAMERAS], src[SS_MAX_CAMERAS];
+    int n_pairs = 0;
+    for (int i = n - 1; i >= 0; i--) {
+        if (s.status[i] != SS_OK) continue;
+        const int id = s.camera_id[i];
+        bool later = false; /* a later OK frame of this camera has been carried already */
+        for (int j = i + 1; j < n && !later; j++) later = s.status[j] == SS_OK && s.camera_id[j] == id;
+        if (later) continue;
+        int k = -1;
+        for (int q = 0; q < SS_MAX_CAMERAS && k < 0; q++)
+            if (cam[q] == id) k = q;
+        for (int q = 0; q < SS_MAX_CAMERAS && k < 0; q++)
+            if (cam[q] == 0) k = q;
+        if (k < 0) continue; /* more cameras than carry slots: this one has in-batch trains only */
+        cam[k] = id;
+        cseq[k] = seq;
+        cframe[k] = i;
+        dst[n_pairs] = k;
+        src[n_pairs++] = i;
+        s.carried.emplace_back(k, i);
+    }
+    if (p->carry_recorded) PIPE_ENQ(p, hipStreamWaitEvent(s.stream, p->carry_done, 0));
+    uint8_t *dm = s.d_match;
+    int rc = ss_match_batch_sources_device(s.ctx, s.train_src.data(), p->d_carry, p->d_carry_n, SS_MAX_CAMERAS, c.match_th, c.ratio_num, c.ratio_den,
+                                           dm, dm + B * K * 4, dm + B * K * 6);
+    if (rc != SS_OK) return pfail(p, rc, ss_last_error(s.ctx));
+    ssk_carry_gather(s.stream, s.view.descriptors, s.view.n_keypoints, p->kcap, dst, src, n_pairs, p->d_carry, p->d_carry_n);
+    PIPE_ENQ(p, hipGetLastError());
+    PIPE_ENQ(p, hipEventRecord(p->carry_done, s.stream));
+    p->carry_recorded = true;
+    std::copy(cam, cam + SS_MAX_CAMERAS, p->carry_cam);
+    std::copy(cseq, cseq + SS_MAX_CAMERAS, p->carry_seq);
+    std::copy(cframe, cframe + SS_MAX_CAMERAS, p->carry_frame);
+    return SS_OK;
+}
+
 /* the enqueues of one submission, on the upload stream and on the slot's stream */
 static int enqueue_batch(ss_pipe *p, pipe_slot &s, int n)
 {
@@ -427,11 +585,17 @@ static int enqueue_batch(ss_pipe *p, pipe_slot &s, int n)
     if (p->inject_fail_after > 0) p->inject_fail_after--;
     int rc = ss_extract_batch_device(s.ctx, s.d_pix, n, c.width, c.height, c.channels, p->row_stride, p->frame_stride);
     if (rc != SS_OK) return pfail(p, rc, ss_last_error(s.ctx));
+    if (c.match_mode == 2) {
+        rc = enqueue_carry_match(p, s, n);
+        if (rc != SS_OK) return rc;
+    }
     if (c.match_mode >= 0) {
         uint8_t *dm = s.d_match;
         const size_t B = (size_t)c.batch;
-        rc = ss_match_batch_device(s.ctx, c.match_mode, c.match_th, c.ratio_num, c.ratio_den, dm, dm + B * K * 4, dm + B * K * 6);
-        if (rc != SS_OK) return pfail(p, rc, ss_last_error(s.ctx));
+        if (c.match_mode != 2) {
+            rc = ss_match_batch_device(s.ctx, c.match_mode, c.match_th, c.ratio_num, c.ratio_den, dm, dm + B * K * 4, dm + B * K * 6);
+            if (rc != SS_OK) return pfail(p, rc, ss_last_error(s.ctx));
+        }
         PIPE_ENQ(p, hipMemcpyAsync(s.h_midx, dm, N * K * 4, hipMemcpyDeviceToHost, s.stream));
         PIPE_ENQ(p, hipMemcpyAsync(s.h_md1, dm + B * K * 4, N * K * 2, hipMemcpyDeviceToHost, s.stream));
         PIPE_ENQ(p, hipMemcpyAsync(s.h_md2, dm + B * K * 6, N * K * 2, hipMemcpyDeviceToHost, s.stream));
@@ -472,6 +636,8 @@ static int submit_locked(ss_pipe *p, int slot, int n, const int32_t *camera_ids,
          * work.  The slot stays ACQUIRED: the caller releases or resubmits it. */
         const std::string first = p->err_producer;
         const hipError_t e1 = hipStreamSynchronize(p->upload), e2 = hipStreamSynchronize(s.stream);
+        /* match_mode 2: what the carry holds is no longer known; the next batch's first frame of each camera has no train */
+        std::fill(p->carry_cam, p->carry_cam + SS_MAX_CAMERAS, 0);
         if (e1 != hipSuccess || e2 != hipSuccess) {
             std::lock_guard<std::mutex> g(p->m);
             p->broken = true;
@@ -573,6 +739,18 @@ int ss_pipe_release(ss_pipe *p, int slot)
     if (s.state != SLOT_RETURNED && s.state != SLOT_ACQUIRED)
         return pfail(p, SS_ERR_STATE, "ss_pipe_release: slot is free or still in flight", SIDE_CONSUMER);
     s.state = SLOT_FREE;
+    return SS_OK;
+}
+
+int ss_pipe_match_sources(const ss_pipe *p, int slot, int64_t *train_sequence, int32_t *train_frame)
+{
+    if (!p || !train_sequence || !train_frame) return SS_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(p->m);
+    if (p->cfg.match_mode != 2) return SS_ERR_STATE;
+    if (slot < 0 || slot >= (int)p->slots.size() || p->slots[(size_t)slot].state != SLOT_RETURNED) return SS_ERR_STATE;
+    const pipe_slot &s = p->slots[(size_t)slot];
+    std::copy(s.src_seq.begin(), s.src_seq.begin() + s.n_frames, train_sequence);
+    std::copy(s.src_frame.begin(), s.src_frame.begin() + s.n_frames, train_frame);
     return SS_OK;
 }
 

@@ -40,6 +40,12 @@
  *                              messages, in the same order as frame-by-frame ss_track (tests/test_wire.py).
  *                              The pose step and the answers run on a second thread (SENDSLAM_TRACK_THREAD=0: on the
  *                              receiving one): batch k is tracked while batch k + 1 is received, decoded and submitted
+ *   SENDSLAM_CAMERAS=1,3       serve only these camera ids: calibrations and frames of other cameras are skipped before
+ *                              decode (one log line per skipped camera).  Unset: every camera.  The host sends every
+ *                              camera to every backend (slam_handler.ex:59-88); one front door tracks them all, each
+ *                              camera with its own state and calibration (up to SS_MAX_CAMERAS).  With read-ahead, all
+ *                              cameras share the pipe's frame shape (a frame of another shape rebuilds the pipe) and
+ *                              the RGB order of colour frames (Camera.RGB of the calibration received last).
  *   --selftest-pose            print the pose packet for fixed values as hex and exit (golden
  *                              wire bytes, tests/test_wire.py; needs no GPU)
  */
@@ -60,8 +66,10 @@
 #include <cstring>
 #include <functional>
 #include <iostream>
+#include <map>
 #include <mutex>
 #include <numeric>
+#include <set>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -333,6 +341,13 @@ int main(int argc, char **argv)
     params.n_features = env_int("SENDSLAM_ORB_NFEATURES", params.n_features);
     const int device = env_int("SENDSLAM_DEVICE", 0);
     const bool emitFeatures = env_int("SENDSLAM_EMIT_FEATURES", 0) != 0;
+    set<int> servedCameras, skippedCameras; /* SENDSLAM_CAMERAS; empty = every camera */
+    if (const char *cs = getenv("SENDSLAM_CAMERAS")) {
+        stringstream ss(cs);
+        string item;
+        while (getline(ss, item, ','))
+            if (!item.empty()) servedCameras.insert(atoi(item.c_str()));
+    }
     int shardRank = -1, shardWorld = 0;
     if (const char *sh = getenv("SENDSLAM_SHARD")) {
         if (sscanf(sh, "%d/%d", &shardRank, &shardWorld) != 2 || shardWorld != 2 || shardRank < 0 || shardRank >= shardWorld) {
@@ -450,6 +465,10 @@ int main(int argc, char **argv)
         lock_guard<mutex> g(qm);
         return batchesInFlight;
     };
+    /* per camera: (sequence, index) of the frame the pose step saw last; the pipe's match sources of a batch */
+    map<int, pair<int64_t, int>> lastTracked;
+    vector<int64_t> srcSeq(64);
+    vector<int32_t> srcFrame(64);
     /* takes the oldest completed batch (blocking), tracks its frames in order, ships poses; false = the pipe has failed */
     auto finish_batch_now = [&]() -> bool {
         ss_pipe_result r{};
@@ -469,30 +488,38 @@ int main(int argc, char **argv)
             return false;
         }
         const double extractShare = chrono::duration_cast<chrono::duration<double>>(chrono::steady_clock::now() - submitted).count() / max(1, r.n_frames);
-        bool prevTracked = false; /* frame i - 1 of this batch went through the pose step */
+        /* the slot's batch matcher has matched each frame against the previous frame of its camera (match_mode 2): which one
+         * that was, per frame */
+        if (r.match_idx && ss_pipe_match_sources(pipe, r.slot, srcSeq.data(), srcFrame.data()) != SS_OK) {
+            pipe_fatal("ss_pipe_match_sources");
+            lock_guard<mutex> g(qm);
+            qcv.notify_all();
+            return false;
+        }
         for (int i = 0; i < r.n_frames; i++) {
             if (r.status[i] != SS_OK) {
                 cerr << "Frame skipped: extraction failed (status " << r.status[i] << ")" << endl; /* bad frame => log + skip */
-                prevTracked = false;
                 continue;
             }
             const auto t1 = chrono::steady_clock::now();
             ss_pose tracked{};
-            /* the slot's batch matcher has matched frame i against frame i - 1 (match_mode 1): the pose step takes those when
-             * frame i - 1 is the frame it saw last, and the slot's rows stay put until the slot is released below */
-            const bool haveMatches = r.match_idx && prevTracked;
-            prevTracked = false;
+            /* the pose step takes the batch matches when their train is the frame it saw last for this camera; the slot's
+             * rows stay put until they are detached before the slot is released below */
+            const auto seen = lastTracked.find(r.camera_id[i]);
+            const bool haveMatches = r.match_idx && srcSeq[i] >= 0 && seen != lastTracked.end() &&
+                                     seen->second == make_pair((int64_t)srcSeq[i], (int)srcFrame[i]);
             const int rc = ss_track_features_matched(ctx, r.camera_id[i], r.timestamp[i],
                                                      (const uint8_t *)r.d_descriptors + (size_t)i * r.kp_capacity * SS_DESC_BYTES,
                                                      r.keypoints + (size_t)i * r.kp_capacity, r.n_keypoints[i],
                                                      haveMatches ? r.match_idx + (size_t)i * r.kp_capacity : nullptr,
                                                      haveMatches ? r.match_d1 + (size_t)i * r.kp_capacity : nullptr,
-                                                     i + 1 < r.n_frames ? SS_TRACK_DESC_STAYS_VALID : 0, &tracked);
+                                                     SS_TRACK_DESC_STAYS_VALID, &tracked);
             if (rc != SS_OK) {
                 cerr << "Frame skipped: " << ss_last_error(ctx) << endl;
+                lastTracked.erase(r.camera_id[i]);
                 continue;
             }
-            prevTracked = true;
+            lastTracked[r.camera_id[i]] = make_pair((int64_t)r.sequence, i);
             tTrack += secs_since(t1);
             const auto ts1 = chrono::steady_clock::now();
             emit_tracked(tracked, r.camera_id[i], r.timestamp[i]);
@@ -500,6 +527,8 @@ int main(int argc, char **argv)
             const double ttrack = chrono::duration_cast<chrono::duration<double>>(chrono::steady_clock::now() - t1).count();
             trackSeconds.push_back((float)(ttrack + extractShare));
         }
+        /* the tracker may still refer to rows of this slot (the last frame of a camera, also after a skipped tail frame) */
+        if (ss_track_detach(ctx) != SS_OK) cerr << "ss_track_detach: " << ss_last_error(ctx) << endl;
         ss_pipe_release(pipe, r.slot);
         {
             lock_guard<mutex> g(qm);
@@ -581,8 +610,12 @@ int main(int argc, char **argv)
             unique_lock<mutex> l(qm);
             qcv.wait(l, [&] { return !trackerBusy; });
         }
-        if (pipe) ss_pipe_destroy(pipe);
+        if (pipe) {
+            if (ctx && ss_track_detach(ctx) != SS_OK) cerr << "ss_track_detach: " << ss_last_error(ctx) << endl;
+            ss_pipe_destroy(pipe);
+        }
         pipe = nullptr;
+        lastTracked.clear();
     };
     auto input_queued = [&]() {
         pollfd pf{fd, POLLIN, 0};
@@ -644,6 +677,12 @@ int main(int argc, char **argv)
         }
 
         tParse += secs_since(tp0);
+        if ((packet.type == "frame" || packet.type == "calibration") && packet.camera_id && !servedCameras.empty() &&
+            !servedCameras.count(packet.camera_id)) {
+            if (skippedCameras.insert(packet.camera_id).second)
+                cout << "Skipping camera " << packet.camera_id << ": not in SENDSLAM_CAMERAS." << endl;
+            continue;
+        }
         if (packet.type != "frame") drain_pipe(); /* messages are answered in order */
         if (pipeFailed) break;
         if (packet.type == "terminate" || packet.type == "shutdown") {
@@ -660,13 +699,10 @@ int main(int argc, char **argv)
                 cerr << "Calibration message missing structured parameter payload." << endl;
                 continue;
             }
-            /* a second calibration rebuilds the whole system (:491-518) */
+            /* a second calibration rebuilds the whole system (:491-518) -- of that camera: ss_set_calibration resets the
+             * camera's tracking state, the other cameras of the connection keep theirs */
             destroy_pipe();
-            if (ctx) {
-                ss_destroy(ctx);
-                ctx = nullptr;
-            }
-            const int rc = ss_create(device, &params, &ctx);
+            const int rc = ctx ? SS_OK : ss_create(device, &params, &ctx);
             if (rc != SS_OK) {
                 /* the reference's System ctor would throw into the outer try (:636-650): exit 1.
                  * No GPU means no service: there is no CPU path to fall back to. */
@@ -729,9 +765,10 @@ int main(int argc, char **argv)
                     ss_pipe_config cfg{};
                     cfg.width = w; cfg.height = h; cfg.channels = ch;
                     cfg.batch = readAhead; cfg.depth = 3;
-                    /* frame b against frame b - 1 inside a batch, by the pose step's own rule: one launch per batch instead of
-                     * one match + two copies + two waits per frame (SENDSLAM_BATCH_MATCH=0: the pose step matches) */
-                    cfg.match_mode = env_int("SENDSLAM_BATCH_MATCH", 1) ? 1 : -1;
+                    /* each frame against the previous frame of its camera (match_mode 2: inside the batch or from the pipe's
+                     * carry), by the pose step's own rule: one launch per batch instead of one match + two copies + two waits
+                     * per frame (SENDSLAM_BATCH_MATCH=0: the pose step matches) */
+                    cfg.match_mode = env_int("SENDSLAM_BATCH_MATCH", 1) ? 2 : -1;
                     cfg.match_th = 50; cfg.ratio_num = 9; cfg.ratio_den = 10;
                     /* a P6 raster is R,G,B on the wire and a B,G,R cv::Mat after imdecode (:546), which Camera.RGB then
                      * labels; the slots keep the wire order (rows copied as they are, no per-pixel swap on this thread) and

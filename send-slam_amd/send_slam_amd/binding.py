@@ -33,7 +33,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_pipe_create", "ss_pipe_destroy", "ss_pipe_last_error", "ss_pipe_acquire", "ss_pipe_submit",
            "ss_pipe_submit_frames", "ss_pipe_wait", "ss_pipe_poll", "ss_pipe_release", "ss_pipe_in_flight",
            "ss_match_fold_strided_device", "ss_xchg_create", "ss_xchg_destroy", "ss_xchg_last_error", "ss_xchg_status",
-           "ss_xchg_allgather", "ss_xchg_broadcast", "ss_pipe_debug_inject_failure", "ss_stereo_exchange_match"]
+           "ss_xchg_allgather", "ss_xchg_broadcast", "ss_pipe_debug_inject_failure", "ss_stereo_exchange_match",
+           "ss_match_batch_sources_device", "ss_track_detach", "ss_pipe_match_sources"]
 
 
 class OrbParams(C.Structure):
@@ -144,9 +145,13 @@ def load():
     lib.ss_match_device.argtypes = lib.ss_match.argtypes
     lib.ss_match_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p]
+    lib.ss_match_batch_sources_device.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                  C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ss_track.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                              C.POINTER(Pose)]
     lib.ss_track_reset.argtypes = [C.c_void_p]
+    lib.ss_track_detach.argtypes = [C.c_void_p]
+    lib.ss_pipe_match_sources.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.ss_synchronize.argtypes = [C.c_void_p]
     lib.ss_get_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     lib.ss_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -317,6 +322,10 @@ class OrbContext:
     def track_reset(self):
         self._check(self._lib.ss_track_reset(self._h))
 
+    def track_detach(self):
+        """Copy the descriptor rows any camera's tracker still refers to (desc_stays_valid) into the context."""
+        self._check(self._lib.ss_track_detach(self._h))
+
     # ---- device in / device out (pointers are raw device addresses, e.g. tensor.data_ptr()) ----
     def extract_batch_device(self, d_ptr: int, n_frames: int, width: int, height: int, channels: int = 1,
                              row_stride: Optional[int] = None, frame_stride: Optional[int] = None):
@@ -352,6 +361,16 @@ class OrbContext:
                            ratio_den: int = 10):
         self._check(self._lib.ss_match_batch_device(self._h, mode, th, ratio_num, ratio_den, C.c_void_p(d_idx),
                                                     C.c_void_p(d_d1), C.c_void_p(d_d2)))
+
+    def match_batch_sources_device(self, train_src, d_idx: int, d_d1: int, d_d2: int, d_carry: int = 0, d_carry_n: int = 0,
+                                   n_carry: int = 0, th: int = 50, ratio_num: int = 9, ratio_den: int = 10):
+        """Every frame of the last batch against the train frame train_src[b] names (host ints, one per frame): >= 0 a frame
+        of the batch, -1 none, <= -2 carry frame -2 - t of d_carry ([n_carry][kp_capacity][32] packed, device) with
+        d_carry_n (device int32 [n_carry]) rows.  Outputs as match_batch_device."""
+        src = np.ascontiguousarray(train_src, dtype=np.int32)
+        self._check(self._lib.ss_match_batch_sources_device(self._h, src.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(d_carry),
+                                                            C.c_void_p(d_carry_n), int(n_carry), th, ratio_num, ratio_den,
+                                                            C.c_void_p(d_idx), C.c_void_p(d_d1), C.c_void_p(d_d2)))
 
     def match_pairs_device(self, d_q: int, d_nq: int, d_t: int, d_nt: int, n_frames: int, rows_per_frame: int, d_idx: int,
                            d_d1: int, d_d2: int, th: int = 50, ratio_num: int = 9, ratio_den: int = 10):
@@ -596,7 +615,15 @@ class Pipe:
                 "level_counts": view(r.level_counts, np.int32, (n, SS_MAX_LEVELS)),
                 "keypoints": view(r.keypoints, KP_DTYPE, (n, k)), "descriptors": view(r.descriptors, np.uint8, (n, k, 32)),
                 "match_idx": view(r.match_idx, np.int32, (n, k)), "match_d1": view(r.match_d1, np.uint16, (n, k)),
-                "match_d2": view(r.match_d2, np.uint16, (n, k)), "d_descriptors": r.d_descriptors}
+                "match_d2": view(r.match_d2, np.uint16, (n, k)), "d_descriptors": r.d_descriptors, **self._sources(r)}
+
+    def _sources(self, r: PipeResult) -> dict:
+        """match_mode 2: which frame each frame was matched against, (sequence, index in its batch) or -1 -1"""
+        if self.cfg.match_mode != 2:
+            return {}
+        seq, frame = np.empty(r.n_frames, np.int64), np.empty(r.n_frames, np.int32)
+        self._check(self._lib.ss_pipe_match_sources(self._h, r.slot, seq.ctypes.data, frame.ctypes.data))
+        return {"train_sequence": seq, "train_frame": frame}
 
     def wait(self) -> dict:
         r = PipeResult()

@@ -105,3 +105,9 @@ def test_geometry_tables_hold_what_the_kernels_assume(tmp_path):
                            os.path.join(ROOT, "send-slam_amd/csrc/ss_geometry.cpp")])
     out = subprocess.run([exe, "7"], capture_output=True, text=True)
     assert out.returncode == 0 and "built=" in out.stdout, out.stdout[-2000:]
+    # the capacity argument of ss_geometry.cpp ("NMS survivors are never 8-adjacent inside one cell window") on the real tables:
+    # the sweep fails on any tile / cell / level whose bound exceeds its capacity and prints the largest per-tile bound it found
+    m = re.search(r"max_tile_survivors=(\d+) of (\d+) .*max_bucket_fill=([\d.]+) max_cand_fill=([\d.]+)", out.stdout)
+    assert m, out.stdout[-2000:]
+    print(m.group(0))
+    assert 0 < int(m.group(1)) <= int(m.group(2)) == 576 and float(m.group(3)) <= 1.0 and float(m.group(4)) <= 1.0

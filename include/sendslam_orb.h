@@ -31,6 +31,8 @@
  *                              TrackMonocular :594 (all-pairs rule: SURVEY.md Appendix A.6)
  *   ss_track                   TrackMonocular :594 -> Twc, tracking state :596 (bounded monocular
  *                              front-end; the pose SendPosePacket :225-282 ships)
+ *   ss_stereo_batch_device /   ORB_SLAM3::Frame::ComputeStereoMatches (the stereo Frame constructor; no counterpart in the
+ *   ss_extract_stereo          monocular shim, which only ships th_depth / baseline :59-77)
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
  *   ss_last_error              the cerr diagnostics of the shim (:457-469, :523-551)
  *
@@ -337,6 +339,50 @@ int ss_xchg_broadcast(ss_xchg *x, ss_ctx *ctx, int root, void *d_buf, int64_t by
  * lockstep.  *n_own / *n_peer: the two keypoint counts.  Synchronous. */
 int ss_stereo_exchange_match(ss_ctx *ctx, ss_xchg *x, int peer_rank, int th, int ratio_num, int ratio_den, int32_t *idx,
                              uint16_t *d1, uint16_t *d2, int32_t *n_own, int32_t *n_peer);
+
+/* ---- stereo depth of rectified pairs (ORB-SLAM3 Frame::ComputeStereoMatches, which the stereo Frame constructor runs right
+ * after the two extractions; the reference's shim is monocular, :511 / :594, and ships th_depth / baseline with every
+ * calibration, :59-77, without a reader) -----------------------------------------------------------------------------
+ * Frames 2p (left) and 2p + 1 (right) of the last batch are pair p.  Per left keypoint: Hamming search over the right
+ * keypoints whose row band (+-2 * scale^octave) holds its row, octave +-1, u inside [uL - bf / mb, uL], best < 75; then an
+ * 11 x 11 SAD window slid -5 .. +5 px over the right eye's unblurred pyramid at the left keypoint's octave, a parabola fit
+ * for the sub-pixel right coordinate, depth = bf / disparity; per pair, points whose SAD is >= 1.5 * 1.4 * the median SAD
+ * lose their depth again.  Ties: lowest right index, lowest shift.  Two deviations from upstream: a SAD window that would
+ * leave the level image rejects the point (upstream would read outside it), and a pair without an accepted point is left
+ * alone (upstream indexes an empty vector).  Input is assumed rectified: distortion coefficients are ignored, as upstream
+ * ignores them here (it uses mvKeys).  Upstream's stereo constructor extracts both eyes with lapping area {0, 0}: that is
+ * the stereo setting of ss_orb_params; the outputs are indexed by left keypoint row, so any lapping works. */
+typedef struct {
+    float fx, baseline, th_depth; /* Camera.fx, Stereo.b (metres; bf = baseline * fx), Stereo.ThDepth */
+} ss_stereo_params;
+typedef struct {          /* 16 bytes, one per LEFT keypoint row */
+    float u_right;        /* mvuRight: -1 = none */
+    float depth;          /* mvDepth:  -1 = none */
+    int32_t right_idx;    /* the search's best right keypoint if its distance is < 75, else -1; kept when refinement or the median cut reject */
+    uint16_t orb_dist;    /* that distance, 0xFFFF when right_idx < 0 */
+    uint16_t sad;         /* best SAD once the 11 sums were formed (kept when later tests or the median cut reject), else 0xFFFF */
+} ss_stereo_point;
+typedef struct {          /* 32 bytes, one per pair */
+    int32_t status;       /* SS_OK, or the ss_status that voided the pair (frame_error of an eye; all its points are "none") */
+    int32_t n_left, n_right;
+    int32_t n_matched;    /* right_idx >= 0 */
+    int32_t n_refined;    /* points with a depth before the median cut */
+    int32_t n_depth;      /* depth > 0 after it */
+    int32_t n_close;      /* 0 < depth < (bf * th_depth) / fx  (Tracking's mThDepth) */
+    int32_t sad_median;   /* -1 when no point was refined */
+} ss_stereo_summary;
+/* Pairs (2p, 2p + 1) of the last ss_extract_batch_device batch; n_frames must be even (else SS_ERR_INVALID_ARG).
+ * d_points: device [n_frames / 2][kp_capacity] ss_stereo_point (rows >= n_left are "none"), d_summary: device [n_frames / 2]
+ * ss_stereo_summary.  fx <= 0, baseline <= 0 or a non-finite value: SS_ERR_INVALID_ARG.  Asynchronous on the context's
+ * stream; a batch whose level 0 was read in place needs the caller's pixel buffer untouched until this has run. */
+int ss_stereo_batch_device(ss_ctx *ctx, const ss_stereo_params *p, void *d_points, void *d_summary);
+/* Host pixels of one rectified pair in, both eyes' features and the left eye's stereo points (n_keypoints of out_left
+ * entries) out; synchronous.  fx / baseline / th_depth are those of camera_id's own calibration (SS_ERR_NOT_CALIBRATED
+ * without one, SS_ERR_INVALID_ARG for baseline <= 0 or a context created with max_batch < 2); pixels as in ss_extract.
+ * The result arrays are owned by the context until the next call on it. */
+int ss_extract_stereo(ss_ctx *ctx, int camera_id, const uint8_t *left, const uint8_t *right, int width, int height,
+                      int channels, int row_stride, double timestamp, ss_frame_result *out_left,
+                      ss_frame_result *out_right, const ss_stereo_point **points, ss_stereo_summary *summary);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -129,6 +130,17 @@ struct ss_ctx {
     std::vector<ss_keypoint> h_kps;
     std::vector<uint8_t> h_desc;
     std::vector<int32_t> h_err;
+    /* ss_extract_stereo: the right eye's host arrays (the left eye uses the set above), the points, their device buffers */
+    std::vector<ss_keypoint> h_kps_r;
+    std::vector<uint8_t> h_desc_r;
+    std::vector<ss_stereo_point> h_stereo;
+    uint8_t *d_stereo = nullptr;
+    size_t d_stereo_bytes = 0;
+    /* test hook, SENDSLAM_TEST_STEREO_FLAG=frame,...: the stereo stages see those frames of a batch as flagged (frame_error
+     * SS_ERR_OVERFLOW, through a copy of the array), the only way to reach the voided-pair rule without overflowing a capacity */
+    std::vector<int> stereo_test_flagged;
+    int32_t *d_stereo_err = nullptr;
+    size_t d_stereo_err_bytes = 0;
 
     int last_n_frames = 0;
     ss_lvl0 last_lvl0; /* where level 0 of the last batch lives (ptr == NULL: in the pyramid block) */
@@ -529,6 +541,14 @@ int ss_create(int device_ordinal, const ss_orb_params *params, ss_ctx **out)
     if (const char *e = getenv("SENDSLAM_FORCE_INGEST")) c->force_ingest = atoi(e) != 0;
     if (const char *e = getenv("SENDSLAM_TRACK_TIMING")) c->track_timing = atoi(e) != 0;
     if (const char *e = getenv("SENDSLAM_MATCH_PACKED")) c->no_desc_x = atoi(e) != 0;
+    if (const char *e = getenv("SENDSLAM_TEST_STEREO_FLAG"))
+        for (const char *q = e; *q;) {
+            char *end = nullptr;
+            const long f = strtol(q, &end, 10);
+            if (end == q) break;
+            c->stereo_test_flagged.push_back((int)f);
+            q = *end == ',' ? end + 1 : end;
+        }
 #ifdef SS_TIMING_KNOBS
     if (const char *e = getenv("SENDSLAM_SKIP_STAGES")) c->skip_stages = atoi(e);
     if (const char *e = getenv("SENDSLAM_SKIP_AFTER")) c->skip_after = atoi(e);
@@ -563,6 +583,8 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_tx);
     dev_free(c->d_train_src);
     dev_free(c->d_carry_x);
+    dev_free(c->d_stereo);
+    dev_free(c->d_stereo_err);
     if (c->h_train_src) (void)hipHostFree(c->h_train_src);
     if (c->train_src_copied) (void)hipEventDestroy(c->train_src_copied);
     for (cam_track &ct : c->cams) {
@@ -1293,6 +1315,138 @@ int ss_stereo_exchange_match(ss_ctx *c, ss_xchg *x, int peer_rank, int th, int r
     if (rc != SS_OK) return fail(c, rc, std::string("ss_stereo_exchange_match: ") + ss_xchg_last_error(x));
     if (n_own) *n_own = counts[0];
     if (n_peer) *n_peer = counts[1];
+    return SS_OK;
+}
+
+static int stereo_check_params(ss_ctx *c, const ss_stereo_params *p)
+{
+    if (!p) return fail(c, SS_ERR_INVALID_ARG, "stereo: params is NULL");
+    if (!std::isfinite(p->fx) || !std::isfinite(p->baseline) || !std::isfinite(p->th_depth))
+        return fail(c, SS_ERR_INVALID_ARG, "stereo: fx, baseline and th_depth must be finite");
+    if (!(p->fx > 0.0f)) return fail(c, SS_ERR_INVALID_ARG, "stereo: fx must be > 0");
+    if (!(p->baseline > 0.0f)) return fail(c, SS_ERR_INVALID_ARG, "stereo: baseline must be > 0 (a monocular calibration has no depth)");
+    return SS_OK;
+}
+
+int ss_stereo_batch_device(ss_ctx *c, const ss_stereo_params *p, void *d_points, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->have_geom || c->last_n_frames <= 0) return fail(c, SS_ERR_STATE, "ss_stereo_batch_device: no batch has been extracted");
+    int rc = stereo_check_params(c, p);
+    if (rc != SS_OK) return rc;
+    if (!d_points || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "ss_stereo_batch_device: NULL output buffer");
+    if (c->last_n_frames % 2 != 0)
+        return fail(c, SS_ERR_INVALID_ARG, "ss_stereo_batch_device: the last batch has " + std::to_string(c->last_n_frames) +
+                                               " frames; stereo pairs are frames (2p, 2p + 1) of an even batch");
+    const ss_geom &g = c->hg;
+    const int n_pairs = c->last_n_frames / 2;
+    /* ComputeStereoMatches' constants, one single-precision operation each: mbf, mb = mbf / fx, minD = 0, maxD = mbf / minZ
+     * with minZ = mb; Tracking's mThDepth = mbf * ThDepth / fx */
+    const float bf = p->baseline * p->fx;
+    const float mb = bf / p->fx;
+    const float min_d = 0.0f, max_d = bf / mb;
+    const float bt = bf * p->th_depth;
+    const float close_depth = bt / p->fx;
+    const int32_t *frame_error = c->frame_error;
+    if (!c->stereo_test_flagged.empty()) {
+        static const int32_t flagged = SS_ERR_OVERFLOW;
+        rc = grow(c, c->d_stereo_err, c->d_stereo_err_bytes, (size_t)c->last_n_frames * sizeof(int32_t));
+        if (rc != SS_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->d_stereo_err, c->frame_error, (size_t)c->last_n_frames * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+        for (int f : c->stereo_test_flagged)
+            if (f >= 0 && f < c->last_n_frames)
+                HIP_TRY(c, hipMemcpyAsync(c->d_stereo_err + f, &flagged, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        frame_error = c->d_stereo_err;
+    }
+    const int64_t nf = g.n_features;
+    {
+        /* both eyes' keypoints, the left descriptors, ~1 % of the right ones per left keypoint (one row here), the points */
+        stage_timer t(c, "stereo_search", (int64_t)n_pairs * (2 * nf * (int64_t)sizeof(ss_keypoint) + 2 * nf * SS_DESC_BYTES + (int64_t)g.kcap * 16));
+        ssk_stereo_search(c->stream, c->dg, g, c->kps, c->desc, c->n_kp, frame_error, max_d, min_d, d_points, n_pairs);
+    }
+    {
+        /* per left keypoint: 11 rows of 11 (left) and 21 (right) pixels, its keypoint, the point read and written */
+        stage_timer t(c, "stereo_refine", (int64_t)n_pairs * nf * (11 * (11 + 21) + (int64_t)sizeof(ss_keypoint) + 4 + 2 * 16));
+        ssk_stereo_refine(c->stream, c->dg, g, c->kps, c->n_kp, frame_error, c->pyr, c->last_lvl0, bf, max_d, min_d, d_points, n_pairs);
+    }
+    {
+        /* three passes over the points (the second and third mostly hit), one write of the cut ones, the summary */
+        stage_timer t(c, "stereo_cut", (int64_t)n_pairs * (nf * 16 * 2 + 32));
+        ssk_stereo_cut(c->stream, c->dg, c->n_kp, frame_error, close_depth, d_points, d_summary, n_pairs);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_extract_stereo(ss_ctx *c, int camera_id, const uint8_t *left, const uint8_t *right, int width, int height, int channels,
+                      int row_stride, double timestamp, ss_frame_result *out_left, ss_frame_result *out_right,
+                      const ss_stereo_point **points, ss_stereo_summary *summary)
+{
+    if (!c || !out_left || !out_right || !points || !summary) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (camera_id == 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing camera identifier.");
+    if (!left || !right || width <= 0 || height <= 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing binary image data.");
+    if (channels != 1 && channels != 3 && channels != 4) return fail(c, SS_ERR_BAD_FRAME, "unsupported channel count");
+    if (row_stride < width * channels) return fail(c, SS_ERR_BAD_FRAME, "row_stride smaller than a row");
+    const cam_track *own = find_camera(c, camera_id);
+    if (!own || !own->has_cam)
+        return fail(c, SS_ERR_NOT_CALIBRATED, "ss_extract_stereo: camera " + std::to_string(camera_id) + " has no calibration (fx, baseline, th_depth)");
+    if (c->params.max_batch < 2) return fail(c, SS_ERR_INVALID_ARG, "ss_extract_stereo: the context needs max_batch >= 2 (both eyes are one batch)");
+    ss_stereo_params sp;
+    sp.fx = (float)own->cam.fx;
+    sp.baseline = (float)own->cam.baseline;
+    sp.th_depth = (float)own->cam.th_depth;
+    int rc = stereo_check_params(c, &sp);
+    if (rc != SS_OK) return rc;
+    rc = ensure_geometry(c, width, height);
+    if (rc != SS_OK) return rc;
+    const ss_geom &g = c->hg;
+    const size_t bytes = (size_t)row_stride * (height - 1) + (size_t)width * channels;
+    const size_t alloc = ((size_t)row_stride * height + 15) & ~(size_t)15;
+    rc = grow(c, c->d_in, c->d_in_bytes, 2 * alloc);
+    if (rc == SS_OK) rc = grow(c, c->d_stereo, c->d_stereo_bytes, (size_t)g.kcap * sizeof(ss_stereo_point) + sizeof(ss_stereo_summary));
+    if (rc != SS_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_in, left, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_in + alloc, right, bytes, hipMemcpyHostToDevice, c->stream));
+    rc = run_extract(c, c->d_in, 2, channels, row_stride, (int64_t)alloc, own->cam.rgb != 0);
+    if (rc != SS_OK) return rc;
+    uint8_t *d_sum = c->d_stereo + (size_t)g.kcap * sizeof(ss_stereo_point);
+    rc = ss_stereo_batch_device(c, &sp, c->d_stereo, d_sum);
+    if (rc != SS_OK) return rc;
+    int32_t nk[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(nk, c->n_kp, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_left->level_counts, c->level_counts, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_right->level_counts, c->level_counts + SS_MAX_LEVELS, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(summary, d_sum, sizeof(ss_stereo_summary), hipMemcpyDeviceToHost, c->stream));
+    rc = check_frame_errors(c); /* synchronises */
+    if (rc != SS_OK) return rc;
+    const int kcap = g.kcap;
+    c->h_kps.resize((size_t)std::max(nk[0], 1));
+    c->h_desc.resize((size_t)std::max(nk[0], 1) * SS_DESC_BYTES);
+    c->h_stereo.resize((size_t)std::max(nk[0], 1));
+    c->h_kps_r.resize((size_t)std::max(nk[1], 1));
+    c->h_desc_r.resize((size_t)std::max(nk[1], 1) * SS_DESC_BYTES);
+    if (nk[0] > 0) {
+        HIP_TRY(c, hipMemcpyAsync(c->h_kps.data(), c->kps, (size_t)nk[0] * sizeof(ss_keypoint), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->h_desc.data(), c->desc, (size_t)nk[0] * SS_DESC_BYTES, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->h_stereo.data(), c->d_stereo, (size_t)nk[0] * sizeof(ss_stereo_point), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (nk[1] > 0) {
+        HIP_TRY(c, hipMemcpyAsync(c->h_kps_r.data(), c->kps + kcap, (size_t)nk[1] * sizeof(ss_keypoint), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->h_desc_r.data(), c->desc + (size_t)kcap * SS_DESC_BYTES, (size_t)nk[1] * SS_DESC_BYTES, hipMemcpyDeviceToHost,
+                                  c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    out_left->n_keypoints = nk[0];
+    out_right->n_keypoints = nk[1];
+    out_left->camera_id = out_right->camera_id = camera_id;
+    out_left->timestamp = out_right->timestamp = timestamp;
+    out_left->keypoints = c->h_kps.data();
+    out_left->descriptors = c->h_desc.data();
+    out_right->keypoints = c->h_kps_r.data();
+    out_right->descriptors = c->h_desc_r.data();
+    *points = c->h_stereo.data();
     return SS_OK;
 }
 

@@ -102,6 +102,15 @@ int ssk_match_x_batch_chunks(int rows_q, int rows_t, int n_frames, int *chunk_le
 void ssk_match_x_single(hipStream_t s, const uint8_t *query_x, int nq, const uint8_t *train_x, int nt, int chunk_len, int n_chunks,
                         int exclude_self, int th, int rnum, int rden, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2,
                         const uint8_t *query_p = nullptr, const uint8_t *train_p = nullptr);
+/* ss_stereo.hip: stereo depth of the pairs (2p, 2p + 1) of a batch; points [n_pairs][kcap] ss_stereo_point, summary [n_pairs]
+ * ss_stereo_summary.  search writes every row (right_idx / orb_dist or "none"), refine fills sad / u_right / depth of the
+ * matched rows from the unblurred pyramids, cut applies the median test and writes the summaries */
+void ssk_stereo_search(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const ss_keypoint *kps, const uint8_t *desc, const int32_t *n_kp,
+                       const int32_t *frame_error, float max_d, float min_d, void *points, int n_pairs);
+void ssk_stereo_refine(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const ss_keypoint *kps, const int32_t *n_kp, const int32_t *frame_error,
+                       const uint8_t *pyr, const ss_lvl0 &l0, float bf, float max_d, float min_d, void *points, int n_pairs);
+void ssk_stereo_cut(hipStream_t s, const ss_geom *dg, const int32_t *n_kp, const int32_t *frame_error, float close_depth, void *points, void *summary,
+                    int n_pairs);
 /* test hook: run the device std::sort restatement on n <= 2048 items (size << 32 | UL.x << 20 | id) */
 int ssk_debug_sort(hipStream_t s, uint64_t *d_items, int n);
 #define SSK_MATCH_PARTIAL_BYTES 8

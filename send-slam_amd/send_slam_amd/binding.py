@@ -34,7 +34,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_pipe_submit_frames", "ss_pipe_wait", "ss_pipe_poll", "ss_pipe_release", "ss_pipe_in_flight",
            "ss_match_fold_strided_device", "ss_xchg_create", "ss_xchg_destroy", "ss_xchg_last_error", "ss_xchg_status",
            "ss_xchg_allgather", "ss_xchg_broadcast", "ss_pipe_debug_inject_failure", "ss_stereo_exchange_match",
-           "ss_match_batch_sources_device", "ss_track_detach", "ss_pipe_match_sources"]
+           "ss_match_batch_sources_device", "ss_track_detach", "ss_pipe_match_sources", "ss_stereo_batch_device",
+           "ss_extract_stereo"]
 
 
 class OrbParams(C.Structure):
@@ -94,6 +95,20 @@ class PipeResult(C.Structure):
 
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4")])
+
+
+class StereoParams(C.Structure):
+    _fields_ = [("fx", C.c_float), ("baseline", C.c_float), ("th_depth", C.c_float)]
+
+
+class StereoSummary(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_left", C.c_int32), ("n_right", C.c_int32), ("n_matched", C.c_int32),
+                ("n_refined", C.c_int32), ("n_depth", C.c_int32), ("n_close", C.c_int32), ("sad_median", C.c_int32)]
+
+
+# ss_stereo_point: one per left keypoint row
+STEREO_POINT_DTYPE = np.dtype([("u_right", "<f4"), ("depth", "<f4"), ("right_idx", "<i4"), ("orb_dist", "<u2"), ("sad", "<u2")])
+STEREO_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n, _ in StereoSummary._fields_])
 
 
 class OrbError(RuntimeError):
@@ -183,6 +198,9 @@ def load():
     lib.ss_xchg_broadcast.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
     lib.ss_stereo_exchange_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.ss_stereo_batch_device.argtypes = [C.c_void_p, C.POINTER(StereoParams), C.c_void_p, C.c_void_p]
+    lib.ss_extract_stereo.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                      C.POINTER(FrameResult), C.POINTER(FrameResult), C.POINTER(C.c_void_p), C.POINTER(StereoSummary)]
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -412,6 +430,40 @@ class OrbContext:
         """the fold on parts part_stride_bytes apart: the layout Exchange.allgather leaves"""
         self._check(self._lib.ss_match_fold_strided_device(self._h, C.c_void_p(d_parts), n_parts, part_stride_bytes, nq, th, ratio_num,
                                                            ratio_den, C.c_void_p(d_idx), C.c_void_p(d_d1), C.c_void_p(d_d2)))
+
+    # ---- stereo depth of rectified pairs (frames 2p = left, 2p + 1 = right) ----
+    def stereo_batch_device(self, d_points: int, d_summary: int, fx: float, baseline: float, th_depth: float = 35.0):
+        """ss_stereo_batch_device on the last batch: d_points [n_frames / 2][kp_capacity] STEREO_POINT_DTYPE rows and
+        d_summary [n_frames / 2] STEREO_SUMMARY_DTYPE rows, both device memory; asynchronous."""
+        sp = StereoParams(fx=fx, baseline=baseline, th_depth=th_depth)
+        self._check(self._lib.ss_stereo_batch_device(self._h, C.byref(sp), C.c_void_p(d_points), C.c_void_p(d_summary)))
+
+    def extract_stereo(self, left: np.ndarray, right: np.ndarray, camera_id: int = 1, timestamp: float = 0.0):
+        """One rectified pair (same shape, (H, W) or (H, W, C) uint8) -> (kpsL, descL, kpsR, descR, points, summary):
+        points is STEREO_POINT_DTYPE[len(kpsL)], summary a dict of the ss_stereo_summary fields.  Needs the calibration
+        of camera_id (fx, baseline, th_depth) and a context created with max_batch >= 2."""
+        left = np.ascontiguousarray(left, dtype=np.uint8)
+        right = np.ascontiguousarray(right, dtype=np.uint8)
+        if left.shape != right.shape:
+            raise ValueError(f"the two eyes differ in shape: {left.shape} and {right.shape}")
+        h, w = left.shape[:2]
+        ch = 1 if left.ndim == 2 else left.shape[2]
+        rl, rr, pts, summ = FrameResult(), FrameResult(), C.c_void_p(), StereoSummary()
+        self._check(self._lib.ss_extract_stereo(self._h, int(camera_id), left.ctypes.data, right.ctypes.data, w, h, ch, w * ch,
+                                                float(timestamp), C.byref(rl), C.byref(rr), C.byref(pts), C.byref(summ)))
+        out = []
+        for res in (rl, rr):
+            n = res.n_keypoints
+            kps = np.empty(n, KP_DTYPE)
+            desc = np.empty((n, 32), np.uint8)
+            if n:
+                C.memmove(kps.ctypes.data, res.keypoints, n * KP_DTYPE.itemsize)
+                C.memmove(desc.ctypes.data, res.descriptors, n * 32)
+            out += [kps, desc]
+        points = np.empty(rl.n_keypoints, STEREO_POINT_DTYPE)
+        if rl.n_keypoints:
+            C.memmove(points.ctypes.data, pts.value, rl.n_keypoints * STEREO_POINT_DTYPE.itemsize)
+        return out[0], out[1], out[2], out[3], points, {n: getattr(summ, n) for n, _ in StereoSummary._fields_}
 
     def wait_stream(self, hip_stream: int):
         """Orders this context's stream after everything enqueued so far on another stream of the device."""

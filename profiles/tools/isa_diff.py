@@ -63,7 +63,7 @@ def main():
     same = differ = 0
     matched = set()
     for n in after:
-        o = old_name(da[n])
+        o = da[n] if da[n] in by_old else old_name(da[n])  # both builds have the table form: the name is unchanged
         if o not in by_old:
             print(f"new   {da[n][:140]}")
             continue

@@ -17,7 +17,8 @@ shape = "1280x720_n2000"
 here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STAGE = {"k_ingest_gray16": "ingest", "k_ingest": "ingest", "k_resize_lds": "resize", "k_fast_score": "fast_blur_nms",
          "k_bucket_gather": "bucket_gather", "k_cells_emit": "cells_emit", "k_quadtree": "quadtree", "k_slots": "slots",
-         "k_orient_describe": "orient_describe", "k_match": "match", "k_match_mfma": "match", "k_match_mfma_x": "match",
+         "k_orient_describe": "orient_describe", "k_orient_moments": "orient_describe", "k_keypoint_finish": "orient_describe",
+         "k_describe": "orient_describe", "k_match": "match", "k_match_mfma": "match", "k_match_mfma_x": "match",
          "k_match_stream": "match_stream"}
 
 
@@ -88,8 +89,11 @@ tj_path = os.path.join(here, "traffic.json")
 tj = json.load(open(tj_path)) if os.path.exists(tj_path) else {}
 if "k_match_stream" in sf and "k_match_stream" in sw:
     tj["k_match_stream@20M_rows"] = int((2 * sf["k_match_stream"][0]["FETCH_SIZE"] + sw["k_match_stream"][0]["WRITE_SIZE"]) * 1024)
+by_stage = collections.defaultdict(int)  # a stage of several kernels (orient_describe: three) is their sum
 for n, v in traffic.items():
-    tj[f"{STAGE[n]}@batch{batch}_{shape}"] = v
+    by_stage[STAGE[n]] += v
+for st, v in by_stage.items():
+    tj[f"{st}@batch{batch}_{shape}"] = v
 json.dump(tj, open(tj_path, "w"), indent=1)
 
 for src, dst in ((f"{tag}_prof4", f"{tag}_bench_kernel_stats.csv"), (f"{tag}_prof1", f"{tag}_bench_kernel_stats_1ctx.csv"),

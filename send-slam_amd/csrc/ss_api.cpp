@@ -105,6 +105,7 @@ struct ss_ctx {
     uint32_t *sel = nullptr;
     ss_level_state *state = nullptr;
     uint32_t *kp_ref = nullptr;
+    void *od_moments = nullptr, *od_steer = nullptr; /* per slot, between the launches of ssk_orient_describe: (m10, m01), (sin, cos) */
     int32_t *n_kp = nullptr, *level_counts = nullptr, *frame_error = nullptr;
     ss_keypoint *kps = nullptr;
     uint8_t *desc = nullptr;
@@ -258,6 +259,8 @@ void free_geometry_buffers(ss_ctx *c)
     dev_free(c->sel);
     dev_free(c->state);
     dev_free(c->kp_ref);
+    dev_free(c->od_moments);
+    dev_free(c->od_steer);
     dev_free(c->n_kp);
     dev_free(c->level_counts);
     dev_free(c->frame_error);
@@ -316,6 +319,8 @@ int ensure_geometry(ss_ctx *c, int w, int h)
     HIP_TRY(c, hipMalloc((void **)&c->sel, B * g.sel_total * sizeof(uint32_t)));
     HIP_TRY(c, hipMalloc((void **)&c->state, B * SS_MAX_LEVELS * sizeof(ss_level_state)));
     HIP_TRY(c, hipMalloc((void **)&c->kp_ref, B * g.kcap * 2 * sizeof(uint32_t))); /* (reference, record) per output slot */
+    HIP_TRY(c, hipMalloc(&c->od_moments, B * g.kcap * 8));
+    HIP_TRY(c, hipMalloc(&c->od_steer, B * g.kcap * 8));
     HIP_TRY(c, hipMalloc((void **)&c->n_kp, B * sizeof(int32_t)));
     HIP_TRY(c, hipMalloc((void **)&c->level_counts, B * SS_MAX_LEVELS * sizeof(int32_t)));
     HIP_TRY(c, hipMalloc((void **)&c->frame_error, B * sizeof(int32_t)));
@@ -409,7 +414,7 @@ int run_extract(ss_ctx *c, const void *d_pix, int n, int channels, int64_t row_s
     }
     if (!(skip_mask & 2)) {
         stage_timer t(c, "orient_describe", (int64_t)n * g.n_features * (709 + 512 + 32 + 24));
-        ssk_orient_describe(s, c->dg, g, c->pyr, c->blur, c->sel, c->kp_ref, c->n_kp, c->kps, c->desc, n, l0, c->params.steer_fma != 0, c->desc_x);
+        ssk_orient_describe(s, c->dg, g, c->pyr, c->blur, c->sel, c->kp_ref, c->n_kp, c->kps, c->desc, n, l0, c->params.steer_fma != 0, c->desc_x, c->od_moments, c->od_steer);
     }
     HIP_TRY(c, hipGetLastError());
     c->last_n_frames = n;

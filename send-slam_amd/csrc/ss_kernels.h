@@ -43,7 +43,9 @@ void ssk_slots(hipStream_t s, const ss_geom *dg, const uint32_t *sel, const ss_l
                int32_t *n_kp, int32_t *level_counts, int32_t *frame_error, int n_frames);
 void ssk_orient_describe(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const uint8_t *pyr, const uint8_t *blur,
                          const uint32_t *sel, const uint32_t *kp_ref, const int32_t *n_kp, ss_keypoint *kps,
-                         uint8_t *desc, int n_frames, const ss_lvl0 &l0, bool steer_fma, uint8_t *desc_x);
+                         uint8_t *desc, int n_frames, const ss_lvl0 &l0, bool steer_fma, uint8_t *desc_x, void *moments, void *steer);
+/* (moments, steer: [n_frames][kcap] 8-byte words between the three launches: the integer patch moments (m10, m01), then the
+ * float (sin, cos) of the keypoint's angle) */
 
 /* train split so that a launch has >> 256 workgroups and local indices fit 16 bits */
 int ssk_match_chunks(int n_query_max, int n_train_max, int n_frames, int *chunk_len);

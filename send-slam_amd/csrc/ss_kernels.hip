@@ -13,7 +13,8 @@
  *                       compaction into the candidate list (rank of every survivor inside its cell)
  *   K4  k_quadtree      ORBextractor::DistributeOctTree, one 4-wave workgroup per (frame, level)
  *   --  k_slots         ORBextractor::operator() output order (lapping-area rule)
- *   K5/K6b k_orient_describe   IC_Angle + fastAtan2, steered rBRIEF (4 x __ballot -> 256 bits)
+ *   K5/K6b k_orient_moments, k_keypoint_finish, k_describe   IC_Angle moments (wave per keypoint), fastAtan2 + sine / cosine
+ *                              (thread per keypoint), steered rBRIEF (4 x __ballot -> 256 bits); -DOD_SPLIT=0: k_orient_describe
  *   K7  k_match_mfma_x / k_match_mfma / k_match / k_match_stream / k_match_merge*   Hamming best / second best + ratio test
  *
  * Integer / byte work throughout.  Two contractions on the path run on the matrix cores, both exact: the Hamming
@@ -2125,6 +2126,199 @@ __global__ __launch_bounds__(256) void k_orient_describe(const ss_geom *__restri
     }
 }
 
+/* OD_SPLIT: k_orient_describe cut at the two points where a keypoint's data shrinks to a few bytes.  In the one kernel all
+ * 64 lanes of a keypoint's wave evaluate the same fastAtan2 and the same double-precision sine / cosine (a third of its
+ * vector instructions, and its longest stretch without a memory operation in flight).  Split, k_orient_moments leaves
+ * (m10, m01) per keypoint, k_keypoint_finish evaluates the float steps with one THREAD per keypoint (64 keypoints per
+ * wave-instruction) and writes the keypoint record and (sin, cos), k_describe reads the taps.  No barrier, no wave lives
+ * longer than before; the arithmetic is the same functions of ss_float_steps.h, only run by another lane.  0 = the one
+ * kernel above (measurements: DESIGN.md section 11). */
+#ifndef OD_SPLIT
+#define OD_SPLIT (OD_KP == 1 && !OD_SEQ) /* several keypoints per wave are forms of the one kernel */
+#endif
+#ifndef OD_PIN_TAPS
+#define OD_PIN_TAPS 0
+#endif
+#if OD_SPLIT
+
+/* K5, first half: the integer patch moments.  One wave per keypoint, the grid and XCD mapping of k_orient_describe. */
+__global__ __launch_bounds__(256) void k_orient_moments(const ss_geom *__restrict__ g, const uint8_t *__restrict__ pyr,
+                                                        const uint32_t *__restrict__ kp_ref, const int32_t *__restrict__ n_kp,
+                                                        const uint8_t *__restrict__ lvl0, int lvl0_pitch, int64_t lvl0_fs,
+                                                        int2 *__restrict__ moments)
+{
+    const int logical = xcd_remap((int)(blockIdx.y * gridDim.x + blockIdx.x), (int)(gridDim.x * gridDim.y));
+    const int frame = logical / (int)gridDim.x;
+    const int slot = rfl((logical - frame * (int)gridDim.x) * 4 + (int)(threadIdx.x >> 6));
+    if (slot >= n_kp[frame]) return;
+    const int lane = lane_id();
+    const int kcap = g->kcap;
+    __shared__ __attribute__((aligned(16))) uint32_t patch_all[4][31 * 12 + 4]; /* + 4: the last row's masked-off tail read */
+    const uint2 ref = ((const uint2 *)kp_ref)[(size_t)frame * kcap + slot];
+    const uint4 icm = ((const uint4 *)g->ic_mask)[lane];
+    const int u0 = g->ic_u0[lane];
+    const int level = rfl((int)(ref.x >> 16));
+    const ss_level &L = g->lv[level];
+    const uint32_t rec = (uint32_t)rfl((int)ref.y);
+    const int kx = SS_PX(rec), ky = SS_PY(rec);
+    const int px0 = (kx - SS_HALF_PATCH) & ~15; /* >= 0: keypoints stay 19 px inside the level */
+    const bool inplace = level == 0 && lvl0 != nullptr; /* level 0 lives in the caller's buffer */
+    const int ipitch = inplace ? lvl0_pitch : L.pitch;
+    const uint8_t *p0 = (inplace ? lvl0 + (int64_t)frame * lvl0_fs : pyr + ((size_t)frame * g->block_bytes + L.off)) +
+                        (size_t)(ky - SS_HALF_PATCH) * ipitch + px0;
+    uint4 *pl = (uint4 *)&patch_all[threadIdx.x >> 6][0];
+    uint4 pv[2];
+#pragma unroll
+    for (int it = 0; it < 2; it++) { /* 31 rows x 3 pieces = 93 */
+        const int idx = lane + WAVE * it;
+        const int r = idx / 3, c = idx - r * 3;
+        pv[it] = idx < 31 * 3 ? *(const uint4 *)(p0 + (__umul24((uint32_t)r, (uint32_t)ipitch) + 16u * (uint32_t)c)) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int it = 0; it < 2; it++)
+        if (lane + WAVE * it < 31 * 3) pl[lane + WAVE * it] = pv[it];
+    wave_sync();
+    /* as in k_orient_describe: 16 consecutive bytes of the lane's staged row from u0, eight v_dot4_u32_u8 */
+    const int row = imin(lane & 31, 30); /* lanes 31 and 63 carry zero masks */
+    const int sb = (kx - px0) + u0;      /* 0 .. 30: byte offset in the staged row */
+    const uint32_t *rw = &patch_all[threadIdx.x >> 6][row * 12 + (sb >> 2)];
+    const uint32_t sh = (uint32_t)sb & 3u;
+    const uint32_t w0 = rw[0], w1 = rw[1], w2 = rw[2], w3 = rw[3], w4 = rw[4];
+    const uint32_t a0 = __builtin_amdgcn_alignbyte(w1, w0, sh) & icm.x, a1 = __builtin_amdgcn_alignbyte(w2, w1, sh) & icm.y;
+    const uint32_t a2 = __builtin_amdgcn_alignbyte(w3, w2, sh) & icm.z, a3 = __builtin_amdgcn_alignbyte(w4, w3, sh) & icm.w;
+    const uint32_t rs = __builtin_amdgcn_udot4(a0, 0x01010101u, __builtin_amdgcn_udot4(a1, 0x01010101u,
+                        __builtin_amdgcn_udot4(a2, 0x01010101u, __builtin_amdgcn_udot4(a3, 0x01010101u, 0u, false), false), false), false);
+    const uint32_t ws = __builtin_amdgcn_udot4(a0, 0x03020100u, __builtin_amdgcn_udot4(a1, 0x07060504u,
+                        __builtin_amdgcn_udot4(a2, 0x0B0A0908u, __builtin_amdgcn_udot4(a3, 0x0F0E0D0Cu, 0u, false), false), false), false);
+    const int m10 = wave_sum(__mul24(u0, (int)rs) + (int)ws);
+    const int m01 = wave_sum(__mul24((lane & 31) - SS_HALF_PATCH, (int)rs));
+    if (lane == 0) moments[(size_t)frame * kcap + slot] = make_int2(m10, m01);
+}
+
+/* K5, second half: one thread per keypoint.  fastAtan2 of the moments, the sine / cosine the descriptor is steered by, and the
+ * complete keypoint record.  gridDim.x * 64 = kcap threads per frame; slots >= n_kp[frame] are left alone. */
+__global__ __launch_bounds__(64) void k_keypoint_finish(const ss_geom *__restrict__ g, const uint32_t *__restrict__ kp_ref,
+                                                        const int32_t *__restrict__ n_kp, const int2 *__restrict__ moments,
+                                                        ss_keypoint *__restrict__ kps, float2 *__restrict__ steer)
+{
+    const int frame = blockIdx.y, slot = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (slot >= n_kp[frame]) return;
+    const size_t at = (size_t)frame * g->kcap + slot;
+    const uint2 ref = ((const uint2 *)kp_ref)[at];
+    const int2 m = moments[at];
+    const int level = (int)(ref.x >> 16);
+    const ss_level &L = g->lv[level];
+    ss_keypoint kp;
+    kp.x = (float)SS_PX(ref.y);
+    kp.y = (float)SS_PY(ref.y);
+    if (level != 0) {
+        kp.x = __fmul_rn(kp.x, L.scale);
+        kp.y = __fmul_rn(kp.y, L.scale);
+    }
+    kp.size = (float)L.scaled_patch;
+    kp.angle = ss_fast_atan2((float)m.y, (float)m.x);
+    kp.response = (float)SS_PR(ref.y);
+    kp.octave = level;
+    float sin_v, cos_v;
+    ss_sincosf_deg(kp.angle, &sin_v, &cos_v);
+    kps[at] = kp;
+    steer[at] = make_float2(sin_v, cos_v);
+}
+
+/* K6b: steered rBRIEF.  One wave per keypoint, the grid and XCD mapping of k_orient_describe.  The window does not depend on
+ * the angle: its loads are issued first; the lane's eight tap offsets need only the sine, the cosine, the pattern word and
+ * kx - wx0, all known before the window arrives. */
+template <bool STEER_FMA>
+__global__ __launch_bounds__(256) void k_describe(const ss_geom *__restrict__ g, const uint8_t *__restrict__ blur,
+                                                  const uint32_t *__restrict__ kp_ref, const int32_t *__restrict__ n_kp,
+                                                  const float2 *__restrict__ steer, uint8_t *__restrict__ desc,
+                                                  uint8_t *__restrict__ desc_x)
+{
+    const int logical = xcd_remap((int)(blockIdx.y * gridDim.x + blockIdx.x), (int)(gridDim.x * gridDim.y));
+    const int frame = logical / (int)gridDim.x;
+    const int slot = rfl((logical - frame * (int)gridDim.x) * 4 + (int)(threadIdx.x >> 6));
+    if (slot >= n_kp[frame]) return;
+    const int lane = lane_id();
+    const int kcap = g->kcap;
+    /* window rows at an OD_PITCH-byte pitch, as in k_orient_describe */
+    __shared__ __attribute__((aligned(16))) uint32_t win_all[4][37 * (OD_PITCH / 4)];
+    const uint2 ref = ((const uint2 *)kp_ref)[(size_t)frame * kcap + slot];
+    const float2 sc = steer[(size_t)frame * kcap + slot];
+    const uint4 pat4 = ((const uint4 *)g->pat4)[lane];
+    const uint32_t pat[4] = {pat4.x, pat4.y, pat4.z, pat4.w};
+    const ss_level &L = g->lv[rfl((int)(ref.x >> 16))];
+    const uint32_t rec = (uint32_t)rfl((int)ref.y);
+    const int kx = SS_PX(rec), ky = SS_PY(rec);
+    const int pitch = L.pitch;
+    const int wx0 = (kx - 18) & ~15;
+    const uint8_t *b0 = blur + ((size_t)frame * g->block_bytes + L.off) + (size_t)(ky - 18) * pitch + wx0;
+    uint4 wv[3];
+#pragma unroll
+    for (int it = 0; it < 3; it++) { /* 37 rows x 4 pieces = 148 */
+        const int idx = lane + WAVE * it;
+        wv[it] = idx < 37 * 4 ? *(const uint4 *)(b0 + (__umul24((uint32_t)(idx >> 2), (uint32_t)pitch) + 16u * (uint32_t)(idx & 3))) : make_uint4(0, 0, 0, 0);
+    }
+    /* cvRound by the magic-number sum and the biases folded into one wave-uniform constant: see k_orient_describe */
+    constexpr float RN_MAGIC = 8388640.f;
+    constexpr int RN_BIAS = 0x4B000020;
+    const float b = __int_as_float(rfl(__float_as_int(sc.x))), a = __int_as_float(rfl(__float_as_int(sc.y)));
+    const uint32_t kbias = (uint32_t)((18 - 32) * OD_PITCH + (kx - wx0)) - (uint32_t)RN_BIAS;
+    uint32_t off0[4], off1[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const uint32_t pt = pat[q]; /* x0 y0 x1 y1 as int8 */
+        const float x0 = (float)(int8_t)(pt & 0xFF), y0 = (float)(int8_t)((pt >> 8) & 0xFF);
+        const float x1 = (float)(int8_t)((pt >> 16) & 0xFF), y1 = (float)(int8_t)(pt >> 24);
+        const float fr0 = STEER_FMA ? __fmaf_rn(x0, b, __fmul_rn(y0, a)) : __fadd_rn(__fmul_rn(x0, b), __fmul_rn(y0, a));
+        const float fc0 = STEER_FMA ? __fmaf_rn(x0, a, -__fmul_rn(y0, b)) : __fsub_rn(__fmul_rn(x0, a), __fmul_rn(y0, b));
+        const float fr1 = STEER_FMA ? __fmaf_rn(x1, b, __fmul_rn(y1, a)) : __fadd_rn(__fmul_rn(x1, b), __fmul_rn(y1, a));
+        const float fc1 = STEER_FMA ? __fmaf_rn(x1, a, -__fmul_rn(y1, b)) : __fsub_rn(__fmul_rn(x1, a), __fmul_rn(y1, b));
+        const int r0 = __float_as_int(__fadd_rn(fr0, RN_MAGIC));
+        const int c0 = __float_as_int(__fadd_rn(fc0, RN_MAGIC));
+        const int r1 = __float_as_int(__fadd_rn(fr1, RN_MAGIC));
+        const int c1 = __float_as_int(__fadd_rn(fc1, RN_MAGIC));
+        off0[q] = (uint32_t)(__mul24(r0, OD_PITCH) + c0) + kbias;
+        off1[q] = (uint32_t)(__mul24(r1, OD_PITCH) + c1) + kbias;
+    }
+    /* The compiler sinks the arithmetic above to its use, below the wait for the window.  OD_PIN_TAPS=1 pins it here, between the
+     * loads and their wait (7 more vector instructions, 30 registers instead of 24): the same time alone (111.1 against 111.4 us
+     * per 128 frames) and in the pipeline (121.63 k against 121.60 k frames/s, medians of five alternations), so it stays off:
+     * other waves of the CU fill the wait as well as this one's own arithmetic would */
+#if OD_PIN_TAPS
+#pragma unroll
+    for (int q = 0; q < 4; q++) asm volatile("" : "+v"(off0[q]), "+v"(off1[q]) : : "memory");
+#endif
+    uint4 *wl = (uint4 *)&win_all[threadIdx.x >> 6][0];
+#pragma unroll
+    for (int it = 0; it < 3; it++)
+        if (lane + WAVE * it < 37 * 4) wl[((lane + WAVE * it) >> 2) * (OD_PITCH / 16) + ((lane + WAVE * it) & 3)] = wv[it];
+    wave_sync();
+    const uint8_t *center = (const uint8_t *)wl;
+    int t0[4], t1[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        t0[q] = center[off0[q]];
+        t1[q] = center[off1[q]];
+    }
+    uint64_t words[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) words[q] = __ballot(t0[q] < t1[q]);
+    if (desc_x) {
+        /* the matcher's operand row (fp4_of_4bits): lane L writes nibbles 4 L .. 4 L + 3, one coalesced 128-byte store per wave */
+        const uint64_t wsel = lane < 16 ? words[0] : lane < 32 ? words[1] : lane < 48 ? words[2] : words[3];
+        const uint32_t nib = (uint32_t)(wsel >> (4 * (lane & 15))) & 15u;
+        *(uint16_t *)(desc_x + ((size_t)frame * kcap + slot) * SS_X_ROW + 2 * lane) = (uint16_t)fp4_of_4bits(nib);
+    }
+    if (lane == 0) {
+        uint64_t *d = (uint64_t *)(desc + ((size_t)frame * kcap + slot) * SS_DESC_BYTES);
+        d[0] = words[0];
+        d[1] = words[1];
+        d[2] = words[2];
+        d[3] = words[3];
+    }
+}
+#endif /* OD_SPLIT */
+
 /* ------------------------------------------------------------------------------------ */
 /* K7: Hamming best / second best.  Lane = one query descriptor (8 dwords in VGPRs); the   */
 /* train descriptor of an iteration is wave-uniform, so its 8 dwords arrive by scalar      */
@@ -3357,8 +3551,18 @@ void ssk_slots(hipStream_t s, const ss_geom *dg, const uint32_t *sel, const ss_l
 
 void ssk_orient_describe(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const uint8_t *pyr, const uint8_t *blur,
                          const uint32_t *sel, const uint32_t *kp_ref, const int32_t *n_kp, ss_keypoint *kps,
-                         uint8_t *desc, int n_frames, const ss_lvl0 &l0, bool steer_fma, uint8_t *desc_x)
+                         uint8_t *desc, int n_frames, const ss_lvl0 &l0, bool steer_fma, uint8_t *desc_x, void *moments, void *steer)
 {
+#if OD_SPLIT
+    /* kcap is a multiple of 64: kcap / 4 blocks of four waves per frame, kcap / 64 waves of the per-thread kernel */
+    const dim3 grid(hg.kcap / 4, n_frames);
+    hipLaunchKernelGGL(k_orient_moments, grid, dim3(256), 0, s, dg, pyr, kp_ref, n_kp, l0.ptr, l0.pitch, l0.frame_stride, (int2 *)moments);
+    hipLaunchKernelGGL(k_keypoint_finish, dim3(hg.kcap / 64, n_frames), dim3(64), 0, s, dg, kp_ref, n_kp, (const int2 *)moments, kps, (float2 *)steer);
+    if (steer_fma)
+        hipLaunchKernelGGL(k_describe<true>, grid, dim3(256), 0, s, dg, blur, kp_ref, n_kp, (const float2 *)steer, desc, desc_x);
+    else
+        hipLaunchKernelGGL(k_describe<false>, grid, dim3(256), 0, s, dg, blur, kp_ref, n_kp, (const float2 *)steer, desc, desc_x);
+#else
     /* kcap is a multiple of 64: kcap / (4 waves x OD_KP keypoints) blocks per frame */
     if (steer_fma)
         hipLaunchKernelGGL((k_orient_describe<true, OD_KP>), dim3(hg.kcap / (4 * OD_KP), n_frames), dim3(256), 0, s, dg, pyr, blur, sel,
@@ -3366,6 +3570,7 @@ void ssk_orient_describe(hipStream_t s, const ss_geom *dg, const ss_geom &hg, co
     else
         hipLaunchKernelGGL((k_orient_describe<false, OD_KP>), dim3(hg.kcap / (4 * OD_KP), n_frames), dim3(256), 0, s, dg, pyr, blur, sel,
                            kp_ref, n_kp, kps, desc, l0.ptr, l0.pitch, l0.frame_stride, desc_x);
+#endif
 }
 
 /* which form of the matrix-core kernel: a single large database has the chip to itself (NU = 2), batches of frames share it */

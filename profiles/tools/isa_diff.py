@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Kernel-by-kernel comparison of the gfx950 instruction streams of two builds of csrc/ss_kernels.hip.
+"""Kernel-by-kernel comparison of the gfx950 code objects of two builds of csrc/ss_kernels.hip: instruction streams,
+the .rodata section (kernel descriptors, constant tables) and the per-kernel metadata the streams do not show.
 
     hipcc --offload-arch=gfx950 <Makefile CXXFLAGS> --cuda-device-only -c csrc/ss_kernels.hip -o before.co   (parent commit)
     hipcc ... -o after.co                                                                                   (this tree)
@@ -8,8 +9,10 @@
 Runs on a machine without a GPU.  The batch matchers gained a table form through a trailing
 template parameter pack (`typename... TAB`, empty in the existing forms): an instantiation with the empty pack is compared
 with the kernel of the same name and template arguments before; kernels only the new build has are listed.  Branch targets are compared as
-offsets inside their function, so code that moved inside the object still compares equal.  Exit status 1 when an
-instruction stream differs."""
+offsets inside their function, so code that moved inside the object still compares equal.  .rodata is compared byte
+for byte (a kernel descriptor holds the distance to its kernel's code, so it also changes when kernels come, go or change places); of the
+metadata notes, the register counts, LDS, scratch and kernel-argument sizes and the workgroup limit of every kernel.
+Exit status 1 when anything differs."""
 import os
 import re
 import subprocess
@@ -20,12 +23,38 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 
 
-def disassemble(bundle):
+META = (".vgpr_count", ".sgpr_count", ".agpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size",
+        ".kernarg_segment_size", ".max_flat_workgroup_size")
+
+
+def read_object(bundle):
+    """(instruction streams by symbol, .rodata bytes as hex, the META fields by kernel symbol)"""
     with tempfile.TemporaryDirectory() as d:
         elf = os.path.join(d, "k.elf")
         subprocess.check_call([f"{ROCM}/llvm/bin/clang-offload-bundler", "--unbundle", "--type=o", f"--input={bundle}",
                                f"--targets={TARGET}", f"--output={elf}"])
         text = subprocess.check_output([f"{ROCM}/llvm/bin/llvm-objdump", "-d", "--no-show-raw-insn", "--no-leading-addr", elf], text=True)
+        dump = subprocess.check_output([f"{ROCM}/llvm/bin/llvm-objdump", "-s", "-j", ".rodata", elf], text=True)
+        notes = subprocess.check_output([f"{ROCM}/llvm/bin/llvm-readelf", "--notes", elf], text=True)
+    # " ADDR hex hex hex hex  ascii": the bytes without the addresses (where the linker put the section)
+    rodata = "".join("".join(m.group(1).split()) for m in re.finditer(r"^ [0-9a-f]+ ((?:[0-9a-f]+ ){1,4}) ", dump, re.M))
+    meta, entry = {}, None
+    for line in notes.splitlines():
+        m = re.match(r"^  (-| ) (\.\w+):\s*(.*)$", line)  # a key of a kernel's own map: the arguments' keys sit deeper
+        if not m:
+            continue
+        if m.group(1) == "-":
+            entry = {}
+        if entry is None:
+            continue
+        if m.group(2) == ".name":
+            meta[m.group(3)] = entry
+        elif m.group(2) in META:
+            entry[m.group(2)] = m.group(3)
+    return functions(text), rodata, meta
+
+
+def functions(text):
     funcs, name = {}, None
     for line in text.splitlines():
         m = re.match(r"^<(\S+)>:$", line)
@@ -57,10 +86,10 @@ def old_name(dem):
 
 
 def main():
-    before, after = disassemble(sys.argv[1]), disassemble(sys.argv[2])
+    (before, ro_b, meta_b), (after, ro_a, meta_a) = read_object(sys.argv[1]), read_object(sys.argv[2])
     db, da = demangle(list(before)), demangle(list(after))
     by_old = {db[n]: n for n in before}
-    same = differ = 0
+    same = differ = checked = meta_differ = 0
     matched = set()
     for n in after:
         o = da[n] if da[n] in by_old else old_name(da[n])  # both builds have the table form: the name is unchanged
@@ -73,12 +102,20 @@ def main():
         else:
             differ += 1
             print(f"DIFF  {o[:140]}  ({len(before[by_old[o]])} -> {len(after[n])} instructions)")
+        if n in meta_a or by_old[o] in meta_b:  # a kernel (device functions have no metadata)
+            mb, ma = meta_b.get(by_old[o], {}), meta_a.get(n, {})
+            checked += 1
+            if len(ma) != len(META) or ma != mb:
+                meta_differ += 1
+                print(f"META  {o[:140]}  " + ", ".join(f"{k} {mb.get(k)} -> {ma.get(k)}" for k in META if mb.get(k) != ma.get(k)))
     for o in by_old:
         if o not in matched:
             print(f"gone  {o[:140]}")
             differ += 1
     print(f"{same} kernels identical, {differ} differ or are gone")
-    return 1 if differ else 0
+    print(f".rodata: {len(ro_a) // 2} bytes, " + ("identical" if ro_a and ro_a == ro_b else f"DIFFERENT (before: {len(ro_b) // 2} bytes)"))
+    print(f"metadata ({', '.join(k[1:] for k in META)}): {checked - meta_differ} of {checked} kernels identical")
+    return 1 if differ or meta_differ or not checked or not ro_a or ro_a != ro_b else 0
 
 
 if __name__ == "__main__":

@@ -14,13 +14,12 @@
  *   K4  k_quadtree      ORBextractor::DistributeOctTree, one 4-wave workgroup per (frame, level)
  *   --  k_slots         ORBextractor::operator() output order (lapping-area rule)
  *   K5/K6b k_orient_moments, k_keypoint_finish, k_describe   IC_Angle moments (wave per keypoint), fastAtan2 + sine / cosine
- *                              (thread per keypoint), steered rBRIEF (4 x __ballot -> 256 bits); -DOD_SPLIT=0: k_orient_describe
+ *                              (thread per keypoint), steered rBRIEF (4 x __ballot -> 256 bits)
  *   K7  k_match_mfma_x / k_match_mfma / k_match / k_match_stream / k_match_merge*   Hamming best / second best + ratio test
  *
  * Integer / byte work throughout.  Two contractions on the path run on the matrix cores, both exact: the Hamming
  * distance of K7 as a +-1 dot product (FP4 operands in k_match_mfma_x, i8 in k_match_mfma) and
- * the 7 x 7 Gaussian of K6a as two band-matrix products of 16 x 16 x 32 int8 tiles inside k_fast_score (FT_BLUR_MFMA;
- * the vector-pipe form is a compile-time switch).  Nothing else is reshaped into a GEMM.  Every kernel takes the batch slot in blockIdx.y or .z so one launch covers a
+ * the 7 x 7 Gaussian of K6a as two band-matrix products of 16 x 16 x 32 int8 tiles inside k_fast_score.  Nothing else is reshaped into a GEMM.  Every kernel takes the batch slot in blockIdx.y or .z so one launch covers a
  * batch of frames.  Level 0 of the pyramid is read IN PLACE from the caller's buffer when that is a
  * 1-channel image with 16-byte aligned rows (lvl0 != NULL below); otherwise k_ingest writes it into the
  * pyramid block first.
@@ -437,16 +436,7 @@ __global__ __launch_bounds__(256) void k_resize_pair(uint8_t *__restrict__ pyr, 
 /* unordered bucket per cell serves both thresholds: the cell's count word holds the number */
 /* of survivors (low half, = bucket slot allocator) and of those >= iniTh (high half).      */
 /* ------------------------------------------------------------------------------------ */
-#ifndef FT_BLUR_MFMA
-/* 2 (default): both passes of the Gaussian on the matrix pipe (below).  0: on the vector pipe (v_dot4_u32_u8 rows into LDS,
- * v_dot2_u32_u16 columns): 6 % more vector instructions in k_fast_score, 0.3036 against 0.2896 ms per 64 frames alone, 116.9 k
- * against 118.4 k frames/s with four batches in flight (profiles/tools/build_variant.sh valub -DFT_BLUR_MFMA=0).  An earlier
- * form that put only the horizontal pass on the matrix pipe and handed the sums over through LDS measured slower than the
- * vector form. */
-#define FT_BLUR_MFMA 2
-#endif
-#if FT_BLUR_MFMA == 2
-/* 2: BOTH passes of K6a on the matrix pipe, the sums of the first handed to the second in registers (no LDS in between).
+/* BOTH passes of K6a on the matrix pipe, the sums of the first handed to the second in registers (no LDS in between).
  * A wave takes 16 columns of the tile and all 32 rows; v_mfma_i32_16x16x32_i8 throughout (lane = (index & 15, group g = lane >> 4),
  * operand bytes k = 8 g .. 8 g + 7; result registers r = rows 4 g + r of the lane's column).
  *   Horizontal: D1[row][col] = sum_k A[row][k] Bh[k][col] for three blocks of 16 staged rows (blur rows rho = 16 mb + 4 g + r);
@@ -482,7 +472,6 @@ constexpr blur_frag make_blur_v()
 }
 __device__ const blur_frag g_blur_h = make_blur_h(), g_blur_v = make_blur_v();
 static_assert(SS_GAUSS_K0 * 2 + SS_GAUSS_K1 * 2 + SS_GAUSS_K2 * 2 + SS_GAUSS_K3 == 256 && SS_GAUSS_K3 < 128, "taps: int8, sum 256");
-#endif
 
 #define FT_ROWS (SS_TILE_H2 + 8)        /* staged rows: y0 - 4 .. y0 + 35 */
 #define FT_BLUR_ROWS (SS_TILE_H2 + 6)   /* of which the blur uses y0 - 3 .. y0 + 34 */
@@ -506,10 +495,6 @@ __device__ __forceinline__ int reflect101(int p, int n)
 
 
 #define FT_THREADS (8 * SS_TILE_H2)
-#ifndef FT_SKIP
-#define FT_SKIP 0 /* accounting builds only (profiles/tools/fast_accounting.sh; results invalid): 1 halo ring, 2 blur H,
-                   * 4 arc search, 8 NMS, 16 blur V, 32 compass + queue */
-#endif
 __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__restrict__ pyr,
                                                     uint8_t *__restrict__ score,
                                                     const ss_geom *__restrict__ g,
@@ -522,11 +507,6 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
                                                     const uint8_t *__restrict__ lvl0, int lvl0_pitch, int64_t lvl0_fs)
 {
     /* `score` may be NULL: no later kernel reads the response map (it exists for stage-by-stage tests) */
-    /* horizontal Gaussian sums (8 fractional bits, less 32768: int16), packed as (row 2p, row 2p+1) per pixel
-     * so the vertical pass is four v_dot2_i32_i16 per output */
-#if FT_BLUR_MFMA != 2
-    __shared__ __attribute__((aligned(16))) uint32_t hpair[FT_BLUR_ROWS / 2][SS_TILE_W];
-#endif
     /* + 1 row: the blur's A operand of the last row / last 16 columns reads up to 40 bytes past it (against zero taps) */
     __shared__ __attribute__((aligned(16))) uint32_t lds[FT_ROWS + 1][FT_WORDS];
     /* scores of the tile and of its 1-px ring: row ly + 1, byte lx + 4 (tile pixels dword-aligned) */
@@ -550,14 +530,9 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
     const uint8_t *img = inplace ? lvl0 + (int64_t)frame * lvl0_fs : pyr + fb;
     const int ipitch = inplace ? lvl0_pitch : pitch;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-#if defined(FT_EXP) && FT_EXP == 1 /* timing experiment: every interior tile stages the same (cache-hot) pixels */
-#define FT_EXP_HOT 1
-#endif
 
-#if FT_BLUR_MFMA == 2
     /* the blur's two constant operands: requested first, needed last */
     uint2 bh2 = *(const uint2 *)&g_blur_h.w[threadIdx.x & 63][0], bv2 = *(const uint2 *)&g_blur_v.w[threadIdx.x & 63][0];
-#endif
     if (threadIdx.x == 0) { n_list = 0; n_corner = 0; }
     if (threadIdx.x < SS_TS_HDR) s_kcnt[threadIdx.x] = 0;
     static_assert(((SS_TILE_H2 + 2) * FT_OWORDS) % 4 == 0 && ((SS_TILE_H2 + 2) * FT_OWORDS) / 4 <= FT_THREADS, "out_tile is cleared by one 16-byte store per thread");
@@ -581,11 +556,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
     if (interior && x0 >= FT_XB && x0 - FT_XB + 4 * FT_WORDS <= ipitch) {
         /* interior tile (the common case): no reflection; thread t takes 16 bytes: row t / 6, bytes 16 (t % 6) */
         static_assert(FT_ROWS * (FT_WORDS / 4) <= FT_THREADS, "one 16-byte load per thread stages the tile");
-#ifdef FT_EXP_HOT
-        const uint8_t *tile0 = img + (size_t)60 * ipitch + 48;
-#else
         const uint8_t *tile0 = img + (size_t)(y0 - 4) * ipitch + (x0 - FT_XB);
-#endif
         const uint32_t r = __umulhi((uint32_t)threadIdx.x, 0xAAAAAAABu) >> 2, c = (uint32_t)threadIdx.x - 6u * r; /* t / 6 */
         static_assert(FT_WORDS / 4 == 6, "t / 6 above");
         if (r < FT_ROWS) *(uint4 *)&lds[r][4 * c] = *(const uint4 *)(tile0 + (__umul24(r, (uint32_t)ipitch) + 16u * c));
@@ -618,11 +589,9 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
     }
     if (threadIdx.x < SS_TILE_W) xinf[threadIdx.x] = cinf_v;
     else if (threadIdx.x < SS_TILE_W + SS_TILE_H2) yinf[threadIdx.x - SS_TILE_W] = cinf_v;
-#if FT_BLUR_MFMA == 2
     /* pins the two loads above here, where the block waits for its staging loads anyway (left alone the compiler sinks them
      * to their first use, and the blur starts with a trip to the cache) */
     asm volatile("" : "+v"(bh2.x), "+v"(bh2.y), "+v"(bv2.x), "+v"(bv2.y));
-#endif
     __syncthreads();
 
     /* Phase 1, every pixel: the compass test of cv::FAST.  Any 9 contiguous ring pixels contain
@@ -665,7 +634,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
         return __builtin_amdgcn_perm(neg[1], neg[0], 0x07050301u) & 0x80808080u;
     };
 #pragma unroll
-    for (int rr = 0; rr < ((FT_SKIP & 32) ? 0 : 2); rr++) { /* two rows per thread */
+    for (int rr = 0; rr < 2; rr++) { /* two rows per thread */
         const uint32_t signs = compass_row(2 * ty + rr, tx + FT_XW);
         cand_bits |= rr ? signs : signs >> 4;
     }
@@ -710,7 +679,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
      * the row below in wave 1, the columns left and right in wave 2.  The ring's four corner pixels would cost a fourth
      * wave the whole test: they are queued untested (phase 2 scores whatever is queued; the test only spares it work). */
     static_assert(SS_TILE_W == 64 && 2 * SS_TILE_H2 <= 64 * (FT_THREADS / 64 - 2), "ring layout: one wave per row, the columns after them");
-    if (!(FT_SKIP & 1) && threadIdx.x < 2 * SS_TILE_W + 2 * SS_TILE_H2) {
+    if (threadIdx.x < 2 * SS_TILE_W + 2 * SS_TILE_H2) {
         const int i = threadIdx.x;
         int lx, ly;
         if (i < SS_TILE_W) { lx = i; ly = -1; }
@@ -725,56 +694,18 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
             const int dark = v - imax(imin(p0, p8), imin(p4, p12)), bright = imin(imax(p0, p8), imax(p4, p12)) - v;
             if (imax(dark, bright) > min_th) list[atomicAdd(&n_list, 1)] = (uint16_t)(((ly + 1) << 8) | (lx + 1));
         }
-    } else if (!(FT_SKIP & 1) && threadIdx.x >= FT_THREADS - 4) {
+    } else if (threadIdx.x >= FT_THREADS - 4) {
         const int k = (int)threadIdx.x - (FT_THREADS - 4);
         const int lx = (k & 1) ? SS_TILE_W : -1, ly = (k & 2) ? SS_TILE_H2 : -1;
         const int x = x0 + lx, y = y0 + ly;
         if (interior || (x >= 3 && x < w - 3 && y >= 3 && y < h - 3)) list[atomicAdd(&n_list, 1)] = (uint16_t)(((ly + 1) << 8) | (lx + 1));
     }
-#if FT_BLUR_MFMA == 0
-    /* K6a horizontal pass on the same staged tile.  The 7 taps of pixel i of a dword sit at bytes i + 1 .. i + 7 of the
-     * three aligned dwords around it: one v_dot4_u32_u8 per dword that holds any of them, against the taps shifted into
-     * place (zeros elsewhere) -- 2 + 3 + 3 + 2 products for four pixels, no byte funnels */
-    if (!(FT_SKIP & 2)) {
-        constexpr uint32_t K0 = SS_GAUSS_K0, K1 = SS_GAUSS_K1, K2 = SS_GAUSS_K2, K3 = SS_GAUSS_K3;
-        /* pixel 0: bytes 1-3 of w0, 0-3 of w1; pixel 1: 2-3, 0-3, 0; pixel 2: 3, 0-3, 0-1; pixel 3: 0-3, 0-2 */
-        constexpr uint32_t A0 = (K0 << 8) | (K1 << 16) | (K2 << 24), B0 = K3 | (K2 << 8) | (K1 << 16) | (K0 << 24);
-        constexpr uint32_t A1 = (K0 << 16) | (K1 << 24), B1 = K2 | (K3 << 8) | (K2 << 16) | (K1 << 24), C1 = K0;
-        constexpr uint32_t A2 = K0 << 24, B2 = K1 | (K2 << 8) | (K3 << 16) | (K2 << 24), C2 = K1 | (K0 << 8);
-        constexpr uint32_t B3 = K0 | (K1 << 8) | (K2 << 16) | (K3 << 24), C3 = K2 | (K1 << 8) | (K0 << 16);
-        /* one item = four pixels of the two rows of a pair: 20 dot products, ONE 16-byte LDS store */
-#pragma unroll
-        for (int it = 0; it < ((FT_BLUR_ROWS / 2) * 16 + FT_THREADS - 1) / FT_THREADS; it++) {
-            /* the leftovers of the second round go to the LAST wave: the first has the longest way to the barrier */
-            static_assert((FT_BLUR_ROWS / 2) * 16 <= 2 * FT_THREADS, "two rounds");
-            const int idx = it ? 2 * FT_THREADS - 1 - (int)threadIdx.x : (int)threadIdx.x;
-            if (idx >= (FT_BLUR_ROWS / 2) * 16) continue;
-            const int pair = idx >> 4, q = idx & 15; /* blur rows 2 pair, 2 pair + 1 = staged rows + 1 */
-            uint32_t hv[2][4];
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                const uint32_t *lr = &lds[2 * pair + k + 1][FT_XW - 1 + q];
-                const uint32_t w0 = lr[0], w1 = lr[1], w2 = lr[2];
-                hv[k][0] = __builtin_amdgcn_udot4(w0, A0, __builtin_amdgcn_udot4(w1, B0, 0, false), false);
-                hv[k][1] = __builtin_amdgcn_udot4(w0, A1, __builtin_amdgcn_udot4(w1, B1, __builtin_amdgcn_udot4(w2, C1, 0, false), false), false);
-                hv[k][2] = __builtin_amdgcn_udot4(w0, A2, __builtin_amdgcn_udot4(w1, B2, __builtin_amdgcn_udot4(w2, C2, 0, false), false), false);
-                hv[k][3] = __builtin_amdgcn_udot4(w1, B3, __builtin_amdgcn_udot4(w2, C3, 0, false), false);
-            }
-            /* sums stay below 2^16 (255 * 256) */
-            *(uint4 *)&hpair[pair][4 * q] = make_uint4(hv[0][0] | (hv[1][0] << 16), hv[0][1] | (hv[1][1] << 16),
-                                                       hv[0][2] | (hv[1][2] << 16), hv[0][3] | (hv[1][3] << 16));
-        }
-    }
-#endif
     __syncthreads();
 
-    /* K6a vertical pass, two output rows per thread (rows 2ty and 2ty+1 read the same four row
-     * pairs); + 2^15 >> 16 as cv::GaussianBlur's fixed-point path.  The queue of phase 2 rarely reaches the upper half
-     * of the block (a wave per 64 entries): those waves run this pass while the lower half scores, and take the NMS
-     * afterwards, while the lower half runs this pass -- the block's critical path loses one of the two. */
-#if FT_BLUR_MFMA == 2
+    /* K6a, a wave per 16 columns; + 2^15 >> 16 as cv::GaussianBlur's fixed-point path.  The queue of phase 2 rarely reaches
+     * the upper half of the block (a wave per 64 entries): those waves run the blur while the lower half scores, and take the
+     * NMS afterwards, while the lower half runs the blur -- the block's critical path loses one of the two. */
     auto blur_cols = [&](int wv) { /* both passes for columns 16 wv .. 16 wv + 15: see g_blur_h */
-        if (FT_SKIP & 16) return;
         const int lane = lane_id();
         const int i16 = lane & 15, g = lane >> 4;
         const long bh = (long)(((uint64_t)bh2.y << 32) | bh2.x), bv = (long)(((uint64_t)bv2.y << 32) | bv2.x);
@@ -808,48 +739,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
             if (y < h && col < pitch) *(uint32_t *)(blur + fb + (__umul24((uint32_t)y, (uint32_t)pitch) + (uint32_t)col)) = out;
         }
     };
-#ifndef FT_BLUR_SPLIT
-#define FT_BLUR_SPLIT 0 /* 1: the upper half of the block blurs all four column blocks while the lower half runs the arc search:
-                         * measured 0.2905 against 0.2865 ms per 64 frames alone, 117.3 k against 117.9 k frames/s in the pipeline */
-#endif
-    auto blur_v = [&]() {
-        const int wv = rfl((int)(threadIdx.x >> 6));
-        if (FT_BLUR_SPLIT) {
-            if (wv >= 2) {
-                blur_cols(wv);
-                blur_cols(wv - 2);
-            }
-        } else {
-            blur_cols(wv);
-        }
-    };
-#else
-    auto blur_v = [&]() {
-        if (FT_SKIP & 16) return;
-        constexpr uint32_t KA0 = SS_GAUSS_K0 | (SS_GAUSS_K1 << 16), KA1 = SS_GAUSS_K2 | (SS_GAUSS_K3 << 16);
-        constexpr uint32_t KA2 = SS_GAUSS_K2 | (SS_GAUSS_K1 << 16), KA3 = SS_GAUSS_K0;
-        constexpr uint32_t KB0 = (uint32_t)SS_GAUSS_K0 << 16, KB1 = SS_GAUSS_K1 | (SS_GAUSS_K2 << 16);
-        constexpr uint32_t KB2 = SS_GAUSS_K3 | (SS_GAUSS_K2 << 16), KB3 = SS_GAUSS_K1 | (SS_GAUSS_K0 << 16);
-        uint32_t va[4], vb[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const uint32_t p0 = hpair[ty][4 * tx + i], p1 = hpair[ty + 1][4 * tx + i];
-            const uint32_t p2 = hpair[ty + 2][4 * tx + i], p3 = hpair[ty + 3][4 * tx + i];
-            va[i] = dot2_u16(p0, KA0, dot2_u16(p1, KA1, dot2_u16(p2, KA2, dot2_u16(p3, KA3, 32768u))));
-            vb[i] = dot2_u16(p0, KB0, dot2_u16(p1, KB1, dot2_u16(p2, KB2, dot2_u16(p3, KB3, 32768u))));
-        }
-        /* (sum + 2^15) >> 16 is byte 2 of each sum (sums stay below 2^24): three v_perm_b32 gather four of them */
-        const uint32_t out_a = __builtin_amdgcn_perm(va[1], va[0], 0x0C0C0602u) | __builtin_amdgcn_perm(va[3], va[2], 0x06020C0Cu);
-        const uint32_t out_b = __builtin_amdgcn_perm(vb[1], vb[0], 0x0C0C0602u) | __builtin_amdgcn_perm(vb[3], vb[2], 0x06020C0Cu);
-        const int ya = y0 + 2 * ty;
-        if (x0 + 4 * tx < pitch) {
-            /* 24-bit multiply + 32-bit offset (a level is far below 2^32 bytes) instead of a 64-bit v_mad_i64_i32 */
-            const uint32_t o = __umul24((uint32_t)ya, (uint32_t)pitch) + (uint32_t)(x0 + 4 * tx);
-            if (ya < h) *(uint32_t *)(blur + fb + o) = out_a;
-            if (ya + 1 < h) *(uint32_t *)(blur + fb + (o + (uint32_t)pitch)) = out_b;
-        }
-    };
-#endif
+    auto blur_v = [&]() { blur_cols(rfl((int)(threadIdx.x >> 6))); };
     const bool upper_half = threadIdx.x >= FT_THREADS / 2; /* wave-uniform */
     if (upper_half) blur_v();
 
@@ -857,7 +747,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
     constexpr int RDX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
     constexpr int RDY[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
     uint8_t *out8 = (uint8_t *)&out_tile[0][0];
-    const int n = (FT_SKIP & 4) ? 0 : n_list;
+    const int n = n_list;
     for (int e = threadIdx.x; e < n; e += FT_THREADS) {
         const int ly = (int)(list[e] >> 8) - 1, lx = (int)(list[e] & 0xFF) - 1;
         const uint8_t *c = tile8 + (ly + 4) * (FT_WORDS * 4) + FT_XB + lx;
@@ -892,7 +782,7 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
      * joins the sub-list of its cell window (a tile meets at most 3 x 2 of them); its slot comes
      * from an LDS counter, so no global atomic is involved: pass 1 here allots the slots, pass 2
      * (after the blur's vertical pass) knows the sub-list offsets and writes the records. */
-    const int nc = (FT_SKIP & 8) ? 0 : n_corner, ini_th = g->ini_th;
+    const int nc = n_corner, ini_th = g->ini_th;
     const uint32_t tc = tr[9];
     const int col0 = (int)(tc & 0xFFFFu), row0 = (int)(tc >> 16);
     for (int e = (int)((threadIdx.x + FT_THREADS / 2) % FT_THREADS); e < nc; e += FT_THREADS) { /* upper half first */
@@ -1298,9 +1188,7 @@ __device__ __forceinline__ void sort_final_rank(const uint64_t *a, uint64_t *tmp
  * quadtree blocks share CUs with the FAST / match blocks of the other batches in flight, and every KB they hold
  * is a KB those cannot use (block LDS 37 KB -> 17.5 KB: +4 % frames/s, quadtree time unchanged; shrinking the
  * sort buffer as well packs the trees onto fewer CUs and loses it again). */
-#ifndef QT_LDS_NODES
 #define QT_LDS_NODES 64
-#endif
 
 struct qt_ctx {
     /* the ping-pong record buffers as base + b * distance: an array indexed by a node's buffer bit (and a select between two
@@ -1513,9 +1401,7 @@ __device__ __forceinline__ void qt_scatter(const qt_ctx &q, int idx, const qt_di
     if (lane == 0) qt_store_flags(q, idx, d.flags & ~1); /* lNodes.erase */
 }
 
-#ifndef QT_WAVES
 #define QT_WAVES 4
-#endif
 #define QT_THREADS (QT_WAVES * 64)
 
 __global__ __launch_bounds__(QT_THREADS) void k_quadtree(const ss_geom *__restrict__ g, const uint32_t *__restrict__ cand,
@@ -1857,10 +1743,11 @@ __global__ __launch_bounds__(64) void k_slots(const ss_geom *__restrict__ g, con
 }
 
 /* ------------------------------------------------------------------------------------ */
-/* K5 + K6b: one wave per keypoint.  IC_Angle: lanes = 31 rows x 2 halves of the radius-15 */
-/* disc, integer moments reduced across the wave, fastAtan2 restated.  rBRIEF: lane L does */
-/* pairs L, L+64, L+128, L+192; __ballot(t0 < t1) IS descriptor bytes 8k .. 8k+7 (bit i of  */
-/* byte j = test 8j+i).                                                                    */
+/* K5 + K6b: one wave per keypoint, three launches.  IC_Angle: lanes = 31 rows x 2 halves   */
+/* of the radius-15 disc, integer moments reduced across the wave (k_orient_moments), then  */
+/* fastAtan2 restated, one thread per keypoint (k_keypoint_finish).  rBRIEF (k_describe):   */
+/* lane L does pairs L, L+64, L+128, L+192; __ballot(t0 < t1) IS descriptor bytes 8k ..     */
+/* 8k+7 (bit i of byte j = test 8j+i).                                                     */
 /* ------------------------------------------------------------------------------------ */
 static_assert(offsetof(ss_geom, ic_mask) % 16 == 0 && offsetof(ss_geom, pat4) % 16 == 0, "ic_mask and pat4 are loaded as dwordx4");
 
@@ -1881,272 +1768,31 @@ __device__ __forceinline__ uint32_t fp4_of_4bits(uint32_t nib)
  * products and one sum, each rounded (the C expression as written); true = what GCC's FMA contraction makes of it
  * when upstream is built -O3 -march=native (CMakeLists.txt:10-13): the FIRST product fused into the sum,
  * fma(x, b, y*a) and fma(x, a, -(y*b)).  Which one the reference binary runs is machine- and compiler-dependent and
- * unpinned (tests/golden/ref_dump/README.md); both are implemented and tested against the oracle's two forms.
- * KP keypoints per wave, side by side: a keypoint is a chain of dependent memory round trips (reference record ->
- * level geometry -> patch + window -> LDS) with little arithmetic in between, so a wave that walks two chains at once
- * keeps twice the bytes in flight for the same lifetime (the loads of both are issued together, stage by stage). */
-#ifndef OD_KP
-#define OD_KP 1 /* measured in the four-context pipeline: 1 -> 93.5-95.4 k frames/s, 2 -> 92.5 k (twice the LDS per block) */
-#endif
-#ifndef OD_SEQ
-#define OD_SEQ 0 /* 1 with OD_KP = 2 or 4: bit-exact, fewer vector instructions, 113.2 k against 117.8 k frames/s in the pipeline */
-#endif
-#ifndef OD_PITCH
-#define OD_PITCH 80
-#endif
-template <bool STEER_FMA, int KP>
-__global__ __launch_bounds__(256) void k_orient_describe(const ss_geom *__restrict__ g, const uint8_t *__restrict__ pyr,
-                                                         const uint8_t *__restrict__ blur,
-                                                         const uint32_t *__restrict__ sel,
-                                                         const uint32_t *__restrict__ kp_ref,
-                                                         const int32_t *__restrict__ n_kp,
-                                                         ss_keypoint *__restrict__ kps, uint8_t *__restrict__ desc,
-                                                         const uint8_t *__restrict__ lvl0, int lvl0_pitch, int64_t lvl0_fs,
-                                                         uint8_t *__restrict__ desc_x)
-{
-    /* all blocks of a frame on one XCD: keypoints whose patches share 64-B lines then share an L2 */
-    const int logical = xcd_remap((int)(blockIdx.y * gridDim.x + blockIdx.x), (int)(gridDim.x * gridDim.y));
-    const int frame = logical / (int)gridDim.x;
-    const int slot0 = rfl(((logical - frame * (int)gridDim.x) * 4 + (int)(threadIdx.x >> 6)) * KP);
-    const int n_frame = n_kp[frame];
-    if (slot0 >= n_frame) return;
-    const int lane = lane_id();
-    const int kcap = g->kcap;
-    /* IC_Angle: the 31-row patch around the keypoint is staged in LDS as aligned dwords (5 coalesced loads per lane
-     * instead of 16 byte gathers); lane = (row, half) of the disc.  The rBRIEF taps land anywhere in the 37 x 37 blurred
-     * window around the keypoint (tap radius <= sqrt(338)): as global byte gathers, every one of a lane's 8 taps was a
-     * separate cache-line lookup in the CU's vector cache (~40 distinct lines per wave-instruction: the kernel was bound
-     * by that).  The window does not depend on the angle, so it is staged with the patch: 37 rows x 10 aligned dwords,
-     * coalesced, one memory latency for both. */
-    /* 16-byte pieces: the texture addresser, which takes 64 lane addresses per load instruction whatever their width,
-     * was the busiest unit of this kernel with dword loads (TA_BUSY 75 %); a row of the patch is 3 pieces from the
-     * 16-byte boundary at or below kx - 15, a row of the window 4 pieces from the one at or below kx - 18 */
-    /* OD_SEQ: the KP keypoints of a wave go through ONE patch buffer and ONE window buffer one after the other (their loads
-     * are still issued together and wait in registers): the LDS of KP = 1, the angle / sine / cosine evaluation shared by KP */
-    constexpr int KL = OD_SEQ ? 1 : KP;
-    __shared__ __attribute__((aligned(16))) uint32_t patch_all[4][KL][31 * 12 + 4]; /* + 4: the last row's masked-off tail read */
-    /* window rows at an OD_PITCH-byte pitch (>= 64, multiple of 16): at 64 bytes rows r and r + 2 share their banks; at 80 only
-     * rows r and r + 8 do, and the byte gathers of the 64 lanes (anywhere in the window) collide less */
-    __shared__ __attribute__((aligned(16))) uint32_t win_all[4][KL][37 * (OD_PITCH / 4)];
-    int slot[KP], level[KP], kx[KP], ky[KP], resp[KP], pitch[KP], px0[KP], wx0[KP];
-    size_t fb[KP];
-    uint2 ref[KP];
-#pragma unroll
-    for (int k = 0; k < KP; k++) {
-        slot[k] = slot0 + k < n_frame ? slot0 + k : slot0; /* an odd count: the last wave walks its keypoint twice, writes it once */
-        ref[k] = ((const uint2 *)kp_ref)[(size_t)frame * kcap + slot[k]]; /* k_slots left the record next to its reference */
-    }
-    /* this lane's four sample pairs of the pattern: independent of the keypoint, requested first */
-    const uint4 pat4 = ((const uint4 *)g->pat4)[lane];
-    const uint32_t pat[4] = {pat4.x, pat4.y, pat4.z, pat4.w};
-    /* this lane's share of the disc (row lane & 31, left or right half): first u and the byte masks of its <= 16 pixels */
-    const uint4 icm = ((const uint4 *)g->ic_mask)[lane];
-    const int u0 = g->ic_u0[lane];
-#pragma unroll
-    for (int k = 0; k < KP; k++) {
-        level[k] = rfl((int)(ref[k].x >> 16));
-        const ss_level &L = g->lv[level[k]];
-        const uint32_t rec = (uint32_t)rfl((int)ref[k].y);
-        kx[k] = SS_PX(rec);
-        ky[k] = SS_PY(rec);
-        resp[k] = SS_PR(rec);
-        fb[k] = (size_t)frame * g->block_bytes + L.off;
-        pitch[k] = L.pitch;
-        px0[k] = (kx[k] - SS_HALF_PATCH) & ~15; /* >= 0: keypoints stay 19 px inside the level */
-        wx0[k] = (kx[k] - 18) & ~15;
-    }
-    uint4 pv[KP][2], wv[KP][3];
-#pragma unroll
-    for (int k = 0; k < KP; k++) {
-        const bool inplace = level[k] == 0 && lvl0 != nullptr; /* level 0 lives in the caller's buffer */
-        const int ipitch = inplace ? lvl0_pitch : pitch[k];
-        const uint8_t *p0 = (inplace ? lvl0 + (int64_t)frame * lvl0_fs : pyr + fb[k]) + (size_t)(ky[k] - SS_HALF_PATCH) * ipitch + px0[k];
-        const uint8_t *b0 = blur + fb[k] + (size_t)(ky[k] - 18) * pitch[k] + wx0[k];
-#pragma unroll
-        for (int it = 0; it < 2; it++) { /* 31 rows x 3 pieces = 93 */
-            const int idx = lane + WAVE * it;
-            const int r = idx / 3, c = idx - r * 3;
-            pv[k][it] = idx < 31 * 3 ? *(const uint4 *)(p0 + (__umul24((uint32_t)r, (uint32_t)ipitch) + 16u * (uint32_t)c)) : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int it = 0; it < 3; it++) { /* 37 rows x 4 pieces = 148 */
-            const int idx = lane + WAVE * it;
-            wv[k][it] = idx < 37 * 4 ? *(const uint4 *)(b0 + (__umul24((uint32_t)(idx >> 2), (uint32_t)pitch[k]) + 16u * (uint32_t)(idx & 3))) : make_uint4(0, 0, 0, 0);
-        }
-    }
-    auto store_patch = [&](int k) {
-        uint4 *pl = (uint4 *)&patch_all[threadIdx.x >> 6][OD_SEQ ? 0 : k][0];
-#pragma unroll
-        for (int it = 0; it < 2; it++)
-            if (lane + WAVE * it < 31 * 3) pl[lane + WAVE * it] = pv[k][it];
-    };
-    auto store_window = [&](int k) {
-        uint4 *wl = (uint4 *)&win_all[threadIdx.x >> 6][OD_SEQ ? 0 : k][0];
-#pragma unroll
-        for (int it = 0; it < 3; it++)
-            if (lane + WAVE * it < 37 * 4) wl[((lane + WAVE * it) >> 2) * (OD_PITCH / 16) + ((lane + WAVE * it) & 3)] = wv[k][it];
-    };
-    if (!OD_SEQ) {
-#pragma unroll
-        for (int k = 0; k < KP; k++) {
-            store_patch(k);
-            store_window(k);
-        }
-        wave_sync();
-    }
-    int m10[KP], m01[KP];
-#pragma unroll
-    for (int k = 0; k < KP; k++) {
-        if (OD_SEQ) {
-            if (k > 0) wave_sync(); /* the reads of the keypoint before are done */
-            store_patch(k);
-            wave_sync();
-        }
-        /* the lane's pixels are 16 consecutive bytes of its staged row starting at u0 (the tail masked off): five
-         * aligned dwords, four v_alignbyte, then m10 = sum u * I = u0 * sum I + sum k * I_k and m01 = v * sum I as
-         * eight v_dot4_u32_u8 -- integer sums, so the order of additions is free */
-        const int row = imin(lane & 31, 30); /* lanes 31 and 63 carry zero masks */
-        const int sb = (kx[k] - px0[k]) + u0; /* 0 .. 30: byte offset in the staged row */
-        const uint32_t *rw = &patch_all[threadIdx.x >> 6][OD_SEQ ? 0 : k][row * 12 + (sb >> 2)];
-        const uint32_t sh = (uint32_t)sb & 3u;
-        const uint32_t w0 = rw[0], w1 = rw[1], w2 = rw[2], w3 = rw[3], w4 = rw[4];
-        const uint32_t a0 = __builtin_amdgcn_alignbyte(w1, w0, sh) & icm.x, a1 = __builtin_amdgcn_alignbyte(w2, w1, sh) & icm.y;
-        const uint32_t a2 = __builtin_amdgcn_alignbyte(w3, w2, sh) & icm.z, a3 = __builtin_amdgcn_alignbyte(w4, w3, sh) & icm.w;
-        const uint32_t rs = __builtin_amdgcn_udot4(a0, 0x01010101u, __builtin_amdgcn_udot4(a1, 0x01010101u,
-                            __builtin_amdgcn_udot4(a2, 0x01010101u, __builtin_amdgcn_udot4(a3, 0x01010101u, 0u, false), false), false), false);
-        const uint32_t ws = __builtin_amdgcn_udot4(a0, 0x03020100u, __builtin_amdgcn_udot4(a1, 0x07060504u,
-                            __builtin_amdgcn_udot4(a2, 0x0B0A0908u, __builtin_amdgcn_udot4(a3, 0x0F0E0D0Cu, 0u, false), false), false), false);
-        m10[k] = __mul24(u0, (int)rs) + (int)ws;
-        m01[k] = __mul24((lane & 31) - SS_HALF_PATCH, (int)rs);
-    }
-    float angle[KP], sb_[KP], ca_[KP];
-#pragma unroll
-    for (int k = 0; k < KP; k++) {
-        m10[k] = wave_sum(m10[k]);
-        m01[k] = wave_sum(m01[k]);
-    }
-    {
-        /* fastAtan2 and the double-precision sine / cosine are the same for all 64 lanes of a keypoint: lane k evaluates
-         * them for keypoint k, so the wave pays for ONE evaluation however many keypoints it walks */
-        int vm01 = m01[0], vm10 = m10[0];
-#pragma unroll
-        for (int k = 1; k < KP; k++) {
-            vm01 = lane == k ? m01[k] : vm01;
-            vm10 = lane == k ? m10[k] : vm10;
-        }
-        const float ang_v = ss_fast_atan2((float)vm01, (float)vm10);
-        float sin_v, cos_v;
-        ss_sincosf_deg(ang_v, &sin_v, &cos_v);
-#pragma unroll
-        for (int k = 0; k < KP; k++) {
-            angle[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ang_v), k));
-            sb_[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sin_v), k));
-            ca_[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cos_v), k));
-        }
-    }
+ * unpinned (tests/golden/ref_dump/README.md); both are implemented and tested against the oracle's two forms. */
 
-    /* steered rBRIEF: the eight sample addresses of a lane first, then the eight byte reads together, then the
-     * four ballots (the pattern words were requested before the IC stage) */
-    /* cvRound without v_rndne + v_cvt: x + (2^23 + 32) has ulp 1, so the sum is the integer nearest to x (ties to even,
-     * like cvRound) and its bits are 0x4B000020 + round(x) for |x| <= 32.  The low 24 bits, 32 + round(x), are what the
-     * 24-bit multiplier reads; the biases move into one wave-uniform constant: byte index in the staged window =
-     * (18 + row) * OD_PITCH + (kx - wx0) + col */
-    constexpr float RN_MAGIC = 8388640.f;
-    constexpr int RN_BIAS = 0x4B000020;
-    uint32_t off0[KP][4], off1[KP][4];
-#pragma unroll
-    for (int k = 0; k < KP; k++) {
-        const float b = sb_[k], a = ca_[k];
-        const uint32_t kbias = (uint32_t)((18 - 32) * OD_PITCH + (kx[k] - wx0[k])) - (uint32_t)RN_BIAS;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t pt = pat[q]; /* x0 y0 x1 y1 as int8 */
-            const float x0 = (float)(int8_t)(pt & 0xFF), y0 = (float)(int8_t)((pt >> 8) & 0xFF);
-            const float x1 = (float)(int8_t)((pt >> 16) & 0xFF), y1 = (float)(int8_t)(pt >> 24);
-            const float fr0 = STEER_FMA ? __fmaf_rn(x0, b, __fmul_rn(y0, a)) : __fadd_rn(__fmul_rn(x0, b), __fmul_rn(y0, a));
-            const float fc0 = STEER_FMA ? __fmaf_rn(x0, a, -__fmul_rn(y0, b)) : __fsub_rn(__fmul_rn(x0, a), __fmul_rn(y0, b));
-            const float fr1 = STEER_FMA ? __fmaf_rn(x1, b, __fmul_rn(y1, a)) : __fadd_rn(__fmul_rn(x1, b), __fmul_rn(y1, a));
-            const float fc1 = STEER_FMA ? __fmaf_rn(x1, a, -__fmul_rn(y1, b)) : __fsub_rn(__fmul_rn(x1, a), __fmul_rn(y1, b));
-            const int r0 = __float_as_int(__fadd_rn(fr0, RN_MAGIC));
-            const int c0 = __float_as_int(__fadd_rn(fc0, RN_MAGIC));
-            const int r1 = __float_as_int(__fadd_rn(fr1, RN_MAGIC));
-            const int c1 = __float_as_int(__fadd_rn(fc1, RN_MAGIC));
-            off0[k][q] = (uint32_t)(__mul24(r0, OD_PITCH) + c0) + kbias;
-            off1[k][q] = (uint32_t)(__mul24(r1, OD_PITCH) + c1) + kbias;
-        }
-    }
-    int t0[KP][4], t1[KP][4];
-#pragma unroll
-    for (int k = 0; k < KP; k++) {
-        if (OD_SEQ) {
-            if (k > 0) wave_sync();
-            store_window(k);
-            wave_sync();
-        }
-        const uint8_t *center = (const uint8_t *)&win_all[threadIdx.x >> 6][OD_SEQ ? 0 : k][0];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            t0[k][q] = center[off0[k][q]];
-            t1[k][q] = center[off1[k][q]];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < KP; k++) {
-        if (k > 0 && slot0 + k >= n_frame) break; /* the duplicate of an odd tail is not written */
-        uint64_t words[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) words[q] = __ballot(t0[k][q] < t1[k][q]);
-        if (desc_x) {
-            /* the same 256 bits as the matcher's operand row (fp4_of_4bits): lane L writes nibbles 4 L .. 4 L + 3 = bits
-             * 4 L .. 4 L + 3, two bytes: one coalesced 128-byte store per wave */
-            const uint64_t wsel = lane < 16 ? words[0] : lane < 32 ? words[1] : lane < 48 ? words[2] : words[3];
-            const uint32_t nib = (uint32_t)(wsel >> (4 * (lane & 15))) & 15u;
-            *(uint16_t *)(desc_x + ((size_t)frame * kcap + slot[k]) * SS_X_ROW + 2 * lane) = (uint16_t)fp4_of_4bits(nib);
-        }
-        if (lane == 0) {
-            const ss_level &L = g->lv[level[k]];
-            uint64_t *d = (uint64_t *)(desc + ((size_t)frame * kcap + slot[k]) * SS_DESC_BYTES);
-            d[0] = words[0];
-            d[1] = words[1];
-            d[2] = words[2];
-            d[3] = words[3];
-            ss_keypoint kp;
-            kp.x = (float)kx[k];
-            kp.y = (float)ky[k];
-            if (level[k] != 0) {
-                kp.x = __fmul_rn(kp.x, L.scale);
-                kp.y = __fmul_rn(kp.y, L.scale);
-            }
-            kp.size = (float)L.scaled_patch;
-            kp.angle = angle[k];
-            kp.response = (float)resp[k];
-            kp.octave = level[k];
-            kps[(size_t)frame * kcap + slot[k]] = kp;
-        }
-    }
-}
-
-/* OD_SPLIT: k_orient_describe cut at the two points where a keypoint's data shrinks to a few bytes.  In the one kernel all
- * 64 lanes of a keypoint's wave evaluate the same fastAtan2 and the same double-precision sine / cosine (a third of its
- * vector instructions, and its longest stretch without a memory operation in flight).  Split, k_orient_moments leaves
- * (m10, m01) per keypoint, k_keypoint_finish evaluates the float steps with one THREAD per keypoint (64 keypoints per
+/* The stage is cut at the two points where a keypoint's data shrinks to a few bytes.  As one kernel, all 64 lanes of a
+ * keypoint's wave evaluated the same fastAtan2 and the same double-precision sine / cosine (a third of its vector
+ * instructions, and its longest stretch without a memory operation in flight).  Split, k_orient_moments leaves (m10, m01)
+ * per keypoint, k_keypoint_finish evaluates the float steps with one THREAD per keypoint (64 keypoints per
  * wave-instruction) and writes the keypoint record and (sin, cos), k_describe reads the taps.  No barrier, no wave lives
- * longer than before; the arithmetic is the same functions of ss_float_steps.h, only run by another lane.  0 = the one
- * kernel above (measurements: DESIGN.md section 11). */
-#ifndef OD_SPLIT
-#define OD_SPLIT (OD_KP == 1 && !OD_SEQ) /* several keypoints per wave are forms of the one kernel */
-#endif
-#ifndef OD_PIN_TAPS
-#define OD_PIN_TAPS 0
-#endif
-#if OD_SPLIT
+ * longer than before; the arithmetic is the same functions of ss_float_steps.h, only run by another lane (measurements:
+ * DESIGN.md section 11). */
 
-/* K5, first half: the integer patch moments.  One wave per keypoint, the grid and XCD mapping of k_orient_describe. */
+/* window rows of k_describe at an OD_PITCH-byte pitch (>= 64, multiple of 16): at 64 bytes rows r and r + 2 share their
+ * banks; at 80 only rows r and r + 8 do, and the byte gathers of the 64 lanes (anywhere in the window) collide less */
+#define OD_PITCH 80
+
+/* K5, first half: the integer patch moments.  One wave per keypoint.  The 31-row patch around the keypoint is staged in
+ * LDS as aligned pieces (2 coalesced loads per lane instead of 16 byte gathers); lane = (row, half) of the disc.
+ * 16-byte pieces: the texture addresser, which takes 64 lane addresses per load instruction whatever their width, was the
+ * busiest unit of this stage with dword loads (TA_BUSY 75 %); a row of the patch is 3 pieces from the 16-byte boundary at
+ * or below kx - 15 (k_describe: a row of the window, 4 pieces from the one at or below kx - 18). */
 __global__ __launch_bounds__(256) void k_orient_moments(const ss_geom *__restrict__ g, const uint8_t *__restrict__ pyr,
                                                         const uint32_t *__restrict__ kp_ref, const int32_t *__restrict__ n_kp,
                                                         const uint8_t *__restrict__ lvl0, int lvl0_pitch, int64_t lvl0_fs,
                                                         int2 *__restrict__ moments)
 {
+    /* all blocks of a frame on one XCD: keypoints whose patches share 64-B lines then share an L2 */
     const int logical = xcd_remap((int)(blockIdx.y * gridDim.x + blockIdx.x), (int)(gridDim.x * gridDim.y));
     const int frame = logical / (int)gridDim.x;
     const int slot = rfl((logical - frame * (int)gridDim.x) * 4 + (int)(threadIdx.x >> 6));
@@ -2178,7 +1824,9 @@ __global__ __launch_bounds__(256) void k_orient_moments(const ss_geom *__restric
     for (int it = 0; it < 2; it++)
         if (lane + WAVE * it < 31 * 3) pl[lane + WAVE * it] = pv[it];
     wave_sync();
-    /* as in k_orient_describe: 16 consecutive bytes of the lane's staged row from u0, eight v_dot4_u32_u8 */
+    /* the lane's pixels are 16 consecutive bytes of its staged row starting at u0 (the tail masked off): five
+     * aligned dwords, four v_alignbyte, then m10 = sum u * I = u0 * sum I + sum k * I_k and m01 = v * sum I as
+     * eight v_dot4_u32_u8 -- integer sums, so the order of additions is free */
     const int row = imin(lane & 31, 30); /* lanes 31 and 63 carry zero masks */
     const int sb = (kx - px0) + u0;      /* 0 .. 30: byte offset in the staged row */
     const uint32_t *rw = &patch_all[threadIdx.x >> 6][row * 12 + (sb >> 2)];
@@ -2225,9 +1873,12 @@ __global__ __launch_bounds__(64) void k_keypoint_finish(const ss_geom *__restric
     steer[at] = make_float2(sin_v, cos_v);
 }
 
-/* K6b: steered rBRIEF.  One wave per keypoint, the grid and XCD mapping of k_orient_describe.  The window does not depend on
- * the angle: its loads are issued first; the lane's eight tap offsets need only the sine, the cosine, the pattern word and
- * kx - wx0, all known before the window arrives. */
+/* K6b: steered rBRIEF.  One wave per keypoint, the grid and XCD mapping of k_orient_moments.  The taps land anywhere in the
+ * 37 x 37 blurred window around the keypoint (tap radius <= sqrt(338)): as global byte gathers, every one of a lane's 8 taps
+ * was a separate cache-line lookup in the CU's vector cache (~40 distinct lines per wave-instruction: the stage was bound by
+ * that).  So the window is staged in LDS: 37 rows x 4 16-byte pieces, coalesced.  It does not depend on the angle: its
+ * loads are issued first; the lane's eight tap offsets need only the sine, the cosine, the pattern word and kx - wx0, all
+ * known before the window arrives. */
 template <bool STEER_FMA>
 __global__ __launch_bounds__(256) void k_describe(const ss_geom *__restrict__ g, const uint8_t *__restrict__ blur,
                                                   const uint32_t *__restrict__ kp_ref, const int32_t *__restrict__ n_kp,
@@ -2240,7 +1891,6 @@ __global__ __launch_bounds__(256) void k_describe(const ss_geom *__restrict__ g,
     if (slot >= n_kp[frame]) return;
     const int lane = lane_id();
     const int kcap = g->kcap;
-    /* window rows at an OD_PITCH-byte pitch, as in k_orient_describe */
     __shared__ __attribute__((aligned(16))) uint32_t win_all[4][37 * (OD_PITCH / 4)];
     const uint2 ref = ((const uint2 *)kp_ref)[(size_t)frame * kcap + slot];
     const float2 sc = steer[(size_t)frame * kcap + slot];
@@ -2258,7 +1908,10 @@ __global__ __launch_bounds__(256) void k_describe(const ss_geom *__restrict__ g,
         const int idx = lane + WAVE * it;
         wv[it] = idx < 37 * 4 ? *(const uint4 *)(b0 + (__umul24((uint32_t)(idx >> 2), (uint32_t)pitch) + 16u * (uint32_t)(idx & 3))) : make_uint4(0, 0, 0, 0);
     }
-    /* cvRound by the magic-number sum and the biases folded into one wave-uniform constant: see k_orient_describe */
+    /* cvRound without v_rndne + v_cvt: x + (2^23 + 32) has ulp 1, so the sum is the integer nearest to x (ties to even,
+     * like cvRound) and its bits are 0x4B000020 + round(x) for |x| <= 32.  The low 24 bits, 32 + round(x), are what the
+     * 24-bit multiplier reads; the biases move into one wave-uniform constant: byte index in the staged window =
+     * (18 + row) * OD_PITCH + (kx - wx0) + col */
     constexpr float RN_MAGIC = 8388640.f;
     constexpr int RN_BIAS = 0x4B000020;
     const float b = __int_as_float(rfl(__float_as_int(sc.x))), a = __int_as_float(rfl(__float_as_int(sc.y)));
@@ -2280,14 +1933,9 @@ __global__ __launch_bounds__(256) void k_describe(const ss_geom *__restrict__ g,
         off0[q] = (uint32_t)(__mul24(r0, OD_PITCH) + c0) + kbias;
         off1[q] = (uint32_t)(__mul24(r1, OD_PITCH) + c1) + kbias;
     }
-    /* The compiler sinks the arithmetic above to its use, below the wait for the window.  OD_PIN_TAPS=1 pins it here, between the
-     * loads and their wait (7 more vector instructions, 30 registers instead of 24): the same time alone (111.1 against 111.4 us
-     * per 128 frames) and in the pipeline (121.63 k against 121.60 k frames/s, medians of five alternations), so it stays off:
-     * other waves of the CU fill the wait as well as this one's own arithmetic would */
-#if OD_PIN_TAPS
-#pragma unroll
-    for (int q = 0; q < 4; q++) asm volatile("" : "+v"(off0[q]), "+v"(off1[q]) : : "memory");
-#endif
+    /* The compiler sinks the arithmetic above to its use, below the wait for the window.  Pinned here, between the loads and
+     * their wait, it measured the same: other waves of the CU fill the wait as well as this one's own
+     * arithmetic would */
     uint4 *wl = (uint4 *)&win_all[threadIdx.x >> 6][0];
 #pragma unroll
     for (int it = 0; it < 3; it++)
@@ -2317,7 +1965,6 @@ __global__ __launch_bounds__(256) void k_describe(const ss_geom *__restrict__ g,
         d[3] = words[3];
     }
 }
-#endif /* OD_SPLIT */
 
 /* ------------------------------------------------------------------------------------ */
 /* K7: Hamming best / second best.  Lane = one query descriptor (8 dwords in VGPRs); the   */
@@ -2492,9 +2139,7 @@ __global__ __launch_bounds__(256) void k_match(const uint32_t *__restrict__ quer
 /* NU = 32-query B tiles per wave.  1: 117 VGPRs, four waves per SIMD -- as fast alone on the 2000 x 2000 frames and 2 % more
  * frames/s with four batches in flight (it leaves room next to the other kernels).  2: 198 VGPRs, two waves per SIMD, half the
  * LDS reads per MFMA -- 17 % faster on a large database that has the chip to itself (2000 x 20 M: 10.0 vs 11.7 ms). */
-#ifndef MM_WAVES
 #define MM_WAVES 4 /* waves per block sharing the train tiles (8: -2.5 % frames/s with four batches in flight) */
-#endif
 #define MM_QBLOCK(NU) (32 * (NU) * MM_WAVES)
 
 /* best / second best per lane, kept as FOUR independent (k1, k2) chains (register groups r >> 2) so the three
@@ -2650,16 +2295,11 @@ __global__ __launch_bounds__(64 * MM_WAVES, NU == 2 ? 2 : 4) void k_match_mfma(c
             mfma_tile(i + 1, nxt0, nxt1);
             mfma_rest(i + 1, nxt0, nxt1);
             select_tile(i, cur0, cur1);
-#ifndef MM_SCHED_VALU
-#define MM_SCHED_VALU 9
-#endif
-#if MM_SCHED_VALU > 0
 #pragma unroll
             for (int g = 0; g < 8 * NU - 2; g++) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);             /* one MFMA */
-                __builtin_amdgcn_sched_group_barrier(0x002, MM_SCHED_VALU, 0); /* nine VALU */
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); /* one MFMA */
+                __builtin_amdgcn_sched_group_barrier(0x002, 9, 0); /* nine VALU */
             }
-#endif
         }
         if (i + 2 < n_tiles) expand(i & 1, wnext);
         wnext = load_word(i + 3);
@@ -2718,7 +2358,7 @@ __global__ __launch_bounds__(64 * MM_WAVES, NU == 2 ? 2 : 4) void k_match_mfma(c
 }
 
 /* ------------------------------------------------------------------------------------ */
-/* K7 on the matrix cores, operands already expanded (k_orient_describe's desc_x / k_expand_desc: one FP4 value per           */
+/* K7 on the matrix cores, operands already expanded (k_describe's desc_x / k_expand_desc: one FP4 value per                  */
 /* descriptor bit, +1 / -1, 128 bytes per row).                                                                                  */
 /* * v_mfma_scale_f32_32x32x64_f8f6f4 with FP4 operands takes the time of the i8 32x32x32 instruction for twice the K           */
 /*   (profiles/tools/fp4_probe.hip): 4 instructions per 32 x 32 tile of pairs.  The E8M0 block scale 2^12 on the train           */
@@ -2776,9 +2416,7 @@ typedef float v16f __attribute__((ext_vector_type(16)));
  * 8 k + 4 half .. + 3 of the tile).  MX_RUNS consecutive runs form a GROUP: the minimum of each group, then the two smallest
  * group minima seen so far.  Larger groups = fewer vector instructions here (4 runs: 10, 2 runs: 12, 1 run: 16 per tile) and
  * more rows to re-examine once the best is final (15 / 7 / 3 rows in 4 / 2 / 1 lines of packed descriptors). */
-#ifndef MX_RUNS
 #define MX_RUNS 1 /* measured, 64 x 2000^2 in one fused launch: 1 run 41.8 us, 2 runs 43.2, 4 runs 46.7 (the epilogue's lines decide) */
-#endif
 __device__ __forceinline__ void mx_select(const v16f &acc, uint32_t &k1, uint32_t &k2)
 {
 #pragma unroll
@@ -2858,9 +2496,6 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 5) void k_match_mfma_x(const uint8_
      * counted waits below rely on.  `slot_off` = byte offset of the ring slot (wave-uniform). */
     auto dma_tile = [&](int tile, int slot_off, auto ndma_c) {
         constexpr int NDMA = decltype(ndma_c)::value;
-#if defined(MX_EXP) && MX_EXP == 1 /* timing experiment: no DMA after the prologue (stale tiles: wrong results) */
-        if (tile >= MX_NBUF - 1) return;
-#endif
         const uint8_t *src = tsrc + (size_t)(uint32_t)(imin(tile, last_tile) * (MM_TILE * SS_X_ROW));
         uint8_t *dst = &tiles[0][0] + slot_off + wave * 1024;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + src_off[0]),
@@ -2879,11 +2514,7 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 5) void k_match_mfma_x(const uint8_
 #pragma unroll
         for (int sstep = 0; sstep < 4; sstep++) bq4[u][sstep] = *(const v4i *)(qrow + 32 * sstep);
     }
-#if defined(MX_EXP) && MX_EXP == 3 /* timing experiment: the tile stream alone, no MFMA, no selection */
-    const bool active = false;
-#else
     const bool active = qbase < nq; /* wave-uniform: a wave without valid queries only helps with the tiles */
-#endif
     uint32_t k1[MX_QT], k2[MX_QT];
 #pragma unroll
     for (int u = 0; u < MX_QT; u++) k1[u] = k2[u] = MX_INIT_KEY;
@@ -2909,13 +2540,9 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 5) void k_match_mfma_x(const uint8_
             mx_wait_vm<NDMA * (MX_NBUF - 2 - (PIPE ? 1 : 0))>(); /* PIPE: tile t + 1 has landed; else: tile t */
             /* every LDS read this wave has issued is complete before it arrives: the compiler otherwise lets the last fragment
              * read of a tile (and the MFMA behind it) sink below the barrier, and the DMA another wave issues right after the
-             * barrier refills exactly that slot */
-#if !(defined(MX_EXP) && MX_EXP == 7) /* experiment 7: the hazard itself (profiles/tools/repro_partial.py shows the wrong partials) */
+             * barrier refills exactly that slot: this wait must stay in front of the barrier */
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-#if !(defined(MX_EXP) && MX_EXP == 5) /* timing experiment 5: no barrier (races: wrong results) */
             __builtin_amdgcn_s_barrier();
-#endif
             asm volatile("" ::: "memory");
             dma_tile(t + MX_NBUF - 1, wr_off, ndma_c);
             wr_off = wr_off == (MX_NBUF - 1) * MX_BUF ? 0 : wr_off + MX_BUF;
@@ -2955,13 +2582,8 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 5) void k_match_mfma_x(const uint8_
         auto read_frags = [&](v4i(&a4)[4]) {
             const uint8_t *arow = &tiles[0][0] + (a_base + (uint32_t)rd_off);
             rd_off = rd_off == (MX_NBUF - 1) * MX_BUF ? 0 : rd_off + MX_BUF;
-#if defined(MX_EXP) && MX_EXP == 6 /* timing experiment 6: no LDS reads (wrong results) */
-#pragma unroll
-            for (int sstep = 0; sstep < 4; sstep++) a4[sstep] = bq4[0][sstep] + (int)(uintptr_t)arow;
-#else
 #pragma unroll
             for (int sstep = 0; sstep < 4; sstep++) a4[sstep] = *(const v4i *)(arow + 32 * sstep);
-#endif
         };
         /* the MFMAs of tile t.  PIPE: the fragments are in registers (a4); compact: each k-step's fragment is read from the
          * tile's LDS slot right before its MFMAs (four registers live instead of sixteen) */
@@ -2972,9 +2594,6 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 5) void k_match_mfma_x(const uint8_
                 arow = &tiles[0][0] + (a_base + (uint32_t)rd_off);
                 rd_off = rd_off == (MX_NBUF - 1) * MX_BUF ? 0 : rd_off + MX_BUF;
             }
-#ifdef MX_SETPRIO /* timing experiment: the wave asks for issue priority while its matrix instructions go out */
-            __builtin_amdgcn_s_setprio(MX_SETPRIO);
-#endif
 #pragma unroll
             for (int sstep = 0; sstep < 4; sstep++) {
                 const v4i f = PIPE ? a4[sstep] : *(const v4i *)(arow + 32 * sstep);
@@ -2993,16 +2612,8 @@ __global__ __launch_bounds__(256, PIPE ? 2 : 5) void k_match_mfma_x(const uint8_
                     ac[u] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, bq[u][sstep], ci, MX_FMT_FP4, MX_FMT_FP4, 0, MX_SCALE_ONE + 12, 0, MX_SCALE_ONE);
                 }
             }
-#ifdef MX_SETPRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
         };
         auto select_tile = [&](v16f(&ac)[MX_QT]) {
-#if defined(MX_EXP) && MX_EXP == 4 /* timing experiment 4: no selection (one key per tile keeps the MFMAs alive) */
-            k1[0] = min(k1[0], __float_as_uint(ac[0][0]));
-            k1[1] = min(k1[1], __float_as_uint(ac[1][0]));
-            return;
-#endif
             /* the running keys fall behind every key of this tile */
 #pragma unroll
             for (int u = 0; u < MX_QT; u++) {
@@ -3242,7 +2853,7 @@ __global__ __launch_bounds__(256) void k_match_merge(const match_partial *__rest
 }
 
 /* packed descriptors (32 B) -> the matrix-core matcher's operand rows (SS_X_ROW bytes, fp4_of_4bits), the same format
- * k_orient_describe writes for the frames of a batch.  One wave per row, one coalesced 128-byte store; rows n .. n_alloc - 1
+ * k_describe writes for the frames of a batch.  One wave per row, one coalesced 128-byte store; rows n .. n_alloc - 1
  * (n_alloc = n rounded up to the 32-row tile) are zero-filled (FP4 zeros: they contribute 0 and are masked anyway). */
 __global__ __launch_bounds__(256) void k_expand_desc(const uint32_t *__restrict__ packed, int n, int n_alloc, uint8_t *__restrict__ out,
                                                      int64_t src_frame_words, int64_t dst_frame_bytes)
@@ -3553,7 +3164,6 @@ void ssk_orient_describe(hipStream_t s, const ss_geom *dg, const ss_geom &hg, co
                          const uint32_t *sel, const uint32_t *kp_ref, const int32_t *n_kp, ss_keypoint *kps,
                          uint8_t *desc, int n_frames, const ss_lvl0 &l0, bool steer_fma, uint8_t *desc_x, void *moments, void *steer)
 {
-#if OD_SPLIT
     /* kcap is a multiple of 64: kcap / 4 blocks of four waves per frame, kcap / 64 waves of the per-thread kernel */
     const dim3 grid(hg.kcap / 4, n_frames);
     hipLaunchKernelGGL(k_orient_moments, grid, dim3(256), 0, s, dg, pyr, kp_ref, n_kp, l0.ptr, l0.pitch, l0.frame_stride, (int2 *)moments);
@@ -3562,15 +3172,6 @@ void ssk_orient_describe(hipStream_t s, const ss_geom *dg, const ss_geom &hg, co
         hipLaunchKernelGGL(k_describe<true>, grid, dim3(256), 0, s, dg, blur, kp_ref, n_kp, (const float2 *)steer, desc, desc_x);
     else
         hipLaunchKernelGGL(k_describe<false>, grid, dim3(256), 0, s, dg, blur, kp_ref, n_kp, (const float2 *)steer, desc, desc_x);
-#else
-    /* kcap is a multiple of 64: kcap / (4 waves x OD_KP keypoints) blocks per frame */
-    if (steer_fma)
-        hipLaunchKernelGGL((k_orient_describe<true, OD_KP>), dim3(hg.kcap / (4 * OD_KP), n_frames), dim3(256), 0, s, dg, pyr, blur, sel,
-                           kp_ref, n_kp, kps, desc, l0.ptr, l0.pitch, l0.frame_stride, desc_x);
-    else
-        hipLaunchKernelGGL((k_orient_describe<false, OD_KP>), dim3(hg.kcap / (4 * OD_KP), n_frames), dim3(256), 0, s, dg, pyr, blur, sel,
-                           kp_ref, n_kp, kps, desc, l0.ptr, l0.pitch, l0.frame_stride, desc_x);
-#endif
 }
 
 /* which form of the matrix-core kernel: a single large database has the chip to itself (NU = 2), batches of frames share it */
@@ -3609,97 +3210,100 @@ static bool mx_pipelined(int n_frames, int rows_t)
     return n_frames == 1 && rows_t >= 65536;
 }
 
-template <bool FUSED, int QT, bool PIPE, bool TABLE>
-static void mx_launch(hipStream_t s, dim3 grid, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr, int nq_fixed,
-                      int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift, int chunk_len, int n_chunks,
-                      int exclude_self_mode, int out_stride, void *partial, const mx_finish &fin, const mt_table &tab)
+/* One matcher call as the host helpers below hand it on and spread it over the kernels' parameter lists; every public
+ * ssk_match* entry point fills one.  Frame strides are in the unit of the rows they step over: words in ssk_match (packed
+ * descriptors), bytes in ssk_match_x (FP4 operand rows, and the same rows as packed descriptors). */
+struct match_call {
+    hipStream_t s = nullptr;
+    int n_frames = 1;
+    const void *query = nullptr, *train = nullptr;             /* the rows the first launch reads */
+    int64_t q_frame_stride = 0, t_frame_stride = 0;
+    const uint8_t *query_p = nullptr, *train_p = nullptr;      /* ssk_match_x: the same rows as packed descriptors, or null */
+    int64_t qp_frame_stride = 0, tp_frame_stride = 0;
+    const int32_t *nq_arr = nullptr, *nt_arr = nullptr;        /* row counts per frame, or null: nq_fixed / nt_fixed */
+    int nq_fixed = 0, nt_fixed = 0;
+    int train_frame_shift = 0;
+    int chunk_len = 0, n_chunks = 0;                           /* the chunk plan */
+    int exclude_self_mode = 0;
+    int th = 0, rnum = 0, rden = 0;                            /* the acceptance test */
+    int out_stride = 0;
+    void *partial = nullptr;
+    int32_t *idx = nullptr;
+    uint16_t *d1 = nullptr, *d2 = nullptr;
+    const ssk_table *tab = nullptr;                            /* the table forms: where each query frame's train rows come from */
+    /* the kernels' table argument, the carry in the row format the launch reads: packed descriptors or FP4 operand rows */
+    mt_table table(bool packed) const
+    {
+        return mt_table{tab->src, (const uint8_t *)(packed ? tab->carry_p : tab->carry_x), (const uint8_t *)tab->carry_p, tab->carry_n};
+    }
+};
+
+/* The FP4 matcher's first launch, k_match_mfma_x in the form `kernel` (blocks of qblock queries).  One chunk and packed
+ * descriptors at hand: the FUSED forms finish their queries themselves and the outputs are final. */
+static bool mx_fused(const match_call &m) { return m.n_chunks == 1 && m.query_p && m.train_p; }
+template <typename K, typename... TAB>
+static void mx_launch(const match_call &m, K kernel, int qblock, TAB... tab)
 {
-    if constexpr (TABLE)
-        hipLaunchKernelGGL((k_match_mfma_x<FUSED, QT, PIPE, mt_table>), grid, dim3(256), 0, s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed,
-                           q_frame_stride, t_frame_stride, train_frame_shift, chunk_len, n_chunks, exclude_self_mode, out_stride,
-                           (match_partial *)partial, fin, tab);
-    else
-        hipLaunchKernelGGL((k_match_mfma_x<FUSED, QT, PIPE>), grid, dim3(256), 0, s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed,
-                           q_frame_stride, t_frame_stride, train_frame_shift, chunk_len, n_chunks, exclude_self_mode, out_stride,
-                           (match_partial *)partial, fin);
+    const dim3 grid(((m.out_stride + qblock - 1) / qblock) * m.n_chunks * m.n_frames);
+    const mx_finish fin{m.query_p, m.train_p, m.qp_frame_stride, m.tp_frame_stride, m.th, m.rnum, m.rden, m.idx, m.d1, m.d2};
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, m.s, (const uint8_t *)m.query, (const uint8_t *)m.train, m.nq_arr, m.nt_arr, m.nq_fixed,
+                       m.nt_fixed, m.q_frame_stride, m.t_frame_stride, m.train_frame_shift, m.chunk_len, m.n_chunks, m.exclude_self_mode,
+                       m.out_stride, (match_partial *)m.partial, fin, tab...);
 }
 
-/* the matcher's first launch (or only one, when fused); returns true when the outputs are final.  The table form has the
- * compact kernel only (pipelined is ignored). */
-template <bool TABLE = false>
-static bool mx_match(hipStream_t s, bool pipelined, int n_frames, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr,
-                     const int32_t *nt_arr, int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift,
-                     int chunk_len, int n_chunks, int exclude_self_mode, int out_stride, void *partial, const mx_finish &fin,
-                     const mt_table &tab = mt_table{})
+/* Its second launch: k_match_finish_x folds the n_chunks partials of a query (0: the outputs hold them folded), adds the second
+ * best inside the best row's group and applies the acceptance test.  packed: on the rows as packed descriptors (`kernel` is the
+ * form for 32-byte rows), a quarter of the traffic. */
+template <typename K, typename... TAB>
+static void mx_finish_launch(const match_call &m, K kernel, bool packed, int n_chunks, TAB... tab)
 {
-    if (TABLE) pipelined = false;
-    const int qblock = pipelined ? MX_QBLOCK_OF(2) : MX_QBLOCK_OF(1);
-    dim3 grid(((out_stride + qblock - 1) / qblock) * n_chunks * n_frames);
-    const bool fused = n_chunks == 1 && fin.query_p && fin.train_p; /* one launch: the kernel finishes its queries itself */
-#define MX_GO(F, Q, P)                                                                                                                      \
-    mx_launch<F, Q, P, TABLE>(s, grid, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride, t_frame_stride, train_frame_shift, \
-                              chunk_len, n_chunks, exclude_self_mode, out_stride, partial, fin, tab)
-    if constexpr (!TABLE) {
-        if (pipelined) {
-            if (fused) MX_GO(true, 2, true);
-            else MX_GO(false, 2, true);
-            return fused;
-        }
-    }
-    if (fused) MX_GO(true, 1, false);
-    else MX_GO(false, 1, false);
-#undef MX_GO
+    hipLaunchKernelGGL(kernel, dim3((m.out_stride + 63) / 64, m.n_frames), dim3(256), 0, m.s, packed ? m.query_p : (const uint8_t *)m.query,
+                       packed ? m.train_p : (const uint8_t *)m.train, m.nq_arr, m.nt_arr, m.nq_fixed, m.nt_fixed,
+                       packed ? m.qp_frame_stride : m.q_frame_stride, packed ? m.tp_frame_stride : m.t_frame_stride, m.train_frame_shift,
+                       m.exclude_self_mode, (const match_partial *)m.partial, n_chunks, m.th, m.rnum, m.rden, m.out_stride, m.idx, m.d1, m.d2,
+                       tab...);
+}
+
+/* the table forms: the compact kernel only */
+static void mx_match_table(const match_call &m)
+{
+    const bool fused = mx_fused(m), packed = m.query_p && m.train_p;
+    const auto finish = packed ? k_match_finish_x<32, mt_table> : k_match_finish_x<SS_X_ROW, mt_table>;
+    const auto first = fused ? k_match_mfma_x<true, 1, false, mt_table> : k_match_mfma_x<false, 1, false, mt_table>;
+    mx_launch(m, first, MX_QBLOCK_OF(1), m.table(false));
+    if (!fused) mx_finish_launch(m, finish, packed, m.n_chunks, m.table(packed));
+}
+
+/* the forms without a table: returns true when the first launch was the only one */
+static bool mx_match(const match_call &m, bool pipelined)
+{
+    const bool fused = mx_fused(m);
+    if (pipelined) mx_launch(m, fused ? k_match_mfma_x<true, 2, true> : k_match_mfma_x<false, 2, true>, MX_QBLOCK_OF(2));
+    else mx_launch(m, fused ? k_match_mfma_x<true, 1, false> : k_match_mfma_x<false, 1, false>, MX_QBLOCK_OF(1));
     return fused;
+}
+static void mx_finish_rows(const match_call &m, int n_chunks)
+{
+    const bool packed = m.query_p && m.train_p;
+    mx_finish_launch(m, packed ? k_match_finish_x<32> : k_match_finish_x<SS_X_ROW>, packed, n_chunks);
 }
 
 /* batch form on expanded descriptors (desc_x of the extraction): same arguments as ssk_match, strides in BYTES.  With several
- * chunks two launches: k_match_mfma_x writes one partial per (query, chunk), k_match_finish_x folds them, adds the second best
- * inside the best row's group and applies the acceptance test. */
-template <bool TABLE>
-static void match_x_batch(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
-                          int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift, int chunk_len,
-                          int n_chunks, int exclude_self_mode, int th, int rnum, int rden, int out_stride, void *partial, int32_t *idx,
-                          uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p, int64_t qp_frame_stride,
-                          int64_t tp_frame_stride, const ssk_table *tab)
-{
-    mx_finish fin{query_p, train_p, qp_frame_stride, tp_frame_stride, th, rnum, rden, idx, d1, d2};
-    /* the carry in the row format each launch reads */
-    mt_table tx{}, tp{};
-    if (tab) {
-        tx = mt_table{tab->src, (const uint8_t *)tab->carry_x, (const uint8_t *)tab->carry_p, tab->carry_n};
-        tp = mt_table{tab->src, (const uint8_t *)tab->carry_p, (const uint8_t *)tab->carry_p, tab->carry_n};
-    }
-    if (mx_match<TABLE>(s, mx_pipelined(n_frames, out_stride), n_frames, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride,
-                        t_frame_stride, train_frame_shift, chunk_len, n_chunks, exclude_self_mode, out_stride, partial, fin, tx))
-        return;
-    dim3 g2((out_stride + 63) / 64, n_frames);
-    if (TABLE && query_p && train_p) /* the same rows as packed descriptors: the finish reads those */
-        hipLaunchKernelGGL((k_match_finish_x<32, mt_table>), g2, dim3(256), 0, s, query_p, train_p, nq_arr, nt_arr, nq_fixed, nt_fixed, qp_frame_stride,
-                           tp_frame_stride, train_frame_shift, exclude_self_mode, (const match_partial *)partial, n_chunks, th, rnum, rden, out_stride,
-                           idx, d1, d2, tp);
-    else if (TABLE)
-        hipLaunchKernelGGL((k_match_finish_x<SS_X_ROW, mt_table>), g2, dim3(256), 0, s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed,
-                           q_frame_stride, t_frame_stride, train_frame_shift, exclude_self_mode, (const match_partial *)partial, n_chunks, th, rnum,
-                           rden, out_stride, idx, d1, d2, tx);
-    else if (query_p && train_p)
-        hipLaunchKernelGGL(k_match_finish_x<32>, g2, dim3(256), 0, s, query_p, train_p, nq_arr, nt_arr, nq_fixed, nt_fixed, qp_frame_stride,
-                           tp_frame_stride, train_frame_shift, exclude_self_mode, (const match_partial *)partial, n_chunks, th, rnum, rden, out_stride,
-                           idx, d1, d2);
-    else
-        hipLaunchKernelGGL(k_match_finish_x<SS_X_ROW>, g2, dim3(256), 0, s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride,
-                           t_frame_stride, train_frame_shift, exclude_self_mode, (const match_partial *)partial, n_chunks, th, rnum, rden, out_stride,
-                           idx, d1, d2);
-}
-
+ * chunks two launches: k_match_mfma_x writes one partial per (query, chunk), k_match_finish_x finishes them. */
 void ssk_match_x(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
                  int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift, int chunk_len,
                  int n_chunks, int exclude_self_mode, int th, int rnum, int rden, int out_stride, void *partial, int32_t *idx,
                  uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p, int64_t qp_frame_stride,
                  int64_t tp_frame_stride)
 {
-    match_x_batch<false>(s, query_x, train_x, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride, t_frame_stride, train_frame_shift, chunk_len,
-                         n_chunks, exclude_self_mode, th, rnum, rden, out_stride, partial, idx, d1, d2, n_frames, query_p, train_p, qp_frame_stride,
-                         tp_frame_stride, nullptr);
+    match_call m;
+    m.s = s; m.n_frames = n_frames; m.query = query_x; m.train = train_x; m.q_frame_stride = q_frame_stride; m.t_frame_stride = t_frame_stride;
+    m.query_p = query_p; m.train_p = train_p; m.qp_frame_stride = qp_frame_stride; m.tp_frame_stride = tp_frame_stride;
+    m.nq_arr = nq_arr; m.nt_arr = nt_arr; m.nq_fixed = nq_fixed; m.nt_fixed = nt_fixed;
+    m.train_frame_shift = train_frame_shift; m.exclude_self_mode = exclude_self_mode;
+    m.chunk_len = chunk_len; m.n_chunks = n_chunks; m.th = th; m.rnum = rnum; m.rden = rden;
+    m.out_stride = out_stride; m.partial = partial; m.idx = idx; m.d1 = d1; m.d2 = d2;
+    if (!mx_match(m, mx_pipelined(n_frames, out_stride))) mx_finish_rows(m, n_chunks);
 }
 
 void ssk_match_x_table(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
@@ -3707,8 +3311,13 @@ void ssk_match_x_table(hipStream_t s, const uint8_t *query_x, const uint8_t *tra
                        void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p,
                        int64_t qp_frame_stride, int64_t tp_frame_stride, const ssk_table &tab)
 {
-    match_x_batch<true>(s, query_x, train_x, nq_arr, nt_arr, 0, 0, q_frame_stride, t_frame_stride, 0, chunk_len, n_chunks, 2, th, rnum, rden,
-                        out_stride, partial, idx, d1, d2, n_frames, query_p, train_p, qp_frame_stride, tp_frame_stride, &tab);
+    match_call m;
+    m.s = s; m.n_frames = n_frames; m.query = query_x; m.train = train_x; m.q_frame_stride = q_frame_stride; m.t_frame_stride = t_frame_stride;
+    m.query_p = query_p; m.train_p = train_p; m.qp_frame_stride = qp_frame_stride; m.tp_frame_stride = tp_frame_stride;
+    m.nq_arr = nq_arr; m.nt_arr = nt_arr; m.exclude_self_mode = 2; m.tab = &tab;
+    m.chunk_len = chunk_len; m.n_chunks = n_chunks; m.th = th; m.rnum = rnum; m.rden = rden;
+    m.out_stride = out_stride; m.partial = partial; m.idx = idx; m.d1 = d1; m.d2 = d2;
+    mx_match_table(m);
 }
 
 /* chunk plan: rows_q query rows and rows_t train rows per frame.  Once the query blocks alone fill the chip, one chunk per
@@ -3757,64 +3366,47 @@ void ssk_match_x_single(hipStream_t s, const uint8_t *query_x, int nq, const uin
                         int exclude_self, int th, int rnum, int rden, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2,
                         const uint8_t *query_p, const uint8_t *train_p)
 {
-    mx_finish fin{query_p, train_p, 0, 0, th, rnum, rden, idx, d1, d2};
-    if (mx_match(s, mx_pipelined(1, nt), 1, query_x, train_x, nullptr, nullptr, nq, nt, 0, 0, 0, chunk_len, n_chunks, exclude_self ? 1 : 0, nq, partial, fin))
-        return;
+    match_call m; /* one frame: no strides, no count arrays */
+    m.s = s; m.query = query_x; m.train = train_x; m.query_p = query_p; m.train_p = train_p;
+    m.nq_fixed = nq; m.nt_fixed = nt; m.exclude_self_mode = exclude_self ? 1 : 0;
+    m.chunk_len = chunk_len; m.n_chunks = n_chunks; m.th = th; m.rnum = rnum; m.rden = rden;
+    m.out_stride = nq; m.partial = partial; m.idx = idx; m.d1 = d1; m.d2 = d2;
+    if (mx_match(m, mx_pipelined(1, nt))) return;
     int fin_chunks = n_chunks;
     if (n_chunks >= 32) { /* many chunks: one wave per query folds them (raw: no acceptance test yet), the finish reads the outputs */
         hipLaunchKernelGGL(k_match_merge_wide, dim3(nq), dim3(64), 0, s, (const match_partial *)partial, nq, n_chunks, -1, 1, 1, nq, idx, d1, d2);
         fin_chunks = 0;
     }
-    if (query_p && train_p)
-        hipLaunchKernelGGL(k_match_finish_x<32>, dim3((nq + 63) / 64, 1), dim3(256), 0, s, query_p, train_p, (const int32_t *)nullptr,
-                           (const int32_t *)nullptr, nq, nt, (int64_t)0, (int64_t)0, 0, exclude_self ? 1 : 0, (const match_partial *)partial,
-                           fin_chunks, th, rnum, rden, nq, idx, d1, d2);
-    else
-        hipLaunchKernelGGL(k_match_finish_x<SS_X_ROW>, dim3((nq + 63) / 64, 1), dim3(256), 0, s, query_x, train_x, (const int32_t *)nullptr,
-                           (const int32_t *)nullptr, nq, nt, (int64_t)0, (int64_t)0, 0, exclude_self ? 1 : 0, (const match_partial *)partial,
-                           fin_chunks, th, rnum, rden, nq, idx, d1, d2);
+    mx_finish_rows(m, fin_chunks);
 }
 
-template <bool TABLE>
-static void match_batch(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr, int nq_fixed,
-                        int nt_fixed, int64_t q_frame_stride_words, int64_t t_frame_stride_words, int train_frame_shift, int chunk_len,
-                        int n_chunks, int exclude_self_mode, int th, int rnum, int rden, int out_stride, void *partial, int32_t *idx,
-                        uint16_t *d1, uint16_t *d2, int n_frames, const mt_table &tab)
+static void match_batch(const match_call &m)
 {
-    if (out_stride >= SSK_MATCH_MFMA_MIN_QUERIES) {
+    /* k_match_mfma and k_match take the same arguments */
+    auto go = [&](auto kernel, dim3 grid, dim3 block, auto... tab) {
+        hipLaunchKernelGGL(kernel, grid, block, 0, m.s, (const uint32_t *)m.query, (const uint32_t *)m.train, m.nq_arr, m.nt_arr, m.nq_fixed,
+                           m.nt_fixed, m.q_frame_stride, m.t_frame_stride, m.train_frame_shift, m.chunk_len, m.n_chunks, m.exclude_self_mode,
+                           m.th, m.rnum, m.rden, m.out_stride, (match_partial *)m.partial, m.idx, m.d1, m.d2, tab...);
+    };
+    if (m.out_stride >= SSK_MATCH_MFMA_MIN_QUERIES) {
         /* many queries: the matrix-core form (the table form: NU = 1 only) */
-        const int nu = TABLE ? 1 : mm_tiles_per_wave(nt_fixed, n_frames);
-        dim3 grid((out_stride + MM_QBLOCK(nu) - 1) / MM_QBLOCK(nu), n_chunks, n_frames);
-        if (TABLE)
-            hipLaunchKernelGGL((k_match_mfma<1, mt_table>), grid, dim3(64 * MM_WAVES), 0, s, (const uint32_t *)query, (const uint32_t *)train, nq_arr,
-                               nt_arr, nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift, chunk_len,
-                               n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2, tab);
-        else if (nu == 2)
-            hipLaunchKernelGGL(k_match_mfma<2>, grid, dim3(64 * MM_WAVES), 0, s, (const uint32_t *)query, (const uint32_t *)train, nq_arr,
-                               nt_arr, nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift, chunk_len,
-                               n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2);
-        else
-            hipLaunchKernelGGL(k_match_mfma<1>, grid, dim3(64 * MM_WAVES), 0, s, (const uint32_t *)query, (const uint32_t *)train, nq_arr,
-                               nt_arr, nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift, chunk_len,
-                               n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2);
+        const int nu = m.tab ? 1 : mm_tiles_per_wave(m.nt_fixed, m.n_frames);
+        const dim3 grid((m.out_stride + MM_QBLOCK(nu) - 1) / MM_QBLOCK(nu), m.n_chunks, m.n_frames), block(64 * MM_WAVES);
+        if (m.tab) go(k_match_mfma<1, mt_table>, grid, block, m.table(true));
+        else if (nu == 2) go(k_match_mfma<2>, grid, block);
+        else go(k_match_mfma<1>, grid, block);
     } else {
-        dim3 grid((out_stride + 63) / 64, n_chunks, n_frames);
-        if (TABLE)
-            hipLaunchKernelGGL(k_match<mt_table>, grid, dim3(256), 0, s, (const uint32_t *)query, (const uint32_t *)train, nq_arr, nt_arr,
-                               nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift, chunk_len,
-                               n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2, tab);
-        else
-            hipLaunchKernelGGL(k_match<>, grid, dim3(256), 0, s, (const uint32_t *)query, (const uint32_t *)train, nq_arr, nt_arr,
-                               nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift, chunk_len,
-                               n_chunks, exclude_self_mode, th, rnum, rden, out_stride, (match_partial *)partial, idx, d1, d2);
+        const dim3 grid((m.out_stride + 63) / 64, m.n_chunks, m.n_frames);
+        if (m.tab) go(k_match<mt_table>, grid, dim3(256), m.table(true));
+        else go(k_match<>, grid, dim3(256));
     }
-    if (n_chunks >= 32 && n_frames == 1 && !nq_arr) {
-        hipLaunchKernelGGL(k_match_merge_wide, dim3(out_stride), dim3(64), 0, s, (const match_partial *)partial, nq_fixed, n_chunks,
-                           th, rnum, rden, out_stride, idx, d1, d2);
-    } else if (n_chunks > 1) {
-        dim3 g2((out_stride + 255) / 256, n_frames);
-        hipLaunchKernelGGL(k_match_merge, g2, dim3(256), 0, s, (const match_partial *)partial, nq_arr, nq_fixed,
-                           n_chunks, th, rnum, rden, out_stride, idx, d1, d2);
+    if (m.n_chunks >= 32 && m.n_frames == 1 && !m.nq_arr) {
+        hipLaunchKernelGGL(k_match_merge_wide, dim3(m.out_stride), dim3(64), 0, m.s, (const match_partial *)m.partial, m.nq_fixed, m.n_chunks,
+                           m.th, m.rnum, m.rden, m.out_stride, m.idx, m.d1, m.d2);
+    } else if (m.n_chunks > 1) {
+        const dim3 g2((m.out_stride + 255) / 256, m.n_frames);
+        hipLaunchKernelGGL(k_match_merge, g2, dim3(256), 0, m.s, (const match_partial *)m.partial, m.nq_arr, m.nq_fixed, m.n_chunks, m.th,
+                           m.rnum, m.rden, m.out_stride, m.idx, m.d1, m.d2);
     }
 }
 
@@ -3823,17 +3415,25 @@ void ssk_match(hipStream_t s, const void *query, const void *train, const int32_
                int train_frame_shift, int chunk_len, int n_chunks, int exclude_self_mode, int th, int rnum, int rden,
                int out_stride, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames)
 {
-    match_batch<false>(s, query, train, nq_arr, nt_arr, nq_fixed, nt_fixed, q_frame_stride_words, t_frame_stride_words, train_frame_shift,
-                       chunk_len, n_chunks, exclude_self_mode, th, rnum, rden, out_stride, partial, idx, d1, d2, n_frames, mt_table{});
+    match_call m;
+    m.s = s; m.n_frames = n_frames; m.query = query; m.train = train; m.q_frame_stride = q_frame_stride_words; m.t_frame_stride = t_frame_stride_words;
+    m.nq_arr = nq_arr; m.nt_arr = nt_arr; m.nq_fixed = nq_fixed; m.nt_fixed = nt_fixed;
+    m.train_frame_shift = train_frame_shift; m.exclude_self_mode = exclude_self_mode;
+    m.chunk_len = chunk_len; m.n_chunks = n_chunks; m.th = th; m.rnum = rnum; m.rden = rden;
+    m.out_stride = out_stride; m.partial = partial; m.idx = idx; m.d1 = d1; m.d2 = d2;
+    match_batch(m);
 }
 
 void ssk_match_table(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr,
                      int64_t q_frame_stride_words, int64_t t_frame_stride_words, int chunk_len, int n_chunks, int th, int rnum, int rden,
                      int out_stride, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames, const ssk_table &tab)
 {
-    const mt_table t{tab.src, (const uint8_t *)tab.carry_p, (const uint8_t *)tab.carry_p, tab.carry_n};
-    match_batch<true>(s, query, train, nq_arr, nt_arr, 0, 0, q_frame_stride_words, t_frame_stride_words, 0, chunk_len, n_chunks, 2, th, rnum,
-                      rden, out_stride, partial, idx, d1, d2, n_frames, t);
+    match_call m;
+    m.s = s; m.n_frames = n_frames; m.query = query; m.train = train; m.q_frame_stride = q_frame_stride_words; m.t_frame_stride = t_frame_stride_words;
+    m.nq_arr = nq_arr; m.nt_arr = nt_arr; m.exclude_self_mode = 2; m.tab = &tab;
+    m.chunk_len = chunk_len; m.n_chunks = n_chunks; m.th = th; m.rnum = rnum; m.rden = rden;
+    m.out_stride = out_stride; m.partial = partial; m.idx = idx; m.d1 = d1; m.d2 = d2;
+    match_batch(m);
 }
 
 /* database-streaming match for n_query <= 8 (see k_match_stream): plan (false = not applicable), kernel launch, merge

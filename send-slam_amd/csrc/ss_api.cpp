@@ -42,6 +42,18 @@ template <typename T> void dev_free(T *&p)
     p = nullptr;
 }
 
+/* a device buffer that grow() enlarges on demand: reads as its pointer */
+template <typename T> struct dev_buf {
+    T *p = nullptr;
+    size_t bytes = 0;
+    operator T *() const { return p; }
+};
+template <typename T> void dev_free(dev_buf<T> &b)
+{
+    dev_free(b.p);
+    b.bytes = 0;
+}
+
 } // namespace
 
 /* ss_track state of one camera: the tracker, the descriptors of its initialisation reference / previous frame, its own
@@ -51,10 +63,8 @@ struct cam_track {
     bool has_cam = false;
     ss_camera cam{};
     sst_tracker tracker;
-    uint8_t *d_ref_desc = nullptr, *d_prev_desc = nullptr;
-    size_t d_ref_desc_bytes = 0, d_prev_desc_bytes = 0;
-    uint8_t *d_ref_desc_x = nullptr, *d_prev_desc_x = nullptr; /* the same rows as matrix-core operands (128 B each) */
-    size_t d_ref_desc_x_bytes = 0, d_prev_desc_x_bytes = 0;
+    dev_buf<uint8_t> d_ref_desc, d_prev_desc;
+    dev_buf<uint8_t> d_ref_desc_x, d_prev_desc_x; /* the same rows as matrix-core operands (128 B each) */
     /* this camera's pose-step calls are numbered: which call's frame the tracker holds as its previous / reference frame, and
      * whether the previous frame's descriptors are still the caller's rows (ss_track_features_matched, prev_ext_n of them) */
     int64_t serial = 0, prev_serial = -1, ref_serial = -1;
@@ -67,6 +77,13 @@ struct cam_track {
         prev_serial = ref_serial = -1;
         d_prev_ext = nullptr;
         prev_ext_n = 0;
+    }
+    void free_rows()
+    {
+        dev_free(d_ref_desc);
+        dev_free(d_prev_desc);
+        dev_free(d_ref_desc_x);
+        dev_free(d_prev_desc_x);
     }
 };
 
@@ -107,21 +124,15 @@ struct ss_ctx {
     uint8_t *desc = nullptr;
     uint8_t *desc_x = nullptr; /* the descriptors as 256 FP4 values (+1 / -1) per row, 128 B: operand of the batch matcher */
 
-    uint8_t *d_in = nullptr;
-    size_t d_in_bytes = 0;
-    void *match_partial = nullptr;
-    size_t match_partial_bytes = 0;
-    uint8_t *d_mq = nullptr, *d_mt = nullptr, *d_mout = nullptr, *d_part_tmp = nullptr;
-    size_t d_mq_bytes = 0, d_mt_bytes = 0, d_mout_bytes = 0, d_part_tmp_bytes = 0;
-    uint8_t *d_qx = nullptr, *d_tx = nullptr; /* caller descriptors expanded to the matrix-core matcher's operand rows */
-    size_t d_qx_bytes = 0, d_tx_bytes = 0;
-    int32_t *d_train_src = nullptr; /* ss_match_batch_sources_device: the train table on the device */
-    size_t d_train_src_bytes = 0;
+    dev_buf<uint8_t> d_in;
+    dev_buf<void> match_partial;
+    dev_buf<uint8_t> d_mq, d_mt, d_mout, d_part_tmp;
+    dev_buf<uint8_t> d_qx, d_tx; /* caller descriptors expanded to the matrix-core matcher's operand rows */
+    dev_buf<int32_t> d_train_src; /* ss_match_batch_sources_device: the train table on the device */
     int32_t *h_train_src = nullptr; /* ... staged in pinned memory; the event marks the end of its last copy */
     int h_train_src_n = 0;
     hipEvent_t train_src_copied = nullptr;
-    uint8_t *d_carry_x = nullptr; /* its carry frames expanded to operand rows */
-    size_t d_carry_x_bytes = 0;
+    dev_buf<uint8_t> d_carry_x; /* its carry frames expanded to operand rows */
 
     /* host results of ss_extract */
     std::vector<ss_keypoint> h_kps;
@@ -131,13 +142,11 @@ struct ss_ctx {
     std::vector<ss_keypoint> h_kps_r;
     std::vector<uint8_t> h_desc_r;
     std::vector<ss_stereo_point> h_stereo;
-    uint8_t *d_stereo = nullptr;
-    size_t d_stereo_bytes = 0;
+    dev_buf<uint8_t> d_stereo;
     /* test hook, SENDSLAM_TEST_STEREO_FLAG=frame,...: the stereo stages see those frames of a batch as flagged (frame_error
      * SS_ERR_OVERFLOW, through a copy of the array), the only way to reach the voided-pair rule without overflowing a capacity */
     std::vector<int> stereo_test_flagged;
-    int32_t *d_stereo_err = nullptr;
-    size_t d_stereo_err_bytes = 0;
+    dev_buf<int32_t> d_stereo_err;
 
     int last_n_frames = 0;
     ss_lvl0 last_lvl0; /* where level 0 of the last batch lives (ptr == NULL: in the pyramid block) */
@@ -425,21 +434,40 @@ int check_frame_errors(ss_ctx *c)
     return SS_OK;
 }
 
-template <typename T> int grow(ss_ctx *c, T *&p, size_t &have, size_t want)
+template <typename T> int grow(ss_ctx *c, dev_buf<T> &b, size_t want)
 {
-    if (have >= want) return SS_OK;
+    if (b.bytes >= want) return SS_OK;
     (void)hipStreamSynchronize(c->stream);
-    dev_free(p);
-    have = 0;
-    HIP_TRY(c, hipMalloc((void **)&p, want));
-    have = want;
+    dev_free(b);
+    HIP_TRY(c, hipMalloc((void **)&b.p, want));
+    b.bytes = want;
+    return SS_OK;
+}
+
+/* the 8 bytes per query of a match scratch as the matcher's three outputs: idx [n] int32, then d1 [n] and d2 [n] uint16 */
+struct match_out {
+    int32_t *idx;
+    uint16_t *d1, *d2;
+};
+match_out split_scratch(uint8_t *p, int n) { return {(int32_t *)p, (uint16_t *)(p + (size_t)n * 4), (uint16_t *)(p + (size_t)n * 6)}; }
+
+/* One matcher call on c->stream: plan, grow match_partial to what the plan needs, launch inside a "match" stage of `bytes`
+ * algorithmic bytes.  The caller has filled everything but the stream, the partials and the plan. */
+int run_match(ss_ctx *c, ssk_match_call &m, int rows_q, int rows_t, int64_t bytes)
+{
+    m.s = c->stream;
+    const int rc = grow(c, c->match_partial, ssk_match_plan(m, rows_q, rows_t));
+    if (rc != SS_OK) return rc;
+    m.partial = c->match_partial;
+    {
+        stage_timer t(c, "match", bytes);
+        ssk_match(m);
+    }
+    HIP_TRY(c, hipGetLastError());
     return SS_OK;
 }
 
 } // namespace
-
-static int match_expanded(ss_ctx *c, const void *d_query_x, int n_query, const void *d_train_x, int n_train, int th, int ratio_num,
-                          int ratio_den, int exclude_self, void *d_idx, void *d_d1, void *d_d2, const uint8_t *q_packed, const uint8_t *t_packed);
 
 extern "C" {
 
@@ -474,11 +502,11 @@ static int detach_rows(ss_ctx *c, cam_track &ct)
 {
     if (!ct.d_prev_ext) return SS_OK;
     const int n = ct.prev_ext_n;
-    int rc = grow(c, ct.d_prev_desc, ct.d_prev_desc_bytes, (size_t)n * SS_DESC_BYTES);
+    int rc = grow(c, ct.d_prev_desc, (size_t)n * SS_DESC_BYTES);
     if (rc != SS_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(ct.d_prev_desc, ct.d_prev_ext, (size_t)n * SS_DESC_BYTES, hipMemcpyDeviceToDevice, c->stream));
     if (!c->no_desc_x) {
-        rc = grow(c, ct.d_prev_desc_x, ct.d_prev_desc_x_bytes, (size_t)SS_EXPANDED_BYTES(n));
+        rc = grow(c, ct.d_prev_desc_x, (size_t)SS_EXPANDED_BYTES(n));
         if (rc != SS_OK) return rc;
         ssk_expand_desc(c->stream, ct.d_prev_ext, n, ct.d_prev_desc_x);
         HIP_TRY(c, hipGetLastError());
@@ -578,12 +606,7 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_stereo_err);
     if (c->h_train_src) (void)hipHostFree(c->h_train_src);
     if (c->train_src_copied) (void)hipEventDestroy(c->train_src_copied);
-    for (cam_track &ct : c->cams) {
-        dev_free(ct.d_ref_desc);
-        dev_free(ct.d_prev_desc);
-        dev_free(ct.d_ref_desc_x);
-        dev_free(ct.d_prev_desc_x);
-    }
+    for (cam_track &ct : c->cams) ct.free_rows();
     (void)hipStreamDestroy(c->stream);
     delete c;
     return SS_OK;
@@ -627,7 +650,7 @@ int ss_extract(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int heig
     /* the last row of a tight caller buffer ends after width * channels bytes, not after row_stride */
     const size_t bytes = (size_t)row_stride * (height - 1) + (size_t)width * channels;
     const size_t alloc = ((size_t)row_stride * height + 15) & ~(size_t)15;
-    rc = grow(c, c->d_in, c->d_in_bytes, alloc);
+    rc = grow(c, c->d_in, alloc);
     if (rc != SS_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_in, pix, bytes, hipMemcpyHostToDevice, c->stream));
     /* the caller keeps ownership of pix: it is consumed before we return */
@@ -710,6 +733,35 @@ int ss_fetch_frame(ss_ctx *c, int frame, ss_frame_result *out)
     return SS_OK;
 }
 
+/* one query set against one train set: one frame, no strides, no count arrays */
+static ssk_match_call single_call(const void *d_query, int n_query, const void *d_train, int n_train, int exclude_self, int th, int ratio_num,
+                                  int ratio_den, void *d_idx, void *d_d1, void *d_d2)
+{
+    ssk_match_call m;
+    m.query = d_query, m.train = d_train ? d_train : d_query;
+    m.nq_fixed = m.out_stride = n_query, m.nt_fixed = n_train;
+    m.exclude_self_mode = exclude_self ? 1 : 0;
+    m.th = th, m.rnum = ratio_num, m.rden = ratio_den;
+    m.idx = (int32_t *)d_idx, m.d1 = (uint16_t *)d_d1, m.d2 = (uint16_t *)d_d2;
+    return m;
+}
+
+/* one expanded query set against one expanded train set (any size).  q_packed / t_packed: the same rows as packed descriptors
+ * when the caller has them (the finishing launch reads those) */
+static int match_expanded(ss_ctx *c, const void *d_query_x, int n_query, const void *d_train_x, int n_train, int th, int ratio_num,
+                          int ratio_den, int exclude_self, void *d_idx, void *d_d1, void *d_d2, const uint8_t *q_packed, const uint8_t *t_packed)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_query < 0 || n_train < 0 || ratio_den <= 0 || ratio_num < 0) return fail(c, SS_ERR_INVALID_ARG, "bad match arguments");
+    if (n_query == 0) return SS_OK;
+    if (!d_query_x || (!d_train_x && n_train > 0) || !d_idx || !d_d1 || !d_d2) return fail(c, SS_ERR_INVALID_ARG, "NULL match buffer");
+    ssk_match_call m = single_call(d_query_x, n_query, d_train_x, n_train, exclude_self, th, ratio_num, ratio_den, d_idx, d_d1, d_d2);
+    m.operand_rows = true;
+    m.query_p = q_packed, m.train_p = t_packed;
+    return run_match(c, m, n_query, std::max(n_train, 1), (int64_t)n_query * SSK_X_ROW + (int64_t)n_train * SSK_X_ROW + (int64_t)n_query * 8);
+}
+
 int ss_match_device(ss_ctx *c, const void *d_query, int n_query, const void *d_train, int n_train, int th,
                     int ratio_num, int ratio_den, int exclude_self, void *d_idx, void *d_d1, void *d_d2)
 {
@@ -720,10 +772,10 @@ int ss_match_device(ss_ctx *c, const void *d_query, int n_query, const void *d_t
     if (!d_query || (!d_train && n_train > 0) || !d_idx || !d_d1 || !d_d2) return fail(c, SS_ERR_INVALID_ARG, "NULL match buffer");
     if (n_query <= 8 && n_train >= 65536 && !exclude_self) {
         /* a handful of queries against a large database: stream the database once (HBM-bound) */
-        int rc = grow(c, c->match_partial, c->match_partial_bytes, (size_t)SSK_STREAM_PARTIAL_MAX);
+        int rc = grow(c, c->match_partial, (size_t)SSK_STREAM_PARTIAL_MAX);
         if (rc != SS_OK) return rc;
         int s_len = 0, s_chunks = 0;
-        if (ssk_match_stream_plan(n_query, n_train, c->match_partial_bytes, &s_len, &s_chunks)) {
+        if (ssk_match_stream_plan(n_query, n_train, c->match_partial.bytes, &s_len, &s_chunks)) {
             {
                 /* the kernel that reads the database exactly once: timed on its own (bench.py match_stream_roofline) */
                 stage_timer t(c, "match_stream_kernel", (int64_t)n_query * 32 + (int64_t)n_train * 32 + (int64_t)s_chunks * n_query * 8);
@@ -743,8 +795,8 @@ int ss_match_device(ss_ctx *c, const void *d_query, int n_query, const void *d_t
          * (k_expand_desc: 32 -> 128 bytes per row) and k_match_mfma_x runs on them.  SENDSLAM_MATCH_PACKED=1 keeps round 1's
          * k_match_mfma, which expands every tile in every query block through an LDS table. */
         const bool same = d_train == d_query && n_train == n_query;
-        int rc = grow(c, c->d_qx, c->d_qx_bytes, (size_t)SS_EXPANDED_BYTES(n_query));
-        if (rc == SS_OK && !same) rc = grow(c, c->d_tx, c->d_tx_bytes, (size_t)SS_EXPANDED_BYTES(n_train));
+        int rc = grow(c, c->d_qx, (size_t)SS_EXPANDED_BYTES(n_query));
+        if (rc == SS_OK && !same) rc = grow(c, c->d_tx, (size_t)SS_EXPANDED_BYTES(n_train));
         if (rc != SS_OK) return rc;
         {
             stage_timer t(c, "expand", ((int64_t)n_query + (same ? 0 : n_train)) * (32 + SSK_X_ROW));
@@ -754,20 +806,8 @@ int ss_match_device(ss_ctx *c, const void *d_query, int n_query, const void *d_t
         return match_expanded(c, c->d_qx, n_query, same ? c->d_qx : c->d_tx, n_train, th, ratio_num, ratio_den, exclude_self, d_idx, d_d1, d_d2,
                               (const uint8_t *)d_query, (const uint8_t *)d_train);
     }
-    int chunk_len = 4;
-    const int n_chunks = ssk_match_chunks(n_query, std::max(n_train, 1), 1, &chunk_len);
-    if (n_chunks > 1) {
-        int rc = grow(c, c->match_partial, c->match_partial_bytes, (size_t)n_chunks * n_query * SSK_MATCH_PARTIAL_BYTES);
-        if (rc != SS_OK) return rc;
-    }
-    {
-        stage_timer t(c, "match", (int64_t)n_query * 32 + (int64_t)n_train * 32 + (int64_t)n_query * 8);
-        ssk_match(c->stream, d_query, d_train ? d_train : d_query, nullptr, nullptr, n_query, n_train, 0, 0, 0, chunk_len,
-                  n_chunks, exclude_self ? 1 : 0, th, ratio_num, ratio_den, n_query, c->match_partial, (int32_t *)d_idx,
-                  (uint16_t *)d_d1, (uint16_t *)d_d2, 1);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return SS_OK;
+    ssk_match_call m = single_call(d_query, n_query, d_train, n_train, exclude_self, th, ratio_num, ratio_den, d_idx, d_d1, d_d2);
+    return run_match(c, m, n_query, std::max(n_train, 1), (int64_t)n_query * 32 + (int64_t)n_train * 32 + (int64_t)n_query * 8);
 }
 
 int ss_match(ss_ctx *c, const uint8_t *query, int n_query, const uint8_t *train, int n_train, int th, int ratio_num,
@@ -778,21 +818,45 @@ int ss_match(ss_ctx *c, const uint8_t *query, int n_query, const uint8_t *train,
     if (n_query < 0 || n_train < 0) return fail(c, SS_ERR_INVALID_ARG, "bad match arguments");
     if (n_query == 0) return SS_OK;
     if (!query || (!train && n_train > 0) || !idx || !d1 || !d2) return fail(c, SS_ERR_INVALID_ARG, "NULL match buffer");
-    int rc = grow(c, c->d_mq, c->d_mq_bytes, (size_t)n_query * 32);
-    if (rc == SS_OK) rc = grow(c, c->d_mt, c->d_mt_bytes, (size_t)std::max(n_train, 1) * 32);
-    if (rc == SS_OK) rc = grow(c, c->d_mout, c->d_mout_bytes, (size_t)n_query * 8);
+    int rc = grow(c, c->d_mq, (size_t)n_query * 32);
+    if (rc == SS_OK) rc = grow(c, c->d_mt, (size_t)std::max(n_train, 1) * 32);
+    if (rc == SS_OK) rc = grow(c, c->d_mout, (size_t)n_query * 8);
     if (rc != SS_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_mq, query, (size_t)n_query * 32, hipMemcpyHostToDevice, c->stream));
     if (n_train > 0) HIP_TRY(c, hipMemcpyAsync(c->d_mt, train, (size_t)n_train * 32, hipMemcpyHostToDevice, c->stream));
-    int32_t *di = (int32_t *)c->d_mout;
-    uint16_t *dd1 = (uint16_t *)(c->d_mout + (size_t)n_query * 4), *dd2 = (uint16_t *)(c->d_mout + (size_t)n_query * 6);
-    rc = ss_match_device(c, c->d_mq, n_query, c->d_mt, n_train, th, ratio_num, ratio_den, exclude_self, di, dd1, dd2);
+    const match_out o = split_scratch(c->d_mout, n_query);
+    rc = ss_match_device(c, c->d_mq, n_query, c->d_mt, n_train, th, ratio_num, ratio_den, exclude_self, o.idx, o.d1, o.d2);
     if (rc != SS_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(idx, di, (size_t)n_query * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d1, dd1, (size_t)n_query * 2, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d2, dd2, (size_t)n_query * 2, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(idx, o.idx, (size_t)n_query * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d1, o.d1, (size_t)n_query * 2, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d2, o.d2, (size_t)n_query * 2, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SS_OK;
+}
+
+/* the frames of the last batch against frames of the same batch: the extraction's rows, as operands where it wrote them */
+static ssk_match_call batch_call(ss_ctx *c, int th, int ratio_num, int ratio_den, void *d_idx, void *d_d1, void *d_d2)
+{
+    const int kcap = c->hg.kcap;
+    ssk_match_call m;
+    m.n_frames = c->last_n_frames;
+    m.operand_rows = c->desc_x != nullptr;
+    m.query = m.train = m.operand_rows ? c->desc_x : c->desc;
+    m.q_frame_stride = m.t_frame_stride = m.operand_rows ? (int64_t)kcap * SSK_X_ROW : (int64_t)kcap * 8;
+    if (m.operand_rows) {
+        m.query_p = m.train_p = c->desc;
+        m.qp_frame_stride = m.tp_frame_stride = (int64_t)kcap * SS_DESC_BYTES;
+    }
+    m.nq_arr = m.nt_arr = c->n_kp;
+    m.th = th, m.rnum = ratio_num, m.rden = ratio_den;
+    m.out_stride = kcap;
+    m.idx = (int32_t *)d_idx, m.d1 = (uint16_t *)d_d1, m.d2 = (uint16_t *)d_d2;
+    return m;
+}
+static int run_batch_match(ss_ctx *c, ssk_match_call &m)
+{
+    const int64_t nf = c->hg.n_features;
+    return run_match(c, m, c->hg.kcap, c->hg.kcap, (int64_t)m.n_frames * (nf * 32 * 2 + nf * 8));
 }
 
 int ss_match_batch_device(ss_ctx *c, int mode, int th, int ratio_num, int ratio_den, void *d_idx, void *d_d1, void *d_d2)
@@ -801,29 +865,10 @@ int ss_match_batch_device(ss_ctx *c, int mode, int th, int ratio_num, int ratio_
     (void)hipSetDevice(c->device);
     if (!c->have_geom || c->last_n_frames <= 0) return fail(c, SS_ERR_STATE, "no batch has been extracted");
     if ((mode != 0 && mode != 1) || !d_idx || !d_d1 || !d_d2 || ratio_den <= 0) return fail(c, SS_ERR_INVALID_ARG, "bad match arguments");
-    const int n = c->last_n_frames, kcap = c->hg.kcap;
-    int chunk_len = 4;
-    int n_chunks = ssk_match_chunks(kcap, kcap, n, &chunk_len);
-    if (c->desc_x) n_chunks = ssk_match_x_batch_chunks(kcap, kcap, n, &chunk_len);
-    if (n_chunks > 1 || c->desc_x) { /* the matrix-core matcher always writes partials: its second launch finishes them */
-        int rc = grow(c, c->match_partial, c->match_partial_bytes, (size_t)n * n_chunks * kcap * SSK_MATCH_PARTIAL_BYTES);
-        if (rc != SS_OK) return rc;
-    }
-    {
-        const int64_t nf = c->hg.n_features;
-        stage_timer t(c, "match", (int64_t)n * (nf * 32 * 2 + nf * 8));
-        if (c->desc_x)
-            ssk_match_x(c->stream, c->desc_x, c->desc_x, c->n_kp, c->n_kp, 0, 0, (int64_t)kcap * SSK_X_ROW, (int64_t)kcap * SSK_X_ROW,
-                        mode == 0 ? 0 : -1, chunk_len, n_chunks, mode == 0 ? 1 : 2, th, ratio_num, ratio_den, kcap,
-                        c->match_partial, (int32_t *)d_idx, (uint16_t *)d_d1, (uint16_t *)d_d2, n, c->desc, c->desc, (int64_t)kcap * SS_DESC_BYTES,
-                        (int64_t)kcap * SS_DESC_BYTES);
-        else
-            ssk_match(c->stream, c->desc, c->desc, c->n_kp, c->n_kp, 0, 0, (int64_t)kcap * 8, (int64_t)kcap * 8,
-                      mode == 0 ? 0 : -1, chunk_len, n_chunks, mode == 0 ? 1 : 2, th, ratio_num, ratio_den, kcap,
-                      c->match_partial, (int32_t *)d_idx, (uint16_t *)d_d1, (uint16_t *)d_d2, n);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return SS_OK;
+    ssk_match_call m = batch_call(c, th, ratio_num, ratio_den, d_idx, d_d1, d_d2);
+    m.train_frame_shift = mode == 0 ? 0 : -1;
+    m.exclude_self_mode = mode == 0 ? 1 : 2;
+    return run_batch_match(c, m);
 }
 
 int ss_match_batch_sources_device(ss_ctx *c, const int32_t *train_src, const void *d_carry, const void *d_carry_n, int n_carry, int th,
@@ -841,7 +886,7 @@ int ss_match_batch_sources_device(ss_ctx *c, const int32_t *train_src, const voi
             return fail(c, SS_ERR_INVALID_ARG, "train_src[" + std::to_string(b) + "] = " + std::to_string(t) + " names no frame of the batch (" +
                                                    std::to_string(n) + ") or of the carry (" + std::to_string(n_carry) + ")");
     }
-    int rc = grow(c, c->d_train_src, c->d_train_src_bytes, (size_t)n * sizeof(int32_t));
+    int rc = grow(c, c->d_train_src, (size_t)n * sizeof(int32_t));
     if (rc != SS_OK) return rc;
     /* the table travels through pinned memory, so the copy is asynchronous and the caller's array is free when this returns;
      * the previous call's copy has left the staging buffer before it is rewritten */
@@ -857,34 +902,18 @@ int ss_match_batch_sources_device(ss_ctx *c, const int32_t *train_src, const voi
     memcpy(c->h_train_src, train_src, (size_t)n * sizeof(int32_t));
     HIP_TRY(c, hipMemcpyAsync(c->d_train_src, c->h_train_src, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(c->train_src_copied, c->stream));
-    int chunk_len = 4;
-    int n_chunks = ssk_match_chunks(kcap, kcap, n, &chunk_len);
-    if (c->desc_x) n_chunks = ssk_match_x_batch_chunks(kcap, kcap, n, &chunk_len);
-    if (n_chunks > 1 || c->desc_x) {
-        rc = grow(c, c->match_partial, c->match_partial_bytes, (size_t)n * n_chunks * kcap * SSK_MATCH_PARTIAL_BYTES);
-        if (rc != SS_OK) return rc;
-    }
     ssk_table tab{c->d_train_src, d_carry, nullptr, (const int32_t *)d_carry_n};
     if (c->desc_x && n_carry > 0) { /* the carry as operand rows, at the batch's frame stride */
-        rc = grow(c, c->d_carry_x, c->d_carry_x_bytes, (size_t)n_carry * kcap * SSK_X_ROW);
+        rc = grow(c, c->d_carry_x, (size_t)n_carry * kcap * SSK_X_ROW);
         if (rc != SS_OK) return rc;
         stage_timer t(c, "expand", (int64_t)n_carry * kcap * (32 + SSK_X_ROW));
         ssk_expand_desc_frames(c->stream, d_carry, kcap, n_carry, c->d_carry_x);
         tab.carry_x = c->d_carry_x;
     }
-    {
-        const int64_t nf = c->hg.n_features;
-        stage_timer t(c, "match", (int64_t)n * (nf * 32 * 2 + nf * 8));
-        if (c->desc_x)
-            ssk_match_x_table(c->stream, c->desc_x, c->desc_x, c->n_kp, c->n_kp, (int64_t)kcap * SSK_X_ROW, (int64_t)kcap * SSK_X_ROW, chunk_len,
-                              n_chunks, th, ratio_num, ratio_den, kcap, c->match_partial, (int32_t *)d_idx, (uint16_t *)d_d1, (uint16_t *)d_d2, n,
-                              c->desc, c->desc, (int64_t)kcap * SS_DESC_BYTES, (int64_t)kcap * SS_DESC_BYTES, tab);
-        else
-            ssk_match_table(c->stream, c->desc, c->desc, c->n_kp, c->n_kp, (int64_t)kcap * 8, (int64_t)kcap * 8, chunk_len, n_chunks, th, ratio_num,
-                            ratio_den, kcap, c->match_partial, (int32_t *)d_idx, (uint16_t *)d_d1, (uint16_t *)d_d2, n, tab);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return SS_OK;
+    ssk_match_call m = batch_call(c, th, ratio_num, ratio_den, d_idx, d_d1, d_d2);
+    m.exclude_self_mode = 2;
+    m.tab = &tab;
+    return run_batch_match(c, m);
 }
 
 int ss_match_pairs_device(ss_ctx *c, const void *d_query, const void *d_n_query, const void *d_train, const void *d_n_train,
@@ -896,47 +925,36 @@ int ss_match_pairs_device(ss_ctx *c, const void *d_query, const void *d_n_query,
     if (n_frames < 0 || rows_per_frame < 1 || ratio_den <= 0 || ratio_num < 0) return fail(c, SS_ERR_INVALID_ARG, "bad match arguments");
     if (n_frames == 0) return SS_OK;
     if (!d_query || !d_n_query || !d_train || !d_n_train || !d_idx || !d_d1 || !d_d2) return fail(c, SS_ERR_INVALID_ARG, "NULL match buffer");
+    ssk_match_call m; /* per-frame counts on both sides, frame b against frame b */
+    m.n_frames = n_frames;
+    m.nq_arr = (const int32_t *)d_n_query, m.nt_arr = (const int32_t *)d_n_train;
+    m.th = th, m.rnum = ratio_num, m.rden = ratio_den;
+    m.out_stride = rows_per_frame;
+    m.idx = (int32_t *)d_idx, m.d1 = (uint16_t *)d_d1, m.d2 = (uint16_t *)d_d2;
     if (rows_per_frame >= SSK_MATCH_MFMA_MIN_QUERIES && !c->no_desc_x) {
         /* both sides expanded frame by frame ([n_frames][rows rounded up to 32][128 B]), then the batch matcher of the metric
          * path with per-frame counts on both sides */
         const int rows_alloc = (rows_per_frame + 31) & ~31;
         const size_t xb = (size_t)n_frames * rows_alloc * SSK_X_ROW;
-        int rc = grow(c, c->d_qx, c->d_qx_bytes, xb);
-        if (rc == SS_OK) rc = grow(c, c->d_tx, c->d_tx_bytes, xb);
-        if (rc != SS_OK) return rc;
-        int x_chunk = 32;
-        const int x_chunks = ssk_match_x_batch_chunks(rows_per_frame, rows_per_frame, n_frames, &x_chunk);
-        rc = grow(c, c->match_partial, c->match_partial_bytes, (size_t)n_frames * x_chunks * rows_per_frame * SSK_MATCH_PARTIAL_BYTES);
+        int rc = grow(c, c->d_qx, xb);
+        if (rc == SS_OK) rc = grow(c, c->d_tx, xb);
         if (rc != SS_OK) return rc;
         {
             stage_timer t(c, "expand", (int64_t)2 * n_frames * rows_per_frame * (32 + SSK_X_ROW));
             ssk_expand_desc_frames(c->stream, d_query, rows_per_frame, n_frames, c->d_qx);
             ssk_expand_desc_frames(c->stream, d_train, rows_per_frame, n_frames, c->d_tx);
         }
-        {
-            stage_timer t(c, "match", (int64_t)n_frames * rows_per_frame * (32 * 2 + 8));
-            ssk_match_x(c->stream, c->d_qx, c->d_tx, (const int32_t *)d_n_query, (const int32_t *)d_n_train, 0, 0, (int64_t)rows_alloc * SSK_X_ROW,
-                        (int64_t)rows_alloc * SSK_X_ROW, 0, x_chunk, x_chunks, 0, th, ratio_num, ratio_den, rows_per_frame, c->match_partial,
-                        (int32_t *)d_idx, (uint16_t *)d_d1, (uint16_t *)d_d2, n_frames, (const uint8_t *)d_query, (const uint8_t *)d_train,
-                        (int64_t)rows_per_frame * SS_DESC_BYTES, (int64_t)rows_per_frame * SS_DESC_BYTES);
-        }
-        HIP_TRY(c, hipGetLastError());
-        return SS_OK;
+        m.operand_rows = true;
+        m.query = c->d_qx, m.train = c->d_tx;
+        m.q_frame_stride = m.t_frame_stride = (int64_t)rows_alloc * SSK_X_ROW;
+        m.query_p = (const uint8_t *)d_query, m.train_p = (const uint8_t *)d_train;
+        m.qp_frame_stride = m.tp_frame_stride = (int64_t)rows_per_frame * SS_DESC_BYTES;
+    } else {
+        m.query = d_query, m.train = d_train;
+        m.q_frame_stride = m.t_frame_stride = (int64_t)rows_per_frame * 8;
+        m.nt_fixed = rows_per_frame;
     }
-    int chunk_len = 4;
-    const int n_chunks = ssk_match_chunks(rows_per_frame, rows_per_frame, n_frames, &chunk_len);
-    if (n_chunks > 1) {
-        int rc = grow(c, c->match_partial, c->match_partial_bytes, (size_t)n_frames * n_chunks * rows_per_frame * SSK_MATCH_PARTIAL_BYTES);
-        if (rc != SS_OK) return rc;
-    }
-    {
-        stage_timer t(c, "match", (int64_t)n_frames * rows_per_frame * (32 * 2 + 8));
-        ssk_match(c->stream, d_query, d_train, (const int32_t *)d_n_query, (const int32_t *)d_n_train, 0, rows_per_frame,
-                  (int64_t)rows_per_frame * 8, (int64_t)rows_per_frame * 8, 0, chunk_len, n_chunks, 0, th, ratio_num, ratio_den,
-                  rows_per_frame, c->match_partial, (int32_t *)d_idx, (uint16_t *)d_d1, (uint16_t *)d_d2, n_frames);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return SS_OK;
+    return run_match(c, m, rows_per_frame, rows_per_frame, (int64_t)n_frames * rows_per_frame * (32 * 2 + 8));
 }
 
 /* the pose half of the frame branch: device match against the initial / previous frame's descriptors, then the host
@@ -954,7 +972,7 @@ static int track_step(ss_ctx *c, cam_track &ct, double timestamp, const uint8_t 
     const int64_t serial = ++ct.serial;
     auto expanded = [&]() -> int {
         if (!use_x || d_desc_x) return SS_OK;
-        int rcx = grow(c, c->d_qx, c->d_qx_bytes, (size_t)SS_EXPANDED_BYTES(n));
+        int rcx = grow(c, c->d_qx, (size_t)SS_EXPANDED_BYTES(n));
         if (rcx != SS_OK) return rcx;
         stage_timer t(c, "expand", (int64_t)n * (32 + SSK_X_ROW));
         ssk_expand_desc(c->stream, d_desc, n, c->d_qx);
@@ -989,19 +1007,18 @@ static int track_step(ss_ctx *c, cam_track &ct, double timestamp, const uint8_t 
             const bool prev_ext = want == SST_MATCH_PREV && ct.d_prev_ext != nullptr;
             const uint8_t *train = want == SST_MATCH_REF ? ct.d_ref_desc : prev_ext ? ct.d_prev_ext : ct.d_prev_desc;
             const uint8_t *train_x = want == SST_MATCH_REF ? ct.d_ref_desc_x : prev_ext ? nullptr : ct.d_prev_desc_x;
-            rc = grow(c, c->d_mout, c->d_mout_bytes, (size_t)n * 8);
+            rc = grow(c, c->d_mout, (size_t)n * 8);
             if (rc != SS_OK) return rc;
-            int32_t *di = (int32_t *)c->d_mout;
-            uint16_t *dd1 = (uint16_t *)(c->d_mout + (size_t)n * 4), *dd2 = (uint16_t *)(c->d_mout + (size_t)n * 6);
+            const match_out o = split_scratch(c->d_mout, n);
             if (use_x && train_x && n >= SSK_MATCH_MFMA_MIN_QUERIES && tr.n_train() > 0) { /* both operands are expanded already */
                 rc = expanded();
-                if (rc == SS_OK) rc = match_expanded(c, d_desc_x, n, train_x, tr.n_train(), SS_TH_LOW, 9, 10, 0, di, dd1, dd2, d_desc, train);
+                if (rc == SS_OK) rc = match_expanded(c, d_desc_x, n, train_x, tr.n_train(), SS_TH_LOW, 9, 10, 0, o.idx, o.d1, o.d2, d_desc, train);
             } else {
-                rc = ss_match_device(c, d_desc, n, train, tr.n_train(), SS_TH_LOW, 9, 10, 0, di, dd1, dd2);
+                rc = ss_match_device(c, d_desc, n, train, tr.n_train(), SS_TH_LOW, 9, 10, 0, o.idx, o.d1, o.d2);
             }
             if (rc != SS_OK) return rc;
-            HIP_TRY(c, hipMemcpyAsync(c->h_midx.data(), di, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(c->h_md1.data(), dd1, (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->h_midx.data(), o.idx, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(c->h_md1.data(), o.d1, (size_t)n * 2, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
         }
     }
@@ -1036,17 +1053,15 @@ static int track_step(ss_ctx *c, cam_track &ct, double timestamp, const uint8_t 
         ct.d_prev_ext = d_desc; /* the caller keeps the rows alive until the next call has returned: nothing to copy */
         ct.prev_ext_n = n;
     } else if (keep != SST_KEEP_NONE && n > 0) {
-        uint8_t *&dst = keep == SST_KEEP_AS_REF ? ct.d_ref_desc : ct.d_prev_desc;
-        size_t &dst_bytes = keep == SST_KEEP_AS_REF ? ct.d_ref_desc_bytes : ct.d_prev_desc_bytes;
-        rc = grow(c, dst, dst_bytes, (size_t)n * SS_DESC_BYTES);
+        dev_buf<uint8_t> &dst = keep == SST_KEEP_AS_REF ? ct.d_ref_desc : ct.d_prev_desc;
+        rc = grow(c, dst, (size_t)n * SS_DESC_BYTES);
         if (rc != SS_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(dst, d_desc, (size_t)n * SS_DESC_BYTES, hipMemcpyDeviceToDevice, c->stream));
         if (use_x) {
             rc = expanded();
             if (rc != SS_OK) return rc;
-            uint8_t *&dst_x = keep == SST_KEEP_AS_REF ? ct.d_ref_desc_x : ct.d_prev_desc_x;
-            size_t &dst_x_bytes = keep == SST_KEEP_AS_REF ? ct.d_ref_desc_x_bytes : ct.d_prev_desc_x_bytes;
-            rc = grow(c, dst_x, dst_x_bytes, (size_t)SS_EXPANDED_BYTES(n));
+            dev_buf<uint8_t> &dst_x = keep == SST_KEEP_AS_REF ? ct.d_ref_desc_x : ct.d_prev_desc_x;
+            rc = grow(c, dst_x, (size_t)SS_EXPANDED_BYTES(n));
             if (rc != SS_OK) return rc;
             HIP_TRY(c, hipMemcpyAsync(dst_x, d_desc_x, (size_t)SS_EXPANDED_BYTES(n), hipMemcpyDeviceToDevice, c->stream));
         }
@@ -1064,54 +1079,6 @@ static int track_step(ss_ctx *c, cam_track &ct, double timestamp, const uint8_t 
     return SS_OK;
 }
 
-static int track_impl(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int height, int channels, int row_stride, double timestamp,
-                      ss_pose *out);
-static int track_features_impl(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
-                               int n_keypoints, ss_pose *out);
-static int track_features_matched_impl(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
-                                       int n_keypoints, const int32_t *match_idx, const uint16_t *match_d1, int flags, ss_pose *out);
-
-/* SS_TRACK_DESC_STAYS_VALID: the rows a camera refers to are valid until the next pose-step call on the context has
- * returned, whatever its outcome.  Every pose-step entry point therefore copies the rows of the other cameras first, and
- * those of its own camera when it fails (a call that reaches the tracker drops or replaces them, track_step). */
-extern "C++" template <typename F> static int pose_call(ss_ctx *c, int camera_id, F &&body)
-{
-    if (!c) return SS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    for (int i = 0; i < c->n_cams; i++)
-        if (c->cams[i].camera_id != camera_id) {
-            const int rcd = detach_rows(c, c->cams[i]);
-            if (rcd != SS_OK) return rcd;
-        }
-    const int rc = body();
-    if (rc != SS_OK)
-        if (cam_track *own = find_camera(c, camera_id)) {
-            const std::string why = c->err; /* the call's own error is what the caller sees */
-            (void)detach_rows(c, *own);
-            c->err = why;
-        }
-    return rc;
-}
-
-int ss_track(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int height, int channels, int row_stride,
-             double timestamp, ss_pose *out)
-{
-    return pose_call(c, camera_id, [&]() { return track_impl(c, camera_id, pix, width, height, channels, row_stride, timestamp, out); });
-}
-
-int ss_track_features(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
-                      int n_keypoints, ss_pose *out)
-{
-    return pose_call(c, camera_id, [&]() { return track_features_impl(c, camera_id, timestamp, d_descriptors, keypoints, n_keypoints, out); });
-}
-
-int ss_track_features_matched(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
-                              int n_keypoints, const int32_t *match_idx, const uint16_t *match_d1, int flags, ss_pose *out)
-{
-    return pose_call(c, camera_id, [&]() {
-        return track_features_matched_impl(c, camera_id, timestamp, d_descriptors, keypoints, n_keypoints, match_idx, match_d1, flags, out);
-    });
-}
 static int track_impl(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int height, int channels, int row_stride, double timestamp,
                       ss_pose *out)
 {
@@ -1161,6 +1128,47 @@ static int track_features_matched_impl(ss_ctx *c, int camera_id, double timestam
     return track_step(c, *ct, timestamp, (const uint8_t *)d_descriptors, nullptr, keypoints, n_keypoints, out, match_idx, match_d1, flags);
 }
 
+/* SS_TRACK_DESC_STAYS_VALID: the rows a camera refers to are valid until the next pose-step call on the context has
+ * returned, whatever its outcome.  Every pose-step entry point therefore copies the rows of the other cameras first, and
+ * those of its own camera when it fails (a call that reaches the tracker drops or replaces them, track_step). */
+extern "C++" template <typename F> static int pose_call(ss_ctx *c, int camera_id, F &&body)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    for (int i = 0; i < c->n_cams; i++)
+        if (c->cams[i].camera_id != camera_id) {
+            const int rcd = detach_rows(c, c->cams[i]);
+            if (rcd != SS_OK) return rcd;
+        }
+    const int rc = body();
+    if (rc != SS_OK)
+        if (cam_track *own = find_camera(c, camera_id)) {
+            const std::string why = c->err; /* the call's own error is what the caller sees */
+            (void)detach_rows(c, *own);
+            c->err = why;
+        }
+    return rc;
+}
+
+int ss_track(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int height, int channels, int row_stride,
+             double timestamp, ss_pose *out)
+{
+    return pose_call(c, camera_id, [&]() { return track_impl(c, camera_id, pix, width, height, channels, row_stride, timestamp, out); });
+}
+
+int ss_track_features(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
+                      int n_keypoints, ss_pose *out)
+{
+    return pose_call(c, camera_id, [&]() { return track_features_impl(c, camera_id, timestamp, d_descriptors, keypoints, n_keypoints, out); });
+}
+
+int ss_track_features_matched(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
+                              int n_keypoints, const int32_t *match_idx, const uint16_t *match_d1, int flags, ss_pose *out)
+{
+    return pose_call(c, camera_id, [&]() {
+        return track_features_matched_impl(c, camera_id, timestamp, d_descriptors, keypoints, n_keypoints, match_idx, match_d1, flags, out);
+    });
+}
 int ss_expand_descriptors_device(ss_ctx *c, const void *d_packed, int n, void *d_expanded)
 {
     if (!c) return SS_ERR_INVALID_ARG;
@@ -1180,31 +1188,6 @@ int ss_match_expanded_device(ss_ctx *c, const void *d_query_x, int n_query, cons
     return match_expanded(c, d_query_x, n_query, d_train_x, n_train, th, ratio_num, ratio_den, exclude_self, d_idx, d_d1, d_d2, nullptr, nullptr);
 }
 
-/* q_packed / t_packed: the same rows as packed descriptors when the caller has them (the finishing launch reads those) */
-static int match_expanded(ss_ctx *c, const void *d_query_x, int n_query, const void *d_train_x, int n_train, int th, int ratio_num,
-                          int ratio_den, int exclude_self, void *d_idx, void *d_d1, void *d_d2, const uint8_t *q_packed, const uint8_t *t_packed)
-{
-    if (!c) return SS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    if (n_query < 0 || n_train < 0 || ratio_den <= 0 || ratio_num < 0) return fail(c, SS_ERR_INVALID_ARG, "bad match arguments");
-    if (n_query == 0) return SS_OK;
-    if (!d_query_x || (!d_train_x && n_train > 0) || !d_idx || !d_d1 || !d_d2) return fail(c, SS_ERR_INVALID_ARG, "NULL match buffer");
-    int chunk_len = 32;
-    const int n_chunks = ssk_match_x_chunks(n_query, std::max(n_train, 1), &chunk_len);
-    {
-        int rc = grow(c, c->match_partial, c->match_partial_bytes, (size_t)n_chunks * n_query * SSK_MATCH_PARTIAL_BYTES);
-        if (rc != SS_OK) return rc;
-    }
-    {
-        stage_timer t(c, "match", (int64_t)n_query * SSK_X_ROW + (int64_t)n_train * SSK_X_ROW + (int64_t)n_query * 8);
-        ssk_match_x_single(c->stream, (const uint8_t *)d_query_x, n_query, (const uint8_t *)(d_train_x ? d_train_x : d_query_x), n_train,
-                           chunk_len, n_chunks, exclude_self, th, ratio_num, ratio_den, c->match_partial, (int32_t *)d_idx, (uint16_t *)d_d1,
-                           (uint16_t *)d_d2, q_packed, t_packed);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return SS_OK;
-}
-
 static int partial_common(ss_ctx *c, bool expanded, const void *d_query, int n_query, const void *d_train, int n_train,
                           int64_t row_offset, void *d_part)
 {
@@ -1214,14 +1197,13 @@ static int partial_common(ss_ctx *c, bool expanded, const void *d_query, int n_q
         return fail(c, SS_ERR_INVALID_ARG, "ss_match_partial_device: rows must fit 31 bits");
     if (n_query == 0) return SS_OK;
     if (!d_query || !d_part || (!d_train && n_train > 0)) return fail(c, SS_ERR_INVALID_ARG, "NULL match buffer");
-    int rc = grow(c, c->d_part_tmp, c->d_part_tmp_bytes, (size_t)n_query * 8);
+    int rc = grow(c, c->d_part_tmp, (size_t)n_query * 8);
     if (rc != SS_OK) return rc;
-    int32_t *di = (int32_t *)c->d_part_tmp;
-    uint16_t *dd1 = (uint16_t *)(c->d_part_tmp + (size_t)n_query * 4), *dd2 = (uint16_t *)(c->d_part_tmp + (size_t)n_query * 6);
-    rc = expanded ? ss_match_expanded_device(c, d_query, n_query, d_train, n_train, -1, 1, 1, 0, di, dd1, dd2)
-                  : ss_match_device(c, d_query, n_query, d_train, n_train, -1, 1, 1, 0, di, dd1, dd2);
+    const match_out o = split_scratch(c->d_part_tmp, n_query);
+    rc = expanded ? ss_match_expanded_device(c, d_query, n_query, d_train, n_train, -1, 1, 1, 0, o.idx, o.d1, o.d2)
+                  : ss_match_device(c, d_query, n_query, d_train, n_train, -1, 1, 1, 0, o.idx, o.d1, o.d2);
     if (rc != SS_OK) return rc;
-    ssk_pack_partial(c->stream, di, dd1, dd2, n_query, (int32_t)row_offset, d_part);
+    ssk_pack_partial(c->stream, o.idx, o.d1, o.d2, n_query, (int32_t)row_offset, d_part);
     HIP_TRY(c, hipGetLastError());
     return SS_OK;
 }
@@ -1283,19 +1265,18 @@ int ss_stereo_exchange_match(ss_ctx *c, ss_xchg *x, int peer_rank, int th, int r
     int64_t stride = 0;
     int rc = ss_xchg_allgather(x, c, segs, sizes, 2, &gathered, &stride);
     if (rc != SS_OK) return fail(c, rc, std::string("ss_stereo_exchange_match: ") + ss_xchg_last_error(x));
-    rc = grow(c, c->d_mout, c->d_mout_bytes, (size_t)kcap * 8);
+    rc = grow(c, c->d_mout, (size_t)kcap * 8);
     if (rc != SS_OK) return rc;
     const uint8_t *peer = (const uint8_t *)gathered + (int64_t)peer_rank * stride;
-    int32_t *di = (int32_t *)c->d_mout;
-    uint16_t *dd1 = (uint16_t *)(c->d_mout + (size_t)kcap * 4), *dd2 = (uint16_t *)(c->d_mout + (size_t)kcap * 6);
-    rc = ss_match_pairs_device(c, c->desc, c->n_kp, peer, peer + blk, 1, kcap, th, ratio_num, ratio_den, di, dd1, dd2);
+    const match_out o = split_scratch(c->d_mout, kcap);
+    rc = ss_match_pairs_device(c, c->desc, c->n_kp, peer, peer + blk, 1, kcap, th, ratio_num, ratio_den, o.idx, o.d1, o.d2);
     if (rc != SS_OK) return rc;
     int32_t counts[2] = {0, 0};
     HIP_TRY(c, hipMemcpyAsync(&counts[0], c->n_kp, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&counts[1], peer + blk, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (idx) HIP_TRY(c, hipMemcpyAsync(idx, di, (size_t)kcap * 4, hipMemcpyDeviceToHost, c->stream));
-    if (d1) HIP_TRY(c, hipMemcpyAsync(d1, dd1, (size_t)kcap * 2, hipMemcpyDeviceToHost, c->stream));
-    if (d2) HIP_TRY(c, hipMemcpyAsync(d2, dd2, (size_t)kcap * 2, hipMemcpyDeviceToHost, c->stream));
+    if (idx) HIP_TRY(c, hipMemcpyAsync(idx, o.idx, (size_t)kcap * 4, hipMemcpyDeviceToHost, c->stream));
+    if (d1) HIP_TRY(c, hipMemcpyAsync(d1, o.d1, (size_t)kcap * 2, hipMemcpyDeviceToHost, c->stream));
+    if (d2) HIP_TRY(c, hipMemcpyAsync(d2, o.d2, (size_t)kcap * 2, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     rc = ss_xchg_status(x);
     if (rc != SS_OK) return fail(c, rc, std::string("ss_stereo_exchange_match: ") + ss_xchg_last_error(x));
@@ -1337,7 +1318,7 @@ int ss_stereo_batch_device(ss_ctx *c, const ss_stereo_params *p, void *d_points,
     const int32_t *frame_error = c->frame_error;
     if (!c->stereo_test_flagged.empty()) {
         static const int32_t flagged = SS_ERR_OVERFLOW;
-        rc = grow(c, c->d_stereo_err, c->d_stereo_err_bytes, (size_t)c->last_n_frames * sizeof(int32_t));
+        rc = grow(c, c->d_stereo_err, (size_t)c->last_n_frames * sizeof(int32_t));
         if (rc != SS_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(c->d_stereo_err, c->frame_error, (size_t)c->last_n_frames * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
         for (int f : c->stereo_test_flagged)
@@ -1390,8 +1371,8 @@ int ss_extract_stereo(ss_ctx *c, int camera_id, const uint8_t *left, const uint8
     const ss_geom &g = c->hg;
     const size_t bytes = (size_t)row_stride * (height - 1) + (size_t)width * channels;
     const size_t alloc = ((size_t)row_stride * height + 15) & ~(size_t)15;
-    rc = grow(c, c->d_in, c->d_in_bytes, 2 * alloc);
-    if (rc == SS_OK) rc = grow(c, c->d_stereo, c->d_stereo_bytes, (size_t)g.kcap * sizeof(ss_stereo_point) + sizeof(ss_stereo_summary));
+    rc = grow(c, c->d_in, 2 * alloc);
+    if (rc == SS_OK) rc = grow(c, c->d_stereo, (size_t)g.kcap * sizeof(ss_stereo_point) + sizeof(ss_stereo_summary));
     if (rc != SS_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_in, left, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_in + alloc, right, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1463,10 +1444,7 @@ int ss_track_reset(ss_ctx *c)
     }
     for (int i = kept; i < c->n_cams; i++) {
         cam_track &ct = c->cams[i];
-        dev_free(ct.d_ref_desc);
-        dev_free(ct.d_prev_desc);
-        dev_free(ct.d_ref_desc_x);
-        dev_free(ct.d_prev_desc_x);
+        ct.free_rows();
         ct = cam_track();
     }
     c->n_cams = kept;
@@ -1604,10 +1582,10 @@ extern "C" int ss_debug_sort(ss_ctx *c, uint64_t *items, int n)
     if (!c || (!items && n > 0)) return SS_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
     if (n == 0) return SS_OK;
-    int rc = grow(c, c->d_mq, c->d_mq_bytes, (size_t)n * 8);
+    int rc = grow(c, c->d_mq, (size_t)n * 8);
     if (rc != SS_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_mq, items, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    if (ssk_debug_sort(c->stream, (uint64_t *)c->d_mq, n) != 0) return fail(c, SS_ERR_INVALID_ARG, "ss_debug_sort: n > 2048");
+    if (ssk_debug_sort(c->stream, (uint64_t *)c->d_mq.p, n) != 0) return fail(c, SS_ERR_INVALID_ARG, "ss_debug_sort: n > 2048");
     HIP_TRY(c, hipMemcpyAsync(items, c->d_mq, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SS_OK;

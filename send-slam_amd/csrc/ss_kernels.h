@@ -47,13 +47,52 @@ void ssk_orient_describe(hipStream_t s, const ss_geom *dg, const ss_geom &hg, co
 /* (moments, steer: [n_frames][kcap] 8-byte words between the three launches: the integer patch moments (m10, m01), then the
  * float (sin, cos) of the keypoint's angle) */
 
-/* train split so that a launch has >> 256 workgroups and local indices fit 16 bits */
-int ssk_match_chunks(int n_query_max, int n_train_max, int n_frames, int *chunk_len);
-/* strides in 32-bit words; exclude_self_mode: 0 never, 1 always, 2 when train frame == query frame */
-void ssk_match(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr,
-               int nq_fixed, int nt_fixed, int64_t q_frame_stride_words, int64_t t_frame_stride_words,
-               int train_frame_shift, int chunk_len, int n_chunks, int exclude_self_mode, int th, int rnum, int rden,
-               int out_stride, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames);
+/* Table form of a matcher call (ss_match_batch_sources_device): query frame b is matched against src[b] (device int32 [n_frames])
+ * instead of b + train_frame_shift.  src[b] >= 0: frame src[b] of the batch, the self pair excluded iff src[b] == b; -1: no train
+ * (idx -1, d1 / d2 0xFFFF); <= -2: carry frame -2 - src[b], with carry_n[c] rows, at the train's frame stride (carry_p packed
+ * 32-byte rows; carry_x expanded rows, needed on operand rows only).  Always the compact kernel forms. */
+struct ssk_table {
+    const int32_t *src;
+    const void *carry_p, *carry_x;
+    const int32_t *carry_n;
+};
+/* One batch or single matcher call, filled by field name.  Its rows are packed 32-byte descriptors (k_match, from
+ * SSK_MATCH_MFMA_MIN_QUERIES query rows per frame on k_match_mfma) or, with operand_rows, descriptors expanded to one FP4 value
+ * (+1 / -1) per bit (k_match_mfma_x; desc_x of ssk_orient_describe, ssk_expand_desc*: SSK_X_ROW bytes per row, multiples of 32
+ * rows allocated). */
+#define SSK_X_ROW 128
+struct ssk_match_call {
+    hipStream_t s = nullptr;
+    int n_frames = 1;
+    bool operand_rows = false;
+    const void *query = nullptr, *train = nullptr;           /* the rows the first launch reads */
+    int64_t q_frame_stride = 0, t_frame_stride = 0;          /* packed rows: in 32-bit words; operand rows: in BYTES */
+    /* operand rows: the same rows as packed descriptors where the caller has them, frame strides in bytes (the second launch,
+     * which recomputes 15 distances per query, then reads a quarter of the bytes; a single chunk finishes in the first) */
+    const uint8_t *query_p = nullptr, *train_p = nullptr;
+    int64_t qp_frame_stride = 0, tp_frame_stride = 0;
+    const int32_t *nq_arr = nullptr, *nt_arr = nullptr;      /* device row counts per frame, or null: nq_fixed / nt_fixed */
+    int nq_fixed = 0, nt_fixed = 0;
+    int train_frame_shift = 0;                               /* query frame b against train frame b + shift */
+    int exclude_self_mode = 0;                               /* 0 never, 1 always, 2 when train frame == query frame */
+    int th = 0, rnum = 0, rden = 0;                          /* the acceptance test */
+    int out_stride = 0;                                      /* rows per frame of partial, idx, d1, d2 */
+    void *partial = nullptr;                                 /* of the bytes ssk_match_plan returned */
+    int32_t *idx = nullptr;
+    uint16_t *d1 = nullptr, *d2 = nullptr;
+    const ssk_table *tab = nullptr;                          /* the table form: exclude_self_mode 2, no shift, counts per frame */
+    /* written by ssk_match_plan: the train split (a launch has >> 256 workgroups, local indices fit their bits) and the
+     * matrix-core kernel's form, k_match_mfma's NU or k_match_mfma_x compact (1) / pipelined (2) */
+    int chunk_len = 0, n_chunks = 0, tiles_per_wave = 1;
+};
+#define SSK_MATCH_PARTIAL_BYTES 8
+/* Plans a call of rows_q query against rows_t train rows per frame (operand rows: reads SENDSLAM_MX_FORM and SENDSLAM_MX_CHUNKS,
+ * once).  Returns the bytes of `partial` the launch needs, n_frames * n_chunks * out_stride records (operand rows: always;
+ * packed rows: with more than one chunk), or 0. */
+size_t ssk_match_plan(ssk_match_call &m, int rows_q, int rows_t);
+/* The launches of a planned call: the first kernel and, unless that finished its queries itself, the merge or finish of the
+ * chunk partials (one frame with fixed counts and >= 32 chunks: k_match_merge_wide before it or in its place). */
+void ssk_match(const ssk_match_call &m);
 /* (idx, d1, d2) of a raw match -> ss_match_part records with global rows (row_offset + idx) */
 void ssk_pack_partial(hipStream_t s, const int32_t *idx, const uint16_t *d1, const uint16_t *d2, int n, int32_t row_offset,
                       void *part);
@@ -62,32 +101,6 @@ void ssk_match_fold(hipStream_t s, const void *parts, int n_parts, int nq, int t
                     uint16_t *d1, uint16_t *d2);
 void ssk_match_fold_strided(hipStream_t s, const void *parts, int64_t part_stride_bytes, int n_parts, int nq, int th, int rnum, int rden,
                             int32_t *idx, uint16_t *d1, uint16_t *d2);
-/* the matrix-core matcher on descriptors already expanded to one FP4 value (+1 / -1) per bit (desc_x, SSK_X_ROW bytes per
- * row, written by ssk_orient_describe): batches of frames; frame strides in BYTES; multiples of 32 rows allocated */
-#define SSK_X_ROW 128
-void ssk_match_x(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
-                 int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift, int chunk_len,
-                 int n_chunks, int exclude_self_mode, int th, int rnum, int rden, int out_stride, void *partial, int32_t *idx,
-                 uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p = nullptr, const uint8_t *train_p = nullptr,
-                 int64_t qp_frame_stride = 0, int64_t tp_frame_stride = 0);
-/* (query_p / train_p: the same rows as packed 32-byte descriptors where the caller has them, frame strides in bytes: the second
- * launch, which recomputes 15 distances per query, then reads a quarter of the bytes) */
-/* Table form of the two batch matchers above (ss_match_batch_sources_device): query frame b is matched against src[b] (device
- * int32 [n_frames]) instead of b + shift.  src[b] >= 0: frame src[b] of the batch, the self pair excluded iff src[b] == b;
- * -1: no train (idx -1, d1 / d2 0xFFFF); <= -2: carry frame -2 - src[b], with carry_n[c] rows, at the train's frame stride
- * (carry_p packed 32-byte rows; carry_x expanded rows, needed by ssk_match_x_table only).  Always the compact kernel forms. */
-struct ssk_table {
-    const int32_t *src;
-    const void *carry_p, *carry_x;
-    const int32_t *carry_n;
-};
-void ssk_match_table(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr,
-                     int64_t q_frame_stride_words, int64_t t_frame_stride_words, int chunk_len, int n_chunks, int th, int rnum, int rden,
-                     int out_stride, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames, const ssk_table &tab);
-void ssk_match_x_table(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
-                       int64_t q_frame_stride, int64_t t_frame_stride, int chunk_len, int n_chunks, int th, int rnum, int rden, int out_stride,
-                       void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p,
-                       int64_t qp_frame_stride, int64_t tp_frame_stride, const ssk_table &tab);
 /* pipe match_mode 2: carry frame dst[i] <- batch frame src[i] (packed rows [kcap][32], row count clamped to kcap), i < n <=
  * SSK_CARRY_MAX, one launch */
 #define SSK_CARRY_MAX 8
@@ -97,13 +110,6 @@ void ssk_carry_gather(hipStream_t s, const void *desc, const int32_t *n_kp, int 
 void ssk_expand_desc(hipStream_t s, const void *packed, int n, void *out);
 /* [n_frames][rows][32] packed -> [n_frames][rows rounded up to 32][SSK_X_ROW] */
 void ssk_expand_desc_frames(hipStream_t s, const void *packed, int rows, int n_frames, void *out);
-/* one expanded query set against one expanded train set (any size): chunk plan + launch (+ merge of the chunk partials) */
-int ssk_match_x_chunks(int n_query, int n_train, int *chunk_len);
-/* chunk plan of a batch of frames (rows_q query rows against rows_t train rows per frame) */
-int ssk_match_x_batch_chunks(int rows_q, int rows_t, int n_frames, int *chunk_len);
-void ssk_match_x_single(hipStream_t s, const uint8_t *query_x, int nq, const uint8_t *train_x, int nt, int chunk_len, int n_chunks,
-                        int exclude_self, int th, int rnum, int rden, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2,
-                        const uint8_t *query_p = nullptr, const uint8_t *train_p = nullptr);
 /* ss_stereo.hip: stereo depth of the pairs (2p, 2p + 1) of a batch; points [n_pairs][kcap] ss_stereo_point, summary [n_pairs]
  * ss_stereo_summary.  search writes every row (right_idx / orb_dist or "none"), refine fills sad / u_right / depth of the
  * matched rows from the unblurred pyramids, cut applies the median test and writes the summaries */
@@ -115,8 +121,7 @@ void ssk_stereo_cut(hipStream_t s, const ss_geom *dg, const int32_t *n_kp, const
                     int n_pairs);
 /* test hook: run the device std::sort restatement on n <= 2048 items (size << 32 | UL.x << 20 | id) */
 int ssk_debug_sort(hipStream_t s, uint64_t *d_items, int n);
-#define SSK_MATCH_PARTIAL_BYTES 8
-#define SSK_MATCH_MFMA_MIN_QUERIES 128 /* from this many query rows on, ssk_match runs the matrix-core kernel */
+#define SSK_MATCH_MFMA_MIN_QUERIES 128 /* from this many query rows on, ssk_match runs a matrix-core kernel */
 /* database-streaming form for n_query <= 8 and n_train >= 65536: plan (false = not applicable), the HBM-bound kernel,
  * the merge of its per-chunk partials */
 bool ssk_match_stream_plan(int nq, int nt, size_t partial_bytes, int *chunk_len, int *n_chunks);

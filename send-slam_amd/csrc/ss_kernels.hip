@@ -3177,15 +3177,16 @@ void ssk_orient_describe(hipStream_t s, const ss_geom *dg, const ss_geom &hg, co
 /* which form of the matrix-core kernel: a single large database has the chip to itself (NU = 2), batches of frames share it */
 static int mm_tiles_per_wave(int n_train_max, int n_frames) { return n_frames == 1 && n_train_max >= 65536 ? 2 : 1; }
 
-int ssk_match_chunks(int n_query_max, int n_train_max, int n_frames, int *chunk_len)
+/* chunk plan on packed rows */
+static void mm_plan(ssk_match_call &m, int n_query_max, int n_train_max)
 {
     /* the matrix-core kernel: 256 queries per block, 2 resident blocks per CU, and a per-block prologue (table, query
      * fragments) that wants >= 8 tiles of 32 train rows behind it; the VALU kernel: 64 queries per block, 8 per CU */
     const bool mfma = n_query_max >= SSK_MATCH_MFMA_MIN_QUERIES;
-    const int qblock = MM_QBLOCK(mm_tiles_per_wave(n_train_max, n_frames));
+    const int qblock = MM_QBLOCK(mm_tiles_per_wave(n_train_max, m.n_frames));
     const int q_groups = mfma ? (n_query_max + qblock - 1) / qblock : (n_query_max + 63) / 64;
     const long blocks_wanted = mfma ? 2048 : 16384; /* >> resident blocks: keeps the last partial round of blocks small */
-    long chunks = (blocks_wanted + (long)q_groups * n_frames - 1) / ((long)q_groups * n_frames > 0 ? (long)q_groups * n_frames : 1);
+    long chunks = (blocks_wanted + (long)q_groups * m.n_frames - 1) / ((long)q_groups * m.n_frames > 0 ? (long)q_groups * m.n_frames : 1);
     const long max_chunks = (n_train_max + 255) / 256; /* >= 64 train rows per wave / >= 8 tiles per block */
     if (chunks > max_chunks) chunks = max_chunks;
     /* 16-bit local row index in the keys: per quarter-chunk of a wave in k_match, per chunk in k_match_mfma */
@@ -3196,53 +3197,58 @@ int ssk_match_chunks(int n_query_max, int n_train_max, int n_frames, int *chunk_
     int len = (int)(((long)n_train_max + chunks - 1) / chunks);
     len = mfma ? (len + MM_TILE - 1) & ~(MM_TILE - 1) : (len + 3) & ~3;
     if (len < 4) len = 4;
-    *chunk_len = len;
-    return (int)(((long)n_train_max + len - 1) / len > 0 ? ((long)n_train_max + len - 1) / len : 1);
+    m.chunk_len = len;
+    m.n_chunks = (int)(((long)n_train_max + len - 1) / len > 0 ? ((long)n_train_max + len - 1) / len : 1);
+    /* the launch's NU: from the fixed train count, which the batch of ss_match_batch_device leaves 0 */
+    m.tiles_per_wave = m.tab ? 1 : mm_tiles_per_wave(m.nt_fixed, m.n_frames);
 }
 
-/* which form of k_match_mfma_x: the pipelined one (two query tiles per wave, two waves per SIMD) for ONE query set against a
+/* chunk plan on operand rows: rows_q query rows and rows_t train rows per frame.  Once the query blocks alone fill the chip,
+ * one chunk per block (and the fused epilogue); fewer query blocks are spread over more chunks of >= 8 tiles, of <= 8192 rows
+ * (the key's row field).
+ * Which form of k_match_mfma_x: the pipelined one (two query tiles per wave, two waves per SIMD) for ONE query set against a
  * large train set, which has the chip to itself; the compact one (five waves per SIMD, 128-query blocks) for the frames of
  * a batch and for small sets, which share the chip with the other batches' kernels.  SENDSLAM_MX_FORM=compact|pipelined
- * overrides (A/B measurements). */
-static bool mx_pipelined(int n_frames, int rows_t)
+ * overrides (A/B measurements); the table form is planned like the others and launched compact. */
+static void mx_plan(ssk_match_call &m, int rows_q, int rows_t)
 {
-    if (const char *e = getenv("SENDSLAM_MX_FORM")) return e[0] == 'p';
-    return n_frames == 1 && rows_t >= 65536;
+    bool pipelined = m.n_frames == 1 && rows_t >= 65536;
+    if (const char *e = getenv("SENDSLAM_MX_FORM")) pipelined = e[0] == 'p';
+    const int qblock = pipelined ? MX_QBLOCK_OF(2) : MX_QBLOCK_OF(1);
+    const int q_groups = ((rows_q + qblock - 1) / qblock) * (m.n_frames > 0 ? m.n_frames : 1);
+    const int fill = pipelined ? 512 : 1024; /* resident blocks: 2 resp. 5 per CU */
+    int want = q_groups >= fill ? 1 : (2 * fill + q_groups / 2) / q_groups;
+    if (const char *e = getenv("SENDSLAM_MX_CHUNKS")) want = atoi(e); /* experiments */
+    const int max_chunks = (rows_t + 255) / 256;
+    if (want > max_chunks) want = max_chunks;
+    if (want < 1) want = 1;
+    int len = ((rows_t + want - 1) / want + MM_TILE - 1) & ~(MM_TILE - 1);
+    if (len > (1 << MX_ROW_BITS)) len = 1 << MX_ROW_BITS;
+    if (len < MM_TILE) len = MM_TILE;
+    m.chunk_len = len;
+    const int n = (rows_t + len - 1) / len;
+    m.n_chunks = n < 1 ? 1 : n;
+    m.tiles_per_wave = pipelined && !m.tab ? 2 : 1;
 }
 
-/* One matcher call as the host helpers below hand it on and spread it over the kernels' parameter lists; every public
- * ssk_match* entry point fills one.  Frame strides are in the unit of the rows they step over: words in ssk_match (packed
- * descriptors), bytes in ssk_match_x (FP4 operand rows, and the same rows as packed descriptors). */
-struct match_call {
-    hipStream_t s = nullptr;
-    int n_frames = 1;
-    const void *query = nullptr, *train = nullptr;             /* the rows the first launch reads */
-    int64_t q_frame_stride = 0, t_frame_stride = 0;
-    const uint8_t *query_p = nullptr, *train_p = nullptr;      /* ssk_match_x: the same rows as packed descriptors, or null */
-    int64_t qp_frame_stride = 0, tp_frame_stride = 0;
-    const int32_t *nq_arr = nullptr, *nt_arr = nullptr;        /* row counts per frame, or null: nq_fixed / nt_fixed */
-    int nq_fixed = 0, nt_fixed = 0;
-    int train_frame_shift = 0;
-    int chunk_len = 0, n_chunks = 0;                           /* the chunk plan */
-    int exclude_self_mode = 0;
-    int th = 0, rnum = 0, rden = 0;                            /* the acceptance test */
-    int out_stride = 0;
-    void *partial = nullptr;
-    int32_t *idx = nullptr;
-    uint16_t *d1 = nullptr, *d2 = nullptr;
-    const ssk_table *tab = nullptr;                            /* the table forms: where each query frame's train rows come from */
-    /* the kernels' table argument, the carry in the row format the launch reads: packed descriptors or FP4 operand rows */
-    mt_table table(bool packed) const
-    {
-        return mt_table{tab->src, (const uint8_t *)(packed ? tab->carry_p : tab->carry_x), (const uint8_t *)tab->carry_p, tab->carry_n};
-    }
-};
+size_t ssk_match_plan(ssk_match_call &m, int rows_q, int rows_t)
+{
+    if (m.operand_rows) mx_plan(m, rows_q, rows_t);
+    else mm_plan(m, rows_q, rows_t);
+    if (!m.operand_rows && m.n_chunks == 1) return 0; /* the matrix-core matcher on operand rows always writes partials */
+    return (size_t)m.n_frames * m.n_chunks * m.out_stride * SSK_MATCH_PARTIAL_BYTES;
+}
+
+/* the kernels' table argument, the carry in the row format the launch reads: packed descriptors or FP4 operand rows */
+static mt_table mt_table_of(const ssk_match_call &m, bool packed)
+{
+    return mt_table{m.tab->src, (const uint8_t *)(packed ? m.tab->carry_p : m.tab->carry_x), (const uint8_t *)m.tab->carry_p, m.tab->carry_n};
+}
 
 /* The FP4 matcher's first launch, k_match_mfma_x in the form `kernel` (blocks of qblock queries).  One chunk and packed
  * descriptors at hand: the FUSED forms finish their queries themselves and the outputs are final. */
-static bool mx_fused(const match_call &m) { return m.n_chunks == 1 && m.query_p && m.train_p; }
 template <typename K, typename... TAB>
-static void mx_launch(const match_call &m, K kernel, int qblock, TAB... tab)
+static void mx_launch(const ssk_match_call &m, K kernel, int qblock, TAB... tab)
 {
     const dim3 grid(((m.out_stride + qblock - 1) / qblock) * m.n_chunks * m.n_frames);
     const mx_finish fin{m.query_p, m.train_p, m.qp_frame_stride, m.tp_frame_stride, m.th, m.rnum, m.rden, m.idx, m.d1, m.d2};
@@ -3255,7 +3261,7 @@ static void mx_launch(const match_call &m, K kernel, int qblock, TAB... tab)
  * best inside the best row's group and applies the acceptance test.  packed: on the rows as packed descriptors (`kernel` is the
  * form for 32-byte rows), a quarter of the traffic. */
 template <typename K, typename... TAB>
-static void mx_finish_launch(const match_call &m, K kernel, bool packed, int n_chunks, TAB... tab)
+static void mx_finish_launch(const ssk_match_call &m, K kernel, bool packed, int n_chunks, TAB... tab)
 {
     hipLaunchKernelGGL(kernel, dim3((m.out_stride + 63) / 64, m.n_frames), dim3(256), 0, m.s, packed ? m.query_p : (const uint8_t *)m.query,
                        packed ? m.train_p : (const uint8_t *)m.train, m.nq_arr, m.nt_arr, m.nq_fixed, m.nt_fixed,
@@ -3264,81 +3270,32 @@ static void mx_finish_launch(const match_call &m, K kernel, bool packed, int n_c
                        tab...);
 }
 
-/* the table forms: the compact kernel only */
-static void mx_match_table(const match_call &m)
+/* one frame with fixed counts and many chunks: one wave per query folds them */
+static bool match_wide(const ssk_match_call &m) { return m.n_chunks >= 32 && m.n_frames == 1 && !m.nq_arr; }
+static void match_merge_wide(const ssk_match_call &m, int th, int rnum, int rden)
 {
-    const bool fused = mx_fused(m), packed = m.query_p && m.train_p;
-    const auto finish = packed ? k_match_finish_x<32, mt_table> : k_match_finish_x<SS_X_ROW, mt_table>;
-    const auto first = fused ? k_match_mfma_x<true, 1, false, mt_table> : k_match_mfma_x<false, 1, false, mt_table>;
-    mx_launch(m, first, MX_QBLOCK_OF(1), m.table(false));
-    if (!fused) mx_finish_launch(m, finish, packed, m.n_chunks, m.table(packed));
+    hipLaunchKernelGGL(k_match_merge_wide, dim3(m.out_stride), dim3(64), 0, m.s, (const match_partial *)m.partial, m.nq_fixed, m.n_chunks, th, rnum,
+                       rden, m.out_stride, m.idx, m.d1, m.d2);
 }
 
-/* the forms without a table: returns true when the first launch was the only one */
-static bool mx_match(const match_call &m, bool pipelined)
+/* on operand rows.  With several chunks two launches: k_match_mfma_x writes one partial per (query, chunk), k_match_finish_x
+ * finishes them. */
+static void mx_match(const ssk_match_call &m)
 {
-    const bool fused = mx_fused(m);
-    if (pipelined) mx_launch(m, fused ? k_match_mfma_x<true, 2, true> : k_match_mfma_x<false, 2, true>, MX_QBLOCK_OF(2));
+    const bool packed = m.query_p && m.train_p, fused = m.n_chunks == 1 && packed;
+    if (m.tab) { /* the compact kernel only */
+        const auto finish = packed ? k_match_finish_x<32, mt_table> : k_match_finish_x<SS_X_ROW, mt_table>;
+        const auto first = fused ? k_match_mfma_x<true, 1, false, mt_table> : k_match_mfma_x<false, 1, false, mt_table>;
+        mx_launch(m, first, MX_QBLOCK_OF(1), mt_table_of(m, false));
+        if (!fused) mx_finish_launch(m, finish, packed, m.n_chunks, mt_table_of(m, packed));
+        return;
+    }
+    if (m.tiles_per_wave == 2) mx_launch(m, fused ? k_match_mfma_x<true, 2, true> : k_match_mfma_x<false, 2, true>, MX_QBLOCK_OF(2));
     else mx_launch(m, fused ? k_match_mfma_x<true, 1, false> : k_match_mfma_x<false, 1, false>, MX_QBLOCK_OF(1));
-    return fused;
-}
-static void mx_finish_rows(const match_call &m, int n_chunks)
-{
-    const bool packed = m.query_p && m.train_p;
-    mx_finish_launch(m, packed ? k_match_finish_x<32> : k_match_finish_x<SS_X_ROW>, packed, n_chunks);
-}
-
-/* batch form on expanded descriptors (desc_x of the extraction): same arguments as ssk_match, strides in BYTES.  With several
- * chunks two launches: k_match_mfma_x writes one partial per (query, chunk), k_match_finish_x finishes them. */
-void ssk_match_x(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
-                 int nq_fixed, int nt_fixed, int64_t q_frame_stride, int64_t t_frame_stride, int train_frame_shift, int chunk_len,
-                 int n_chunks, int exclude_self_mode, int th, int rnum, int rden, int out_stride, void *partial, int32_t *idx,
-                 uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p, int64_t qp_frame_stride,
-                 int64_t tp_frame_stride)
-{
-    match_call m;
-    m.s = s; m.n_frames = n_frames; m.query = query_x; m.train = train_x; m.q_frame_stride = q_frame_stride; m.t_frame_stride = t_frame_stride;
-    m.query_p = query_p; m.train_p = train_p; m.qp_frame_stride = qp_frame_stride; m.tp_frame_stride = tp_frame_stride;
-    m.nq_arr = nq_arr; m.nt_arr = nt_arr; m.nq_fixed = nq_fixed; m.nt_fixed = nt_fixed;
-    m.train_frame_shift = train_frame_shift; m.exclude_self_mode = exclude_self_mode;
-    m.chunk_len = chunk_len; m.n_chunks = n_chunks; m.th = th; m.rnum = rnum; m.rden = rden;
-    m.out_stride = out_stride; m.partial = partial; m.idx = idx; m.d1 = d1; m.d2 = d2;
-    if (!mx_match(m, mx_pipelined(n_frames, out_stride))) mx_finish_rows(m, n_chunks);
-}
-
-void ssk_match_x_table(hipStream_t s, const uint8_t *query_x, const uint8_t *train_x, const int32_t *nq_arr, const int32_t *nt_arr,
-                       int64_t q_frame_stride, int64_t t_frame_stride, int chunk_len, int n_chunks, int th, int rnum, int rden, int out_stride,
-                       void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames, const uint8_t *query_p, const uint8_t *train_p,
-                       int64_t qp_frame_stride, int64_t tp_frame_stride, const ssk_table &tab)
-{
-    match_call m;
-    m.s = s; m.n_frames = n_frames; m.query = query_x; m.train = train_x; m.q_frame_stride = q_frame_stride; m.t_frame_stride = t_frame_stride;
-    m.query_p = query_p; m.train_p = train_p; m.qp_frame_stride = qp_frame_stride; m.tp_frame_stride = tp_frame_stride;
-    m.nq_arr = nq_arr; m.nt_arr = nt_arr; m.exclude_self_mode = 2; m.tab = &tab;
-    m.chunk_len = chunk_len; m.n_chunks = n_chunks; m.th = th; m.rnum = rnum; m.rden = rden;
-    m.out_stride = out_stride; m.partial = partial; m.idx = idx; m.d1 = d1; m.d2 = d2;
-    mx_match_table(m);
-}
-
-/* chunk plan: rows_q query rows and rows_t train rows per frame.  Once the query blocks alone fill the chip, one chunk per
- * block (and the fused epilogue); fewer query blocks are spread over more chunks of >= 8 tiles. */
-int ssk_match_x_batch_chunks(int rows_q, int rows_t, int n_frames, int *chunk_len)
-{
-    const bool pipelined = mx_pipelined(n_frames, rows_t);
-    const int qblock = pipelined ? MX_QBLOCK_OF(2) : MX_QBLOCK_OF(1);
-    const int q_groups = ((rows_q + qblock - 1) / qblock) * (n_frames > 0 ? n_frames : 1);
-    const int fill = pipelined ? 512 : 1024; /* resident blocks: 2 resp. 5 per CU */
-    int want = q_groups >= fill ? 1 : (2 * fill + q_groups / 2) / q_groups;
-    if (const char *e = getenv("SENDSLAM_MX_CHUNKS")) want = atoi(e); /* experiments */
-    const int max_chunks = (rows_t + 255) / 256;
-    if (want > max_chunks) want = max_chunks;
-    if (want < 1) want = 1;
-    int len = ((rows_t + want - 1) / want + MM_TILE - 1) & ~(MM_TILE - 1);
-    if (len > (1 << MX_ROW_BITS)) len = 1 << MX_ROW_BITS;
-    if (len < MM_TILE) len = MM_TILE;
-    *chunk_len = len;
-    const int n = (rows_t + len - 1) / len;
-    return n < 1 ? 1 : n;
+    if (fused) return;
+    const bool wide = match_wide(m);
+    if (wide) match_merge_wide(m, -1, 1, 1); /* raw: no acceptance test yet, the finish reads the outputs */
+    mx_finish_launch(m, packed ? k_match_finish_x<32> : k_match_finish_x<SS_X_ROW>, packed, wide ? 0 : m.n_chunks);
 }
 
 void ssk_expand_desc(hipStream_t s, const void *packed, int n, void *out)
@@ -3358,29 +3315,8 @@ void ssk_expand_desc_frames(hipStream_t s, const void *packed, int rows, int n_f
                            (int64_t)rows * 8, (int64_t)n_alloc * SS_X_ROW);
 }
 
-/* one query set against one (large) train set, both expanded: chunks of <= 8192 rows (the key's row field), the query
- * blocks of a chunk adjacent in the grid (one XCD streams the chunk once) */
-int ssk_match_x_chunks(int n_query, int n_train, int *chunk_len) { return ssk_match_x_batch_chunks(n_query, n_train, 1, chunk_len); }
-
-void ssk_match_x_single(hipStream_t s, const uint8_t *query_x, int nq, const uint8_t *train_x, int nt, int chunk_len, int n_chunks,
-                        int exclude_self, int th, int rnum, int rden, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2,
-                        const uint8_t *query_p, const uint8_t *train_p)
-{
-    match_call m; /* one frame: no strides, no count arrays */
-    m.s = s; m.query = query_x; m.train = train_x; m.query_p = query_p; m.train_p = train_p;
-    m.nq_fixed = nq; m.nt_fixed = nt; m.exclude_self_mode = exclude_self ? 1 : 0;
-    m.chunk_len = chunk_len; m.n_chunks = n_chunks; m.th = th; m.rnum = rnum; m.rden = rden;
-    m.out_stride = nq; m.partial = partial; m.idx = idx; m.d1 = d1; m.d2 = d2;
-    if (mx_match(m, mx_pipelined(1, nt))) return;
-    int fin_chunks = n_chunks;
-    if (n_chunks >= 32) { /* many chunks: one wave per query folds them (raw: no acceptance test yet), the finish reads the outputs */
-        hipLaunchKernelGGL(k_match_merge_wide, dim3(nq), dim3(64), 0, s, (const match_partial *)partial, nq, n_chunks, -1, 1, 1, nq, idx, d1, d2);
-        fin_chunks = 0;
-    }
-    mx_finish_rows(m, fin_chunks);
-}
-
-static void match_batch(const match_call &m)
+/* on packed rows */
+static void mm_match(const ssk_match_call &m)
 {
     /* k_match_mfma and k_match take the same arguments */
     auto go = [&](auto kernel, dim3 grid, dim3 block, auto... tab) {
@@ -3390,19 +3326,18 @@ static void match_batch(const match_call &m)
     };
     if (m.out_stride >= SSK_MATCH_MFMA_MIN_QUERIES) {
         /* many queries: the matrix-core form (the table form: NU = 1 only) */
-        const int nu = m.tab ? 1 : mm_tiles_per_wave(m.nt_fixed, m.n_frames);
+        const int nu = m.tiles_per_wave;
         const dim3 grid((m.out_stride + MM_QBLOCK(nu) - 1) / MM_QBLOCK(nu), m.n_chunks, m.n_frames), block(64 * MM_WAVES);
-        if (m.tab) go(k_match_mfma<1, mt_table>, grid, block, m.table(true));
+        if (m.tab) go(k_match_mfma<1, mt_table>, grid, block, mt_table_of(m, true));
         else if (nu == 2) go(k_match_mfma<2>, grid, block);
         else go(k_match_mfma<1>, grid, block);
     } else {
         const dim3 grid((m.out_stride + 63) / 64, m.n_chunks, m.n_frames);
-        if (m.tab) go(k_match<mt_table>, grid, dim3(256), m.table(true));
+        if (m.tab) go(k_match<mt_table>, grid, dim3(256), mt_table_of(m, true));
         else go(k_match<>, grid, dim3(256));
     }
-    if (m.n_chunks >= 32 && m.n_frames == 1 && !m.nq_arr) {
-        hipLaunchKernelGGL(k_match_merge_wide, dim3(m.out_stride), dim3(64), 0, m.s, (const match_partial *)m.partial, m.nq_fixed, m.n_chunks,
-                           m.th, m.rnum, m.rden, m.out_stride, m.idx, m.d1, m.d2);
+    if (match_wide(m)) {
+        match_merge_wide(m, m.th, m.rnum, m.rden);
     } else if (m.n_chunks > 1) {
         const dim3 g2((m.out_stride + 255) / 256, m.n_frames);
         hipLaunchKernelGGL(k_match_merge, g2, dim3(256), 0, m.s, (const match_partial *)m.partial, m.nq_arr, m.nq_fixed, m.n_chunks, m.th,
@@ -3410,30 +3345,10 @@ static void match_batch(const match_call &m)
     }
 }
 
-void ssk_match(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr,
-               int nq_fixed, int nt_fixed, int64_t q_frame_stride_words, int64_t t_frame_stride_words,
-               int train_frame_shift, int chunk_len, int n_chunks, int exclude_self_mode, int th, int rnum, int rden,
-               int out_stride, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames)
+void ssk_match(const ssk_match_call &m)
 {
-    match_call m;
-    m.s = s; m.n_frames = n_frames; m.query = query; m.train = train; m.q_frame_stride = q_frame_stride_words; m.t_frame_stride = t_frame_stride_words;
-    m.nq_arr = nq_arr; m.nt_arr = nt_arr; m.nq_fixed = nq_fixed; m.nt_fixed = nt_fixed;
-    m.train_frame_shift = train_frame_shift; m.exclude_self_mode = exclude_self_mode;
-    m.chunk_len = chunk_len; m.n_chunks = n_chunks; m.th = th; m.rnum = rnum; m.rden = rden;
-    m.out_stride = out_stride; m.partial = partial; m.idx = idx; m.d1 = d1; m.d2 = d2;
-    match_batch(m);
-}
-
-void ssk_match_table(hipStream_t s, const void *query, const void *train, const int32_t *nq_arr, const int32_t *nt_arr,
-                     int64_t q_frame_stride_words, int64_t t_frame_stride_words, int chunk_len, int n_chunks, int th, int rnum, int rden,
-                     int out_stride, void *partial, int32_t *idx, uint16_t *d1, uint16_t *d2, int n_frames, const ssk_table &tab)
-{
-    match_call m;
-    m.s = s; m.n_frames = n_frames; m.query = query; m.train = train; m.q_frame_stride = q_frame_stride_words; m.t_frame_stride = t_frame_stride_words;
-    m.nq_arr = nq_arr; m.nt_arr = nt_arr; m.exclude_self_mode = 2; m.tab = &tab;
-    m.chunk_len = chunk_len; m.n_chunks = n_chunks; m.th = th; m.rnum = rnum; m.rden = rden;
-    m.out_stride = out_stride; m.partial = partial; m.idx = idx; m.d1 = d1; m.d2 = d2;
-    match_batch(m);
+    if (m.operand_rows) mx_match(m);
+    else mm_match(m);
 }
 
 /* database-streaming match for n_query <= 8 (see k_match_stream): plan (false = not applicable), kernel launch, merge

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -102,27 +103,7 @@ struct ss_ctx {
     bool have_geom = false;
     ss_geom hg{};
     ss_host_tables tabs;
-    ss_geom *dg = nullptr;
-    ss_rtab *d_rtab = nullptr;
-    uint32_t *d_tiles2 = nullptr; /* per-tile records of the FAST kernel (SS_TILE_REC_WORDS each) */
-
-    uint8_t *pyr = nullptr, *blur = nullptr, *score = nullptr;
-    uint32_t *cell_cnt = nullptr;
-    uint16_t *d_cinfo = nullptr;
-    uint32_t *cand = nullptr, *qbuf0 = nullptr, *qbuf1 = nullptr;
-    uint32_t *bucket = nullptr; /* per cell: NMS survivors, unordered */
-    uint32_t *tsurv = nullptr, *thdr = nullptr; /* per 64x32 tile: survivor sub-lists and their count words */
-    uint32_t *d_cell_units = nullptr;
-    ss_qnode *nodes = nullptr;
-    int32_t *lists = nullptr;
-    uint32_t *sel = nullptr;
-    ss_level_state *state = nullptr;
-    uint32_t *kp_ref = nullptr;
-    void *od_moments = nullptr, *od_steer = nullptr; /* per slot, between the launches of ssk_orient_describe: (m10, m01), (sin, cos) */
-    int32_t *n_kp = nullptr, *level_counts = nullptr, *frame_error = nullptr;
-    ss_keypoint *kps = nullptr;
-    uint8_t *desc = nullptr;
-    uint8_t *desc_x = nullptr; /* the descriptors as 256 FP4 values (+1 / -1) per row, 128 B: operand of the batch matcher */
+    ssk_extract_ws ws; /* the device buffers of the extraction: ws_table below lists them with their sizes */
 
     dev_buf<uint8_t> d_in;
     dev_buf<void> match_partial;
@@ -242,36 +223,79 @@ void collect_events(ss_ctx *c)
     }
 }
 
+/* The buffers of c->ws in allocation order: the one place where their sizes live.  ensure_geometry, free_geometry_buffers and
+ * the first ss_debug_fetch(2) walk it (ws_alloc: one hipMalloc per buffer). */
+/* a group is allocated and uploaded in table order, then cleared: with the geometry; desc_x, after that group's clears; score, when
+ * ss_debug_fetch(2) first asks for it */
+enum ws_when { WS_GEOMETRY, WS_OPERANDS, WS_FIRST_USE };
+struct ws_buf {
+    void **p;
+    size_t bytes;      /* from the geometry and max_batch; 0: not allocated */
+    const void *host;  /* the host table whose host_bytes are uploaded, or NULL */
+    size_t host_bytes;
+    bool zero;         /* cleared once */
+    ws_when when;
+};
+std::array<ws_buf, 28> ws_table(ss_ctx *c)
+{
+    ssk_extract_ws &w = c->ws;
+    const ss_geom &g = c->hg;
+    const ss_host_tables &t = c->tabs;
+    const size_t B = (size_t)c->params.max_batch, K = B * g.kcap;
+    const size_t rtab = t.rtab.size() * sizeof(ss_rtab), tiles = t.tile_recs.size() * sizeof(uint32_t);
+    const size_t cinfo = t.cinfo.size() * sizeof(uint16_t), units = t.cell_units.size() * sizeof(uint32_t);
+    /* desc_x: zeroed once, a row that was never written contributes 0 to every dot product (and is masked out anyway) */
+    const bool operands = !c->no_desc_x && g.kcap >= SSK_MATCH_MFMA_MIN_QUERIES;
+#define WS(m) (void **)&w.m
+    return {{
+        {WS(dg), sizeof(ss_geom), &g, sizeof(ss_geom)},
+        {WS(rtab), std::max<size_t>(t.rtab.size(), 1) * sizeof(ss_rtab), t.rtab.data(), rtab},
+        {WS(tile_recs), tiles, t.tile_recs.data(), tiles},
+        {WS(pyr), B * g.block_bytes},
+        {WS(blur), B * g.block_bytes},
+        {WS(score), B * g.block_bytes, nullptr, 0, false, WS_FIRST_USE},
+        {WS(cinfo), cinfo, t.cinfo.data(), cinfo},
+        {WS(cell_cnt), B * g.n_cells * sizeof(uint32_t)},
+        {WS(cand), B * g.cand_total * sizeof(uint32_t)},
+        {WS(qbuf0), B * g.cand_total * sizeof(uint32_t)},
+        {WS(qbuf1), B * g.cand_total * sizeof(uint32_t)},
+        {WS(bucket), B * g.bucket_total * sizeof(uint32_t)},
+        {WS(tsurv), B * g.tiles2_total * (size_t)SS_TS_CAP * sizeof(uint32_t)},
+        {WS(thdr), B * g.tiles2_total * (size_t)SS_TS_HDR * sizeof(uint32_t)},
+        {WS(cell_units), units, t.cell_units.data(), units},
+        {WS(nodes), B * g.node_total * sizeof(ss_qnode)},
+        {WS(lists), B * g.item_total * 2 * sizeof(int32_t)},
+        {WS(sel), B * g.sel_total * sizeof(uint32_t)},
+        {WS(state), B * SS_MAX_LEVELS * sizeof(ss_level_state)},
+        {WS(kp_ref), K * 2 * sizeof(uint32_t)},
+        {WS(od_moments), K * sizeof(int2)},
+        {WS(od_steer), K * sizeof(float2)},
+        {WS(n_kp), B * sizeof(int32_t), nullptr, 0, true},
+        {WS(level_counts), B * SS_MAX_LEVELS * sizeof(int32_t)},
+        {WS(frame_error), B * sizeof(int32_t)},
+        {WS(kps), K * sizeof(ss_keypoint), nullptr, 0, true},
+        {WS(desc), K * SS_DESC_BYTES, nullptr, 0, true},
+        {WS(desc_x), operands ? K * SSK_X_ROW : 0, nullptr, 0, true, WS_OPERANDS},
+    }};
+#undef WS
+}
+
+int ws_alloc(ss_ctx *c, ws_when when)
+{
+    const auto table = ws_table(c);
+    for (const ws_buf &b : table) {
+        if (b.when != when || !b.bytes) continue;
+        HIP_TRY(c, hipMalloc(b.p, b.bytes));
+        if (b.host_bytes) HIP_TRY(c, hipMemcpy(*b.p, b.host, b.host_bytes, hipMemcpyHostToDevice));
+    }
+    for (const ws_buf &b : table)
+        if (b.when == when && b.bytes && b.zero) HIP_TRY(c, hipMemset(*b.p, 0, b.bytes));
+    return SS_OK;
+}
+
 void free_geometry_buffers(ss_ctx *c)
 {
-    dev_free(c->dg);
-    dev_free(c->d_rtab);
-    dev_free(c->d_tiles2);
-    dev_free(c->pyr);
-    dev_free(c->blur);
-    dev_free(c->score);
-    dev_free(c->d_cinfo);
-    dev_free(c->cell_cnt);
-    dev_free(c->cand);
-    dev_free(c->qbuf0);
-    dev_free(c->qbuf1);
-    dev_free(c->bucket);
-    dev_free(c->tsurv);
-    dev_free(c->thdr);
-    dev_free(c->d_cell_units);
-    dev_free(c->nodes);
-    dev_free(c->lists);
-    dev_free(c->sel);
-    dev_free(c->state);
-    dev_free(c->kp_ref);
-    dev_free(c->od_moments);
-    dev_free(c->od_steer);
-    dev_free(c->n_kp);
-    dev_free(c->level_counts);
-    dev_free(c->frame_error);
-    dev_free(c->kps);
-    dev_free(c->desc);
-    dev_free(c->desc_x);
+    for (const ws_buf &b : ws_table(c)) dev_free(*b.p);
     c->have_geom = false;
 }
 
@@ -297,48 +321,9 @@ int ensure_geometry(ss_ctx *c, int w, int h)
         for (int l = 1; l + 1 < g.n_levels && e && atoi(e);)
             if (ssk_resize_pair_fits(g, c->tabs.rtab.data(), l)) { c->resize_pair[l] = true; l += 2; } else l += 1;
     }
-    const size_t B = (size_t)c->params.max_batch;
-    HIP_TRY(c, hipMalloc((void **)&c->dg, sizeof(ss_geom)));
-    HIP_TRY(c, hipMemcpy(c->dg, &g, sizeof(ss_geom), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMalloc((void **)&c->d_rtab, std::max<size_t>(c->tabs.rtab.size(), 1) * sizeof(ss_rtab)));
-    if (!c->tabs.rtab.empty())
-        HIP_TRY(c, hipMemcpy(c->d_rtab, c->tabs.rtab.data(), c->tabs.rtab.size() * sizeof(ss_rtab), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMalloc((void **)&c->d_tiles2, c->tabs.tile_recs.size() * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemcpy(c->d_tiles2, c->tabs.tile_recs.data(), c->tabs.tile_recs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMalloc((void **)&c->pyr, B * g.block_bytes));
-    HIP_TRY(c, hipMalloc((void **)&c->blur, B * g.block_bytes));
-    /* c->score (the FAST response map) is allocated by the first ss_debug_fetch(2): no kernel reads it */
-    HIP_TRY(c, hipMalloc((void **)&c->d_cinfo, c->tabs.cinfo.size() * sizeof(uint16_t)));
-    HIP_TRY(c, hipMemcpy(c->d_cinfo, c->tabs.cinfo.data(), c->tabs.cinfo.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMalloc((void **)&c->cell_cnt, B * g.n_cells * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->cand, B * g.cand_total * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->qbuf0, B * g.cand_total * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->qbuf1, B * g.cand_total * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->bucket, B * g.bucket_total * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->tsurv, B * g.tiles2_total * (size_t)SS_TS_CAP * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->thdr, B * g.tiles2_total * (size_t)SS_TS_HDR * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->d_cell_units, c->tabs.cell_units.size() * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemcpy(c->d_cell_units, c->tabs.cell_units.data(), c->tabs.cell_units.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMalloc((void **)&c->nodes, B * g.node_total * sizeof(ss_qnode)));
-    HIP_TRY(c, hipMalloc((void **)&c->lists, B * g.item_total * 2 * sizeof(int32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->sel, B * g.sel_total * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->state, B * SS_MAX_LEVELS * sizeof(ss_level_state)));
-    HIP_TRY(c, hipMalloc((void **)&c->kp_ref, B * g.kcap * 2 * sizeof(uint32_t))); /* (reference, record) per output slot */
-    HIP_TRY(c, hipMalloc(&c->od_moments, B * g.kcap * 8));
-    HIP_TRY(c, hipMalloc(&c->od_steer, B * g.kcap * 8));
-    HIP_TRY(c, hipMalloc((void **)&c->n_kp, B * sizeof(int32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->level_counts, B * SS_MAX_LEVELS * sizeof(int32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->frame_error, B * sizeof(int32_t)));
-    HIP_TRY(c, hipMalloc((void **)&c->kps, B * g.kcap * sizeof(ss_keypoint)));
-    HIP_TRY(c, hipMalloc((void **)&c->desc, B * g.kcap * SS_DESC_BYTES));
-    HIP_TRY(c, hipMemset(c->n_kp, 0, B * sizeof(int32_t)));
-    HIP_TRY(c, hipMemset(c->kps, 0, B * g.kcap * sizeof(ss_keypoint)));
-    HIP_TRY(c, hipMemset(c->desc, 0, B * g.kcap * SS_DESC_BYTES));
-    if (!c->no_desc_x && g.kcap >= SSK_MATCH_MFMA_MIN_QUERIES) {
-        /* zeroed once: a row that was never written contributes 0 to every dot product (and is masked out anyway) */
-        HIP_TRY(c, hipMalloc((void **)&c->desc_x, B * g.kcap * SSK_X_ROW));
-        HIP_TRY(c, hipMemset(c->desc_x, 0, B * g.kcap * SSK_X_ROW));
-    }
+    rc = ws_alloc(c, WS_GEOMETRY);
+    if (rc == SS_OK) rc = ws_alloc(c, WS_OPERANDS);
+    if (rc != SS_OK) return rc;
     c->have_geom = true;
     c->last_n_frames = 0;
     return SS_OK;
@@ -354,7 +339,7 @@ int run_extract(ss_ctx *c, const void *d_pix, int n, int channels, int64_t row_s
     int64_t all_px = 0;
     for (int l = 0; l < g.n_levels; l++) all_px += level_px(g, l);
 
-    HIP_TRY(c, hipMemsetAsync(c->state, 0, (size_t)n * SS_MAX_LEVELS * sizeof(ss_level_state), s));
+    HIP_TRY(c, hipMemsetAsync(c->ws.state, 0, (size_t)n * SS_MAX_LEVELS * sizeof(ss_level_state), s));
     /* A 1-channel image whose base, rows and frames are 16-byte aligned IS pyramid level 0: the kernels read it in
      * place (aligned dword loads work on it as they do on the pyramid block) and the ingest copy is skipped.  The
      * caller's buffer must stay untouched until the batch has finished (it is asynchronous, as before). */
@@ -376,16 +361,16 @@ int run_extract(ss_ctx *c, const void *d_pix, int n, int channels, int64_t row_s
             c2 = rgb ? SS_GRAY_BY : SS_GRAY_RY;
         }
         stage_timer t(c, "ingest", n * level_px(g, 0) * (channels + 1));
-        ssk_ingest(s, d_pix, channels, row_stride, frame_stride, c0, c1, c2, c->pyr, c->dg, g, n);
+        ssk_ingest(s, c->ws, g, n, d_pix, channels, row_stride, frame_stride, c0, c1, c2);
     }
     for (int l = 1; l < g.n_levels;) {
         if (c->resize_pair[l]) { /* two pyramid steps, the middle level never read back */
             stage_timer t(c, "resize", n * (level_px(g, l - 1) + level_px(g, l) + level_px(g, l + 1)));
-            ssk_resize_pair(s, c->pyr, c->dg, g, c->d_rtab, l, n, l0);
+            ssk_resize_pair(s, c->ws, g, n, l, l0);
             l += 2;
         } else {
             stage_timer t(c, "resize", n * (level_px(g, l - 1) + level_px(g, l)));
-            ssk_resize(s, c->pyr, c->dg, g, c->d_rtab, l, n, l0);
+            ssk_resize(s, c->ws, g, n, l, l0);
             l += 1;
         }
     }
@@ -393,27 +378,20 @@ int run_extract(ss_ctx *c, const void *d_pix, int n, int channels, int64_t row_s
         /* algorithmic bytes: read the pyramid once, write the blurred pyramid (the score map and the
          * survivor lists are this design's own intermediates) */
         stage_timer t(c, "fast_blur_nms", n * 2 * all_px);
-        ssk_fast_blur_nms(s, c->pyr, c->score, c->blur, c->dg, g, c->d_tiles2, c->d_cinfo, c->tsurv, c->thdr, c->state, n, l0);
+        ssk_fast_blur_nms(s, c->ws, g, n, l0);
     }
-    {
-        stage_timer t(c, "bucket_gather", 0);
-        ssk_bucket_gather(s, c->dg, g, c->d_cell_units, c->tsurv, c->thdr, c->bucket, c->cell_cnt, c->state, n);
-    }
-    {
-        stage_timer t(c, "cells_emit", 0);
-        ssk_cells_emit(s, c->bucket, c->dg, g, c->cell_cnt, c->cand, c->state, n);
-    }
-    {
-        stage_timer t(c, "quadtree", 0);
-        ssk_quadtree(s, c->dg, g, c->cand, c->qbuf0, c->qbuf1, c->nodes, c->lists, c->sel, c->state, n);
-    }
-    {
-        stage_timer t(c, "slots", 0);
-        ssk_slots(s, c->dg, c->sel, c->state, c->kp_ref, c->n_kp, c->level_counts, c->frame_error, n);
+    /* the stages between them take nothing per call */
+    static const struct {
+        const char *name;
+        void (*launch)(hipStream_t, const ssk_extract_ws &, const ss_geom &, int);
+    } mid[] = {{"bucket_gather", ssk_bucket_gather}, {"cells_emit", ssk_cells_emit}, {"quadtree", ssk_quadtree}, {"slots", ssk_slots}};
+    for (const auto &m : mid) {
+        stage_timer t(c, m.name, 0);
+        m.launch(s, c->ws, g, n);
     }
     {
         stage_timer t(c, "orient_describe", (int64_t)n * g.n_features * (709 + 512 + 32 + 24));
-        ssk_orient_describe(s, c->dg, g, c->pyr, c->blur, c->sel, c->kp_ref, c->n_kp, c->kps, c->desc, n, l0, c->params.steer_fma != 0, c->desc_x, c->od_moments, c->od_steer);
+        ssk_orient_describe(s, c->ws, g, n, l0, c->params.steer_fma != 0);
     }
     HIP_TRY(c, hipGetLastError());
     c->last_n_frames = n;
@@ -425,7 +403,7 @@ int check_frame_errors(ss_ctx *c)
     const int n = c->last_n_frames;
     if (n <= 0) return SS_OK;
     c->h_err.resize((size_t)n);
-    HIP_TRY(c, hipMemcpyAsync(c->h_err.data(), c->frame_error, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_err.data(), c->ws.frame_error, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n; i++)
         if (c->h_err[i] != 0)
@@ -634,46 +612,75 @@ int ss_set_calibration(ss_ctx *c, int camera_id, const ss_camera *cam)
     return SS_OK;
 }
 
+/* The image-argument checks of the extraction entry points, in their order of precedence; `no_image` and `small` are the entry
+ * point's own wording of the first and the last one.  A single image is one frame of frame_stride row_stride * height. */
+static int check_image_args(ss_ctx *c, bool have_pixels, int n_frames, int width, int height, int channels, int64_t row_stride,
+                            int64_t frame_stride, bool needs_calibration, const char *no_image, const char *small)
+{
+    if (!have_pixels || n_frames < 1 || width <= 0 || height <= 0) return fail(c, SS_ERR_BAD_FRAME, no_image);
+    if (n_frames > c->params.max_batch) return fail(c, SS_ERR_INVALID_ARG, "n_frames exceeds max_batch of this context");
+    if (channels != 1 && channels != 3 && channels != 4) return fail(c, SS_ERR_BAD_FRAME, "unsupported channel count");
+    if (needs_calibration && channels != 1 && !c->calibrated)
+        return fail(c, SS_ERR_NOT_CALIBRATED, "Received frame before calibration. Ignoring.");
+    if (row_stride < (int64_t)width * channels || frame_stride < row_stride * height) return fail(c, SS_ERR_BAD_FRAME, small);
+    return SS_OK;
+}
+
+/* upload footprint of one host image: the last row of a tight caller buffer ends after width * channels bytes, not after
+ * row_stride; frames lie `alloc` (16-byte rounded) apart in d_in */
+struct upload_size {
+    size_t bytes, alloc;
+};
+static upload_size upload_footprint(int width, int height, int channels, int row_stride)
+{
+    return {(size_t)row_stride * (height - 1) + (size_t)width * channels, ((size_t)row_stride * height + 15) & ~(size_t)15};
+}
+
+/* frame f's nk keypoints and descriptors -> the host vectors, which *out then points to; the copies are asynchronous on
+ * c->stream and out->level_counts is the caller's */
+static int fetch_rows(ss_ctx *c, int f, int32_t nk, std::vector<ss_keypoint> &kps, std::vector<uint8_t> &desc, int camera_id, double timestamp,
+                      ss_frame_result *out)
+{
+    const size_t row0 = (size_t)f * c->hg.kcap;
+    kps.resize((size_t)std::max(nk, 1));
+    desc.resize((size_t)std::max(nk, 1) * SS_DESC_BYTES);
+    if (nk > 0) {
+        HIP_TRY(c, hipMemcpyAsync(kps.data(), c->ws.kps + row0, (size_t)nk * sizeof(ss_keypoint), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(desc.data(), c->ws.desc + row0 * SS_DESC_BYTES, (size_t)nk * SS_DESC_BYTES, hipMemcpyDeviceToHost, c->stream));
+    }
+    out->n_keypoints = nk;
+    out->camera_id = camera_id;
+    out->timestamp = timestamp;
+    out->keypoints = kps.data();
+    out->descriptors = desc.data();
+    return SS_OK;
+}
+
 int ss_extract(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int height, int channels, int row_stride,
                double timestamp, ss_frame_result *out)
 {
     if (!c || !out) return SS_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
     if (camera_id == 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing camera identifier.");
-    if (!pix || width <= 0 || height <= 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing binary image data.");
-    if (channels != 1 && channels != 3 && channels != 4) return fail(c, SS_ERR_BAD_FRAME, "unsupported channel count");
-    if (channels != 1 && !c->calibrated)
-        return fail(c, SS_ERR_NOT_CALIBRATED, "Received frame before calibration. Ignoring.");
-    if (row_stride < width * channels) return fail(c, SS_ERR_BAD_FRAME, "row_stride smaller than a row");
-    int rc = ensure_geometry(c, width, height);
+    int rc = check_image_args(c, pix != nullptr, 1, width, height, channels, row_stride, (int64_t)row_stride * height, true,
+                              "Frame message missing binary image data.", "row_stride smaller than a row");
+    if (rc == SS_OK) rc = ensure_geometry(c, width, height);
     if (rc != SS_OK) return rc;
-    /* the last row of a tight caller buffer ends after width * channels bytes, not after row_stride */
-    const size_t bytes = (size_t)row_stride * (height - 1) + (size_t)width * channels;
-    const size_t alloc = ((size_t)row_stride * height + 15) & ~(size_t)15;
-    rc = grow(c, c->d_in, alloc);
+    const upload_size up = upload_footprint(width, height, channels, row_stride);
+    rc = grow(c, c->d_in, up.alloc);
     if (rc != SS_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_in, pix, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_in, pix, up.bytes, hipMemcpyHostToDevice, c->stream));
     /* the caller keeps ownership of pix: it is consumed before we return */
     const cam_track *own = find_camera(c, camera_id);
-    rc = run_extract(c, c->d_in, 1, channels, row_stride, (int64_t)alloc, own && own->has_cam ? (own->cam.rgb != 0) : -1);
+    rc = run_extract(c, c->d_in, 1, channels, row_stride, (int64_t)up.alloc, own && own->has_cam ? (own->cam.rgb != 0) : -1);
     if (rc != SS_OK) return rc;
     int32_t nk = 0;
-    HIP_TRY(c, hipMemcpyAsync(&nk, c->n_kp, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out->level_counts, c->level_counts, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&nk, c->ws.n_kp, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->level_counts, c->ws.level_counts, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     rc = check_frame_errors(c); /* synchronises */
+    if (rc == SS_OK) rc = fetch_rows(c, 0, nk, c->h_kps, c->h_desc, camera_id, timestamp, out);
     if (rc != SS_OK) return rc;
-    c->h_kps.resize((size_t)std::max(nk, 1));
-    c->h_desc.resize((size_t)std::max(nk, 1) * SS_DESC_BYTES);
-    if (nk > 0) {
-        HIP_TRY(c, hipMemcpyAsync(c->h_kps.data(), c->kps, (size_t)nk * sizeof(ss_keypoint), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->h_desc.data(), c->desc, (size_t)nk * SS_DESC_BYTES, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    out->n_keypoints = nk;
-    out->camera_id = camera_id;
-    out->timestamp = timestamp;
-    out->keypoints = c->h_kps.data();
-    out->descriptors = c->h_desc.data();
+    if (nk > 0) HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }
 
@@ -682,14 +689,9 @@ int ss_extract_batch_device(ss_ctx *c, const void *d_pix, int n_frames, int widt
 {
     if (!c) return SS_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
-    if (!d_pix || n_frames < 1 || width <= 0 || height <= 0) return fail(c, SS_ERR_BAD_FRAME, "empty batch");
-    if (n_frames > c->params.max_batch) return fail(c, SS_ERR_INVALID_ARG, "n_frames exceeds max_batch of this context");
-    if (channels != 1 && channels != 3 && channels != 4) return fail(c, SS_ERR_BAD_FRAME, "unsupported channel count");
-    if (channels != 1 && !c->calibrated)
-        return fail(c, SS_ERR_NOT_CALIBRATED, "Received frame before calibration. Ignoring.");
-    if (row_stride < (int64_t)width * channels || frame_stride < row_stride * height)
-        return fail(c, SS_ERR_BAD_FRAME, "strides smaller than the frame");
-    int rc = ensure_geometry(c, width, height);
+    int rc = check_image_args(c, d_pix != nullptr, n_frames, width, height, channels, row_stride, frame_stride, true, "empty batch",
+                              "strides smaller than the frame");
+    if (rc == SS_OK) rc = ensure_geometry(c, width, height);
     if (rc != SS_OK) return rc;
     return run_extract(c, d_pix, n_frames, channels, row_stride, frame_stride);
 }
@@ -700,11 +702,11 @@ int ss_get_batch_view(ss_ctx *c, ss_batch_view *out)
     if (!c->have_geom || c->last_n_frames <= 0) return fail(c, SS_ERR_STATE, "no batch has been extracted");
     out->n_frames = c->last_n_frames;
     out->kp_capacity = c->hg.kcap;
-    out->keypoints = c->kps;
-    out->descriptors = c->desc;
-    out->n_keypoints = c->n_kp;
-    out->level_counts = c->level_counts;
-    out->frame_error = c->frame_error;
+    out->keypoints = c->ws.kps;
+    out->descriptors = c->ws.desc;
+    out->n_keypoints = c->ws.n_kp;
+    out->level_counts = c->ws.level_counts;
+    out->frame_error = c->ws.frame_error;
     return SS_OK;
 }
 
@@ -715,21 +717,14 @@ int ss_fetch_frame(ss_ctx *c, int frame, ss_frame_result *out)
     if (!c->have_geom || frame < 0 || frame >= c->last_n_frames) return fail(c, SS_ERR_STATE, "ss_fetch_frame: no such frame");
     int rc = check_frame_errors(c);
     if (rc != SS_OK) return rc;
-    const int kcap = c->hg.kcap;
     int32_t nk = 0;
-    HIP_TRY(c, hipMemcpy(&nk, c->n_kp + frame, sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(out->level_counts, c->level_counts + (size_t)frame * SS_MAX_LEVELS, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost));
-    c->h_kps.resize((size_t)std::max(nk, 1));
-    c->h_desc.resize((size_t)std::max(nk, 1) * SS_DESC_BYTES);
-    if (nk > 0) {
-        HIP_TRY(c, hipMemcpy(c->h_kps.data(), c->kps + (size_t)frame * kcap, (size_t)nk * sizeof(ss_keypoint), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(c->h_desc.data(), c->desc + (size_t)frame * kcap * SS_DESC_BYTES, (size_t)nk * SS_DESC_BYTES, hipMemcpyDeviceToHost));
-    }
-    out->n_keypoints = nk;
-    out->camera_id = c->cam_id;
-    out->timestamp = 0.0;
-    out->keypoints = c->h_kps.data();
-    out->descriptors = c->h_desc.data();
+    HIP_TRY(c, hipMemcpyAsync(&nk, c->ws.n_kp + frame, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out->level_counts, c->ws.level_counts + (size_t)frame * SS_MAX_LEVELS, SS_MAX_LEVELS * sizeof(int32_t),
+                              hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    rc = fetch_rows(c, frame, nk, c->h_kps, c->h_desc, c->cam_id, 0.0, out);
+    if (rc != SS_OK) return rc;
+    if (nk > 0) HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }
 
@@ -746,16 +741,28 @@ static ssk_match_call single_call(const void *d_query, int n_query, const void *
     return m;
 }
 
+/* the argument guard of a single match on device rows: true when the call ends here, with *rc (an error, or no query to match) */
+static bool match_ends(ss_ctx *c, const void *d_query, int n_query, const void *d_train, int n_train, int ratio_num, int ratio_den,
+                       const void *d_idx, const void *d_d1, const void *d_d2, int *rc)
+{
+    *rc = SS_OK;
+    if (!c) {
+        *rc = SS_ERR_INVALID_ARG;
+    } else {
+        (void)hipSetDevice(c->device);
+        if (n_query < 0 || n_train < 0 || ratio_den <= 0 || ratio_num < 0) *rc = fail(c, SS_ERR_INVALID_ARG, "bad match arguments");
+        else if (n_query > 0 && (!d_query || (!d_train && n_train > 0) || !d_idx || !d_d1 || !d_d2)) *rc = fail(c, SS_ERR_INVALID_ARG, "NULL match buffer");
+    }
+    return *rc != SS_OK || n_query == 0;
+}
+
 /* one expanded query set against one expanded train set (any size).  q_packed / t_packed: the same rows as packed descriptors
  * when the caller has them (the finishing launch reads those) */
 static int match_expanded(ss_ctx *c, const void *d_query_x, int n_query, const void *d_train_x, int n_train, int th, int ratio_num,
                           int ratio_den, int exclude_self, void *d_idx, void *d_d1, void *d_d2, const uint8_t *q_packed, const uint8_t *t_packed)
 {
-    if (!c) return SS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    if (n_query < 0 || n_train < 0 || ratio_den <= 0 || ratio_num < 0) return fail(c, SS_ERR_INVALID_ARG, "bad match arguments");
-    if (n_query == 0) return SS_OK;
-    if (!d_query_x || (!d_train_x && n_train > 0) || !d_idx || !d_d1 || !d_d2) return fail(c, SS_ERR_INVALID_ARG, "NULL match buffer");
+    int rc;
+    if (match_ends(c, d_query_x, n_query, d_train_x, n_train, ratio_num, ratio_den, d_idx, d_d1, d_d2, &rc)) return rc;
     ssk_match_call m = single_call(d_query_x, n_query, d_train_x, n_train, exclude_self, th, ratio_num, ratio_den, d_idx, d_d1, d_d2);
     m.operand_rows = true;
     m.query_p = q_packed, m.train_p = t_packed;
@@ -765,14 +772,11 @@ static int match_expanded(ss_ctx *c, const void *d_query_x, int n_query, const v
 int ss_match_device(ss_ctx *c, const void *d_query, int n_query, const void *d_train, int n_train, int th,
                     int ratio_num, int ratio_den, int exclude_self, void *d_idx, void *d_d1, void *d_d2)
 {
-    if (!c) return SS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    if (n_query < 0 || n_train < 0 || ratio_den <= 0 || ratio_num < 0) return fail(c, SS_ERR_INVALID_ARG, "bad match arguments");
-    if (n_query == 0) return SS_OK;
-    if (!d_query || (!d_train && n_train > 0) || !d_idx || !d_d1 || !d_d2) return fail(c, SS_ERR_INVALID_ARG, "NULL match buffer");
+    int rc;
+    if (match_ends(c, d_query, n_query, d_train, n_train, ratio_num, ratio_den, d_idx, d_d1, d_d2, &rc)) return rc;
     if (n_query <= 8 && n_train >= 65536 && !exclude_self) {
         /* a handful of queries against a large database: stream the database once (HBM-bound) */
-        int rc = grow(c, c->match_partial, (size_t)SSK_STREAM_PARTIAL_MAX);
+        rc = grow(c, c->match_partial, (size_t)SSK_STREAM_PARTIAL_MAX);
         if (rc != SS_OK) return rc;
         int s_len = 0, s_chunks = 0;
         if (ssk_match_stream_plan(n_query, n_train, c->match_partial.bytes, &s_len, &s_chunks)) {
@@ -795,7 +799,7 @@ int ss_match_device(ss_ctx *c, const void *d_query, int n_query, const void *d_t
          * (k_expand_desc: 32 -> 128 bytes per row) and k_match_mfma_x runs on them.  SENDSLAM_MATCH_PACKED=1 keeps round 1's
          * k_match_mfma, which expands every tile in every query block through an LDS table. */
         const bool same = d_train == d_query && n_train == n_query;
-        int rc = grow(c, c->d_qx, (size_t)SS_EXPANDED_BYTES(n_query));
+        rc = grow(c, c->d_qx, (size_t)SS_EXPANDED_BYTES(n_query));
         if (rc == SS_OK && !same) rc = grow(c, c->d_tx, (size_t)SS_EXPANDED_BYTES(n_train));
         if (rc != SS_OK) return rc;
         {
@@ -840,14 +844,14 @@ static ssk_match_call batch_call(ss_ctx *c, int th, int ratio_num, int ratio_den
     const int kcap = c->hg.kcap;
     ssk_match_call m;
     m.n_frames = c->last_n_frames;
-    m.operand_rows = c->desc_x != nullptr;
-    m.query = m.train = m.operand_rows ? c->desc_x : c->desc;
+    m.operand_rows = c->ws.desc_x != nullptr;
+    m.query = m.train = m.operand_rows ? c->ws.desc_x : c->ws.desc;
     m.q_frame_stride = m.t_frame_stride = m.operand_rows ? (int64_t)kcap * SSK_X_ROW : (int64_t)kcap * 8;
     if (m.operand_rows) {
-        m.query_p = m.train_p = c->desc;
+        m.query_p = m.train_p = c->ws.desc;
         m.qp_frame_stride = m.tp_frame_stride = (int64_t)kcap * SS_DESC_BYTES;
     }
-    m.nq_arr = m.nt_arr = c->n_kp;
+    m.nq_arr = m.nt_arr = c->ws.n_kp;
     m.th = th, m.rnum = ratio_num, m.rden = ratio_den;
     m.out_stride = kcap;
     m.idx = (int32_t *)d_idx, m.d1 = (uint16_t *)d_d1, m.d2 = (uint16_t *)d_d2;
@@ -903,7 +907,7 @@ int ss_match_batch_sources_device(ss_ctx *c, const int32_t *train_src, const voi
     HIP_TRY(c, hipMemcpyAsync(c->d_train_src, c->h_train_src, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipEventRecord(c->train_src_copied, c->stream));
     ssk_table tab{c->d_train_src, d_carry, nullptr, (const int32_t *)d_carry_n};
-    if (c->desc_x && n_carry > 0) { /* the carry as operand rows, at the batch's frame stride */
+    if (c->ws.desc_x && n_carry > 0) { /* the carry as operand rows, at the batch's frame stride */
         rc = grow(c, c->d_carry_x, (size_t)n_carry * kcap * SSK_X_ROW);
         if (rc != SS_OK) return rc;
         stage_timer t(c, "expand", (int64_t)n_carry * kcap * (32 + SSK_X_ROW));
@@ -1097,31 +1101,20 @@ static int track_impl(ss_ctx *c, int camera_id, const uint8_t *pix, int width, i
     rc = camera_slot(c, camera_id, &ct);
     if (rc != SS_OK) return rc;
     /* this frame's descriptors are still in HBM (frame 0 of the batch arrays) */
-    return track_step(c, *ct, timestamp, c->desc, c->desc_x, res.keypoints, res.n_keypoints, out);
+    return track_step(c, *ct, timestamp, c->ws.desc, c->ws.desc_x, res.keypoints, res.n_keypoints, out);
 }
 
-static int track_features_impl(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
-                               int n_keypoints, ss_pose *out)
+/* the body of ss_track_features_matched, and of ss_track_features (`who`) with no matches and no flags */
+static int track_features_impl(ss_ctx *c, const char *who, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
+                               int n_keypoints, const int32_t *match_idx, const uint16_t *match_d1, int flags, ss_pose *out)
 {
+    const std::string name = who;
     if (!out || n_keypoints < 0) return SS_ERR_INVALID_ARG;
     if (!c->calibrated) return fail(c, SS_ERR_NOT_CALIBRATED, "Received frame before calibration. Ignoring.");
     if (camera_id == 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing camera identifier.");
-    if (n_keypoints > 0 && (!d_descriptors || !keypoints)) return fail(c, SS_ERR_INVALID_ARG, "ss_track_features: NULL feature arrays");
-    cam_track *ct = nullptr;
-    const int rc = camera_slot(c, camera_id, &ct);
-    if (rc != SS_OK) return rc;
-    return track_step(c, *ct, timestamp, (const uint8_t *)d_descriptors, nullptr, keypoints, n_keypoints, out);
-}
-
-static int track_features_matched_impl(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
-                                       int n_keypoints, const int32_t *match_idx, const uint16_t *match_d1, int flags, ss_pose *out)
-{
-    if (!out || n_keypoints < 0) return SS_ERR_INVALID_ARG;
-    if (!c->calibrated) return fail(c, SS_ERR_NOT_CALIBRATED, "Received frame before calibration. Ignoring.");
-    if (camera_id == 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing camera identifier.");
-    if (n_keypoints > 0 && (!d_descriptors || !keypoints)) return fail(c, SS_ERR_INVALID_ARG, "ss_track_features_matched: NULL feature arrays");
-    if ((match_idx == nullptr) != (match_d1 == nullptr)) return fail(c, SS_ERR_INVALID_ARG, "ss_track_features_matched: match_idx and match_d1 go together");
-    if (flags & ~SS_TRACK_DESC_STAYS_VALID) return fail(c, SS_ERR_INVALID_ARG, "ss_track_features_matched: unknown flag");
+    if (n_keypoints > 0 && (!d_descriptors || !keypoints)) return fail(c, SS_ERR_INVALID_ARG, name + ": NULL feature arrays");
+    if ((match_idx == nullptr) != (match_d1 == nullptr)) return fail(c, SS_ERR_INVALID_ARG, name + ": match_idx and match_d1 go together");
+    if (flags & ~SS_TRACK_DESC_STAYS_VALID) return fail(c, SS_ERR_INVALID_ARG, name + ": unknown flag");
     cam_track *ct = nullptr;
     const int rc = camera_slot(c, camera_id, &ct);
     if (rc != SS_OK) return rc;
@@ -1159,14 +1152,16 @@ int ss_track(ss_ctx *c, int camera_id, const uint8_t *pix, int width, int height
 int ss_track_features(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
                       int n_keypoints, ss_pose *out)
 {
-    return pose_call(c, camera_id, [&]() { return track_features_impl(c, camera_id, timestamp, d_descriptors, keypoints, n_keypoints, out); });
+    return pose_call(c, camera_id, [&]() {
+        return track_features_impl(c, "ss_track_features", camera_id, timestamp, d_descriptors, keypoints, n_keypoints, nullptr, nullptr, 0, out);
+    });
 }
 
 int ss_track_features_matched(ss_ctx *c, int camera_id, double timestamp, const void *d_descriptors, const ss_keypoint *keypoints,
                               int n_keypoints, const int32_t *match_idx, const uint16_t *match_d1, int flags, ss_pose *out)
 {
     return pose_call(c, camera_id, [&]() {
-        return track_features_matched_impl(c, camera_id, timestamp, d_descriptors, keypoints, n_keypoints, match_idx, match_d1, flags, out);
+        return track_features_impl(c, "ss_track_features_matched", camera_id, timestamp, d_descriptors, keypoints, n_keypoints, match_idx, match_d1, flags, out);
     });
 }
 int ss_expand_descriptors_device(ss_ctx *c, const void *d_packed, int n, void *d_expanded)
@@ -1259,7 +1254,7 @@ int ss_stereo_exchange_match(ss_ctx *c, ss_xchg *x, int peer_rank, int th, int r
     if (peer_rank < 0) return fail(c, SS_ERR_INVALID_ARG, "ss_stereo_exchange_match: bad peer rank");
     const int kcap = c->hg.kcap;
     const int64_t blk = (int64_t)kcap * SS_DESC_BYTES;
-    const void *segs[2] = {c->desc, c->n_kp};
+    const void *segs[2] = {c->ws.desc, c->ws.n_kp};
     const int64_t sizes[2] = {blk, (int64_t)sizeof(int32_t)};
     const void *gathered = nullptr;
     int64_t stride = 0;
@@ -1269,10 +1264,10 @@ int ss_stereo_exchange_match(ss_ctx *c, ss_xchg *x, int peer_rank, int th, int r
     if (rc != SS_OK) return rc;
     const uint8_t *peer = (const uint8_t *)gathered + (int64_t)peer_rank * stride;
     const match_out o = split_scratch(c->d_mout, kcap);
-    rc = ss_match_pairs_device(c, c->desc, c->n_kp, peer, peer + blk, 1, kcap, th, ratio_num, ratio_den, o.idx, o.d1, o.d2);
+    rc = ss_match_pairs_device(c, c->ws.desc, c->ws.n_kp, peer, peer + blk, 1, kcap, th, ratio_num, ratio_den, o.idx, o.d1, o.d2);
     if (rc != SS_OK) return rc;
     int32_t counts[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(&counts[0], c->n_kp, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&counts[0], c->ws.n_kp, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(&counts[1], peer + blk, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (idx) HIP_TRY(c, hipMemcpyAsync(idx, o.idx, (size_t)kcap * 4, hipMemcpyDeviceToHost, c->stream));
     if (d1) HIP_TRY(c, hipMemcpyAsync(d1, o.d1, (size_t)kcap * 2, hipMemcpyDeviceToHost, c->stream));
@@ -1310,37 +1305,38 @@ int ss_stereo_batch_device(ss_ctx *c, const ss_stereo_params *p, void *d_points,
     const int n_pairs = c->last_n_frames / 2;
     /* ComputeStereoMatches' constants, one single-precision operation each: mbf, mb = mbf / fx, minD = 0, maxD = mbf / minZ
      * with minZ = mb; Tracking's mThDepth = mbf * ThDepth / fx */
-    const float bf = p->baseline * p->fx;
-    const float mb = bf / p->fx;
-    const float min_d = 0.0f, max_d = bf / mb;
-    const float bt = bf * p->th_depth;
-    const float close_depth = bt / p->fx;
-    const int32_t *frame_error = c->frame_error;
+    ssk_stereo_call st;
+    st.bf = p->baseline * p->fx;
+    const float mb = st.bf / p->fx;
+    st.min_d = 0.0f, st.max_d = st.bf / mb;
+    const float bt = st.bf * p->th_depth;
+    st.close_depth = bt / p->fx;
+    st.points = d_points, st.summary = d_summary;
     if (!c->stereo_test_flagged.empty()) {
         static const int32_t flagged = SS_ERR_OVERFLOW;
         rc = grow(c, c->d_stereo_err, (size_t)c->last_n_frames * sizeof(int32_t));
         if (rc != SS_OK) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->d_stereo_err, c->frame_error, (size_t)c->last_n_frames * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_stereo_err, c->ws.frame_error, (size_t)c->last_n_frames * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
         for (int f : c->stereo_test_flagged)
             if (f >= 0 && f < c->last_n_frames)
                 HIP_TRY(c, hipMemcpyAsync(c->d_stereo_err + f, &flagged, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        frame_error = c->d_stereo_err;
+        st.frame_error = c->d_stereo_err;
     }
     const int64_t nf = g.n_features;
     {
         /* both eyes' keypoints, the left descriptors, ~1 % of the right ones per left keypoint (one row here), the points */
         stage_timer t(c, "stereo_search", (int64_t)n_pairs * (2 * nf * (int64_t)sizeof(ss_keypoint) + 2 * nf * SS_DESC_BYTES + (int64_t)g.kcap * 16));
-        ssk_stereo_search(c->stream, c->dg, g, c->kps, c->desc, c->n_kp, frame_error, max_d, min_d, d_points, n_pairs);
+        ssk_stereo_search(c->stream, c->ws, g, c->last_n_frames, st);
     }
     {
         /* per left keypoint: 11 rows of 11 (left) and 21 (right) pixels, its keypoint, the point read and written */
         stage_timer t(c, "stereo_refine", (int64_t)n_pairs * nf * (11 * (11 + 21) + (int64_t)sizeof(ss_keypoint) + 4 + 2 * 16));
-        ssk_stereo_refine(c->stream, c->dg, g, c->kps, c->n_kp, frame_error, c->pyr, c->last_lvl0, bf, max_d, min_d, d_points, n_pairs);
+        ssk_stereo_refine(c->stream, c->ws, g, c->last_n_frames, c->last_lvl0, st);
     }
     {
         /* three passes over the points (the second and third mostly hit), one write of the cut ones, the summary */
         stage_timer t(c, "stereo_cut", (int64_t)n_pairs * (nf * 16 * 2 + 32));
-        ssk_stereo_cut(c->stream, c->dg, c->n_kp, frame_error, close_depth, d_points, d_summary, n_pairs);
+        ssk_stereo_cut(c->stream, c->ws, g, c->last_n_frames, st);
     }
     HIP_TRY(c, hipGetLastError());
     return SS_OK;
@@ -1353,9 +1349,10 @@ int ss_extract_stereo(ss_ctx *c, int camera_id, const uint8_t *left, const uint8
     if (!c || !out_left || !out_right || !points || !summary) return SS_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
     if (camera_id == 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing camera identifier.");
-    if (!left || !right || width <= 0 || height <= 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing binary image data.");
-    if (channels != 1 && channels != 3 && channels != 4) return fail(c, SS_ERR_BAD_FRAME, "unsupported channel count");
-    if (row_stride < width * channels) return fail(c, SS_ERR_BAD_FRAME, "row_stride smaller than a row");
+    /* each eye is a single image here: that the context holds both is checked below, in this entry point's words */
+    int rc = check_image_args(c, left && right, 1, width, height, channels, row_stride, (int64_t)row_stride * height, false,
+                              "Frame message missing binary image data.", "row_stride smaller than a row");
+    if (rc != SS_OK) return rc;
     const cam_track *own = find_camera(c, camera_id);
     if (!own || !own->has_cam)
         return fail(c, SS_ERR_NOT_CALIBRATED, "ss_extract_stereo: camera " + std::to_string(camera_id) + " has no calibration (fx, baseline, th_depth)");
@@ -1364,55 +1361,36 @@ int ss_extract_stereo(ss_ctx *c, int camera_id, const uint8_t *left, const uint8
     sp.fx = (float)own->cam.fx;
     sp.baseline = (float)own->cam.baseline;
     sp.th_depth = (float)own->cam.th_depth;
-    int rc = stereo_check_params(c, &sp);
-    if (rc != SS_OK) return rc;
-    rc = ensure_geometry(c, width, height);
+    rc = stereo_check_params(c, &sp);
+    if (rc == SS_OK) rc = ensure_geometry(c, width, height);
     if (rc != SS_OK) return rc;
     const ss_geom &g = c->hg;
-    const size_t bytes = (size_t)row_stride * (height - 1) + (size_t)width * channels;
-    const size_t alloc = ((size_t)row_stride * height + 15) & ~(size_t)15;
-    rc = grow(c, c->d_in, 2 * alloc);
+    const upload_size up = upload_footprint(width, height, channels, row_stride);
+    rc = grow(c, c->d_in, 2 * up.alloc);
     if (rc == SS_OK) rc = grow(c, c->d_stereo, (size_t)g.kcap * sizeof(ss_stereo_point) + sizeof(ss_stereo_summary));
     if (rc != SS_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->d_in, left, bytes, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(c->d_in + alloc, right, bytes, hipMemcpyHostToDevice, c->stream));
-    rc = run_extract(c, c->d_in, 2, channels, row_stride, (int64_t)alloc, own->cam.rgb != 0);
+    HIP_TRY(c, hipMemcpyAsync(c->d_in, left, up.bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_in + up.alloc, right, up.bytes, hipMemcpyHostToDevice, c->stream));
+    rc = run_extract(c, c->d_in, 2, channels, row_stride, (int64_t)up.alloc, own->cam.rgb != 0);
     if (rc != SS_OK) return rc;
     uint8_t *d_sum = c->d_stereo + (size_t)g.kcap * sizeof(ss_stereo_point);
     rc = ss_stereo_batch_device(c, &sp, c->d_stereo, d_sum);
     if (rc != SS_OK) return rc;
     int32_t nk[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(nk, c->n_kp, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out_left->level_counts, c->level_counts, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out_right->level_counts, c->level_counts + SS_MAX_LEVELS, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(nk, c->ws.n_kp, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_left->level_counts, c->ws.level_counts, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_right->level_counts, c->ws.level_counts + SS_MAX_LEVELS, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(summary, d_sum, sizeof(ss_stereo_summary), hipMemcpyDeviceToHost, c->stream));
     rc = check_frame_errors(c); /* synchronises */
     if (rc != SS_OK) return rc;
-    const int kcap = g.kcap;
-    c->h_kps.resize((size_t)std::max(nk[0], 1));
-    c->h_desc.resize((size_t)std::max(nk[0], 1) * SS_DESC_BYTES);
+    rc = fetch_rows(c, 0, nk[0], c->h_kps, c->h_desc, camera_id, timestamp, out_left);
+    if (rc != SS_OK) return rc;
     c->h_stereo.resize((size_t)std::max(nk[0], 1));
-    c->h_kps_r.resize((size_t)std::max(nk[1], 1));
-    c->h_desc_r.resize((size_t)std::max(nk[1], 1) * SS_DESC_BYTES);
-    if (nk[0] > 0) {
-        HIP_TRY(c, hipMemcpyAsync(c->h_kps.data(), c->kps, (size_t)nk[0] * sizeof(ss_keypoint), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->h_desc.data(), c->desc, (size_t)nk[0] * SS_DESC_BYTES, hipMemcpyDeviceToHost, c->stream));
+    if (nk[0] > 0)
         HIP_TRY(c, hipMemcpyAsync(c->h_stereo.data(), c->d_stereo, (size_t)nk[0] * sizeof(ss_stereo_point), hipMemcpyDeviceToHost, c->stream));
-    }
-    if (nk[1] > 0) {
-        HIP_TRY(c, hipMemcpyAsync(c->h_kps_r.data(), c->kps + kcap, (size_t)nk[1] * sizeof(ss_keypoint), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->h_desc_r.data(), c->desc + (size_t)kcap * SS_DESC_BYTES, (size_t)nk[1] * SS_DESC_BYTES, hipMemcpyDeviceToHost,
-                                  c->stream));
-    }
+    rc = fetch_rows(c, 1, nk[1], c->h_kps_r, c->h_desc_r, camera_id, timestamp, out_right);
+    if (rc != SS_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    out_left->n_keypoints = nk[0];
-    out_right->n_keypoints = nk[1];
-    out_left->camera_id = out_right->camera_id = camera_id;
-    out_left->timestamp = out_right->timestamp = timestamp;
-    out_left->keypoints = c->h_kps.data();
-    out_left->descriptors = c->h_desc.data();
-    out_right->keypoints = c->h_kps_r.data();
-    out_right->descriptors = c->h_desc_r.data();
     *points = c->h_stereo.data();
     return SS_OK;
 }
@@ -1534,16 +1512,16 @@ int ss_debug_fetch(ss_ctx *c, int what, int frame, int level, void *dst, int64_t
     const ss_geom &g = c->hg;
     const ss_level &L = g.lv[level];
     if (what >= 0 && what <= 2) {
-        if (what == 2 && !c->score) {
+        if (what == 2 && !c->ws.score) {
             /* the response map is not kept in normal operation: allocate it and run the FAST kernel
              * again on the pyramid of the last batch (same kernel, same outputs, plus the map);
              * from now on this context keeps it */
-            HIP_TRY(c, hipMalloc((void **)&c->score, (size_t)c->params.max_batch * g.block_bytes));
-            ssk_fast_blur_nms(c->stream, c->pyr, c->score, c->blur, c->dg, g, c->d_tiles2, c->d_cinfo, c->tsurv,
-                              c->thdr, c->state, c->last_n_frames, c->last_lvl0);
+            const int rc = ws_alloc(c, WS_FIRST_USE);
+            if (rc != SS_OK) return rc;
+            ssk_fast_blur_nms(c->stream, c->ws, g, c->last_n_frames, c->last_lvl0);
             HIP_TRY(c, hipStreamSynchronize(c->stream));
         }
-        const uint8_t *base = what == 0 ? c->pyr : what == 1 ? c->blur : c->score;
+        const uint8_t *base = what == 0 ? c->ws.pyr : what == 1 ? c->ws.blur : c->ws.score;
         const int64_t need = (int64_t)L.w * L.h;
         if (dst_bytes < need) return fail(c, SS_ERR_INVALID_ARG, "ss_debug_fetch: dst too small");
         if (what == 0 && level == 0 && c->last_lvl0.ptr) { /* level 0 was read in place from the caller's buffer */
@@ -1557,12 +1535,12 @@ int ss_debug_fetch(ss_ctx *c, int what, int frame, int level, void *dst, int64_t
     }
     if (what == 3 || what == 4) {
         ss_level_state st;
-        HIP_TRY(c, hipMemcpy(&st, c->state + (size_t)frame * SS_MAX_LEVELS + level, sizeof(st), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(&st, c->ws.state + (size_t)frame * SS_MAX_LEVELS + level, sizeof(st), hipMemcpyDeviceToHost));
         const int n = what == 3 ? st.n_cand : st.n_sel;
         if (dst_bytes < (int64_t)n * 12) return fail(c, SS_ERR_INVALID_ARG, "ss_debug_fetch: dst too small");
         std::vector<uint32_t> packed((size_t)std::max(n, 1));
-        const uint32_t *src = what == 3 ? c->cand + (size_t)frame * g.cand_total + L.cand_base
-                                        : c->sel + (size_t)frame * g.sel_total + L.sel_base;
+        const uint32_t *src = what == 3 ? c->ws.cand + (size_t)frame * g.cand_total + L.cand_base
+                                        : c->ws.sel + (size_t)frame * g.sel_total + L.sel_base;
         if (n > 0) HIP_TRY(c, hipMemcpy(packed.data(), src, (size_t)n * 4, hipMemcpyDeviceToHost));
         int32_t *o = (int32_t *)dst;
         for (int i = 0; i < n; i++) {

@@ -16,36 +16,56 @@ struct ss_lvl0 {
     int64_t frame_stride = 0;
 };
 
-void ssk_ingest(hipStream_t s, const void *src, int channels, int64_t row_stride, int64_t frame_stride,
-                int c0, int c1, int c2, uint8_t *pyr, const ss_geom *dg, const ss_geom &hg, int n_frames);
-void ssk_resize(hipStream_t s, uint8_t *pyr, const ss_geom *dg, const ss_geom &hg, const ss_rtab *rtab,
-                int level, int n_frames, const ss_lvl0 &l0);
+/* Every device pointer of an extraction context (ss_layout.h; ss_api.cpp's ws_table is the one place their sizes live).  A
+ * wrapper below picks the ones its kernel takes by name. */
+struct ssk_extract_ws {
+    /* tables uploaded once per geometry */
+    ss_geom *dg = nullptr;
+    ss_rtab *rtab = nullptr;
+    uint32_t *tile_recs = nullptr; /* per-tile records of the FAST kernel (SS_TILE_REC_WORDS each) */
+    uint16_t *cinfo = nullptr;
+    uint32_t *cell_units = nullptr;
+    /* per-batch buffers, [batch slot][...] */
+    uint8_t *pyr = nullptr, *blur = nullptr;
+    uint8_t *score = nullptr;                   /* the FAST response map: NULL until ss_debug_fetch(2) asks for it, no kernel reads it */
+    uint32_t *tsurv = nullptr, *thdr = nullptr; /* per 64x32 tile: survivor sub-lists and their count words */
+    uint32_t *bucket = nullptr;                 /* per cell: NMS survivors, unordered */
+    uint32_t *cell_cnt = nullptr;
+    uint32_t *cand = nullptr, *qbuf0 = nullptr, *qbuf1 = nullptr;
+    ss_qnode *nodes = nullptr;
+    int32_t *lists = nullptr;
+    uint32_t *sel = nullptr;
+    ss_level_state *state = nullptr;
+    uint32_t *kp_ref = nullptr;                 /* (reference, record) per output slot */
+    /* per slot, between the three launches of ssk_orient_describe: the integer patch moments (m10, m01), then the float
+     * (sin, cos) of the keypoint's angle */
+    int2 *od_moments = nullptr;
+    float2 *od_steer = nullptr;
+    int32_t *n_kp = nullptr, *level_counts = nullptr, *frame_error = nullptr;
+    ss_keypoint *kps = nullptr;
+    uint8_t *desc = nullptr;
+    uint8_t *desc_x = nullptr; /* the descriptors as 256 FP4 values (+1 / -1) per row, 128 B: operand of the batch matcher, or NULL */
+};
+
+/* The extraction stages of n_frames frames of geometry hg (the host copy of *ws.dg), in launch order. */
+/* src -> level 0 in ws.pyr: the gray weights c0, c1, c2 of its channels, its row and frame strides */
+void ssk_ingest(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const void *src, int channels,
+                int64_t row_stride, int64_t frame_stride, int c0, int c1, int c2);
+void ssk_resize(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, int level, const ss_lvl0 &l0);
 /* levels `level` and `level + 1` in one launch (k_resize_pair), where ssk_resize_pair_fits(host geometry, HOST tap tables)
  * said so */
 bool ssk_resize_pair_fits(const ss_geom &hg, const ss_rtab *host_rtab, int level);
-void ssk_resize_pair(hipStream_t s, uint8_t *pyr, const ss_geom *dg, const ss_geom &hg, const ss_rtab *rtab, int level,
-                     int n_frames, const ss_lvl0 &l0);
-/* K2 + K3a + K6a fused: FAST response map, in-window NMS into per-tile survivor sub-lists, blurred pyramid -- one
- * staged tile, no global atomics */
-void ssk_fast_blur_nms(hipStream_t s, const uint8_t *pyr, uint8_t *score, uint8_t *blur, const ss_geom *dg, const ss_geom &hg,
-                       const uint32_t *tile_recs, const uint16_t *cinfo, uint32_t *tsurv, uint32_t *thdr, ss_level_state *state,
-                       int n_frames, const ss_lvl0 &l0);
+void ssk_resize_pair(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, int level, const ss_lvl0 &l0);
+/* K2 + K3a + K6a fused: FAST response map (where ws.score exists), in-window NMS into per-tile survivor sub-lists, blurred
+ * pyramid -- one staged tile, no global atomics */
+void ssk_fast_blur_nms(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ss_lvl0 &l0);
 /* tile sub-lists -> per-cell buckets + count words (one thread per cell) */
-void ssk_bucket_gather(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const uint32_t *cell_units, const uint32_t *tsurv,
-                       const uint32_t *thdr, uint32_t *bucket, uint32_t *cell_cnt, ss_level_state *state, int n_frames);
+void ssk_bucket_gather(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames);
 /* K3b: ranks the bucket entries of every cell into upstream's candidate order */
-void ssk_cells_emit(hipStream_t s, const uint32_t *bucket, const ss_geom *dg, const ss_geom &hg, const uint32_t *cell_cnt,
-                    uint32_t *cand, ss_level_state *state, int n_frames);
-void ssk_quadtree(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const uint32_t *cand, uint32_t *qbuf0,
-                  uint32_t *qbuf1, ss_qnode *nodes, int32_t *lists, uint32_t *sel, ss_level_state *state,
-                  int n_frames);
-void ssk_slots(hipStream_t s, const ss_geom *dg, const uint32_t *sel, const ss_level_state *state, uint32_t *kp_ref,
-               int32_t *n_kp, int32_t *level_counts, int32_t *frame_error, int n_frames);
-void ssk_orient_describe(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const uint8_t *pyr, const uint8_t *blur,
-                         const uint32_t *sel, const uint32_t *kp_ref, const int32_t *n_kp, ss_keypoint *kps,
-                         uint8_t *desc, int n_frames, const ss_lvl0 &l0, bool steer_fma, uint8_t *desc_x, void *moments, void *steer);
-/* (moments, steer: [n_frames][kcap] 8-byte words between the three launches: the integer patch moments (m10, m01), then the
- * float (sin, cos) of the keypoint's angle) */
+void ssk_cells_emit(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames);
+void ssk_quadtree(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames);
+void ssk_slots(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames);
+void ssk_orient_describe(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ss_lvl0 &l0, bool steer_fma);
 
 /* Table form of a matcher call (ss_match_batch_sources_device): query frame b is matched against src[b] (device int32 [n_frames])
  * instead of b + train_frame_shift.  src[b] >= 0: frame src[b] of the batch, the self pair excluded iff src[b] == b; -1: no train
@@ -110,15 +130,18 @@ void ssk_carry_gather(hipStream_t s, const void *desc, const int32_t *n_kp, int 
 void ssk_expand_desc(hipStream_t s, const void *packed, int n, void *out);
 /* [n_frames][rows][32] packed -> [n_frames][rows rounded up to 32][SSK_X_ROW] */
 void ssk_expand_desc_frames(hipStream_t s, const void *packed, int rows, int n_frames, void *out);
-/* ss_stereo.hip: stereo depth of the pairs (2p, 2p + 1) of a batch; points [n_pairs][kcap] ss_stereo_point, summary [n_pairs]
- * ss_stereo_summary.  search writes every row (right_idx / orb_dist or "none"), refine fills sad / u_right / depth of the
- * matched rows from the unblurred pyramids, cut applies the median test and writes the summaries */
-void ssk_stereo_search(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const ss_keypoint *kps, const uint8_t *desc, const int32_t *n_kp,
-                       const int32_t *frame_error, float max_d, float min_d, void *points, int n_pairs);
-void ssk_stereo_refine(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const ss_keypoint *kps, const int32_t *n_kp, const int32_t *frame_error,
-                       const uint8_t *pyr, const ss_lvl0 &l0, float bf, float max_d, float min_d, void *points, int n_pairs);
-void ssk_stereo_cut(hipStream_t s, const ss_geom *dg, const int32_t *n_kp, const int32_t *frame_error, float close_depth, void *points, void *summary,
-                    int n_pairs);
+/* ss_stereo.hip: stereo depth of the pairs (2p, 2p + 1) of a batch of n_frames (even); points [n_frames / 2][kcap]
+ * ss_stereo_point, summary [n_frames / 2] ss_stereo_summary.  search writes every row (right_idx / orb_dist or "none"), refine
+ * fills sad / u_right / depth of the matched rows from the unblurred pyramids, cut applies the median test and writes the
+ * summaries */
+struct ssk_stereo_call {
+    float bf = 0, max_d = 0, min_d = 0, close_depth = 0; /* ComputeStereoMatches' constants */
+    const int32_t *frame_error = nullptr;                /* in place of ws.frame_error (the stereo test hook), or NULL */
+    void *points = nullptr, *summary = nullptr;
+};
+void ssk_stereo_search(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ssk_stereo_call &st);
+void ssk_stereo_refine(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ss_lvl0 &l0, const ssk_stereo_call &st);
+void ssk_stereo_cut(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ssk_stereo_call &st);
 /* test hook: run the device std::sort restatement on n <= 2048 items (size << 32 | UL.x << 20 | id) */
 int ssk_debug_sort(hipStream_t s, uint64_t *d_items, int n);
 #define SSK_MATCH_MFMA_MIN_QUERIES 128 /* from this many query rows on, ssk_match runs a matrix-core kernel */

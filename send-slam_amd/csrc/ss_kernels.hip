@@ -3035,30 +3035,29 @@ __global__ __launch_bounds__(256) void k_match_stream(const uint32_t *__restrict
 /* ------------------------------------------------------------------------------------ */
 /* launch wrappers (host)                                                                */
 /* ------------------------------------------------------------------------------------ */
-void ssk_ingest(hipStream_t s, const void *src, int channels, int64_t row_stride, int64_t frame_stride,
-                int c0, int c1, int c2, uint8_t *pyr, const ss_geom *dg, const ss_geom &hg, int n_frames)
+void ssk_ingest(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const void *src, int channels,
+                int64_t row_stride, int64_t frame_stride, int c0, int c1, int c2)
 {
     if (channels == 1 && ((uintptr_t)src % 16) == 0 && row_stride % 16 == 0 && frame_stride % 16 == 0) {
         dim3 grid16((hg.lv[0].w + 1023) / 1024, (hg.lv[0].h + 3) / 4, n_frames);
-        hipLaunchKernelGGL(k_ingest_gray16, grid16, dim3(256), 0, s, (const uint8_t *)src, row_stride, frame_stride, pyr, dg);
+        hipLaunchKernelGGL(k_ingest_gray16, grid16, dim3(256), 0, s, (const uint8_t *)src, row_stride, frame_stride, ws.pyr, ws.dg);
         return;
     }
     dim3 grid((hg.lv[0].w + 255) / 256, (hg.lv[0].h + 3) / 4, n_frames);
     hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, (const uint8_t *)src, channels, row_stride, frame_stride,
-                       c0, c1, c2, pyr, dg);
+                       c0, c1, c2, ws.pyr, ws.dg);
 }
 
-void ssk_resize(hipStream_t s, uint8_t *pyr, const ss_geom *dg, const ss_geom &hg, const ss_rtab *rtab,
-                int level, int n_frames, const ss_lvl0 &l0)
+void ssk_resize(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, int level, const ss_lvl0 &l0)
 {
     /* source window of a 64x64 tile: (64 * scale + 1 + 15 alignment) bytes x (64 * scale + 2) rows */
     const float sx = (float)hg.lv[level - 1].w / (float)hg.lv[level].w, sy = (float)hg.lv[level - 1].h / (float)hg.lv[level].h;
     if (64.f * sx + 18.f <= 4.f * RS_WORDS && (float)RS_TILE_H * sy + 3.f <= (float)RS_ROWS) {
         dim3 grid(((hg.lv[level].w + SS_TILE_W - 1) / SS_TILE_W) * ((hg.lv[level].h + RS_TILE_H - 1) / RS_TILE_H), n_frames);
-        hipLaunchKernelGGL(k_resize_lds, grid, dim3(256), 0, s, pyr, dg, rtab, level, l0.ptr, l0.pitch, l0.frame_stride);
+        hipLaunchKernelGGL(k_resize_lds, grid, dim3(256), 0, s, ws.pyr, ws.dg, ws.rtab, level, l0.ptr, l0.pitch, l0.frame_stride);
     } else {
         dim3 grid((hg.lv[level].w + 255) / 256, (hg.lv[level].h + 3) / 4, n_frames);
-        hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, s, pyr, dg, rtab, level, l0.ptr, l0.pitch, l0.frame_stride);
+        hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, s, ws.pyr, ws.dg, ws.rtab, level, l0.ptr, l0.pitch, l0.frame_stride);
     }
 }
 
@@ -3118,60 +3117,51 @@ bool ssk_resize_pair_fits(const ss_geom &hg, const ss_rtab *t, int level)
     return true;
 }
 
-void ssk_resize_pair(hipStream_t s, uint8_t *pyr, const ss_geom *dg, const ss_geom &hg, const ss_rtab *rtab, int level,
-                     int n_frames, const ss_lvl0 &l0)
+void ssk_resize_pair(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, int level, const ss_lvl0 &l0)
 {
     const ss_level &B = hg.lv[level + 1];
     dim3 grid(((B.w + RP_TILE_W - 1) / RP_TILE_W) * ((B.h + RS_TILE_H - 1) / RS_TILE_H), n_frames);
-    hipLaunchKernelGGL(k_resize_pair, grid, dim3(256), 0, s, pyr, dg, rtab, level, l0.ptr, l0.pitch, l0.frame_stride);
+    hipLaunchKernelGGL(k_resize_pair, grid, dim3(256), 0, s, ws.pyr, ws.dg, ws.rtab, level, l0.ptr, l0.pitch, l0.frame_stride);
 }
 
-void ssk_fast_blur_nms(hipStream_t s, const uint8_t *pyr, uint8_t *score, uint8_t *blur, const ss_geom *dg, const ss_geom &hg,
-                       const uint32_t *tile_recs, const uint16_t *cinfo, uint32_t *tsurv, uint32_t *thdr, ss_level_state *state,
-                       int n_frames, const ss_lvl0 &l0)
+void ssk_fast_blur_nms(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ss_lvl0 &l0)
 {
-    hipLaunchKernelGGL(k_fast_score, dim3(hg.tiles2_total, n_frames), dim3(FT_THREADS), 0, s, pyr, score, dg, tile_recs, cinfo, tsurv, thdr,
-                       state, blur, l0.ptr, l0.pitch, l0.frame_stride);
+    hipLaunchKernelGGL(k_fast_score, dim3(hg.tiles2_total, n_frames), dim3(FT_THREADS), 0, s, ws.pyr, ws.score, ws.dg, ws.tile_recs, ws.cinfo,
+                       ws.tsurv, ws.thdr, ws.state, ws.blur, l0.ptr, l0.pitch, l0.frame_stride);
 }
-void ssk_bucket_gather(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const uint32_t *cell_units, const uint32_t *tsurv,
-                       const uint32_t *thdr, uint32_t *bucket, uint32_t *cell_cnt, ss_level_state *state, int n_frames)
+void ssk_bucket_gather(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames)
 {
-    hipLaunchKernelGGL(k_bucket_gather, dim3((hg.n_cells * 16 + 255) / 256, n_frames), dim3(256), 0, s, dg, cell_units, tsurv, thdr, bucket,
-                       cell_cnt, state);
+    hipLaunchKernelGGL(k_bucket_gather, dim3((hg.n_cells * 16 + 255) / 256, n_frames), dim3(256), 0, s, ws.dg, ws.cell_units, ws.tsurv, ws.thdr,
+                       ws.bucket, ws.cell_cnt, ws.state);
 }
-void ssk_cells_emit(hipStream_t s, const uint32_t *bucket, const ss_geom *dg, const ss_geom &hg, const uint32_t *cell_cnt,
-                    uint32_t *cand, ss_level_state *state, int n_frames)
+void ssk_cells_emit(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames)
 {
-    hipLaunchKernelGGL(k_cells_emit, dim3(hg.chunks_total, n_frames), dim3(256), 0, s, bucket, dg, cell_cnt, cand, state);
+    hipLaunchKernelGGL(k_cells_emit, dim3(hg.chunks_total, n_frames), dim3(256), 0, s, ws.bucket, ws.dg, ws.cell_cnt, ws.cand, ws.state);
 }
-void ssk_quadtree(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const uint32_t *cand, uint32_t *qbuf0,
-                  uint32_t *qbuf1, ss_qnode *nodes, int32_t *lists, uint32_t *sel, ss_level_state *state, int n_frames)
+void ssk_quadtree(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames)
 {
     int need = 0;
     for (int l = 0; l < hg.n_levels; l++) need = hg.lv[l].item_cap > need ? hg.lv[l].item_cap : need;
     need = (need + 63) & ~63;
-    hipLaunchKernelGGL(k_quadtree, dim3(n_frames, hg.n_levels), dim3(QT_THREADS), (size_t)need * (2 * sizeof(uint64_t) + 2 * sizeof(int32_t)), s, dg, cand, qbuf0,
-                       qbuf1, nodes, lists, sel, state, need);
+    hipLaunchKernelGGL(k_quadtree, dim3(n_frames, hg.n_levels), dim3(QT_THREADS), (size_t)need * (2 * sizeof(uint64_t) + 2 * sizeof(int32_t)), s, ws.dg, ws.cand,
+                       ws.qbuf0, ws.qbuf1, ws.nodes, ws.lists, ws.sel, ws.state, need);
 }
 
-void ssk_slots(hipStream_t s, const ss_geom *dg, const uint32_t *sel, const ss_level_state *state, uint32_t *kp_ref,
-               int32_t *n_kp, int32_t *level_counts, int32_t *frame_error, int n_frames)
+void ssk_slots(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames)
 {
-    hipLaunchKernelGGL(k_slots, dim3(n_frames), dim3(64), 0, s, dg, sel, state, kp_ref, n_kp, level_counts, frame_error);
+    hipLaunchKernelGGL(k_slots, dim3(n_frames), dim3(64), 0, s, ws.dg, ws.sel, ws.state, ws.kp_ref, ws.n_kp, ws.level_counts, ws.frame_error);
 }
 
-void ssk_orient_describe(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const uint8_t *pyr, const uint8_t *blur,
-                         const uint32_t *sel, const uint32_t *kp_ref, const int32_t *n_kp, ss_keypoint *kps,
-                         uint8_t *desc, int n_frames, const ss_lvl0 &l0, bool steer_fma, uint8_t *desc_x, void *moments, void *steer)
+void ssk_orient_describe(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ss_lvl0 &l0, bool steer_fma)
 {
     /* kcap is a multiple of 64: kcap / 4 blocks of four waves per frame, kcap / 64 waves of the per-thread kernel */
     const dim3 grid(hg.kcap / 4, n_frames);
-    hipLaunchKernelGGL(k_orient_moments, grid, dim3(256), 0, s, dg, pyr, kp_ref, n_kp, l0.ptr, l0.pitch, l0.frame_stride, (int2 *)moments);
-    hipLaunchKernelGGL(k_keypoint_finish, dim3(hg.kcap / 64, n_frames), dim3(64), 0, s, dg, kp_ref, n_kp, (const int2 *)moments, kps, (float2 *)steer);
+    hipLaunchKernelGGL(k_orient_moments, grid, dim3(256), 0, s, ws.dg, ws.pyr, ws.kp_ref, ws.n_kp, l0.ptr, l0.pitch, l0.frame_stride, ws.od_moments);
+    hipLaunchKernelGGL(k_keypoint_finish, dim3(hg.kcap / 64, n_frames), dim3(64), 0, s, ws.dg, ws.kp_ref, ws.n_kp, ws.od_moments, ws.kps, ws.od_steer);
     if (steer_fma)
-        hipLaunchKernelGGL(k_describe<true>, grid, dim3(256), 0, s, dg, blur, kp_ref, n_kp, (const float2 *)steer, desc, desc_x);
+        hipLaunchKernelGGL(k_describe<true>, grid, dim3(256), 0, s, ws.dg, ws.blur, ws.kp_ref, ws.n_kp, ws.od_steer, ws.desc, ws.desc_x);
     else
-        hipLaunchKernelGGL(k_describe<false>, grid, dim3(256), 0, s, dg, blur, kp_ref, n_kp, (const float2 *)steer, desc, desc_x);
+        hipLaunchKernelGGL(k_describe<false>, grid, dim3(256), 0, s, ws.dg, ws.blur, ws.kp_ref, ws.n_kp, ws.od_steer, ws.desc, ws.desc_x);
 }
 
 /* which form of the matrix-core kernel: a single large database has the chip to itself (NU = 2), batches of frames share it */

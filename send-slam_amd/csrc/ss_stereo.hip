@@ -359,23 +359,21 @@ __global__ __launch_bounds__(256) void k_stereo_cut(const ss_geom *__restrict__ 
 
 } // namespace
 
-void ssk_stereo_search(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const ss_keypoint *kps, const uint8_t *desc, const int32_t *n_kp,
-                       const int32_t *frame_error, float max_d, float min_d, void *points, int n_pairs)
+void ssk_stereo_search(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ssk_stereo_call &st)
 {
-    hipLaunchKernelGGL(k_stereo_search, dim3((unsigned)((hg.kcap + 63) / 64), (unsigned)n_pairs), dim3(256), 0, s, dg, kps, desc, n_kp, frame_error,
-                       max_d, min_d, (ss_stereo_point *)points);
+    hipLaunchKernelGGL(k_stereo_search, dim3((unsigned)((hg.kcap + 63) / 64), (unsigned)(n_frames / 2)), dim3(256), 0, s, ws.dg, ws.kps, ws.desc,
+                       ws.n_kp, st.frame_error ? st.frame_error : ws.frame_error, st.max_d, st.min_d, (ss_stereo_point *)st.points);
 }
 
-void ssk_stereo_refine(hipStream_t s, const ss_geom *dg, const ss_geom &hg, const ss_keypoint *kps, const int32_t *n_kp, const int32_t *frame_error,
-                       const uint8_t *pyr, const ss_lvl0 &l0, float bf, float max_d, float min_d, void *points, int n_pairs)
+void ssk_stereo_refine(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ss_lvl0 &l0, const ssk_stereo_call &st)
 {
-    hipLaunchKernelGGL(k_stereo_refine, dim3((unsigned)((hg.kcap + 3) / 4), (unsigned)n_pairs), dim3(256), 0, s, dg, kps, n_kp, frame_error, pyr, l0.ptr,
-                       l0.pitch, l0.frame_stride, bf, max_d, min_d, (ss_stereo_point *)points);
+    hipLaunchKernelGGL(k_stereo_refine, dim3((unsigned)((hg.kcap + 3) / 4), (unsigned)(n_frames / 2)), dim3(256), 0, s, ws.dg, ws.kps, ws.n_kp,
+                       st.frame_error ? st.frame_error : ws.frame_error, ws.pyr, l0.ptr, l0.pitch, l0.frame_stride, st.bf, st.max_d, st.min_d,
+                       (ss_stereo_point *)st.points);
 }
 
-void ssk_stereo_cut(hipStream_t s, const ss_geom *dg, const int32_t *n_kp, const int32_t *frame_error, float close_depth, void *points, void *summary,
-                    int n_pairs)
+void ssk_stereo_cut(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ssk_stereo_call &st)
 {
-    hipLaunchKernelGGL(k_stereo_cut, dim3((unsigned)n_pairs), dim3(256), 0, s, dg, n_kp, frame_error, close_depth, (ss_stereo_point *)points,
-                       (ss_stereo_summary *)summary);
+    hipLaunchKernelGGL(k_stereo_cut, dim3((unsigned)(n_frames / 2)), dim3(256), 0, s, ws.dg, ws.n_kp, st.frame_error ? st.frame_error : ws.frame_error,
+                       st.close_depth, (ss_stereo_point *)st.points, (ss_stereo_summary *)st.summary);
 }

@@ -35,32 +35,50 @@ def level_dims(ctx, w, h, oracle):
     return [(g.w[l], g.h[l]) for l in range(g.n_levels)]
 
 
+def check_golden_stages(ctx, z, oracle):
+    """ctx.extract(z's frame), then every stage of every level, the outputs and the self-match against the golden vectors"""
+    img = z["frame"]
+    h, w = img.shape
+    kps, desc, counts = ctx.extract(img)
+    dims = level_dims(ctx, w, h, oracle)
+    for l, (lw, lh) in enumerate(dims):
+        lvl = ctx.debug_fetch(0, 0, l, (lh, lw))
+        assert np.array_equal(sha(lvl), z["level_sha"][l]), f"pyramid level {l}"
+        blr = ctx.debug_fetch(1, 0, l, (lh, lw))
+        assert np.array_equal(sha(blr), z["blur_sha"][l]), f"blurred level {l}"
+        sc = ctx.debug_fetch(2, 0, l, (lh, lw))
+        assert np.array_equal(sha(sc), z["score7_sha"][l]), f"FAST score map level {l}"
+        cand = ctx.debug_fetch(3, 0, l, (lw * lh,), np.int32)
+        assert triples(cand) == pts(z[f"cand{l}"]), f"candidates level {l}"
+        sel = ctx.debug_fetch(4, 0, l, (4096 * 3,), np.int32)
+        want = [(x + 16, y + 16, r) for x, y, r in pts(z[f"sel{l}"])]
+        assert triples(sel) == want, f"quadtree level {l}"
+    assert np.array_equal(counts, z["level_counts"])
+    assert kps.tobytes() == z["kps"].tobytes()
+    assert np.array_equal(desc, z["desc"])
+    idx, d1, d2 = ctx.match(desc, desc, exclude_self=True)
+    assert np.array_equal(idx, z["self_idx"]) and np.array_equal(d1, z["self_d1"]) and np.array_equal(d2, z["self_d2"])
+
+
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz"))))
 def test_golden_vectors_stage_by_stage(path, oracle):
     z = np.load(path)
-    img = z["frame"]
-    h, w = img.shape
     lap = z["lapping"]
     with binding.OrbContext(0, n_features=int(z["n_features"]), lapping_x0=int(lap[0]), lapping_x1=int(lap[1])) as ctx:
-        kps, desc, counts = ctx.extract(img)
-        dims = level_dims(ctx, w, h, oracle)
-        for l, (lw, lh) in enumerate(dims):
-            lvl = ctx.debug_fetch(0, 0, l, (lh, lw))
-            assert np.array_equal(sha(lvl), z["level_sha"][l]), f"pyramid level {l}"
-            blr = ctx.debug_fetch(1, 0, l, (lh, lw))
-            assert np.array_equal(sha(blr), z["blur_sha"][l]), f"blurred level {l}"
-            sc = ctx.debug_fetch(2, 0, l, (lh, lw))
-            assert np.array_equal(sha(sc), z["score7_sha"][l]), f"FAST score map level {l}"
-            cand = ctx.debug_fetch(3, 0, l, (lw * lh,), np.int32)
-            assert triples(cand) == pts(z[f"cand{l}"]), f"candidates level {l}"
-            sel = ctx.debug_fetch(4, 0, l, (4096 * 3,), np.int32)
-            want = [(x + 16, y + 16, r) for x, y, r in pts(z[f"sel{l}"])]
-            assert triples(sel) == want, f"quadtree level {l}"
-        assert np.array_equal(counts, z["level_counts"])
-        assert kps.tobytes() == z["kps"].tobytes()
-        assert np.array_equal(desc, z["desc"])
-        idx, d1, d2 = ctx.match(desc, desc, exclude_self=True)
-        assert np.array_equal(idx, z["self_idx"]) and np.array_equal(d1, z["self_d1"]) and np.array_equal(d2, z["self_d2"])
+        check_golden_stages(ctx, z, oracle)
+
+
+def test_stages_across_a_geometry_change(oracle, golden_dir):
+    """One context through 320x240 -> 400x260 -> 320x240: every buffer of the extraction is freed and allocated again from the
+    buffer table at each change of size, the FAST score map included (which each size's first debug_fetch(2) allocates).
+    Every stage of every level, the keypoints, descriptors and level counts are checked at each size; all of it equality."""
+    from test_adversarial_content import check_stages
+    z = np.load(os.path.join(golden_dir, "g0_320x240_n500.npz"))
+    assert int(z["n_features"]) == 500 and list(z["lapping"]) == [0, 1000]  # the context below is the one g0 was made with
+    with binding.OrbContext(0, n_features=500) as ctx:
+        check_golden_stages(ctx, z, oracle)
+        check_stages(oracle, binding, synth.frame(31, 400, 260), "after 320x240", n_features=500, ctx=ctx)
+        check_golden_stages(ctx, z, oracle)
 
 
 def test_golden_consecutive_frame_match():

@@ -33,6 +33,8 @@
  *                              front-end; the pose SendPosePacket :225-282 ships)
  *   ss_stereo_batch_device /   ORB_SLAM3::Frame::ComputeStereoMatches (the stereo Frame constructor; no counterpart in the
  *   ss_extract_stereo          monocular shim, which only ships th_depth / baseline :59-77)
+ *   ss_match_guided*           ORBmatcher::SearchForInitialization / SearchByProjection on Frame::GetFeaturesInArea (window
+ *                              search, conflicts, rotation histogram; the monocular shim reaches them inside TrackMonocular :594)
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
  *   ss_last_error              the cerr diagnostics of the shim (:457-469, :523-551)
  *
@@ -383,6 +385,76 @@ int ss_stereo_batch_device(ss_ctx *ctx, const ss_stereo_params *p, void *d_point
 int ss_extract_stereo(ss_ctx *ctx, int camera_id, const uint8_t *left, const uint8_t *right, int width, int height,
                       int channels, int row_stride, double timestamp, ss_frame_result *out_left,
                       ss_frame_result *out_right, const ss_stereo_point **points, ss_stereo_summary *summary);
+
+/* ---- guided matching: descriptor search inside a pixel window (ORB-SLAM3 ORBmatcher::SearchForInitialization /
+ * SearchByProjection on Frame::GetFeaturesInArea; neither source file is in the reference tree: the rule below is this
+ * library's own restatement, parity unpinned like the rest of the path) ----------------------------
+ * Query row i has a window (x, y, radius, oct_lo, oct_hi).
+ *   Candidates: train row j < n_train with oct_lo <= octave_j <= oct_hi, fabsf(x_j - x) < radius and fabsf(y_j - y) < radius
+ *     (both strict, every difference one float32 operation on the keypoints' x / y as they are: the membership test inside
+ *     GetFeaturesInArea; the device's grid only finds them faster).  A query whose radius is not > 0 (zero, negative, NaN) has
+ *     none; oct_lo > oct_hi gives none.
+ *   d1 = the lowest distance over the candidates, idx = the lowest j among those, d2 = the lowest distance over the candidates
+ *     j != idx (a duplicate gives d2 == d1), 0xFFFF = absent: ss_match's rule, so a window that covers everything gives what
+ *     ss_match gives.  d1 / d2 are always these raw values; idx is what survives the tests below, else -1.
+ *   Accept iff d1 <= th and (ratio_den == 0 or d1 * ratio_den < d2 * ratio_num).  ratio_den 0 is SearchByProjection (no ratio
+ *     test), 9 / 10 with th 50 SearchForInitialization.  0 <= ratio_num, ratio_den <= 32767.
+ *   one_to_one: among the accepted queries that name the same train row the one with the lowest d1 << 20 | i keeps it, the
+ *     others get -1.  Deviation: upstream resolves such conflicts while it walks the queries in order (vMatchedDistance,
+ *     vnMatches21), which depends on that order; this is the order-free form of "the closer one wins, ties to the lower query".
+ *   orientation (0 off, 1, 2), on what is left: rot = angle_query - angle_train; if (rot < 0) rot += 360.0f;
+ *     bin = (int)roundf(rot * factor) (half away from zero); if (bin == 30) bin = 0.  factor is 1.0f / 30 for 1 (bins 0..12 are
+ *     used and 359 degrees lands in bin 12) and 30 / 360.0f for 2: both forms exist upstream, which one the reference binary
+ *     runs is unpinned.  Then ComputeThreeMaxima: bins 0..29 scanned with a strict > against max1, max2, max3 in turn; if
+ *     (float)max2 < 0.1f * (float)max1 the second and third are dropped, else if (float)max3 < 0.1f * (float)max1 the third.
+ *     Matches outside the kept bins get -1; so does a match whose bin is outside 0..29 or NaN, which takes caller-made angles
+ *     outside [0, 360) (upstream asserts).  Every step is a single float32 operation. */
+#define SS_GUIDED_MAX_ROWS 16384 /* rows per frame: the conflict keys hold a row in 20 bits, a frame's keys one workgroup's LDS */
+typedef struct {          /* 16 bytes, one per query row */
+    float x, y, radius;
+    int16_t oct_lo, oct_hi;
+} ss_guided_window;
+typedef struct {          /* 40 bytes */
+    int32_t th, ratio_num, ratio_den;   /* ratio_den 0 = no ratio test */
+    int32_t one_to_one, orientation;    /* orientation 0 / 1 / 2 as above */
+    /* only when d_windows == NULL (batch form): the window of a query is its own position, radius `radius`, or radius *
+     * scale[octave] of the context's pyramid when radius_by_octave is set, octaves octave -+ octave_span */
+    float radius;
+    int32_t radius_by_octave, octave_span;
+    /* pairs / host form: the image size the coordinates live in; it sizes the index only and never changes a result
+     * (coordinates outside it, infinite or NaN are binned into a border cell); <= 0 is SS_ERR_INVALID_ARG.  Batch form: ignored */
+    int32_t extent_w, extent_h;
+} ss_guided_params;
+typedef struct {          /* 32 bytes, one per frame */
+    int32_t status;       /* SS_OK, or the ss_status that voided the frame (frame_error of either side: all rows "none", counts 0) */
+    int32_t n_query, n_train;
+    int32_t n_candidates; /* Hamming distances taken = the sum of the candidate-set sizes */
+    int32_t n_accepted, n_unique, n_final; /* after the acceptance test, after one_to_one, after orientation */
+    int32_t rot_bins;     /* the kept bins ind1 | ind2 << 8 | ind3 << 16, 0xFF = none; 0xFFFFFF when orientation is off */
+} ss_guided_summary;
+/* n_frames independent (query frame, train frame) pairs on caller-supplied device arrays laid out like ss_match_pairs_device:
+ * descriptors [n_frames][rows_per_frame][32] and keypoints [n_frames][rows_per_frame] (ss_keypoint: x, y, octave of the train
+ * side and angle of both sides are read) on both sides, counts d_n_query / d_n_train (device int32 [n_frames], clamped to
+ * 0 .. rows_per_frame), d_windows [n_frames][rows_per_frame] ss_guided_window.  Outputs: d_idx (int32) / d_d1 / d_d2 (uint16)
+ * [n_frames][rows_per_frame], rows >= n_query get -1 / 0xFFFF, and d_summary [n_frames] ss_guided_summary.  No self-exclusion.
+ * rows_per_frame > SS_GUIDED_MAX_ROWS is SS_ERR_INVALID_ARG.  Asynchronous on the context's stream. */
+int ss_match_guided_pairs_device(ss_ctx *ctx, const void *d_query, const void *d_query_kp, const void *d_n_query,
+                                 const void *d_train, const void *d_train_kp, const void *d_n_train, const void *d_windows,
+                                 int n_frames, int rows_per_frame, const ss_guided_params *p, void *d_idx, void *d_d1, void *d_d2,
+                                 void *d_summary);
+/* The frames of the last ss_extract_batch_device batch.  train_src is a HOST table [n_frames] as in
+ * ss_match_batch_sources_device, without the carry: t >= 0 names frame t of the batch (the pair j == i is excluded iff
+ * t == b), -1 no train; t <= -2 or t >= n_frames is SS_ERR_INVALID_ARG.  NULL: frame b against frame b - 1, frame 0 without a
+ * train.  d_windows: device [n_frames][kp_capacity], or NULL (the windows follow from p, above).  Outputs are
+ * [n_frames][kp_capacity] and d_summary [n_frames].  A frame whose frame_error is set, on either side, gets that status and
+ * all-none rows, as the stereo stages do.  Asynchronous on the context's stream. */
+int ss_match_guided_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_windows, const ss_guided_params *p,
+                                 void *d_idx, void *d_d1, void *d_d2, void *d_summary);
+/* One pair with host pointers in and out (copy in, the pairs form, copy out), synchronous: the counterpart of ss_match.
+ * n_query, n_train <= SS_GUIDED_MAX_ROWS; windows has n_query entries. */
+int ss_match_guided(ss_ctx *ctx, const uint8_t *query, const ss_keypoint *query_kp, int n_query, const uint8_t *train,
+                    const ss_keypoint *train_kp, int n_train, const ss_guided_window *windows, const ss_guided_params *p,
+                    int32_t *idx, uint16_t *d1, uint16_t *d2, ss_guided_summary *summary);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

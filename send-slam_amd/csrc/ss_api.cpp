@@ -128,6 +128,8 @@ struct ss_ctx {
      * SS_ERR_OVERFLOW, through a copy of the array), the only way to reach the voided-pair rule without overflowing a capacity */
     std::vector<int> stereo_test_flagged;
     dev_buf<int32_t> d_stereo_err;
+    /* guided matching: the grid index and candidate counts of a call (guided_run sizes them); the host form's device copies */
+    dev_buf<uint8_t> d_guided_ws, d_guided_io;
 
     int last_n_frames = 0;
     ss_lvl0 last_lvl0; /* where level 0 of the last batch lives (ptr == NULL: in the pyramid block) */
@@ -582,6 +584,8 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_carry_x);
     dev_free(c->d_stereo);
     dev_free(c->d_stereo_err);
+    dev_free(c->d_guided_ws);
+    dev_free(c->d_guided_io);
     if (c->h_train_src) (void)hipHostFree(c->h_train_src);
     if (c->train_src_copied) (void)hipEventDestroy(c->train_src_copied);
     for (cam_track &ct : c->cams) ct.free_rows();
@@ -875,6 +879,30 @@ int ss_match_batch_device(ss_ctx *c, int mode, int th, int ratio_num, int ratio_
     return run_batch_match(c, m);
 }
 
+/* A host train table [n] -> c->d_train_src on c->stream.  train_src NULL: frame b against frame b - 1, frame 0 without a train.
+ * The table travels through pinned memory, so the copy is asynchronous and the caller's array is free when this returns; the
+ * previous call's copy has left the staging buffer before it is rewritten */
+static int upload_train_src(ss_ctx *c, const int32_t *train_src, int n)
+{
+    int rc = grow(c, c->d_train_src, (size_t)n * sizeof(int32_t));
+    if (rc != SS_OK) return rc;
+    if (c->train_src_copied) HIP_TRY(c, hipEventSynchronize(c->train_src_copied));
+    else HIP_TRY(c, hipEventCreateWithFlags(&c->train_src_copied, hipEventDisableTiming));
+    if (c->h_train_src_n < n) {
+        if (c->h_train_src) (void)hipHostFree(c->h_train_src);
+        c->h_train_src = nullptr;
+        c->h_train_src_n = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_train_src, (size_t)n * sizeof(int32_t), hipHostMallocDefault));
+        c->h_train_src_n = n;
+    }
+    if (train_src) memcpy(c->h_train_src, train_src, (size_t)n * sizeof(int32_t));
+    else
+        for (int b = 0; b < n; b++) c->h_train_src[b] = b - 1;
+    HIP_TRY(c, hipMemcpyAsync(c->d_train_src, c->h_train_src, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->train_src_copied, c->stream));
+    return SS_OK;
+}
+
 int ss_match_batch_sources_device(ss_ctx *c, const int32_t *train_src, const void *d_carry, const void *d_carry_n, int n_carry, int th,
                                   int ratio_num, int ratio_den, void *d_idx, void *d_d1, void *d_d2)
 {
@@ -890,22 +918,8 @@ int ss_match_batch_sources_device(ss_ctx *c, const int32_t *train_src, const voi
             return fail(c, SS_ERR_INVALID_ARG, "train_src[" + std::to_string(b) + "] = " + std::to_string(t) + " names no frame of the batch (" +
                                                    std::to_string(n) + ") or of the carry (" + std::to_string(n_carry) + ")");
     }
-    int rc = grow(c, c->d_train_src, (size_t)n * sizeof(int32_t));
+    int rc = upload_train_src(c, train_src, n);
     if (rc != SS_OK) return rc;
-    /* the table travels through pinned memory, so the copy is asynchronous and the caller's array is free when this returns;
-     * the previous call's copy has left the staging buffer before it is rewritten */
-    if (c->train_src_copied) HIP_TRY(c, hipEventSynchronize(c->train_src_copied));
-    else HIP_TRY(c, hipEventCreateWithFlags(&c->train_src_copied, hipEventDisableTiming));
-    if (c->h_train_src_n < n) {
-        if (c->h_train_src) (void)hipHostFree(c->h_train_src);
-        c->h_train_src = nullptr;
-        c->h_train_src_n = 0;
-        HIP_TRY(c, hipHostMalloc((void **)&c->h_train_src, (size_t)n * sizeof(int32_t), hipHostMallocDefault));
-        c->h_train_src_n = n;
-    }
-    memcpy(c->h_train_src, train_src, (size_t)n * sizeof(int32_t));
-    HIP_TRY(c, hipMemcpyAsync(c->d_train_src, c->h_train_src, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipEventRecord(c->train_src_copied, c->stream));
     ssk_table tab{c->d_train_src, d_carry, nullptr, (const int32_t *)d_carry_n};
     if (c->ws.desc_x && n_carry > 0) { /* the carry as operand rows, at the batch's frame stride */
         rc = grow(c, c->d_carry_x, (size_t)n_carry * kcap * SSK_X_ROW);
@@ -1392,6 +1406,162 @@ int ss_extract_stereo(ss_ctx *c, int camera_id, const uint8_t *left, const uint8
     if (rc != SS_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *points = c->h_stereo.data();
+    return SS_OK;
+}
+
+/* ---- guided matching (csrc/ss_guided.hip) ---- */
+static int guided_check_params(ss_ctx *c, const ss_guided_params *p)
+{
+    if (!p) return fail(c, SS_ERR_INVALID_ARG, "guided match: params is NULL");
+    if (p->ratio_num < 0 || p->ratio_num > 32767 || p->ratio_den < 0 || p->ratio_den > 32767)
+        return fail(c, SS_ERR_INVALID_ARG, "guided match: ratio_num and ratio_den must be 0 .. 32767 (ratio_den 0 = no ratio test)");
+    if (p->orientation < 0 || p->orientation > 2) return fail(c, SS_ERR_INVALID_ARG, "guided match: orientation must be 0, 1 or 2");
+    return SS_OK;
+}
+
+/* The three launches of a call whose operands, windows and outputs are filled in: sizes the grid from the extent, carves the
+ * index and the candidate counts out of c->d_guided_ws. */
+static int guided_run(ss_ctx *c, ssk_guided_call &g, const ss_guided_params *p, int extent_w, int extent_h)
+{
+    g.th = p->th, g.rnum = p->ratio_num, g.rden = p->ratio_den;
+    g.one_to_one = p->one_to_one != 0, g.orientation = p->orientation;
+    ssk_guided_grid(g, extent_w, extent_h);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t cells = up((size_t)g.n_frames * (SSK_GUIDED_MAX_CELLS + 1) * sizeof(uint32_t));
+    const size_t recs = up((size_t)g.n_frames * g.rows * 16);
+    const size_t cand = up((size_t)g.n_frames * g.rows * sizeof(int32_t));
+    const int rc = grow(c, c->d_guided_ws, cells + recs + cand);
+    if (rc != SS_OK) return rc;
+    g.cell_start = (uint32_t *)c->d_guided_ws.p;
+    g.recs = c->d_guided_ws.p + cells;
+    g.n_cand = (int32_t *)(c->d_guided_ws.p + cells + recs);
+    const int64_t nq = (int64_t)g.n_frames * g.rows, n_cells = (int64_t)g.cols * g.grid_rows;
+    {
+        /* algorithmic bytes: keypoints in, records and cell offsets out */
+        stage_timer t(c, "guided_index", nq * ((int64_t)sizeof(ss_keypoint) + 16) + g.n_frames * (n_cells + 1) * 4);
+        ssk_guided_index(c->stream, g);
+    }
+    {
+        /* per query: its window (or keypoint), its descriptor, the 12 bytes it writes; the records and descriptors it visits depend
+         * on the content and are not counted */
+        stage_timer t(c, "guided_search", nq * ((g.windows ? 16 : (int64_t)sizeof(ss_keypoint)) + SS_DESC_BYTES + 12));
+        ssk_guided_search(c->stream, g);
+    }
+    {
+        /* idx read and written, d1, the candidate count; the two angles of a surviving match on top when orientation is on */
+        stage_timer t(c, "guided_finish", nq * (8 + 2 + 4 + (g.orientation ? 8 : 0)) + g.n_frames * (int64_t)sizeof(ss_guided_summary));
+        ssk_guided_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_match_guided_pairs_device(ss_ctx *c, const void *d_query, const void *d_query_kp, const void *d_n_query, const void *d_train,
+                                 const void *d_train_kp, const void *d_n_train, const void *d_windows, int n_frames, int rows_per_frame,
+                                 const ss_guided_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = guided_check_params(c, p);
+    if (rc != SS_OK) return rc;
+    if (n_frames < 0 || rows_per_frame < 1) return fail(c, SS_ERR_INVALID_ARG, "guided match: bad frame or row count");
+    if (rows_per_frame > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "guided match: rows_per_frame " + std::to_string(rows_per_frame) + " exceeds SS_GUIDED_MAX_ROWS (" +
+                                               std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    if (p->extent_w <= 0 || p->extent_h <= 0) return fail(c, SS_ERR_INVALID_ARG, "guided match: extent_w and extent_h must be > 0");
+    if (n_frames == 0) return SS_OK;
+    if (!d_query || !d_query_kp || !d_n_query || !d_train || !d_train_kp || !d_n_train || !d_windows || !d_idx || !d_d1 || !d_d2 || !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "guided match: NULL buffer");
+    ssk_guided_call g;
+    g.n_frames = n_frames;
+    g.rows = rows_per_frame;
+    g.q_kp = (const ss_keypoint *)d_query_kp, g.t_kp = (const ss_keypoint *)d_train_kp;
+    g.q_desc = (const uint8_t *)d_query, g.t_desc = (const uint8_t *)d_train;
+    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
+    g.windows = (const ss_guided_window *)d_windows;
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
+    g.summary = (ss_guided_summary *)d_summary;
+    return guided_run(c, g, p, p->extent_w, p->extent_h);
+}
+
+int ss_match_guided_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_windows, const ss_guided_params *p, void *d_idx,
+                                 void *d_d1, void *d_d2, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->have_geom || c->last_n_frames <= 0) return fail(c, SS_ERR_STATE, "ss_match_guided_batch_device: no batch has been extracted");
+    int rc = guided_check_params(c, p);
+    if (rc != SS_OK) return rc;
+    if (!d_idx || !d_d1 || !d_d2 || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "guided match: NULL output buffer");
+    const int n = c->last_n_frames, kcap = c->hg.kcap;
+    if (kcap > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "guided match: kp_capacity " + std::to_string(kcap) + " exceeds SS_GUIDED_MAX_ROWS");
+    for (int b = 0; train_src && b < n; b++)
+        if (train_src[b] < -1 || train_src[b] >= n)
+            return fail(c, SS_ERR_INVALID_ARG, "train_src[" + std::to_string(b) + "] = " + std::to_string(train_src[b]) + " names no frame of the batch (" +
+                                                   std::to_string(n) + "); the guided match takes no carry frames");
+    rc = upload_train_src(c, train_src, n);
+    if (rc != SS_OK) return rc;
+    ssk_guided_call g;
+    g.n_frames = n;
+    g.rows = kcap;
+    g.q_kp = g.t_kp = c->ws.kps;
+    g.q_desc = g.t_desc = c->ws.desc;
+    g.nq = g.nt = c->ws.n_kp;
+    g.src = c->d_train_src;
+    g.frame_error = c->ws.frame_error;
+    g.exclude_same_frame = 1;
+    g.windows = (const ss_guided_window *)d_windows;
+    g.dg = c->ws.dg;
+    g.radius = p->radius, g.radius_by_octave = p->radius_by_octave != 0, g.octave_span = p->octave_span;
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
+    g.summary = (ss_guided_summary *)d_summary;
+    return guided_run(c, g, p, c->hg.w, c->hg.h);
+}
+
+int ss_match_guided(ss_ctx *c, const uint8_t *query, const ss_keypoint *query_kp, int n_query, const uint8_t *train,
+                    const ss_keypoint *train_kp, int n_train, const ss_guided_window *windows, const ss_guided_params *p, int32_t *idx,
+                    uint16_t *d1, uint16_t *d2, ss_guided_summary *summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_query < 0 || n_train < 0 || n_query > SS_GUIDED_MAX_ROWS || n_train > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "guided match: n_query and n_train must be 0 .. SS_GUIDED_MAX_ROWS");
+    if ((n_query > 0 && (!query || !query_kp || !windows || !idx || !d1 || !d2)) || (n_train > 0 && (!train || !train_kp)) || !summary)
+        return fail(c, SS_ERR_INVALID_ARG, "guided match: NULL buffer");
+    /* one frame of `rows` rows on both sides: descriptors, keypoints, windows, the two counts, then the outputs */
+    const size_t rows = (size_t)std::max(std::max(n_query, n_train), 1);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_qd = 0, o_td = o_qd + up(rows * 32), o_qk = o_td + up(rows * 32), o_tk = o_qk + up(rows * sizeof(ss_keypoint));
+    const size_t o_win = o_tk + up(rows * sizeof(ss_keypoint)), o_n = o_win + up(rows * sizeof(ss_guided_window)), o_idx = o_n + 256;
+    const size_t o_d1 = o_idx + up(rows * 4), o_d2 = o_d1 + up(rows * 2), o_sum = o_d2 + up(rows * 2), total = o_sum + 256;
+    int rc = grow(c, c->d_guided_io, total);
+    if (rc != SS_OK) return rc;
+    uint8_t *d = c->d_guided_io;
+    const int32_t counts[2] = {n_query, n_train};
+    if (n_query > 0) {
+        HIP_TRY(c, hipMemcpyAsync(d + o_qd, query, (size_t)n_query * 32, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d + o_qk, query_kp, (size_t)n_query * sizeof(ss_keypoint), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d + o_win, windows, (size_t)n_query * sizeof(ss_guided_window), hipMemcpyHostToDevice, c->stream));
+    }
+    if (n_train > 0) {
+        HIP_TRY(c, hipMemcpyAsync(d + o_td, train, (size_t)n_train * 32, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d + o_tk, train_kp, (size_t)n_train * sizeof(ss_keypoint), hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(d + o_n, counts, sizeof(counts), hipMemcpyHostToDevice, c->stream));
+    rc = ss_match_guided_pairs_device(c, d + o_qd, d + o_qk, d + o_n, d + o_td, d + o_tk, d + o_n + 4, d + o_win, 1, (int)rows, p, d + o_idx, d + o_d1,
+                                      d + o_d2, d + o_sum);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream); /* `counts` is on this stack */
+        return rc;
+    }
+    if (n_query > 0) {
+        HIP_TRY(c, hipMemcpyAsync(idx, d + o_idx, (size_t)n_query * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d1, d + o_d1, (size_t)n_query * 2, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d2, d + o_d2, (size_t)n_query * 2, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(summary, d + o_sum, sizeof(ss_guided_summary), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }
 

@@ -142,6 +142,43 @@ struct ssk_stereo_call {
 void ssk_stereo_search(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ssk_stereo_call &st);
 void ssk_stereo_refine(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ss_lvl0 &l0, const ssk_stereo_call &st);
 void ssk_stereo_cut(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const ssk_stereo_call &st);
+/* ss_guided.hip: window search of n_frames (query frame, train frame) pairs (DESIGN.md "Guided matching").  Both sides are
+ * [frames][rows] arrays of keypoints and packed descriptors with per-frame counts; query frame b is matched against train frame
+ * src[b] (device int32 [n_frames]; -1 = no train; NULL = frame b).  index bins the keypoints of each train frame into the cells of a grid (cell_start, recs), search walks the cells a query's window meets and writes the raw best /
+ * second best, the accepted index and the candidate count of every row, finish applies the one-to-one and orientation filters
+ * and writes the summaries. */
+#define SSK_GUIDED_MAX_CELLS 4096 /* grid cells per train frame: their counts and offsets live in one workgroup's LDS */
+struct ssk_guided_call {
+    int n_frames = 0, rows = 0; /* frames on both sides, rows per frame */
+    const ss_keypoint *q_kp = nullptr, *t_kp = nullptr;
+    const uint8_t *q_desc = nullptr, *t_desc = nullptr;
+    const int32_t *nq = nullptr, *nt = nullptr;
+    const int32_t *src = nullptr;
+    const int32_t *frame_error = nullptr;       /* per frame of both sides (the batch form: they are the same frames), or NULL */
+    int exclude_same_frame = 0;                 /* the pair j == i is no candidate when src[b] == b */
+    const ss_guided_window *windows = nullptr;  /* [n_frames][rows], or NULL: the query's own position, radius (* scale[octave]
+                                                 * of *dg), octave -+ octave_span */
+    const ss_geom *dg = nullptr;
+    float radius = 0;
+    int radius_by_octave = 0, octave_span = 0;
+    int th = 0, rnum = 0, rden = 0, one_to_one = 0, orientation = 0;
+    /* the grid (ssk_guided_grid): cells of 1 << shift pixels, cols x grid_rows <= SSK_GUIDED_MAX_CELLS of them; coordinates are
+     * clamped to [0, x_max] x [0, y_max] before they are binned */
+    int shift = 0, cols = 1, grid_rows = 1;
+    float x_max = 0, y_max = 0;
+    /* workspace: [n_frames][SSK_GUIDED_MAX_CELLS + 1] cell offsets, [n_frames][rows] 16-byte records,
+     * [n_frames][rows] candidate counts */
+    uint32_t *cell_start = nullptr;
+    void *recs = nullptr;
+    int32_t *n_cand = nullptr;
+    int32_t *idx = nullptr;
+    uint16_t *d1 = nullptr, *d2 = nullptr;
+    ss_guided_summary *summary = nullptr;
+};
+void ssk_guided_grid(ssk_guided_call &g, int extent_w, int extent_h);
+void ssk_guided_index(hipStream_t s, const ssk_guided_call &g);
+void ssk_guided_search(hipStream_t s, const ssk_guided_call &g);
+void ssk_guided_finish(hipStream_t s, const ssk_guided_call &g);
 /* test hook: run the device std::sort restatement on n <= 2048 items (size << 32 | UL.x << 20 | id) */
 int ssk_debug_sort(hipStream_t s, uint64_t *d_items, int n);
 #define SSK_MATCH_MFMA_MIN_QUERIES 128 /* from this many query rows on, ssk_match runs a matrix-core kernel */

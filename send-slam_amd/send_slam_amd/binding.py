@@ -18,6 +18,7 @@ SS_MAX_LEVELS = 16
 EXPANDED_ROW_BYTES = 128  # one FP4 value (+1 / -1) per descriptor bit
 ABI_VERSION = 5
 SS_TRACK_DESC_STAYS_VALID = 1
+SS_GUIDED_MAX_ROWS = 16384
 
 SS_OK = 0
 SS_ERR_INVALID_ARG, SS_ERR_NO_DEVICE, SS_ERR_HIP, SS_ERR_TOO_SMALL = -1, -2, -3, -4
@@ -35,7 +36,7 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_match_fold_strided_device", "ss_xchg_create", "ss_xchg_destroy", "ss_xchg_last_error", "ss_xchg_status",
            "ss_xchg_allgather", "ss_xchg_broadcast", "ss_pipe_debug_inject_failure", "ss_stereo_exchange_match",
            "ss_match_batch_sources_device", "ss_track_detach", "ss_pipe_match_sources", "ss_stereo_batch_device",
-           "ss_extract_stereo"]
+           "ss_extract_stereo", "ss_match_guided_pairs_device", "ss_match_guided_batch_device", "ss_match_guided"]
 
 
 class OrbParams(C.Structure):
@@ -109,6 +110,30 @@ class StereoSummary(C.Structure):
 # ss_stereo_point: one per left keypoint row
 STEREO_POINT_DTYPE = np.dtype([("u_right", "<f4"), ("depth", "<f4"), ("right_idx", "<i4"), ("orb_dist", "<u2"), ("sad", "<u2")])
 STEREO_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n, _ in StereoSummary._fields_])
+
+
+class GuidedParams(C.Structure):
+    _fields_ = [("th", C.c_int32), ("ratio_num", C.c_int32), ("ratio_den", C.c_int32), ("one_to_one", C.c_int32),
+                ("orientation", C.c_int32), ("radius", C.c_float), ("radius_by_octave", C.c_int32), ("octave_span", C.c_int32),
+                ("extent_w", C.c_int32), ("extent_h", C.c_int32)]
+
+
+class GuidedSummary(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_query", C.c_int32), ("n_train", C.c_int32), ("n_candidates", C.c_int32),
+                ("n_accepted", C.c_int32), ("n_unique", C.c_int32), ("n_final", C.c_int32), ("rot_bins", C.c_int32)]
+
+
+# ss_guided_window: one per query row
+GUIDED_WINDOW_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("radius", "<f4"), ("oct_lo", "<i2"), ("oct_hi", "<i2")])
+GUIDED_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n, _ in GuidedSummary._fields_])
+
+
+def guided_params(th: int = 50, ratio_num: int = 9, ratio_den: int = 10, one_to_one: bool = False, orientation: int = 0,
+                  radius: float = 0.0, radius_by_octave: bool = False, octave_span: int = 0, extent_w: int = 0,
+                  extent_h: int = 0) -> GuidedParams:
+    return GuidedParams(th=th, ratio_num=ratio_num, ratio_den=ratio_den, one_to_one=int(one_to_one), orientation=orientation,
+                        radius=radius, radius_by_octave=int(radius_by_octave), octave_span=octave_span, extent_w=extent_w,
+                        extent_h=extent_h)
 
 
 class OrbError(RuntimeError):
@@ -201,6 +226,10 @@ def load():
     lib.ss_stereo_batch_device.argtypes = [C.c_void_p, C.POINTER(StereoParams), C.c_void_p, C.c_void_p]
     lib.ss_extract_stereo.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                       C.POINTER(FrameResult), C.POINTER(FrameResult), C.POINTER(C.c_void_p), C.POINTER(StereoSummary)]
+    lib.ss_match_guided_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 7 + [C.c_int, C.c_int, C.POINTER(GuidedParams)] + [C.c_void_p] * 4
+    lib.ss_match_guided_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GuidedParams)] + [C.c_void_p] * 4
+    lib.ss_match_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.POINTER(GuidedParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GuidedSummary)]
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -464,6 +493,42 @@ class OrbContext:
         if rl.n_keypoints:
             C.memmove(points.ctypes.data, pts.value, rl.n_keypoints * STEREO_POINT_DTYPE.itemsize)
         return out[0], out[1], out[2], out[3], points, {n: getattr(summ, n) for n, _ in StereoSummary._fields_}
+
+    # ---- guided matching: window search, conflicts, rotation histogram (the rule: include/sendslam_orb.h) ----
+    def match_guided_pairs_device(self, d_q: int, d_q_kp: int, d_nq: int, d_t: int, d_t_kp: int, d_nt: int, d_windows: int,
+                                  n_frames: int, rows_per_frame: int, params: GuidedParams, d_idx: int, d_d1: int, d_d2: int,
+                                  d_summary: int):
+        """n_frames independent (query, train) pairs on device arrays [n_frames][rows_per_frame] (descriptors, KP_DTYPE
+        keypoints, GUIDED_WINDOW_DTYPE windows); d_summary [n_frames] GUIDED_SUMMARY_DTYPE rows; asynchronous."""
+        self._check(self._lib.ss_match_guided_pairs_device(self._h, C.c_void_p(d_q), C.c_void_p(d_q_kp), C.c_void_p(d_nq), C.c_void_p(d_t),
+                                                           C.c_void_p(d_t_kp), C.c_void_p(d_nt), C.c_void_p(d_windows), n_frames,
+                                                           rows_per_frame, C.byref(params), C.c_void_p(d_idx), C.c_void_p(d_d1),
+                                                           C.c_void_p(d_d2), C.c_void_p(d_summary)))
+
+    def match_guided_batch_device(self, params: GuidedParams, d_idx: int, d_d1: int, d_d2: int, d_summary: int, train_src=None,
+                                  d_windows: int = 0):
+        """The frames of the last batch, frame b against train_src[b] (host ints; None: b - 1); d_windows [n_frames][kp_capacity]
+        or 0: the windows follow from params (radius, radius_by_octave, octave_span); asynchronous."""
+        src = None if train_src is None else np.ascontiguousarray(train_src, dtype=np.int32)
+        self._check(self._lib.ss_match_guided_batch_device(self._h, None if src is None else src.ctypes.data, C.c_void_p(d_windows),
+                                                           C.byref(params), C.c_void_p(d_idx), C.c_void_p(d_d1), C.c_void_p(d_d2),
+                                                           C.c_void_p(d_summary)))
+
+    def match_guided(self, q: np.ndarray, q_kp: np.ndarray, t: np.ndarray, t_kp: np.ndarray, windows: np.ndarray, params: GuidedParams):
+        """One pair, host arrays in and out -> (idx, d1, d2, summary dict)."""
+        q = np.ascontiguousarray(q, np.uint8).reshape(-1, 32)
+        t = np.ascontiguousarray(t, np.uint8).reshape(-1, 32)
+        q_kp, t_kp = np.ascontiguousarray(q_kp, KP_DTYPE), np.ascontiguousarray(t_kp, KP_DTYPE)
+        windows = np.ascontiguousarray(windows, GUIDED_WINDOW_DTYPE)
+        nq, nt = len(q), len(t)
+        if len(q_kp) != nq or len(windows) != nq or len(t_kp) != nt:
+            raise ValueError("descriptors, keypoints and windows differ in length")
+        idx, d1, d2, summ = np.empty(nq, np.int32), np.empty(nq, np.uint16), np.empty(nq, np.uint16), GuidedSummary()
+        self._check(self._lib.ss_match_guided(self._h, q.ctypes.data if nq else None, q_kp.ctypes.data if nq else None, nq,
+                                              t.ctypes.data if nt else None, t_kp.ctypes.data if nt else None, nt,
+                                              windows.ctypes.data if nq else None, C.byref(params), idx.ctypes.data, d1.ctypes.data,
+                                              d2.ctypes.data, C.byref(summ)))
+        return idx, d1, d2, {n: getattr(summ, n) for n, _ in GuidedSummary._fields_}
 
     def wait_stream(self, hip_stream: int):
         """Orders this context's stream after everything enqueued so far on another stream of the device."""

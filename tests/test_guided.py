@@ -1,0 +1,356 @@
+"""GPU parity of guided matching (ss_match_guided_batch_device, ss_match_guided_pairs_device, ss_match_guided) against
+tests/guided_ref.py: bit for bit, no tolerance -- idx, d1, d2 of every row and every summary field."""
+import glob
+import os
+
+import numpy as np
+import pytest
+
+import guided_cases as G
+import guided_ref as R
+
+pytestmark = pytest.mark.gpu
+
+
+def _dev():
+    import torch
+    return torch.device("cuda:0")
+
+
+class Outputs:
+    """device idx / d1 / d2 [n, rows] and summaries [n], prefilled with a pattern no result has"""
+
+    def __init__(self, n, rows):
+        import torch
+        self.n, self.rows = n, rows
+        self.idx = torch.full((n, rows), 0x5A5A5A5A, dtype=torch.int32, device=_dev())
+        self.d1 = torch.full((n, rows), 0x5A5A, dtype=torch.int16, device=_dev())
+        self.d2 = torch.full((n, rows), 0x5A5A, dtype=torch.int16, device=_dev())
+        self.summary = torch.full((n, 32), 0x5A, dtype=torch.uint8, device=_dev())
+
+    def ptrs(self):
+        return self.idx.data_ptr(), self.d1.data_ptr(), self.d2.data_ptr(), self.summary.data_ptr()
+
+    def host(self):
+        from send_slam_amd import binding
+        summ = self.summary.cpu().numpy().copy().view(binding.GUIDED_SUMMARY_DTYPE).reshape(self.n)
+        return (self.idx.cpu().numpy(), self.d1.cpu().numpy().view(np.uint16), self.d2.cpu().numpy().view(np.uint16),
+                [{f: int(s[f]) for f in R.SUMMARY_FIELDS} for s in summ])
+
+
+def _check(tag, got, b, want):
+    """frame b of a call's host outputs against a reference result; rows past the queries must be "none" """
+    idx, d1, d2, summ = got
+    widx, wd1, wd2, wsumm = want[:4]
+    n = len(widx)
+    assert summ[b] == wsumm, f"{tag}: summary {summ[b]} != {wsumm}"
+    for name, g, w in (("idx", idx[b], widx), ("d1", d1[b], wd1), ("d2", d2[b], wd2)):
+        bad = np.flatnonzero(g[:n] != w)
+        assert len(bad) == 0, f"{tag}: {name} differs at rows {bad[:8]}: {g[:n][bad[:8]]} != {w[bad[:8]]}"
+    assert (idx[b][n:] == -1).all() and (d1[b][n:] == R.NONE).all() and (d2[b][n:] == R.NONE).all(), f"{tag}: rows past the queries are not 'none'"
+
+
+def _params(binding, combo, **kw):
+    return binding.guided_params(radius=G.RADIUS, radius_by_octave=True, octave_span=G.SPAN, **combo, **kw)
+
+
+def _extract(ctx, names, w=G.W, h=G.H, nf=G.NF):
+    """the named frames as one batch; the device features must be the oracle's (the references are computed on those)"""
+    import torch
+    frames = np.stack([G.frame(n, w, h) for n in names])
+    d = torch.from_numpy(frames).to(_dev())
+    ctx.extract_batch_device(d.data_ptr(), len(names), w, h)
+    ctx.synchronize()
+    for b, n in enumerate(names):
+        kp, desc, _ = ctx.fetch_frame(b)
+        okp, odesc = G.features(n, w, h, nf)
+        assert kp.tobytes() == okp.tobytes() and np.array_equal(desc, odesc), f"frame {b} ({n}): extraction differs from the oracle"
+    return d, ctx.batch_view().kp_capacity
+
+
+@pytest.fixture(scope="module")
+def batch_ctx():
+    from send_slam_amd import binding
+    with binding.OrbContext(0, n_features=G.NF, max_batch=len(G.BATCH)) as ctx:
+        pixels, kcap = _extract(ctx, G.BATCH)
+        yield ctx, kcap, pixels
+
+
+@pytest.mark.parametrize("combo", G.COMBOS, ids=G.combo_name)
+def test_batch_window_form(batch_ctx, combo):
+    """one batch, frame b against b - 1, radius 15 * scale[octave], octave -+ 1"""
+    from send_slam_amd import binding
+    ctx, kcap, _ = batch_ctx
+    out = Outputs(len(G.BATCH), kcap)
+    ctx.match_guided_batch_device(_params(binding, combo), *out.ptrs())
+    ctx.synchronize()
+    got = out.host()
+    for b, name in enumerate(G.BATCH):
+        want = G.reference_pair(name, G.BATCH[b - 1] if b else None, combo)
+        print(b, name, want[3])
+        _check(f"frame {b} ({name}) {G.combo_name(combo)}", got, b, want)
+
+
+def _upload(frames, rows):
+    """frames: list of dicts q_kp q_desc t_kp t_desc windows -> device arrays [n][rows] of the pairs form"""
+    import torch
+    from send_slam_amd import binding
+    n = len(frames)
+    host = {"q_desc": np.zeros((n, rows, 32), np.uint8), "t_desc": np.zeros((n, rows, 32), np.uint8),
+            "q_kp": np.zeros((n, rows), binding.KP_DTYPE), "t_kp": np.zeros((n, rows), binding.KP_DTYPE),
+            "windows": np.zeros((n, rows), binding.GUIDED_WINDOW_DTYPE), "nq": np.zeros(n, np.int32), "nt": np.zeros(n, np.int32)}
+    for b, f in enumerate(frames):
+        nq, nt = len(f["q_kp"]), len(f["t_kp"])
+        host["nq"][b], host["nt"][b] = nq, nt
+        host["q_desc"][b, :nq], host["q_kp"][b, :nq], host["windows"][b, :nq] = f["q_desc"], f["q_kp"], f["windows"]
+        host["t_desc"][b, :nt], host["t_kp"][b, :nt] = f["t_desc"], f["t_kp"]
+    dev = {k: torch.from_numpy(v.view(np.uint8).reshape(n, -1) if v.dtype.fields else v).to(_dev()) for k, v in host.items()}
+    return dev
+
+
+def _run_pairs(ctx, dev, n, rows, params):
+    out = Outputs(n, rows)
+    ctx.match_guided_pairs_device(dev["q_desc"].data_ptr(), dev["q_kp"].data_ptr(), dev["nq"].data_ptr(), dev["t_desc"].data_ptr(),
+                                  dev["t_kp"].data_ptr(), dev["nt"].data_ptr(), dev["windows"].data_ptr(), n, rows, params, *out.ptrs())
+    ctx.synchronize()
+    return out.host()
+
+
+def _named_pairs(names):
+    frames = []
+    for q, t in zip(names[1:], names[:-1]):
+        (qk, qd), (tk, td) = G.features(q), G.features(t)
+        frames.append({"q_kp": qk, "q_desc": qd, "t_kp": tk, "t_desc": td, "windows": R.whole_windows(len(qk))})
+    return frames
+
+
+def test_whole_image_windows_equal_the_all_pairs_matcher():
+    """the same device arrays through ss_match_pairs_device and through the guided search with windows that hold everything:
+    outputs equal, no reference involved"""
+    from send_slam_amd import binding
+    frames = _named_pairs(G.BATCH)
+    n, rows = len(frames), 512
+    dev = _upload(frames, rows)
+    with binding.OrbContext(0, n_features=G.NF) as ctx:
+        want = Outputs(n, rows)
+        ctx.match_pairs_device(dev["q_desc"].data_ptr(), dev["nq"].data_ptr(), dev["t_desc"].data_ptr(), dev["nt"].data_ptr(), n, rows,
+                               want.idx.data_ptr(), want.d1.data_ptr(), want.d2.data_ptr(), th=50, ratio_num=9, ratio_den=10)
+        ctx.synchronize()
+        got = _run_pairs(ctx, dev, n, rows, binding.guided_params(th=50, ratio_num=9, ratio_den=10, extent_w=G.W, extent_h=G.H))
+    widx, wd1, wd2, _ = want.host()
+    assert np.array_equal(got[0], widx) and np.array_equal(got[1], wd1) and np.array_equal(got[2], wd2)
+    assert sum(s["n_accepted"] for s in got[3]) == int((widx >= 0).sum()) > 500
+    for b, f in enumerate(frames):
+        assert got[3][b]["n_candidates"] == len(f["q_kp"]) * len(f["t_kp"])
+
+
+def _kp(x, y, octave=0, angle=0.0):
+    from send_slam_amd import binding
+    x = np.asarray(x, np.float32)
+    kp = np.zeros(len(x), binding.KP_DTYPE)
+    kp["x"], kp["y"], kp["octave"], kp["angle"], kp["size"] = x, y, octave, angle, 31
+    return kp
+
+
+def _crafted_frames():
+    """pairs-form frames that reach the edges of the rule (rows_per_frame 4100, counts 1 / 31 / 33 / 4100)"""
+    rng = np.random.Generator(np.random.PCG64(0x9D1DED))
+
+    def desc(n):
+        return rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
+
+    def angles(n):
+        return rng.integers(0, 360 * 4, size=n).astype(np.float32) / np.float32(4)
+
+    frames = {}
+    # |dx| == radius exactly is outside: integer coordinates, radius 7 around x = 120 holds 114 .. 126 of 100 .. 140; same for y
+    tx = np.arange(100, 141, dtype=np.float32)
+    tk = np.concatenate([_kp(tx, np.full(41, 50.0)), _kp(np.full(41, 300.0), tx)])
+    tk["angle"] = angles(82)
+    qk = _kp([120.0] * 33, [50.0] * 33, angle=angles(33))
+    win = R.make_windows([120.0] * 16 + [300.0] * 17, [50.0] * 16 + [120.0] * 17, [7.0] * 33, 0, 0)
+    frames["boundary"] = {"q_kp": qk, "q_desc": desc(33), "t_kp": tk, "t_desc": desc(82), "windows": win}
+    # 600 train rows at one position: all in one cell, no per-cell capacity
+    tk = _kp(np.full(600, 77.0), np.full(600, 33.0), octave=rng.integers(0, 3, 600), angle=angles(600))
+    frames["one_cell"] = {"q_kp": _kp([77.0] * 31, [33.0] * 31, angle=angles(31)), "q_desc": desc(31), "t_kp": tk, "t_desc": desc(600),
+                          "windows": R.make_windows([77.0] * 31, [33.5] * 31, [1.0] * 31, rng.integers(0, 2, 31), 2)}
+    # coordinates no image has, on both sides
+    odd = np.array([np.nan, np.inf, -np.inf, -50.0, 1e30, 10.0, 600.0], np.float32)
+    tk = _kp(odd[rng.integers(0, 7, 200)], odd[rng.integers(0, 7, 200)], angle=angles(200))
+    tk["x"][:20], tk["y"][:20] = rng.integers(0, 640, 20), rng.integers(0, 480, 20)
+    wx, wy = odd[rng.integers(0, 7, 33)], odd[rng.integers(0, 7, 33)]
+    wr = np.array([30.0, 100.0, 1e9, np.inf, 1e31], np.float32)[rng.integers(0, 5, 33)]
+    frames["odd_coordinates"] = {"q_kp": _kp(np.zeros(33), np.zeros(33), angle=angles(33)), "q_desc": desc(33), "t_kp": tk, "t_desc": desc(200),
+                                 "windows": R.make_windows(wx, wy, wr, 0, 15)}
+    # radius 0 / negative / NaN and oct_lo > oct_hi take no part; every fifth window is a plain one
+    tk = _kp(rng.integers(0, 640, 300), rng.integers(0, 480, 300), octave=rng.integers(0, 8, 300), angle=angles(300))
+    win = R.make_windows(rng.integers(0, 640, 33), rng.integers(0, 480, 33), np.tile(np.array([0.0, -5.0, np.nan, 80.0, 80.0], np.float32), 7)[:33], 0, 7)
+    win["oct_lo"][3::5], win["oct_hi"][3::5] = 5, 4
+    frames["no_part"] = {"q_kp": _kp(np.zeros(33), np.zeros(33), angle=angles(33)), "q_desc": desc(33), "t_kp": tk, "t_desc": desc(300), "windows": win}
+    # an empty side
+    frames["no_train"] = {"q_kp": _kp([5.0], [5.0]), "q_desc": desc(1), "t_kp": _kp([], []), "t_desc": desc(0), "windows": R.make_windows([5.0], [5.0], [50.0], 0, 7)}
+    frames["no_query"] = {"q_kp": _kp([], []), "q_desc": desc(0), "t_kp": _kp(rng.integers(0, 640, 4100), rng.integers(0, 480, 4100)), "t_desc": desc(4100),
+                          "windows": R.make_windows([], [], [], 0, 7)}
+    # every row used on both sides, windows of 12 .. 36 px, descriptors drawn from 64 prototypes with a few bits flipped
+    proto = desc(64)
+
+    def near(n):
+        d = proto[rng.integers(0, 64, n)].copy()
+        d[np.arange(n), rng.integers(0, 32, n)] ^= rng.integers(0, 256, n).astype(np.uint8)
+        return d
+
+    tk = _kp(rng.integers(0, 640, 4100), rng.integers(0, 480, 4100), octave=rng.integers(0, 8, 4100), angle=angles(4100))
+    qk = _kp(np.zeros(4100), np.zeros(4100), angle=angles(4100))
+    win = R.make_windows(rng.integers(0, 640, 4100), rng.integers(0, 480, 4100), rng.integers(12, 37, 4100), rng.integers(0, 4, 4100), rng.integers(3, 8, 4100))
+    frames["full"] = {"q_kp": qk, "q_desc": near(4100), "t_kp": tk, "t_desc": near(4100), "windows": win}
+    # all descriptors identical: the lowest train row, and under one_to_one the lowest query
+    same = np.tile(desc(1), (33, 1))
+    frames["identical"] = {"q_kp": _kp(np.zeros(33), np.zeros(33), angle=angles(33)), "q_desc": same, "t_kp": _kp(rng.integers(0, 640, 31), rng.integers(0, 480, 31)),
+                           "t_desc": same[:31], "windows": R.whole_windows(33)}
+    return frames
+
+
+def test_pairs_form_on_crafted_arrays():
+    from send_slam_amd import binding
+    frames = _crafted_frames()
+    names, rows = list(frames), 4100
+    dev = _upload([frames[k] for k in names], rows)
+    found = {k: R.search(f["q_desc"], f["t_kp"] if len(f["t_kp"]) else None, f["t_desc"], f["windows"]) for k, f in frames.items()}
+    # the cases are what they claim to be, on the REFERENCE
+    b = found["boundary"]
+    assert b[3][0] == list(range(14, 27)) and b[3][20] == list(range(41 + 14, 41 + 27))
+    assert all(len(c) > 100 for c in found["one_cell"][3]) and sum(len(c) for c in found["full"][3]) > 20000
+    assert sum(len(c) for c in found["no_part"][3][3::5]) == 0 and sum(len(c) for c in found["no_part"][3][4::5]) > 0
+    assert 0 < sum(len(c) for c in found["odd_coordinates"][3])
+    assert (found["identical"][0] == 0).all() and (found["identical"][1] == 0).all() and (found["identical"][2] == 0).all()
+    combos = [dict(G.RULES[0], one_to_one=False, orientation=0), dict(G.RULES[1], one_to_one=True, orientation=2),
+              dict(G.RULES[1], one_to_one=True, orientation=1)]
+    with binding.OrbContext(0, n_features=G.NF) as ctx:
+        for c in combos:
+            got = _run_pairs(ctx, dev, len(names), rows, binding.guided_params(**c, extent_w=640, extent_h=480))
+            for i, k in enumerate(names):
+                f = frames[k]
+                want = R.finish(found[k], f["q_kp"], f["t_kp"] if len(f["t_kp"]) else None, **c)
+                _check(f"{k} {G.combo_name(c)}", got, i, want)
+                if k == "identical" and c["one_to_one"]:
+                    assert want[3]["n_accepted"] == 33 and want[3]["n_unique"] == 1 and want[0][0] == 0
+        # too many rows: refused, and the context still works
+        with pytest.raises(binding.OrbError) as e:
+            _run_pairs(ctx, dev, 1, binding.SS_GUIDED_MAX_ROWS + 1, binding.guided_params(extent_w=640, extent_h=480))
+        assert e.value.code == binding.SS_ERR_INVALID_ARG and "SS_GUIDED_MAX_ROWS" in e.value.message
+        for bad in (dict(extent_w=0, extent_h=480), dict(extent_w=640, extent_h=480, orientation=3), dict(extent_w=640, extent_h=480, ratio_den=-1)):
+            with pytest.raises(binding.OrbError) as e:
+                _run_pairs(ctx, dev, len(names), rows, binding.guided_params(**bad))
+            assert e.value.code == binding.SS_ERR_INVALID_ARG
+        # the index is sized by the extent only: another extent, the same results
+        c = combos[1]
+        got = _run_pairs(ctx, dev, len(names), rows, binding.guided_params(**c, extent_w=5000, extent_h=37))
+        for i, k in enumerate(names):
+            f = frames[k]
+            _check(f"{k} after the refused calls", got, i, R.finish(found[k], f["q_kp"], f["t_kp"] if len(f["t_kp"]) else None, **c))
+
+
+def test_table_form(batch_ctx):
+    """t == b (the self pair is excluded), t == -1, an earlier and a later frame; bad entries are refused; explicit windows
+    give what the NULL form gives"""
+    import torch
+    from send_slam_amd import binding
+    ctx, kcap, _ = batch_ctx
+    n = len(G.BATCH)
+    table = np.array([0, -1, 2, 1, 9, 4, 7, 6, 8, 0, 10, 3, 12], np.int32)  # self: 0 2 8 10 12; later: 4 <- 9, 6 <- 7
+    combo = dict(G.RULES[1], one_to_one=True, orientation=1)
+    out = Outputs(n, kcap)
+    ctx.match_guided_batch_device(_params(binding, combo), *out.ptrs(), train_src=table)
+    ctx.synchronize()
+    got = out.host()
+    selfs = 0
+    for b, t in enumerate(table):
+        want = G.reference_pair(G.BATCH[b], G.BATCH[t] if t >= 0 else None, combo, exclude_self=bool(t == b))
+        _check(f"frame {b} against {t}", got, b, want)
+        if t == b and want[3]["n_query"]:
+            assert not (got[0][b][:want[3]["n_query"]] == np.arange(want[3]["n_query"])).any()
+            selfs += want[3]["n_accepted"]
+    assert selfs > 0
+    for bad in (-2, n):
+        t2 = table.copy()
+        t2[5] = bad
+        with pytest.raises(binding.OrbError) as e:
+            ctx.match_guided_batch_device(_params(binding, combo), *out.ptrs(), train_src=t2)
+        assert e.value.code == binding.SS_ERR_INVALID_ARG and "train_src[5]" in e.value.message
+    # explicit windows
+    win = np.zeros((n, kcap), binding.GUIDED_WINDOW_DTYPE)
+    for b, name in enumerate(G.BATCH):
+        w = G.own_windows(G.features(name)[0])
+        win[b, :len(w)] = w
+    d_win = torch.from_numpy(win.view(np.uint8).reshape(n, -1)).to(_dev())
+    out2 = Outputs(n, kcap)
+    ctx.match_guided_batch_device(binding.guided_params(**combo), *out2.ptrs(), train_src=table, d_windows=d_win.data_ptr())
+    ctx.synchronize()
+    got2 = out2.host()
+    assert all(np.array_equal(a, b) for a, b in zip(got[:3], got2[:3])) and got[3] == got2[3]
+
+
+def test_second_batch_of_another_size_on_the_same_context():
+    """nothing of the first call's index or workspace leaks into the second: 320 x 240 frames, then 400 x 260 ones, then back"""
+    from send_slam_amd import binding
+    combo = dict(G.RULES[0], one_to_one=True, orientation=2)
+    calls = [(["dots", "dots_shift", "synth_t0", "synth_t1"], G.W, G.H), (["synth_t0", "synth_t1", "checker"], 400, 260),
+             (["synth_t2", "synth_t3"], G.W, G.H)]
+    with binding.OrbContext(0, n_features=G.NF, max_batch=4) as ctx:
+        for names, w, h in calls:
+            pixels, kcap = _extract(ctx, names, w, h)
+            out = Outputs(len(names), kcap)
+            ctx.match_guided_batch_device(_params(binding, combo), *out.ptrs())
+            ctx.synchronize()
+            got = out.host()
+            for b, name in enumerate(names):
+                want = G.reference_pair(name, names[b - 1] if b else None, combo, w, h)
+                _check(f"{w}x{h} frame {b} ({name})", got, b, want)
+            assert got[3][1]["n_final"] > 50
+
+
+def test_host_form_equals_the_pairs_form_and_the_goldens(golden_dir):
+    from send_slam_amd import binding
+    files = sorted(glob.glob(os.path.join(golden_dir, "guided", "*.npz")))
+    assert len(files) >= 3
+    with binding.OrbContext(0, n_features=G.NF) as ctx:
+        for path in files:
+            g = np.load(path)
+            f = {k: g[k] for k in ("q_kp", "q_desc", "t_kp", "t_desc", "windows")}
+            rows = max(len(f["q_kp"]), len(f["t_kp"]))
+            dev = _upload([f], rows)
+            for c in G.COMBOS:
+                p = binding.guided_params(**c, extent_w=G.W, extent_h=G.H)
+                idx, d1, d2, summ = ctx.match_guided(f["q_desc"], f["q_kp"], f["t_desc"], f["t_kp"], f["windows"], p)
+                n = G.combo_name(c)
+                assert np.array_equal(idx, g[n + "_idx"]) and np.array_equal(d1, g[n + "_d1"]) and np.array_equal(d2, g[n + "_d2"]), (path, n)
+                assert [summ[k] for k in R.SUMMARY_FIELDS] == list(g[n + "_summary"]), (path, n)
+                pairs = _run_pairs(ctx, dev, 1, rows, p)
+                nq = len(idx)
+                assert np.array_equal(pairs[0][0][:nq], idx) and np.array_equal(pairs[1][0][:nq], d1) and np.array_equal(pairs[2][0][:nq], d2)
+                assert pairs[3][0] == summ
+        # empty sides through the host form
+        f = {k: g[k] for k in ("q_kp", "q_desc", "t_kp", "t_desc", "windows")}
+        idx, d1, d2, summ = ctx.match_guided(f["q_desc"], f["q_kp"], f["t_desc"][:0], f["t_kp"][:0], f["windows"], p)
+        assert (idx == -1).all() and (d1 == R.NONE).all() and summ["n_train"] == 0 and summ["n_query"] == len(idx)
+        idx, d1, d2, summ = ctx.match_guided(f["q_desc"][:0], f["q_kp"][:0], f["t_desc"], f["t_kp"], f["windows"][:0], p)
+        assert len(idx) == 0 and summ["n_query"] == 0 and summ["n_candidates"] == 0
+
+
+def test_one_pair_at_1280x720_2000_features():
+    """the capacity paths: kp_capacity rows, a 40 x 23 cell grid"""
+    from send_slam_amd import binding
+    w, h, nf = 1280, 720, 2000
+    names = ["synth_t0", "synth_t1"]
+    combo = dict(G.RULES[0], one_to_one=True, orientation=1)
+    with binding.OrbContext(0, n_features=nf, max_batch=2) as ctx:
+        pixels, kcap = _extract(ctx, names, w, h, nf)
+        out = Outputs(2, kcap)
+        ctx.match_guided_batch_device(_params(binding, combo), *out.ptrs())
+        ctx.synchronize()
+        got = out.host()
+    for b, name in enumerate(names):
+        want = G.reference_pair(name, names[b - 1] if b else None, combo, w, h, nf)
+        print(want[3])
+        _check(f"1280x720 frame {b}", got, b, want)
+    assert want[3]["n_query"] > 1500 and want[3]["n_final"] > 500 and want[3]["n_candidates"] < want[3]["n_query"] * want[3]["n_train"] // 50

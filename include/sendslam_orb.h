@@ -33,6 +33,8 @@
  *                              front-end; the pose SendPosePacket :225-282 ships)
  *   ss_stereo_batch_device /   ORB_SLAM3::Frame::ComputeStereoMatches (the stereo Frame constructor; no counterpart in the
  *   ss_extract_stereo          monocular shim, which only ships th_depth / baseline :59-77)
+ *   ss_rectify_* /             cv::initUndistortRectifyMap + cv::remap(INTER_LINEAR) of upstream's stereo examples, which run on every
+ *   ss_extract_stereo_raw      frame of both eyes before the extractor (no counterpart in the monocular shim)
  *   ss_match_guided*           ORBmatcher::SearchForInitialization / SearchByProjection on Frame::GetFeaturesInArea (window
  *                              search, conflicts, rotation histogram; the monocular shim reaches them inside TrackMonocular :594)
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
@@ -352,7 +354,7 @@ int ss_stereo_exchange_match(ss_ctx *ctx, ss_xchg *x, int peer_rank, int th, int
  * lose their depth again.  Ties: lowest right index, lowest shift.  Two deviations from upstream: a SAD window that would
  * leave the level image rejects the point (upstream would read outside it), and a pair without an accepted point is left
  * alone (upstream indexes an empty vector).  Input is assumed rectified: distortion coefficients are ignored, as upstream
- * ignores them here (it uses mvKeys).  Upstream's stereo constructor extracts both eyes with lapping area {0, 0}: that is
+ * ignores them here (it uses mvKeys); ss_rectify_* below make such a pair from raw frames.  Upstream's stereo constructor extracts both eyes with lapping area {0, 0}: that is
  * the stereo setting of ss_orb_params; the outputs are indexed by left keypoint row, so any lapping works. */
 typedef struct {
     float fx, baseline, th_depth; /* Camera.fx, Stereo.b (metres; bf = baseline * fx), Stereo.ThDepth */
@@ -385,6 +387,65 @@ int ss_stereo_batch_device(ss_ctx *ctx, const ss_stereo_params *p, void *d_point
 int ss_extract_stereo(ss_ctx *ctx, int camera_id, const uint8_t *left, const uint8_t *right, int width, int height,
                       int channels, int row_stride, double timestamp, ss_frame_result *out_left,
                       ss_frame_result *out_right, const ss_stereo_point **points, ss_stereo_summary *summary);
+
+/* ---- rectification of raw stereo pairs (upstream ORB-SLAM3's stereo examples: cv::initUndistortRectifyMap once per eye, then
+ * cv::remap(raw, rect, M1, M2, INTER_LINEAR) on every frame of both eyes before the extractor sees a pixel; neither OpenCV file,
+ * imgwarp.cpp / undistort.dispatch.cpp, is in the reference tree: the rule below is this library's own restatement from OpenCV
+ * 4.x as recalled, parity with a real OpenCV build unpinned like the rest of the path; tests/rectify_ref.py is the normative
+ * statement, reproduced bit for bit) -------------------------------------------------------------------
+ * Map builder (double precision, every step one IEEE operation): A = K' * R (each entry summed k = 0, 1, 2 left to right),
+ *   ir = A^-1 by the 3 x 3 adjugate (det == 0 or not finite: SS_ERR_INVALID_ARG).  Row i starts at _x = i * ir[1] + ir[2],
+ *   _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8]; column j uses them and then adds ir[0], ir[3], ir[6] (the running sum is
+ *   upstream's form, not j * ir[0] + ...).  Per pixel: w = 1 / _w, x = _x * w, y = _y * w, x2 = x * x, y2 = y * y, r2 = x2 + y2,
+ *   _2xy = 2 * x * y, kr = 1 + ((k3 * r2 + k2) * r2 + k1) * r2, xd = x * kr + p1 * _2xy + p2 * (r2 + 2 * x2),
+ *   yd = y * kr + p1 * (r2 + 2 * y2) + p2 * _2xy, map_x = (float)(fx * xd + cx), map_y = (float)(fy * yd + cy).  The rational
+ *   denominator (k4 .. k6), the thin-prism and the tilt terms are not modelled; fisheye models are not either: such callers
+ *   hand their own float maps to ss_rectify_set_map.
+ * Fixed point, per float32 map value v: t = v * 32.0f; s = (int32)rintf(t), half to even, when t is finite and
+ *   -2^31 <= t < 2^31, else INT32_MIN (cvRound on x86-64; the pixel then lies outside every image);
+ *   i = clamp(s >> 5, -32768, 32767) (arithmetic shift), f = s & 31.  (ix, a) come from map_x, (iy, b) from map_y.
+ * Remap (same size and channel count on both sides, every channel the same weights, constant border 0):
+ *   S(y, x) = src[y][x] inside the image, else 0;
+ *   acc = S(iy, ix) * (32 - a)(32 - b) * 32 + S(iy, ix + 1) * a(32 - b) * 32 + S(iy + 1, ix) * (32 - a) * b * 32
+ *       + S(iy + 1, ix + 1) * a * b * 32;  out = (acc + 16384) >> 15.
+ *   The weights sum to 32768, so out <= 255 without a clamp.  OpenCV's table of shorts saturates the entry a = b = 0 to 32767
+ *   and moves the missing 1 to another tap; for 8-bit pixels the rounded byte is the same.
+ * Widths and heights up to 32767 are accepted, so a saturated i is always outside the image.  R and K' are the caller's
+ * stereoRectify output (R1 / R2 and the left 3 x 3 block of P1 / P2); computing them from extrinsics is not part of this. */
+#define SS_MAX_RECTIFY_MAPS 16 /* maps one context holds: two eyes for each of SS_MAX_CAMERAS */
+typedef struct {
+    double fx, fy, cx, cy;     /* raw intrinsics */
+    double k1, k2, p1, p2, k3; /* distortion, OpenCV's order */
+    double R[9];               /* rectifying rotation, row-major */
+    double fx_new, fy_new, cx_new, cy_new;
+    int32_t width, height;
+} ss_rectify_model;
+/* Fills two [height][width] float arrays by the builder above.  Pure host code: no context, no device. */
+int ss_rectify_build_map(const ss_rectify_model *m, float *map_x, float *map_y);
+/* Converts any float map pair (the builder's or the caller's own) to the fixed-point form and uploads it as map map_id
+ * (0 <= map_id < SS_MAX_RECTIFY_MAPS), replacing what was there; another size is allowed.  map_x == map_y == NULL with width 0
+ * drops the map.  Synchronises the context's stream: a per-calibration call, not a per-frame one. */
+int ss_rectify_set_map(ss_ctx *ctx, int map_id, const float *map_x, const float *map_y, int width, int height);
+/* n_frames <= max_batch frames in device memory (strides in bytes, channels 1, 3 or 4), frame b remapped with map map_ids[b]
+ * (a HOST table [n_frames], copied before the call returns) into d_dst.  Asynchronous on the context's stream.  Writes exactly
+ * width * channels bytes of every destination row and nothing else.  SS_ERR_INVALID_ARG: an id out of range, an unset map, a map
+ * whose size differs from the frames', source and destination ranges that overlap, a destination stride smaller than a row /
+ * a frame, n_frames > max_batch, a source frame whose rows span 4 GiB or more; a NULL pointer, n_frames < 1 or source strides
+ * smaller than the frame are SS_ERR_BAD_FRAME, as in ss_extract_batch_device.  A gray result whose d_dst,
+ * dst_row_stride and dst_frame_stride are multiples of 16 is read in place, as level 0, by a following
+ * ss_extract_batch_device. */
+int ss_rectify_batch_device(ss_ctx *ctx, const void *d_src, int n_frames, int width, int height, int channels,
+                            int64_t row_stride, int64_t frame_stride, const int32_t *map_ids, void *d_dst,
+                            int64_t dst_row_stride, int64_t dst_frame_stride);
+/* ss_extract_stereo on a RAW pair: both eyes are uploaded, remapped on the device (colour included: upstream remaps before the
+ * gray conversion too) with maps map_left / map_right into a buffer of the context, then extracted and matched as
+ * ss_extract_stereo does.  The stereo parameters are the caller's: after rectification fx is fx_new and the baseline comes from
+ * P2, not from the raw calibration, so gray input needs no calibration; colour input follows ss_extract's rule for the RGB
+ * order (SS_ERR_NOT_CALIBRATED before any calibration).  Needs a context created with max_batch >= 2. */
+int ss_extract_stereo_raw(ss_ctx *ctx, int camera_id, const uint8_t *left, const uint8_t *right, int width, int height,
+                          int channels, int row_stride, double timestamp, int map_left, int map_right,
+                          const ss_stereo_params *sp, ss_frame_result *out_left, ss_frame_result *out_right,
+                          const ss_stereo_point **points, ss_stereo_summary *summary);
 
 /* ---- guided matching: descriptor search inside a pixel window (ORB-SLAM3 ORBmatcher::SearchForInitialization /
  * SearchByProjection on Frame::GetFeaturesInArea; neither source file is in the reference tree: the rule below is this

@@ -130,6 +130,13 @@ struct ss_ctx {
     dev_buf<int32_t> d_stereo_err;
     /* guided matching: the grid index and candidate counts of a call (guided_run sizes them); the host form's device copies */
     dev_buf<uint8_t> d_guided_ws, d_guided_io;
+    /* rectification: map map_id in its fixed-point form (one allocation each: the xy array, then ab; d == NULL: unset) and the
+     * 16-byte aligned buffer ss_extract_stereo_raw remaps both eyes into */
+    struct rect_map {
+        uint8_t *d = nullptr;
+        int w = 0, h = 0;
+    } rect_maps[SS_MAX_RECTIFY_MAPS];
+    dev_buf<uint8_t> d_rect;
 
     int last_n_frames = 0;
     ss_lvl0 last_lvl0; /* where level 0 of the last batch lives (ptr == NULL: in the pyramid block) */
@@ -586,6 +593,8 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_stereo_err);
     dev_free(c->d_guided_ws);
     dev_free(c->d_guided_io);
+    for (auto &rm : c->rect_maps) dev_free(rm.d);
+    dev_free(c->d_rect);
     if (c->h_train_src) (void)hipHostFree(c->h_train_src);
     if (c->train_src_copied) (void)hipEventDestroy(c->train_src_copied);
     for (cam_track &ct : c->cams) ct.free_rows();
@@ -1356,6 +1365,33 @@ int ss_stereo_batch_device(ss_ctx *c, const ss_stereo_params *p, void *d_points,
     return SS_OK;
 }
 
+/* frames 0 / 1 of the batch just extracted are one pair: its stereo points, then both eyes' features, the points and the summary
+ * to the host (c->d_stereo holds kcap points and the summary); synchronises */
+static int stereo_pair_results(ss_ctx *c, const ss_stereo_params &sp, int camera_id, double timestamp, ss_frame_result *out_left,
+                               ss_frame_result *out_right, const ss_stereo_point **points, ss_stereo_summary *summary)
+{
+    uint8_t *d_sum = c->d_stereo + (size_t)c->hg.kcap * sizeof(ss_stereo_point);
+    int rc = ss_stereo_batch_device(c, &sp, c->d_stereo, d_sum);
+    if (rc != SS_OK) return rc;
+    int32_t nk[2] = {0, 0};
+    HIP_TRY(c, hipMemcpyAsync(nk, c->ws.n_kp, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_left->level_counts, c->ws.level_counts, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out_right->level_counts, c->ws.level_counts + SS_MAX_LEVELS, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(summary, d_sum, sizeof(ss_stereo_summary), hipMemcpyDeviceToHost, c->stream));
+    rc = check_frame_errors(c); /* synchronises */
+    if (rc != SS_OK) return rc;
+    rc = fetch_rows(c, 0, nk[0], c->h_kps, c->h_desc, camera_id, timestamp, out_left);
+    if (rc != SS_OK) return rc;
+    c->h_stereo.resize((size_t)std::max(nk[0], 1));
+    if (nk[0] > 0)
+        HIP_TRY(c, hipMemcpyAsync(c->h_stereo.data(), c->d_stereo, (size_t)nk[0] * sizeof(ss_stereo_point), hipMemcpyDeviceToHost, c->stream));
+    rc = fetch_rows(c, 1, nk[1], c->h_kps_r, c->h_desc_r, camera_id, timestamp, out_right);
+    if (rc != SS_OK) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *points = c->h_stereo.data();
+    return SS_OK;
+}
+
 int ss_extract_stereo(ss_ctx *c, int camera_id, const uint8_t *left, const uint8_t *right, int width, int height, int channels,
                       int row_stride, double timestamp, ss_frame_result *out_left, ss_frame_result *out_right,
                       const ss_stereo_point **points, ss_stereo_summary *summary)
@@ -1387,26 +1423,172 @@ int ss_extract_stereo(ss_ctx *c, int camera_id, const uint8_t *left, const uint8
     HIP_TRY(c, hipMemcpyAsync(c->d_in + up.alloc, right, up.bytes, hipMemcpyHostToDevice, c->stream));
     rc = run_extract(c, c->d_in, 2, channels, row_stride, (int64_t)up.alloc, own->cam.rgb != 0);
     if (rc != SS_OK) return rc;
-    uint8_t *d_sum = c->d_stereo + (size_t)g.kcap * sizeof(ss_stereo_point);
-    rc = ss_stereo_batch_device(c, &sp, c->d_stereo, d_sum);
-    if (rc != SS_OK) return rc;
-    int32_t nk[2] = {0, 0};
-    HIP_TRY(c, hipMemcpyAsync(nk, c->ws.n_kp, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out_left->level_counts, c->ws.level_counts, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(out_right->level_counts, c->ws.level_counts + SS_MAX_LEVELS, SS_MAX_LEVELS * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(summary, d_sum, sizeof(ss_stereo_summary), hipMemcpyDeviceToHost, c->stream));
-    rc = check_frame_errors(c); /* synchronises */
-    if (rc != SS_OK) return rc;
-    rc = fetch_rows(c, 0, nk[0], c->h_kps, c->h_desc, camera_id, timestamp, out_left);
-    if (rc != SS_OK) return rc;
-    c->h_stereo.resize((size_t)std::max(nk[0], 1));
-    if (nk[0] > 0)
-        HIP_TRY(c, hipMemcpyAsync(c->h_stereo.data(), c->d_stereo, (size_t)nk[0] * sizeof(ss_stereo_point), hipMemcpyDeviceToHost, c->stream));
-    rc = fetch_rows(c, 1, nk[1], c->h_kps_r, c->h_desc_r, camera_id, timestamp, out_right);
-    if (rc != SS_OK) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *points = c->h_stereo.data();
+    return stereo_pair_results(c, sp, camera_id, timestamp, out_left, out_right, points, summary);
+}
+
+/* ---- rectification (csrc/ss_rectify.hip) ---- */
+int ss_rectify_build_map(const ss_rectify_model *m, float *map_x, float *map_y)
+{
+    if (!m || !map_x || !map_y || m->width <= 0 || m->height <= 0 || m->width > 32767 || m->height > 32767) return SS_ERR_INVALID_ARG;
+    /* A = K' * R, ir = A^-1 by the adjugate; every step one double operation (-ffp-contract=off) */
+    const double kn[3][3] = {{m->fx_new, 0.0, m->cx_new}, {0.0, m->fy_new, m->cy_new}, {0.0, 0.0, 1.0}};
+    double a[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) a[i][j] = kn[i][0] * m->R[j] + kn[i][1] * m->R[3 + j] + kn[i][2] * m->R[6 + j];
+    const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) +
+                       a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+    if (det == 0.0 || !std::isfinite(det)) return SS_ERR_INVALID_ARG;
+    const double d = 1.0 / det;
+    const double ir[9] = {(a[1][1] * a[2][2] - a[1][2] * a[2][1]) * d, (a[0][2] * a[2][1] - a[0][1] * a[2][2]) * d,
+                          (a[0][1] * a[1][2] - a[0][2] * a[1][1]) * d, (a[1][2] * a[2][0] - a[1][0] * a[2][2]) * d,
+                          (a[0][0] * a[2][2] - a[0][2] * a[2][0]) * d, (a[0][2] * a[1][0] - a[0][0] * a[1][2]) * d,
+                          (a[1][0] * a[2][1] - a[1][1] * a[2][0]) * d, (a[0][1] * a[2][0] - a[0][0] * a[2][1]) * d,
+                          (a[0][0] * a[1][1] - a[0][1] * a[1][0]) * d};
+    const double k1 = m->k1, k2 = m->k2, p1 = m->p1, p2 = m->p2, k3 = m->k3;
+    for (int i = 0; i < m->height; i++) {
+        double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
+        float *mx = map_x + (size_t)i * m->width, *my = map_y + (size_t)i * m->width;
+        for (int j = 0; j < m->width; j++, _x += ir[0], _y += ir[3], _w += ir[6]) {
+            const double w = 1.0 / _w, x = _x * w, y = _y * w;
+            const double x2 = x * x, y2 = y * y, r2 = x2 + y2, _2xy = 2.0 * x * y;
+            const double kr = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2;
+            const double xd = x * kr + p1 * _2xy + p2 * (r2 + 2.0 * x2);
+            const double yd = y * kr + p1 * (r2 + 2.0 * y2) + p2 * _2xy;
+            mx[j] = (float)(m->fx * xd + m->cx);
+            my[j] = (float)(m->fy * yd + m->cy);
+        }
+    }
     return SS_OK;
+}
+
+int ss_rectify_set_map(ss_ctx *c, int map_id, const float *map_x, const float *map_y, int width, int height)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (map_id < 0 || map_id >= SS_MAX_RECTIFY_MAPS)
+        return fail(c, SS_ERR_INVALID_ARG, "ss_rectify_set_map: map_id " + std::to_string(map_id) + " is outside 0 .. " + std::to_string(SS_MAX_RECTIFY_MAPS - 1));
+    ss_ctx::rect_map &rm = c->rect_maps[map_id];
+    if (!map_x && !map_y && width == 0) { /* drop it, once the remaps that read it have run */
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        dev_free(rm.d);
+        rm.w = rm.h = 0;
+        return SS_OK;
+    }
+    if (!map_x || !map_y || width <= 0 || height <= 0 || width > 32767 || height > 32767)
+        return fail(c, SS_ERR_INVALID_ARG, "ss_rectify_set_map: two maps of 1 .. 32767 columns and rows are needed (NULL, NULL, width 0 drops the map)");
+    const int pitch = ssk_rectify_pitch(width);
+    const size_t n = (size_t)pitch * height;
+    std::vector<uint32_t> host((n * SSK_RECTIFY_ENTRY_BYTES + 3) / 4); /* xy [n] uint32, then ab [n] uint16 */
+    ssk_rectify_fixed(map_x, map_y, width, height, pitch, host.data(), (uint16_t *)(host.data() + n));
+    uint8_t *d = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&d, n * SSK_RECTIFY_ENTRY_BYTES));
+    hipError_t e = hipMemcpy(d, host.data(), n * SSK_RECTIFY_ENTRY_BYTES, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); /* the map this one replaces may still be read */
+    if (e != hipSuccess) {
+        dev_free(d);
+        return fail(c, SS_ERR_HIP, std::string("ss_rectify_set_map: ") + hipGetErrorString(e));
+    }
+    dev_free(rm.d);
+    rm.d = d, rm.w = width, rm.h = height;
+    return SS_OK;
+}
+
+/* the checks and the launch of ss_rectify_batch_device; `who` names the entry point in the messages */
+static int rectify_run(ss_ctx *c, const std::string &who, const void *d_src, int n, int w, int h, int channels, int64_t row_stride,
+                       int64_t frame_stride, const int32_t *map_ids, void *d_dst, int64_t dst_row_stride, int64_t dst_frame_stride)
+{
+    int rc = check_image_args(c, d_src && d_dst && map_ids, n, w, h, channels, row_stride, frame_stride, false,
+                              "rectify: NULL source, destination or map table, or an empty batch", "rectify: source strides smaller than the frame");
+    if (rc != SS_OK) return rc;
+    const int64_t row_bytes = (int64_t)w * channels, max_stride = (int64_t)1 << 40;
+    if (w > 32767 || h > 32767) return fail(c, SS_ERR_INVALID_ARG, who + ": frames larger than 32767 columns or rows");
+    if (dst_row_stride < row_bytes || dst_frame_stride < dst_row_stride * h || dst_row_stride > max_stride || dst_frame_stride > max_stride)
+        return fail(c, SS_ERR_INVALID_ARG, who + ": destination strides smaller than the frame (or beyond 2^40)");
+    if (row_stride > max_stride || frame_stride > max_stride) return fail(c, SS_ERR_INVALID_ARG, who + ": source strides beyond 2^40");
+    const int64_t src_span = (h - 1) * row_stride + row_bytes, dst_span = (h - 1) * dst_row_stride + row_bytes;
+    if (src_span > (int64_t)UINT32_MAX) return fail(c, SS_ERR_INVALID_ARG, who + ": the rows of a source frame span 4 GiB or more");
+    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)((n - 1) * frame_stride + src_span);
+    const uintptr_t d0 = (uintptr_t)d_dst, d1 = d0 + (uintptr_t)((n - 1) * dst_frame_stride + dst_span);
+    if (s0 < d1 && d0 < s1) return fail(c, SS_ERR_INVALID_ARG, who + ": source and destination overlap (the remap is not in place)");
+    for (int b = 0; b < n; b++) {
+        const int id = map_ids[b];
+        if (id < 0 || id >= SS_MAX_RECTIFY_MAPS)
+            return fail(c, SS_ERR_INVALID_ARG, who + ": map_ids[" + std::to_string(b) + "] = " + std::to_string(id) + " is outside 0 .. " +
+                                                   std::to_string(SS_MAX_RECTIFY_MAPS - 1));
+        const ss_ctx::rect_map &rm = c->rect_maps[id];
+        if (!rm.d) return fail(c, SS_ERR_INVALID_ARG, who + ": map " + std::to_string(id) + " has not been set");
+        if (rm.w != w || rm.h != h)
+            return fail(c, SS_ERR_INVALID_ARG, who + ": map " + std::to_string(id) + " is " + std::to_string(rm.w) + " x " + std::to_string(rm.h) +
+                                                   ", the frames are " + std::to_string(w) + " x " + std::to_string(h));
+    }
+    /* the frame table grouped by map: a workgroup keeps its tile of ONE map in registers over all the frames that use it */
+    std::vector<int32_t> order;
+    order.reserve((size_t)n);
+    ssk_rectify_group groups[SS_MAX_RECTIFY_MAPS];
+    int n_groups = 0;
+    const size_t n_entries = (size_t)ssk_rectify_pitch(w) * h;
+    for (int id = 0; id < SS_MAX_RECTIFY_MAPS; id++) {
+        const int first = (int)order.size();
+        for (int b = 0; b < n; b++)
+            if (map_ids[b] == id) order.push_back(b);
+        if ((int)order.size() == first) continue;
+        ssk_rectify_group &g = groups[n_groups++];
+        g.xy = (const uint32_t *)c->rect_maps[id].d;
+        g.ab = (const uint16_t *)(c->rect_maps[id].d + n_entries * 4);
+        g.first = first, g.count = (int)order.size() - first;
+    }
+    rc = upload_train_src(c, order.data(), n); /* the staged host -> device table of the batch calls */
+    if (rc != SS_OK) return rc;
+    {
+        stage_timer t(c, "rectify", (int64_t)n * w * h * channels * 2 + (int64_t)n_groups * w * h * SSK_RECTIFY_ENTRY_BYTES);
+        ssk_rectify(c->stream, groups, n_groups, c->d_train_src, d_src, channels, row_stride, frame_stride, d_dst, dst_row_stride,
+                    dst_frame_stride, w, h);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_rectify_batch_device(ss_ctx *c, const void *d_src, int n_frames, int width, int height, int channels, int64_t row_stride,
+                            int64_t frame_stride, const int32_t *map_ids, void *d_dst, int64_t dst_row_stride, int64_t dst_frame_stride)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    return rectify_run(c, "ss_rectify_batch_device", d_src, n_frames, width, height, channels, row_stride, frame_stride, map_ids, d_dst,
+                       dst_row_stride, dst_frame_stride);
+}
+
+int ss_extract_stereo_raw(ss_ctx *c, int camera_id, const uint8_t *left, const uint8_t *right, int width, int height, int channels,
+                          int row_stride, double timestamp, int map_left, int map_right, const ss_stereo_params *sp,
+                          ss_frame_result *out_left, ss_frame_result *out_right, const ss_stereo_point **points, ss_stereo_summary *summary)
+{
+    if (!c || !out_left || !out_right || !points || !summary) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (camera_id == 0) return fail(c, SS_ERR_BAD_FRAME, "Frame message missing camera identifier.");
+    int rc = check_image_args(c, left && right, 1, width, height, channels, row_stride, (int64_t)row_stride * height, true,
+                              "Frame message missing binary image data.", "row_stride smaller than a row");
+    if (rc != SS_OK) return rc;
+    if (c->params.max_batch < 2) return fail(c, SS_ERR_INVALID_ARG, "ss_extract_stereo_raw: the context needs max_batch >= 2 (both eyes are one batch)");
+    rc = stereo_check_params(c, sp);
+    if (rc != SS_OK) return rc;
+    const ss_stereo_params params = *sp;
+    /* both eyes raw in d_in, remapped into d_rect with rows and frames 16 bytes aligned: a gray pair is level 0 in place */
+    const upload_size up = upload_footprint(width, height, channels, row_stride);
+    const int64_t rect_row = ((int64_t)width * channels + 15) & ~(int64_t)15, rect_frame = rect_row * height;
+    rc = grow(c, c->d_in, 2 * up.alloc);
+    if (rc == SS_OK) rc = grow(c, c->d_rect, (size_t)(2 * rect_frame));
+    if (rc != SS_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_in, left, up.bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_in + up.alloc, right, up.bytes, hipMemcpyHostToDevice, c->stream));
+    const int32_t ids[2] = {map_left, map_right};
+    rc = rectify_run(c, "ss_extract_stereo_raw", c->d_in, 2, width, height, channels, row_stride, (int64_t)up.alloc, ids, c->d_rect, rect_row,
+                     rect_frame);
+    if (rc == SS_OK) rc = ensure_geometry(c, width, height);
+    if (rc == SS_OK) rc = grow(c, c->d_stereo, (size_t)c->hg.kcap * sizeof(ss_stereo_point) + sizeof(ss_stereo_summary));
+    if (rc != SS_OK) return rc;
+    const cam_track *own = find_camera(c, camera_id);
+    rc = run_extract(c, c->d_rect, 2, channels, rect_row, rect_frame, own && own->has_cam ? (own->cam.rgb != 0) : -1);
+    if (rc != SS_OK) return rc;
+    return stereo_pair_results(c, params, camera_id, timestamp, out_left, out_right, points, summary);
 }
 
 /* ---- guided matching (csrc/ss_guided.hip) ---- */

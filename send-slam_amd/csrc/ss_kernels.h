@@ -179,6 +179,22 @@ void ssk_guided_grid(ssk_guided_call &g, int extent_w, int extent_h);
 void ssk_guided_index(hipStream_t s, const ssk_guided_call &g);
 void ssk_guided_search(hipStream_t s, const ssk_guided_call &g);
 void ssk_guided_finish(hipStream_t s, const ssk_guided_call &g);
+/* ss_rectify.hip: bilinear remap through fixed-point maps (DESIGN.md "Rectification").  A map on the device is two arrays of
+ * height rows, ssk_rectify_pitch(width) entries apart: xy = (uint16)ix | (uint16)iy << 16 and ab = a | b << 5; the entries past the
+ * width are "outside" records.  ssk_rectify_fixed is the host conversion of a float map pair into them.  ssk_rectify remaps the
+ * frames of n_groups <= SS_MAX_RECTIFY_MAPS groups, group g = the frames order[first .. first + count) (device int32) that
+ * share one map; a source frame's rows must span less than 4 GiB (32-bit tap offsets).  A source whose base, strides and row bytes
+ * are multiples of 16 takes the form that stages each tile's source box in LDS, any other the byte gathers. */
+struct ssk_rectify_group {
+    const uint32_t *xy = nullptr;
+    const uint16_t *ab = nullptr;
+    int32_t first = 0, count = 0;
+};
+#define SSK_RECTIFY_ENTRY_BYTES 6
+inline int ssk_rectify_pitch(int width) { return (width + 3) & ~3; }
+void ssk_rectify_fixed(const float *map_x, const float *map_y, int width, int height, int pitch, uint32_t *xy, uint16_t *ab);
+void ssk_rectify(hipStream_t s, const ssk_rectify_group *groups, int n_groups, const int32_t *order, const void *src, int channels,
+                 int64_t row_stride, int64_t frame_stride, void *dst, int64_t dst_row_stride, int64_t dst_frame_stride, int w, int h);
 /* test hook: run the device std::sort restatement on n <= 2048 items (size << 32 | UL.x << 20 | id) */
 int ssk_debug_sort(hipStream_t s, uint64_t *d_items, int n);
 #define SSK_MATCH_MFMA_MIN_QUERIES 128 /* from this many query rows on, ssk_match runs a matrix-core kernel */

@@ -19,6 +19,7 @@ EXPANDED_ROW_BYTES = 128  # one FP4 value (+1 / -1) per descriptor bit
 ABI_VERSION = 5
 SS_TRACK_DESC_STAYS_VALID = 1
 SS_GUIDED_MAX_ROWS = 16384
+SS_MAX_RECTIFY_MAPS = 16
 
 SS_OK = 0
 SS_ERR_INVALID_ARG, SS_ERR_NO_DEVICE, SS_ERR_HIP, SS_ERR_TOO_SMALL = -1, -2, -3, -4
@@ -36,7 +37,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_match_fold_strided_device", "ss_xchg_create", "ss_xchg_destroy", "ss_xchg_last_error", "ss_xchg_status",
            "ss_xchg_allgather", "ss_xchg_broadcast", "ss_pipe_debug_inject_failure", "ss_stereo_exchange_match",
            "ss_match_batch_sources_device", "ss_track_detach", "ss_pipe_match_sources", "ss_stereo_batch_device",
-           "ss_extract_stereo", "ss_match_guided_pairs_device", "ss_match_guided_batch_device", "ss_match_guided"]
+           "ss_extract_stereo", "ss_match_guided_pairs_device", "ss_match_guided_batch_device", "ss_match_guided",
+           "ss_rectify_build_map", "ss_rectify_set_map", "ss_rectify_batch_device", "ss_extract_stereo_raw"]
 
 
 class OrbParams(C.Structure):
@@ -136,6 +138,19 @@ def guided_params(th: int = 50, ratio_num: int = 9, ratio_den: int = 10, one_to_
                         extent_h=extent_h)
 
 
+class RectifyModel(C.Structure):
+    """ss_rectify_model: raw intrinsics, distortion in OpenCV's order, the rectifying rotation (row-major), the new intrinsics"""
+    _fields_ = [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")] + [("R", C.c_double * 9)] + \
+               [(n, C.c_double) for n in ("fx_new", "fy_new", "cx_new", "cy_new")] + [("width", C.c_int32), ("height", C.c_int32)]
+
+
+def rectify_model(fx, fy, cx, cy, k1, k2, p1, p2, k3, R, fx_new, fy_new, cx_new, cy_new, width, height) -> RectifyModel:
+    m = RectifyModel(fx=fx, fy=fy, cx=cx, cy=cy, k1=k1, k2=k2, p1=p1, p2=p2, k3=k3, fx_new=fx_new, fy_new=fy_new, cx_new=cx_new,
+                     cy_new=cy_new, width=int(width), height=int(height))
+    m.R[:] = [float(v) for v in np.asarray(R, np.float64).reshape(9)]
+    return m
+
+
 class OrbError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libsendslam_orb: {message} (status {code})")
@@ -230,6 +245,13 @@ def load():
     lib.ss_match_guided_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GuidedParams)] + [C.c_void_p] * 4
     lib.ss_match_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                     C.POINTER(GuidedParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GuidedSummary)]
+    lib.ss_rectify_build_map.argtypes = [C.POINTER(RectifyModel), C.c_void_p, C.c_void_p]
+    lib.ss_rectify_set_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    lib.ss_rectify_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                            C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.c_int64]
+    lib.ss_extract_stereo_raw.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                          C.c_int, C.c_int, C.POINTER(StereoParams), C.POINTER(FrameResult), C.POINTER(FrameResult),
+                                          C.POINTER(C.c_void_p), C.POINTER(StereoSummary)]
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -247,6 +269,17 @@ def load():
         raise ImportError(f"{LIB_PATH}: ABI {lib.ss_abi_version()} != {ABI_VERSION}")
     _lib = lib
     return lib
+
+
+def rectify_build_map(model: RectifyModel):
+    """ss_rectify_build_map: the float maps of a model -> (map_x, map_y) float32 [height][width].  Host code: needs no context and
+    no device."""
+    map_x = np.empty((model.height, model.width), np.float32)
+    map_y = np.empty((model.height, model.width), np.float32)
+    rc = load().ss_rectify_build_map(C.byref(model), map_x.ctypes.data, map_y.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_rectify_build_map: bad size or a singular K' * R")
+    return map_x, map_y
 
 
 def default_params(**kw) -> OrbParams:
@@ -480,6 +513,9 @@ class OrbContext:
         rl, rr, pts, summ = FrameResult(), FrameResult(), C.c_void_p(), StereoSummary()
         self._check(self._lib.ss_extract_stereo(self._h, int(camera_id), left.ctypes.data, right.ctypes.data, w, h, ch, w * ch,
                                                 float(timestamp), C.byref(rl), C.byref(rr), C.byref(pts), C.byref(summ)))
+        return self._pair_results(rl, rr, pts, summ)
+
+    def _pair_results(self, rl, rr, pts, summ):
         out = []
         for res in (rl, rr):
             n = res.n_keypoints
@@ -493,6 +529,54 @@ class OrbContext:
         if rl.n_keypoints:
             C.memmove(points.ctypes.data, pts.value, rl.n_keypoints * STEREO_POINT_DTYPE.itemsize)
         return out[0], out[1], out[2], out[3], points, {n: getattr(summ, n) for n, _ in StereoSummary._fields_}
+
+    # ---- rectification of raw frames (the rule: include/sendslam_orb.h) ----
+    def set_rectify_map(self, map_id: int, map_x: Optional[np.ndarray], map_y: Optional[np.ndarray]):
+        """ss_rectify_set_map: any float32 map pair [height][width] becomes map map_id; None, None drops it.  Synchronises."""
+        if map_x is None and map_y is None:
+            self._check(self._lib.ss_rectify_set_map(self._h, int(map_id), None, None, 0, 0))
+            return
+        map_x, map_y = np.ascontiguousarray(map_x, np.float32), np.ascontiguousarray(map_y, np.float32)
+        if map_x.ndim != 2 or map_x.shape != map_y.shape:
+            raise ValueError(f"the two maps must be [height][width] arrays of one shape: {map_x.shape} and {map_y.shape}")
+        h, w = map_x.shape
+        self._check(self._lib.ss_rectify_set_map(self._h, int(map_id), map_x.ctypes.data, map_y.ctypes.data, w, h))
+
+    def set_rectify_model(self, map_id: int, model: RectifyModel):
+        """builds the maps of a model on the host and sets them as map map_id"""
+        self.set_rectify_map(map_id, *rectify_build_map(model))
+
+    def rectify_batch_device(self, d_src: int, n_frames: int, width: int, height: int, map_ids, d_dst: int, channels: int = 1,
+                             row_stride: Optional[int] = None, frame_stride: Optional[int] = None,
+                             dst_row_stride: Optional[int] = None, dst_frame_stride: Optional[int] = None):
+        """ss_rectify_batch_device: frame b of d_src remapped with map map_ids[b] (host ints) into d_dst; asynchronous."""
+        row_stride = width * channels if row_stride is None else row_stride
+        frame_stride = row_stride * height if frame_stride is None else frame_stride
+        dst_row_stride = width * channels if dst_row_stride is None else dst_row_stride
+        dst_frame_stride = dst_row_stride * height if dst_frame_stride is None else dst_frame_stride
+        ids = np.ascontiguousarray(map_ids, dtype=np.int32)
+        if len(ids) != n_frames:
+            raise ValueError(f"{len(ids)} map ids for {n_frames} frames")
+        self._check(self._lib.ss_rectify_batch_device(self._h, C.c_void_p(d_src), n_frames, width, height, channels, row_stride,
+                                                      frame_stride, ids.ctypes.data_as(C.POINTER(C.c_int32)), C.c_void_p(d_dst),
+                                                      dst_row_stride, dst_frame_stride))
+
+    def extract_stereo_raw(self, left: np.ndarray, right: np.ndarray, map_left: int, map_right: int, fx: float, baseline: float,
+                           th_depth: float = 35.0, camera_id: int = 1, timestamp: float = 0.0):
+        """extract_stereo on a RAW pair: both eyes are remapped on the device with maps map_left / map_right first.  fx, baseline
+        and th_depth are those of the RECTIFIED pair (fx_new, the baseline of P2).  Returns what extract_stereo returns."""
+        left = np.ascontiguousarray(left, dtype=np.uint8)
+        right = np.ascontiguousarray(right, dtype=np.uint8)
+        if left.shape != right.shape:
+            raise ValueError(f"the two eyes differ in shape: {left.shape} and {right.shape}")
+        h, w = left.shape[:2]
+        ch = 1 if left.ndim == 2 else left.shape[2]
+        sp = StereoParams(fx=fx, baseline=baseline, th_depth=th_depth)
+        rl, rr, pts, summ = FrameResult(), FrameResult(), C.c_void_p(), StereoSummary()
+        self._check(self._lib.ss_extract_stereo_raw(self._h, int(camera_id), left.ctypes.data, right.ctypes.data, w, h, ch, w * ch,
+                                                    float(timestamp), int(map_left), int(map_right), C.byref(sp), C.byref(rl),
+                                                    C.byref(rr), C.byref(pts), C.byref(summ)))
+        return self._pair_results(rl, rr, pts, summ)
 
     # ---- guided matching: window search, conflicts, rotation histogram (the rule: include/sendslam_orb.h) ----
     def match_guided_pairs_device(self, d_q: int, d_q_kp: int, d_nq: int, d_t: int, d_t_kp: int, d_nt: int, d_windows: int,

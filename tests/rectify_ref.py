@@ -206,3 +206,57 @@ def end_to_end_pair(width=320, height=240, seed=7):
     from send_slam_amd import synth
     sc = synth.scene(seed, width, height)
     return synth.parallax_frame(seed, width, height, 4, sc=sc), synth.parallax_frame(seed, width, height, 0, sc=sc)
+
+
+TILE_W, TILE_H = 128, 8  # the destination tile one workgroup of the kernel owns
+BOX_CLASSES = ("empty", "<= 8192 B", "8193 - 10240 B", "> 10240 B")
+
+
+def rotation_map(width, height, degrees):
+    """-> (map_x, map_y) float32: the source position of destination pixel (x, y) is (x, y) rotated by `degrees` about the image
+    centre.  An input builder, not part of the rule: any map is as good as another to remap()"""
+    t = np.deg2rad(np.float64(degrees))
+    c, s = np.cos(t), np.sin(t)
+    cx, cy = width / 2, height / 2
+    x, y = np.meshgrid(np.arange(width, dtype=np.float64) - cx, np.arange(height, dtype=np.float64) - cy)
+    return (cx + c * x - s * y).astype(np.float32), (cy + s * x + c * y).astype(np.float32)
+
+
+def identity_map(width, height):
+    x, y = np.meshgrid(np.arange(width, dtype=np.float32), np.arange(height, dtype=np.float32))
+    return x, y
+
+
+def tile_boxes(map_x, map_y, channels):
+    """-> int64 [ceil(h / 8)][ceil(w / 128)]: per 128 x 8 destination tile the bytes of the bounding box of its taps that carry
+    weight (inside the image and weight > 0), as the device stages it: the byte range of the box's columns rounded outward
+    to multiples of 16, times its rows; 0 for a tile without such a tap"""
+    h, w = map_x.shape
+    ix, a = to_fixed(map_x)
+    iy, b = to_fixed(map_y)
+    wts = weights(a.astype(np.int64), b.astype(np.int64))
+    big = 1 << 40
+    xl, xh, yl, yh = np.full((h, w), big), np.full((h, w), -1), np.full((h, w), big), np.full((h, w), -1)
+    for k, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+        x, y = ix.astype(np.int64) + dx, iy.astype(np.int64) + dy
+        on = (x >= 0) & (x < w) & (y >= 0) & (y < h) & (wts[k] > 0)
+        xl, xh = np.where(on, np.minimum(xl, x), xl), np.where(on, np.maximum(xh, x), xh)
+        yl, yh = np.where(on, np.minimum(yl, y), yl), np.where(on, np.maximum(yh, y), yh)
+    ty, tx = -(-h // TILE_H), -(-w // TILE_W)
+    out = np.zeros((ty, tx), np.int64)
+    for j in range(ty):
+        for i in range(tx):
+            t = (slice(j * TILE_H, (j + 1) * TILE_H), slice(i * TILE_W, (i + 1) * TILE_W))
+            x1, y1 = int(xh[t].max()), int(yh[t].max())
+            if x1 < 0:
+                continue
+            x0, y0 = int(xl[t].min()), int(yl[t].min())
+            b0 = (x0 * channels) // 16 * 16
+            out[j, i] = -(-((x1 + 1) * channels - b0) // 16) * 16 * (y1 - y0 + 1)
+    return out
+
+
+def box_classes(boxes):
+    """tile_boxes -> how many tiles are empty, fit two 16-byte chunks per lane, need the third, do not fit the 10240-byte box"""
+    return [int((boxes == 0).sum()), int(((boxes > 0) & (boxes <= 8192)).sum()), int(((boxes > 8192) & (boxes <= 10240)).sum()),
+            int((boxes > 10240).sum())]

@@ -1,5 +1,13 @@
 """GPU parity of guided matching (ss_match_guided_batch_device, ss_match_guided_pairs_device, ss_match_guided) against
-tests/guided_ref.py: bit for bit, no tolerance -- idx, d1, d2 of every row and every summary field."""
+tests/guided_ref.py: bit for bit, no tolerance -- idx, d1, d2 of every row and every summary field.
+
+That the full-capacity case can fail was tried once on an MI355X with a one-line variant of k_guided_finish built outside lib/
+(selected by SENDSLAM_LIB; not committed):
+  only the first pass over the conflict keys  -> test_full_capacity_pairs_and_host_form alone fails (the other 18 tests of this
+  (`base < min(nt, GD_KEY_ROWS)`)                file pass: no other train set is longer than 8192 rows): frame 0 under
+                                                 th 256, ratio 10/10, one_to_one, orientation 2 has n_unique 1764 for 1552 and
+                                                 n_final 223 for 197 -- the contested rows from 8192 on keep all their queries.
+"""
 import glob
 import os
 
@@ -248,6 +256,39 @@ def test_pairs_form_on_crafted_arrays():
         for i, k in enumerate(names):
             f = frames[k]
             _check(f"{k} after the refused calls", got, i, R.finish(found[k], f["q_kp"], f["t_kp"] if len(f["t_kp"]) else None, **c))
+
+
+def _frame_args(f):
+    return f["q_desc"], f["q_kp"], f["t_desc"], f["t_kp"], f["windows"]
+
+
+def test_full_capacity_pairs_and_host_form():
+    """SS_GUIDED_MAX_ROWS rows per frame: both passes of the conflict table of k_guided_finish (contested rows at 8191, 8192 and
+    16383), 64 px cells, a frame of 16384 queries, the per-frame offsets of the index at that size; then the same arrays on
+    grids of 256 px cells, of cells beyond 2^24 px and of 2 x 2 cells.  The pairs form and the host form against the
+    reference, which knows no grid (tests/test_guided_ref.py asserts what the frames hold)."""
+    from send_slam_amd import binding
+    frames = G.capacity_frames()
+    rows = G.CAP_ROWS
+    dev = _upload(frames, rows)
+    with binding.OrbContext(0, n_features=G.NF) as ctx:
+        for c in G.CAP_COMBOS:
+            p = binding.guided_params(**c, extent_w=G.CAP_W, extent_h=G.CAP_H)
+            got = _run_pairs(ctx, dev, 2, rows, p)
+            for b, f in enumerate(frames):
+                want = G.capacity_reference(b, c)
+                print(b, G.combo_name(c), want[3])
+                _check(f"capacity frame {b} {G.combo_name(c)}", got, b, want)
+                idx, d1, d2, summ = ctx.match_guided(*_frame_args(f), p)
+                _check(f"capacity frame {b} {G.combo_name(c)}, host form", (idx[None], d1[None], d2[None], [summ]), 0, want)
+        c = G.CAP_COMBOS[1]
+        for ew, eh in G.CAP_EXTENTS:
+            p = binding.guided_params(**c, extent_w=ew, extent_h=eh)
+            got = _run_pairs(ctx, dev, 2, rows, p)
+            for b, f in enumerate(frames):
+                _check(f"capacity frame {b}, extent {ew} x {eh}", got, b, G.capacity_reference(b, c))
+            idx, d1, d2, summ = ctx.match_guided(*_frame_args(frames[0]), p)
+            _check(f"capacity frame 0, extent {ew} x {eh}, host form", (idx[None], d1[None], d2[None], [summ]), 0, G.capacity_reference(0, c))
 
 
 def test_table_form(batch_ctx):

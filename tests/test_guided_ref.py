@@ -118,6 +118,52 @@ def test_every_filter_has_work_on_the_batch():
     assert all(((s["rot_bins"] >> k) & 0xFF) != 0xFF for k in (0, 8, 16))
 
 
+def _accepted(b, combo):
+    """the rows the accepted queries of capacity frame b point at, before one_to_one and orientation"""
+    idx = G.capacity_reference(b, dict(combo, one_to_one=False, orientation=0))[0]
+    return idx[idx >= 0]
+
+
+@pytest.mark.parametrize("combo", G.CAP_COMBOS, ids=G.combo_name)
+def test_capacity_frames_need_both_conflict_passes(combo):
+    """no vacuous pass on the GPU, asserted on the reference: at SS_GUIDED_MAX_ROWS train rows the accepted queries point at
+    both halves of the train set, rows that several accepted queries want exist in both halves (the planted ones at 8191,
+    8192 and 16383 among them), both filters drop something, and matches beyond 2^24 px survive"""
+    f0, f1 = G.capacity_frames()
+    assert len(f0["t_kp"]) == len(f1["q_kp"]) == G.CAP_ROWS == binding.SS_GUIDED_MAX_ROWS == 2 * G.CAP_KEY_ROWS
+    assert len(f0["q_kp"]) == len(f1["t_kp"]) == 3006
+    rows = _accepted(0, combo)
+    wanted, times = np.unique(rows, return_counts=True)
+    contested = wanted[times >= 2]
+    lo, hi = int((rows < G.CAP_KEY_ROWS).sum()), int((rows >= G.CAP_KEY_ROWS).sum())
+    clo, chi = int((contested < G.CAP_KEY_ROWS).sum()), int((contested >= G.CAP_KEY_ROWS).sum())
+    idx, _, _, s, cands = G.capacity_reference(0, combo)
+    print(G.combo_name(combo), s, "accepted", lo, hi, "contested rows", clo, chi)
+    assert lo > 500 and hi > 500 and clo > 50 and chi > 50
+    assert set(G.CAP_PLANTED) <= set(contested.tolist())
+    assert s["n_candidates"] > 1000000 and s["n_unique"] < s["n_accepted"] == lo + hi
+    if combo["orientation"] == 2:
+        assert 0 < s["n_final"] < s["n_unique"]
+    else:
+        # of each planted pair the first query keeps the row; the far queries keep their rows beyond 2^24 px
+        assert list(idx[-6:]) == [8191, -1, 8192, -1, 16383, -1]
+        far = idx[[30, 31, 32, 1500, 1501, 1502]]
+        assert list(far) == [101, 9001, 102, 9002, 103, 9003] and (f0["t_kp"]["x"][far] > G.CAP_FAR).all()
+        assert f0["t_kp"]["y"][9003] > G.CAP_FAR and f0["windows"]["y"][1502] == G.CAP_FAR
+    # frame 1: more queries than any other frame of the suite, most of them contesting a row
+    s1 = G.capacity_reference(1, combo)[3]
+    print(s1)
+    assert s1["n_query"] == G.CAP_ROWS and s1["n_unique"] < s1["n_accepted"] // 2 and s1["n_unique"] > 1000
+    assert np.unique(_accepted(1, combo) // 1024).size == 3  # every part of the 3006 train rows is wanted
+
+
+def test_capacity_extents_form_the_grids_they_are_there_for():
+    assert G.grid_shift(G.W, G.H) == G.grid_shift(1280, 720) == G.grid_shift(5000, 37) == 5  # all the suite had
+    assert G.grid_shift(G.CAP_W, G.CAP_H) == 6
+    assert [G.grid_shift(*e) for e in G.CAP_EXTENTS] == [8, 12, 5]
+    assert G.CAP_EXTENTS[1][0] > G.CAP_FAR and ((G.CAP_EXTENTS[2][0] - 1) >> 5) + 1 == 2
+
+
 def test_degenerate_windows():
     qk, qd = G.features("synth_t1")
     tk, td = G.features("synth_t0")

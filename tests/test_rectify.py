@@ -1,6 +1,15 @@
 """GPU parity of the rectification stage (ss_rectify_set_map, ss_rectify_batch_device, ss_extract_stereo_raw) against
 tests/rectify_ref.py: every remapped byte equal, no tolerance; the chain into extraction and stereo depth against
-tests/stereo_ref.py on the reference-rectified pair, bit for bit."""
+tests/stereo_ref.py on the reference-rectified pair, bit for bit.
+
+That the rotated maps can fail was tried once on an MI355X with a one-line variant of k_rectify built outside lib/ (selected by
+SENDSLAM_LIB; not committed):
+  the third chunk register is never stored     -> the three cases of test_rotated_maps_mix_every_form_of_the_staging alone fail,
+  (no `box[16 * (tid + 512)] = st2`)              in their staged runs, in the tiles whose box is above 8192 B: 1919 bytes of
+                                                 frame 0 differ on 640 x 484 gray (first at row 67, column 255), 80 with 3
+                                                 channels, 1255 with 4; the other 12 tests of this file pass, as no box of
+                                                 theirs is above 6144 B.
+"""
 import functools
 from collections import Counter
 
@@ -36,8 +45,9 @@ def _set_model(ctx, binding, map_id, name):
     ctx.set_rectify_model(map_id, binding.rectify_model(**_maps(name)[0]))
 
 
-def _remap(ctx, frames, ids, row_stride=None, dst_row_stride=None, dst_offset=0):
-    """frames [n, h, w] or [n, h, w, c] -> (result [n, h, w(, c)], the whole destination buffer as the device left it)"""
+def _remap(ctx, frames, ids, row_stride=None, dst_row_stride=None, dst_offset=0, staged=None):
+    """frames [n, h, w] or [n, h, w, c] -> (result [n, h, w(, c)], the whole destination buffer as the device left it);
+    staged: when given, whether the source must meet the alignment rule of the kernel's LDS form"""
     import torch
     dev = torch.device("cuda:0")
     n, h, w = frames.shape[:3]
@@ -47,6 +57,8 @@ def _remap(ctx, frames, ids, row_stride=None, dst_row_stride=None, dst_offset=0)
     src = np.full((n, h, rs), 0x5C, np.uint8)
     src[:, :, :w * ch] = frames.reshape(n, h, w * ch)
     d_src = torch.from_numpy(src).to(dev)
+    if staged is not None:
+        assert ((d_src.data_ptr() | rs | (rs * h) | (w * ch)) % 16 == 0) == staged
     d_dst = torch.full((dst_offset + n * h * drs,), FILL, dtype=torch.uint8, device=dev)
     ctx.rectify_batch_device(d_src.data_ptr(), n, w, h, ids, d_dst.data_ptr() + dst_offset, channels=ch, row_stride=rs, frame_stride=rs * h,
                              dst_row_stride=drs, dst_frame_stride=drs * h)
@@ -167,6 +179,35 @@ def test_a_map_without_any_smoothness():
     assert (cls == 0).mean() > 0.05 and (cls == 4).mean() > 0.5
     _same("scrambled", got[0], R.remap(frames[0], mx, my))
     _same("its neighbour", got[1], R.remap(frames[1], *_maps("E")[1]))
+
+
+@pytest.mark.parametrize("w,h,degrees,ch", [(640, 484, 45, 1), (336, 61, 8, 3), (336, 61, 8, 4)])
+def test_rotated_maps_mix_every_form_of_the_staging(w, h, degrees, ch):
+    """A rotation about the centre (45 degrees on 640 x 484 gray, 8 degrees on 336 x 61 with 3 and 4 channels): in ONE staged
+    launch tiles without a tap, tiles of two chunks per lane, tiles that fill the third chunk register (8193 - 10240 B) and
+    tiles that fall back to the gather loop (tests/test_rectify_ref.py counts them), a height that is no multiple of 8 and,
+    with colour, a width that is no multiple of 128, so lanes without a pixel take part in the staging.  Three frames: the
+    frame loop and the prefetch of the next box run; the gray batch has an identity frame in the middle.  Then the same
+    frames onto a destination of stride w * ch + 3 at base offset 1, and with source rows 4 bytes longer, which takes the
+    gather form: the same bytes."""
+    from send_slam_amd import binding
+    mx, my = R.rotation_map(w, h, degrees)
+    maps = {0: (mx, my), 1: R.identity_map(w, h)}
+    ids = [0, 1, 0] if ch == 1 else [0, 0, 0]
+    frames = _random((3, h, w) if ch == 1 else (3, h, w, ch), 80 + ch) | 1  # no zero byte: a tap wrongly taken as border shows
+    want = [R.remap(frames[f], *maps[i]) for f, i in enumerate(ids)]
+    with _ctx(binding) as ctx:
+        for i, m in maps.items():
+            ctx.set_rectify_map(i, *m)
+        runs = {"staged": _remap(ctx, frames, ids, staged=True)[0],
+                "staged, unaligned destination": _remap(ctx, frames, ids, dst_row_stride=w * ch + 3, dst_offset=1, staged=True)[0],
+                "gathered": _remap(ctx, frames, ids, row_stride=w * ch + 4, staged=False)[0],
+                "gathered, unaligned destination": _remap(ctx, frames, ids, row_stride=w * ch + 4, dst_row_stride=w * ch + 3, dst_offset=1,
+                                                          staged=False)[0]}
+    for tag, got in runs.items():
+        for f in range(3):
+            _same(f"{w} x {h} x {ch} frame {f}, {tag}", got[f], want[f])
+    assert not np.array_equal(want[0], frames[0]) and (ch > 1 or np.array_equal(want[1], frames[1]))
 
 
 def test_state_and_argument_checks():

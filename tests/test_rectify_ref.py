@@ -153,6 +153,43 @@ def test_closed_and_literal_forms_agree_on_crafted_edges():
     assert np.array_equal(R.remap(src, mx, my), lit) and min(branches) > 0
 
 
+def test_tile_boxes_on_crafted_maps():
+    """the box rule on maps whose boxes are known by hand"""
+    w, h = 256, 16
+    ident = R.identity_map(w, h)
+    # identity, gray: a tile reads its own 128 columns and 8 rows; a = b = 0, so the taps right and below weigh nothing
+    assert R.tile_boxes(*ident, 1).tolist() == [[128 * 8, 128 * 8], [128 * 8, 128 * 8]]
+    assert R.tile_boxes(*ident, 3).tolist() == [[384 * 8, 384 * 8]] * 2
+    # half a pixel to the right: the second tap column counts, except past the right edge; the range grows to the next 16
+    mx, my = _shift_maps(w, h, 0.5, 0)
+    assert R.tile_boxes(mx, my, 1).tolist() == [[144 * 8, 128 * 8], [144 * 8, 128 * 8]]
+    # 3 columns to the right and a quarter down, 4 channels: bytes 12 .. 524 -> 0 .. 528 and 524 .. 1024 -> 512 .. 1024, 9 rows
+    # (8 in the last tile row, whose lower taps are outside)
+    mx, my = _shift_maps(w, h, 3, 0.25)
+    assert R.tile_boxes(mx, my, 4).tolist() == [[528 * 9, 512 * 9], [528 * 8, 512 * 8]]
+    # everything outside: empty
+    assert R.tile_boxes(*_shift_maps(w, h, w, 0), 1).tolist() == [[0, 0], [0, 0]]
+    assert R.box_classes(np.array([[0, 1, 8192], [8193, 10240, 10241]])) == [1, 2, 2, 1]
+
+
+ROTATED = [(640, 484, 45, 1), (336, 61, 8, 3), (336, 61, 8, 4)]
+
+
+@pytest.mark.parametrize("w,h,degrees,ch", ROTATED)
+def test_rotated_maps_reach_every_form_of_the_staging(w, h, degrees, ch):
+    """no vacuous pass on the GPU: the rotated maps of tests/test_rectify.py have tiles without a weighted tap, tiles whose box
+    fits two 16-byte chunks per lane, tiles that need the third (8193 - 10240 B) and tiles that fall back to the gather
+    loop, in one launch; every map of the suite before them stayed at or below 6144 B"""
+    got = R.box_classes(R.tile_boxes(*R.rotation_map(w, h, degrees), ch))
+    print(w, h, degrees, ch, dict(zip(R.BOX_CLASSES, got)))
+    assert min(got) >= 1, got
+    assert (w * ch) % 16 == 0 and h % R.TILE_H != 0 and (ch == 1 or w % R.TILE_W != 0)
+    assert got == {1: [22, 71, 19, 193], 3: [1, 12, 2, 9], 4: [1, 10, 2, 11]}[ch]
+    for name, m, c in (("A_hd", R.scaled(R.model_a(), 1280, 720, focal=4.0), 1), ("E", R.model_e(), 1), ("E", R.model_e(), 3)):
+        if ch == 1:
+            assert 0 < R.tile_boxes(*R.build_map(m), c).max() <= 6144, name
+
+
 def test_end_to_end_input_stays_meaningful(oracle):
     """the raw pair the GPU chain test rectifies: after the remap the reference still finds depth on it"""
     left, right = R.end_to_end_pair()

@@ -5,6 +5,7 @@ import glob
 import os
 import re
 import subprocess
+from collections import Counter
 
 import numpy as np
 import pytest
@@ -57,6 +58,54 @@ def test_disparities_of_a_parallax_pair(oracle, w, h, nf, t, seed):
     d = kL["x"][ok] - pts["u_right"][ok]
     assert np.array_equal(pts["depth"][ok], (bf / d).astype(np.float32))
     assert summ["n_close"] == int((pts["depth"][ok] < np.float32(np.float32(bf * np.float32(35.0)) / np.float32(500.0))).sum())
+
+
+def _stereo_params(oracle, nf, scale=1.2, levels=8):
+    return oracle.default_params(n_features=nf, lapping_x0=0, lapping_x1=0, scale_factor=scale, n_levels=levels)
+
+
+def test_tiny_pairs_have_one_two_and_three_refined_points(oracle):
+    """no vacuous pass on the GPU: the pairs of test_stereo.test_tiny_counts_through_the_median_select put 1, 2 and 3 SADs
+    through the median; with two, the median is the LARGER one (element [n / 2]) and the cut, 2.1 times it, drops neither --
+    the smaller one as the median would drop the larger"""
+    import test_stereo as T
+    want = {"patch22": (1, 389), "patch26": (2, 4656), "flat": (0, -1), "patch28": (3, 379)}
+    pairs = T.tiny_pairs()
+    assert [n for n, _ in pairs] == list(want)
+    for name, (l, r) in pairs:
+        st = Counter()
+        kL, dL, kR, dR, pts, summ = R.stereo_pair(l, r, _stereo_params(oracle, 500), 500.0, T.BASELINE, T.TH_DEPTH, st)
+        print(name, summ, dict(st))
+        assert st["guard"] == 0 and (summ["n_refined"], summ["sad_median"]) == want[name]
+        assert summ["n_depth"] == summ["n_refined"] and st["median_cut"] == 0
+        if name == "flat":
+            assert summ["n_left"] == summ["n_right"] == 0
+        if name == "patch26":
+            lo, hi = sorted(int(s) for s in pts["sad"][pts["depth"] > 0])
+            assert hi == summ["sad_median"] and hi >= np.float32(np.float32(1.5) * np.float32(1.4)) * np.float32(lo) > lo
+
+
+def test_odd_width_pairs_and_pyramid_shapes_have_depth(oracle):
+    """the pairs of test_stereo.test_level_0_* and test_pyramid_shapes: no guard, a median cut that bites, enough depth; the
+    narrow disparity range of fx = 20 rejects matches; every level of each pyramid holds keypoints"""
+    import test_stereo as T
+    for (w, h, t, seed), (n_depth, n_refined) in zip(T.ODD_PAIRS, ((201, 279), (290, 368))):
+        assert w % 16 != 0 and 336 % 16 == 0 and 336 >= w
+        left, right = T._parallax_pair(w, h, t, seed)
+        summ = {}
+        for fx in (500.0, 20.0):
+            st = Counter()
+            summ[fx] = R.stereo_pair(left, right, _stereo_params(oracle, 500), fx, T.BASELINE, T.TH_DEPTH, st)[5]
+            assert st["guard"] == 0 and st["median_cut"] >= 1
+        assert (summ[500.0]["n_depth"], summ[500.0]["n_refined"]) == (n_depth, n_refined)
+        assert 0 < summ[20.0]["n_matched"] < summ[500.0]["n_matched"]
+    for w, h, nf, t, seed, scale, levels in T.PYRAMIDS:
+        left, right = T._parallax_pair(w, h, t, seed)
+        st = Counter()
+        kL, dL, kR, dR, pts, summ = R.stereo_pair(left, right, _stereo_params(oracle, nf, scale, levels), 500.0, T.BASELINE, T.TH_DEPTH, st)
+        print(w, h, scale, levels, summ, dict(st))
+        assert st["guard"] == 0 and st["median_cut"] >= 1 and summ["n_depth"] > 300
+        assert set(kL["octave"].tolist()) == set(range(levels)) and len(R.level_scales(_stereo_params(oracle, nf, scale, levels), w, h)) == levels
 
 
 def test_parabola_offset_is_bounded():

@@ -37,6 +37,9 @@
  *   ss_extract_stereo_raw      frame of both eyes before the extractor (no counterpart in the monocular shim)
  *   ss_match_guided*           ORBmatcher::SearchForInitialization / SearchByProjection on Frame::GetFeaturesInArea (window
  *                              search, conflicts, rotation histogram; the monocular shim reaches them inside TrackMonocular :594)
+ *   ss_vocab_* / ss_bow_* /    the ORBvoc.txt argument of the System constructor :511 (DBoW2 TemplatedVocabulary::loadFromTextFile),
+ *   ss_match_bow_*             Frame::ComputeBoW, ORBmatcher::SearchByBoW (TrackReferenceKeyFrame, relocalisation) and
+ *                              L1Scoring::score (KeyFrameDatabase) inside TrackMonocular :594
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
  *   ss_last_error              the cerr diagnostics of the shim (:457-469, :523-551)
  *
@@ -516,6 +519,100 @@ int ss_match_guided_batch_device(ss_ctx *ctx, const int32_t *train_src, const vo
 int ss_match_guided(ss_ctx *ctx, const uint8_t *query, const ss_keypoint *query_kp, int n_query, const uint8_t *train,
                     const ss_keypoint *train_kp, int n_train, const ss_guided_window *windows, const ss_guided_params *p,
                     int32_t *idx, uint16_t *d1, uint16_t *d2, ss_guided_summary *summary);
+
+/* ---- bag of words: DBoW2's vocabulary tree on the device (TemplatedVocabulary::transform as Frame::ComputeBoW calls it,
+ * ORBmatcher::SearchByBoW, L1Scoring::score as KeyFrameDatabase ranks keyframes with it; none of these sources is in the reference
+ * tree and no ORBvoc.txt is at hand: the rule below is this library's own restatement from DBoW2 / ORBmatcher.cc as published,
+ * parity with the real binary unpinned like the rest of the path; tests/bow_ref.py is the normative statement, reproduced bit
+ * for bit) ----------------------------------------------------------------------------------------------
+ * Vocabulary: a tree whose root is node 0; node ids are the text file's (line n, from 0, is node n + 1), word ids count the
+ *   leaves in file order, a node's children are in file order.  Node and word ids reported by any call are these, whatever the
+ *   device layout (breadth first, so that the children of a node are consecutive 32-byte rows).
+ * Transform of one descriptor row (transform(feature, id, w, &nid, levelsup)): start at the root, depth 0; until the node is a
+ *   leaf go to the child with the lowest Hamming distance (ties: the earliest child, upstream's strict < in a forward scan),
+ *   depth += 1, and when depth == L - levelsup remember that node as the row's NODE.  The leaf is the row's WORD, its weight w.
+ *   L - levelsup <= 0: the node is 0.  Deviation: a leaf shallower than L - levelsup is the row's node itself (upstream leaves
+ *   *nid unwritten there).  A row for which w > 0 is false takes part in nothing: its word is reported, its node is -1.
+ * BoW vector of a frame (BowVector::addWeight, normalize(L1)): the distinct words of the rows with w > 0, ascending; the value of
+ *   a word seen c times is w, then += w (c - 1) times; norm = the sum of fabs(value) in ascending word order, ONE serial chain of
+ *   double additions; if norm > 0.0 every value is divided by it.  Every step is one IEEE double operation.
+ * Bounds.  SS_VOCAB_MAX_K: the descent folds the key distance << 8 | child ordinal, so an ordinal has 8 bits (DBoW2 builds k = 10,
+ *   OpenCV-style trees up to 32).  SS_VOCAB_MAX_DEPTH: bounds the descent loop, nothing is stored per level (ORBvoc.txt has L = 6).
+ *   SS_VOCAB_MAX_NODES: 2^24 nodes are 768 MiB on the device (32-byte row + 16-byte record each); ORBvoc.txt has about 1.08 M.
+ *   SS_BOW_MAX_ROWS: a frame's rows are sorted as 64-bit keys in one workgroup's LDS (128 KiB of the CU's 160), and the match
+ *   shares ss_match_guided's row bound. */
+#define SS_VOCAB_MAX_K 256
+#define SS_VOCAB_MAX_DEPTH 32
+#define SS_VOCAB_MAX_NODES (1 << 24)
+#define SS_BOW_MAX_ROWS SS_GUIDED_MAX_ROWS
+typedef struct ss_vocab ss_vocab; /* host object, no device needed */
+typedef struct {          /* 20 bytes */
+    int32_t k, L;         /* the header's branching factor and depth */
+    int32_t n_nodes;      /* nodes without the root = lines of the file; ids 1 .. n_nodes */
+    int32_t n_words;      /* leaves */
+    int32_t max_depth;    /* of the deepest leaf (the root has depth 0); may differ from L */
+} ss_vocab_shape;
+/* DBoW2's text format: a header line `k L scoring weighting`, then one line per node `parent_id is_leaf b0 .. b31 weight`
+ * (weight through strtod).  Only scoring 0 (L1) and weighting 0 (TF-IDF) are accepted, what ORBvoc.txt declares.  A file that is
+ * malformed (truncated line, a byte > 255, a parent id that is not an earlier node, more than k children, an inner node without
+ * children, a leaf with children, no node at all, a token that is no number) or exceeds a bound above is SS_ERR_INVALID_ARG with
+ * a message in err (err_bytes including the NUL; err may be NULL); a file that cannot be read is SS_ERR_INVALID_ARG too. */
+int ss_vocab_load_text(const char *path, ss_vocab **out, char *err, int err_bytes);
+/* The same from arrays of n_nodes entries, entry n = node n + 1: parent ids, leaf flags, 32-byte descriptors, weights. */
+int ss_vocab_from_arrays(int n_nodes, const int32_t *parent, const uint8_t *is_leaf, const uint8_t *desc, const double *weight,
+                         int k, int L, ss_vocab **out, char *err, int err_bytes);
+int ss_vocab_info(const ss_vocab *voc, ss_vocab_shape *out);
+/* The flattened tree, for tests: arrays of n_nodes + 1 entries indexed by node id (0 = the root): the id of the first child (-1
+ * for a leaf), the child count, the word id (-1 for an inner node), the weight (0.0 for an inner node), the depth.  Any pointer
+ * may be NULL. */
+int ss_vocab_copy_out(const ss_vocab *voc, int32_t *first_child, int32_t *n_children, int32_t *word, double *weight, int32_t *depth);
+int ss_vocab_destroy(ss_vocab *voc);
+/* Uploads the vocabulary; the context keeps its own device copy (voc may be destroyed afterwards), a second call replaces it.
+ * Synchronises the context's stream.  The transform and match calls below return SS_ERR_STATE before the first one. */
+int ss_bow_set_vocabulary(ss_ctx *ctx, const ss_vocab *voc);
+typedef struct {          /* 32 bytes, one per frame */
+    int32_t status;       /* SS_OK, or the frame_error that voided the frame (all rows -1, empty vector) */
+    int32_t n_rows;       /* rows transformed */
+    int32_t n_used;       /* rows with w > 0 */
+    int32_t n_words;      /* distinct words among them = entries of the BoW vector */
+    int32_t n_nodes;      /* distinct nodes among them */
+    int32_t reserved;     /* 0 */
+    double norm;          /* the L1 norm the values were divided by (0.0: nothing was divided) */
+} ss_bow_summary;
+/* Caller arrays laid out as for ss_match_pairs_device: d_desc [n_frames][rows_per_frame][32], d_n_rows device int32 [n_frames]
+ * (clamped to 0 .. rows_per_frame).  Outputs [n_frames][rows_per_frame]: d_word / d_node (int32, -1 past the count), d_bow_word
+ * (int32, ascending, -1 past n_words), d_bow_value (double, 0.0 past n_words); d_summary [n_frames] ss_bow_summary.
+ * rows_per_frame > SS_BOW_MAX_ROWS or levelsup < 0 is SS_ERR_INVALID_ARG.  Asynchronous on the context's stream, which is a
+ * non-blocking one: the outputs are written by one kernel and read again by the next, so they stay allocated and untouched until
+ * the call has run (ss_synchronize, or an event on ss_get_stream). */
+int ss_bow_transform_device(ss_ctx *ctx, const void *d_desc, const void *d_n_rows, int n_frames, int rows_per_frame, int levelsup,
+                            void *d_word, void *d_node, void *d_bow_word, void *d_bow_value, void *d_summary);
+/* The frames of the last ss_extract_batch_device batch (rows_per_frame = kp_capacity).  A frame whose frame_error is set gets
+ * that status, all rows -1 and an empty vector.  The context keeps the nodes and their index for ss_match_bow_batch_device. */
+int ss_bow_transform_batch_device(ss_ctx *ctx, int levelsup, void *d_word, void *d_node, void *d_bow_word, void *d_bow_value,
+                                  void *d_summary);
+/* SearchByBoW.  The candidates of query row i are the train rows j < n_train with node_j == node_i, node_i >= 0; from there on
+ * ss_match_guided's rule word for word (d1 / lowest idx / d2, acceptance, one_to_one, orientation, raw d1 / d2), through the same
+ * finishing kernel.  Of p only th, ratio_num, ratio_den, one_to_one and orientation are read; upstream's call is th 50, ratio
+ * 7 / 10, orientation on.  Upstream skips keyframe rows without a map point: write -1 into their node.  It also skips frame rows
+ * already matched, which is the one_to_one deviation of ss_match_guided.  Arrays as for ss_match_guided_pairs_device, with
+ * d_query_node / d_train_node (device int32 [n_frames][rows_per_frame]) in place of the windows; needs no vocabulary. */
+int ss_match_bow_pairs_device(ss_ctx *ctx, const void *d_query, const void *d_query_kp, const void *d_query_node, const void *d_n_query,
+                              const void *d_train, const void *d_train_kp, const void *d_train_node, const void *d_n_train,
+                              int n_frames, int rows_per_frame, const ss_guided_params *p, void *d_idx, void *d_d1, void *d_d2,
+                              void *d_summary);
+/* The frames and nodes of the last ss_bow_transform_batch_device (SS_ERR_STATE without one on the current batch); train_src and
+ * its self-exclusion rule are those of ss_match_guided_batch_device. */
+int ss_match_bow_batch_device(ss_ctx *ctx, const int32_t *train_src, const ss_guided_params *p, void *d_idx, void *d_d1, void *d_d2,
+                              void *d_summary);
+/* L1Scoring::score of one query vector (d_q_word ascending int32 / d_q_value double, q_rows entries allocated, *d_q_count used)
+ * against n_db vectors stored [n_db][stride] with a device int32 count each (counts are clamped to the allocation): both
+ * ascending lists are walked; for each common word, in ascending order, s += fabs(v - w) - fabs(v) - fabs(w) (v the query's
+ * value; three double operations left to right, then the add), s starting at 0.0; score = -s / 2.0 (so -0.0 without a common
+ * word); an empty side gives 0.0.  d_score: double [n_db].  Vectors are kept outputs of the transform; needs no vocabulary.
+ * Asynchronous on the context's stream. */
+int ss_bow_score_device(ss_ctx *ctx, const void *d_q_word, const void *d_q_value, const void *d_q_count, int q_rows,
+                        const void *d_db_word, const void *d_db_value, const void *d_db_count, int n_db, int stride, void *d_score);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

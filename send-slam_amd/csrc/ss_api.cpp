@@ -16,6 +16,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -130,6 +132,12 @@ struct ss_ctx {
     dev_buf<int32_t> d_stereo_err;
     /* guided matching: the grid index and candidate counts of a call (guided_run sizes them); the host form's device copies */
     dev_buf<uint8_t> d_guided_ws, d_guided_io;
+    /* bag of words: the vocabulary on the device (one allocation: rows, records, weights), the node index of a pairs call, and
+     * what ss_bow_transform_batch_device keeps of bow_frames frames of the last batch for ss_match_bow_batch_device (nodes, node
+     * index, index counts) */
+    dev_buf<uint8_t> d_voc, d_bow_ws, d_bow_keep;
+    ssk_bow_voc voc;
+    int bow_frames = 0;
     /* rectification: map map_id in its fixed-point form (one allocation each: the xy array, then ab; d == NULL: unset) and the
      * 16-byte aligned buffer ss_extract_stereo_raw remaps both eyes into */
     struct rect_map {
@@ -335,6 +343,7 @@ int ensure_geometry(ss_ctx *c, int w, int h)
     if (rc != SS_OK) return rc;
     c->have_geom = true;
     c->last_n_frames = 0;
+    c->bow_frames = 0;
     return SS_OK;
 }
 
@@ -404,6 +413,7 @@ int run_extract(ss_ctx *c, const void *d_pix, int n, int channels, int64_t row_s
     }
     HIP_TRY(c, hipGetLastError());
     c->last_n_frames = n;
+    c->bow_frames = 0; /* the nodes a BoW transform kept belong to the batch before */
     return SS_OK;
 }
 
@@ -593,6 +603,9 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_stereo_err);
     dev_free(c->d_guided_ws);
     dev_free(c->d_guided_io);
+    dev_free(c->d_voc);
+    dev_free(c->d_bow_ws);
+    dev_free(c->d_bow_keep);
     for (auto &rm : c->rect_maps) dev_free(rm.d);
     dev_free(c->d_rect);
     if (c->h_train_src) (void)hipHostFree(c->h_train_src);
@@ -1744,6 +1757,483 @@ int ss_match_guided(ss_ctx *c, const uint8_t *query, const ss_keypoint *query_kp
     }
     HIP_TRY(c, hipMemcpyAsync(summary, d + o_sum, sizeof(ss_guided_summary), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SS_OK;
+}
+
+/* ---- bag of words (csrc/ss_bow.hip) ---- */
+/* The vocabulary tree on the host, indexed by the file's node ids (0 = the root).  parent < own id for every node, so the children
+ * of a node in file order are its children in ascending id: children[child_pos[p] .. child_pos[p] + n_child[p]). */
+struct ss_vocab {
+    int k = 0, L = 0, n_nodes = 0, n_words = 0, max_depth = 0;
+    std::vector<int32_t> parent, n_child, child_pos, children, word, depth;
+    std::vector<double> weight;
+    std::vector<uint8_t> leaf, desc;
+};
+
+static int voc_fail(char *err, int err_bytes, const std::string &msg)
+{
+    if (err && err_bytes > 0) snprintf(err, (size_t)err_bytes, "%s", msg.c_str());
+    return SS_ERR_INVALID_ARG;
+}
+
+/* checks and links a tree whose parent / leaf / desc / weight arrays are filled for the ids 1 .. n */
+static int voc_link(ss_vocab &v, char *err, int err_bytes)
+{
+    const int n = v.n_nodes;
+    if (v.k < 1 || v.k > SS_VOCAB_MAX_K) return voc_fail(err, err_bytes, "vocabulary: k " + std::to_string(v.k) + " is outside 1 .. SS_VOCAB_MAX_K");
+    if (v.L < 1 || v.L > SS_VOCAB_MAX_DEPTH) return voc_fail(err, err_bytes, "vocabulary: L " + std::to_string(v.L) + " is outside 1 .. SS_VOCAB_MAX_DEPTH");
+    if (n < 1) return voc_fail(err, err_bytes, "vocabulary: no nodes");
+    if (n >= SS_VOCAB_MAX_NODES) return voc_fail(err, err_bytes, "vocabulary: more than SS_VOCAB_MAX_NODES nodes");
+    v.n_child.assign((size_t)n + 1, 0);
+    v.depth.assign((size_t)n + 1, 0);
+    v.word.assign((size_t)n + 1, -1);
+    v.leaf[0] = 0;
+    v.parent[0] = -1;
+    v.weight[0] = 0.0;
+    for (int id = 1; id <= n; id++) {
+        const int p = v.parent[id];
+        if (p < 0 || p >= id) return voc_fail(err, err_bytes, "vocabulary: node " + std::to_string(id) + " names parent " + std::to_string(p) + ", which is no earlier node");
+        if (v.leaf[p]) return voc_fail(err, err_bytes, "vocabulary: leaf " + std::to_string(p) + " has a child (node " + std::to_string(id) + ")");
+        if (++v.n_child[p] > v.k) return voc_fail(err, err_bytes, "vocabulary: node " + std::to_string(p) + " has more than k = " + std::to_string(v.k) + " children");
+        v.depth[id] = v.depth[p] + 1;
+        if (v.depth[id] > SS_VOCAB_MAX_DEPTH) return voc_fail(err, err_bytes, "vocabulary: node " + std::to_string(id) + " is deeper than SS_VOCAB_MAX_DEPTH");
+    }
+    v.n_words = v.max_depth = 0;
+    for (int id = 1; id <= n; id++) {
+        if (v.leaf[id]) {
+            v.word[id] = v.n_words++;
+            v.max_depth = std::max(v.max_depth, (int)v.depth[id]);
+        } else {
+            if (v.n_child[id] == 0) return voc_fail(err, err_bytes, "vocabulary: inner node " + std::to_string(id) + " has no children");
+            v.weight[id] = 0.0;
+        }
+    }
+    v.child_pos.assign((size_t)n + 2, 0);
+    for (int id = 0; id <= n; id++) v.child_pos[id + 1] = v.child_pos[id] + v.n_child[id];
+    v.children.assign((size_t)n, 0);
+    std::vector<int32_t> fill(v.child_pos.begin(), v.child_pos.end() - 1);
+    for (int id = 1; id <= n; id++) v.children[fill[v.parent[id]]++] = id;
+    return SS_OK;
+}
+
+static void voc_reserve(ss_vocab &v, size_t n)
+{
+    v.parent.assign(n + 1, 0);
+    v.leaf.assign(n + 1, 0);
+    v.weight.assign(n + 1, 0.0);
+    v.desc.assign((n + 1) * 32, 0);
+}
+
+int ss_vocab_from_arrays(int n_nodes, const int32_t *parent, const uint8_t *is_leaf, const uint8_t *desc, const double *weight, int k, int L,
+                         ss_vocab **out, char *err, int err_bytes)
+{
+    if (!out) return voc_fail(err, err_bytes, "vocabulary: out is NULL");
+    *out = nullptr;
+    if (n_nodes < 1) return voc_fail(err, err_bytes, "vocabulary: no nodes");
+    if (n_nodes >= SS_VOCAB_MAX_NODES) return voc_fail(err, err_bytes, "vocabulary: more than SS_VOCAB_MAX_NODES nodes");
+    if (!parent || !is_leaf || !desc || !weight) return voc_fail(err, err_bytes, "vocabulary: NULL array");
+    ss_vocab *v = new (std::nothrow) ss_vocab;
+    if (!v) return SS_ERR_NO_MEMORY;
+    v->k = k, v->L = L, v->n_nodes = n_nodes;
+    voc_reserve(*v, (size_t)n_nodes);
+    for (int i = 0; i < n_nodes; i++) {
+        v->parent[i + 1] = parent[i];
+        v->leaf[i + 1] = is_leaf[i] != 0;
+        v->weight[i + 1] = weight[i];
+    }
+    memcpy(v->desc.data() + 32, desc, (size_t)n_nodes * 32);
+    const int rc = voc_link(*v, err, err_bytes);
+    if (rc != SS_OK) {
+        delete v;
+        return rc;
+    }
+    *out = v;
+    return SS_OK;
+}
+
+/* the next blank-separated token of [p, end), or false */
+static bool voc_token(const char *&p, const char *end, const char *&tok, size_t &len)
+{
+    while (p < end && (*p == ' ' || *p == '\t' || *p == '\r')) p++;
+    if (p >= end) return false;
+    tok = p;
+    while (p < end && *p != ' ' && *p != '\t' && *p != '\r') p++;
+    len = (size_t)(p - tok);
+    return true;
+}
+
+/* a decimal integer of at most 9 digits with an optional minus sign, nothing else */
+static bool voc_int(const char *tok, size_t len, long &out)
+{
+    size_t i = 0;
+    const bool neg = len > 0 && tok[0] == '-';
+    if (neg) i = 1;
+    if (i >= len || len - i > 9) return false;
+    long v = 0;
+    for (; i < len; i++) {
+        if (tok[i] < '0' || tok[i] > '9') return false;
+        v = v * 10 + (tok[i] - '0');
+    }
+    out = neg ? -v : v;
+    return true;
+}
+
+/* a decimal floating-point literal (digits, sign, point, exponent), correctly rounded by strtod */
+static bool voc_double(const char *tok, size_t len, double &out)
+{
+    char buf[64];
+    if (len == 0 || len >= sizeof(buf)) return false;
+    bool digit = false;
+    for (size_t i = 0; i < len; i++) {
+        const char ch = tok[i];
+        if (ch >= '0' && ch <= '9') digit = true;
+        else if (ch != '+' && ch != '-' && ch != '.' && ch != 'e' && ch != 'E') return false;
+        buf[i] = ch;
+    }
+    buf[len] = 0;
+    if (!digit) return false;
+    char *stop = nullptr;
+    out = strtod(buf, &stop);
+    return stop == buf + len;
+}
+
+int ss_vocab_load_text(const char *path, ss_vocab **out, char *err, int err_bytes)
+{
+    if (!out) return voc_fail(err, err_bytes, "vocabulary: out is NULL");
+    *out = nullptr;
+    if (!path) return voc_fail(err, err_bytes, "vocabulary: path is NULL");
+    std::string text;
+    {
+        std::ifstream in(path, std::ios::binary);
+        if (!in) return voc_fail(err, err_bytes, std::string("vocabulary: cannot open ") + path);
+        std::ostringstream ss;
+        ss << in.rdbuf();
+        text = ss.str();
+    }
+    ss_vocab *v = new (std::nothrow) ss_vocab;
+    if (!v) return SS_ERR_NO_MEMORY;
+    auto bad = [&](long line, const std::string &what) {
+        delete v;
+        return voc_fail(err, err_bytes, "vocabulary: line " + std::to_string(line) + ": " + what);
+    };
+    const char *p = text.data(), *const end = p + text.size();
+    long line = 0, nodes = 0;
+    bool header = false;
+    while (p < end) {
+        const char *le = (const char *)memchr(p, '\n', (size_t)(end - p));
+        if (!le) le = end;
+        const char *q = p, *tok = nullptr;
+        size_t len = 0;
+        p = le < end ? le + 1 : end;
+        line++;
+        if (!voc_token(q, le, tok, len)) continue; /* a blank line */
+        long val[36];
+        const int want = header ? 34 : 4; /* integers of the line; a node line ends with the weight */
+        int got = 0;
+        bool more = false; /* a token behind the integers: tok */
+        do {
+            if (got == want) {
+                more = true;
+                break;
+            }
+            if (!voc_int(tok, len, val[got])) return bad(line, "token " + std::to_string(got + 1) + " is no integer");
+            got++;
+        } while (voc_token(q, le, tok, len));
+        if (got < want || (header && !more)) return bad(line, "truncated: " + std::to_string(got) + " of " + std::to_string(want + (header ? 1 : 0)) + " tokens");
+        if (!header) {
+            if (more) return bad(line, "more than 4 tokens in the header");
+            if (val[2] != 0 || val[3] != 0) return bad(line, "only scoring 0 (L1) with weighting 0 (TF-IDF) is supported");
+            v->k = (int)std::min(std::max(val[0], -1L), (long)SS_VOCAB_MAX_K + 1);
+            v->L = (int)std::min(std::max(val[1], -1L), (long)SS_VOCAB_MAX_DEPTH + 1);
+            header = true;
+            /* at most one node per 70 bytes of text: sizes the arrays once */
+            voc_reserve(*v, std::min(text.size() / 70 + 16, (size_t)SS_VOCAB_MAX_NODES));
+            continue;
+        }
+        /* tok is the 35th token: the weight */
+        double w = 0;
+        if (!voc_double(tok, len, w)) return bad(line, "the weight is no number");
+        if (voc_token(q, le, tok, len)) return bad(line, "more than 35 tokens");
+        if (val[1] != 0 && val[1] != 1) return bad(line, "is_leaf must be 0 or 1");
+        const size_t id = (size_t)++nodes;
+        if (id >= (size_t)SS_VOCAB_MAX_NODES) return bad(line, "more than SS_VOCAB_MAX_NODES nodes");
+        if (id >= v->parent.size()) {
+            const size_t cap = v->parent.size() * 2;
+            v->parent.resize(cap), v->leaf.resize(cap), v->weight.resize(cap), v->desc.resize(cap * 32);
+        }
+        for (int b = 0; b < 32; b++) {
+            if (val[2 + b] < 0 || val[2 + b] > 255) return bad(line, "descriptor byte " + std::to_string(b) + " is outside 0 .. 255");
+            v->desc[id * 32 + b] = (uint8_t)val[2 + b];
+        }
+        v->parent[id] = (int32_t)std::min(std::max(val[0], -1L), (long)SS_VOCAB_MAX_NODES);
+        v->leaf[id] = (uint8_t)val[1];
+        v->weight[id] = w;
+    }
+    if (!header) return bad(line, "no header line");
+    v->n_nodes = (int)nodes;
+    const int rc = voc_link(*v, err, err_bytes);
+    if (rc != SS_OK) {
+        delete v;
+        return rc;
+    }
+    *out = v;
+    return SS_OK;
+}
+
+int ss_vocab_info(const ss_vocab *v, ss_vocab_shape *out)
+{
+    if (!v || !out) return SS_ERR_INVALID_ARG;
+    out->k = v->k, out->L = v->L, out->n_nodes = v->n_nodes, out->n_words = v->n_words, out->max_depth = v->max_depth;
+    return SS_OK;
+}
+
+int ss_vocab_copy_out(const ss_vocab *v, int32_t *first_child, int32_t *n_children, int32_t *word, double *weight, int32_t *depth)
+{
+    if (!v) return SS_ERR_INVALID_ARG;
+    for (int id = 0; id <= v->n_nodes; id++) {
+        if (first_child) first_child[id] = v->n_child[id] ? v->children[v->child_pos[id]] : -1;
+        if (n_children) n_children[id] = v->n_child[id];
+        if (word) word[id] = v->word[id];
+        if (weight) weight[id] = v->weight[id];
+        if (depth) depth[id] = v->depth[id];
+    }
+    return SS_OK;
+}
+
+int ss_vocab_destroy(ss_vocab *v)
+{
+    if (!v) return SS_ERR_INVALID_ARG;
+    delete v;
+    return SS_OK;
+}
+
+static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+int ss_bow_set_vocabulary(ss_ctx *c, const ss_vocab *v)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!v) return fail(c, SS_ERR_INVALID_ARG, "ss_bow_set_vocabulary: voc is NULL");
+    /* breadth first: the children of the node at position u take the next n_child positions, in file order */
+    const size_t n = (size_t)v->n_nodes + 1;
+    std::vector<int32_t> at(n); /* position -> file id */
+    std::vector<ssk_bow_node> recs(n);
+    std::vector<uint8_t> rows(n * 32);
+    std::vector<double> wgt((size_t)v->n_words);
+    size_t next = 1;
+    at[0] = 0;
+    for (size_t u = 0; u < n; u++) {
+        const int id = at[u];
+        ssk_bow_node &r = recs[u];
+        r.child_base = v->n_child[id] ? (int32_t)next : 0;
+        r.n_child = v->n_child[id];
+        r.word = v->word[id];
+        r.file_id = id;
+        memcpy(&rows[u * 32], &v->desc[(size_t)id * 32], 32);
+        if (r.word >= 0) wgt[(size_t)r.word] = v->weight[id];
+        for (int ch = 0; ch < v->n_child[id]; ch++) at[next++] = v->children[v->child_pos[id] + ch];
+    }
+    const size_t o_recs = up256(n * 32), o_wgt = o_recs + up256(n * sizeof(ssk_bow_node)), total = o_wgt + up256(wgt.size() * sizeof(double) + 8);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->voc = ssk_bow_voc();
+    c->bow_frames = 0;
+    dev_free(c->d_voc);
+    const int rc = grow(c, c->d_voc, total);
+    if (rc != SS_OK) return rc;
+    HIP_TRY(c, hipMemcpy(c->d_voc.p, rows.data(), rows.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_voc.p + o_recs, recs.data(), recs.size() * sizeof(ssk_bow_node), hipMemcpyHostToDevice));
+    if (!wgt.empty()) HIP_TRY(c, hipMemcpy(c->d_voc.p + o_wgt, wgt.data(), wgt.size() * sizeof(double), hipMemcpyHostToDevice));
+    c->voc.rows = c->d_voc.p;
+    c->voc.recs = (const ssk_bow_node *)(c->d_voc.p + o_recs);
+    c->voc.weight = (const double *)(c->d_voc.p + o_wgt);
+    c->voc.L = v->L;
+    c->voc.max_depth = v->max_depth;
+    c->voc.n_words = v->n_words;
+    return SS_OK;
+}
+
+/* the two launches of a transform whose arrays are filled in */
+static int bow_transform_run(ss_ctx *c, ssk_bow_call &b)
+{
+    const int64_t nr = (int64_t)b.n_frames * b.rows;
+    {
+        /* per row: its descriptor and the two ids it writes; the children it visits depend on the tree */
+        stage_timer t(c, "bow_descend", nr * (SS_DESC_BYTES + 8));
+        ssk_bow_descend(c->stream, c->voc, b);
+    }
+    {
+        /* word and node read (the node twice), the vector and the index written */
+        stage_timer t(c, "bow_vector", nr * (12 + 12 + (b.index ? 8 : 0)) + b.n_frames * (int64_t)sizeof(ss_bow_summary));
+        ssk_bow_vector(c->stream, c->voc, b);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_bow_transform_device(ss_ctx *c, const void *d_desc, const void *d_n_rows, int n_frames, int rows_per_frame, int levelsup, void *d_word,
+                            void *d_node, void *d_bow_word, void *d_bow_value, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->voc.rows) return fail(c, SS_ERR_STATE, "ss_bow_transform_device: no vocabulary (ss_bow_set_vocabulary)");
+    if (n_frames < 0 || rows_per_frame < 1 || levelsup < 0) return fail(c, SS_ERR_INVALID_ARG, "bow transform: bad frame count, row count or levelsup");
+    if (rows_per_frame > SS_BOW_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "bow transform: rows_per_frame " + std::to_string(rows_per_frame) + " exceeds SS_BOW_MAX_ROWS (" +
+                                               std::to_string(SS_BOW_MAX_ROWS) + ")");
+    if (n_frames == 0) return SS_OK;
+    if (!d_desc || !d_n_rows || !d_word || !d_node || !d_bow_word || !d_bow_value || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "bow transform: NULL buffer");
+    ssk_bow_call b;
+    b.n_frames = n_frames, b.rows = rows_per_frame, b.levelsup = levelsup;
+    b.desc = (const uint8_t *)d_desc, b.n_rows = (const int32_t *)d_n_rows;
+    b.word = (int32_t *)d_word, b.node = (int32_t *)d_node;
+    b.bow_word = (int32_t *)d_bow_word, b.bow_value = (double *)d_bow_value, b.summary = (ss_bow_summary *)d_summary;
+    return bow_transform_run(c, b);
+}
+
+/* what a batch transform keeps: [index][nodes][index counts] of n frames of kcap rows */
+struct bow_keep {
+    uint64_t *index;
+    int32_t *node, *n_index;
+    size_t total;
+};
+static bow_keep bow_keep_of(uint8_t *p, int n, int kcap)
+{
+    const size_t o_node = up256((size_t)n * kcap * sizeof(uint64_t)), o_cnt = o_node + up256((size_t)n * kcap * sizeof(int32_t));
+    return {(uint64_t *)p, (int32_t *)(p + o_node), (int32_t *)(p + o_cnt), o_cnt + up256((size_t)n * sizeof(int32_t))};
+}
+
+int ss_bow_transform_batch_device(ss_ctx *c, int levelsup, void *d_word, void *d_node, void *d_bow_word, void *d_bow_value, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->voc.rows) return fail(c, SS_ERR_STATE, "ss_bow_transform_batch_device: no vocabulary (ss_bow_set_vocabulary)");
+    if (!c->have_geom || c->last_n_frames <= 0) return fail(c, SS_ERR_STATE, "ss_bow_transform_batch_device: no batch has been extracted");
+    if (levelsup < 0) return fail(c, SS_ERR_INVALID_ARG, "bow transform: levelsup must be >= 0");
+    if (!d_word || !d_node || !d_bow_word || !d_bow_value || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "bow transform: NULL output buffer");
+    const int n = c->last_n_frames, kcap = c->hg.kcap;
+    if (kcap > SS_BOW_MAX_ROWS) return fail(c, SS_ERR_INVALID_ARG, "bow transform: kp_capacity " + std::to_string(kcap) + " exceeds SS_BOW_MAX_ROWS");
+    c->bow_frames = 0;
+    const int rc = grow(c, c->d_bow_keep, bow_keep_of(nullptr, n, kcap).total);
+    if (rc != SS_OK) return rc;
+    const bow_keep keep = bow_keep_of(c->d_bow_keep.p, n, kcap);
+    ssk_bow_call b;
+    b.n_frames = n, b.rows = kcap, b.levelsup = levelsup;
+    b.desc = c->ws.desc, b.n_rows = c->ws.n_kp, b.frame_error = c->ws.frame_error;
+    b.word = (int32_t *)d_word, b.node = (int32_t *)d_node, b.node2 = keep.node;
+    b.bow_word = (int32_t *)d_bow_word, b.bow_value = (double *)d_bow_value, b.summary = (ss_bow_summary *)d_summary;
+    b.index = keep.index, b.n_index = keep.n_index;
+    const int rc2 = bow_transform_run(c, b);
+    if (rc2 == SS_OK) c->bow_frames = n;
+    return rc2;
+}
+
+/* The launches of a BoW match whose operands, query nodes and outputs are filled in: the index of the train nodes where the call
+ * brings its own (t_node != NULL), the search, then guided matching's finish as it is. */
+static int bow_match_run(ss_ctx *c, ssk_guided_call &g, const ss_guided_params *p, const int32_t *q_node, const int32_t *t_node, const uint64_t *index,
+                         const int32_t *n_index)
+{
+    g.th = p->th, g.rnum = p->ratio_num, g.rden = p->ratio_den;
+    g.one_to_one = p->one_to_one != 0, g.orientation = p->orientation;
+    const size_t nr = (size_t)g.n_frames * g.rows;
+    const size_t o_index = up256(nr * sizeof(int32_t)), o_cnt = o_index + (t_node ? up256(nr * sizeof(uint64_t)) : 0);
+    const int rc = grow(c, c->d_bow_ws, o_cnt + (t_node ? up256((size_t)g.n_frames * sizeof(int32_t)) : 0));
+    if (rc != SS_OK) return rc;
+    g.n_cand = (int32_t *)c->d_bow_ws.p;
+    if (t_node) {
+        uint64_t *own = (uint64_t *)(c->d_bow_ws.p + o_index);
+        int32_t *own_n = (int32_t *)(c->d_bow_ws.p + o_cnt);
+        stage_timer t(c, "bow_index", (int64_t)nr * 12);
+        ssk_bow_index(c->stream, t_node, g.nt, nullptr, g.n_frames, g.rows, own, own_n);
+        index = own, n_index = own_n;
+    }
+    {
+        /* per query: its node, its descriptor, the 12 bytes it writes; the keys and descriptors of its run depend on the content */
+        stage_timer t(c, "bow_search", (int64_t)nr * (4 + SS_DESC_BYTES + 12));
+        ssk_bow_search(c->stream, g, q_node, index, n_index);
+    }
+    {
+        stage_timer t(c, "bow_finish", (int64_t)nr * (8 + 2 + 4 + (g.orientation ? 8 : 0)) + g.n_frames * (int64_t)sizeof(ss_guided_summary));
+        ssk_guided_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_match_bow_pairs_device(ss_ctx *c, const void *d_query, const void *d_query_kp, const void *d_query_node, const void *d_n_query,
+                              const void *d_train, const void *d_train_kp, const void *d_train_node, const void *d_n_train, int n_frames,
+                              int rows_per_frame, const ss_guided_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = guided_check_params(c, p);
+    if (rc != SS_OK) return rc;
+    if (n_frames < 0 || rows_per_frame < 1) return fail(c, SS_ERR_INVALID_ARG, "bow match: bad frame or row count");
+    if (rows_per_frame > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "bow match: rows_per_frame " + std::to_string(rows_per_frame) + " exceeds SS_GUIDED_MAX_ROWS (" +
+                                               std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    if (n_frames == 0) return SS_OK;
+    if (!d_query || !d_query_kp || !d_query_node || !d_n_query || !d_train || !d_train_kp || !d_train_node || !d_n_train || !d_idx || !d_d1 || !d_d2 ||
+        !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "bow match: NULL buffer");
+    ssk_guided_call g;
+    g.n_frames = n_frames;
+    g.rows = rows_per_frame;
+    g.q_kp = (const ss_keypoint *)d_query_kp, g.t_kp = (const ss_keypoint *)d_train_kp;
+    g.q_desc = (const uint8_t *)d_query, g.t_desc = (const uint8_t *)d_train;
+    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
+    g.summary = (ss_guided_summary *)d_summary;
+    return bow_match_run(c, g, p, (const int32_t *)d_query_node, (const int32_t *)d_train_node, nullptr, nullptr);
+}
+
+int ss_match_bow_batch_device(ss_ctx *c, const int32_t *train_src, const ss_guided_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->have_geom || c->last_n_frames <= 0) return fail(c, SS_ERR_STATE, "ss_match_bow_batch_device: no batch has been extracted");
+    if (c->bow_frames != c->last_n_frames)
+        return fail(c, SS_ERR_STATE, "ss_match_bow_batch_device: the last batch has not been through ss_bow_transform_batch_device");
+    int rc = guided_check_params(c, p);
+    if (rc != SS_OK) return rc;
+    if (!d_idx || !d_d1 || !d_d2 || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "bow match: NULL output buffer");
+    const int n = c->last_n_frames, kcap = c->hg.kcap;
+    if (kcap > SS_GUIDED_MAX_ROWS) return fail(c, SS_ERR_INVALID_ARG, "bow match: kp_capacity " + std::to_string(kcap) + " exceeds SS_GUIDED_MAX_ROWS");
+    for (int b = 0; train_src && b < n; b++)
+        if (train_src[b] < -1 || train_src[b] >= n)
+            return fail(c, SS_ERR_INVALID_ARG, "train_src[" + std::to_string(b) + "] = " + std::to_string(train_src[b]) + " names no frame of the batch (" +
+                                                   std::to_string(n) + "); the bow match takes no carry frames");
+    rc = upload_train_src(c, train_src, n);
+    if (rc != SS_OK) return rc;
+    const bow_keep keep = bow_keep_of(c->d_bow_keep.p, n, kcap);
+    ssk_guided_call g;
+    g.n_frames = n;
+    g.rows = kcap;
+    g.q_kp = g.t_kp = c->ws.kps;
+    g.q_desc = g.t_desc = c->ws.desc;
+    g.nq = g.nt = c->ws.n_kp;
+    g.src = c->d_train_src;
+    g.frame_error = c->ws.frame_error;
+    g.exclude_same_frame = 1;
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
+    g.summary = (ss_guided_summary *)d_summary;
+    return bow_match_run(c, g, p, keep.node, nullptr, keep.index, keep.n_index);
+}
+
+int ss_bow_score_device(ss_ctx *c, const void *d_q_word, const void *d_q_value, const void *d_q_count, int q_rows, const void *d_db_word,
+                        const void *d_db_value, const void *d_db_count, int n_db, int stride, void *d_score)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_db < 0 || stride < 1 || q_rows < 1) return fail(c, SS_ERR_INVALID_ARG, "bow score: bad vector count, stride or query size");
+    if (n_db == 0) return SS_OK;
+    if (!d_q_word || !d_q_value || !d_q_count || !d_db_word || !d_db_value || !d_db_count || !d_score) return fail(c, SS_ERR_INVALID_ARG, "bow score: NULL buffer");
+    {
+        /* the allocation of every vector is an upper bound of what is read */
+        stage_timer t(c, "bow_score", (int64_t)n_db * ((int64_t)stride * 12 + 12) + (int64_t)q_rows * 12);
+        ssk_bow_score(c->stream, (const int32_t *)d_q_word, (const double *)d_q_value, (const int32_t *)d_q_count, q_rows, (const int32_t *)d_db_word,
+                      (const double *)d_db_value, (const int32_t *)d_db_count, n_db, stride, (double *)d_score);
+    }
+    HIP_TRY(c, hipGetLastError());
     return SS_OK;
 }
 

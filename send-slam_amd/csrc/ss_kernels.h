@@ -179,6 +179,45 @@ void ssk_guided_grid(ssk_guided_call &g, int extent_w, int extent_h);
 void ssk_guided_index(hipStream_t s, const ssk_guided_call &g);
 void ssk_guided_search(hipStream_t s, const ssk_guided_call &g);
 void ssk_guided_finish(hipStream_t s, const ssk_guided_call &g);
+/* ss_bow.hip: vocabulary descent, BoW vectors, the node index and search of SearchByBoW, the L1 score (DESIGN.md "Bag of
+ * words").  The vocabulary on the device, nodes numbered breadth first (0 = the root) so that a node's children are consecutive:
+ * rows [n][32] descriptors, recs [n] ssk_bow_node, weight [n_words] doubles by word id. */
+struct ssk_bow_node { /* 16 bytes: one dwordx4 */
+    int32_t child_base, n_child; /* n_child 0 = a leaf */
+    int32_t word;                /* -1 for an inner node */
+    int32_t file_id;             /* the id the text file gives the node */
+};
+struct ssk_bow_voc {
+    const uint8_t *rows = nullptr;
+    const ssk_bow_node *recs = nullptr;
+    const double *weight = nullptr;
+    int L = 0, max_depth = 0, n_words = 0;
+};
+/* One transform call: [n_frames][rows] descriptors with per-frame counts (frame_error: per frame, or NULL).  descend writes
+ * word / node of every row (node2: a second copy, or NULL), vector sorts a frame's words and nodes in LDS and writes the BoW
+ * vector, the summary and, where index != NULL, the frame's node index: the keys node << 32 | row of its rows with node >= 0 in
+ * ascending order, n_index[frame] of them. */
+struct ssk_bow_call {
+    int n_frames = 0, rows = 0, levelsup = 0;
+    const uint8_t *desc = nullptr;
+    const int32_t *n_rows = nullptr, *frame_error = nullptr;
+    int32_t *word = nullptr, *node = nullptr, *node2 = nullptr;
+    int32_t *bow_word = nullptr;
+    double *bow_value = nullptr;
+    ss_bow_summary *summary = nullptr;
+    uint64_t *index = nullptr;
+    int32_t *n_index = nullptr;
+};
+void ssk_bow_descend(hipStream_t s, const ssk_bow_voc &v, const ssk_bow_call &c);
+void ssk_bow_vector(hipStream_t s, const ssk_bow_voc &v, const ssk_bow_call &c);
+/* the node index alone, of caller-made nodes [n_frames][rows] with counts n_rows */
+void ssk_bow_index(hipStream_t s, const int32_t *node, const int32_t *n_rows, const int32_t *frame_error, int n_frames, int rows,
+                   uint64_t *index, int32_t *n_index);
+/* fills idx / d1 / d2 / n_cand of a guided call whose candidates are the train rows of the query's node (q_node [n_frames][rows];
+ * index / n_index of the train frames); ssk_guided_finish then runs on g as it is */
+void ssk_bow_search(hipStream_t s, const ssk_guided_call &g, const int32_t *q_node, const uint64_t *index, const int32_t *n_index);
+void ssk_bow_score(hipStream_t s, const int32_t *q_word, const double *q_value, const int32_t *q_count, int q_rows, const int32_t *db_word,
+                   const double *db_value, const int32_t *db_count, int n_db, int stride, double *score);
 /* ss_rectify.hip: bilinear remap through fixed-point maps (DESIGN.md "Rectification").  A map on the device is two arrays of
  * height rows, ssk_rectify_pitch(width) entries apart: xy = (uint16)ix | (uint16)iy << 16 and ab = a | b << 5; the entries past the
  * width are "outside" records.  ssk_rectify_fixed is the host conversion of a float map pair into them.  ssk_rectify remaps the

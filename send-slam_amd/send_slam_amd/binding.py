@@ -20,6 +20,7 @@ ABI_VERSION = 5
 SS_TRACK_DESC_STAYS_VALID = 1
 SS_GUIDED_MAX_ROWS = 16384
 SS_MAX_RECTIFY_MAPS = 16
+SS_VOCAB_MAX_K, SS_VOCAB_MAX_DEPTH, SS_VOCAB_MAX_NODES, SS_BOW_MAX_ROWS = 256, 32, 1 << 24, SS_GUIDED_MAX_ROWS
 
 SS_OK = 0
 SS_ERR_INVALID_ARG, SS_ERR_NO_DEVICE, SS_ERR_HIP, SS_ERR_TOO_SMALL = -1, -2, -3, -4
@@ -38,7 +39,10 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_xchg_allgather", "ss_xchg_broadcast", "ss_pipe_debug_inject_failure", "ss_stereo_exchange_match",
            "ss_match_batch_sources_device", "ss_track_detach", "ss_pipe_match_sources", "ss_stereo_batch_device",
            "ss_extract_stereo", "ss_match_guided_pairs_device", "ss_match_guided_batch_device", "ss_match_guided",
-           "ss_rectify_build_map", "ss_rectify_set_map", "ss_rectify_batch_device", "ss_extract_stereo_raw"]
+           "ss_rectify_build_map", "ss_rectify_set_map", "ss_rectify_batch_device", "ss_extract_stereo_raw",
+           "ss_vocab_load_text", "ss_vocab_from_arrays", "ss_vocab_info", "ss_vocab_copy_out", "ss_vocab_destroy",
+           "ss_bow_set_vocabulary", "ss_bow_transform_device", "ss_bow_transform_batch_device", "ss_match_bow_pairs_device",
+           "ss_match_bow_batch_device", "ss_bow_score_device"]
 
 
 class OrbParams(C.Structure):
@@ -136,6 +140,18 @@ def guided_params(th: int = 50, ratio_num: int = 9, ratio_den: int = 10, one_to_
     return GuidedParams(th=th, ratio_num=ratio_num, ratio_den=ratio_den, one_to_one=int(one_to_one), orientation=orientation,
                         radius=radius, radius_by_octave=int(radius_by_octave), octave_span=octave_span, extent_w=extent_w,
                         extent_h=extent_h)
+
+
+class VocabShape(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("n_nodes", C.c_int32), ("n_words", C.c_int32), ("max_depth", C.c_int32)]
+
+
+class BowSummary(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_rows", C.c_int32), ("n_used", C.c_int32), ("n_words", C.c_int32),
+                ("n_nodes", C.c_int32), ("reserved", C.c_int32), ("norm", C.c_double)]
+
+
+BOW_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n, _ in BowSummary._fields_[:6]] + [("norm", "<f8")])
 
 
 class RectifyModel(C.Structure):
@@ -252,6 +268,19 @@ def load():
     lib.ss_extract_stereo_raw.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                           C.c_int, C.c_int, C.POINTER(StereoParams), C.POINTER(FrameResult), C.POINTER(FrameResult),
                                           C.POINTER(C.c_void_p), C.POINTER(StereoSummary)]
+    lib.ss_vocab_load_text.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.c_char_p, C.c_int]
+    lib.ss_vocab_from_arrays.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                         C.c_char_p, C.c_int]
+    lib.ss_vocab_info.argtypes = [C.c_void_p, C.POINTER(VocabShape)]
+    lib.ss_vocab_copy_out.argtypes = [C.c_void_p] * 6
+    lib.ss_vocab_destroy.argtypes = [C.c_void_p]
+    lib.ss_bow_set_vocabulary.argtypes = [C.c_void_p, C.c_void_p]
+    lib.ss_bow_transform_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
+    lib.ss_bow_transform_batch_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    lib.ss_match_bow_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_int, C.c_int, C.POINTER(GuidedParams)] + [C.c_void_p] * 4
+    lib.ss_match_bow_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(GuidedParams)] + [C.c_void_p] * 4
+    lib.ss_bow_score_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_int, C.c_void_p]
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -280,6 +309,71 @@ def rectify_build_map(model: RectifyModel):
     if rc != SS_OK:
         raise OrbError(rc, "ss_rectify_build_map: bad size or a singular K' * R")
     return map_x, map_y
+
+
+class Vocabulary:
+    """ss_vocab: a DBoW2 vocabulary tree on the host (no device needed).  Node ids are the text file's (0 = the root), word ids
+    count the leaves in file order."""
+
+    def __init__(self, handle):
+        self._lib = load()
+        self._h = handle
+
+    @staticmethod
+    def _made(rc: int, h, err) -> "Vocabulary":
+        if rc != SS_OK:
+            raise OrbError(rc, err.value.decode(errors="replace"))
+        return Vocabulary(h)
+
+    @classmethod
+    def load_text(cls, path: str) -> "Vocabulary":
+        h, err = C.c_void_p(), C.create_string_buffer(256)
+        return cls._made(load().ss_vocab_load_text(os.fsencode(path), C.byref(h), err, len(err)), h, err)
+
+    @classmethod
+    def from_arrays(cls, parent, is_leaf, desc, weight, k: int, L: int) -> "Vocabulary":
+        parent = np.ascontiguousarray(parent, np.int32)
+        is_leaf = np.ascontiguousarray(is_leaf, np.uint8)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        weight = np.ascontiguousarray(weight, np.float64)
+        assert len(parent) == len(is_leaf) == len(desc) == len(weight)
+        h, err = C.c_void_p(), C.create_string_buffer(256)
+        return cls._made(load().ss_vocab_from_arrays(len(parent), parent.ctypes.data, is_leaf.ctypes.data, desc.ctypes.data, weight.ctypes.data,
+                                                     int(k), int(L), C.byref(h), err, len(err)), h, err)
+
+    def info(self) -> dict:
+        s = VocabShape()
+        rc = self._lib.ss_vocab_info(self._h, C.byref(s))
+        if rc != SS_OK:
+            raise OrbError(rc, "ss_vocab_info")
+        return {n: int(getattr(s, n)) for n, _ in VocabShape._fields_}
+
+    def copy_out(self) -> dict:
+        """per node id (0 = the root): first_child (-1: a leaf), n_children, word (-1: an inner node), weight, depth"""
+        n = self.info()["n_nodes"] + 1
+        out = {"first_child": np.empty(n, np.int32), "n_children": np.empty(n, np.int32), "word": np.empty(n, np.int32),
+               "weight": np.empty(n, np.float64), "depth": np.empty(n, np.int32)}
+        rc = self._lib.ss_vocab_copy_out(self._h, *(out[k].ctypes.data for k in ("first_child", "n_children", "word", "weight", "depth")))
+        if rc != SS_OK:
+            raise OrbError(rc, "ss_vocab_copy_out")
+        return out
+
+    def close(self):
+        if self._h:
+            self._lib.ss_vocab_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def default_params(**kw) -> OrbParams:
@@ -613,6 +707,43 @@ class OrbContext:
                                               windows.ctypes.data if nq else None, C.byref(params), idx.ctypes.data, d1.ctypes.data,
                                               d2.ctypes.data, C.byref(summ)))
         return idx, d1, d2, {n: getattr(summ, n) for n, _ in GuidedSummary._fields_}
+
+    # ---- bag of words: vocabulary transform, SearchByBoW, L1 score (the rule: include/sendslam_orb.h) ----
+    def set_vocabulary(self, voc: Vocabulary):
+        """uploads the vocabulary; the context keeps its own copy"""
+        self._check(self._lib.ss_bow_set_vocabulary(self._h, voc._h))
+
+    def bow_transform_device(self, d_desc: int, d_n_rows: int, n_frames: int, rows_per_frame: int, levelsup: int, d_word: int, d_node: int,
+                             d_bow_word: int, d_bow_value: int, d_summary: int):
+        """asynchronous; outputs [n_frames][rows_per_frame] int32 / int32 / int32 / float64 and [n_frames] BOW_SUMMARY_DTYPE"""
+        self._check(self._lib.ss_bow_transform_device(self._h, C.c_void_p(d_desc), C.c_void_p(d_n_rows), n_frames, rows_per_frame, int(levelsup),
+                                                      C.c_void_p(d_word), C.c_void_p(d_node), C.c_void_p(d_bow_word), C.c_void_p(d_bow_value),
+                                                      C.c_void_p(d_summary)))
+
+    def bow_transform_batch_device(self, levelsup: int, d_word: int, d_node: int, d_bow_word: int, d_bow_value: int, d_summary: int):
+        """the frames of the last batch; outputs [n_frames][kp_capacity]"""
+        self._check(self._lib.ss_bow_transform_batch_device(self._h, int(levelsup), C.c_void_p(d_word), C.c_void_p(d_node), C.c_void_p(d_bow_word),
+                                                            C.c_void_p(d_bow_value), C.c_void_p(d_summary)))
+
+    def match_bow_pairs_device(self, d_q: int, d_q_kp: int, d_q_node: int, d_nq: int, d_t: int, d_t_kp: int, d_t_node: int, d_nt: int,
+                               n_frames: int, rows_per_frame: int, params: GuidedParams, d_idx: int, d_d1: int, d_d2: int, d_summary: int):
+        self._check(self._lib.ss_match_bow_pairs_device(self._h, C.c_void_p(d_q), C.c_void_p(d_q_kp), C.c_void_p(d_q_node), C.c_void_p(d_nq),
+                                                        C.c_void_p(d_t), C.c_void_p(d_t_kp), C.c_void_p(d_t_node), C.c_void_p(d_nt), n_frames,
+                                                        rows_per_frame, C.byref(params), C.c_void_p(d_idx), C.c_void_p(d_d1), C.c_void_p(d_d2),
+                                                        C.c_void_p(d_summary)))
+
+    def match_bow_batch_device(self, params: GuidedParams, d_idx: int, d_d1: int, d_d2: int, d_summary: int, train_src=None):
+        """the frames and nodes of the last bow_transform_batch_device; train_src as in match_guided_batch_device"""
+        src = None if train_src is None else np.ascontiguousarray(train_src, np.int32)
+        self._check(self._lib.ss_match_bow_batch_device(self._h, None if src is None else src.ctypes.data, C.byref(params), C.c_void_p(d_idx),
+                                                        C.c_void_p(d_d1), C.c_void_p(d_d2), C.c_void_p(d_summary)))
+
+    def bow_score_device(self, d_q_word: int, d_q_value: int, d_q_count: int, q_rows: int, d_db_word: int, d_db_value: int, d_db_count: int,
+                         n_db: int, stride: int, d_score: int):
+        """one query vector against n_db kept vectors [n_db][stride] -> float64 [n_db]; asynchronous"""
+        self._check(self._lib.ss_bow_score_device(self._h, C.c_void_p(d_q_word), C.c_void_p(d_q_value), C.c_void_p(d_q_count), int(q_rows),
+                                                  C.c_void_p(d_db_word), C.c_void_p(d_db_value), C.c_void_p(d_db_count), int(n_db), int(stride),
+                                                  C.c_void_p(d_score)))
 
     def wait_stream(self, hip_stream: int):
         """Orders this context's stream after everything enqueued so far on another stream of the device."""

@@ -262,7 +262,10 @@ int ss_build_geometry(const ss_orb_params &p, int width, int height, ss_geom *g,
                     const uint32_t rec[SS_TILE_REC_WORDS] = {(uint32_t)l, (uint32_t)(tx * SS_TILE_W), (uint32_t)(ty * SS_TILE_H2),
                                                              (uint32_t)L.w, (uint32_t)L.h, (uint32_t)L.pitch, L.off,
                                                              (uint32_t)L.xinfo_off, (uint32_t)L.yinfo_off,
-                                                             (uint32_t)col0 | ((uint32_t)row0 << 16)};
+                                                             (uint32_t)col0 | ((uint32_t)row0 << 16),
+                                                             /* as a block of its own (ss_layout.h): one tile, its index */
+                                                             1u, (uint32_t)L.tiles_x, 0u,
+                                                             (uint32_t)(L.tile2_base + ty * L.tiles_x + tx)};
                     tabs->tile_recs.insert(tabs->tile_recs.end(), rec, rec + SS_TILE_REC_WORDS);
                 }
             const size_t ubase = tabs->cell_units.size();
@@ -306,6 +309,23 @@ int ss_build_geometry(const ss_orb_params &p, int width, int height, ss_geom *g,
             L.ytab_off = (int)tabs->rtab.size();
             build_axis_table(L.h, P.h, false, tabs->rtab, L.h);
         }
+    }
+    /* the FAST kernel's blocks: pairs of vertically adjacent tiles, level by level and row-major as the tiles (so the blocks of
+     * a level neighbourhood keep consecutive indices), after the tile records */
+    for (int l = 0; l < p.n_levels; l++) {
+        const ss_level &L = g->lv[l];
+        for (int ty = 0; ty < L.tiles2_y; ty += 2)
+            for (int tx = 0; tx < L.tiles_x; tx++) {
+                const int tile = L.tile2_base + ty * L.tiles_x + tx;
+                const bool pair = ty + 1 < L.tiles2_y;
+                uint32_t rec[SS_TILE_REC_WORDS];
+                std::copy_n(tabs->tile_recs.begin() + (size_t)tile * SS_TILE_REC_WORDS, SS_TILE_REC_WORDS, rec);
+                rec[10] = pair ? 2u : 1u;
+                rec[11] = (uint32_t)L.tiles_x;
+                rec[12] = pair ? tabs->tilecell[tile + L.tiles_x] >> 16 : 0u;
+                rec[13] = (uint32_t)tile;
+                tabs->tile_recs.insert(tabs->tile_recs.end(), rec, rec + SS_TILE_REC_WORDS);
+            }
     }
     /* the resize kernels read a whole 64-column tile's taps whatever the level's width: the last table must not end
      * the allocation short of that */

@@ -22,7 +22,7 @@ struct ssk_extract_ws {
     /* tables uploaded once per geometry */
     ss_geom *dg = nullptr;
     ss_rtab *rtab = nullptr;
-    uint32_t *tile_recs = nullptr; /* per-tile records of the FAST kernel (SS_TILE_REC_WORDS each) */
+    uint32_t *tile_recs = nullptr; /* per-tile records (the FAST kernel's blocks in a launch too small to fill the chip), then its per-block records of two stacked tiles (SS_TILE_REC_WORDS each) */
     uint16_t *cinfo = nullptr;
     uint32_t *cell_units = nullptr;
     /* per-batch buffers, [batch slot][...] */

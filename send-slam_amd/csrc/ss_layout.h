@@ -39,6 +39,12 @@
 #define SS_TS_CELLS (3 * SS_TS_ROWS) /* sub-lists per tile: (cell row - first row) * 3 + (cell col - first col) */
 #define SS_TS_HDR (SS_TILE_H2 > 32 ? 12 : 8) /* header words per tile (SS_TS_CELLS count words, padded) */
 #define SS_TILE_REC_WORDS 16 /* per-tile record of the FAST kernel: level, x0, y0, w, h, pitch, off, xinfo_off, yinfo_off, first cells */
+/* A block of the FAST kernel takes the tiles (tx, 2k) and (tx, 2k + 1) of a level, or the lone tile of an odd last tile row.  Its
+ * record, after the tile records in the same table, is the upper tile's record plus word 10: tiles in the block (1 or 2),
+ * word 11: tiles_x (the lower tile's index less the upper's), word 12: first cell row of the lower tile, word 13: the upper
+ * tile's index.  The tile records carry the same four words for a block of that one tile: a launch whose tiles do not fill
+ * the chip's block slots (a single frame) runs a block per tile from them, since its FAST stage lasts as long as ONE block
+ * and a block of two tiles is twice as long (ssk_fast_blur_nms decides, from the launch's size alone). */
 #define SS_CELL_UNITS 12 /* (tile, sub-list) pairs one cell can be spread over */
 
 #define SS_PACK(x, y, r) ((uint32_t)(x) | ((uint32_t)(y) << 12) | ((uint32_t)(r) << 24))
@@ -100,6 +106,14 @@ typedef struct {
     uint32_t pat4[64][4];
     ss_level lv[SS_MAX_LEVELS_];
 } ss_geom;
+
+/* blocks of the FAST kernel, all levels */
+static inline int ss_fast_blocks(const ss_geom *g)
+{
+    int n = 0;
+    for (int l = 0; l < g->n_levels; l++) n += g->lv[l].tiles_x * ((g->lv[l].tiles2_y + 1) / 2);
+    return n;
+}
 
 /* cell-window info of one column (or row): is it inside an evaluated FAST window, is it the
  * first / last pixel of that window (no NMS neighbour on that side), which cell */

@@ -40,6 +40,8 @@
  *   ss_vocab_* / ss_bow_* /    the ORBvoc.txt argument of the System constructor :511 (DBoW2 TemplatedVocabulary::loadFromTextFile),
  *   ss_match_bow_*             Frame::ComputeBoW, ORBmatcher::SearchByBoW (TrackReferenceKeyFrame, relocalisation) and
  *                              L1Scoring::score (KeyFrameDatabase) inside TrackMonocular :594
+ *   ss_proj_* / ss_match_proj* Tracking::SearchLocalPoints: Frame::isInFrustum, MapPoint::PredictScale and
+ *                              ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>&, th) inside TrackMonocular :594
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
  *   ss_last_error              the cerr diagnostics of the shim (:457-469, :523-551)
  *
@@ -613,6 +615,116 @@ int ss_match_bow_batch_device(ss_ctx *ctx, const int32_t *train_src, const ss_gu
  * Asynchronous on the context's stream. */
 int ss_bow_score_device(ss_ctx *ctx, const void *d_q_word, const void *d_q_value, const void *d_q_count, int q_rows,
                         const void *d_db_word, const void *d_db_value, const void *d_db_count, int n_db, int stride, void *d_score);
+
+/* ---- map-point projection search: Tracking::SearchLocalPoints = Frame::isInFrustum followed by
+ * ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>&, th).  Neither upstream source is in the reference tree.  This is the
+ * library's own restatement and parity with the real binary stays unpinned, as for the guided and the bag-of-words stages.
+ * tests/proj_ref.py is its normative statement; DESIGN.md section 17 --------------------------------------------------------
+ * - Every float step is one float32 IEEE operation, left to right as written, with no contraction.
+ * - Every test is written in its accepting form, so a NaN fails it.
+ * Per frame there is one view, ss_proj_view, all float32: rcw[9] row-major, tcw[3], ow[3]; fx, fy, cx, cy, bf; min_x, max_x,
+ * min_y, max_y (upstream's mnMinX and the rest).
+ * Per map point there is one ss_map_point of 32 bytes: x y z, nx ny nz (mean viewing direction), min_dist, max_dist.  These are
+ * mfMinDistance / mfMaxDistance as stored, before the 0.8 / 1.2 factors.  Each point also has a 32-byte descriptor.
+ * 1. Frustum.  The state is the number of the first test that fails; 0 means in view.
+ *    1. Test 1: pc = R.P + t, each component ((r0*x + r1*y) + r2*z) + t.  The test is pc.z > 0.
+ *    2. Test 2: invz = 1.0f / pc.z; u = fx*pc.x*invz + cx (two products, then the sum); v is formed likewise; the test is
+ *       u >= min_x && u <= max_x && v >= min_y && v <= max_y.
+ *    3. Test 3: po = P - ow; dist = sqrtf((po.x*po.x + po.y*po.y) + po.z*po.z); the test is
+ *       dist >= 0.8f*min_dist && dist <= 1.2f*max_dist.
+ *    4. Test 4: view_cos = ((po.x*nx + po.y*ny) + po.z*nz) / dist; the test is view_cos >= view_cos_limit.
+ *    5. Test 5 applies only when far_limit > 0.  The test is dist <= far_limit.
+ *       Deviation: upstream tests ||pc||, which is the same number in exact arithmetic.
+ * 2. Level.  ratio = max_dist / dist.  level is the smallest n in 0 .. n_levels-1 with ratio <= scale[n], else n_levels-1.
+ *    scale[] is the context's pyramid table (ss_geometry.cpp).
+ *    Deviation: upstream evaluates ceil(logf(ratio) / logScaleFactor) and clamps it.  Checked on the CPU with numpy's float32 log,
+ *    scale 1.2 and 8 levels: the sweep was 2 M ratios in [0.3, 5] plus +-3000 ulp around every table entry; the two forms differ
+ *    at one value, and that ratio equals a table entry.  (How many ratios differ depends on the float32 log at hand;
+ *    tests/test_proj_ref.py repeats the sweep and requires every disagreement to lie within 2 ulp of a table entry.)
+ * 3. Window.  r = (view_cos > 0.998f ? 2.5f : 4.0f) * th.  radius = r * scale[level].  u_right = u - bf*invz.
+ *    A candidate is a train row j < n_train that passes all of:
+ *    - level-1 <= octave_j <= level;
+ *    - fabsf(x_j - u) < radius and fabsf(y_j - v) < radius, ss_match_guided's membership test, unchanged;
+ *    - if a taken mask is given, taken[j] == 0;
+ *    - if check_right is set and right[j] > 0, then fabsf(u_right - right[j]) <= radius.
+ * 4. Best and second.  The key is distance << 20 | j.  The best is the lowest key.  The second is the lowest key over the other
+ *    candidates.  idx, d1, lvl1 come from the best.  d2, lvl2 come from the second.  With no second candidate, d2 is 0xFFFF and
+ *    lvl2 is -1.  Deviation: upstream's bestLevel2 depends on the scan order when seconds tie.
+ * 5. Accept iff d1 <= th_high and not (ratio_den != 0 and lvl1 == lvl2 and d1*ratio_den > d2*ratio_num).  Upstream uses 100 and
+ *    8 / 10.  Equality accepts, as upstream's bestDist > mfNNratio*bestDist2 does.
+ * 6. one_to_one is optional and is ss_match_guided's order-free rule on d1 << 20 | i.  Upstream has none: a later map point
+ *    overwrites an earlier one.  With 0, several points may name one row.
+ * Outputs per point row: idx is int32, -1 when not accepted.  d1 / d2 are uint16 raw values, 0xFFFF when absent.  ss_proj_point is
+ * 32 bytes: u, v, u_right, view_cos, dist, radius, int32 level, int32 state.  When state != 0, the floats are 0.0f and level is
+ * -1.  Rows >= n_points get state -1 and "none".
+ * Outputs per frame: ss_proj_summary, 32 bytes, holding status, n_points, n_train, n_in_view, n_candidates, n_accepted, n_unique,
+ * reserved 0. */
+typedef struct {          /* 96 bytes, one per frame */
+    float rcw[9], tcw[3], ow[3];
+    float fx, fy, cx, cy, bf;
+    float min_x, max_x, min_y, max_y;
+} ss_proj_view;
+typedef struct {          /* 32 bytes, one per map point */
+    float x, y, z;
+    float nx, ny, nz;
+    float min_dist, max_dist;
+} ss_map_point;
+typedef struct {          /* 32 bytes, one per point row */
+    float u, v, u_right, view_cos, dist, radius;
+    int32_t level, state;
+} ss_proj_point;
+typedef struct {          /* 40 bytes */
+    float view_cos_limit; /* upstream: 0.5; NaN is SS_ERR_INVALID_ARG */
+    float th;             /* the window factor of step 3; must be finite and > 0 */
+    float far_limit;      /* test 5; not > 0 (zero, negative, NaN): no test */
+    int32_t th_high;      /* 0 .. 256 */
+    int32_t ratio_num, ratio_den; /* 0 .. 32767; ratio_den 0 = no ratio test */
+    int32_t one_to_one, check_right;
+    int32_t extent_w, extent_h;   /* as in ss_guided_params: they size the index only; the batch form ignores them */
+} ss_proj_params;
+typedef struct {          /* 32 bytes, one per frame */
+    int32_t status;       /* SS_OK, or the frame_error that voided the frame (all rows "none", counts 0) */
+    int32_t n_points, n_train;
+    int32_t n_in_view;    /* points with state 0 */
+    int32_t n_candidates; /* Hamming distances taken */
+    int32_t n_accepted, n_unique; /* after the acceptance test, after one_to_one */
+    int32_t reserved;     /* 0 */
+} ss_proj_summary;
+/* The view of a camera at pose (rcw row-major, tcw), needs no device: every number rounded to float32 once; ow = -R^T t is formed
+ * in double (((r0*t0 + r3*t1) + r6*t2, negated) and then rounded; the bounds are 0 .. width, 0 .. height. */
+int ss_proj_view_init(const ss_camera *cam, const double rcw[9], const double tcw[3], float bf, ss_proj_view *out);
+/* The host twin of steps 1 - 3 for n points: out[i] is what the device calls write for the point.  scale: n_levels entries,
+ * 1 <= n_levels <= SS_MAX_LEVELS.  Needs no device.  p is checked as the device calls check it (SS_ERR_INVALID_ARG). */
+int ss_proj_points_host(const ss_proj_view *view, const ss_proj_params *p, const float *scale, int n_levels,
+                        const ss_map_point *points, int n, ss_proj_point *out);
+/* n_frames frames on caller-supplied device arrays.  Map points: d_points [n_blocks][point_rows] ss_map_point, d_point_desc
+ * [n_blocks][point_rows][32], counts d_n_points (device int32 [n_blocks], clamped to 0 .. point_rows).  Train side, as for
+ * ss_match_guided_pairs_device: d_train [n_frames][rows_per_frame][32], d_train_kp [n_frames][rows_per_frame] ss_keypoint,
+ * d_n_train device int32 [n_frames]; optional (NULL: absent) d_train_right float and d_train_taken uint8, both
+ * [n_frames][rows_per_frame].  views: a HOST table of n_frames views.  point_src: a HOST table [n_frames] of block numbers, frame b
+ * searches the points of block point_src[b]; NULL: frame b reads block b (then n_blocks >= n_frames).  Both tables are copied
+ * before the call returns.  Outputs: d_idx (int32) / d_d1 / d_d2 (uint16) / d_proj (ss_proj_point) [n_frames][point_rows] and
+ * d_summary [n_frames] ss_proj_summary.  SS_ERR_INVALID_ARG: either row count above SS_GUIDED_MAX_ROWS, th not > 0 or not finite, a
+ * NaN view_cos_limit, th_high outside 0 .. 256, a ratio term outside 0 .. 32767, a point_src entry outside 0 .. n_blocks - 1,
+ * extent_w or extent_h <= 0, a NULL buffer.  Asynchronous on the context's stream. */
+int ss_match_proj_pairs_device(ss_ctx *ctx, const void *d_points, const void *d_point_desc, const void *d_n_points, int n_blocks,
+                               int point_rows, const void *d_train, const void *d_train_kp, const void *d_n_train,
+                               const void *d_train_right, const void *d_train_taken, int n_frames, int rows_per_frame,
+                               const ss_proj_view *views, const int32_t *point_src, const ss_proj_params *p, void *d_idx, void *d_d1,
+                               void *d_d2, void *d_proj, void *d_summary);
+/* The same, the train side being the frames of the last ss_extract_batch_device batch (n_frames and kp_capacity are the batch's;
+ * d_train_right / d_train_taken are [n_frames][kp_capacity]).  A frame whose frame_error is set gets that status in its summary
+ * and all its rows are "none". */
+int ss_match_proj_batch_device(ss_ctx *ctx, const void *d_points, const void *d_point_desc, const void *d_n_points, int n_blocks,
+                               int point_rows, const void *d_train_right, const void *d_train_taken, const ss_proj_view *views,
+                               const int32_t *point_src, const ss_proj_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_proj,
+                               void *d_summary);
+/* One frame with host pointers in and out (copy in, the pairs form, copy out), synchronous: the counterpart of ss_match_guided.
+ * n_points, n_train <= SS_GUIDED_MAX_ROWS; train_right / train_taken may be NULL; proj may be NULL. */
+int ss_match_proj(ss_ctx *ctx, const ss_proj_view *view, const ss_map_point *points, const uint8_t *point_desc, int n_points,
+                  const uint8_t *train, const ss_keypoint *train_kp, int n_train, const float *train_right,
+                  const uint8_t *train_taken, const ss_proj_params *p, int32_t *idx, uint16_t *d1, uint16_t *d2,
+                  ss_proj_point *proj, ss_proj_summary *summary);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

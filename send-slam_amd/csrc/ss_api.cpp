@@ -26,6 +26,7 @@
 #include "ss_geometry.h"
 #include "ss_kernels.h"
 #include "ss_layout.h"
+#include "ss_proj_steps.h"
 #include "ss_track.h"
 
 namespace {
@@ -132,6 +133,12 @@ struct ss_ctx {
     dev_buf<int32_t> d_stereo_err;
     /* guided matching: the grid index and candidate counts of a call (guided_run sizes them); the host form's device copies */
     dev_buf<uint8_t> d_guided_ws, d_guided_io;
+    /* projection search: the host form's device copies; the views and block numbers of a call on the device, staged in pinned
+     * memory as h_train_src is (the event marks the end of the last copy) */
+    dev_buf<uint8_t> d_proj_io, d_proj_tab;
+    uint8_t *h_proj_tab = nullptr;
+    size_t h_proj_tab_bytes = 0;
+    hipEvent_t proj_tab_copied = nullptr;
     /* bag of words: the vocabulary on the device (one allocation: rows, records, weights), the node index of a pairs call, and
      * what ss_bow_transform_batch_device keeps of bow_frames frames of the last batch for ss_match_bow_batch_device (nodes, node
      * index, index counts) */
@@ -603,6 +610,10 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_stereo_err);
     dev_free(c->d_guided_ws);
     dev_free(c->d_guided_io);
+    dev_free(c->d_proj_io);
+    dev_free(c->d_proj_tab);
+    if (c->h_proj_tab) (void)hipHostFree(c->h_proj_tab);
+    if (c->proj_tab_copied) (void)hipEventDestroy(c->proj_tab_copied);
     dev_free(c->d_voc);
     dev_free(c->d_bow_ws);
     dev_free(c->d_bow_keep);
@@ -1756,6 +1767,230 @@ int ss_match_guided(ss_ctx *c, const uint8_t *query, const ss_keypoint *query_kp
         HIP_TRY(c, hipMemcpyAsync(d2, d + o_d2, (size_t)n_query * 2, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipMemcpyAsync(summary, d + o_sum, sizeof(ss_guided_summary), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SS_OK;
+}
+
+/* ---- map-point projection search (csrc/ss_proj.hip, csrc/ss_proj_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *proj_params_error(const ss_proj_params *p)
+{
+    if (!p) return "projection search: params is NULL";
+    if (!(p->th > 0.0f) || !std::isfinite(p->th)) return "projection search: th must be finite and > 0";
+    if (p->view_cos_limit != p->view_cos_limit) return "projection search: view_cos_limit is NaN";
+    if (p->th_high < 0 || p->th_high > 256) return "projection search: th_high must be 0 .. 256";
+    if (p->ratio_num < 0 || p->ratio_num > 32767 || p->ratio_den < 0 || p->ratio_den > 32767)
+        return "projection search: ratio_num and ratio_den must be 0 .. 32767 (ratio_den 0 = no ratio test)";
+    return nullptr;
+}
+
+int ss_proj_view_init(const ss_camera *cam, const double rcw[9], const double tcw[3], float bf, ss_proj_view *out)
+{
+    if (!cam || !rcw || !tcw || !out) return SS_ERR_INVALID_ARG;
+    for (int k = 0; k < 9; k++) out->rcw[k] = (float)rcw[k];
+    for (int k = 0; k < 3; k++) {
+        out->tcw[k] = (float)tcw[k];
+        out->ow[k] = (float)-((rcw[k] * tcw[0] + rcw[3 + k] * tcw[1]) + rcw[6 + k] * tcw[2]);
+    }
+    out->fx = (float)cam->fx, out->fy = (float)cam->fy, out->cx = (float)cam->cx, out->cy = (float)cam->cy;
+    out->bf = bf;
+    out->min_x = 0.0f, out->max_x = (float)cam->width;
+    out->min_y = 0.0f, out->max_y = (float)cam->height;
+    return SS_OK;
+}
+
+int ss_proj_points_host(const ss_proj_view *view, const ss_proj_params *p, const float *scale, int n_levels, const ss_map_point *points,
+                        int n, ss_proj_point *out)
+{
+    if (proj_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!view || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n < 0 || (n > 0 && (!points || !out))) return SS_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) out[i] = ss_proj_eval(*view, points[i], p->view_cos_limit, p->th, p->far_limit, scale, n_levels);
+    return SS_OK;
+}
+
+/* The host tables of a call -> c->d_proj_tab on c->stream: n views, then n block numbers (point_src NULL: 0, 1, ...).  Through
+ * pinned memory, as upload_train_src does it: the caller's arrays are free when this returns */
+static int upload_proj_tables(ss_ctx *c, const ss_proj_view *views, const int32_t *point_src, int n)
+{
+    const size_t bytes = (size_t)n * (sizeof(ss_proj_view) + sizeof(int32_t));
+    int rc = grow(c, c->d_proj_tab, bytes);
+    if (rc != SS_OK) return rc;
+    if (c->proj_tab_copied) HIP_TRY(c, hipEventSynchronize(c->proj_tab_copied));
+    else HIP_TRY(c, hipEventCreateWithFlags(&c->proj_tab_copied, hipEventDisableTiming));
+    if (c->h_proj_tab_bytes < bytes) {
+        if (c->h_proj_tab) (void)hipHostFree(c->h_proj_tab);
+        c->h_proj_tab = nullptr;
+        c->h_proj_tab_bytes = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_proj_tab, bytes, hipHostMallocDefault));
+        c->h_proj_tab_bytes = bytes;
+    }
+    memcpy(c->h_proj_tab, views, (size_t)n * sizeof(ss_proj_view));
+    int32_t *src = (int32_t *)(c->h_proj_tab + (size_t)n * sizeof(ss_proj_view));
+    for (int b = 0; b < n; b++) src[b] = point_src ? point_src[b] : b;
+    HIP_TRY(c, hipMemcpyAsync(c->d_proj_tab, c->h_proj_tab, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->proj_tab_copied, c->stream));
+    return SS_OK;
+}
+
+/* The checks the device forms share, the tables, then the three launches of a call whose device operands and outputs are filled
+ * in: the index of the train frames (k_guided_index on a guided call over the same arrays), the search, the finish */
+static int proj_run(ss_ctx *c, ssk_proj_call &g, int n_blocks, const ss_proj_view *views, const int32_t *point_src, const ss_proj_params *p,
+                    int extent_w, int extent_h)
+{
+    if (const char *msg = proj_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (g.n_frames < 0 || n_blocks < 0 || g.point_rows < 1 || g.rows < 1) return fail(c, SS_ERR_INVALID_ARG, "projection search: bad frame, block or row count");
+    if (g.point_rows > SS_GUIDED_MAX_ROWS || g.rows > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "projection search: point_rows " + std::to_string(g.point_rows) + " / rows_per_frame " + std::to_string(g.rows) +
+                                               " exceed SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    if (extent_w <= 0 || extent_h <= 0) return fail(c, SS_ERR_INVALID_ARG, "projection search: extent_w and extent_h must be > 0");
+    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
+        return fail(c, SS_ERR_INVALID_ARG, "projection search: the context's n_levels / scale_factor give no pyramid table");
+    if (g.n_frames == 0) return SS_OK;
+    if (!views) return fail(c, SS_ERR_INVALID_ARG, "projection search: views is NULL");
+    for (int b = 0; b < g.n_frames; b++) {
+        const int pb = point_src ? point_src[b] : b;
+        if (pb < 0 || pb >= n_blocks)
+            return fail(c, SS_ERR_INVALID_ARG, std::string(point_src ? "point_src[" : "frame [") + std::to_string(b) + "] = " + std::to_string(pb) +
+                                                   " names no block of points (" + std::to_string(n_blocks) + ")");
+    }
+    if (!g.points || !g.p_desc || !g.np || !g.t_kp || !g.t_desc || !g.nt || !g.idx || !g.d1 || !g.d2 || !g.proj || !g.summary)
+        return fail(c, SS_ERR_INVALID_ARG, "projection search: NULL buffer");
+    if (p->check_right && !g.t_right) return fail(c, SS_ERR_INVALID_ARG, "projection search: check_right needs the right coordinates of the train rows");
+    g.view_cos_limit = p->view_cos_limit, g.th = p->th, g.far_limit = p->far_limit;
+    g.th_high = p->th_high, g.rnum = p->ratio_num, g.rden = p->ratio_den;
+    g.one_to_one = p->one_to_one != 0, g.check_right = p->check_right != 0;
+    g.n_levels = c->params.n_levels;
+    ss_scale_table(c->params.scale_factor, g.n_levels, g.scale);
+    int rc = upload_proj_tables(c, views, point_src, g.n_frames);
+    if (rc != SS_OK) return rc;
+    g.views = (const ss_proj_view *)c->d_proj_tab.p;
+    g.src = (const int32_t *)(c->d_proj_tab.p + (size_t)g.n_frames * sizeof(ss_proj_view));
+    ssk_guided_call ix; /* the index alone: train keypoints, counts, errors, grid, workspace */
+    ix.n_frames = g.n_frames;
+    ix.rows = g.rows;
+    ix.t_kp = g.t_kp;
+    ix.nt = g.nt;
+    ix.frame_error = g.frame_error;
+    ssk_guided_grid(ix, extent_w, extent_h);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t cells = up((size_t)g.n_frames * (SSK_GUIDED_MAX_CELLS + 1) * sizeof(uint32_t));
+    const size_t recs = up((size_t)g.n_frames * g.rows * 16);
+    const size_t cand = up((size_t)g.n_frames * g.point_rows * sizeof(int32_t));
+    rc = grow(c, c->d_guided_ws, cells + recs + cand);
+    if (rc != SS_OK) return rc;
+    ix.cell_start = (uint32_t *)c->d_guided_ws.p;
+    ix.recs = c->d_guided_ws.p + cells;
+    g.shift = ix.shift, g.cols = ix.cols, g.x_max = ix.x_max, g.y_max = ix.y_max;
+    g.cell_start = ix.cell_start, g.recs = ix.recs;
+    g.n_cand = (int32_t *)(c->d_guided_ws.p + cells + recs);
+    const int64_t nt = (int64_t)g.n_frames * g.rows, np = (int64_t)g.n_frames * g.point_rows, n_cells = (int64_t)ix.cols * ix.grid_rows;
+    {
+        stage_timer t(c, "proj_index", nt * ((int64_t)sizeof(ss_keypoint) + 16) + g.n_frames * (n_cells + 1) * 4);
+        ssk_guided_index(c->stream, ix);
+    }
+    {
+        /* per point: the point, its descriptor, the 44 bytes it writes; the records and descriptors it visits depend on the content */
+        stage_timer t(c, "proj_search", np * ((int64_t)sizeof(ss_map_point) + SS_DESC_BYTES + 12 + (int64_t)sizeof(ss_proj_point)));
+        ssk_proj_search(c->stream, g);
+    }
+    {
+        stage_timer t(c, "proj_finish", np * (8 + 2 + 4 + 4) + g.n_frames * (int64_t)sizeof(ss_proj_summary));
+        ssk_proj_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+static void proj_outputs(ssk_proj_call &g, void *d_idx, void *d_d1, void *d_d2, void *d_proj, void *d_summary)
+{
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
+    g.proj = (ss_proj_point *)d_proj;
+    g.summary = (ss_proj_summary *)d_summary;
+}
+
+int ss_match_proj_pairs_device(ss_ctx *c, const void *d_points, const void *d_point_desc, const void *d_n_points, int n_blocks, int point_rows,
+                               const void *d_train, const void *d_train_kp, const void *d_n_train, const void *d_train_right,
+                               const void *d_train_taken, int n_frames, int rows_per_frame, const ss_proj_view *views, const int32_t *point_src,
+                               const ss_proj_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_proj, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    ssk_proj_call g;
+    g.n_frames = n_frames;
+    g.point_rows = point_rows;
+    g.rows = rows_per_frame;
+    g.points = (const ss_map_point *)d_points, g.p_desc = (const uint8_t *)d_point_desc, g.np = (const int32_t *)d_n_points;
+    g.t_kp = (const ss_keypoint *)d_train_kp, g.t_desc = (const uint8_t *)d_train, g.nt = (const int32_t *)d_n_train;
+    g.t_right = (const float *)d_train_right, g.t_taken = (const uint8_t *)d_train_taken;
+    proj_outputs(g, d_idx, d_d1, d_d2, d_proj, d_summary);
+    return proj_run(c, g, n_blocks, views, point_src, p, p ? p->extent_w : 1, p ? p->extent_h : 1);
+}
+
+int ss_match_proj_batch_device(ss_ctx *c, const void *d_points, const void *d_point_desc, const void *d_n_points, int n_blocks, int point_rows,
+                               const void *d_train_right, const void *d_train_taken, const ss_proj_view *views, const int32_t *point_src,
+                               const ss_proj_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_proj, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->have_geom || c->last_n_frames <= 0) return fail(c, SS_ERR_STATE, "ss_match_proj_batch_device: no batch has been extracted");
+    ssk_proj_call g;
+    g.n_frames = c->last_n_frames;
+    g.point_rows = point_rows;
+    g.rows = c->hg.kcap;
+    g.points = (const ss_map_point *)d_points, g.p_desc = (const uint8_t *)d_point_desc, g.np = (const int32_t *)d_n_points;
+    g.t_kp = c->ws.kps, g.t_desc = c->ws.desc, g.nt = c->ws.n_kp;
+    g.frame_error = c->ws.frame_error;
+    g.t_right = (const float *)d_train_right, g.t_taken = (const uint8_t *)d_train_taken;
+    proj_outputs(g, d_idx, d_d1, d_d2, d_proj, d_summary);
+    return proj_run(c, g, n_blocks, views, point_src, p, c->hg.w, c->hg.h);
+}
+
+int ss_match_proj(ss_ctx *c, const ss_proj_view *view, const ss_map_point *points, const uint8_t *point_desc, int n_points, const uint8_t *train,
+                  const ss_keypoint *train_kp, int n_train, const float *train_right, const uint8_t *train_taken, const ss_proj_params *p,
+                  int32_t *idx, uint16_t *d1, uint16_t *d2, ss_proj_point *proj, ss_proj_summary *summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_points < 0 || n_train < 0 || n_points > SS_GUIDED_MAX_ROWS || n_train > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "projection search: n_points and n_train must be 0 .. SS_GUIDED_MAX_ROWS");
+    if (!view || (n_points > 0 && (!points || !point_desc || !idx || !d1 || !d2)) || (n_train > 0 && (!train || !train_kp)) || !summary)
+        return fail(c, SS_ERR_INVALID_ARG, "projection search: NULL buffer");
+    /* one block of `pr` points, one train frame of `tr` rows, the two counts, then the outputs */
+    const size_t pr = (size_t)std::max(n_points, 1), tr = (size_t)std::max(n_train, 1);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_pt = 0, o_pd = o_pt + up(pr * sizeof(ss_map_point)), o_td = o_pd + up(pr * 32), o_tk = o_td + up(tr * 32);
+    const size_t o_tr = o_tk + up(tr * sizeof(ss_keypoint)), o_tt = o_tr + up(tr * 4), o_n = o_tt + up(tr), o_idx = o_n + 256;
+    const size_t o_d1 = o_idx + up(pr * 4), o_d2 = o_d1 + up(pr * 2), o_pj = o_d2 + up(pr * 2), o_sum = o_pj + up(pr * sizeof(ss_proj_point));
+    const size_t total = o_sum + 256;
+    int rc = grow(c, c->d_proj_io, total);
+    if (rc != SS_OK) return rc;
+    uint8_t *d = c->d_proj_io;
+    const int32_t counts[2] = {n_points, n_train};
+    if (n_points > 0) {
+        HIP_TRY(c, hipMemcpyAsync(d + o_pt, points, (size_t)n_points * sizeof(ss_map_point), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d + o_pd, point_desc, (size_t)n_points * 32, hipMemcpyHostToDevice, c->stream));
+    }
+    if (n_train > 0) {
+        HIP_TRY(c, hipMemcpyAsync(d + o_td, train, (size_t)n_train * 32, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d + o_tk, train_kp, (size_t)n_train * sizeof(ss_keypoint), hipMemcpyHostToDevice, c->stream));
+        if (train_right) HIP_TRY(c, hipMemcpyAsync(d + o_tr, train_right, (size_t)n_train * 4, hipMemcpyHostToDevice, c->stream));
+        if (train_taken) HIP_TRY(c, hipMemcpyAsync(d + o_tt, train_taken, (size_t)n_train, hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(d + o_n, counts, sizeof(counts), hipMemcpyHostToDevice, c->stream));
+    /* a side without rows has no array to pass: its count is 0 and nothing of it is read */
+    rc = ss_match_proj_pairs_device(c, d + o_pt, d + o_pd, d + o_n, 1, (int)pr, d + o_td, d + o_tk, d + o_n + 4, (train_right || n_train == 0) ? d + o_tr : nullptr,
+                                    train_taken ? d + o_tt : nullptr, 1, (int)tr, view, nullptr, p, d + o_idx, d + o_d1, d + o_d2, d + o_pj, d + o_sum);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream); /* `counts` is on this stack */
+        return rc;
+    }
+    if (n_points > 0) {
+        HIP_TRY(c, hipMemcpyAsync(idx, d + o_idx, (size_t)n_points * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d1, d + o_d1, (size_t)n_points * 2, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d2, d + o_d2, (size_t)n_points * 2, hipMemcpyDeviceToHost, c->stream));
+        if (proj) HIP_TRY(c, hipMemcpyAsync(proj, d + o_pj, (size_t)n_points * sizeof(ss_proj_point), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(summary, d + o_sum, sizeof(ss_proj_summary), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SS_OK;
 }

@@ -97,8 +97,7 @@ int ss_build_geometry(const ss_orb_params &p, int width, int height, ss_geom *g,
     /* ORBextractor ctor: mvScaleFactor (float, multiplied by the double member), quotas */
     float scale[SS_MAX_LEVELS_], inv_scale[SS_MAX_LEVELS_];
     const double scale_factor = (double)p.scale_factor;
-    scale[0] = 1.0f;
-    for (int i = 1; i < p.n_levels; i++) scale[i] = (float)(scale[i - 1] * scale_factor);
+    ss_scale_table(p.scale_factor, p.n_levels, scale);
     for (int i = 0; i < p.n_levels; i++) inv_scale[i] = 1.0f / scale[i];
     const float factor = (float)(1.0f / scale_factor);
     float n_desired = p.n_features * (1 - factor) /

@@ -17,6 +17,14 @@ struct ss_host_tables {
     std::vector<uint32_t> cell_units; /* per cell: SS_CELL_UNITS x (tile2 index | sub-list << 24), ~0 = end */
 };
 
+/* mvScaleFactor of the ORBextractor constructor: scale[0] = 1, scale[i] = (float)(scale[i - 1] * (double)scale_factor).  It depends
+ * on the ORB parameters only, not on the image size */
+inline void ss_scale_table(float scale_factor, int n_levels, float *scale)
+{
+    scale[0] = 1.0f;
+    for (int i = 1; i < n_levels; i++) scale[i] = (float)(scale[i - 1] * (double)scale_factor);
+}
+
 int ss_build_geometry(const ss_orb_params &p, int width, int height, ss_geom *g,
                       ss_host_tables *tabs, std::string *err);
 

@@ -179,6 +179,41 @@ void ssk_guided_grid(ssk_guided_call &g, int extent_w, int extent_h);
 void ssk_guided_index(hipStream_t s, const ssk_guided_call &g);
 void ssk_guided_search(hipStream_t s, const ssk_guided_call &g);
 void ssk_guided_finish(hipStream_t s, const ssk_guided_call &g);
+/* ss_proj.hip: map-point projection search (DESIGN.md "Projection search").  Frame b searches the points of block src[b]
+ * ([n_blocks][point_rows] map points and descriptors, counts np) in its train frame b ([n_frames][rows] keypoints, descriptors,
+ * optional right coordinates and taken flags, counts nt).  The train frames are indexed by ssk_guided_index on a guided call that
+ * shares t_kp, nt, frame_error, the grid and the workspace; search evaluates frustum, level and window of every point and walks
+ * the cells, finish applies one_to_one and writes the summaries. */
+struct ssk_proj_call {
+    int n_frames = 0, point_rows = 0, rows = 0;
+    const ss_map_point *points = nullptr;
+    const uint8_t *p_desc = nullptr;
+    const int32_t *np = nullptr;
+    const int32_t *src = nullptr;      /* device int32 [n_frames], or NULL: block b */
+    const ss_proj_view *views = nullptr; /* device [n_frames] */
+    const ss_keypoint *t_kp = nullptr;
+    const uint8_t *t_desc = nullptr;
+    const int32_t *nt = nullptr;
+    const int32_t *frame_error = nullptr; /* per train frame, or NULL */
+    const float *t_right = nullptr;       /* [n_frames][rows], or NULL */
+    const uint8_t *t_taken = nullptr;     /* [n_frames][rows], or NULL */
+    float view_cos_limit = 0, th = 0, far_limit = 0;
+    int th_high = 0, rnum = 0, rden = 0, one_to_one = 0, check_right = 0;
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    /* the grid and the index of the guided call */
+    int shift = 0, cols = 1;
+    float x_max = 0, y_max = 0;
+    const uint32_t *cell_start = nullptr;
+    const void *recs = nullptr;
+    int32_t *n_cand = nullptr; /* workspace [n_frames][point_rows] */
+    int32_t *idx = nullptr;
+    uint16_t *d1 = nullptr, *d2 = nullptr;
+    ss_proj_point *proj = nullptr;
+    ss_proj_summary *summary = nullptr;
+};
+void ssk_proj_search(hipStream_t s, const ssk_proj_call &g);
+void ssk_proj_finish(hipStream_t s, const ssk_proj_call &g);
 /* ss_bow.hip: vocabulary descent, BoW vectors, the node index and search of SearchByBoW, the L1 score (DESIGN.md "Bag of
  * words").  The vocabulary on the device, nodes numbered breadth first (0 = the root) so that a node's children are consecutive:
  * rows [n][32] descriptors, recs [n] ssk_bow_node, weight [n_words] doubles by word id. */

@@ -42,7 +42,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_rectify_build_map", "ss_rectify_set_map", "ss_rectify_batch_device", "ss_extract_stereo_raw",
            "ss_vocab_load_text", "ss_vocab_from_arrays", "ss_vocab_info", "ss_vocab_copy_out", "ss_vocab_destroy",
            "ss_bow_set_vocabulary", "ss_bow_transform_device", "ss_bow_transform_batch_device", "ss_match_bow_pairs_device",
-           "ss_match_bow_batch_device", "ss_bow_score_device"]
+           "ss_match_bow_batch_device", "ss_bow_score_device", "ss_proj_view_init", "ss_proj_points_host",
+           "ss_match_proj_pairs_device", "ss_match_proj_batch_device", "ss_match_proj"]
 
 
 class OrbParams(C.Structure):
@@ -140,6 +141,77 @@ def guided_params(th: int = 50, ratio_num: int = 9, ratio_den: int = 10, one_to_
     return GuidedParams(th=th, ratio_num=ratio_num, ratio_den=ratio_den, one_to_one=int(one_to_one), orientation=orientation,
                         radius=radius, radius_by_octave=int(radius_by_octave), octave_span=octave_span, extent_w=extent_w,
                         extent_h=extent_h)
+
+
+class ProjView(C.Structure):
+    """ss_proj_view: the pose and intrinsics a frame's map points are projected with, all float32"""
+    _fields_ = [("rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("min_x", C.c_float), ("max_x", C.c_float),
+                ("min_y", C.c_float), ("max_y", C.c_float)]
+
+
+class ProjParams(C.Structure):
+    _fields_ = [("view_cos_limit", C.c_float), ("th", C.c_float), ("far_limit", C.c_float), ("th_high", C.c_int32),
+                ("ratio_num", C.c_int32), ("ratio_den", C.c_int32), ("one_to_one", C.c_int32), ("check_right", C.c_int32),
+                ("extent_w", C.c_int32), ("extent_h", C.c_int32)]
+
+
+class ProjSummary(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_points", C.c_int32), ("n_train", C.c_int32), ("n_in_view", C.c_int32),
+                ("n_candidates", C.c_int32), ("n_accepted", C.c_int32), ("n_unique", C.c_int32), ("reserved", C.c_int32)]
+
+
+PROJ_VIEW_DTYPE = np.dtype([("rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("ow", "<f4", (3,))] +
+                           [(n, "<f4") for n in ("fx", "fy", "cx", "cy", "bf", "min_x", "max_x", "min_y", "max_y")])
+# ss_map_point: one per map point; ss_proj_point: one per point row of the outputs
+MAP_POINT_DTYPE = np.dtype([(n, "<f4") for n in ("x", "y", "z", "nx", "ny", "nz", "min_dist", "max_dist")])
+PROJ_POINT_DTYPE = np.dtype([(n, "<f4") for n in ("u", "v", "u_right", "view_cos", "dist", "radius")] + [("level", "<i4"), ("state", "<i4")])
+PROJ_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n, _ in ProjSummary._fields_])
+
+
+def proj_params(view_cos_limit: float = 0.5, th: float = 1.0, far_limit: float = 0.0, th_high: int = 100, ratio_num: int = 8,
+                ratio_den: int = 10, one_to_one: bool = False, check_right: bool = False, extent_w: int = 0,
+                extent_h: int = 0) -> ProjParams:
+    """upstream's SearchLocalPoints: view_cos_limit 0.5, TH_HIGH 100, ratio 8 / 10, th 1 (3 after a relocalisation)"""
+    return ProjParams(view_cos_limit=view_cos_limit, th=th, far_limit=far_limit, th_high=th_high, ratio_num=ratio_num,
+                      ratio_den=ratio_den, one_to_one=int(one_to_one), check_right=int(check_right), extent_w=extent_w,
+                      extent_h=extent_h)
+
+
+def proj_view(camera: Camera, rcw, tcw, bf: float = 0.0) -> ProjView:
+    """ss_proj_view_init: the view of `camera` at pose (rcw 3 x 3 row-major, tcw); needs no device"""
+    r = np.ascontiguousarray(rcw, np.float64).reshape(9)
+    t = np.ascontiguousarray(tcw, np.float64).reshape(3)
+    v = ProjView()
+    rc = load().ss_proj_view_init(C.byref(camera), r.ctypes.data, t.ctypes.data, C.c_float(bf), C.byref(v))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_proj_view_init refused its arguments")
+    return v
+
+
+def _views_array(views):
+    """one ProjView, a sequence of them or a PROJ_VIEW_DTYPE array -> a contiguous PROJ_VIEW_DTYPE array"""
+    if isinstance(views, ProjView):
+        views = [views]
+    if isinstance(views, np.ndarray):
+        return np.ascontiguousarray(views, PROJ_VIEW_DTYPE).reshape(-1)
+    return np.frombuffer(b"".join(bytes(v) for v in views), PROJ_VIEW_DTYPE).copy()
+
+
+def proj_points_host(view, params: ProjParams, scale, points: np.ndarray) -> np.ndarray:
+    """ss_proj_points_host: frustum, level and window of every map point on the host (the text the kernel compiles) ->
+    PROJ_POINT_DTYPE rows; needs no device"""
+    v = _views_array(view)
+    if len(v) != 1:
+        raise ValueError("one view")
+    sc = np.ascontiguousarray(scale, np.float32)
+    pts = np.ascontiguousarray(points, MAP_POINT_DTYPE)
+    out = np.empty(len(pts), PROJ_POINT_DTYPE)
+    rc = load().ss_proj_points_host(v.ctypes.data, C.byref(params), sc.ctypes.data, len(sc), pts.ctypes.data if len(pts) else None, len(pts),
+                                    out.ctypes.data if len(pts) else None)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_proj_points_host refused its arguments")
+    return out
 
 
 class VocabShape(C.Structure):
@@ -281,6 +353,14 @@ def load():
     lib.ss_match_bow_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(GuidedParams)] + [C.c_void_p] * 4
     lib.ss_bow_score_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_int, C.c_void_p]
+    lib.ss_proj_view_init.argtypes = [C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_float, C.POINTER(ProjView)]
+    lib.ss_proj_points_host.argtypes = [C.c_void_p, C.POINTER(ProjParams), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.ss_match_proj_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int] + \
+                                              [C.c_void_p, C.c_void_p, C.POINTER(ProjParams)] + [C.c_void_p] * 5
+    lib.ss_match_proj_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(ProjParams)] + \
+                                              [C.c_void_p] * 5
+    lib.ss_match_proj.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.POINTER(ProjParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProjSummary)]
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -707,6 +787,65 @@ class OrbContext:
                                               windows.ctypes.data if nq else None, C.byref(params), idx.ctypes.data, d1.ctypes.data,
                                               d2.ctypes.data, C.byref(summ)))
         return idx, d1, d2, {n: getattr(summ, n) for n, _ in GuidedSummary._fields_}
+
+    # ---- map-point projection search: frustum, level, window match (the rule: include/sendslam_orb.h) ----
+    @staticmethod
+    def _proj_tables(views, point_src, n_frames=None):
+        v = _views_array(views)
+        if n_frames is not None and len(v) != n_frames:
+            raise ValueError("one view per frame")
+        src = None if point_src is None else np.ascontiguousarray(point_src, np.int32)
+        if src is not None and len(src) != len(v):
+            raise ValueError("one point_src entry per frame")
+        return v, src
+
+    def match_proj_pairs_device(self, d_points: int, d_point_desc: int, d_n_points: int, n_blocks: int, point_rows: int, d_train: int,
+                                d_train_kp: int, d_n_train: int, n_frames: int, rows_per_frame: int, views, params: ProjParams, d_idx: int,
+                                d_d1: int, d_d2: int, d_proj: int, d_summary: int, point_src=None, d_train_right: int = 0,
+                                d_train_taken: int = 0):
+        """n_frames frames on device arrays: map points [n_blocks][point_rows] (MAP_POINT_DTYPE, descriptors, counts), train frames
+        [n_frames][rows_per_frame]; views: n_frames ProjView (host); point_src: host ints, frame b searches block point_src[b]
+        (None: block b); outputs [n_frames][point_rows], d_proj PROJ_POINT_DTYPE, d_summary PROJ_SUMMARY_DTYPE; asynchronous."""
+        v, src = self._proj_tables(views, point_src, n_frames)
+        self._check(self._lib.ss_match_proj_pairs_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_desc), C.c_void_p(d_n_points), n_blocks,
+                                                         point_rows, C.c_void_p(d_train), C.c_void_p(d_train_kp), C.c_void_p(d_n_train),
+                                                         C.c_void_p(d_train_right), C.c_void_p(d_train_taken), n_frames, rows_per_frame,
+                                                         v.ctypes.data if len(v) else None, None if src is None else src.ctypes.data, C.byref(params),
+                                                         C.c_void_p(d_idx), C.c_void_p(d_d1), C.c_void_p(d_d2), C.c_void_p(d_proj),
+                                                         C.c_void_p(d_summary)))
+
+    def match_proj_batch_device(self, d_points: int, d_point_desc: int, d_n_points: int, n_blocks: int, point_rows: int, views,
+                                params: ProjParams, d_idx: int, d_d1: int, d_d2: int, d_proj: int, d_summary: int, point_src=None,
+                                d_train_right: int = 0, d_train_taken: int = 0):
+        """the same against the frames of the last batch (one view per frame of it; d_train_right / d_train_taken
+        [n_frames][kp_capacity]); asynchronous."""
+        v, src = self._proj_tables(views, point_src)
+        self._check(self._lib.ss_match_proj_batch_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_desc), C.c_void_p(d_n_points), n_blocks,
+                                                         point_rows, C.c_void_p(d_train_right), C.c_void_p(d_train_taken), v.ctypes.data,
+                                                         None if src is None else src.ctypes.data, C.byref(params), C.c_void_p(d_idx),
+                                                         C.c_void_p(d_d1), C.c_void_p(d_d2), C.c_void_p(d_proj), C.c_void_p(d_summary)))
+
+    def match_proj(self, view: ProjView, points: np.ndarray, point_desc: np.ndarray, t: np.ndarray, t_kp: np.ndarray, params: ProjParams,
+                   right=None, taken=None):
+        """One frame, host arrays in and out -> (idx, d1, d2, PROJ_POINT_DTYPE rows, summary dict)."""
+        v = _views_array(view)
+        pts = np.ascontiguousarray(points, MAP_POINT_DTYPE)
+        pd = np.ascontiguousarray(point_desc, np.uint8).reshape(-1, 32)
+        t = np.ascontiguousarray(t, np.uint8).reshape(-1, 32)
+        t_kp = np.ascontiguousarray(t_kp, KP_DTYPE)
+        n, nt = len(pts), len(t)
+        right = None if right is None else np.ascontiguousarray(right, np.float32)
+        taken = None if taken is None else np.ascontiguousarray(taken, np.uint8)
+        if len(v) != 1 or len(pd) != n or len(t_kp) != nt or (right is not None and len(right) != nt) or (taken is not None and len(taken) != nt):
+            raise ValueError("points, descriptors, keypoints, right coordinates and taken flags differ in length")
+        idx, d1, d2 = np.empty(n, np.int32), np.empty(n, np.uint16), np.empty(n, np.uint16)
+        proj, summ = np.empty(n, PROJ_POINT_DTYPE), ProjSummary()
+        self._check(self._lib.ss_match_proj(self._h, v.ctypes.data, pts.ctypes.data if n else None, pd.ctypes.data if n else None, n,
+                                            t.ctypes.data if nt else None, t_kp.ctypes.data if nt else None, nt,
+                                            None if right is None else right.ctypes.data, None if taken is None else taken.ctypes.data,
+                                            C.byref(params), idx.ctypes.data, d1.ctypes.data, d2.ctypes.data, proj.ctypes.data if n else None,
+                                            C.byref(summ)))
+        return idx, d1, d2, proj, {n_: getattr(summ, n_) for n_, _ in ProjSummary._fields_}
 
     # ---- bag of words: vocabulary transform, SearchByBoW, L1 score (the rule: include/sendslam_orb.h) ----
     def set_vocabulary(self, voc: Vocabulary):

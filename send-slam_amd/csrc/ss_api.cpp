@@ -127,10 +127,12 @@ struct ss_ctx {
     std::vector<uint8_t> h_desc_r;
     std::vector<ss_stereo_point> h_stereo;
     dev_buf<uint8_t> d_stereo;
-    /* test hook, SENDSLAM_TEST_STEREO_FLAG=frame,...: the stereo stages see those frames of a batch as flagged (frame_error
-     * SS_ERR_OVERFLOW, through a copy of the array), the only way to reach the voided-pair rule without overflowing a capacity */
-    std::vector<int> stereo_test_flagged;
-    dev_buf<int32_t> d_stereo_err;
+    /* test hooks, SENDSLAM_TEST_STEREO_FLAG=frame,... and SENDSLAM_TEST_FLAG_BATCH=frame,...: the stereo stages / the batch forms
+     * of guided matching, bag of words and projection search see those frames of a batch as flagged (frame_error SS_ERR_OVERFLOW,
+     * through a copy of the array: flagged_frame_error), the only way to reach the voided-frame rules without overflowing a
+     * capacity; n_kp stays as extracted */
+    std::vector<int> stereo_test_flagged, batch_test_flagged;
+    dev_buf<int32_t> d_test_err;
     /* guided matching: the grid index and candidate counts of a call (guided_run sizes them); the host form's device copies */
     dev_buf<uint8_t> d_guided_ws, d_guided_io;
     /* projection search: the host form's device copies; the views and block numbers of a call on the device, staged in pinned
@@ -448,6 +450,35 @@ template <typename T> int grow(ss_ctx *c, dev_buf<T> &b, size_t want)
     return SS_OK;
 }
 
+/* the frames a test hook names: "frame,frame,..." */
+void parse_test_frames(const char *e, std::vector<int> &out)
+{
+    for (const char *q = e; q && *q;) {
+        char *end = nullptr;
+        const long f = strtol(q, &end, 10);
+        if (end == q) break;
+        out.push_back((int)f);
+        q = *end == ',' ? end + 1 : end;
+    }
+}
+
+/* The frame_error array a stage of the last batch reads: the extraction's own, or, where a test hook names frames, a copy of it
+ * on c->stream in which those frames carry SS_ERR_OVERFLOW. */
+int flagged_frame_error(ss_ctx *c, const std::vector<int> &frames, const int32_t **out)
+{
+    *out = c->ws.frame_error;
+    if (frames.empty()) return SS_OK;
+    static const int32_t flagged = SS_ERR_OVERFLOW;
+    const int rc = grow(c, c->d_test_err, (size_t)c->last_n_frames * sizeof(int32_t));
+    if (rc != SS_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_test_err, c->ws.frame_error, (size_t)c->last_n_frames * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    for (int f : frames)
+        if (f >= 0 && f < c->last_n_frames)
+            HIP_TRY(c, hipMemcpyAsync(c->d_test_err + f, &flagged, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    *out = c->d_test_err;
+    return SS_OK;
+}
+
 /* the 8 bytes per query of a match scratch as the matcher's three outputs: idx [n] int32, then d1 [n] and d2 [n] uint16 */
 struct match_out {
     int32_t *idx;
@@ -568,14 +599,8 @@ int ss_create(int device_ordinal, const ss_orb_params *params, ss_ctx **out)
     if (const char *e = getenv("SENDSLAM_FORCE_INGEST")) c->force_ingest = atoi(e) != 0;
     if (const char *e = getenv("SENDSLAM_TRACK_TIMING")) c->track_timing = atoi(e) != 0;
     if (const char *e = getenv("SENDSLAM_MATCH_PACKED")) c->no_desc_x = atoi(e) != 0;
-    if (const char *e = getenv("SENDSLAM_TEST_STEREO_FLAG"))
-        for (const char *q = e; *q;) {
-            char *end = nullptr;
-            const long f = strtol(q, &end, 10);
-            if (end == q) break;
-            c->stereo_test_flagged.push_back((int)f);
-            q = *end == ',' ? end + 1 : end;
-        }
+    parse_test_frames(getenv("SENDSLAM_TEST_STEREO_FLAG"), c->stereo_test_flagged);
+    parse_test_frames(getenv("SENDSLAM_TEST_FLAG_BATCH"), c->batch_test_flagged);
     hipError_t se = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (se != hipSuccess) {
         delete c;
@@ -607,7 +632,7 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_train_src);
     dev_free(c->d_carry_x);
     dev_free(c->d_stereo);
-    dev_free(c->d_stereo_err);
+    dev_free(c->d_test_err);
     dev_free(c->d_guided_ws);
     dev_free(c->d_guided_io);
     dev_free(c->d_proj_io);
@@ -1359,16 +1384,8 @@ int ss_stereo_batch_device(ss_ctx *c, const ss_stereo_params *p, void *d_points,
     const float bt = st.bf * p->th_depth;
     st.close_depth = bt / p->fx;
     st.points = d_points, st.summary = d_summary;
-    if (!c->stereo_test_flagged.empty()) {
-        static const int32_t flagged = SS_ERR_OVERFLOW;
-        rc = grow(c, c->d_stereo_err, (size_t)c->last_n_frames * sizeof(int32_t));
-        if (rc != SS_OK) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->d_stereo_err, c->ws.frame_error, (size_t)c->last_n_frames * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-        for (int f : c->stereo_test_flagged)
-            if (f >= 0 && f < c->last_n_frames)
-                HIP_TRY(c, hipMemcpyAsync(c->d_stereo_err + f, &flagged, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        st.frame_error = c->d_stereo_err;
-    }
+    rc = flagged_frame_error(c, c->stereo_test_flagged, &st.frame_error);
+    if (rc != SS_OK) return rc;
     const int64_t nf = g.n_features;
     {
         /* both eyes' keypoints, the left descriptors, ~1 % of the right ones per left keypoint (one row here), the points */
@@ -1715,7 +1732,8 @@ int ss_match_guided_batch_device(ss_ctx *c, const int32_t *train_src, const void
     g.q_desc = g.t_desc = c->ws.desc;
     g.nq = g.nt = c->ws.n_kp;
     g.src = c->d_train_src;
-    g.frame_error = c->ws.frame_error;
+    rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
     g.exclude_same_frame = 1;
     g.windows = (const ss_guided_window *)d_windows;
     g.dg = c->ws.dg;
@@ -1939,7 +1957,8 @@ int ss_match_proj_batch_device(ss_ctx *c, const void *d_points, const void *d_po
     g.rows = c->hg.kcap;
     g.points = (const ss_map_point *)d_points, g.p_desc = (const uint8_t *)d_point_desc, g.np = (const int32_t *)d_n_points;
     g.t_kp = c->ws.kps, g.t_desc = c->ws.desc, g.nt = c->ws.n_kp;
-    g.frame_error = c->ws.frame_error;
+    const int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
     g.t_right = (const float *)d_train_right, g.t_taken = (const uint8_t *)d_train_taken;
     proj_outputs(g, d_idx, d_d1, d_d2, d_proj, d_summary);
     return proj_run(c, g, n_blocks, views, point_src, p, c->hg.w, c->hg.h);
@@ -2353,7 +2372,9 @@ int ss_bow_transform_batch_device(ss_ctx *c, int levelsup, void *d_word, void *d
     const bow_keep keep = bow_keep_of(c->d_bow_keep.p, n, kcap);
     ssk_bow_call b;
     b.n_frames = n, b.rows = kcap, b.levelsup = levelsup;
-    b.desc = c->ws.desc, b.n_rows = c->ws.n_kp, b.frame_error = c->ws.frame_error;
+    b.desc = c->ws.desc, b.n_rows = c->ws.n_kp;
+    const int rc1 = flagged_frame_error(c, c->batch_test_flagged, &b.frame_error);
+    if (rc1 != SS_OK) return rc1;
     b.word = (int32_t *)d_word, b.node = (int32_t *)d_node, b.node2 = keep.node;
     b.bow_word = (int32_t *)d_bow_word, b.bow_value = (double *)d_bow_value, b.summary = (ss_bow_summary *)d_summary;
     b.index = keep.index, b.n_index = keep.n_index;
@@ -2447,7 +2468,8 @@ int ss_match_bow_batch_device(ss_ctx *c, const int32_t *train_src, const ss_guid
     g.q_desc = g.t_desc = c->ws.desc;
     g.nq = g.nt = c->ws.n_kp;
     g.src = c->d_train_src;
-    g.frame_error = c->ws.frame_error;
+    rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
     g.exclude_same_frame = 1;
     g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
     g.summary = (ss_guided_summary *)d_summary;

@@ -2,7 +2,10 @@
 
     scenes()           map points = a frame's oracle keypoints back-projected at varied depths, seen under a pose a few pixels away
                        from identity, searched in a train frame of guided_cases (320 x 240, 500 features)
-    boundary_table()   identity pose, exact products: every boundary of steps 1 - 3 taken with np.nextafter on both sides
+    boundary_table()   identity pose, exact products: every boundary of steps 1 - 3 taken with np.nextafter on both sides; over any
+                       pyramid table (PYRAMIDS)
+    edge_table()       projections on and next to the image bounds, windows that reach beyond it, train rows in the border cells
+    count_frames()     point and train counts at 0, 1, 63, 64, 65 and above their row counts, live rows past them
     ratio_frames()     the level-aware acceptance test, a taken row and a right-eye rejection that change the winner
     capacity_frames()  two frames of SS_GUIDED_MAX_ROWS points and train rows
 """
@@ -148,13 +151,26 @@ def around(v):
     return [np.nextafter(v, f32(-np.inf)), v, np.nextafter(v, f32(np.inf))]
 
 
+# the pyramid tables a context can hold besides the default: name -> (scale_factor, n_levels).  ss_create accepts all of them
+# (its geometry check on a nominal 640 x 480 image refuses invalid parameters only)
+PYRAMIDS = {"one_level": (1.2, 1), "two_levels": (1.2, 2), "factor_2": (2.0, 4), "sixteen_levels": (1.1, 16)}
+
+
+def scale_table(scale_factor: float, n_levels: int):
+    """the context's table as include/sendslam_orb.h states it: scale[0] = 1, scale[i] = (float)(scale[i - 1] * (double)factor)"""
+    sc = [f32(1)]
+    for _ in range(1, n_levels):
+        sc.append(f32(float(sc[-1]) * float(f32(scale_factor))))
+    return tuple(sc)
+
+
 @functools.lru_cache(maxsize=None)
-def boundary_table():
+def boundary_table(sc=None):
     """-> (view, points, groups, train keypoints).  Identity pose, principal point 0, image bounds -160 .. 160 x -120 .. 120: with
     x = y = 0 the distance is z and the cosine nz, with z = 1 the projection is 256 * x and the ratio max_dist, all exactly.
     groups: (name, first row, live): three consecutive rows below / on / above a boundary; live False = a boundary the rule makes
-    moot (ratio on the last table entry: both sides give the last level)."""
-    sc = scale()
+    moot (ratio on the last table entry: both sides give the last level).  sc: the pyramid table (None: the default one)."""
+    sc = scale() if sc is None else sc
     view = P.view_init(B_FX, B_FX, 0.0, 0.0, 0, 0, np.eye(3), (0.0, 0.0, 0.0), 16.0)
     view["min_x"], view["max_x"], view["min_y"], view["max_y"] = -160, 160, -120, 120
     rows, groups = [], []
@@ -178,12 +194,14 @@ def boundary_table():
         group(f"ratio on scale[{n}]", "max_dist", sc[n], live=n < len(sc) - 1)
     singles = [_point(max_dist=0.9), _point(max_dist=0.84), _point(max_dist=5.0), _point(max_dist=np.inf), _point(x=np.nan), _point(y=np.inf),
                _point(x=-np.inf), _point(z=np.inf), _point(z=np.inf, max_dist=np.inf), _point(z=np.nan), _point(nx=np.nan),
-               _point(nz=np.inf), _point(min_dist=np.nan), _point(max_dist=np.nan), _point(min_dist=np.inf), _point(z=-1.0)]
+               _point(nz=np.inf), _point(min_dist=np.nan), _point(max_dist=np.nan), _point(min_dist=np.inf), _point(z=-1.0),
+               _point(max_dist=2.0 * float(sc[-1]))]  # ratios below scale[0] = 1 and above the last entry, whatever the table
     points = np.array(rows + singles, P.MAP_POINT_DTYPE)
-    # a handful of train rows: every octave at the principal point, two octaves on each image bound
-    x = [0.0] * 8 + [-160.0, -160.0, 160.0, 160.0, 0.0, 0.0, 0.0, 0.0]
-    y = [0.0] * 8 + [0.0, 0.0, 0.0, 0.0, -120.0, -120.0, 120.0, 120.0]
-    tk = G.kp_rows(x, y, octave=list(range(8)) + [0, 1] * 4)
+    # a handful of train rows: every octave (and one below / above the table) at the principal point, two octaves on each image bound
+    octs = list(range(-1, len(sc) + 1))
+    x = [0.0] * len(octs) + [-160.0, -160.0, 160.0, 160.0, 0.0, 0.0, 0.0, 0.0]
+    y = [0.0] * len(octs) + [0.0, 0.0, 0.0, 0.0, -120.0, -120.0, 120.0, 120.0]
+    tk = G.kp_rows(x, y, octave=octs + [0, min(1, len(sc) - 1)] * 4)
     rng = np.random.Generator(np.random.PCG64(0xB0DE))
     td = rng.integers(0, 256, (len(tk), 32), dtype=np.uint8)
     pd = rng.integers(0, 256, (len(points), 32), dtype=np.uint8)
@@ -279,3 +297,91 @@ def capacity_reference(b: int, one_to_one: bool = True):
     proj, found = capacity_found(b)
     idx, d1, d2, summ, cands = P.finish(found, proj, f["t_kp"], c["th_high"], c["ratio_num"], c["ratio_den"], one_to_one)
     return idx, d1, d2, proj, summ, cands
+
+
+# ---- other grids --------------------------------------------------------------------------------------------------------------
+# the index follows the extent, the answer does not: 256 px cells; 4096 x 1 cells beyond 2^24; a 2 x 2 grid; 157 x 2 cells; one cell;
+# an extent smaller than the keypoints' spread (train rows outside it share the border cells)
+EXTENTS = list(G.CAP_EXTENTS) + [(5000, 37), (1, 1), (100, 80)]
+EXTENT_COMBOS = [dict(ratio=(8, 10), one_to_one=True, th=3.0, check_right=True, taken=True), dict(ratio=(0, 0), one_to_one=False, th=1.0, check_right=False, taken=False)]
+
+
+# ---- windows at the image's edge and beyond -----------------------------------------------------------------------------------
+E_W, E_H = 320, 240
+E_THS = (1.0, 20.0, 300.0, 1e30)  # radii of 4 .. 14 px, 80 .. 290 px, beyond the image on all sides, and as large as th can make them
+
+
+@functools.lru_cache(maxsize=None)
+def edge_table():
+    """-> (view, points, p_desc, train keypoints, t_desc).  Identity pose, fx = fy = 256, principal point (160, 120), z = 1: the
+    projection is 256 * x + 160 exactly.  Points on each image bound and in each corner, one float32 step of x / y inside and
+    outside it (of x / y at the lower bounds, of u / v at the upper ones), at levels 0, 3 and 7; train rows in the first and the last cell of rows and columns, on pixel 0, on the last pixel
+    (319, 239), on the bound (320, 240) and outside the extent on every side, at every octave."""
+    view = P.view_init(B_FX, B_FX, E_W / 2, E_H / 2, E_W, E_H, np.eye(3), (0.0, 0.0, 0.0), BF)
+    sc = scale()
+    # the lower bounds: the float32 steps of x around -160 / 256 (u = -2^-16, 0, 2^-16); the upper bounds: the x that lands on the
+    # float32 steps of u around 320 (a step of x there is half a step of u, and would round onto the bound)
+    xs = around(-160.0 / B_FX) + [f32((float(u) - E_W / 2) / B_FX) for u in around(E_W)] + [f32(0)]
+    ys = around(-120.0 / B_FX) + [f32((float(v) - E_H / 2) / B_FX) for v in around(E_H)] + [f32(0)]
+    rows = []
+    for x in xs:
+        for y in ys:
+            dist = float(np.sqrt(np.float64(x) ** 2 + np.float64(y) ** 2 + 1.0))
+            for level in (0, 3, 7):
+                rows.append(_point(x=x, y=y, max_dist=dist * float(sc[level]) * 0.97, min_dist=0.1))
+    points = np.array(rows, P.MAP_POINT_DTYPE)
+    rng = np.random.Generator(np.random.PCG64(0xED6E))
+    ex = [0.0, 31.0, 32.0, 319.0, 319.0, 0.0, 320.0, 320.0, 319.5, 5.0, 315.0, 160.0, 160.0, 288.0, 0.0, -3.0, 330.0, 160.0, 160.0, 1000.0]
+    ey = [0.0, 0.0, 0.0, 0.0, 239.0, 239.0, 240.0, 120.0, 239.5, 120.0, 120.0, 3.0, 236.0, 224.0, 208.0, 120.0, 120.0, -2.0, 250.0, 1000.0]
+    n_rand = 140
+    tk = G.kp_rows(np.concatenate([np.repeat(ex, 2), rng.integers(-40, (E_W + 40) * 4, n_rand) / 4.0]).astype(np.float32),
+                   np.concatenate([np.repeat(ey, 2), rng.integers(-40, (E_H + 40) * 4, n_rand) / 4.0]).astype(np.float32),
+                   octave=np.concatenate([np.tile([0, 3], len(ex)), rng.integers(-1, 9, n_rand)]))
+    td = rng.integers(0, 256, (len(tk), 32), dtype=np.uint8)
+    pd = rng.integers(0, 256, (len(points), 32), dtype=np.uint8)
+    return view, points, pd, tk, td
+
+
+E_PARAMS = dict(view_cos_limit=0.5, far_limit=0.0, th_high=256, ratio_num=0, ratio_den=0, one_to_one=False, check_right=False)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference(th: float):
+    view, points, pd, tk, td = edge_table()
+    return P.match(view, points, pd, tk, td, scale(), **dict(E_PARAMS, th=th))
+
+
+# ---- a distance of 256 --------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def far_descriptor_frame():
+    """one point whose only candidate holds the complement of its descriptor"""
+    view = P.view_init(B_FX, B_FX, R_U, R_V, G.W, G.H, np.eye(3), (0.0, 0.0, 0.0), BF)
+    pd = np.random.Generator(np.random.PCG64(0xD256)).integers(0, 256, (1, 32), dtype=np.uint8)
+    return {"view": view, "points": np.array([_point(max_dist=1.3)], P.MAP_POINT_DTYPE), "p_desc": pd, "t_kp": G.kp_rows([R_U + 0.5], [R_V - 0.25], octave=2),
+            "t_desc": np.bitwise_xor(pd, np.uint8(255))}
+
+
+# ---- counts -------------------------------------------------------------------------------------------------------------------
+COUNT_ROWS = 65  # point_rows and rows_per_frame: one past the 64 points of a workgroup
+COUNTS = [(0, 65), (1, 65), (63, 65), (64, 65), (65, 65), (65, 0), (65, 1), (65, 63), (65, 64), (0, 0), (1, 1), (70, 65), (65, 1000), (-3, 65), (65, -1),
+          (1 << 30, 1 << 30)]
+
+
+def count_frames():
+    """-> (scene 0 cut to COUNT_ROWS points and train rows, COUNTS): every frame of the call holds ALL the rows, live, whatever its
+    counts say"""
+    s = scenes()[0]
+    n = COUNT_ROWS
+    return {"view": s["view"], "points": s["points"][:n], "p_desc": s["p_desc"][:n], "t_kp": s["t_kp"][:n], "t_desc": s["t_desc"][:n],
+            "right": s["right"][:n], "taken": s["taken"][:n]}, COUNTS
+
+
+COUNT_PARAMS = dict(view_cos_limit=0.5, th=3.0, far_limit=0.0, th_high=100, ratio_num=8, ratio_den=10, one_to_one=True, check_right=True)
+
+
+@functools.lru_cache(maxsize=None)
+def count_reference(n_points: int, n_train: int):
+    f, _ = count_frames()
+    k, nt = min(max(n_points, 0), COUNT_ROWS), min(max(n_train, 0), COUNT_ROWS)
+    return P.match(f["view"], f["points"][:k], f["p_desc"][:k], f["t_kp"][:nt], f["t_desc"][:nt], scale(), right=f["right"][:nt], taken=f["taken"][:nt],
+                   **COUNT_PARAMS)

@@ -8,7 +8,13 @@ import bow_cases as BC
 import bow_ref as B
 import guided_cases as G
 import guided_ref as R
+import proj_cases as PC
+import proj_ref
 from test_guided import Outputs, _check, _extract, _kp
+from test_guided import _params as _guided_params
+from test_guided import _upload as _upload_guided
+from test_proj import Outputs as ProjOutputs
+from test_proj import _upload as _upload_proj
 
 pytestmark = pytest.mark.gpu
 
@@ -143,17 +149,23 @@ def test_batch_transform(batch_ctx, name):
     assert BC.frame_transform(name, "flat", 2)[4]["n_rows"] == 0 and BC.frame_transform(name, "synth_t0", 9)[4]["n_nodes"] == 1
 
 
+def _transform_host(ctx, host, counts, lu):
+    """the device-array form on descriptors [n][rows][32] and counts [n] as the caller holds them"""
+    n, rows = host.shape[:2]
+    d_desc, d_n = _to_dev(host), _to_dev(np.asarray(counts, np.int32))
+    out = Transformed(n, rows)
+    ctx.bow_transform_device(d_desc.data_ptr(), d_n.data_ptr(), n, rows, lu, *out.ptrs())
+    ctx.synchronize()
+    return out.host()
+
+
 def _transform_arrays(ctx, descs, rows, lu):
     """the device-array form on a list of per-frame descriptor arrays"""
     n = len(descs)
     host = np.full((n, rows, 32), 0xA5, np.uint8)  # rows past the count hold a pattern; they must not matter
     for f, d in enumerate(descs):
         host[f, :len(d)] = d
-    d_desc, d_n = _to_dev(host), _to_dev(np.array([len(d) for d in descs], np.int32))
-    out = Transformed(n, rows)
-    ctx.bow_transform_device(d_desc.data_ptr(), d_n.data_ptr(), n, rows, lu, *out.ptrs())
-    ctx.synchronize()
-    return out.host()
+    return _transform_host(ctx, host, [len(d) for d in descs], lu)
 
 
 def test_device_array_form_counts_ties_repeats_and_zero_weights():
@@ -270,6 +282,71 @@ def test_orbvoc_shaped_tree():
     assert 0 < want[4]["n_used"] < 500 and want[4]["n_nodes"] > 50
 
 
+# ---- above 1024 rows: thread t of k_bow_vector owns ceil(n2 / 1024) sorted positions -------------------------------------------
+def _big_frames(name):
+    """-> (descriptors [n][BIG_ROWS][32], counts as given to the device, (rows, count) the reference sees).  Rows past a count stay
+    live (the first frame's own rows) except in the last frame, which holds 0xA5 there."""
+    rows = BC.big_rows()
+    frames = [(rows, BC.BIG_ROWS, BC.BIG_ROWS)]
+    if name == "k4_l8":
+        frames += [(rows, c, c) for c in BC.BIG_COUNTS]
+        frames += [(rows, BC.BIG_ROWS + 3616, BC.BIG_ROWS), (rows, 0, 0), (rows, -7, 0)]  # a count above rows_per_frame is clamped
+        masked = np.full_like(rows, 0xA5)
+        masked[:5000] = rows[:5000]
+        frames.append((masked, 5000, 5000))
+    else:
+        frames += [(np.tile(rows[BC.one_word_index(name)], (BC.BIG_ROWS, 1)), BC.BIG_ROWS, None), (rows, 2049, 2049)]
+    return np.stack([f[0] for f in frames]), [f[1] for f in frames], [f[2] for f in frames]
+
+
+@pytest.mark.parametrize("name,levelsups", [("k4_l8", (2, 9)), ("k10", (2, 0))])
+def test_transform_above_1024_rows(name, levelsups):
+    """SS_BOW_MAX_ROWS rows per frame in the device-array form: many distinct words (k4_l8: more than 8192), long runs that cross
+    the sixteen positions a thread owns (k10), one word 16384 times, counts on both sides of a power of two, clamped counts"""
+    from send_slam_amd import binding
+    voc = BC.big_vocab(name)
+    host, counts, seen = _big_frames(name)
+    with binding.OrbContext(0, n_features=G.NF) as ctx:
+        _set(ctx, voc)
+        for lu in levelsups:
+            got = _transform_host(ctx, host, counts, lu)
+            for f, c in enumerate(seen):
+                want = BC.big_transform(name, lu, c) if c is not None else BC.one_word_transform(name, lu)
+                print(name, "levelsup", lu, "frame", f, "count", counts[f], want[4])
+                _check_transform(f"{name} levelsup {lu} frame {f} (count {counts[f]})", got, f, want)
+                if c is None:  # w added to itself 16383 times, then divided by itself
+                    acc = w = float(voc.weight[BC.big_paths(name)[BC.one_word_index(name)][-1]])
+                    for _ in range(BC.BIG_ROWS - 1):
+                        acc += w
+                    assert want[4]["n_words"] == 1 and want[4]["n_used"] == BC.BIG_ROWS and want[4]["norm"] == acc and want[3][0] == 1.0
+    full = BC.big_transform(name, levelsups[0])
+    if name == "k4_l8":
+        assert full[4]["n_words"] > 8192 and full[4]["n_used"] < full[4]["n_rows"] == BC.BIG_ROWS
+    else:
+        assert BC.longest_run(full[0][full[1] >= 0]) > 16 and full[4]["n_words"] < full[4]["n_used"] / 4
+
+
+@pytest.mark.parametrize("name", list(BC.BOUND_CASES))
+def test_descent_at_the_vocabulary_bounds(name):
+    """k = SS_VOCAB_MAX_K with equal children in one lane's strides and in different lanes, k one past a stride of eight lanes,
+    k = 1, depth SS_VOCAB_MAX_DEPTH, a distance of 256 (tests/test_bow_ref.py asserts what each case reaches)"""
+    from send_slam_amd import binding
+    voc, rows, levelsups = BC.bound_case(name)
+    n = len(rows) + 5
+    with BC.library_vocab(voc) as lv:
+        assert lv.info() == voc.info()
+        with binding.OrbContext(0, n_features=G.NF) as ctx:
+            ctx.set_vocabulary(lv)
+            for lu in levelsups:
+                got = _transform_arrays(ctx, [rows, rows[::-1], rows[:1]], n, lu)
+                want = BC.bound_transform(name, lu)
+                _check_transform(f"{name} levelsup {lu}", got, 0, want)
+                _check_transform(f"{name} levelsup {lu}, one row", got, 2, B.transform_paths(voc, BC.bound_paths(name)[:1], lu))
+                back = B.transform_paths(voc, BC.bound_paths(name)[::-1], lu)  # the same vector from another row order
+                _check_transform(f"{name} levelsup {lu}, rows reversed", got, 1, back)
+                assert np.array_equal(back[2], want[2]) and np.array_equal(B.bits(back[3]), B.bits(want[3]))
+
+
 # ---- SearchByBoW ----------------------------------------------------------------------------------------------------------
 UPSTREAM = dict(th=50, ratio_num=7, ratio_den=10)
 MATCH_RULES = [UPSTREAM, dict(th=100, ratio_num=0, ratio_den=0)]
@@ -337,6 +414,38 @@ def test_batch_match_table_form(transformed_ctx):
         with pytest.raises(binding.OrbError) as e:
             ctx.match_bow_batch_device(binding.guided_params(**combo), *out.ptrs(), train_src=t2)
         assert e.value.code == binding.SS_ERR_INVALID_ARG and "train_src[5]" in e.value.message
+
+
+def test_batch_forms_above_1024_rows():
+    """two frames at 640 x 480 / 2000 features: kp_capacity and the used rows are above the 1024 threads of k_bow_vector; the
+    transform, then the match under both rules with one_to_one on"""
+    from send_slam_amd import binding
+    name, lu = MATCH_VOC, MATCH_LU
+    w, h, nf = BC.WIDE_SIZE
+    with binding.OrbContext(0, n_features=nf, max_batch=len(BC.WIDE)) as ctx:
+        _, kcap = _extract(ctx, list(BC.WIDE), w, h, nf)  # asserts that the extraction is the oracle's
+        assert kcap > 1024
+        _set(ctx, BC.vocab(name))
+        out = Transformed(len(BC.WIDE), kcap)
+        ctx.bow_transform_batch_device(lu, *out.ptrs())
+        ctx.synchronize()
+        got = out.host()
+        for f, frame in enumerate(BC.WIDE):
+            want = BC.wide_transform(name, frame, lu)
+            print(frame, want[4])
+            _check_transform(f"{frame} at {w} x {h}", got, f, want)
+        assert max(BC.wide_transform(name, frame, lu)[4]["n_used"] for frame in BC.WIDE) > 1024
+        for rule in MATCH_RULES:
+            combo = dict(rule, one_to_one=True, orientation=1)
+            m = _outputs(len(BC.WIDE), kcap)
+            ctx.match_bow_batch_device(binding.guided_params(**combo), *m.ptrs())
+            ctx.synchronize()
+            mg = m.host()
+            for b, frame in enumerate(BC.WIDE):
+                want = BC.wide_reference_pair(name, lu, frame, BC.WIDE[b - 1] if b else None, combo)
+                print(b, frame, want[3])
+                _check(f"{frame} at {w} x {h} {G.combo_name(combo)}", mg, b, want)
+            assert want[3]["n_final"] > 100
 
 
 def _upload_pairs(frames, rows):
@@ -520,3 +629,205 @@ def test_scores_of_transformed_frames_rank_the_sequence_first(batch_ctx):
     assert np.array_equal(B.bits(got), B.bits(want)), (got, want)
     print(dict(zip(BC.BATCH, got)))
     assert got[0] > got[BC.BATCH.index("noise")] and got[2] > got[BC.BATCH.index("noise")] and got[BC.BATCH.index("flat")] == 0.0
+
+
+@pytest.mark.parametrize("n_db", BC.SCORE_N_DB)
+def test_score_partial_blocks_and_long_vectors(n_db):
+    """n_db no multiple of the four waves of a block, a query of more than 8192 words against itself and against vectors of 1, 63,
+    64, 65 and 9000 words and vectors sharing only its first or its last word; the scores past n_db stay as they were"""
+    import torch
+    from send_slam_amd import binding
+    qw, qv, db, want = BC.long_score_case()
+    assert len(qw) > 8192 and [len(w) for w, _ in db[1:6]] == [1, 63, 64, 65, 9000]
+    first = len(db) - n_db if n_db > 1 else 0  # n_db 7 scores vectors 1 .. 7, 5: 3 .. 7, ...; n_db 1 the query itself
+    part = db[first:first + n_db]
+    stride = max(len(w) for w, _ in part) + 3
+    dbw, dbv, cnt = np.full((n_db, stride), qw[0], np.int32), np.full((n_db, stride), 0.5), np.zeros(n_db, np.int32)  # past a count: a word of the query
+    for i, (w, v) in enumerate(part):
+        dbw[i, :len(w)], dbv[i, :len(w)], cnt[i] = w, v, len(w)
+    q_rows = len(qw) + 7
+    hq_w, hq_v = np.full(q_rows, qw[-1], np.int32), np.full(q_rows, 0.5)
+    hq_w[:len(qw)], hq_v[:len(qw)] = qw, qv
+    d = [_to_dev(a) for a in (hq_w, hq_v, np.array([len(qw)], np.int32), dbw, dbv, cnt)]
+    score = _filled((n_db + 9,), FILL64, torch.int64)
+    with binding.OrbContext(0, n_features=G.NF) as ctx:
+        ctx.bow_score_device(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), q_rows, d[3].data_ptr(), d[4].data_ptr(), d[5].data_ptr(), n_db, stride,
+                             score.data_ptr())
+        ctx.synchronize()
+    got = score.cpu().numpy().view(np.uint64)
+    exp = B.bits(want[first:first + n_db])
+    assert np.array_equal(got[:n_db], exp), f"n_db {n_db}: {got[:n_db].view(np.float64)} != {want[first:first + n_db]}"
+    assert (got[n_db:] == FILL64).all(), "a score past n_db was written"
+    if first == 0:
+        assert abs(want[0] - 1.0) <= len(qw) * np.finfo(np.float64).eps
+
+
+# ---- stages interleaved on one context ---------------------------------------------------------------------------------------------
+def _raw(out):
+    """every device array of an outputs object, on the host"""
+    import torch
+    return {k: v.cpu().numpy().copy() for k, v in vars(out).items() if isinstance(v, torch.Tensor)}
+
+
+def _interleaved_steps():
+    """-> [(name, alloc() -> outputs object, launch(ctx, outputs))]: calls that share d_guided_ws and the bow workspaces at changing
+    sizes; every device input is uploaded here, every launch only enqueues"""
+    import torch
+    from send_slam_amd import binding
+    (qk, qd), (tk, td) = G.features("synth_t1"), G.features("synth_t0")
+    g_rows = 512
+    g_dev = _upload_guided([{"q_kp": qk, "q_desc": qd, "t_kp": tk, "t_desc": td, "windows": G.own_windows(qk)}], g_rows)
+    g_par = binding.guided_params(th=50, ratio_num=9, ratio_den=10, one_to_one=True, orientation=1, extent_w=G.W, extent_h=G.H)
+    scenes = PC.scenes()
+    p_rows, t_rows = 470, 483
+    p_dev = _upload_proj(scenes, p_rows, t_rows)
+    combo = PC.EXTENT_COMBOS[0]
+    rng = np.random.Generator(np.random.PCG64(0x1C7E))
+    b_frames = [dict(q_kp=qk, q_desc=qd, t_kp=tk, t_desc=td, q_node=rng.integers(-1, 9, len(qk)).astype(np.int32), t_node=rng.integers(-1, 9, len(tk)).astype(np.int32)),
+                dict(q_kp=tk, q_desc=td, t_kp=qk, t_desc=qd, q_node=rng.integers(0, 3, len(tk)).astype(np.int32), t_node=rng.integers(0, 3, len(qk)).astype(np.int32))]
+    b_rows = 600
+    b_dev = _upload_pairs(b_frames, b_rows)
+    b_par = binding.guided_params(**UPSTREAM, one_to_one=True, orientation=2)
+    x_rows = 2100
+    x_host = np.full((3, x_rows, 32), 0xA5, np.uint8)
+    x_host[:, :2049] = BC.big_rows()[:2049]
+    x_dev, x_n = _to_dev(x_host), _to_dev(np.array([2049, 500, 0], np.int32))
+
+    def guided(ctx, out):
+        ctx.match_guided_pairs_device(g_dev["q_desc"].data_ptr(), g_dev["q_kp"].data_ptr(), g_dev["nq"].data_ptr(), g_dev["t_desc"].data_ptr(),
+                                      g_dev["t_kp"].data_ptr(), g_dev["nt"].data_ptr(), g_dev["windows"].data_ptr(), 1, g_rows, g_par, *out.ptrs())
+
+    def proj(extent):
+        def run(ctx, out):
+            ctx.match_proj_pairs_device(p_dev["points"].data_ptr(), p_dev["p_desc"].data_ptr(), p_dev["np"].data_ptr(), len(scenes), p_rows,
+                                        p_dev["t_desc"].data_ptr(), p_dev["t_kp"].data_ptr(), p_dev["nt"].data_ptr(), len(scenes), t_rows, p_dev["views"],
+                                        PC.combo_params(binding, combo, extent_w=extent[0], extent_h=extent[1]), *out.ptrs(),
+                                        d_train_right=p_dev["right"].data_ptr(), d_train_taken=p_dev["taken"].data_ptr())
+        return run
+
+    def bow(ctx, out):
+        ctx.match_bow_pairs_device(b_dev["q_desc"].data_ptr(), b_dev["q_kp"].data_ptr(), b_dev["q_node"].data_ptr(), b_dev["nq"].data_ptr(),
+                                   b_dev["t_desc"].data_ptr(), b_dev["t_kp"].data_ptr(), b_dev["t_node"].data_ptr(), b_dev["nt"].data_ptr(), 2, b_rows, b_par,
+                                   *out.ptrs())
+
+    def transform(ctx, out):
+        ctx.bow_transform_device(x_dev.data_ptr(), x_n.data_ptr(), 3, x_rows, 1, *out.ptrs())
+
+    g_out, p_out, b_out = (lambda: Outputs(1, g_rows)), (lambda: ProjOutputs(len(scenes), p_rows)), (lambda: Outputs(2, b_rows))
+    steps = [("guided", g_out, guided), ("proj 320 x 240", p_out, proj((G.W, G.H))), ("bow pairs", b_out, bow),
+             ("bow transform", lambda: Transformed(3, x_rows), transform), ("guided again", g_out, guided),
+             ("proj 16000 x 12000", p_out, proj(PC.EXTENTS[0])), ("bow pairs again", b_out, bow), ("proj 1 x 1", p_out, proj((1, 1)))]
+    return steps
+
+
+def test_stages_interleaved_on_one_context_equal_the_stages_alone():
+    """guided, projection and bag-of-words calls back to back on one context, no synchronise in between, at sizes that make the
+    shared workspaces grow and then be reused at another layout; twice (the second round grows nothing).  Every output equals what
+    the same call gives alone on a fresh context, and the first proj call equals the reference."""
+    import torch
+    from send_slam_amd import binding
+    steps = _interleaved_steps()
+    voc = BC.vocab("k10")
+    torch.cuda.synchronize()
+    with binding.OrbContext(0, n_features=G.NF) as ctx:
+        _set(ctx, voc)
+        rounds = []
+        for _ in range(2):
+            outs = [alloc() for _, alloc, _ in steps]
+            torch.cuda.synchronize()  # the prefills are complete; from here on the calls only enqueue
+            for (_, _, launch), out in zip(steps, outs):
+                launch(ctx, out)
+            ctx.synchronize()
+            rounds.append([_raw(o) for o in outs])
+    for k, (name, alloc, launch) in enumerate(steps):
+        with binding.OrbContext(0, n_features=G.NF) as ctx:
+            _set(ctx, voc)
+            out = alloc()
+            torch.cuda.synchronize()
+            launch(ctx, out)
+            ctx.synchronize()
+            alone = _raw(out)
+        for r, got in enumerate(rounds):
+            for field, want in alone.items():
+                assert np.array_equal(got[k][field], want), f"round {r}, step {k} ({name}): {field} differs from the call alone"
+    summ = rounds[0][1]["summary"].view(binding.PROJ_SUMMARY_DTYPE).reshape(-1)
+    for k in range(len(PC.SCENES)):
+        want = PC.scene_reference(k, PC.EXTENT_COMBOS[0])
+        assert {f: int(summ[k][f]) for f in proj_ref.SUMMARY_FIELDS} == want[4] and np.array_equal(rounds[0][1]["idx"][k][:len(want[0])], want[0])
+    assert int(rounds[0][0]["summary"].view(binding.GUIDED_SUMMARY_DTYPE)[0]["n_final"][0]) > 50
+    want = BC.big_transform("k10", 1, 2049)
+    assert np.array_equal(rounds[1][3]["bow_word"][0][:len(want[2])], want[2])
+
+
+# ---- flagged frames in the batch forms -----------------------------------------------------------------------------------------------
+FLAG_BATCH = ["synth_t0", "synth_t1", "synth_t2", "synth_t3"]
+FLAG_TABLE = [-1, 0, 3, 0]  # frame 3 against frame 0: a pair the flags leave alone; by default (b - 1) its train frame is flagged
+FLAG_COMBO = dict(th=50, ratio_num=9, ratio_den=10, one_to_one=True, orientation=1)
+FLAG_BOW = dict(UPSTREAM, one_to_one=True, orientation=1)
+
+
+def _flag_run(binding):
+    """the guided, transform and bow-match batch forms on FLAG_BATCH, with the default pairs and with FLAG_TABLE"""
+    with binding.OrbContext(0, n_features=G.NF, max_batch=len(FLAG_BATCH)) as ctx:
+        _, kcap = _extract(ctx, FLAG_BATCH)
+        n = len(FLAG_BATCH)
+        got = {}
+        for key, table in (("guided", None), ("guided_table", FLAG_TABLE)):
+            out = _outputs(n, kcap)
+            ctx.match_guided_batch_device(_guided_params(binding, FLAG_COMBO), *out.ptrs(), train_src=table)
+            ctx.synchronize()
+            got[key] = out.host()
+        _set(ctx, BC.vocab(MATCH_VOC))
+        t = Transformed(n, kcap)
+        ctx.bow_transform_batch_device(MATCH_LU, *t.ptrs())
+        ctx.synchronize()
+        got["transform"] = t.host()
+        for key, table in (("bow", None), ("bow_table", FLAG_TABLE)):
+            out = _outputs(n, kcap)
+            ctx.match_bow_batch_device(binding.guided_params(**FLAG_BOW), *out.ptrs(), train_src=table)
+            ctx.synchronize()  # raises nothing: the extraction's own frame_error is clean
+            got[key] = out.host()
+    return got
+
+
+def test_flagged_frames_void_their_rows_in_the_batch_forms(monkeypatch):
+    """SENDSLAM_TEST_FLAG_BATCH=1,2: frames 1 and 2 are flagged although they have keypoints.  Their summaries carry the status with
+    zero counts, their rows are "none", their vectors empty; a query whose train frame is flagged is voided; everything else is
+    what the unflagged run and the reference give"""
+    from send_slam_amd import binding
+    monkeypatch.delenv("SENDSLAM_TEST_FLAG_BATCH", raising=False)
+    plain = _flag_run(binding)
+    monkeypatch.setenv("SENDSLAM_TEST_FLAG_BATCH", "1,2")
+    flagged = _flag_run(binding)
+    void = lambda want: want[:3] + (dict(want[3], status=binding.SS_ERR_OVERFLOW),)
+    none_g = void(G.reference_pair("flat", None, FLAG_COMBO))
+    none_b = void(BC.reference_pair(MATCH_VOC, MATCH_LU, "flat", None, FLAG_BOW))
+    assert none_g[3]["n_query"] == 0 and len(none_g[0]) == 0
+    for key, table, ref, none in (("guided", None, lambda q, t: G.reference_pair(q, t, FLAG_COMBO), none_g),
+                                  ("guided_table", FLAG_TABLE, lambda q, t: G.reference_pair(q, t, FLAG_COMBO), none_g),
+                                  ("bow", None, lambda q, t: BC.reference_pair(MATCH_VOC, MATCH_LU, q, t, FLAG_BOW), none_b),
+                                  ("bow_table", FLAG_TABLE, lambda q, t: BC.reference_pair(MATCH_VOC, MATCH_LU, q, t, FLAG_BOW), none_b)):
+        kept = 0
+        for b, name in enumerate(FLAG_BATCH):
+            t = (b - 1) if table is None else table[b]
+            want = ref(name, FLAG_BATCH[t] if t >= 0 else None)
+            _check(f"{key}, unflagged, frame {b}", plain[key], b, want)
+            if b in (1, 2) or t in (1, 2):
+                _check(f"{key}, frame {b} voided", flagged[key], b, none)
+                assert want[3]["n_query"] > 100  # it had rows
+            else:
+                _check(f"{key}, flagged run, frame {b}", flagged[key], b, want)
+                assert all(np.array_equal(flagged[key][j][b], plain[key][j][b]) for j in range(3)) and flagged[key][3][b] == plain[key][3][b]
+                kept += want[3]["n_final"]
+        assert kept > 50 if table else kept == 0, key  # by default only frame 0 is left, and it has no train frame
+    voc = BC.vocab(MATCH_VOC)
+    for b, name in enumerate(FLAG_BATCH):
+        want = BC.frame_transform(MATCH_VOC, name, MATCH_LU)
+        _check_transform(f"transform, unflagged, frame {b}", plain["transform"], b, want)
+        if b in (1, 2):
+            empty = B.transform_paths(voc, [], MATCH_LU, status=binding.SS_ERR_OVERFLOW)
+            _check_transform(f"transform, frame {b} flagged", flagged["transform"], b, empty)
+            assert want[4]["n_words"] > 10 and empty[4]["n_rows"] == 0 and empty[4]["norm"] == 0.0
+        else:
+            _check_transform(f"transform, flagged run, frame {b}", flagged["transform"], b, want)
+            assert all(np.array_equal(flagged["transform"][j][b], plain["transform"][j][b]) for j in range(4))

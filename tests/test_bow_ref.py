@@ -79,6 +79,9 @@ MALFORMED = {
     "k_above_bound": "257 2 0 0\n" + _line(0, 1),
     "L_above_bound": "3 33 0 0\n" + _line(0, 1),
     "huge_number": "3 2 0 0\n" + _line(0, 1, desc=[10 ** 12] + [0] * 31),
+    # L within its bound, the tree one level deeper than SS_VOCAB_MAX_DEPTH; k = SS_VOCAB_MAX_K with 257 children of the root
+    "depth_33": "1 32 0 0\n" + "".join(_line(d, int(d == 32)) for d in range(33)),
+    "child_257": "256 1 0 0\n" + _line(0, 1) * 257,
 }
 
 
@@ -104,6 +107,19 @@ def test_missing_file_and_bad_arrays_are_refused():
         with pytest.raises(binding.OrbError) as e:
             binding.Vocabulary.from_arrays(parent, leaf, d, [1.0, 1.0], k, L)
         assert e.value.code == binding.SS_ERR_INVALID_ARG
+    # the bounds themselves pass, one past them does not: k = SS_VOCAB_MAX_K + 1, a chain of depth SS_VOCAB_MAX_DEPTH + 1 under L = 32
+    chain = lambda n: (list(range(n)), [0] * (n - 1) + [1], np.zeros((n, 32), np.uint8), [1.0] * n)
+    with binding.Vocabulary.from_arrays(*chain(32), 1, 32) as lv:
+        assert lv.info()["max_depth"] == 32 == B.Vocab(1, 32, *chain(32)).max_depth
+    with binding.Vocabulary.from_arrays([0] * 256, [1] * 256, np.zeros((256, 32), np.uint8), [1.0] * 256, 256, 1) as lv:
+        assert lv.info()["n_words"] == 256
+    for args in ((*chain(33), 1, 32), ([0] * 2, [1] * 2, d, [1.0] * 2, binding.SS_VOCAB_MAX_K + 1, 1),
+                 ([0] * 257, [1] * 257, np.zeros((257, 32), np.uint8), [1.0] * 257, 256, 1)):
+        with pytest.raises(binding.OrbError) as e:
+            binding.Vocabulary.from_arrays(*args)
+        assert e.value.code == binding.SS_ERR_INVALID_ARG
+        with pytest.raises(ValueError):
+            B.Vocab(args[4], args[5], *args[:4])
     # a short error buffer is filled without overflow, a NULL one is allowed
     lib = binding.load()
     h, err = C.c_void_p(), C.create_string_buffer(b"\x7f" * 16, 16)
@@ -239,3 +255,124 @@ def test_goldens_equal_the_reference(golden_dir):
             assert np.array_equal(word, g[f"lu{lu}_word"]) and np.array_equal(node, g[f"lu{lu}_node"]) and np.array_equal(bw, g[f"lu{lu}_bow_word"])
             assert np.array_equal(B.bits(bv), g[f"lu{lu}_bow_value_bits"]) and B.bits([summ["norm"]])[0] == g[f"lu{lu}_norm_bits"]
         assert np.array_equal(B.bits([B.score(bw, bv, g["other_word"], g["other_value"])]), g["score_bits"])
+
+
+# ---- the limit cases of tests/bow_cases.py reach what they are meant for ----------------------------------------------------------
+def test_big_transforms_give_every_thread_several_positions():
+    """k_bow_vector's thread t owns ceil(n2 / 1024) sorted positions, n2 the count rounded up to a power of two: every count is
+    above 1024, on both sides of a power of two; k4_l8 gives more than 8192 distinct words, k10 runs longer than the 16 positions a
+    thread owns at 16384 rows, and one row repeated gives one run over everything"""
+    assert BC.BIG_ROWS == binding.SS_BOW_MAX_ROWS == 16384 and BC.big_vocab("k4_l8").info() == {"k": 4, "L": 8, "n_nodes": 87380, "n_words": 65536, "max_depth": 8}
+    full = BC.big_transform("k4_l8", 2)
+    print(full[4])
+    assert full[4]["n_words"] > 8192 and full[4]["n_used"] < full[4]["n_rows"] == BC.BIG_ROWS and full[4]["n_nodes"] > 1024
+    assert set(BC.big_transform("k4_l8", 9)[1]) == {0, -1}  # levelsup >= L: the root
+    pow2 = lambda n: 1 << (n - 1).bit_length()
+    assert [pow2(c) for c in BC.BIG_COUNTS] == [2048, 2048, 4096, 8192, 16384] and min(BC.BIG_COUNTS) > 1024
+    for c in BC.BIG_COUNTS:
+        part = BC.big_transform("k4_l8", 2, c)
+        assert c // 2 < part[4]["n_words"] < part[4]["n_used"] < part[4]["n_rows"] == c  # per counts the padded size, not the used rows
+    runs = BC.big_transform("k10", 2)
+    used = runs[0][runs[1] >= 0]
+    per = BC.BIG_ROWS // 1024
+    print(runs[4], "longest run", BC.longest_run(used))
+    assert BC.longest_run(used) > per == 16 and runs[4]["n_words"] < runs[4]["n_used"] / 4
+    one = BC.one_word_transform("k10", 2)
+    assert one[4]["n_words"] == 1 and one[4]["n_used"] == BC.BIG_ROWS and one[3][0] == 1.0
+    w = float(BC.big_vocab("k10").weight[BC.big_paths("k10")[BC.one_word_index("k10")][-1]])
+    assert one[4]["norm"] != w * BC.BIG_ROWS or w * BC.BIG_ROWS == sum([w] * BC.BIG_ROWS)
+
+
+@pytest.mark.parametrize("name", list(BC.BOUND_CASES))
+def test_library_links_the_bound_vocabularies_as_the_reference_does(name):
+    voc = BC.bound_case(name)[0]
+    with BC.library_vocab(voc) as lv:
+        _same_tree(lv, voc)
+        if name == "spine32":
+            assert lv.info()["max_depth"] == 32
+
+
+def _ordinals(voc, path):
+    """the child ordinal taken at every step of a path"""
+    out, cur = [], 0
+    for nd in path:
+        out.append(voc.children[cur].index(nd))
+        cur = nd
+    return out
+
+
+def _dist(a, b) -> int:
+    return int(R.distances(np.asarray(a, np.uint8).reshape(1, 32), np.asarray(b, np.uint8).reshape(1, 32))[0, 0])
+
+
+@pytest.mark.parametrize("L", (1, 2))
+def test_k256_cases_reach_ordinal_255_both_tie_placements_and_distance_256(L):
+    voc, rows = BC.k256_vocab(L), BC.k256_rows(L)
+    assert voc.k == binding.SS_VOCAB_MAX_K == 256 and len(voc.children[0]) == 256 and voc.max_depth == L
+    paths = BC.bound_paths(f"k256_l{L}")
+    first = [_ordinals(voc, p)[0] for p in paths]
+    assert 255 in first and max(first) == 255
+    top = voc.children[0]
+    for pairs, same_lane in ((BC.K256_SAME_LANE, True), (BC.K256_OTHER_LANE, False)):
+        for a, b in pairs:
+            assert a < b and ((b - a) % 8 == 0) == same_lane and voc.desc[top[a]].tobytes() == voc.desc[top[b]].tobytes()
+            assert first[b] == a and first[a] == a, "the row equal to both children goes to the earlier one"  # rows 0 .. 255 are the children
+    assert any(a % 8 > b % 8 for a, b in BC.K256_OTHER_LANE)  # the earlier child in a later lane
+    # the complement of a child is 256 from it
+    assert _dist(rows[256], voc.desc[top[0]]) == 256
+    if L == 2:
+        assert [len(voc.children[c + 1]) for c in BC.K256_INNER] == [256] * len(BC.K256_INNER)
+        second = [_ordinals(voc, p) for p in paths if len(p) == 2]
+        assert any(o == [255, 255] for o in second) and any(o[0] == 3 and o[1] > 127 for o in second)
+        for a, b in BC.K256_SAME_LANE + BC.K256_OTHER_LANE:  # the same placements one level down
+            assert [255, a] in second and [255, b] not in second
+        # under root child 0 all 256 children are one descriptor: ordinal 0 wins
+        under0 = voc.desc[voc.children[1][0]]
+        hits = [(r, p) for r, p in zip(rows, paths) if len(p) == 2 and p[0] == top[0]]
+        assert {_dist(r, under0) for r, p in hits} >= {0, 8} and all(_ordinals(voc, p) == [0, 0] for r, p in hits)
+        depth1 = [p for p in paths if len(p) == 1]
+        assert len(depth1) > 100  # leaves shallower than L
+
+
+def test_small_bound_cases_reach_one_past_a_stride_a_chain_and_depth_32():
+    voc, rows, _ = BC.bound_case("k256_one")  # a winning distance of 256 among 256 children
+    assert _dist(rows[1], voc.desc[1]) == 256 and _dist(rows[1], voc.desc[256]) == 256 and set(BC.bound_transform("k256_one", 0)[0]) == {0}
+    for name, k in (("k9", 9), ("k17", 17)):
+        voc, rows, _ = BC.bound_case(name)
+        ords = [o for p in BC.bound_paths(name) for o in _ordinals(voc, p)]
+        assert voc.k == k and max(len(c) for c in voc.children) == k and max(ords) == k - 1 and {8} <= set(ords), name
+        dup = [p for p in range(voc.n_nodes + 1) if len(voc.children[p]) > len(set(voc.desc[c].tobytes() for c in voc.children[p]))]
+        assert dup, name
+    voc, rows, lus = BC.bound_case("k1_chain")
+    assert voc.k == 1 and voc.n_words == 1 and voc.max_depth == 5 and all(len(p) == 5 for p in BC.bound_paths("k1_chain"))
+    assert any(_dist(r, voc.desc[1]) == 256 for r in rows)  # the only child, as far as a descriptor can be
+    for lu, node in ((0, 5), (1, 4), (5, 0)):
+        assert set(BC.bound_transform("k1_chain", lu)[1]) == {node}
+    voc, rows, lus = BC.bound_case("spine32")
+    assert voc.info()["max_depth"] == 32 == binding.SS_VOCAB_MAX_DEPTH == voc.L and voc.n_nodes == 64
+    paths = BC.bound_paths("spine32")
+    assert [len(p) for p in paths[:len(BC.SPINE_DEPTHS)]] == list(BC.SPINE_DEPTHS)
+    assert {len(p) for p in paths} == set(range(1, 33)) and lus == (0, 1, 16, 31, 32, 40)
+    for i, d in enumerate(BC.SPINE_DEPTHS):  # the row's node at depth L - levelsup: its own leaf where the path is shorter
+        for lu in lus:
+            target = 32 - lu
+            want = 0 if target <= 0 else paths[i][min(target, d) - 1]
+            assert BC.bound_transform("spine32", lu)[1][i] == want
+    ties = [p for r, p in zip(rows, paths) if r.sum() == 0x0F and (r != 0).sum() == 1]
+    assert len(ties) == 6 and {len(p) for p in ties} == {1, 15, 31, 32}  # odd depths: the leaf first; even: on down the spine
+    assert (BC.bound_transform("spine32", 0)[1] == -1).sum() >= 2  # the leaves of weight 0.0
+
+
+def test_wide_batch_and_long_score_cases():
+    used = [BC.wide_transform("cluster", f, 1)[4]["n_used"] for f in BC.WIDE]
+    print("used rows at 640 x 480 / 2000:", used, [len(BC.wide_features(f)[0]) for f in BC.WIDE])
+    assert max(used) > 1024
+    combo = dict(th=50, ratio_num=7, ratio_den=10, one_to_one=True, orientation=1)
+    assert BC.wide_reference_pair("cluster", 1, BC.WIDE[1], BC.WIDE[0], combo)[3]["n_final"] > 100
+    qw, qv, db, want = BC.long_score_case()
+    assert len(qw) > 8192 and [len(w) for w, _ in db] == [len(qw), 1, 63, 64, 65, 9000, 201, 201]
+    assert abs(want[0] - 1.0) <= len(qw) * np.finfo(np.float64).eps and (want[1:] > 0).all() and (want[1:] < 1).all()
+    for (w, v), word in ((db[6], qw[0]), (db[7], qw[-1])):
+        assert set(w) & set(qw) == {word} and (np.diff(w) > 0).all()
+    assert len(set(db[5][0]) & set(qw)) == 4500 and (np.diff(db[5][0]) > 0).all()
+    assert all(n % 4 != 0 for n in BC.SCORE_N_DB)

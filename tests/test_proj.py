@@ -63,7 +63,8 @@ def _check(tag, got, b, want):
 
 
 def _upload(frames, point_rows, rows):
-    """frames: dicts view points p_desc t_kp t_desc [right] [taken] -> device arrays of the pairs form, block b = frame b"""
+    """frames: dicts view points p_desc t_kp t_desc [right] [taken] -> device arrays of the pairs form, block b = frame b;
+    [n_points] [n_train]: the counts the device is told, where they are not the lengths of the arrays"""
     from send_slam_amd import binding
     n = len(frames)
     host = {"points": np.zeros((n, point_rows), binding.MAP_POINT_DTYPE), "p_desc": np.zeros((n, point_rows, 32), np.uint8),
@@ -71,7 +72,7 @@ def _upload(frames, point_rows, rows):
             "taken": np.zeros((n, rows), np.uint8), "np": np.zeros(n, np.int32), "nt": np.zeros(n, np.int32)}
     for b, f in enumerate(frames):
         k, nt = len(f["points"]), len(f["t_kp"])
-        host["np"][b], host["nt"][b] = k, nt
+        host["np"][b], host["nt"][b] = f.get("n_points", k), f.get("n_train", nt)
         host["points"][b, :k], host["p_desc"][b, :k] = f["points"], f["p_desc"]
         host["t_desc"][b, :nt], host["t_kp"][b, :nt] = f["t_desc"], f["t_kp"]
         if "right" in f:
@@ -101,27 +102,44 @@ def ctx():
         yield c
 
 
-def test_boundary_table(ctx):
-    """identity pose, exact products: z at 0, u / v on each image bound, dist on 0.8f * min_dist, 1.2f * max_dist and far_limit,
-    view_cos on the limit and on 0.998, the ratio on every scale[n], each with np.nextafter on both sides; NaN and infinite
-    coordinates; ratios below 1 and above the last entry"""
+def _boundary_table_on(c, sc, tag):
+    """the boundary table of a pyramid table through the pairs form and the host twin of a context that holds that table"""
     from send_slam_amd import binding
-    view, points, groups, tk, td, pd = PC.boundary_table()
-    sc = PC.scale()
+    view, points, groups, tk, td, pd = PC.boundary_table(sc)
     want = P.match(view, points, pd, tk, td, sc, th_high=256, ratio_num=0, ratio_den=0, **PC.B_LIMITS)
     proj = want[3]
     for name, a, live in groups:  # every case is live, on the reference
         rows = {(int(proj["state"][i]), int(proj["level"][i]), float(proj["radius"][i])) for i in range(a, a + 3)}
-        assert (len(rows) > 1) == live, (name, rows)
-    assert want[4]["n_candidates"] > 20 and want[4]["n_accepted"] > 10
+        assert (len(rows) > 1) == live, (tag, name, rows)
     frame = {"view": view, "points": points, "p_desc": pd, "t_kp": tk, "t_desc": td}
     point_rows, rows = len(points) + 3, len(tk) + 1
     dev = _upload([frame], point_rows, rows)
     p = binding.proj_params(th_high=256, ratio_num=0, ratio_den=0, extent_w=G.W, extent_h=G.H, **PC.B_LIMITS)
-    _check("boundary table", _run_pairs(ctx, dev, 1, point_rows, rows, p, taken=False, right=False), 0, want)
-    # and the host twin on the device's projections
+    _check(tag, _run_pairs(c, dev, 1, point_rows, rows, p, taken=False, right=False), 0, want)
     got = binding.proj_points_host(view, p, sc, points)
-    assert got.tobytes() == proj.tobytes()
+    assert got.tobytes() == proj.tobytes(), tag
+    return want
+
+
+@pytest.mark.parametrize("name", list(PC.PYRAMIDS))
+def test_boundary_table_under_other_pyramid_tables(name):
+    """contexts with one level (octaves -1 .. 0 only), two levels, a scale factor of 2 and SS_MAX_LEVELS levels: the ratio on
+    every scale[n] with np.nextafter on both sides, ratios below scale[0] and above the last entry"""
+    from send_slam_amd import binding
+    factor, n_levels = PC.PYRAMIDS[name]
+    sc = PC.scale_table(factor, n_levels)
+    with binding.OrbContext(0, n_features=G.NF, scale_factor=factor, n_levels=n_levels) as c:
+        want = _boundary_table_on(c, sc, name)
+    levels = set(int(v) for v in want[3]["level"][want[3]["state"] == 0])
+    assert levels == set(range(n_levels)) and want[4]["n_accepted"] > 10, (name, levels)
+
+
+def test_boundary_table(ctx):
+    """identity pose, exact products: z at 0, u / v on each image bound, dist on 0.8f * min_dist, 1.2f * max_dist and far_limit,
+    view_cos on the limit and on 0.998, the ratio on every scale[n], each with np.nextafter on both sides; NaN and infinite
+    coordinates; ratios below 1 and above the last entry"""
+    want = _boundary_table_on(ctx, PC.scale(), "boundary table")
+    assert want[4]["n_candidates"] > 20 and want[4]["n_accepted"] > 10
 
 
 def test_level_aware_ratio_taken_row_and_right_eye(ctx):
@@ -298,3 +316,117 @@ def test_full_capacity(ctx):
         print(b, want[4])
         _check(f"capacity frame {b}", got, b, want)
         assert (want[0] >= 8192).sum() > 1000
+
+
+# ---- other grids, the image's edge, counts --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("combo", PC.EXTENT_COMBOS, ids=PC.combo_name)
+@pytest.mark.parametrize("extent", PC.EXTENTS, ids=lambda e: f"{e[0]}x{e[1]}")
+def test_scenes_on_other_grids(ctx, scene_arrays, extent, combo):
+    """the extent sizes the index and never the answer: 256 px cells, 4096 x 1 cells, an extent beyond 2^24, 157 x 2 cells, one
+    cell, extents smaller than the keypoints' spread"""
+    from send_slam_amd import binding
+    dev, point_rows, rows = scene_arrays
+    n = len(PC.SCENES)
+    got = _run_pairs(ctx, dev, n, point_rows, rows, PC.combo_params(binding, combo, extent_w=extent[0], extent_h=extent[1]), taken=combo["taken"],
+                     right=combo["check_right"])
+    for k in range(n):
+        _check(f"scene {k} {PC.combo_name(combo)} on {extent}", got, k, PC.scene_reference(k, combo))
+    assert sum(s["n_accepted"] for s in got[4]) > 100
+
+
+@pytest.mark.parametrize("extent", [(PC.E_W, PC.E_H), (64, 64), (1 << 25, 1 << 25)], ids=lambda e: f"{e[0]}x{e[1]}")
+def test_windows_at_the_edge_of_the_image_and_beyond(ctx, extent):
+    """projections on each image bound and one float32 step inside and outside it, radii from 4 px to 4e30 px, train rows in the
+    border cells, on the last pixel, on the bound and outside the extent"""
+    from send_slam_amd import binding
+    view, points, pd, tk, td = PC.edge_table()
+    frame = {"view": view, "points": points, "p_desc": pd, "t_kp": tk, "t_desc": td}
+    point_rows, rows = len(points) + 2, len(tk) + 5
+    dev = _upload([frame], point_rows, rows)
+    for th in PC.E_THS:
+        want = PC.edge_reference(th)
+        p = binding.proj_params(extent_w=extent[0], extent_h=extent[1], **dict(PC.E_PARAMS, th=th))
+        got = _run_pairs(ctx, dev, 1, point_rows, rows, p, taken=False, right=False)
+        print(th, want[4])
+        _check(f"edge table, th {th}, extent {extent}", got, 0, want)
+        assert binding.proj_points_host(view, p, PC.scale(), points).tobytes() == want[3].tobytes()
+
+
+def test_a_distance_of_256_is_accepted_at_th_high_256_only(ctx):
+    from send_slam_amd import binding
+    f = PC.far_descriptor_frame()
+    dev = _upload([f], 2, 3)
+    for th_high, idx in ((256, 0), (255, -1)):
+        kw = dict(PC.RATIO_PARAMS, th_high=th_high, check_right=False)
+        want = P.match(f["view"], f["points"], f["p_desc"], f["t_kp"], f["t_desc"], PC.scale(), **kw)
+        assert want[0][0] == idx and want[1][0] == 256 and want[4]["n_candidates"] == 1
+        got = _run_pairs(ctx, dev, 1, 2, 3, binding.proj_params(extent_w=G.W, extent_h=G.H, **kw), taken=False, right=False)
+        _check(f"th_high {th_high}", got, 0, want)
+        assert got[0][0][0] == idx and got[1][0][0] == 256
+
+
+def test_counts_at_zero_one_a_workgroup_and_above_the_rows(ctx):
+    """one call, every frame holds the same 65 live points and train rows; only the counts differ: 0, 1, 63, 64, 65, above the row
+    counts (clamped) and negative (0)"""
+    from send_slam_amd import binding
+    base, counts = PC.count_frames()
+    frames = [dict(base, n_points=k, n_train=nt) for k, nt in counts]
+    rows = PC.COUNT_ROWS
+    dev = _upload(frames, rows, rows)
+    got = _run_pairs(ctx, dev, len(frames), rows, rows, binding.proj_params(extent_w=G.W, extent_h=G.H, **PC.COUNT_PARAMS))
+    for b, (k, nt) in enumerate(counts):
+        _check(f"counts {k} / {nt}", got, b, PC.count_reference(k, nt))
+    assert PC.count_reference(65, 65)[4]["n_unique"] > 30
+
+
+FLAG_BATCH = ["synth_t0", "synth_t1", "synth_t2", "synth_t3"]
+
+
+def _flag_run(binding, combo):
+    """the batch form on FLAG_BATCH: every frame searches the map points of scene 0 under scene 0's view"""
+    import torch
+    s0 = PC.scenes()[0]
+    frames = np.stack([G.frame(n) for n in FLAG_BATCH])
+    n = len(FLAG_BATCH)
+    views = np.concatenate([np.asarray(s0["view"]).reshape(1)] * n)
+    with binding.OrbContext(0, n_features=G.NF, max_batch=n) as c:
+        d = torch.from_numpy(frames).to(_dev())
+        c.extract_batch_device(d.data_ptr(), n, G.W, G.H)
+        c.synchronize()
+        for b, name in enumerate(FLAG_BATCH):  # the references are computed on the oracle's features
+            kp, desc, _ = c.fetch_frame(b)
+            okp, odesc = G.features(name)
+            assert kp.tobytes() == okp.tobytes() and np.array_equal(desc, odesc), f"frame {b} ({name}): extraction differs from the oracle"
+        point_rows = 470
+        dev = _upload([dict(s0, t_kp=s0["t_kp"][:0], t_desc=s0["t_desc"][:0], right=s0["right"][:0], taken=s0["taken"][:0])], point_rows, 1)
+        out = Outputs(n, point_rows)
+        torch.cuda.synchronize()
+        c.match_proj_batch_device(dev["points"].data_ptr(), dev["p_desc"].data_ptr(), dev["np"].data_ptr(), 1, point_rows, views,
+                                  PC.combo_params(binding, combo), *out.ptrs(), point_src=[0] * n)
+        c.synchronize()  # raises nothing: the extraction's own frame_error is clean
+        return out.host()
+
+
+def test_flagged_frames_are_voided_in_the_batch_form(monkeypatch):
+    """SENDSLAM_TEST_FLAG_BATCH=1,2: frames 1 and 2 are flagged although they have keypoints: status, zero counts, every row "none";
+    frames 0 and 3 are what the unflagged run and the reference give"""
+    from send_slam_amd import binding
+    combo = dict(ratio=(8, 10), one_to_one=True, th=3.0, check_right=False, taken=False)
+    monkeypatch.delenv("SENDSLAM_TEST_FLAG_BATCH", raising=False)
+    plain = _flag_run(binding, combo)
+    monkeypatch.setenv("SENDSLAM_TEST_FLAG_BATCH", "1,2")
+    flagged = _flag_run(binding, combo)
+    s0 = PC.scenes()[0]
+    kw = dict(th=combo["th"], ratio_num=combo["ratio"][0], ratio_den=combo["ratio"][1], one_to_one=True)
+    for b, name in enumerate(FLAG_BATCH):
+        tk, td = G.features(name)
+        want = P.match(s0["view"], s0["points"], s0["p_desc"], tk, td, PC.scale(), **kw)
+        _check(f"unflagged, frame {b}", plain, b, want)
+        assert want[4]["n_train"] > 100 and want[4]["n_in_view"] > 100
+        if b in (1, 2):
+            none = P.match(s0["view"], s0["points"][:0], s0["p_desc"][:0], tk[:0], td[:0], PC.scale(), **kw)
+            _check(f"frame {b} flagged", flagged, b, none[:4] + (dict(none[4], status=binding.SS_ERR_OVERFLOW),))
+        else:
+            _check(f"flagged run, frame {b}", flagged, b, want)
+            assert all(np.array_equal(flagged[j][b], plain[j][b]) for j in range(3)) and flagged[3][b].tobytes() == plain[3][b].tobytes()
+            assert want[4]["n_unique"] > (50 if b == 0 else 0)

@@ -265,3 +265,84 @@ def test_capacity_frames_need_both_conflict_passes():
         assert (contested >= 8192).sum() > 500 and summ["n_unique"] < summ["n_accepted"] - 1000
         if b == 0:
             assert (contested < 8192).sum() > 500
+
+
+# ---- the limit cases of tests/proj_cases.py reach what they are meant for ---------------------------------------------------------
+def test_scale_table_is_the_context_table_and_other_tables_are_live():
+    assert PC.scale_table(1.2, 8) == tuple(PC.scale())
+    assert set(PC.PYRAMIDS.values()) == {(1.2, 1), (1.2, 2), (2.0, 4), (1.1, binding.SS_MAX_LEVELS)}
+    for name, (factor, n) in PC.PYRAMIDS.items():
+        sc = PC.scale_table(factor, n)
+        assert len(sc) == n and sc[0] == 1 and all(a < b for a, b in zip(sc, sc[1:]))
+        view, points, groups, tk, td, pd = PC.boundary_table(sc)
+        p = binding.proj_params(**PC.B_LIMITS)
+        proj = P.eval_points(view, points, **PC.B_LIMITS, scale=sc)
+        _same(binding.proj_points_host(view, p, sc, points), proj, name)
+        for g, a, live in groups:
+            rows = [(int(proj["state"][i]), int(proj["level"][i]), float(proj["radius"][i])) for i in range(a, a + 3)]
+            assert (len(set(rows)) > 1) == live, (name, g, rows)
+        ratio = [g for g, _, _ in groups if g.startswith("ratio on")]
+        assert len(ratio) == n and sum(1 for _, _, live in groups if not live) == 1
+        seen = set(int(v) for v in proj["level"][proj["state"] == 0])
+        assert seen == set(range(n)), (name, seen)
+        # a ratio below scale[0] gives level 0, one above the last entry the last level; the window takes octaves level - 1 .. level
+        below, above = proj[len(points) - 17], proj[len(points) - 1]
+        assert below["state"] == 0 and below["level"] == 0 and above["state"] == 0 and above["level"] == n - 1
+        want = P.match(view, points, pd, tk, td, sc, th_high=256, ratio_num=0, ratio_den=0, **PC.B_LIMITS)
+        octs = {int(tk["octave"][j]) for c in want[5] for j in c}
+        assert octs == set(range(-1, n)), (name, octs)  # octave -1 is a candidate of level 0, octave n of nobody
+    assert tuple(PC.scale_table(2.0, 4)) == (1, 2, 4, 8)
+
+
+def test_other_grids_are_the_documented_ones():
+    shapes = []
+    for w, h in PC.EXTENTS:
+        s = G.grid_shift(w, h)
+        shapes.append((s, ((min(w, G.CAP_FAR) - 1) >> s) + 1, ((min(h, G.CAP_FAR) - 1) >> s) + 1))
+    print(shapes)
+    assert shapes == [(8, 63, 47), (12, 4096, 1), (5, 2, 2), (5, 157, 2), (5, 1, 1), (5, 4, 3)]
+    spread = np.concatenate([s["t_kp"]["x"] for s in PC.scenes()]).max(), np.concatenate([s["t_kp"]["y"] for s in PC.scenes()]).max()
+    assert spread[0] > 200 and spread[1] > 160  # train rows lie outside 100 x 80, 33 x 33 and 1 x 1
+    assert any(c["one_to_one"] and c["check_right"] and c["taken"] for c in PC.EXTENT_COMBOS) and len(PC.EXTENT_COMBOS) >= 2
+
+
+def test_edge_table_windows_reach_beyond_the_image_and_hold_every_row():
+    view, points, pd, tk, td = PC.edge_table()
+    assert float(view["max_x"]) == PC.E_W and float(view["max_y"]) == PC.E_H
+    small, huge = PC.edge_reference(PC.E_THS[0]), PC.edge_reference(PC.E_THS[-1])
+    proj = small[3]
+    ok = proj["state"] == 0
+    for name, lo, hi in (("u", 0, PC.E_W), ("v", 0, PC.E_H)):  # on each bound, and one step inside it
+        vals = set(float(v) for v in proj[name][ok])
+        assert {float(lo), float(hi), float(np.nextafter(f32(hi), f32(0)))} <= vals and 0 < min(vals - {float(lo)}) < 2.0 ** -15, (name, sorted(vals))
+    assert (proj["state"] == 2).sum() == len(points) - ok.sum() > 30  # one step outside
+    sides = lambda p: sum(c.astype(int) for c in (p["u"] - p["radius"] < 0, p["u"] + p["radius"] > PC.E_W, p["v"] - p["radius"] < 0, p["v"] + p["radius"] > PC.E_H))
+    assert {1, 2} <= set(int(v) for v in sides(small[3][ok]))
+    assert set(int(v) for v in sides(PC.edge_reference(PC.E_THS[2])[3][ok])) == {4}
+    # th = 1e30: the window holds every train row; the candidates are the rows of the two octaves
+    assert np.isfinite(huge[3]["radius"][ok]).all() and huge[3]["radius"][ok].min() > 1e30
+    for i in np.flatnonzero(ok):
+        lvl = int(huge[3]["level"][i])
+        assert huge[5][i] == [j for j in range(len(tk)) if lvl - 1 <= tk["octave"][j] <= lvl], i
+    assert huge[4]["n_candidates"] > PC.edge_reference(PC.E_THS[2])[4]["n_candidates"]
+    kx, ky = tk["x"], tk["y"]
+    assert ((kx == 319) & (ky == 239)).any() and ((kx == 0) & (ky == 0)).any() and ((kx == 320) & (ky == 240)).any()
+    assert (kx < 0).any() and (kx > PC.E_W).any() and (ky < 0).any() and (ky > PC.E_H).any()
+    used = {j for c in small[5] for j in c}
+    assert {j for j in range(len(tk)) if kx[j] in (0, 319, 320) or ky[j] in (0, 239, 240)} & used  # border rows are candidates
+
+
+def test_far_descriptor_and_count_cases():
+    f = PC.far_descriptor_frame()
+    kw = dict(PC.RATIO_PARAMS, check_right=False)
+    for th_high, idx in ((256, 0), (255, -1)):
+        got = P.match(f["view"], f["points"], f["p_desc"], f["t_kp"], f["t_desc"], PC.scale(), **dict(kw, th_high=th_high))
+        assert got[0][0] == idx and got[1][0] == 256 and got[2][0] == P.NONE
+    base, counts = PC.count_frames()
+    assert len(base["points"]) == len(base["t_kp"]) == PC.COUNT_ROWS == 65
+    assert {0, 1, 63, 64, 65} <= {k for k, _ in counts} and {0, 1, 63, 64, 65} <= {nt for _, nt in counts}
+    assert any(k > 65 for k, _ in counts) and any(nt > 65 for _, nt in counts)
+    full = PC.count_reference(65, 65)
+    assert full[4]["n_unique"] < full[4]["n_accepted"] and full[4]["n_candidates"] > 100
+    assert PC.count_reference(64, 65)[4] != full[4] != PC.count_reference(65, 64)[4]  # the 65th row of either side matters
+    assert PC.count_reference(70, 1 << 30)[4] == full[4]

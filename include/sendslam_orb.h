@@ -726,6 +726,165 @@ int ss_match_proj(ss_ctx *ctx, const ss_proj_view *view, const ss_map_point *poi
                   const uint8_t *train_taken, const ss_proj_params *p, int32_t *idx, uint16_t *d1, uint16_t *d2,
                   ss_proj_point *proj, ss_proj_summary *summary);
 
+/* ---- epipolar search and triangulation: ORBmatcher::SearchForTriangulation, then the per-match part of
+ * LocalMapping::CreateNewMapPoints with MapPoint::UpdateNormalAndDepth: new map points from (keyframe 1 = query, keyframe 2 =
+ * train) pairs.  Neither upstream source is in the reference tree.  This is the library's own restatement and parity with the real
+ * binary stays unpinned, as for the guided, bag-of-words and projection stages.  tests/epi_ref.py is its normative statement;
+ * DESIGN.md section 18.  An addition to ABI 5: nothing existing changes ---------------------------------------------------------
+ * Out of scope: stereo rows (bOnlyStereo, stereo parallax, unprojectStereo: a row with a right coordinate is treated as monocular),
+ * fisheye models (pinhole only; keypoints are taken as undistorted, upstream's mvKeysUn: k1 k2 p1 p2 are not read), the per-pair
+ * baseline / median-depth gate of CreateNewMapPoints (the caller decides which pairs to submit), Fuse, culling, the observations
+ * bookkeeping and any wiring into ss_track.
+ * The pair.  One ss_epi_pair per pair, made on the host by ss_epi_pair_init, handed to the device calls as a HOST table that is
+ * copied before the call returns.  It has a float32 part for the search and a double part for the triangulation.
+ *   Float32 part.  All of it is formed in double, one IEEE operation per step, then rounded once:
+ *   - R12[i][j] = (R1[i][0]*R2[j][0] + R1[i][1]*R2[j][1]) + R1[i][2]*R2[j][2]           (R12 = R1w.R2w^T)
+ *   - t12[i] = t1[i] - ((R12[i][0]*t2[0] + R12[i][1]*t2[1]) + R12[i][2]*t2[2])
+ *   - E = [t12]x.R12: E[0][j] = t12[1]*R12[2][j] - t12[2]*R12[1][j], E[1][j] = t12[2]*R12[0][j] - t12[0]*R12[2][j],
+ *     E[2][j] = t12[0]*R12[1][j] - t12[1]*R12[0][j]
+ *   - G = K1^-T.E: G[0][j] = invfx1*E[0][j], G[1][j] = invfy1*E[1][j], G[2][j] = E[2][j] - (cx1*G[0][j] + cy1*G[1][j])
+ *   - F = G.K2^-1: F[i][0] = G[i][0]*invfx2, F[i][1] = G[i][1]*invfy2, F[i][2] = G[i][2] - (F[i][0]*cx2 + F[i][1]*cy2)
+ *   - f12[3*i + j] = (float)(F[i][j] / m), m the largest |F[i][j]|.  If an entry is not finite or m is 0, f12 is all 0.0f and the
+ *     epipolar test fails for every couple (den > 0 is false).  Deviation: upstream does not normalise; the test is scale-free in
+ *     exact arithmetic, and the division keeps a*a + b*b away from float32 underflow for short baselines.
+ *   - The epipole of camera 1 in image 2: C2[i] = ((R2[i][0]*ow1[0] + R2[i][1]*ow1[1]) + R2[i][2]*ow1[2]) + t2[i];
+ *     ex = (float)((fx2*C2[0])/C2[2] + cx2), ey = (float)((fy2*C2[1])/C2[2] + cy2).  epipole_test is 1 iff both are finite after the
+ *     rounding; else it is 0, ex = ey = 0.0f are stored and the epipole test is skipped (sideways motion has its epipole at
+ *     infinity, no keypoint is near it).
+ *   Double part.  rcw, tcw as given, ow[k] = -((r[k]*t[0] + r[3+k]*t[1]) + r[6+k]*t[2]) as in ss_proj_view_init, then
+ *   fx, fy, cx, cy, 1.0/fx, 1.0/fy of each camera.
+ * The search, for query row i.  The row is live iff i < n_query, node_i >= 0 and it is not taken.  A candidate is a train row
+ *   j < n_train, not taken, with node_j == node_i (a VISITED couple).  scale[] is the context's pyramid table, n_levels entries,
+ *   sigma2[n] = scale[n]*scale[n] in float32.  Every float step is one float32 operation, left to right, no contraction; every test
+ *   is in its accepting form, so a NaN fails it.  A candidate must pass, in this order:
+ *   1. Octave: 0 <= octave_j < n_levels (caller-made keypoints may violate it; such a row is no candidate).
+ *   2. Epipole, only when epipole_test: dx = ex - x_j, dy = ey - y_j; accept iff dx*dx + dy*dy >= 100.0f * scale[octave_j]
+ *      (upstream rejects <).
+ *   3. Epipolar line, unless coarse: a = (x_i*f[0] + y_i*f[3]) + f[6], b = (x_i*f[1] + y_i*f[4]) + f[7],
+ *      c = (x_i*f[2] + y_i*f[5]) + f[8]; num = (a*x_j + b*y_j) + c; den = a*a + b*b; accept iff den > 0.0f and
+ *      num*num/den < 3.84f * sigma2[octave_j].  Deviation: upstream evaluates the right-hand side in double.
+ *   4. Distance: Hamming <= th.
+ *   The best is the lowest key distance << 20 | j; idx and d1 come from it; there is no second best and no ratio test.
+ *   Deviation: upstream keeps the LAST of several equal distances in scan order (dist > bestDist -> continue); here the lowest row
+ *   wins, as everywhere in this library.  Then one_to_one and the rotation histogram run through guided matching's finishing kernel,
+ *   unchanged (orientation 0 / 1 / 2 as there).  Upstream's vbMatched2 is the ORB-SLAM2 behaviour and ORB-SLAM3 never sets it; here
+ *   one_to_one is ss_match_guided's order-free rule, off by default.  Upstream's call: th 50, coarse 0, orientation on.
+ *   The counters follow the rule's order, so a descriptor is loaded only for a couple that passed the geometry; the conjunction makes
+ *   the winner independent of the order.
+ *   Outputs per query row: idx int32 (-1: none), d1 uint16 (raw, 0xFFFF: none); rows >= n_query get -1 / 0xFFFF.
+ * The triangulation of query row i with train row j = idx[i]; an entry outside 0 .. n_train - 1 is "no match", state -1.  All steps
+ *   are in double, one IEEE operation each, left to right; x, y and scale[] are converted exactly from float32, s_n = scale[n],
+ *   sigma2 = s*s in double.  The state is the number of the first failing test, 0 = a map point.  An octave of either row outside
+ *   0 .. n_levels - 1 is state 10, tested before step 1.
+ *   1. Parallax: xn = ((x - cx)*invfx, (y - cy)*invfy, 1); ray[k] = (R[k]*xn.x + R[3+k]*xn.y) + R[6+k] (R^T.xn) for each side;
+ *      cos = ((r1x*r2x + r1y*r2y) + r1z*r2z) / (sqrt((r1x*r1x + r1y*r1y) + r1z*r1z) * sqrt(the same of ray2)); accept iff
+ *      cos > 0 && cos < cos_parallax_max.
+ *   2. DLT: A[0][c] = xn1.x*P1[2][c] - P1[0][c], A[1][c] = xn1.y*P1[2][c] - P1[1][c], A[2], A[3] the same of side 2 (P = [R|t]);
+ *      M[i][j] = ((A[0][i]*A[0][j] + A[1][i]*A[1][j]) + A[2][i]*A[2][j]) + A[3][i]*A[3][j] for i <= j, mirrored.  SS_TRI_SWEEPS
+ *      sweeps of cyclic Jacobi on M, V = I, pairs (p, q) in the order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); a rotation is skipped
+ *      iff M[p][q] is exactly 0.0; else theta = (M[q][q] - M[p][p]) / (2.0*M[p][q]), t = (theta >= 0 ? 1.0 : -1.0) /
+ *      (fabs(theta) + sqrt(theta*theta + 1.0)), c = 1.0 / sqrt(t*t + 1.0), s = t*c; for k != p, q: M[k][p] = c*M[k][p] - s*M[k][q] and
+ *      M[k][q] = s*M[k][p] + c*M[k][q] (both from the old values, mirrored); M[p][p] -= t*M[p][q]; M[q][q] += t*M[p][q];
+ *      M[p][q] = 0.0; for every k: V[k][p] = c*V[k][p] - s*V[k][q], V[k][q] = s*V[k][p] + c*V[k][q] (old values).  v is the column
+ *      of V at the smallest M[k][k], lowest k on a tie.  Accept iff v[3] is finite and != 0; X = v[0..2] / v[3].  No loop has a trip
+ *      count that depends on the data.  Deviation: upstream runs Eigen's float32 JacobiSVD.
+ *   3. z1 = ((R1[6]*X0 + R1[7]*X1) + R1[8]*X2) + t1[2] > 0.        4. The same for z2.
+ *   5. Reprojection, side 1: u = (fx*x1c)/z1 + cx, v = (fy*y1c)/z1 + cy (x1c, y1c as z1 with rows 0 and 1); eu = u - x, ev = v - y;
+ *      err1 = eu*eu + ev*ev; accept iff err1 <= chi2 * sigma2[octave_1].        6. The same for side 2.
+ *   7. n1 = X - ow1, d1 = sqrt((n1x*n1x + n1y*n1y) + n1z*n1z); n2, d2 likewise; accept iff d1 > 0 && d2 > 0.
+ *   8. Far limit, only when far_limit > 0: d1 < far_limit && d2 < far_limit.
+ *   9. Scale: rd = d2/d1, ro = s[o1]/s[o2]; accept iff rd*ratio_factor >= ro && rd <= ro*ratio_factor.
+ *   The map point of a state-0 row (UpdateNormalAndDepth, reference keyframe = keyframe 1): position X; normal
+ *   (n1[k]/d1 + n2[k]/d2) / 2.0 (upstream does not renormalise either); max_dist = d1*s[o1]; min_dist = max_dist / s[n_levels - 1];
+ *   each of the eight numbers rounded to float32 once.  Its descriptor is keyframe 1's row: with two observations
+ *   ComputeDistinctiveDescriptors takes the first of a pointer-ordered map, here that is keyframe 1.
+ *   ss_tri_info per query row: state, and cos_parallax, err1_sq, err2_sq rounded to float32 once the step that forms them was
+ *   reached (whether it passed or not), 0.0f before; a NaN is reported as 0.0f.  Rows >= n_query get state -1 and 0.0f.
+ *   Compact outputs, in ascending query row: d_points / d_point_desc / d_point_rows (int32 i, j) / d_n_points.  Rows from n_points
+ *   on are not written.  d_points, d_point_desc and d_n_points are exactly the blocks ss_match_proj_pairs_device reads, with
+ *   point_rows = rows_per_frame.
+ * Alignment of the device buffers of these calls (hipMalloc's and any allocator's 256 bytes satisfy all of them; a sub-view at an
+ *   odd offset does not): descriptors, d_points and d_point_desc 16 bytes; keypoints and d_point_rows 8; the rest 4. */
+#define SS_TRI_SWEEPS 6
+typedef struct {          /* 384 bytes, one per pair */
+    float f12[9];
+    float ex, ey;
+    int32_t epipole_test;
+    double rcw1[9], tcw1[3], ow1[3];
+    double rcw2[9], tcw2[3], ow2[3];
+    double fx1, fy1, cx1, cy1, invfx1, invfy1;
+    double fx2, fy2, cx2, cy2, invfx2, invfy2;
+} ss_epi_pair;
+typedef struct {          /* 16 bytes */
+    int32_t th;           /* 0 .. 256; upstream: 50 */
+    int32_t coarse;       /* not 0: no epipolar-line test (upstream's bCoarse) */
+    int32_t one_to_one, orientation; /* as in ss_guided_params */
+} ss_epi_params;
+typedef struct {          /* 40 bytes, one per pair */
+    int32_t status;       /* SS_OK, or the frame_error that voided the pair (all rows "none", counts 0) */
+    int32_t n_query, n_train;
+    int32_t n_candidates; /* couples visited: same node, both untaken */
+    int32_t n_geometric;  /* couples passing tests 1 - 3 */
+    int32_t n_near;       /* couples also passing test 4 */
+    int32_t n_accepted, n_unique, n_final; /* rows with a winner, after one_to_one, after orientation */
+    int32_t rot_bins;     /* as in ss_guided_summary */
+} ss_epi_summary;
+typedef struct {          /* 32 bytes */
+    double cos_parallax_max; /* upstream: 0.9998 */
+    double chi2;             /* upstream: 5.991 */
+    double ratio_factor;     /* upstream: 1.5f * scale_factor */
+    double far_limit;        /* test 8; not > 0 (zero, negative, NaN): no test */
+} ss_tri_params;
+typedef struct {          /* 16 bytes, one per query row */
+    int32_t state;
+    float cos_parallax, err1_sq, err2_sq;
+} ss_tri_info;
+typedef struct {          /* 64 bytes, one per pair */
+    int32_t status;       /* SS_OK, or the frame_error that voided the pair (all rows -1, no point) */
+    int32_t n_query, n_train;
+    int32_t n_matches;    /* rows whose state is not -1 */
+    int32_t n_points;     /* rows of state 0 = n_state[0] */
+    int32_t n_state[11];  /* rows per state 0 .. 10 */
+} ss_tri_summary;
+/* Needs no device.  NULL pointer: SS_ERR_INVALID_ARG.  A pose or camera that is not finite gives a pair that matches nothing. */
+int ss_epi_pair_init(const ss_camera *cam1, const double rcw1[9], const double tcw1[3], const ss_camera *cam2, const double rcw2[9],
+                     const double tcw2[3], ss_epi_pair *out);
+/* Host twins of the steps (the text the kernels compile, csrc/ss_epi_steps.h); neither needs a device.  scale: n_levels entries,
+ * 1 <= n_levels <= SS_MAX_LEVELS.  ss_epi_check_host: tests 1 - 3 of the n couples (kp1[k], kp2[k]); out[k] is 0 pass, 1 octave,
+ * 2 epipole, 3 line.  ss_triangulate_host: the triangulation of the n couples; points[k] is all 0.0f unless info[k].state == 0. */
+int ss_epi_check_host(const ss_epi_pair *pair, const ss_epi_params *p, const float *scale, int n_levels, const ss_keypoint *kp1,
+                      const ss_keypoint *kp2, int n, uint8_t *out);
+int ss_triangulate_host(const ss_epi_pair *pair, const ss_tri_params *tp, const float *scale, int n_levels, const ss_keypoint *kp1,
+                        const ss_keypoint *kp2, int n, ss_map_point *points, ss_tri_info *info);
+/* n_frames independent pairs.  The arrays of ss_match_bow_pairs_device, plus d_query_taken / d_train_taken (device uint8
+ * [n_frames][rows_per_frame]; not 0 = the row already has a map point; NULL = none is taken) and pairs, a HOST table of n_frames
+ * ss_epi_pair.  Outputs d_idx (int32) / d_d1 (uint16) [n_frames][rows_per_frame] and d_summary [n_frames] ss_epi_summary.  Needs no
+ * vocabulary.  SS_ERR_INVALID_ARG: rows_per_frame above SS_GUIDED_MAX_ROWS, th outside 0 .. 256, orientation outside 0 .. 2, a NULL
+ * required buffer; the context stays usable.  Asynchronous on the context's stream. */
+int ss_match_epi_pairs_device(ss_ctx *ctx, const void *d_query, const void *d_query_kp, const void *d_query_node, const void *d_query_taken,
+                              const void *d_n_query, const void *d_train, const void *d_train_kp, const void *d_train_node,
+                              const void *d_train_taken, const void *d_n_train, int n_frames, int rows_per_frame, const ss_epi_pair *pairs,
+                              const ss_epi_params *p, void *d_idx, void *d_d1, void *d_summary);
+/* The frames and nodes of the last ss_bow_transform_batch_device (SS_ERR_STATE without one on the current batch).  train_src and its
+ * rules are those of ss_match_guided_batch_device (the couple j == i is excluded iff train_src[b] == b; a bad entry is
+ * SS_ERR_INVALID_ARG); pairs[b] is the pair (frame b, frame train_src[b]).  d_taken: device uint8 [n_frames][kp_capacity], read for
+ * both sides, or NULL.  A frame whose frame_error is set, on either side, gets that status and all-none rows. */
+int ss_match_epi_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_taken, const ss_epi_pair *pairs, const ss_epi_params *p,
+                              void *d_idx, void *d_d1, void *d_summary);
+/* Triangulates the matches d_idx (device int32 [n_frames][rows_per_frame], the search's output or the caller's own) of n_frames
+ * pairs: keypoints of both sides, the query descriptors, the counts, the HOST table pairs.  Outputs: d_info [n_frames][rows_per_frame]
+ * ss_tri_info; the compact d_points (ss_map_point) / d_point_desc ([32]) / d_point_rows (int32 i, j) [n_frames][rows_per_frame],
+ * d_n_points int32 [n_frames]; d_summary [n_frames] ss_tri_summary.  The compaction is deterministic.  SS_ERR_INVALID_ARG:
+ * rows_per_frame above SS_GUIDED_MAX_ROWS, a NULL buffer.  Asynchronous on the context's stream. */
+int ss_triangulate_pairs_device(ss_ctx *ctx, const void *d_query, const void *d_query_kp, const void *d_n_query, const void *d_train_kp,
+                                const void *d_n_train, const void *d_idx, int n_frames, int rows_per_frame, const ss_epi_pair *pairs,
+                                const ss_tri_params *tp, void *d_info, void *d_points, void *d_point_desc, void *d_point_rows,
+                                void *d_n_points, void *d_summary);
+/* The same on the frames of the last ss_extract_batch_device batch (rows_per_frame = kp_capacity), frame b against frame
+ * train_src[b] (ss_match_guided_batch_device's table; -1: no train, every row -1).  A flagged frame on either side voids the pair. */
+int ss_triangulate_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_idx, const ss_epi_pair *pairs, const ss_tri_params *tp,
+                                void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points, void *d_summary);
+
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device
  * (hipStream_t; NULL = the legacy default stream): for callers that produce the inputs of a *_device call on their own

@@ -26,6 +26,7 @@
 #include "ss_geometry.h"
 #include "ss_kernels.h"
 #include "ss_layout.h"
+#include "ss_epi_steps.h"
 #include "ss_proj_steps.h"
 #include "ss_track.h"
 
@@ -147,6 +148,12 @@ struct ss_ctx {
     dev_buf<uint8_t> d_voc, d_bow_ws, d_bow_keep;
     ssk_bow_voc voc;
     int bow_frames = 0;
+    /* epipolar search and triangulation: the workspace of each (counters, the node index of a pairs call, the finish's summaries;
+     * the uncompacted map points) and the pairs of a call on the device, staged in pinned memory as h_proj_tab is */
+    dev_buf<uint8_t> d_epi_ws, d_tri_ws, d_epi_tab;
+    uint8_t *h_epi_tab = nullptr;
+    size_t h_epi_tab_bytes = 0;
+    hipEvent_t epi_tab_copied = nullptr;
     /* rectification: map map_id in its fixed-point form (one allocation each: the xy array, then ab; d == NULL: unset) and the
      * 16-byte aligned buffer ss_extract_stereo_raw remaps both eyes into */
     struct rect_map {
@@ -642,6 +649,11 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_voc);
     dev_free(c->d_bow_ws);
     dev_free(c->d_bow_keep);
+    dev_free(c->d_epi_ws);
+    dev_free(c->d_tri_ws);
+    dev_free(c->d_epi_tab);
+    if (c->h_epi_tab) (void)hipHostFree(c->h_epi_tab);
+    if (c->epi_tab_copied) (void)hipEventDestroy(c->epi_tab_copied);
     for (auto &rm : c->rect_maps) dev_free(rm.d);
     dev_free(c->d_rect);
     if (c->h_train_src) (void)hipHostFree(c->h_train_src);
@@ -2492,6 +2504,328 @@ int ss_bow_score_device(ss_ctx *c, const void *d_q_word, const void *d_q_value, 
     }
     HIP_TRY(c, hipGetLastError());
     return SS_OK;
+}
+
+/* ---- epipolar search and triangulation (csrc/ss_epi.hip, csrc/ss_epi_steps.h) ---- */
+int ss_epi_pair_init(const ss_camera *cam1, const double rcw1[9], const double tcw1[3], const ss_camera *cam2, const double rcw2[9],
+                     const double tcw2[3], ss_epi_pair *out)
+{
+    if (!cam1 || !rcw1 || !tcw1 || !cam2 || !rcw2 || !tcw2 || !out) return SS_ERR_INVALID_ARG;
+    ss_epi_pair &w = *out;
+    for (int k = 0; k < 9; k++) w.rcw1[k] = rcw1[k], w.rcw2[k] = rcw2[k];
+    for (int k = 0; k < 3; k++) {
+        w.tcw1[k] = tcw1[k], w.tcw2[k] = tcw2[k];
+        w.ow1[k] = -((rcw1[k] * tcw1[0] + rcw1[3 + k] * tcw1[1]) + rcw1[6 + k] * tcw1[2]);
+        w.ow2[k] = -((rcw2[k] * tcw2[0] + rcw2[3 + k] * tcw2[1]) + rcw2[6 + k] * tcw2[2]);
+    }
+    w.fx1 = cam1->fx, w.fy1 = cam1->fy, w.cx1 = cam1->cx, w.cy1 = cam1->cy, w.invfx1 = 1.0 / cam1->fx, w.invfy1 = 1.0 / cam1->fy;
+    w.fx2 = cam2->fx, w.fy2 = cam2->fy, w.cx2 = cam2->cx, w.cy2 = cam2->cy, w.invfx2 = 1.0 / cam2->fx, w.invfy2 = 1.0 / cam2->fy;
+    const double *R1 = w.rcw1, *R2 = w.rcw2, *t1 = w.tcw1, *t2 = w.tcw2;
+    double R12[3][3], t12[3], E[3][3], G[3][3], F[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R12[i][j] = (R1[3 * i] * R2[3 * j] + R1[3 * i + 1] * R2[3 * j + 1]) + R1[3 * i + 2] * R2[3 * j + 2];
+    for (int i = 0; i < 3; i++) t12[i] = t1[i] - ((R12[i][0] * t2[0] + R12[i][1] * t2[1]) + R12[i][2] * t2[2]);
+    for (int j = 0; j < 3; j++) {
+        E[0][j] = t12[1] * R12[2][j] - t12[2] * R12[1][j];
+        E[1][j] = t12[2] * R12[0][j] - t12[0] * R12[2][j];
+        E[2][j] = t12[0] * R12[1][j] - t12[1] * R12[0][j];
+    }
+    for (int j = 0; j < 3; j++) {
+        G[0][j] = w.invfx1 * E[0][j];
+        G[1][j] = w.invfy1 * E[1][j];
+        G[2][j] = E[2][j] - (w.cx1 * G[0][j] + w.cy1 * G[1][j]);
+    }
+    double m = 0.0;
+    bool finite = true;
+    for (int i = 0; i < 3; i++) {
+        F[i][0] = G[i][0] * w.invfx2;
+        F[i][1] = G[i][1] * w.invfy2;
+        F[i][2] = G[i][2] - (F[i][0] * w.cx2 + F[i][1] * w.cy2);
+        for (int j = 0; j < 3; j++) {
+            const double v = fabs(F[i][j]);
+            if (!(v <= 1.7976931348623157e308)) finite = false;
+            else if (v > m) m = v;
+        }
+    }
+    const bool usable = finite && m > 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) w.f12[3 * i + j] = usable ? (float)(F[i][j] / m) : 0.0f;
+    double C2[3];
+    for (int i = 0; i < 3; i++) C2[i] = ((R2[3 * i] * w.ow1[0] + R2[3 * i + 1] * w.ow1[1]) + R2[3 * i + 2] * w.ow1[2]) + t2[i];
+    const float ex = (float)((w.fx2 * C2[0]) / C2[2] + w.cx2), ey = (float)((w.fy2 * C2[1]) / C2[2] + w.cy2);
+    w.epipole_test = (std::isfinite(ex) && std::isfinite(ey)) ? 1 : 0;
+    w.ex = w.epipole_test ? ex : 0.0f;
+    w.ey = w.epipole_test ? ey : 0.0f;
+    return SS_OK;
+}
+
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *epi_params_error(const ss_epi_params *p)
+{
+    if (!p) return "epipolar search: params is NULL";
+    if (p->th < 0 || p->th > 256) return "epipolar search: th must be 0 .. 256";
+    if (p->orientation < 0 || p->orientation > 2) return "epipolar search: orientation must be 0, 1 or 2";
+    return nullptr;
+}
+
+int ss_epi_check_host(const ss_epi_pair *pair, const ss_epi_params *p, const float *scale, int n_levels, const ss_keypoint *kp1,
+                      const ss_keypoint *kp2, int n, uint8_t *out)
+{
+    if (epi_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!pair || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n < 0 || (n > 0 && (!kp1 || !kp2 || !out))) return SS_ERR_INVALID_ARG;
+    for (int k = 0; k < n; k++) {
+        const ss_epi_line line = ss_epi_line_of(pair->f12, kp1[k].x, kp1[k].y);
+        out[k] = (uint8_t)ss_epi_check(pair->ex, pair->ey, pair->epipole_test, p->coarse != 0, line, scale, n_levels, kp2[k].x, kp2[k].y, kp2[k].octave);
+    }
+    return SS_OK;
+}
+
+int ss_triangulate_host(const ss_epi_pair *pair, const ss_tri_params *tp, const float *scale, int n_levels, const ss_keypoint *kp1,
+                        const ss_keypoint *kp2, int n, ss_map_point *points, ss_tri_info *info)
+{
+    if (!pair || !tp || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n < 0 || (n > 0 && (!kp1 || !kp2 || !points || !info))) return SS_ERR_INVALID_ARG;
+    for (int k = 0; k < n; k++) {
+        const ss_tri_out r = ss_tri_eval(*pair, *tp, scale, n_levels, kp1[k].x, kp1[k].y, kp1[k].octave, kp2[k].x, kp2[k].y, kp2[k].octave);
+        points[k] = r.point;
+        info[k] = r.info;
+    }
+    return SS_OK;
+}
+
+/* The host pairs of a call -> c->d_epi_tab on c->stream, through pinned memory as upload_proj_tables does it */
+static int upload_epi_pairs(ss_ctx *c, const ss_epi_pair *pairs, int n)
+{
+    const size_t bytes = (size_t)n * sizeof(ss_epi_pair);
+    int rc = grow(c, c->d_epi_tab, bytes);
+    if (rc != SS_OK) return rc;
+    if (c->epi_tab_copied) HIP_TRY(c, hipEventSynchronize(c->epi_tab_copied));
+    else HIP_TRY(c, hipEventCreateWithFlags(&c->epi_tab_copied, hipEventDisableTiming));
+    if (c->h_epi_tab_bytes < bytes) {
+        if (c->h_epi_tab) (void)hipHostFree(c->h_epi_tab);
+        c->h_epi_tab = nullptr;
+        c->h_epi_tab_bytes = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_epi_tab, bytes, hipHostMallocDefault));
+        c->h_epi_tab_bytes = bytes;
+    }
+    memcpy(c->h_epi_tab, pairs, bytes);
+    HIP_TRY(c, hipMemcpyAsync(c->d_epi_tab, c->h_epi_tab, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->epi_tab_copied, c->stream));
+    return SS_OK;
+}
+
+static int epi_pyramid(ss_ctx *c, int *n_levels, float *scale)
+{
+    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
+        return fail(c, SS_ERR_INVALID_ARG, "epipolar search: the context's n_levels / scale_factor give no pyramid table");
+    *n_levels = c->params.n_levels;
+    ss_scale_table(c->params.scale_factor, *n_levels, scale);
+    return SS_OK;
+}
+
+/* The launches of a search whose operands, counts and outputs are filled in: the index of the train nodes where the call brings its
+ * own (t_node != NULL), the search, guided matching's finish as it is (its summaries go to the workspace), the summaries */
+static int epi_match_run(ss_ctx *c, ssk_guided_call &g, ssk_epi_call &e, const ss_epi_pair *pairs, const ss_epi_params *p, const int32_t *t_node)
+{
+    g.th = p->th, g.rnum = 0, g.rden = 0;
+    g.one_to_one = p->one_to_one != 0, g.orientation = p->orientation;
+    e.coarse = p->coarse != 0;
+    int rc = epi_pyramid(c, &e.n_levels, e.scale);
+    if (rc != SS_OK) return rc;
+    const size_t nr = (size_t)g.n_frames * g.rows;
+    const size_t o_geo = up256(nr * sizeof(int32_t)), o_near = o_geo + up256(nr * sizeof(int32_t)), o_sum = o_near + up256(nr * sizeof(int32_t));
+    const size_t o_index = o_sum + up256((size_t)g.n_frames * sizeof(ss_guided_summary));
+    const size_t o_cnt = o_index + (t_node ? up256(nr * sizeof(uint64_t)) : 0);
+    rc = grow(c, c->d_epi_ws, o_cnt + (t_node ? up256((size_t)g.n_frames * sizeof(int32_t)) : 0));
+    if (rc != SS_OK) return rc;
+    rc = upload_epi_pairs(c, pairs, g.n_frames);
+    if (rc != SS_OK) return rc;
+    e.pairs = (const ss_epi_pair *)c->d_epi_tab.p;
+    g.n_cand = (int32_t *)c->d_epi_ws.p;
+    e.n_geo = (int32_t *)(c->d_epi_ws.p + o_geo);
+    e.n_near = (int32_t *)(c->d_epi_ws.p + o_near);
+    g.summary = (ss_guided_summary *)(c->d_epi_ws.p + o_sum);
+    if (t_node) {
+        uint64_t *own = (uint64_t *)(c->d_epi_ws.p + o_index);
+        int32_t *own_n = (int32_t *)(c->d_epi_ws.p + o_cnt);
+        stage_timer t(c, "epi_index", (int64_t)nr * 12);
+        ssk_bow_index(c->stream, t_node, g.nt, nullptr, g.n_frames, g.rows, own, own_n);
+        e.index = own, e.n_index = own_n;
+    }
+    {
+        /* per query: its node, keypoint and descriptor, the 18 bytes it writes; what it visits of its run depends on the content */
+        stage_timer t(c, "epi_search", (int64_t)nr * (4 + (int64_t)sizeof(ss_keypoint) + SS_DESC_BYTES + 18));
+        ssk_epi_search(c->stream, g, e);
+    }
+    {
+        stage_timer t(c, "epi_finish", (int64_t)nr * (8 + 2 + 4 + 8 + (g.orientation ? 8 : 0)) + g.n_frames * (int64_t)(sizeof(ss_guided_summary) + sizeof(ss_epi_summary)));
+        ssk_guided_finish(c->stream, g);
+        ssk_epi_summary(c->stream, g, e);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_match_epi_pairs_device(ss_ctx *c, const void *d_query, const void *d_query_kp, const void *d_query_node, const void *d_query_taken,
+                              const void *d_n_query, const void *d_train, const void *d_train_kp, const void *d_train_node,
+                              const void *d_train_taken, const void *d_n_train, int n_frames, int rows_per_frame, const ss_epi_pair *pairs,
+                              const ss_epi_params *p, void *d_idx, void *d_d1, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = epi_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_frames < 0 || rows_per_frame < 1) return fail(c, SS_ERR_INVALID_ARG, "epipolar search: bad pair or row count");
+    if (rows_per_frame > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "epipolar search: rows_per_frame " + std::to_string(rows_per_frame) + " exceeds SS_GUIDED_MAX_ROWS (" +
+                                               std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    if (n_frames == 0) return SS_OK;
+    if (!d_query || !d_query_kp || !d_query_node || !d_n_query || !d_train || !d_train_kp || !d_train_node || !d_n_train || !pairs || !d_idx || !d_d1 ||
+        !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "epipolar search: NULL buffer");
+    ssk_guided_call g;
+    g.n_frames = n_frames;
+    g.rows = rows_per_frame;
+    g.q_kp = (const ss_keypoint *)d_query_kp, g.t_kp = (const ss_keypoint *)d_train_kp;
+    g.q_desc = (const uint8_t *)d_query, g.t_desc = (const uint8_t *)d_train;
+    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1;
+    ssk_epi_call e;
+    e.q_node = (const int32_t *)d_query_node;
+    e.q_taken = (const uint8_t *)d_query_taken, e.t_taken = (const uint8_t *)d_train_taken;
+    e.summary = (ss_epi_summary *)d_summary;
+    return epi_match_run(c, g, e, pairs, p, (const int32_t *)d_train_node);
+}
+
+/* the train table of a batch form: checked, then on the device */
+static int epi_train_src(ss_ctx *c, const int32_t *train_src, int n, const char *what)
+{
+    for (int b = 0; train_src && b < n; b++)
+        if (train_src[b] < -1 || train_src[b] >= n)
+            return fail(c, SS_ERR_INVALID_ARG, "train_src[" + std::to_string(b) + "] = " + std::to_string(train_src[b]) + " names no frame of the batch (" +
+                                                   std::to_string(n) + "); " + what + " takes no carry frames");
+    return upload_train_src(c, train_src, n);
+}
+
+int ss_match_epi_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_taken, const ss_epi_pair *pairs, const ss_epi_params *p,
+                              void *d_idx, void *d_d1, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->have_geom || c->last_n_frames <= 0) return fail(c, SS_ERR_STATE, "ss_match_epi_batch_device: no batch has been extracted");
+    if (c->bow_frames != c->last_n_frames)
+        return fail(c, SS_ERR_STATE, "ss_match_epi_batch_device: the last batch has not been through ss_bow_transform_batch_device");
+    if (const char *msg = epi_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (!pairs || !d_idx || !d_d1 || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "epipolar search: NULL buffer");
+    const int n = c->last_n_frames, kcap = c->hg.kcap;
+    if (kcap > SS_GUIDED_MAX_ROWS) return fail(c, SS_ERR_INVALID_ARG, "epipolar search: kp_capacity " + std::to_string(kcap) + " exceeds SS_GUIDED_MAX_ROWS");
+    int rc = epi_train_src(c, train_src, n, "the epipolar search");
+    if (rc != SS_OK) return rc;
+    const bow_keep keep = bow_keep_of(c->d_bow_keep.p, n, kcap);
+    ssk_guided_call g;
+    g.n_frames = n;
+    g.rows = kcap;
+    g.q_kp = g.t_kp = c->ws.kps;
+    g.q_desc = g.t_desc = c->ws.desc;
+    g.nq = g.nt = c->ws.n_kp;
+    g.src = c->d_train_src;
+    rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
+    g.exclude_same_frame = 1;
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1;
+    ssk_epi_call e;
+    e.q_node = keep.node;
+    e.index = keep.index, e.n_index = keep.n_index;
+    e.q_taken = e.t_taken = (const uint8_t *)d_taken;
+    e.summary = (ss_epi_summary *)d_summary;
+    return epi_match_run(c, g, e, pairs, p, nullptr);
+}
+
+/* the two launches of a triangulation whose operands and outputs are filled in */
+static int tri_run(ss_ctx *c, ssk_tri_call &t, const ss_epi_pair *pairs, const ss_tri_params *tp)
+{
+    t.tp = *tp;
+    int rc = epi_pyramid(c, &t.n_levels, t.scale);
+    if (rc != SS_OK) return rc;
+    const size_t nr = (size_t)t.n_frames * t.rows;
+    rc = grow(c, c->d_tri_ws, nr * sizeof(ss_map_point));
+    if (rc != SS_OK) return rc;
+    rc = upload_epi_pairs(c, pairs, t.n_frames);
+    if (rc != SS_OK) return rc;
+    t.pairs = (const ss_epi_pair *)c->d_epi_tab.p;
+    t.tmp = (ss_map_point *)c->d_tri_ws.p;
+    {
+        /* per row: its match, its keypoint and its info; a matched row reads the other keypoint on top */
+        stage_timer s(c, "tri_eval", (int64_t)nr * (4 + (int64_t)sizeof(ss_keypoint) + (int64_t)sizeof(ss_tri_info)));
+        ssk_tri_eval(c->stream, t);
+    }
+    {
+        /* the states read; what a point moves (its 32 bytes twice, its descriptor twice, its rows) depends on the content */
+        stage_timer s(c, "tri_compact", (int64_t)nr * 4 + t.n_frames * (int64_t)(sizeof(ss_tri_summary) + 4));
+        ssk_tri_compact(c->stream, t);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+static void tri_outputs(ssk_tri_call &t, void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points, void *d_summary)
+{
+    t.info = (ss_tri_info *)d_info;
+    t.points = (ss_map_point *)d_points, t.point_desc = (uint8_t *)d_point_desc, t.point_rows = (int32_t *)d_point_rows;
+    t.n_points = (int32_t *)d_n_points;
+    t.summary = (ss_tri_summary *)d_summary;
+}
+
+int ss_triangulate_pairs_device(ss_ctx *c, const void *d_query, const void *d_query_kp, const void *d_n_query, const void *d_train_kp,
+                                const void *d_n_train, const void *d_idx, int n_frames, int rows_per_frame, const ss_epi_pair *pairs,
+                                const ss_tri_params *tp, void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points,
+                                void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!tp) return fail(c, SS_ERR_INVALID_ARG, "triangulation: params is NULL");
+    if (n_frames < 0 || rows_per_frame < 1) return fail(c, SS_ERR_INVALID_ARG, "triangulation: bad pair or row count");
+    if (rows_per_frame > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "triangulation: rows_per_frame " + std::to_string(rows_per_frame) + " exceeds SS_GUIDED_MAX_ROWS (" +
+                                               std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    if (n_frames == 0) return SS_OK;
+    if (!d_query || !d_query_kp || !d_n_query || !d_train_kp || !d_n_train || !d_idx || !pairs || !d_info || !d_points || !d_point_desc || !d_point_rows ||
+        !d_n_points || !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "triangulation: NULL buffer");
+    ssk_tri_call t;
+    t.n_frames = n_frames;
+    t.rows = rows_per_frame;
+    t.q_kp = (const ss_keypoint *)d_query_kp, t.t_kp = (const ss_keypoint *)d_train_kp;
+    t.q_desc = (const uint8_t *)d_query;
+    t.nq = (const int32_t *)d_n_query, t.nt = (const int32_t *)d_n_train;
+    t.idx = (const int32_t *)d_idx;
+    tri_outputs(t, d_info, d_points, d_point_desc, d_point_rows, d_n_points, d_summary);
+    return tri_run(c, t, pairs, tp);
+}
+
+int ss_triangulate_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_idx, const ss_epi_pair *pairs, const ss_tri_params *tp,
+                                void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->have_geom || c->last_n_frames <= 0) return fail(c, SS_ERR_STATE, "ss_triangulate_batch_device: no batch has been extracted");
+    if (!tp) return fail(c, SS_ERR_INVALID_ARG, "triangulation: params is NULL");
+    if (!d_idx || !pairs || !d_info || !d_points || !d_point_desc || !d_point_rows || !d_n_points || !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "triangulation: NULL buffer");
+    const int n = c->last_n_frames, kcap = c->hg.kcap;
+    if (kcap > SS_GUIDED_MAX_ROWS) return fail(c, SS_ERR_INVALID_ARG, "triangulation: kp_capacity " + std::to_string(kcap) + " exceeds SS_GUIDED_MAX_ROWS");
+    int rc = epi_train_src(c, train_src, n, "the triangulation");
+    if (rc != SS_OK) return rc;
+    ssk_tri_call t;
+    t.n_frames = n;
+    t.rows = kcap;
+    t.q_kp = t.t_kp = c->ws.kps;
+    t.q_desc = c->ws.desc;
+    t.nq = t.nt = c->ws.n_kp;
+    t.src = c->d_train_src;
+    rc = flagged_frame_error(c, c->batch_test_flagged, &t.frame_error);
+    if (rc != SS_OK) return rc;
+    t.idx = (const int32_t *)d_idx;
+    tri_outputs(t, d_info, d_points, d_point_desc, d_point_rows, d_n_points, d_summary);
+    return tri_run(c, t, pairs, tp);
 }
 
 int ss_wait_stream(ss_ctx *c, void *hip_stream)

@@ -26,7 +26,8 @@
 
 namespace {
 
-/* what the three kernels agree on for query frame b: its train frame, its status, both row counts */
+/* what the three kernels agree on for query frame b: its train frame, its status, both row counts.  k_guided_finish also runs
+ * behind k_bow_search (ss_bow.hip, the rule inline) and k_epi_search (ss_epi.hip, ep_frame_of): the three statements must agree */
 struct gd_frame {
     int t, status, nq, nt;
 };

@@ -253,6 +253,49 @@ void ssk_bow_index(hipStream_t s, const int32_t *node, const int32_t *n_rows, co
 void ssk_bow_search(hipStream_t s, const ssk_guided_call &g, const int32_t *q_node, const uint64_t *index, const int32_t *n_index);
 void ssk_bow_score(hipStream_t s, const int32_t *q_word, const double *q_value, const int32_t *q_count, int q_rows, const int32_t *db_word,
                    const double *db_value, const int32_t *db_count, int n_db, int stride, double *score);
+/* ss_epi.hip: epipolar search and triangulation (DESIGN.md "Epipolar search and triangulation").  The search runs on a guided
+ * call (operands, counts, src, frame_error, exclude_same_frame, th, one_to_one, orientation, idx, d1, n_cand; d2 is not written
+ * and g.summary is a workspace row per pair) plus what follows; ssk_guided_finish then runs on g as it is, and ssk_epi_summary
+ * turns its summary and the per-row counters into the ss_epi_summary of every pair. */
+struct ssk_epi_call {
+    const int32_t *q_node = nullptr;      /* [n_frames][rows] */
+    const uint64_t *index = nullptr;      /* the node index of the train frames (ssk_bow_index), n_index keys each */
+    const int32_t *n_index = nullptr;
+    const uint8_t *q_taken = nullptr, *t_taken = nullptr; /* [n_frames][rows], or NULL */
+    const ss_epi_pair *pairs = nullptr;   /* device [n_frames] */
+    int coarse = 0, n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    int32_t *n_geo = nullptr, *n_near = nullptr; /* workspace [n_frames][rows] */
+    ss_epi_summary *summary = nullptr;
+};
+void ssk_epi_search(hipStream_t s, const ssk_guided_call &g, const ssk_epi_call &e);
+void ssk_epi_summary(hipStream_t s, const ssk_guided_call &g, const ssk_epi_call &e);
+/* Pair b triangulates the matches idx[b][i] of its query rows with the rows of train frame src[b] (NULL: b).  eval writes info and,
+ * into the workspace tmp [n_frames][rows], the map point of every row; compact (one workgroup per pair, SSK_TRI_CHUNK rows at a
+ * time, in ascending row order) gathers the state-0 rows into points / point_desc / point_rows, counts them and writes the summary */
+#define SSK_TRI_CHUNK 1024
+struct ssk_tri_call {
+    int n_frames = 0, rows = 0;
+    const ss_keypoint *q_kp = nullptr, *t_kp = nullptr;
+    const uint8_t *q_desc = nullptr;
+    const int32_t *nq = nullptr, *nt = nullptr;
+    const int32_t *src = nullptr;
+    const int32_t *frame_error = nullptr;
+    const int32_t *idx = nullptr;
+    const ss_epi_pair *pairs = nullptr; /* device [n_frames] */
+    ss_tri_params tp = {};
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    ss_map_point *tmp = nullptr;
+    ss_tri_info *info = nullptr;
+    ss_map_point *points = nullptr;
+    uint8_t *point_desc = nullptr;
+    int32_t *point_rows = nullptr;
+    int32_t *n_points = nullptr;
+    ss_tri_summary *summary = nullptr;
+};
+void ssk_tri_eval(hipStream_t s, const ssk_tri_call &t);
+void ssk_tri_compact(hipStream_t s, const ssk_tri_call &t);
 /* ss_rectify.hip: bilinear remap through fixed-point maps (DESIGN.md "Rectification").  A map on the device is two arrays of
  * height rows, ssk_rectify_pitch(width) entries apart: xy = (uint16)ix | (uint16)iy << 16 and ab = a | b << 5; the entries past the
  * width are "outside" records.  ssk_rectify_fixed is the host conversion of a float map pair into them.  ssk_rectify remaps the

@@ -43,7 +43,9 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_vocab_load_text", "ss_vocab_from_arrays", "ss_vocab_info", "ss_vocab_copy_out", "ss_vocab_destroy",
            "ss_bow_set_vocabulary", "ss_bow_transform_device", "ss_bow_transform_batch_device", "ss_match_bow_pairs_device",
            "ss_match_bow_batch_device", "ss_bow_score_device", "ss_proj_view_init", "ss_proj_points_host",
-           "ss_match_proj_pairs_device", "ss_match_proj_batch_device", "ss_match_proj"]
+           "ss_match_proj_pairs_device", "ss_match_proj_batch_device", "ss_match_proj", "ss_epi_pair_init", "ss_epi_check_host",
+           "ss_triangulate_host", "ss_match_epi_pairs_device", "ss_match_epi_batch_device", "ss_triangulate_pairs_device",
+           "ss_triangulate_batch_device"]
 
 
 class OrbParams(C.Structure):
@@ -214,6 +216,107 @@ def proj_points_host(view, params: ProjParams, scale, points: np.ndarray) -> np.
     return out
 
 
+class EpiPair(C.Structure):
+    """ss_epi_pair: a (keyframe 1 = query, keyframe 2 = train) pair; float32 for the search, double for the triangulation"""
+    _fields_ = [("f12", C.c_float * 9), ("ex", C.c_float), ("ey", C.c_float), ("epipole_test", C.c_int32)] + \
+               [(n + s, C.c_double * k) for s in ("1", "2") for n, k in (("rcw", 9), ("tcw", 3), ("ow", 3))] + \
+               [(n + s, C.c_double) for s in ("1", "2") for n in ("fx", "fy", "cx", "cy", "invfx", "invfy")]
+
+
+class EpiParams(C.Structure):
+    _fields_ = [("th", C.c_int32), ("coarse", C.c_int32), ("one_to_one", C.c_int32), ("orientation", C.c_int32)]
+
+
+class EpiSummary(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_query", C.c_int32), ("n_train", C.c_int32), ("n_candidates", C.c_int32),
+                ("n_geometric", C.c_int32), ("n_near", C.c_int32), ("n_accepted", C.c_int32), ("n_unique", C.c_int32),
+                ("n_final", C.c_int32), ("rot_bins", C.c_int32)]
+
+
+class TriParams(C.Structure):
+    _fields_ = [("cos_parallax_max", C.c_double), ("chi2", C.c_double), ("ratio_factor", C.c_double), ("far_limit", C.c_double)]
+
+
+class TriSummary(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_query", C.c_int32), ("n_train", C.c_int32), ("n_matches", C.c_int32),
+                ("n_points", C.c_int32), ("n_state", C.c_int32 * 11)]
+
+
+EPI_PAIR_DTYPE = np.dtype([("f12", "<f4", (9,)), ("ex", "<f4"), ("ey", "<f4"), ("epipole_test", "<i4")] +
+                          [(n + s, "<f8", (k,)) for s in ("1", "2") for n, k in (("rcw", 9), ("tcw", 3), ("ow", 3))] +
+                          [(n + s, "<f8") for s in ("1", "2") for n in ("fx", "fy", "cx", "cy", "invfx", "invfy")])
+EPI_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n, _ in EpiSummary._fields_])
+# ss_tri_info: one per query row; ss_tri_summary: one per pair
+TRI_INFO_DTYPE = np.dtype([("state", "<i4"), ("cos_parallax", "<f4"), ("err1_sq", "<f4"), ("err2_sq", "<f4")])
+TRI_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n, _ in TriSummary._fields_[:5]] + [("n_state", "<i4", (11,))])
+
+
+def epi_params(th: int = 50, coarse: bool = False, one_to_one: bool = False, orientation: int = 1) -> EpiParams:
+    """upstream's SearchForTriangulation: TH_LOW 50, bCoarse false, the rotation histogram on"""
+    return EpiParams(th=th, coarse=int(coarse), one_to_one=int(one_to_one), orientation=orientation)
+
+
+def tri_params(cos_parallax_max: float = 0.9998, chi2: float = 5.991, ratio_factor: float = 1.5 * 1.2, far_limit: float = 0.0) -> TriParams:
+    """upstream's CreateNewMapPoints: 0.9998, 5.991, ratio_factor = 1.5f * scale_factor, no far limit"""
+    return TriParams(cos_parallax_max=cos_parallax_max, chi2=chi2, ratio_factor=ratio_factor, far_limit=far_limit)
+
+
+def epi_pair(cam1: Camera, rcw1, tcw1, cam2: Camera, rcw2, tcw2) -> EpiPair:
+    """ss_epi_pair_init: the pair of `cam1` at pose 1 (query side) and `cam2` at pose 2 (train side); needs no device"""
+    r1, t1 = np.ascontiguousarray(rcw1, np.float64).reshape(9), np.ascontiguousarray(tcw1, np.float64).reshape(3)
+    r2, t2 = np.ascontiguousarray(rcw2, np.float64).reshape(9), np.ascontiguousarray(tcw2, np.float64).reshape(3)
+    w = EpiPair()
+    rc = load().ss_epi_pair_init(C.byref(cam1), r1.ctypes.data, t1.ctypes.data, C.byref(cam2), r2.ctypes.data, t2.ctypes.data, C.byref(w))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_epi_pair_init refused its arguments")
+    return w
+
+
+def _pairs_array(pairs):
+    """one EpiPair, a sequence of them or an EPI_PAIR_DTYPE array -> a contiguous EPI_PAIR_DTYPE array"""
+    if isinstance(pairs, EpiPair):
+        pairs = [pairs]
+    if isinstance(pairs, np.ndarray):
+        return np.ascontiguousarray(pairs, EPI_PAIR_DTYPE).reshape(-1)
+    return np.frombuffer(b"".join(bytes(v) for v in pairs), EPI_PAIR_DTYPE).copy()
+
+
+def _one_pair_couples(pair, scale, kp1, kp2):
+    w = _pairs_array(pair)
+    if len(w) != 1:
+        raise ValueError("one pair")
+    k1, k2 = np.ascontiguousarray(kp1, KP_DTYPE), np.ascontiguousarray(kp2, KP_DTYPE)
+    if len(k1) != len(k2):
+        raise ValueError("one keypoint of each side per couple")
+    return w, np.ascontiguousarray(scale, np.float32), k1, k2
+
+
+def epi_check_host(pair, params: EpiParams, scale, kp1: np.ndarray, kp2: np.ndarray) -> np.ndarray:
+    """ss_epi_check_host: tests 1 - 3 of the couples (kp1[k], kp2[k]) on the host (the text the kernel compiles) -> uint8, 0 pass,
+    1 octave, 2 epipole, 3 line; needs no device"""
+    w, sc, k1, k2 = _one_pair_couples(pair, scale, kp1, kp2)
+    n = len(k1)
+    out = np.empty(n, np.uint8)
+    rc = load().ss_epi_check_host(w.ctypes.data, C.byref(params), sc.ctypes.data, len(sc), k1.ctypes.data if n else None,
+                                  k2.ctypes.data if n else None, n, out.ctypes.data if n else None)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_epi_check_host refused its arguments")
+    return out
+
+
+def triangulate_host(pair, params: TriParams, scale, kp1: np.ndarray, kp2: np.ndarray):
+    """ss_triangulate_host: the triangulation of the couples (kp1[k], kp2[k]) on the host -> (MAP_POINT_DTYPE rows, TRI_INFO_DTYPE
+    rows); needs no device"""
+    w, sc, k1, k2 = _one_pair_couples(pair, scale, kp1, kp2)
+    n = len(k1)
+    pts, info = np.empty(n, MAP_POINT_DTYPE), np.empty(n, TRI_INFO_DTYPE)
+    rc = load().ss_triangulate_host(w.ctypes.data, C.byref(params), sc.ctypes.data, len(sc), k1.ctypes.data if n else None,
+                                    k2.ctypes.data if n else None, n, pts.ctypes.data if n else None, info.ctypes.data if n else None)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_triangulate_host refused its arguments")
+    return pts, info
+
+
 class VocabShape(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("n_nodes", C.c_int32), ("n_words", C.c_int32), ("max_depth", C.c_int32)]
 
@@ -361,6 +464,14 @@ def load():
                                               [C.c_void_p] * 5
     lib.ss_match_proj.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                   C.c_void_p, C.POINTER(ProjParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ProjSummary)]
+    lib.ss_epi_pair_init.argtypes = [C.POINTER(Camera), C.c_void_p, C.c_void_p, C.POINTER(Camera), C.c_void_p, C.c_void_p, C.POINTER(EpiPair)]
+    lib.ss_epi_check_host.argtypes = [C.c_void_p, C.POINTER(EpiParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.ss_triangulate_host.argtypes = [C.c_void_p, C.POINTER(TriParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_void_p]
+    lib.ss_match_epi_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(EpiParams)] + [C.c_void_p] * 3
+    lib.ss_match_epi_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EpiParams)] + [C.c_void_p] * 3
+    lib.ss_triangulate_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(TriParams)] + [C.c_void_p] * 6
+    lib.ss_triangulate_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TriParams)] + [C.c_void_p] * 6
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -883,6 +994,53 @@ class OrbContext:
         self._check(self._lib.ss_bow_score_device(self._h, C.c_void_p(d_q_word), C.c_void_p(d_q_value), C.c_void_p(d_q_count), int(q_rows),
                                                   C.c_void_p(d_db_word), C.c_void_p(d_db_value), C.c_void_p(d_db_count), int(n_db), int(stride),
                                                   C.c_void_p(d_score)))
+
+    # ---- epipolar search and triangulation: new map points from pairs (the rule: include/sendslam_orb.h) ----
+    def match_epi_pairs_device(self, d_q: int, d_q_kp: int, d_q_node: int, d_nq: int, d_t: int, d_t_kp: int, d_t_node: int, d_nt: int,
+                               n_frames: int, rows_per_frame: int, pairs, params: EpiParams, d_idx: int, d_d1: int, d_summary: int,
+                               d_q_taken: int = 0, d_t_taken: int = 0):
+        """n_frames pairs on device arrays [n_frames][rows_per_frame] (those of match_bow_pairs_device, uint8 taken flags or 0);
+        pairs: n_frames EpiPair (host); outputs d_idx int32 / d_d1 uint16, d_summary EPI_SUMMARY_DTYPE; asynchronous."""
+        w = _pairs_array(pairs)
+        if len(w) != n_frames:
+            raise ValueError("one pair per frame")
+        self._check(self._lib.ss_match_epi_pairs_device(self._h, C.c_void_p(d_q), C.c_void_p(d_q_kp), C.c_void_p(d_q_node), C.c_void_p(d_q_taken),
+                                                        C.c_void_p(d_nq), C.c_void_p(d_t), C.c_void_p(d_t_kp), C.c_void_p(d_t_node),
+                                                        C.c_void_p(d_t_taken), C.c_void_p(d_nt), n_frames, rows_per_frame,
+                                                        w.ctypes.data if len(w) else None, C.byref(params), C.c_void_p(d_idx), C.c_void_p(d_d1),
+                                                        C.c_void_p(d_summary)))
+
+    def match_epi_batch_device(self, pairs, params: EpiParams, d_idx: int, d_d1: int, d_summary: int, train_src=None, d_taken: int = 0):
+        """the frames and nodes of the last bow_transform_batch_device, frame b against train_src[b] (None: b - 1) under pairs[b];
+        d_taken uint8 [n_frames][kp_capacity] for both sides, or 0; asynchronous."""
+        w = _pairs_array(pairs)
+        src = None if train_src is None else np.ascontiguousarray(train_src, np.int32)
+        self._check(self._lib.ss_match_epi_batch_device(self._h, None if src is None else src.ctypes.data, C.c_void_p(d_taken), w.ctypes.data,
+                                                        C.byref(params), C.c_void_p(d_idx), C.c_void_p(d_d1), C.c_void_p(d_summary)))
+
+    def triangulate_pairs_device(self, d_q: int, d_q_kp: int, d_nq: int, d_t_kp: int, d_nt: int, d_idx: int, n_frames: int,
+                                 rows_per_frame: int, pairs, params: TriParams, d_info: int, d_points: int, d_point_desc: int,
+                                 d_point_rows: int, d_n_points: int, d_summary: int):
+        """triangulates the matches d_idx of n_frames pairs; d_info TRI_INFO_DTYPE [n_frames][rows_per_frame]; the compact
+        d_points (MAP_POINT_DTYPE) / d_point_desc / d_point_rows (int32 pairs) and d_n_points are the blocks match_proj_pairs_device
+        reads; d_summary TRI_SUMMARY_DTYPE; asynchronous."""
+        w = _pairs_array(pairs)
+        if len(w) != n_frames:
+            raise ValueError("one pair per frame")
+        self._check(self._lib.ss_triangulate_pairs_device(self._h, C.c_void_p(d_q), C.c_void_p(d_q_kp), C.c_void_p(d_nq), C.c_void_p(d_t_kp),
+                                                          C.c_void_p(d_nt), C.c_void_p(d_idx), n_frames, rows_per_frame,
+                                                          w.ctypes.data if len(w) else None, C.byref(params), C.c_void_p(d_info),
+                                                          C.c_void_p(d_points), C.c_void_p(d_point_desc), C.c_void_p(d_point_rows),
+                                                          C.c_void_p(d_n_points), C.c_void_p(d_summary)))
+
+    def triangulate_batch_device(self, d_idx: int, pairs, params: TriParams, d_info: int, d_points: int, d_point_desc: int, d_point_rows: int,
+                                 d_n_points: int, d_summary: int, train_src=None):
+        """the same on the frames of the last batch, frame b against train_src[b] (None: b - 1); asynchronous."""
+        w = _pairs_array(pairs)
+        src = None if train_src is None else np.ascontiguousarray(train_src, np.int32)
+        self._check(self._lib.ss_triangulate_batch_device(self._h, None if src is None else src.ctypes.data, C.c_void_p(d_idx), w.ctypes.data,
+                                                          C.byref(params), C.c_void_p(d_info), C.c_void_p(d_points), C.c_void_p(d_point_desc),
+                                                          C.c_void_p(d_point_rows), C.c_void_p(d_n_points), C.c_void_p(d_summary)))
 
     def wait_stream(self, hip_stream: int):
         """Orders this context's stream after everything enqueued so far on another stream of the device."""

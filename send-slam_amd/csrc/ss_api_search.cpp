@@ -1,0 +1,1181 @@
+/*
+ * ss_api_search.cpp -- the search family of the C ABI (include/sendslam_orb.h): guided matching, map-point projection search,
+ * the vocabulary and bag of words, epipolar search and triangulation.  Each has a pairs form on caller arrays, a batch form on the
+ * frames of the last extraction and, for some, a host form.  The context and the helpers they share: ss_ctx.h.
+ */
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "ss_ctx.h"
+#include "ss_epi_steps.h"
+#include "ss_proj_steps.h"
+
+extern "C" {
+
+/* ---- what the forms share ---- */
+/* false, with the error set: a batch form (`entry`) before any extraction */
+static bool have_batch(ss_ctx *c, const char *entry)
+{
+    if (c->have_geom && c->last_n_frames > 0) return true;
+    fail(c, SS_ERR_STATE, std::string(entry) + ": no batch has been extracted");
+    return false;
+}
+
+/* The operands of a batch form with a train table: frame b of the last batch against frame src[b] of it */
+struct batch_operands {
+    int n_frames = 0, kcap = 0;
+    const ss_keypoint *kps = nullptr;
+    const uint8_t *desc = nullptr;
+    const int32_t *n_kp = nullptr, *src = nullptr, *frame_error = nullptr;
+};
+
+/* Fills them once the form (`form`: as its messages name it) has checked its own arguments: the capacity, the train table (checked,
+ * then on the device; NULL: frame b against b - 1), the frame errors */
+static int batch_operands_of(ss_ctx *c, const std::string &form, const int32_t *train_src, batch_operands &o)
+{
+    const int n = c->last_n_frames, kcap = c->hg.kcap;
+    if (kcap > SS_GUIDED_MAX_ROWS) return fail(c, SS_ERR_INVALID_ARG, form + ": kp_capacity " + std::to_string(kcap) + " exceeds SS_GUIDED_MAX_ROWS");
+    for (int b = 0; train_src && b < n; b++)
+        if (train_src[b] < -1 || train_src[b] >= n)
+            return fail(c, SS_ERR_INVALID_ARG, "train_src[" + std::to_string(b) + "] = " + std::to_string(train_src[b]) + " names no frame of the batch (" +
+                                                   std::to_string(n) + "); the " + form + " takes no carry frames");
+    const int rc = upload_train_src(c, train_src, n);
+    if (rc != SS_OK) return rc;
+    o.n_frames = n, o.kcap = kcap;
+    o.kps = c->ws.kps, o.desc = c->ws.desc, o.n_kp = c->ws.n_kp, o.src = c->train_src.as<int32_t>();
+    return flagged_frame_error(c, c->batch_test_flagged, &o.frame_error);
+}
+
+/* a guided call (the BoW match and the epipolar search run on one too) on the frames of the batch, none against itself */
+static void batch_sides(ssk_guided_call &g, const batch_operands &o)
+{
+    g.n_frames = o.n_frames, g.rows = o.kcap;
+    g.q_kp = g.t_kp = o.kps, g.q_desc = g.t_desc = o.desc, g.nq = g.nt = o.n_kp;
+    g.src = o.src, g.frame_error = o.frame_error;
+    g.exclude_same_frame = 1;
+}
+
+/* ... and on the caller arrays of a pairs form */
+static void pairs_sides(ssk_guided_call &g, int n_frames, int rows_per_frame, const void *d_query, const void *d_query_kp, const void *d_n_query,
+                        const void *d_train, const void *d_train_kp, const void *d_n_train)
+{
+    g.n_frames = n_frames, g.rows = rows_per_frame;
+    g.q_kp = (const ss_keypoint *)d_query_kp, g.t_kp = (const ss_keypoint *)d_train_kp;
+    g.q_desc = (const uint8_t *)d_query, g.t_desc = (const uint8_t *)d_train;
+    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
+}
+
+/* the frame (or pair: `counted`) and row counts of a pairs form; n_frames == 0 passes: the form returns SS_OK on it once its other
+ * shape checks are through */
+static int pairs_shape(ss_ctx *c, const std::string &form, const char *counted, int n_frames, int rows_per_frame)
+{
+    if (n_frames < 0 || rows_per_frame < 1) return fail(c, SS_ERR_INVALID_ARG, form + ": bad " + counted + " or row count");
+    if (rows_per_frame > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, form + ": rows_per_frame " + std::to_string(rows_per_frame) + " exceeds SS_GUIDED_MAX_ROWS (" +
+                                               std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    return SS_OK;
+}
+
+static void guided_rule(ssk_guided_call &g, const ss_guided_params *p)
+{
+    g.th = p->th, g.rnum = p->ratio_num, g.rden = p->ratio_den;
+    g.one_to_one = p->one_to_one != 0, g.orientation = p->orientation;
+}
+
+/* The index of the train frames of ix on the grid: sizes the grid from the extent, carves the index and the candidate counts
+ * ([n_frames][cand_rows]) out of c->d_guided_ws, launches k_guided_index as stage `stage` */
+static int grid_index(ss_ctx *c, ssk_guided_call &ix, const char *stage, int extent_w, int extent_h, int cand_rows)
+{
+    ssk_guided_grid(ix, extent_w, extent_h);
+    const size_t frames = (size_t)ix.n_frames;
+    const int rc = carve_from(c, c->d_guided_ws, [&](carve &w) {
+        ix.cell_start = w.take<uint32_t>(frames * (SSK_GUIDED_MAX_CELLS + 1) * sizeof(uint32_t));
+        ix.recs = w.take<void>(frames * ix.rows * 16);
+        ix.n_cand = w.take<int32_t>(frames * cand_rows * sizeof(int32_t));
+    });
+    if (rc != SS_OK) return rc;
+    const int64_t nt = (int64_t)ix.n_frames * ix.rows, n_cells = (int64_t)ix.cols * ix.grid_rows;
+    /* algorithmic bytes: keypoints in, records and cell offsets out */
+    stage_timer t(c, stage, nt * ((int64_t)sizeof(ss_keypoint) + 16) + ix.n_frames * (n_cells + 1) * 4);
+    ssk_guided_index(c->stream, ix);
+    return SS_OK;
+}
+
+/* The index of the train nodes a pairs form brings (BoW match, epipolar search): its two pieces of the workspace being carved, then
+ * the launch as stage `stage` */
+struct node_index {
+    uint64_t *index = nullptr;
+    int32_t *n_index = nullptr;
+};
+static void take_node_index(carve &w, node_index &x, const ssk_guided_call &g)
+{
+    x.index = w.take<uint64_t>((size_t)g.n_frames * g.rows * sizeof(uint64_t));
+    x.n_index = w.take<int32_t>((size_t)g.n_frames * sizeof(int32_t));
+}
+static void index_train_nodes(ss_ctx *c, const char *stage, const ssk_guided_call &g, const int32_t *t_node, const node_index &x)
+{
+    stage_timer t(c, stage, (int64_t)g.n_frames * g.rows * 12);
+    ssk_bow_index(c->stream, t_node, g.nt, nullptr, g.n_frames, g.rows, x.index, x.n_index);
+}
+
+/* One array of a host form: `room` bytes of the form's device buffer, at d once io_send has carved it; `bytes` of it come from
+ * `in` before the device call and go to `out` after it (either NULL, or bytes 0: no copy) */
+struct io_piece {
+    const void *in;
+    void *out;
+    size_t room, bytes;
+    uint8_t *d = nullptr;
+};
+static int io_send(ss_ctx *c, dev_buf<uint8_t> &buf, io_piece *io, int n)
+{
+    const int rc = carve_from(c, buf, [&](carve &w) {
+        for (int k = 0; k < n; k++) io[k].d = w.take<uint8_t>(io[k].room);
+    });
+    if (rc != SS_OK) return rc;
+    for (int k = 0; k < n; k++)
+        if (io[k].in && io[k].bytes) HIP_TRY(c, hipMemcpyAsync(io[k].d, io[k].in, io[k].bytes, hipMemcpyHostToDevice, c->stream));
+    return SS_OK;
+}
+static int io_fetch(ss_ctx *c, const io_piece *io, int n)
+{
+    for (int k = 0; k < n; k++)
+        if (io[k].out && io[k].bytes) HIP_TRY(c, hipMemcpyAsync(io[k].out, io[k].d, io[k].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SS_OK;
+}
+
+/* ---- guided matching (csrc/ss_guided.hip) ---- */
+static int guided_check_params(ss_ctx *c, const ss_guided_params *p)
+{
+    if (!p) return fail(c, SS_ERR_INVALID_ARG, "guided match: params is NULL");
+    if (p->ratio_num < 0 || p->ratio_num > 32767 || p->ratio_den < 0 || p->ratio_den > 32767)
+        return fail(c, SS_ERR_INVALID_ARG, "guided match: ratio_num and ratio_den must be 0 .. 32767 (ratio_den 0 = no ratio test)");
+    if (p->orientation < 0 || p->orientation > 2) return fail(c, SS_ERR_INVALID_ARG, "guided match: orientation must be 0, 1 or 2");
+    return SS_OK;
+}
+
+/* The three launches of a call whose operands, windows and outputs are filled in */
+static int guided_run(ss_ctx *c, ssk_guided_call &g, const ss_guided_params *p, int extent_w, int extent_h)
+{
+    guided_rule(g, p);
+    const int rc = grid_index(c, g, "guided_index", extent_w, extent_h, g.rows);
+    if (rc != SS_OK) return rc;
+    const int64_t nq = (int64_t)g.n_frames * g.rows;
+    {
+        /* per query: its window (or keypoint), its descriptor, the 12 bytes it writes; the records and descriptors it visits depend
+         * on the content and are not counted */
+        stage_timer t(c, "guided_search", nq * ((g.windows ? 16 : (int64_t)sizeof(ss_keypoint)) + SS_DESC_BYTES + 12));
+        ssk_guided_search(c->stream, g);
+    }
+    {
+        /* idx read and written, d1, the candidate count; the two angles of a surviving match on top when orientation is on */
+        stage_timer t(c, "guided_finish", nq * (8 + 2 + 4 + (g.orientation ? 8 : 0)) + g.n_frames * (int64_t)sizeof(ss_guided_summary));
+        ssk_guided_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_match_guided_pairs_device(ss_ctx *c, const void *d_query, const void *d_query_kp, const void *d_n_query, const void *d_train,
+                                 const void *d_train_kp, const void *d_n_train, const void *d_windows, int n_frames, int rows_per_frame,
+                                 const ss_guided_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = guided_check_params(c, p);
+    if (rc != SS_OK) return rc;
+    rc = pairs_shape(c, "guided match", "frame", n_frames, rows_per_frame);
+    if (rc != SS_OK) return rc;
+    if (p->extent_w <= 0 || p->extent_h <= 0) return fail(c, SS_ERR_INVALID_ARG, "guided match: extent_w and extent_h must be > 0");
+    if (n_frames == 0) return SS_OK;
+    if (!d_query || !d_query_kp || !d_n_query || !d_train || !d_train_kp || !d_n_train || !d_windows || !d_idx || !d_d1 || !d_d2 || !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "guided match: NULL buffer");
+    ssk_guided_call g;
+    pairs_sides(g, n_frames, rows_per_frame, d_query, d_query_kp, d_n_query, d_train, d_train_kp, d_n_train);
+    g.windows = (const ss_guided_window *)d_windows;
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
+    g.summary = (ss_guided_summary *)d_summary;
+    return guided_run(c, g, p, p->extent_w, p->extent_h);
+}
+
+int ss_match_guided_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_windows, const ss_guided_params *p, void *d_idx,
+                                 void *d_d1, void *d_d2, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_match_guided_batch_device")) return SS_ERR_STATE;
+    int rc = guided_check_params(c, p);
+    if (rc != SS_OK) return rc;
+    if (!d_idx || !d_d1 || !d_d2 || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "guided match: NULL output buffer");
+    batch_operands o;
+    rc = batch_operands_of(c, "guided match", train_src, o);
+    if (rc != SS_OK) return rc;
+    ssk_guided_call g;
+    batch_sides(g, o);
+    g.windows = (const ss_guided_window *)d_windows;
+    g.dg = c->ws.dg;
+    g.radius = p->radius, g.radius_by_octave = p->radius_by_octave != 0, g.octave_span = p->octave_span;
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
+    g.summary = (ss_guided_summary *)d_summary;
+    return guided_run(c, g, p, c->hg.w, c->hg.h);
+}
+
+int ss_match_guided(ss_ctx *c, const uint8_t *query, const ss_keypoint *query_kp, int n_query, const uint8_t *train,
+                    const ss_keypoint *train_kp, int n_train, const ss_guided_window *windows, const ss_guided_params *p, int32_t *idx,
+                    uint16_t *d1, uint16_t *d2, ss_guided_summary *summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_query < 0 || n_train < 0 || n_query > SS_GUIDED_MAX_ROWS || n_train > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "guided match: n_query and n_train must be 0 .. SS_GUIDED_MAX_ROWS");
+    if ((n_query > 0 && (!query || !query_kp || !windows || !idx || !d1 || !d2)) || (n_train > 0 && (!train || !train_kp)) || !summary)
+        return fail(c, SS_ERR_INVALID_ARG, "guided match: NULL buffer");
+    /* one frame of `rows` rows on both sides; `counts` is on this stack: no return before the stream has read it */
+    const size_t rows = (size_t)std::max(std::max(n_query, n_train), 1), nq = (size_t)n_query, nt = (size_t)n_train, kp = sizeof(ss_keypoint);
+    const int32_t counts[2] = {n_query, n_train};
+    enum { QD, TD, QK, TK, WIN, N, IDX, D1, D2, SUM, PIECES };
+    io_piece io[PIECES] = {{query, nullptr, rows * 32, nq * 32}, {train, nullptr, rows * 32, nt * 32}, {query_kp, nullptr, rows * kp, nq * kp},
+                           {train_kp, nullptr, rows * kp, nt * kp}, {windows, nullptr, rows * sizeof(ss_guided_window), nq * sizeof(ss_guided_window)},
+                           {counts, nullptr, sizeof(counts), sizeof(counts)}, {nullptr, idx, rows * 4, nq * 4}, {nullptr, d1, rows * 2, nq * 2},
+                           {nullptr, d2, rows * 2, nq * 2}, {nullptr, summary, sizeof(ss_guided_summary), sizeof(ss_guided_summary)}};
+    int rc = io_send(c, c->d_guided_io, io, PIECES);
+    if (rc == SS_OK)
+        rc = ss_match_guided_pairs_device(c, io[QD].d, io[QK].d, io[N].d, io[TD].d, io[TK].d, io[N].d + 4, io[WIN].d, 1, (int)rows, p, io[IDX].d, io[D1].d,
+                                          io[D2].d, io[SUM].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
+}
+
+/* ---- map-point projection search (csrc/ss_proj.hip, csrc/ss_proj_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *proj_params_error(const ss_proj_params *p)
+{
+    if (!p) return "projection search: params is NULL";
+    if (!(p->th > 0.0f) || !std::isfinite(p->th)) return "projection search: th must be finite and > 0";
+    if (p->view_cos_limit != p->view_cos_limit) return "projection search: view_cos_limit is NaN";
+    if (p->th_high < 0 || p->th_high > 256) return "projection search: th_high must be 0 .. 256";
+    if (p->ratio_num < 0 || p->ratio_num > 32767 || p->ratio_den < 0 || p->ratio_den > 32767)
+        return "projection search: ratio_num and ratio_den must be 0 .. 32767 (ratio_den 0 = no ratio test)";
+    return nullptr;
+}
+
+int ss_proj_view_init(const ss_camera *cam, const double rcw[9], const double tcw[3], float bf, ss_proj_view *out)
+{
+    if (!cam || !rcw || !tcw || !out) return SS_ERR_INVALID_ARG;
+    for (int k = 0; k < 9; k++) out->rcw[k] = (float)rcw[k];
+    for (int k = 0; k < 3; k++) {
+        out->tcw[k] = (float)tcw[k];
+        out->ow[k] = (float)-((rcw[k] * tcw[0] + rcw[3 + k] * tcw[1]) + rcw[6 + k] * tcw[2]);
+    }
+    out->fx = (float)cam->fx, out->fy = (float)cam->fy, out->cx = (float)cam->cx, out->cy = (float)cam->cy;
+    out->bf = bf;
+    out->min_x = 0.0f, out->max_x = (float)cam->width;
+    out->min_y = 0.0f, out->max_y = (float)cam->height;
+    return SS_OK;
+}
+
+int ss_proj_points_host(const ss_proj_view *view, const ss_proj_params *p, const float *scale, int n_levels, const ss_map_point *points,
+                        int n, ss_proj_point *out)
+{
+    if (proj_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!view || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n < 0 || (n > 0 && (!points || !out))) return SS_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) out[i] = ss_proj_eval(*view, points[i], p->view_cos_limit, p->th, p->far_limit, scale, n_levels);
+    return SS_OK;
+}
+
+/* The checks the device forms share, the tables, then the three launches of a call whose device operands and outputs are filled
+ * in: the index of the train frames (k_guided_index on a guided call over the same arrays), the search, the finish */
+static int proj_run(ss_ctx *c, ssk_proj_call &g, int n_blocks, const ss_proj_view *views, const int32_t *point_src, const ss_proj_params *p,
+                    int extent_w, int extent_h)
+{
+    if (const char *msg = proj_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (g.n_frames < 0 || n_blocks < 0 || g.point_rows < 1 || g.rows < 1) return fail(c, SS_ERR_INVALID_ARG, "projection search: bad frame, block or row count");
+    if (g.point_rows > SS_GUIDED_MAX_ROWS || g.rows > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "projection search: point_rows " + std::to_string(g.point_rows) + " / rows_per_frame " + std::to_string(g.rows) +
+                                               " exceed SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    if (extent_w <= 0 || extent_h <= 0) return fail(c, SS_ERR_INVALID_ARG, "projection search: extent_w and extent_h must be > 0");
+    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
+        return fail(c, SS_ERR_INVALID_ARG, "projection search: the context's n_levels / scale_factor give no pyramid table");
+    if (g.n_frames == 0) return SS_OK;
+    if (!views) return fail(c, SS_ERR_INVALID_ARG, "projection search: views is NULL");
+    for (int b = 0; b < g.n_frames; b++) {
+        const int pb = point_src ? point_src[b] : b;
+        if (pb < 0 || pb >= n_blocks)
+            return fail(c, SS_ERR_INVALID_ARG, std::string(point_src ? "point_src[" : "frame [") + std::to_string(b) + "] = " + std::to_string(pb) +
+                                                   " names no block of points (" + std::to_string(n_blocks) + ")");
+    }
+    if (!g.points || !g.p_desc || !g.np || !g.t_kp || !g.t_desc || !g.nt || !g.idx || !g.d1 || !g.d2 || !g.proj || !g.summary)
+        return fail(c, SS_ERR_INVALID_ARG, "projection search: NULL buffer");
+    if (p->check_right && !g.t_right) return fail(c, SS_ERR_INVALID_ARG, "projection search: check_right needs the right coordinates of the train rows");
+    g.view_cos_limit = p->view_cos_limit, g.th = p->th, g.far_limit = p->far_limit;
+    g.th_high = p->th_high, g.rnum = p->ratio_num, g.rden = p->ratio_den;
+    g.one_to_one = p->one_to_one != 0, g.check_right = p->check_right != 0;
+    g.n_levels = c->params.n_levels;
+    ss_scale_table(c->params.scale_factor, g.n_levels, g.scale);
+    /* the host tables of the call: n_frames views, then n_frames block numbers (point_src NULL: 0, 1, ...) */
+    const size_t views_bytes = (size_t)g.n_frames * sizeof(ss_proj_view);
+    int rc = staged_upload(c, c->proj_tab, views_bytes + (size_t)g.n_frames * sizeof(int32_t), [&](uint8_t *h) {
+        memcpy(h, views, views_bytes);
+        int32_t *src = (int32_t *)(h + views_bytes);
+        for (int b = 0; b < g.n_frames; b++) src[b] = point_src ? point_src[b] : b;
+    });
+    if (rc != SS_OK) return rc;
+    g.views = c->proj_tab.as<ss_proj_view>();
+    g.src = c->proj_tab.as<int32_t>(views_bytes);
+    ssk_guided_call ix; /* the index alone: train keypoints, counts, errors, grid, workspace */
+    ix.n_frames = g.n_frames;
+    ix.rows = g.rows;
+    ix.t_kp = g.t_kp;
+    ix.nt = g.nt;
+    ix.frame_error = g.frame_error;
+    rc = grid_index(c, ix, "proj_index", extent_w, extent_h, g.point_rows);
+    if (rc != SS_OK) return rc;
+    g.shift = ix.shift, g.cols = ix.cols, g.x_max = ix.x_max, g.y_max = ix.y_max;
+    g.cell_start = ix.cell_start, g.recs = ix.recs, g.n_cand = ix.n_cand;
+    const int64_t np = (int64_t)g.n_frames * g.point_rows;
+    {
+        /* per point: the point, its descriptor, the 44 bytes it writes; the records and descriptors it visits depend on the content */
+        stage_timer t(c, "proj_search", np * ((int64_t)sizeof(ss_map_point) + SS_DESC_BYTES + 12 + (int64_t)sizeof(ss_proj_point)));
+        ssk_proj_search(c->stream, g);
+    }
+    {
+        stage_timer t(c, "proj_finish", np * (8 + 2 + 4 + 4) + g.n_frames * (int64_t)sizeof(ss_proj_summary));
+        ssk_proj_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+static void proj_outputs(ssk_proj_call &g, void *d_idx, void *d_d1, void *d_d2, void *d_proj, void *d_summary)
+{
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
+    g.proj = (ss_proj_point *)d_proj;
+    g.summary = (ss_proj_summary *)d_summary;
+}
+
+int ss_match_proj_pairs_device(ss_ctx *c, const void *d_points, const void *d_point_desc, const void *d_n_points, int n_blocks, int point_rows,
+                               const void *d_train, const void *d_train_kp, const void *d_n_train, const void *d_train_right,
+                               const void *d_train_taken, int n_frames, int rows_per_frame, const ss_proj_view *views, const int32_t *point_src,
+                               const ss_proj_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_proj, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    ssk_proj_call g;
+    g.n_frames = n_frames;
+    g.point_rows = point_rows;
+    g.rows = rows_per_frame;
+    g.points = (const ss_map_point *)d_points, g.p_desc = (const uint8_t *)d_point_desc, g.np = (const int32_t *)d_n_points;
+    g.t_kp = (const ss_keypoint *)d_train_kp, g.t_desc = (const uint8_t *)d_train, g.nt = (const int32_t *)d_n_train;
+    g.t_right = (const float *)d_train_right, g.t_taken = (const uint8_t *)d_train_taken;
+    proj_outputs(g, d_idx, d_d1, d_d2, d_proj, d_summary);
+    return proj_run(c, g, n_blocks, views, point_src, p, p ? p->extent_w : 1, p ? p->extent_h : 1);
+}
+
+int ss_match_proj_batch_device(ss_ctx *c, const void *d_points, const void *d_point_desc, const void *d_n_points, int n_blocks, int point_rows,
+                               const void *d_train_right, const void *d_train_taken, const ss_proj_view *views, const int32_t *point_src,
+                               const ss_proj_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_proj, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_match_proj_batch_device")) return SS_ERR_STATE;
+    ssk_proj_call g;
+    g.n_frames = c->last_n_frames;
+    g.point_rows = point_rows;
+    g.rows = c->hg.kcap;
+    g.points = (const ss_map_point *)d_points, g.p_desc = (const uint8_t *)d_point_desc, g.np = (const int32_t *)d_n_points;
+    g.t_kp = c->ws.kps, g.t_desc = c->ws.desc, g.nt = c->ws.n_kp;
+    const int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
+    g.t_right = (const float *)d_train_right, g.t_taken = (const uint8_t *)d_train_taken;
+    proj_outputs(g, d_idx, d_d1, d_d2, d_proj, d_summary);
+    return proj_run(c, g, n_blocks, views, point_src, p, c->hg.w, c->hg.h);
+}
+
+int ss_match_proj(ss_ctx *c, const ss_proj_view *view, const ss_map_point *points, const uint8_t *point_desc, int n_points, const uint8_t *train,
+                  const ss_keypoint *train_kp, int n_train, const float *train_right, const uint8_t *train_taken, const ss_proj_params *p,
+                  int32_t *idx, uint16_t *d1, uint16_t *d2, ss_proj_point *proj, ss_proj_summary *summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_points < 0 || n_train < 0 || n_points > SS_GUIDED_MAX_ROWS || n_train > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "projection search: n_points and n_train must be 0 .. SS_GUIDED_MAX_ROWS");
+    if (!view || (n_points > 0 && (!points || !point_desc || !idx || !d1 || !d2)) || (n_train > 0 && (!train || !train_kp)) || !summary)
+        return fail(c, SS_ERR_INVALID_ARG, "projection search: NULL buffer");
+    /* one block of `pr` points, one train frame of `tr` rows; `counts` is on this stack: no return before the stream has read it */
+    const size_t pr = (size_t)std::max(n_points, 1), tr = (size_t)std::max(n_train, 1), np = (size_t)n_points, nt = (size_t)n_train;
+    const size_t kp = sizeof(ss_keypoint), mp = sizeof(ss_map_point), pp = sizeof(ss_proj_point);
+    const int32_t counts[2] = {n_points, n_train};
+    enum { PT, PD, TD, TK, TR, TT, N, IDX, D1, D2, PJ, SUM, PIECES };
+    io_piece io[PIECES] = {{points, nullptr, pr * mp, np * mp}, {point_desc, nullptr, pr * 32, np * 32}, {train, nullptr, tr * 32, nt * 32},
+                           {train_kp, nullptr, tr * kp, nt * kp}, {train_right, nullptr, tr * 4, nt * 4}, {train_taken, nullptr, tr, nt},
+                           {counts, nullptr, sizeof(counts), sizeof(counts)}, {nullptr, idx, pr * 4, np * 4}, {nullptr, d1, pr * 2, np * 2},
+                           {nullptr, d2, pr * 2, np * 2}, {nullptr, proj, pr * pp, np * pp},
+                           {nullptr, summary, sizeof(ss_proj_summary), sizeof(ss_proj_summary)}};
+    int rc = io_send(c, c->d_proj_io, io, PIECES);
+    /* a side without rows has no array to pass: its count is 0 and nothing of it is read */
+    if (rc == SS_OK)
+        rc = ss_match_proj_pairs_device(c, io[PT].d, io[PD].d, io[N].d, 1, (int)pr, io[TD].d, io[TK].d, io[N].d + 4,
+                                        (train_right || n_train == 0) ? io[TR].d : nullptr, train_taken ? io[TT].d : nullptr, 1, (int)tr, view, nullptr, p,
+                                        io[IDX].d, io[D1].d, io[D2].d, io[PJ].d, io[SUM].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
+}
+
+/* ---- bag of words (csrc/ss_bow.hip) ---- */
+/* The vocabulary tree on the host, indexed by the file's node ids (0 = the root).  parent < own id for every node, so the children
+ * of a node in file order are its children in ascending id: children[child_pos[p] .. child_pos[p] + n_child[p]). */
+struct ss_vocab {
+    int k = 0, L = 0, n_nodes = 0, n_words = 0, max_depth = 0;
+    std::vector<int32_t> parent, n_child, child_pos, children, word, depth;
+    std::vector<double> weight;
+    std::vector<uint8_t> leaf, desc;
+};
+
+static int voc_fail(char *err, int err_bytes, const std::string &msg)
+{
+    if (err && err_bytes > 0) snprintf(err, (size_t)err_bytes, "%s", msg.c_str());
+    return SS_ERR_INVALID_ARG;
+}
+
+/* checks and links a tree whose parent / leaf / desc / weight arrays are filled for the ids 1 .. n */
+static int voc_link(ss_vocab &v, char *err, int err_bytes)
+{
+    const int n = v.n_nodes;
+    if (v.k < 1 || v.k > SS_VOCAB_MAX_K) return voc_fail(err, err_bytes, "vocabulary: k " + std::to_string(v.k) + " is outside 1 .. SS_VOCAB_MAX_K");
+    if (v.L < 1 || v.L > SS_VOCAB_MAX_DEPTH) return voc_fail(err, err_bytes, "vocabulary: L " + std::to_string(v.L) + " is outside 1 .. SS_VOCAB_MAX_DEPTH");
+    if (n < 1) return voc_fail(err, err_bytes, "vocabulary: no nodes");
+    if (n >= SS_VOCAB_MAX_NODES) return voc_fail(err, err_bytes, "vocabulary: more than SS_VOCAB_MAX_NODES nodes");
+    v.n_child.assign((size_t)n + 1, 0);
+    v.depth.assign((size_t)n + 1, 0);
+    v.word.assign((size_t)n + 1, -1);
+    v.leaf[0] = 0;
+    v.parent[0] = -1;
+    v.weight[0] = 0.0;
+    for (int id = 1; id <= n; id++) {
+        const int p = v.parent[id];
+        if (p < 0 || p >= id) return voc_fail(err, err_bytes, "vocabulary: node " + std::to_string(id) + " names parent " + std::to_string(p) + ", which is no earlier node");
+        if (v.leaf[p]) return voc_fail(err, err_bytes, "vocabulary: leaf " + std::to_string(p) + " has a child (node " + std::to_string(id) + ")");
+        if (++v.n_child[p] > v.k) return voc_fail(err, err_bytes, "vocabulary: node " + std::to_string(p) + " has more than k = " + std::to_string(v.k) + " children");
+        v.depth[id] = v.depth[p] + 1;
+        if (v.depth[id] > SS_VOCAB_MAX_DEPTH) return voc_fail(err, err_bytes, "vocabulary: node " + std::to_string(id) + " is deeper than SS_VOCAB_MAX_DEPTH");
+    }
+    v.n_words = v.max_depth = 0;
+    for (int id = 1; id <= n; id++) {
+        if (v.leaf[id]) {
+            v.word[id] = v.n_words++;
+            v.max_depth = std::max(v.max_depth, (int)v.depth[id]);
+        } else {
+            if (v.n_child[id] == 0) return voc_fail(err, err_bytes, "vocabulary: inner node " + std::to_string(id) + " has no children");
+            v.weight[id] = 0.0;
+        }
+    }
+    v.child_pos.assign((size_t)n + 2, 0);
+    for (int id = 0; id <= n; id++) v.child_pos[id + 1] = v.child_pos[id] + v.n_child[id];
+    v.children.assign((size_t)n, 0);
+    std::vector<int32_t> fill(v.child_pos.begin(), v.child_pos.end() - 1);
+    for (int id = 1; id <= n; id++) v.children[fill[v.parent[id]]++] = id;
+    return SS_OK;
+}
+
+static void voc_reserve(ss_vocab &v, size_t n)
+{
+    v.parent.assign(n + 1, 0);
+    v.leaf.assign(n + 1, 0);
+    v.weight.assign(n + 1, 0.0);
+    v.desc.assign((n + 1) * 32, 0);
+}
+
+int ss_vocab_from_arrays(int n_nodes, const int32_t *parent, const uint8_t *is_leaf, const uint8_t *desc, const double *weight, int k, int L,
+                         ss_vocab **out, char *err, int err_bytes)
+{
+    if (!out) return voc_fail(err, err_bytes, "vocabulary: out is NULL");
+    *out = nullptr;
+    if (n_nodes < 1) return voc_fail(err, err_bytes, "vocabulary: no nodes");
+    if (n_nodes >= SS_VOCAB_MAX_NODES) return voc_fail(err, err_bytes, "vocabulary: more than SS_VOCAB_MAX_NODES nodes");
+    if (!parent || !is_leaf || !desc || !weight) return voc_fail(err, err_bytes, "vocabulary: NULL array");
+    ss_vocab *v = new (std::nothrow) ss_vocab;
+    if (!v) return SS_ERR_NO_MEMORY;
+    v->k = k, v->L = L, v->n_nodes = n_nodes;
+    voc_reserve(*v, (size_t)n_nodes);
+    for (int i = 0; i < n_nodes; i++) {
+        v->parent[i + 1] = parent[i];
+        v->leaf[i + 1] = is_leaf[i] != 0;
+        v->weight[i + 1] = weight[i];
+    }
+    memcpy(v->desc.data() + 32, desc, (size_t)n_nodes * 32);
+    const int rc = voc_link(*v, err, err_bytes);
+    if (rc != SS_OK) {
+        delete v;
+        return rc;
+    }
+    *out = v;
+    return SS_OK;
+}
+
+/* the next blank-separated token of [p, end), or false */
+static bool voc_token(const char *&p, const char *end, const char *&tok, size_t &len)
+{
+    while (p < end && (*p == ' ' || *p == '\t' || *p == '\r')) p++;
+    if (p >= end) return false;
+    tok = p;
+    while (p < end && *p != ' ' && *p != '\t' && *p != '\r') p++;
+    len = (size_t)(p - tok);
+    return true;
+}
+
+/* a decimal integer of at most 9 digits with an optional minus sign, nothing else */
+static bool voc_int(const char *tok, size_t len, long &out)
+{
+    size_t i = 0;
+    const bool neg = len > 0 && tok[0] == '-';
+    if (neg) i = 1;
+    if (i >= len || len - i > 9) return false;
+    long v = 0;
+    for (; i < len; i++) {
+        if (tok[i] < '0' || tok[i] > '9') return false;
+        v = v * 10 + (tok[i] - '0');
+    }
+    out = neg ? -v : v;
+    return true;
+}
+
+/* a decimal floating-point literal (digits, sign, point, exponent), correctly rounded by strtod */
+static bool voc_double(const char *tok, size_t len, double &out)
+{
+    char buf[64];
+    if (len == 0 || len >= sizeof(buf)) return false;
+    bool digit = false;
+    for (size_t i = 0; i < len; i++) {
+        const char ch = tok[i];
+        if (ch >= '0' && ch <= '9') digit = true;
+        else if (ch != '+' && ch != '-' && ch != '.' && ch != 'e' && ch != 'E') return false;
+        buf[i] = ch;
+    }
+    buf[len] = 0;
+    if (!digit) return false;
+    char *stop = nullptr;
+    out = strtod(buf, &stop);
+    return stop == buf + len;
+}
+
+int ss_vocab_load_text(const char *path, ss_vocab **out, char *err, int err_bytes)
+{
+    if (!out) return voc_fail(err, err_bytes, "vocabulary: out is NULL");
+    *out = nullptr;
+    if (!path) return voc_fail(err, err_bytes, "vocabulary: path is NULL");
+    std::string text;
+    {
+        std::ifstream in(path, std::ios::binary);
+        if (!in) return voc_fail(err, err_bytes, std::string("vocabulary: cannot open ") + path);
+        std::ostringstream ss;
+        ss << in.rdbuf();
+        text = ss.str();
+    }
+    ss_vocab *v = new (std::nothrow) ss_vocab;
+    if (!v) return SS_ERR_NO_MEMORY;
+    auto bad = [&](long line, const std::string &what) {
+        delete v;
+        return voc_fail(err, err_bytes, "vocabulary: line " + std::to_string(line) + ": " + what);
+    };
+    const char *p = text.data(), *const end = p + text.size();
+    long line = 0, nodes = 0;
+    bool header = false;
+    while (p < end) {
+        const char *le = (const char *)memchr(p, '\n', (size_t)(end - p));
+        if (!le) le = end;
+        const char *q = p, *tok = nullptr;
+        size_t len = 0;
+        p = le < end ? le + 1 : end;
+        line++;
+        if (!voc_token(q, le, tok, len)) continue; /* a blank line */
+        long val[36];
+        const int want = header ? 34 : 4; /* integers of the line; a node line ends with the weight */
+        int got = 0;
+        bool more = false; /* a token behind the integers: tok */
+        do {
+            if (got == want) {
+                more = true;
+                break;
+            }
+            if (!voc_int(tok, len, val[got])) return bad(line, "token " + std::to_string(got + 1) + " is no integer");
+            got++;
+        } while (voc_token(q, le, tok, len));
+        if (got < want || (header && !more)) return bad(line, "truncated: " + std::to_string(got) + " of " + std::to_string(want + (header ? 1 : 0)) + " tokens");
+        if (!header) {
+            if (more) return bad(line, "more than 4 tokens in the header");
+            if (val[2] != 0 || val[3] != 0) return bad(line, "only scoring 0 (L1) with weighting 0 (TF-IDF) is supported");
+            v->k = (int)std::min(std::max(val[0], -1L), (long)SS_VOCAB_MAX_K + 1);
+            v->L = (int)std::min(std::max(val[1], -1L), (long)SS_VOCAB_MAX_DEPTH + 1);
+            header = true;
+            /* at most one node per 70 bytes of text: sizes the arrays once */
+            voc_reserve(*v, std::min(text.size() / 70 + 16, (size_t)SS_VOCAB_MAX_NODES));
+            continue;
+        }
+        /* tok is the 35th token: the weight */
+        double w = 0;
+        if (!voc_double(tok, len, w)) return bad(line, "the weight is no number");
+        if (voc_token(q, le, tok, len)) return bad(line, "more than 35 tokens");
+        if (val[1] != 0 && val[1] != 1) return bad(line, "is_leaf must be 0 or 1");
+        const size_t id = (size_t)++nodes;
+        if (id >= (size_t)SS_VOCAB_MAX_NODES) return bad(line, "more than SS_VOCAB_MAX_NODES nodes");
+        if (id >= v->parent.size()) {
+            const size_t cap = v->parent.size() * 2;
+            v->parent.resize(cap), v->leaf.resize(cap), v->weight.resize(cap), v->desc.resize(cap * 32);
+        }
+        for (int b = 0; b < 32; b++) {
+            if (val[2 + b] < 0 || val[2 + b] > 255) return bad(line, "descriptor byte " + std::to_string(b) + " is outside 0 .. 255");
+            v->desc[id * 32 + b] = (uint8_t)val[2 + b];
+        }
+        v->parent[id] = (int32_t)std::min(std::max(val[0], -1L), (long)SS_VOCAB_MAX_NODES);
+        v->leaf[id] = (uint8_t)val[1];
+        v->weight[id] = w;
+    }
+    if (!header) return bad(line, "no header line");
+    v->n_nodes = (int)nodes;
+    const int rc = voc_link(*v, err, err_bytes);
+    if (rc != SS_OK) {
+        delete v;
+        return rc;
+    }
+    *out = v;
+    return SS_OK;
+}
+
+int ss_vocab_info(const ss_vocab *v, ss_vocab_shape *out)
+{
+    if (!v || !out) return SS_ERR_INVALID_ARG;
+    out->k = v->k, out->L = v->L, out->n_nodes = v->n_nodes, out->n_words = v->n_words, out->max_depth = v->max_depth;
+    return SS_OK;
+}
+
+int ss_vocab_copy_out(const ss_vocab *v, int32_t *first_child, int32_t *n_children, int32_t *word, double *weight, int32_t *depth)
+{
+    if (!v) return SS_ERR_INVALID_ARG;
+    for (int id = 0; id <= v->n_nodes; id++) {
+        if (first_child) first_child[id] = v->n_child[id] ? v->children[v->child_pos[id]] : -1;
+        if (n_children) n_children[id] = v->n_child[id];
+        if (word) word[id] = v->word[id];
+        if (weight) weight[id] = v->weight[id];
+        if (depth) depth[id] = v->depth[id];
+    }
+    return SS_OK;
+}
+
+int ss_vocab_destroy(ss_vocab *v)
+{
+    if (!v) return SS_ERR_INVALID_ARG;
+    delete v;
+    return SS_OK;
+}
+
+int ss_bow_set_vocabulary(ss_ctx *c, const ss_vocab *v)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!v) return fail(c, SS_ERR_INVALID_ARG, "ss_bow_set_vocabulary: voc is NULL");
+    /* breadth first: the children of the node at position u take the next n_child positions, in file order */
+    const size_t n = (size_t)v->n_nodes + 1;
+    std::vector<int32_t> at(n); /* position -> file id */
+    std::vector<ssk_bow_node> recs(n);
+    std::vector<uint8_t> rows(n * 32);
+    std::vector<double> wgt((size_t)v->n_words);
+    size_t next = 1;
+    at[0] = 0;
+    for (size_t u = 0; u < n; u++) {
+        const int id = at[u];
+        ssk_bow_node &r = recs[u];
+        r.child_base = v->n_child[id] ? (int32_t)next : 0;
+        r.n_child = v->n_child[id];
+        r.word = v->word[id];
+        r.file_id = id;
+        memcpy(&rows[u * 32], &v->desc[(size_t)id * 32], 32);
+        if (r.word >= 0) wgt[(size_t)r.word] = v->weight[id];
+        for (int ch = 0; ch < v->n_child[id]; ch++) at[next++] = v->children[v->child_pos[id] + ch];
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->voc = ssk_bow_voc();
+    c->bow_frames = 0;
+    dev_free(c->d_voc);
+    uint8_t *d_rows;
+    ssk_bow_node *d_recs;
+    double *d_wgt;
+    const int rc = carve_from(c, c->d_voc, [&](carve &w) {
+        d_rows = w.take<uint8_t>(n * 32);
+        d_recs = w.take<ssk_bow_node>(n * sizeof(ssk_bow_node));
+        d_wgt = w.take<double>(wgt.size() * sizeof(double) + 8);
+    });
+    if (rc != SS_OK) return rc;
+    HIP_TRY(c, hipMemcpy(d_rows, rows.data(), rows.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_recs, recs.data(), recs.size() * sizeof(ssk_bow_node), hipMemcpyHostToDevice));
+    if (!wgt.empty()) HIP_TRY(c, hipMemcpy(d_wgt, wgt.data(), wgt.size() * sizeof(double), hipMemcpyHostToDevice));
+    c->voc.rows = d_rows;
+    c->voc.recs = d_recs;
+    c->voc.weight = d_wgt;
+    c->voc.L = v->L;
+    c->voc.max_depth = v->max_depth;
+    c->voc.n_words = v->n_words;
+    return SS_OK;
+}
+
+/* the two launches of a transform whose arrays are filled in */
+static int bow_transform_run(ss_ctx *c, ssk_bow_call &b)
+{
+    const int64_t nr = (int64_t)b.n_frames * b.rows;
+    {
+        /* per row: its descriptor and the two ids it writes; the children it visits depend on the tree */
+        stage_timer t(c, "bow_descend", nr * (SS_DESC_BYTES + 8));
+        ssk_bow_descend(c->stream, c->voc, b);
+    }
+    {
+        /* word and node read (the node twice), the vector and the index written */
+        stage_timer t(c, "bow_vector", nr * (12 + 12 + (b.index ? 8 : 0)) + b.n_frames * (int64_t)sizeof(ss_bow_summary));
+        ssk_bow_vector(c->stream, c->voc, b);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_bow_transform_device(ss_ctx *c, const void *d_desc, const void *d_n_rows, int n_frames, int rows_per_frame, int levelsup, void *d_word,
+                            void *d_node, void *d_bow_word, void *d_bow_value, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->voc.rows) return fail(c, SS_ERR_STATE, "ss_bow_transform_device: no vocabulary (ss_bow_set_vocabulary)");
+    if (n_frames < 0 || rows_per_frame < 1 || levelsup < 0) return fail(c, SS_ERR_INVALID_ARG, "bow transform: bad frame count, row count or levelsup");
+    if (rows_per_frame > SS_BOW_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "bow transform: rows_per_frame " + std::to_string(rows_per_frame) + " exceeds SS_BOW_MAX_ROWS (" +
+                                               std::to_string(SS_BOW_MAX_ROWS) + ")");
+    if (n_frames == 0) return SS_OK;
+    if (!d_desc || !d_n_rows || !d_word || !d_node || !d_bow_word || !d_bow_value || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "bow transform: NULL buffer");
+    ssk_bow_call b;
+    b.n_frames = n_frames, b.rows = rows_per_frame, b.levelsup = levelsup;
+    b.desc = (const uint8_t *)d_desc, b.n_rows = (const int32_t *)d_n_rows;
+    b.word = (int32_t *)d_word, b.node = (int32_t *)d_node;
+    b.bow_word = (int32_t *)d_bow_word, b.bow_value = (double *)d_bow_value, b.summary = (ss_bow_summary *)d_summary;
+    return bow_transform_run(c, b);
+}
+
+/* what a batch transform keeps: [index][nodes][index counts] of n frames of kcap rows; p NULL: only the total */
+struct bow_keep {
+    uint64_t *index;
+    int32_t *node, *n_index;
+    size_t total;
+};
+static bow_keep bow_keep_of(uint8_t *p, int n, int kcap)
+{
+    carve w(p);
+    bow_keep k;
+    k.index = w.take<uint64_t>((size_t)n * kcap * sizeof(uint64_t));
+    k.node = w.take<int32_t>((size_t)n * kcap * sizeof(int32_t));
+    k.n_index = w.take<int32_t>((size_t)n * sizeof(int32_t));
+    k.total = w.total();
+    return k;
+}
+
+int ss_bow_transform_batch_device(ss_ctx *c, int levelsup, void *d_word, void *d_node, void *d_bow_word, void *d_bow_value, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!c->voc.rows) return fail(c, SS_ERR_STATE, "ss_bow_transform_batch_device: no vocabulary (ss_bow_set_vocabulary)");
+    if (!have_batch(c, "ss_bow_transform_batch_device")) return SS_ERR_STATE;
+    if (levelsup < 0) return fail(c, SS_ERR_INVALID_ARG, "bow transform: levelsup must be >= 0");
+    if (!d_word || !d_node || !d_bow_word || !d_bow_value || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "bow transform: NULL output buffer");
+    const int n = c->last_n_frames, kcap = c->hg.kcap;
+    if (kcap > SS_BOW_MAX_ROWS) return fail(c, SS_ERR_INVALID_ARG, "bow transform: kp_capacity " + std::to_string(kcap) + " exceeds SS_BOW_MAX_ROWS");
+    c->bow_frames = 0;
+    const int rc = grow(c, c->d_bow_keep, bow_keep_of(nullptr, n, kcap).total);
+    if (rc != SS_OK) return rc;
+    const bow_keep keep = bow_keep_of(c->d_bow_keep.p, n, kcap);
+    ssk_bow_call b;
+    b.n_frames = n, b.rows = kcap, b.levelsup = levelsup;
+    b.desc = c->ws.desc, b.n_rows = c->ws.n_kp;
+    const int rc1 = flagged_frame_error(c, c->batch_test_flagged, &b.frame_error);
+    if (rc1 != SS_OK) return rc1;
+    b.word = (int32_t *)d_word, b.node = (int32_t *)d_node, b.node2 = keep.node;
+    b.bow_word = (int32_t *)d_bow_word, b.bow_value = (double *)d_bow_value, b.summary = (ss_bow_summary *)d_summary;
+    b.index = keep.index, b.n_index = keep.n_index;
+    const int rc2 = bow_transform_run(c, b);
+    if (rc2 == SS_OK) c->bow_frames = n;
+    return rc2;
+}
+
+/* The launches of a BoW match whose operands, query nodes and outputs are filled in: the index of the train nodes where the call
+ * brings its own (t_node != NULL), the search, then guided matching's finish as it is. */
+static int bow_match_run(ss_ctx *c, ssk_guided_call &g, const ss_guided_params *p, const int32_t *q_node, const int32_t *t_node, const uint64_t *index,
+                         const int32_t *n_index)
+{
+    guided_rule(g, p);
+    const size_t nr = (size_t)g.n_frames * g.rows;
+    node_index own;
+    const int rc = carve_from(c, c->d_bow_ws, [&](carve &w) {
+        g.n_cand = w.take<int32_t>(nr * sizeof(int32_t));
+        if (t_node) take_node_index(w, own, g);
+    });
+    if (rc != SS_OK) return rc;
+    if (t_node) {
+        index_train_nodes(c, "bow_index", g, t_node, own);
+        index = own.index, n_index = own.n_index;
+    }
+    {
+        /* per query: its node, its descriptor, the 12 bytes it writes; the keys and descriptors of its run depend on the content */
+        stage_timer t(c, "bow_search", (int64_t)nr * (4 + SS_DESC_BYTES + 12));
+        ssk_bow_search(c->stream, g, q_node, index, n_index);
+    }
+    {
+        stage_timer t(c, "bow_finish", (int64_t)nr * (8 + 2 + 4 + (g.orientation ? 8 : 0)) + g.n_frames * (int64_t)sizeof(ss_guided_summary));
+        ssk_guided_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_match_bow_pairs_device(ss_ctx *c, const void *d_query, const void *d_query_kp, const void *d_query_node, const void *d_n_query,
+                              const void *d_train, const void *d_train_kp, const void *d_train_node, const void *d_n_train, int n_frames,
+                              int rows_per_frame, const ss_guided_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = guided_check_params(c, p);
+    if (rc != SS_OK) return rc;
+    rc = pairs_shape(c, "bow match", "frame", n_frames, rows_per_frame);
+    if (rc != SS_OK) return rc;
+    if (n_frames == 0) return SS_OK;
+    if (!d_query || !d_query_kp || !d_query_node || !d_n_query || !d_train || !d_train_kp || !d_train_node || !d_n_train || !d_idx || !d_d1 || !d_d2 ||
+        !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "bow match: NULL buffer");
+    ssk_guided_call g;
+    pairs_sides(g, n_frames, rows_per_frame, d_query, d_query_kp, d_n_query, d_train, d_train_kp, d_n_train);
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
+    g.summary = (ss_guided_summary *)d_summary;
+    return bow_match_run(c, g, p, (const int32_t *)d_query_node, (const int32_t *)d_train_node, nullptr, nullptr);
+}
+
+int ss_match_bow_batch_device(ss_ctx *c, const int32_t *train_src, const ss_guided_params *p, void *d_idx, void *d_d1, void *d_d2, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_match_bow_batch_device")) return SS_ERR_STATE;
+    if (c->bow_frames != c->last_n_frames)
+        return fail(c, SS_ERR_STATE, "ss_match_bow_batch_device: the last batch has not been through ss_bow_transform_batch_device");
+    int rc = guided_check_params(c, p);
+    if (rc != SS_OK) return rc;
+    if (!d_idx || !d_d1 || !d_d2 || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "bow match: NULL output buffer");
+    batch_operands o;
+    rc = batch_operands_of(c, "bow match", train_src, o);
+    if (rc != SS_OK) return rc;
+    const bow_keep keep = bow_keep_of(c->d_bow_keep.p, o.n_frames, o.kcap);
+    ssk_guided_call g;
+    batch_sides(g, o);
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1, g.d2 = (uint16_t *)d_d2;
+    g.summary = (ss_guided_summary *)d_summary;
+    return bow_match_run(c, g, p, keep.node, nullptr, keep.index, keep.n_index);
+}
+
+int ss_bow_score_device(ss_ctx *c, const void *d_q_word, const void *d_q_value, const void *d_q_count, int q_rows, const void *d_db_word,
+                        const void *d_db_value, const void *d_db_count, int n_db, int stride, void *d_score)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_db < 0 || stride < 1 || q_rows < 1) return fail(c, SS_ERR_INVALID_ARG, "bow score: bad vector count, stride or query size");
+    if (n_db == 0) return SS_OK;
+    if (!d_q_word || !d_q_value || !d_q_count || !d_db_word || !d_db_value || !d_db_count || !d_score) return fail(c, SS_ERR_INVALID_ARG, "bow score: NULL buffer");
+    {
+        /* the allocation of every vector is an upper bound of what is read */
+        stage_timer t(c, "bow_score", (int64_t)n_db * ((int64_t)stride * 12 + 12) + (int64_t)q_rows * 12);
+        ssk_bow_score(c->stream, (const int32_t *)d_q_word, (const double *)d_q_value, (const int32_t *)d_q_count, q_rows, (const int32_t *)d_db_word,
+                      (const double *)d_db_value, (const int32_t *)d_db_count, n_db, stride, (double *)d_score);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+/* ---- epipolar search and triangulation (csrc/ss_epi.hip, csrc/ss_epi_steps.h) ---- */
+int ss_epi_pair_init(const ss_camera *cam1, const double rcw1[9], const double tcw1[3], const ss_camera *cam2, const double rcw2[9],
+                     const double tcw2[3], ss_epi_pair *out)
+{
+    if (!cam1 || !rcw1 || !tcw1 || !cam2 || !rcw2 || !tcw2 || !out) return SS_ERR_INVALID_ARG;
+    ss_epi_pair &w = *out;
+    for (int k = 0; k < 9; k++) w.rcw1[k] = rcw1[k], w.rcw2[k] = rcw2[k];
+    for (int k = 0; k < 3; k++) {
+        w.tcw1[k] = tcw1[k], w.tcw2[k] = tcw2[k];
+        w.ow1[k] = -((rcw1[k] * tcw1[0] + rcw1[3 + k] * tcw1[1]) + rcw1[6 + k] * tcw1[2]);
+        w.ow2[k] = -((rcw2[k] * tcw2[0] + rcw2[3 + k] * tcw2[1]) + rcw2[6 + k] * tcw2[2]);
+    }
+    w.fx1 = cam1->fx, w.fy1 = cam1->fy, w.cx1 = cam1->cx, w.cy1 = cam1->cy, w.invfx1 = 1.0 / cam1->fx, w.invfy1 = 1.0 / cam1->fy;
+    w.fx2 = cam2->fx, w.fy2 = cam2->fy, w.cx2 = cam2->cx, w.cy2 = cam2->cy, w.invfx2 = 1.0 / cam2->fx, w.invfy2 = 1.0 / cam2->fy;
+    const double *R1 = w.rcw1, *R2 = w.rcw2, *t1 = w.tcw1, *t2 = w.tcw2;
+    double R12[3][3], t12[3], E[3][3], G[3][3], F[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R12[i][j] = (R1[3 * i] * R2[3 * j] + R1[3 * i + 1] * R2[3 * j + 1]) + R1[3 * i + 2] * R2[3 * j + 2];
+    for (int i = 0; i < 3; i++) t12[i] = t1[i] - ((R12[i][0] * t2[0] + R12[i][1] * t2[1]) + R12[i][2] * t2[2]);
+    for (int j = 0; j < 3; j++) {
+        E[0][j] = t12[1] * R12[2][j] - t12[2] * R12[1][j];
+        E[1][j] = t12[2] * R12[0][j] - t12[0] * R12[2][j];
+        E[2][j] = t12[0] * R12[1][j] - t12[1] * R12[0][j];
+    }
+    for (int j = 0; j < 3; j++) {
+        G[0][j] = w.invfx1 * E[0][j];
+        G[1][j] = w.invfy1 * E[1][j];
+        G[2][j] = E[2][j] - (w.cx1 * G[0][j] + w.cy1 * G[1][j]);
+    }
+    double m = 0.0;
+    bool finite = true;
+    for (int i = 0; i < 3; i++) {
+        F[i][0] = G[i][0] * w.invfx2;
+        F[i][1] = G[i][1] * w.invfy2;
+        F[i][2] = G[i][2] - (F[i][0] * w.cx2 + F[i][1] * w.cy2);
+        for (int j = 0; j < 3; j++) {
+            const double v = fabs(F[i][j]);
+            if (!(v <= 1.7976931348623157e308)) finite = false;
+            else if (v > m) m = v;
+        }
+    }
+    const bool usable = finite && m > 0.0;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) w.f12[3 * i + j] = usable ? (float)(F[i][j] / m) : 0.0f;
+    double C2[3];
+    for (int i = 0; i < 3; i++) C2[i] = ((R2[3 * i] * w.ow1[0] + R2[3 * i + 1] * w.ow1[1]) + R2[3 * i + 2] * w.ow1[2]) + t2[i];
+    const float ex = (float)((w.fx2 * C2[0]) / C2[2] + w.cx2), ey = (float)((w.fy2 * C2[1]) / C2[2] + w.cy2);
+    w.epipole_test = (std::isfinite(ex) && std::isfinite(ey)) ? 1 : 0;
+    w.ex = w.epipole_test ? ex : 0.0f;
+    w.ey = w.epipole_test ? ey : 0.0f;
+    return SS_OK;
+}
+
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *epi_params_error(const ss_epi_params *p)
+{
+    if (!p) return "epipolar search: params is NULL";
+    if (p->th < 0 || p->th > 256) return "epipolar search: th must be 0 .. 256";
+    if (p->orientation < 0 || p->orientation > 2) return "epipolar search: orientation must be 0, 1 or 2";
+    return nullptr;
+}
+
+int ss_epi_check_host(const ss_epi_pair *pair, const ss_epi_params *p, const float *scale, int n_levels, const ss_keypoint *kp1,
+                      const ss_keypoint *kp2, int n, uint8_t *out)
+{
+    if (epi_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!pair || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n < 0 || (n > 0 && (!kp1 || !kp2 || !out))) return SS_ERR_INVALID_ARG;
+    for (int k = 0; k < n; k++) {
+        const ss_epi_line line = ss_epi_line_of(pair->f12, kp1[k].x, kp1[k].y);
+        out[k] = (uint8_t)ss_epi_check(pair->ex, pair->ey, pair->epipole_test, p->coarse != 0, line, scale, n_levels, kp2[k].x, kp2[k].y, kp2[k].octave);
+    }
+    return SS_OK;
+}
+
+int ss_triangulate_host(const ss_epi_pair *pair, const ss_tri_params *tp, const float *scale, int n_levels, const ss_keypoint *kp1,
+                        const ss_keypoint *kp2, int n, ss_map_point *points, ss_tri_info *info)
+{
+    if (!pair || !tp || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n < 0 || (n > 0 && (!kp1 || !kp2 || !points || !info))) return SS_ERR_INVALID_ARG;
+    for (int k = 0; k < n; k++) {
+        const ss_tri_out r = ss_tri_eval(*pair, *tp, scale, n_levels, kp1[k].x, kp1[k].y, kp1[k].octave, kp2[k].x, kp2[k].y, kp2[k].octave);
+        points[k] = r.point;
+        info[k] = r.info;
+    }
+    return SS_OK;
+}
+
+/* The host pairs of a call -> c->epi_tab, which the search and the triangulation share */
+static int upload_epi_pairs(ss_ctx *c, const ss_epi_pair *pairs, int n)
+{
+    const size_t bytes = (size_t)n * sizeof(ss_epi_pair);
+    return staged_upload(c, c->epi_tab, bytes, [&](uint8_t *h) { memcpy(h, pairs, bytes); });
+}
+
+static int epi_pyramid(ss_ctx *c, int *n_levels, float *scale)
+{
+    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
+        return fail(c, SS_ERR_INVALID_ARG, "epipolar search: the context's n_levels / scale_factor give no pyramid table");
+    *n_levels = c->params.n_levels;
+    ss_scale_table(c->params.scale_factor, *n_levels, scale);
+    return SS_OK;
+}
+
+/* The launches of a search whose operands, counts and outputs are filled in: the index of the train nodes where the call brings its
+ * own (t_node != NULL), the search, guided matching's finish as it is (its summaries go to the workspace), the summaries */
+static int epi_match_run(ss_ctx *c, ssk_guided_call &g, ssk_epi_call &e, const ss_epi_pair *pairs, const ss_epi_params *p, const int32_t *t_node)
+{
+    g.th = p->th, g.rnum = 0, g.rden = 0;
+    g.one_to_one = p->one_to_one != 0, g.orientation = p->orientation;
+    e.coarse = p->coarse != 0;
+    int rc = epi_pyramid(c, &e.n_levels, e.scale);
+    if (rc != SS_OK) return rc;
+    const size_t nr = (size_t)g.n_frames * g.rows;
+    node_index own;
+    rc = carve_from(c, c->d_epi_ws, [&](carve &w) {
+        g.n_cand = w.take<int32_t>(nr * sizeof(int32_t));
+        e.n_geo = w.take<int32_t>(nr * sizeof(int32_t));
+        e.n_near = w.take<int32_t>(nr * sizeof(int32_t));
+        g.summary = w.take<ss_guided_summary>((size_t)g.n_frames * sizeof(ss_guided_summary));
+        if (t_node) take_node_index(w, own, g);
+    });
+    if (rc != SS_OK) return rc;
+    rc = upload_epi_pairs(c, pairs, g.n_frames);
+    if (rc != SS_OK) return rc;
+    e.pairs = c->epi_tab.as<ss_epi_pair>();
+    if (t_node) {
+        index_train_nodes(c, "epi_index", g, t_node, own);
+        e.index = own.index, e.n_index = own.n_index;
+    }
+    {
+        /* per query: its node, keypoint and descriptor, the 18 bytes it writes; what it visits of its run depends on the content */
+        stage_timer t(c, "epi_search", (int64_t)nr * (4 + (int64_t)sizeof(ss_keypoint) + SS_DESC_BYTES + 18));
+        ssk_epi_search(c->stream, g, e);
+    }
+    {
+        stage_timer t(c, "epi_finish", (int64_t)nr * (8 + 2 + 4 + 8 + (g.orientation ? 8 : 0)) + g.n_frames * (int64_t)(sizeof(ss_guided_summary) + sizeof(ss_epi_summary)));
+        ssk_guided_finish(c->stream, g);
+        ssk_epi_summary(c->stream, g, e);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_match_epi_pairs_device(ss_ctx *c, const void *d_query, const void *d_query_kp, const void *d_query_node, const void *d_query_taken,
+                              const void *d_n_query, const void *d_train, const void *d_train_kp, const void *d_train_node,
+                              const void *d_train_taken, const void *d_n_train, int n_frames, int rows_per_frame, const ss_epi_pair *pairs,
+                              const ss_epi_params *p, void *d_idx, void *d_d1, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = epi_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    const int rc = pairs_shape(c, "epipolar search", "pair", n_frames, rows_per_frame);
+    if (rc != SS_OK) return rc;
+    if (n_frames == 0) return SS_OK;
+    if (!d_query || !d_query_kp || !d_query_node || !d_n_query || !d_train || !d_train_kp || !d_train_node || !d_n_train || !pairs || !d_idx || !d_d1 ||
+        !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "epipolar search: NULL buffer");
+    ssk_guided_call g;
+    pairs_sides(g, n_frames, rows_per_frame, d_query, d_query_kp, d_n_query, d_train, d_train_kp, d_n_train);
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1;
+    ssk_epi_call e;
+    e.q_node = (const int32_t *)d_query_node;
+    e.q_taken = (const uint8_t *)d_query_taken, e.t_taken = (const uint8_t *)d_train_taken;
+    e.summary = (ss_epi_summary *)d_summary;
+    return epi_match_run(c, g, e, pairs, p, (const int32_t *)d_train_node);
+}
+
+int ss_match_epi_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_taken, const ss_epi_pair *pairs, const ss_epi_params *p,
+                              void *d_idx, void *d_d1, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_match_epi_batch_device")) return SS_ERR_STATE;
+    if (c->bow_frames != c->last_n_frames)
+        return fail(c, SS_ERR_STATE, "ss_match_epi_batch_device: the last batch has not been through ss_bow_transform_batch_device");
+    if (const char *msg = epi_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (!pairs || !d_idx || !d_d1 || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "epipolar search: NULL buffer");
+    batch_operands o;
+    const int rc = batch_operands_of(c, "epipolar search", train_src, o);
+    if (rc != SS_OK) return rc;
+    const bow_keep keep = bow_keep_of(c->d_bow_keep.p, o.n_frames, o.kcap);
+    ssk_guided_call g;
+    batch_sides(g, o);
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1;
+    ssk_epi_call e;
+    e.q_node = keep.node;
+    e.index = keep.index, e.n_index = keep.n_index;
+    e.q_taken = e.t_taken = (const uint8_t *)d_taken;
+    e.summary = (ss_epi_summary *)d_summary;
+    return epi_match_run(c, g, e, pairs, p, nullptr);
+}
+
+/* the two launches of a triangulation whose operands and outputs are filled in */
+static int tri_run(ss_ctx *c, ssk_tri_call &t, const ss_epi_pair *pairs, const ss_tri_params *tp)
+{
+    t.tp = *tp;
+    int rc = epi_pyramid(c, &t.n_levels, t.scale);
+    if (rc != SS_OK) return rc;
+    const size_t nr = (size_t)t.n_frames * t.rows;
+    rc = grow(c, c->d_tri_ws, nr * sizeof(ss_map_point));
+    if (rc != SS_OK) return rc;
+    rc = upload_epi_pairs(c, pairs, t.n_frames);
+    if (rc != SS_OK) return rc;
+    t.pairs = c->epi_tab.as<ss_epi_pair>();
+    t.tmp = (ss_map_point *)c->d_tri_ws.p;
+    {
+        /* per row: its match, its keypoint and its info; a matched row reads the other keypoint on top */
+        stage_timer s(c, "tri_eval", (int64_t)nr * (4 + (int64_t)sizeof(ss_keypoint) + (int64_t)sizeof(ss_tri_info)));
+        ssk_tri_eval(c->stream, t);
+    }
+    {
+        /* the states read; what a point moves (its 32 bytes twice, its descriptor twice, its rows) depends on the content */
+        stage_timer s(c, "tri_compact", (int64_t)nr * 4 + t.n_frames * (int64_t)(sizeof(ss_tri_summary) + 4));
+        ssk_tri_compact(c->stream, t);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+static void tri_outputs(ssk_tri_call &t, void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points, void *d_summary)
+{
+    t.info = (ss_tri_info *)d_info;
+    t.points = (ss_map_point *)d_points, t.point_desc = (uint8_t *)d_point_desc, t.point_rows = (int32_t *)d_point_rows;
+    t.n_points = (int32_t *)d_n_points;
+    t.summary = (ss_tri_summary *)d_summary;
+}
+
+int ss_triangulate_pairs_device(ss_ctx *c, const void *d_query, const void *d_query_kp, const void *d_n_query, const void *d_train_kp,
+                                const void *d_n_train, const void *d_idx, int n_frames, int rows_per_frame, const ss_epi_pair *pairs,
+                                const ss_tri_params *tp, void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points,
+                                void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!tp) return fail(c, SS_ERR_INVALID_ARG, "triangulation: params is NULL");
+    const int rc = pairs_shape(c, "triangulation", "pair", n_frames, rows_per_frame);
+    if (rc != SS_OK) return rc;
+    if (n_frames == 0) return SS_OK;
+    if (!d_query || !d_query_kp || !d_n_query || !d_train_kp || !d_n_train || !d_idx || !pairs || !d_info || !d_points || !d_point_desc || !d_point_rows ||
+        !d_n_points || !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "triangulation: NULL buffer");
+    ssk_tri_call t;
+    t.n_frames = n_frames;
+    t.rows = rows_per_frame;
+    t.q_kp = (const ss_keypoint *)d_query_kp, t.t_kp = (const ss_keypoint *)d_train_kp;
+    t.q_desc = (const uint8_t *)d_query;
+    t.nq = (const int32_t *)d_n_query, t.nt = (const int32_t *)d_n_train;
+    t.idx = (const int32_t *)d_idx;
+    tri_outputs(t, d_info, d_points, d_point_desc, d_point_rows, d_n_points, d_summary);
+    return tri_run(c, t, pairs, tp);
+}
+
+int ss_triangulate_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_idx, const ss_epi_pair *pairs, const ss_tri_params *tp,
+                                void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_triangulate_batch_device")) return SS_ERR_STATE;
+    if (!tp) return fail(c, SS_ERR_INVALID_ARG, "triangulation: params is NULL");
+    if (!d_idx || !pairs || !d_info || !d_points || !d_point_desc || !d_point_rows || !d_n_points || !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "triangulation: NULL buffer");
+    batch_operands o;
+    const int rc = batch_operands_of(c, "triangulation", train_src, o);
+    if (rc != SS_OK) return rc;
+    ssk_tri_call t;
+    t.n_frames = o.n_frames;
+    t.rows = o.kcap;
+    t.q_kp = t.t_kp = o.kps;
+    t.q_desc = o.desc;
+    t.nq = t.nt = o.n_kp;
+    t.src = o.src;
+    t.frame_error = o.frame_error;
+    t.idx = (const int32_t *)d_idx;
+    tri_outputs(t, d_info, d_points, d_point_desc, d_point_rows, d_n_points, d_summary);
+    return tri_run(c, t, pairs, tp);
+}
+
+} /* extern "C" */

@@ -1,7 +1,7 @@
 /*
  * ss_epi_steps.h -- the steps of the epipolar search and of the triangulation (the rule: include/sendslam_orb.h; DESIGN.md
  * section 18): the epipole and epipolar-line tests of one couple in float32, steps 1 - 9 of one match with its map point in
- * double.  The kernels (ss_epi.hip), the host twins ss_epi_check_host / ss_triangulate_host (ss_api.cpp) and
+ * double.  The kernels (ss_epi.hip), the host twins ss_epi_check_host / ss_triangulate_host (ss_api_search.cpp) and
  * tests/native/epi_steps_asan.cpp compile this text.
  *
  * Every step is one IEEE operation, left to right as written; every test is in its accepting form, so a NaN fails it.  Compile

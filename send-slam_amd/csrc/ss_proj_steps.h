@@ -1,6 +1,6 @@
 /*
  * ss_proj_steps.h -- steps 1 - 3 of the map-point projection search (the rule: include/sendslam_orb.h):
- * frustum, predicted level, window.  k_proj_search (ss_proj.hip), the host twin ss_proj_points_host (ss_api.cpp) and
+ * frustum, predicted level, window.  k_proj_search (ss_proj.hip), the host twin ss_proj_points_host (ss_api_search.cpp) and
  * tests/native/proj_steps_asan.cpp compile this text.
  *
  * Every float step is one float32 IEEE operation, left to right as written; every test is in its accepting form, so a NaN

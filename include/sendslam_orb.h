@@ -42,6 +42,8 @@
  *                              L1Scoring::score (KeyFrameDatabase) inside TrackMonocular :594
  *   ss_proj_* / ss_match_proj* Tracking::SearchLocalPoints: Frame::isInFrustum, MapPoint::PredictScale and
  *                              ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>&, th) inside TrackMonocular :594
+ *   ss_fuse_* / ss_match_fuse* ORBmatcher::Fuse (LocalMapping::SearchInNeighbors), its Sim3 form (LoopClosing::SearchAndFuse) and
+ *                              the Sim3 SearchByProjection of the loop and merge candidate check
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
  *   ss_last_error              the cerr diagnostics of the shim (:457-469, :523-551)
  *
@@ -884,6 +886,121 @@ int ss_triangulate_pairs_device(ss_ctx *ctx, const void *d_query, const void *d_
  * train_src[b] (ss_match_guided_batch_device's table; -1: no train, every row -1).  A flagged frame on either side voids the pair. */
 int ss_triangulate_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_idx, const ss_epi_pair *pairs, const ss_tri_params *tp,
                                 void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points, void *d_summary);
+
+/* ---- map-point fusion: ORBmatcher::Fuse(pKF, vpMapPoints, th) of LocalMapping::SearchInNeighbors, Fuse(pKF, Scw, ...) of
+ * LoopClosing::SearchAndFuse and SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) of the loop and merge
+ * candidate check.  Neither upstream source is in the reference tree.  This is the library's own restatement and parity with the
+ * real binary stays unpinned, as for the guided, bag-of-words, projection and epipolar stages.  tests/fuse_ref.py is its normative
+ * statement; DESIGN.md section 19.  An addition to ABI 5: nothing existing changes ---------------------------------------------
+ * - Every float step is one float32 IEEE operation, left to right as written, with no contraction.
+ * - Every test is written in its accepting form, so a NaN fails it.
+ * Inputs.  Per frame: one ss_proj_view, the struct as it is (an SE3 pose through ss_proj_view_init, a Sim3 through
+ * ss_fuse_view_sim3: the kernel never sees a Sim3), and the train side of ss_match_proj_*.  Per map point: one ss_map_point, its
+ * descriptor and, optionally, skip[frame][i] (uint8; upstream's isBad(), IsInKeyFrame(pKF) and spAlreadyFound).  Per train row, all
+ * optional: right[j] (float), taken[j] (uint8: vpMatched[idx] of the Sim3 SearchByProjection), train_point[j] (int32: the caller's
+ * id of the map point the row already carries, < 0 for none).
+ * 1. The point.  The state is the number of the first failing test, 0 if none fails.  A rejected point gets floats 0.0f and level
+ *    -1.  Rows at or past the count get state -1.
+ *    1. State 1: skip is given and is non-zero.
+ *    2. State 2: pc = R.P + t, formed as in the projection search.  The test is pc.z > 0.
+ *       Deviation: upstream rejects z < 0 only, so a point at z == 0 goes on with an infinite invz.
+ *    3. State 3: u and v are formed as in the projection search.  The test is u >= min_x && u < max_x && v >= min_y && v < max_y:
+ *       KeyFrame::IsInImage, strict at the upper bound (Frame::isInFrustum of the projection search is closed there).
+ *    4. State 4: dist is formed as in the projection search.  The test is dist >= 0.8f*min_dist && dist <= 1.2f*max_dist.
+ *    5. State 5: dot = (po.x*nx + po.y*ny) + po.z*nz.  The test is dot >= view_cos_limit * dist.  There is no division, as
+ *       upstream's PO.dot(Pn) < 0.5*dist3D.
+ *    Then level is the projection search's table rule on max_dist / dist; radius = th * scale[level] (its 2.5 / 4.0 factor does
+ *    not apply); u_right = u - bf*invz.
+ * 2. Candidates.  A candidate is a train row j < n_train that passes, in this order:
+ *    1. max(level-1, 0) <= octave_j <= level.  An octave outside the table is never a candidate (test 4 reads scale[octave_j]; the
+ *       projection search accepts octave -1 at level 0).
+ *    2. fabsf(x_j - u) < radius && fabsf(y_j - v) < radius.
+ *    3. If taken is given, taken[j] == 0.
+ *    4. Only when chi2_mono > 0: ex = u - x_j, ey = v - y_j, e2 = ex*ex + ey*ey.  If check_right is set and right[j] >= 0:
+ *       er = u_right - right[j], e2 = e2 + er*er and the limit is chi2_stereo; otherwise the limit is chi2_mono.  Accept iff
+ *       e2 <= limit * (scale[octave_j]*scale[octave_j]).
+ *       Deviation, as in the triangulation: upstream multiplies e2 by invLevelSigma2 and rejects on >.
+ *    A Hamming distance is taken only for a row that passed all four; n_candidates counts exactly those rows.
+ * 3. Best.  The key is distance << 20 | j; the best is the lowest key; d1 is its distance.  The point names row idx iff
+ *    d1 <= th_low.  Deviation: at equal distance upstream keeps the first row in its grid scan order.
+ * 4. Outcome, one ss_fuse_action per point.  The rule is order-free; upstream walks the points in sequence and mutates the keyframe
+ *    as it goes.
+ *      SS_FUSE_NONE       no row named                                                                          other -1
+ *      SS_FUSE_REPLACE    train_point is given and train_point[idx] >= 0                                        other = that id
+ *      SS_FUSE_ADD        the row is free, and this point holds the lowest d1 << 20 | i among the frame's
+ *                         points that name the row                                                              other -1
+ *      SS_FUSE_DUPLICATE  the row is free, and another point row w holds the lowest key                         other = w, a
+ *                                                                                                   point row of the same block
+ *    Deviation: every point that names an occupied row gets REPLACE; where one row has several points, upstream fuses the second
+ *    with whatever the first left there.
+ *    Deviation: upstream lets the first point in order add and fuses later ones into it; here the closest point adds.
+ * Outputs per point row: idx int32 (-1: none); d1 uint16 (0xFFFF: no candidate); ss_fuse_action; ss_fuse_point, 32 bytes.
+ * Outputs per frame: ss_fuse_summary, 32 bytes. */
+#define SS_FUSE_NONE 0
+#define SS_FUSE_ADD 1
+#define SS_FUSE_REPLACE 2
+#define SS_FUSE_DUPLICATE 3
+typedef struct {          /* 32 bytes, one per point row */
+    float u, v, u_right, dot, dist, radius;
+    int32_t level, state;
+} ss_fuse_point;
+typedef struct {          /* 8 bytes, one per point row */
+    int32_t action, other;
+} ss_fuse_action;
+typedef struct {          /* 40 bytes */
+    float view_cos_limit; /* upstream: 0.5; NaN is SS_ERR_INVALID_ARG */
+    float th;             /* finite and > 0; upstream: 3.0 in local mapping, 4.0 in SearchAndFuse, 8 in the candidate check */
+    float chi2_mono;      /* upstream: 5.99; not > 0 (zero, negative, NaN): no test 2.4, which is the Sim3 forms */
+    float chi2_stereo;    /* upstream: 7.8; must be finite and > 0 when both chi2_mono > 0 and check_right */
+    int32_t th_low;       /* 0 .. 256; upstream: 50, or 50*ratioHamming */
+    int32_t check_right;  /* test 2.4 uses right[j] */
+    int32_t extent_w, extent_h; /* as in ss_proj_params */
+    int32_t reserved[2];  /* must be 0 */
+} ss_fuse_params;
+typedef struct {          /* 32 bytes, one per frame */
+    int32_t status;       /* SS_OK, or the frame_error that voided the frame (all rows "none", counts 0) */
+    int32_t n_points, n_train;
+    int32_t n_in_view;    /* points with state 0 */
+    int32_t n_candidates; /* Hamming distances taken */
+    int32_t n_add, n_replace, n_duplicate;
+} ss_fuse_summary;
+/* The view of a camera under upstream's Sim3 Scw = [s.R | t], needs no device.  In double, in this order:
+ * s = sqrt((m0*m0 + m1*m1) + m2*m2) of row 0 of srcw; R[k] = srcw[k] / s; t[k] = t[k] / s; then exactly ss_proj_view_init(cam, R, t,
+ * bf, out).  SS_ERR_INVALID_ARG if s is not finite or not > 0, or a pointer is NULL.  An SE3 caller uses ss_proj_view_init. */
+int ss_fuse_view_sim3(const ss_camera *cam, const double srcw[9], const double t[3], float bf, ss_proj_view *out);
+/* Host twins of steps 1 and 2 (the text the kernel compiles, csrc/ss_fuse_steps.h); neither needs a device.  scale: n_levels
+ * entries, 1 <= n_levels <= SS_MAX_LEVELS.  p is checked as the device calls check it (SS_ERR_INVALID_ARG).
+ * ss_fuse_points_host: out[i] is what the device calls write for point i; skip: n flags, or NULL.
+ * ss_fuse_check_host: step 2 of the n couples (points[k], kp[k]) with right[k] (NULL: no row has a right coordinate) and
+ * taken[k] (NULL: none is taken); out[k] is 0 for a candidate, else the number 1 .. 4 of the first failing test. */
+int ss_fuse_points_host(const ss_proj_view *view, const ss_fuse_params *p, const float *scale, int n_levels, const ss_map_point *points,
+                        const uint8_t *skip, int n, ss_fuse_point *out);
+int ss_fuse_check_host(const ss_fuse_params *p, const float *scale, int n_levels, const ss_fuse_point *points, const ss_keypoint *kp,
+                       const float *right, const uint8_t *taken, int n, uint8_t *out);
+/* n_frames frames on caller-supplied device arrays: the arrays, HOST tables (views, point_src) and rules of
+ * ss_match_proj_pairs_device, plus d_point_skip (uint8 [n_frames][point_rows], NULL: none) and d_train_point (int32
+ * [n_frames][rows_per_frame], NULL: every row is free).  Outputs [n_frames][point_rows]: d_idx (int32), d_d1 (uint16), d_fuse
+ * (ss_fuse_action), d_point (ss_fuse_point); d_summary [n_frames] ss_fuse_summary.  SS_ERR_INVALID_ARG: either row count above
+ * SS_GUIDED_MAX_ROWS, th not > 0 or not finite, a NaN view_cos_limit, th_low outside 0 .. 256, chi2_stereo not finite or not > 0
+ * where it is used, a reserved field that is not 0, a point_src entry outside 0 .. n_blocks - 1, extent_w or extent_h <= 0,
+ * check_right without d_train_right, a NULL buffer.  Asynchronous on the context's stream. */
+int ss_match_fuse_pairs_device(ss_ctx *ctx, const void *d_points, const void *d_point_desc, const void *d_n_points, int n_blocks,
+                               int point_rows, const void *d_point_skip, const void *d_train, const void *d_train_kp,
+                               const void *d_n_train, const void *d_train_right, const void *d_train_taken, const void *d_train_point,
+                               int n_frames, int rows_per_frame, const ss_proj_view *views, const int32_t *point_src,
+                               const ss_fuse_params *p, void *d_idx, void *d_d1, void *d_fuse, void *d_point, void *d_summary);
+/* The same, the train side being the frames of the last ss_extract_batch_device batch (SS_ERR_STATE without one; n_frames and
+ * kp_capacity are the batch's).  A frame whose frame_error is set gets that status in its summary and all its rows are "none". */
+int ss_match_fuse_batch_device(ss_ctx *ctx, const void *d_points, const void *d_point_desc, const void *d_n_points, int n_blocks,
+                               int point_rows, const void *d_point_skip, const void *d_train_right, const void *d_train_taken,
+                               const void *d_train_point, const ss_proj_view *views, const int32_t *point_src, const ss_fuse_params *p,
+                               void *d_idx, void *d_d1, void *d_fuse, void *d_point, void *d_summary);
+/* One frame with host pointers in and out (copy in, the pairs form, copy out), synchronous.  n_points, n_train <=
+ * SS_GUIDED_MAX_ROWS; point_skip, train_right, train_taken and train_point may be NULL; point may be NULL. */
+int ss_match_fuse(ss_ctx *ctx, const ss_proj_view *view, const ss_map_point *points, const uint8_t *point_desc, const uint8_t *point_skip,
+                  int n_points, const uint8_t *train, const ss_keypoint *train_kp, int n_train, const float *train_right,
+                  const uint8_t *train_taken, const int32_t *train_point, const ss_fuse_params *p, int32_t *idx, uint16_t *d1,
+                  ss_fuse_action *fuse, ss_fuse_point *point, ss_fuse_summary *summary);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

@@ -1,6 +1,6 @@
 /*
  * ss_api_search.cpp -- the search family of the C ABI (include/sendslam_orb.h): guided matching, map-point projection search,
- * the vocabulary and bag of words, epipolar search and triangulation.  Each has a pairs form on caller arrays, a batch form on the
+ * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation.  Each has a pairs form on caller arrays, a batch form on the
  * frames of the last extraction and, for some, a host form.  The context and the helpers they share: ss_ctx.h.
  */
 #include <algorithm>
@@ -15,6 +15,7 @@
 
 #include "ss_ctx.h"
 #include "ss_epi_steps.h"
+#include "ss_fuse_steps.h"
 #include "ss_proj_steps.h"
 
 extern "C" {
@@ -293,33 +294,34 @@ int ss_proj_points_host(const ss_proj_view *view, const ss_proj_params *p, const
     return SS_OK;
 }
 
-/* The checks the device forms share, the tables, then the three launches of a call whose device operands and outputs are filled
- * in: the index of the train frames (k_guided_index on a guided call over the same arrays), the search, the finish */
-static int proj_run(ss_ctx *c, ssk_proj_call &g, int n_blocks, const ss_proj_view *views, const int32_t *point_src, const ss_proj_params *p,
-                    int extent_w, int extent_h)
+/* What a call of blocks of points searched by frames needs before its search is launched, for the projection search and fusion
+ * (Call is ssk_proj_call or ssk_fuse_call; `what` heads the messages): the checks the device forms share, the pyramid table, the
+ * staged table of views and block numbers, and the index of the train frames (k_guided_index on a guided call over the same arrays,
+ * timed as `index_stage`).  `buffers` says that no operand or output the call needs is NULL.  A call of no frames returns SS_OK and
+ * launches nothing: the caller returns with it */
+extern "C++" template <class Call>
+static int points_call_prepare(ss_ctx *c, Call &g, const std::string &what, const char *index_stage, int n_blocks, const ss_proj_view *views,
+                               const int32_t *point_src, bool buffers, bool check_right, int extent_w, int extent_h)
 {
-    if (const char *msg = proj_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
-    if (g.n_frames < 0 || n_blocks < 0 || g.point_rows < 1 || g.rows < 1) return fail(c, SS_ERR_INVALID_ARG, "projection search: bad frame, block or row count");
+    if (g.n_frames < 0 || n_blocks < 0 || g.point_rows < 1 || g.rows < 1) return fail(c, SS_ERR_INVALID_ARG, what + ": bad frame, block or row count");
     if (g.point_rows > SS_GUIDED_MAX_ROWS || g.rows > SS_GUIDED_MAX_ROWS)
-        return fail(c, SS_ERR_INVALID_ARG, "projection search: point_rows " + std::to_string(g.point_rows) + " / rows_per_frame " + std::to_string(g.rows) +
+        return fail(c, SS_ERR_INVALID_ARG, what + ": point_rows " + std::to_string(g.point_rows) + " / rows_per_frame " + std::to_string(g.rows) +
                                                " exceed SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")");
-    if (extent_w <= 0 || extent_h <= 0) return fail(c, SS_ERR_INVALID_ARG, "projection search: extent_w and extent_h must be > 0");
+    if (extent_w <= 0 || extent_h <= 0) return fail(c, SS_ERR_INVALID_ARG, what + ": extent_w and extent_h must be > 0");
     if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
-        return fail(c, SS_ERR_INVALID_ARG, "projection search: the context's n_levels / scale_factor give no pyramid table");
+        return fail(c, SS_ERR_INVALID_ARG, what + ": the context's n_levels / scale_factor give no pyramid table");
     if (g.n_frames == 0) return SS_OK;
-    if (!views) return fail(c, SS_ERR_INVALID_ARG, "projection search: views is NULL");
+    if (!views) return fail(c, SS_ERR_INVALID_ARG, what + ": views is NULL");
     for (int b = 0; b < g.n_frames; b++) {
         const int pb = point_src ? point_src[b] : b;
         if (pb < 0 || pb >= n_blocks)
             return fail(c, SS_ERR_INVALID_ARG, std::string(point_src ? "point_src[" : "frame [") + std::to_string(b) + "] = " + std::to_string(pb) +
                                                    " names no block of points (" + std::to_string(n_blocks) + ")");
     }
-    if (!g.points || !g.p_desc || !g.np || !g.t_kp || !g.t_desc || !g.nt || !g.idx || !g.d1 || !g.d2 || !g.proj || !g.summary)
-        return fail(c, SS_ERR_INVALID_ARG, "projection search: NULL buffer");
-    if (p->check_right && !g.t_right) return fail(c, SS_ERR_INVALID_ARG, "projection search: check_right needs the right coordinates of the train rows");
-    g.view_cos_limit = p->view_cos_limit, g.th = p->th, g.far_limit = p->far_limit;
-    g.th_high = p->th_high, g.rnum = p->ratio_num, g.rden = p->ratio_den;
-    g.one_to_one = p->one_to_one != 0, g.check_right = p->check_right != 0;
+    if (!buffers || !g.points || !g.p_desc || !g.np || !g.t_kp || !g.t_desc || !g.nt || !g.idx || !g.d1 || !g.summary)
+        return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
+    if (check_right && !g.t_right) return fail(c, SS_ERR_INVALID_ARG, what + ": check_right needs the right coordinates of the train rows");
+    g.check_right = check_right;
     g.n_levels = c->params.n_levels;
     ss_scale_table(c->params.scale_factor, g.n_levels, g.scale);
     /* the host tables of the call: n_frames views, then n_frames block numbers (point_src NULL: 0, 1, ...) */
@@ -338,10 +340,25 @@ static int proj_run(ss_ctx *c, ssk_proj_call &g, int n_blocks, const ss_proj_vie
     ix.t_kp = g.t_kp;
     ix.nt = g.nt;
     ix.frame_error = g.frame_error;
-    rc = grid_index(c, ix, "proj_index", extent_w, extent_h, g.point_rows);
+    rc = grid_index(c, ix, index_stage, extent_w, extent_h, g.point_rows);
     if (rc != SS_OK) return rc;
     g.shift = ix.shift, g.cols = ix.cols, g.x_max = ix.x_max, g.y_max = ix.y_max;
     g.cell_start = ix.cell_start, g.recs = ix.recs, g.n_cand = ix.n_cand;
+    return SS_OK;
+}
+
+/* The three launches of a call whose device operands and outputs are filled in: the index of the train frames, the search, the
+ * finish */
+static int proj_run(ss_ctx *c, ssk_proj_call &g, int n_blocks, const ss_proj_view *views, const int32_t *point_src, const ss_proj_params *p,
+                    int extent_w, int extent_h)
+{
+    if (const char *msg = proj_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    const int rc = points_call_prepare(c, g, "projection search", "proj_index", n_blocks, views, point_src, g.d2 && g.proj, p->check_right != 0, extent_w,
+                                       extent_h);
+    if (rc != SS_OK || g.n_frames == 0) return rc;
+    g.view_cos_limit = p->view_cos_limit, g.th = p->th, g.far_limit = p->far_limit;
+    g.th_high = p->th_high, g.rnum = p->ratio_num, g.rden = p->ratio_den;
+    g.one_to_one = p->one_to_one != 0;
     const int64_t np = (int64_t)g.n_frames * g.point_rows;
     {
         /* per point: the point, its descriptor, the 44 bytes it writes; the records and descriptors it visits depend on the content */
@@ -427,6 +444,166 @@ int ss_match_proj(ss_ctx *c, const ss_proj_view *view, const ss_map_point *point
         rc = ss_match_proj_pairs_device(c, io[PT].d, io[PD].d, io[N].d, 1, (int)pr, io[TD].d, io[TK].d, io[N].d + 4,
                                         (train_right || n_train == 0) ? io[TR].d : nullptr, train_taken ? io[TT].d : nullptr, 1, (int)tr, view, nullptr, p,
                                         io[IDX].d, io[D1].d, io[D2].d, io[PJ].d, io[SUM].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
+}
+
+/* ---- map-point fusion (csrc/ss_fuse.hip, csrc/ss_fuse_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *fuse_params_error(const ss_fuse_params *p)
+{
+    if (!p) return "fusion: params is NULL";
+    if (!(p->th > 0.0f) || !std::isfinite(p->th)) return "fusion: th must be finite and > 0";
+    if (p->view_cos_limit != p->view_cos_limit) return "fusion: view_cos_limit is NaN";
+    if (p->th_low < 0 || p->th_low > 256) return "fusion: th_low must be 0 .. 256";
+    if (p->chi2_mono > 0.0f && p->check_right && (!(p->chi2_stereo > 0.0f) || !std::isfinite(p->chi2_stereo)))
+        return "fusion: chi2_stereo must be finite and > 0 when chi2_mono > 0 and check_right is set";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return "fusion: the reserved fields must be 0";
+    return nullptr;
+}
+
+int ss_fuse_view_sim3(const ss_camera *cam, const double srcw[9], const double t[3], float bf, ss_proj_view *out)
+{
+    if (!cam || !srcw || !t || !out) return SS_ERR_INVALID_ARG;
+    const double s = sqrt((srcw[0] * srcw[0] + srcw[1] * srcw[1]) + srcw[2] * srcw[2]);
+    if (!(s > 0.0) || !std::isfinite(s)) return SS_ERR_INVALID_ARG;
+    double r[9], tc[3];
+    for (int k = 0; k < 9; k++) r[k] = srcw[k] / s;
+    for (int k = 0; k < 3; k++) tc[k] = t[k] / s;
+    return ss_proj_view_init(cam, r, tc, bf, out);
+}
+
+int ss_fuse_points_host(const ss_proj_view *view, const ss_fuse_params *p, const float *scale, int n_levels, const ss_map_point *points,
+                        const uint8_t *skip, int n, ss_fuse_point *out)
+{
+    if (fuse_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!view || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n < 0 || (n > 0 && (!points || !out))) return SS_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) out[i] = ss_fuse_eval(*view, points[i], skip ? skip[i] : 0, p->view_cos_limit, p->th, scale, n_levels);
+    return SS_OK;
+}
+
+int ss_fuse_check_host(const ss_fuse_params *p, const float *scale, int n_levels, const ss_fuse_point *points, const ss_keypoint *kp,
+                       const float *right, const uint8_t *taken, int n, uint8_t *out)
+{
+    if (fuse_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n < 0 || (n > 0 && (!points || !kp || !out))) return SS_ERR_INVALID_ARG;
+    for (int k = 0; k < n; k++) {
+        float s_lo, s_hi;
+        ss_fuse_scales(scale, n_levels, points[k].level, &s_lo, &s_hi);
+        out[k] = (uint8_t)ss_fuse_check(points[k], s_lo, s_hi, kp[k].x, kp[k].y, kp[k].octave, k, taken, right, p->chi2_mono, p->chi2_stereo,
+                                        p->check_right != 0);
+    }
+    return SS_OK;
+}
+
+/* The three launches of a fusion call, as proj_run.  The host tables go through the projection search's staged table and the index
+ * through guided matching's workspace: all of it is on the context's one stream */
+static int fuse_run(ss_ctx *c, ssk_fuse_call &g, int n_blocks, const ss_proj_view *views, const int32_t *point_src, const ss_fuse_params *p,
+                    int extent_w, int extent_h)
+{
+    if (const char *msg = fuse_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    const int rc = points_call_prepare(c, g, "fusion", "fuse_index", n_blocks, views, point_src, g.fuse && g.point, p->check_right != 0, extent_w, extent_h);
+    if (rc != SS_OK || g.n_frames == 0) return rc;
+    g.view_cos_limit = p->view_cos_limit, g.th = p->th;
+    g.chi2_mono = p->chi2_mono, g.chi2_stereo = p->chi2_stereo;
+    g.th_low = p->th_low;
+    const int64_t np = (int64_t)g.n_frames * g.point_rows;
+    {
+        /* per point: the point, its descriptor, its flag, the 42 bytes it writes; the records and descriptors it visits depend on the
+         * content */
+        stage_timer t(c, "fuse_search", np * ((int64_t)sizeof(ss_map_point) + SS_DESC_BYTES + (g.p_skip ? 1 : 0) + 10 + (int64_t)sizeof(ss_fuse_point)));
+        ssk_fuse_search(c->stream, g);
+    }
+    {
+        /* idx, d1, the candidate count and the state read, the action written; the id of a named row on top */
+        stage_timer t(c, "fuse_finish", np * (4 + 2 + 4 + 4 + 8 + (g.t_point ? 4 : 0)) + g.n_frames * (int64_t)sizeof(ss_fuse_summary));
+        ssk_fuse_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+static void fuse_outputs(ssk_fuse_call &g, void *d_idx, void *d_d1, void *d_fuse, void *d_point, void *d_summary)
+{
+    g.idx = (int32_t *)d_idx, g.d1 = (uint16_t *)d_d1;
+    g.fuse = (ss_fuse_action *)d_fuse;
+    g.point = (ss_fuse_point *)d_point;
+    g.summary = (ss_fuse_summary *)d_summary;
+}
+
+int ss_match_fuse_pairs_device(ss_ctx *c, const void *d_points, const void *d_point_desc, const void *d_n_points, int n_blocks, int point_rows,
+                               const void *d_point_skip, const void *d_train, const void *d_train_kp, const void *d_n_train,
+                               const void *d_train_right, const void *d_train_taken, const void *d_train_point, int n_frames, int rows_per_frame,
+                               const ss_proj_view *views, const int32_t *point_src, const ss_fuse_params *p, void *d_idx, void *d_d1, void *d_fuse,
+                               void *d_point, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    ssk_fuse_call g;
+    g.n_frames = n_frames;
+    g.point_rows = point_rows;
+    g.rows = rows_per_frame;
+    g.points = (const ss_map_point *)d_points, g.p_desc = (const uint8_t *)d_point_desc, g.np = (const int32_t *)d_n_points;
+    g.p_skip = (const uint8_t *)d_point_skip;
+    g.t_kp = (const ss_keypoint *)d_train_kp, g.t_desc = (const uint8_t *)d_train, g.nt = (const int32_t *)d_n_train;
+    g.t_right = (const float *)d_train_right, g.t_taken = (const uint8_t *)d_train_taken, g.t_point = (const int32_t *)d_train_point;
+    fuse_outputs(g, d_idx, d_d1, d_fuse, d_point, d_summary);
+    return fuse_run(c, g, n_blocks, views, point_src, p, p ? p->extent_w : 1, p ? p->extent_h : 1);
+}
+
+int ss_match_fuse_batch_device(ss_ctx *c, const void *d_points, const void *d_point_desc, const void *d_n_points, int n_blocks, int point_rows,
+                               const void *d_point_skip, const void *d_train_right, const void *d_train_taken, const void *d_train_point,
+                               const ss_proj_view *views, const int32_t *point_src, const ss_fuse_params *p, void *d_idx, void *d_d1, void *d_fuse,
+                               void *d_point, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_match_fuse_batch_device")) return SS_ERR_STATE;
+    ssk_fuse_call g;
+    g.n_frames = c->last_n_frames;
+    g.point_rows = point_rows;
+    g.rows = c->hg.kcap;
+    g.points = (const ss_map_point *)d_points, g.p_desc = (const uint8_t *)d_point_desc, g.np = (const int32_t *)d_n_points;
+    g.p_skip = (const uint8_t *)d_point_skip;
+    g.t_kp = c->ws.kps, g.t_desc = c->ws.desc, g.nt = c->ws.n_kp;
+    const int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
+    g.t_right = (const float *)d_train_right, g.t_taken = (const uint8_t *)d_train_taken, g.t_point = (const int32_t *)d_train_point;
+    fuse_outputs(g, d_idx, d_d1, d_fuse, d_point, d_summary);
+    return fuse_run(c, g, n_blocks, views, point_src, p, c->hg.w, c->hg.h);
+}
+
+int ss_match_fuse(ss_ctx *c, const ss_proj_view *view, const ss_map_point *points, const uint8_t *point_desc, const uint8_t *point_skip, int n_points,
+                  const uint8_t *train, const ss_keypoint *train_kp, int n_train, const float *train_right, const uint8_t *train_taken,
+                  const int32_t *train_point, const ss_fuse_params *p, int32_t *idx, uint16_t *d1, ss_fuse_action *fuse, ss_fuse_point *point,
+                  ss_fuse_summary *summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_points < 0 || n_train < 0 || n_points > SS_GUIDED_MAX_ROWS || n_train > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "fusion: n_points and n_train must be 0 .. SS_GUIDED_MAX_ROWS");
+    if (!view || (n_points > 0 && (!points || !point_desc || !idx || !d1 || !fuse)) || (n_train > 0 && (!train || !train_kp)) || !summary)
+        return fail(c, SS_ERR_INVALID_ARG, "fusion: NULL buffer");
+    /* one block of `pr` points, one train frame of `tr` rows; `counts` is on this stack: no return before the stream has read it */
+    const size_t pr = (size_t)std::max(n_points, 1), tr = (size_t)std::max(n_train, 1), np = (size_t)n_points, nt = (size_t)n_train;
+    const size_t kp = sizeof(ss_keypoint), mp = sizeof(ss_map_point), fp = sizeof(ss_fuse_point), fa = sizeof(ss_fuse_action);
+    const int32_t counts[2] = {n_points, n_train};
+    enum { PT, PD, PS, TD, TK, TR, TT, TP, N, IDX, D1, FU, FP, SUM, PIECES };
+    io_piece io[PIECES] = {{points, nullptr, pr * mp, np * mp}, {point_desc, nullptr, pr * 32, np * 32}, {point_skip, nullptr, pr, np},
+                           {train, nullptr, tr * 32, nt * 32}, {train_kp, nullptr, tr * kp, nt * kp}, {train_right, nullptr, tr * 4, nt * 4},
+                           {train_taken, nullptr, tr, nt}, {train_point, nullptr, tr * 4, nt * 4}, {counts, nullptr, sizeof(counts), sizeof(counts)},
+                           {nullptr, idx, pr * 4, np * 4}, {nullptr, d1, pr * 2, np * 2}, {nullptr, fuse, pr * fa, np * fa},
+                           {nullptr, point, pr * fp, np * fp}, {nullptr, summary, sizeof(ss_fuse_summary), sizeof(ss_fuse_summary)}};
+    int rc = io_send(c, c->d_proj_io, io, PIECES);
+    /* a side without rows has no array to pass: its count is 0 and nothing of it is read */
+    if (rc == SS_OK)
+        rc = ss_match_fuse_pairs_device(c, io[PT].d, io[PD].d, io[N].d, 1, (int)pr, point_skip ? io[PS].d : nullptr, io[TD].d, io[TK].d, io[N].d + 4,
+                                        (train_right || n_train == 0) ? io[TR].d : nullptr, train_taken ? io[TT].d : nullptr,
+                                        train_point ? io[TP].d : nullptr, 1, (int)tr, view, nullptr, p, io[IDX].d, io[D1].d, io[FU].d, io[FP].d,
+                                        io[SUM].d);
     if (rc != SS_OK) {
         (void)hipStreamSynchronize(c->stream);
         return rc;

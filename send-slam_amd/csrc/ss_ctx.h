@@ -131,7 +131,7 @@ struct ss_ctx {
     /* guided matching: the grid index and candidate counts of a call (grid_index carves them; the projection search uses the same
      * buffer); the host form's device copies */
     dev_buf<uint8_t> d_guided_ws, d_guided_io;
-    /* projection search: the host form's device copies; the views, then the block numbers of a call */
+    /* projection search and map-point fusion: the host form's device copies; the views, then the block numbers of a call */
     dev_buf<uint8_t> d_proj_io;
     staged_table proj_tab;
     /* bag of words: the vocabulary on the device (one allocation: rows, records, weights), the node index of a pairs call, and

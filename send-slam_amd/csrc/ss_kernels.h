@@ -214,6 +214,43 @@ struct ssk_proj_call {
 };
 void ssk_proj_search(hipStream_t s, const ssk_proj_call &g);
 void ssk_proj_finish(hipStream_t s, const ssk_proj_call &g);
+/* ss_fuse.hip: map-point fusion (DESIGN.md "Map-point fusion").  The operands of a projection call (blocks of points searched by
+ * frames, the train side, the index of the guided call) plus the skip flags of the points ([n_frames][point_rows]) and the map-point
+ * ids the train rows already carry ([n_frames][rows]).  search evaluates step 1 of every point, walks the cells and writes the best
+ * row, its distance, the candidate count and the ss_fuse_point; finish turns them into one action per point and the summaries. */
+struct ssk_fuse_call {
+    int n_frames = 0, point_rows = 0, rows = 0;
+    const ss_map_point *points = nullptr;
+    const uint8_t *p_desc = nullptr;
+    const int32_t *np = nullptr;
+    const uint8_t *p_skip = nullptr;     /* [n_frames][point_rows], or NULL */
+    const int32_t *src = nullptr;        /* device int32 [n_frames], or NULL: block b */
+    const ss_proj_view *views = nullptr; /* device [n_frames] */
+    const ss_keypoint *t_kp = nullptr;
+    const uint8_t *t_desc = nullptr;
+    const int32_t *nt = nullptr;
+    const int32_t *frame_error = nullptr; /* per train frame, or NULL */
+    const float *t_right = nullptr;       /* [n_frames][rows], or NULL */
+    const uint8_t *t_taken = nullptr;     /* [n_frames][rows], or NULL */
+    const int32_t *t_point = nullptr;     /* [n_frames][rows], or NULL */
+    float view_cos_limit = 0, th = 0, chi2_mono = 0, chi2_stereo = 0;
+    int th_low = 0, check_right = 0;
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    /* the grid and the index of the guided call */
+    int shift = 0, cols = 1;
+    float x_max = 0, y_max = 0;
+    const uint32_t *cell_start = nullptr;
+    const void *recs = nullptr;
+    int32_t *n_cand = nullptr; /* workspace [n_frames][point_rows] */
+    int32_t *idx = nullptr;
+    uint16_t *d1 = nullptr;
+    ss_fuse_action *fuse = nullptr;
+    ss_fuse_point *point = nullptr;
+    ss_fuse_summary *summary = nullptr;
+};
+void ssk_fuse_search(hipStream_t s, const ssk_fuse_call &g);
+void ssk_fuse_finish(hipStream_t s, const ssk_fuse_call &g);
 /* ss_bow.hip: vocabulary descent, BoW vectors, the node index and search of SearchByBoW, the L1 score (DESIGN.md "Bag of
  * words").  The vocabulary on the device, nodes numbered breadth first (0 = the root) so that a node's children are consecutive:
  * rows [n][32] descriptors, recs [n] ssk_bow_node, weight [n_words] doubles by word id. */

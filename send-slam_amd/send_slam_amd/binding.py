@@ -45,7 +45,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_match_bow_batch_device", "ss_bow_score_device", "ss_proj_view_init", "ss_proj_points_host",
            "ss_match_proj_pairs_device", "ss_match_proj_batch_device", "ss_match_proj", "ss_epi_pair_init", "ss_epi_check_host",
            "ss_triangulate_host", "ss_match_epi_pairs_device", "ss_match_epi_batch_device", "ss_triangulate_pairs_device",
-           "ss_triangulate_batch_device"]
+           "ss_triangulate_batch_device", "ss_fuse_view_sim3", "ss_fuse_points_host", "ss_fuse_check_host",
+           "ss_match_fuse_pairs_device", "ss_match_fuse_batch_device", "ss_match_fuse"]
 
 
 class OrbParams(C.Structure):
@@ -213,6 +214,84 @@ def proj_points_host(view, params: ProjParams, scale, points: np.ndarray) -> np.
                                     out.ctypes.data if len(pts) else None)
     if rc != SS_OK:
         raise OrbError(rc, "ss_proj_points_host refused its arguments")
+    return out
+
+
+SS_FUSE_NONE, SS_FUSE_ADD, SS_FUSE_REPLACE, SS_FUSE_DUPLICATE = 0, 1, 2, 3
+
+
+class FuseParams(C.Structure):
+    _fields_ = [("view_cos_limit", C.c_float), ("th", C.c_float), ("chi2_mono", C.c_float), ("chi2_stereo", C.c_float),
+                ("th_low", C.c_int32), ("check_right", C.c_int32), ("extent_w", C.c_int32), ("extent_h", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class FuseSummary(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_points", C.c_int32), ("n_train", C.c_int32), ("n_in_view", C.c_int32),
+                ("n_candidates", C.c_int32), ("n_add", C.c_int32), ("n_replace", C.c_int32), ("n_duplicate", C.c_int32)]
+
+
+# ss_fuse_point and ss_fuse_action: one per point row of the outputs
+FUSE_POINT_DTYPE = np.dtype([(n, "<f4") for n in ("u", "v", "u_right", "dot", "dist", "radius")] + [("level", "<i4"), ("state", "<i4")])
+FUSE_ACTION_DTYPE = np.dtype([("action", "<i4"), ("other", "<i4")])
+FUSE_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n, _ in FuseSummary._fields_])
+
+
+def fuse_params(view_cos_limit: float = 0.5, th: float = 3.0, chi2_mono: float = 5.99, chi2_stereo: float = 7.8, th_low: int = 50,
+                check_right: bool = False, extent_w: int = 0, extent_h: int = 0, reserved=(0, 0)) -> FuseParams:
+    """upstream's Fuse in local mapping: 0.5, th 3, chi-square 5.99 / 7.8, TH_LOW 50.  The Sim3 forms: chi2_mono 0 (no chi-square
+    test), th 4 (SearchAndFuse) or 8 (the candidate check), th_low 50 or 50 * ratioHamming"""
+    return FuseParams(view_cos_limit=view_cos_limit, th=th, chi2_mono=chi2_mono, chi2_stereo=chi2_stereo, th_low=th_low,
+                      check_right=int(check_right), extent_w=extent_w, extent_h=extent_h, reserved=(C.c_int32 * 2)(*reserved))
+
+
+def fuse_view_sim3(camera: Camera, srcw, t, bf: float = 0.0) -> ProjView:
+    """ss_fuse_view_sim3: the view of `camera` under upstream's Sim3 Scw = [s.R | t] (srcw 3 x 3 row-major); needs no device"""
+    r = np.ascontiguousarray(srcw, np.float64).reshape(9)
+    tt = np.ascontiguousarray(t, np.float64).reshape(3)
+    v = ProjView()
+    rc = load().ss_fuse_view_sim3(C.byref(camera), r.ctypes.data, tt.ctypes.data, C.c_float(bf), C.byref(v))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_fuse_view_sim3 refused its arguments")
+    return v
+
+
+def fuse_points_host(view, params: FuseParams, scale, points: np.ndarray, skip=None) -> np.ndarray:
+    """ss_fuse_points_host: step 1 of every map point on the host (the text the kernel compiles) -> FUSE_POINT_DTYPE rows; needs no
+    device"""
+    v = _views_array(view)
+    if len(v) != 1:
+        raise ValueError("one view")
+    sc = np.ascontiguousarray(scale, np.float32)
+    pts = np.ascontiguousarray(points, MAP_POINT_DTYPE)
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    if sk is not None and len(sk) != len(pts):
+        raise ValueError("one skip flag per point")
+    out = np.empty(len(pts), FUSE_POINT_DTYPE)
+    rc = load().ss_fuse_points_host(v.ctypes.data, C.byref(params), sc.ctypes.data, len(sc), pts.ctypes.data if len(pts) else None,
+                                    None if sk is None or not len(pts) else sk.ctypes.data, len(pts), out.ctypes.data if len(pts) else None)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_fuse_points_host refused its arguments")
+    return out
+
+
+def fuse_check_host(params: FuseParams, scale, points: np.ndarray, kp: np.ndarray, right=None, taken=None) -> np.ndarray:
+    """ss_fuse_check_host: step 2 of the couples (points[k] FUSE_POINT_DTYPE, kp[k], right[k], taken[k]) on the host (the text the
+    kernel compiles) -> uint8, 0 a candidate, else the number 1 .. 4 of the first failing test; needs no device"""
+    sc = np.ascontiguousarray(scale, np.float32)
+    pts = np.ascontiguousarray(points, FUSE_POINT_DTYPE)
+    k = np.ascontiguousarray(kp, KP_DTYPE)
+    n = len(pts)
+    r = None if right is None else np.ascontiguousarray(right, np.float32)
+    tk = None if taken is None else np.ascontiguousarray(taken, np.uint8)
+    if len(k) != n or (r is not None and len(r) != n) or (tk is not None and len(tk) != n):
+        raise ValueError("one keypoint, right coordinate and taken flag per couple")
+    out = np.empty(n, np.uint8)
+    rc = load().ss_fuse_check_host(C.byref(params), sc.ctypes.data, len(sc), pts.ctypes.data if n else None, k.ctypes.data if n else None,
+                                   None if r is None or not n else r.ctypes.data, None if tk is None or not n else tk.ctypes.data, n,
+                                   out.ctypes.data if n else None)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_fuse_check_host refused its arguments")
     return out
 
 
@@ -472,6 +551,16 @@ def load():
     lib.ss_match_epi_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EpiParams)] + [C.c_void_p] * 3
     lib.ss_triangulate_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.POINTER(TriParams)] + [C.c_void_p] * 6
     lib.ss_triangulate_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TriParams)] + [C.c_void_p] * 6
+    lib.ss_fuse_view_sim3.argtypes = [C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_float, C.POINTER(ProjView)]
+    lib.ss_fuse_points_host.argtypes = [C.c_void_p, C.POINTER(FuseParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.ss_fuse_check_host.argtypes = [C.POINTER(FuseParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_void_p]
+    lib.ss_match_fuse_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_int] + \
+                                              [C.c_void_p, C.c_void_p, C.POINTER(FuseParams)] + [C.c_void_p] * 5
+    lib.ss_match_fuse_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(FuseParams)] + \
+                                              [C.c_void_p] * 5
+    lib.ss_match_fuse.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + \
+                                 [C.POINTER(FuseParams)] + [C.c_void_p] * 4 + [C.POINTER(FuseSummary)]
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -957,6 +1046,59 @@ class OrbContext:
                                             C.byref(params), idx.ctypes.data, d1.ctypes.data, d2.ctypes.data, proj.ctypes.data if n else None,
                                             C.byref(summ)))
         return idx, d1, d2, proj, {n_: getattr(summ, n_) for n_, _ in ProjSummary._fields_}
+
+    # ---- map-point fusion: Fuse and the Sim3 projection search (the rule: include/sendslam_orb.h) ----
+    def match_fuse_pairs_device(self, d_points: int, d_point_desc: int, d_n_points: int, n_blocks: int, point_rows: int, d_train: int,
+                                d_train_kp: int, d_n_train: int, n_frames: int, rows_per_frame: int, views, params: FuseParams, d_idx: int,
+                                d_d1: int, d_fuse: int, d_point: int, d_summary: int, point_src=None, d_point_skip: int = 0,
+                                d_train_right: int = 0, d_train_taken: int = 0, d_train_point: int = 0):
+        """n_frames frames on device arrays, laid out as for match_proj_pairs_device, plus d_point_skip (uint8 [n_frames][point_rows])
+        and d_train_point (int32 [n_frames][rows_per_frame]); outputs [n_frames][point_rows]: d_idx, d_d1, d_fuse FUSE_ACTION_DTYPE,
+        d_point FUSE_POINT_DTYPE; d_summary FUSE_SUMMARY_DTYPE; asynchronous."""
+        v, src = self._proj_tables(views, point_src, n_frames)
+        self._check(self._lib.ss_match_fuse_pairs_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_desc), C.c_void_p(d_n_points), n_blocks,
+                                                         point_rows, C.c_void_p(d_point_skip), C.c_void_p(d_train), C.c_void_p(d_train_kp),
+                                                         C.c_void_p(d_n_train), C.c_void_p(d_train_right), C.c_void_p(d_train_taken),
+                                                         C.c_void_p(d_train_point), n_frames, rows_per_frame, v.ctypes.data if len(v) else None,
+                                                         None if src is None else src.ctypes.data, C.byref(params), C.c_void_p(d_idx),
+                                                         C.c_void_p(d_d1), C.c_void_p(d_fuse), C.c_void_p(d_point), C.c_void_p(d_summary)))
+
+    def match_fuse_batch_device(self, d_points: int, d_point_desc: int, d_n_points: int, n_blocks: int, point_rows: int, views,
+                                params: FuseParams, d_idx: int, d_d1: int, d_fuse: int, d_point: int, d_summary: int, point_src=None,
+                                d_point_skip: int = 0, d_train_right: int = 0, d_train_taken: int = 0, d_train_point: int = 0):
+        """the same against the frames of the last batch (one view per frame of it; the train-row arrays [n_frames][kp_capacity]);
+        asynchronous."""
+        v, src = self._proj_tables(views, point_src)
+        self._check(self._lib.ss_match_fuse_batch_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_desc), C.c_void_p(d_n_points), n_blocks,
+                                                         point_rows, C.c_void_p(d_point_skip), C.c_void_p(d_train_right), C.c_void_p(d_train_taken),
+                                                         C.c_void_p(d_train_point), v.ctypes.data, None if src is None else src.ctypes.data,
+                                                         C.byref(params), C.c_void_p(d_idx), C.c_void_p(d_d1), C.c_void_p(d_fuse),
+                                                         C.c_void_p(d_point), C.c_void_p(d_summary)))
+
+    def match_fuse(self, view: ProjView, points: np.ndarray, point_desc: np.ndarray, t: np.ndarray, t_kp: np.ndarray, params: FuseParams,
+                   skip=None, right=None, taken=None, train_point=None):
+        """One frame, host arrays in and out -> (idx, d1, FUSE_ACTION_DTYPE rows, FUSE_POINT_DTYPE rows, summary dict)."""
+        v = _views_array(view)
+        pts = np.ascontiguousarray(points, MAP_POINT_DTYPE)
+        pd = np.ascontiguousarray(point_desc, np.uint8).reshape(-1, 32)
+        t = np.ascontiguousarray(t, np.uint8).reshape(-1, 32)
+        t_kp = np.ascontiguousarray(t_kp, KP_DTYPE)
+        n, nt = len(pts), len(t)
+        skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        right = None if right is None else np.ascontiguousarray(right, np.float32)
+        taken = None if taken is None else np.ascontiguousarray(taken, np.uint8)
+        train_point = None if train_point is None else np.ascontiguousarray(train_point, np.int32)
+        if len(v) != 1 or len(pd) != n or len(t_kp) != nt or (skip is not None and len(skip) != n) or \
+                any(a is not None and len(a) != nt for a in (right, taken, train_point)):
+            raise ValueError("points, descriptors, flags, keypoints, right coordinates and ids differ in length")
+        idx, d1 = np.empty(n, np.int32), np.empty(n, np.uint16)
+        fuse, point, summ = np.empty(n, FUSE_ACTION_DTYPE), np.empty(n, FUSE_POINT_DTYPE), FuseSummary()
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        self._check(self._lib.ss_match_fuse(self._h, v.ctypes.data, pts.ctypes.data if n else None, pd.ctypes.data if n else None, ptr(skip), n,
+                                            t.ctypes.data if nt else None, t_kp.ctypes.data if nt else None, nt, ptr(right), ptr(taken),
+                                            ptr(train_point), C.byref(params), idx.ctypes.data, d1.ctypes.data, fuse.ctypes.data,
+                                            point.ctypes.data if n else None, C.byref(summ)))
+        return idx, d1, fuse, point, {n_: getattr(summ, n_) for n_, _ in FuseSummary._fields_}
 
     # ---- bag of words: vocabulary transform, SearchByBoW, L1 score (the rule: include/sendslam_orb.h) ----
     def set_vocabulary(self, voc: Vocabulary):

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Kernel-by-kernel comparison of the gfx950 code objects of two builds of csrc/ss_kernels.hip: instruction streams,
-the .rodata section (kernel descriptors, constant tables) and the per-kernel metadata the streams do not show.
+"""Kernel-by-kernel comparison of two gfx950 device objects, usually two builds of one source of csrc/ (ss_kernels.hip, ss_guided.hip,
+...): instruction streams, the .rodata section (kernel descriptors, constant tables) and the per-kernel metadata the streams do
+not show.
 
-    hipcc --offload-arch=gfx950 <Makefile CXXFLAGS> --cuda-device-only -c csrc/ss_kernels.hip -o before.co   (parent commit)
-    hipcc ... -o after.co                                                                                   (this tree)
+    hipcc --offload-arch=gfx950 <Makefile CXXFLAGS> --cuda-device-only -c csrc/<source>.hip -o before.co   (parent commit)
+    hipcc ... -o after.co                                                                                 (this tree)
     python3 profiles/tools/isa_diff.py before.co after.co
 
 Runs on a machine without a GPU.  The batch matchers gained a table form through a trailing

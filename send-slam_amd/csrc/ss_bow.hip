@@ -9,8 +9,9 @@
  *                       counts and values (w added to itself), ONE thread walks the norm in ascending word order, everybody
  *                       divides; then the keys node << 32 | row sorted the same way are the frame's node index
  *        k_bow_index    the node index alone, for caller-made nodes
- *   B-C  k_bow_search   four lanes per query: binary search for the run of its node in the train frame's index, then the lane
- *                       scheme, the fold and the acceptance test of k_guided_search; k_guided_finish runs on what it writes
+ *   B-C  k_bow_search   four lanes per query: binary search for the run of its node in the train frame's index (gd_walk_node,
+ *                       ss_quad.h), then the lane scheme, the fold (gd_fold_second) and the acceptance test of k_guided_search;
+ *                       k_guided_finish runs on what it writes
  *   B-D  k_bow_score    one wave per database vector: every lane looks its word up in the query (binary search), the terms of
  *                       the common words are added in ascending order, one double addition at a time
  *
@@ -21,13 +22,13 @@
 
 #include "ss_constants.h"
 #include "ss_kernels.h"
+#include "ss_quad.h"
 
 namespace {
 
 #define BW_LANES 8      /* lanes per row of k_bow_descend */
 #define BW_SORT 16384   /* keys one workgroup sorts: SS_BOW_MAX_ROWS */
 #define BW_T 1024       /* threads of k_bow_vector / k_bow_index */
-#define BW_NONE 0xFFFFFFFFu
 #define BW_PAD 0xFFFFFFFFFFFFFFFFull /* sorts behind every key: a row is < 2^32 - 1 */
 
 static_assert(SS_BOW_MAX_ROWS == BW_SORT, "the LDS sort holds SS_BOW_MAX_ROWS keys");
@@ -39,13 +40,6 @@ __device__ __forceinline__ int bw_count(const int32_t *n_rows, const int32_t *fr
     return min(max(n_rows[f], 0), rows);
 }
 
-__device__ __forceinline__ uint32_t bw_hamming(uint64_t q0, uint64_t q1, uint64_t q2, uint64_t q3, const uint8_t *row)
-{
-    const uint4 ta = ((const uint4 *)row)[0], tb = ((const uint4 *)row)[1];
-    return (uint32_t)(__popcll(q0 ^ ((uint64_t)ta.x | ((uint64_t)ta.y << 32))) + __popcll(q1 ^ ((uint64_t)ta.z | ((uint64_t)ta.w << 32))) +
-                      __popcll(q2 ^ ((uint64_t)tb.x | ((uint64_t)tb.y << 32))) + __popcll(q3 ^ ((uint64_t)tb.z | ((uint64_t)tb.w << 32))));
-}
-
 /* B-A.  grid (ceil(rows / 32), frames), 256 threads; every row < rows is written.  The loop is uniform over the wave (a row
  * that has reached its leaf idles), so all 64 lanes take part in every fold; max_depth bounds it whatever the tables hold. */
 __global__ __launch_bounds__(256) void k_bow_descend(ssk_bow_voc v, ssk_bow_call c)
@@ -54,13 +48,11 @@ __global__ __launch_bounds__(256) void k_bow_descend(ssk_bow_voc v, ssk_bow_call
     const int i = (int)(blockIdx.x * (256 / BW_LANES) + (threadIdx.x / BW_LANES)), sub = (int)(threadIdx.x % BW_LANES);
     const int n = bw_count(c.n_rows, c.frame_error, f, rows);
     const bool live = i < n;
-    uint64_t q0 = 0, q1 = 0, q2 = 0, q3 = 0;
+    uint64_t q0 = 0, q1 = 0, q2 = 0, q3 = 0; /* four words, not a gd_desc: in this form the kernel compiles to the code it had */
     int base = 0, nc = 0;
     if (live) {
-        const uint4 *qd = (const uint4 *)(c.desc + ((size_t)f * rows + i) * SS_DESC_BYTES);
-        const uint4 qa = qd[0], qb = qd[1];
-        q0 = (uint64_t)qa.x | ((uint64_t)qa.y << 32), q1 = (uint64_t)qa.z | ((uint64_t)qa.w << 32);
-        q2 = (uint64_t)qb.x | ((uint64_t)qb.y << 32), q3 = (uint64_t)qb.z | ((uint64_t)qb.w << 32);
+        const gd_desc l = gd_load_desc(c.desc + ((size_t)f * rows + i) * SS_DESC_BYTES);
+        q0 = l.q0, q1 = l.q1, q2 = l.q2, q3 = l.q3;
         const uint4 root = *(const uint4 *)v.recs;
         base = (int)root.x, nc = (int)root.y;
     }
@@ -69,10 +61,10 @@ __global__ __launch_bounds__(256) void k_bow_descend(ssk_bow_voc v, ssk_bow_call
     bool go = live && nc > 0;
     for (int step = 0; step < v.max_depth; step++) {
         if (!__any(go)) break;
-        uint32_t best = BW_NONE;
+        uint32_t best = GD_NONE;
         if (go)
             for (int ch = sub; ch < nc; ch += BW_LANES)
-                best = min(best, (bw_hamming(q0, q1, q2, q3, v.rows + (size_t)(base + ch) * SS_DESC_BYTES) << 8) | (uint32_t)ch);
+                best = min(best, (gd_hamming(q0, q1, q2, q3, v.rows + (size_t)(base + ch) * SS_DESC_BYTES) << 8) | (uint32_t)ch);
 #pragma unroll
         for (int m = 1; m < BW_LANES; m <<= 1) best = min(best, (uint32_t)__shfl_xor((int)best, m));
         if (go) {
@@ -169,7 +161,7 @@ __global__ __launch_bounds__(BW_T) void k_bow_vector(ssk_bow_voc v, ssk_bow_call
     for (int j = tid; j < n2; j += BW_T) {
         /* w > 0: the descent gave the row a node.  The two arrays are the caller's outputs: a word that is none of the
          * vocabulary's (the caller reused the memory while the call was in flight) must not index the weights */
-        const uint32_t wd = j < n ? (uint32_t)word[j] : BW_NONE;
+        const uint32_t wd = j < n ? (uint32_t)word[j] : GD_NONE;
         const bool used = j < n && node[j] >= 0 && wd < (uint32_t)v.n_words;
         a[j] = used ? ((uint64_t)wd << 32) | (uint32_t)j : BW_PAD;
         mine += used;
@@ -244,66 +236,38 @@ __global__ __launch_bounds__(BW_T) void k_bow_index(const int32_t *node, const i
     if (tid == 0) n_index[f] = m;
 }
 
-__device__ __forceinline__ uint32_t bw_dist_of(uint32_t key) { return key == BW_NONE ? 0xFFFFu : key >> 20; }
-
 /* B-C.  grid (ceil(rows / 64), frames), 256 threads: k_guided_search with the run of the query's node in place of the window's
- * cells.  The frame rule (train frame, status, counts) is k_guided_finish's, which reads the same call. */
+ * cells.  The frame rule (train frame, status, counts) is k_guided_finish's, which reads the same call: gd_frame_of. */
 __global__ __launch_bounds__(256) void k_bow_search(ssk_guided_call a, const int32_t *q_node, const uint64_t *index, const int32_t *n_index)
 {
     const int b = (int)blockIdx.y, rows = a.rows;
     const int i = (int)(blockIdx.x * 64 + (threadIdx.x >> 2)), sub = (int)(threadIdx.x & 3);
-    const int t = a.src ? a.src[b] : b;
-    int status = 0;
-    if (a.frame_error) {
-        status = a.frame_error[b];
-        if (status == 0 && t >= 0) status = a.frame_error[t];
-    }
-    const int nq = status ? 0 : min(max(a.nq[b], 0), rows);
-    const int nt = (status || t < 0) ? 0 : min(max(a.nt[t], 0), rows);
-    const bool live = i < nq;
+    const gd_frame f = gd_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
+    const int t = f.t, nt = f.nt;
+    const bool live = i < f.nq;
     const int node = live ? q_node[(size_t)b * rows + i] : -1;
-    uint32_t best = BW_NONE, second = 0xFFFFu, count = 0;
+    uint32_t best = GD_NONE, second = 0xFFFFu, count = 0;
     if (live && nt > 0 && node >= 0) {
-        const uint4 *qd = (const uint4 *)(a.q_desc + ((size_t)b * rows + i) * SS_DESC_BYTES);
-        const uint4 qa = qd[0], qb = qd[1];
-        const uint64_t q0 = (uint64_t)qa.x | ((uint64_t)qa.y << 32), q1 = (uint64_t)qa.z | ((uint64_t)qa.w << 32);
-        const uint64_t q2 = (uint64_t)qb.x | ((uint64_t)qb.y << 32), q3 = (uint64_t)qb.z | ((uint64_t)qb.w << 32);
-        const uint64_t *keys = index + (size_t)t * rows;
+        const gd_desc q = gd_load_desc(a.q_desc + ((size_t)b * rows + i) * SS_DESC_BYTES);
         const uint8_t *td = a.t_desc + (size_t)t * rows * SS_DESC_BYTES;
-        const int m = min(max(n_index[t], 0), rows);
         const int skip = (a.exclude_same_frame && t == b) ? i : -1;
-        int lo = 0, hi = m; /* the first key of the node, if it has any */
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if ((uint32_t)(keys[mid] >> 32) < (uint32_t)node) lo = mid + 1;
-            else hi = mid;
-        }
-        for (int k = lo + sub; k < m; k += 4) {
-            const uint64_t key64 = keys[k];
-            if ((uint32_t)(key64 >> 32) != (uint32_t)node) break;
-            const int row = (int)(uint32_t)key64;
-            if (row >= nt || row == skip) continue; /* row < nt: the index was made with the same count */
-            const uint32_t dist = bw_hamming(q0, q1, q2, q3, td + (size_t)row * SS_DESC_BYTES);
+        gd_walk_node(index + (size_t)t * rows, min(max(n_index[t], 0), rows), node, sub, [&](int row) {
+            if (row >= nt || row == skip) return; /* row < nt: the index was made with the same count */
+            const uint32_t dist = gd_hamming(q, td + (size_t)row * SS_DESC_BYTES);
             const uint32_t key = (dist << 20) | (uint32_t)row;
             count++;
             if (key < best) {
-                second = min(second, bw_dist_of(best));
+                second = min(second, gd_dist_of(best));
                 best = key;
             } else {
                 second = min(second, dist);
             }
-        }
+        });
     }
-#pragma unroll
-    for (int m = 1; m <= 2; m <<= 1) {
-        const uint32_t ob = (uint32_t)__shfl_xor((int)best, m), os = (uint32_t)__shfl_xor((int)second, m), oc = (uint32_t)__shfl_xor((int)count, m);
-        second = min(min(second, os), bw_dist_of(max(best, ob)));
-        best = min(best, ob);
-        count += oc;
-    }
+    gd_fold_second(best, second, count);
     if (i >= rows || sub != 0) return;
-    const uint32_t d1 = bw_dist_of(best), d2 = second;
-    const int row = best == BW_NONE ? -1 : (int)(best & 0xFFFFFu);
+    const uint32_t d1 = gd_dist_of(best), d2 = second;
+    const int row = best == GD_NONE ? -1 : (int)(best & 0xFFFFFu);
     const bool accept = row >= 0 && (int)d1 <= a.th && (a.rden == 0 || (int)d1 * a.rden < (int)d2 * a.rnum);
     const size_t o = (size_t)b * rows + i;
     a.idx[o] = accept ? row : -1;

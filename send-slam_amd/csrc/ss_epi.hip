@@ -5,9 +5,10 @@
  * histogram are k_guided_finish (ss_guided.hip), both as they are.
  *
  *   E-A  k_epi_search   k_bow_search's shape: four lanes (a quad) per query row walk the run of the row's node in the train frame's
- *                       index.  The pair is one address per workgroup (scalar loads); the epipolar line a, b, c is evaluated once
- *                       per row; a couple passes taken flag, octave, epipole and line (ss_epi_steps.h, the text the host twin
- *                       compiles) before its descriptor is loaded.  Only the best key d << 20 | row is folded: no second best
+ *                       index (gd_walk_node, ss_quad.h).  The pair is one address per workgroup (scalar loads); the epipolar line
+ *                       a, b, c is evaluated once per row; a couple passes taken flag, octave, epipole and line (ss_epi_steps.h, the
+ *                       text the host twin compiles) before its descriptor is loaded.  Only the best key d << 20 | row is folded:
+ *                       no second best
  *   E-B  k_epi_summary  one workgroup per pair: the sums of the per-row counters next to what k_guided_finish counted
  *   T-A  k_tri_eval     one thread per query row: steps 1 - 9 in double with the 4 x 4 arrays in registers, the info record, the
  *                       map point of the row into a workspace
@@ -20,41 +21,20 @@
 #include <stdint.h>
 
 #include "ss_constants.h"
-#include "ss_guided_index.h"
 #include "ss_kernels.h"
 #include "ss_epi_steps.h"
+#include "ss_quad.h"
 
 namespace {
 
 static_assert(SSK_TRI_CHUNK == 1024, "k_tri_compact: one row per thread and chunk, 16 waves");
-
-/* what the kernels agree on for pair b: its train frame, its status, both row counts.  This is gd_frame_of's rule (ss_guided.hip),
- * restated because k_guided_finish runs on what k_epi_search writes and ss_guided.hip must compile to the code it had: keep them equal */
-struct ep_frame {
-    int t, status, nq, nt;
-};
-__device__ __forceinline__ ep_frame ep_frame_of(const int32_t *src, const int32_t *frame_error, const int32_t *nq, const int32_t *nt, int rows, int b)
-{
-    ep_frame f;
-    f.t = src ? src[b] : b;
-    f.status = 0;
-    if (frame_error) {
-        f.status = frame_error[b];
-        if (f.status == 0 && f.t >= 0) f.status = frame_error[f.t];
-    }
-    f.nq = f.status ? 0 : gd_clamp_count(nq[b], rows);
-    f.nt = (f.status || f.t < 0) ? 0 : gd_clamp_count(nt[f.t], rows);
-    return f;
-}
-
-__device__ __forceinline__ uint32_t ep_dist_of(uint32_t key) { return key == GD_NONE ? 0xFFFFu : key >> 20; }
 
 /* E-A.  grid (ceil(rows / 64), pairs), 256 threads; every row < rows is written */
 __global__ __launch_bounds__(256) void k_epi_search(ssk_guided_call a, ssk_epi_call e)
 {
     const int b = (int)blockIdx.y, rows = a.rows;
     const int i = (int)(blockIdx.x * 64 + (threadIdx.x >> 2)), sub = (int)(threadIdx.x & 3);
-    const ep_frame f = ep_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
+    const gd_frame f = gd_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
     const ss_epi_pair *w = e.pairs + b; /* one address per workgroup */
     const int n_levels = min(max(e.n_levels, 1), SS_MAX_LEVELS);
     const int t = max(f.t, 0), nt = f.nt;
@@ -67,54 +47,36 @@ __global__ __launch_bounds__(256) void k_epi_search(ssk_guided_call a, ssk_epi_c
         const ss_epi_line line = ss_epi_line_of(w->f12, qk->x, qk->y);
         const float ex = w->ex, ey = w->ey;
         const int epipole_test = w->epipole_test;
-        const uint4 *qd = (const uint4 *)(a.q_desc + ((size_t)b * rows + i) * SS_DESC_BYTES);
-        const uint4 qa = qd[0], qb = qd[1];
-        const uint64_t q0 = (uint64_t)qa.x | ((uint64_t)qa.y << 32), q1 = (uint64_t)qa.z | ((uint64_t)qa.w << 32);
-        const uint64_t q2 = (uint64_t)qb.x | ((uint64_t)qb.y << 32), q3 = (uint64_t)qb.z | ((uint64_t)qb.w << 32);
-        const uint64_t *keys = e.index + (size_t)t * rows;
+        const gd_desc q = gd_load_desc(a.q_desc + ((size_t)b * rows + i) * SS_DESC_BYTES);
         const uint8_t *td = a.t_desc + (size_t)t * rows * SS_DESC_BYTES;
         const ss_keypoint *tkp = a.t_kp + (size_t)t * rows;
         const uint8_t *taken = e.t_taken ? e.t_taken + (size_t)t * rows : nullptr;
-        const int m = min(max(e.n_index[t], 0), rows);
         const int skip = (a.exclude_same_frame && f.t == b) ? i : -1;
-        int lo = 0, hi = m; /* the first key of the node, if it has any */
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if ((uint32_t)(keys[mid] >> 32) < (uint32_t)node) lo = mid + 1;
-            else hi = mid;
-        }
-        for (int k = lo + sub; k < m; k += 4) {
-            const uint64_t key64 = keys[k];
-            if ((uint32_t)(key64 >> 32) != (uint32_t)node) break;
-            const int row = (int)(uint32_t)key64;
-            if (row >= nt || row == skip) continue; /* row < nt <= rows: the index was made with the same count */
-            if (taken && taken[row] != 0) continue;
+        gd_walk_node(e.index + (size_t)t * rows, min(max(e.n_index[t], 0), rows), node, sub, [&](int row) {
+            if (row >= nt || row == skip) return; /* row < nt <= rows: the index was made with the same count */
+            if (taken && taken[row] != 0) return;
             count++;
             const ss_keypoint *tk = tkp + row;
             const float2 xy = *(const float2 *)tk;
-            if (ss_epi_check(ex, ey, epipole_test, e.coarse, line, e.scale, n_levels, xy.x, xy.y, tk->octave) != 0) continue;
+            if (ss_epi_check(ex, ey, epipole_test, e.coarse, line, e.scale, n_levels, xy.x, xy.y, tk->octave) != 0) return;
             geo++;
-            const uint4 *d = (const uint4 *)(td + (size_t)row * SS_DESC_BYTES);
-            const uint4 ta = d[0], tb = d[1];
-            const uint32_t dist = (uint32_t)(__popcll(q0 ^ ((uint64_t)ta.x | ((uint64_t)ta.y << 32))) + __popcll(q1 ^ ((uint64_t)ta.z | ((uint64_t)ta.w << 32))) +
-                                             __popcll(q2 ^ ((uint64_t)tb.x | ((uint64_t)tb.y << 32))) + __popcll(q3 ^ ((uint64_t)tb.z | ((uint64_t)tb.w << 32))));
-            if ((int)dist > a.th) continue;
+            const uint32_t dist = gd_hamming(q, td + (size_t)row * SS_DESC_BYTES);
+            if ((int)dist > a.th) return;
             near++;
             best = min(best, (dist << 20) | (uint32_t)row);
-        }
+        });
     }
     /* fold the quad: all 64 lanes take part */
 #pragma unroll
     for (int m = 1; m <= 2; m <<= 1) {
-        best = min(best, (uint32_t)__shfl_xor((int)best, m));
-        count += (uint32_t)__shfl_xor((int)count, m);
+        gd_fold_step(best, count, m);
         geo += (uint32_t)__shfl_xor((int)geo, m);
         near += (uint32_t)__shfl_xor((int)near, m);
     }
     if (i >= rows || sub != 0) return;
     const size_t o = (size_t)b * rows + i;
     a.idx[o] = best == GD_NONE ? -1 : (int)(best & 0xFFFFFu);
-    a.d1[o] = (uint16_t)ep_dist_of(best);
+    a.d1[o] = (uint16_t)gd_dist_of(best);
     a.n_cand[o] = (int32_t)count;
     e.n_geo[o] = (int32_t)geo;
     e.n_near[o] = (int32_t)near;
@@ -159,7 +121,7 @@ __global__ __launch_bounds__(256) void k_tri_eval(ssk_tri_call a)
     const int b = (int)blockIdx.y, rows = a.rows;
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     if (i >= rows) return;
-    const ep_frame f = ep_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
+    const gd_frame f = gd_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
     const int n_levels = min(max(a.n_levels, 1), SS_MAX_LEVELS);
     const size_t o = (size_t)b * rows + i;
     const int j = i < f.nq ? a.idx[o] : -1;
@@ -184,7 +146,7 @@ __global__ __launch_bounds__(SSK_TRI_CHUNK) void k_tri_compact(ssk_tri_call a)
     __shared__ int cnt[11];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, rows = a.rows;
     const int lane = tid & 63, wave = tid >> 6;
-    const ep_frame f = ep_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
+    const gd_frame f = gd_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
     if (tid < 11) cnt[tid] = 0;
     __syncthreads();
     int base = 0;

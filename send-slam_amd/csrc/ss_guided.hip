@@ -20,30 +20,11 @@
 #include <stdint.h>
 
 #include "ss_constants.h"
-#include "ss_guided_index.h"
 #include "ss_kernels.h"
 #include "ss_layout.h"
+#include "ss_quad.h"
 
 namespace {
-
-/* what the three kernels agree on for query frame b: its train frame, its status, both row counts.  k_guided_finish also runs
- * behind k_bow_search (ss_bow.hip, the rule inline) and k_epi_search (ss_epi.hip, ep_frame_of): the three statements must agree */
-struct gd_frame {
-    int t, status, nq, nt;
-};
-__device__ __forceinline__ gd_frame gd_frame_of(const ssk_guided_call &a, int b)
-{
-    gd_frame f;
-    f.t = a.src ? a.src[b] : b;
-    f.status = 0;
-    if (a.frame_error) {
-        f.status = a.frame_error[b];
-        if (f.status == 0 && f.t >= 0) f.status = a.frame_error[f.t];
-    }
-    f.nq = f.status ? 0 : gd_clamp_count(a.nq[b], a.rows);
-    f.nt = (f.status || f.t < 0) ? 0 : gd_clamp_count(a.nt[f.t], a.rows);
-    return f;
-}
 
 /* G-A.  grid (train frames), 256 threads */
 __global__ __launch_bounds__(256) void k_guided_index(ssk_guided_call a)
@@ -96,17 +77,14 @@ __global__ __launch_bounds__(256) void k_guided_index(ssk_guided_call a)
     }
 }
 
-__device__ __forceinline__ uint32_t gd_dist_of(uint32_t key) { return key == GD_NONE ? 0xFFFFu : key >> 20; }
-
 /* G-B.  grid (ceil(rows / 64), frames), 256 threads: four lanes (a quad) per query row, lane `sub` takes every fourth record of
- * each cell row of the window; every row < rows is written.  Per lane: the lowest key d << 20 | row (= lowest distance, then
- * lowest row, whatever the order of the walk), the second-best distance, the candidate count.  Two lanes fold as two train
- * chunks do: the second best is the minimum over the loser's best and both seconds. */
+ * each cell row of the window (gd_walk_window's walk); every row < rows is written.  Per lane: the lowest key d << 20 | row (= lowest
+ * distance, then lowest row, whatever the order of the walk), the second-best distance, the candidate count (gd_fold_second) */
 __global__ __launch_bounds__(256) void k_guided_search(ssk_guided_call a)
 {
     const int b = (int)blockIdx.y, rows = a.rows;
     const int i = (int)(blockIdx.x * 64 + (threadIdx.x >> 2)), sub = (int)(threadIdx.x & 3);
-    const gd_frame f = gd_frame_of(a, b);
+    const gd_frame f = gd_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
     const bool live = i < f.nq;
     float x = 0.f, y = 0.f, r = 0.f;
     int olo = 0, ohi = -1;
@@ -125,14 +103,12 @@ __global__ __launch_bounds__(256) void k_guided_search(ssk_guided_call a)
     const bool search = live && f.nt > 0 && r > 0.0f && olo <= ohi; /* a NaN radius compares false */
     uint32_t best = GD_NONE, second = 0xFFFFu, count = 0;
     if (search) {
-        const uint4 *qd = (const uint4 *)(a.q_desc + ((size_t)b * rows + i) * SS_DESC_BYTES);
-        const uint4 qa = qd[0], qb = qd[1];
-        const uint64_t q0 = (uint64_t)qa.x | ((uint64_t)qa.y << 32), q1 = (uint64_t)qa.z | ((uint64_t)qa.w << 32);
-        const uint64_t q2 = (uint64_t)qb.x | ((uint64_t)qb.y << 32), q3 = (uint64_t)qb.z | ((uint64_t)qb.w << 32);
+        const gd_desc q = gd_load_desc(a.q_desc + ((size_t)b * rows + i) * SS_DESC_BYTES);
         const uint32_t *cs = a.cell_start + (size_t)f.t * (GD_CELLS + 1);
         const gd_rec *recs = (const gd_rec *)a.recs + (size_t)f.t * rows;
         const uint8_t *td = a.t_desc + (size_t)f.t * rows * SS_DESC_BYTES;
         const int skip = (a.exclude_same_frame && f.t == b) ? i : -1;
+        /* gd_walk_window (ss_quad.h) written out: through its functor this kernel's record load compiles to other vector loads */
         const int cx0 = gd_bin(x - r, a.x_max, a.shift), cx1 = gd_bin(x + r, a.x_max, a.shift);
         const int cy0 = gd_bin(y - r, a.y_max, a.shift), cy1 = gd_bin(y + r, a.y_max, a.shift);
         for (int cy = cy0; cy <= cy1; cy++) {
@@ -145,10 +121,7 @@ __global__ __launch_bounds__(256) void k_guided_search(ssk_guided_call a)
                 if (eo < olo || eo > ohi) continue;
                 if (!(fabsf(ex - x) < r) || !(fabsf(ey - y) < r)) continue;
                 if (row == skip) continue;
-                const uint4 *d = (const uint4 *)(td + (size_t)row * SS_DESC_BYTES);
-                const uint4 ta = d[0], tb = d[1];
-                const uint32_t dist = (uint32_t)(__popcll(q0 ^ ((uint64_t)ta.x | ((uint64_t)ta.y << 32))) + __popcll(q1 ^ ((uint64_t)ta.z | ((uint64_t)ta.w << 32))) +
-                                                 __popcll(q2 ^ ((uint64_t)tb.x | ((uint64_t)tb.y << 32))) + __popcll(q3 ^ ((uint64_t)tb.z | ((uint64_t)tb.w << 32))));
+                const uint32_t dist = gd_hamming(q, td + (size_t)row * SS_DESC_BYTES);
                 const uint32_t key = (dist << 20) | (uint32_t)row;
                 count++;
                 if (key < best) {
@@ -160,14 +133,7 @@ __global__ __launch_bounds__(256) void k_guided_search(ssk_guided_call a)
             }
         }
     }
-    /* fold the quad: all 64 lanes take part */
-#pragma unroll
-    for (int m = 1; m <= 2; m <<= 1) {
-        const uint32_t ob = (uint32_t)__shfl_xor((int)best, m), os = (uint32_t)__shfl_xor((int)second, m), oc = (uint32_t)__shfl_xor((int)count, m);
-        second = min(min(second, os), gd_dist_of(max(best, ob)));
-        best = min(best, ob);
-        count += oc;
-    }
+    gd_fold_second(best, second, count);
     if (i >= rows || sub != 0) return;
     const uint32_t d1 = gd_dist_of(best), d2 = second;
     const int row = best == GD_NONE ? -1 : (int)(best & 0xFFFFFu);
@@ -200,7 +166,7 @@ __global__ __launch_bounds__(GD_FIN) void k_guided_finish(ssk_guided_call a)
     __shared__ int cnt[4]; /* candidates, accepted, unique, final */
     __shared__ int kept[3];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, rows = a.rows;
-    const gd_frame f = gd_frame_of(a, b);
+    const gd_frame f = gd_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
     int32_t *idx = a.idx + (size_t)b * rows;
     const uint16_t *d1 = a.d1 + (size_t)b * rows;
     if (tid < 4) cnt[tid] = 0;
@@ -214,7 +180,7 @@ __global__ __launch_bounds__(GD_FIN) void k_guided_finish(ssk_guided_call a)
     }
     if (cand) atomicAdd(&cnt[0], cand);
     if (acc) atomicAdd(&cnt[1], acc);
-    if (a.one_to_one) {
+    if (a.one_to_one) { /* gd_settle (ss_quad.h) written out: with the call, the three-maxima block below compiles to more LDS reads */
         for (int base = 0; base < f.nt; base += GD_KEY_ROWS) { /* uniform */
             const int len = min(GD_KEY_ROWS, f.nt - base);
             for (int k = tid; k < len; k += GD_FIN) keys[k] = GD_NONE;

@@ -5,10 +5,10 @@
  *
  *   P-A  k_proj_search  four lanes (a quad) per map point.  The frame's view is block-uniform and read once; every lane of the
  *                       quad evaluates frustum, level and window itself (ss_proj_steps.h, the text the host twin compiles), then
- *                       the quad walks the cell rows the window meets as k_guided_search does, with the taken mask and the
+ *                       the quad walks the cell rows the window meets (gd_walk_window, ss_quad.h), with the taken mask and the
  *                       right-eye test on top.  Best and second best are folded as full keys d << 20 | row, because the octave
  *                       of the second best decides whether the ratio test counts
- *   P-B  k_proj_finish  one workgroup per frame: conflicts by an LDS atomicMin of d1 << 20 | i per train row, the summary
+ *   P-B  k_proj_finish  one workgroup per frame: conflicts by an LDS atomicMin of d1 << 20 | i per train row (gd_settle), the summary
  *
  * Every float step is a single IEEE operation (-ffp-contract=off).  Every global write is a plain vector store.
  */
@@ -16,44 +16,24 @@
 #include <stdint.h>
 
 #include "ss_constants.h"
-#include "ss_guided_index.h"
 #include "ss_kernels.h"
 #include "ss_layout.h"
 #include "ss_proj_steps.h"
+#include "ss_quad.h"
 
 namespace {
-
-/* what the two kernels agree on for frame b: its block of points, its status, both row counts */
-struct pj_frame {
-    int pb, status, np, nt;
-};
-__device__ __forceinline__ pj_frame pj_frame_of(const ssk_proj_call &a, int b)
-{
-    pj_frame f;
-    f.pb = a.src ? a.src[b] : b;
-    f.status = a.frame_error ? a.frame_error[b] : 0;
-    f.np = f.status ? 0 : gd_clamp_count(a.np[f.pb], a.point_rows);
-    f.nt = f.status ? 0 : gd_clamp_count(a.nt[b], a.rows);
-    return f;
-}
-
-__device__ __forceinline__ uint32_t pj_dist_of(uint32_t key) { return key == GD_NONE ? 0xFFFFu : key >> 20; }
 
 /* P-A.  grid (ceil(point_rows / 64), frames), 256 threads; every row < point_rows is written */
 __global__ __launch_bounds__(256) void k_proj_search(ssk_proj_call a)
 {
     const int b = (int)blockIdx.y, prow = a.point_rows, rows = a.rows;
     const int i = (int)(blockIdx.x * 64 + (threadIdx.x >> 2)), sub = (int)(threadIdx.x & 3);
-    const pj_frame f = pj_frame_of(a, b);
+    const gd_points_frame f = gd_points_frame_of(a.src, a.frame_error, a.np, a.nt, prow, a.rows, b);
     const ss_proj_view view = a.views[b]; /* one address per workgroup */
     const bool live = i < f.np;
     ss_proj_point o = ss_proj_rejected(-1);
     if (live) {
-        const float4 *pp = (const float4 *)(a.points + (size_t)f.pb * prow + i);
-        const float4 pa = pp[0], pb = pp[1];
-        ss_map_point p;
-        p.x = pa.x, p.y = pa.y, p.z = pa.z, p.nx = pa.w;
-        p.ny = pb.x, p.nz = pb.y, p.min_dist = pb.z, p.max_dist = pb.w;
+        const ss_map_point p = gd_load_point(a.points + (size_t)f.pb * prow + i);
         o = ss_proj_eval(view, p, a.view_cos_limit, a.th, a.far_limit, a.scale, a.n_levels);
     }
     const float x = o.u, y = o.v, r = o.radius;
@@ -62,57 +42,39 @@ __global__ __launch_bounds__(256) void k_proj_search(ssk_proj_call a)
     uint32_t best = GD_NONE, second = GD_NONE, count = 0;
     const ss_keypoint *tkp = a.t_kp + (size_t)b * rows;
     if (search) {
-        const uint4 *qd = (const uint4 *)(a.p_desc + ((size_t)f.pb * prow + i) * SS_DESC_BYTES);
-        const uint4 qa = qd[0], qb = qd[1];
-        const uint64_t q0 = (uint64_t)qa.x | ((uint64_t)qa.y << 32), q1 = (uint64_t)qa.z | ((uint64_t)qa.w << 32);
-        const uint64_t q2 = (uint64_t)qb.x | ((uint64_t)qb.y << 32), q3 = (uint64_t)qb.z | ((uint64_t)qb.w << 32);
+        const gd_desc q = gd_load_desc(a.p_desc + ((size_t)f.pb * prow + i) * SS_DESC_BYTES);
         const uint32_t *cs = a.cell_start + (size_t)b * (GD_CELLS + 1);
         const gd_rec *recs = (const gd_rec *)a.recs + (size_t)b * rows;
         const uint8_t *td = a.t_desc + (size_t)b * rows * SS_DESC_BYTES;
         const uint8_t *taken = a.t_taken ? a.t_taken + (size_t)b * rows : nullptr;
         const float *right = a.check_right ? a.t_right + (size_t)b * rows : nullptr;
-        const int cx0 = gd_bin(x - r, a.x_max, a.shift), cx1 = gd_bin(x + r, a.x_max, a.shift);
-        const int cy0 = gd_bin(y - r, a.y_max, a.shift), cy1 = gd_bin(y + r, a.y_max, a.shift);
-        for (int cy = cy0; cy <= cy1; cy++) {
-            /* the cells cx0 .. cx1 of a grid row are one run of records */
-            const uint32_t k0 = cs[cy * a.cols + cx0], k1 = cx1 >= cx0 ? cs[cy * a.cols + cx1 + 1] : k0;
-            for (uint32_t k = k0 + (uint32_t)sub; k < k1; k += 4) {
-                const uint4 raw = *(const uint4 *)(recs + k);
-                const float ex = __uint_as_float(raw.x), ey = __uint_as_float(raw.y);
-                const int eo = (int)raw.z, row = (int)raw.w;
-                if (eo < olo || eo > ohi) continue;
-                if (!(fabsf(ex - x) < r) || !(fabsf(ey - y) < r)) continue;
-                if (taken && taken[row] != 0) continue;
-                if (right) {
-                    const float ur = right[row];
-                    if (ur > 0.0f && !(fabsf(o.u_right - ur) <= r)) continue;
-                }
-                const uint4 *d = (const uint4 *)(td + (size_t)row * SS_DESC_BYTES);
-                const uint4 ta = d[0], tb = d[1];
-                const uint32_t dist = (uint32_t)(__popcll(q0 ^ ((uint64_t)ta.x | ((uint64_t)ta.y << 32))) + __popcll(q1 ^ ((uint64_t)ta.z | ((uint64_t)ta.w << 32))) +
-                                                 __popcll(q2 ^ ((uint64_t)tb.x | ((uint64_t)tb.y << 32))) + __popcll(q3 ^ ((uint64_t)tb.z | ((uint64_t)tb.w << 32))));
-                const uint32_t key = (dist << 20) | (uint32_t)row;
-                count++;
-                if (key < best) {
-                    second = best;
-                    best = key;
-                } else {
-                    second = min(second, key);
-                }
+        gd_walk_window(cs, recs, a.cols, a.x_max, a.y_max, a.shift, x, y, r, sub, [&](float ex, float ey, int eo, int row) {
+            if (eo < olo || eo > ohi) return;
+            if (!(fabsf(ex - x) < r) || !(fabsf(ey - y) < r)) return;
+            if (taken && taken[row] != 0) return;
+            if (right) {
+                const float ur = right[row];
+                if (ur > 0.0f && !(fabsf(o.u_right - ur) <= r)) return;
             }
-        }
+            const uint32_t key = (gd_hamming(q, td + (size_t)row * SS_DESC_BYTES) << 20) | (uint32_t)row;
+            count++;
+            if (key < best) {
+                second = best;
+                best = key;
+            } else {
+                second = min(second, key);
+            }
+        });
     }
     /* fold the quad: all 64 lanes take part.  The lanes hold different rows, so their keys differ: the second best of two lanes
      * is the lowest of the losing best and both seconds */
 #pragma unroll
     for (int m = 1; m <= 2; m <<= 1) {
-        const uint32_t ob = (uint32_t)__shfl_xor((int)best, m), os = (uint32_t)__shfl_xor((int)second, m), oc = (uint32_t)__shfl_xor((int)count, m);
-        second = min(min(second, os), max(best, ob));
-        best = min(best, ob);
-        count += oc;
+        const uint32_t os = (uint32_t)__shfl_xor((int)second, m);
+        second = min(min(second, os), gd_fold_step(best, count, m));
     }
     if (i >= prow || sub != 0) return;
-    const uint32_t d1 = pj_dist_of(best), d2 = pj_dist_of(second);
+    const uint32_t d1 = gd_dist_of(best), d2 = gd_dist_of(second);
     const int row1 = best == GD_NONE ? -1 : (int)(best & 0xFFFFFu), row2 = second == GD_NONE ? -1 : (int)(second & 0xFFFFFu);
     const int lvl1 = row1 >= 0 ? tkp[row1].octave : -1, lvl2 = row2 >= 0 ? tkp[row2].octave : -1;
     const bool accept = row1 >= 0 && (int)d1 <= a.th_high && !(a.rden != 0 && lvl1 == lvl2 && (int)d1 * a.rden > (int)d2 * a.rnum);
@@ -133,7 +95,7 @@ __global__ __launch_bounds__(GD_FIN) void k_proj_finish(ssk_proj_call a)
     __shared__ uint32_t keys[GD_KEY_ROWS];
     __shared__ int cnt[4]; /* in view, candidates, accepted, unique */
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, prow = a.point_rows;
-    const pj_frame f = pj_frame_of(a, b);
+    const gd_points_frame f = gd_points_frame_of(a.src, a.frame_error, a.np, a.nt, prow, a.rows, b);
     int32_t *idx = a.idx + (size_t)b * prow;
     const uint16_t *d1 = a.d1 + (size_t)b * prow;
     if (tid < 4) cnt[tid] = 0;
@@ -147,23 +109,7 @@ __global__ __launch_bounds__(GD_FIN) void k_proj_finish(ssk_proj_call a)
     if (view) atomicAdd(&cnt[0], view);
     if (cand) atomicAdd(&cnt[1], cand);
     if (acc) atomicAdd(&cnt[2], acc);
-    if (a.one_to_one) {
-        for (int base = 0; base < f.nt; base += GD_KEY_ROWS) { /* uniform */
-            const int len = min(GD_KEY_ROWS, f.nt - base);
-            for (int k = tid; k < len; k += GD_FIN) keys[k] = GD_NONE;
-            __syncthreads();
-            for (int i = tid; i < f.np; i += GD_FIN) {
-                const int j = idx[i] - base;
-                if (j >= 0 && j < len && idx[i] >= 0) atomicMin(&keys[j], ((uint32_t)d1[i] << 20) | (uint32_t)i);
-            }
-            __syncthreads();
-            for (int i = tid; i < f.np; i += GD_FIN) {
-                const int j = idx[i] - base;
-                if (j >= 0 && j < len && idx[i] >= 0 && keys[j] != (((uint32_t)d1[i] << 20) | (uint32_t)i)) idx[i] = -1;
-            }
-            __syncthreads();
-        }
-    }
+    if (a.one_to_one) gd_settle(keys, d1, f.np, f.nt, tid, [&](int i) { return idx[i]; }, [&](int i, uint32_t) { idx[i] = -1; });
     int uniq = 0;
     for (int i = tid; i < f.np; i += GD_FIN) uniq += idx[i] >= 0;
     if (uniq) atomicAdd(&cnt[3], uniq);

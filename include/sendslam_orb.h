@@ -1002,6 +1002,120 @@ int ss_match_fuse(ss_ctx *ctx, const ss_proj_view *view, const ss_map_point *poi
                   const uint8_t *train_taken, const int32_t *train_point, const ss_fuse_params *p, int32_t *idx, uint16_t *d1,
                   ss_fuse_action *fuse, ss_fuse_point *point, ss_fuse_summary *summary);
 
+/* ---- Sim3 from matched map points: Sim3Solver (Horn 1987, RANSAC over 3-point alignments) as LoopClosing::
+ * DetectCommonRegionsFromBoW uses it on the matches of SearchByBoW.  The upstream source is not in the reference tree.  This is the
+ * library's own restatement and parity with the real binary stays unpinned, as for the guided, bag-of-words, projection, epipolar
+ * and fusion stages.  tests/sim3_ref.py is its normative statement; DESIGN.md section 20.  An addition to ABI 5: nothing existing
+ * changes ------------------------------------------------------------------------------------------------------------------------
+ * - Every float32 step is one IEEE operation, left to right as written, with no contraction; so is every double step of the model.
+ * - Every test is written in its accepting form, so a NaN fails it.
+ * One pair: keyframe 1 is the query with view v1, keyframe 2 the train with view v2 (ss_proj_view; only rcw, tcw, fx, fy, cx, cy
+ * are read).  Every keypoint row of either has an ss_map_point (only x, y, z are read), an ss_keypoint (only octave is read) and,
+ * optionally, a skip byte (fusion's convention: non-zero = the row has no usable map point).  idx[i] is the train row matched to
+ * query row i, or < 0: what ss_match_bow_pairs_device wrote.
+ * 1. Correspondences.  Query rows i < n_query in ascending order; (i, j = idx[i]) is kept iff 0 <= j < n_train, neither row is
+ *    skipped and both octaves lie in 0 .. n_levels-1.  The kept ones are numbered 0 .. N-1 in that order.  For each, in float32:
+ *    X1 = R1.P1 + t1 and X2 = R2.P2 + t2, each component ((r0*x + r1*y) + r2*z) + t; p = project(X, K): invz = 1.0f / X.z,
+ *    u = fx*X.x*invz + cx, v = fy*X.y*invz + cy (two products, then the sum); max1 = chi2 * (s1*s1) with s1 = scale[octave_i],
+ *    max2 = chi2 * (s2*s2) with s2 = scale[octave_j].  p1 and p2 are the projections of the map points, not the keypoints, as
+ *    upstream has it.
+ * 2. State 1: N < 3 or N < min_inliers.  There is no model.
+ * 3. Hypothesis t, 0 <= t < max_iterations; each is independent of the others.
+ *    a. Draws.  Three draws without replacement over the virtual array 0 .. N-1 under upstream's swap-with-last rule: draw k
+ *       (0, 1, 2) takes r = mix32(seed, pair, 3t + k) and j = (uint64(r) * (N - k)) >> 32; the value at slot j is drawn, and slot j
+ *       then receives the value at slot N-1-k.  mix32, all in uint32: h = (seed ^ pair*0x9E3779B1) + n*0x85EBCA77; h ^= h >> 16;
+ *       h *= 0x7FEB352D; h ^= h >> 15; h *= 0x846CA68B; h ^= h >> 16.  pair is the pair's number in the call.
+ *    b. Model, in double from the float32 X1, X2 of the three draws a, b, c in draw order.  O = ((a + b) + c) / 3.0 per component;
+ *       Pr = P - O; M[i][j] = (Pr2a[i]*Pr1a[j] + Pr2b[i]*Pr1b[j]) + Pr2c[i]*Pr1c[j].  Horn's symmetric N: N00 = (M00 + M11) + M22,
+ *       N01 = M12 - M21, N02 = M20 - M02, N03 = M01 - M10, N11 = (M00 - M11) - M22, N12 = M01 + M10, N13 = M20 + M02,
+ *       N22 = (M11 - M00) - M22, N23 = M12 + M21, N33 = (M22 - M00) - M11.  SS_TRI_SWEEPS sweeps of the triangulation's rotation
+ *       in its order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), V starting as the identity.  The quaternion (w, x, y, z) is the column of
+ *       V at the LARGEST diagonal entry (strict >, so the first index wins a tie), divided by
+ *       sqrt(((w*w + x*x) + y*y) + z*z).  R: r00 = 1 - 2*(y*y + z*z), r01 = 2*(x*y - w*z), r02 = 2*(x*z + w*y),
+ *       r10 = 2*(x*y + w*z), r11 = 1 - 2*(x*x + z*z), r12 = 2*(y*z - w*x), r20 = 2*(x*z - w*y), r21 = 2*(y*z + w*x),
+ *       r22 = 1 - 2*(x*x + y*y).  P3 = R.Pr2, each component (r0*x + r1*y) + r2*z.  Scale: with d(p, q) = (p0*q0 + p1*q1) + p2*q2,
+ *       s = ((d(Pr1a, P3a) + d(Pr1b, P3b)) + d(Pr1c, P3c)) / ((d(P3a, P3a) + d(P3b, P3b)) + d(P3c, P3c)), or exactly 1.0 with
+ *       fix_scale.  t12 = O1 - s*(R.O2).  The inverse: s21 = 1.0 / s, sR21[i][j] = s21 * R[j][i], t21[i] = -(s21 * ((R[0][i]*t12[0]
+ *       + R[1][i]*t12[1]) + R[2][i]*t12[2])).  s*R, t12, s, s21*R^T, t21 are rounded to float32 once.  If any of these 25 floats
+ *       is not finite, the model is the zero model: all 25 are 0.0f (no correspondence passes it: invz is infinite and 0*inf is
+ *       NaN).
+ *    c. Count, in float32.  Correspondence n is an inlier iff both tests pass: with Y = sR12.X2 + t12 (components as in step 1) and
+ *       q = project(Y, K1), e1 = (p1.u - q.u)^2 + (p1.v - q.v)^2 (two products, one sum) and e1 < max1; with Y = sR21.X1 + t21 and
+ *       q = project(Y, K2), e2 = (q.u - p2.u)^2 + (q.v - p2.v)^2 and e2 < max2.  There is no depth-sign test, as upstream has
+ *       none.  count[t] is an integer.
+ * 4. Selection.  The winner is the SMALLEST t with count[t] > min_inliers: the model upstream's iterate returns, since nothing
+ *    earlier exceeded the threshold and so it is also the best so far.  State 0: the model, inlier[i] = 1 for the query rows of its
+ *    inliers, n_inliers, iteration = t.  State 2, no winner: model and flags all 0, iteration -1.  best_inliers = max count[t] in
+ *    states 0 and 2, 0 in state 1.
+ * Deviations from upstream: the draw stream (DUtils::Random there); R from the quaternion's nine polynomial entries (upstream goes
+ * through atan2 and Rodrigues, the same rotation: atan2, sin and cos are not the same bits on host and device); the model in double
+ * (float there); max_iterations is the caller's number (upstream shrinks 300 by log(1 - p) / log(1 - eps^3), and log is not
+ * portable bit for bit); one call evaluates every t instead of iterate(20) in a loop with an early exit, which selects the same
+ * model; chi2 is a parameter (9.210 there); eigenvectors by cyclic Jacobi (cv::eigen there); a non-finite model is the zero model.
+ * Outputs per pair: ss_sim3_result, 128 bytes, and inlier uint8 [rows] by QUERY row (every row < rows is written).  A pair with a
+ * frame the extraction flagged has that status, state 1 and no correspondences. */
+#define SS_SIM3_MAX_ITERATIONS 1024
+typedef struct {          /* 32 bytes */
+    float chi2;           /* finite and > 0; upstream: 9.210 */
+    int32_t min_inliers;  /* >= 0; a model wins with MORE inliers than this; upstream: 20 */
+    int32_t max_iterations; /* 1 .. SS_SIM3_MAX_ITERATIONS; upstream: at most 300 */
+    int32_t fix_scale;    /* non-zero: s = 1.0 (stereo and RGB-D) */
+    uint32_t seed;
+    int32_t reserved[3];  /* must be 0 */
+} ss_sim3_params;
+typedef struct {          /* 128 bytes, one per pair */
+    float sr12[9], t12[3], s12; /* X1 = sr12.X2 + t12 (row-major); all 0.0f unless state == 0 */
+    float sr21[9], t21[3];      /* the inverse: X2 = sr21.X1 + t21 */
+    int32_t state;        /* 0 a model, 1 too few correspondences, 2 no hypothesis over min_inliers */
+    int32_t n_corr;       /* N */
+    int32_t n_inliers;    /* state 0: count of the winner, else 0 */
+    int32_t best_inliers; /* max count[t]; 0 in state 1 */
+    int32_t iteration;    /* the winner's t, or -1 */
+    int32_t status;       /* SS_OK, or the frame_error that voided the pair */
+    int32_t reserved;     /* 0 */
+} ss_sim3_result;
+/* Host twins of steps 3b and 3c (the text the kernels compile, csrc/ss_sim3_steps.h); neither needs a device.  p is checked as the
+ * device calls check it (SS_ERR_INVALID_ARG).
+ * ss_sim3_model_host: the model of the triple x1[k], x2[k] (k = 0, 1, 2 in draw order; float32 camera coordinates) into
+ * out->sr12 .. out->t21; state 0, iteration -1, the other integers 0.
+ * ss_sim3_check_host: steps 1 and 3c of the n couples (points1[k] with kp1[k] under view1, points2[k] with kp2[k] under view2)
+ * against the model in `model`; scale: n_levels entries, 1 <= n_levels <= SS_MAX_LEVELS.  out[k]: 0 an inlier, 1 an octave outside
+ * the table (not a correspondence), 2 the first test fails, 3 the second.  err (NULL, or 2n floats): e1, e2 of couple k at
+ * err[2k], err[2k + 1]; 0.0f where out[k] == 1. */
+int ss_sim3_model_host(const ss_sim3_params *p, const float x1[9], const float x2[9], ss_sim3_result *out);
+int ss_sim3_check_host(const ss_sim3_params *p, const ss_proj_view *view1, const ss_proj_view *view2, const float *scale, int n_levels,
+                       const ss_map_point *points1, const ss_keypoint *kp1, const ss_map_point *points2, const ss_keypoint *kp2, int n,
+                       const ss_sim3_result *model, uint8_t *out, float *err);
+/* Closes the chain on the host, needs no device: upstream's gScw = gScm * gSmw, the Sim3 that takes the world of keyframe 2's pose
+ * (the loop candidate, rcw2 / tcw2) into the camera of keyframe 1 (the current keyframe), as the view ss_match_fuse_* projects the
+ * candidate's map points with.  In double from the result's floats: srcw[9] = sr12 . rcw2 (each entry (a0*b0 + a1*b1) + a2*b2),
+ * t[k] = ((sr12[3k]*tcw2[0] + sr12[3k+1]*tcw2[1]) + sr12[3k+2]*tcw2[2]) + t12[k]; then exactly ss_fuse_view_sim3(cam, srcw, t, bf,
+ * out).  SS_ERR_INVALID_ARG: a NULL pointer, result->state != 0.  srcw_out (9) and t_out (3) receive the Sim3 when not NULL. */
+int ss_sim3_to_view(const ss_camera *cam, const ss_sim3_result *result, const double rcw2[9], const double tcw2[3], float bf,
+                    double *srcw_out, double *t_out, ss_proj_view *out);
+/* n_pairs pairs on caller-supplied device arrays, pair b = query block b against train block b.  d_query_xyz / d_train_xyz
+ * [n_pairs][rows] ss_map_point; d_query_kp / d_train_kp [n_pairs][rows] ss_keypoint; d_query_skip / d_train_skip uint8
+ * [n_pairs][rows], or NULL; d_n_query / d_n_train device int32 [n_pairs], clamped to 0 .. rows; d_idx int32 [n_pairs][rows].
+ * views1 / views2: HOST tables of n_pairs views each, copied before the call returns.  Outputs: d_inlier uint8 [n_pairs][rows],
+ * d_result [n_pairs] ss_sim3_result.  SS_ERR_INVALID_ARG: rows above SS_GUIDED_MAX_ROWS, max_iterations outside
+ * 1 .. SS_SIM3_MAX_ITERATIONS, min_inliers < 0, chi2 not finite or not > 0, a reserved field that is not 0, a NULL buffer.
+ * Asynchronous on the context's stream. */
+int ss_sim3_pairs_device(ss_ctx *ctx, const void *d_query_xyz, const void *d_query_kp, const void *d_query_skip, const void *d_n_query,
+                         const void *d_train_xyz, const void *d_train_kp, const void *d_train_skip, const void *d_n_train,
+                         const void *d_idx, int n_pairs, int rows, const ss_proj_view *views1, const ss_proj_view *views2,
+                         const ss_sim3_params *p, void *d_inlier, void *d_result);
+/* The same on the frames of the last ss_extract_batch_device batch (SS_ERR_STATE without one; rows = kp_capacity), frame b against
+ * frame train_src[b] (ss_match_guided_batch_device's table; -1: no train, state 1): d_xyz [n_frames][kp_capacity] ss_map_point and
+ * d_skip (or NULL) hold the map points of every frame's rows, views (HOST, n_frames) the view of every frame: pair b reads
+ * views[b] and views[train_src[b]].  A flagged frame on either side voids the pair. */
+int ss_sim3_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_xyz, const void *d_skip, const void *d_idx,
+                         const ss_proj_view *views, const ss_sim3_params *p, void *d_inlier, void *d_result);
+/* One pair with host pointers in and out (copy in, the pairs form, copy out), synchronous.  n_query, n_train <=
+ * SS_GUIDED_MAX_ROWS; the skip arrays may be NULL; inlier: n_query bytes. */
+int ss_sim3(ss_ctx *ctx, const ss_proj_view *view1, const ss_map_point *query_xyz, const ss_keypoint *query_kp, const uint8_t *query_skip,
+            int n_query, const ss_proj_view *view2, const ss_map_point *train_xyz, const ss_keypoint *train_kp, const uint8_t *train_skip,
+            int n_train, const int32_t *idx, const ss_sim3_params *p, uint8_t *inlier, ss_sim3_result *result);
+
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device
  * (hipStream_t; NULL = the legacy default stream): for callers that produce the inputs of a *_device call on their own

@@ -1,6 +1,6 @@
 /*
  * ss_api_search.cpp -- the search family of the C ABI (include/sendslam_orb.h): guided matching, map-point projection search,
- * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation.  Each has a pairs form on caller arrays, a batch form on the
+ * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation, the Sim3 RANSAC.  Each has a pairs form on caller arrays, a batch form on the
  * frames of the last extraction and, for some, a host form.  The context and the helpers they share: ss_ctx.h.
  */
 #include <algorithm>
@@ -17,6 +17,7 @@
 #include "ss_epi_steps.h"
 #include "ss_fuse_steps.h"
 #include "ss_proj_steps.h"
+#include "ss_sim3_steps.h"
 
 extern "C" {
 
@@ -1353,6 +1354,213 @@ int ss_triangulate_batch_device(ss_ctx *c, const int32_t *train_src, const void 
     t.idx = (const int32_t *)d_idx;
     tri_outputs(t, d_info, d_points, d_point_desc, d_point_rows, d_n_points, d_summary);
     return tri_run(c, t, pairs, tp);
+}
+
+/* ---- Sim3 from matched map points (csrc/ss_sim3.hip, csrc/ss_sim3_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *sim3_params_error(const ss_sim3_params *p)
+{
+    if (!p) return "sim3: params is NULL";
+    if (!(p->chi2 > 0.0f) || !std::isfinite(p->chi2)) return "sim3: chi2 must be finite and > 0";
+    if (p->min_inliers < 0) return "sim3: min_inliers must be >= 0";
+    if (p->max_iterations < 1 || p->max_iterations > SS_SIM3_MAX_ITERATIONS) return "sim3: max_iterations must be 1 .. SS_SIM3_MAX_ITERATIONS";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0) return "sim3: the reserved fields must be 0";
+    return nullptr;
+}
+
+static void sim3_model_into(const ss_sim3_model &m, ss_sim3_result *out)
+{
+    memcpy(out->sr12, m.sr12, sizeof(m.sr12));
+    memcpy(out->t12, m.t12, sizeof(m.t12));
+    memcpy(out->sr21, m.sr21, sizeof(m.sr21));
+    memcpy(out->t21, m.t21, sizeof(m.t21));
+    out->s12 = m.s12;
+}
+
+int ss_sim3_model_host(const ss_sim3_params *p, const float x1[9], const float x2[9], ss_sim3_result *out)
+{
+    if (sim3_params_error(p) || !x1 || !x2 || !out) return SS_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    sim3_model_into(ss_sim3_model_of(x1, x2, p->fix_scale != 0), out);
+    out->iteration = -1;
+    return SS_OK;
+}
+
+int ss_sim3_check_host(const ss_sim3_params *p, const ss_proj_view *view1, const ss_proj_view *view2, const float *scale, int n_levels,
+                       const ss_map_point *points1, const ss_keypoint *kp1, const ss_map_point *points2, const ss_keypoint *kp2, int n,
+                       const ss_sim3_result *model, uint8_t *out, float *err)
+{
+    if (sim3_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!view1 || !view2 || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || !model || n < 0 || (n > 0 && (!points1 || !kp1 || !points2 || !kp2 || !out)))
+        return SS_ERR_INVALID_ARG;
+    for (int k = 0; k < n; k++) {
+        const int o1 = kp1[k].octave, o2 = kp2[k].octave;
+        if (err) err[2 * k] = err[2 * k + 1] = 0.0f;
+        if (!(o1 >= 0 && o1 < n_levels && o2 >= 0 && o2 < n_levels)) {
+            out[k] = 1;
+            continue;
+        }
+        const ss_sim3_corr c = ss_sim3_corr_of(*view1, *view2, points1[k].x, points1[k].y, points1[k].z, points2[k].x, points2[k].y, points2[k].z,
+                                               p->chi2, scale[o1], scale[o2]);
+        const float e1 = ss_sim3_err(model->sr12, model->t12, c.x2, view1->fx, view1->fy, view1->cx, view1->cy, c.u1, c.v1);
+        const float e2 = ss_sim3_err(model->sr21, model->t21, c.x1, view2->fx, view2->fy, view2->cx, view2->cy, c.u2, c.v2);
+        if (err) err[2 * k] = e1, err[2 * k + 1] = e2;
+        out[k] = !(e1 < c.max1) ? 2 : !(e2 < c.max2) ? 3 : 0;
+    }
+    return SS_OK;
+}
+
+int ss_sim3_to_view(const ss_camera *cam, const ss_sim3_result *result, const double rcw2[9], const double tcw2[3], float bf, double *srcw_out,
+                    double *t_out, ss_proj_view *out)
+{
+    if (!cam || !result || !rcw2 || !tcw2 || !out || result->state != 0) return SS_ERR_INVALID_ARG;
+    double m[9], t[3];
+    for (int i = 0; i < 3; i++) {
+        const double a0 = result->sr12[3 * i], a1 = result->sr12[3 * i + 1], a2 = result->sr12[3 * i + 2];
+        for (int j = 0; j < 3; j++) m[3 * i + j] = (a0 * rcw2[j] + a1 * rcw2[3 + j]) + a2 * rcw2[6 + j];
+        t[i] = ((a0 * tcw2[0] + a1 * tcw2[1]) + a2 * tcw2[2]) + (double)result->t12[i];
+    }
+    if (srcw_out) memcpy(srcw_out, m, sizeof(m));
+    if (t_out) memcpy(t_out, t, sizeof(t));
+    return ss_fuse_view_sim3(cam, m, t, bf, out);
+}
+
+/* The checks the device forms share, the workspace, the views (views1 then views2, each of n_frames, through `fill`), then the four
+ * launches of a call whose device operands and outputs are filled in */
+extern "C++" template <class Fill> static int sim3_run(ss_ctx *c, ssk_sim3_call &g, const ss_sim3_params *p, Fill fill_views)
+{
+    if (g.n_frames > 65535) return fail(c, SS_ERR_INVALID_ARG, "sim3: more than 65535 pairs in one call");
+    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
+        return fail(c, SS_ERR_INVALID_ARG, "sim3: the context's n_levels / scale_factor give no pyramid table");
+    g.chi2 = p->chi2, g.min_inliers = p->min_inliers, g.max_iterations = p->max_iterations, g.fix_scale = p->fix_scale != 0, g.seed = p->seed;
+    g.n_levels = c->params.n_levels;
+    ss_scale_table(c->params.scale_factor, g.n_levels, g.scale);
+    const size_t nr = (size_t)g.n_frames * g.rows, nh = (size_t)g.n_frames * g.max_iterations;
+    int rc = carve_from(c, c->d_sim3_ws, [&](carve &w) {
+        g.corr = w.take<float>(12 * nr * sizeof(float));
+        g.corr_of_row = w.take<int32_t>(nr * sizeof(int32_t));
+        g.n_corr = w.take<int32_t>((size_t)g.n_frames * sizeof(int32_t));
+        g.models = w.take<ssk_sim3_model>(nh * sizeof(ssk_sim3_model));
+        g.counts = w.take<int32_t>(nh * sizeof(int32_t));
+    });
+    if (rc != SS_OK) return rc;
+    const size_t vb = (size_t)g.n_frames * sizeof(ss_proj_view);
+    rc = staged_upload(c, c->sim3_tab, 2 * vb, [&](uint8_t *h) { fill_views((ss_proj_view *)h, (ss_proj_view *)(h + vb)); });
+    if (rc != SS_OK) return rc;
+    g.views1 = c->sim3_tab.as<ss_proj_view>(), g.views2 = c->sim3_tab.as<ss_proj_view>(vb);
+    const int64_t np = g.n_frames;
+    {
+        /* per query row: its match and the number written; a correspondence reads two map points, two octaves and up to two flags
+         * and writes its twelve floats */
+        stage_timer t(c, "sim3_gather", (int64_t)nr * (4 + 4 + 2 * (int64_t)sizeof(ss_map_point) + 2 * 4 + (g.q_skip ? 1 : 0) + (g.t_skip ? 1 : 0) + 48) + np * 4);
+        ssk_sim3_gather(c->stream, g);
+    }
+    {
+        /* per hypothesis: three correspondences' six floats read, one record and one count written */
+        stage_timer t(c, "sim3_model", (int64_t)nh * (3 * 24 + (int64_t)sizeof(ssk_sim3_model) + 4));
+        ssk_sim3_model_launch(c->stream, g);
+    }
+    {
+        /* every block of hypotheses reads the twelve floats of every correspondence once and its own records; the counts are added */
+        const int64_t hb = (g.max_iterations + SSK_SIM3_HYP_BLOCK - 1) / SSK_SIM3_HYP_BLOCK;
+        stage_timer t(c, "sim3_count", (int64_t)nr * 48 * hb + (int64_t)nh * ((int64_t)sizeof(ssk_sim3_model) + 4));
+        ssk_sim3_count(c->stream, g);
+    }
+    {
+        /* the counts read; per query row its number read and its flag written, an inlier candidate's twelve floats on top */
+        stage_timer t(c, "sim3_finish", (int64_t)nh * 4 + (int64_t)nr * (4 + 1 + 48) + np * (int64_t)(sizeof(ssk_sim3_model) + sizeof(ss_sim3_result)));
+        ssk_sim3_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_sim3_pairs_device(ss_ctx *c, const void *d_query_xyz, const void *d_query_kp, const void *d_query_skip, const void *d_n_query,
+                         const void *d_train_xyz, const void *d_train_kp, const void *d_train_skip, const void *d_n_train, const void *d_idx,
+                         int n_pairs, int rows, const ss_proj_view *views1, const ss_proj_view *views2, const ss_sim3_params *p, void *d_inlier,
+                         void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = sim3_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    const int rc = pairs_shape(c, "sim3", "pair", n_pairs, rows);
+    if (rc != SS_OK) return rc;
+    if (n_pairs == 0) return SS_OK;
+    if (!d_query_xyz || !d_query_kp || !d_n_query || !d_train_xyz || !d_train_kp || !d_n_train || !d_idx || !views1 || !views2 || !d_inlier || !d_result)
+        return fail(c, SS_ERR_INVALID_ARG, "sim3: NULL buffer");
+    ssk_sim3_call g;
+    g.n_frames = n_pairs, g.rows = rows;
+    g.q_xyz = (const ss_map_point *)d_query_xyz, g.t_xyz = (const ss_map_point *)d_train_xyz;
+    g.q_kp = (const ss_keypoint *)d_query_kp, g.t_kp = (const ss_keypoint *)d_train_kp;
+    g.q_skip = (const uint8_t *)d_query_skip, g.t_skip = (const uint8_t *)d_train_skip;
+    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
+    g.idx = (const int32_t *)d_idx;
+    g.inlier = (uint8_t *)d_inlier, g.result = (ss_sim3_result *)d_result;
+    const size_t vb = (size_t)n_pairs * sizeof(ss_proj_view);
+    return sim3_run(c, g, p, [&](ss_proj_view *v1, ss_proj_view *v2) {
+        memcpy(v1, views1, vb);
+        memcpy(v2, views2, vb);
+    });
+}
+
+int ss_sim3_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_xyz, const void *d_skip, const void *d_idx, const ss_proj_view *views,
+                         const ss_sim3_params *p, void *d_inlier, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_sim3_batch_device")) return SS_ERR_STATE;
+    if (const char *msg = sim3_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (!d_xyz || !d_idx || !views || !d_inlier || !d_result) return fail(c, SS_ERR_INVALID_ARG, "sim3: NULL buffer");
+    batch_operands o;
+    const int rc = batch_operands_of(c, "sim3", train_src, o);
+    if (rc != SS_OK) return rc;
+    ssk_sim3_call g;
+    g.n_frames = o.n_frames, g.rows = o.kcap;
+    g.q_xyz = g.t_xyz = (const ss_map_point *)d_xyz;
+    g.q_kp = g.t_kp = o.kps;
+    g.q_skip = g.t_skip = (const uint8_t *)d_skip;
+    g.nq = g.nt = o.n_kp;
+    g.src = o.src, g.frame_error = o.frame_error;
+    g.idx = (const int32_t *)d_idx;
+    g.inlier = (uint8_t *)d_inlier, g.result = (ss_sim3_result *)d_result;
+    const int n = o.n_frames;
+    return sim3_run(c, g, p, [&](ss_proj_view *v1, ss_proj_view *v2) {
+        for (int b = 0; b < n; b++) {
+            const int t = train_src ? train_src[b] : b - 1; /* checked by batch_operands_of; -1: the pair has no train and reads no view */
+            v1[b] = views[b];
+            v2[b] = views[t < 0 ? b : t];
+        }
+    });
+}
+
+int ss_sim3(ss_ctx *c, const ss_proj_view *view1, const ss_map_point *query_xyz, const ss_keypoint *query_kp, const uint8_t *query_skip, int n_query,
+            const ss_proj_view *view2, const ss_map_point *train_xyz, const ss_keypoint *train_kp, const uint8_t *train_skip, int n_train,
+            const int32_t *idx, const ss_sim3_params *p, uint8_t *inlier, ss_sim3_result *result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_query < 0 || n_train < 0 || n_query > SS_GUIDED_MAX_ROWS || n_train > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "sim3: n_query and n_train must be 0 .. SS_GUIDED_MAX_ROWS");
+    if (!view1 || !view2 || !result || (n_query > 0 && (!query_xyz || !query_kp || !idx || !inlier)) || (n_train > 0 && (!train_xyz || !train_kp)))
+        return fail(c, SS_ERR_INVALID_ARG, "sim3: NULL buffer");
+    /* one pair of `rows` rows on both sides; `counts` is on this stack: no return before the stream has read it */
+    const size_t rows = (size_t)std::max(std::max(n_query, n_train), 1), nq = (size_t)n_query, nt = (size_t)n_train;
+    const size_t kp = sizeof(ss_keypoint), mp = sizeof(ss_map_point);
+    const int32_t counts[2] = {n_query, n_train};
+    enum { QX, QK, QS, TX, TK, TS, IDX, N, INL, RES, PIECES };
+    io_piece io[PIECES] = {{query_xyz, nullptr, rows * mp, nq * mp}, {query_kp, nullptr, rows * kp, nq * kp}, {query_skip, nullptr, rows, nq},
+                           {train_xyz, nullptr, rows * mp, nt * mp}, {train_kp, nullptr, rows * kp, nt * kp}, {train_skip, nullptr, rows, nt},
+                           {idx, nullptr, rows * 4, nq * 4}, {counts, nullptr, sizeof(counts), sizeof(counts)}, {nullptr, inlier, rows, nq},
+                           {nullptr, result, sizeof(ss_sim3_result), sizeof(ss_sim3_result)}};
+    int rc = io_send(c, c->d_sim3_io, io, PIECES);
+    if (rc == SS_OK)
+        rc = ss_sim3_pairs_device(c, io[QX].d, io[QK].d, query_skip ? io[QS].d : nullptr, io[N].d, io[TX].d, io[TK].d, train_skip ? io[TS].d : nullptr,
+                                  io[N].d + 4, io[IDX].d, 1, (int)rows, view1, view2, p, io[INL].d, io[RES].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
 }
 
 } /* extern "C" */

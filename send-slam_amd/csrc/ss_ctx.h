@@ -144,6 +144,10 @@ struct ss_ctx {
      * the uncompacted map points) and the pairs of a call, one table for both */
     dev_buf<uint8_t> d_epi_ws, d_tri_ws;
     staged_table epi_tab;
+    /* Sim3 RANSAC: the workspace of a call (correspondences, models, counts), the host form's device copies, the views of a call
+     * (views1, then views2) */
+    dev_buf<uint8_t> d_sim3_ws, d_sim3_io;
+    staged_table sim3_tab;
     /* rectification: map map_id in its fixed-point form (one allocation each: the xy array, then ab; d == NULL: unset) and the
      * 16-byte aligned buffer ss_extract_stereo_raw remaps both eyes into */
     struct rect_map {

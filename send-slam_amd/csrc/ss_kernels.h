@@ -333,6 +333,47 @@ struct ssk_tri_call {
 };
 void ssk_tri_eval(hipStream_t s, const ssk_tri_call &t);
 void ssk_tri_compact(hipStream_t s, const ssk_tri_call &t);
+/* ss_sim3.hip: Sim3 from matched map points (DESIGN.md "Sim3 RANSAC").  Pair b solves the matches idx[b][i] of its query rows with
+ * the rows of train frame src[b] (NULL: b).  gather (one workgroup per pair, SSK_SIM3_CHUNK rows at a time in ascending order)
+ * numbers the correspondences and writes their twelve floats as a structure of arrays (corr: 12 planes of [n_frames][rows]), the
+ * number of every query row's correspondence (corr_of_row, -1: none) and N; model (one lane per pair and hypothesis) writes one
+ * ssk_sim3_model and zeroes its count; count (a lane per correspondence, SSK_SIM3_COUNT_ROWS of them and SSK_SIM3_HYP_BLOCK
+ * hypotheses per workgroup) adds the inliers; finish (one workgroup per pair) selects and writes flags and result */
+#define SSK_SIM3_CHUNK 1024
+#define SSK_SIM3_COUNT_ROWS 256
+#define SSK_SIM3_HYP_BLOCK 32
+struct alignas(16) ssk_sim3_model { /* 128 bytes, so that a wave reads one with wide scalar loads */
+    float sr12[9], t12[3], sr21[9], t21[3], s12;
+    float pad[7];
+};
+struct ssk_sim3_call {
+    int n_frames = 0, rows = 0;
+    const ss_map_point *q_xyz = nullptr, *t_xyz = nullptr;
+    const ss_keypoint *q_kp = nullptr, *t_kp = nullptr;
+    const uint8_t *q_skip = nullptr, *t_skip = nullptr; /* [n_frames][rows], or NULL */
+    const int32_t *nq = nullptr, *nt = nullptr;
+    const int32_t *src = nullptr;
+    const int32_t *frame_error = nullptr;
+    const int32_t *idx = nullptr;
+    const ss_proj_view *views1 = nullptr, *views2 = nullptr; /* device [n_frames] each */
+    float chi2 = 0;
+    int min_inliers = 0, max_iterations = 1, fix_scale = 0;
+    uint32_t seed = 0;
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    /* workspace */
+    float *corr = nullptr;
+    int32_t *corr_of_row = nullptr; /* [n_frames][rows] */
+    int32_t *n_corr = nullptr;      /* [n_frames] */
+    ssk_sim3_model *models = nullptr; /* [n_frames][max_iterations] */
+    int32_t *counts = nullptr;        /* [n_frames][max_iterations] */
+    uint8_t *inlier = nullptr;
+    ss_sim3_result *result = nullptr;
+};
+void ssk_sim3_gather(hipStream_t s, const ssk_sim3_call &g);
+void ssk_sim3_model_launch(hipStream_t s, const ssk_sim3_call &g);
+void ssk_sim3_count(hipStream_t s, const ssk_sim3_call &g);
+void ssk_sim3_finish(hipStream_t s, const ssk_sim3_call &g);
 /* ss_rectify.hip: bilinear remap through fixed-point maps (DESIGN.md "Rectification").  A map on the device is two arrays of
  * height rows, ssk_rectify_pitch(width) entries apart: xy = (uint16)ix | (uint16)iy << 16 and ab = a | b << 5; the entries past the
  * width are "outside" records.  ssk_rectify_fixed is the host conversion of a float map pair into them.  ssk_rectify remaps the

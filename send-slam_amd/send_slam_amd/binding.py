@@ -46,7 +46,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_match_proj_pairs_device", "ss_match_proj_batch_device", "ss_match_proj", "ss_epi_pair_init", "ss_epi_check_host",
            "ss_triangulate_host", "ss_match_epi_pairs_device", "ss_match_epi_batch_device", "ss_triangulate_pairs_device",
            "ss_triangulate_batch_device", "ss_fuse_view_sim3", "ss_fuse_points_host", "ss_fuse_check_host",
-           "ss_match_fuse_pairs_device", "ss_match_fuse_batch_device", "ss_match_fuse"]
+           "ss_match_fuse_pairs_device", "ss_match_fuse_batch_device", "ss_match_fuse", "ss_sim3_model_host", "ss_sim3_check_host",
+           "ss_sim3_to_view", "ss_sim3_pairs_device", "ss_sim3_batch_device", "ss_sim3"]
 
 
 class OrbParams(C.Structure):
@@ -293,6 +294,80 @@ def fuse_check_host(params: FuseParams, scale, points: np.ndarray, kp: np.ndarra
     if rc != SS_OK:
         raise OrbError(rc, "ss_fuse_check_host refused its arguments")
     return out
+
+
+SS_SIM3_MAX_ITERATIONS = 1024
+
+
+class Sim3Params(C.Structure):
+    _fields_ = [("chi2", C.c_float), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("fix_scale", C.c_int32),
+                ("seed", C.c_uint32), ("reserved", C.c_int32 * 3)]
+
+
+class Sim3Result(C.Structure):
+    _fields_ = [("sr12", C.c_float * 9), ("t12", C.c_float * 3), ("s12", C.c_float), ("sr21", C.c_float * 9), ("t21", C.c_float * 3),
+                ("state", C.c_int32), ("n_corr", C.c_int32), ("n_inliers", C.c_int32), ("best_inliers", C.c_int32),
+                ("iteration", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+# ss_sim3_result: one per pair
+SIM3_RESULT_DTYPE = np.dtype([("sr12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4"), ("sr21", "<f4", (9,)), ("t21", "<f4", (3,))] +
+                             [(n, "<i4") for n in ("state", "n_corr", "n_inliers", "best_inliers", "iteration", "status", "reserved")])
+
+
+def sim3_params(chi2: float = 9.210, min_inliers: int = 20, max_iterations: int = 300, fix_scale: bool = False, seed: int = 0,
+                reserved=(0, 0, 0)) -> Sim3Params:
+    """upstream's Sim3Solver::SetRansacParameters(0.99, 20, 300) with th 9.210; fix_scale for stereo and RGB-D"""
+    return Sim3Params(chi2=chi2, min_inliers=min_inliers, max_iterations=max_iterations, fix_scale=int(fix_scale), seed=seed & 0xFFFFFFFF,
+                      reserved=(C.c_int32 * 3)(*reserved))
+
+
+def sim3_model_host(params: Sim3Params, x1, x2) -> np.ndarray:
+    """ss_sim3_model_host: step 3b for the triple x1[k], x2[k] (3 x 3 float32 camera coordinates, draw order) -> one SIM3_RESULT_DTYPE
+    record holding the model; needs no device"""
+    a = np.ascontiguousarray(x1, np.float32).reshape(9)
+    b = np.ascontiguousarray(x2, np.float32).reshape(9)
+    out = np.zeros(1, SIM3_RESULT_DTYPE)
+    rc = load().ss_sim3_model_host(C.byref(params), a.ctypes.data, b.ctypes.data, out.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_sim3_model_host refused its arguments")
+    return out[0]
+
+
+def sim3_check_host(params: Sim3Params, view1, view2, scale, points1, kp1, points2, kp2, model):
+    """ss_sim3_check_host: steps 1 and 3c of the couples under `model` (a SIM3_RESULT_DTYPE record) -> (uint8 [n]: 0 inlier, 1 octave
+    outside the table, 2 first test fails, 3 second; float32 [n][2]: e1, e2); needs no device"""
+    v1, v2 = _views_array(view1), _views_array(view2)
+    if len(v1) != 1 or len(v2) != 1:
+        raise ValueError("one view each")
+    sc = np.ascontiguousarray(scale, np.float32)
+    p1, p2 = np.ascontiguousarray(points1, MAP_POINT_DTYPE), np.ascontiguousarray(points2, MAP_POINT_DTYPE)
+    k1, k2 = np.ascontiguousarray(kp1, KP_DTYPE), np.ascontiguousarray(kp2, KP_DTYPE)
+    n = len(p1)
+    if len(p2) != n or len(k1) != n or len(k2) != n:
+        raise ValueError("one map point and keypoint per side and couple")
+    m = np.ascontiguousarray(np.asarray(model, SIM3_RESULT_DTYPE).reshape(1))
+    out, err = np.empty(n, np.uint8), np.empty((n, 2), np.float32)
+    ptr = lambda a: a.ctypes.data if n else None  # noqa: E731
+    rc = load().ss_sim3_check_host(C.byref(params), v1.ctypes.data, v2.ctypes.data, sc.ctypes.data, len(sc), ptr(p1), ptr(k1), ptr(p2), ptr(k2), n,
+                                   m.ctypes.data, ptr(out), ptr(err))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_sim3_check_host refused its arguments")
+    return out, err
+
+
+def sim3_to_view(camera: Camera, result, rcw2, tcw2, bf: float = 0.0):
+    """ss_sim3_to_view: upstream's gScw = gScm * gSmw from a state-0 result and keyframe 2's pose -> (ProjView of keyframe 1's camera
+    under it, srcw 3 x 3, t); needs no device"""
+    m = np.ascontiguousarray(np.asarray(result, SIM3_RESULT_DTYPE).reshape(1))
+    r = np.ascontiguousarray(rcw2, np.float64).reshape(9)
+    t = np.ascontiguousarray(tcw2, np.float64).reshape(3)
+    srcw, tt, v = np.empty(9, np.float64), np.empty(3, np.float64), ProjView()
+    rc = load().ss_sim3_to_view(C.byref(camera), m.ctypes.data, r.ctypes.data, t.ctypes.data, C.c_float(bf), srcw.ctypes.data, tt.ctypes.data,
+                                C.byref(v))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_sim3_to_view refused its arguments")
+    return v, srcw.reshape(3, 3), tt
 
 
 class EpiPair(C.Structure):
@@ -561,6 +636,15 @@ def load():
                                               [C.c_void_p] * 5
     lib.ss_match_fuse.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + \
                                  [C.POINTER(FuseParams)] + [C.c_void_p] * 4 + [C.POINTER(FuseSummary)]
+    lib.ss_sim3_model_host.argtypes = [C.POINTER(Sim3Params), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ss_sim3_check_host.argtypes = [C.POINTER(Sim3Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + \
+                                      [C.c_void_p] * 3
+    lib.ss_sim3_to_view.argtypes = [C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(ProjView)]
+    lib.ss_sim3_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Sim3Params)] + \
+                                        [C.c_void_p] * 2
+    lib.ss_sim3_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(Sim3Params)] + [C.c_void_p] * 2
+    lib.ss_sim3.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.POINTER(Sim3Params), C.c_void_p,
+                                                                                            C.c_void_p]
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -1183,6 +1267,48 @@ class OrbContext:
         self._check(self._lib.ss_triangulate_batch_device(self._h, None if src is None else src.ctypes.data, C.c_void_p(d_idx), w.ctypes.data,
                                                           C.byref(params), C.c_void_p(d_info), C.c_void_p(d_points), C.c_void_p(d_point_desc),
                                                           C.c_void_p(d_point_rows), C.c_void_p(d_n_points), C.c_void_p(d_summary)))
+
+    # ---- Sim3 from matched map points: Horn RANSAC per loop candidate (the rule: include/sendslam_orb.h) ----
+    def sim3_pairs_device(self, d_query_xyz: int, d_query_kp: int, d_n_query: int, d_train_xyz: int, d_train_kp: int, d_n_train: int, d_idx: int,
+                          n_pairs: int, rows: int, views1, views2, params: Sim3Params, d_inlier: int, d_result: int, d_query_skip: int = 0,
+                          d_train_skip: int = 0):
+        """n_pairs pairs on device arrays: MAP_POINT_DTYPE / KP_DTYPE [n_pairs][rows] of either side, optional skip bytes, counts, d_idx as
+        match_bow_pairs_device wrote it; views1 / views2 host views, one per pair each; d_inlier uint8 [n_pairs][rows] by query row,
+        d_result SIM3_RESULT_DTYPE [n_pairs]; asynchronous."""
+        v1, v2 = _views_array(views1), _views_array(views2)
+        if len(v1) != n_pairs or len(v2) != n_pairs:
+            raise ValueError("one view of either keyframe per pair")
+        self._check(self._lib.ss_sim3_pairs_device(self._h, C.c_void_p(d_query_xyz), C.c_void_p(d_query_kp), C.c_void_p(d_query_skip),
+                                                   C.c_void_p(d_n_query), C.c_void_p(d_train_xyz), C.c_void_p(d_train_kp), C.c_void_p(d_train_skip),
+                                                   C.c_void_p(d_n_train), C.c_void_p(d_idx), n_pairs, rows, v1.ctypes.data if n_pairs else None,
+                                                   v2.ctypes.data if n_pairs else None, C.byref(params), C.c_void_p(d_inlier), C.c_void_p(d_result)))
+
+    def sim3_batch_device(self, d_xyz: int, d_idx: int, views, params: Sim3Params, d_inlier: int, d_result: int, train_src=None, d_skip: int = 0):
+        """the same on the frames of the last batch, frame b against train_src[b] (None: b - 1): d_xyz MAP_POINT_DTYPE
+        [n_frames][kp_capacity], views one per frame; asynchronous."""
+        v = _views_array(views)
+        src = None if train_src is None else np.ascontiguousarray(train_src, np.int32)
+        self._check(self._lib.ss_sim3_batch_device(self._h, None if src is None else src.ctypes.data, C.c_void_p(d_xyz), C.c_void_p(d_skip),
+                                                   C.c_void_p(d_idx), v.ctypes.data, C.byref(params), C.c_void_p(d_inlier), C.c_void_p(d_result)))
+
+    def sim3(self, view1, q_xyz: np.ndarray, q_kp: np.ndarray, view2, t_xyz: np.ndarray, t_kp: np.ndarray, idx: np.ndarray, params: Sim3Params,
+             q_skip=None, t_skip=None):
+        """One pair, host arrays in and out -> (uint8 inlier flag per query row, SIM3_RESULT_DTYPE record)."""
+        v1, v2 = _views_array(view1), _views_array(view2)
+        qx, tx = np.ascontiguousarray(q_xyz, MAP_POINT_DTYPE), np.ascontiguousarray(t_xyz, MAP_POINT_DTYPE)
+        qk, tk = np.ascontiguousarray(q_kp, KP_DTYPE), np.ascontiguousarray(t_kp, KP_DTYPE)
+        ix = np.ascontiguousarray(idx, np.int32)
+        nq, nt = len(qx), len(tx)
+        q_skip = None if q_skip is None else np.ascontiguousarray(q_skip, np.uint8)
+        t_skip = None if t_skip is None else np.ascontiguousarray(t_skip, np.uint8)
+        if len(v1) != 1 or len(v2) != 1 or len(qk) != nq or len(ix) != nq or len(tk) != nt or (q_skip is not None and len(q_skip) != nq) or \
+                (t_skip is not None and len(t_skip) != nt):
+            raise ValueError("views, map points, keypoints, flags and matches differ in length")
+        inlier, res = np.empty(nq, np.uint8), np.zeros(1, SIM3_RESULT_DTYPE)
+        ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+        self._check(self._lib.ss_sim3(self._h, v1.ctypes.data, ptr(qx, nq), ptr(qk, nq), ptr(q_skip, nq), nq, v2.ctypes.data, ptr(tx, nt), ptr(tk, nt),
+                                      ptr(t_skip, nt), nt, ptr(ix, nq), C.byref(params), ptr(inlier, nq), res.ctypes.data))
+        return inlier, res[0]
 
     def wait_stream(self, hip_stream: int):
         """Orders this context's stream after everything enqueued so far on another stream of the device."""

@@ -1116,6 +1116,115 @@ int ss_sim3(ss_ctx *ctx, const ss_proj_view *view1, const ss_map_point *query_xy
             int n_query, const ss_proj_view *view2, const ss_map_point *train_xyz, const ss_keypoint *train_kp, const uint8_t *train_skip,
             int n_train, const int32_t *idx, const ss_sim3_params *p, uint8_t *inlier, ss_sim3_result *result);
 
+/* ---- Pose-only optimisation: Optimizer::PoseOptimization (g2o EdgeSE3ProjectXYZOnlyPose and EdgeStereoSE3ProjectXYZOnlyPose) as
+ * TrackWithMotionModel, TrackReferenceKeyFrame, TrackLocalMap and Relocalization run it on the matches of a search, for every frame
+ * of a call at once.  It is the rule of ss_track's host step (sst_pose_only) with the stereo row added and the order of every sum
+ * fixed.  tests/pose_ref.py is its normative statement; DESIGN.md section 21.  An addition to ABI 5: nothing existing changes, and
+ * ss_track keeps calling its host step -----------------------------------------------------------------------------------------
+ * - All arithmetic is double.  Every step is one IEEE operation, left to right as written, with no contraction.  The only library
+ *   function is sqrt: no transcendental appears, because the device's and the host's differ in the last bits.
+ * - Every test is written in its accepting form, so a NaN fails it; the one exception is the step-size test of step 3.
+ * One frame: a view (ss_proj_view; only fx, fy, cx, cy, bf are read, widened to double), a start pose of twelve doubles (rcw
+ * row-major, then tcw), a block of map points (only x, y, z are read) with an optional skip byte each (fusion's convention: non-zero
+ * = no usable map point), keypoint rows (x, y, octave; taken as undistorted) with an optional right coordinate each, and idx.
+ * 1. Observations.  Slots i = 0 .. slots-1 in ascending order.  idx_by_row == 0: slots = point_rows, slot i is point row i and
+ *    idx[i] its keypoint row (what ss_match_proj_* writes).  idx_by_row == 1: slots = rows_per_frame, slot i is keypoint row i and
+ *    idx[i] its point row (what ss_match_bow_* writes, with one map point per train row as for ss_sim3_*).  A slot is an observation
+ *    iff the point row is in 0 .. n_points-1, the keypoint row in 0 .. n_kp-1, the point's skip byte (if given) is 0 and the
+ *    keypoint's octave lies in 0 .. n_levels-1.  Observations are numbered 0 .. N-1 in slot order.  X, Y, Z, u, v are the float32
+ *    inputs widened; w = 1.0 / (s*s) with s = (double)scale[octave].  The observation is stereo iff check_right is set, a right array
+ *    is given and right[row] > 0; then ur is widened as well.
+ * 2. Start.  n0 = sqrt((r0*r0 + r1*r1) + r2*r2), a = row0 / n0; d = (r3*a0 + r4*a1) + r5*a2; b = row1 - d*a; c = b / sqrt((b0*b0 +
+ *    b1*b1) + b2*b2); R = [a; c; a x c] with (a x c)0 = a1*c2 - a2*c1 and so on; t as given.  State 1: N < min_obs.
+ * 3. A step.  Each active observation (round 0: every one) with z > 0 contributes; P = R.X + t, each component ((r0*X + r1*Y) +
+ *    r2*Z) + t; iz = 1.0 / z, iz2 = iz*iz; up = fx*x*iz + cx; rx = u - up, ry = v - (fy*y*iz + cy);
+ *    J0 = {x*y*iz2*fx, -(1.0 + x*x*iz2)*fx, y*iz*fx, -iz*fx, 0, x*iz2*fx}, J1 = {(1.0 + y*y*iz2)*fy, -x*y*iz2*fy, -x*iz*fy, 0, -iz*fy,
+ *    y*iz2*fy} (products left to right; the unary minus applies to the first factor).  Stereo adds rr = ur - (up - bf*iz) and
+ *    J2 = {J0[0] - bf*y*iz2, J0[1] + bf*x*iz2, J0[2], J0[3], 0, J0[5] - bf*iz2}.  e2 = w*(rx*rx + ry*ry), stereo w*((rx*rx + ry*ry) +
+ *    rr*rr).  With delta = sqrt(chi2_mono) (stereo: sqrt(chi2_stereo)) the weight is w*delta / sqrt(e2) in a robust round when
+ *    e2 > delta*delta, else w.  With wJ = weight*J entry by entry, the term of H_ab is (wJ0[a]*J0[b] + wJ1[a]*J1[b]) + wJ2[a]*J2[b]
+ *    and that of g_a (wJ0[a]*rx + wJ1[a]*ry) + wJ2[a]*rr, a row whose entry a or b is the structural 0 above being left out (H34 has
+ *    no term and is 0).  The 26 sums (20 of H's upper triangle, 6 of g): slot s of 256 adds the terms of the active contributing
+ *    observations k = s, s + 256, ... in ascending order from +0.0, the others are skipped; each group of 64 consecutive slots is
+ *    folded by halving (a[l] += a[l + h], h = 32 .. 1), and the four results combine as (r0 + r1) + (r2 + r3).  Solve: H symmetric,
+ *    H_aa += lambda*(1.0 + H_aa), b = -g, Cholesky column by column (s = H_jj - sum of squares in ascending k, L_jj = sqrt(s),
+ *    L_ij = (H_ij - sum) / L_jj), forward then backward substitution, as chol6_solve of ss_track.cpp spells it.  A pivot that is not
+ *    > 0: state 2, the pose stays the one before the step.  exp(delta), delta = (omega, upsilon): q = (w0*w0 + w1*w1) + w2*w2;
+ *    q > pi*pi (the double next to it): state 4, the pose stays; a NaN q passes and ends in step 5.  A = sum (-q)^k / (2k+1)!,
+ *    B = sum (-q)^k / (2k+2)!, C = sum (-q)^k / (2k+3)!, k = 0 .. 14, Horner from the last term (acc = acc*(-q) + coefficient; the coefficients are the
+ *    doubles next to 1/n!, a table of hex-float literals in csrc/ss_pose_steps.h).  The first term left out is below 2^-60 for
+ *    q <= pi*pi.  dR = I + A.W + B.W2 and V = I + B.W + C.W2 with W the cross-product matrix of omega and W2 its square written as
+ *    W2_ii = -(the two other squares' sum), W2_ij = wi*wj; a diagonal entry is 1.0 + B*W2_ii, an off-diagonal one B*W2_ij -+ A*wk.
+ *    dt_i = (V_i0*u0 + V_i1*u1) + V_i2*u2.  Update: R <- dR.R, t <- dR.t + dt, each entry ((a*b + c*d) + e*f) [+ g].  A round ends
+ *    after `iterations` steps, or after a step with every |delta_a| < step_eps.
+ * 4. After a round.  The chi-square of every observation, outliers included, under the new pose: z > 0 is required, else 1e30; the
+ *    projection is formed with / z (up = fx*x/z + cx; stereo: er = ur - (up - bf/z)); chi2 = w*(ex*ex + ey*ey), stereo
+ *    w*((ex*ex + ey*ey) + er*er).  An outlier iff not chi2 <= th, th = chi2_mono or chi2_stereo by kind.  The inliers are the next
+ *    round's active observations.  cost is the sum of the inliers' chi-squares in the tree order above.  Fewer than min_obs inliers:
+ *    state 3, and the frame stops with the pose it has.  Rounds r < robust_rounds are robust.
+ * 5. A pose with an entry that is not finite becomes the orthonormalised start pose with state 2 (the identity and zero, should
+ *    that one not be finite either), so no NaN bits reach a result.
+ * Outputs per frame: ss_pose_result, 160 bytes.  Per slot one byte: 0 inlier, 1 outlier (mvbOutlier), 2 no observation; the flags
+ * are those of the last classification that ran, and all 0 before any (then n_inliers = n_obs and cost = 0).  rcw and tcw feed
+ * ss_proj_view_init unchanged.
+ * Deviations from upstream: robust_rounds defaults to 2, the host step's value (upstream's loop effectively has 3: it switches the
+ * kernel off from its third pass on but optimises before it does); the exponential by series (sin and cos there); lambda and the
+ * early end of a round are the host step's (g2o's Levenberg-Marquardt adapts lambda and has its own stop test); a point behind the
+ * camera takes no part in a step; the order of every sum is fixed; a step above pi ends the frame; keypoints are taken as
+ * undistorted.  Against sst_pose_only: the tree of a sum (four interleaved partial sums there), delta*delta in place of the
+ * literal 5.991 on the right of the Huber test, a NaN delta does not end a round, and the stereo row. */
+typedef struct {          /* 64 bytes */
+    double chi2_mono;     /* finite and > 0; upstream: 5.991 */
+    double chi2_stereo;   /* finite and > 0; upstream: 7.815 */
+    double lambda;        /* finite and >= 0; the host step: 1e-6 */
+    double step_eps;      /* finite and >= 0; the host step: 1e-10; 0 runs every step */
+    int32_t n_rounds;     /* 1 .. 8; upstream: 4 */
+    int32_t iterations;   /* 1 .. 32; upstream: 10 */
+    int32_t robust_rounds; /* 0 .. 8; the host step: 2 */
+    int32_t min_obs;      /* >= 3; upstream: 3 */
+    int32_t check_right;  /* non-zero: a row with right > 0 is a stereo observation */
+    int32_t idx_by_row;   /* 0: idx by point row; 1: idx by keypoint row */
+    int32_t reserved[2];  /* must be 0 */
+} ss_pose_opt_params;
+typedef struct {          /* 160 bytes, one per frame */
+    double rcw[9], tcw[3];
+    double cost;          /* the sum of the inliers' chi-squares after the last round that ended */
+    int32_t state;        /* 0 ok, 1 too few observations, 2 not positive definite, 3 too few inliers, 4 step too large */
+    int32_t status;       /* SS_OK, or the frame_error that voided the frame (no observations, state 1) */
+    int32_t n_obs, n_stereo, n_inliers;
+    int32_t steps[8];     /* steps taken in round r */
+    int32_t reserved;     /* 0 */
+} ss_pose_result;
+/* The whole rule on the host from the text the kernels compile (csrc/ss_pose_steps.h), one frame; needs no device.  start: twelve
+ * doubles; scale: n_levels entries, 1 <= n_levels <= SS_MAX_LEVELS; skip and right may be NULL; idx and flags have n_points entries
+ * (idx_by_row == 0) or n_kp (idx_by_row == 1).  p is checked as the device calls check it (SS_ERR_INVALID_ARG). */
+int ss_pose_opt_host(const ss_proj_view *view, const double *start, const float *scale, int n_levels, const ss_map_point *points,
+                     const uint8_t *point_skip, int n_points, const ss_keypoint *kp, const float *right, int n_kp, const int32_t *idx,
+                     const ss_pose_opt_params *p, uint8_t *flags, ss_pose_result *result);
+/* n_frames frames on caller-supplied device arrays.  Map points as for ss_match_proj_pairs_device: d_points [n_blocks][point_rows]
+ * ss_map_point, d_point_skip uint8 [n_blocks][point_rows] or NULL, d_n_points device int32 [n_blocks]; point_src a HOST table
+ * [n_frames] of block numbers or NULL (frame b reads block b).  Keypoints: d_kp [n_frames][rows_per_frame] ss_keypoint, d_right float
+ * [n_frames][rows_per_frame] or NULL, d_n_kp device int32 [n_frames]; counts are clamped to 0 .. their rows.  d_idx int32 and
+ * d_flags uint8 are [n_frames][slots].  views (n_frames) and start_poses (n_frames x 12 doubles) are HOST tables, copied before the
+ * call returns.  d_result [n_frames] ss_pose_result.  SS_ERR_INVALID_ARG: either row count above SS_GUIDED_MAX_ROWS, a parameter
+ * out of its range, a reserved field that is not 0, a point_src entry outside 0 .. n_blocks - 1, a NULL buffer.  Asynchronous on the
+ * context's stream. */
+int ss_pose_opt_pairs_device(ss_ctx *ctx, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks,
+                             int point_rows, const void *d_kp, const void *d_right, const void *d_n_kp, int n_frames, int rows_per_frame,
+                             const void *d_idx, const ss_proj_view *views, const double *start_poses, const int32_t *point_src,
+                             const ss_pose_opt_params *p, void *d_flags, void *d_result);
+/* The same, the keypoints being the frames of the last ss_extract_batch_device batch (SS_ERR_STATE without one; n_frames and
+ * rows_per_frame = kp_capacity are the batch's; d_right is [n_frames][kp_capacity] or NULL).  A frame whose frame_error is set gets
+ * that status, state 1 and flag 2 in every slot. */
+int ss_pose_opt_batch_device(ss_ctx *ctx, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks,
+                             int point_rows, const void *d_right, const void *d_idx, const ss_proj_view *views, const double *start_poses,
+                             const int32_t *point_src, const ss_pose_opt_params *p, void *d_flags, void *d_result);
+/* One frame with host pointers in and out (copy in, the pairs form, copy out), synchronous.  n_points, n_kp <= SS_GUIDED_MAX_ROWS;
+ * point_skip and right may be NULL; idx and flags as for ss_pose_opt_host. */
+int ss_pose_opt(ss_ctx *ctx, const ss_proj_view *view, const double *start, const ss_map_point *points, const uint8_t *point_skip,
+                int n_points, const ss_keypoint *kp, const float *right, int n_kp, const int32_t *idx, const ss_pose_opt_params *p,
+                uint8_t *flags, ss_pose_result *result);
+
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device
  * (hipStream_t; NULL = the legacy default stream): for callers that produce the inputs of a *_device call on their own

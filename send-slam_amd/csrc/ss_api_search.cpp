@@ -1,6 +1,6 @@
 /*
  * ss_api_search.cpp -- the search family of the C ABI (include/sendslam_orb.h): guided matching, map-point projection search,
- * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation, the Sim3 RANSAC.  Each has a pairs form on caller arrays, a batch form on the
+ * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation, the Sim3 RANSAC, the pose-only optimisation.  Each has a pairs form on caller arrays, a batch form on the
  * frames of the last extraction and, for some, a host form.  The context and the helpers they share: ss_ctx.h.
  */
 #include <algorithm>
@@ -16,6 +16,7 @@
 #include "ss_ctx.h"
 #include "ss_epi_steps.h"
 #include "ss_fuse_steps.h"
+#include "ss_pose_steps.h"
 #include "ss_proj_steps.h"
 #include "ss_sim3_steps.h"
 
@@ -1556,6 +1557,242 @@ int ss_sim3(ss_ctx *c, const ss_proj_view *view1, const ss_map_point *query_xyz,
     if (rc == SS_OK)
         rc = ss_sim3_pairs_device(c, io[QX].d, io[QK].d, query_skip ? io[QS].d : nullptr, io[N].d, io[TX].d, io[TK].d, train_skip ? io[TS].d : nullptr,
                                   io[N].d + 4, io[IDX].d, 1, (int)rows, view1, view2, p, io[INL].d, io[RES].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
+}
+
+/* ---- pose-only optimisation (csrc/ss_pose.hip, csrc/ss_pose_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *pose_params_error(const ss_pose_opt_params *p)
+{
+    if (!p) return "pose optimisation: params is NULL";
+    if (!(p->chi2_mono > 0.0) || !std::isfinite(p->chi2_mono)) return "pose optimisation: chi2_mono must be finite and > 0";
+    if (!(p->chi2_stereo > 0.0) || !std::isfinite(p->chi2_stereo)) return "pose optimisation: chi2_stereo must be finite and > 0";
+    if (!(p->lambda >= 0.0) || !std::isfinite(p->lambda)) return "pose optimisation: lambda must be finite and >= 0";
+    if (!(p->step_eps >= 0.0) || !std::isfinite(p->step_eps)) return "pose optimisation: step_eps must be finite and >= 0";
+    if (p->n_rounds < 1 || p->n_rounds > 8) return "pose optimisation: n_rounds must be 1 .. 8";
+    if (p->iterations < 1 || p->iterations > 32) return "pose optimisation: iterations must be 1 .. 32";
+    if (p->robust_rounds < 0 || p->robust_rounds > 8) return "pose optimisation: robust_rounds must be 0 .. 8";
+    if (p->min_obs < 3) return "pose optimisation: min_obs must be >= 3";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return "pose optimisation: the reserved fields must be 0";
+    return nullptr;
+}
+
+int ss_pose_opt_host(const ss_proj_view *view, const double *start, const float *scale, int n_levels, const ss_map_point *points,
+                     const uint8_t *point_skip, int n_points, const ss_keypoint *kp, const float *right, int n_kp, const int32_t *idx,
+                     const ss_pose_opt_params *p, uint8_t *flags, ss_pose_result *result)
+{
+    if (pose_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!view || !start || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n_points < 0 || n_kp < 0 || !result) return SS_ERR_INVALID_ARG;
+    const int slots = p->idx_by_row ? n_kp : n_points;
+    if ((n_points > 0 && !points) || (n_kp > 0 && !kp) || (slots > 0 && (!idx || !flags))) return SS_ERR_INVALID_ARG;
+    /* step 1 */
+    std::vector<ss_pose_obs> obs;
+    std::vector<int> slot_of;
+    int n_stereo = 0;
+    for (int i = 0; i < slots; i++) {
+        const int prow = p->idx_by_row ? idx[i] : i, krow = p->idx_by_row ? i : idx[i];
+        flags[i] = 2;
+        if (!(prow >= 0 && prow < n_points && krow >= 0 && krow < n_kp)) continue;
+        const int octave = kp[krow].octave;
+        if (!(octave >= 0 && octave < n_levels)) continue;
+        if (point_skip && point_skip[prow] != 0) continue;
+        const float ur = ss_pose_stored_right(p->check_right != 0, right != nullptr, right ? right[krow] : 0.0f);
+        obs.push_back(ss_pose_obs_of(points[prow].x, points[prow].y, points[prow].z, kp[krow].x, kp[krow].y, ur, scale[octave]));
+        slot_of.push_back(i);
+        n_stereo += obs.back().stereo ? 1 : 0;
+    }
+    const int n = (int)obs.size();
+    const ss_pose_cam cam = ss_pose_cam_of(*view, p->chi2_mono, p->chi2_stereo);
+    double R[9], t[3], R0[9], t0[3];
+    const bool start_ok = ss_pose_start(start, R, t);
+    memcpy(R0, R, sizeof(R));
+    memcpy(t0, t, sizeof(t));
+    std::vector<uint8_t> active((size_t)n, 1);
+    int state = !start_ok ? 2 : n < p->min_obs ? 1 : 0, n_in = n;
+    int32_t steps[8] = {};
+    double cost = 0.0;
+    std::vector<double> slot((size_t)(SS_POSE_SUMS + 1) * SS_POSE_SLOTS);
+    for (int round = 0; state == 0 && round < p->n_rounds; round++) {
+        const bool robust = round < p->robust_rounds;
+        for (int it = 0; it < p->iterations; it++) {
+            std::fill(slot.begin(), slot.end(), 0.0);
+            for (int k = 0; k < n; k++) {
+                double term[SS_POSE_SUMS];
+                if (!active[(size_t)k] || !ss_pose_terms(obs[(size_t)k], cam, R, t, robust, term)) continue;
+                for (int s = 0; s < SS_POSE_SUMS; s++) {
+                    double &a = slot[(size_t)s * SS_POSE_SLOTS + k % SS_POSE_SLOTS];
+                    a = a + term[s];
+                }
+            }
+            double sum[SS_POSE_SUMS];
+            for (int s = 0; s < SS_POSE_SUMS; s++) sum[s] = ss_pose_tree(&slot[(size_t)s * SS_POSE_SLOTS]);
+            bool small;
+            const int rc = ss_pose_step(sum, p->lambda, p->step_eps, R, t, &small);
+            if (rc != 0) {
+                state = rc;
+                break;
+            }
+            steps[round]++;
+            if (small) break;
+        }
+        if (state != 0) break;
+        /* step 4 */
+        double *c = &slot[(size_t)SS_POSE_SUMS * SS_POSE_SLOTS];
+        std::fill(c, c + SS_POSE_SLOTS, 0.0);
+        n_in = 0;
+        for (int k = 0; k < n; k++) {
+            const double chi2 = ss_pose_chi2(obs[(size_t)k], cam, R, t);
+            active[(size_t)k] = ss_pose_inlier(obs[(size_t)k], cam, chi2) ? 1 : 0;
+            if (!active[(size_t)k]) continue;
+            c[k % SS_POSE_SLOTS] = c[k % SS_POSE_SLOTS] + chi2;
+            n_in++;
+        }
+        cost = ss_pose_tree(c);
+        if (n_in < p->min_obs) state = 3;
+    }
+    if (!ss_pose_all_finite(R, t)) {
+        state = 2;
+        memcpy(R, R0, sizeof(R));
+        memcpy(t, t0, sizeof(t));
+    }
+    for (int k = 0; k < n; k++) flags[slot_of[(size_t)k]] = active[(size_t)k] ? 0 : 1;
+    memset(result, 0, sizeof(*result));
+    memcpy(result->rcw, R, sizeof(R));
+    memcpy(result->tcw, t, sizeof(t));
+    result->cost = cost;
+    result->state = state;
+    result->n_obs = n, result->n_stereo = n_stereo, result->n_inliers = n_in;
+    memcpy(result->steps, steps, sizeof(steps));
+    return SS_OK;
+}
+
+/* The checks the device forms share, the workspace, the host tables (views, block numbers, start poses), then the two launches of
+ * a call whose device operands and outputs are filled in */
+static int pose_run(ss_ctx *c, ssk_pose_call &g, int n_blocks, const ss_proj_view *views, const double *start_poses, const int32_t *point_src,
+                    const ss_pose_opt_params *p)
+{
+    if (const char *msg = pose_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (g.n_frames < 0 || n_blocks < 0 || g.point_rows < 1 || g.rows < 1) return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: bad frame, block or row count");
+    if (g.point_rows > SS_GUIDED_MAX_ROWS || g.rows > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: point_rows " + std::to_string(g.point_rows) + " / rows_per_frame " + std::to_string(g.rows) +
+                                               " exceed SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    if (g.n_frames > 65535) return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: more than 65535 frames in one call");
+    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
+        return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: the context's n_levels / scale_factor give no pyramid table");
+    if (g.n_frames == 0) return SS_OK;
+    if (!views || !start_poses) return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: views or start_poses is NULL");
+    for (int b = 0; b < g.n_frames; b++) {
+        const int pb = point_src ? point_src[b] : b;
+        if (pb < 0 || pb >= n_blocks)
+            return fail(c, SS_ERR_INVALID_ARG, std::string(point_src ? "point_src[" : "frame [") + std::to_string(b) + "] = " + std::to_string(pb) +
+                                                   " names no block of points (" + std::to_string(n_blocks) + ")");
+    }
+    if (!g.points || !g.np || !g.kp || !g.nk || !g.idx || !g.flags || !g.result) return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: NULL buffer");
+    g.chi2_mono = p->chi2_mono, g.chi2_stereo = p->chi2_stereo, g.lambda = p->lambda, g.step_eps = p->step_eps;
+    g.n_rounds = p->n_rounds, g.iterations = p->iterations, g.robust_rounds = p->robust_rounds, g.min_obs = p->min_obs;
+    g.check_right = p->check_right != 0, g.idx_by_row = p->idx_by_row != 0;
+    g.slots = g.idx_by_row ? g.rows : g.point_rows;
+    g.n_levels = c->params.n_levels;
+    ss_scale_table(c->params.scale_factor, g.n_levels, g.scale);
+    const size_t ns = (size_t)g.n_frames * g.slots;
+    int rc = carve_from(c, c->d_pose_ws, [&](carve &w) {
+        g.planes = w.take<float>(7 * ns * sizeof(float));
+        g.slot_of = w.take<int32_t>(ns * sizeof(int32_t));
+        g.n_obs = w.take<int32_t>((size_t)g.n_frames * sizeof(int32_t));
+    });
+    if (rc != SS_OK) return rc;
+    /* the host tables of the call: n_frames views, then n_frames start poses, then n_frames block numbers */
+    const size_t vb = (size_t)g.n_frames * sizeof(ss_proj_view), sb = (size_t)g.n_frames * 12 * sizeof(double);
+    rc = staged_upload(c, c->pose_tab, vb + sb + (size_t)g.n_frames * sizeof(int32_t), [&](uint8_t *h) {
+        memcpy(h, views, vb);
+        memcpy(h + vb, start_poses, sb);
+        int32_t *src = (int32_t *)(h + vb + sb);
+        for (int b = 0; b < g.n_frames; b++) src[b] = point_src ? point_src[b] : b;
+    });
+    if (rc != SS_OK) return rc;
+    g.views = c->pose_tab.as<ss_proj_view>();
+    g.start = c->pose_tab.as<double>(vb);
+    g.src = c->pose_tab.as<int32_t>(vb + sb);
+    {
+        /* per slot: its match and its flag or slot number; an observation reads a map point, a keypoint, up to a flag and a right
+         * coordinate and writes its seven floats */
+        stage_timer t(c, "pose_gather", (int64_t)ns * (4 + 4 + (int64_t)sizeof(ss_map_point) + (int64_t)sizeof(ss_keypoint) + (g.p_skip ? 1 : 0) + (g.right ? 4 : 0) + 28) +
+                                            (int64_t)g.n_frames * 4);
+        ssk_pose_gather(c->stream, g);
+    }
+    {
+        /* every step and every classification reads the observations' planes once (an upper bound: a round may end early) */
+        const int64_t passes = (int64_t)g.n_rounds * (g.iterations + 1);
+        stage_timer t(c, "pose_solve", (int64_t)ns * (28 * passes + 4 + 1) + (int64_t)g.n_frames * (int64_t)(sizeof(ss_proj_view) + 96 + sizeof(ss_pose_result)));
+        ssk_pose_solve(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_pose_opt_pairs_device(ss_ctx *c, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks, int point_rows,
+                             const void *d_kp, const void *d_right, const void *d_n_kp, int n_frames, int rows_per_frame, const void *d_idx,
+                             const ss_proj_view *views, const double *start_poses, const int32_t *point_src, const ss_pose_opt_params *p,
+                             void *d_flags, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    ssk_pose_call g;
+    g.n_frames = n_frames, g.point_rows = point_rows, g.rows = rows_per_frame;
+    g.points = (const ss_map_point *)d_points, g.p_skip = (const uint8_t *)d_point_skip, g.np = (const int32_t *)d_n_points;
+    g.kp = (const ss_keypoint *)d_kp, g.right = (const float *)d_right, g.nk = (const int32_t *)d_n_kp;
+    g.idx = (const int32_t *)d_idx;
+    g.flags = (uint8_t *)d_flags, g.result = (ss_pose_result *)d_result;
+    return pose_run(c, g, n_blocks, views, start_poses, point_src, p);
+}
+
+int ss_pose_opt_batch_device(ss_ctx *c, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks, int point_rows,
+                             const void *d_right, const void *d_idx, const ss_proj_view *views, const double *start_poses, const int32_t *point_src,
+                             const ss_pose_opt_params *p, void *d_flags, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_pose_opt_batch_device")) return SS_ERR_STATE;
+    ssk_pose_call g;
+    g.n_frames = c->last_n_frames, g.point_rows = point_rows, g.rows = c->hg.kcap;
+    g.points = (const ss_map_point *)d_points, g.p_skip = (const uint8_t *)d_point_skip, g.np = (const int32_t *)d_n_points;
+    g.kp = c->ws.kps, g.right = (const float *)d_right, g.nk = c->ws.n_kp;
+    const int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
+    g.idx = (const int32_t *)d_idx;
+    g.flags = (uint8_t *)d_flags, g.result = (ss_pose_result *)d_result;
+    return pose_run(c, g, n_blocks, views, start_poses, point_src, p);
+}
+
+int ss_pose_opt(ss_ctx *c, const ss_proj_view *view, const double *start, const ss_map_point *points, const uint8_t *point_skip, int n_points,
+                const ss_keypoint *kp, const float *right, int n_kp, const int32_t *idx, const ss_pose_opt_params *p, uint8_t *flags,
+                ss_pose_result *result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = pose_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_points < 0 || n_kp < 0 || n_points > SS_GUIDED_MAX_ROWS || n_kp > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: n_points and n_kp must be 0 .. SS_GUIDED_MAX_ROWS");
+    const size_t ns = (size_t)(p->idx_by_row ? n_kp : n_points);
+    if (!view || !start || !result || (n_points > 0 && !points) || (n_kp > 0 && !kp) || (ns > 0 && (!idx || !flags)))
+        return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: NULL buffer");
+    /* one block of `pr` points, one frame of `kr` rows; `counts` is on this stack: no return before the stream has read it */
+    const size_t pr = (size_t)std::max(n_points, 1), kr = (size_t)std::max(n_kp, 1), np = (size_t)n_points, nk = (size_t)n_kp;
+    const size_t sr = p->idx_by_row ? kr : pr;
+    const int32_t counts[2] = {n_points, n_kp};
+    enum { PT, PS, KP, RT, IDX, N, FL, RES, PIECES };
+    io_piece io[PIECES] = {{points, nullptr, pr * sizeof(ss_map_point), np * sizeof(ss_map_point)}, {point_skip, nullptr, pr, np},
+                           {kp, nullptr, kr * sizeof(ss_keypoint), nk * sizeof(ss_keypoint)}, {right, nullptr, kr * 4, nk * 4},
+                           {idx, nullptr, sr * 4, ns * 4}, {counts, nullptr, sizeof(counts), sizeof(counts)}, {nullptr, flags, sr, ns},
+                           {nullptr, result, sizeof(ss_pose_result), sizeof(ss_pose_result)}};
+    int rc = io_send(c, c->d_pose_io, io, PIECES);
+    if (rc == SS_OK)
+        rc = ss_pose_opt_pairs_device(c, io[PT].d, point_skip ? io[PS].d : nullptr, io[N].d, 1, (int)pr, io[KP].d, right ? io[RT].d : nullptr, io[N].d + 4, 1,
+                                      (int)kr, io[IDX].d, view, start, nullptr, p, io[FL].d, io[RES].d);
     if (rc != SS_OK) {
         (void)hipStreamSynchronize(c->stream);
         return rc;

@@ -148,6 +148,10 @@ struct ss_ctx {
      * (views1, then views2) */
     dev_buf<uint8_t> d_sim3_ws, d_sim3_io;
     staged_table sim3_tab;
+    /* pose-only optimisation: the workspace of a call (the observations' planes and slots, their counts), the host form's device
+     * copies, the tables of a call (views, then block numbers, then start poses) */
+    dev_buf<uint8_t> d_pose_ws, d_pose_io;
+    staged_table pose_tab;
     /* rectification: map map_id in its fixed-point form (one allocation each: the xy array, then ab; d == NULL: unset) and the
      * 16-byte aligned buffer ss_extract_stereo_raw remaps both eyes into */
     struct rect_map {

@@ -374,6 +374,39 @@ void ssk_sim3_gather(hipStream_t s, const ssk_sim3_call &g);
 void ssk_sim3_model_launch(hipStream_t s, const ssk_sim3_call &g);
 void ssk_sim3_count(hipStream_t s, const ssk_sim3_call &g);
 void ssk_sim3_finish(hipStream_t s, const ssk_sim3_call &g);
+/* ss_pose.hip: pose-only optimisation (DESIGN.md "Pose-only optimisation").  Frame b optimises its start pose on the observations
+ * its slots give: slot i pairs point row i of block src[b] with keypoint row idx[b][i] (idx_by_row: keypoint row i with point row
+ * idx[b][i]); slots = idx_by_row ? rows : point_rows.  gather (one workgroup per frame, SSK_POSE_CHUNK slots at a time in ascending
+ * order) numbers the observations, writes their seven floats as a structure of arrays (planes: 7 of [n_frames][slots]), the slot of
+ * every observation and N, and flag 2 into every other slot; solve (one workgroup per frame) runs every round and step and writes
+ * the observations' flags and the result */
+#define SSK_POSE_CHUNK 1024
+struct ssk_pose_call {
+    int n_frames = 0, point_rows = 0, rows = 0, slots = 0;
+    const ss_map_point *points = nullptr; /* [n_blocks][point_rows] */
+    const uint8_t *p_skip = nullptr;      /* [n_blocks][point_rows], or NULL */
+    const int32_t *np = nullptr;
+    const int32_t *src = nullptr;         /* device int32 [n_frames] */
+    const ss_proj_view *views = nullptr;  /* device [n_frames] */
+    const double *start = nullptr;        /* device [n_frames][12] */
+    const ss_keypoint *kp = nullptr;      /* [n_frames][rows] */
+    const float *right = nullptr;         /* [n_frames][rows], or NULL */
+    const int32_t *nk = nullptr;
+    const int32_t *frame_error = nullptr; /* per frame, or NULL */
+    const int32_t *idx = nullptr;         /* [n_frames][slots] */
+    double chi2_mono = 0, chi2_stereo = 0, lambda = 0, step_eps = 0;
+    int n_rounds = 1, iterations = 1, robust_rounds = 0, min_obs = 3, check_right = 0, idx_by_row = 0;
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    /* workspace */
+    float *planes = nullptr;
+    int32_t *slot_of = nullptr; /* [n_frames][slots] */
+    int32_t *n_obs = nullptr;   /* [n_frames] */
+    uint8_t *flags = nullptr;   /* [n_frames][slots] */
+    ss_pose_result *result = nullptr;
+};
+void ssk_pose_gather(hipStream_t s, const ssk_pose_call &g);
+void ssk_pose_solve(hipStream_t s, const ssk_pose_call &g);
 /* ss_rectify.hip: bilinear remap through fixed-point maps (DESIGN.md "Rectification").  A map on the device is two arrays of
  * height rows, ssk_rectify_pitch(width) entries apart: xy = (uint16)ix | (uint16)iy << 16 and ab = a | b << 5; the entries past the
  * width are "outside" records.  ssk_rectify_fixed is the host conversion of a float map pair into them.  ssk_rectify remaps the

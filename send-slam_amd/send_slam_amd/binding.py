@@ -47,7 +47,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_triangulate_host", "ss_match_epi_pairs_device", "ss_match_epi_batch_device", "ss_triangulate_pairs_device",
            "ss_triangulate_batch_device", "ss_fuse_view_sim3", "ss_fuse_points_host", "ss_fuse_check_host",
            "ss_match_fuse_pairs_device", "ss_match_fuse_batch_device", "ss_match_fuse", "ss_sim3_model_host", "ss_sim3_check_host",
-           "ss_sim3_to_view", "ss_sim3_pairs_device", "ss_sim3_batch_device", "ss_sim3"]
+           "ss_sim3_to_view", "ss_sim3_pairs_device", "ss_sim3_batch_device", "ss_sim3", "ss_pose_opt_host", "ss_pose_opt_pairs_device",
+           "ss_pose_opt_batch_device", "ss_pose_opt"]
 
 
 class OrbParams(C.Structure):
@@ -370,6 +371,60 @@ def sim3_to_view(camera: Camera, result, rcw2, tcw2, bf: float = 0.0):
     return v, srcw.reshape(3, 3), tt
 
 
+class PoseOptParams(C.Structure):
+    _fields_ = [("chi2_mono", C.c_double), ("chi2_stereo", C.c_double), ("lambda_", C.c_double), ("step_eps", C.c_double),
+                ("n_rounds", C.c_int32), ("iterations", C.c_int32), ("robust_rounds", C.c_int32), ("min_obs", C.c_int32),
+                ("check_right", C.c_int32), ("idx_by_row", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# ss_pose_result: one per frame
+POSE_RESULT_DTYPE = np.dtype([("rcw", "<f8", (9,)), ("tcw", "<f8", (3,)), ("cost", "<f8")] +
+                             [(n, "<i4") for n in ("state", "status", "n_obs", "n_stereo", "n_inliers")] + [("steps", "<i4", (8,)), ("reserved", "<i4")])
+
+
+def pose_opt_params(chi2_mono: float = 5.991, chi2_stereo: float = 7.815, lambda_: float = 1e-6, step_eps: float = 1e-10, n_rounds: int = 4,
+                    iterations: int = 10, robust_rounds: int = 2, min_obs: int = 3, check_right: bool = False, idx_by_row: bool = False,
+                    reserved=(0, 0)) -> PoseOptParams:
+    """upstream's Optimizer::PoseOptimization: 4 rounds of 10 steps, chi-square 5.991 / 7.815; lambda, step_eps and robust_rounds are
+    the host step's (sst_pose_only)"""
+    return PoseOptParams(chi2_mono=chi2_mono, chi2_stereo=chi2_stereo, lambda_=lambda_, step_eps=step_eps, n_rounds=n_rounds,
+                         iterations=iterations, robust_rounds=robust_rounds, min_obs=min_obs, check_right=int(check_right),
+                         idx_by_row=int(idx_by_row), reserved=(C.c_int32 * 2)(*reserved))
+
+
+def _start_array(start, n):
+    """n start poses, each twelve doubles (rcw row-major, then tcw) -> a contiguous float64 array [n][12]"""
+    a = np.ascontiguousarray(start, np.float64).reshape(-1, 12)
+    if len(a) != n:
+        raise ValueError("one start pose of twelve doubles per frame")
+    return a
+
+
+def pose_opt_host(view, start, scale, points: np.ndarray, kp: np.ndarray, idx: np.ndarray, params: PoseOptParams, skip=None, right=None):
+    """ss_pose_opt_host: the whole rule on the host for one frame -> (uint8 flag per slot: 0 inlier, 1 outlier, 2 no observation; one
+    POSE_RESULT_DTYPE record); needs no device"""
+    v = _views_array(view)
+    if len(v) != 1:
+        raise ValueError("one view")
+    st = _start_array(start, 1)
+    sc = np.ascontiguousarray(scale, np.float32)
+    pts, k = np.ascontiguousarray(points, MAP_POINT_DTYPE), np.ascontiguousarray(kp, KP_DTYPE)
+    ix = np.ascontiguousarray(idx, np.int32)
+    n_p, n_k = len(pts), len(k)
+    ns = n_k if params.idx_by_row else n_p
+    skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    right = None if right is None else np.ascontiguousarray(right, np.float32)
+    if len(ix) != ns or (skip is not None and len(skip) != n_p) or (right is not None and len(right) != n_k):
+        raise ValueError("map points, keypoints, flags and matches differ in length")
+    flags, res = np.empty(ns, np.uint8), np.zeros(1, POSE_RESULT_DTYPE)
+    ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+    rc = load().ss_pose_opt_host(v.ctypes.data, st.ctypes.data, sc.ctypes.data, len(sc), ptr(pts, n_p), ptr(skip, n_p), n_p, ptr(k, n_k),
+                                 ptr(right, n_k), n_k, ptr(ix, ns), C.byref(params), ptr(flags, ns), res.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_pose_opt_host refused its arguments")
+    return flags, res[0]
+
+
 class EpiPair(C.Structure):
     """ss_epi_pair: a (keyframe 1 = query, keyframe 2 = train) pair; float32 for the search, double for the triangulation"""
     _fields_ = [("f12", C.c_float * 9), ("ex", C.c_float), ("ey", C.c_float), ("epipole_test", C.c_int32)] + \
@@ -645,6 +700,14 @@ def load():
     lib.ss_sim3_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(Sim3Params)] + [C.c_void_p] * 2
     lib.ss_sim3.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.POINTER(Sim3Params), C.c_void_p,
                                                                                             C.c_void_p]
+    lib.ss_pose_opt_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.POINTER(PoseOptParams), C.c_void_p, C.c_void_p]
+    lib.ss_pose_opt_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + \
+                                            [C.c_void_p] * 4 + [C.POINTER(PoseOptParams)] + [C.c_void_p] * 2
+    lib.ss_pose_opt_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.POINTER(PoseOptParams)] + \
+                                            [C.c_void_p] * 2
+    lib.ss_pose_opt.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PoseOptParams),
+                                                                  C.c_void_p, C.c_void_p]
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -1309,6 +1372,50 @@ class OrbContext:
         self._check(self._lib.ss_sim3(self._h, v1.ctypes.data, ptr(qx, nq), ptr(qk, nq), ptr(q_skip, nq), nq, v2.ctypes.data, ptr(tx, nt), ptr(tk, nt),
                                       ptr(t_skip, nt), nt, ptr(ix, nq), C.byref(params), ptr(inlier, nq), res.ctypes.data))
         return inlier, res[0]
+
+    # ---- pose-only optimisation: Gauss-Newton per frame of a batch (the rule: include/sendslam_orb.h) ----
+    def pose_opt_pairs_device(self, d_points: int, d_n_points: int, n_blocks: int, point_rows: int, d_kp: int, d_n_kp: int, n_frames: int,
+                              rows_per_frame: int, d_idx: int, views, start_poses, params: PoseOptParams, d_flags: int, d_result: int,
+                              point_src=None, d_point_skip: int = 0, d_right: int = 0):
+        """n_frames frames on device arrays: map points [n_blocks][point_rows] (MAP_POINT_DTYPE, optional skip bytes, counts), keypoints
+        KP_DTYPE [n_frames][rows_per_frame] (optional right coordinates, counts), d_idx as match_proj_* (or, with idx_by_row, match_bow_*)
+        wrote it; views and start_poses (twelve doubles each) host tables, one per frame; d_flags uint8 [n_frames][slots], d_result
+        POSE_RESULT_DTYPE [n_frames]; asynchronous."""
+        v, src = self._proj_tables(views, point_src, n_frames)
+        st = _start_array(start_poses, n_frames)
+        self._check(self._lib.ss_pose_opt_pairs_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_skip), C.c_void_p(d_n_points), n_blocks,
+                                                       point_rows, C.c_void_p(d_kp), C.c_void_p(d_right), C.c_void_p(d_n_kp), n_frames,
+                                                       rows_per_frame, C.c_void_p(d_idx), v.ctypes.data if n_frames else None,
+                                                       st.ctypes.data if n_frames else None, None if src is None else src.ctypes.data,
+                                                       C.byref(params), C.c_void_p(d_flags), C.c_void_p(d_result)))
+
+    def pose_opt_batch_device(self, d_points: int, d_n_points: int, n_blocks: int, point_rows: int, d_idx: int, views, start_poses,
+                              params: PoseOptParams, d_flags: int, d_result: int, point_src=None, d_point_skip: int = 0, d_right: int = 0):
+        """the same, the keypoints being the frames of the last batch (rows_per_frame = kp_capacity); asynchronous."""
+        v, src = self._proj_tables(views, point_src)
+        st = _start_array(start_poses, len(v))
+        self._check(self._lib.ss_pose_opt_batch_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_skip), C.c_void_p(d_n_points), n_blocks,
+                                                       point_rows, C.c_void_p(d_right), C.c_void_p(d_idx), v.ctypes.data, st.ctypes.data,
+                                                       None if src is None else src.ctypes.data, C.byref(params), C.c_void_p(d_flags),
+                                                       C.c_void_p(d_result)))
+
+    def pose_opt(self, view, start, points: np.ndarray, kp: np.ndarray, idx: np.ndarray, params: PoseOptParams, skip=None, right=None):
+        """One frame, host arrays in and out -> (uint8 flag per slot, POSE_RESULT_DTYPE record)."""
+        v = _views_array(view)
+        st = _start_array(start, 1)
+        pts, k = np.ascontiguousarray(points, MAP_POINT_DTYPE), np.ascontiguousarray(kp, KP_DTYPE)
+        ix = np.ascontiguousarray(idx, np.int32)
+        n_p, n_k = len(pts), len(k)
+        ns = n_k if params.idx_by_row else n_p
+        skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        right = None if right is None else np.ascontiguousarray(right, np.float32)
+        if len(v) != 1 or len(ix) != ns or (skip is not None and len(skip) != n_p) or (right is not None and len(right) != n_k):
+            raise ValueError("view, map points, keypoints, flags and matches differ in length")
+        flags, res = np.empty(ns, np.uint8), np.zeros(1, POSE_RESULT_DTYPE)
+        ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+        self._check(self._lib.ss_pose_opt(self._h, v.ctypes.data, st.ctypes.data, ptr(pts, n_p), ptr(skip, n_p), n_p, ptr(k, n_k), ptr(right, n_k),
+                                          n_k, ptr(ix, ns), C.byref(params), ptr(flags, ns), res.ctypes.data))
+        return flags, res[0]
 
     def wait_stream(self, hip_stream: int):
         """Orders this context's stream after everything enqueued so far on another stream of the device."""

@@ -21,6 +21,7 @@ import numpy as np
 
 import bow_cases as BC
 import bow_ref as B
+import camera_cases as CC
 import epi_ref as E
 import guided_cases as G
 import proj_cases as PC
@@ -64,17 +65,17 @@ def library_pair(binding, p1, p2, cam1=CAM, cam2=CAM):
     return binding.epi_pair(c1, p1[0], p1[1], c2, p2[0], p2[1])
 
 
-def second_view(rng, kp, p1, p2, noise=0.3):
-    """the keypoints seen from pose 2: back-projected at depths 2 - 8 in camera 1, projected, sub-pixel noise; octave and angle kept
-    for most rows"""
+def second_view(rng, kp, p1, p2, noise=0.3, cam1=CAM, cam2=CAM):
+    """the keypoints seen from pose 2: back-projected at depths 2 - 8 in camera 1 (cam1), projected by camera 2 (cam2), sub-pixel
+    noise; octave and angle kept for most rows"""
     n = len(kp)
     z = 2.0 + 6.0 * rng.random(n)
-    xc = np.stack([(kp["x"].astype(np.float64) - CAM[2]) / CAM[0] * z, (kp["y"].astype(np.float64) - CAM[3]) / CAM[1] * z, z], 1)
+    xc = np.stack([(kp["x"].astype(np.float64) - cam1[2]) / cam1[0] * z, (kp["y"].astype(np.float64) - cam1[3]) / cam1[1] * z, z], 1)
     xw = (xc - np.asarray(p1[1])) @ np.asarray(p1[0])          # R1^T (xc - t1)
     pc = xw @ np.asarray(p2[0]).T + np.asarray(p2[1])
     k2 = kp.copy()
-    k2["x"] = CAM[0] * pc[:, 0] / pc[:, 2] + CAM[2] + rng.normal(0, noise, n)
-    k2["y"] = CAM[1] * pc[:, 1] / pc[:, 2] + CAM[3] + rng.normal(0, noise, n)
+    k2["x"] = cam2[0] * pc[:, 0] / pc[:, 2] + cam2[2] + rng.normal(0, noise, n)
+    k2["y"] = cam2[1] * pc[:, 1] / pc[:, 2] + cam2[3] + rng.normal(0, noise, n)
     what = rng.random(n)
     k2["octave"] = np.clip(kp["octave"] + np.where(what < 0.1, 1, np.where(what < 0.2, -1, 0)), 0, 7)
     k2["angle"] = np.where(rng.random(n) < 0.15, rng.integers(0, 360, n), np.mod(kp["angle"] + rng.normal(0, 2.0, n) + 360.0, 360.0)).astype(np.float32)
@@ -82,8 +83,9 @@ def second_view(rng, kp, p1, p2, noise=0.3):
 
 
 @functools.lru_cache(maxsize=None)
-def scenes():
-    """-> list of dicts pair poses q_kp q_desc q_node q_taken t_kp t_desc t_node t_taken truth (the train row of query row i)"""
+def scenes(cams=None):
+    """-> list of dicts pair poses cams q_kp q_desc q_node q_taken t_kp t_desc t_node t_taken truth (the train row of query row i).
+    cams: the (camera 1, camera 2) of every scene, each (fx, fy, cx, cy) (a tuple of tuples; None: CAM on both sides of all)"""
     out = []
     voc = BC.vocab(VOC)
     for k, (src, a, b) in enumerate(SCENES):
@@ -91,8 +93,9 @@ def scenes():
         qk, qd = G.features(src)
         qn = np.array(BC.frame_transform(VOC, src, LEVELSUP)[1], np.int32)
         p1, p2 = pose(a), pose(b)
-        pair = make_pair(p1, p2)
-        k2, _ = second_view(rng, qk, p1, p2)
+        c1, c2 = (CAM, CAM) if cams is None else cams[k]
+        pair = make_pair(p1, p2, c1, c2)
+        k2, _ = second_view(rng, qk, p1, p2, cam1=c1, cam2=c2)
         d2 = PC.desc_near(rng, qd)
         n = len(qk)
         perm = rng.permutation(n)             # train row j holds query row perm[j]
@@ -123,7 +126,7 @@ def scenes():
         qn, tn = qn.copy(), tn.copy()
         qn[rng.random(n) < 0.05] = -1
         tn[rng.random(n) < 0.05] = -1
-        out.append({"pair": pair, "poses": (p1, p2), "q_kp": qk, "q_desc": qd, "q_node": qn, "q_taken": (rng.random(n) < 0.1).astype(np.uint8),
+        out.append({"pair": pair, "poses": (p1, p2), "cams": (c1, c2), "q_kp": qk, "q_desc": qd, "q_node": qn, "q_taken": (rng.random(n) < 0.1).astype(np.uint8),
                     "t_kp": tk, "t_desc": td, "t_node": tn, "t_taken": (rng.random(n) < 0.1).astype(np.uint8), "truth": truth})
     return out
 
@@ -163,6 +166,44 @@ def scene_triangulation(k: int):
     """-> (info, points, point_desc, point_rows, summary) of scene k's matches"""
     s = scenes()[k]
     return E.triangulate_rows(s["pair"], TRI, scale(), s["q_kp"], s["q_desc"], s["t_kp"], scene_matches(k))
+
+
+# ---- odd cameras: the three scenes, one pair of cameras each (CC.PAIR_CAMERAS) -----------------------------------------------------------
+CAMERA_COMBO = dict(coarse=False, one_to_one=True, orientation=1, taken=True)
+
+
+def camera_scenes():
+    return scenes(tuple((CC.intrinsics(a), CC.intrinsics(b)) for a, b in CC.PAIR_CAMERAS))
+
+
+@functools.lru_cache(maxsize=None)
+def camera_reference(k: int, cams=None):
+    """scene k of the camera scenes: the search, then the triangulation of its matches -> ((idx, d1, summary), (info, points,
+    point_desc, point_rows, summary)); cams: the (camera 1, camera 2) a confused pair record would hold (None: the scene's own)"""
+    s = camera_scenes()[k]
+    pair = s["pair"] if cams is None else make_pair(*s["poses"], CC.intrinsics(cams[0]), CC.intrinsics(cams[1]))
+    found = reference(dict(s, pair=pair), CAMERA_COMBO)
+    return found, E.triangulate_rows(pair, TRI, scale(), s["q_kp"], s["q_desc"], s["t_kp"], found[0])
+
+
+@functools.lru_cache(maxsize=None)
+def camera_matches(k: int) -> np.ndarray:
+    """matches for the triangulation alone, as scene_matches() makes them: the coarse search (false couples included) and every 7th
+    unmatched row given a random train row"""
+    s = camera_scenes()[k]
+    idx = reference(s, dict(coarse=True, one_to_one=False, orientation=0, taken=True))[0].copy()
+    rng = np.random.Generator(np.random.PCG64(0x7A1C + k))
+    free = np.flatnonzero(idx < 0)
+    idx[free[::7]] = rng.integers(0, len(s["t_kp"]), len(free[::7]))
+    return idx
+
+
+@functools.lru_cache(maxsize=None)
+def camera_triangulation(k: int, cams=None):
+    """-> (info, points, point_desc, point_rows, summary) of camera_matches(k), under the scene's pair or a confused one"""
+    s = camera_scenes()[k]
+    pair = s["pair"] if cams is None else make_pair(*s["poses"], CC.intrinsics(cams[0]), CC.intrinsics(cams[1]))
+    return E.triangulate_rows(pair, TRI, scale(), s["q_kp"], s["q_desc"], s["t_kp"], camera_matches(k))
 
 
 # ---- bisection on float32 / float64 bit patterns --------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ import functools
 
 import numpy as np
 
+import camera_cases as CC
 import fuse_ref as F
 import guided_cases as G
 import proj_cases as PC
@@ -215,16 +216,75 @@ SET_NAMES = [s["name"] for s in PARAM_SETS]
 
 
 @functools.lru_cache(maxsize=None)
-def scenes():
-    """proj_cases.scenes() with a seeded 10 % skip mask over the points and ids on a seeded 40 % of the train rows"""
+def scenes(cams=None):
+    """proj_cases.scenes(cams) with a seeded 10 % skip mask over the points and ids on a seeded 40 % of the train rows"""
     out = []
-    for k, s in enumerate(PC.scenes()):
+    for k, s in enumerate(PC.scenes(cams)):
         rng = np.random.Generator(np.random.PCG64(0xF5E0 + k))
         skip = (rng.random(len(s["points"])) < 0.1).astype(np.uint8)
         nt = len(s["t_kp"])
         ids = np.where(rng.random(nt) < 0.4, 1000 + np.arange(nt), -1).astype(np.int32)
         out.append(dict(s, skip=skip, train_point=ids))
     return out
+
+
+# ---- odd cameras: the three scenes, one camera each (CC.FRAME_CAMERAS) ------------------------------------------------------------------
+# Fuse as local mapping calls it, with the right coordinates (each frame's bf reaches u_right and the stereo chi-square test), and the
+# Sim3 projection search of the candidate check under views made from Scw = [s.R | s.t]
+CAMERA_SETS = {"fuse": dict(F.LOCAL_MAPPING, check_right=True), "sim3_search": dict(F.CANDIDATE_CHECK)}
+SIM3_SCALE = 1.25
+
+
+def camera_scenes():
+    return scenes(CC.FRAME_CAMERAS)
+
+
+def scw(k: int):
+    """the Sim3 of scene k's pose at the scale SIM3_SCALE: (s.R, s.t)"""
+    r, t = PC.POSES[k]
+    return SIM3_SCALE * np.asarray(r, np.float64), SIM3_SCALE * np.asarray(t, np.float64)
+
+
+def camera_view(k: int, which: str, cam):
+    """the view of scene k under a camera: the plain one, or the one ss_fuse_view_sim3 makes from scw(k)"""
+    if which == "fuse":
+        return PC.camera_view(k, cam)
+    return F.view_sim3(*cam[:4], G.W, G.H, *scw(k), cam[4])
+
+
+def library_view(binding, k: int, which: str):
+    """the same view from the library's own view makers: ss_proj_view_init for Fuse; for the Sim3 search ss_fuse_view_sim3 on scw(k),
+    and for the last scene ss_sim3_to_view on a Sim3 result of the scale alone (s12 = SIM3_SCALE, R12 = I, t12 = 0) and the scene's pose"""
+    fx, fy, cx, cy, bf = CC.FRAME_CAMERAS[k]
+    cam = binding.Camera(fx=fx, fy=fy, cx=cx, cy=cy, width=G.W, height=G.H)
+    if which == "fuse":
+        return binding.proj_view(cam, *PC.POSES[k], bf)
+    if k < 2:
+        return binding.fuse_view_sim3(cam, *scw(k), bf)
+    res = np.zeros((), binding.SIM3_RESULT_DTYPE)
+    res["sr12"], res["s12"] = (SIM3_SCALE * np.eye(3)).reshape(9), SIM3_SCALE
+    res["sr21"], res["iteration"] = (np.eye(3) / SIM3_SCALE).reshape(9), 0
+    return binding.sim3_to_view(cam, res, *PC.POSES[k], bf)[0]
+
+
+def camera_skip(k: int, shared: bool):
+    """the skip flags of frame k over its own block, or over block 0: the flags are the frame's, not the block's"""
+    s = camera_scenes()
+    skip = np.zeros(len(s[0 if shared else k]["points"]), np.uint8)
+    m = min(len(skip), len(s[k]["skip"]))
+    skip[:m] = s[k]["skip"][:m]
+    return skip
+
+
+@functools.lru_cache(maxsize=None)
+def camera_reference(k: int, which: str, shared: bool, cam=None):
+    """frame k of the camera scenes on its own block of points, or on block 0 (point_src [0, 0, 0]), under CAMERA_SETS[which]; cam:
+    the camera a confused kernel would see frame k through (None: its own)"""
+    s = camera_scenes()
+    b = s[0] if shared else s[k]
+    view = camera_view(k, which, CC.FRAME_CAMERAS[k] if cam is None else cam)
+    return F.match(view, b["points"], b["p_desc"], s[k]["t_kp"], s[k]["t_desc"], PC.scale(), skip=camera_skip(k, shared), right=s[k]["right"],
+                   taken=s[k]["taken"], train_point=s[k]["train_point"], **CAMERA_SETS[which])
 
 
 @functools.lru_cache(maxsize=None)

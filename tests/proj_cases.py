@@ -16,6 +16,7 @@ import itertools
 
 import numpy as np
 
+import camera_cases as CC
 import guided_cases as G
 import proj_ref as P
 
@@ -88,24 +89,51 @@ def back_project(rng, kp, sc, fx=FX, fy=FY, cx=CX, cy=CY, depth=None):
 
 
 @functools.lru_cache(maxsize=None)
-def scenes():
-    """-> list of dicts view points p_desc t_kp t_desc right taken, one per SCENES entry"""
+def scenes(cams=None):
+    """-> list of dicts view points p_desc t_kp t_desc right taken, one per SCENES entry.  cams: one camera (fx, fy, cx, cy, bf)
+    per scene (a tuple of tuples; None: the square camera for all): the points are back-projected and seen under it, the right
+    coordinates made with its bf"""
     out = []
     for k, (src, train) in enumerate(SCENES):
         rng = np.random.Generator(np.random.PCG64(0x9E0 + k))
         kp, desc = G.features(src)
         tk, td = G.features(train)
-        pts, z = back_project(rng, kp, scale())
-        view = P.view_init(FX, FY, CX, CY, G.W, G.H, POSES[k][0], POSES[k][1], BF)
+        fx, fy, cx, cy, bf = (FX, FY, CX, CY, BF) if cams is None else cams[k]
+        pts, z = back_project(rng, kp, scale(), fx, fy, cx, cy)
+        view = P.view_init(fx, fy, cx, cy, G.W, G.H, POSES[k][0], POSES[k][1], bf)
         # right coordinates: a stereo match at the row's depth (the map point's depth where both frames are the same, else a random
         # one), -1 for a monocular row, a wrong one for some; taken: one row in five
         depth = np.resize(np.abs(z), len(tk))
-        right = (tk["x"].astype(np.float64) - BF / depth + rng.normal(0, 0.5, len(tk))).astype(np.float32)
+        right = (tk["x"].astype(np.float64) - bf / depth + rng.normal(0, 0.5, len(tk))).astype(np.float32)
         kind = rng.random(len(tk))
         right = np.where(kind < 0.15, f32(-1), np.where(kind < 0.30, right - f32(40), right)).astype(np.float32)
         taken = (rng.random(len(tk)) < 0.2).astype(np.uint8)
         out.append({"view": view, "points": pts, "p_desc": desc_near(rng, desc), "t_kp": tk, "t_desc": td, "right": right, "taken": taken})
     return out
+
+
+# ---- odd cameras: the three scenes, one camera each (CC.FRAME_CAMERAS) ------------------------------------------------------------------
+CAMERA_COMBO = dict(ratio=(8, 10), one_to_one=True, th=3.0, check_right=True, taken=True)  # check_right: each frame's bf reaches u_right
+
+
+def camera_scenes():
+    return scenes(CC.FRAME_CAMERAS)
+
+
+def camera_view(k: int, cam):
+    """the view of scene k under another camera"""
+    return P.view_init(*cam[:4], G.W, G.H, POSES[k][0], POSES[k][1], cam[4])
+
+
+@functools.lru_cache(maxsize=None)
+def camera_reference(k: int, shared: bool, cam=None):
+    """frame k of the camera scenes on its own block of points, or on block 0 (point_src [0, 0, 0]); cam: the camera a confused
+    kernel would see frame k through (None: its own)"""
+    s, c = camera_scenes(), CAMERA_COMBO
+    b = s[0] if shared else s[k]
+    view = s[k]["view"] if cam is None else camera_view(k, cam)
+    return P.match(view, b["points"], b["p_desc"], s[k]["t_kp"], s[k]["t_desc"], scale(), th=c["th"], ratio_num=c["ratio"][0], ratio_den=c["ratio"][1],
+                   one_to_one=c["one_to_one"], check_right=c["check_right"], right=s[k]["right"], taken=s[k]["taken"])
 
 
 @functools.lru_cache(maxsize=None)

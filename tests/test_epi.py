@@ -309,6 +309,31 @@ def test_search_then_triangulate_then_project(ctx, scene_arrays):
         assert w[4]["n_in_view"] > 50 and w[4]["n_unique"] > 30, w[4]
 
 
+# ---- odd cameras, per pair and per side ---------------------------------------------------------------------------------------------------
+def test_three_camera_pairs_per_call(ctx):
+    """one call whose pairs are (camera A, camera B), (B, A) and (square, A), their records made by ss_epi_pair_init: the search, the
+    triangulation of the search's own idx on the device, and the triangulation of looser matches; every idx, d1, info record, point,
+    descriptor and row couple.  tests/test_epi_ref.py shows that exchanging fx and fy, cx and cy, the sides or the pairs changes
+    these bytes"""
+    from send_slam_amd import binding
+    scenes = EC.camera_scenes()
+    frames = [dict(s, pair=np.frombuffer(bytes(EC.library_pair(binding, *s["poses"], *s["cams"])), E.PAIR_DTYPE)[0], idx=EC.camera_matches(k))
+              for k, s in enumerate(scenes)]
+    assert len({f["pair"].tobytes() for f in frames}) == 3 and all(f["pair"].tobytes() == s["pair"].tobytes() for f, s in zip(frames, scenes))
+    n, rows = 3, SCENE_ROWS
+    dev = _upload(frames, rows)
+    found = _search(ctx, dev, n, rows, EC.combo_params(binding, EC.CAMERA_COMBO))
+    tri = _triangulate(ctx, dev, n, rows, binding.tri_params(**EC.TRI), d_idx=found.idx.data_ptr()).host()
+    loose = _triangulate(ctx, dev, n, rows, binding.tri_params(**EC.TRI)).host()
+    got = found.host()
+    for k in range(n):
+        want, want_tri = EC.camera_reference(k)
+        _check_search(f"cameras, pair {k}", got, k, want)
+        _check_tri(f"cameras, pair {k}, the search's matches", tri, k, want_tri)
+        _check_tri(f"cameras, pair {k}, looser matches", loose, k, EC.camera_triangulation(k))
+        assert want[2]["n_final"] > 150 and want_tri[4]["n_points"] > 150
+
+
 # ---- counts, capacity, compaction -----------------------------------------------------------------------------------------------------
 def test_counts_on_both_sides(ctx):
     """0, 1, 63, 64, 65 rows, counts above the rows (clamped) and negative (0), at 65 rows per frame: every frame of the call holds all

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import camera_cases as CC
 import epi_cases as EC
 import epi_ref as E
 import guided_cases as G
@@ -364,3 +365,51 @@ def test_capacity_pairs_need_both_conflict_passes():
             assert (contested < 8192).sum() > 300
         fine = EC.capacity_reference(b, coarse=False)[2]
         assert 0 < fine["n_geometric"] < summ["n_geometric"] and fine["n_accepted"] > 1000
+
+
+# ---- odd cameras: what makes the camera test of tests/test_epi.py able to fail ---------------------------------------------------------------
+def test_camera_scenes_are_live_and_the_library_makes_their_pairs():
+    """the three scenes under (A, B), (B, A) and (square, A): ss_epi_pair_init gives the reference's record; the search has matches
+    that the line test shaped, the triangulation of its matches points and rejections, the triangulation of the looser matches most
+    of its states.  The rule has no image bounds: the train keypoints of a scene whose cameras differ fall outside 320 x 240, and
+    match all the same"""
+    for k, s in enumerate(EC.camera_scenes()):
+        c1, c2 = CC.PAIR_CAMERAS[k]
+        assert s["cams"] == (CC.intrinsics(c1), CC.intrinsics(c2))
+        assert bytes(EC.library_pair(binding, *s["poses"], *s["cams"])) == s["pair"].tobytes(), k
+        assert [float(s["pair"][n]) for n in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2")] == list(c1[:4] + c2[:4])
+        (idx, d1, summ), tri = EC.camera_reference(k)
+        assert summ["n_final"] > 150 and summ["n_geometric"] < summ["n_candidates"] // 5 and summ["n_near"] > summ["n_accepted"] > summ["n_unique"], (k, summ)
+        assert (idx[idx >= 0] == s["truth"][idx >= 0]).mean() > 0.9  # the search finds the partners the scene planted
+        assert tri[4]["n_points"] > 150 and tri[4]["n_matches"] == summ["n_final"], (k, tri[4])
+        m = np.flatnonzero(idx >= 0)
+        gp, gi = binding.triangulate_host(s["pair"], binding.tri_params(**EC.TRI), EC.scale(), s["q_kp"][m], s["t_kp"][idx[m]])  # the host twins
+        assert gi.tobytes() == tri[0][m].tobytes() and gp[gi["state"] == 0].tobytes() == tri[1].tobytes(), k
+        codes = binding.epi_check_host(s["pair"], binding.epi_params(), EC.scale(), s["q_kp"], s["t_kp"][s["truth"]])
+        assert list(codes) == [E.check(s["pair"], False, EC.scale(), E.line_of(s["pair"], s["q_kp"]["x"][i], s["q_kp"]["y"][i]), *[s["t_kp"][n][s["truth"][i]]
+                                       for n in ("x", "y", "octave")]) for i in range(len(codes))] and 0 < (codes == 0).sum() < len(codes)
+        loose = EC.camera_triangulation(k)[4]
+        assert loose["n_points"] > 100 and sum(n > 0 for n in loose["n_state"]) >= 4, (k, loose)
+        outside = (s["t_kp"]["x"] < 0) | (s["t_kp"]["x"] >= G.W) | (s["t_kp"]["y"] < 0) | (s["t_kp"]["y"] >= G.H)
+        assert k == 2 or (outside.sum() > 20 and (np.isin(idx[idx >= 0], np.flatnonzero(outside))).sum() > 5), (k, int(outside.sum()))
+    assert EC.camera_reference(1)[1][4]["n_state"][1] > 0 and EC.camera_reference(2)[1][4]["n_state"][1] > 0
+
+
+@pytest.mark.parametrize("mixup", list(CC.PAIR_MIXUPS))
+def test_camera_mixups_change_the_reference(mixup):
+    """under the pair record a confusion of the cameras would make, every pair it changes has other idx and d1, and on the SAME
+    matches other triangulation info, other points and another compact block.  No mix-up is exempt"""
+    cams = list(CC.PAIR_CAMERAS)
+    mixed = CC.PAIR_MIXUPS[mixup](cams)
+    hit = CC.changed(cams, mixed, fields=(0, 1, 2, 3))
+    assert hit, mixup
+    for k in hit:
+        (ri, rd, rs), _ = EC.camera_reference(k)
+        (wi, wd, ws), _ = EC.camera_reference(k, mixed[k])
+        assert (ri != wi).sum() > 50 and (rd != wd).sum() > 50 and rs != ws, (mixup, k)
+        right, wrong = EC.camera_triangulation(k), EC.camera_triangulation(k, mixed[k])
+        assert right[0].tobytes() != wrong[0].tobytes() and right[4] != wrong[4], (mixup, k)
+        both = np.intersect1d(right[3][:, 0], wrong[3][:, 0])
+        assert len(both) == 0 or right[1][np.isin(right[3][:, 0], both)].tobytes() != wrong[1][np.isin(wrong[3][:, 0], both)].tobytes(), (mixup, k)
+        rows = np.flatnonzero((right[0]["state"] >= 0) & (wrong[0]["state"] >= 0))
+        assert (right[0]["cos_parallax"][rows] != wrong[0]["cos_parallax"][rows]).mean() > 0.9, (mixup, k)

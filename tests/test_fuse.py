@@ -264,6 +264,80 @@ def test_one_block_searched_by_several_frames(ctx, scene_arrays):
     assert sum(s["n_replace"] for s in got[4]) > 5
 
 
+# ---- odd cameras, per frame ----------------------------------------------------------------------------------------------------------------
+CAMERA_FORMS = [(w, sh) for w in FC.CAMERA_SETS for sh in (False, True)]
+CAMERA_IDS = [f"{w}_{'one_shared_block' if sh else 'own_blocks'}" for w, sh in CAMERA_FORMS]
+
+
+def _camera_frames(binding, which, shared):
+    """the camera scenes with the library's own views and the skip flags of the form"""
+    frames = [dict(f, view=np.frombuffer(bytes(FC.library_view(binding, k, which)), P.VIEW_DTYPE)[0], skip=FC.camera_skip(k, shared))
+              for k, f in enumerate(FC.camera_scenes())]
+    assert len({f["view"].tobytes() for f in frames}) == 3
+    return frames
+
+
+@pytest.mark.parametrize("which,shared", CAMERA_FORMS, ids=CAMERA_IDS)
+def test_three_cameras_per_call(ctx, which, shared):
+    """one call whose frames are seen by camera A, camera B and the square camera (fx != fy, principal points off the centre, three
+    values of bf), each on its own block of points and all on block 0 (point_src [0, 0, 0]): Fuse with the right coordinates under
+    views of ss_proj_view_init, and the Sim3 projection search under views of ss_fuse_view_sim3 and ss_sim3_to_view; the pairs form
+    and the host form.  tests/test_fuse_ref.py shows that a kernel which exchanged fx and fy or cx and cy, or read another frame's
+    view or bf, would give other bytes"""
+    from send_slam_amd import binding
+    frames = _camera_frames(binding, which, shared)
+    point_rows, rows = 470, 483
+    blocks = [dict(f, skip=None) for f in frames]
+    dev = _upload(blocks, point_rows, rows)
+    skips = np.zeros((3, point_rows), np.uint8)
+    for k, f in enumerate(frames):
+        skips[k, :len(f["skip"])] = f["skip"]
+    dev["skip"] = _to_dev(skips)
+    _sync()
+    p = binding.fuse_params(extent_w=G.W, extent_h=G.H, **FC.CAMERA_SETS[which])
+    got = _run_pairs(ctx, dev, 3, point_rows, rows, p, point_src=[0, 0, 0] if shared else None, n_blocks=1 if shared else None)
+    for k, f in enumerate(frames):
+        want = FC.camera_reference(k, which, shared)
+        _check(f"cameras, {which}, frame {k}", got, k, want)
+        b = frames[0] if shared else f
+        idx, d1, act, pts, summ = ctx.match_fuse(f["view"], b["points"], b["p_desc"], f["t_desc"], f["t_kp"], p, skip=f["skip"], right=f["right"],
+                                                 taken=f["taken"], train_point=f["train_point"])
+        _check(f"cameras, {which}, host form, frame {k}", (idx[None], d1[None], act[None], pts[None], [summ]), 0, want)
+    assert sum(s["n_add"] for s in got[4]) > 100
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["own_blocks", "one_shared_block"])
+def test_batch_form_under_a_camera_per_frame(shared):
+    """ss_match_fuse_batch_device on three extracted frames (the train frames of the camera scenes) under three cameras"""
+    from send_slam_amd import binding
+    from test_guided import _extract
+    which = "fuse"
+    frames = _camera_frames(binding, which, shared)
+    n, point_rows = 3, 500
+    views = np.concatenate([np.asarray(f["view"]).reshape(1) for f in frames])
+    with binding.OrbContext(0, n_features=G.NF, max_batch=n) as c:
+        _, kcap = _extract(c, [train for _, train in PC.SCENES])
+        pts, pd = np.zeros((n, point_rows), binding.MAP_POINT_DTYPE), np.zeros((n, point_rows, 32), np.uint8)
+        skip = np.zeros((n, point_rows), np.uint8)
+        right, taken, ids = np.full((n, kcap), -1, np.float32), np.zeros((n, kcap), np.uint8), np.full((n, kcap), -1, np.int32)
+        for b, f in enumerate(frames):
+            k, m = len(f["points"]), len(f["t_kp"])
+            pts[b, :k], pd[b, :k], skip[b, :len(f["skip"])] = f["points"], f["p_desc"], f["skip"]
+            right[b, :m], taken[b, :m], ids[b, :m] = f["right"], f["taken"], f["train_point"]
+        counts = np.array([len(f["points"]) for f in frames], np.int32)
+        d_pts, d_pd, d_n, d_skip, d_right, d_taken, d_ids = (_to_dev(a) for a in (pts, pd, counts, skip, right, taken, ids))
+        out = Outputs(n, point_rows)
+        _sync()
+        c.match_fuse_batch_device(d_pts.data_ptr(), d_pd.data_ptr(), d_n.data_ptr(), 1 if shared else n, point_rows, views,
+                                  binding.fuse_params(**FC.CAMERA_SETS[which]), *out.ptrs(), point_src=[0, 0, 0] if shared else None,
+                                  d_point_skip=d_skip.data_ptr(), d_train_right=d_right.data_ptr(), d_train_taken=d_taken.data_ptr(),
+                                  d_train_point=d_ids.data_ptr())
+        c.synchronize()
+        got = out.host()
+    for k in range(n):
+        _check(f"cameras, batch form, frame {k}", got, k, FC.camera_reference(k, which, shared))
+
+
 BATCH = ["synth_t0", "synth_t1", "flat", "synth_t1"]
 BATCH_SRC = [0, 0, 0, 1]
 

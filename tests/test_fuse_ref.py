@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import camera_cases as CC
 import fuse_cases as FC
 import fuse_ref as F
 import guided_cases as G
@@ -416,3 +417,61 @@ def test_end_to_end_chain_is_live_on_the_reference():
             total[f] += w[4][f]
     print(total)
     assert total["n_replace"] >= 1 and total["n_add"] >= 1, total
+
+
+# ---- odd cameras: what makes the camera tests of tests/test_fuse.py able to fail -----------------------------------------------------------
+FORMS = [(w, sh) for w in FC.CAMERA_SETS for sh in (False, True)]
+FORM_IDS = [f"{w}_{'one_shared_block' if sh else 'own_blocks'}" for w, sh in FORMS]
+
+
+def test_camera_views_are_the_librarys():
+    """ss_proj_view_init, ss_fuse_view_sim3 and ss_sim3_to_view under cameras A, B and the square one give the reference's views"""
+    for which in FC.CAMERA_SETS:
+        for k in range(3):
+            want = FC.camera_view(k, which, CC.FRAME_CAMERAS[k])
+            assert _view_bytes(FC.library_view(binding, k, which)) == want.tobytes(), (which, k)
+            assert [float(want[n]) for n in ("fx", "fy", "cx", "cy", "bf")] == list(CC.FRAME_CAMERAS[k])
+    # the Sim3 views are the plain ones up to the rounding of s.R / s
+    for k in range(3):
+        a, b = FC.camera_view(k, "fuse", CC.A), FC.camera_view(k, "sim3_search", CC.A)
+        assert np.abs(a["rcw"] - b["rcw"]).max() < 1e-6 and np.abs(a["tcw"] - b["tcw"]).max() < 1e-6
+
+
+@pytest.mark.parametrize("which,shared", FORMS, ids=FORM_IDS)
+def test_camera_scenes_are_live(which, shared):
+    """every state of step 1 on every frame, rows outside the image under the off-centre principal points, chi-square rejections
+    under Fuse, adds and replacements on the frames' own blocks"""
+    for k in range(3):
+        idx, d1, act, pts, summ, found = FC.camera_reference(k, which, shared)
+        assert set(pts["state"].tolist()) == {0, 1, 2, 3, 4, 5} and (pts["state"] == 3).sum() >= 10 and summ["n_in_view"] > 200, (k, summ)
+        assert summ["n_candidates"] >= 20 and found[4][3] > 0 and (which != "fuse" or found[4][4] > 20), (k, summ, found[4])
+        if not shared and (k < 2 or which == "sim3_search"):
+            assert summ["n_add"] > 20 and summ["n_replace"] > 15, (k, summ)
+        view, s = FC.camera_view(k, which, CC.FRAME_CAMERAS[k]), FC.camera_scenes()
+        p = binding.fuse_params(extent_w=G.W, extent_h=G.H, **FC.CAMERA_SETS[which])
+        twin = binding.fuse_points_host(view, p, PC.scale(), s[0 if shared else k]["points"], FC.camera_skip(k, shared))
+        assert twin.tobytes() == pts.tobytes(), (which, k)  # the host twin
+    assert FC.camera_reference(0, which, shared)[4]["n_duplicate"] > 5
+
+
+@pytest.mark.parametrize("mixup", list(CC.FRAME_MIXUPS))
+@pytest.mark.parametrize("which,shared", FORMS, ids=FORM_IDS)
+def test_camera_mixups_change_the_reference(which, shared, mixup):
+    """seen through the camera a confused kernel would use, every frame whose camera the mix-up changes has other point records;
+    where the frame has matches at all (its own block, or block 0 for frame 0) and the mix-up moves the projection or reaches a
+    test (bf under check_right), other idx, d1 and actions too.  No mix-up is exempt"""
+    cams = list(CC.FRAME_CAMERAS)
+    mixed = CC.FRAME_MIXUPS[mixup](cams)
+    hit = CC.changed(cams, mixed)
+    assert hit, mixup
+    bf_only = mixup == "bf of another frame"
+    for k in hit:
+        right, wrong = FC.camera_reference(k, which, shared), FC.camera_reference(k, which, shared, mixed[k])
+        live = (right[3]["state"] == 0) & (wrong[3]["state"] == 0)
+        fields = ("u_right",) if bf_only else ("u", "v", "u_right")
+        assert live.sum() > 100 and all((right[3][f][live] != wrong[3][f][live]).any() for f in fields), (mixup, k)
+        if bf_only and not FC.CAMERA_SETS[which]["check_right"]:
+            continue  # u_right is computed and stored, no test reads it
+        assert (right[1] != wrong[1]).any(), (mixup, k)
+        if not shared or k == 0:
+            assert (right[0] != wrong[0]).any() and right[2].tobytes() != wrong[2].tobytes(), (mixup, k)

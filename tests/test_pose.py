@@ -4,6 +4,7 @@ starts prefilled with a pattern no result has.  tests/test_pose_ref.py asserts o
 import numpy as np
 import pytest
 
+import camera_cases as CC
 import guided_cases as G
 import pose_cases as C
 import pose_ref as PR
@@ -52,14 +53,14 @@ def _told(fr):
     return fr.get("n_points", len(fr["points"])), fr.get("n_kp", len(fr["kp"]))
 
 
-def _reference(fr, params, status=0):
+def _reference(fr, params, status=0, scale=None):
     """pose_ref on what the device may read of fr: the rows under the counts it is told; the flags of all its slots"""
     n_p, n_k = _told(fr)
     n_p, n_k = min(max(n_p, 0), len(fr["points"])), min(max(n_k, 0), len(fr["kp"]))
     by_row = bool(params.get("idx_by_row", False))
     cut = dict(fr, points=fr["points"][:n_p], kp=fr["kp"][:n_k], idx=fr["idx"][:n_k if by_row else n_p],
                skip=None if fr.get("skip") is None else fr["skip"][:n_p], right=None if fr.get("right") is None else fr["right"][:n_k])
-    res, flags = C.solve_frame(cut, params, status)
+    res, flags = C.solve_frame(cut, params, status, scale=scale)
     full = np.full(len(fr["idx"]), 2, np.uint8)
     full[:len(flags)] = flags
     return res, full
@@ -270,6 +271,101 @@ def test_shared_block_twice_and_permuted(ctx):
     with pytest.raises(Exception) as e:
         _run(ctx, one_block, 3, 300, 300, PR.UPSTREAM, point_src=[0, 1, 0], n_blocks=1)
     assert "point_src[1]" in str(e.value)
+
+
+# ---- odd cameras, per frame ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", list(C.CAMERA_KINDS))
+def test_three_cameras_per_call(ctx, kind):
+    """one call whose frames are seen by camera A, camera B and the square camera (fx != fy, principal points off the centre, three
+    values of bf), monocular, with every third row stereo, and by keypoint row; the stereo call has a fourth frame whose view has
+    bf = 0.  The pairs form and the host form.  tests/test_pose_ref.py shows that a kernel which exchanged fx and fy or cx and cy,
+    or read another frame's view or bf, would give other bytes"""
+    from send_slam_amd import binding
+    frames, p = list(C.camera_frames(kind)), C.camera_params(kind)
+    if kind == "every_third_row_stereo":
+        frames.append(C.no_baseline_frame())
+    assert len({fr["view"].tobytes() for fr in frames}) == len(frames)
+    wants, got, _ = _against_reference(ctx, frames, *_dims(frames), p, kind)
+    for b, (res, flags, _) in enumerate(C.camera_reference(kind)):
+        assert wants[b][0].tobytes() == res.tobytes() and np.array_equal(wants[b][1][:len(flags)], flags) and res["state"] == 0
+    for b, fr in enumerate(frames):
+        flags, res = ctx.pose_opt(fr["view"], fr["start"], fr["points"], fr["kp"], fr["idx"], _params(binding, p), right=fr["right"])
+        _check(f"{kind}, host form, frame {b}", (flags[None], np.array([res])), 0, (wants[b][0], wants[b][1][:len(flags)]))
+    if len(frames) == 4:
+        assert frames[3]["view"]["bf"] == 0 and wants[3][0]["n_stereo"] > 40 and wants[3][0]["state"] == 0
+
+
+@pytest.mark.parametrize("name", ["one_level", "sixteen_levels"])
+def test_other_pyramid_tables(name):
+    """the octave test and the weights read the context's table: one level (every octave but 0 is outside) and SS_MAX_LEVELS"""
+    from send_slam_amd import binding
+    factor, n_levels = PC.PYRAMIDS[name]
+    sc = PC.scale_table(factor, n_levels)
+    fr = C.pyramid_frame(n_levels)
+    octave = fr["kp"]["octave"][fr["idx"][fr["obs_slots"]]]
+    outside = int(((octave < 0) | (octave >= n_levels)).sum())
+    with binding.OrbContext(0, n_features=G.NF, scale_factor=factor, n_levels=n_levels) as c:
+        dev = _upload([fr], *_dims([fr]), False)
+        got = _run(c, dev, 1, *_dims([fr]), PR.UPSTREAM)
+        flags, res = c.pose_opt(fr["view"], fr["start"], fr["points"], fr["kp"], fr["idx"], _params(binding, PR.UPSTREAM))
+    want = _reference(fr, PR.UPSTREAM, scale=sc)
+    _check(name, got, 0, want)
+    _check(name + ", host form", (flags[None], np.array([res])), 0, want)
+    assert outside > 20 and want[0]["n_obs"] == 120 - outside and want[0]["state"] == 0
+
+
+@pytest.mark.parametrize("name", list(C.LIMITS))
+def test_parameter_limits(ctx, name):
+    """n_rounds, iterations and robust_rounds at 8, 32 and 0 / 8, step_eps and lambda at 0, min_obs at and above n_obs, on a frame
+    of 65 observations and the same frame started at the truth"""
+    kw, states = C.LIMITS[name]
+    fr = C.make_frame(**C.LIMIT_FRAME)
+    frames = [fr, dict(fr, start=C.start_of(*fr["truth"]))]
+    wants, _, _ = _against_reference(ctx, frames, *_dims(frames), dict(PR.UPSTREAM, **kw), name)
+    assert wants[0][0]["n_obs"] == 65 and wants[0][0]["state"] in states and wants[1][0]["state"] in states
+    if name == "eight rounds of 32 steps":
+        assert wants[0][0]["steps"].tolist() == [32] * 8 and wants[1][0]["steps"].tolist() == [32] * 8
+    if name == "min_obs above n_obs":
+        assert wants[0][0]["steps"].tolist() == [0] * 8
+
+
+def test_singular_system_with_finite_sums(ctx):
+    """every observation is one map point on the optical axis, lambda = 0: a pivot is not > 0 (tests/test_pose_ref.py), the frame ends
+    in state 2 and carries its start pose; the frame next to it in the call is solved"""
+    fr, p = C.singular_frame(), C.SINGULAR_PARAMS
+    other = C.camera_frames("by_keypoint_row")[0]
+    frames = [fr, dict(other, right=None)]
+    wants, got, _ = _against_reference(ctx, frames, *_dims(frames), p, "singular", right=False)
+    R, t, ok = PR.start_pose(fr["start"])
+    assert ok and got[1][0]["state"] == 2 and got[1][0]["steps"].tolist() == [0] * 8
+    assert got[1][0]["rcw"].tobytes() == np.array(R, np.float64).tobytes() and got[1][0]["tcw"].tobytes() == np.array(t, np.float64).tobytes()
+    assert got[1][0]["rcw"].tolist() != np.eye(3).reshape(9).tolist() and wants[1][0]["state"] == 0
+
+
+def test_point_src_neither_identity_nor_constant(ctx):
+    """point_src [1, 0, 1] over two blocks with different counts (both under their arrays' lengths) and different skip bytes:
+    frames 0 and 2 read block 1's points, count and skip bytes, frame 1 block 0's"""
+    a = C.make_frame(91, 130, n_out=15, n_border=20, n_points=150, n_kp=140, cam=CC.A)
+    b = C.make_frame(92, 120, n_out=12, n_border=20, n_points=128, n_kp=140, cam=CC.B)
+    rng = np.random.Generator(np.random.PCG64(0x5C1))
+    for fr, cut in ((a, 7), (b, 3)):
+        fr["skip"] = np.zeros(len(fr["points"]), np.uint8)
+        fr["skip"][rng.choice(fr["obs_slots"], 9, replace=False)] = rng.integers(1, 256, 9)
+        fr["n_points"] = len(fr["points"]) - cut
+    frames, blocks, src = [a, b, dict(a, start=C.start_of(*a["truth"]))], [b, a], [1, 0, 1]
+    point_rows, rows = _dims(frames)
+    dev, blk = _upload(frames, point_rows, rows, False), _upload(blocks, point_rows, rows, False)
+    dev = dict(dev, points=blk["points"], np=blk["np"], skip=blk["skip"])
+    _sync()
+    got = _run(ctx, dev, 3, point_rows, rows, PR.UPSTREAM, skip=True, point_src=src, n_blocks=2)
+    wants = [_reference(fr, PR.UPSTREAM) for fr in frames]
+    for k, w in enumerate(wants):
+        _check(f"point_src {src}, frame {k}", got, k, w)
+    assert [int(w[0]["state"]) for w in wants] == [0, 0, 0] and wants[0][0]["rcw"].tobytes() != wants[2][0]["rcw"].tobytes()
+    for fr, w in zip(frames, wants):  # the count and the skip bytes of the frame's block both removed observations
+        seen = fr["obs_slots"] < fr["n_points"]
+        assert 0 < w[0]["n_obs"] == int((seen & (fr["skip"][fr["obs_slots"]] == 0)).sum()) < seen.sum() < len(seen)
+    assert wants[0][0]["n_obs"] != wants[1][0]["n_obs"] and a["n_points"] != b["n_points"]
 
 
 BATCH = ["synth_t0", "synth_t1", "flat"]

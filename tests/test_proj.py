@@ -301,6 +301,60 @@ def test_batch_form():
         assert e.value.code == binding.SS_ERR_STATE
 
 
+# ---- odd cameras, per frame ----------------------------------------------------------------------------------------------------------------
+CAMERA_ROWS = (470, 483)  # no multiple of the 64 points of a workgroup
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["own_blocks", "one_shared_block"])
+def test_three_cameras_per_call(ctx, shared):
+    """one call whose frames are seen by camera A, camera B and the square camera (fx != fy, principal points off the centre, three
+    values of bf, check_right on), each on its own block of points and all on block 0 (point_src [0, 0, 0]); the pairs form and the
+    host form.  tests/test_proj_ref.py shows that a kernel which exchanged fx and fy or cx and cy, or read another frame's view or
+    bf, would give other bytes"""
+    from send_slam_amd import binding
+    frames, combo = PC.camera_scenes(), PC.CAMERA_COMBO
+    point_rows, rows = CAMERA_ROWS
+    assert len({f["view"].tobytes() for f in frames}) == 3
+    dev = _upload(frames, point_rows, rows)
+    p = PC.combo_params(binding, combo, extent_w=G.W, extent_h=G.H)
+    got = _run_pairs(ctx, dev, 3, point_rows, rows, p, point_src=[0, 0, 0] if shared else None, n_blocks=1 if shared else None)
+    for k, f in enumerate(frames):
+        want = PC.camera_reference(k, shared)
+        _check(f"cameras, frame {k}", got, k, want)
+        b = frames[0] if shared else f
+        idx, d1, d2, proj, summ = ctx.match_proj(f["view"], b["points"], b["p_desc"], f["t_desc"], f["t_kp"], p, right=f["right"], taken=f["taken"])
+        _check(f"cameras, host form, frame {k}", (idx[None], d1[None], d2[None], proj[None], [summ]), 0, want)
+    assert sum(s["n_unique"] for s in got[4]) > 200
+
+
+@pytest.mark.parametrize("shared", [False, True], ids=["own_blocks", "one_shared_block"])
+def test_batch_form_under_a_camera_per_frame(shared):
+    """ss_match_proj_batch_device on three extracted frames (the train frames of the camera scenes) under three cameras"""
+    from send_slam_amd import binding
+    from test_guided import _extract
+    frames, combo = PC.camera_scenes(), PC.CAMERA_COMBO
+    n, point_rows = 3, 500
+    views = np.concatenate([np.asarray(f["view"]).reshape(1) for f in frames])
+    with binding.OrbContext(0, n_features=G.NF, max_batch=n) as c:
+        _, kcap = _extract(c, [train for _, train in PC.SCENES])
+        pts, pd = np.zeros((n, point_rows), binding.MAP_POINT_DTYPE), np.zeros((n, point_rows, 32), np.uint8)
+        right, taken = np.full((n, kcap), -1, np.float32), np.zeros((n, kcap), np.uint8)
+        for b, f in enumerate(frames):
+            pts[b, :len(f["points"])], pd[b, :len(f["points"])] = f["points"], f["p_desc"]
+            right[b, :len(f["right"])], taken[b, :len(f["taken"])] = f["right"], f["taken"]
+        counts = np.array([len(f["points"]) for f in frames], np.int32)
+        d_pts, d_pd, d_n, d_right, d_taken = (_to_dev(a) for a in (pts, pd, counts, right, taken))
+        out = Outputs(n, point_rows)
+        import torch
+        torch.cuda.synchronize()
+        c.match_proj_batch_device(d_pts.data_ptr(), d_pd.data_ptr(), d_n.data_ptr(), 1 if shared else n, point_rows, views, PC.combo_params(binding, combo),
+                                  *out.ptrs(), point_src=[0, 0, 0] if shared else None, d_train_right=d_right.data_ptr(), d_train_taken=d_taken.data_ptr())
+        c.synchronize()
+        got = out.host()
+    for k in range(n):
+        _check(f"cameras, batch form, frame {k}", got, k, PC.camera_reference(k, shared))
+
+
 def test_full_capacity(ctx):
     """two frames with point_rows = rows_per_frame = SS_GUIDED_MAX_ROWS, one_to_one on, dense coordinates: contested train rows on
     both sides of the 8192-row pass of the conflict table (tests/test_proj_ref.py counts them), 64 px cells"""

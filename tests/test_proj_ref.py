@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import camera_cases as CC
 import guided_cases as G
 import guided_ref as R
 import proj_cases as PC
@@ -346,3 +347,39 @@ def test_far_descriptor_and_count_cases():
     assert full[4]["n_unique"] < full[4]["n_accepted"] and full[4]["n_candidates"] > 100
     assert PC.count_reference(64, 65)[4] != full[4] != PC.count_reference(65, 64)[4]  # the 65th row of either side matters
     assert PC.count_reference(70, 1 << 30)[4] == full[4]
+
+
+# ---- odd cameras: what makes the camera tests of tests/test_proj.py able to fail -----------------------------------------------------------
+@pytest.mark.parametrize("shared", [False, True], ids=["own_blocks", "one_shared_block"])
+def test_camera_scenes_are_live(shared):
+    """the three scenes under cameras A, B and the square one: matches on every frame, every rejection state of step 1, rows outside
+    the image under the off-centre principal points, right-eye rejections under each frame's own bf; at most 500 points a frame"""
+    for k, s in enumerate(PC.camera_scenes()):
+        assert s["view"].tobytes() == PC.camera_view(k, CC.FRAME_CAMERAS[k]).tobytes() and len(s["points"]) <= 500 and len(s["t_kp"]) <= 500
+        idx, d1, d2, proj, summ, cands = PC.camera_reference(k, shared)
+        assert summ["n_unique"] > (50 if not shared or k == 0 else 5) and summ["n_candidates"] > 300, (k, summ)
+        assert (proj["state"] == 2).sum() >= 10 and {1, 2, 3, 4} <= set(proj["state"].tolist()), k
+        b = PC.camera_scenes()[0 if shared else k]
+        blind = P.search(proj, b["p_desc"], s["t_kp"], s["t_desc"], False, None, s["taken"])[4]
+        assert sum(len(c) for c in blind) > summ["n_candidates"], k  # the right-eye test rejected candidates
+        p = PC.combo_params(binding, PC.CAMERA_COMBO, extent_w=G.W, extent_h=G.H)
+        assert binding.proj_points_host(s["view"], p, PC.scale(), b["points"]).tobytes() == proj.tobytes(), k  # the host twin
+    assert len({s["view"][n].tobytes() for s in PC.camera_scenes() for n in ("fx", "fy", "cx", "cy", "bf")}) == 14  # all different but the square camera's fx and fy
+
+
+@pytest.mark.parametrize("mixup", list(CC.FRAME_MIXUPS))
+@pytest.mark.parametrize("shared", [False, True], ids=["own_blocks", "one_shared_block"])
+def test_camera_mixups_change_the_reference(shared, mixup):
+    """seen through the camera a confused kernel would use, every frame whose camera the mix-up changes has other idx, d1, d2 and
+    projection records.  No mix-up is exempt"""
+    cams = list(CC.FRAME_CAMERAS)
+    mixed = CC.FRAME_MIXUPS[mixup](cams)
+    hit = CC.changed(cams, mixed)
+    assert hit, mixup
+    for k in hit:
+        right, wrong = PC.camera_reference(k, shared), PC.camera_reference(k, shared, mixed[k])
+        for j, name in enumerate(("idx", "d1", "d2")):
+            assert (right[j] != wrong[j]).any(), (mixup, k, name)
+        fields = ("u_right",) if mixup == "bf of another frame" else ("u", "v", "u_right")
+        live = (right[3]["state"] == 0) & (wrong[3]["state"] == 0)
+        assert live.sum() > 100 and all((right[3][f][live] != wrong[3][f][live]).any() for f in fields), (mixup, k)

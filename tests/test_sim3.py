@@ -272,6 +272,48 @@ def test_other_pyramid_tables(name):
     assert 3 <= want[0]["n_corr"] < 50 and want[0]["state"] == 0
 
 
+# ---- odd cameras, per pair and per side ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("min_inliers", SC.CAMERA_MIN_INLIERS)
+def test_three_camera_pairs_per_call(ctx, min_inliers):
+    """one call whose pairs are seen by the cameras (P, Q), (Q, P) and (square, P): fx != fy, principal points off the centre, the
+    two sides of a pair different.  The query points carry noise, so the counts depend on the views (tests/test_sim3_ref.py shows
+    that exchanging fx and fy, the sides, or the pairs' views changes the bytes compared here).  The pairs form and the host form"""
+    from send_slam_amd import binding
+    pairs, p = SC.camera_pairs(), SC.camera_params(min_inliers)
+    wants = _pairs_against_reference(ctx, pairs, SC.ROWS, p, f"cameras, min_inliers {min_inliers}", skip=False)
+    for b, w in enumerate(SC.camera_reference(min_inliers)):
+        assert wants[b][0].tobytes() == w[0].tobytes() and w[0]["state"] == 0 and min_inliers < w[0]["n_inliers"] < w[0]["n_corr"] == 60
+    for b, pr in enumerate(pairs):  # the host form is pair 0 of its own call
+        flags, one = ctx.sim3(pr["view1"], pr["q_xyz"], pr["q_kp"], pr["view2"], pr["t_xyz"], pr["t_kp"], pr["idx"], _params(binding, p))
+        _check(f"cameras, host form of pair {b}", (flags[None], np.array([one])), 0, _reference(pr, p, 0))
+
+
+def test_batch_form_under_a_camera_per_frame():
+    """ss_sim3_batch_device with views[b] and views[train_src[b]] different for every frame: frames 1 and 2 train on frame 0, the
+    frames are seen by P, Q and the square camera"""
+    from send_slam_amd import binding
+    from test_guided import _extract
+    kps, xyz, idx, views = SC.camera_batch()
+    n = len(SC.CAMERA_BATCH)
+    with binding.OrbContext(0, n_features=G.NF, max_batch=n) as c:
+        _, kcap = _extract(c, SC.CAMERA_BATCH)
+        assert kcap >= xyz.shape[1]
+        pad = lambda a, fill: np.concatenate([a, np.full((n, kcap - a.shape[1]), fill, a.dtype)], axis=1)  # noqa: E731
+        d_xyz, d_idx = _to_dev(pad(xyz, 0)), _to_dev(pad(idx, -1))
+        _sync()
+        for m in SC.CAMERA_MIN_INLIERS:
+            p = SC.camera_params(m)
+            out = Out(n, kcap)
+            c.sim3_batch_device(d_xyz.data_ptr(), d_idx.data_ptr(), views, _params(binding, p), out.inlier.data_ptr(), out.result.data_ptr(),
+                                train_src=SC.CAMERA_BATCH_SRC)
+            c.synchronize()
+            got = out.host()
+            for b in range(n):
+                w = _reference(SC.batch_pair(b), p, b)
+                _check(f"cameras, batch form, min_inliers {m}, frame {b} against {SC.CAMERA_BATCH_SRC[b]}", got, b, w)
+                assert (w[0]["state"], w[0]["n_corr"]) == ((1, 0) if b == 0 else (0, 60))
+
+
 # ---- the batch form and the one-pair host form -----------------------------------------------------------------------------------------
 BATCH = ["synth_t0", "synth_t1", "flat"]
 BATCH_SRC = [-1, 0, 1]

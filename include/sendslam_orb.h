@@ -44,6 +44,9 @@
  *                              ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>&, th) inside TrackMonocular :594
  *   ss_fuse_* / ss_match_fuse* ORBmatcher::Fuse (LocalMapping::SearchInNeighbors), its Sim3 form (LoopClosing::SearchAndFuse) and
  *                              the Sim3 SearchByProjection of the loop and merge candidate check
+ *   ss_sim3_opt_* /            the rest of ORBmatcher::SearchBySim3 (the skip marks of its two projection searches and their
+ *   ss_sim3_marks_* /          agreement test) and Optimizer::OptimizeSim3 of LoopClosing::DetectCommonRegionsFromBoW, starting from
+ *   ss_sim3_mutual_*           the result ss_sim3_* left in device memory
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
  *   ss_last_error              the cerr diagnostics of the shim (:457-469, :523-551)
  *
@@ -1224,6 +1227,144 @@ int ss_pose_opt_batch_device(ss_ctx *ctx, const void *d_points, const void *d_po
 int ss_pose_opt(ss_ctx *ctx, const ss_proj_view *view, const double *start, const ss_map_point *points, const uint8_t *point_skip,
                 int n_points, const ss_keypoint *kp, const float *right, int n_kp, const int32_t *idx, const ss_pose_opt_params *p,
                 uint8_t *flags, ss_pose_result *result);
+
+/* ---- Sim3 refinement: the rest of ORBmatcher::SearchBySim3 and Optimizer::OptimizeSim3 (g2o EdgeSim3ProjectXYZ and
+ * EdgeInverseSim3ProjectXYZ) as LoopClosing::DetectCommonRegionsFromBoW runs them after the RANSAC, for every loop candidate of a
+ * call at once.  The upstream source is not in the reference tree.  This is the library's own restatement and parity with the real
+ * binary stays unpinned, as for the Sim3 RANSAC.  tests/sim3opt_ref.py is its normative statement; DESIGN.md section 23.  An
+ * addition to ABI 5: nothing existing changes ------------------------------------------------------------------------------------
+ * - All arithmetic below step 1 is double.  Every step is one IEEE operation, left to right as written, with no contraction.  The
+ *   only library function is sqrt.
+ * - Every test is written in its accepting form, so a NaN fails it; the one exception is the rotation's step-size test of step 3.
+ * One pair: the arrays ss_sim3_* takes (keyframe 1 the query with view v1, keyframe 2 the train with view v2, idx[i] the train row
+ * of query row i), and a start: the ss_sim3_result the RANSAC wrote.  A start with state != 0 or status != SS_OK, or a frame the
+ * extraction flagged, gives state 1, no correspondences (flag 2 in every row) and that status (the frame's before the start's).
+ * 1. Correspondences.  The keep rule and the numbering 0 .. N-1 of ss_sim3_* step 1.  X1 = R1.P1 + t1 and X2 = R2.P2 + t2 in
+ *    float32 exactly as that step spells them, then widened.  The observations are the KEYPOINTS (x, y of query row i and of train
+ *    row j, float32 widened, taken as undistorted), not the projections the RANSAC compares.  w1 = 1.0 / (s1*s1) with
+ *    s1 = (double)scale[octave_i], w2 likewise from octave_j.
+ * 2. Start.  s = sqrt((a0*a0 + a1*a1) + a2*a2) over row 0 of the start's sr12 widened, as ss_fuse_view_sim3 reads a scale; with
+ *    fix_scale s is exactly 1.0 and is never updated.  R is the Gram-Schmidt rotation of the pose rule's step 2 on sr12's rows,
+ *    t = t12.  An entry that is not finite, or s not > 0: state 2 with R = I, t = 0, s = 1.  State 1: N < min_corr.
+ * 3. A step.  Every active correspondence (round 0: every one) contributes up to two edges, e12 first.
+ *    e12: Y = s.(R.X2) + t, each component s*((r0*x + r1*y) + r2*z) + t.  It takes part iff Y.z > 0.  With (x, y, z) = Y,
+ *    iz = 1.0 / z, iz2 = iz*iz: rx = u1 - (fx1*x*iz + cx1), ry = v1 - (fy1*y*iz + cy1); the rows by (omega, upsilon, sigma) are the
+ *    pose rule's J0 and J1 under K1 with a seventh entry: J0 = {x*y*iz2*fx, -(1.0 + x*x*iz2)*fx, y*iz*fx, -iz*fx, 0, x*iz2*fx, 0},
+ *    J1 = {(1.0 + y*y*iz2)*fy, -x*y*iz2*fy, -x*iz*fy, 0, -iz*fy, y*iz2*fy, 0}.  Y moves by (-[Y]x, I, Y) and a scale about the
+ *    camera centre moves no projection, so the sigma entries are the structural 0.  Here a structural 0 is the factor +0.0 and its
+ *    products ARE added.  Weight w1.
+ *    e21: M[i][j] = (1.0 / s) * R[j][i]; d = X1 - t; Z[i] = (M[i][0]*d0 + M[i][1]*d1) + M[i][2]*d2.  It takes part iff Z.z > 0.  With
+ *    (x, y, z) = Z: rx = u2 - (fx2*x*iz + cx2), ry = v2 - (fy2*y*iz + cy2).  X1 = (a, b, g) moves by E = ([X1]x, -I, -X1), then by M:
+ *    D[i] = {M[i][1]*g - M[i][2]*b, M[i][2]*a - M[i][0]*g, M[i][0]*b - M[i][1]*a, -M[i][0], -M[i][1], -M[i][2],
+ *    -((M[i][0]*a + M[i][1]*b) + M[i][2]*g)}.  With px = fx2*iz, pxz = fx2*x*iz2, py = fy2*iz, pyz = fy2*y*iz2:
+ *    J0[c] = pxz*D[2][c] - px*D[0][c], J1[c] = pyz*D[2][c] - py*D[1][c].  Weight w2.
+ *    Per edge: e2 = w*(rx*rx + ry*ry); with delta = sqrt(chi2) the weight is wq = w*delta / sqrt(e2) in the robust round when
+ *    e2 > delta*delta, else w.  The term of H_ab (a <= b) is (wq*J0[a])*J0[b] + (wq*J1[a])*J1[b], that of g_a
+ *    (wq*J0[a])*rx + (wq*J1[a])*ry.  The 35 sums (28 of H's upper triangle row by row, then 7 of g): slot s of 256 adds, from +0.0,
+ *    for its active correspondences k = s, s + 256, ... in ascending order first the e12 term, then the e21 term (an edge that
+ *    takes no part is skipped); each group of 64 slots folds by halving and the four results combine as (r0 + r1) + (r2 + r3), the
+ *    pose rule's tree.  Solve over n = 7 (with fix_scale the leading 6 x 6 and its 6 of g): H_aa += lambda*(1.0 + H_aa), b = -g,
+ *    Cholesky and both substitutions as in the pose rule; a pivot that is not > 0: state 2, the model stays.  Retraction of
+ *    delta = (omega, upsilon, sigma): dR from the pose rule's series A and B; |omega|^2 > pi*pi (a NaN passes), or not
+ *    |sigma| <= 1.0: state 4, the model stays.  ds = sum sigma^k / k!, k = 0 .. 19, Horner from the last term over the pose rule's
+ *    table of 1 / n! (the first term left out, 1 / 20!, is below 2^-60); with fix_scale ds is 1.0 and s is not touched.
+ *    R <- dR.R (each entry (a*b + c*d) + e*f), t[i] <- ds*((dR[i][0]*t0 + dR[i][1]*t1) + dR[i][2]*t2) + upsilon[i], s <- ds*s.  A
+ *    round ends after its number of steps, or after a step with every |delta_a| < step_eps, a < n.
+ * 4. Rounds.  Round 0: iterations0 robust steps on every correspondence.  Then every correspondence is classified: chi2_12 =
+ *    w1*(ex*ex + ey*ey) with the projection formed with / z (ex = u1 - (fx1*x/z + cx1)), or 1e30 when Y.z is not > 0; chi2_21
+ *    likewise.  It is removed iff not (chi2_12 <= chi2 && chi2_21 <= chi2).  n_removed counts these.  Fewer than min_inliers left:
+ *    state 3.  Round 1 is not robust and runs on what is left, iterations_more steps if n_removed > 0, else iterations_same.  The
+ *    same test then runs on what round 1 ran on (a removed correspondence stays removed, as upstream has deleted its edges) and
+ *    gives n_inliers and the flags.  cost is the sum of the inliers' (chi2_12 + chi2_21) in the tree order above.
+ * 5. Result.  s.R, t, s and the inverse are formed and rounded to float32 once as ss_sim3_* step 3b forms them (s21 = 1.0 / s).
+ *    If R, t, s or one of these 25 floats is not finite, the result is the start of step 2 with state 2, so no NaN bits reach an
+ *    output.  The embedded ss_sim3_result carries the floats and state 0 only when the state is 0; otherwise its floats are all
+ *    0.0f and its state is the optimisation's.  ss_sim3_to_view, ss_sim3_to_view21 and a later ss_sim3_opt_* call take it unchanged.
+ * Flags, one byte per QUERY row < rows, each written exactly once per call: 0 inlier, 1 removed (upstream's vpMatches1[i] = NULL),
+ * 2 no correspondence.  They are those of the last classification that ran, and 0 for every correspondence before any.
+ * Deviations from upstream: the left increment is applied by a first-order retraction (g2o: the closed-form Sim3 exponential with
+ * sin, cos and exp, which are not the same bits on host and device; a stationary point does not depend on the retraction); analytic
+ * Jacobians (g2o differentiates these two edges numerically); lambda and the early end of a round are the pose rule's (g2o's
+ * Levenberg-Marquardt adapts lambda); an edge with depth not > 0 takes no part in a step and fails the classification; the order of
+ * every sum is fixed; a step above pi or |sigma| above 1 ends the pair; chi2 is a parameter (th2 = 10 there) and so are the step
+ * counts; keypoints are taken as undistorted; upstream's bAllPoints / covisibility bookkeeping stays with the caller. */
+typedef struct {          /* 64 bytes */
+    double chi2;          /* finite and > 0; upstream: th2 = 10 */
+    double lambda;        /* finite and >= 0; the pose rule: 1e-6 */
+    double step_eps;      /* finite and >= 0; 0 runs every step */
+    int32_t iterations0;  /* 1 .. 32; upstream: 5 */
+    int32_t iterations_more; /* 1 .. 32, round 1 after a removal; upstream: 10 */
+    int32_t iterations_same; /* 1 .. 32, round 1 otherwise; upstream: 5 */
+    int32_t min_corr;     /* >= 3; upstream: 10 */
+    int32_t min_inliers;  /* >= 0; upstream: 10 */
+    int32_t fix_scale;    /* non-zero: s = 1.0 and six unknowns (stereo and RGB-D) */
+    int32_t reserved[4];  /* must be 0 */
+} ss_sim3_opt_params;
+typedef struct {          /* 272 bytes, one per pair */
+    double r12[9], t12[3], s12; /* X1 = s12 * r12.X2 + t12 */
+    double cost;
+    int32_t state;        /* 0 ok, 1 no usable start or too few correspondences, 2 not positive definite or not finite, 3 too few inliers, 4 step too large */
+    int32_t status;       /* SS_OK, the frame_error that voided the pair, or the start's status */
+    int32_t n_corr, n_removed, n_inliers;
+    int32_t steps[2];     /* steps taken in round r */
+    int32_t reserved;     /* 0 */
+    ss_sim3_result model; /* step 5; iteration -1, best_inliers 0, n_inliers as above in state 0 */
+} ss_sim3_opt_result;
+typedef struct {          /* 8 bytes, one per pair */
+    int32_t n_prior;      /* rows that keep their prior match */
+    int32_t n_new;        /* rows that gained a mutual match */
+} ss_sim3_mutual_summary;
+/* The whole rule on the host from the text the kernels compile (csrc/ss_sim3opt_steps.h), one pair; needs no device.  scale:
+ * n_levels entries, 1 <= n_levels <= SS_MAX_LEVELS; the skip arrays may be NULL; idx and flags have n_query entries.  p is checked as
+ * the device calls check it (SS_ERR_INVALID_ARG). */
+int ss_sim3_opt_host(const ss_proj_view *view1, const ss_proj_view *view2, const float *scale, int n_levels, const ss_map_point *query_xyz,
+                     const ss_keypoint *query_kp, const uint8_t *query_skip, int n_query, const ss_map_point *train_xyz,
+                     const ss_keypoint *train_kp, const uint8_t *train_skip, int n_train, const int32_t *idx, const ss_sim3_result *start,
+                     const ss_sim3_opt_params *p, uint8_t *flags, ss_sim3_opt_result *result);
+/* n_pairs pairs on caller-supplied device arrays: every array as for ss_sim3_pairs_device, and d_start, a DEVICE array [n_pairs] of
+ * ss_sim3_result (ss_sim3_pairs_device's d_result feeds it unchanged).  Outputs: d_flags uint8 [n_pairs][rows], d_result [n_pairs]
+ * ss_sim3_opt_result.  SS_ERR_INVALID_ARG: rows above SS_GUIDED_MAX_ROWS, a parameter out of its range, a reserved field that is
+ * not 0, a NULL buffer.  Asynchronous on the context's stream. */
+int ss_sim3_opt_pairs_device(ss_ctx *ctx, const void *d_query_xyz, const void *d_query_kp, const void *d_query_skip, const void *d_n_query,
+                             const void *d_train_xyz, const void *d_train_kp, const void *d_train_skip, const void *d_n_train,
+                             const void *d_idx, int n_pairs, int rows, const ss_proj_view *views1, const ss_proj_view *views2,
+                             const void *d_start, const ss_sim3_opt_params *p, void *d_flags, void *d_result);
+/* The same on the frames of the last ss_extract_batch_device batch, with train_src, d_xyz, d_skip and views as for
+ * ss_sim3_batch_device; d_start [n_frames]. */
+int ss_sim3_opt_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_xyz, const void *d_skip, const void *d_idx,
+                             const ss_proj_view *views, const void *d_start, const ss_sim3_opt_params *p, void *d_flags, void *d_result);
+/* One pair with host pointers in and out (copy in, the pairs form, copy out), synchronous.  n_query, n_train <=
+ * SS_GUIDED_MAX_ROWS; the skip arrays may be NULL; flags: n_query bytes. */
+int ss_sim3_opt(ss_ctx *ctx, const ss_proj_view *view1, const ss_map_point *query_xyz, const ss_keypoint *query_kp, const uint8_t *query_skip,
+                int n_query, const ss_proj_view *view2, const ss_map_point *train_xyz, const ss_keypoint *train_kp, const uint8_t *train_skip,
+                int n_train, const int32_t *idx, const ss_sim3_result *start, const ss_sim3_opt_params *p, uint8_t *flags,
+                ss_sim3_opt_result *result);
+/* The bookkeeping of SearchBySim3 around its two searches, which are ss_match_fuse_* called twice.  A match idx[i] is VALID iff
+ * i < n_query and 0 <= idx[i] < n_train.
+ * Marks: d_skip1_out[i] = (query skip byte of row i != 0) || idx[i] is valid; d_skip2_out[j] = (train skip byte of row j != 0) ||
+ * some valid idx[i] == j; a skip array that is NULL reads as 0.  Both are uint8 [n_pairs][rows], every row < rows is written, 0 or 1:
+ * the point_skip of the search of one keyframe's points in the other and its train_taken in the other direction.
+ * Mutual: d_idx12 [n_pairs][rows] is the train row the search found for query row i, d_idx21 [n_pairs][rows] the query row found for
+ * train row j.  d_idx_out[i] = idx[i] if that is valid; else j = idx12[i] iff i < n_query, 0 <= j < n_train, idx21[j] == i and no valid
+ * idx[i'] == j; else -1.  Every row < rows is written.  d_summary [n_pairs] ss_sim3_mutual_summary.
+ * SS_ERR_INVALID_ARG: rows above SS_GUIDED_MAX_ROWS, a NULL buffer (the skip arrays may be NULL).  Asynchronous. */
+int ss_sim3_marks_pairs_device(ss_ctx *ctx, const void *d_idx, const void *d_query_skip, const void *d_train_skip, const void *d_n_query,
+                               const void *d_n_train, int n_pairs, int rows, void *d_skip1_out, void *d_skip2_out);
+int ss_sim3_mutual_pairs_device(ss_ctx *ctx, const void *d_idx, const void *d_idx12, const void *d_idx21, const void *d_n_query,
+                                const void *d_n_train, int n_pairs, int rows, void *d_idx_out, void *d_summary);
+/* The same on the frames of the last batch: pair b is frame b against frame train_src[b], d_skip (or NULL) [n_frames][kp_capacity]
+ * holds every frame's skip bytes, d_skip2_out[b] and d_idx21[b] go by the rows of pair b's train frame.  A flagged frame on either
+ * side leaves the pair no valid match. */
+int ss_sim3_marks_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_idx, const void *d_skip, void *d_skip1_out,
+                               void *d_skip2_out);
+int ss_sim3_mutual_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_idx, const void *d_idx12, const void *d_idx21,
+                                void *d_idx_out, void *d_summary);
+/* ss_sim3_to_view in the other direction, for the search of keyframe 1's points in keyframe 2: S21.T1w, the Sim3 that takes the
+ * world of keyframe 1's pose (rcw1 / tcw1) into the camera of keyframe 2.  In double from the result's floats: srcw = sr21 . rcw1,
+ * t[k] = ((sr21[3k]*tcw1[0] + sr21[3k+1]*tcw1[1]) + sr21[3k+2]*tcw1[2]) + t21[k]; then exactly ss_fuse_view_sim3(cam, srcw, t, bf,
+ * out).  SS_ERR_INVALID_ARG: a NULL pointer, result->state != 0. */
+int ss_sim3_to_view21(const ss_camera *cam, const ss_sim3_result *result, const double rcw1[9], const double tcw1[3], float bf,
+                      double *srcw_out, double *t_out, ss_proj_view *out);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

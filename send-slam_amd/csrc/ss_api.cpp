@@ -451,6 +451,9 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_pose_ws);
     dev_free(c->d_pose_io);
     staged_free(c->pose_tab);
+    dev_free(c->d_sim3opt_ws);
+    dev_free(c->d_sim3opt_io);
+    staged_free(c->sim3opt_tab);
     for (auto &rm : c->rect_maps) dev_free(rm.d);
     dev_free(c->d_rect);
     for (cam_track &ct : c->cams) ct.free_rows();

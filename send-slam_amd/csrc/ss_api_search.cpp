@@ -1,6 +1,6 @@
 /*
  * ss_api_search.cpp -- the search family of the C ABI (include/sendslam_orb.h): guided matching, map-point projection search,
- * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation, the Sim3 RANSAC, the pose-only optimisation.  Each has a pairs form on caller arrays, a batch form on the
+ * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation, the Sim3 RANSAC, the pose-only optimisation, the Sim3 refinement.  Each has a pairs form on caller arrays, a batch form on the
  * frames of the last extraction and, for some, a host form.  The context and the helpers they share: ss_ctx.h.
  */
 #include <algorithm>
@@ -19,6 +19,7 @@
 #include "ss_pose_steps.h"
 #include "ss_proj_steps.h"
 #include "ss_sim3_steps.h"
+#include "ss_sim3opt_steps.h"
 
 extern "C" {
 
@@ -1798,6 +1799,290 @@ int ss_pose_opt(ss_ctx *c, const ss_proj_view *view, const double *start, const 
         return rc;
     }
     return io_fetch(c, io, PIECES);
+}
+
+/* ---- Sim3 refinement (csrc/ss_sim3opt.hip, csrc/ss_sim3opt_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *sim3opt_params_error(const ss_sim3_opt_params *p)
+{
+    if (!p) return "sim3 refinement: params is NULL";
+    if (!(p->chi2 > 0.0) || !std::isfinite(p->chi2)) return "sim3 refinement: chi2 must be finite and > 0";
+    if (!(p->lambda >= 0.0) || !std::isfinite(p->lambda)) return "sim3 refinement: lambda must be finite and >= 0";
+    if (!(p->step_eps >= 0.0) || !std::isfinite(p->step_eps)) return "sim3 refinement: step_eps must be finite and >= 0";
+    if (p->iterations0 < 1 || p->iterations0 > 32) return "sim3 refinement: iterations0 must be 1 .. 32";
+    if (p->iterations_more < 1 || p->iterations_more > 32) return "sim3 refinement: iterations_more must be 1 .. 32";
+    if (p->iterations_same < 1 || p->iterations_same > 32) return "sim3 refinement: iterations_same must be 1 .. 32";
+    if (p->min_corr < 3) return "sim3 refinement: min_corr must be >= 3";
+    if (p->min_inliers < 0) return "sim3 refinement: min_inliers must be >= 0";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0 || p->reserved[3] != 0) return "sim3 refinement: the reserved fields must be 0";
+    return nullptr;
+}
+
+int ss_sim3_opt_host(const ss_proj_view *view1, const ss_proj_view *view2, const float *scale, int n_levels, const ss_map_point *query_xyz,
+                     const ss_keypoint *query_kp, const uint8_t *query_skip, int n_query, const ss_map_point *train_xyz,
+                     const ss_keypoint *train_kp, const uint8_t *train_skip, int n_train, const int32_t *idx, const ss_sim3_result *start,
+                     const ss_sim3_opt_params *p, uint8_t *flags, ss_sim3_opt_result *result)
+{
+    if (sim3opt_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!view1 || !view2 || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n_query < 0 || n_train < 0 || !start || !result) return SS_ERR_INVALID_ARG;
+    if ((n_query > 0 && (!query_xyz || !query_kp || !idx || !flags)) || (n_train > 0 && (!train_xyz || !train_kp))) return SS_ERR_INVALID_ARG;
+    /* step 1 */
+    std::vector<ss_sim3opt_corr> corr;
+    std::vector<int> row_of;
+    const bool usable = ss_sim3opt_start_usable(*start);
+    for (int i = 0; i < n_query; i++) {
+        flags[i] = 2;
+        const int j = idx[i];
+        if (!usable || !(j >= 0 && j < n_train)) continue;
+        const int o1 = query_kp[i].octave, o2 = train_kp[j].octave;
+        if (!(o1 >= 0 && o1 < n_levels && o2 >= 0 && o2 < n_levels)) continue;
+        if ((query_skip && query_skip[i] != 0) || (train_skip && train_skip[j] != 0)) continue;
+        float x1[3], x2[3];
+        ss_sim3_transform(view1->rcw, view1->tcw, query_xyz[i].x, query_xyz[i].y, query_xyz[i].z, x1);
+        ss_sim3_transform(view2->rcw, view2->tcw, train_xyz[j].x, train_xyz[j].y, train_xyz[j].z, x2);
+        corr.push_back(ss_sim3opt_corr_of(x1, x2, query_kp[i].x, query_kp[i].y, train_kp[j].x, train_kp[j].y, scale[o1], scale[o2]));
+        row_of.push_back(i);
+    }
+    const int n = (int)corr.size();
+    std::vector<uint8_t> active((size_t)n + 1);
+    std::vector<double> slot((size_t)(SS_SIM3OPT_SUMS + 1) * SS_POSE_SLOTS);
+    ss_sim3opt_pair_host(corr.data(), n, ss_sim3opt_cams_of(*view1, *view2, p->chi2), *start, start->status, *p, active.data(), slot.data(), result);
+    for (int k = 0; k < n; k++) flags[row_of[(size_t)k]] = active[(size_t)k] ? 0 : 1;
+    return SS_OK;
+}
+
+int ss_sim3_to_view21(const ss_camera *cam, const ss_sim3_result *result, const double rcw1[9], const double tcw1[3], float bf, double *srcw_out,
+                      double *t_out, ss_proj_view *out)
+{
+    if (!cam || !result || !rcw1 || !tcw1 || !out || result->state != 0) return SS_ERR_INVALID_ARG;
+    double m[9], t[3];
+    for (int i = 0; i < 3; i++) {
+        const double a0 = result->sr21[3 * i], a1 = result->sr21[3 * i + 1], a2 = result->sr21[3 * i + 2];
+        for (int j = 0; j < 3; j++) m[3 * i + j] = (a0 * rcw1[j] + a1 * rcw1[3 + j]) + a2 * rcw1[6 + j];
+        t[i] = ((a0 * tcw1[0] + a1 * tcw1[1]) + a2 * tcw1[2]) + (double)result->t21[i];
+    }
+    if (srcw_out) memcpy(srcw_out, m, sizeof(m));
+    if (t_out) memcpy(t_out, t, sizeof(t));
+    return ss_fuse_view_sim3(cam, m, t, bf, out);
+}
+
+/* The checks the device forms share, the workspace, the views (views1 then views2, each of n_frames, through `fill`), then the two
+ * launches of a call whose device operands and outputs are filled in */
+extern "C++" template <class Fill> static int sim3opt_run(ss_ctx *c, ssk_sim3opt_call &g, const ss_sim3_opt_params *p, Fill fill_views)
+{
+    if (g.n_frames > 65535) return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: more than 65535 pairs in one call");
+    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
+        return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: the context's n_levels / scale_factor give no pyramid table");
+    g.p = *p;
+    g.n_levels = c->params.n_levels;
+    ss_scale_table(c->params.scale_factor, g.n_levels, g.scale);
+    const size_t nr = (size_t)g.n_frames * g.rows;
+    int rc = carve_from(c, c->d_sim3opt_ws, [&](carve &w) {
+        g.planes = w.take<float>(12 * nr * sizeof(float));
+        g.row_of = w.take<int32_t>(nr * sizeof(int32_t));
+        g.n_corr = w.take<int32_t>((size_t)g.n_frames * sizeof(int32_t));
+    });
+    if (rc != SS_OK) return rc;
+    const size_t vb = (size_t)g.n_frames * sizeof(ss_proj_view);
+    rc = staged_upload(c, c->sim3opt_tab, 2 * vb, [&](uint8_t *h) { fill_views((ss_proj_view *)h, (ss_proj_view *)(h + vb)); });
+    if (rc != SS_OK) return rc;
+    g.views1 = c->sim3opt_tab.as<ss_proj_view>(), g.views2 = c->sim3opt_tab.as<ss_proj_view>(vb);
+    const int64_t np = g.n_frames;
+    {
+        /* per query row: its match and its flag or row number; a correspondence reads two map points, two keypoints and up to two
+         * flags and writes its twelve floats; per pair the start is read and N written */
+        stage_timer t(c, "sim3opt_gather", (int64_t)nr * (4 + 4 + 2 * (int64_t)sizeof(ss_map_point) + 2 * (int64_t)sizeof(ss_keypoint) + (g.q_skip ? 1 : 0) +
+                                                          (g.t_skip ? 1 : 0) + 48) + np * (int64_t)(sizeof(ss_sim3_result) + 4));
+        ssk_sim3opt_gather(c->stream, g);
+    }
+    {
+        /* every step and both classifications read the correspondences' planes once (an upper bound: a round may end early) */
+        const int64_t passes = (int64_t)p->iterations0 + std::max(p->iterations_more, p->iterations_same) + 2;
+        stage_timer t(c, "sim3opt_solve", (int64_t)nr * (48 * passes + 4 + 1) + np * (int64_t)(2 * sizeof(ss_proj_view) + sizeof(ss_sim3_result) + sizeof(ss_sim3_opt_result)));
+        ssk_sim3opt_solve(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_sim3_opt_pairs_device(ss_ctx *c, const void *d_query_xyz, const void *d_query_kp, const void *d_query_skip, const void *d_n_query,
+                             const void *d_train_xyz, const void *d_train_kp, const void *d_train_skip, const void *d_n_train, const void *d_idx,
+                             int n_pairs, int rows, const ss_proj_view *views1, const ss_proj_view *views2, const void *d_start,
+                             const ss_sim3_opt_params *p, void *d_flags, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = sim3opt_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    const int rc = pairs_shape(c, "sim3 refinement", "pair", n_pairs, rows);
+    if (rc != SS_OK) return rc;
+    if (n_pairs == 0) return SS_OK;
+    if (!d_query_xyz || !d_query_kp || !d_n_query || !d_train_xyz || !d_train_kp || !d_n_train || !d_idx || !views1 || !views2 || !d_start || !d_flags ||
+        !d_result)
+        return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: NULL buffer");
+    ssk_sim3opt_call g;
+    g.n_frames = n_pairs, g.rows = rows;
+    g.q_xyz = (const ss_map_point *)d_query_xyz, g.t_xyz = (const ss_map_point *)d_train_xyz;
+    g.q_kp = (const ss_keypoint *)d_query_kp, g.t_kp = (const ss_keypoint *)d_train_kp;
+    g.q_skip = (const uint8_t *)d_query_skip, g.t_skip = (const uint8_t *)d_train_skip;
+    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
+    g.idx = (const int32_t *)d_idx, g.start = (const ss_sim3_result *)d_start;
+    g.flags = (uint8_t *)d_flags, g.result = (ss_sim3_opt_result *)d_result;
+    const size_t vb = (size_t)n_pairs * sizeof(ss_proj_view);
+    return sim3opt_run(c, g, p, [&](ss_proj_view *v1, ss_proj_view *v2) {
+        memcpy(v1, views1, vb);
+        memcpy(v2, views2, vb);
+    });
+}
+
+int ss_sim3_opt_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_xyz, const void *d_skip, const void *d_idx, const ss_proj_view *views,
+                             const void *d_start, const ss_sim3_opt_params *p, void *d_flags, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_sim3_opt_batch_device")) return SS_ERR_STATE;
+    if (const char *msg = sim3opt_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (!d_xyz || !d_idx || !views || !d_start || !d_flags || !d_result) return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: NULL buffer");
+    batch_operands o;
+    const int rc = batch_operands_of(c, "sim3 refinement", train_src, o);
+    if (rc != SS_OK) return rc;
+    ssk_sim3opt_call g;
+    g.n_frames = o.n_frames, g.rows = o.kcap;
+    g.q_xyz = g.t_xyz = (const ss_map_point *)d_xyz;
+    g.q_kp = g.t_kp = o.kps;
+    g.q_skip = g.t_skip = (const uint8_t *)d_skip;
+    g.nq = g.nt = o.n_kp;
+    g.src = o.src, g.frame_error = o.frame_error;
+    g.idx = (const int32_t *)d_idx, g.start = (const ss_sim3_result *)d_start;
+    g.flags = (uint8_t *)d_flags, g.result = (ss_sim3_opt_result *)d_result;
+    const int n = o.n_frames;
+    return sim3opt_run(c, g, p, [&](ss_proj_view *v1, ss_proj_view *v2) {
+        for (int b = 0; b < n; b++) {
+            const int t = train_src ? train_src[b] : b - 1; /* checked by batch_operands_of; -1: the pair has no train and reads no view */
+            v1[b] = views[b];
+            v2[b] = views[t < 0 ? b : t];
+        }
+    });
+}
+
+int ss_sim3_opt(ss_ctx *c, const ss_proj_view *view1, const ss_map_point *query_xyz, const ss_keypoint *query_kp, const uint8_t *query_skip, int n_query,
+                const ss_proj_view *view2, const ss_map_point *train_xyz, const ss_keypoint *train_kp, const uint8_t *train_skip, int n_train,
+                const int32_t *idx, const ss_sim3_result *start, const ss_sim3_opt_params *p, uint8_t *flags, ss_sim3_opt_result *result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_query < 0 || n_train < 0 || n_query > SS_GUIDED_MAX_ROWS || n_train > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: n_query and n_train must be 0 .. SS_GUIDED_MAX_ROWS");
+    if (!view1 || !view2 || !start || !result || (n_query > 0 && (!query_xyz || !query_kp || !idx || !flags)) || (n_train > 0 && (!train_xyz || !train_kp)))
+        return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: NULL buffer");
+    /* one pair of `rows` rows on both sides; `counts` is on this stack: no return before the stream has read it */
+    const size_t rows = (size_t)std::max(std::max(n_query, n_train), 1), nq = (size_t)n_query, nt = (size_t)n_train;
+    const size_t kp = sizeof(ss_keypoint), mp = sizeof(ss_map_point);
+    const int32_t counts[2] = {n_query, n_train};
+    enum { QX, QK, QS, TX, TK, TS, IDX, N, ST, FL, RES, PIECES };
+    io_piece io[PIECES] = {{query_xyz, nullptr, rows * mp, nq * mp}, {query_kp, nullptr, rows * kp, nq * kp}, {query_skip, nullptr, rows, nq},
+                           {train_xyz, nullptr, rows * mp, nt * mp}, {train_kp, nullptr, rows * kp, nt * kp}, {train_skip, nullptr, rows, nt},
+                           {idx, nullptr, rows * 4, nq * 4}, {counts, nullptr, sizeof(counts), sizeof(counts)},
+                           {start, nullptr, sizeof(ss_sim3_result), sizeof(ss_sim3_result)}, {nullptr, flags, rows, nq},
+                           {nullptr, result, sizeof(ss_sim3_opt_result), sizeof(ss_sim3_opt_result)}};
+    int rc = io_send(c, c->d_sim3opt_io, io, PIECES);
+    if (rc == SS_OK)
+        rc = ss_sim3_opt_pairs_device(c, io[QX].d, io[QK].d, query_skip ? io[QS].d : nullptr, io[N].d, io[TX].d, io[TK].d, train_skip ? io[TS].d : nullptr,
+                                      io[N].d + 4, io[IDX].d, 1, (int)rows, view1, view2, io[ST].d, p, io[FL].d, io[RES].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
+}
+
+/* the two launches of SearchBySim3's bookkeeping: the call's sides are filled in */
+static int sim3_marks_run(ss_ctx *c, ssk_sim3_marks_call &g, bool mutual)
+{
+    if (g.n_frames > 65535) return fail(c, SS_ERR_INVALID_ARG, "sim3 marks: more than 65535 pairs in one call");
+    const int64_t nr = (int64_t)g.n_frames * g.rows;
+    if (!mutual) {
+        /* per row: its match and up to two skip bytes read, two bytes written; a valid match writes one more */
+        stage_timer t(c, "sim3opt_marks", nr * (4 + (g.q_skip ? 1 : 0) + (g.t_skip ? 1 : 0) + 2 + 4 + 1) + (int64_t)g.n_frames * 8);
+        ssk_sim3_marks(c->stream, g);
+    } else {
+        const int rc = carve_from(c, c->d_sim3opt_ws, [&](carve &w) { g.taken = w.take<uint8_t>((size_t)nr); });
+        if (rc != SS_OK) return rc;
+        /* per row: the taken byte written, the prior match read twice and marked, then up to two search results and a taken byte
+         * read and the match written */
+        stage_timer t(c, "sim3opt_mutual", nr * (1 + 4 + 1 + 4 + 4 + 4 + 1 + 4) + (int64_t)g.n_frames * (8 + (int64_t)sizeof(ss_sim3_mutual_summary)));
+        ssk_sim3_mutual(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_sim3_marks_pairs_device(ss_ctx *c, const void *d_idx, const void *d_query_skip, const void *d_train_skip, const void *d_n_query,
+                               const void *d_n_train, int n_pairs, int rows, void *d_skip1_out, void *d_skip2_out)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const int rc = pairs_shape(c, "sim3 marks", "pair", n_pairs, rows);
+    if (rc != SS_OK) return rc;
+    if (n_pairs == 0) return SS_OK;
+    if (!d_idx || !d_n_query || !d_n_train || !d_skip1_out || !d_skip2_out) return fail(c, SS_ERR_INVALID_ARG, "sim3 marks: NULL buffer");
+    ssk_sim3_marks_call g;
+    g.n_frames = n_pairs, g.rows = rows;
+    g.idx = (const int32_t *)d_idx, g.q_skip = (const uint8_t *)d_query_skip, g.t_skip = (const uint8_t *)d_train_skip;
+    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
+    g.skip1 = (uint8_t *)d_skip1_out, g.skip2 = (uint8_t *)d_skip2_out;
+    return sim3_marks_run(c, g, false);
+}
+
+int ss_sim3_mutual_pairs_device(ss_ctx *c, const void *d_idx, const void *d_idx12, const void *d_idx21, const void *d_n_query, const void *d_n_train,
+                                int n_pairs, int rows, void *d_idx_out, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const int rc = pairs_shape(c, "sim3 mutual", "pair", n_pairs, rows);
+    if (rc != SS_OK) return rc;
+    if (n_pairs == 0) return SS_OK;
+    if (!d_idx || !d_idx12 || !d_idx21 || !d_n_query || !d_n_train || !d_idx_out || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "sim3 mutual: NULL buffer");
+    ssk_sim3_marks_call g;
+    g.n_frames = n_pairs, g.rows = rows;
+    g.idx = (const int32_t *)d_idx, g.idx12 = (const int32_t *)d_idx12, g.idx21 = (const int32_t *)d_idx21;
+    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
+    g.idx_out = (int32_t *)d_idx_out, g.summary = (ss_sim3_mutual_summary *)d_summary;
+    return sim3_marks_run(c, g, true);
+}
+
+int ss_sim3_marks_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_idx, const void *d_skip, void *d_skip1_out, void *d_skip2_out)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_sim3_marks_batch_device")) return SS_ERR_STATE;
+    if (!d_idx || !d_skip1_out || !d_skip2_out) return fail(c, SS_ERR_INVALID_ARG, "sim3 marks: NULL buffer");
+    batch_operands o;
+    const int rc = batch_operands_of(c, "sim3 marks", train_src, o);
+    if (rc != SS_OK) return rc;
+    ssk_sim3_marks_call g;
+    g.n_frames = o.n_frames, g.rows = o.kcap;
+    g.idx = (const int32_t *)d_idx, g.q_skip = g.t_skip = (const uint8_t *)d_skip;
+    g.nq = g.nt = o.n_kp, g.src = o.src, g.frame_error = o.frame_error;
+    g.skip1 = (uint8_t *)d_skip1_out, g.skip2 = (uint8_t *)d_skip2_out;
+    return sim3_marks_run(c, g, false);
+}
+
+int ss_sim3_mutual_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_idx, const void *d_idx12, const void *d_idx21, void *d_idx_out,
+                                void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_sim3_mutual_batch_device")) return SS_ERR_STATE;
+    if (!d_idx || !d_idx12 || !d_idx21 || !d_idx_out || !d_summary) return fail(c, SS_ERR_INVALID_ARG, "sim3 mutual: NULL buffer");
+    batch_operands o;
+    const int rc = batch_operands_of(c, "sim3 mutual", train_src, o);
+    if (rc != SS_OK) return rc;
+    ssk_sim3_marks_call g;
+    g.n_frames = o.n_frames, g.rows = o.kcap;
+    g.idx = (const int32_t *)d_idx, g.idx12 = (const int32_t *)d_idx12, g.idx21 = (const int32_t *)d_idx21;
+    g.nq = g.nt = o.n_kp, g.src = o.src, g.frame_error = o.frame_error;
+    g.idx_out = (int32_t *)d_idx_out, g.summary = (ss_sim3_mutual_summary *)d_summary;
+    return sim3_marks_run(c, g, true);
 }
 
 } /* extern "C" */

@@ -152,6 +152,10 @@ struct ss_ctx {
      * copies, the tables of a call (views, then block numbers, then start poses) */
     dev_buf<uint8_t> d_pose_ws, d_pose_io;
     staged_table pose_tab;
+    /* Sim3 refinement: the workspace of a call (the correspondences' planes and rows, their counts; the taken bytes of the mutual
+     * check), the host form's device copies, the views of a call (views1, then views2) */
+    dev_buf<uint8_t> d_sim3opt_ws, d_sim3opt_io;
+    staged_table sim3opt_tab;
     /* rectification: map map_id in its fixed-point form (one allocation each: the xy array, then ab; d == NULL: unset) and the
      * 16-byte aligned buffer ss_extract_stereo_raw remaps both eyes into */
     struct rect_map {

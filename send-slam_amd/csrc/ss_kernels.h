@@ -407,6 +407,51 @@ struct ssk_pose_call {
 };
 void ssk_pose_gather(hipStream_t s, const ssk_pose_call &g);
 void ssk_pose_solve(hipStream_t s, const ssk_pose_call &g);
+/* ss_sim3opt.hip: Sim3 refinement (DESIGN.md "Sim3 refinement").  Pair b as for ssk_sim3_call, and start[b], the model it starts
+ * from.  gather (one workgroup per pair, SSK_SIM3OPT_CHUNK rows at a time in ascending order) numbers the correspondences, writes
+ * their twelve floats as a structure of arrays (planes: 12 of [n_frames][rows]: X1, X2, both keypoints, both scales), the query row
+ * of every correspondence and N, and flag 2 into every other row; solve (one workgroup per pair) runs both rounds and writes the
+ * correspondences' flags and the result */
+#define SSK_SIM3OPT_CHUNK 1024
+struct ssk_sim3opt_call {
+    int n_frames = 0, rows = 0;
+    const ss_map_point *q_xyz = nullptr, *t_xyz = nullptr;
+    const ss_keypoint *q_kp = nullptr, *t_kp = nullptr;
+    const uint8_t *q_skip = nullptr, *t_skip = nullptr; /* [n_frames][rows], or NULL */
+    const int32_t *nq = nullptr, *nt = nullptr;
+    const int32_t *src = nullptr;
+    const int32_t *frame_error = nullptr;
+    const int32_t *idx = nullptr;
+    const ss_proj_view *views1 = nullptr, *views2 = nullptr; /* device [n_frames] each */
+    const ss_sim3_result *start = nullptr;                   /* device [n_frames] */
+    ss_sim3_opt_params p = {};
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    /* workspace */
+    float *planes = nullptr;
+    int32_t *row_of = nullptr; /* [n_frames][rows] */
+    int32_t *n_corr = nullptr; /* [n_frames] */
+    uint8_t *flags = nullptr;  /* [n_frames][rows] */
+    ss_sim3_opt_result *result = nullptr;
+};
+void ssk_sim3opt_gather(hipStream_t s, const ssk_sim3opt_call &g);
+void ssk_sim3opt_solve(hipStream_t s, const ssk_sim3opt_call &g);
+/* The bookkeeping of SearchBySim3 (the rule: include/sendslam_orb.h).  One workgroup per pair: a base pass over the rows, a barrier,
+ * a scatter pass in which every store to one address writes the same value.  marks writes skip1 and skip2; mutual marks the train
+ * rows that carry a prior match in taken (workspace, [n_frames][rows]) and writes idx_out and the summary */
+struct ssk_sim3_marks_call {
+    int n_frames = 0, rows = 0;
+    const int32_t *idx = nullptr, *idx12 = nullptr, *idx21 = nullptr;
+    const uint8_t *q_skip = nullptr, *t_skip = nullptr;
+    const int32_t *nq = nullptr, *nt = nullptr;
+    const int32_t *src = nullptr;
+    const int32_t *frame_error = nullptr;
+    uint8_t *skip1 = nullptr, *skip2 = nullptr, *taken = nullptr;
+    int32_t *idx_out = nullptr;
+    ss_sim3_mutual_summary *summary = nullptr;
+};
+void ssk_sim3_marks(hipStream_t s, const ssk_sim3_marks_call &g);
+void ssk_sim3_mutual(hipStream_t s, const ssk_sim3_marks_call &g);
 /* ss_rectify.hip: bilinear remap through fixed-point maps (DESIGN.md "Rectification").  A map on the device is two arrays of
  * height rows, ssk_rectify_pitch(width) entries apart: xy = (uint16)ix | (uint16)iy << 16 and ab = a | b << 5; the entries past the
  * width are "outside" records.  ssk_rectify_fixed is the host conversion of a float map pair into them.  ssk_rectify remaps the

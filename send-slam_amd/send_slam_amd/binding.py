@@ -48,7 +48,9 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_triangulate_batch_device", "ss_fuse_view_sim3", "ss_fuse_points_host", "ss_fuse_check_host",
            "ss_match_fuse_pairs_device", "ss_match_fuse_batch_device", "ss_match_fuse", "ss_sim3_model_host", "ss_sim3_check_host",
            "ss_sim3_to_view", "ss_sim3_pairs_device", "ss_sim3_batch_device", "ss_sim3", "ss_pose_opt_host", "ss_pose_opt_pairs_device",
-           "ss_pose_opt_batch_device", "ss_pose_opt"]
+           "ss_pose_opt_batch_device", "ss_pose_opt", "ss_sim3_opt_host", "ss_sim3_opt_pairs_device", "ss_sim3_opt_batch_device",
+           "ss_sim3_opt", "ss_sim3_marks_pairs_device", "ss_sim3_mutual_pairs_device", "ss_sim3_marks_batch_device",
+           "ss_sim3_mutual_batch_device", "ss_sim3_to_view21"]
 
 
 class OrbParams(C.Structure):
@@ -368,6 +370,73 @@ def sim3_to_view(camera: Camera, result, rcw2, tcw2, bf: float = 0.0):
                                 C.byref(v))
     if rc != SS_OK:
         raise OrbError(rc, "ss_sim3_to_view refused its arguments")
+    return v, srcw.reshape(3, 3), tt
+
+
+class Sim3OptParams(C.Structure):
+    _fields_ = [("chi2", C.c_double), ("lambda_", C.c_double), ("step_eps", C.c_double), ("iterations0", C.c_int32),
+                ("iterations_more", C.c_int32), ("iterations_same", C.c_int32), ("min_corr", C.c_int32), ("min_inliers", C.c_int32),
+                ("fix_scale", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+# ss_sim3_opt_result: one per pair; ss_sim3_mutual_summary likewise
+SIM3_OPT_RESULT_DTYPE = np.dtype([("r12", "<f8", (9,)), ("t12", "<f8", (3,)), ("s12", "<f8"), ("cost", "<f8")] +
+                                 [(n, "<i4") for n in ("state", "status", "n_corr", "n_removed", "n_inliers")] +
+                                 [("steps", "<i4", (2,)), ("reserved", "<i4"), ("model", SIM3_RESULT_DTYPE)])
+SIM3_MUTUAL_DTYPE = np.dtype([("n_prior", "<i4"), ("n_new", "<i4")])
+
+
+def sim3_opt_params(chi2: float = 10.0, lambda_: float = 1e-6, step_eps: float = 1e-10, iterations0: int = 5, iterations_more: int = 10,
+                    iterations_same: int = 5, min_corr: int = 10, min_inliers: int = 10, fix_scale: bool = False,
+                    reserved=(0, 0, 0, 0)) -> Sim3OptParams:
+    """upstream's Optimizer::OptimizeSim3 as LoopClosing calls it: th2 10, 5 robust steps, then 10 or 5; lambda and step_eps are the pose
+    rule's"""
+    return Sim3OptParams(chi2=chi2, lambda_=lambda_, step_eps=step_eps, iterations0=iterations0, iterations_more=iterations_more,
+                         iterations_same=iterations_same, min_corr=min_corr, min_inliers=min_inliers, fix_scale=int(fix_scale),
+                         reserved=(C.c_int32 * 4)(*reserved))
+
+
+def _sim3_pair_arrays(view1, q_xyz, q_kp, view2, t_xyz, t_kp, idx, start, q_skip, t_skip):
+    """the host arrays of one pair, checked -> (v1, v2, qx, qk, tx, tk, ix, st, q_skip, t_skip, nq, nt)"""
+    v1, v2 = _views_array(view1), _views_array(view2)
+    qx, tx = np.ascontiguousarray(q_xyz, MAP_POINT_DTYPE), np.ascontiguousarray(t_xyz, MAP_POINT_DTYPE)
+    qk, tk = np.ascontiguousarray(q_kp, KP_DTYPE), np.ascontiguousarray(t_kp, KP_DTYPE)
+    ix = np.ascontiguousarray(idx, np.int32)
+    st = np.ascontiguousarray(np.asarray(start, SIM3_RESULT_DTYPE).reshape(1))
+    nq, nt = len(qx), len(tx)
+    q_skip = None if q_skip is None else np.ascontiguousarray(q_skip, np.uint8)
+    t_skip = None if t_skip is None else np.ascontiguousarray(t_skip, np.uint8)
+    if len(v1) != 1 or len(v2) != 1 or len(qk) != nq or len(ix) != nq or len(tk) != nt or (q_skip is not None and len(q_skip) != nq) or \
+            (t_skip is not None and len(t_skip) != nt):
+        raise ValueError("views, map points, keypoints, flags and matches differ in length")
+    return v1, v2, qx, qk, tx, tk, ix, st, q_skip, t_skip, nq, nt
+
+
+def sim3_opt_host(view1, q_xyz, q_kp, view2, t_xyz, t_kp, idx, start, scale, params: Sim3OptParams, q_skip=None, t_skip=None):
+    """ss_sim3_opt_host: the whole rule on the host for one pair -> (uint8 flag per query row: 0 inlier, 1 removed, 2 no correspondence;
+    one SIM3_OPT_RESULT_DTYPE record); needs no device"""
+    v1, v2, qx, qk, tx, tk, ix, st, q_skip, t_skip, nq, nt = _sim3_pair_arrays(view1, q_xyz, q_kp, view2, t_xyz, t_kp, idx, start, q_skip, t_skip)
+    sc = np.ascontiguousarray(scale, np.float32)
+    flags, res = np.empty(nq, np.uint8), np.zeros(1, SIM3_OPT_RESULT_DTYPE)
+    ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+    rc = load().ss_sim3_opt_host(v1.ctypes.data, v2.ctypes.data, sc.ctypes.data, len(sc), ptr(qx, nq), ptr(qk, nq), ptr(q_skip, nq), nq, ptr(tx, nt),
+                                 ptr(tk, nt), ptr(t_skip, nt), nt, ptr(ix, nq), st.ctypes.data, C.byref(params), ptr(flags, nq), res.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_sim3_opt_host refused its arguments")
+    return flags, res[0]
+
+
+def sim3_to_view21(camera: Camera, result, rcw1, tcw1, bf: float = 0.0):
+    """ss_sim3_to_view21: S21.T1w from a state-0 result and keyframe 1's pose -> (ProjView of keyframe 2's camera under it, srcw 3 x 3, t 3);
+    needs no device"""
+    m = np.ascontiguousarray(np.asarray(result, SIM3_RESULT_DTYPE).reshape(1))
+    r, t = np.ascontiguousarray(rcw1, np.float64).reshape(9), np.ascontiguousarray(tcw1, np.float64).reshape(3)
+    srcw, tt = np.zeros(9, np.float64), np.zeros(3, np.float64)
+    v = ProjView()
+    rc = load().ss_sim3_to_view21(C.byref(camera), m.ctypes.data, r.ctypes.data, t.ctypes.data, C.c_float(bf), srcw.ctypes.data, tt.ctypes.data,
+                                  C.byref(v))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_sim3_to_view21 refused its arguments")
     return v, srcw.reshape(3, 3), tt
 
 
@@ -708,6 +777,18 @@ def load():
                                             [C.c_void_p] * 2
     lib.ss_pose_opt.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PoseOptParams),
                                                                   C.c_void_p, C.c_void_p]
+    lib.ss_sim3_opt_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + \
+                                    [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(Sim3OptParams), C.c_void_p, C.c_void_p]
+    lib.ss_sim3_opt_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                               C.POINTER(Sim3OptParams)] + [C.c_void_p] * 2
+    lib.ss_sim3_opt_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.POINTER(Sim3OptParams)] + [C.c_void_p] * 2
+    lib.ss_sim3_opt.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p,
+                                                                                                 C.POINTER(Sim3OptParams), C.c_void_p, C.c_void_p]
+    lib.ss_sim3_marks_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 2
+    lib.ss_sim3_mutual_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 2
+    lib.ss_sim3_marks_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+    lib.ss_sim3_mutual_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+    lib.ss_sim3_to_view21.argtypes = [C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(ProjView)]
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -1416,6 +1497,65 @@ class OrbContext:
         self._check(self._lib.ss_pose_opt(self._h, v.ctypes.data, st.ctypes.data, ptr(pts, n_p), ptr(skip, n_p), n_p, ptr(k, n_k), ptr(right, n_k),
                                           n_k, ptr(ix, ns), C.byref(params), ptr(flags, ns), res.ctypes.data))
         return flags, res[0]
+
+    # ---- Sim3 refinement: SearchBySim3's bookkeeping and OptimizeSim3 per loop candidate (the rule: include/sendslam_orb.h) ----
+    def sim3_opt_pairs_device(self, d_query_xyz: int, d_query_kp: int, d_n_query: int, d_train_xyz: int, d_train_kp: int, d_n_train: int,
+                              d_idx: int, n_pairs: int, rows: int, views1, views2, d_start: int, params: Sim3OptParams, d_flags: int,
+                              d_result: int, d_query_skip: int = 0, d_train_skip: int = 0):
+        """n_pairs pairs on device arrays as for sim3_pairs_device; d_start SIM3_RESULT_DTYPE [n_pairs] on the device (sim3_pairs_device's
+        d_result); d_flags uint8 [n_pairs][rows] by query row, d_result SIM3_OPT_RESULT_DTYPE [n_pairs]; asynchronous."""
+        v1, v2 = _views_array(views1), _views_array(views2)
+        if len(v1) != n_pairs or len(v2) != n_pairs:
+            raise ValueError("one view of either keyframe per pair")
+        self._check(self._lib.ss_sim3_opt_pairs_device(self._h, C.c_void_p(d_query_xyz), C.c_void_p(d_query_kp), C.c_void_p(d_query_skip),
+                                                       C.c_void_p(d_n_query), C.c_void_p(d_train_xyz), C.c_void_p(d_train_kp),
+                                                       C.c_void_p(d_train_skip), C.c_void_p(d_n_train), C.c_void_p(d_idx), n_pairs, rows,
+                                                       v1.ctypes.data if n_pairs else None, v2.ctypes.data if n_pairs else None,
+                                                       C.c_void_p(d_start), C.byref(params), C.c_void_p(d_flags), C.c_void_p(d_result)))
+
+    def sim3_opt_batch_device(self, d_xyz: int, d_idx: int, views, d_start: int, params: Sim3OptParams, d_flags: int, d_result: int,
+                              train_src=None, d_skip: int = 0):
+        """the same on the frames of the last batch, frame b against train_src[b] (None: b - 1); asynchronous."""
+        v = _views_array(views)
+        src = None if train_src is None else np.ascontiguousarray(train_src, np.int32)
+        self._check(self._lib.ss_sim3_opt_batch_device(self._h, None if src is None else src.ctypes.data, C.c_void_p(d_xyz), C.c_void_p(d_skip),
+                                                       C.c_void_p(d_idx), v.ctypes.data, C.c_void_p(d_start), C.byref(params),
+                                                       C.c_void_p(d_flags), C.c_void_p(d_result)))
+
+    def sim3_opt(self, view1, q_xyz, q_kp, view2, t_xyz, t_kp, idx, start, params: Sim3OptParams, q_skip=None, t_skip=None):
+        """One pair, host arrays in and out -> (uint8 flag per query row, SIM3_OPT_RESULT_DTYPE record)."""
+        v1, v2, qx, qk, tx, tk, ix, st, q_skip, t_skip, nq, nt = _sim3_pair_arrays(view1, q_xyz, q_kp, view2, t_xyz, t_kp, idx, start, q_skip, t_skip)
+        flags, res = np.empty(nq, np.uint8), np.zeros(1, SIM3_OPT_RESULT_DTYPE)
+        ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+        self._check(self._lib.ss_sim3_opt(self._h, v1.ctypes.data, ptr(qx, nq), ptr(qk, nq), ptr(q_skip, nq), nq, v2.ctypes.data, ptr(tx, nt),
+                                          ptr(tk, nt), ptr(t_skip, nt), nt, ptr(ix, nq), st.ctypes.data, C.byref(params), ptr(flags, nq),
+                                          res.ctypes.data))
+        return flags, res[0]
+
+    def sim3_marks_pairs_device(self, d_idx: int, d_n_query: int, d_n_train: int, n_pairs: int, rows: int, d_skip1_out: int, d_skip2_out: int,
+                                d_query_skip: int = 0, d_train_skip: int = 0):
+        """the skip bytes of SearchBySim3's two searches, uint8 [n_pairs][rows] each; asynchronous."""
+        self._check(self._lib.ss_sim3_marks_pairs_device(self._h, C.c_void_p(d_idx), C.c_void_p(d_query_skip), C.c_void_p(d_train_skip),
+                                                         C.c_void_p(d_n_query), C.c_void_p(d_n_train), n_pairs, rows, C.c_void_p(d_skip1_out),
+                                                         C.c_void_p(d_skip2_out)))
+
+    def sim3_mutual_pairs_device(self, d_idx: int, d_idx12: int, d_idx21: int, d_n_query: int, d_n_train: int, n_pairs: int, rows: int,
+                                 d_idx_out: int, d_summary: int):
+        """the agreement test of the two searches: d_idx_out int32 [n_pairs][rows], d_summary SIM3_MUTUAL_DTYPE [n_pairs]; asynchronous."""
+        self._check(self._lib.ss_sim3_mutual_pairs_device(self._h, C.c_void_p(d_idx), C.c_void_p(d_idx12), C.c_void_p(d_idx21), C.c_void_p(d_n_query),
+                                                          C.c_void_p(d_n_train), n_pairs, rows, C.c_void_p(d_idx_out), C.c_void_p(d_summary)))
+
+    def sim3_marks_batch_device(self, d_idx: int, d_skip1_out: int, d_skip2_out: int, train_src=None, d_skip: int = 0):
+        """sim3_marks_pairs_device on the frames of the last batch; asynchronous."""
+        src = None if train_src is None else np.ascontiguousarray(train_src, np.int32)
+        self._check(self._lib.ss_sim3_marks_batch_device(self._h, None if src is None else src.ctypes.data, C.c_void_p(d_idx), C.c_void_p(d_skip),
+                                                         C.c_void_p(d_skip1_out), C.c_void_p(d_skip2_out)))
+
+    def sim3_mutual_batch_device(self, d_idx: int, d_idx12: int, d_idx21: int, d_idx_out: int, d_summary: int, train_src=None):
+        """sim3_mutual_pairs_device on the frames of the last batch; asynchronous."""
+        src = None if train_src is None else np.ascontiguousarray(train_src, np.int32)
+        self._check(self._lib.ss_sim3_mutual_batch_device(self._h, None if src is None else src.ctypes.data, C.c_void_p(d_idx), C.c_void_p(d_idx12),
+                                                          C.c_void_p(d_idx21), C.c_void_p(d_idx_out), C.c_void_p(d_summary)))
 
     def wait_stream(self, hip_stream: int):
         """Orders this context's stream after everything enqueued so far on another stream of the device."""

@@ -2,7 +2,9 @@
 series in exact fractions, the host twin ss_sim3_opt_host against the restatement bit for bit, both edges' Jacobians against central
 differences through the retraction, every threshold from both sides, the liveness of the shared cases, the result against an
 independent optimiser that uses g2o's closed-form Sim3 exponential and numerical Jacobians, the bookkeeping of SearchBySim3, the
-inverse view, every refusal, and the steps under the address and undefined-behaviour sanitizers.  None needs a GPU."""
+inverse view, every refusal, and the steps under the address and undefined-behaviour sanitizers; and that the scenes of
+tests/test_sim3opt.py under odd cameras, other pyramid tables, the parameters' limits, a singular system and skip bytes per frame
+do what their names say: every confusion of camera_cases changes the bytes the GPU tests compare.  None needs a GPU."""
 import ctypes as C
 import math
 import os
@@ -12,6 +14,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import camera_cases as CC
 import fuse_ref
 import pose_ref as PR
 import proj_cases as PC
@@ -20,21 +23,22 @@ import sim3_ref as S
 import sim3opt_cases as OC
 import sim3opt_ref as O
 from send_slam_amd import binding
+from sim3opt_cases import FROZEN, frozen_pair
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f64 = np.float64
 
 
-def host(pr, params, start=None):
+def host(pr, params, start=None, scale=None):
     p = binding.sim3_opt_params(**params)
     return binding.sim3_opt_host(pr["view1"], pr["q_xyz"], pr["q_kp"], pr["view2"], pr["t_xyz"], pr["t_kp"], pr["idx"],
-                                 pr["start"] if start is None else start, PC.scale(), p, pr["q_skip"], pr["t_skip"])
+                                 pr["start"] if start is None else start, PC.scale() if scale is None else scale, p, pr["q_skip"], pr["t_skip"])
 
 
-def same(pr, params, start=None, ref=None):
+def same(pr, params, start=None, ref=None, scale=None):
     """the host twin equals the restatement in every byte -> the restatement's (result, flags)"""
-    res, flags = ref if ref is not None else OC.solve_pair(pr, params, start=start)
-    f2, r2 = host(pr, params, start)
+    res, flags = ref if ref is not None else OC.solve_pair(pr, params, start=start, scale=scale)
+    f2, r2 = host(pr, params, start, scale)
     assert flags.tobytes() == f2.tobytes()
     for name in res.dtype.names:
         assert np.asarray(res[name]).tobytes() == np.asarray(r2[name]).tobytes(), (name, res[name], r2[name])
@@ -145,24 +149,7 @@ def test_jacobians_against_central_differences_through_the_retraction(fix):
 
 
 # ---- thresholds -------------------------------------------------------------------------------------------------------------------------
-FROZEN = dict(O.UPSTREAM, lambda_=1e300, step_eps=0.0, min_corr=3, min_inliers=0)  # no step moves the model
-
-
-def frozen_pair(edge: int):
-    """12 exact correspondences, one with a keypoint two pixels off in one keyframe only -> (pair, that query row, its chi-square)"""
-    pr = dict(OC.make_pair(70, 12, 0, 16, 16, noise_px=0.0))
-    pr["start"] = OC.model_record(*OC.true_model())  # the scene's own Sim3 rounded to float32: every other chi-square is tiny
-    row = int(pr["rows"][4])
-    kp = pr["q_kp" if edge == 0 else "t_kp"].copy()
-    kp["x"][row if edge == 0 else pr["idx"][row]] += np.float32(2.0)
-    pr["q_kp" if edge == 0 else "t_kp"] = kp
-    c = O.correspondences(pr["view1"], pr["q_xyz"], pr["q_kp"], None, pr["view2"], pr["t_xyz"], pr["t_kp"], None, pr["idx"], PC.scale())
-    R, t, s, _ = O.start(pr["start"], False)
-    both = O.chi2(c, O.cameras(pr["view1"], pr["view2"], 10.0), R, t, s)
-    n = int(np.nonzero(c["rows"] == row)[0][0])
-    return pr, row, both, n
-
-
+# sim3opt_cases.frozen_pair: 12 exact correspondences, one keypoint two pixels off, under FROZEN no step moves the model
 @pytest.mark.parametrize("edge", [0, 1], ids=["e12", "e21"])
 def test_chi_square_threshold_from_both_sides(edge):
     pr, row, both, n = frozen_pair(edge)
@@ -351,19 +338,215 @@ def test_marks_and_mutual_loops_against_array_forms(rows):
 
 
 # ---- the inverse view -----------------------------------------------------------------------------------------------------------------------
-def test_inverse_view_is_the_fuse_view_of_the_double_product():
+def _views_of_the_double_products(c):
+    """ss_sim3_to_view21 and ss_sim3_to_view under the camera c (fx, fy, cx, cy, bf) against fuse_ref.view_sim3 of the double products"""
     res = OC.reference(0)[0]["model"]
-    cam = binding.Camera(fx=SC.F, fy=SC.F, cx=SC.CX, cy=SC.CY, width=SC.W, height=SC.H)
+    cam = binding.Camera(fx=c[0], fy=c[1], cx=c[2], cy=c[3], width=SC.W, height=SC.H)
     rcw1, tcw1 = np.asarray(SC.POSE1[0], f64), np.asarray(SC.POSE1[1], f64)
     view, srcw, t = binding.sim3_to_view21(cam, res, rcw1, tcw1)
     m, tt = O.to_s21w(res, rcw1, tcw1)
     assert srcw.tobytes() == m.tobytes() and t.tobytes() == tt.tobytes()
     assert bytes(view) == bytes(binding.fuse_view_sim3(cam, m, tt))
-    assert bytes(view) == fuse_ref.view_sim3(SC.F, SC.F, SC.CX, SC.CY, SC.W, SC.H, m, tt, 0.0).tobytes()
+    assert bytes(view) == fuse_ref.view_sim3(c[0], c[1], c[2], c[3], SC.W, SC.H, m, tt, 0.0).tobytes()
+    rcw2, tcw2 = np.asarray(SC.POSE2[0], f64), np.asarray(SC.POSE2[1], f64)
+    view12, srcw, t = binding.sim3_to_view(cam, res, rcw2, tcw2)
+    m, tt = S.to_scw(res, rcw2, tcw2)
+    assert srcw.tobytes() == m.tobytes() and t.tobytes() == tt.tobytes()
+    assert bytes(view12) == fuse_ref.view_sim3(c[0], c[1], c[2], c[3], SC.W, SC.H, m, tt, 0.0).tobytes()
     bad = res.copy()
     bad["state"] = 2
     with pytest.raises(binding.OrbError):
         binding.sim3_to_view21(cam, bad, rcw1, tcw1)
+    return view, view12
+
+
+def test_inverse_view_is_the_fuse_view_of_the_double_product():
+    _views_of_the_double_products(SC.CAM)
+
+
+@pytest.mark.parametrize("name", ["P", "Q"])
+def test_views_under_odd_cameras(name):
+    """fx != fy and cx, cy off the centre: a view built with two intrinsics exchanged has other bytes than the square camera shows"""
+    c = getattr(CC, name)
+    views = _views_of_the_double_products(c)
+    for wrong in (CC.swap_f(c), CC.swap_c(c)):
+        cam = binding.Camera(fx=wrong[0], fy=wrong[1], cx=wrong[2], cy=wrong[3], width=SC.W, height=SC.H)
+        res = OC.reference(0)[0]["model"]
+        assert bytes(binding.sim3_to_view21(cam, res, SC.POSE1[0], SC.POSE1[1])[0]) != bytes(views[0])
+        assert bytes(binding.sim3_to_view(cam, res, SC.POSE2[0], SC.POSE2[1])[0]) != bytes(views[1])
+
+
+# ---- odd cameras ----------------------------------------------------------------------------------------------------------------------------
+def _differ(a, b):
+    """(the result bytes differ, the flag bytes differ) of two (result, flags)"""
+    return a[0].tobytes() != b[0].tobytes(), a[1].tobytes() != b[1].tobytes()
+
+
+def test_camera_pairs_are_live():
+    """every pair of the call ends in state 0, loses some correspondences but not all, and steps in both rounds"""
+    for b, pr in enumerate(OC.camera_pairs()):
+        res, flags = same(pr, O.UPSTREAM, ref=OC.camera_reference()[b])
+        print(b, res["state"], res["n_corr"], res["n_removed"], res["steps"])
+        assert res["state"] == 0 and res["n_corr"] == 60 and 0 < res["n_removed"] < res["n_corr"] and res["steps"][0] >= 1 and res["steps"][1] >= 1
+        assert (flags[pr["outlier_rows"]] == 1).all()
+    assert [tuple(CC.intrinsics(c) for c in pair) for pair in CC.SIM3_PAIR_CAMERAS][2][0] == (SC.F, SC.F, SC.CX, SC.CY)  # the square camera is one side of one pair
+
+
+# the confusions one edge or one table of the refinement could make on top of camera_cases.PAIR_MIXUPS
+EDGE_MIXUPS = {
+    "cx and cy exchanged on side 1": lambda pairs: [(CC.swap_c(a), b) for a, b in pairs],
+    "cx and cy exchanged on side 2": lambda pairs: [(a, CC.swap_c(b)) for a, b in pairs],
+    "side 1 of every pair is pair 0's": lambda pairs: [(pairs[0][0], b) for a, b in pairs],
+    "side 2 of every pair is pair 0's": lambda pairs: [(a, pairs[0][1]) for a, b in pairs],
+}
+PAIR_MIXUPS = dict(CC.PAIR_MIXUPS, **EDGE_MIXUPS)
+
+
+@pytest.mark.parametrize("mixup", list(PAIR_MIXUPS))
+def test_camera_mixups_change_the_reference_of_the_pairs_form(mixup):
+    """the keypoints stay, the views are the ones a wrong kernel would use: the result bytes and the flag bytes change for exactly the
+    pairs whose cameras the mix-up changes.  No mix-up is exempt: both residuals read fx, fy, cx and cy of their side"""
+    cams = list(CC.SIM3_PAIR_CAMERAS)
+    mixed = PAIR_MIXUPS[mixup](cams)
+    hit = CC.changed(cams, mixed, fields=(0, 1, 2, 3))
+    assert hit, mixup
+    for b, pr in enumerate(OC.camera_pairs()):
+        wrong = same(SC.with_cameras(pr, *mixed[b]), O.UPSTREAM)
+        assert _differ(wrong, OC.camera_reference()[b]) == ((True, True) if b in hit else (False, False)), (mixup, b, wrong[0]["state"])
+
+
+@pytest.mark.parametrize("mixup", list(CC.FRAME_MIXUPS))
+def test_camera_mixups_change_the_reference_of_the_batch_form(mixup):
+    """the batch form: frame b's view is side 1 of pair b, frame train_src[b]'s its side 2; every mix-up changes the result bytes of
+    every pair one of whose two views it changes, and bf, which no step reads, changes nothing"""
+    cams = list(CC.SIM3_FRAME_CAMERAS)
+    mixed = CC.FRAME_MIXUPS[mixup](cams)
+    hit = CC.changed(cams, mixed, fields=(0, 1, 2, 3))
+    assert bool(hit) != (mixup == "bf of another frame")
+    wrong_views = SC.frame_views(mixed)
+    for b, t in enumerate(SC.CAMERA_BATCH_SRC):
+        right = same(OC.camera_batch_pair(b), OC.BATCH_PARAMS)
+        wrong = same(OC.camera_batch_pair(b, wrong_views), OC.BATCH_PARAMS)
+        if t < 0:
+            assert right[0]["state"] == 1 and (right[1] == 2).all()
+            continue
+        assert OC.camera_batch_starts()[b]["state"] == 0 and right[0]["state"] == 0 and right[0]["n_corr"] == 60 and min(right[0]["steps"]) >= 1
+        assert _differ(wrong, right)[0] == (b in hit or t in hit), (mixup, b)
+        if not hit:
+            assert _differ(wrong, right) == (False, False)
+
+
+def test_batch_form_train_view_is_that_of_the_trains_frame():
+    """side 2 of pair b is views[train_src[b]]: with views[b] there, as a table filled by frame number would have it, or with the two
+    frames' views exchanged, the result bytes differ"""
+    vs = SC.camera_batch()[3]
+    for b, t in enumerate(SC.CAMERA_BATCH_SRC):
+        if t < 0:
+            continue
+        right = OC.solve_pair(OC.camera_batch_pair(b), OC.BATCH_PARAMS)
+        for v1, v2 in ((vs[b], vs[b]), (vs[t], vs[b]), (vs[t], vs[t])):
+            wrong = same(dict(OC.camera_batch_pair(b), view1=v1, view2=v2), OC.BATCH_PARAMS)
+            assert wrong[0]["n_corr"] == right[0]["n_corr"] and _differ(wrong, right)[0], b
+
+
+def test_batch_form_skip_bytes_are_those_of_the_trains_frame():
+    """one skip array serves both sides: the query side reads frame b's bytes, the train side frame train_src[b]'s.  Under
+    camera_batch_skip() the train side read at frame b keeps other correspondences, in the refinement and in the marks"""
+    skip = OC.camera_batch_skip()
+    kps, xyz, idx, _ = SC.camera_batch()
+    assert skip.shape == idx.shape and not (skip[0].astype(bool) & (skip[1] | skip[2]).astype(bool)).any()
+    for b, t in enumerate(SC.CAMERA_BATCH_SRC):
+        right = same(OC.camera_batch_pair(b, skip=skip), OC.BATCH_PARAMS)
+        if t < 0:
+            assert right[0]["state"] == 1 and (right[1] == 2).all()
+            continue
+        plain = same(OC.camera_batch_pair(b), OC.BATCH_PARAMS)
+        wrong = same(OC.camera_batch_pair(b, skip=skip, train_skip_of=b), OC.BATCH_PARAMS)
+        rows = np.flatnonzero(idx[b] >= 0)
+        assert skip[b][rows].any() and skip[t][idx[b][rows]].any()  # bytes on correspondences of both sides
+        assert right[0]["state"] == 0 and 20 < right[0]["n_corr"] < plain[0]["n_corr"] == 60
+        assert right[0]["n_corr"] != wrong[0]["n_corr"] and _differ(wrong, right) == (True, True), b
+        nq, nt = len(kps[b]), len(kps[t])
+        m_right, m_wrong = O.marks(idx[b], skip[b], skip[t], nq, nt), O.marks(idx[b], skip[b], skip[b], nq, nt)
+        assert m_right[0].tobytes() == m_wrong[0].tobytes() and m_right[1].tobytes() != m_wrong[1].tobytes(), b
+
+
+# ---- other pyramid tables -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(OC.PYRAMID_OCTAVES))
+def test_pyramid_pairs_are_live(name):
+    """more than 20 correspondences fall to the octave test, at least 30 stay, the pair ends in state 0 under its table -- and another
+    table, or exchanged weights, give other bytes"""
+    pr, sc = OC.pyramid_pair(name)
+    assert len(sc) == PC.PYRAMIDS[name][1]
+    res, flags = same(pr, O.UPSTREAM, scale=sc)
+    matched = np.flatnonzero(pr["idx"] >= 0)
+    o1, o2 = pr["q_kp"]["octave"][matched], pr["t_kp"]["octave"][pr["idx"][matched]]
+    inside = (o1 >= 0) & (o1 < len(sc)) & (o2 >= 0) & (o2 < len(sc))
+    print(name, len(matched), int(inside.sum()), res["n_corr"], res["n_removed"], res["steps"])
+    assert len(matched) == 100 and res["n_corr"] == inside.sum() >= 30 and (~inside).sum() > 20
+    assert (~((o1 >= 0) & (o1 < len(sc)))).sum() > 5 and (~((o2 >= 0) & (o2 < len(sc)))).sum() > 5  # on either side
+    assert res["state"] == 0 and 0 < res["n_removed"] < res["n_corr"] and min(res["steps"]) >= 1 and (flags[matched[~inside]] == 2).all()
+    if len(sc) == 1:
+        assert not o1[inside].any() and not o2[inside].any()  # one level: what stays has octave 0 on both sides
+    else:
+        assert (o1[inside] != o2[inside]).sum() > inside.sum() // 2  # the octaves of the two sides differ for most
+        swapped = dict(pr, q_kp=pr["q_kp"].copy(), t_kp=pr["t_kp"].copy())
+        swapped["q_kp"]["octave"][matched[inside]], swapped["t_kp"]["octave"][pr["idx"][matched[inside]]] = o2[inside], o1[inside]
+        assert _differ(OC.solve_pair(swapped, O.UPSTREAM, scale=sc), (res, flags))[0]  # w1 for w2
+    default = OC.solve_pair(pr, O.UPSTREAM)
+    assert default[0]["n_corr"] != res["n_corr"] and _differ(default, (res, flags)) == (True, True)  # a kernel with the default table built in
+
+
+# ---- the parameters at their limits --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(OC.LIMITS))
+def test_limits_are_what_was_recorded(name):
+    assert list(OC.LIMITS) == list(OC.LIMITS_RECORDED)
+    allowed = OC.LIMITS[name][1]
+    for pr, (state, steps, n_removed) in zip(OC.limit_pairs(), OC.LIMITS_RECORDED[name]):
+        res, flags = same(pr, OC.limit_params(name))
+        print(name, res["state"], res["steps"], res["n_removed"], res["n_inliers"])
+        assert res["n_corr"] == OC.LIMITS_CORR and res["state"] in allowed
+        assert (int(res["state"]), res["steps"].tolist(), int(res["n_removed"])) == (state, steps, n_removed)
+    a, b = OC.limit_pairs()
+    assert a["start"].tobytes() != b["start"].tobytes() and b["start"].tobytes() == OC.model_record(*OC.true_model()).tobytes()
+
+
+def test_limits_cover_what_their_names_say():
+    rec = OC.LIMITS_RECORDED
+    assert rec["32 iterations in every round, step_eps 0"][0][1] == [32, 32] and rec["1 iteration in every round"][0][1] == [1, 1]
+    assert [r[0] for r in rec["min_corr at the count"]] == [0, 0] and [r[0] for r in rec["min_corr one above the count"]] == [1, 1]
+    for name in ("round 0 removes everything, min_inliers 0", "round 0 removes everything, min_inliers 0, lambda 0"):
+        for pr in OC.limit_pairs():  # the second round starts with no correspondence left
+            res, flags = OC.solve_pair(pr, OC.limit_params(name))
+            assert res["n_removed"] == OC.LIMITS_CORR and res["n_inliers"] == 0 and res["steps"][0] == 5 and (flags[pr["rows"]] == 1).all()
+    assert rec["round 0 removes everything, min_inliers 0"][0][:2] == (0, [5, 1])       # lambda alone gives the pivots
+    assert rec["round 0 removes everything, min_inliers 0, lambda 0"][0][:2] == (2, [5, 0])  # no pivot: state 2 in the second round
+    res, _ = OC.solve_pair(OC.limit_pairs()[0], OC.limit_params("round 0 removes everything, min_inliers 0, lambda 0"))
+    R, t, s, _ = O.start(OC.limit_pairs()[0]["start"], False)
+    assert res["r12"].tolist() != [float(v) for v in R] and not res["model"]["sr12"].any()  # the model of round 0 stays, no model is embedded
+
+
+# ---- a singular system with finite sums ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fix", [False, True], ids=["scale", "fix_scale"])
+def test_singular_pair_ends_in_state_2_with_finite_sums(fix):
+    """the third pivot is 0 by structure; the model stays the start, which is not the identity"""
+    pr = OC.singular_pair(fix)
+    p = dict(OC.SINGULAR_PARAMS, fix_scale=fix)
+    res, flags = same(pr, p)
+    R, t, s, ok = O.start(pr["start"], fix)
+    assert ok and [float(v) for v in R] != [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0] and float(t[2]) == 0.5 and float(s) == (1.0 if fix else 2.0)
+    assert res["state"] == 2 and res["n_corr"] == 30 and res["steps"].tolist() == [0, 0] and (flags[pr["rows"]] == 0).all()
+    assert res["r12"].tolist() == [float(v) for v in R] and res["t12"].tolist() == [float(v) for v in t] and res["s12"] == s
+    m = res["model"]
+    assert m["state"] == 2 and not any(np.asarray(m[n]).any() for n in ("sr12", "t12", "s12", "sr21", "t21"))
+    c = O.correspondences(pr["view1"], pr["q_xyz"], pr["q_kp"], None, pr["view2"], pr["t_xyz"], pr["t_kp"], None, pr["idx"], PC.scale())
+    assert not c["x1"][:, :2].any() and not c["x2"][:, :2].any() and len(set(c["x2"][:, 2].tolist())) > 10  # on the axes, at their own depths
+    total = O.sums(c, O.cameras(pr["view1"], pr["view2"], p["chi2"]), R, t, s, True, np.ones(30, bool))
+    H = {ab: float(total[q]) for q, ab in enumerate(O.H_PAIRS)}
+    assert np.isfinite(total).all() and H[(0, 0)] > 0 and H[(1, 1)] - H[(0, 1)] ** 2 / H[(0, 0)] > 0
+    assert all(H[(min(2, q), max(2, q))] == 0.0 for q in range(7)) and np.abs(total[28:30]).min() > 1.0  # the third pivot is 0 - 0 - 0
+    assert O.solve(total, 0.0, 6 if fix else 7) is None and O.solve(total, 1e-8, 6 if fix else 7) is not None
+    assert OC.solve_pair(pr, dict(p, lambda_=1e-8))[0]["state"] != 2  # the damping alone makes the system regular
 
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------------------------

@@ -38,7 +38,7 @@ int main(int argc, char **argv)
     ss_sim3_opt_params p = {};
     p.chi2 = 10.0, p.lambda = 1e-6, p.step_eps = 1e-10, p.iterations0 = 5, p.iterations_more = 10, p.iterations_same = 5, p.min_corr = 10, p.min_inliers = 10;
     std::vector<uint8_t> active((size_t)n + 1);
-    std::vector<double> slot((size_t)(SS_SIM3OPT_SUMS + 1) * SS_POSE_SLOTS);
+    std::vector<double> slot((size_t)(SS_SIM3OPT_SUMS + 1) * SS_GN_SLOTS);
     std::vector<double> ms;
     long inliers = 0, failed = 0, steps = 0;
     for (int r = 0; r < reps; r++) {

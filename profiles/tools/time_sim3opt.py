@@ -1,6 +1,8 @@
 """Per-stage HIP-event times of the Sim3 refinement, one context alone on the chip: 1, 8 and 128 pairs of 300 correspondences each in
 2048 rows (15 % gross mismatches, half a pixel of noise, the synthetic scene of tests/sim3opt_cases.py, a start a few pixels off,
-upstream's 5 + 10 steps), ss_sim3_opt_pairs_device; gather and solve separately.  Next to them the host twin on one host core:
+upstream's 5 + 10 steps), ss_sim3_opt_pairs_device; gather and solve separately, and the mutual check of SearchBySim3's bookkeeping
+(ss_sim3_mutual_pairs_device: every other match as the prior ones, the matches and their inverse as the two searches' results; not in
+total_ms).  Next to them the host twin on one host core:
 profiles/tools/sim3opt_host_time.cpp, built here with g++ -O3 (or the executable named by the third argument) and run on the same
 correspondences and start models.  Prints the per-call median of every stage and, with an output path, writes the rows as JSON.
 usage: python profiles/tools/time_sim3opt.py [reps] [out.json] [sim3opt_host_time executable]"""
@@ -49,9 +51,20 @@ with tempfile.TemporaryDirectory() as tmp:
         d_res = torch.empty((B, 272), dtype=torch.uint8, device="cuda")
         views1 = np.concatenate([np.asarray(pr["view1"]).reshape(1) for pr in part])
         views2 = np.concatenate([np.asarray(pr["view2"]).reshape(1) for pr in part])
+        idx = np.stack([pr["idx"] for pr in part])
+        prior, idx21 = idx.copy(), np.full((B, ROWS), -1, np.int32)
+        prior[:, ::2] = -1
+        for b in range(B):
+            r = np.flatnonzero(idx[b] >= 0)
+            idx21[b, idx[b][r]] = r
+        d_prior, d_idx21 = torch.from_numpy(prior).cuda(), torch.from_numpy(idx21).cuda()
+        d_out = torch.empty((B, ROWS), dtype=torch.int32, device="cuda")
+        d_summary = torch.empty((B, 8), dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
 
         def call():
+            ctx.sim3_mutual_pairs_device(d_prior.data_ptr(), d["idx"].data_ptr(), d_idx21.data_ptr(), d_n.data_ptr(), d_n.data_ptr(), B, ROWS, d_out.data_ptr(),
+                                         d_summary.data_ptr())
             ctx.sim3_opt_pairs_device(d["q_xyz"].data_ptr(), d["q_kp"].data_ptr(), d_n.data_ptr(), d["t_xyz"].data_ptr(), d["t_kp"].data_ptr(), d_n.data_ptr(),
                                       d["idx"].data_ptr(), B, ROWS, views1, views2, d_start.data_ptr(), params, d_flags.data_ptr(), d_res.data_ptr())
 
@@ -67,7 +80,7 @@ with tempfile.TemporaryDirectory() as tmp:
         stages = {s["name"]: {"median_ms": round(s["median_ms"], 5), "mean_ms": round(s["total_ms"] / reps, 5), "launches_per_call": s["launches"] // reps,
                               "algorithmic_bytes": s["algorithmic_bytes"]} for s in ctx.stats() if s["launches"] and s["name"].startswith("sim3opt_")}
         res = d_res.cpu().numpy().view(binding.SIM3_OPT_RESULT_DTYPE).reshape(B)
-        row = {"pairs": B, "correspondences": N, "rows": ROWS, "reps": reps, "stages": stages, "total_ms": round(sum(v["median_ms"] for v in stages.values()), 5),
+        row = {"pairs": B, "correspondences": N, "rows": ROWS, "reps": reps, "stages": stages, "total_ms": round(sum(v["median_ms"] for k, v in stages.items() if k != "sim3opt_mutual"), 5),
                "states": sorted(set(int(v) for v in res["state"])), "mean_inliers": int(res["n_inliers"].mean()), "mean_steps": float(res["steps"].sum(axis=1).mean())}
         # the same correspondences, views and start models for the host twin
         path = os.path.join(tmp, f"pairs_{B}.bin")

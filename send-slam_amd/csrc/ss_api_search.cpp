@@ -87,6 +87,68 @@ static int pairs_shape(ss_ctx *c, const std::string &form, const char *counted, 
     return SS_OK;
 }
 
+/* the pyramid table of the context into a call (`what` heads the message) */
+static int context_pyramid(ss_ctx *c, const std::string &what, int *n_levels, float *scale)
+{
+    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
+        return fail(c, SS_ERR_INVALID_ARG, what + ": the context's n_levels / scale_factor give no pyramid table");
+    *n_levels = c->params.n_levels;
+    ss_scale_table(c->params.scale_factor, *n_levels, scale);
+    return SS_OK;
+}
+
+/* a call of one workgroup per frame or pair (`counted`: "frames", "pairs") takes 65535 of them */
+static int call_count_ok(ss_ctx *c, const std::string &what, int n, const char *counted)
+{
+    if (n > 65535) return fail(c, SS_ERR_INVALID_ARG, what + ": more than 65535 " + counted + " in one call");
+    return SS_OK;
+}
+
+/* the sides of the pairs of a Sim3 call on the caller arrays of a pairs form */
+static void pairs_sides(ssk_pair_sides &g, int n_pairs, int rows, const void *d_query_xyz, const void *d_query_kp, const void *d_query_skip,
+                        const void *d_n_query, const void *d_train_xyz, const void *d_train_kp, const void *d_train_skip, const void *d_n_train,
+                        const void *d_idx)
+{
+    g.n_frames = n_pairs, g.rows = rows;
+    g.q_xyz = (const ss_map_point *)d_query_xyz, g.t_xyz = (const ss_map_point *)d_train_xyz;
+    g.q_kp = (const ss_keypoint *)d_query_kp, g.t_kp = (const ss_keypoint *)d_train_kp;
+    g.q_skip = (const uint8_t *)d_query_skip, g.t_skip = (const uint8_t *)d_train_skip;
+    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
+    g.idx = (const int32_t *)d_idx;
+}
+
+/* ... and on the frames of the batch */
+static void batch_sides(ssk_pair_sides &g, const batch_operands &o, const void *d_xyz, const void *d_skip, const void *d_idx)
+{
+    g.n_frames = o.n_frames, g.rows = o.kcap;
+    g.q_xyz = g.t_xyz = (const ss_map_point *)d_xyz;
+    g.q_kp = g.t_kp = o.kps;
+    g.q_skip = g.t_skip = (const uint8_t *)d_skip;
+    g.nq = g.nt = o.n_kp;
+    g.src = o.src, g.frame_error = o.frame_error;
+    g.idx = (const int32_t *)d_idx;
+}
+
+/* The views of the pairs of g through the staged table `tab`: views1 then views2, each of n_frames.  A pairs form brings both; a
+ * batch form brings the frames' views as views1 and views2 NULL: pair b reads the view of its train frame (train_src NULL: b - 1) */
+static int pair_views(ss_ctx *c, staged_table &tab, ssk_pair_sides &g, const ss_proj_view *views1, const ss_proj_view *views2, const int32_t *train_src)
+{
+    const int n = g.n_frames;
+    const size_t vb = (size_t)n * sizeof(ss_proj_view);
+    const int rc = staged_upload(c, tab, 2 * vb, [&](uint8_t *h) {
+        ss_proj_view *v1 = (ss_proj_view *)h, *v2 = (ss_proj_view *)(h + vb);
+        memcpy(v1, views1, vb);
+        if (views2) memcpy(v2, views2, vb);
+        for (int b = 0; !views2 && b < n; b++) {
+            const int t = train_src ? train_src[b] : b - 1; /* checked by batch_operands_of; -1: the pair has no train and reads no view */
+            v2[b] = views1[t < 0 ? b : t];
+        }
+    });
+    if (rc != SS_OK) return rc;
+    g.views1 = tab.as<ss_proj_view>(), g.views2 = tab.as<ss_proj_view>(vb);
+    return SS_OK;
+}
+
 static void guided_rule(ssk_guided_call &g, const ss_guided_params *p)
 {
     g.th = p->th, g.rnum = p->ratio_num, g.rden = p->ratio_den;
@@ -153,6 +215,39 @@ static int io_fetch(ss_ctx *c, const io_piece *io, int n)
         if (io[k].out && io[k].bytes) HIP_TRY(c, hipMemcpyAsync(io[k].out, io[k].d, io[k].bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SS_OK;
+}
+
+/* The host form of one pair (ss_sim3, ss_sim3_opt; `what` heads the messages): the checks, the pair's arrays as one pair of `rows`
+ * rows on both sides in the form's device buffer `buf`, the pairs form on those pieces (device(io, rows)), the flags and the
+ * result back.  others: what else the form needs is there; extra: one more input of the form (the start), or NULL and 0 bytes */
+enum { PP_QX, PP_QK, PP_QS, PP_TX, PP_TK, PP_TS, PP_IDX, PP_N, PP_EXTRA, PP_FLAGS, PP_RES, PP_PIECES };
+extern "C++" template <class Device>
+static int single_pair(ss_ctx *c, const std::string &what, dev_buf<uint8_t> &buf, const ss_map_point *query_xyz, const ss_keypoint *query_kp,
+                       const uint8_t *query_skip, int n_query, const ss_map_point *train_xyz, const ss_keypoint *train_kp, const uint8_t *train_skip,
+                       int n_train, const int32_t *idx, bool others, const void *extra, size_t extra_bytes, uint8_t *flags, void *result,
+                       size_t result_bytes, Device device)
+{
+    if (n_query < 0 || n_train < 0 || n_query > SS_GUIDED_MAX_ROWS || n_train > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, what + ": n_query and n_train must be 0 .. SS_GUIDED_MAX_ROWS");
+    if (!others || !result || (n_query > 0 && (!query_xyz || !query_kp || !idx || !flags)) || (n_train > 0 && (!train_xyz || !train_kp)))
+        return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
+    /* `counts` is on this stack: no return before the stream has read it */
+    const size_t rows = (size_t)std::max(std::max(n_query, n_train), 1), nq = (size_t)n_query, nt = (size_t)n_train;
+    const size_t kp = sizeof(ss_keypoint), mp = sizeof(ss_map_point);
+    const int32_t counts[2] = {n_query, n_train};
+    io_piece io[PP_PIECES] = {{query_xyz, nullptr, rows * mp, nq * mp}, {query_kp, nullptr, rows * kp, nq * kp}, {query_skip, nullptr, rows, nq},
+                              {train_xyz, nullptr, rows * mp, nt * mp}, {train_kp, nullptr, rows * kp, nt * kp}, {train_skip, nullptr, rows, nt},
+                              {idx, nullptr, rows * 4, nq * 4}, {counts, nullptr, sizeof(counts), sizeof(counts)}, {extra, nullptr, extra_bytes, extra_bytes},
+                              {nullptr, flags, rows, nq}, {nullptr, result, result_bytes, result_bytes}};
+    int rc = io_send(c, buf, io, PP_PIECES);
+    if (!query_skip) io[PP_QS].d = nullptr; /* the pairs form takes NULL for "no flags" */
+    if (!train_skip) io[PP_TS].d = nullptr;
+    if (rc == SS_OK) rc = device(io, (int)rows);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PP_PIECES);
 }
 
 /* ---- guided matching (csrc/ss_guided.hip) ---- */
@@ -311,8 +406,8 @@ static int points_call_prepare(ss_ctx *c, Call &g, const std::string &what, cons
         return fail(c, SS_ERR_INVALID_ARG, what + ": point_rows " + std::to_string(g.point_rows) + " / rows_per_frame " + std::to_string(g.rows) +
                                                " exceed SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")");
     if (extent_w <= 0 || extent_h <= 0) return fail(c, SS_ERR_INVALID_ARG, what + ": extent_w and extent_h must be > 0");
-    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
-        return fail(c, SS_ERR_INVALID_ARG, what + ": the context's n_levels / scale_factor give no pyramid table");
+    int rc = context_pyramid(c, what, &g.n_levels, g.scale);
+    if (rc != SS_OK) return rc;
     if (g.n_frames == 0) return SS_OK;
     if (!views) return fail(c, SS_ERR_INVALID_ARG, what + ": views is NULL");
     for (int b = 0; b < g.n_frames; b++) {
@@ -325,11 +420,9 @@ static int points_call_prepare(ss_ctx *c, Call &g, const std::string &what, cons
         return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
     if (check_right && !g.t_right) return fail(c, SS_ERR_INVALID_ARG, what + ": check_right needs the right coordinates of the train rows");
     g.check_right = check_right;
-    g.n_levels = c->params.n_levels;
-    ss_scale_table(c->params.scale_factor, g.n_levels, g.scale);
     /* the host tables of the call: n_frames views, then n_frames block numbers (point_src NULL: 0, 1, ...) */
     const size_t views_bytes = (size_t)g.n_frames * sizeof(ss_proj_view);
-    int rc = staged_upload(c, c->proj_tab, views_bytes + (size_t)g.n_frames * sizeof(int32_t), [&](uint8_t *h) {
+    rc = staged_upload(c, c->proj_tab, views_bytes + (size_t)g.n_frames * sizeof(int32_t), [&](uint8_t *h) {
         memcpy(h, views, views_bytes);
         int32_t *src = (int32_t *)(h + views_bytes);
         for (int b = 0; b < g.n_frames; b++) src[b] = point_src ? point_src[b] : b;
@@ -1175,15 +1268,6 @@ static int upload_epi_pairs(ss_ctx *c, const ss_epi_pair *pairs, int n)
     return staged_upload(c, c->epi_tab, bytes, [&](uint8_t *h) { memcpy(h, pairs, bytes); });
 }
 
-static int epi_pyramid(ss_ctx *c, int *n_levels, float *scale)
-{
-    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
-        return fail(c, SS_ERR_INVALID_ARG, "epipolar search: the context's n_levels / scale_factor give no pyramid table");
-    *n_levels = c->params.n_levels;
-    ss_scale_table(c->params.scale_factor, *n_levels, scale);
-    return SS_OK;
-}
-
 /* The launches of a search whose operands, counts and outputs are filled in: the index of the train nodes where the call brings its
  * own (t_node != NULL), the search, guided matching's finish as it is (its summaries go to the workspace), the summaries */
 static int epi_match_run(ss_ctx *c, ssk_guided_call &g, ssk_epi_call &e, const ss_epi_pair *pairs, const ss_epi_params *p, const int32_t *t_node)
@@ -1191,7 +1275,7 @@ static int epi_match_run(ss_ctx *c, ssk_guided_call &g, ssk_epi_call &e, const s
     g.th = p->th, g.rnum = 0, g.rden = 0;
     g.one_to_one = p->one_to_one != 0, g.orientation = p->orientation;
     e.coarse = p->coarse != 0;
-    int rc = epi_pyramid(c, &e.n_levels, e.scale);
+    int rc = context_pyramid(c, "epipolar search", &e.n_levels, e.scale);
     if (rc != SS_OK) return rc;
     const size_t nr = (size_t)g.n_frames * g.rows;
     node_index own;
@@ -1277,7 +1361,7 @@ int ss_match_epi_batch_device(ss_ctx *c, const int32_t *train_src, const void *d
 static int tri_run(ss_ctx *c, ssk_tri_call &t, const ss_epi_pair *pairs, const ss_tri_params *tp)
 {
     t.tp = *tp;
-    int rc = epi_pyramid(c, &t.n_levels, t.scale);
+    int rc = context_pyramid(c, "epipolar search", &t.n_levels, t.scale);
     if (rc != SS_OK) return rc;
     const size_t nr = (size_t)t.n_frames * t.rows;
     rc = grow(c, c->d_tri_ws, nr * sizeof(ss_map_point));
@@ -1427,29 +1511,24 @@ int ss_sim3_to_view(const ss_camera *cam, const ss_sim3_result *result, const do
     return ss_fuse_view_sim3(cam, m, t, bf, out);
 }
 
-/* The checks the device forms share, the workspace, the views (views1 then views2, each of n_frames, through `fill`), then the four
- * launches of a call whose device operands and outputs are filled in */
-extern "C++" template <class Fill> static int sim3_run(ss_ctx *c, ssk_sim3_call &g, const ss_sim3_params *p, Fill fill_views)
+/* The checks the device forms share, the workspace, the views (pair_views), then the four launches of a call whose device operands
+ * and outputs are filled in */
+static int sim3_run(ss_ctx *c, ssk_sim3_call &g, const ss_sim3_params *p, const ss_proj_view *views1, const ss_proj_view *views2, const int32_t *train_src)
 {
-    if (g.n_frames > 65535) return fail(c, SS_ERR_INVALID_ARG, "sim3: more than 65535 pairs in one call");
-    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
-        return fail(c, SS_ERR_INVALID_ARG, "sim3: the context's n_levels / scale_factor give no pyramid table");
+    int rc = call_count_ok(c, "sim3", g.n_frames, "pairs");
+    if (rc == SS_OK) rc = context_pyramid(c, "sim3", &g.n_levels, g.scale);
+    if (rc != SS_OK) return rc;
     g.chi2 = p->chi2, g.min_inliers = p->min_inliers, g.max_iterations = p->max_iterations, g.fix_scale = p->fix_scale != 0, g.seed = p->seed;
-    g.n_levels = c->params.n_levels;
-    ss_scale_table(c->params.scale_factor, g.n_levels, g.scale);
     const size_t nr = (size_t)g.n_frames * g.rows, nh = (size_t)g.n_frames * g.max_iterations;
-    int rc = carve_from(c, c->d_sim3_ws, [&](carve &w) {
+    rc = carve_from(c, c->d_sim3_ws, [&](carve &w) {
         g.corr = w.take<float>(12 * nr * sizeof(float));
         g.corr_of_row = w.take<int32_t>(nr * sizeof(int32_t));
         g.n_corr = w.take<int32_t>((size_t)g.n_frames * sizeof(int32_t));
         g.models = w.take<ssk_sim3_model>(nh * sizeof(ssk_sim3_model));
         g.counts = w.take<int32_t>(nh * sizeof(int32_t));
     });
+    if (rc == SS_OK) rc = pair_views(c, c->sim3_tab, g, views1, views2, train_src);
     if (rc != SS_OK) return rc;
-    const size_t vb = (size_t)g.n_frames * sizeof(ss_proj_view);
-    rc = staged_upload(c, c->sim3_tab, 2 * vb, [&](uint8_t *h) { fill_views((ss_proj_view *)h, (ss_proj_view *)(h + vb)); });
-    if (rc != SS_OK) return rc;
-    g.views1 = c->sim3_tab.as<ss_proj_view>(), g.views2 = c->sim3_tab.as<ss_proj_view>(vb);
     const int64_t np = g.n_frames;
     {
         /* per query row: its match and the number written; a correspondence reads two map points, two octaves and up to two flags
@@ -1491,18 +1570,9 @@ int ss_sim3_pairs_device(ss_ctx *c, const void *d_query_xyz, const void *d_query
     if (!d_query_xyz || !d_query_kp || !d_n_query || !d_train_xyz || !d_train_kp || !d_n_train || !d_idx || !views1 || !views2 || !d_inlier || !d_result)
         return fail(c, SS_ERR_INVALID_ARG, "sim3: NULL buffer");
     ssk_sim3_call g;
-    g.n_frames = n_pairs, g.rows = rows;
-    g.q_xyz = (const ss_map_point *)d_query_xyz, g.t_xyz = (const ss_map_point *)d_train_xyz;
-    g.q_kp = (const ss_keypoint *)d_query_kp, g.t_kp = (const ss_keypoint *)d_train_kp;
-    g.q_skip = (const uint8_t *)d_query_skip, g.t_skip = (const uint8_t *)d_train_skip;
-    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
-    g.idx = (const int32_t *)d_idx;
+    pairs_sides(g, n_pairs, rows, d_query_xyz, d_query_kp, d_query_skip, d_n_query, d_train_xyz, d_train_kp, d_train_skip, d_n_train, d_idx);
     g.inlier = (uint8_t *)d_inlier, g.result = (ss_sim3_result *)d_result;
-    const size_t vb = (size_t)n_pairs * sizeof(ss_proj_view);
-    return sim3_run(c, g, p, [&](ss_proj_view *v1, ss_proj_view *v2) {
-        memcpy(v1, views1, vb);
-        memcpy(v2, views2, vb);
-    });
+    return sim3_run(c, g, p, views1, views2, nullptr);
 }
 
 int ss_sim3_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_xyz, const void *d_skip, const void *d_idx, const ss_proj_view *views,
@@ -1517,22 +1587,9 @@ int ss_sim3_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_xyz,
     const int rc = batch_operands_of(c, "sim3", train_src, o);
     if (rc != SS_OK) return rc;
     ssk_sim3_call g;
-    g.n_frames = o.n_frames, g.rows = o.kcap;
-    g.q_xyz = g.t_xyz = (const ss_map_point *)d_xyz;
-    g.q_kp = g.t_kp = o.kps;
-    g.q_skip = g.t_skip = (const uint8_t *)d_skip;
-    g.nq = g.nt = o.n_kp;
-    g.src = o.src, g.frame_error = o.frame_error;
-    g.idx = (const int32_t *)d_idx;
+    batch_sides(g, o, d_xyz, d_skip, d_idx);
     g.inlier = (uint8_t *)d_inlier, g.result = (ss_sim3_result *)d_result;
-    const int n = o.n_frames;
-    return sim3_run(c, g, p, [&](ss_proj_view *v1, ss_proj_view *v2) {
-        for (int b = 0; b < n; b++) {
-            const int t = train_src ? train_src[b] : b - 1; /* checked by batch_operands_of; -1: the pair has no train and reads no view */
-            v1[b] = views[b];
-            v2[b] = views[t < 0 ? b : t];
-        }
-    });
+    return sim3_run(c, g, p, views, nullptr, train_src);
 }
 
 int ss_sim3(ss_ctx *c, const ss_proj_view *view1, const ss_map_point *query_xyz, const ss_keypoint *query_kp, const uint8_t *query_skip, int n_query,
@@ -1541,28 +1598,11 @@ int ss_sim3(ss_ctx *c, const ss_proj_view *view1, const ss_map_point *query_xyz,
 {
     if (!c) return SS_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
-    if (n_query < 0 || n_train < 0 || n_query > SS_GUIDED_MAX_ROWS || n_train > SS_GUIDED_MAX_ROWS)
-        return fail(c, SS_ERR_INVALID_ARG, "sim3: n_query and n_train must be 0 .. SS_GUIDED_MAX_ROWS");
-    if (!view1 || !view2 || !result || (n_query > 0 && (!query_xyz || !query_kp || !idx || !inlier)) || (n_train > 0 && (!train_xyz || !train_kp)))
-        return fail(c, SS_ERR_INVALID_ARG, "sim3: NULL buffer");
-    /* one pair of `rows` rows on both sides; `counts` is on this stack: no return before the stream has read it */
-    const size_t rows = (size_t)std::max(std::max(n_query, n_train), 1), nq = (size_t)n_query, nt = (size_t)n_train;
-    const size_t kp = sizeof(ss_keypoint), mp = sizeof(ss_map_point);
-    const int32_t counts[2] = {n_query, n_train};
-    enum { QX, QK, QS, TX, TK, TS, IDX, N, INL, RES, PIECES };
-    io_piece io[PIECES] = {{query_xyz, nullptr, rows * mp, nq * mp}, {query_kp, nullptr, rows * kp, nq * kp}, {query_skip, nullptr, rows, nq},
-                           {train_xyz, nullptr, rows * mp, nt * mp}, {train_kp, nullptr, rows * kp, nt * kp}, {train_skip, nullptr, rows, nt},
-                           {idx, nullptr, rows * 4, nq * 4}, {counts, nullptr, sizeof(counts), sizeof(counts)}, {nullptr, inlier, rows, nq},
-                           {nullptr, result, sizeof(ss_sim3_result), sizeof(ss_sim3_result)}};
-    int rc = io_send(c, c->d_sim3_io, io, PIECES);
-    if (rc == SS_OK)
-        rc = ss_sim3_pairs_device(c, io[QX].d, io[QK].d, query_skip ? io[QS].d : nullptr, io[N].d, io[TX].d, io[TK].d, train_skip ? io[TS].d : nullptr,
-                                  io[N].d + 4, io[IDX].d, 1, (int)rows, view1, view2, p, io[INL].d, io[RES].d);
-    if (rc != SS_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    return io_fetch(c, io, PIECES);
+    return single_pair(c, "sim3", c->d_sim3_io, query_xyz, query_kp, query_skip, n_query, train_xyz, train_kp, train_skip, n_train, idx, view1 && view2,
+                       nullptr, 0, inlier, result, sizeof(ss_sim3_result), [&](const io_piece *io, int rows) {
+                           return ss_sim3_pairs_device(c, io[PP_QX].d, io[PP_QK].d, io[PP_QS].d, io[PP_N].d, io[PP_TX].d, io[PP_TK].d, io[PP_TS].d,
+                                                       io[PP_N].d + 4, io[PP_IDX].d, 1, rows, view1, view2, p, io[PP_FLAGS].d, io[PP_RES].d);
+                       });
 }
 
 /* ---- pose-only optimisation (csrc/ss_pose.hip, csrc/ss_pose_steps.h) ---- */
@@ -1593,7 +1633,6 @@ int ss_pose_opt_host(const ss_proj_view *view, const double *start, const float 
     /* step 1 */
     std::vector<ss_pose_obs> obs;
     std::vector<int> slot_of;
-    int n_stereo = 0;
     for (int i = 0; i < slots; i++) {
         const int prow = p->idx_by_row ? idx[i] : i, krow = p->idx_by_row ? i : idx[i];
         flags[i] = 2;
@@ -1604,70 +1643,12 @@ int ss_pose_opt_host(const ss_proj_view *view, const double *start, const float 
         const float ur = ss_pose_stored_right(p->check_right != 0, right != nullptr, right ? right[krow] : 0.0f);
         obs.push_back(ss_pose_obs_of(points[prow].x, points[prow].y, points[prow].z, kp[krow].x, kp[krow].y, ur, scale[octave]));
         slot_of.push_back(i);
-        n_stereo += obs.back().stereo ? 1 : 0;
     }
     const int n = (int)obs.size();
-    const ss_pose_cam cam = ss_pose_cam_of(*view, p->chi2_mono, p->chi2_stereo);
-    double R[9], t[3], R0[9], t0[3];
-    const bool start_ok = ss_pose_start(start, R, t);
-    memcpy(R0, R, sizeof(R));
-    memcpy(t0, t, sizeof(t));
-    std::vector<uint8_t> active((size_t)n, 1);
-    int state = !start_ok ? 2 : n < p->min_obs ? 1 : 0, n_in = n;
-    int32_t steps[8] = {};
-    double cost = 0.0;
-    std::vector<double> slot((size_t)(SS_POSE_SUMS + 1) * SS_POSE_SLOTS);
-    for (int round = 0; state == 0 && round < p->n_rounds; round++) {
-        const bool robust = round < p->robust_rounds;
-        for (int it = 0; it < p->iterations; it++) {
-            std::fill(slot.begin(), slot.end(), 0.0);
-            for (int k = 0; k < n; k++) {
-                double term[SS_POSE_SUMS];
-                if (!active[(size_t)k] || !ss_pose_terms(obs[(size_t)k], cam, R, t, robust, term)) continue;
-                for (int s = 0; s < SS_POSE_SUMS; s++) {
-                    double &a = slot[(size_t)s * SS_POSE_SLOTS + k % SS_POSE_SLOTS];
-                    a = a + term[s];
-                }
-            }
-            double sum[SS_POSE_SUMS];
-            for (int s = 0; s < SS_POSE_SUMS; s++) sum[s] = ss_pose_tree(&slot[(size_t)s * SS_POSE_SLOTS]);
-            bool small;
-            const int rc = ss_pose_step(sum, p->lambda, p->step_eps, R, t, &small);
-            if (rc != 0) {
-                state = rc;
-                break;
-            }
-            steps[round]++;
-            if (small) break;
-        }
-        if (state != 0) break;
-        /* step 4 */
-        double *c = &slot[(size_t)SS_POSE_SUMS * SS_POSE_SLOTS];
-        std::fill(c, c + SS_POSE_SLOTS, 0.0);
-        n_in = 0;
-        for (int k = 0; k < n; k++) {
-            const double chi2 = ss_pose_chi2(obs[(size_t)k], cam, R, t);
-            active[(size_t)k] = ss_pose_inlier(obs[(size_t)k], cam, chi2) ? 1 : 0;
-            if (!active[(size_t)k]) continue;
-            c[k % SS_POSE_SLOTS] = c[k % SS_POSE_SLOTS] + chi2;
-            n_in++;
-        }
-        cost = ss_pose_tree(c);
-        if (n_in < p->min_obs) state = 3;
-    }
-    if (!ss_pose_all_finite(R, t)) {
-        state = 2;
-        memcpy(R, R0, sizeof(R));
-        memcpy(t, t0, sizeof(t));
-    }
+    std::vector<uint8_t> active((size_t)n + 1);
+    std::vector<double> slot((size_t)(SS_POSE_SUMS + 1) * SS_GN_SLOTS);
+    ss_pose_frame_host(obs.data(), n, ss_pose_cam_of(*view, p->chi2_mono, p->chi2_stereo), start, *p, active.data(), slot.data(), result);
     for (int k = 0; k < n; k++) flags[slot_of[(size_t)k]] = active[(size_t)k] ? 0 : 1;
-    memset(result, 0, sizeof(*result));
-    memcpy(result->rcw, R, sizeof(R));
-    memcpy(result->tcw, t, sizeof(t));
-    result->cost = cost;
-    result->state = state;
-    result->n_obs = n, result->n_stereo = n_stereo, result->n_inliers = n_in;
-    memcpy(result->steps, steps, sizeof(steps));
     return SS_OK;
 }
 
@@ -1681,9 +1662,9 @@ static int pose_run(ss_ctx *c, ssk_pose_call &g, int n_blocks, const ss_proj_vie
     if (g.point_rows > SS_GUIDED_MAX_ROWS || g.rows > SS_GUIDED_MAX_ROWS)
         return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: point_rows " + std::to_string(g.point_rows) + " / rows_per_frame " + std::to_string(g.rows) +
                                                " exceed SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")");
-    if (g.n_frames > 65535) return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: more than 65535 frames in one call");
-    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
-        return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: the context's n_levels / scale_factor give no pyramid table");
+    int rc = call_count_ok(c, "pose optimisation", g.n_frames, "frames");
+    if (rc == SS_OK) rc = context_pyramid(c, "pose optimisation", &g.n_levels, g.scale);
+    if (rc != SS_OK) return rc;
     if (g.n_frames == 0) return SS_OK;
     if (!views || !start_poses) return fail(c, SS_ERR_INVALID_ARG, "pose optimisation: views or start_poses is NULL");
     for (int b = 0; b < g.n_frames; b++) {
@@ -1697,10 +1678,8 @@ static int pose_run(ss_ctx *c, ssk_pose_call &g, int n_blocks, const ss_proj_vie
     g.n_rounds = p->n_rounds, g.iterations = p->iterations, g.robust_rounds = p->robust_rounds, g.min_obs = p->min_obs;
     g.check_right = p->check_right != 0, g.idx_by_row = p->idx_by_row != 0;
     g.slots = g.idx_by_row ? g.rows : g.point_rows;
-    g.n_levels = c->params.n_levels;
-    ss_scale_table(c->params.scale_factor, g.n_levels, g.scale);
     const size_t ns = (size_t)g.n_frames * g.slots;
-    int rc = carve_from(c, c->d_pose_ws, [&](carve &w) {
+    rc = carve_from(c, c->d_pose_ws, [&](carve &w) {
         g.planes = w.take<float>(7 * ns * sizeof(float));
         g.slot_of = w.take<int32_t>(ns * sizeof(int32_t));
         g.n_obs = w.take<int32_t>((size_t)g.n_frames * sizeof(int32_t));
@@ -1845,7 +1824,7 @@ int ss_sim3_opt_host(const ss_proj_view *view1, const ss_proj_view *view2, const
     }
     const int n = (int)corr.size();
     std::vector<uint8_t> active((size_t)n + 1);
-    std::vector<double> slot((size_t)(SS_SIM3OPT_SUMS + 1) * SS_POSE_SLOTS);
+    std::vector<double> slot((size_t)(SS_SIM3OPT_SUMS + 1) * SS_GN_SLOTS);
     ss_sim3opt_pair_host(corr.data(), n, ss_sim3opt_cams_of(*view1, *view2, p->chi2), *start, start->status, *p, active.data(), slot.data(), result);
     for (int k = 0; k < n; k++) flags[row_of[(size_t)k]] = active[(size_t)k] ? 0 : 1;
     return SS_OK;
@@ -1866,27 +1845,23 @@ int ss_sim3_to_view21(const ss_camera *cam, const ss_sim3_result *result, const 
     return ss_fuse_view_sim3(cam, m, t, bf, out);
 }
 
-/* The checks the device forms share, the workspace, the views (views1 then views2, each of n_frames, through `fill`), then the two
- * launches of a call whose device operands and outputs are filled in */
-extern "C++" template <class Fill> static int sim3opt_run(ss_ctx *c, ssk_sim3opt_call &g, const ss_sim3_opt_params *p, Fill fill_views)
+/* The checks the device forms share, the workspace, the views (pair_views), then the two launches of a call whose device operands
+ * and outputs are filled in */
+static int sim3opt_run(ss_ctx *c, ssk_sim3opt_call &g, const ss_sim3_opt_params *p, const ss_proj_view *views1, const ss_proj_view *views2,
+                       const int32_t *train_src)
 {
-    if (g.n_frames > 65535) return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: more than 65535 pairs in one call");
-    if (c->params.n_levels < 1 || c->params.n_levels > SS_MAX_LEVELS || !(c->params.scale_factor > 1.0f))
-        return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: the context's n_levels / scale_factor give no pyramid table");
+    int rc = call_count_ok(c, "sim3 refinement", g.n_frames, "pairs");
+    if (rc == SS_OK) rc = context_pyramid(c, "sim3 refinement", &g.n_levels, g.scale);
+    if (rc != SS_OK) return rc;
     g.p = *p;
-    g.n_levels = c->params.n_levels;
-    ss_scale_table(c->params.scale_factor, g.n_levels, g.scale);
     const size_t nr = (size_t)g.n_frames * g.rows;
-    int rc = carve_from(c, c->d_sim3opt_ws, [&](carve &w) {
+    rc = carve_from(c, c->d_sim3opt_ws, [&](carve &w) {
         g.planes = w.take<float>(12 * nr * sizeof(float));
         g.row_of = w.take<int32_t>(nr * sizeof(int32_t));
         g.n_corr = w.take<int32_t>((size_t)g.n_frames * sizeof(int32_t));
     });
+    if (rc == SS_OK) rc = pair_views(c, c->sim3opt_tab, g, views1, views2, train_src);
     if (rc != SS_OK) return rc;
-    const size_t vb = (size_t)g.n_frames * sizeof(ss_proj_view);
-    rc = staged_upload(c, c->sim3opt_tab, 2 * vb, [&](uint8_t *h) { fill_views((ss_proj_view *)h, (ss_proj_view *)(h + vb)); });
-    if (rc != SS_OK) return rc;
-    g.views1 = c->sim3opt_tab.as<ss_proj_view>(), g.views2 = c->sim3opt_tab.as<ss_proj_view>(vb);
     const int64_t np = g.n_frames;
     {
         /* per query row: its match and its flag or row number; a correspondence reads two map points, two keypoints and up to two
@@ -1920,18 +1895,10 @@ int ss_sim3_opt_pairs_device(ss_ctx *c, const void *d_query_xyz, const void *d_q
         !d_result)
         return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: NULL buffer");
     ssk_sim3opt_call g;
-    g.n_frames = n_pairs, g.rows = rows;
-    g.q_xyz = (const ss_map_point *)d_query_xyz, g.t_xyz = (const ss_map_point *)d_train_xyz;
-    g.q_kp = (const ss_keypoint *)d_query_kp, g.t_kp = (const ss_keypoint *)d_train_kp;
-    g.q_skip = (const uint8_t *)d_query_skip, g.t_skip = (const uint8_t *)d_train_skip;
-    g.nq = (const int32_t *)d_n_query, g.nt = (const int32_t *)d_n_train;
-    g.idx = (const int32_t *)d_idx, g.start = (const ss_sim3_result *)d_start;
+    pairs_sides(g, n_pairs, rows, d_query_xyz, d_query_kp, d_query_skip, d_n_query, d_train_xyz, d_train_kp, d_train_skip, d_n_train, d_idx);
+    g.start = (const ss_sim3_result *)d_start;
     g.flags = (uint8_t *)d_flags, g.result = (ss_sim3_opt_result *)d_result;
-    const size_t vb = (size_t)n_pairs * sizeof(ss_proj_view);
-    return sim3opt_run(c, g, p, [&](ss_proj_view *v1, ss_proj_view *v2) {
-        memcpy(v1, views1, vb);
-        memcpy(v2, views2, vb);
-    });
+    return sim3opt_run(c, g, p, views1, views2, nullptr);
 }
 
 int ss_sim3_opt_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_xyz, const void *d_skip, const void *d_idx, const ss_proj_view *views,
@@ -1946,22 +1913,10 @@ int ss_sim3_opt_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_
     const int rc = batch_operands_of(c, "sim3 refinement", train_src, o);
     if (rc != SS_OK) return rc;
     ssk_sim3opt_call g;
-    g.n_frames = o.n_frames, g.rows = o.kcap;
-    g.q_xyz = g.t_xyz = (const ss_map_point *)d_xyz;
-    g.q_kp = g.t_kp = o.kps;
-    g.q_skip = g.t_skip = (const uint8_t *)d_skip;
-    g.nq = g.nt = o.n_kp;
-    g.src = o.src, g.frame_error = o.frame_error;
-    g.idx = (const int32_t *)d_idx, g.start = (const ss_sim3_result *)d_start;
+    batch_sides(g, o, d_xyz, d_skip, d_idx);
+    g.start = (const ss_sim3_result *)d_start;
     g.flags = (uint8_t *)d_flags, g.result = (ss_sim3_opt_result *)d_result;
-    const int n = o.n_frames;
-    return sim3opt_run(c, g, p, [&](ss_proj_view *v1, ss_proj_view *v2) {
-        for (int b = 0; b < n; b++) {
-            const int t = train_src ? train_src[b] : b - 1; /* checked by batch_operands_of; -1: the pair has no train and reads no view */
-            v1[b] = views[b];
-            v2[b] = views[t < 0 ? b : t];
-        }
-    });
+    return sim3opt_run(c, g, p, views, nullptr, train_src);
 }
 
 int ss_sim3_opt(ss_ctx *c, const ss_proj_view *view1, const ss_map_point *query_xyz, const ss_keypoint *query_kp, const uint8_t *query_skip, int n_query,
@@ -1970,35 +1925,18 @@ int ss_sim3_opt(ss_ctx *c, const ss_proj_view *view1, const ss_map_point *query_
 {
     if (!c) return SS_ERR_INVALID_ARG;
     (void)hipSetDevice(c->device);
-    if (n_query < 0 || n_train < 0 || n_query > SS_GUIDED_MAX_ROWS || n_train > SS_GUIDED_MAX_ROWS)
-        return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: n_query and n_train must be 0 .. SS_GUIDED_MAX_ROWS");
-    if (!view1 || !view2 || !start || !result || (n_query > 0 && (!query_xyz || !query_kp || !idx || !flags)) || (n_train > 0 && (!train_xyz || !train_kp)))
-        return fail(c, SS_ERR_INVALID_ARG, "sim3 refinement: NULL buffer");
-    /* one pair of `rows` rows on both sides; `counts` is on this stack: no return before the stream has read it */
-    const size_t rows = (size_t)std::max(std::max(n_query, n_train), 1), nq = (size_t)n_query, nt = (size_t)n_train;
-    const size_t kp = sizeof(ss_keypoint), mp = sizeof(ss_map_point);
-    const int32_t counts[2] = {n_query, n_train};
-    enum { QX, QK, QS, TX, TK, TS, IDX, N, ST, FL, RES, PIECES };
-    io_piece io[PIECES] = {{query_xyz, nullptr, rows * mp, nq * mp}, {query_kp, nullptr, rows * kp, nq * kp}, {query_skip, nullptr, rows, nq},
-                           {train_xyz, nullptr, rows * mp, nt * mp}, {train_kp, nullptr, rows * kp, nt * kp}, {train_skip, nullptr, rows, nt},
-                           {idx, nullptr, rows * 4, nq * 4}, {counts, nullptr, sizeof(counts), sizeof(counts)},
-                           {start, nullptr, sizeof(ss_sim3_result), sizeof(ss_sim3_result)}, {nullptr, flags, rows, nq},
-                           {nullptr, result, sizeof(ss_sim3_opt_result), sizeof(ss_sim3_opt_result)}};
-    int rc = io_send(c, c->d_sim3opt_io, io, PIECES);
-    if (rc == SS_OK)
-        rc = ss_sim3_opt_pairs_device(c, io[QX].d, io[QK].d, query_skip ? io[QS].d : nullptr, io[N].d, io[TX].d, io[TK].d, train_skip ? io[TS].d : nullptr,
-                                      io[N].d + 4, io[IDX].d, 1, (int)rows, view1, view2, io[ST].d, p, io[FL].d, io[RES].d);
-    if (rc != SS_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    return io_fetch(c, io, PIECES);
+    return single_pair(c, "sim3 refinement", c->d_sim3opt_io, query_xyz, query_kp, query_skip, n_query, train_xyz, train_kp, train_skip, n_train, idx,
+                       view1 && view2 && start, start, sizeof(ss_sim3_result), flags, result, sizeof(ss_sim3_opt_result), [&](const io_piece *io, int rows) {
+                           return ss_sim3_opt_pairs_device(c, io[PP_QX].d, io[PP_QK].d, io[PP_QS].d, io[PP_N].d, io[PP_TX].d, io[PP_TK].d, io[PP_TS].d,
+                                                           io[PP_N].d + 4, io[PP_IDX].d, 1, rows, view1, view2, io[PP_EXTRA].d, p, io[PP_FLAGS].d,
+                                                           io[PP_RES].d);
+                       });
 }
 
 /* the two launches of SearchBySim3's bookkeeping: the call's sides are filled in */
 static int sim3_marks_run(ss_ctx *c, ssk_sim3_marks_call &g, bool mutual)
 {
-    if (g.n_frames > 65535) return fail(c, SS_ERR_INVALID_ARG, "sim3 marks: more than 65535 pairs in one call");
+    if (const int rc = call_count_ok(c, "sim3 marks", g.n_frames, "pairs")) return rc;
     const int64_t nr = (int64_t)g.n_frames * g.rows;
     if (!mutual) {
         /* per row: its match and up to two skip bytes read, two bytes written; a valid match writes one more */

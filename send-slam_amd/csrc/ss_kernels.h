@@ -346,7 +346,8 @@ struct alignas(16) ssk_sim3_model { /* 128 bytes, so that a wave reads one with 
     float sr12[9], t12[3], sr21[9], t21[3], s12;
     float pad[7];
 };
-struct ssk_sim3_call {
+/* the two sides of the pairs of a call: what the Sim3 RANSAC and the Sim3 refinement read of them */
+struct ssk_pair_sides {
     int n_frames = 0, rows = 0;
     const ss_map_point *q_xyz = nullptr, *t_xyz = nullptr;
     const ss_keypoint *q_kp = nullptr, *t_kp = nullptr;
@@ -356,6 +357,8 @@ struct ssk_sim3_call {
     const int32_t *frame_error = nullptr;
     const int32_t *idx = nullptr;
     const ss_proj_view *views1 = nullptr, *views2 = nullptr; /* device [n_frames] each */
+};
+struct ssk_sim3_call : ssk_pair_sides {
     float chi2 = 0;
     int min_inliers = 0, max_iterations = 1, fix_scale = 0;
     uint32_t seed = 0;
@@ -413,16 +416,7 @@ void ssk_pose_solve(hipStream_t s, const ssk_pose_call &g);
  * of every correspondence and N, and flag 2 into every other row; solve (one workgroup per pair) runs both rounds and writes the
  * correspondences' flags and the result */
 #define SSK_SIM3OPT_CHUNK 1024
-struct ssk_sim3opt_call {
-    int n_frames = 0, rows = 0;
-    const ss_map_point *q_xyz = nullptr, *t_xyz = nullptr;
-    const ss_keypoint *q_kp = nullptr, *t_kp = nullptr;
-    const uint8_t *q_skip = nullptr, *t_skip = nullptr; /* [n_frames][rows], or NULL */
-    const int32_t *nq = nullptr, *nt = nullptr;
-    const int32_t *src = nullptr;
-    const int32_t *frame_error = nullptr;
-    const int32_t *idx = nullptr;
-    const ss_proj_view *views1 = nullptr, *views2 = nullptr; /* device [n_frames] each */
+struct ssk_sim3opt_call : ssk_pair_sides {
     const ss_sim3_result *start = nullptr;                   /* device [n_frames] */
     ss_sim3_opt_params p = {};
     int n_levels = 1;

@@ -4,15 +4,16 @@
  * the text of ss_pose_steps.h, which the host twin compiles too.
  *
  *   P-A  k_pose_gather  one workgroup per frame walks the slots in chunks of SSK_POSE_CHUNK in ascending order: ballot and prefix
- *                       sums number the observations (k_sim3_gather's compaction), so the numbering is the rule's whatever the
+ *                       sums number the observations (gn_chunk_compact of ss_gn.h), so the numbering is the rule's whatever the
  *                       schedule.  An observation writes its seven floats (X Y Z u v, the right coordinate or -1, the scale of its
  *                       octave) into seven planes and its slot; every other slot gets its flag 2 here
- *   P-B  k_pose_solve   one workgroup of SS_POSE_SLOTS threads per frame holds the whole round and step loop.  Thread s owns the
+ *   P-B  k_pose_solve   one workgroup of SS_GN_SLOTS threads per frame holds the whole round and step loop.  Thread s owns the
  *                       observations s, s + 256, ...: it re-reads their planes every step (they stay in L2; a frame of 2000 has
  *                       eight per thread), keeps its 26 partial sums in registers and its observations' inlier bits in one 64-bit
  *                       mask.  A wave folds by halving through cross-lane moves, the four wave results go through LDS (two buffers
- *                       in turn: one barrier per tree), and every thread solves the same 6 x 6 system from them, so the pose needs
- *                       no broadcast and every branch on it is uniform.  Flags and result are written at the end
+ *                       in turn: one barrier per tree; gn_block_sum of ss_gn.h), and every thread solves the same 6 x 6 system
+ *                       from them, so the pose needs no broadcast and every branch on it is uniform.  Flags and result are
+ *                       written at the end
  *
  * Every floating-point step is a single IEEE operation (-ffp-contract=off).  Every global write is a plain vector store.
  */
@@ -20,6 +21,7 @@
 #include <stdint.h>
 
 #include "ss_constants.h"
+#include "ss_gn.h"
 #include "ss_kernels.h"
 #include "ss_pose_steps.h"
 #include "ss_quad.h"
@@ -27,8 +29,8 @@
 namespace {
 
 static_assert(SSK_POSE_CHUNK == 1024, "k_pose_gather: one slot per thread and chunk, 16 waves");
-static_assert(SS_POSE_SLOTS == 256, "k_pose_solve: four waves, one group of 64 slots each");
-static_assert(SS_GUIDED_MAX_ROWS <= 64 * SS_POSE_SLOTS, "k_pose_solve: a thread's observations have one bit each in a 64-bit mask");
+static_assert(SS_GN_SLOTS == 256, "k_pose_solve: four waves, one group of 64 slots each");
+static_assert(SS_GUIDED_MAX_ROWS <= 64 * SS_GN_SLOTS, "k_pose_solve: a thread's observations have one bit each in a 64-bit mask");
 static_assert(sizeof(ss_pose_result) == 160, "thirteen doubles, fourteen integers, no padding");
 
 /* plane k of the observations of frame b */
@@ -45,7 +47,6 @@ __global__ __launch_bounds__(SSK_POSE_CHUNK) void k_pose_gather(ssk_pose_call a)
 {
     __shared__ int wave_n[SSK_POSE_CHUNK / 64];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, slots = a.slots;
-    const int lane = tid & 63, wave = tid >> 6;
     const gd_points_frame f = gd_points_frame_of(a.src, a.frame_error, a.np, a.nk, a.point_rows, a.rows, b);
     const int n_levels = min(max(a.n_levels, 1), SS_MAX_LEVELS);
     int base = 0;
@@ -63,18 +64,9 @@ __global__ __launch_bounds__(SSK_POSE_CHUNK) void k_pose_gather(ssk_pose_call a)
                 if (keep && a.p_skip && a.p_skip[(size_t)f.pb * a.point_rows + prow] != 0) keep = false;
             }
         }
-        const unsigned long long mask = __ballot(keep);
-        if (lane == 0) wave_n[wave] = __popcll(mask);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < SSK_POSE_CHUNK / 64; k++) {
-            const int n = wave_n[k];
-            before += k < wave ? n : 0;
-            total += n;
-        }
+        const gn_chunk ch = gn_chunk_compact<SSK_POSE_CHUNK>(keep, wave_n);
         if (keep) {
-            const int pos = base + before + __popcll(mask & ((1ull << lane) - 1ull)); /* pos <= i < slots */
+            const int pos = gn_chunk_pos(ch, base); /* pos <= i < slots */
             const ss_map_point *p = a.points + (size_t)f.pb * a.point_rows + prow;
             const ss_keypoint *kp = a.kp + (size_t)b * a.rows + krow;
             const float right = a.right ? a.right[(size_t)b * a.rows + krow] : 0.0f;
@@ -86,27 +78,18 @@ __global__ __launch_bounds__(SSK_POSE_CHUNK) void k_pose_gather(ssk_pose_call a)
         } else if (i < slots) {
             a.flags[o] = 2;
         }
-        base += total;
+        base += ch.total;
         __syncthreads(); /* wave_n is rewritten */
     }
     if (tid == 0) a.n_obs[b] = base;
 }
 
-/* a[l] += a[l + h], h = 32 .. 1: lane 0 ends with the group's sum */
-__device__ __forceinline__ double pose_wave_fold(double v)
-{
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_down(v, h);
-    return v;
-}
-
-/* P-B.  grid (frames), SS_POSE_SLOTS threads; the flag of every observation's slot and the result are written */
-__global__ __launch_bounds__(SS_POSE_SLOTS) void k_pose_solve(ssk_pose_call a)
+/* P-B.  grid (frames), SS_GN_SLOTS threads; the flag of every observation's slot and the result are written */
+__global__ __launch_bounds__(SS_GN_SLOTS) void k_pose_solve(ssk_pose_call a)
 {
     __shared__ double part[2][4][SS_POSE_SUMS];
     __shared__ int part_n[2][4];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, slots = a.slots;
-    const int lane = tid & 63, wave = tid >> 6;
     const gd_points_frame f = gd_points_frame_of(a.src, a.frame_error, a.np, a.nk, a.point_rows, a.rows, b);
     const int n = min(max(a.n_obs[b], 0), slots);
     const ss_pose_cam cam = ss_pose_cam_of(a.views[b], a.chi2_mono, a.chi2_stereo);
@@ -124,28 +107,18 @@ __global__ __launch_bounds__(SS_POSE_SLOTS) void k_pose_solve(ssk_pose_call a)
     for (int round = 0; state == 0 && round < a.n_rounds; round++) { /* everything the loops branch on is the same in every thread */
         const bool robust = round < a.robust_rounds;
         for (int it = 0; it < a.iterations; it++) {
-            double acc[SS_POSE_SUMS];
+            double sum[SS_POSE_SUMS]; /* this thread's partial sums, then the frame's */
 #pragma unroll
-            for (int s = 0; s < SS_POSE_SUMS; s++) acc[s] = 0.0;
+            for (int s = 0; s < SS_POSE_SUMS; s++) sum[s] = 0.0;
             int j = 0;
-            for (int k = tid; k < n; k += SS_POSE_SLOTS, j++) {
+            for (int k = tid; k < n; k += SS_GN_SLOTS, j++) {
                 if (!((active >> j) & 1ull)) continue;
                 double term[SS_POSE_SUMS];
                 if (!ss_pose_terms(pose_load_obs(a, b, k), cam, R, t, robust, term)) continue;
 #pragma unroll
-                for (int s = 0; s < SS_POSE_SUMS; s++) acc[s] = acc[s] + term[s];
+                for (int s = 0; s < SS_POSE_SUMS; s++) sum[s] = sum[s] + term[s];
             }
-#pragma unroll
-            for (int s = 0; s < SS_POSE_SUMS; s++) acc[s] = pose_wave_fold(acc[s]);
-            if (lane == 0) {
-#pragma unroll
-                for (int s = 0; s < SS_POSE_SUMS; s++) part[buf][wave][s] = acc[s];
-            }
-            __syncthreads();
-            double sum[SS_POSE_SUMS];
-#pragma unroll
-            for (int s = 0; s < SS_POSE_SUMS; s++) sum[s] = ss_pose_combine(part[buf][0][s], part[buf][1][s], part[buf][2][s], part[buf][3][s]);
-            buf ^= 1;
+            gn_block_sum(sum, part, &buf);
             bool small;
             const int rc = ss_pose_step(sum, a.lambda, a.step_eps, R, t, &small);
             if (rc != 0) {
@@ -159,7 +132,7 @@ __global__ __launch_bounds__(SS_POSE_SLOTS) void k_pose_solve(ssk_pose_call a)
         unsigned long long now = 0ull;
         double mine = 0.0;
         int mine_n = 0, j = 0;
-        for (int k = tid; k < n; k += SS_POSE_SLOTS, j++) {
+        for (int k = tid; k < n; k += SS_GN_SLOTS, j++) {
             const ss_pose_obs o = pose_load_obs(a, b, k);
             const double chi2 = ss_pose_chi2(o, cam, R, t);
             if (ss_pose_inlier(o, cam, chi2)) {
@@ -169,17 +142,11 @@ __global__ __launch_bounds__(SS_POSE_SLOTS) void k_pose_solve(ssk_pose_call a)
             }
         }
         active = now;
-        mine = pose_wave_fold(mine);
-#pragma unroll
-        for (int h = 32; h >= 1; h >>= 1) mine_n += __shfl_down(mine_n, h);
-        if (lane == 0) part[buf][wave][0] = mine, part_n[buf][wave] = mine_n;
-        __syncthreads();
-        cost = ss_pose_combine(part[buf][0][0], part[buf][1][0], part[buf][2][0], part[buf][3][0]);
-        n_in = (part_n[buf][0] + part_n[buf][1]) + (part_n[buf][2] + part_n[buf][3]);
-        buf ^= 1;
+        gn_block_sum(&mine, &mine_n, part, part_n, &buf);
+        cost = mine, n_in = mine_n;
         if (n_in < a.min_obs) state = 3;
     }
-    if (!ss_pose_all_finite(R, t)) {
+    if (!ss_gn_all_finite(R, t)) {
         state = 2;
 #pragma unroll
         for (int k = 0; k < 9; k++) R[k] = R0[k];
@@ -187,15 +154,12 @@ __global__ __launch_bounds__(SS_POSE_SLOTS) void k_pose_solve(ssk_pose_call a)
         for (int k = 0; k < 3; k++) t[k] = t0[k];
     }
     int n_stereo = 0, j = 0;
-    for (int k = tid; k < n; k += SS_POSE_SLOTS, j++) {
+    for (int k = tid; k < n; k += SS_GN_SLOTS, j++) {
         const int slot = a.slot_of[(size_t)b * slots + k];
         if (slot >= 0 && slot < slots) a.flags[(size_t)b * slots + slot] = ((active >> j) & 1ull) ? 0 : 1;
         n_stereo += pose_plane(a, 5, b)[k] > 0.0f ? 1 : 0;
     }
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) n_stereo += __shfl_down(n_stereo, h);
-    if (lane == 0) part_n[buf][wave] = n_stereo;
-    __syncthreads();
+    n_stereo = gn_block_sum(n_stereo, part_n, &buf);
     if (tid == 0) {
         ss_pose_result r;
 #pragma unroll
@@ -206,7 +170,7 @@ __global__ __launch_bounds__(SS_POSE_SLOTS) void k_pose_solve(ssk_pose_call a)
         r.state = state;
         r.status = f.status;
         r.n_obs = n;
-        r.n_stereo = (part_n[buf][0] + part_n[buf][1]) + (part_n[buf][2] + part_n[buf][3]);
+        r.n_stereo = n_stereo;
         r.n_inliers = n_in;
 #pragma unroll
         for (int k = 0; k < 8; k++) r.steps[k] = (int32_t)((steps >> (8 * k)) & 0xFFull);
@@ -219,4 +183,4 @@ __global__ __launch_bounds__(SS_POSE_SLOTS) void k_pose_solve(ssk_pose_call a)
 
 void ssk_pose_gather(hipStream_t s, const ssk_pose_call &g) { hipLaunchKernelGGL(k_pose_gather, dim3((unsigned)g.n_frames), dim3(SSK_POSE_CHUNK), 0, s, g); }
 
-void ssk_pose_solve(hipStream_t s, const ssk_pose_call &g) { hipLaunchKernelGGL(k_pose_solve, dim3((unsigned)g.n_frames), dim3(SS_POSE_SLOTS), 0, s, g); }
+void ssk_pose_solve(hipStream_t s, const ssk_pose_call &g) { hipLaunchKernelGGL(k_pose_solve, dim3((unsigned)g.n_frames), dim3(SS_GN_SLOTS), 0, s, g); }

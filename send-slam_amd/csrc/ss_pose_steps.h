@@ -1,7 +1,8 @@
 /*
  * ss_pose_steps.h -- the steps of the pose-only optimisation (the rule: include/sendslam_orb.h): the start
- * rotation, one observation's 26 terms, the tree of a sum, the damped 6 x 6 Cholesky solve, the exponential by fixed-length series,
- * the update and the chi-square.  The kernels (ss_pose.hip), the host twin ss_pose_opt_host (ss_api_search.cpp) and
+ * rotation, one observation's 26 terms, the unpacking of the 6 x 6 system, the exponential by fixed-length series, the update, the
+ * chi-square, and the whole frame on the host.  The tree of a sum, the damped Cholesky solve and the Huber weight are
+ * ss_gn_steps.h's.  The kernels (ss_pose.hip), the host twin ss_pose_opt_host (ss_api_search.cpp) and
  * tests/native/pose_steps_asan.cpp compile this text.
  *
  * All arithmetic is double.  Every step is one IEEE operation, left to right as written; every test is in its accepting form, so a
@@ -13,19 +14,11 @@
 #define SS_POSE_STEPS_H
 
 #include "../../include/sendslam_orb.h"
-#include "ss_float_steps.h" /* SS_HD, math.h */
+#include "ss_gn_steps.h"
 
-#if defined(__HIPCC__) || defined(__clang__)
-#define SS_POSE_UNROLL _Pragma("unroll")
-#else
-#define SS_POSE_UNROLL
-#endif
-
-#define SS_POSE_SLOTS 256 /* the partial sums of a tree: slot s adds the observations s, s + 256, ... */
 #define SS_POSE_SUMS 26   /* H00 H01 H02 H03 H04 H05 H11 H12 H13 H14 H15 H22 H23 H24 H25 H33 H35 H44 H45 H55 (H34 = 0), then g0 .. g5 */
 #define SS_POSE_SERIES 15 /* terms of each series of the exponential: the first one left out is below 2^-60 for q <= pi^2 */
 #define SS_POSE_PI2 0x1.3bd3cc9be45dep+3 /* the double next to pi^2 */
-#define SS_POSE_BEHIND 1e30              /* the chi-square of an observation with z not > 0 */
 
 /* ss_pose_inv_fact[n] is the double next to 1 / n!, n = 0 .. 2 * SS_POSE_SERIES + 1 (tests/pose_ref.py holds the same table) */
 #define SS_POSE_INV_FACT                                                                                                              \
@@ -74,8 +67,6 @@ SS_HD ss_pose_obs ss_pose_obs_of(float X, float Y, float Z, float u, float v, fl
 /* what the gather stores for the right coordinate of a keypoint row (right: the row's value, or absent) */
 SS_HD float ss_pose_stored_right(bool check_right, bool have_right, float right) { return (check_right && have_right && right > 0.0f) ? right : -1.0f; }
 
-SS_HD bool ss_pose_is_finite(double x) { return x - x == 0.0; }
-
 /* step 2: the rotation next to start[0 .. 8] (rows by Gram-Schmidt, the third as a cross product) and start[9 .. 11].  False when an
  * entry of the result is not finite: the pose is then the identity */
 SS_HD bool ss_pose_start(const double *start, double R[9], double t[3])
@@ -92,26 +83,8 @@ SS_HD bool ss_pose_start(const double *start, double R[9], double t[3])
     R[7] = a2 * c0 - a0 * c2;
     R[8] = a0 * c1 - a1 * c0;
     t[0] = start[9], t[1] = start[10], t[2] = start[11];
-    bool ok = true;
-    SS_POSE_UNROLL
-    for (int k = 0; k < 9; k++) ok = ok && ss_pose_is_finite(R[k]);
-    SS_POSE_UNROLL
-    for (int k = 0; k < 3; k++) ok = ok && ss_pose_is_finite(t[k]);
-    if (!ok) {
-        SS_POSE_UNROLL
-        for (int k = 0; k < 9; k++) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
-        t[0] = t[1] = t[2] = 0.0;
-    }
-    return ok;
-}
-
-SS_HD bool ss_pose_all_finite(const double R[9], const double t[3])
-{
-    bool ok = true;
-    SS_POSE_UNROLL
-    for (int k = 0; k < 9; k++) ok = ok && ss_pose_is_finite(R[k]);
-    SS_POSE_UNROLL
-    for (int k = 0; k < 3; k++) ok = ok && ss_pose_is_finite(t[k]);
+    const bool ok = ss_gn_all_finite(R, t);
+    if (!ok) ss_gn_identity(R, t);
     return ok;
 }
 
@@ -137,8 +110,7 @@ SS_HD bool ss_pose_terms(const ss_pose_obs &o, const ss_pose_cam &c, const doubl
     const double c0 = (1.0 + y * y * iz2) * c.fy, c1 = -x * y * iz2 * c.fy, c2 = -x * iz * c.fy, c4 = -iz * c.fy, c5 = y * iz2 * c.fy;
     if (!o.stereo) {
         const double e2 = o.w * (rx * rx + ry * ry);
-        const double d = c.delta_mono;
-        const double wq = (robust && e2 > d * d) ? o.w * d / sqrt(e2) : o.w;
+        const double wq = ss_gn_huber(robust, e2, c.delta_mono, o.w);
         const double wa0 = wq * a0, wa1 = wq * a1, wa2 = wq * a2, wa3 = wq * a3, wa5 = wq * a5;
         const double wc0 = wq * c0, wc1 = wq * c1, wc2 = wq * c2, wc4 = wq * c4, wc5 = wq * c5;
         term[0] = wa0 * a0 + wc0 * c0;
@@ -172,8 +144,7 @@ SS_HD bool ss_pose_terms(const ss_pose_obs &o, const ss_pose_cam &c, const doubl
     const double rr = o.ur - (up - c.bf * iz);
     const double d0 = a0 - c.bf * y * iz2, d1 = a1 + c.bf * x * iz2, d5 = a5 - c.bf * iz2;
     const double e2 = o.w * ((rx * rx + ry * ry) + rr * rr);
-    const double d = c.delta_stereo;
-    const double wq = (robust && e2 > d * d) ? o.w * d / sqrt(e2) : o.w;
+    const double wq = ss_gn_huber(robust, e2, c.delta_stereo, o.w);
     const double wa0 = wq * a0, wa1 = wq * a1, wa2 = wq * a2, wa3 = wq * a3, wa5 = wq * a5;
     const double wc0 = wq * c0, wc1 = wq * c1, wc2 = wq * c2, wc4 = wq * c4, wc5 = wq * c5;
     const double wd0 = wq * d0, wd1 = wq * d1, wd2 = wq * a2, wd3 = wq * a3, wd5 = wq * d5;
@@ -211,7 +182,7 @@ SS_HD double ss_pose_chi2(const ss_pose_obs &o, const ss_pose_cam &c, const doub
 {
     double x, y, z;
     ss_pose_transform(R, t, o, &x, &y, &z);
-    if (!(z > 0.0)) return SS_POSE_BEHIND;
+    if (!(z > 0.0)) return SS_GN_BEHIND;
     const double up = c.fx * x / z + c.cx;
     const double ex = o.u - up, ey = o.v - (c.fy * y / z + c.cy);
     if (!o.stereo) return o.w * (ex * ex + ey * ey);
@@ -222,21 +193,7 @@ SS_HD double ss_pose_chi2(const ss_pose_obs &o, const ss_pose_cam &c, const doub
 /* an outlier iff not chi2 <= th */
 SS_HD bool ss_pose_inlier(const ss_pose_obs &o, const ss_pose_cam &c, double chi2) { return chi2 <= (o.stereo ? c.chi2_stereo : c.chi2_mono); }
 
-/* the four group results of a tree */
-SS_HD double ss_pose_combine(double r0, double r1, double r2, double r3) { return (r0 + r1) + (r2 + r3); }
-
-/* a tree on the host: the SS_POSE_SLOTS partial sums (overwritten) -> the sum.  Each group of 64 consecutive slots is folded by
- * halving, a[l] += a[l + h] for h = 32 .. 1; the kernel does the same through cross-lane moves */
-SS_HD double ss_pose_tree(double a[SS_POSE_SLOTS])
-{
-    for (int g = 0; g < SS_POSE_SLOTS; g += 64)
-        for (int h = 32; h >= 1; h >>= 1)
-            for (int l = 0; l < h; l++) a[g + l] = a[g + l] + a[g + l + h];
-    return ss_pose_combine(a[0], a[64], a[128], a[192]);
-}
-
-/* The solve of a step: the 26 sums -> delta.  H symmetric from its upper triangle, H_aa += lambda * (1 + H_aa), g negated, Cholesky
- * and the two triangular solves.  False when a pivot is not > 0 */
+/* The solve of a step: the 26 sums -> delta.  H_34 is the structural 0 */
 SS_HD bool ss_pose_solve(const double sum[SS_POSE_SUMS], double lambda, double delta[6])
 {
     double H[6][6];
@@ -246,47 +203,7 @@ SS_HD bool ss_pose_solve(const double sum[SS_POSE_SUMS], double lambda, double d
     H[3][3] = sum[15], H[3][4] = 0.0, H[3][5] = sum[16];
     H[4][4] = sum[17], H[4][5] = sum[18];
     H[5][5] = sum[19];
-    SS_POSE_UNROLL
-    for (int a = 1; a < 6; a++) {
-        SS_POSE_UNROLL
-        for (int b = 0; b < a; b++) H[a][b] = H[b][a];
-    }
-    SS_POSE_UNROLL
-    for (int a = 0; a < 6; a++) {
-        H[a][a] = H[a][a] + lambda * (1.0 + H[a][a]);
-        delta[a] = -sum[20 + a];
-    }
-    bool ok = true;
-    SS_POSE_UNROLL
-    for (int j = 0; j < 6; j++) {
-        double s = H[j][j];
-        SS_POSE_UNROLL
-        for (int k = 0; k < j; k++) s = s - H[j][k] * H[j][k];
-        ok = ok && s > 0.0;
-        H[j][j] = sqrt(s);
-        SS_POSE_UNROLL
-        for (int i = j + 1; i < 6; i++) {
-            double v = H[i][j];
-            SS_POSE_UNROLL
-            for (int k = 0; k < j; k++) v = v - H[i][k] * H[j][k];
-            H[i][j] = v / H[j][j];
-        }
-    }
-    SS_POSE_UNROLL
-    for (int i = 0; i < 6; i++) {
-        double v = delta[i];
-        SS_POSE_UNROLL
-        for (int k = 0; k < i; k++) v = v - H[i][k] * delta[k];
-        delta[i] = v / H[i][i];
-    }
-    SS_POSE_UNROLL
-    for (int i = 5; i >= 0; i--) {
-        double v = delta[i];
-        SS_POSE_UNROLL
-        for (int k = i + 1; k < 6; k++) v = v - H[k][i] * delta[k];
-        delta[i] = v / H[i][i];
-    }
-    return ok;
+    return ss_gn_solve<6>(H, sum + 20, lambda, delta);
 }
 
 /* The exponential of delta = (omega, upsilon): dR = I + A.W + B.W^2, dt = (I + B.W + C.W^2).upsilon with A = sum (-q)^k / (2k+1)!,
@@ -301,7 +218,7 @@ SS_HD bool ss_pose_exp(const double delta[6], double dR[9], double dt[3])
     if (q > SS_POSE_PI2) return false; /* a NaN q passes: the pose is then not finite, which ends the frame in state 2 */
     const double mq = -q;
     double A = f[2 * SS_POSE_SERIES - 1], B = f[2 * SS_POSE_SERIES], C = f[2 * SS_POSE_SERIES + 1];
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int k = SS_POSE_SERIES - 2; k >= 0; k--) {
         A = A * mq + f[2 * k + 1];
         B = B * mq + f[2 * k + 2];
@@ -330,16 +247,11 @@ SS_HD bool ss_pose_exp(const double delta[6], double dR[9], double dt[3])
 /* R <- dR.R, t <- dR.t + dt, each entry ((a*b + c*d) + e*f) [+ g] */
 SS_HD void ss_pose_update(const double dR[9], const double dt[3], double R[9], double t[3])
 {
-    double Rn[9], tn[3];
-    SS_POSE_UNROLL
-    for (int i = 0; i < 3; i++) {
-        SS_POSE_UNROLL
-        for (int j = 0; j < 3; j++) Rn[3 * i + j] = (dR[3 * i] * R[j] + dR[3 * i + 1] * R[3 + j]) + dR[3 * i + 2] * R[6 + j];
-        tn[i] = ((dR[3 * i] * t[0] + dR[3 * i + 1] * t[1]) + dR[3 * i + 2] * t[2]) + dt[i];
-    }
-    SS_POSE_UNROLL
-    for (int k = 0; k < 9; k++) R[k] = Rn[k];
-    SS_POSE_UNROLL
+    double tn[3];
+    SS_GN_UNROLL
+    for (int i = 0; i < 3; i++) tn[i] = ((dR[3 * i] * t[0] + dR[3 * i + 1] * t[1]) + dR[3 * i + 2] * t[2]) + dt[i];
+    ss_gn_rotate(dR, R);
+    SS_GN_UNROLL
     for (int k = 0; k < 3; k++) t[k] = tn[k];
 }
 
@@ -353,10 +265,75 @@ SS_HD int ss_pose_step(const double sum[SS_POSE_SUMS], double lambda, double ste
     if (!ss_pose_exp(delta, dR, dt)) return 4;
     ss_pose_update(dR, dt, R, t);
     bool all = true;
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int a = 0; a < 6; a++) all = all && fabs(delta[a]) < step_eps;
     *small = all;
     return 0;
+}
+
+/* The whole frame on the host the way the kernel runs it: obs[0 .. n) in numbering order; active: n bytes, 1 = inlier on return;
+ * slot: (SS_POSE_SUMS + 1) * SS_GN_SLOTS doubles of scratch.  Every field of *out is written; its status is 0 */
+static inline void ss_pose_frame_host(const ss_pose_obs *obs, int n, const ss_pose_cam &cam, const double *start, const ss_pose_opt_params &p,
+                                      uint8_t *active, double *slot, ss_pose_result *out)
+{
+    double R[9], t[3], R0[9], t0[3];
+    const bool start_ok = ss_pose_start(start, R, t);
+    for (int k = 0; k < 9; k++) R0[k] = R[k];
+    for (int k = 0; k < 3; k++) t0[k] = t[k];
+    for (int k = 0; k < n; k++) active[k] = 1;
+    int state = !start_ok ? 2 : n < p.min_obs ? 1 : 0, n_in = n, n_stereo = 0;
+    for (int k = 0; k < 8; k++) out->steps[k] = 0;
+    double cost = 0.0;
+    for (int round = 0; state == 0 && round < p.n_rounds; round++) {
+        const bool robust = round < p.robust_rounds;
+        for (int it = 0; it < p.iterations; it++) {
+            for (int k = 0; k < SS_POSE_SUMS * SS_GN_SLOTS; k++) slot[k] = 0.0;
+            for (int k = 0; k < n; k++) {
+                double term[SS_POSE_SUMS];
+                if (!active[k] || !ss_pose_terms(obs[k], cam, R, t, robust, term)) continue;
+                for (int s = 0; s < SS_POSE_SUMS; s++) {
+                    double &a = slot[(size_t)s * SS_GN_SLOTS + k % SS_GN_SLOTS];
+                    a = a + term[s];
+                }
+            }
+            double sum[SS_POSE_SUMS];
+            for (int s = 0; s < SS_POSE_SUMS; s++) sum[s] = ss_gn_tree(&slot[(size_t)s * SS_GN_SLOTS]);
+            bool small;
+            const int rc = ss_pose_step(sum, p.lambda, p.step_eps, R, t, &small);
+            if (rc != 0) {
+                state = rc;
+                break;
+            }
+            out->steps[round]++;
+            if (small) break;
+        }
+        if (state != 0) break;
+        /* step 4 */
+        double *c = &slot[(size_t)SS_POSE_SUMS * SS_GN_SLOTS];
+        for (int k = 0; k < SS_GN_SLOTS; k++) c[k] = 0.0;
+        n_in = 0;
+        for (int k = 0; k < n; k++) {
+            const double chi2 = ss_pose_chi2(obs[k], cam, R, t);
+            active[k] = ss_pose_inlier(obs[k], cam, chi2) ? 1 : 0;
+            if (!active[k]) continue;
+            c[k % SS_GN_SLOTS] = c[k % SS_GN_SLOTS] + chi2;
+            n_in++;
+        }
+        cost = ss_gn_tree(c);
+        if (n_in < p.min_obs) state = 3;
+    }
+    if (!ss_gn_all_finite(R, t)) {
+        state = 2;
+        for (int k = 0; k < 9; k++) R[k] = R0[k];
+        for (int k = 0; k < 3; k++) t[k] = t0[k];
+    }
+    for (int k = 0; k < n; k++) n_stereo += obs[k].stereo ? 1 : 0;
+    for (int k = 0; k < 9; k++) out->rcw[k] = R[k];
+    for (int k = 0; k < 3; k++) out->tcw[k] = t[k];
+    out->cost = cost;
+    out->state = state, out->status = 0;
+    out->n_obs = n, out->n_stereo = n_stereo, out->n_inliers = n_in;
+    out->reserved = 0;
 }
 
 #endif

@@ -4,7 +4,7 @@
  * ss_sim3_steps.h, which the host twins compile too.
  *
  *   S-A  k_sim3_gather  one workgroup per pair walks the query rows in chunks of SSK_SIM3_CHUNK in ascending order: ballot and
- *                       prefix sums number the correspondences (k_tri_compact's compaction), so the numbering is the rule's
+ *                       prefix sums number the correspondences (gn_chunk_compact of ss_gn.h), so the numbering is the rule's
  *                       whatever the schedule.  A kept row writes its twelve floats into twelve planes and every row the number of
  *                       its correspondence
  *   S-B  k_sim3_model   one lane per pair and hypothesis: the draws, the model in double with the 4 x 4 arrays in registers, one
@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "ss_constants.h"
+#include "ss_gn.h"
 #include "ss_kernels.h"
 #include "ss_sim3_steps.h"
 #include "ss_quad.h"
@@ -60,7 +61,6 @@ __global__ __launch_bounds__(SSK_SIM3_CHUNK) void k_sim3_gather(ssk_sim3_call a)
 {
     __shared__ int wave_n[SSK_SIM3_CHUNK / 64];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, rows = a.rows;
-    const int lane = tid & 63, wave = tid >> 6;
     const gd_frame f = gd_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
     const int n_levels = min(max(a.n_levels, 1), SS_MAX_LEVELS);
     const int t = max(f.t, 0);
@@ -81,19 +81,10 @@ __global__ __launch_bounds__(SSK_SIM3_CHUNK) void k_sim3_gather(ssk_sim3_call a)
                 if (keep && a.t_skip && a.t_skip[oj] != 0) keep = false;
             }
         }
-        const unsigned long long mask = __ballot(keep);
-        if (lane == 0) wave_n[wave] = __popcll(mask);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < SSK_SIM3_CHUNK / 64; k++) {
-            const int n = wave_n[k];
-            before += k < wave ? n : 0;
-            total += n;
-        }
+        const gn_chunk ch = gn_chunk_compact<SSK_SIM3_CHUNK>(keep, wave_n);
         int pos = -1;
         if (keep) {
-            pos = base + before + __popcll(mask & ((1ull << lane) - 1ull)); /* pos <= i < rows */
+            pos = gn_chunk_pos(ch, base); /* pos <= i < rows */
             const ss_map_point *p1 = a.q_xyz + o, *p2 = a.t_xyz + (size_t)t * rows + j;
             const ss_sim3_corr c = ss_sim3_corr_of(*v1, *v2, p1->x, p1->y, p1->z, p2->x, p2->y, p2->z, a.chi2, a.scale[o1], a.scale[o2]);
             sim3_plane(a, 0, b)[pos] = c.x1[0], sim3_plane(a, 1, b)[pos] = c.x1[1], sim3_plane(a, 2, b)[pos] = c.x1[2];
@@ -103,7 +94,7 @@ __global__ __launch_bounds__(SSK_SIM3_CHUNK) void k_sim3_gather(ssk_sim3_call a)
             sim3_plane(a, 10, b)[pos] = c.max1, sim3_plane(a, 11, b)[pos] = c.max2;
         }
         if (i < rows) a.corr_of_row[o] = pos;
-        base += total;
+        base += ch.total;
         __syncthreads(); /* wave_n is rewritten */
     }
     if (tid == 0) a.n_corr[b] = base;

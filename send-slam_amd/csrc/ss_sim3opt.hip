@@ -4,14 +4,14 @@
  * refinement").  Every step of the arithmetic is the text of ss_sim3opt_steps.h, which the host twin compiles too.
  *
  *   O-A  k_sim3opt_gather  one workgroup per pair walks the query rows in chunks of SSK_SIM3OPT_CHUNK in ascending order: ballot and
- *                          prefix sums number the correspondences (k_sim3_gather's compaction).  A kept row writes its twelve floats
+ *                          prefix sums number the correspondences (gn_chunk_compact of ss_gn.h).  A kept row writes its twelve floats
  *                          (X1 and X2 in float32 by the RANSAC's text, both keypoints, both scales) into twelve planes and its query
  *                          row; every other row gets its flag 2 here.  A pair without a usable start keeps nothing
- *   O-B  k_sim3opt_solve   one workgroup of SS_POSE_SLOTS threads per pair holds both rounds (k_pose_solve's shape).  Thread s owns
+ *   O-B  k_sim3opt_solve   one workgroup of SS_GN_SLOTS threads per pair holds both rounds (its own loop on ss_gn.h).  Thread s owns
  *                          the correspondences s, s + 256, ...: it re-reads their planes every step, adds the e12 terms and then the
  *                          e21 terms into its 35 partial sums in registers (one edge's rows are live at a time) and keeps its
  *                          correspondences' inlier bits in one 64-bit mask.  A wave folds by halving through cross-lane moves, the
- *                          four wave results go through LDS (two buffers in turn), and every thread solves the same system, so the
+ *                          four wave results go through LDS (gn_block_sum of ss_gn.h), and every thread solves the same system, so the
  *                          model needs no broadcast and every branch on it is uniform
  *   O-C  k_sim3_marks      one workgroup per pair: the skip bytes of both searches of SearchBySim3
  *   O-D  k_sim3_mutual     one workgroup per pair: the agreement test of the two searches' results
@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "ss_constants.h"
+#include "ss_gn.h"
 #include "ss_kernels.h"
 #include "ss_sim3opt_steps.h"
 #include "ss_quad.h"
@@ -30,8 +31,8 @@
 namespace {
 
 static_assert(SSK_SIM3OPT_CHUNK == 1024, "k_sim3opt_gather: one row per thread and chunk, 16 waves");
-static_assert(SS_POSE_SLOTS == 256, "k_sim3opt_solve: four waves, one group of 64 slots each");
-static_assert(SS_GUIDED_MAX_ROWS <= 64 * SS_POSE_SLOTS, "k_sim3opt_solve: a thread's correspondences have one bit each in a 64-bit mask");
+static_assert(SS_GN_SLOTS == 256, "k_sim3opt_solve: four waves, one group of 64 slots each");
+static_assert(SS_GUIDED_MAX_ROWS <= 64 * SS_GN_SLOTS, "k_sim3opt_solve: a thread's correspondences have one bit each in a 64-bit mask");
 static_assert(sizeof(ss_sim3_opt_result) == 272, "fourteen doubles, eight integers, one ss_sim3_result, no padding");
 static_assert(sizeof(ss_sim3_opt_params) == 64 && sizeof(ss_sim3_mutual_summary) == 8, "the documented sizes");
 
@@ -54,7 +55,6 @@ __global__ __launch_bounds__(SSK_SIM3OPT_CHUNK) void k_sim3opt_gather(ssk_sim3op
 {
     __shared__ int wave_n[SSK_SIM3OPT_CHUNK / 64];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, rows = a.rows;
-    const int lane = tid & 63, wave = tid >> 6;
     const gd_frame f = gd_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
     const int n_levels = min(max(a.n_levels, 1), SS_MAX_LEVELS);
     const int t = max(f.t, 0);
@@ -76,18 +76,9 @@ __global__ __launch_bounds__(SSK_SIM3OPT_CHUNK) void k_sim3opt_gather(ssk_sim3op
                 if (keep && a.t_skip && a.t_skip[oj] != 0) keep = false;
             }
         }
-        const unsigned long long mask = __ballot(keep);
-        if (lane == 0) wave_n[wave] = __popcll(mask);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < SSK_SIM3OPT_CHUNK / 64; k++) {
-            const int n = wave_n[k];
-            before += k < wave ? n : 0;
-            total += n;
-        }
+        const gn_chunk ch = gn_chunk_compact<SSK_SIM3OPT_CHUNK>(keep, wave_n);
         if (keep) {
-            const int pos = base + before + __popcll(mask & ((1ull << lane) - 1ull)); /* pos <= i < rows */
+            const int pos = gn_chunk_pos(ch, base); /* pos <= i < rows */
             const size_t oj = (size_t)t * rows + j;
             const ss_map_point *p1 = a.q_xyz + o, *p2 = a.t_xyz + oj;
             float x1[3], x2[3];
@@ -102,27 +93,18 @@ __global__ __launch_bounds__(SSK_SIM3OPT_CHUNK) void k_sim3opt_gather(ssk_sim3op
         } else if (i < rows) {
             a.flags[o] = 2;
         }
-        base += total;
+        base += ch.total;
         __syncthreads(); /* wave_n is rewritten */
     }
     if (tid == 0) a.n_corr[b] = base;
 }
 
-/* a[l] += a[l + h], h = 32 .. 1: lane 0 ends with the group's sum */
-__device__ __forceinline__ double opt_wave_fold(double v)
-{
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_down(v, h);
-    return v;
-}
-
-/* O-B.  grid (pairs), SS_POSE_SLOTS threads; the flag of every correspondence's row and the result are written */
-__global__ __launch_bounds__(SS_POSE_SLOTS) void k_sim3opt_solve(ssk_sim3opt_call a)
+/* O-B.  grid (pairs), SS_GN_SLOTS threads; the flag of every correspondence's row and the result are written */
+__global__ __launch_bounds__(SS_GN_SLOTS) void k_sim3opt_solve(ssk_sim3opt_call a)
 {
     __shared__ double part[2][4][SS_SIM3OPT_SUMS];
     __shared__ int part_n[2][4];
     const int b = (int)blockIdx.x, tid = (int)threadIdx.x, rows = a.rows;
-    const int lane = tid & 63, wave = tid >> 6;
     const gd_frame f = gd_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
     const int n = min(max(a.n_corr[b], 0), rows);
     const ss_sim3opt_cams cam = ss_sim3opt_cams_of(a.views1[b], a.views2[b], a.p.chi2);
@@ -145,28 +127,18 @@ __global__ __launch_bounds__(SS_POSE_SLOTS) void k_sim3opt_solve(ssk_sim3opt_cal
         const bool robust = round == 0;
         const int iterations = round == 0 ? a.p.iterations0 : n_removed > 0 ? a.p.iterations_more : a.p.iterations_same;
         for (int it = 0; it < iterations; it++) {
-            double acc[SS_SIM3OPT_SUMS];
+            double sum[SS_SIM3OPT_SUMS]; /* this thread's partial sums, then the pair's */
 #pragma unroll
-            for (int q = 0; q < SS_SIM3OPT_SUMS; q++) acc[q] = 0.0;
+            for (int q = 0; q < SS_SIM3OPT_SUMS; q++) sum[q] = 0.0;
             int j = 0;
-            for (int k = tid; k < n; k += SS_POSE_SLOTS, j++) {
+            for (int k = tid; k < n; k += SS_GN_SLOTS, j++) {
                 if (!((active >> j) & 1ull)) continue;
                 const ss_sim3opt_corr c = opt_load(a, b, k);
                 ss_sim3opt_edge e;
-                if (ss_sim3opt_edge12(c, cam, R, t, s, e)) ss_sim3opt_add(e, cam, robust, acc);
-                if (ss_sim3opt_edge21(c, cam, R, t, s, e)) ss_sim3opt_add(e, cam, robust, acc);
+                if (ss_sim3opt_edge12(c, cam, R, t, s, e)) ss_sim3opt_add(e, cam, robust, sum);
+                if (ss_sim3opt_edge21(c, cam, R, t, s, e)) ss_sim3opt_add(e, cam, robust, sum);
             }
-#pragma unroll
-            for (int q = 0; q < SS_SIM3OPT_SUMS; q++) acc[q] = opt_wave_fold(acc[q]);
-            if (lane == 0) {
-#pragma unroll
-                for (int q = 0; q < SS_SIM3OPT_SUMS; q++) part[buf][wave][q] = acc[q];
-            }
-            __syncthreads();
-            double sum[SS_SIM3OPT_SUMS];
-#pragma unroll
-            for (int q = 0; q < SS_SIM3OPT_SUMS; q++) sum[q] = ss_pose_combine(part[buf][0][q], part[buf][1][q], part[buf][2][q], part[buf][3][q]);
-            buf ^= 1;
+            gn_block_sum(sum, part, &buf);
             bool small;
             const int rc = ss_sim3opt_step(sum, fix, a.p.lambda, a.p.step_eps, R, t, &s, &small);
             if (rc != 0) {
@@ -181,7 +153,7 @@ __global__ __launch_bounds__(SS_POSE_SLOTS) void k_sim3opt_solve(ssk_sim3opt_cal
         unsigned long long now = 0ull;
         double mine = 0.0;
         int mine_n = 0, j = 0;
-        for (int k = tid; k < n; k += SS_POSE_SLOTS, j++) {
+        for (int k = tid; k < n; k += SS_GN_SLOTS, j++) {
             if (!((active >> j) & 1ull)) continue; /* a removed correspondence stays removed */
             const ss_sim3opt_corr c = opt_load(a, b, k);
             const double c12 = ss_sim3opt_chi2_12(c, cam, R, t, s), c21 = ss_sim3opt_chi2_21(c, cam, R, t, s);
@@ -192,21 +164,15 @@ __global__ __launch_bounds__(SS_POSE_SLOTS) void k_sim3opt_solve(ssk_sim3opt_cal
             }
         }
         active = now;
-        mine = opt_wave_fold(mine);
-#pragma unroll
-        for (int h = 32; h >= 1; h >>= 1) mine_n += __shfl_down(mine_n, h);
-        if (lane == 0) part[buf][wave][0] = mine, part_n[buf][wave] = mine_n;
-        __syncthreads();
-        cost = ss_pose_combine(part[buf][0][0], part[buf][1][0], part[buf][2][0], part[buf][3][0]);
-        n_in = (part_n[buf][0] + part_n[buf][1]) + (part_n[buf][2] + part_n[buf][3]);
-        buf ^= 1;
+        gn_block_sum(&mine, &mine_n, part, part_n, &buf);
+        cost = mine, n_in = mine_n;
         if (round == 0) {
             n_removed = n - n_in;
             if (n_in < a.p.min_inliers) state = 3;
         }
     }
     int j = 0;
-    for (int k = tid; k < n; k += SS_POSE_SLOTS, j++) {
+    for (int k = tid; k < n; k += SS_GN_SLOTS, j++) {
         const int row = a.row_of[(size_t)b * rows + k];
         if (row >= 0 && row < rows) a.flags[(size_t)b * rows + row] = ((active >> j) & 1ull) ? 0 : 1;
     }
@@ -271,8 +237,7 @@ __global__ __launch_bounds__(256) void k_sim3_mutual(ssk_sim3_marks_call a)
         }
         a.idx_out[o] = out;
     }
-#pragma unroll
-    for (int h = 32; h >= 1; h >>= 1) n_prior += __shfl_down(n_prior, h), n_new += __shfl_down(n_new, h);
+    n_prior = gn_wave_fold(n_prior), n_new = gn_wave_fold(n_new);
     if (lane == 0) cnt[0][wave] = n_prior, cnt[1][wave] = n_new;
     __syncthreads();
     if (tid == 0) {
@@ -287,7 +252,7 @@ __global__ __launch_bounds__(256) void k_sim3_mutual(ssk_sim3_marks_call a)
 
 void ssk_sim3opt_gather(hipStream_t s, const ssk_sim3opt_call &g) { hipLaunchKernelGGL(k_sim3opt_gather, dim3((unsigned)g.n_frames), dim3(SSK_SIM3OPT_CHUNK), 0, s, g); }
 
-void ssk_sim3opt_solve(hipStream_t s, const ssk_sim3opt_call &g) { hipLaunchKernelGGL(k_sim3opt_solve, dim3((unsigned)g.n_frames), dim3(SS_POSE_SLOTS), 0, s, g); }
+void ssk_sim3opt_solve(hipStream_t s, const ssk_sim3opt_call &g) { hipLaunchKernelGGL(k_sim3opt_solve, dim3((unsigned)g.n_frames), dim3(SS_GN_SLOTS), 0, s, g); }
 
 void ssk_sim3_marks(hipStream_t s, const ssk_sim3_marks_call &g) { hipLaunchKernelGGL(k_sim3_marks, dim3((unsigned)g.n_frames), dim3(256), 0, s, g); }
 

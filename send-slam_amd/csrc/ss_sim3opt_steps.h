@@ -3,7 +3,8 @@
  * correspondence's twelve floats widened, the start, the rows of both edges, the 35 terms of an edge added into the sums, the
  * damped 6 x 6 or 7 x 7 Cholesky solve, the retraction, both chi-squares, the result's floats, and the whole pair on the host.  The
  * kernels (ss_sim3opt.hip), the host twin ss_sim3_opt_host (ss_api_search.cpp) and tests/native/sim3opt_steps_asan.cpp compile this
- * text.  The start rotation, the rotation's series, the tree of a sum and the table of 1 / n! are ss_pose_steps.h's.
+ * text.  The start rotation, the rotation's series and the table of 1 / n! are ss_pose_steps.h's; the tree of a sum, the damped
+ * Cholesky solve and the Huber weight are ss_gn_steps.h's.
  *
  * All arithmetic is double.  Every step is one IEEE operation, left to right as written; every test is in its accepting form, so a
  * NaN fails it (but for the step-size test of ss_pose_exp).  Compile with -ffp-contract=off.  Arrays are indexed by constants only
@@ -41,7 +42,7 @@ struct ss_sim3opt_corr {
 SS_HD ss_sim3opt_corr ss_sim3opt_corr_of(const float x1[3], const float x2[3], float u1, float v1, float u2, float v2, float s1, float s2)
 {
     ss_sim3opt_corr c;
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int k = 0; k < 3; k++) c.x1[k] = (double)x1[k], c.x2[k] = (double)x2[k];
     c.u1 = (double)u1, c.v1 = (double)v1, c.u2 = (double)u2, c.v2 = (double)v2;
     const double a = (double)s1, b = (double)s2;
@@ -55,18 +56,16 @@ SS_HD ss_sim3opt_corr ss_sim3opt_corr_of(const float x1[3], const float x2[3], f
 SS_HD bool ss_sim3opt_start(const ss_sim3_result &m, bool fix_scale, double R[9], double t[3], double *s)
 {
     double st[12];
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int k = 0; k < 9; k++) st[k] = (double)m.sr12[k];
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int k = 0; k < 3; k++) st[9 + k] = (double)m.t12[k];
     const double n0 = sqrt((st[0] * st[0] + st[1] * st[1]) + st[2] * st[2]);
     bool ok = ss_pose_start(st, R, t);
     *s = fix_scale ? 1.0 : n0;
-    ok = ok && *s > 0.0 && ss_pose_is_finite(*s);
+    ok = ok && *s > 0.0 && ss_gn_is_finite(*s);
     if (!ok) {
-        SS_POSE_UNROLL
-        for (int k = 0; k < 9; k++) R[k] = (k % 4 == 0) ? 1.0 : 0.0;
-        t[0] = t[1] = t[2] = 0.0;
+        ss_gn_identity(R, t);
         *s = 1.0;
     }
     return ok;
@@ -89,9 +88,9 @@ SS_HD void ss_sim3opt_map12(const ss_sim3opt_corr &c, const double R[9], const d
 SS_HD void ss_sim3opt_map21(const ss_sim3opt_corr &c, const double R[9], const double t[3], double s, double M[9], double *x, double *y, double *z)
 {
     const double is = 1.0 / s;
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int i = 0; i < 3; i++) {
-        SS_POSE_UNROLL
+        SS_GN_UNROLL
         for (int j = 0; j < 3; j++) M[3 * i + j] = is * R[3 * j + i];
     }
     const double d0 = c.x1[0] - t[0], d1 = c.x1[1] - t[1], d2 = c.x1[2] - t[2];
@@ -133,7 +132,7 @@ SS_HD bool ss_sim3opt_edge21(const ss_sim3opt_corr &c, const ss_sim3opt_cams &k,
     const double px = k.fx2 * iz, pxz = k.fx2 * x * iz2, py = k.fy2 * iz, pyz = k.fy2 * y * iz2;
     const double a = c.x1[0], b = c.x1[1], g = c.x1[2];
     double D[3][7];
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int i = 0; i < 3; i++) {
         const double m0 = M[3 * i], m1 = M[3 * i + 1], m2 = M[3 * i + 2];
         D[i][0] = m1 * g - m2 * b;
@@ -142,7 +141,7 @@ SS_HD bool ss_sim3opt_edge21(const ss_sim3opt_corr &c, const ss_sim3opt_cams &k,
         D[i][3] = -m0, D[i][4] = -m1, D[i][5] = -m2;
         D[i][6] = -((m0 * a + m1 * b) + m2 * g);
     }
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int q = 0; q < 7; q++) {
         e.J0[q] = pxz * D[2][q] - px * D[0][q];
         e.J1[q] = pyz * D[2][q] - py * D[1][q];
@@ -150,17 +149,16 @@ SS_HD bool ss_sim3opt_edge21(const ss_sim3opt_corr &c, const ss_sim3opt_cams &k,
     return true;
 }
 
-/* step 3: the 35 terms of one edge, each added to its sum: acc = acc + term.  The Huber weight is the pose rule's */
+/* step 3: the 35 terms of one edge, each added to its sum: acc = acc + term */
 SS_HD void ss_sim3opt_add(const ss_sim3opt_edge &e, const ss_sim3opt_cams &k, bool robust, double acc[SS_SIM3OPT_SUMS])
 {
     const double e2 = e.w * (e.rx * e.rx + e.ry * e.ry);
-    const double d = k.delta;
-    const double wq = (robust && e2 > d * d) ? e.w * d / sqrt(e2) : e.w;
+    const double wq = ss_gn_huber(robust, e2, k.delta, e.w);
     int n = 0;
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int a = 0; a < 7; a++) {
         const double w0 = wq * e.J0[a], w1 = wq * e.J1[a];
-        SS_POSE_UNROLL
+        SS_GN_UNROLL
         for (int b = a; b < 7; b++, n++) acc[n] = acc[n] + (w0 * e.J0[b] + w1 * e.J1[b]);
         acc[28 + a] = acc[28 + a] + (w0 * e.rx + w1 * e.ry);
     }
@@ -169,51 +167,16 @@ SS_HD void ss_sim3opt_add(const ss_sim3opt_edge &e, const ss_sim3opt_cams &k, bo
 /* the sum of H_ab, a <= b */
 SS_HD constexpr int ss_sim3opt_h(int a, int b) { return a * 7 - a * (a - 1) / 2 + (b - a); }
 
-/* The solve of a step over the leading N x N (6 with fix_scale, else 7): ss_pose_solve's text */
+/* The solve of a step over the leading N x N (6 with fix_scale, else 7) */
 template <int N> SS_HD bool ss_sim3opt_solve(const double sum[SS_SIM3OPT_SUMS], double lambda, double delta[7])
 {
     double H[N][N];
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int a = 0; a < N; a++) {
-        SS_POSE_UNROLL
-        for (int b = a; b < N; b++) H[a][b] = H[b][a] = sum[ss_sim3opt_h(a, b)];
+        SS_GN_UNROLL
+        for (int b = a; b < N; b++) H[a][b] = sum[ss_sim3opt_h(a, b)];
     }
-    SS_POSE_UNROLL
-    for (int a = 0; a < N; a++) {
-        H[a][a] = H[a][a] + lambda * (1.0 + H[a][a]);
-        delta[a] = -sum[28 + a];
-    }
-    bool ok = true;
-    SS_POSE_UNROLL
-    for (int j = 0; j < N; j++) {
-        double s = H[j][j];
-        SS_POSE_UNROLL
-        for (int k = 0; k < j; k++) s = s - H[j][k] * H[j][k];
-        ok = ok && s > 0.0;
-        H[j][j] = sqrt(s);
-        SS_POSE_UNROLL
-        for (int i = j + 1; i < N; i++) {
-            double v = H[i][j];
-            SS_POSE_UNROLL
-            for (int k = 0; k < j; k++) v = v - H[i][k] * H[j][k];
-            H[i][j] = v / H[j][j];
-        }
-    }
-    SS_POSE_UNROLL
-    for (int i = 0; i < N; i++) {
-        double v = delta[i];
-        SS_POSE_UNROLL
-        for (int k = 0; k < i; k++) v = v - H[i][k] * delta[k];
-        delta[i] = v / H[i][i];
-    }
-    SS_POSE_UNROLL
-    for (int i = N - 1; i >= 0; i--) {
-        double v = delta[i];
-        SS_POSE_UNROLL
-        for (int k = i + 1; k < N; k++) v = v - H[k][i] * delta[k];
-        delta[i] = v / H[i][i];
-    }
-    return ok;
+    return ss_gn_solve<N>(H, sum + 28, lambda, delta);
 }
 
 /* ds = sum sigma^k / k!, k < SS_SIM3OPT_SERIES, a Horner sum from the last term */
@@ -221,7 +184,7 @@ SS_HD double ss_sim3opt_exp_scale(double sigma)
 {
     const double f[2 * SS_POSE_SERIES + 2] = SS_POSE_INV_FACT;
     double v = f[SS_SIM3OPT_SERIES - 1];
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int k = SS_SIM3OPT_SERIES - 2; k >= 0; k--) v = v * sigma + f[k];
     return v;
 }
@@ -237,32 +200,27 @@ SS_HD int ss_sim3opt_step(const double sum[SS_SIM3OPT_SUMS], bool fix_scale, dou
     if (!ss_pose_exp(delta, dR, dt)) return 4;
     if (!fix_scale && !(fabs(delta[6]) <= 1.0)) return 4;
     const double ds = fix_scale ? 1.0 : ss_sim3opt_exp_scale(delta[6]);
-    double Rn[9], tn[3];
-    SS_POSE_UNROLL
-    for (int i = 0; i < 3; i++) {
-        SS_POSE_UNROLL
-        for (int j = 0; j < 3; j++) Rn[3 * i + j] = (dR[3 * i] * R[j] + dR[3 * i + 1] * R[3 + j]) + dR[3 * i + 2] * R[6 + j];
-        tn[i] = ds * ((dR[3 * i] * t[0] + dR[3 * i + 1] * t[1]) + dR[3 * i + 2] * t[2]) + delta[3 + i];
-    }
-    SS_POSE_UNROLL
-    for (int k = 0; k < 9; k++) R[k] = Rn[k];
-    SS_POSE_UNROLL
+    double tn[3];
+    SS_GN_UNROLL
+    for (int i = 0; i < 3; i++) tn[i] = ds * ((dR[3 * i] * t[0] + dR[3 * i + 1] * t[1]) + dR[3 * i + 2] * t[2]) + delta[3 + i];
+    ss_gn_rotate(dR, R);
+    SS_GN_UNROLL
     for (int k = 0; k < 3; k++) t[k] = tn[k];
     if (!fix_scale) *s = ds * *s;
     bool all = true;
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int a = 0; a < 6; a++) all = all && fabs(delta[a]) < step_eps;
     if (!fix_scale) all = all && fabs(delta[6]) < step_eps;
     *small = all;
     return 0;
 }
 
-/* step 4: the chi-squares of both edges; the projection is formed with / z; SS_POSE_BEHIND when the depth is not > 0 */
+/* step 4: the chi-squares of both edges; the projection is formed with / z; SS_GN_BEHIND when the depth is not > 0 */
 SS_HD double ss_sim3opt_chi2_12(const ss_sim3opt_corr &c, const ss_sim3opt_cams &k, const double R[9], const double t[3], double s)
 {
     double x, y, z;
     ss_sim3opt_map12(c, R, t, s, &x, &y, &z);
-    if (!(z > 0.0)) return SS_POSE_BEHIND;
+    if (!(z > 0.0)) return SS_GN_BEHIND;
     const double ex = c.u1 - (k.fx1 * x / z + k.cx1), ey = c.v1 - (k.fy1 * y / z + k.cy1);
     return c.w1 * (ex * ex + ey * ey);
 }
@@ -271,7 +229,7 @@ SS_HD double ss_sim3opt_chi2_21(const ss_sim3opt_corr &c, const ss_sim3opt_cams 
 {
     double M[9], x, y, z;
     ss_sim3opt_map21(c, R, t, s, M, &x, &y, &z);
-    if (!(z > 0.0)) return SS_POSE_BEHIND;
+    if (!(z > 0.0)) return SS_GN_BEHIND;
     const double ex = c.u2 - (k.fx2 * x / z + k.cx2), ey = c.v2 - (k.fy2 * y / z + k.cy2);
     return c.w2 * (ex * ex + ey * ey);
 }
@@ -285,10 +243,10 @@ SS_HD bool ss_sim3opt_floats(const double R[9], const double t[3], double s, ss_
 {
     const double s21 = 1.0 / s;
     const float big = 3.4028234663852886e38f;
-    bool ok = ss_pose_all_finite(R, t) && ss_pose_is_finite(s);
-    SS_POSE_UNROLL
+    bool ok = ss_gn_all_finite(R, t) && ss_gn_is_finite(s);
+    SS_GN_UNROLL
     for (int i = 0; i < 3; i++) {
-        SS_POSE_UNROLL
+        SS_GN_UNROLL
         for (int j = 0; j < 3; j++) {
             m->sr12[3 * i + j] = (float)(s * R[3 * i + j]);
             m->sr21[3 * i + j] = (float)(s21 * R[3 * j + i]);
@@ -297,9 +255,9 @@ SS_HD bool ss_sim3opt_floats(const double R[9], const double t[3], double s, ss_
         m->t21[i] = (float)-(s21 * ss_sim3_dot(R[i], R[3 + i], R[6 + i], t[0], t[1], t[2]));
     }
     m->s12 = (float)s;
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int k = 0; k < 9; k++) ok = ok && fabsf(m->sr12[k]) <= big && fabsf(m->sr21[k]) <= big;
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int k = 0; k < 3; k++) ok = ok && fabsf(m->t12[k]) <= big && fabsf(m->t21[k]) <= big;
     ok = ok && fabsf(m->s12) <= big;
     return ok;
@@ -312,23 +270,23 @@ SS_HD void ss_sim3opt_record(double R[9], double t[3], double s, const double R0
     ss_sim3_result m;
     if (!ss_sim3opt_floats(R, t, s, &m)) {
         state = 2;
-        SS_POSE_UNROLL
+        SS_GN_UNROLL
         for (int k = 0; k < 9; k++) R[k] = R0[k];
-        SS_POSE_UNROLL
+        SS_GN_UNROLL
         for (int k = 0; k < 3; k++) t[k] = t0[k];
         s = s0;
     }
     if (state != 0) {
-        SS_POSE_UNROLL
+        SS_GN_UNROLL
         for (int k = 0; k < 9; k++) m.sr12[k] = m.sr21[k] = 0.0f;
-        SS_POSE_UNROLL
+        SS_GN_UNROLL
         for (int k = 0; k < 3; k++) m.t12[k] = m.t21[k] = 0.0f;
         m.s12 = 0.0f;
     }
     m.state = state, m.n_corr = n_corr, m.n_inliers = state == 0 ? n_inliers : 0, m.best_inliers = 0, m.iteration = -1, m.status = status, m.reserved = 0;
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int k = 0; k < 9; k++) out->r12[k] = R[k];
-    SS_POSE_UNROLL
+    SS_GN_UNROLL
     for (int k = 0; k < 3; k++) out->t12[k] = t[k];
     out->s12 = s;
     out->cost = cost;
@@ -342,7 +300,7 @@ SS_HD void ss_sim3opt_record(double R[9], double t[3], double s, const double R0
 SS_HD bool ss_sim3opt_start_usable(const ss_sim3_result &m) { return m.state == 0 && m.status == SS_OK; }
 
 /* The whole pair on the host the way the kernel runs it: corr[0 .. n) in numbering order; active: n bytes, 1 = inlier on return;
- * slot: (SS_SIM3OPT_SUMS + 1) * SS_POSE_SLOTS doubles of scratch.  status: the pair's (a voided pair has n = 0) */
+ * slot: (SS_SIM3OPT_SUMS + 1) * SS_GN_SLOTS doubles of scratch.  status: the pair's (a voided pair has n = 0) */
 static inline void ss_sim3opt_pair_host(const ss_sim3opt_corr *corr, int n, const ss_sim3opt_cams &cam, const ss_sim3_result &start, int status,
                                         const ss_sim3_opt_params &p, uint8_t *active, double *slot, ss_sim3_opt_result *out)
 {
@@ -361,18 +319,18 @@ static inline void ss_sim3opt_pair_host(const ss_sim3opt_corr *corr, int n, cons
         const bool robust = round == 0;
         const int iterations = round == 0 ? p.iterations0 : n_removed > 0 ? p.iterations_more : p.iterations_same;
         for (int it = 0; it < iterations; it++) {
-            for (int k = 0; k < SS_SIM3OPT_SUMS * SS_POSE_SLOTS; k++) slot[k] = 0.0;
+            for (int k = 0; k < SS_SIM3OPT_SUMS * SS_GN_SLOTS; k++) slot[k] = 0.0;
             double acc[SS_SIM3OPT_SUMS];
             for (int k = 0; k < n; k++) {
                 if (!active[k]) continue;
-                for (int q = 0; q < SS_SIM3OPT_SUMS; q++) acc[q] = slot[(size_t)q * SS_POSE_SLOTS + k % SS_POSE_SLOTS];
+                for (int q = 0; q < SS_SIM3OPT_SUMS; q++) acc[q] = slot[(size_t)q * SS_GN_SLOTS + k % SS_GN_SLOTS];
                 ss_sim3opt_edge e;
                 if (ss_sim3opt_edge12(corr[k], cam, R, t, s, e)) ss_sim3opt_add(e, cam, robust, acc);
                 if (ss_sim3opt_edge21(corr[k], cam, R, t, s, e)) ss_sim3opt_add(e, cam, robust, acc);
-                for (int q = 0; q < SS_SIM3OPT_SUMS; q++) slot[(size_t)q * SS_POSE_SLOTS + k % SS_POSE_SLOTS] = acc[q];
+                for (int q = 0; q < SS_SIM3OPT_SUMS; q++) slot[(size_t)q * SS_GN_SLOTS + k % SS_GN_SLOTS] = acc[q];
             }
             double sum[SS_SIM3OPT_SUMS];
-            for (int q = 0; q < SS_SIM3OPT_SUMS; q++) sum[q] = ss_pose_tree(&slot[(size_t)q * SS_POSE_SLOTS]);
+            for (int q = 0; q < SS_SIM3OPT_SUMS; q++) sum[q] = ss_gn_tree(&slot[(size_t)q * SS_GN_SLOTS]);
             bool small;
             const int rc = ss_sim3opt_step(sum, fix, p.lambda, p.step_eps, R, t, &s, &small);
             if (rc != 0) {
@@ -383,18 +341,18 @@ static inline void ss_sim3opt_pair_host(const ss_sim3opt_corr *corr, int n, cons
             if (small) break;
         }
         if (state != 0) break;
-        double *c = &slot[(size_t)SS_SIM3OPT_SUMS * SS_POSE_SLOTS];
-        for (int k = 0; k < SS_POSE_SLOTS; k++) c[k] = 0.0;
+        double *c = &slot[(size_t)SS_SIM3OPT_SUMS * SS_GN_SLOTS];
+        for (int k = 0; k < SS_GN_SLOTS; k++) c[k] = 0.0;
         n_in = 0;
         for (int k = 0; k < n; k++) {
             if (!active[k]) continue; /* a removed correspondence stays removed */
             const double c12 = ss_sim3opt_chi2_12(corr[k], cam, R, t, s), c21 = ss_sim3opt_chi2_21(corr[k], cam, R, t, s);
             active[k] = ss_sim3opt_inlier(cam, c12, c21) ? 1 : 0;
             if (!active[k]) continue;
-            c[k % SS_POSE_SLOTS] = c[k % SS_POSE_SLOTS] + (c12 + c21);
+            c[k % SS_GN_SLOTS] = c[k % SS_GN_SLOTS] + (c12 + c21);
             n_in++;
         }
-        cost = ss_pose_tree(c);
+        cost = ss_gn_tree(c);
         if (round == 0) {
             n_removed = n - n_in;
             if (n_in < p.min_inliers) state = 3;

@@ -23,39 +23,22 @@ static ss_proj_view view_of(float f, float cx, float cy, float bf)
     return v;
 }
 
-/* one frame on the rule's order of operations; returns the state and counts the steps */
+/* one frame through the header's host loop (ss_pose_frame_host, what ss_pose_opt_host runs); returns the state and counts the steps taken */
 static int frame(const std::vector<ss_pose_obs> &obs, const ss_pose_cam &cam, const double *start, double R[9], double t[3], int *n_in, long *steps)
 {
     const int n = (int)obs.size();
-    if (!ss_pose_start(start, R, t)) return 2;
-    if (n < 3) return 1;
-    std::vector<uint8_t> active((size_t)n, 1);
-    std::vector<double> slot((size_t)(SS_POSE_SUMS + 1) * SS_POSE_SLOTS);
-    *n_in = n;
-    for (int round = 0; round < 4; round++) {
-        for (int it = 0; it < 10; it++) {
-            for (double &v : slot) v = 0.0;
-            for (int k = 0; k < n; k++) {
-                double term[SS_POSE_SUMS];
-                if (!active[(size_t)k] || !ss_pose_terms(obs[(size_t)k], cam, R, t, round < 2, term)) continue;
-                for (int s = 0; s < SS_POSE_SUMS; s++) slot[(size_t)s * SS_POSE_SLOTS + k % SS_POSE_SLOTS] += term[s];
-            }
-            double sum[SS_POSE_SUMS];
-            for (int s = 0; s < SS_POSE_SUMS; s++) sum[s] = ss_pose_tree(&slot[(size_t)s * SS_POSE_SLOTS]);
-            bool small;
-            const int rc = ss_pose_step(sum, 1e-6, 1e-10, R, t, &small);
-            ++*steps;
-            if (rc != 0) return rc;
-            if (small) break;
-        }
-        *n_in = 0;
-        for (int k = 0; k < n; k++) {
-            active[(size_t)k] = ss_pose_inlier(obs[(size_t)k], cam, ss_pose_chi2(obs[(size_t)k], cam, R, t)) ? 1 : 0;
-            *n_in += active[(size_t)k];
-        }
-        if (*n_in < 3) return 3;
-    }
-    return ss_pose_all_finite(R, t) ? 0 : 2;
+    ss_pose_opt_params p = {};
+    p.chi2_mono = cam.chi2_mono, p.chi2_stereo = cam.chi2_stereo, p.lambda = 1e-6, p.step_eps = 1e-10;
+    p.n_rounds = 4, p.iterations = 10, p.robust_rounds = 2, p.min_obs = 3;
+    std::vector<uint8_t> active((size_t)n + 1);
+    std::vector<double> slot((size_t)(SS_POSE_SUMS + 1) * SS_GN_SLOTS);
+    ss_pose_result r;
+    ss_pose_frame_host(obs.data(), n, cam, start, p, active.data(), slot.data(), &r);
+    for (int k = 0; k < 9; k++) R[k] = r.rcw[k];
+    for (int k = 0; k < 3; k++) t[k] = r.tcw[k];
+    *n_in = r.n_inliers;
+    for (int k = 0; k < 8; k++) *steps += r.steps[k];
+    return r.state;
 }
 
 int main()
@@ -72,7 +55,7 @@ int main()
         if (it % 5 == 2)
             for (int k = 0; k < 3; k++) st[3 + k] = 2.0 * st[k]; /* the second row along the first */
         const bool ok = ss_pose_start(st, R, t);
-        if (!ss_pose_all_finite(R, t)) return printf("a start pose is not finite\n"), 1;
+        if (!ss_gn_all_finite(R, t)) return printf("a start pose is not finite\n"), 1;
         if (ok && it % 5 != 1 && it % 5 != 2) { /* rows that are parallel, tiny or huge give a finite matrix, not a rotation */
             const double d = (R[0] * R[3] + R[1] * R[4]) + R[2] * R[5], n = (R[6] * R[6] + R[7] * R[7]) + R[8] * R[8];
             if (fabs(d) > 1e-9 || fabs(n - 1.0) > 1e-9) return printf("a start rotation is not orthonormal: %g %g\n", d, n), 1;

@@ -23,7 +23,7 @@ static ss_proj_view view_of(float f, float cx, float cy)
 
 static bool result_finite(const ss_sim3_opt_result &r)
 {
-    bool ok = ss_pose_all_finite(r.r12, r.t12) && ss_pose_is_finite(r.s12) && ss_pose_is_finite(r.cost);
+    bool ok = ss_gn_all_finite(r.r12, r.t12) && ss_gn_is_finite(r.s12) && ss_gn_is_finite(r.cost);
     for (int k = 0; k < 9; k++) ok = ok && std::isfinite(r.model.sr12[k]) && std::isfinite(r.model.sr21[k]);
     for (int k = 0; k < 3; k++) ok = ok && std::isfinite(r.model.t12[k]) && std::isfinite(r.model.t21[k]);
     return ok && std::isfinite(r.model.s12);
@@ -49,7 +49,7 @@ int main()
             for (int k = 0; k < 9; k++) m.sr12[k] = 0.0f;
         double R[9], t[3], sv;
         const bool ok = ss_sim3opt_start(m, it % 2 == 0, R, t, &sv);
-        if (!ss_pose_all_finite(R, t) || !ss_pose_is_finite(sv) || !(sv > 0.0)) return printf("a start is not finite\n"), 1;
+        if (!ss_gn_all_finite(R, t) || !ss_gn_is_finite(sv) || !(sv > 0.0)) return printf("a start is not finite\n"), 1;
         if (it % 5 == 3 && ok) return printf("the zero model was accepted as a start\n"), 1;
         if (ok && it % 5 == 0) {
             const double d = (R[0] * R[3] + R[1] * R[4]) + R[2] * R[5], n = (R[6] * R[6] + R[7] * R[7]) + R[8] * R[8];
@@ -125,7 +125,7 @@ int main()
             if (variant == 4) start.sr12[4] = nan;
             p.fix_scale = n % 2 == 0 && variant == 0 ? 0 : variant == 3;
             std::vector<uint8_t> active((size_t)n + 1);
-            std::vector<double> slot((size_t)(SS_SIM3OPT_SUMS + 1) * SS_POSE_SLOTS);
+            std::vector<double> slot((size_t)(SS_SIM3OPT_SUMS + 1) * SS_GN_SLOTS);
             ss_sim3_opt_result r;
             ss_sim3opt_pair_host(corr.data(), n, ss_sim3opt_cams_of(v1, v2, p.chi2), start, 0, p, active.data(), slot.data(), &r);
             steps += r.steps[0] + r.steps[1] + 1;

@@ -195,6 +195,19 @@ def test_compaction_across_the_chunk_with_bad_rows(ctx, by_row):
         assert w[0]["n_obs"] > wants[b][0]["n_obs"]
 
 
+def test_compaction_with_a_wave_that_keeps_nothing(ctx):
+    """CHUNK + 65 slots, every one an observation but for the 64 of one wave (skip bytes): a wave without a kept slot ahead of waves with
+    some, and the chunk boundary inside a run of kept slots"""
+    slots = CHUNK + 65
+    fr = dict(C.make_frame(48, slots, n_out=100, n_border=100, stereo_every=4))
+    fr["skip"] = np.zeros(slots, np.uint8)
+    fr["skip"][192:256] = 1
+    wants, _, _ = _against_reference(ctx, [fr], slots, slots, dict(PR.UPSTREAM, check_right=True), "a wave that keeps nothing", skip=True)
+    res, flags = wants[0]
+    assert res["n_obs"] == slots - 64 and res["state"] == 0
+    assert (flags[192:256] == 2).all() and (flags[[191, 256, CHUNK - 1, CHUNK, slots - 1]] != 2).all()
+
+
 def test_two_frames_at_the_row_limit(ctx):
     """SS_GUIDED_MAX_ROWS slots: every slot an observation (64 per thread, the whole mask) and a frame of 9000"""
     frames = [C.make_frame(60, MAX_ROWS, n_out=2000, n_border=2000, stereo_every=2), C.make_frame(61, 9000, n_out=1000, n_border=1000, n_points=MAX_ROWS, n_kp=MAX_ROWS)]

@@ -145,6 +145,19 @@ def test_every_state_and_the_pair_number_in_one_call(ctx):
     assert len({int(w[0]["iteration"]) for w in wants}) > 1 and all(w[0]["state"] == 0 for w in wants)
 
 
+def test_compaction_with_a_wave_that_keeps_nothing(ctx):
+    """CHUNK + 65 rows, every one a correspondence but for the 64 of one wave (skip bytes): a wave without a kept row ahead of waves with
+    some, and the chunk boundary inside a run of kept rows"""
+    rows = CHUNK + 65
+    pr = dict(SC.make_pair(45, rows, rows // 3, rows, rows))
+    pr["q_skip"] = np.zeros(rows, np.uint8)
+    pr["q_skip"][192:256] = 1
+    p = dict(chi2=9.210, min_inliers=20, max_iterations=48, fix_scale=False, seed=7)
+    res, flags, _ = _pairs_against_reference(ctx, [pr], rows, p, "a wave that keeps nothing")[0]
+    assert res["n_corr"] == rows - 64 and res["state"] == 0
+    assert not flags[192:256].any() and flags[:192].any() and flags[256:CHUNK].any() and flags[CHUNK:].any()
+
+
 @pytest.mark.parametrize("rows", [128, CHUNK + 76])
 def test_compaction(ctx, rows):
     """matches and skip bytes scattered so that the kept rows straddle the wave (and, in the larger shape, the chunk) boundaries;

@@ -126,6 +126,19 @@ def test_compaction_over_chunks(ctx):
     assert 150 < wants[0][0]["n_corr"] < 400 and wants[0][0]["state"] == 0
 
 
+def test_compaction_with_a_wave_that_keeps_nothing(ctx):
+    """1024 + 65 rows, every one a correspondence but for the 64 of one wave (skip bytes): a wave without a kept row ahead of waves with
+    some, and the chunk boundary inside a run of kept rows"""
+    rows = 1024 + 65
+    pr = dict(OC.make_pair(62, rows, rows // 8, rows, rows))
+    pr["q_skip"] = np.zeros(rows, np.uint8)
+    pr["q_skip"][192:256] = 1
+    wants, _ = _pairs_against_reference(ctx, [pr], rows, O.UPSTREAM, "a wave that keeps nothing")
+    res, flags = wants[0]
+    assert res["n_corr"] == rows - 64 and res["state"] == 0
+    assert (flags[192:256] == 2).all() and (flags[[191, 256, 1023, 1024, rows - 1]] != 2).all()
+
+
 def test_two_full_pairs(ctx):
     from send_slam_amd import binding
     rows = binding.SS_GUIDED_MAX_ROWS

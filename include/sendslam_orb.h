@@ -1366,6 +1366,156 @@ int ss_sim3_mutual_batch_device(ss_ctx *ctx, const int32_t *train_src, const voi
 int ss_sim3_to_view21(const ss_camera *cam, const ss_sim3_result *result, const double rcw1[9], const double tcw1[3], float bf,
                       double *srcw_out, double *t_out, ss_proj_view *out);
 
+/* ---- Local bundle adjustment: Optimizer::LocalBundleAdjustment (g2o EdgeSE3ProjectXYZ and EdgeStereoSE3ProjectXYZ under a
+ * Levenberg-Marquardt loop with the points marginalised) as LocalMapping::Run calls it after the map-building chain, for several
+ * local maps (problems) of a call at once.  tests/ba_ref.py is its normative statement; DESIGN.md section 25.  An addition to ABI 5:
+ * nothing existing changes.  The upstream source is not in the reference tree: parity with the real binary is unpinned, as for the
+ * Sim3 refinement -----------------------------------------------------------------------------------------------------------------
+ * - All arithmetic is double.  Every step is one IEEE operation, left to right as written, with no contraction.  The only library
+ *   function is sqrt.  Every test is written in its accepting form, so a NaN fails it (the step-size test of ss_pose_exp excepted).
+ * - Every sum has one fixed order, so ss_local_ba_host and the kernels agree bit for bit.
+ * A call has n_frames keyframes (their keypoint rows with an optional right coordinate each, as for ss_pose_opt_*), blocks of map
+ * points (only x, y, z are read) with an optional skip byte each, d_idx int32 [n_frames][point_rows] (idx[f][i]: the keypoint row of
+ * point row i in keyframe f, or a negative value: a stack of ss_match_proj_* outputs), and a HOST table of problems.  Problem q owns
+ * the keyframes first_frame .. first_frame + n_kf - 1 (k = 0 .. n_kf-1 below) and reads the points of block point_block.  The first
+ * n_free keyframes are optimised, the others are fixed (upstream's lFixedCameras) and hold the gauge: n_kf - n_free >= 1.  The frame
+ * ranges of the problems of a call do not overlap; two problems may read one block of points.
+ * 1. Observations and points.  Point row i is a point iff i < n_points, its skip byte (if given) is 0 and x, y, z are finite.  (k, i)
+ *    is an observation iff i is a point, 0 <= idx < n_kp of the keyframe and the keypoint's octave lies in 0 .. n_levels-1; u, v are
+ *    the float32 keypoint coordinates widened, w = 1.0 / (s*s) with s = (double)scale[octave]; stereo iff check_right is set, a right
+ *    array is given and right[row] > 0.  A point is active iff it has at least min_point_obs observations; the others are flagged 1
+ *    and never move.  Start poses go through step 2 of the pose-only optimisation (Gram-Schmidt); one that is not finite gives the
+ *    problem state 2 at once.  Points are widened to double.  No active point: state 1.
+ * 2. Linearisation of an inlier observation (round 0: every one) of an active point under (R, t) of its keyframe and the point X:
+ *    x, y, z, iz, iz2, rx, ry, rr, J0, J1, J2, e2 and the Huber weight are those of step 3 of the pose-only optimisation, term by
+ *    term (ss_pose_terms); so are the 26 terms of U_k and g_k.  An observation with z > 0 false takes no part in the step.  The
+ *    point Jacobian reuses the translation entries of J: with a3 = J0[3], a5 = J0[5], c4 = J1[4], c5 = J1[5], d5 = J2[5] (a3 =
+ *    -iz*fx is minus the entry fx*iz of the projection's Jacobian, a5 = x*iz2*fx minus its entry -fx*x*iz2, and so on: Jp =
+ *    -Jproj.R), Jp0[b] = a3*R[b] + a5*R[6+b], Jp1[b] = c4*R[3+b] + c5*R[6+b], Jp2[b] = a3*R[b] + d5*R[6+b], b = 0 .. 2.  With
+ *    q = the Huber weight, qJp = q*Jp and qJ = q*J entry by entry (J's structural zeros are +0.0 here), the terms are V_ab =
+ *    (qJp0[a]*Jp0[b] + qJp1[a]*Jp1[b]) [+ qJp2[a]*Jp2[b]] for a <= b, b_a = (qJp0[a]*rx + qJp1[a]*ry) [+ qJp2[a]*rr], and
+ *    W[a][b] = (qJ0[a]*Jp0[b] + qJ1[a]*Jp1[b]) [+ qJ2[a]*Jp2[b]], a = 0 .. 5, b = 0 .. 2 (the bracket: stereo only).
+ * 3. Per active point.  V_i (6 sums) and b_i (3) are added over the contributing observations in ascending k from +0.0, fixed
+ *    keyframes included; W_ki is kept for every free k.  V_aa += lambda*(1.0 + V_aa), then the column Cholesky of ss_gn_solve<3>.
+ *    Y_ki = W_ki.V_i^-1, each row by the two triangular solves.  A point with a pivot that is not > 0 is frozen for this step: its
+ *    observations still contribute U and g, it gets no coupling and its delta is 0.
+ * 4. Reduced system, for free k <= l.  The entries of U_k (21: H34 is the structural 0), g_k (6), C_kl = sum_i Y_ki.W_li^T (36; the
+ *    21 of the upper triangle on the diagonal; an entry is (Y[a][0]*W[b][0] + Y[a][1]*W[b][1]) + Y[a][2]*W[b][2]) and sum_i Y_ki.b_i
+ *    (6, the same form) are each summed over the points i in the tree order of the pose-only optimisation: slot s of 256 adds the
+ *    points s, s + 256, ... in ascending order from +0.0, skipping those that do not contribute; each group of 64 slots folds by
+ *    halving; the four results combine as (r0 + r1) + (r2 + r3).  U_aa += lambda*(1.0 + U_aa); S_kk = U_k - C_kk, S_kl = 0.0 - C_kl
+ *    for k < l, r_k = g_k - sum Y.b, one subtraction per entry.
+ * 5. Solve S.dc = -r by Cholesky by columns of order 6*n_free (ss_gn_chol_n and ss_gn_subst_n of csrc/ss_gn_steps.h: the text of
+ *    ss_gn_solve for a run-time order).  Every inner sum subtracts in ascending k; since each entry's subtractions are sequential in
+ *    k, the rows of a column may be computed in parallel, and a right-looking schedule gives the same bits.  A pivot that is not
+ *    > 0: state 2, the problem ends, poses and points stay as before the step.
+ * 6. Back-substitution and update.  v = -b_i; for every free k with a contributing observation, ascending: v_b = v_b - (((((W[0][b]*
+ *    dc[0] + W[1][b]*dc[1]) + W[2][b]*dc[2]) + W[3][b]*dc[3]) + W[4][b]*dc[4]) + W[5][b]*dc[5]); dp_i = V_i^-1.v by the two
+ *    triangular solves; X <- X + dp, entry by entry.  Frozen and inactive points are not touched.  Poses: exp(dc_k) and the update
+ *    as in the pose-only optimisation; q > pi*pi in any free keyframe: state 4, the problem ends, nothing moves.
+ * 7. Accept or reject: the one place the rule departs from the fixed-lambda steps of the pose-only optimisation, because a coupled
+ *    problem needs it.  The cost of a state is the sum over k = 0 .. n_kf-1, ascending from +0.0, of the tree sum over the points i
+ *    of the chi-terms of the inlier observations (k, i) of active points: the chi-square of step 4 of the pose-only optimisation
+ *    (projection formed with / z; 1e30 when z > 0 is false), and in a robust round e2 <= d*d ? e2 : 2.0*d*sqrt(e2) - d*d with d =
+ *    sqrt(chi2_mono) or sqrt(chi2_stereo).  A step is accepted iff every entry of the trial poses and points is finite, its cost is
+ *    finite and <= the cost before it; then lambda <- max(lambda / lambda_factor, lambda_min).  Otherwise nothing moves and lambda <-
+ *    lambda*lambda_factor.  Either way the step counts as an iteration.  A round ends after iterations[r] steps, or after an accepted
+ *    step with every |delta| < step_eps, pose and moved-point entries alike.  The cost before the first step of a round is formed
+ *    under that round's inliers and robustness; one that is not finite (an input that is not finite) ends the problem in state 2
+ *    with the poses and points it has (in round 0: the start) and the costs recorded before.
+ * 8. Rounds r = 0 .. n_rounds-1; r < robust_rounds is robust.  The defaults are ORB-SLAM2's schedule: 5 robust iterations,
+ *    classification, then 10 plain iterations on the inliers; ORB-SLAM3's single robust round of 10 is n_rounds = 1, iterations[0] =
+ *    10, robust_rounds = 1.  After a round every inlier observation of an active point is classified: an outlier iff not chi2 <= th
+ *    (chi2_mono or chi2_stereo by kind; the chi-square of step 7 without the Huber form, so a depth that is not positive is an
+ *    outlier).  A removed observation stays removed.  A point left with fewer than min_point_obs inliers becomes inactive (flag 1)
+ *    and keeps its place.
+ * 9. Non-finite results.  Step 7 accepts no state with an entry that is not finite and step 1 ends a problem whose start poses are
+ *    not finite (state 2; such a pose is returned as the identity and zero), so no NaN bits reach a result.
+ * Outputs.  Per problem one ss_ba_result, 88 bytes.  Per keyframe of the call twelve doubles (rcw row-major, tcw): fixed keyframes
+ * and those of no problem get their orthonormalised start.  Per problem and point row three doubles and one flag byte: 0 optimised,
+ * 1 too few observations or inliers, 2 not a point (its doubles are +0.0).  Per (keyframe, point row) one byte: 0 inlier, 1
+ * outlier, 2 no observation (every row of a keyframe of no problem).  Every output byte is written exactly once per call.
+ * Deviations from upstream: g2o's Levenberg-Marquardt scales lambda by its gain ratio and seeds it from the diagonal, here it is
+ * multiplied or divided by lambda_factor from the given start; the exponential by series; a point behind a camera takes no part
+ * in a step; the order of every sum is fixed; keypoints are taken as undistorted; no map bookkeeping (the caller erases what the
+ * flags name). */
+#define SS_BA_MAX_KF 64     /* keyframes of a problem */
+#define SS_BA_MAX_FREE 32   /* optimised keyframes of a problem: the reduced system has order 192 at the most */
+#define SS_BA_MAX_ROUNDS 4
+typedef struct {            /* 16 bytes, one per problem (a HOST table) */
+    int32_t first_frame, n_kf, n_free, point_block;
+} ss_ba_problem;
+typedef struct {            /* 96 bytes */
+    double chi2_mono;       /* finite and > 0; upstream: 5.991 */
+    double chi2_stereo;     /* finite and > 0; upstream: 7.815 */
+    double lambda;          /* the first step's; finite and >= 0; default 1e-4 */
+    double lambda_factor;   /* finite and > 1; default 10 */
+    double lambda_min;      /* finite and >= 0; default 1e-9 */
+    double step_eps;        /* finite and >= 0; default 1e-10; 0 runs every step */
+    int32_t n_rounds;       /* 1 .. SS_BA_MAX_ROUNDS; default 2 */
+    int32_t iterations[4];  /* each 1 .. 32 for r < n_rounds; default 5, 10 */
+    int32_t robust_rounds;  /* 0 .. SS_BA_MAX_ROUNDS; default 1 */
+    int32_t min_point_obs;  /* >= 1; default 2 */
+    int32_t check_right;    /* non-zero: a row with right > 0 is a stereo observation */
+    int32_t reserved[4];    /* must be 0 */
+} ss_ba_params;
+typedef struct {            /* 88 bytes, one per problem */
+    double lambda;          /* after the last step */
+    double cost_before;     /* the cost ahead of the first step of round 0 */
+    double cost_after;      /* the cost of the state returned, under the inliers and robustness of the last round that ran */
+    int32_t state;          /* 0 ok, 1 no active point, 2 not positive definite, or a start pose or a cost that is not finite, 4 step too large */
+    int32_t status;         /* SS_OK, or the frame_error that voided the problem (state 1) */
+    int32_t n_obs, n_stereo; /* observations of points, active or not; the stereo ones among them */
+    int32_t n_inliers;      /* observation bytes that are 0 on return */
+    int32_t n_points_active; /* point flags that are 0 on return */
+    int32_t n_frozen_max;   /* the most points frozen in one step */
+    int32_t steps[4];       /* steps taken in round r, rejected ones included */
+    int32_t accepted[4];    /* steps accepted in round r */
+    int32_t reserved;       /* 0 */
+} ss_ba_result;
+/* The whole rule on the host from the text the kernels compile (csrc/ss_ba_steps.h), one problem of n_kf keyframes; needs no device.
+ * views, start (n_kf x 12 doubles), n_kp are per keyframe; kp and right (or NULL) are [n_kf][rows_per_frame]; idx and obs_flags
+ * [n_kf][n_points]; poses n_kf x 12 doubles, xyz n_points x 3 doubles, point_flags n_points bytes.  p is checked as the device calls
+ * check it (SS_ERR_INVALID_ARG). */
+int ss_local_ba_host(const ss_proj_view *views, const double *start, int n_kf, int n_free, const float *scale, int n_levels,
+                     const ss_map_point *points, const uint8_t *point_skip, int n_points, const ss_keypoint *kp, const float *right,
+                     const int32_t *n_kp, int rows_per_frame, const int32_t *idx, const ss_ba_params *p, double *poses, double *xyz,
+                     uint8_t *point_flags, uint8_t *obs_flags, ss_ba_result *result);
+/* n_problems problems on caller-supplied device arrays: map points, keypoints and d_idx as described above (counts are clamped to
+ * 0 .. their rows).  problems (n_problems), views (n_frames) and start_poses (n_frames x 12 doubles) are HOST tables, copied before
+ * the call returns.  Outputs: d_poses double [n_frames][12], d_xyz double [n_problems][point_rows][3], d_point_flags uint8
+ * [n_problems][point_rows], d_obs_flags uint8 [n_frames][point_rows], d_result [n_problems] ss_ba_result.  SS_ERR_INVALID_ARG: a row
+ * count above SS_GUIDED_MAX_ROWS, n_kf outside 1 .. SS_BA_MAX_KF, n_free outside 1 .. SS_BA_MAX_FREE, n_free == n_kf, a frame range
+ * outside the call or overlapping another, a point_block outside 0 .. n_blocks - 1, a parameter out of its range, a reserved field
+ * that is not 0, a NULL buffer.  Without a frame or without a problem the call returns SS_OK and writes nothing.  The context's
+ * workspace for a call is dominated by the points' W and Y blocks: n_problems x F x point_rows x 288 bytes, F being the largest
+ * n_free of the call (16 problems of 32 free keyframes and 16 384 rows: 2.4 GB; SS_ERR_NO_MEMORY when it cannot be had), so choose
+ * point_rows by the local maps, not by the row limit.  The fixed schedule
+ * of every round and iteration is enqueued at once; a problem that has ended costs empty launches.  Asynchronous on the context's
+ * stream. */
+int ss_local_ba_pairs_device(ss_ctx *ctx, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks,
+                             int point_rows, const void *d_kp, const void *d_right, const void *d_n_kp, int n_frames, int rows_per_frame,
+                             const void *d_idx, const ss_ba_problem *problems, int n_problems, const ss_proj_view *views,
+                             const double *start_poses, const ss_ba_params *p, void *d_poses, void *d_xyz, void *d_point_flags,
+                             void *d_obs_flags, void *d_result);
+/* The same, the keyframes being the frames of the last ss_extract_batch_device batch (SS_ERR_STATE without one; n_frames and
+ * rows_per_frame = kp_capacity are the batch's).  A problem with a frame whose frame_error is set gets that status and state 1. */
+int ss_local_ba_batch_device(ss_ctx *ctx, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks,
+                             int point_rows, const void *d_right, const void *d_idx, const ss_ba_problem *problems, int n_problems,
+                             const ss_proj_view *views, const double *start_poses, const ss_ba_params *p, void *d_poses, void *d_xyz,
+                             void *d_point_flags, void *d_obs_flags, void *d_result);
+/* One problem with host pointers in and out (copy in, the pairs form, copy out), synchronous; the arguments of ss_local_ba_host. */
+int ss_local_ba(ss_ctx *ctx, const ss_proj_view *views, const double *start, int n_kf, int n_free, const ss_map_point *points,
+                const uint8_t *point_skip, int n_points, const ss_keypoint *kp, const float *right, const int32_t *n_kp,
+                int rows_per_frame, const int32_t *idx, const ss_ba_params *p, double *poses, double *xyz, uint8_t *point_flags,
+                uint8_t *obs_flags, ss_ba_result *result);
+/* Rounds the points of n problems back into blocks of ss_map_point, so that the next ss_match_proj_* reads them: x, y, z of row i of
+ * block block_of[q] (a HOST table, or NULL: block q) become (float) of d_xyz[q][i] wherever d_point_flags[q][i] is not 2; nothing
+ * else of the block is written.  SS_ERR_INVALID_ARG: a bad count, a block number outside 0 .. n_blocks - 1, a NULL buffer.
+ * Asynchronous. */
+int ss_local_ba_points_to_block(ss_ctx *ctx, const void *d_xyz, const void *d_point_flags, int n_problems, int point_rows,
+                                const int32_t *block_of, void *d_points, int n_blocks);
+
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device
  * (hipStream_t; NULL = the legacy default stream): for callers that produce the inputs of a *_device call on their own

@@ -1,6 +1,7 @@
 /*
  * ss_api_search.cpp -- the search family of the C ABI (include/sendslam_orb.h): guided matching, map-point projection search,
- * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation, the Sim3 RANSAC, the pose-only optimisation, the Sim3 refinement.  Each has a pairs form on caller arrays, a batch form on the
+ * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation, the Sim3 RANSAC, the pose-only optimisation, the Sim3 refinement,
+ * the local bundle adjustment.  Each has a pairs form on caller arrays, a batch form on the
  * frames of the last extraction and, for some, a host form.  The context and the helpers they share: ss_ctx.h.
  */
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "ss_ctx.h"
+#include "ss_ba_steps.h"
 #include "ss_epi_steps.h"
 #include "ss_fuse_steps.h"
 #include "ss_pose_steps.h"
@@ -2021,6 +2023,311 @@ int ss_sim3_mutual_batch_device(ss_ctx *c, const int32_t *train_src, const void 
     g.nq = g.nt = o.n_kp, g.src = o.src, g.frame_error = o.frame_error;
     g.idx_out = (int32_t *)d_idx_out, g.summary = (ss_sim3_mutual_summary *)d_summary;
     return sim3_marks_run(c, g, true);
+}
+
+/* ---- local bundle adjustment (csrc/ss_ba.hip, csrc/ss_ba_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *ba_params_error(const ss_ba_params *p)
+{
+    if (!p) return "local BA: params is NULL";
+    if (!(p->chi2_mono > 0.0) || !std::isfinite(p->chi2_mono)) return "local BA: chi2_mono must be finite and > 0";
+    if (!(p->chi2_stereo > 0.0) || !std::isfinite(p->chi2_stereo)) return "local BA: chi2_stereo must be finite and > 0";
+    if (!(p->lambda >= 0.0) || !std::isfinite(p->lambda)) return "local BA: lambda must be finite and >= 0";
+    if (!(p->lambda_factor > 1.0) || !std::isfinite(p->lambda_factor)) return "local BA: lambda_factor must be finite and > 1";
+    if (!(p->lambda_min >= 0.0) || !std::isfinite(p->lambda_min)) return "local BA: lambda_min must be finite and >= 0";
+    if (!(p->step_eps >= 0.0) || !std::isfinite(p->step_eps)) return "local BA: step_eps must be finite and >= 0";
+    if (p->n_rounds < 1 || p->n_rounds > SS_BA_MAX_ROUNDS) return "local BA: n_rounds must be 1 .. 4";
+    for (int r = 0; r < p->n_rounds; r++)
+        if (p->iterations[r] < 1 || p->iterations[r] > 32) return "local BA: iterations must be 1 .. 32 in every round";
+    if (p->robust_rounds < 0 || p->robust_rounds > SS_BA_MAX_ROUNDS) return "local BA: robust_rounds must be 0 .. 4";
+    if (p->min_point_obs < 1) return "local BA: min_point_obs must be >= 1";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0 || p->reserved[3] != 0) return "local BA: the reserved fields must be 0";
+    return nullptr;
+}
+
+/* the message of the rule the shape of problem q breaks (frames and blocks apart), or empty */
+static std::string ba_problem_error(const ss_ba_problem &b, int q)
+{
+    const std::string head = "local BA: problem " + std::to_string(q) + ": ";
+    if (b.n_kf < 1 || b.n_kf > SS_BA_MAX_KF) return head + "n_kf " + std::to_string(b.n_kf) + " outside 1 .. SS_BA_MAX_KF (" + std::to_string(SS_BA_MAX_KF) + ")";
+    if (b.n_free < 1 || b.n_free > SS_BA_MAX_FREE)
+        return head + "n_free " + std::to_string(b.n_free) + " outside 1 .. SS_BA_MAX_FREE (" + std::to_string(SS_BA_MAX_FREE) + ")";
+    if (b.n_kf - b.n_free < 1) return head + "n_free " + std::to_string(b.n_free) + " of n_kf " + std::to_string(b.n_kf) + " leaves no fixed keyframe to hold the gauge";
+    return std::string();
+}
+
+int ss_local_ba_host(const ss_proj_view *views, const double *start, int n_kf, int n_free, const float *scale, int n_levels, const ss_map_point *points,
+                     const uint8_t *point_skip, int n_points, const ss_keypoint *kp, const float *right, const int32_t *n_kp, int rows_per_frame,
+                     const int32_t *idx, const ss_ba_params *p, double *poses, double *xyz, uint8_t *point_flags, uint8_t *obs_flags, ss_ba_result *result)
+{
+    if (ba_params_error(p)) return SS_ERR_INVALID_ARG;
+    const ss_ba_problem shape = {0, n_kf, n_free, 0};
+    if (!ba_problem_error(shape, 0).empty()) return SS_ERR_INVALID_ARG;
+    if (!views || !start || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n_points < 0 || rows_per_frame < 1 || !n_kp || !kp || !poses || !result)
+        return SS_ERR_INVALID_ARG;
+    if (n_points > 0 && (!points || !idx || !xyz || !point_flags || !obs_flags)) return SS_ERR_INVALID_ARG;
+    const size_t P = (size_t)n_points;
+    std::vector<ss_pose_cam> cam((size_t)n_kf);
+    for (int k = 0; k < n_kf; k++) cam[(size_t)k] = ss_pose_cam_of(views[k], p->chi2_mono, p->chi2_stereo);
+    std::vector<ss_ba_meas> meas((size_t)n_kf * P + 1);
+    std::vector<double> X(P * 3 + 1);
+    std::vector<uint8_t> obs((size_t)n_kf * P + 1), pflag(P + 1);
+    /* step 1 */
+    for (size_t i = 0; i < P; i++) {
+        const ss_map_point &pt = points[i];
+        const bool is_point = !(point_skip && point_skip[i] != 0) && ss_gn_is_finite((double)pt.x) && ss_gn_is_finite((double)pt.y) && ss_gn_is_finite((double)pt.z);
+        pflag[i] = is_point ? 0 : 2;
+        X[3 * i] = is_point ? (double)pt.x : 0.0, X[3 * i + 1] = is_point ? (double)pt.y : 0.0, X[3 * i + 2] = is_point ? (double)pt.z : 0.0;
+        for (int k = 0; k < n_kf; k++) {
+            const size_t o = (size_t)k * P + i;
+            const int nk = std::min(std::max(n_kp[k], 0), rows_per_frame), krow = idx[o];
+            ss_ba_meas m = {0.0f, 0.0f, -1.0f, 1.0f};
+            obs[o] = 2;
+            if (is_point && krow >= 0 && krow < nk) {
+                const ss_keypoint &kk = kp[(size_t)k * rows_per_frame + krow];
+                if (kk.octave >= 0 && kk.octave < n_levels) {
+                    m.u = kk.x, m.v = kk.y, m.scale = scale[kk.octave];
+                    m.ur = ss_pose_stored_right(p->check_right != 0, right != nullptr, right ? right[(size_t)k * rows_per_frame + krow] : 0.0f);
+                    obs[o] = 0;
+                }
+            }
+            meas[o] = m;
+        }
+    }
+    ss_ba_problem_host(n_kf, n_free, n_points, cam.data(), start, meas.data(), *p, obs.data(), X.data(), pflag.data(), poses, result);
+    for (size_t i = 0; i < P; i++) {
+        point_flags[i] = pflag[i];
+        for (int e = 0; e < 3; e++) xyz[3 * i + e] = pflag[i] == 2 ? 0.0 : X[3 * i + e];
+    }
+    for (size_t o = 0; o < (size_t)n_kf * P; o++) obs_flags[o] = obs[o];
+    return SS_OK;
+}
+
+/* The checks the device forms share, the workspace, the host tables (start poses, views, problems, the frames' problems), then the
+ * fixed schedule of a call whose device operands and outputs are filled in */
+static int ba_run(ss_ctx *c, ssk_ba_call &g, int n_blocks, const ss_ba_problem *problems, const ss_proj_view *views, const double *start_poses,
+                  const ss_ba_params *p)
+{
+    if (const char *msg = ba_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (g.n_frames < 0 || g.n_problems < 0 || n_blocks < 0 || g.point_rows < 1 || g.rows < 1)
+        return fail(c, SS_ERR_INVALID_ARG, "local BA: bad frame, problem, block or row count");
+    if (g.point_rows > SS_GUIDED_MAX_ROWS || g.rows > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "local BA: point_rows " + std::to_string(g.point_rows) + " / rows_per_frame " + std::to_string(g.rows) +
+                                               " exceed SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    int rc = call_count_ok(c, "local BA", g.n_frames, "frames");
+    if (rc == SS_OK) rc = context_pyramid(c, "local BA", &g.n_levels, g.scale);
+    if (rc != SS_OK) return rc;
+    if (g.n_frames == 0 || g.n_problems == 0) return SS_OK;
+    if (!problems || !views || !start_poses) return fail(c, SS_ERR_INVALID_ARG, "local BA: problems, views or start_poses is NULL");
+    std::vector<int32_t> frame_prob((size_t)g.n_frames, -1);
+    g.max_kf = g.max_free = 0;
+    for (int q = 0; q < g.n_problems; q++) {
+        const ss_ba_problem &b = problems[q];
+        const std::string msg = ba_problem_error(b, q);
+        if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+        const std::string head = "local BA: problem " + std::to_string(q) + ": ";
+        if (b.first_frame < 0 || b.first_frame > g.n_frames - b.n_kf)
+            return fail(c, SS_ERR_INVALID_ARG, head + "frames " + std::to_string(b.first_frame) + " .. + " + std::to_string(b.n_kf) + " lie outside the call's " +
+                                                   std::to_string(g.n_frames));
+        if (b.point_block < 0 || b.point_block >= n_blocks)
+            return fail(c, SS_ERR_INVALID_ARG, head + "point_block " + std::to_string(b.point_block) + " names no block of points (" + std::to_string(n_blocks) + ")");
+        for (int k = 0; k < b.n_kf; k++) {
+            int32_t &owner = frame_prob[(size_t)(b.first_frame + k)];
+            if (owner >= 0) return fail(c, SS_ERR_INVALID_ARG, head + "frame " + std::to_string(b.first_frame + k) + " belongs to problem " + std::to_string(owner) + " already");
+            owner = q;
+        }
+        g.max_kf = std::max(g.max_kf, (int)b.n_kf), g.max_free = std::max(g.max_free, (int)b.n_free);
+    }
+    if (!g.points || !g.np || !g.kp || !g.nk || !g.idx || !g.out_pose || !g.out_xyz || !g.pflag || !g.obs || !g.result)
+        return fail(c, SS_ERR_INVALID_ARG, "local BA: NULL buffer");
+    g.p = *p;
+    const size_t P = (size_t)g.point_rows, nf = (size_t)g.n_frames, nq = (size_t)g.n_problems, F = (size_t)g.max_free, K = (size_t)g.max_kf;
+    const size_t pblocks = (P + SS_GN_SLOTS - 1) / SS_GN_SLOTS;
+    rc = carve_from(c, c->d_ba_ws, [&](carve &w) {
+        g.meas = w.take<ssk_ba_meas>(nf * P * sizeof(ssk_ba_meas));
+        g.lin = w.take<uint8_t>(nf * P);
+        g.pose = w.take<double>(2 * nf * 12 * sizeof(double));
+        g.X = w.take<double>(2 * nq * P * 3 * sizeof(double));
+        g.WY = w.take<double>(nq * F * 36 * P * sizeof(double));
+        g.Lb = w.take<double>(nq * 9 * P * sizeof(double));
+        g.solved = w.take<uint8_t>(nq * P);
+        g.A = w.take<double>(nq * 36 * F * F * sizeof(double));
+        g.r = w.take<double>(nq * 6 * F * sizeof(double));
+        g.dc = w.take<double>(nq * 6 * F * sizeof(double));
+        g.cost_k = w.take<double>(nq * K * sizeof(double));
+        g.blk = w.take<int32_t>(nq * pblocks * 4 * sizeof(int32_t));
+        g.st = w.take<ssk_ba_state>(nq * sizeof(ssk_ba_state));
+    });
+    if (rc != SS_OK) return rc;
+    /* the host tables of the call: n_frames start poses, n_frames views, n_problems problems, n_frames problem numbers */
+    const size_t sb = nf * 12 * sizeof(double), vb = nf * sizeof(ss_proj_view), pb = nq * sizeof(ss_ba_problem);
+    rc = staged_upload(c, c->ba_tab, sb + vb + pb + nf * sizeof(int32_t), [&](uint8_t *h) {
+        memcpy(h, start_poses, sb);
+        memcpy(h + sb, views, vb);
+        memcpy(h + sb + vb, problems, pb);
+        memcpy(h + sb + vb + pb, frame_prob.data(), nf * sizeof(int32_t));
+    });
+    if (rc != SS_OK) return rc;
+    g.start = c->ba_tab.as<double>();
+    g.views = c->ba_tab.as<ss_proj_view>(sb);
+    g.prob = c->ba_tab.as<ss_ba_problem>(sb + vb);
+    g.frame_prob = c->ba_tab.as<int32_t>(sb + vb + pb);
+    /* the stages' bytes: what a launch reads and writes when every slot is an observation of a free keyframe (an upper bound) */
+    const int64_t nfP = (int64_t)(nf * P), nqP = (int64_t)(nq * P), iF = (int64_t)F, iK = (int64_t)K, iq = (int64_t)nq;
+    {
+        stage_timer t(c, "ba_gather", nfP * (4 + 16 + 1) + nqP * (32 + 1 + 48) + (g.p_skip ? nqP : 0));
+        ssk_ba_gather(c->stream, g);
+    }
+    for (int r = 0; r < p->n_rounds; r++) {
+        for (int it = -1; it < p->iterations[r]; it++) {
+            if (it >= 0) {
+                {
+                    stage_timer t(c, "ba_points", nqP * (iK * 18 + 24 + iF * 288 + 72 + 2));
+                    ssk_ba_points(c->stream, g, r);
+                }
+                {
+                    stage_timer t(c, "ba_blocks", iq * (iF * (iF + 1) / 2) * (int64_t)P * (3 + 288) + iq * 36 * iF * iF * 8);
+                    ssk_ba_blocks(c->stream, g, r);
+                }
+                {
+                    stage_timer t(c, "ba_solve", iq * (36 * iF * iF * 8 + 6 * iF * 16 + iF * 192));
+                    ssk_ba_solve(c->stream, g);
+                }
+                {
+                    stage_timer t(c, "ba_update", nqP * (2 + 48 + 72 + iF * (1 + 144)));
+                    ssk_ba_update(c->stream, g);
+                }
+            }
+            {
+                stage_timer t(c, "ba_cost", iq * iK * (int64_t)P * (2 + 16 + 24) + iq * iK * 8);
+                ssk_ba_cost(c->stream, g, r, it >= 0 ? 1 : 0);
+            }
+            {
+                stage_timer t(c, "ba_accept", iq * (iK * 8 + (int64_t)sizeof(ssk_ba_state)));
+                ssk_ba_accept(c->stream, g, r, it >= 0 ? 0 : 1);
+            }
+        }
+        stage_timer t(c, "ba_classify", nqP * (1 + iK * 17 + 24));
+        ssk_ba_classify(c->stream, g);
+    }
+    {
+        stage_timer t(c, "ba_finish", nqP * (1 + 48 + iK) + (int64_t)nf * 96 + iq * (int64_t)sizeof(ss_ba_result));
+        ssk_ba_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_local_ba_pairs_device(ss_ctx *c, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks, int point_rows,
+                             const void *d_kp, const void *d_right, const void *d_n_kp, int n_frames, int rows_per_frame, const void *d_idx,
+                             const ss_ba_problem *problems, int n_problems, const ss_proj_view *views, const double *start_poses, const ss_ba_params *p,
+                             void *d_poses, void *d_xyz, void *d_point_flags, void *d_obs_flags, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    ssk_ba_call g;
+    g.n_frames = n_frames, g.n_problems = n_problems, g.point_rows = point_rows, g.rows = rows_per_frame;
+    g.points = (const ss_map_point *)d_points, g.p_skip = (const uint8_t *)d_point_skip, g.np = (const int32_t *)d_n_points;
+    g.kp = (const ss_keypoint *)d_kp, g.right = (const float *)d_right, g.nk = (const int32_t *)d_n_kp;
+    g.idx = (const int32_t *)d_idx;
+    g.out_pose = (double *)d_poses, g.out_xyz = (double *)d_xyz, g.pflag = (uint8_t *)d_point_flags, g.obs = (uint8_t *)d_obs_flags;
+    g.result = (ss_ba_result *)d_result;
+    return ba_run(c, g, n_blocks, problems, views, start_poses, p);
+}
+
+int ss_local_ba_batch_device(ss_ctx *c, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks, int point_rows,
+                             const void *d_right, const void *d_idx, const ss_ba_problem *problems, int n_problems, const ss_proj_view *views,
+                             const double *start_poses, const ss_ba_params *p, void *d_poses, void *d_xyz, void *d_point_flags, void *d_obs_flags,
+                             void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_local_ba_batch_device")) return SS_ERR_STATE;
+    ssk_ba_call g;
+    g.n_frames = c->last_n_frames, g.n_problems = n_problems, g.point_rows = point_rows, g.rows = c->hg.kcap;
+    g.points = (const ss_map_point *)d_points, g.p_skip = (const uint8_t *)d_point_skip, g.np = (const int32_t *)d_n_points;
+    g.kp = c->ws.kps, g.right = (const float *)d_right, g.nk = c->ws.n_kp;
+    const int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
+    g.idx = (const int32_t *)d_idx;
+    g.out_pose = (double *)d_poses, g.out_xyz = (double *)d_xyz, g.pflag = (uint8_t *)d_point_flags, g.obs = (uint8_t *)d_obs_flags;
+    g.result = (ss_ba_result *)d_result;
+    return ba_run(c, g, n_blocks, problems, views, start_poses, p);
+}
+
+int ss_local_ba(ss_ctx *c, const ss_proj_view *views, const double *start, int n_kf, int n_free, const ss_map_point *points, const uint8_t *point_skip,
+                int n_points, const ss_keypoint *kp, const float *right, const int32_t *n_kp, int rows_per_frame, const int32_t *idx, const ss_ba_params *p,
+                double *poses, double *xyz, uint8_t *point_flags, uint8_t *obs_flags, ss_ba_result *result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = ba_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    const ss_ba_problem problem = {0, n_kf, n_free, 0};
+    const std::string msg = ba_problem_error(problem, 0);
+    if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_points < 0 || n_points > SS_GUIDED_MAX_ROWS || rows_per_frame < 1 || rows_per_frame > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "local BA: n_points must be 0 .. SS_GUIDED_MAX_ROWS and rows_per_frame 1 .. SS_GUIDED_MAX_ROWS");
+    if (!views || !start || !kp || !n_kp || !poses || !result || (n_points > 0 && (!points || !idx || !xyz || !point_flags || !obs_flags)))
+        return fail(c, SS_ERR_INVALID_ARG, "local BA: NULL buffer");
+    /* one block of `pr` points, n_kf frames of rows_per_frame rows; `count` is on this stack: no return before the stream has read it */
+    const size_t pr = (size_t)std::max(n_points, 1), np = (size_t)n_points, kf = (size_t)n_kf, kr = kf * (size_t)rows_per_frame;
+    const int32_t count[1] = {n_points};
+    enum { PT, PS, NP, KP, RT, NK, IDX, POSE, XYZ, PF, OF, RES, PIECES };
+    io_piece io[PIECES] = {{points, nullptr, pr * sizeof(ss_map_point), np * sizeof(ss_map_point)},
+                           {point_skip, nullptr, pr, np},
+                           {count, nullptr, sizeof(count), sizeof(count)},
+                           {kp, nullptr, kr * sizeof(ss_keypoint), kr * sizeof(ss_keypoint)},
+                           {right, nullptr, kr * 4, kr * 4},
+                           {n_kp, nullptr, kf * 4, kf * 4},
+                           {idx, nullptr, kf * pr * 4, kf * np * 4},
+                           {nullptr, poses, kf * 12 * sizeof(double), kf * 12 * sizeof(double)},
+                           {nullptr, xyz, pr * 3 * sizeof(double), np * 3 * sizeof(double)},
+                           {nullptr, point_flags, pr, np},
+                           {nullptr, obs_flags, kf * pr, kf * np},
+                           {nullptr, result, sizeof(ss_ba_result), sizeof(ss_ba_result)}};
+    int rc = io_send(c, c->d_ba_io, io, PIECES);
+    if (rc == SS_OK)
+        rc = ss_local_ba_pairs_device(c, io[PT].d, point_skip ? io[PS].d : nullptr, io[NP].d, 1, (int)pr, io[KP].d, right ? io[RT].d : nullptr, io[NK].d, n_kf,
+                                      rows_per_frame, io[IDX].d, &problem, 1, views, start, p, io[POSE].d, io[XYZ].d, io[PF].d, io[OF].d, io[RES].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
+}
+
+int ss_local_ba_points_to_block(ss_ctx *c, const void *d_xyz, const void *d_point_flags, int n_problems, int point_rows, const int32_t *block_of,
+                                void *d_points, int n_blocks)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_problems < 0 || n_blocks < 0 || point_rows < 1 || point_rows > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "local BA points: bad problem, block or row count");
+    const int rc0 = call_count_ok(c, "local BA points", n_problems, "problems");
+    if (rc0 != SS_OK) return rc0;
+    for (int q = 0; q < n_problems; q++) {
+        const int b = block_of ? block_of[q] : q;
+        if (b < 0 || b >= n_blocks)
+            return fail(c, SS_ERR_INVALID_ARG, std::string(block_of ? "block_of[" : "problem [") + std::to_string(q) + "] = " + std::to_string(b) +
+                                                   " names no block of points (" + std::to_string(n_blocks) + ")");
+    }
+    if (n_problems == 0) return SS_OK;
+    if (!d_xyz || !d_point_flags || !d_points) return fail(c, SS_ERR_INVALID_ARG, "local BA points: NULL buffer");
+    const int rc = staged_upload(c, c->ba_block_tab, (size_t)n_problems * sizeof(int32_t), [&](uint8_t *h) {
+        int32_t *t = (int32_t *)h;
+        for (int q = 0; q < n_problems; q++) t[q] = block_of ? block_of[q] : q;
+    });
+    if (rc != SS_OK) return rc;
+    ssk_ba_block_call g;
+    g.n = n_problems, g.point_rows = point_rows;
+    g.xyz = (const double *)d_xyz, g.flags = (const uint8_t *)d_point_flags, g.block_of = c->ba_block_tab.as<int32_t>();
+    g.points = (ss_map_point *)d_points;
+    {
+        stage_timer t(c, "ba_points_to_block", (int64_t)n_problems * point_rows * (1 + 24 + 12));
+        ssk_ba_points_to_block(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
 }
 
 } /* extern "C" */

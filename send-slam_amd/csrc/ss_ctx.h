@@ -156,6 +156,10 @@ struct ss_ctx {
      * check), the host form's device copies, the views of a call (views1, then views2) */
     dev_buf<uint8_t> d_sim3opt_ws, d_sim3opt_io;
     staged_table sim3opt_tab;
+    /* local bundle adjustment: the workspace of a call, the host form's device copies, the tables of a call (problems, the frames'
+     * problems, views, start poses; the block numbers of ss_local_ba_points_to_block) */
+    dev_buf<uint8_t> d_ba_ws, d_ba_io;
+    staged_table ba_tab, ba_block_tab;
     /* rectification: map map_id in its fixed-point form (one allocation each: the xy array, then ab; d == NULL: unset) and the
      * 16-byte aligned buffer ss_extract_stereo_raw remaps both eyes into */
     struct rect_map {

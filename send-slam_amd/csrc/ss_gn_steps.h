@@ -1,8 +1,8 @@
 /*
  * ss_gn_steps.h -- the steps every damped Gauss-Newton of the library shares, whatever its rule (DESIGN.md "Gauss-Newton core"): the
  * tree of a sum, the damped Cholesky solve, the Huber weight, R <- dR.R, the identity and the all-finite test.  The pose-only
- * optimisation (ss_pose_steps.h) and the Sim3 refinement (ss_sim3opt_steps.h) build their rules on it; the kernels, the host twins
- * and the programs under tests/native compile this text.
+ * optimisation (ss_pose_steps.h), the Sim3 refinement (ss_sim3opt_steps.h) and the local bundle adjustment (ss_ba_steps.h) build
+ * their rules on it; the kernels, the host twins and the programs under tests/native compile this text.
  *
  * All arithmetic is double.  Every step is one IEEE operation, left to right as written; every test is in its accepting form, so a
  * NaN fails it.  Compile with -ffp-contract=off.  Division and square root are correctly rounded on both sides (hipcc's default);
@@ -117,6 +117,56 @@ template <int N> SS_HD bool ss_gn_solve(double H[N][N], const double *g, double 
         for (int k = i + 1; k < N; k++) v = v - H[k][i] * delta[k];
         delta[i] = v / H[i][i];
     }
+    return ok;
+}
+
+/* The same text for a run-time order n (the reduced system of the bundle adjustment, ss_ba_steps.h): H is n rows of ld doubles, its
+ * lower triangle filled.  The factor: Cholesky by columns, L over H's lower triangle; every inner sum subtracts in ascending k.
+ * Each entry's subtractions being sequential in k, the rows of a column may be computed in parallel, and a right-looking schedule
+ * (column k taken off every later entry once it is final) gives the same bits.  False when a pivot is not > 0 */
+SS_HD bool ss_gn_chol_n(double *H, int n, int ld)
+{
+    bool ok = true;
+    for (int j = 0; j < n; j++) {
+        double s = H[(size_t)j * ld + j];
+        for (int k = 0; k < j; k++) s = s - H[(size_t)j * ld + k] * H[(size_t)j * ld + k];
+        ok = ok && s > 0.0;
+        H[(size_t)j * ld + j] = sqrt(s);
+        for (int i = j + 1; i < n; i++) {
+            double v = H[(size_t)i * ld + j];
+            for (int k = 0; k < j; k++) v = v - H[(size_t)i * ld + k] * H[(size_t)j * ld + k];
+            H[(size_t)i * ld + j] = v / H[(size_t)j * ld + j];
+        }
+    }
+    return ok;
+}
+
+/* the two triangular solves on the factor: delta (the right-hand side on entry) <- L^-T L^-1 delta */
+SS_HD void ss_gn_subst_n(const double *L, int n, int ld, double *delta)
+{
+    for (int i = 0; i < n; i++) {
+        double v = delta[i];
+        for (int k = 0; k < i; k++) v = v - L[(size_t)i * ld + k] * delta[k];
+        delta[i] = v / L[(size_t)i * ld + i];
+    }
+    for (int i = n - 1; i >= 0; i--) {
+        double v = delta[i];
+        for (int k = i + 1; k < n; k++) v = v - L[(size_t)k * ld + i] * delta[k];
+        delta[i] = v / L[(size_t)i * ld + i];
+    }
+}
+
+/* ss_gn_solve for a run-time order: H's upper triangle filled (overwritten), the gradient g -> delta[0 .. n) */
+SS_HD bool ss_gn_solve_n(double *H, int n, int ld, const double *g, double lambda, double *delta)
+{
+    for (int a = 1; a < n; a++)
+        for (int b = 0; b < a; b++) H[(size_t)a * ld + b] = H[(size_t)b * ld + a];
+    for (int a = 0; a < n; a++) {
+        H[(size_t)a * ld + a] = H[(size_t)a * ld + a] + lambda * (1.0 + H[(size_t)a * ld + a]);
+        delta[a] = -g[a];
+    }
+    const bool ok = ss_gn_chol_n(H, n, ld);
+    ss_gn_subst_n(H, n, ld, delta);
     return ok;
 }
 

@@ -430,6 +430,74 @@ struct ssk_sim3opt_call : ssk_pair_sides {
 };
 void ssk_sim3opt_gather(hipStream_t s, const ssk_sim3opt_call &g);
 void ssk_sim3opt_solve(hipStream_t s, const ssk_sim3opt_call &g);
+/* ss_ba.hip: local bundle adjustment (DESIGN.md "Local bundle adjustment").  Problem q owns the frames prob[q].first_frame .. of the
+ * call and reads block prob[q].point_block; P = point_rows.  Every kernel of the fixed schedule reads its problem's ssk_ba_state and
+ * returns at once when the problem has ended or the round is over.  Poses and points are double-buffered: st.cur names the buffer
+ * of the current state, the other one takes the trial state, and an accepted step flips cur.  obs and pflag are the caller's
+ * output arrays, which carry the rule's bytes from the gather on */
+struct ssk_ba_state {
+    double lambda, cost0, cost_before;
+    int32_t state, status, ended, round_over, cur, pose_small, pose_finite;
+    int32_t n_obs, n_stereo, n_frozen_max;
+    int32_t steps[4], accepted[4];
+};
+struct ssk_ba_meas { /* ss_ba_meas of ss_ba_steps.h */
+    float u, v, ur, scale;
+};
+struct ssk_ba_call {
+    int n_frames = 0, n_problems = 0, point_rows = 0, rows = 0;
+    int max_kf = 0, max_free = 0;          /* the largest of the call's problems */
+    const ss_map_point *points = nullptr; /* [n_blocks][point_rows] */
+    const uint8_t *p_skip = nullptr;      /* [n_blocks][point_rows], or NULL */
+    const int32_t *np = nullptr;
+    const ss_keypoint *kp = nullptr;      /* [n_frames][rows] */
+    const float *right = nullptr;         /* [n_frames][rows], or NULL */
+    const int32_t *nk = nullptr;
+    const int32_t *frame_error = nullptr; /* per frame, or NULL */
+    const int32_t *idx = nullptr;         /* [n_frames][point_rows] */
+    const ss_ba_problem *prob = nullptr;  /* device [n_problems] */
+    const int32_t *frame_prob = nullptr;  /* device [n_frames]: the frame's problem, or -1 */
+    const ss_proj_view *views = nullptr;  /* device [n_frames] */
+    const double *start = nullptr;        /* device [n_frames][12] */
+    ss_ba_params p = {};
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    /* workspace */
+    ssk_ba_meas *meas = nullptr;  /* [n_frames][P] */
+    uint8_t *lin = nullptr;       /* [n_frames][P]: the observation took part in this step's linearisation */
+    double *pose = nullptr;       /* [2][n_frames][12] */
+    double *X = nullptr;          /* [2][n_problems][P][3] */
+    double *WY = nullptr;         /* [n_problems][max_free][36][P]: W (18 planes), then Y */
+    double *Lb = nullptr;         /* [n_problems][9][P]: a point's factor (6 planes), then b */
+    uint8_t *solved = nullptr;    /* [n_problems][P] */
+    double *A = nullptr;          /* [n_problems][(6 max_free)^2]: the upper triangle of S, rows of 6 n_free */
+    double *r = nullptr;          /* [n_problems][6 max_free] */
+    double *dc = nullptr;         /* [n_problems][6 max_free] */
+    double *cost_k = nullptr;     /* [n_problems][max_kf] */
+    int32_t *blk = nullptr;       /* [n_problems][pblocks][4]: per workgroup of points, what a kernel hands to the next */
+    ssk_ba_state *st = nullptr;   /* [n_problems] */
+    /* outputs */
+    double *out_pose = nullptr, *out_xyz = nullptr;
+    uint8_t *pflag = nullptr, *obs = nullptr;
+    ss_ba_result *result = nullptr;
+};
+void ssk_ba_gather(hipStream_t s, const ssk_ba_call &g);                 /* three launches */
+void ssk_ba_cost(hipStream_t s, const ssk_ba_call &g, int round, int trial);
+void ssk_ba_accept(hipStream_t s, const ssk_ba_call &g, int round, int begin);
+void ssk_ba_points(hipStream_t s, const ssk_ba_call &g, int round);
+void ssk_ba_blocks(hipStream_t s, const ssk_ba_call &g, int round);
+void ssk_ba_solve(hipStream_t s, const ssk_ba_call &g);
+void ssk_ba_update(hipStream_t s, const ssk_ba_call &g);
+void ssk_ba_classify(hipStream_t s, const ssk_ba_call &g);
+void ssk_ba_finish(hipStream_t s, const ssk_ba_call &g);                 /* two launches */
+struct ssk_ba_block_call {
+    int n = 0, point_rows = 0;
+    const double *xyz = nullptr;
+    const uint8_t *flags = nullptr;
+    const int32_t *block_of = nullptr; /* device [n] */
+    ss_map_point *points = nullptr;
+};
+void ssk_ba_points_to_block(hipStream_t s, const ssk_ba_block_call &g);
 /* The bookkeeping of SearchBySim3 (the rule: include/sendslam_orb.h).  One workgroup per pair: a base pass over the rows, a barrier,
  * a scatter pass in which every store to one address writes the same value.  marks writes skip1 and skip2; mutual marks the train
  * rows that carry a prior match in taken (workspace, [n_frames][rows]) and writes idx_out and the summary */

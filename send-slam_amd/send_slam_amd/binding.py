@@ -50,7 +50,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_sim3_to_view", "ss_sim3_pairs_device", "ss_sim3_batch_device", "ss_sim3", "ss_pose_opt_host", "ss_pose_opt_pairs_device",
            "ss_pose_opt_batch_device", "ss_pose_opt", "ss_sim3_opt_host", "ss_sim3_opt_pairs_device", "ss_sim3_opt_batch_device",
            "ss_sim3_opt", "ss_sim3_marks_pairs_device", "ss_sim3_mutual_pairs_device", "ss_sim3_marks_batch_device",
-           "ss_sim3_mutual_batch_device", "ss_sim3_to_view21"]
+           "ss_sim3_mutual_batch_device", "ss_sim3_to_view21", "ss_local_ba_host", "ss_local_ba_pairs_device",
+           "ss_local_ba_batch_device", "ss_local_ba", "ss_local_ba_points_to_block"]
 
 
 class OrbParams(C.Structure):
@@ -494,6 +495,70 @@ def pose_opt_host(view, start, scale, points: np.ndarray, kp: np.ndarray, idx: n
     return flags, res[0]
 
 
+# ---- local bundle adjustment (the rule: include/sendslam_orb.h) ----
+SS_BA_MAX_KF, SS_BA_MAX_FREE, SS_BA_MAX_ROUNDS = 64, 32, 4
+
+
+class BaParams(C.Structure):
+    _fields_ = [("chi2_mono", C.c_double), ("chi2_stereo", C.c_double), ("lambda_", C.c_double), ("lambda_factor", C.c_double),
+                ("lambda_min", C.c_double), ("step_eps", C.c_double), ("n_rounds", C.c_int32), ("iterations", C.c_int32 * 4),
+                ("robust_rounds", C.c_int32), ("min_point_obs", C.c_int32), ("check_right", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+# ss_ba_problem: one per problem (a host table); ss_ba_result: one per problem
+BA_PROBLEM_DTYPE = np.dtype([(n, "<i4") for n in ("first_frame", "n_kf", "n_free", "point_block")])
+BA_RESULT_DTYPE = np.dtype([("lambda_", "<f8"), ("cost_before", "<f8"), ("cost_after", "<f8")] +
+                           [(n, "<i4") for n in ("state", "status", "n_obs", "n_stereo", "n_inliers", "n_points_active", "n_frozen_max")] +
+                           [("steps", "<i4", (4,)), ("accepted", "<i4", (4,)), ("reserved", "<i4")])
+
+
+def ba_params(chi2_mono: float = 5.991, chi2_stereo: float = 7.815, lambda_: float = 1e-4, lambda_factor: float = 10.0, lambda_min: float = 1e-9,
+              step_eps: float = 1e-10, n_rounds: int = 2, iterations=(5, 10, 0, 0), robust_rounds: int = 1, min_point_obs: int = 2,
+              check_right: bool = False, reserved=(0, 0, 0, 0)) -> BaParams:
+    """ORB-SLAM2's LocalBundleAdjustment schedule: 5 robust iterations, classification, 10 plain ones on the inliers; ORB-SLAM3's single
+    robust round of 10 is n_rounds=1, iterations=(10,), robust_rounds=1"""
+    its = tuple(iterations) + (0,) * (4 - len(tuple(iterations)))
+    return BaParams(chi2_mono=chi2_mono, chi2_stereo=chi2_stereo, lambda_=lambda_, lambda_factor=lambda_factor, lambda_min=lambda_min,
+                    step_eps=step_eps, n_rounds=n_rounds, iterations=(C.c_int32 * 4)(*its), robust_rounds=robust_rounds,
+                    min_point_obs=min_point_obs, check_right=int(check_right), reserved=(C.c_int32 * 4)(*reserved))
+
+
+def _ba_host_arrays(views, start, points, kp, idx, n_kp, skip, right):
+    """the arrays of one problem, checked against each other: kp [n_kf][rows], idx [n_kf][n_points]"""
+    v = _views_array(views)
+    n_kf = len(v)
+    st = _start_array(start, n_kf)
+    pts, k = np.ascontiguousarray(points, MAP_POINT_DTYPE), np.ascontiguousarray(kp, KP_DTYPE)
+    n_p = len(pts)
+    if k.ndim != 2 or len(k) != n_kf or k.shape[1] < 1:
+        raise ValueError("keypoints are [n_kf][rows_per_frame]")
+    ix = np.ascontiguousarray(idx, np.int32).reshape(n_kf, n_p)
+    nk = np.full(n_kf, k.shape[1], np.int32) if n_kp is None else np.ascontiguousarray(n_kp, np.int32)
+    skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    right = None if right is None else np.ascontiguousarray(right, np.float32)
+    if len(nk) != n_kf or (skip is not None and len(skip) != n_p) or (right is not None and right.shape != k.shape):
+        raise ValueError("views, map points, keypoints, counts and matches differ in length")
+    return v, st, pts, k, ix, nk, skip, right
+
+
+def local_ba_host(views, start, n_free: int, scale, points: np.ndarray, kp: np.ndarray, idx: np.ndarray, params: BaParams, n_kp=None, skip=None,
+                  right=None):
+    """ss_local_ba_host: the whole rule on the host for one problem -> (poses float64 [n_kf][12], xyz float64 [n_points][3], uint8 point
+    flags, uint8 observation flags [n_kf][n_points], one BA_RESULT_DTYPE record); needs no device"""
+    v, st, pts, k, ix, nk, skip, right = _ba_host_arrays(views, start, points, kp, idx, n_kp, skip, right)
+    sc = np.ascontiguousarray(scale, np.float32)
+    n_kf, n_p = len(v), len(pts)
+    poses, xyz = np.empty((n_kf, 12), np.float64), np.empty((n_p, 3), np.float64)
+    pf, of, res = np.empty(n_p, np.uint8), np.empty((n_kf, n_p), np.uint8), np.zeros(1, BA_RESULT_DTYPE)
+    ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+    rc = load().ss_local_ba_host(v.ctypes.data, st.ctypes.data, n_kf, n_free, sc.ctypes.data, len(sc), ptr(pts, n_p), ptr(skip, n_p), n_p,
+                                 k.ctypes.data, ptr(right, 1), nk.ctypes.data, k.shape[1], ptr(ix, n_p), C.byref(params), poses.ctypes.data,
+                                 ptr(xyz, n_p), ptr(pf, n_p), ptr(of, n_p), res.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_local_ba_host refused its arguments")
+    return poses, xyz, pf, of, res[0]
+
+
 class EpiPair(C.Structure):
     """ss_epi_pair: a (keyframe 1 = query, keyframe 2 = train) pair; float32 for the search, double for the triangulation"""
     _fields_ = [("f12", C.c_float * 9), ("ex", C.c_float), ("ey", C.c_float), ("epipole_test", C.c_int32)] + \
@@ -769,6 +834,15 @@ def load():
     lib.ss_sim3_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(Sim3Params)] + [C.c_void_p] * 2
     lib.ss_sim3.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.POINTER(Sim3Params), C.c_void_p,
                                                                                             C.c_void_p]
+    lib.ss_local_ba_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(BaParams)] + [C.c_void_p] * 5
+    lib.ss_local_ba_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + \
+                                            [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(BaParams)] + [C.c_void_p] * 5
+    lib.ss_local_ba_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + \
+                                            [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(BaParams)] + [C.c_void_p] * 5
+    lib.ss_local_ba.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_int, C.c_void_p, C.POINTER(BaParams)] + [C.c_void_p] * 5
+    lib.ss_local_ba_points_to_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     lib.ss_pose_opt_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_void_p, C.POINTER(PoseOptParams), C.c_void_p, C.c_void_p]
     lib.ss_pose_opt_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + \
@@ -1497,6 +1571,63 @@ class OrbContext:
         self._check(self._lib.ss_pose_opt(self._h, v.ctypes.data, st.ctypes.data, ptr(pts, n_p), ptr(skip, n_p), n_p, ptr(k, n_k), ptr(right, n_k),
                                           n_k, ptr(ix, ns), C.byref(params), ptr(flags, ns), res.ctypes.data))
         return flags, res[0]
+
+    # ---- local bundle adjustment: Schur-reduced steps per local map (the rule: include/sendslam_orb.h) ----
+    @staticmethod
+    def _ba_tables(problems, views, start_poses, n_frames):
+        pr = np.ascontiguousarray(problems, BA_PROBLEM_DTYPE).reshape(-1)
+        v = _views_array(views)
+        if n_frames is not None and len(v) != n_frames:
+            raise ValueError("one view per frame")
+        return pr, v, _start_array(start_poses, len(v))
+
+    def local_ba_pairs_device(self, d_points: int, d_n_points: int, n_blocks: int, point_rows: int, d_kp: int, d_n_kp: int, n_frames: int,
+                              rows_per_frame: int, d_idx: int, problems, views, start_poses, params: BaParams, d_poses: int, d_xyz: int,
+                              d_point_flags: int, d_obs_flags: int, d_result: int, d_point_skip: int = 0, d_right: int = 0):
+        """the problems (BA_PROBLEM_DTYPE, a host table) of one call on device arrays: map points and keypoints as for
+        pose_opt_pairs_device, d_idx int32 [n_frames][point_rows]; views and start_poses host tables, one per frame; d_poses float64
+        [n_frames][12], d_xyz float64 [n_problems][point_rows][3], d_point_flags uint8 [n_problems][point_rows], d_obs_flags uint8
+        [n_frames][point_rows], d_result BA_RESULT_DTYPE [n_problems]; asynchronous."""
+        pr, v, st = self._ba_tables(problems, views, start_poses, n_frames)
+        self._check(self._lib.ss_local_ba_pairs_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_skip), C.c_void_p(d_n_points), n_blocks,
+                                                       point_rows, C.c_void_p(d_kp), C.c_void_p(d_right), C.c_void_p(d_n_kp), n_frames,
+                                                       rows_per_frame, C.c_void_p(d_idx), pr.ctypes.data if len(pr) else None, len(pr),
+                                                       v.ctypes.data if n_frames else None, st.ctypes.data if n_frames else None,
+                                                       C.byref(params), C.c_void_p(d_poses), C.c_void_p(d_xyz), C.c_void_p(d_point_flags),
+                                                       C.c_void_p(d_obs_flags), C.c_void_p(d_result)))
+
+    def local_ba_batch_device(self, d_points: int, d_n_points: int, n_blocks: int, point_rows: int, d_idx: int, problems, views, start_poses,
+                              params: BaParams, d_poses: int, d_xyz: int, d_point_flags: int, d_obs_flags: int, d_result: int,
+                              d_point_skip: int = 0, d_right: int = 0):
+        """the same, the keyframes being the frames of the last batch (rows_per_frame = kp_capacity); asynchronous."""
+        pr, v, st = self._ba_tables(problems, views, start_poses, None)
+        self._check(self._lib.ss_local_ba_batch_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_skip), C.c_void_p(d_n_points), n_blocks,
+                                                       point_rows, C.c_void_p(d_right), C.c_void_p(d_idx), pr.ctypes.data if len(pr) else None,
+                                                       len(pr), v.ctypes.data, st.ctypes.data, C.byref(params), C.c_void_p(d_poses),
+                                                       C.c_void_p(d_xyz), C.c_void_p(d_point_flags), C.c_void_p(d_obs_flags), C.c_void_p(d_result)))
+
+    def local_ba(self, views, start, n_free: int, points: np.ndarray, kp: np.ndarray, idx: np.ndarray, params: BaParams, n_kp=None, skip=None,
+                 right=None):
+        """One problem, host arrays in and out -> what local_ba_host returns."""
+        v, st, pts, k, ix, nk, skip, right = _ba_host_arrays(views, start, points, kp, idx, n_kp, skip, right)
+        n_kf, n_p = len(v), len(pts)
+        poses, xyz = np.empty((n_kf, 12), np.float64), np.empty((n_p, 3), np.float64)
+        pf, of, res = np.empty(n_p, np.uint8), np.empty((n_kf, n_p), np.uint8), np.zeros(1, BA_RESULT_DTYPE)
+        ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+        self._check(self._lib.ss_local_ba(self._h, v.ctypes.data, st.ctypes.data, n_kf, n_free, ptr(pts, n_p), ptr(skip, n_p), n_p, k.ctypes.data,
+                                          ptr(right, 1), nk.ctypes.data, k.shape[1], ptr(ix, n_p), C.byref(params), poses.ctypes.data,
+                                          ptr(xyz, n_p), ptr(pf, n_p), ptr(of, n_p), res.ctypes.data))
+        return poses, xyz, pf, of, res[0]
+
+    def local_ba_points_to_block(self, d_xyz: int, d_point_flags: int, n_problems: int, point_rows: int, d_points: int, n_blocks: int,
+                                 block_of=None):
+        """x, y, z of the points of n_problems problems rounded into their blocks of MAP_POINT_DTYPE (block_of: host ints, or problem q
+        into block q); rows flagged 2 and the other fields stay; asynchronous."""
+        bo = None if block_of is None else np.ascontiguousarray(block_of, np.int32)
+        if bo is not None and len(bo) != n_problems:
+            raise ValueError("one block number per problem")
+        self._check(self._lib.ss_local_ba_points_to_block(self._h, C.c_void_p(d_xyz), C.c_void_p(d_point_flags), n_problems, point_rows,
+                                                          None if bo is None else bo.ctypes.data, C.c_void_p(d_points), n_blocks))
 
     # ---- Sim3 refinement: SearchBySim3's bookkeeping and OptimizeSim3 per loop candidate (the rule: include/sendslam_orb.h) ----
     def sim3_opt_pairs_device(self, d_query_xyz: int, d_query_kp: int, d_n_query: int, d_train_xyz: int, d_train_kp: int, d_n_train: int,

@@ -1,0 +1,405 @@
+"""The local bundle adjustment on the CPU: the ABI surface, the host twin (ss_local_ba_host, the text the kernels compile) against the
+reference (tests/ba_ref.py) bit for bit, the reference against an independent optimiser that never forms a Schur complement, both
+Jacobians against central differences, the chi-square thresholds from both sides, the liveness of the shared cases, the refused
+arguments and the steps under the sanitizers."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import ba_cases as BC
+import ba_ref as BR
+import camera_cases as CC
+import pose_cases as PO
+import pose_ref as PR
+import proj_cases as PC
+from send_slam_amd import binding
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32, f64 = np.float32, np.float64
+# Ten times the largest deviation seen between the reference and the independent optimiser (DESIGN.md section 25 holds the measured
+# values): one step's dc and dp relative to the step's largest entry or to 1, the scale of the state (a step near convergence is
+# rounding noise of the gradient), whichever is larger, and the end state of the shared cases in absolute terms
+STEP_BOUND_DC = 5.1e-13    # seen: 5.05e-14 (far_start)
+STEP_BOUND_DP = 8.3e-11    # seen: 8.23e-12 (one_round_of_ten, a step of 932 m)
+END_BOUND_POSE = 9.8e-10   # seen: 9.8e-11 (stereo_mixed_6kf_257)
+END_BOUND_POINT = 9.1e-7   # seen: 9.07e-08 (stereo_mixed_6kf_257, a point two keyframes see)
+
+
+@pytest.fixture(autouse=True)
+def _the_feature_is_there():
+    """every test of this file, those of the reference alone included, is a test of the feature: without its symbols it fails here"""
+    lib = binding.load()
+    for n in ("ss_local_ba_host", "ss_local_ba_pairs_device", "ss_local_ba_batch_device", "ss_local_ba", "ss_local_ba_points_to_block"):
+        assert hasattr(lib, n), n
+
+
+def _host(pr, params, scale=None):
+    p = dict(BR.DEFAULTS, **params)
+    return binding.local_ba_host(pr["views"], pr["start"], pr["n_free"], PC.scale() if scale is None else scale, pr["points"], pr["kp"], pr["idx"],
+                                 binding.ba_params(**p), pr["n_kp"], pr.get("skip"), pr.get("right"))
+
+
+def _same(tag, got, want):
+    for name, g, w in zip(("poses", "xyz", "point flags", "observation flags"), got[:4], want[:4]):
+        assert g.shape == w.shape and g.tobytes() == w.tobytes(), f"{tag}: {name} differ at {np.argwhere(g != w)[:4].tolist()}"
+    for name in BR.RESULT_DTYPE.names:
+        assert got[4][name].tobytes() == want[4][name].tobytes(), f"{tag}: result.{name} {got[4][name]} != {want[4][name]}"
+
+
+def test_abi_surface():
+    text = open(os.path.join(ROOT, "include", "sendslam_orb.h")).read()
+    lib = binding.load()
+    for n in ("ss_local_ba_host", "ss_local_ba_pairs_device", "ss_local_ba_batch_device", "ss_local_ba", "ss_local_ba_points_to_block"):
+        assert n + "(" in text and n in binding.EXPORTS and hasattr(lib, n) and getattr(lib, n).argtypes is not None
+    assert lib.ss_abi_version() == 5
+    assert C.sizeof(binding.BaParams) == 96 and binding.BaParams.n_rounds.offset == 48 and binding.BaParams.reserved.offset == 80
+    assert binding.BA_PROBLEM_DTYPE.itemsize == 16
+    assert binding.BA_RESULT_DTYPE == BR.RESULT_DTYPE and BR.RESULT_DTYPE.itemsize == 88
+    assert BR.RESULT_DTYPE.fields["state"][1] == 24 and BR.RESULT_DTYPE.fields["steps"][1] == 52 and BR.RESULT_DTYPE.fields["reserved"][1] == 84
+    assert (binding.SS_BA_MAX_KF, binding.SS_BA_MAX_FREE, binding.SS_BA_MAX_ROUNDS) == (64, 32, 4)
+    for name, value in (("SS_BA_MAX_KF", 64), ("SS_BA_MAX_FREE", 32), ("SS_BA_MAX_ROUNDS", 4)):
+        assert f"#define {name} {value}" in text
+    p = binding.ba_params()
+    got = {k: (tuple(getattr(p, k)) if k == "iterations" else getattr(p, k)) for k in BR.DEFAULTS}
+    assert got == {k: (int(v) if isinstance(v, bool) else v) for k, v in BR.DEFAULTS.items()}
+
+
+@pytest.mark.parametrize("k", range(len(BC.CASES)), ids=BC.CASE_NAMES)
+def test_host_twin_equals_the_reference_on_the_shared_cases(k):
+    _same(BC.CASE_NAMES[k], _host(BC.case_problem(k), BC.CASES[k]["params"]), BC.reference(k))
+
+
+SHORT = dict(n_rounds=2, iterations=(2, 1, 0, 0))
+
+
+@pytest.mark.parametrize("n_kf,n_free", [(2, 1), (3, 2), (4, 3), (33, 32), (64, 32), (64, 1)])
+def test_host_twin_equals_the_reference_over_the_keyframe_ladder(n_kf, n_free):
+    pr = BC.make_problem(seed=100 + n_kf + n_free, n_kf=n_kf, n_free=n_free, n_points=70, p_obs=0.5 if n_kf > 8 else 0.9, n_out=6 if n_kf > 2 else 0, stereo_every=3)
+    want = BC.solve(pr, dict(SHORT, check_right=True))
+    assert want[4]["state"] == 0 and want[4]["n_stereo"] > 0 and want[4]["steps"][:2].tolist() == [2, 1]
+    _same(f"{n_kf} keyframes, {n_free} free", _host(pr, dict(SHORT, check_right=True)), want)
+
+
+@pytest.mark.parametrize("n_points", [0, 1, 2, 255, 256, 257, 513])
+def test_host_twin_equals_the_reference_over_the_point_ladder(n_points):
+    pr = BC.make_problem(seed=200 + n_points, n_kf=4, n_free=2, n_points=n_points, rows=max(n_points, 3) + 5, n_out=min(n_points // 16, 8))
+    want = BC.solve(pr, SHORT)
+    assert want[4]["state"] == (1 if n_points == 0 else 0) and want[4]["n_points_active"] == (n_points if n_points < 3 else want[4]["n_points_active"])
+    _same(f"{n_points} points", _host(pr, SHORT), want)
+
+
+def test_host_twin_equals_the_reference_on_a_full_block_with_skip_bytes():
+    pr = BC.make_problem(seed=300, n_kf=3, n_free=1, n_points=binding.SS_GUIDED_MAX_ROWS, p_obs=0.8, n_out=100, skip_every=5)
+    want = BC.solve(pr, SHORT)
+    assert want[4]["state"] == 0 and (want[2][1::5] == 2).all() and (want[1][1::5] == 0.0).all() and (want[3][:, 1::5] == 2).all()
+    assert want[4]["n_points_active"] > 8000 and want[4]["n_obs"] > 30000
+    _same("16384 rows", _host(pr, SHORT), want)
+
+
+def test_failures_on_the_reference_and_the_host_twin():
+    """points behind a camera take no part and are classified out; a NaN keypoint makes every sum of its keyframe NaN, which ends in
+    state 2 with the start returned; a NaN point is no point; a rolled start ends in state 4; a start that is not finite in state 2"""
+    base = BC.make_problem(seed=400, n_kf=4, n_free=2, n_points=90, p_obs=1.0, n_out=8)
+    behind = dict(base, points=base["points"].copy())
+    behind["points"]["z"][5:15] = -behind["points"]["z"][5:15]
+    nan_kp = dict(base, kp=base["kp"].copy())
+    nan_kp["kp"]["y"][0, base["idx"][0, 20]] = np.nan
+    nan_point = dict(base, points=base["points"].copy())
+    nan_point["points"]["y"][33] = np.nan
+    rolled = dict(base, start=base["start"].copy())
+    rolled["start"][0] = PO.start_of(PC.rot(0.0, 0.0, 3.0) @ base["start"][0][:9].reshape(3, 3), base["start"][0][9:])
+    nan_start = dict(base, start=base["start"].copy())
+    nan_start["start"][3, 4] = np.nan
+    for name, pr, state in (("behind", behind, 0), ("a NaN keypoint", nan_kp, 2), ("a NaN point", nan_point, 0), ("a rolled start", rolled, 4), ("a NaN start", nan_start, 2)):
+        want = BC.solve(pr, {})
+        assert want[4]["state"] == state, (name, want[4])
+        assert np.isfinite(want[0]).all() and np.isfinite(want[1]).all(), name
+        _same(name, _host(pr, {}), want)
+    want = BC.solve(behind, {})
+    assert (want[3][:, 5:15] == 1).all() and (want[2][5:15] == 1).all()  # every observation of a point behind the cameras is out
+    want = BC.solve(nan_point, {})
+    assert want[2][33] == 2 and (want[3][:, 33] == 2).all() and (want[1][33] == 0.0).all()
+    want = BC.solve(nan_kp, {})
+    start = np.array([list(R) + list(t) for R, t in (PR.start_pose(s)[:2] for s in nan_kp["start"])])
+    assert want[0].tobytes() == start.tobytes() and want[4]["steps"].sum() == 0  # the first solve meets a NaN pivot
+    want = BC.solve(nan_start, {})
+    assert want[0][3].tolist() == [1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0] and want[4]["steps"].sum() == 0
+
+
+# ---- the independent optimiser -------------------------------------------------------------------------------------------------------
+def _skew(p):
+    return np.array([[0.0, -p[2], p[1]], [p[2], 0.0, -p[0]], [-p[1], p[0], 0.0]])
+
+
+def _residual(cam, R, t, X, o, i):
+    """(residual, projection Jacobian, camera point) of observation i of a keyframe, in matrix form"""
+    fx, fy, cx, cy, bf = (float(cam[n]) for n in ("fx", "fy", "cx", "cy", "bf"))
+    pc = R @ X + t
+    x, y, z = pc
+    r = [o["u"][i] - (fx * x / z + cx), o["v"][i] - (fy * y / z + cy)]
+    Jp = [[fx / z, 0.0, -fx * x / z ** 2], [0.0, fy / z, -fy * y / z ** 2]]
+    if o["stereo"][i]:
+        r.append(o["ur"][i] - (fx * x / z + cx - bf / z))
+        Jp.append([fx / z, 0.0, -(fx * x - bf) / z ** 2])
+    return np.array(r), np.array(Jp), pc
+
+
+def _full_step(frames, cams, poses, X, lin, solved, lam, robust, n_free, p):
+    """one damped step on the un-reduced normal equations: the full Jacobian stacked row by row, numpy.linalg.solve, no Schur
+    complement -> (dc [6 n_free], dp [P][3] with zeros where a point does not move)"""
+    col = {i: 6 * n_free + 3 * j for j, i in enumerate(np.flatnonzero(solved))}
+    n = 6 * n_free + 3 * len(col)
+    rows, rhs, wts = [], [], []
+    for k, o in enumerate(frames):
+        R, t = np.array(poses[k][0], f64).reshape(3, 3), np.array(poses[k][1], f64)
+        for i in np.flatnonzero(lin[k]):
+            r, Jp, pc = _residual(cams[k], R, t, X[i], o, i)
+            e2 = o["w"][i] * float(r @ r)
+            d = np.sqrt(p["chi2_stereo"] if o["stereo"][i] else p["chi2_mono"])
+            w = o["w"][i] * d / np.sqrt(e2) if robust and e2 > d * d else o["w"][i]
+            J = np.zeros((len(r), n))
+            if k < n_free:
+                J[:, 6 * k:6 * k + 6] = -Jp @ np.hstack([-_skew(pc), np.eye(3)])
+            if i in col:
+                J[:, col[i]:col[i] + 3] = -Jp @ R
+            rows.append(J), rhs.append(r), wts.append(np.full(len(r), w))
+    J, r, w = np.vstack(rows), np.concatenate(rhs), np.concatenate(wts)
+    H = J.T @ (w[:, None] * J)
+    H[np.diag_indices(n)] += lam * (1.0 + np.diag(H))
+    delta = np.linalg.solve(H, -(J.T @ (w * r)))
+    dp = np.zeros((len(X), 3))
+    for i, c in col.items():
+        dp[i] = delta[c:c + 3]
+    return delta[:6 * n_free], dp
+
+
+def _independent_run(pr, p):
+    """the whole schedule with _full_step: its own cost, the rule's accept test and classification -> (poses, X, the steps' (dc, dp))"""
+    X, is_point, frames = BR.gather(pr["points"], pr["kp"], pr["idx"], pr["n_kp"], PC.scale(), pr.get("skip"), pr.get("right"), p["check_right"])
+    cams = [PR.camera(v, p["chi2_mono"], p["chi2_stereo"]) for v in pr["views"]]
+    n_kf, n_free = len(frames), pr["n_free"]
+    poses = [PR.start_pose(s)[:2] for s in pr["start"]]
+    obs = [o["obs"].copy() for o in frames]
+    active = is_point & (sum(m.astype(int) for m in obs) >= p["min_point_obs"])
+
+    def chi(k, i, ps, Xs):
+        r, _, pc = _residual(cams[k], np.array(ps[k][0], f64).reshape(3, 3), np.array(ps[k][1], f64), Xs[i], frames[k], i)
+        return frames[k]["w"][i] * float(r @ r) if pc[2] > 0 else PR.BEHIND
+
+    def cost(ps, Xs, robust):
+        total = 0.0
+        for k in range(n_kf):
+            for i in np.flatnonzero(obs[k] & active):
+                e2 = chi(k, i, ps, Xs)
+                d = np.sqrt(p["chi2_stereo"] if frames[k]["stereo"][i] else p["chi2_mono"])
+                total += e2 if not robust or e2 <= d * d else 2 * d * np.sqrt(e2) - d * d
+        return total
+
+    lam, steps = p["lambda_"], []
+    for rnd in range(p["n_rounds"]):
+        robust = rnd < p["robust_rounds"]
+        c0 = cost(poses, X, robust)
+        for _ in range(p["iterations"][rnd]):
+            lin = [obs[k] & active & ((np.array(poses[k][0], f64).reshape(3, 3) @ X.T)[2] + poses[k][1][2] > 0) for k in range(n_kf)]
+            dc, dp = _full_step(frames, cams, poses, X, lin, active, lam, robust, n_free, p)
+            steps.append((dc, dp))
+            trial = list(poses)
+            for k in range(n_free):
+                e = PR.exp([f64(v) for v in dc[6 * k:6 * k + 6]])
+                trial[k] = PR.update(e[0], e[1], poses[k][0], poses[k][1])
+            Xt = X + dp
+            c1 = cost(trial, Xt, robust)
+            if np.isfinite(c1) and c1 <= c0:
+                small = max(np.abs(dc).max(), np.abs(dp).max()) < p["step_eps"]
+                lam, c0, poses, X = max(lam / p["lambda_factor"], p["lambda_min"]), c1, trial, Xt
+                if small:
+                    break
+            else:
+                lam *= p["lambda_factor"]
+        for k in range(n_kf):
+            for i in np.flatnonzero(obs[k] & active):
+                if not chi(k, i, poses, X) <= (p["chi2_stereo"] if frames[k]["stereo"][i] else p["chi2_mono"]):
+                    obs[k][i] = False
+        active &= sum(m.astype(int) for m in obs) >= p["min_point_obs"]
+    return np.array([list(R) + list(t) for R, t in poses], f64), X, steps
+
+
+@pytest.mark.parametrize("k", range(len(BC.CASES)), ids=BC.CASE_NAMES)
+def test_reference_against_an_independent_optimiser(k):
+    """every step of the reference from the state it was linearised at, and the end state of the whole schedule"""
+    pr, p = BC.case_problem(k), BC.CASES[k]["params"]
+    poses, xyz, pflag, oflag, res, trace = BC.reference(k)
+    _, _, frames = BR.gather(pr["points"], pr["kp"], pr["idx"], pr["n_kp"], PC.scale(), pr.get("skip"), pr.get("right"), p["check_right"])
+    cams = [PR.camera(v, p["chi2_mono"], p["chi2_stereo"]) for v in pr["views"]]
+    worst_dc = worst_dp = 0.0
+    for step in [t for t in trace if t["kind"] == "step"]:
+        dc, dp = _full_step(frames, cams, step["poses"], step["X"], step["lin"], step["solved"], float(step["lam"]), step["robust"], pr["n_free"], p)
+        worst_dc = max(worst_dc, np.abs(dc - step["dc"]).max() / max(1.0, np.abs(step["dc"]).max()))
+        worst_dp = max(worst_dp, np.abs(dp - step["dp"]).max() / max(1.0, np.abs(step["dp"]).max()))
+    end_poses, end_X, _ = _independent_run(pr, p)
+    moved = pflag == 0
+    worst_pose, worst_point = np.abs(end_poses - poses).max(), np.abs(end_X - xyz)[moved].max()
+    print(f"{BC.CASE_NAMES[k]}: step dc {worst_dc:.3g} dp {worst_dp:.3g}; end poses {worst_pose:.3g} points {worst_point:.3g}")
+    assert worst_dc <= STEP_BOUND_DC and worst_dp <= STEP_BOUND_DP
+    assert worst_pose <= END_BOUND_POSE and worst_point <= END_BOUND_POINT
+
+
+# ---- the Jacobians, the thresholds ----------------------------------------------------------------------------------------------------
+def test_both_jacobians_against_central_differences():
+    pr = BC.make_problem(seed=500, n_kf=2, n_free=1, n_points=40, p_obs=1.0, stereo_every=1, cams=[CC.A, CC.B])
+    X, _, frames = BR.gather(pr["points"], pr["kp"], pr["idx"], pr["n_kp"], PC.scale(), None, pr["right"], True)
+    assert frames[0]["stereo"].all()
+    h = 1e-6
+    for k in range(2):
+        c = PR.camera(pr["views"][k], 5.991, 7.815)
+        R, t, _ = PR.start_pose(pr["start"][k])
+        o = BR.with_points(frames[k], X)
+        _, res, J = PR.jacobians(o, c, R, t)
+        Jp = BR.point_rows(J, R)
+        for a in range(6):  # the pose rows: the residuals under exp(delta).pose
+            d = [f64(0.0)] * 6
+            side = {}
+            for sign in (+1, -1):
+                d[a] = f64(sign * h)
+                dR, dt = PR.exp(d)
+                side[sign] = PR.jacobians(o, c, *PR.update(dR, dt, R, t))[1]
+            for row in range(3):
+                fd = (side[1][row] - side[-1][row]) / (2 * h)
+                an = np.zeros(len(fd)) if J[row][a] is None else J[row][a]
+                assert np.abs(fd - an).max() < 1e-5 * max(1.0, np.abs(an).max()), (k, row, a)
+        for b in range(3):  # the point rows: the residuals under X + delta
+            side = {}
+            for sign in (+1, -1):
+                Xs = X.copy()
+                Xs[:, b] += sign * h
+                side[sign] = PR.jacobians(BR.with_points(frames[k], Xs), c, R, t)[1]
+            for row in range(3):
+                fd = (side[1][row] - side[-1][row]) / (2 * h)
+                assert np.abs(fd - Jp[row][b]).max() < 1e-5 * max(1.0, np.abs(Jp[row][b]).max()), (k, row, b)
+
+
+def _axis_problem(d, e=None):
+    """three keyframes at the identity (the first free), four points seen exactly by all of them, but point 0 lies on the axis and
+    keyframe 0 sees it d px to the right (and, with e, with a right coordinate e px off).  lambda = 1e300 keeps every step below
+    1e-290, so the chi-square of that observation is w * d * d exactly"""
+    z = 4.0
+    xyz = np.array([[0.0, 0.0, z], [1.0, 0.5, z], [-1.0, 0.5, z], [0.5, -1.0, z]], f32)
+    u, v = PC.FX * xyz[:, 0] / z + PC.CX, PC.FY * xyz[:, 1] / z + PC.CY
+    ur = u - PC.BF / z
+    kp = np.stack([BC.G.kp_rows(u.astype(f32), v.astype(f32), np.zeros(4, int)) for _ in range(3)])
+    right = np.full((3, 4), -1.0, f32)
+    kp["x"][0, 0] += d
+    if e is not None:
+        right[0, 0] = ur[0] + e
+    eye = PO.start_of(np.eye(3), np.zeros(3))
+    return {"views": np.array([PO.view()] * 3), "start": np.stack([eye] * 3), "n_free": 1, "points": PO.points_of(xyz), "kp": kp,
+            "idx": np.tile(np.arange(4, dtype=np.int32), (3, 1)), "right": right, "skip": None, "n_kp": np.full(3, 4, np.int32)}
+
+
+def test_chi_square_thresholds_from_both_sides():
+    """an outlier iff not chi2 <= th: at the threshold an inlier, one ulp below it an outlier, for both kinds"""
+    base = dict(lambda_=1e300, n_rounds=1, iterations=(2, 0, 0, 0))
+    for kind, pr in (("mono", _axis_problem(2.5)), ("stereo", _axis_problem(2.0, 1.5))):  # chi2 = 6.25 = (4 + 0) + 2.25
+        for th, flag in ((6.25, 0), (np.nextafter(6.25, 0.0), 1), (np.nextafter(6.25, 7.0), 0)):
+            p = dict(base, chi2_mono=float(th)) if kind == "mono" else dict(base, chi2_stereo=float(th), chi2_mono=1.0, check_right=True)
+            want = BC.solve(pr, p)
+            assert want[3][0].tolist() == [flag, 0, 0, 0] and (want[3][1:] == 0).all() and want[4]["state"] == 0, (kind, th, want[3])
+            assert want[4]["n_stereo"] == (1 if kind == "stereo" else 0) and want[4]["n_inliers"] == 12 - flag and want[4]["n_points_active"] == 4
+            _same(f"{kind} threshold {th!r}", _host(pr, p), want)
+    # with three observations wanted per point, the point that lost one becomes inactive
+    p = dict(base, chi2_mono=1.0, min_point_obs=3)
+    want = BC.solve(_axis_problem(2.5), p)
+    assert want[2].tolist() == [1, 0, 0, 0] and want[4]["n_points_active"] == 3
+    _same("too few inliers", _host(_axis_problem(2.5), p), want)
+
+
+# ---- liveness -------------------------------------------------------------------------------------------------------------------------
+def test_shared_cases_are_live():
+    """on the reference: round 0 removes every planted gross outlier; a step is rejected and lambda rises; a round ends early; no
+    point freezes; on the noise-free scene the free poses return to the ground truth"""
+    rejected = early = False
+    for k, case in enumerate(BC.CASES):
+        pr, p = BC.case_problem(k), case["params"]
+        poses, xyz, pflag, oflag, res, trace = BC.reference(k)
+        steps = [t for t in trace if t["kind"] == "step"]
+        assert res["state"] == 0 and res["n_frozen_max"] == 0 and res["n_obs"] == int((pr["idx"] >= 0).sum() - (0 if pr["skip"] is None else (pr["idx"][:, pr["skip"] != 0] >= 0).sum()))
+        planted = pr["planted"] if pr["skip"] is None else pr["planted"] & (pr["skip"] == 0)
+        assert (oflag[planted] == 1).all() and [t for t in trace if t["kind"] == "classify"][0]["removed"] >= planted.sum()
+        assert (res["n_stereo"] > 0) == bool(p["check_right"])
+        for a, b in zip(steps, steps[1:]):
+            if not a["accepted"] and a["round"] == b["round"]:
+                assert b["lam"] == a["lam"] * p["lambda_factor"] and b["X"].tobytes() == a["X"].tobytes()
+                rejected = True
+        early = early or any(res["steps"][r] < p["iterations"][r] for r in range(p["n_rounds"]))
+        assert res["steps"].sum() == len(steps) and res["accepted"].sum() == sum(t["accepted"] for t in steps)
+    assert rejected and early
+    k = BC.CASE_NAMES.index("noise_free")
+    pr = BC.case_problem(k)
+    poses, xyz, pflag, oflag, res, _ = BC.reference(k)
+    truth, txyz = pr["truth"]
+    nf = pr["n_free"]
+    before, after = np.abs(pr["start"][:nf] - truth[:nf]).max(), np.abs(poses[:nf] - truth[:nf]).max()
+    print(f"noise-free: pose error {before:.3g} -> {after:.3g}, point error -> {np.abs(xyz - txyz).max():.3g}")
+    assert before > 0.01 and after < 1e-5 and np.abs(xyz - txyz).max() < 1e-4  # the keypoints are float32: 1e-5 px of them is the floor
+    assert poses[nf:].tobytes() == np.array([list(R) + list(t) for R, t in (PR.start_pose(s)[:2] for s in pr["start"][nf:])]).tobytes()
+
+
+def test_the_frozen_point_freezes_and_only_it():
+    pr = BC.frozen_problem()
+    trace = []
+    want = BC.solve(pr, BC.FROZEN_PARAMS, trace=trace)
+    steps = [t for t in trace if t["kind"] == "step"]
+    assert want[4]["state"] == 0 and want[4]["n_frozen_max"] == 1 and len(steps) > 0
+    for t in steps:
+        assert t["active"][0] and not t["solved"][0] and t["solved"][1:].all() and (t["dp"][0] == 0.0).all()
+    assert want[1][0].tolist() == [0.0, 0.0, 4.0] and want[2][0] == 0  # it never moved and stays a point
+    _same("frozen", _host(pr, BC.FROZEN_PARAMS), want)
+    # under a lambda that is not 0 it moves like any other
+    assert BC.solve(pr, {})[4]["n_frozen_max"] == 0
+
+
+# ---- refused arguments ------------------------------------------------------------------------------------------------------------------
+def test_refused_arguments():
+    pr = BC.case_problem(0)
+    nan = float("nan")
+    args = lambda p=None, n_free=None, scale=None: (pr["views"], pr["start"], pr["n_free"] if n_free is None else n_free, PC.scale() if scale is None else scale,  # noqa: E731
+                                                    pr["points"], pr["kp"], pr["idx"], p or binding.ba_params(), pr["n_kp"])
+    for kw in (dict(chi2_mono=0.0), dict(chi2_mono=nan), dict(chi2_stereo=float("inf")), dict(lambda_=-1.0), dict(lambda_=nan), dict(lambda_factor=1.0),
+               dict(lambda_factor=nan), dict(lambda_min=-1e-9), dict(step_eps=-1e-10), dict(n_rounds=0), dict(n_rounds=5), dict(iterations=(0, 10, 0, 0)),
+               dict(iterations=(5, 33, 0, 0)), dict(robust_rounds=-1), dict(robust_rounds=5), dict(min_point_obs=0), dict(reserved=(0, 0, 0, 1)), dict(reserved=(1, 0, 0, 0))):
+        with pytest.raises(binding.OrbError) as e:
+            binding.local_ba_host(*args(binding.ba_params(**kw)))
+        assert e.value.code == binding.SS_ERR_INVALID_ARG, kw
+    binding.local_ba_host(*args(binding.ba_params(n_rounds=1, iterations=(1, 99, 0, 0))))  # only the rounds that run are checked
+    for n_free in (0, 8, 9, -1):  # n_free == n_kf leaves no fixed keyframe
+        with pytest.raises(binding.OrbError):
+            binding.local_ba_host(*args(n_free=n_free))
+    for levels in (np.zeros(0, f32), np.ones(17, f32)):
+        with pytest.raises(binding.OrbError):
+            binding.local_ba_host(*args(scale=levels))
+    big = BC.make_problem(seed=600, n_kf=65, n_free=33, n_points=4, p_obs=1.0)
+    for n_kf, n_free in ((65, 32), (64, 33), (34, 33)):  # the bounds + 1
+        with pytest.raises(binding.OrbError):
+            binding.local_ba_host(big["views"][:n_kf], big["start"][:n_kf], n_free, PC.scale(), big["points"], big["kp"][:n_kf], big["idx"][:n_kf], binding.ba_params())
+    lib = binding.load()
+    p = binding.ba_params()
+    assert lib.ss_local_ba_pairs_device(None, None, None, None, 1, 1, None, None, None, 0, 1, None, None, 0, None, None, C.byref(p), None, None, None, None, None) == binding.SS_ERR_INVALID_ARG
+    assert lib.ss_local_ba_batch_device(None, None, None, None, 1, 1, None, None, None, 0, None, None, C.byref(p), None, None, None, None, None) == binding.SS_ERR_INVALID_ARG
+    assert lib.ss_local_ba(None, None, None, 2, 1, None, None, 0, None, None, None, 1, None, C.byref(p), None, None, None, None, None) == binding.SS_ERR_INVALID_ARG
+    assert lib.ss_local_ba_points_to_block(None, None, None, 0, 1, None, None, 0) == binding.SS_ERR_INVALID_ARG
+    assert lib.ss_local_ba_host(None, None, 2, 1, None, 0, None, None, 0, None, None, None, 1, None, None, None, None, None, None, None) == binding.SS_ERR_INVALID_ARG
+
+
+def test_steps_under_address_and_undefined_sanitizers(tmp_path):
+    """tests/native/ba_steps_asan.cpp: its own main, the steps header, -fsanitize=address,undefined; run as a child process with the
+    environment as it is"""
+    exe = str(tmp_path / "ba_steps_asan")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "send-slam_amd", "csrc"), "-o", exe,
+                           os.path.join(ROOT, "tests", "native", "ba_steps_asan.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-4000:]
+    assert int(out.stdout.split()[1]) > 40000

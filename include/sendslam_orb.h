@@ -47,6 +47,8 @@
  *   ss_sim3_opt_* /            the rest of ORBmatcher::SearchBySim3 (the skip marks of its two projection searches and their
  *   ss_sim3_marks_* /          agreement test) and Optimizer::OptimizeSim3 of LoopClosing::DetectCommonRegionsFromBoW, starting from
  *   ss_sim3_mutual_*           the result ss_sim3_* left in device memory
+ *   ss_pnp_*                   MLPnPsolver's RANSAC of Tracking::Relocalization: a pose from the 2D-3D matches of SearchByBoW against
+ *                              each relocalisation candidate, with no prior
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
  *   ss_last_error              the cerr diagnostics of the shim (:457-469, :523-551)
  *
@@ -245,7 +247,8 @@ typedef struct {
  * ss_extract, device match against the initial / previous frame's descriptors (th 50, ratio
  * 0.9), then host double-precision geometry (csrc/ss_track.h: two-view initialisation, pose-only
  * optimisation, triangulation).  Requires ss_set_calibration (fx fy cx cy k1 k2 p1 p2 are used).
- * No keyframes, local mapping, loop closing or relocalisation. */
+ * No keyframes, local mapping or loop closing.  Relocalisation: the link exists (ss_pnp_*, below);
+ * ss_track itself still re-initialises a lost tracker from the next frame. */
 int ss_track(ss_ctx *ctx, int camera_id, const uint8_t *pix, int width, int height, int channels,
              int row_stride, double timestamp, ss_pose *out);
 /* Several cameras on one context: every camera id gets its own tracker state (reference, previous frame, motion model)
@@ -1515,6 +1518,128 @@ int ss_local_ba(ss_ctx *ctx, const ss_proj_view *views, const double *start, int
  * Asynchronous. */
 int ss_local_ba_points_to_block(ss_ctx *ctx, const void *d_xyz, const void *d_point_flags, int n_problems, int point_rows,
                                 const int32_t *block_of, void *d_points, int n_blocks);
+
+/* ---- PnP RANSAC: a pose from 2D-3D matches with no prior, MLPnPsolver (Urban et al. 2016) as Tracking::Relocalization runs it on
+ * the matches of SearchByBoW against each relocalisation candidate, for every candidate of a call at once.  The upstream source is
+ * not in the reference tree.  This is the library's own restatement and parity with the real binary stays unpinned, as for the Sim3
+ * RANSAC.  tests/pnp_ref.py is its normative statement; DESIGN.md section 26.  An addition to ABI 5: nothing existing changes -----
+ * - Every step is one IEEE operation, left to right as written, with no contraction: float32 in steps 1 and 3e, double in 3b - 3d.
+ * - Every test is written in its accepting form, so a NaN fails it.  Division and sqrt are the only library operations.
+ * - Host and device agree bit for bit, for any number of problems in a call and in any order.
+ * One problem q: the keypoints of a frame (ss_keypoint; x, y, octave are read; taken as undistorted), a block of ss_map_point (x, y,
+ * z are read) with an optional skip byte each (fusion's convention), a camera (fx, fy, cx, cy of an ss_proj_view; nothing else of
+ * it is read) and idx[i], the point row matched to keypoint row i, or < 0: what ss_match_bow_pairs_device writes, and
+ * ss_pose_opt's idx_by_row = 1 form.
+ * 1. Correspondences.  Rows i < n_kp in ascending order; (i, j = idx[i]) is kept iff 0 <= j < n_points, point j is not skipped and
+ *    0 <= octave_i < n_levels.  The kept ones are numbered 0 .. N-1 in that order.  Each carries six float32 values: X Y Z of the
+ *    point, u v of the keypoint and max = chi2 * (s*s) with s = scale[octave_i]; the model reads s and j of its six as well.
+ * 2. State 1: N < 6 or N < min_inliers.  There is no model.
+ * 3. Hypothesis t, 0 <= t < max_iterations; each is independent of the others.
+ *    a. Draws.  Six draws without replacement over the virtual array 0 .. N-1 under the swap-with-last rule of ss_sim3_* step 3a
+ *       with its mix32: draw k (0 .. 5) takes r = mix32(seed, q, 6t + k) and j = (uint64(r) * (N - k)) >> 32; the value at slot j
+ *       is drawn, and slot j then receives the value at slot N-1-k.  q is the problem's number in the call.
+ *    b. Linear model, in double from the float32 inputs widened.  Bearing of draw i: xn = (u - cx) / fx, yn = (v - cy) / fy,
+ *       n = sqrt((xn*xn + yn*yn) + 1.0), b_i = (xn / n, yn / n, 1.0 / n).  O = (((((X0 + X1) + X2) + X3) + X4) + X5) / 6.0 per
+ *       component, draws in draw order; d_i = (X_i - O, 1.0).  P_i[r][c] = (r == c ? 1.0 : 0.0) - b_ir*b_ic.  The twelve unknowns
+ *       are the columns c1 c2 c3 of R^ and then t^: unknown 3a + r is component r of column a.  Entry (3a + r, 3e + c) of the
+ *       symmetric H is the sum over the six draws, in draw order starting from the first term, of (d_ia*d_ie) * P_i[r][c]: the
+ *       normal matrix of MLPnP's tangent-plane residuals under identity covariance, which does not depend on the choice of
+ *       null-space basis, so none is formed.  trace = ((H00 + H11) + ...) + H_11,11 in ascending order; H_kk += 1e-13 * trace.  One
+ *       Cholesky by columns (s = H_jj - the squares in ascending k, L_jj = sqrt(s), L_ij = (H_ij - sum in ascending k) / L_jj); a
+ *       pivot that is not > 0 makes the model the zero model.  x starts as twelve times 1.0 / sqrt(12.0); six times: forward then
+ *       backward substitution on the factor (each entry subtracts in ascending k, then divides by the diagonal), n =
+ *       sqrt(((x0*x0 + x1*x1) + ...) + x11*x11), x_k = x_k / n.  The count is fixed; there is no convergence test.  Sign: with
+ *       y_i[r] = ((x[r]*d_i0 + x[3+r]*d_i1) + x[6+r]*d_i2) + x[9+r] and f_i = (b_i0*y_i0 + b_i1*y_i1) + b_i2*y_i2, if
+ *       ((((f_0 + f_1) + f_2) + f_3) + f_4) + f_5 < 0 all twelve are negated.  Scale: n_a = sqrt((x[3a]*x[3a] + x[3a+1]*x[3a+1]) +
+ *       x[3a+2]*x[3a+2]), s = 3.0 / ((n_0 + n_1) + n_2).  R is the rotation nearest to R^: Horn's quaternion exactly as ss_sim3_*
+ *       step 3b has it (N, SS_TRI_SWEEPS sweeps, the largest diagonal entry, the nine polynomial entries) with M[i][j] = x[3i + j],
+ *       the columns of R^ as Pr1 against the unit vectors as Pr2; it is always a proper rotation.  tcw[r] = s*x[9+r] -
+ *       ((R[r][0]*O0 + R[r][1]*O1) + R[r][2]*O2).
+ *    c. Refinement on the six: refine_steps plain (non-robust) steps of ss_pose_opt_* step 3 with its own functions: each draw an
+ *       observation with w = 1.0 / (s*s) and no right coordinate; each of the 26 sums starts at +0.0 and adds the terms of the draws
+ *       with z > 0 in draw order; the solve with `lambda`, the exponential and the update as there.  A step the pose rule refuses
+ *       (a pivot not > 0, a step above pi) or that leaves an entry not finite ends the refinement; the hypothesis keeps the pose it
+ *       had before that step.  A model that is already the zero model by (d) is not refined.
+ *    d. The record.  rcw and tcw in double, and rounded to float32 once.  If any of the twelve floats is not finite, the Cholesky
+ *       met a pivot not > 0, the linear pose has an entry that is not finite, or two of the six share a point row, the model is
+ *       the zero model, all 0: no correspondence passes it.
+ *    e. Count, in float32.  Y = R.X + t, each component ((r0*X + r1*Y) + r2*Z) + t; correspondence n is an inlier iff Y.z > 0 and,
+ *       with invz = 1.0f / Y.z, qu = fx*Y.x*invz + cx, qv = fy*Y.y*invz + cy (two products, then the sum),
+ *       (u - qu)*(u - qu) + (v - qv)*(v - qv) < max.  count[t] is an integer.
+ * 4. Selection.  The winner is the hypothesis with the LARGEST count, the smallest t among equals; it must also satisfy
+ *    count >= min_inliers and (float)count >= min_ratio * (float)N.  State 0: the double model, inlier[i] = 1 for the keypoint
+ *    rows of its inliers, n_inliers, iteration = t.  State 2, the best hypothesis does not qualify: model and flags all 0,
+ *    iteration -1.  best_inliers = max count[t] in states 0 and 2, 0 in state 1.
+ * Deviations from upstream: the draw stream (DUtils::Random there); no covariance (identity); no planar branch (upstream switches
+ * to nine unknowns only when the points' scatter has rank exactly 2; a planar set here gives an arbitrary finite model, or the zero
+ * model, that the count votes down); the scale is the mean of the column norms (a cube root through pow there); the rotation comes
+ * from Horn's quaternion (an SVD there); the refinement minimises pixel error with the pose rule's step (five Gauss-Newton steps on
+ * tangent-plane residuals there); every hypothesis is evaluated and the best is taken (upstream runs iterate(5) in a loop with an
+ * early exit at the first hypothesis over the threshold whose Refine() holds); there is no final refit over all inliers: the
+ * ss_pose_opt_* call that follows does that job from result.rcw / tcw; the smallest eigenvector by inverse iteration on a shifted
+ * Cholesky factor (an SVD there); max_iterations is the caller's number.
+ * Outputs per problem: ss_pnp_result, 128 bytes, and inlier uint8 [rows] by KEYPOINT row (every row < rows is written).  A problem
+ * whose keypoint frame the extraction flagged has that status, state 1 and no correspondences. */
+#define SS_PNP_MAX_ITERATIONS 1024
+#define SS_PNP_MAX_REFINE 16
+typedef struct {            /* 40 bytes */
+    float chi2;             /* finite and > 0; upstream: 5.991 */
+    float min_ratio;        /* finite and >= 0; upstream: 0.5; 0 switches the test off */
+    double lambda;          /* finite and >= 0; the pose rule's: 1e-6 */
+    int32_t min_inliers;    /* >= 0; upstream: 10 */
+    int32_t max_iterations; /* 1 .. SS_PNP_MAX_ITERATIONS; upstream: 300 */
+    int32_t refine_steps;   /* 0 .. SS_PNP_MAX_REFINE; upstream: 5 */
+    uint32_t seed;
+    int32_t reserved[2];    /* must be 0 */
+} ss_pnp_params;
+typedef struct {            /* 128 bytes, one per problem */
+    double rcw[9], tcw[3];  /* all 0.0 unless state == 0; feed ss_proj_view_init and ss_pose_opt_*'s start unchanged */
+    int32_t state;          /* 0 a model, 1 too few correspondences, 2 the best hypothesis does not qualify */
+    int32_t status;         /* SS_OK, or the frame_error that voided the problem */
+    int32_t n_corr;         /* N */
+    int32_t n_inliers;      /* state 0: count of the winner, else 0 */
+    int32_t best_inliers;   /* max count[t]; 0 in state 1 */
+    int32_t iteration;      /* the winner's t, or -1 */
+    int32_t reserved[2];    /* 0 */
+} ss_pnp_result;
+/* Host twins (the text the kernels compile, csrc/ss_pnp_steps.h); none needs a device.  p is checked as the device calls check it
+ * (SS_ERR_INVALID_ARG); scale: n_levels entries, 1 <= n_levels <= SS_MAX_LEVELS.
+ * ss_pnp_host: the whole rule for one problem whose number in the call is `problem`; point_skip may be NULL; idx and inlier have
+ * n_kp entries.
+ * ss_pnp_model_host: steps 3b - 3d of one sextuple in draw order: xyz 18 floats, uv 12 floats, scale6 the six keypoints' scales,
+ * point_rows6 their point rows, into out->rcw / tcw; state 0, iteration -1, the other integers 0.
+ * ss_pnp_check_host: steps 1 and 3e of the n couples (points[k] with kp[k]) against the pose in `model`, rounded to float32 as step
+ * 3d rounds it.  out[k]: 0 an inlier, 1 an octave outside the table (not a correspondence), 2 the depth is not > 0, 3 the error
+ * is not < max.  err (NULL, or n floats): the squared error, 0.0f where out[k] is 1 or 2. */
+int ss_pnp_host(const ss_proj_view *view, const float *scale, int n_levels, const ss_map_point *points, const uint8_t *point_skip,
+                int n_points, const ss_keypoint *kp, int n_kp, const int32_t *idx, const ss_pnp_params *p, int problem, uint8_t *inlier,
+                ss_pnp_result *result);
+int ss_pnp_model_host(const ss_pnp_params *p, const ss_proj_view *view, const float *xyz, const float *uv, const float *scale6,
+                      const int32_t *point_rows6, ss_pnp_result *out);
+int ss_pnp_check_host(const ss_pnp_params *p, const ss_proj_view *view, const float *scale, int n_levels, const ss_map_point *points,
+                      const ss_keypoint *kp, int n, const ss_pnp_result *model, uint8_t *out, float *err);
+/* n_problems problems on caller-supplied device arrays.  Map points as for ss_pose_opt_pairs_device: d_points [n_blocks][point_rows]
+ * ss_map_point, d_point_skip uint8 [n_blocks][point_rows] or NULL, d_n_points device int32 [n_blocks].  Keypoints: d_kp
+ * [n_kp_frames][rows_per_frame] ss_keypoint, d_n_kp device int32 [n_kp_frames]; counts are clamped to 0 .. their rows.  kp_src and
+ * point_src: HOST tables [n_problems] of frame and block numbers, or NULL (problem q reads frame q, block q): several candidate
+ * keyframes of one lost frame are several problems that share one keypoint frame, with no copies.  d_idx int32 and d_inlier uint8
+ * are [n_problems][rows_per_frame].  views (n_problems) is a HOST table, copied before the call returns.  d_result [n_problems]
+ * ss_pnp_result.  SS_ERR_INVALID_ARG: either row count above SS_GUIDED_MAX_ROWS, a parameter out of its range, a reserved field
+ * that is not 0, a kp_src or point_src entry out of range, a NULL buffer.  Asynchronous on the context's stream. */
+int ss_pnp_pairs_device(ss_ctx *ctx, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks, int point_rows,
+                        const void *d_kp, const void *d_n_kp, int n_kp_frames, int rows_per_frame, const void *d_idx, int n_problems,
+                        const ss_proj_view *views, const int32_t *kp_src, const int32_t *point_src, const ss_pnp_params *p,
+                        void *d_inlier, void *d_result);
+/* The same, the keypoints being the frames of the last ss_extract_batch_device batch (SS_ERR_STATE without one; n_kp_frames and
+ * rows_per_frame = kp_capacity are the batch's).  A problem whose keypoint frame has its frame_error set gets that status, state 1
+ * and no correspondences. */
+int ss_pnp_batch_device(ss_ctx *ctx, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks, int point_rows,
+                        const void *d_idx, int n_problems, const ss_proj_view *views, const int32_t *kp_src, const int32_t *point_src,
+                        const ss_pnp_params *p, void *d_inlier, void *d_result);
+/* One problem (number 0) with host pointers in and out (copy in, the pairs form, copy out), synchronous.  n_points, n_kp <=
+ * SS_GUIDED_MAX_ROWS; point_skip may be NULL; idx and inlier have n_kp entries. */
+int ss_pnp(ss_ctx *ctx, const ss_proj_view *view, const ss_map_point *points, const uint8_t *point_skip, int n_points,
+           const ss_keypoint *kp, int n_kp, const int32_t *idx, const ss_pnp_params *p, uint8_t *inlier, ss_pnp_result *result);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

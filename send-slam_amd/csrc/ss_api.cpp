@@ -448,6 +448,9 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_sim3_ws);
     dev_free(c->d_sim3_io);
     staged_free(c->sim3_tab);
+    dev_free(c->d_pnp_ws);
+    dev_free(c->d_pnp_io);
+    staged_free(c->pnp_tab);
     dev_free(c->d_pose_ws);
     dev_free(c->d_pose_io);
     staged_free(c->pose_tab);

@@ -1,7 +1,7 @@
 /*
  * ss_api_search.cpp -- the search family of the C ABI (include/sendslam_orb.h): guided matching, map-point projection search,
  * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation, the Sim3 RANSAC, the pose-only optimisation, the Sim3 refinement,
- * the local bundle adjustment.  Each has a pairs form on caller arrays, a batch form on the
+ * the local bundle adjustment, the PnP RANSAC.  Each has a pairs form on caller arrays, a batch form on the
  * frames of the last extraction and, for some, a host form.  The context and the helpers they share: ss_ctx.h.
  */
 #include <algorithm>
@@ -18,6 +18,7 @@
 #include "ss_ba_steps.h"
 #include "ss_epi_steps.h"
 #include "ss_fuse_steps.h"
+#include "ss_pnp_steps.h"
 #include "ss_pose_steps.h"
 #include "ss_proj_steps.h"
 #include "ss_sim3_steps.h"
@@ -2328,6 +2329,225 @@ int ss_local_ba_points_to_block(ss_ctx *c, const void *d_xyz, const void *d_poin
     }
     HIP_TRY(c, hipGetLastError());
     return SS_OK;
+}
+
+/* ---- PnP RANSAC (csrc/ss_pnp.hip, csrc/ss_pnp_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *pnp_params_error(const ss_pnp_params *p)
+{
+    if (!p) return "pnp: params is NULL";
+    if (!(p->chi2 > 0.0f) || !std::isfinite(p->chi2)) return "pnp: chi2 must be finite and > 0";
+    if (!(p->min_ratio >= 0.0f) || !std::isfinite(p->min_ratio)) return "pnp: min_ratio must be finite and >= 0";
+    if (!(p->lambda >= 0.0) || !std::isfinite(p->lambda)) return "pnp: lambda must be finite and >= 0";
+    if (p->min_inliers < 0) return "pnp: min_inliers must be >= 0";
+    if (p->max_iterations < 1 || p->max_iterations > SS_PNP_MAX_ITERATIONS) return "pnp: max_iterations must be 1 .. SS_PNP_MAX_ITERATIONS";
+    if (p->refine_steps < 0 || p->refine_steps > SS_PNP_MAX_REFINE) return "pnp: refine_steps must be 0 .. SS_PNP_MAX_REFINE";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return "pnp: the reserved fields must be 0";
+    return nullptr;
+}
+
+int ss_pnp_host(const ss_proj_view *view, const float *scale, int n_levels, const ss_map_point *points, const uint8_t *point_skip, int n_points,
+                const ss_keypoint *kp, int n_kp, const int32_t *idx, const ss_pnp_params *p, int problem, uint8_t *inlier, ss_pnp_result *result)
+{
+    if (pnp_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!view || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n_points < 0 || n_kp < 0 || problem < 0 || !result) return SS_ERR_INVALID_ARG;
+    if ((n_points > 0 && !points) || (n_kp > 0 && (!kp || !idx || !inlier))) return SS_ERR_INVALID_ARG;
+    /* step 1 */
+    std::vector<ss_pnp_corr> corr;
+    std::vector<float> sc;
+    std::vector<int32_t> point, row_of;
+    for (int i = 0; i < n_kp; i++) {
+        const int j = idx[i], octave = kp[i].octave;
+        inlier[i] = 0;
+        if (!(j >= 0 && j < n_points) || !(octave >= 0 && octave < n_levels)) continue;
+        if (point_skip && point_skip[j] != 0) continue;
+        ss_pnp_corr c;
+        c.X[0] = points[j].x, c.X[1] = points[j].y, c.X[2] = points[j].z;
+        c.u = kp[i].x, c.v = kp[i].y, c.max = ss_pnp_max(p->chi2, scale[octave]);
+        corr.push_back(c), sc.push_back(scale[octave]), point.push_back(j), row_of.push_back(i);
+    }
+    const int n = (int)corr.size();
+    std::vector<uint8_t> in((size_t)n + 1);
+    ss_pnp_problem_host(corr.data(), sc.data(), point.data(), n, ss_pnp_cam_of(*view), *p, (uint32_t)problem, in.data(), result);
+    for (int k = 0; k < n; k++) inlier[row_of[(size_t)k]] = in[(size_t)k];
+    return SS_OK;
+}
+
+int ss_pnp_model_host(const ss_pnp_params *p, const ss_proj_view *view, const float *xyz, const float *uv, const float *scale6,
+                      const int32_t *point_rows6, ss_pnp_result *out)
+{
+    if (pnp_params_error(p) || !view || !xyz || !uv || !scale6 || !point_rows6 || !out) return SS_ERR_INVALID_ARG;
+    memset(out, 0, sizeof(*out));
+    int row[SS_PNP_DRAWS];
+    for (int k = 0; k < SS_PNP_DRAWS; k++) row[k] = point_rows6[k];
+    ss_pnp_work_host w;
+    const ss_pnp_model m = ss_pnp_model_of(xyz, uv, scale6, row, ss_pnp_cam_of(*view), p->lambda, p->refine_steps, w);
+    memcpy(out->rcw, m.rcw, sizeof(m.rcw));
+    memcpy(out->tcw, m.tcw, sizeof(m.tcw));
+    out->iteration = -1;
+    return SS_OK;
+}
+
+int ss_pnp_check_host(const ss_pnp_params *p, const ss_proj_view *view, const float *scale, int n_levels, const ss_map_point *points,
+                      const ss_keypoint *kp, int n, const ss_pnp_result *model, uint8_t *out, float *err)
+{
+    if (pnp_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!view || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || !model || n < 0 || (n > 0 && (!points || !kp || !out))) return SS_ERR_INVALID_ARG;
+    float r[9], t[3];
+    for (int k = 0; k < 9; k++) r[k] = (float)model->rcw[k];
+    for (int k = 0; k < 3; k++) t[k] = (float)model->tcw[k];
+    const ss_pnp_cam cam = ss_pnp_cam_of(*view);
+    for (int k = 0; k < n; k++) {
+        const int octave = kp[k].octave;
+        if (err) err[k] = 0.0f;
+        if (!(octave >= 0 && octave < n_levels)) {
+            out[k] = 1;
+            continue;
+        }
+        ss_pnp_corr c;
+        c.X[0] = points[k].x, c.X[1] = points[k].y, c.X[2] = points[k].z;
+        c.u = kp[k].x, c.v = kp[k].y, c.max = ss_pnp_max(p->chi2, scale[octave]);
+        float e;
+        out[k] = (uint8_t)ss_pnp_test(r, t, c, cam, &e);
+        if (err) err[k] = e;
+    }
+    return SS_OK;
+}
+
+/* The checks the device forms share, the workspace, the host tables (views, then the frame and block numbers), then the four
+ * launches of a call whose device operands and outputs are filled in */
+static int pnp_run(ss_ctx *c, ssk_pnp_call &g, int n_blocks, int n_kp_frames, const ss_proj_view *views, const int32_t *kp_src, const int32_t *point_src,
+                   const ss_pnp_params *p)
+{
+    if (const char *msg = pnp_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (g.n_frames < 0 || n_blocks < 0 || n_kp_frames < 0 || g.point_rows < 1 || g.rows < 1)
+        return fail(c, SS_ERR_INVALID_ARG, "pnp: bad problem, frame, block or row count");
+    if (g.point_rows > SS_GUIDED_MAX_ROWS || g.rows > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "pnp: point_rows " + std::to_string(g.point_rows) + " / rows_per_frame " + std::to_string(g.rows) +
+                                               " exceed SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    int rc = call_count_ok(c, "pnp", g.n_frames, "problems");
+    if (rc == SS_OK) rc = context_pyramid(c, "pnp", &g.n_levels, g.scale);
+    if (rc != SS_OK) return rc;
+    if (g.n_frames == 0) return SS_OK;
+    if (!views) return fail(c, SS_ERR_INVALID_ARG, "pnp: views is NULL");
+    for (int q = 0; q < g.n_frames; q++) {
+        const int kf = kp_src ? kp_src[q] : q, pb = point_src ? point_src[q] : q;
+        if (kf < 0 || kf >= n_kp_frames)
+            return fail(c, SS_ERR_INVALID_ARG, std::string(kp_src ? "kp_src[" : "problem [") + std::to_string(q) + "] = " + std::to_string(kf) +
+                                                   " names no frame of keypoints (" + std::to_string(n_kp_frames) + ")");
+        if (pb < 0 || pb >= n_blocks)
+            return fail(c, SS_ERR_INVALID_ARG, std::string(point_src ? "point_src[" : "problem [") + std::to_string(q) + "] = " + std::to_string(pb) +
+                                                   " names no block of points (" + std::to_string(n_blocks) + ")");
+    }
+    if (!g.points || !g.np || !g.kp || !g.nk || !g.idx || !g.inlier || !g.result) return fail(c, SS_ERR_INVALID_ARG, "pnp: NULL buffer");
+    g.chi2 = p->chi2, g.min_ratio = p->min_ratio, g.lambda = p->lambda;
+    g.min_inliers = p->min_inliers, g.max_iterations = p->max_iterations, g.refine_steps = p->refine_steps, g.seed = p->seed;
+    const size_t np = (size_t)g.n_frames, nr = np * g.rows, nh = np * g.max_iterations;
+    rc = carve_from(c, c->d_pnp_ws, [&](carve &w) {
+        g.corr = w.take<float>(6 * nr * sizeof(float));
+        g.corr_scale = w.take<float>(nr * sizeof(float));
+        g.corr_point = w.take<int32_t>(nr * sizeof(int32_t));
+        g.corr_of_row = w.take<int32_t>(nr * sizeof(int32_t));
+        g.n_corr = w.take<int32_t>(np * sizeof(int32_t));
+        g.models = w.take<ssk_pnp_model>(nh * sizeof(ssk_pnp_model));
+        g.poses = w.take<double>(nh * 12 * sizeof(double));
+        g.counts = w.take<int32_t>(nh * sizeof(int32_t));
+    });
+    if (rc != SS_OK) return rc;
+    const size_t vb = np * sizeof(ss_proj_view), sb = np * sizeof(int32_t);
+    rc = staged_upload(c, c->pnp_tab, vb + 2 * sb, [&](uint8_t *h) {
+        memcpy(h, views, vb);
+        int32_t *ks = (int32_t *)(h + vb), *ps = (int32_t *)(h + vb + sb);
+        for (int q = 0; q < g.n_frames; q++) ks[q] = kp_src ? kp_src[q] : q, ps[q] = point_src ? point_src[q] : q;
+    });
+    if (rc != SS_OK) return rc;
+    g.views = c->pnp_tab.as<ss_proj_view>();
+    g.kp_src = c->pnp_tab.as<int32_t>(vb), g.point_src = c->pnp_tab.as<int32_t>(vb + sb);
+    {
+        /* per row: its match and the number written; a correspondence reads a map point, a keypoint and up to a flag and writes its
+         * six floats, its scale and its point row */
+        stage_timer t(c, "pnp_gather", (int64_t)nr * (4 + 4 + (int64_t)sizeof(ss_map_point) + (int64_t)sizeof(ss_keypoint) + (g.p_skip ? 1 : 0) + 32) + (int64_t)np * 4);
+        ssk_pnp_gather(c->stream, g);
+    }
+    {
+        /* per hypothesis: six correspondences' five floats, scale and row read, one record, twelve doubles and one count written */
+        stage_timer t(c, "pnp_model", (int64_t)nh * (SS_PNP_DRAWS * 28 + (int64_t)sizeof(ssk_pnp_model) + 96 + 4));
+        ssk_pnp_model_launch(c->stream, g);
+    }
+    {
+        /* every block of hypotheses reads the six floats of every correspondence once and its own records; the counts are added */
+        const int64_t hb = (g.max_iterations + SSK_PNP_HYP_BLOCK - 1) / SSK_PNP_HYP_BLOCK;
+        stage_timer t(c, "pnp_count", (int64_t)nr * 24 * hb + (int64_t)nh * ((int64_t)sizeof(ssk_pnp_model) + 4));
+        ssk_pnp_count(c->stream, g);
+    }
+    {
+        /* the counts read; per row its number read and its flag written, an inlier candidate's six floats on top */
+        stage_timer t(c, "pnp_finish", (int64_t)nh * 4 + (int64_t)nr * (4 + 1 + 24) + (int64_t)np * (int64_t)(sizeof(ssk_pnp_model) + 96 + sizeof(ss_pnp_result)));
+        ssk_pnp_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_pnp_pairs_device(ss_ctx *c, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks, int point_rows, const void *d_kp,
+                        const void *d_n_kp, int n_kp_frames, int rows_per_frame, const void *d_idx, int n_problems, const ss_proj_view *views,
+                        const int32_t *kp_src, const int32_t *point_src, const ss_pnp_params *p, void *d_inlier, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    ssk_pnp_call g;
+    g.n_frames = n_problems, g.point_rows = point_rows, g.rows = rows_per_frame;
+    g.points = (const ss_map_point *)d_points, g.p_skip = (const uint8_t *)d_point_skip, g.np = (const int32_t *)d_n_points;
+    g.kp = (const ss_keypoint *)d_kp, g.nk = (const int32_t *)d_n_kp;
+    g.idx = (const int32_t *)d_idx;
+    g.inlier = (uint8_t *)d_inlier, g.result = (ss_pnp_result *)d_result;
+    return pnp_run(c, g, n_blocks, n_kp_frames, views, kp_src, point_src, p);
+}
+
+int ss_pnp_batch_device(ss_ctx *c, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks, int point_rows,
+                        const void *d_idx, int n_problems, const ss_proj_view *views, const int32_t *kp_src, const int32_t *point_src,
+                        const ss_pnp_params *p, void *d_inlier, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_pnp_batch_device")) return SS_ERR_STATE;
+    ssk_pnp_call g;
+    g.n_frames = n_problems, g.point_rows = point_rows, g.rows = c->hg.kcap;
+    g.points = (const ss_map_point *)d_points, g.p_skip = (const uint8_t *)d_point_skip, g.np = (const int32_t *)d_n_points;
+    g.kp = c->ws.kps, g.nk = c->ws.n_kp;
+    const int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
+    g.idx = (const int32_t *)d_idx;
+    g.inlier = (uint8_t *)d_inlier, g.result = (ss_pnp_result *)d_result;
+    return pnp_run(c, g, n_blocks, c->last_n_frames, views, kp_src, point_src, p);
+}
+
+int ss_pnp(ss_ctx *c, const ss_proj_view *view, const ss_map_point *points, const uint8_t *point_skip, int n_points, const ss_keypoint *kp, int n_kp,
+           const int32_t *idx, const ss_pnp_params *p, uint8_t *inlier, ss_pnp_result *result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = pnp_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_points < 0 || n_kp < 0 || n_points > SS_GUIDED_MAX_ROWS || n_kp > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "pnp: n_points and n_kp must be 0 .. SS_GUIDED_MAX_ROWS");
+    if (!view || !result || (n_points > 0 && !points) || (n_kp > 0 && (!kp || !idx || !inlier))) return fail(c, SS_ERR_INVALID_ARG, "pnp: NULL buffer");
+    /* one block of `pr` points, one frame of `kr` rows; `counts` is on this stack: no return before the stream has read it */
+    const size_t pr = (size_t)std::max(n_points, 1), kr = (size_t)std::max(n_kp, 1), np = (size_t)n_points, nk = (size_t)n_kp;
+    const int32_t counts[2] = {n_points, n_kp};
+    enum { PT, PS, KP, IDX, N, FL, RES, PIECES };
+    io_piece io[PIECES] = {{points, nullptr, pr * sizeof(ss_map_point), np * sizeof(ss_map_point)}, {point_skip, nullptr, pr, np},
+                           {kp, nullptr, kr * sizeof(ss_keypoint), nk * sizeof(ss_keypoint)}, {idx, nullptr, kr * 4, nk * 4},
+                           {counts, nullptr, sizeof(counts), sizeof(counts)}, {nullptr, inlier, kr, nk},
+                           {nullptr, result, sizeof(ss_pnp_result), sizeof(ss_pnp_result)}};
+    int rc = io_send(c, c->d_pnp_io, io, PIECES);
+    if (rc == SS_OK)
+        rc = ss_pnp_pairs_device(c, io[PT].d, point_skip ? io[PS].d : nullptr, io[N].d, 1, (int)pr, io[KP].d, io[N].d + 4, 1, (int)kr, io[IDX].d, 1, view,
+                                 nullptr, nullptr, p, io[FL].d, io[RES].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
 }
 
 } /* extern "C" */

@@ -410,6 +410,53 @@ struct ssk_pose_call {
 };
 void ssk_pose_gather(hipStream_t s, const ssk_pose_call &g);
 void ssk_pose_solve(hipStream_t s, const ssk_pose_call &g);
+/* ss_pnp.hip: PnP RANSAC (DESIGN.md "PnP RANSAC").  Problem q solves the matches idx[q][i] of the rows of keypoint frame kp_src[q]
+ * with the rows of point block point_src[q].  gather (one workgroup per problem, SSK_PNP_CHUNK rows at a time in ascending order)
+ * numbers the correspondences and writes their six floats as a structure of arrays (corr: 6 planes of [n_frames][rows]: X Y Z u v
+ * max), the two values only the model reads (corr_scale, corr_point: the keypoint's scale and the point row), the number of every
+ * row's correspondence (corr_of_row, -1: none) and N; model (one lane per problem and hypothesis) writes one ssk_pnp_model, the
+ * pose's twelve doubles and zeroes its count; count (a lane per correspondence, SSK_PNP_COUNT_ROWS of them and SSK_PNP_HYP_BLOCK
+ * hypotheses per workgroup) adds the inliers; finish (one workgroup per problem) selects and writes flags and result */
+#define SSK_PNP_CHUNK 1024
+#define SSK_PNP_COUNT_ROWS 256
+#define SSK_PNP_HYP_BLOCK 32
+struct alignas(16) ssk_pnp_model { /* 64 bytes, so that a wave reads one with wide scalar loads */
+    float r[9], t[3];
+    float pad[4];
+};
+struct ssk_pnp_call {
+    int n_frames = 0, point_rows = 0, rows = 0; /* n_frames: the problems of the call */
+    const ss_map_point *points = nullptr; /* [n_blocks][point_rows] */
+    const uint8_t *p_skip = nullptr;      /* [n_blocks][point_rows], or NULL */
+    const int32_t *np = nullptr;
+    const ss_keypoint *kp = nullptr;      /* [n_kp_frames][rows] */
+    const int32_t *nk = nullptr;
+    const int32_t *frame_error = nullptr; /* per keypoint frame, or NULL */
+    const int32_t *kp_src = nullptr, *point_src = nullptr; /* device int32 [n_frames] each */
+    const ss_proj_view *views = nullptr;  /* device [n_frames] */
+    const int32_t *idx = nullptr;         /* [n_frames][rows] */
+    float chi2 = 0, min_ratio = 0;
+    double lambda = 0;
+    int min_inliers = 0, max_iterations = 1, refine_steps = 0;
+    uint32_t seed = 0;
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    /* workspace */
+    float *corr = nullptr;          /* 6 planes */
+    float *corr_scale = nullptr;    /* [n_frames][rows] */
+    int32_t *corr_point = nullptr;  /* [n_frames][rows] */
+    int32_t *corr_of_row = nullptr; /* [n_frames][rows] */
+    int32_t *n_corr = nullptr;      /* [n_frames] */
+    ssk_pnp_model *models = nullptr; /* [n_frames][max_iterations] */
+    double *poses = nullptr;         /* [n_frames][max_iterations][12] */
+    int32_t *counts = nullptr;       /* [n_frames][max_iterations] */
+    uint8_t *inlier = nullptr;       /* [n_frames][rows] */
+    ss_pnp_result *result = nullptr;
+};
+void ssk_pnp_gather(hipStream_t s, const ssk_pnp_call &g);
+void ssk_pnp_model_launch(hipStream_t s, const ssk_pnp_call &g);
+void ssk_pnp_count(hipStream_t s, const ssk_pnp_call &g);
+void ssk_pnp_finish(hipStream_t s, const ssk_pnp_call &g);
 /* ss_sim3opt.hip: Sim3 refinement (DESIGN.md "Sim3 refinement").  Pair b as for ssk_sim3_call, and start[b], the model it starts
  * from.  gather (one workgroup per pair, SSK_SIM3OPT_CHUNK rows at a time in ascending order) numbers the correspondences, writes
  * their twelve floats as a structure of arrays (planes: 12 of [n_frames][rows]: X1, X2, both keypoints, both scales), the query row

@@ -1,5 +1,5 @@
 /*
- * ss_sim3_steps.h -- the steps of the Sim3 RANSAC (the rule: include/sendslam_orb.h): mix32 and the three
+ * ss_sim3_steps.h -- the steps of the Sim3 RANSAC (the rule: include/sendslam_orb.h): mix32 and the
  * draws of a hypothesis, the Horn model of a triple in double, a correspondence's twelve floats, one reprojection test and the
  * selection predicate.  The kernels (ss_sim3.hip), the host twins ss_sim3_model_host / ss_sim3_check_host (ss_api_search.cpp) and
  * tests/native/sim3_steps_asan.cpp compile this text.
@@ -25,20 +25,30 @@ SS_HD uint32_t ss_sim3_mix32(uint32_t seed, uint32_t pair, uint32_t n)
     return h;
 }
 
-/* The three draws of hypothesis t over 0 .. n-1 (n >= 3) without replacement, swap-with-last: at most two slots are ever
- * displaced (slot s0 holds v0 after draw 0, slot s1 holds v1 after draw 1; the later one wins), so no array is kept */
-SS_HD void ss_sim3_draw(uint32_t seed, uint32_t pair, int t, int n, int out[3])
+/* K draws of hypothesis t over 0 .. n-1 (n >= K) without replacement, swap-with-last: draw k takes value base + k of the stream
+ * (base = K * t), j = (uint64(r) * (n - k)) >> 32, the value at slot j, and slot j then receives the value at slot n-1-k.  At most K
+ * slots are ever displaced (slot[e] holds val[e] after draw e; the latest record of a slot wins), so no array of n is kept */
+template <int K> SS_HD void ss_sim3_draw_k(uint32_t seed, uint32_t pair, int t, int n, int out[K])
 {
-    const uint32_t base = 3u * (uint32_t)t;
-    const int j0 = (int)(((uint64_t)ss_sim3_mix32(seed, pair, base) * (uint64_t)(uint32_t)n) >> 32);
-    out[0] = j0;
-    const int s0 = j0, v0 = n - 1;
-    const int j1 = (int)(((uint64_t)ss_sim3_mix32(seed, pair, base + 1u) * (uint64_t)(uint32_t)(n - 1)) >> 32);
-    out[1] = j1 == s0 ? v0 : j1;
-    const int s1 = j1, v1 = (n - 2) == s0 ? v0 : n - 2;
-    const int j2 = (int)(((uint64_t)ss_sim3_mix32(seed, pair, base + 2u) * (uint64_t)(uint32_t)(n - 2)) >> 32);
-    out[2] = j2 == s1 ? v1 : j2 == s0 ? v0 : j2;
+    int slot[K] = {}, val[K] = {};
+    const uint32_t base = (uint32_t)K * (uint32_t)t;
+    SS_EPI_UNROLL
+    for (int k = 0; k < K; k++) {
+        const int last = n - 1 - k;
+        const int j = (int)(((uint64_t)ss_sim3_mix32(seed, pair, base + (uint32_t)k) * (uint64_t)(uint32_t)(n - k)) >> 32);
+        int vj = j, vl = last;
+        SS_EPI_UNROLL
+        for (int e = 0; e < k; e++) {
+            if (slot[e] == j) vj = val[e];
+            if (slot[e] == last) vl = val[e];
+        }
+        out[k] = vj;
+        slot[k] = j, val[k] = vl;
+    }
 }
+
+/* the three draws of hypothesis t over 0 .. n-1 (n >= 3) */
+SS_HD void ss_sim3_draw(uint32_t seed, uint32_t pair, int t, int n, int out[3]) { ss_sim3_draw_k<3>(seed, pair, t, n, out); }
 
 /* a hypothesis: X1 = sr12.X2 + t12 and its inverse, float32 */
 struct ss_sim3_model {
@@ -47,29 +57,10 @@ struct ss_sim3_model {
 
 SS_HD double ss_sim3_dot(double a0, double a1, double a2, double b0, double b1, double b2) { return (a0 * b0 + a1 * b1) + a2 * b2; }
 
-/* step 3b: x1[k], x2[k] the camera coordinates of draw k in keyframe 1 and 2 */
-SS_HD ss_sim3_model ss_sim3_model_of(const float x1[9], const float x2[9], int fix_scale)
+/* Horn's rotation of M = sum Pr2 Pr1^T: the symmetric N, SS_TRI_SWEEPS sweeps of the triangulation's rotation, the quaternion at the
+ * largest diagonal entry, its nine polynomial entries.  X1 ~ r.X2 (the PnP model takes the nearest rotation of a matrix from it) */
+SS_HD void ss_sim3_horn(const double m[3][3], double r[9])
 {
-    double o1[3], o2[3], a[3][3], b[3][3]; /* a[k] = Pr1 of draw k, b[k] = Pr2 */
-    SS_EPI_UNROLL
-    for (int i = 0; i < 3; i++) {
-        o1[i] = (((double)x1[i] + (double)x1[3 + i]) + (double)x1[6 + i]) / 3.0;
-        o2[i] = (((double)x2[i] + (double)x2[3 + i]) + (double)x2[6 + i]) / 3.0;
-    }
-    SS_EPI_UNROLL
-    for (int k = 0; k < 3; k++) {
-        SS_EPI_UNROLL
-        for (int i = 0; i < 3; i++) {
-            a[k][i] = (double)x1[3 * k + i] - o1[i];
-            b[k][i] = (double)x2[3 * k + i] - o2[i];
-        }
-    }
-    double m[3][3];
-    SS_EPI_UNROLL
-    for (int i = 0; i < 3; i++) {
-        SS_EPI_UNROLL
-        for (int j = 0; j < 3; j++) m[i][j] = (b[0][i] * a[0][j] + b[1][i] * a[1][j]) + b[2][i] * a[2][j];
-    }
     double N[4][4], V[4][4];
     N[0][0] = (m[0][0] + m[1][1]) + m[2][2];
     N[0][1] = m[1][2] - m[2][1];
@@ -107,7 +98,6 @@ SS_HD ss_sim3_model ss_sim3_model_of(const float x1[9], const float x2[9], int f
     const double q3 = best == 0 ? V[3][0] : best == 1 ? V[3][1] : best == 2 ? V[3][2] : V[3][3];
     const double qn = sqrt(((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3);
     const double w = q0 / qn, x = q1 / qn, y = q2 / qn, z = q3 / qn;
-    double r[9];
     r[0] = 1.0 - 2.0 * (y * y + z * z);
     r[1] = 2.0 * (x * y - w * z);
     r[2] = 2.0 * (x * z + w * y);
@@ -117,6 +107,33 @@ SS_HD ss_sim3_model ss_sim3_model_of(const float x1[9], const float x2[9], int f
     r[6] = 2.0 * (x * z - w * y);
     r[7] = 2.0 * (y * z + w * x);
     r[8] = 1.0 - 2.0 * (x * x + y * y);
+}
+
+/* step 3b: x1[k], x2[k] the camera coordinates of draw k in keyframe 1 and 2 */
+SS_HD ss_sim3_model ss_sim3_model_of(const float x1[9], const float x2[9], int fix_scale)
+{
+    double o1[3], o2[3], a[3][3], b[3][3]; /* a[k] = Pr1 of draw k, b[k] = Pr2 */
+    SS_EPI_UNROLL
+    for (int i = 0; i < 3; i++) {
+        o1[i] = (((double)x1[i] + (double)x1[3 + i]) + (double)x1[6 + i]) / 3.0;
+        o2[i] = (((double)x2[i] + (double)x2[3 + i]) + (double)x2[6 + i]) / 3.0;
+    }
+    SS_EPI_UNROLL
+    for (int k = 0; k < 3; k++) {
+        SS_EPI_UNROLL
+        for (int i = 0; i < 3; i++) {
+            a[k][i] = (double)x1[3 * k + i] - o1[i];
+            b[k][i] = (double)x2[3 * k + i] - o2[i];
+        }
+    }
+    double m[3][3];
+    SS_EPI_UNROLL
+    for (int i = 0; i < 3; i++) {
+        SS_EPI_UNROLL
+        for (int j = 0; j < 3; j++) m[i][j] = (b[0][i] * a[0][j] + b[1][i] * a[1][j]) + b[2][i] * a[2][j];
+    }
+    double r[9];
+    ss_sim3_horn(m, r);
     double s = 1.0;
     if (!fix_scale) {
         double p3[3][3];

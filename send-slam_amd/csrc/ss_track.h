@@ -69,8 +69,9 @@ void sst_pose_to_twc(const double R[9], const double t[3], double pos[3], double
  * depth is 1 (CreateInitialMapMonocular), and every later frame is tracked against its predecessor
  * (constant-velocity prediction, SearchByProjection's th * scale^octave gate around the projected
  * point, pose-only optimisation on the carried-over points, >= 30 inliers as in TrackLocalMap), new
- * matches being triangulated between the first observation of their track and the current one.  No keyframes, local mapping, loop closing or
- * relocalisation: a lost tracker re-initialises from the next frame.  */
+ * matches being triangulated between the first observation of their track and the current one.  No keyframes, local mapping or loop closing.
+ * Relocalisation: the link exists (ss_pnp_*, the PnP RANSAC of include/sendslam_orb.h); ss_track itself still re-initialises a lost
+ * tracker from the next frame.  */
 struct sst_frame {
     int n = 0;
     std::vector<double> und;     /* 2n undistorted pixels */

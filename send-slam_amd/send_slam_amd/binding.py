@@ -51,7 +51,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_pose_opt_batch_device", "ss_pose_opt", "ss_sim3_opt_host", "ss_sim3_opt_pairs_device", "ss_sim3_opt_batch_device",
            "ss_sim3_opt", "ss_sim3_marks_pairs_device", "ss_sim3_mutual_pairs_device", "ss_sim3_marks_batch_device",
            "ss_sim3_mutual_batch_device", "ss_sim3_to_view21", "ss_local_ba_host", "ss_local_ba_pairs_device",
-           "ss_local_ba_batch_device", "ss_local_ba", "ss_local_ba_points_to_block"]
+           "ss_local_ba_batch_device", "ss_local_ba", "ss_local_ba_points_to_block", "ss_pnp_host", "ss_pnp_model_host", "ss_pnp_check_host",
+           "ss_pnp_pairs_device", "ss_pnp_batch_device", "ss_pnp"]
 
 
 class OrbParams(C.Structure):
@@ -495,6 +496,92 @@ def pose_opt_host(view, start, scale, points: np.ndarray, kp: np.ndarray, idx: n
     return flags, res[0]
 
 
+# ---- PnP RANSAC (the rule: include/sendslam_orb.h) ----
+SS_PNP_MAX_ITERATIONS, SS_PNP_MAX_REFINE = 1024, 16
+
+
+class PnpParams(C.Structure):
+    _fields_ = [("chi2", C.c_float), ("min_ratio", C.c_float), ("lambda_", C.c_double), ("min_inliers", C.c_int32),
+                ("max_iterations", C.c_int32), ("refine_steps", C.c_int32), ("seed", C.c_uint32), ("reserved", C.c_int32 * 2)]
+
+
+class PnpResult(C.Structure):
+    _fields_ = [("rcw", C.c_double * 9), ("tcw", C.c_double * 3), ("state", C.c_int32), ("status", C.c_int32), ("n_corr", C.c_int32),
+                ("n_inliers", C.c_int32), ("best_inliers", C.c_int32), ("iteration", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# ss_pnp_result: one per problem
+PNP_RESULT_DTYPE = np.dtype([("rcw", "<f8", (9,)), ("tcw", "<f8", (3,))] +
+                            [(n, "<i4") for n in ("state", "status", "n_corr", "n_inliers", "best_inliers", "iteration")] + [("reserved", "<i4", (2,))])
+
+
+def pnp_params(chi2: float = 5.991, min_ratio: float = 0.5, lambda_: float = 1e-6, min_inliers: int = 10, max_iterations: int = 300,
+               refine_steps: int = 5, seed: int = 0, reserved=(0, 0)) -> PnpParams:
+    """upstream's MLPnPsolver::SetRansacParameters(0.99, 10, 300, 6, 0.5, 5.991) as Tracking::Relocalization calls it; lambda is the
+    pose rule's"""
+    return PnpParams(chi2=chi2, min_ratio=min_ratio, lambda_=lambda_, min_inliers=min_inliers, max_iterations=max_iterations,
+                     refine_steps=refine_steps, seed=seed & 0xFFFFFFFF, reserved=(C.c_int32 * 2)(*reserved))
+
+
+def _pnp_arrays(view, points, kp, idx, skip):
+    """the host arrays of one problem, checked -> (v, pts, k, ix, skip, n_p, n_k)"""
+    v = _views_array(view)
+    pts, k = np.ascontiguousarray(points, MAP_POINT_DTYPE), np.ascontiguousarray(kp, KP_DTYPE)
+    ix = np.ascontiguousarray(idx, np.int32)
+    n_p, n_k = len(pts), len(k)
+    skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    if len(v) != 1 or len(ix) != n_k or (skip is not None and len(skip) != n_p):
+        raise ValueError("view, map points, keypoints, flags and matches differ in length")
+    return v, pts, k, ix, skip, n_p, n_k
+
+
+def pnp_host(view, scale, points: np.ndarray, kp: np.ndarray, idx: np.ndarray, params: PnpParams, skip=None, problem: int = 0):
+    """ss_pnp_host: the whole rule on the host for one problem -> (uint8 inlier flag per keypoint row, one PNP_RESULT_DTYPE record); needs
+    no device"""
+    v, pts, k, ix, skip, n_p, n_k = _pnp_arrays(view, points, kp, idx, skip)
+    sc = np.ascontiguousarray(scale, np.float32)
+    inlier, res = np.empty(n_k, np.uint8), np.zeros(1, PNP_RESULT_DTYPE)
+    ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+    rc = load().ss_pnp_host(v.ctypes.data, sc.ctypes.data, len(sc), ptr(pts, n_p), ptr(skip, n_p), n_p, ptr(k, n_k), n_k, ptr(ix, n_k),
+                            C.byref(params), problem, ptr(inlier, n_k), res.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_pnp_host refused its arguments")
+    return inlier, res[0]
+
+
+def pnp_model_host(params: PnpParams, view, xyz, uv, scale6, point_rows6) -> np.ndarray:
+    """ss_pnp_model_host: steps 3b - 3d of one sextuple in draw order (xyz 6 x 3, uv 6 x 2, the six scales and point rows) -> one
+    PNP_RESULT_DTYPE record holding the pose; needs no device"""
+    v = _views_array(view)
+    a = np.ascontiguousarray(xyz, np.float32).reshape(18)
+    b = np.ascontiguousarray(uv, np.float32).reshape(12)
+    s = np.ascontiguousarray(scale6, np.float32).reshape(6)
+    r = np.ascontiguousarray(point_rows6, np.int32).reshape(6)
+    out = np.zeros(1, PNP_RESULT_DTYPE)
+    rc = load().ss_pnp_model_host(C.byref(params), v.ctypes.data, a.ctypes.data, b.ctypes.data, s.ctypes.data, r.ctypes.data, out.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_pnp_model_host refused its arguments")
+    return out[0]
+
+
+def pnp_check_host(params: PnpParams, view, scale, points, kp, model):
+    """ss_pnp_check_host: steps 1 and 3e of the couples under `model` (a PNP_RESULT_DTYPE record) -> (uint8 [n]: 0 inlier, 1 octave
+    outside the table, 2 depth not > 0, 3 error not < max; float32 [n]: the squared error); needs no device"""
+    v = _views_array(view)
+    sc = np.ascontiguousarray(scale, np.float32)
+    pts, k = np.ascontiguousarray(points, MAP_POINT_DTYPE), np.ascontiguousarray(kp, KP_DTYPE)
+    n = len(pts)
+    if len(v) != 1 or len(k) != n:
+        raise ValueError("one view; one map point and keypoint per couple")
+    m = np.ascontiguousarray(np.asarray(model, PNP_RESULT_DTYPE).reshape(1))
+    out, err = np.empty(n, np.uint8), np.empty(n, np.float32)
+    ptr = lambda a: a.ctypes.data if n else None  # noqa: E731
+    rc = load().ss_pnp_check_host(C.byref(params), v.ctypes.data, sc.ctypes.data, len(sc), ptr(pts), ptr(k), n, m.ctypes.data, ptr(out), ptr(err))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_pnp_check_host refused its arguments")
+    return out, err
+
+
 # ---- local bundle adjustment (the rule: include/sendslam_orb.h) ----
 SS_BA_MAX_KF, SS_BA_MAX_FREE, SS_BA_MAX_ROUNDS = 64, 32, 4
 
@@ -843,6 +930,15 @@ def load():
     lib.ss_local_ba.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int, C.c_void_p, C.POINTER(BaParams)] + [C.c_void_p] * 5
     lib.ss_local_ba_points_to_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    lib.ss_pnp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                C.POINTER(PnpParams), C.c_int, C.c_void_p, C.c_void_p]
+    lib.ss_pnp_model_host.argtypes = [C.POINTER(PnpParams)] + [C.c_void_p] * 6
+    lib.ss_pnp_check_host.argtypes = [C.POINTER(PnpParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+    lib.ss_pnp_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                                         C.c_int] + [C.c_void_p] * 3 + [C.POINTER(PnpParams)] + [C.c_void_p] * 2
+    lib.ss_pnp_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + \
+                                       [C.POINTER(PnpParams)] + [C.c_void_p] * 2
+    lib.ss_pnp.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PnpParams), C.c_void_p, C.c_void_p]
     lib.ss_pose_opt_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_void_p, C.POINTER(PoseOptParams), C.c_void_p, C.c_void_p]
     lib.ss_pose_opt_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + \
@@ -1628,6 +1724,50 @@ class OrbContext:
             raise ValueError("one block number per problem")
         self._check(self._lib.ss_local_ba_points_to_block(self._h, C.c_void_p(d_xyz), C.c_void_p(d_point_flags), n_problems, point_rows,
                                                           None if bo is None else bo.ctypes.data, C.c_void_p(d_points), n_blocks))
+
+    # ---- PnP RANSAC: a pose for every relocalisation candidate (the rule: include/sendslam_orb.h) ----
+    @staticmethod
+    def _pnp_tables(views, kp_src, point_src, n_problems):
+        v = _views_array(views)
+        if len(v) != n_problems:
+            raise ValueError("one view per problem")
+        ks = None if kp_src is None else np.ascontiguousarray(kp_src, np.int32)
+        ps = None if point_src is None else np.ascontiguousarray(point_src, np.int32)
+        if (ks is not None and len(ks) != n_problems) or (ps is not None and len(ps) != n_problems):
+            raise ValueError("one frame and block number per problem")
+        return v, ks, ps
+
+    def pnp_pairs_device(self, d_points: int, d_n_points: int, n_blocks: int, point_rows: int, d_kp: int, d_n_kp: int, n_kp_frames: int,
+                         rows_per_frame: int, d_idx: int, n_problems: int, views, params: PnpParams, d_inlier: int, d_result: int, kp_src=None,
+                         point_src=None, d_point_skip: int = 0):
+        """n_problems problems on device arrays: map points [n_blocks][point_rows] (MAP_POINT_DTYPE, optional skip bytes, counts), keypoints
+        KP_DTYPE [n_kp_frames][rows_per_frame] with counts, d_idx as match_bow_pairs_device wrote it; views one per problem, kp_src and
+        point_src host tables or None (problem q reads frame q, block q); d_inlier uint8 [n_problems][rows_per_frame], d_result
+        PNP_RESULT_DTYPE [n_problems]; asynchronous."""
+        v, ks, ps = self._pnp_tables(views, kp_src, point_src, n_problems)
+        self._check(self._lib.ss_pnp_pairs_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_skip), C.c_void_p(d_n_points), n_blocks,
+                                                  point_rows, C.c_void_p(d_kp), C.c_void_p(d_n_kp), n_kp_frames, rows_per_frame, C.c_void_p(d_idx),
+                                                  n_problems, v.ctypes.data if n_problems else None, None if ks is None else ks.ctypes.data,
+                                                  None if ps is None else ps.ctypes.data, C.byref(params), C.c_void_p(d_inlier),
+                                                  C.c_void_p(d_result)))
+
+    def pnp_batch_device(self, d_points: int, d_n_points: int, n_blocks: int, point_rows: int, d_idx: int, n_problems: int, views,
+                         params: PnpParams, d_inlier: int, d_result: int, kp_src=None, point_src=None, d_point_skip: int = 0):
+        """the same, the keypoints being the frames of the last batch (rows_per_frame = kp_capacity); asynchronous."""
+        v, ks, ps = self._pnp_tables(views, kp_src, point_src, n_problems)
+        self._check(self._lib.ss_pnp_batch_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_skip), C.c_void_p(d_n_points), n_blocks,
+                                                  point_rows, C.c_void_p(d_idx), n_problems, v.ctypes.data if n_problems else None,
+                                                  None if ks is None else ks.ctypes.data, None if ps is None else ps.ctypes.data,
+                                                  C.byref(params), C.c_void_p(d_inlier), C.c_void_p(d_result)))
+
+    def pnp(self, view, points: np.ndarray, kp: np.ndarray, idx: np.ndarray, params: PnpParams, skip=None):
+        """One problem, host arrays in and out -> (uint8 inlier flag per keypoint row, PNP_RESULT_DTYPE record)."""
+        v, pts, k, ix, skip, n_p, n_k = _pnp_arrays(view, points, kp, idx, skip)
+        inlier, res = np.empty(n_k, np.uint8), np.zeros(1, PNP_RESULT_DTYPE)
+        ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+        self._check(self._lib.ss_pnp(self._h, v.ctypes.data, ptr(pts, n_p), ptr(skip, n_p), n_p, ptr(k, n_k), n_k, ptr(ix, n_k), C.byref(params),
+                                     ptr(inlier, n_k), res.ctypes.data))
+        return inlier, res[0]
 
     # ---- Sim3 refinement: SearchBySim3's bookkeeping and OptimizeSim3 per loop candidate (the rule: include/sendslam_orb.h) ----
     def sim3_opt_pairs_device(self, d_query_xyz: int, d_query_kp: int, d_n_query: int, d_train_xyz: int, d_train_kp: int, d_n_train: int,

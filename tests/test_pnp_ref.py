@@ -1,0 +1,418 @@
+"""CPU tests of the PnP RANSAC as tests/pnp_ref.py states it, and of its C ABI surface: symbols and struct layouts, the draw, the
+host twins ss_pnp_model_host, ss_pnp_check_host and ss_pnp_host (the text the kernels compile) against the restatement bit for bit,
+the linear model against two independent derivations (numpy.linalg.eigh and svd; the ground truth), the thresholds from both sides,
+the states and the selection on the shared cases, the recovery of planted inliers, refused arguments, and the stand-alone sanitizer
+run of the steps."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import pnp_cases as NC
+import pnp_ref as N
+import proj_cases as PC
+from send_slam_amd import binding
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "sendslam_orb.h")
+f32 = np.float32
+
+# The largest deviation of the linear six-point pose (refine_steps 0) on LINEAR_N well-spread sextuples with exact projections,
+# measured once with this file (the test prints it): against numpy's eigh + svd on the same matrix 1.7e-10 (rotation entries) and
+# 1.1e-9 (translation); against the ground truth, where the rounding of u, v to float32 (up to 2^-16 px at 500 px) is the data's
+# own error, 4.4e-6 and 2.5e-5.  The bounds are ten times those figures (DESIGN.md section 26 holds them too)
+LINEAR_N = 300
+LINEAR_MIN_SPREAD = 0.25
+BOUND_EIGH = (1.7e-9, 1.1e-8)
+BOUND_TRUTH = (4.4e-5, 2.5e-4)
+
+
+def _same_result(got, want, tag):
+    for name in N.RESULT_DTYPE.names:
+        assert np.asarray(got[name]).tobytes() == np.asarray(want[name]).tobytes(), f"{tag}: result.{name} {got[name]} != {want[name]}"
+
+
+def test_symbols_structs_and_constants(tmp_path):
+    names = ["ss_pnp_host", "ss_pnp_model_host", "ss_pnp_check_host", "ss_pnp_pairs_device", "ss_pnp_batch_device", "ss_pnp"]
+    text = open(HEADER).read()
+    lib = binding.load()
+    for n in names:
+        assert n + "(" in text and n in binding.EXPORTS and hasattr(lib, n) and getattr(lib, n).argtypes is not None
+    for m in ("pnp_pairs_device", "pnp_batch_device", "pnp"):
+        assert callable(getattr(binding.OrbContext, m))
+    for m in ("pnp_params", "pnp_host", "pnp_model_host", "pnp_check_host"):
+        assert callable(getattr(binding, m))
+    assert C.sizeof(binding.PnpParams) == 40 and C.sizeof(binding.PnpResult) == 128 and binding.PNP_RESULT_DTYPE.itemsize == 128
+    assert binding.PNP_RESULT_DTYPE == N.RESULT_DTYPE
+    assert tuple(n for n, _ in binding.PnpResult._fields_) == N.RESULT_DTYPE.names
+    assert binding.SS_PNP_MAX_ITERATIONS == N.MAX_ITERATIONS == 1024 and binding.SS_PNP_MAX_REFINE == N.MAX_REFINE == 16
+    p = binding.pnp_params()
+    assert {k: getattr(p, k) for k in ("min_inliers", "max_iterations", "refine_steps")} == {k: N.UPSTREAM[k] for k in ("min_inliers", "max_iterations", "refine_steps")}
+    assert p.chi2 == f32(N.UPSTREAM["chi2"]) and p.min_ratio == 0.5 and p.lambda_ == 1e-6
+    src = tmp_path / "sizes.c"
+    src.write_text('#include "sendslam_orb.h"\n#include <stddef.h>\n'
+                   '_Static_assert(sizeof(ss_pnp_params) == 40 && sizeof(ss_pnp_params) % 8 == 0, "params");\n'
+                   '_Static_assert(sizeof(ss_pnp_result) == 128 && sizeof(ss_pnp_result) % 8 == 0, "result");\n'
+                   '_Static_assert(offsetof(ss_pnp_params, chi2) == 0 && offsetof(ss_pnp_params, min_ratio) == 4 && offsetof(ss_pnp_params, lambda) == 8 && '
+                   'offsetof(ss_pnp_params, min_inliers) == 16 && offsetof(ss_pnp_params, max_iterations) == 20 && '
+                   'offsetof(ss_pnp_params, refine_steps) == 24 && offsetof(ss_pnp_params, seed) == 28 && offsetof(ss_pnp_params, reserved) == 32, '
+                   '"params fields");\n'
+                   '_Static_assert(offsetof(ss_pnp_result, rcw) == 0 && offsetof(ss_pnp_result, tcw) == 72 && offsetof(ss_pnp_result, state) == 96 && '
+                   'offsetof(ss_pnp_result, status) == 100 && offsetof(ss_pnp_result, n_corr) == 104 && offsetof(ss_pnp_result, n_inliers) == 108 && '
+                   'offsetof(ss_pnp_result, best_inliers) == 112 && offsetof(ss_pnp_result, iteration) == 116 && offsetof(ss_pnp_result, reserved) == 120, '
+                   '"result fields");\n'
+                   '_Static_assert(offsetof(ss_pnp_result, rcw) == offsetof(ss_pose_result, rcw) && offsetof(ss_pnp_result, tcw) == offsetof(ss_pose_result, tcw), '
+                   '"the twelve doubles lie as the pose result has them");\n'
+                   '_Static_assert(SS_PNP_MAX_ITERATIONS == 1024 && SS_PNP_MAX_REFINE == 16 && SS_TRI_SWEEPS == 6, "constants");\n'
+                   '_Static_assert(SS_GUIDED_MAX_ROWS == 16384 && SS_ABI_VERSION == 5 && SS_MAX_LEVELS == 16, "constants");\n')
+    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)])
+    for f, off in (("chi2", 0), ("min_ratio", 4), ("lambda_", 8), ("min_inliers", 16), ("max_iterations", 20), ("refine_steps", 24), ("seed", 28), ("reserved", 32)):
+        assert getattr(binding.PnpParams, f).offset == off, f
+    for f, off in (("rcw", 0), ("tcw", 72), ("state", 96), ("status", 100), ("n_corr", 104), ("n_inliers", 108), ("best_inliers", 112), ("iteration", 116),
+                   ("reserved", 120)):
+        assert getattr(binding.PnpResult, f).offset == off and N.RESULT_DTYPE.fields[f][1] == off, f
+    assert lib.ss_abi_version() == 5 and binding.ABI_VERSION == 5
+    assert "tests/pnp_ref.py is its normative" in text
+    for word in ("the draw stream", "no covariance", "no planar branch", "the mean of the column norms", "Horn's quaternion (an SVD there)",
+                 "the pose rule's step", "iterate(5)", "no final refit", "max_iterations is the caller's number", "inverse iteration"):
+        assert word in text, word  # every deviation is listed
+
+
+# ---- the draw ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [6, 7, 8, 64, 16384])
+def test_draws_are_distinct_in_range_and_the_literal_array_form(n):
+    for seed, problem in ((0, 0), (1, 0), (0xDEADBEEF, 7), (0xFFFFFFFF, 65535)):
+        for t in range(300):
+            d = N.draw(seed, problem, t, n)
+            assert len(set(d)) == 6 and all(0 <= v < n for v in d), (n, seed, problem, t, d)
+            assert d == N.draw_literal(seed, problem, t, n), (n, seed, problem, t)
+            if n == 6:
+                assert sorted(d) == [0, 1, 2, 3, 4, 5]
+    # the generalised draw at three is the Sim3 rule's
+    import sim3_ref
+    assert all(N.draw(5, 2, t, n, 3) == sim3_ref.draw(5, 2, t, n) for t in range(64))
+
+
+def test_the_draws_of_the_twin_are_the_restatements():
+    """ss_pnp_host with one hypothesis, no refinement and no threshold returns the model of that hypothesis' six draws.  The draw of
+    the twin is not exported: every bit-for-bit comparison of this file goes through it, and here the problem number and the seed
+    each change the six, and with them the result"""
+    sc = NC.make_scene(50, 40, 20, 48, 48)
+    base = dict(NC.CASES[0]["params"], max_iterations=1, min_inliers=0, min_ratio=0.0, refine_steps=0)
+    seen = set()
+    for seed, problem in ((0, 0), (1, 0), (0, 1), (0xFFFFFFFF, 65535), (77, 3)):
+        p = dict(base, seed=seed)
+        want = NC.solve_scene(sc, p, problem)
+        got = NC.host(sc, p, problem)
+        _same_result(got[0], want[0], f"seed {seed} problem {problem}")
+        assert np.array_equal(got[1], want[1])
+        seen.add(want[0]["rcw"].tobytes())
+    assert len(seen) == 5
+
+
+# ---- the model -----------------------------------------------------------------------------------------------------------------------
+SCALES6 = np.array([1.0, 1.2, 1.44, 1.728, 1.0, 1.2], f32)
+
+
+@pytest.mark.parametrize("refine_steps", [0, 5, 16])
+def test_model_twin_agrees_with_the_restatement(refine_steps):
+    rng = np.random.Generator(np.random.PCG64(700 + refine_steps))
+    view = NC.view()
+    p = binding.pnp_params(refine_steps=refine_steps)
+    sets = [(f"noisy {k}", x, u, np.arange(6)) for k, (x, u) in enumerate(zip(*NC.noisy_sextuples(rng, 120)))]
+    sets += [(f"exact {k}", x, u, np.arange(6)) for k, (x, u) in enumerate(zip(*NC.exact_sextuples(rng, 30)))]
+    sets += NC.degenerate_sextuples()
+    moved = 0
+    for name, xyz, uv, rows in sets:
+        got = binding.pnp_model_host(p, view, xyz, uv, SCALES6, rows)
+        rcw, tcw = N.model(xyz, uv, SCALES6, rows, view, 1e-6, refine_steps)
+        assert got["rcw"].tobytes() == rcw.tobytes() and got["tcw"].tobytes() == tcw.tobytes(), f"{name}: {got['rcw']} {got['tcw']} != {rcw} {tcw}"
+        assert np.isfinite(got["rcw"]).all() and np.isfinite(got["tcw"]).all(), name
+        assert got["state"] == 0 and got["iteration"] == -1 and got["n_corr"] == 0
+        assert got["rcw"].any() or not name.startswith(("noisy", "exact")), name  # an ordinary sextuple has a model
+        if refine_steps:
+            lin = N.model(xyz, uv, SCALES6, rows, view, 1e-6, 0)
+            moved += lin[0].tobytes() != rcw.tobytes()
+    names = [s[0] for s in sets]
+    assert refine_steps == 0 or moved >= 140
+    for broken in ("a repeated point row", "infinite in a point", "NaN in a point", "NaN in a keypoint", "infinite in a keypoint"):
+        k = names.index(broken)
+        assert not N.model(sets[k][1], sets[k][2], SCALES6, sets[k][3], view, 1e-6, refine_steps)[0].any(), broken
+
+
+def test_refinement_is_not_optional_polish():
+    """1 px noise: the linear pose against three and five steps of the refinement, measured with the restatement's twin.  The issue's
+    prototype gave 0.03 rad (median) and 0.3 rad (95th percentile) without, 0.003 and 0.009 with three steps"""
+    rng = np.random.Generator(np.random.PCG64(11))
+    xyz, uv = NC.noisy_sextuples(rng, 400, 1.0)
+    view, r_true = NC.view(), np.asarray(NC.POSE[0])
+    err = {}
+    for steps in (0, 3, 5):
+        p = binding.pnp_params(refine_steps=steps)
+        e = []
+        for x, u in zip(xyz, uv):
+            r = binding.pnp_model_host(p, view, x, u, np.ones(6, f32), np.arange(6))["rcw"].reshape(3, 3)
+            e.append(np.arccos(np.clip((np.trace(r @ r_true.T) - 1.0) / 2.0, -1.0, 1.0)) if r.any() else np.pi)
+        err[steps] = (float(np.median(e)), float(np.percentile(e, 95)))
+    print("rotation error (median, 95th percentile) in rad by refinement steps:", err)
+    assert err[3][0] < err[0][0] / 3 and err[3][1] < err[0][1] / 3
+    assert err[3][0] < 0.01 and err[5][0] < 0.01
+
+
+def _independent_linear(xyz, uv, cam):
+    """the same least-squares problem through numpy: the smallest eigenvector of H by eigh, the nearest rotation by svd"""
+    H, O, d, b = N.normal_matrix(xyz, uv, cam)
+    H, O, d, b = np.array(H), np.array(O), np.array(d), np.array(b)
+    w, v = np.linalg.eigh(H)
+    x = v[:, 0]
+    rhat, that = x[:9].reshape(3, 3).T, x[9:]  # columns c1 c2 c3
+    if sum(b[i] @ (rhat @ d[i, :3] + that) for i in range(6)) < 0:
+        rhat, that = -rhat, -that
+    s = 3.0 / np.linalg.norm(rhat, axis=0).sum()
+    u, _, vt = np.linalg.svd(rhat)
+    r = u @ np.diag([1.0, 1.0, np.linalg.det(u @ vt)]) @ vt
+    return r, s * that - r @ O, w
+
+
+def test_linear_model_against_two_independent_derivations():
+    rng = np.random.Generator(np.random.PCG64(26))
+    xyz, uv = NC.exact_sextuples(rng, LINEAR_N, LINEAR_MIN_SPREAD)
+    view = NC.view()
+    cam = N.camera(view)
+    p = binding.pnp_params(refine_steps=0)
+    r_true, t_true = np.asarray(NC.POSE[0]), np.asarray(NC.POSE[1])
+    worst = np.zeros(4)
+    for k in range(LINEAR_N):
+        assert NC.spread_of(xyz[k]) >= LINEAR_MIN_SPREAD, k
+        got = binding.pnp_model_host(p, view, xyz[k], uv[k], np.ones(6, f32), np.arange(6))
+        r, t = got["rcw"].reshape(3, 3), got["tcw"]
+        assert r.any(), k
+        assert abs(np.linalg.det(r) - 1.0) < 1e-12 and np.abs(r @ r.T - np.eye(3)).max() < 1e-12, k  # a proper rotation
+        ri, ti, w = _independent_linear(xyz[k], uv[k], cam)
+        assert w[0] < 1e-9 * w[1], (k, w[:3])  # exact data: one null direction, well separated
+        worst = np.maximum(worst, [np.abs(r - ri).max(), np.abs(t - ti).max(), np.abs(r - r_true).max(), np.abs(t - t_true).max()])
+    print("linear model, largest deviation (R, t against eigh + svd; R, t against the ground truth):", worst)
+    assert worst[0] <= BOUND_EIGH[0] and worst[1] <= BOUND_EIGH[1], worst
+    assert worst[2] <= BOUND_TRUTH[0] and worst[3] <= BOUND_TRUTH[1], worst
+
+
+# ---- steps 1 and 3e --------------------------------------------------------------------------------------------------------------------
+def _identity_model(tz=0.0):
+    m = np.zeros((), N.RESULT_DTYPE)
+    m["rcw"], m["tcw"] = np.eye(3).reshape(9), (0.0, 0.0, tz)
+    return m
+
+
+def _couple(x, y, z, u, v, octave=0):
+    import guided_cases as G
+    return NC.points_of(np.array([[x, y, z]], f32)), G.kp_rows(f32([u]), f32([v]), octave=octave)
+
+
+def _check(chi2, pts, kp, model, scale=(1.0,), view=None):
+    view = NC.view() if view is None else view
+    out, err = binding.pnp_check_host(binding.pnp_params(chi2=chi2), view, np.asarray(scale, f32), pts, kp, model)
+    c = N.correspondences(pts, kp, None, np.arange(len(pts)), np.asarray(scale, f32), chi2)
+    if len(c["rows"]) == len(pts):  # the restatement's verdict on the same couples
+        front, e = N.errors(c, model["rcw"], model["tcw"], view)
+        with np.errstate(all="ignore"):
+            want = np.where(~front, 2, np.where(e < c["max"], 0, 3))
+        assert np.array_equal(out, want), (out, want)
+        assert np.array_equal(err[front].view(np.int32), e[front].view(np.int32)) and not err[~front].any()
+    return out, err
+
+
+def test_thresholds_from_both_sides_and_the_octave_table():
+    model = _identity_model()
+    # a point on the optical axis projects to (cx, cy); the keypoint three pixels off: the error is the float 9.0
+    pts, kp = _couple(0.0, 0.0, 5.0, f32(NC.CX) + f32(3.0), NC.CY)
+    out, err = _check(9.0, pts, kp, model)
+    assert err[0] == f32(9.0) and out[0] == 3  # max on the error: rejected
+    out, err = _check(float(np.nextafter(f32(9.0), f32(10.0))), pts, kp, model)
+    assert err[0] == f32(9.0) and out[0] == 0  # the error one ulp below max: accepted
+    out, _ = _check(float(np.nextafter(f32(9.0), f32(0.0))), pts, kp, model)
+    assert out[0] == 3
+    # the scale of the octave squares into max: at scale 2 the same error passes chi2 = 2.2500002 and fails 2.25
+    out, _ = _check(2.25, pts, dict_octave(kp, 1), model, scale=(1.0, 2.0))
+    assert out[0] == 3
+    out, _ = _check(float(np.nextafter(f32(2.25), f32(3.0))), pts, dict_octave(kp, 1), model, scale=(1.0, 2.0))
+    assert out[0] == 0
+    # depth: Z_cam at 0 fails the depth test; at the next float above it passes that test (and fails the error: invz is infinite)
+    for z, want in ((0.0, 2), (-0.0, 2), (-1.0, 2), (float(np.nextafter(f32(0.0), f32(1.0))), 3), (float("nan"), 2)):
+        pts, kp = _couple(0.0, 0.0, z, NC.CX, NC.CY)
+        out, err = _check(5.991, pts, kp, model)
+        assert out[0] == want, (z, out)
+    pts, kp = _couple(0.5, 0.0, 1.0, f32(NC.CX) + f32(0.5) * f32(NC.FX), NC.CY)
+    assert _check(5.991, pts, kp, _identity_model(-1.0))[0][0] == 2  # t brings it onto the camera plane
+    # the smallest depth at which the projection is finite again passes with its keypoint on it
+    assert _check(5.991, pts, kp, model)[0][0] == 0
+    # octaves: the last entry of the table is a correspondence, the first outside and a negative one are not
+    table = PC.scale()
+    for octave, want in ((len(table) - 1, 0), (len(table), 1), (-1, 1), (1 << 20, 1)):
+        pts, kp = _couple(0.0, 0.0, 5.0, NC.CX, NC.CY, octave)
+        out, err = binding.pnp_check_host(binding.pnp_params(), NC.view(), np.asarray(table, f32), pts, kp, model)
+        assert out[0] == want and err[0] == 0.0, (octave, out)
+        c = N.correspondences(pts, kp, None, [0], table, 5.991)
+        assert len(c["rows"]) == (want == 0)
+    # a table of one level and of sixteen
+    for levels in (1, 16):
+        table = PC.scale_table(1.2, levels)
+        for octave, want in ((levels - 1, 0), (levels, 1)):
+            pts, kp = _couple(0.0, 0.0, 5.0, NC.CX, NC.CY, octave)
+            assert binding.pnp_check_host(binding.pnp_params(), NC.view(), np.asarray(table, f32), pts, kp, model)[0][0] == want
+    # the zero model passes nothing
+    zero = np.zeros((), N.RESULT_DTYPE)
+    sc = NC.case_scene(0)
+    c = NC.corr_of(sc)
+    out, _ = binding.pnp_check_host(binding.pnp_params(), sc["view"], np.asarray(PC.scale(), f32), sc["points"][c["cols"]], sc["kp"][c["rows"]], zero)
+    assert (out == 2).all() and not N.inliers(c, zero["rcw"], zero["tcw"], sc["view"]).any()
+
+
+def dict_octave(kp, octave):
+    kp = kp.copy()
+    kp["octave"] = octave
+    return kp
+
+
+# ---- states and selection ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k", range(len(NC.CASES)), ids=NC.CASE_NAMES)
+def test_cases_reach_their_states_on_the_reference_and_the_twin(k):
+    case, sc = NC.CASES[k], NC.case_scene(k)
+    p = case["params"]
+    res, flags, counts = NC.reference(k)
+    assert res["state"] == case["expect_state"], (int(res["state"]), None if counts is None else counts.max())
+    assert len(sc["kp"]) <= NC.ROWS and len(sc["points"]) <= NC.ROWS
+    got = NC.host(sc, p)
+    _same_result(got[0], res, case["name"])
+    assert np.array_equal(got[1], flags)
+    c = NC.corr_of(sc, p["chi2"])
+    n = len(c["rows"])
+    assert res["n_corr"] == n == len(sc["rows"]) and res["reserved"].tolist() == [0, 0] and res["status"] == 0
+    if res["state"] == 1:
+        assert counts is None and (n < 6 or n < p["min_inliers"]) and not flags.any() and res["iteration"] == -1 and res["best_inliers"] == 0
+        return
+    # every count recomputed through the twins of steps 3b - 3e, with the draws of the restatement
+    params = binding.pnp_params(**p)
+    scale = np.asarray(PC.scale(), f32)
+    again = []
+    for t in range(p["max_iterations"]):
+        pick = N.draw(p["seed"], 0, t, n)
+        m = binding.pnp_model_host(params, sc["view"], c["X"][pick], np.stack([c["u"][pick], c["v"][pick]], 1), c["s"][pick], c["cols"][pick])
+        out, _ = binding.pnp_check_host(params, sc["view"], scale, sc["points"][c["cols"]], sc["kp"][c["rows"]], m)
+        again.append(int((out == 0).sum()))
+    assert again == counts.tolist()
+    best = int(counts.max())
+    first = int(np.flatnonzero(counts == best)[0])
+    assert res["best_inliers"] == best
+    qualifies = best >= p["min_inliers"] and f32(best) >= f32(p["min_ratio"]) * f32(n)
+    assert (res["state"] == 0) == bool(qualifies)
+    if res["state"] == 0:
+        assert res["iteration"] == first and res["n_inliers"] == best == flags.sum()
+        assert set(np.flatnonzero(flags).tolist()) <= set(sc["rows"].tolist())
+        r = res["rcw"].reshape(3, 3)
+        assert np.abs(r @ r.T - np.eye(3)).max() < 1e-9
+    else:
+        assert res["iteration"] == -1 and res["n_inliers"] == 0 and not flags.any() and not res["rcw"].any() and not res["tcw"].any()
+
+
+def test_the_table_is_what_its_names_say():
+    by = {c["name"]: NC.reference(k) for k, c in enumerate(NC.CASES)}
+    ties = by["ties: 30 exact correspondences, the smallest t wins"]
+    assert (ties[2] == 30).sum() > 1 and ties[0]["iteration"] == int(np.flatnonzero(ties[2] == 30)[0])
+    for name in ("min_inliers met: 30 of 30", "min_inliers missed: 30 of 31", "min_ratio met: 30 >= 0.75 * 40", "min_ratio missed: 30 < 0.76 * 40"):
+        assert by[name][0]["best_inliers"] == 30 and by[name][0]["n_corr"] == 40, name
+    assert by["min_ratio off: 14 inliers of 30"][0]["n_inliers"] == 14 and by["min_ratio on: 14 < 0.5 * 30"][0]["best_inliers"] == 14
+    # the winner of the noisy scene finds the planted pose and the planted inliers
+    res, flags, _ = by["state 0: 60 correspondences, 24 gross outliers, 0.5 px noise"]
+    sc = NC.case_scene(0)
+    assert set(sc["inlier_rows"].tolist()) <= set(np.flatnonzero(flags).tolist())
+    assert np.abs(res["rcw"].reshape(3, 3) - NC.POSE[0]).max() < 0.02 and np.abs(res["tcw"] - NC.POSE[1]).max() < 0.1
+    # the problem number is in the draw stream
+    assert NC.reference(0, 1)[0]["iteration"] != res["iteration"] or NC.reference(0, 2)[0]["iteration"] != res["iteration"]
+
+
+def test_degenerate_scenes_and_skip_bytes_on_the_twin():
+    p = dict(NC.CASES[0]["params"], max_iterations=16)
+    for name, sc in NC.degenerate_scenes():
+        want = NC.solve_scene(sc, p)
+        got = NC.host(sc, p)
+        _same_result(got[0], want[0], name)
+        assert np.array_equal(got[1], want[1]) and np.isfinite(got[0]["rcw"]).all() and np.isfinite(got[0]["tcw"]).all(), name
+    sc = dict(NC.case_scene(0))
+    sc["skip"] = np.zeros(len(sc["points"]), np.uint8)
+    sc["skip"][sc["idx"][sc["rows"][:7]]] = [1, 2, 255, 1, 1, 7, 128]
+    want = NC.solve_scene(sc, p)
+    got = NC.host(sc, p)
+    _same_result(got[0], want[0], "skip bytes")
+    assert np.array_equal(got[1], want[1]) and want[0]["n_corr"] == NC.reference(0)[0]["n_corr"] - 7 and not want[1][sc["rows"][:7]].any()
+    void = NC.solve_scene(sc, p, status=-5)
+    assert void[0]["state"] == 1 and void[0]["status"] == -5 and void[0]["n_corr"] == 0
+
+
+@pytest.mark.parametrize("seed", NC.RECOVERY_SEEDS)
+def test_recovery_of_the_planted_inliers(seed):
+    """200 correspondences, 40 % gross outliers, 0.5 px noise, 300 hypotheses, refine_steps 5: the winner's inliers contain at least 90 %
+    of the planted ones.  The seeds are those for which the restatement alone passes: the first one is run through it here, all of them
+    were when the test was written (each kept 100 %), and the twin that runs them all equals it bit for bit on every case above"""
+    sc = NC.recovery_scene(seed)
+    p = dict(NC.RECOVERY, seed=seed)
+    res, flags = NC.host(sc, p)
+    planted = sc["inlier_rows"]
+    assert len(planted) == 120 and res["n_corr"] == 200 and res["state"] == 0
+    kept = int(flags[planted].sum())
+    print(f"seed {seed}: {kept} of {len(planted)} planted inliers kept, {int(res['n_inliers'])} inliers in all, winner {int(res['iteration'])}")
+    assert kept >= 0.9 * len(planted)
+    assert np.abs(res["rcw"].reshape(3, 3) - NC.POSE[0]).max() < 0.01 and np.abs(res["tcw"] - NC.POSE[1]).max() < 0.05
+    if seed == NC.RECOVERY_SEEDS[0]:
+        want = NC.solve_scene(sc, p)
+        _same_result(res, want[0], "recovery on the restatement")
+        assert np.array_equal(flags, want[1]) and int(want[1][planted].sum()) >= 0.9 * len(planted)
+
+
+# ---- refusals ------------------------------------------------------------------------------------------------------------------------
+def test_invalid_arguments_are_refused_without_a_device():
+    sc = NC.case_scene(0)
+    ok = dict(NC.CASES[0]["params"])
+    for bad in (dict(chi2=0.0), dict(chi2=float("nan")), dict(chi2=float("inf")), dict(min_ratio=-0.1), dict(min_ratio=float("nan")), dict(lambda_=-1.0),
+                dict(lambda_=float("inf")), dict(min_inliers=-1), dict(max_iterations=0), dict(max_iterations=1025), dict(refine_steps=-1),
+                dict(refine_steps=17), dict(reserved=(1, 0)), dict(reserved=(0, 1))):
+        with pytest.raises(binding.OrbError) as e:
+            NC.host(sc, dict(ok, **bad))
+        assert e.value.code == binding.SS_ERR_INVALID_ARG, bad
+        with pytest.raises(binding.OrbError):
+            binding.pnp_model_host(binding.pnp_params(**dict(ok, **bad)), sc["view"], np.zeros((6, 3), f32), np.zeros((6, 2), f32), np.ones(6, f32), np.arange(6))
+        with pytest.raises(binding.OrbError):
+            binding.pnp_check_host(binding.pnp_params(**dict(ok, **bad)), sc["view"], PC.scale(), sc["points"][:1], sc["kp"][:1], _identity_model())
+    for good in (dict(max_iterations=1), dict(max_iterations=1024), dict(refine_steps=0), dict(refine_steps=16), dict(min_ratio=0.0), dict(lambda_=0.0)):
+        NC.host(NC.case_scene(9), dict(ok, **good))
+    for levels in (np.zeros(0, f32), np.ones(17, f32)):
+        with pytest.raises(binding.OrbError):
+            NC.host(sc, ok, scale=levels)
+        with pytest.raises(binding.OrbError):
+            binding.pnp_check_host(binding.pnp_params(), sc["view"], levels, sc["points"][:1], sc["kp"][:1], _identity_model())
+    with pytest.raises(binding.OrbError):
+        NC.host(sc, ok, problem=-1)
+    lib = binding.load()
+    p = binding.pnp_params()
+    assert lib.ss_pnp_pairs_device(None, None, None, None, 1, 1, None, None, 1, 1, None, 0, None, None, None, C.byref(p), None, None) == binding.SS_ERR_INVALID_ARG
+    assert lib.ss_pnp_batch_device(None, None, None, None, 1, 1, None, 0, None, None, None, C.byref(p), None, None) == binding.SS_ERR_INVALID_ARG
+    assert lib.ss_pnp(None, None, None, None, 0, None, 0, None, C.byref(p), None, None) == binding.SS_ERR_INVALID_ARG
+    assert lib.ss_pnp_model_host(None, None, None, None, None, None, None) == binding.SS_ERR_INVALID_ARG
+    assert lib.ss_pnp_host(None, None, 0, None, None, 0, None, 0, None, None, 0, None, None) == binding.SS_ERR_INVALID_ARG
+    # the empty problem is no error
+    empty = dict(sc, points=sc["points"][:0], kp=sc["kp"][:0], idx=sc["idx"][:0])
+    res, flags = NC.host(empty, ok)
+    assert res["state"] == 1 and res["n_corr"] == 0 and len(flags) == 0
+
+
+def test_steps_under_address_and_undefined_sanitizers(tmp_path):
+    """tests/native/pnp_steps_asan.cpp: its own main, the steps header, -fsanitize=address,undefined; run as a child process with
+    the environment as it is"""
+    exe = str(tmp_path / "pnp_steps_asan")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-Wall", "-Wextra", "-Werror", "-I" + os.path.join(ROOT, "send-slam_amd", "csrc"), "-o", exe,
+                           os.path.join(ROOT, "tests", "native", "pnp_steps_asan.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-4000:]
+    assert int(out.stdout.split()[1]) > 40000

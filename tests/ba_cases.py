@@ -24,16 +24,19 @@ def true_pose(k: int):
 
 
 def make_problem(seed: int, n_kf: int, n_free: int, n_points: int, p_obs: float = 0.7, n_out: int = 0, stereo_every: int = 0, noise: float = 0.5,
-                 point_noise: float = 0.03, pose_off=(1.0 * DEG, 0.05), cams=None, rows: int | None = None, skip_every: int = 0, min_obs: int = 2):
+                 point_noise: float = 0.03, pose_off=(1.0 * DEG, 0.05), cams=None, rows: int | None = None, skip_every: int = 0, min_obs: int = 2, scale=None,
+                 octave_edits: int = 0):
     """n_points map points, each seen by a keyframe with probability p_obs (and by min_obs at the least); the first n_out observations
     drawn, of points that three keyframes see, are gross outliers; every stereo_every-th keypoint row has a right coordinate; every skip_every-th point row carries a skip
     byte.  cams: one (fx, fy, cx, cy, bf) per keyframe (None: the square camera).  The free keyframes (the first n_free) start pose_off
     = (angle, distance) away from the truth, the fixed ones at it.  -> a dict: views, start [n_kf][12], n_free, points, kp [n_kf][rows],
     idx [n_kf][n_points], right [n_kf][rows], skip, n_kp, truth (poses [n_kf][12], xyz [n_points][3] in double), planted (bool
-    [n_kf][n_points]: the gross outliers)"""
+    [n_kf][n_points]: the gross outliers).  scale: the pyramid table the octaves and the noise are drawn against (None: the default
+    one, PC.scale()).  octave_edits: after everything is drawn, that many observations (spread over the keyframes, none a planted
+    outlier) get the octaves -1, n_levels and n_levels - 1 in turn -> edited: a list of (keyframe, point row, octave)"""
     rng = np.random.Generator(np.random.PCG64(seed))
     rows = rows or max(n_points, 1)
-    sc = np.asarray(PC.scale(), f32)
+    sc = np.asarray(PC.scale() if scale is None else scale, f32)
     cams = [CC.SQUARE] * n_kf if cams is None else [cams[k % len(cams)] for k in range(n_kf)]
     xyz = np.empty((n_points, 3))
     xyz[:, 2] = rng.uniform(4.0, 10.0, n_points)
@@ -84,8 +87,17 @@ def make_problem(seed: int, n_kf: int, n_free: int, n_points: int, p_obs: float 
     skip = None
     if skip_every:
         skip = (np.arange(n_points) % skip_every == 1).astype(np.uint8)
-    return {"views": np.array(views), "start": start, "n_free": n_free, "points": PO.points_of(moved), "kp": kp, "idx": idx, "right": right if stereo_every else None,
-            "skip": skip, "n_kp": np.full(n_kf, rows, np.int32), "truth": (truth, xyz.astype(f32).astype(np.float64)), "planted": planted}
+    edited = []
+    if octave_edits:
+        where = np.argwhere((idx >= 0) & ~planted)
+        for j, (k, i) in enumerate(where[np.linspace(0, len(where) - 1, octave_edits).astype(int)]):
+            edited.append((int(k), int(i), (-1, len(sc), len(sc) - 1)[j % 3]))
+            kp["octave"][k, idx[k, i]] = edited[-1][2]
+    pr = {"views": np.array(views), "start": start, "n_free": n_free, "points": PO.points_of(moved), "kp": kp, "idx": idx, "right": right if stereo_every else None,
+          "skip": skip, "n_kp": np.full(n_kf, rows, np.int32), "truth": (truth, xyz.astype(f32).astype(np.float64)), "planted": planted}
+    if octave_edits:
+        pr["edited"] = edited
+    return pr
 
 
 def _case(name, problem_kw, **params):
@@ -144,3 +156,86 @@ def frozen_problem():
 
 
 FROZEN_PARAMS = dict(BR.DEFAULTS, lambda_=0.0, lambda_min=0.0)
+
+
+# ---- rotated camera rows, other pyramid tables, row counts, a free keyframe nobody sees -------------------------------------------------
+CAMERA_PARAMS = dict(BR.DEFAULTS, n_rounds=2, iterations=(2, 1, 0, 0), check_right=True)
+
+
+@functools.lru_cache(maxsize=None)
+def camera_problems():
+    """three problems of four keyframes for one call: keyframe k of problem q has camera (k + q) % 3 of camera_cases.FRAME_CAMERAS, so
+    with first frames 0, 4 and 8 no two problems share a camera row, and views[k] for views[first_frame + k] gives problems 1 and 2
+    other cameras"""
+    return [make_problem(seed=800 + q, n_kf=4, n_free=2, n_points=60, n_out=6, stereo_every=2, cams=[CC.FRAME_CAMERAS[(k + q) % 3] for k in range(4)])
+            for q in range(3)]
+
+
+def with_cameras(problems, cams):
+    """the problems of a call under the cameras `cams`, one per frame of the call (a mix-up's: what a wrong kernel would read)"""
+    out, f0 = [], 0
+    for pr in problems:
+        n_kf = len(pr["views"])
+        out.append(dict(pr, views=np.array([PO.view(cam=c) for c in cams[f0:f0 + n_kf]])))
+        f0 += n_kf
+    return out
+
+
+def call_cameras(problems):
+    """(fx, fy, cx, cy, bf) of every frame of a call"""
+    return [tuple(float(v[n]) for n in ("fx", "fy", "cx", "cy", "bf")) for pr in problems for v in pr["views"]]
+
+
+PYRAMID_NAMES = ("one_level", "factor_2", "sixteen_levels")
+PYRAMID_PARAMS = dict(BR.DEFAULTS, n_rounds=2, iterations=(2, 1, 0, 0))
+
+
+@functools.lru_cache(maxsize=None)
+def pyramid_problem(name: str):
+    """-> (problem, table): octaves and noise drawn against PC.PYRAMIDS[name]; nine observations carry the octaves -1, n_levels and
+    n_levels - 1, three each (pr["edited"])"""
+    table = PC.scale_table(*PC.PYRAMIDS[name])
+    return make_problem(seed=820 + PYRAMID_NAMES.index(name), n_kf=4, n_free=2, n_points=80, n_out=6, scale=table, octave_edits=9), table
+
+
+ROW_COUNTS = (100, 91, 0, 64, 100)
+ROW_COUNT_PARAMS = dict(BR.DEFAULTS, n_rounds=2, iterations=(2, 1, 0, 0))
+
+
+@functools.lru_cache(maxsize=None)
+def row_count_problem():
+    """five keyframes of 100 keypoint rows, told ROW_COUNTS: keyframe 2 (fixed) has none, keyframes 1 and 3 lose the observations whose
+    keypoint row lies at or past their count.  Four points that keep two good observations besides carry junk in one more keyframe's
+    idx: n_kp[k], n_kp[k] + 5, 1 << 30 and -7 (pr["junk"]: a list of (keyframe, point row, entry))"""
+    pr = make_problem(seed=840, n_kf=5, n_free=2, n_points=90, n_out=6, rows=100)
+    pr = dict(pr, idx=pr["idx"].copy(), n_kp=np.array(ROW_COUNTS, np.int32))
+    good = (pr["idx"] >= 0) & (pr["idx"] < pr["n_kp"][:, None])
+    junk = []
+    for i in np.flatnonzero(good.sum(axis=0) >= 3):
+        k = (1, 3, 0, 4)[len(junk)]
+        if good[k, i]:
+            junk.append((k, int(i), (int(pr["n_kp"][k]), int(pr["n_kp"][k]) + 5, 1 << 30, -7)[len(junk)]))
+            pr["idx"][k, i] = junk[-1][2]
+            if len(junk) == 4:
+                break
+    assert len(junk) == 4
+    pr["junk"] = junk
+    return pr
+
+
+def without_junk(pr):
+    """the row-count problem with -1 where the rule sees no observation: an entry at or past n_kp[k], or below -1"""
+    idx = np.where((pr["idx"] >= 0) & (pr["idx"] < np.clip(pr["n_kp"], 0, pr["kp"].shape[1])[:, None]), pr["idx"], -1).astype(np.int32)
+    return dict(pr, idx=idx)
+
+
+@functools.lru_cache(maxsize=None)
+def unobserved_free_problem():
+    """camera_problems()[0] with no observation in keyframe 0, which is free: its diagonal block is lambda alone"""
+    pr = camera_problems()[0]
+    idx = pr["idx"].copy()
+    idx[0] = -1
+    return dict(pr, idx=idx)
+
+
+UNOBSERVED_PARAMS = (dict(CAMERA_PARAMS), dict(CAMERA_PARAMS, lambda_=0.0, lambda_min=0.0))

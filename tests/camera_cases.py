@@ -8,6 +8,7 @@ a kernel that takes fy for fx, one frame's record for another's or one side of a
     PAIR_CAMERAS      (camera 1, camera 2) of the three pairs of a 320 x 240 call
     SIM3_PAIR_CAMERAS the same for the 640 x 480 Sim3 scenes
     FRAME_MIXUPS      name -> (the cameras of a call -> the cameras a wrong kernel would use)
+    frame_mixups(row) FRAME_MIXUPS and "every problem with problem 0's camera row", for calls whose problems own `row` frames each
     PAIR_MIXUPS       the same for calls of pairs; bf is no part of a pair, so it has no mix-up there
 
 tests/test_*_ref.py run every reference under every mix-up and assert that the bytes the GPU tests compare change.
@@ -50,6 +51,16 @@ FRAME_MIXUPS = {
     "every frame with its neighbour's camera": lambda cams: [cams[(b + 1) % len(cams)] for b in range(len(cams))],
     "bf of another frame": lambda cams: [with_bf(c, cams[(b + 1) % len(cams)]) for b, c in enumerate(cams)],
 }
+
+PROBLEM_ROW_MIXUP = "every problem with problem 0's camera row"
+
+
+def frame_mixups(row: int):
+    """FRAME_MIXUPS for a call whose problems each own `row` consecutive frames (the local bundle adjustment's keyframes), with one
+    more: keyframe k of every problem read at views[k], not at views[first_frame + k].  It is a function of the row length, so it
+    stands beside the table: the families that run one frame per problem iterate over FRAME_MIXUPS, where it would change nothing"""
+    return dict(FRAME_MIXUPS, **{PROBLEM_ROW_MIXUP: lambda cams: [cams[b % row] for b in range(len(cams))]})
+
 
 PAIR_MIXUPS = {
     "fx and fy exchanged": lambda pairs: [(swap_f(a), swap_f(b)) for a, b in pairs],

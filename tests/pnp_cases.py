@@ -16,6 +16,7 @@ import functools
 
 import numpy as np
 
+import camera_cases as CC
 import guided_cases as G
 import pnp_ref as N
 import proj_cases as PC
@@ -213,6 +214,69 @@ def degenerate_scenes():
     sc["idx"][sc["rows"][6]] = sc["idx"][sc["rows"][5]]  # two keypoints on one point row
     scenes.append(("broken rows among good ones", sc))
     return scenes
+
+
+# ---- a camera per problem, strides that differ, counts told wrong ----------------------------------------------------------------------
+CAMERA_POSES = (POSE, (PC.rot(-0.2, 0.25, -0.15), (-0.4, 0.1, 0.8)), (PC.rot(0.1, 0.1, 0.3), (0.2, 0.3, -0.2)))
+CAMERA_PARAMS = dict(chi2=5.991, min_ratio=0.5, lambda_=1e-6, min_inliers=10, max_iterations=24, refine_steps=5, seed=7)
+CAMERA_INLIERS, CAMERA_WINNERS = 36, (3, 3, 6)  # of every scene as problem b of one call (asserted on the restatement)
+
+
+def camera_scenes(cams=CC.SIM3_FRAME_CAMERAS):
+    """scene b under camera b of camera_cases.SIM3_FRAME_CAMERAS (P, Q, the square one) and pose b, to be run as problem b of one call:
+    48 correspondences, 12 gross outliers, 0.5 px noise, over 64 keypoint rows and 80 point rows.  cams: the cameras the views are
+    built from (a mix-up's, where a test shows what a wrong kernel would compute); the keypoints are always the true cameras'"""
+    scenes = [make_scene(300 + b, 48, 12, 64, 80, noise=0.5, cam=CC.intrinsics(CC.SIM3_FRAME_CAMERAS[b]), pose=CAMERA_POSES[b]) for b in range(3)]
+    return [dict(sc, view=view(CC.intrinsics(c))) for sc, c in zip(scenes, cams)]
+
+
+def cut(sc):
+    """what a call may read of sc: the rows under the counts it is told (the keys n_points and n_kp, where they are not the lengths of
+    the arrays), clamped to 0 .. the rows there are, as the rule clamps them"""
+    n_p = min(max(sc.get("n_points", len(sc["points"])), 0), len(sc["points"]))
+    n_k = min(max(sc.get("n_kp", len(sc["kp"])), 0), len(sc["kp"]))
+    return dict(sc, points=sc["points"][:n_p], kp=sc["kp"][:n_k], idx=sc["idx"][:n_k], skip=None if sc["skip"] is None else sc["skip"][:n_p])
+
+
+# (point_rows, rows_per_frame, the n_points and the n_kp told for each scene): no count reaches either row figure, so whichever of the
+# two a stride or a clamp is taken from, only the stride shows
+STRIDE_LAYOUTS = {"more point rows than keypoint rows": (83, 67, (66, 60, 63), (61, 64, 58)),
+                  "fewer point rows than keypoint rows": (51, 69, (48, 48, 48), (50, 47, 49))}
+STRIDE_PARAMS = dict(chi2=5.991, min_ratio=0.3, lambda_=1e-6, min_inliers=10, max_iterations=16, refine_steps=5, seed=3)
+
+
+@functools.lru_cache(maxsize=None)
+def stride_scenes(layout: str):
+    """-> (three scenes, point_rows, rows_per_frame): 40 correspondences each (6 gross outliers, 0.5 px noise) under the counts told,
+    skip bytes on five matched points, and rows that look live past the counts: the keypoint rows past n_kp repeat matched rows with
+    their matches, the point rows past n_points repeat matched points, and three unmatched keypoint rows name them"""
+    point_rows, rows, n_points, n_kp = STRIDE_LAYOUTS[layout]
+    scenes = []
+    for b in range(3):
+        sc = dict(make_scene(310 + 3 * list(STRIDE_LAYOUTS).index(layout) + b, 40, 6, n_kp[b], n_points[b], noise=0.5))
+        more_k, more_p = sc["rows"][np.arange(rows - n_kp[b]) % 40], sc["idx"][sc["rows"]][np.arange(point_rows - n_points[b]) % 40]
+        sc["kp"], sc["points"] = np.concatenate([sc["kp"], sc["kp"][more_k]]), np.concatenate([sc["points"], sc["points"][more_p]])
+        sc["idx"] = np.concatenate([sc["idx"], sc["idx"][more_k]])
+        sc["idx"][np.flatnonzero(sc["idx"][:n_kp[b]] < 0)[:3]] = n_points[b] + np.arange(3) % (point_rows - n_points[b])
+        sc["skip"] = np.zeros(point_rows, np.uint8)
+        sc["skip"][sc["idx"][sc["rows"][b::8]]] = (1, 2, 255, 7, 128)
+        sc["n_points"], sc["n_kp"] = n_points[b], n_kp[b]
+        scenes.append(sc)
+    return scenes, point_rows, rows
+
+
+COUNT_ROWS, COUNT_POINT_ROWS = 64, 72
+COUNT_PARAMS = dict(chi2=5.991, min_ratio=0.5, lambda_=1e-6, min_inliers=10, max_iterations=16, refine_steps=5, seed=2)
+
+
+@functools.lru_cache(maxsize=None)
+def count_scenes():
+    """-> [(name, scene)]: one good scene whose arrays are COUNT_POINT_ROWS and COUNT_ROWS long, told counts past its rows and below
+    0.  The rule clamps a count to 0 .. rows: a count past the rows reads them all, a negative one none"""
+    sc = make_scene(330, 44, 8, COUNT_ROWS, COUNT_POINT_ROWS, noise=0.5)
+    told = (("n_kp = rows + 9", dict(n_kp=COUNT_ROWS + 9)), ("n_kp = -3", dict(n_kp=-3)),
+            ("n_points = point_rows + 5", dict(n_points=COUNT_POINT_ROWS + 5)), ("n_points = -2", dict(n_points=-2)))
+    return [(name, dict(sc, **kw)) for name, kw in told]
 
 
 # ---- recovery -------------------------------------------------------------------------------------------------------------------------

@@ -250,6 +250,72 @@ def test_frames_of_no_problem_and_the_frozen_point(ctx):
     assert only[0][:f0].tobytes() == start.tobytes() and (only[3][:f0] == 2).all()
 
 
+def test_three_problems_with_rotated_camera_rows(ctx):
+    """BC.camera_problems(): first frames 0, 4 and 8, and keyframe k of problem q under camera (k + q) % 3, so views[k] for
+    views[first_frame + k] in the staging, the blocks or the cost gives problems 1 and 2 other cameras (tests/test_ba_ref.py shows
+    on the reference that their bytes change).  Then the table's rows permuted: the frames stay, the problems follow the table"""
+    problems, p = BC.camera_problems(), BC.CAMERA_PARAMS
+    wants, got, dev, (point_rows, rows) = _against_reference(ctx, problems, p, "rotated camera rows", right=True)
+    assert dev["table"]["first_frame"].tolist() == [0, 4, 8] and [int(w[4]["n_obs"]) for w in wants] == [178, 182, 167]
+    assert all(w[4]["state"] == 0 and w[4]["n_stereo"] > 80 and w[4]["accepted"].tolist() == [2, 1, 0, 0] for w in wants)
+    order = [2, 0, 1]
+    perm = _run(ctx, dev, point_rows, rows, p, right=True, table=dev["table"][order])
+    assert perm[0].tobytes() == got[0].tobytes() and perm[3].tobytes() == got[3].tobytes()
+    for q, src in enumerate(order):
+        _check(f"rotated camera rows, permuted, problem {q}", perm, q, int(dev["table"]["first_frame"][src]), wants[src], point_rows)
+        assert perm[1][q].tobytes() == got[1][src].tobytes() and perm[2][q].tobytes() == got[2][src].tobytes() and perm[4][q].tobytes() == got[4][src].tobytes()
+
+
+@pytest.mark.parametrize("name", BC.PYRAMID_NAMES)
+def test_other_pyramid_tables(name):
+    """the octave test of the gather and the weights read the context's table: 1, 4 and 16 levels, with octaves -1, n_levels and
+    n_levels - 1 among the observations"""
+    from send_slam_amd import binding
+    factor, n_levels = PC.PYRAMIDS[name]
+    pr, table = BC.pyramid_problem(name)
+    p = BC.PYRAMID_PARAMS
+    want = BC.solve(pr, p, scale=table)
+    with binding.OrbContext(0, n_features=G.NF, scale_factor=factor, n_levels=n_levels) as c:
+        _against_reference(c, [pr, _from_truth(pr)], p, name, wants=[want, BC.solve(_from_truth(pr), p, scale=table)])
+    outside = [(k, i) for k, i, octave in pr["edited"] if octave in (-1, n_levels)]
+    assert len(table) == n_levels and len(outside) == 6 and want[4]["n_obs"] == (pr["idx"] >= 0).sum() - 6 and want[4]["state"] == 0
+    assert BC.solve(pr, p)[0].tobytes() != want[0].tobytes()  # the default table gives other poses
+
+
+def test_row_counts_and_junk_idx(ctx):
+    """n_kp = (100, 91, 0, 64, 100) over 100 rows with idx entries at n_kp[k], past it, at 1 << 30 and at -7; then the same with one
+    count told as rows + 9 and one as -3; and a second problem whose block is told n_points = point_rows + 5"""
+    pr, p = BC.row_count_problem(), BC.ROW_COUNT_PARAMS
+    second = BC.make_problem(seed=841, n_kf=3, n_free=1, n_points=90, n_out=4, rows=100)
+    problems = [pr, second]
+    point_rows, rows = 90, 100  # the arrays' own lengths: a count past them has nothing to hide behind
+    wants = [BC.solve(q, p) for q in problems]
+    assert wants[0][4]["state"] == 0 and (wants[0][3][2] == 2).all() and all(wants[0][3][k, i] == 2 for k, i, _ in pr["junk"])
+    dev = _upload(problems, point_rows, rows)
+    got = _run(ctx, dev, point_rows, rows, p)
+    for q, w in enumerate(wants):
+        _check(f"row counts, problem {q}", got, q, 5 * q, w, point_rows)
+    told = dict(pr, n_kp=np.array([rows + 9, 91, -3, 64, 100], np.int32))
+    dev = _upload([told, second], point_rows, rows)
+    dev["np"] = _to_dev(np.array([90, point_rows + 5], np.int32))
+    _sync()
+    assert dev["nk"].cpu().numpy()[:5].tolist() == [rows + 9, 91, -3, 64, 100]
+    again = _run(ctx, dev, point_rows, rows, p)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(again, got))
+
+
+def test_a_free_keyframe_without_observations(ctx):
+    """a free keyframe nobody observes: its block of the reduced system is lambda alone.  lambda is a call's, so two calls of two
+    problems each, an ordinary problem behind it: under the default lambda state 0, under lambda 0 state 2 with every byte finite
+    (_check demands it) and the problem behind it solved"""
+    pr = BC.unobserved_free_problem()
+    a, b = BC.UNOBSERVED_PARAMS
+    for p, state in ((a, 0), (b, 2)):
+        wants, got, _, _ = _against_reference(ctx, [pr, BC.camera_problems()[1]], p, f"unobserved free keyframe, lambda {p['lambda_']}", right=True)
+        assert wants[0][4]["state"] == state and wants[1][4]["state"] == 0 and (got[3][0] == 2).all()
+        assert got[0][0].tobytes() == wants[0][0][0].tobytes()
+
+
 def test_host_pointer_form_and_points_to_block(ctx):
     import torch
     from send_slam_amd import binding

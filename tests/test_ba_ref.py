@@ -3,6 +3,8 @@ reference (tests/ba_ref.py) bit for bit, the reference against an independent op
 Jacobians against central differences, the chi-square thresholds from both sides, the liveness of the shared cases, the refused
 arguments and the steps under the sanitizers."""
 import ctypes as C
+import functools
+import hashlib
 import os
 import subprocess
 
@@ -359,6 +361,125 @@ def test_the_frozen_point_freezes_and_only_it():
     _same("frozen", _host(pr, BC.FROZEN_PARAMS), want)
     # under a lambda that is not 0 it moves like any other
     assert BC.solve(pr, {})[4]["n_frozen_max"] == 0
+
+
+# ---- rotated camera rows, other pyramid tables, row counts, a free keyframe nobody sees -------------------------------------------------
+# sha256 over every array of case_problem(k) (keys in sorted order) and the five arrays of reference(k), k = 0 .. 4, computed at the
+# commit before make_problem gained `scale` and `octave_edits`
+SHARED_CASES_DIGEST = "e721bde84e25f6b25e3411ec2d5fc376b8833d40b974fcab093fc340064854c3"
+
+
+def test_the_shared_cases_are_the_bytes_they_were():
+    """make_problem's new arguments leave the random stream of the shared cases alone: problems and references byte for byte"""
+    h = hashlib.sha256()
+    for k in range(len(BC.CASES)):
+        pr = BC.case_problem(k)
+        assert sorted(pr) == ["idx", "kp", "n_free", "n_kp", "planted", "points", "right", "skip", "start", "truth", "views"]
+        for key in sorted(pr):
+            v = pr[key]
+            for a in (v if isinstance(v, tuple) else (v,)):
+                h.update(b"none" if a is None else str(a).encode() if isinstance(a, int) else np.ascontiguousarray(a).tobytes())
+        for a in BC.reference(k)[:5]:
+            h.update(np.ascontiguousarray(a).tobytes())
+    assert h.hexdigest() == SHARED_CASES_DIGEST
+
+
+@functools.lru_cache(maxsize=None)
+def _camera_reference():
+    return [BC.solve(pr, BC.CAMERA_PARAMS) for pr in BC.camera_problems()]
+
+
+def test_camera_problems_are_live_and_the_host_twin_equals_the_reference():
+    """three problems of four keyframes whose camera rows are rotations of one another: no two share a row, no row is one camera"""
+    problems = BC.camera_problems()
+    rows = [tuple(BC.call_cameras([pr])) for pr in problems]
+    assert len(set(rows)) == 3 and all(len(set(r)) == 3 for r in rows) and all(rows[q][k] == CC.FRAME_CAMERAS[(k + q) % 3] for q in range(3) for k in range(4))
+    wants = _camera_reference()
+    assert [int(w[4]["n_obs"]) for w in wants] == [178, 182, 167] and [int(w[4]["n_stereo"]) for w in wants] == [93, 90, 85]
+    for q, (pr, w) in enumerate(zip(problems, wants)):
+        assert w[4]["state"] == 0 and w[4]["steps"].tolist() == [2, 1, 0, 0] == w[4]["accepted"].tolist() and w[4]["cost_after"] < w[4]["cost_before"] / 20
+        _same(f"camera problem {q}", _host(pr, BC.CAMERA_PARAMS), w)
+
+
+@pytest.mark.parametrize("mixup", list(CC.frame_mixups(4)))
+def test_camera_mixups_change_the_reference(mixup):
+    """the twelve cameras of the call as a confused kernel would read them: every problem one of whose cameras changes has other poses
+    and another result record.  bf counts: the stereo rows read it.  views[k] for views[first_frame + k] leaves problem 0 alone"""
+    problems = BC.camera_problems()
+    cams = BC.call_cameras(problems)
+    mixed = CC.frame_mixups(4)[mixup](cams)
+    hit = sorted({f // 4 for f in CC.changed(cams, mixed)})
+    assert hit == ([1, 2] if mixup == CC.PROBLEM_ROW_MIXUP else [0, 1, 2])
+    for q, (pr, w) in enumerate(zip(BC.with_cameras(problems, mixed), _camera_reference())):
+        if q not in hit:
+            assert pr["views"].tobytes() == problems[q]["views"].tobytes()
+            continue
+        got = BC.solve(pr, BC.CAMERA_PARAMS)
+        assert got[0].tobytes() != w[0].tobytes() and got[4].tobytes() != w[4].tobytes(), (mixup, q)
+        assert got[0][:pr["n_free"]].tobytes() != w[0][:pr["n_free"]].tobytes() and got[1].tobytes() != w[1].tobytes(), (mixup, q)
+
+
+@pytest.mark.parametrize("name", BC.PYRAMID_NAMES)
+def test_other_pyramid_tables(name):
+    """octaves and noise drawn against a table of 1, 4 and 16 levels: the result depends on the table, an octave of -1 or n_levels is
+    no observation, n_levels - 1 is one"""
+    pr, table = BC.pyramid_problem(name)
+    n_levels = len(table)
+    assert n_levels == PC.PYRAMIDS[name][1] != len(PC.scale()) and len(pr["edited"]) == 9
+    want = BC.solve(pr, BC.PYRAMID_PARAMS, scale=table)
+    _same(name, _host(pr, BC.PYRAMID_PARAMS, scale=table), want)
+    other = BC.solve(pr, BC.PYRAMID_PARAMS)
+    _same(name + " under the default table", _host(pr, BC.PYRAMID_PARAMS), other)
+    assert other[0].tobytes() != want[0].tobytes() and other[4].tobytes() != want[4].tobytes()
+    outside = [(k, i) for k, i, octave in pr["edited"] if octave in (-1, n_levels)]
+    last = [(k, i) for k, i, octave in pr["edited"] if octave == n_levels - 1]
+    assert len(outside) == 6 and len(last) == 3 and all(pr["idx"][k, i] >= 0 for k, i in outside + last)
+    assert all(want[3][k, i] == 2 for k, i in outside) and all(want[3][k, i] != 2 for k, i in last)
+    assert want[4]["state"] == 0 and want[4]["n_obs"] == (pr["idx"] >= 0).sum() - len(outside) == (want[3] != 2).sum()
+    seen = set(np.concatenate([pr["kp"]["octave"][k][pr["idx"][k][want[3][k] != 2]] for k in range(len(pr["views"]))]).tolist())
+    assert seen == set(range(n_levels))  # under one level every observation has octave 0
+
+
+def test_row_counts_and_junk_idx():
+    """n_kp = (100, 91, 0, 64, 100) over 100 rows: an idx entry at or past n_kp[k], or below -1, is no observation, whatever lies in
+    the keypoint row it names"""
+    pr = BC.row_count_problem()
+    rows = pr["kp"].shape[1]
+    assert rows == 100 and pr["n_kp"].tolist() == list(BC.ROW_COUNTS) and pr["n_free"] == 2
+    want = BC.solve(pr, BC.ROW_COUNT_PARAMS)
+    _same("row counts", _host(pr, BC.ROW_COUNT_PARAMS), want)
+    assert want[4]["state"] == 0 and want[4]["steps"][:2].tolist() == [2, 1] and want[4]["accepted"].sum() > 0
+    assert [e for _, _, e in pr["junk"]] == [91, 69, 1 << 30, -7] and [k for k, _, _ in pr["junk"]] == [1, 3, 0, 4]
+    for k, i, e in pr["junk"]:
+        assert want[3][k, i] == 2 and (want[3][:, i] != 2).sum() >= 2 and want[2][i] != 2, (k, i, e)
+    cut = (pr["idx"] >= pr["n_kp"][:, None]) & (pr["idx"] < rows)
+    assert cut[1].sum() > 2 and cut[3].sum() > 10 and cut[2].sum() > 30 and not cut[0].any() and not cut[4].any()  # live-looking entries past the counts
+    assert (want[3][cut] == 2).all() and (want[3][2] == 2).all() and want[4]["n_obs"] == ((pr["idx"] >= 0) & (pr["idx"] < pr["n_kp"][:, None])).sum()
+    clean = BC.solve(BC.without_junk(pr), BC.ROW_COUNT_PARAMS)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(clean[:5], want[:5]))
+    whole = BC.solve(dict(pr, n_kp=np.full(5, rows, np.int32), idx=np.where(pr["idx"] >= rows, -1, pr["idx"])), BC.ROW_COUNT_PARAMS)
+    assert whole[4]["n_obs"] > want[4]["n_obs"] + 40 and whole[0].tobytes() != want[0].tobytes()
+    # counts past the rows and below 0 clamp to the rows and to 0
+    told = dict(pr, n_kp=np.array([rows + 9, 91, -3, 64, 100], np.int32))
+    _same("counts told wrong", _host(told, BC.ROW_COUNT_PARAMS), want)
+    _same("counts told wrong, reference", BC.solve(told, BC.ROW_COUNT_PARAMS), want)
+
+
+def test_a_free_keyframe_without_observations():
+    """keyframe 0 is free and nobody's observation: its block of the reduced system is lambda on the diagonal and nothing else.  Under
+    the default lambda the run goes on (its step is 0); under lambda 0 the first pivot is not > 0: state 2, every byte finite.  The
+    keyframe's pose is its orthonormalised start in both"""
+    pr = BC.unobserved_free_problem()
+    assert (pr["idx"][0] == -1).all() and pr["n_free"] == 2 and (pr["idx"][1:] >= 0).sum() > 100
+    start = np.array(sum((list(v) for v in PR.start_pose(pr["start"][0])[:2]), []))
+    for p, state, steps in zip(BC.UNOBSERVED_PARAMS, (0, 2), ([2, 1, 0, 0], [0, 0, 0, 0])):
+        want = BC.solve(pr, p)
+        _same(f"lambda {p['lambda_']}", _host(pr, p), want)
+        assert want[4]["state"] == state and want[4]["steps"].tolist() == steps and (want[3][0] == 2).all()
+        assert np.isfinite(want[0]).all() and np.isfinite(want[1]).all() and all(np.isfinite(want[4][n]) for n in ("lambda_", "cost_before", "cost_after"))
+        assert want[0][0].tobytes() == start.tobytes()
+    moved = BC.solve(pr, BC.UNOBSERVED_PARAMS[0])
+    assert moved[0][1].tobytes() != np.array(sum((list(v) for v in PR.start_pose(pr["start"][1])[:2]), [])).tobytes()  # the other free keyframe moves
 
 
 # ---- refused arguments ------------------------------------------------------------------------------------------------------------------

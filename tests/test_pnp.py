@@ -347,6 +347,106 @@ def test_other_pyramid_tables(name):
     assert 6 <= want[0]["n_corr"] < 50 and want[0]["state"] == 0
 
 
+# ---- a camera per problem, strides that differ, counts told wrong, a small call after a large one ------------------------------------------
+def _run_into(ctx, dev, out, n, point_rows, rows, params, skip=False, kp_src=None, point_src=None):
+    """_run into outputs of the caller's, which may be longer than the call's"""
+    from send_slam_amd import binding
+    ctx.pnp_pairs_device(dev["points"].data_ptr(), dev["np"].data_ptr(), n, point_rows, dev["kp"].data_ptr(), dev["nk"].data_ptr(), n, rows,
+                         dev["idx"].data_ptr(), n, dev["views"], _params(binding, params), out.inlier.data_ptr(), out.result.data_ptr(),
+                         kp_src=kp_src, point_src=point_src, d_point_skip=dev["skip"].data_ptr() if skip else 0)
+    ctx.synchronize()
+    return out.host()
+
+
+def _twin_of_told(sc, params, problem):
+    """_twin under counts that may lie past the rows or below 0: the rule clamps them"""
+    res, flags = NC.host(NC.cut(sc), params, problem)
+    full = np.zeros(len(sc["kp"]), np.uint8)
+    full[:len(flags)] = flags
+    return res, full
+
+
+def test_a_camera_per_problem(ctx):
+    """three problems under the cameras P, Q and the square one, each with its own pose, against the restatement: views[0] for
+    views[b] in any of the three kernels that read a view loses problems 1 and 2.  Then the same problems with their keypoint frames
+    and point blocks uploaded in another order, views still by problem: views[kp_src[b]] or views[point_src[b]] for views[b] would
+    change the bytes"""
+    scenes = NC.camera_scenes()
+    p = NC.CAMERA_PARAMS
+    dev = _upload(scenes, 80, 64)
+    got = _run(ctx, dev, 3, 80, 64, p)
+    for b, sc in enumerate(scenes):
+        want = _restatement(sc, p, b)
+        _check(f"camera scene {b}", got, b, want)
+        assert want[0]["state"] == 0 and want[0]["n_inliers"] == NC.CAMERA_INLIERS and want[0]["iteration"] == NC.CAMERA_WINNERS[b]
+    kp_src, point_src = [2, 0, 1], [1, 2, 0]
+    frames, blocks = [scenes[kp_src.index(f)] for f in range(3)], [scenes[point_src.index(f)] for f in range(3)]
+    moved = _upload(frames, 80, 64)  # kp and nk by frame
+    by_block = _upload(blocks, 80, 64)
+    moved["points"], moved["np"] = by_block["points"], by_block["np"]
+    moved["idx"], moved["views"] = dev["idx"], dev["views"]  # by problem
+    again = _run(ctx, moved, 3, 80, 64, p, kp_src=kp_src, point_src=point_src)
+    assert again[0].tobytes() == got[0].tobytes() and again[1].tobytes() == got[1].tobytes()
+
+
+@pytest.mark.parametrize("layout", list(NC.STRIDE_LAYOUTS))
+def test_point_rows_and_keypoint_rows_differ(ctx, layout):
+    """point_rows != rows_per_frame, with and without the skip array: a stride of points, p_skip, idx, kp, corr_of_row or inlier taken
+    from the wrong one of the two reads another scene's rows or the rows past the counts, which look live.  The flags past n_kp are
+    0, and the bytes of d_inlier behind the call's problems stay as they were"""
+    scenes, point_rows, rows = NC.stride_scenes(layout)
+    dev = _upload(scenes, point_rows, rows)
+    for skip in (True, False):
+        out = Out(len(scenes) + 1, rows)
+        got = _run_into(ctx, dev, out, len(scenes), point_rows, rows, NC.STRIDE_PARAMS, skip)
+        for b, sc in enumerate(scenes):
+            want = _twin(sc if skip else dict(sc, skip=None), NC.STRIDE_PARAMS, b)
+            _check(f"{layout}, skip {skip}, problem {b}", got, b, want)
+            assert not got[0][b][sc["n_kp"]:].any() and want[0]["n_corr"] == (35 if skip else 40) and want[0]["state"] == 0
+        assert (got[0][len(scenes)] == 0x5A).all() and (got[1].view(np.uint8).reshape(len(scenes) + 1, -1)[len(scenes)] == 0x5A).all()
+
+
+def test_counts_told_wrong(ctx):
+    """n_kp and n_points past their rows and below 0: the device clamps them as the rule does, and a count past the rows gives the
+    bytes of the rows"""
+    named = NC.count_scenes()
+    scenes = [sc for _, sc in named]
+    dev = _upload(scenes, NC.COUNT_POINT_ROWS, NC.COUNT_ROWS)
+    assert dev["nk"].cpu().numpy().tolist() == [NC.COUNT_ROWS + 9, -3, NC.COUNT_ROWS, NC.COUNT_ROWS]
+    assert dev["np"].cpu().numpy().tolist() == [NC.COUNT_POINT_ROWS, NC.COUNT_POINT_ROWS, NC.COUNT_POINT_ROWS + 5, -2]
+    got = _run(ctx, dev, len(scenes), NC.COUNT_POINT_ROWS, NC.COUNT_ROWS, NC.COUNT_PARAMS)
+    for b, (name, sc) in enumerate(named):
+        want = _twin_of_told(sc, NC.COUNT_PARAMS, b)
+        _check(name, got, b, want)
+        assert (want[0]["state"], want[0]["n_corr"]) == ((0, 44) if "+" in name else (1, 0))
+    plain = dict(scenes[0], n_kp=NC.COUNT_ROWS, n_points=NC.COUNT_POINT_ROWS)
+    exact = _run(ctx, _upload([plain] * 4, NC.COUNT_POINT_ROWS, NC.COUNT_ROWS), 4, NC.COUNT_POINT_ROWS, NC.COUNT_ROWS, NC.COUNT_PARAMS)
+    for b in (0, 2):
+        assert got[0][b].tobytes() == exact[0][b].tobytes() and got[1][b].tobytes() == exact[1][b].tobytes()
+
+
+def test_a_small_call_after_a_large_one():
+    """3 problems of 300 rows and 1024 hypotheses, 1 problem of 64 rows and 8 hypotheses, the first again, on one context: each gives
+    the bytes of a context that has run nothing else, so nothing of a call's workspace outlives it"""
+    from send_slam_amd import binding
+    large = [NC.make_scene(340 + b, 200, 80, 300, 300, noise=0.5) for b in range(3)]
+    small = [NC.case_scene(0)]
+    calls = [(large, 300, dict(NC.RECOVERY, max_iterations=1024, seed=6)), (small, 64, dict(NC.CASES[0]["params"], max_iterations=8)),
+             (large, 300, dict(NC.RECOVERY, max_iterations=1024, seed=6))]
+    devs = [_upload(scenes, rows, rows) for scenes, rows, _ in calls]
+    fresh = []
+    for (scenes, rows, p), dev in zip(calls[:2], devs):
+        with binding.OrbContext(0, n_features=G.NF) as c:
+            fresh.append(_run(c, dev, len(scenes), rows, rows, p))
+    fresh.append(fresh[0])
+    _check("fresh context, 64 rows", fresh[1], 0, _twin(small[0], calls[1][2], 0))
+    assert all(r["state"] == 0 and r["n_inliers"] == 120 for r in fresh[0][1]) and fresh[1][1][0]["n_corr"] == 60  # the large call is live
+    with binding.OrbContext(0, n_features=G.NF) as c:
+        for k, ((scenes, rows, p), dev) in enumerate(zip(calls, devs)):
+            got = _run(c, dev, len(scenes), rows, rows, p)
+            assert got[0].tobytes() == fresh[k][0].tobytes() and got[1].tobytes() == fresh[k][1].tobytes(), f"call {k} on the used context"
+
+
 # ---- the batch form and the one-problem host form ---------------------------------------------------------------------------------------
 BATCH = ["synth_t0", "synth_t1"]
 

@@ -4,12 +4,14 @@ the linear model against two independent derivations (numpy.linalg.eigh and svd;
 the states and the selection on the shared cases, the recovery of planted inliers, refused arguments, and the stand-alone sanitizer
 run of the steps."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import camera_cases as CC
 import pnp_cases as NC
 import pnp_ref as N
 import proj_cases as PC
@@ -368,6 +370,104 @@ def test_recovery_of_the_planted_inliers(seed):
         want = NC.solve_scene(sc, p)
         _same_result(res, want[0], "recovery on the restatement")
         assert np.array_equal(flags, want[1]) and int(want[1][planted].sum()) >= 0.9 * len(planted)
+
+
+# ---- a camera per problem, strides that differ, counts told wrong ----------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _camera_reference(b: int):
+    """scene b of NC.camera_scenes() as problem b on the restatement"""
+    return NC.solve_scene(NC.camera_scenes()[b], NC.CAMERA_PARAMS, b)
+
+
+def test_camera_scenes_reach_their_poses_and_the_twin_equals_the_restatement():
+    """problems 0, 1 and 2 of one call under the cameras P, Q and the square one, each with a pose of its own: state 0 with the 36
+    planted inliers, the rotation within 5e-3 of the planted one"""
+    cams = [tuple(float(sc["view"][n]) for n in ("fx", "fy", "cx", "cy")) for sc in NC.camera_scenes()]
+    assert cams == [CC.intrinsics(c) for c in (CC.P, CC.Q, CC.SIM3_SQUARE)] and len(set(cams)) == 3
+    for b, sc in enumerate(NC.camera_scenes()):
+        res, flags, _ = _camera_reference(b)
+        assert (res["state"], res["n_inliers"], res["iteration"]) == (0, NC.CAMERA_INLIERS, NC.CAMERA_WINNERS[b]), res
+        assert len(sc["inlier_rows"]) == NC.CAMERA_INLIERS and set(np.flatnonzero(flags).tolist()) == set(sc["inlier_rows"].tolist())
+        assert np.abs(res["rcw"].reshape(3, 3) - NC.CAMERA_POSES[b][0]).max() < 5e-3
+        got = NC.host(sc, NC.CAMERA_PARAMS, b)
+        _same_result(got[0], res, f"camera scene {b}")
+        assert np.array_equal(got[1], flags)
+
+
+@pytest.mark.parametrize("mixup", list(CC.FRAME_MIXUPS))
+def test_camera_mixups_change_the_reference(mixup):
+    """solved under the cameras a confused kernel would use, exactly the problems whose fx, fy, cx or cy the mix-up changes have other
+    result bytes (and lose the pose: state 2, no inlier); bf, which the rule does not read, changes nothing"""
+    cams = list(CC.SIM3_FRAME_CAMERAS)
+    mixed = CC.FRAME_MIXUPS[mixup](cams)
+    hit = CC.changed(cams, mixed, fields=(0, 1, 2, 3))
+    assert hit == {"fx and fy exchanged": [0, 1], "cx and cy exchanged": [0, 1, 2], "every frame with frame 0's camera": [1, 2],
+                   "every frame with its neighbour's camera": [0, 1, 2], "bf of another frame": []}[mixup]
+    for b, (sc, wrong) in enumerate(zip(NC.camera_scenes(), NC.camera_scenes(tuple(mixed)))):
+        res, flags, _ = _camera_reference(b)
+        if b not in hit:  # the same view bytes: the same problem
+            assert wrong["view"].tobytes() == sc["view"].tobytes()
+            continue
+        got = NC.solve_scene(wrong, NC.CAMERA_PARAMS, b)
+        assert got[0].tobytes() != res.tobytes() and not np.array_equal(got[1], flags), (mixup, b)
+        assert got[0]["state"] == 2 and got[0]["n_inliers"] == 0 and got[0]["best_inliers"] < NC.CAMERA_INLIERS, (mixup, b, got[0])
+
+
+def test_one_stage_alone_under_another_problems_camera():
+    """what views[0] for views[b] in the counting or the finishing pass alone would give: the model of problem 1's winning six under
+    its own camera Q, every correspondence checked under P.  The restatement has one view for all its steps, so this goes through
+    the twins of the steps; the device test compares best_inliers, n_inliers and the flags"""
+    b = 1
+    sc, p = NC.camera_scenes()[b], NC.CAMERA_PARAMS
+    res, flags, counts = _camera_reference(b)
+    c = NC.corr_of(sc, p["chi2"])
+    params, scale = binding.pnp_params(**p), np.asarray(PC.scale(), f32)
+    pick = N.draw(p["seed"], b, int(res["iteration"]), len(c["rows"]))
+    m = binding.pnp_model_host(params, sc["view"], c["X"][pick], np.stack([c["u"][pick], c["v"][pick]], 1), c["s"][pick], c["cols"][pick])
+    assert m["rcw"].tobytes() == res["rcw"].tobytes() and m["tcw"].tobytes() == res["tcw"].tobytes()
+    own, _ = binding.pnp_check_host(params, sc["view"], scale, sc["points"][c["cols"]], sc["kp"][c["rows"]], m)
+    assert int((own == 0).sum()) == NC.CAMERA_INLIERS == counts[res["iteration"]] and np.array_equal(c["rows"][own == 0], np.flatnonzero(flags))
+    other, _ = binding.pnp_check_host(params, NC.camera_scenes()[0]["view"], scale, sc["points"][c["cols"]], sc["kp"][c["rows"]], m)
+    assert int((other == 0).sum()) != NC.CAMERA_INLIERS and not np.array_equal(other == 0, own == 0)
+
+
+@pytest.mark.parametrize("layout", list(NC.STRIDE_LAYOUTS))
+def test_stride_scenes_on_the_twin_and_the_restatement(layout):
+    """point_rows != rows_per_frame, counts below both: the 40 correspondences under the counts are the problem, the rows that look
+    live past them and the five skipped points are not"""
+    scenes, point_rows, rows = NC.stride_scenes(layout)
+    assert point_rows != rows
+    for b, sc in enumerate(scenes):
+        assert len(sc["points"]) == point_rows == len(sc["skip"]) and len(sc["kp"]) == rows == len(sc["idx"])
+        assert max(sc["n_points"], sc["n_kp"]) < min(point_rows, rows)
+        past = sc["idx"][sc["n_kp"]:]
+        assert ((past >= 0) & (past < sc["n_points"])).any() and (sc["idx"][:sc["n_kp"]] >= sc["n_points"]).sum() == 3
+        want = NC.solve_scene(NC.cut(sc), NC.STRIDE_PARAMS, b)
+        got = NC.host(NC.cut(sc), NC.STRIDE_PARAMS, b)
+        _same_result(got[0], want[0], f"{layout}, scene {b}")
+        assert np.array_equal(got[1], want[1]) and want[0]["n_corr"] == 35 and want[0]["state"] == 0 and want[0]["n_inliers"] >= 25
+        open_ = NC.host(NC.cut(dict(sc, skip=None)), NC.STRIDE_PARAMS, b)
+        assert open_[0]["n_corr"] == 40 and open_[0].tobytes() != got[0].tobytes()
+        whole = NC.host(dict(sc, skip=None, n_kp=rows, n_points=point_rows), NC.STRIDE_PARAMS, b)  # the rows past the counts are live-looking
+        assert whole[0]["n_corr"] > 43
+
+
+def test_count_scenes_on_the_twin_and_the_restatement():
+    """a count past the rows reads every row, a negative one none (state 1, n_corr 0)"""
+    full = None
+    for name, sc in NC.count_scenes():
+        assert len(sc["kp"]) == NC.COUNT_ROWS and len(sc["points"]) == NC.COUNT_POINT_ROWS
+        want = NC.solve_scene(NC.cut(sc), NC.COUNT_PARAMS)
+        got = NC.host(NC.cut(sc), NC.COUNT_PARAMS)
+        _same_result(got[0], want[0], name)
+        assert np.array_equal(got[1], want[1])
+        if "+" in name:
+            assert len(NC.cut(sc)["kp"]) == NC.COUNT_ROWS and len(NC.cut(sc)["points"]) == NC.COUNT_POINT_ROWS
+            assert want[0]["state"] == 0 and want[0]["n_corr"] == 44 and want[0]["n_inliers"] == 36
+            full = want[0].tobytes() if full is None else full
+            assert want[0].tobytes() == full
+        else:
+            assert (want[0]["state"], want[0]["n_corr"], want[0]["iteration"]) == (1, 0, -1) and not want[1].any()
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------------------

@@ -1641,6 +1641,124 @@ int ss_pnp_batch_device(ss_ctx *ctx, const void *d_points, const void *d_point_s
 int ss_pnp(ss_ctx *ctx, const ss_proj_view *view, const ss_map_point *points, const uint8_t *point_skip, int n_points,
            const ss_keypoint *kp, int n_kp, const int32_t *idx, const ss_pnp_params *p, uint8_t *inlier, ss_pnp_result *result);
 
+/* ---- Essential-graph optimisation: Optimizer::OptimizeEssentialGraph (g2o VertexSim3Expmap and EdgeSim3 under Levenberg-Marquardt)
+ * as LoopClosing::CorrectLoop calls it once a loop is accepted, for several loops (problems) of a call at once, and the map-point
+ * correction that follows it there.  tests/graph_ref.py is its normative statement; DESIGN.md section 28.  An addition to ABI 5:
+ * nothing existing changes.  The g2o and ORB-SLAM3 sources are not in the reference tree: parity with the real binary is unpinned,
+ * as for the Sim3 refinement and the local bundle adjustment ----------------------------------------------------------------------
+ * - All arithmetic is double.  Every step is one IEEE operation, left to right as written, with no contraction.  Division and sqrt
+ *   are the only library operations: atan2 and ln are series of csrc/ss_graph_steps.h, the same text on host and device.
+ * - Every sum has one fixed order, so ss_pose_graph_host and the kernels agree bit for bit, for any number of problems in a call.
+ * A Sim3 S = (R, t, s) maps x to s.R.x + t and is thirteen doubles: R row-major, t, s.  Product A.B = (RA.RB, sA.(RA.tB) + tA,
+ * sA.sB), entries (a*b + c*d) + e*f; inverse (R^T, -((1/s).(R^T.t)), 1/s).
+ * A call has n_kf keyframes, each with a NON-CORRECTED Sim3 N_v, a START Sim3 S_v and a `fixed` byte, a HOST table of edges (i, j),
+ * keyframe numbers of the call, and a HOST table of problems.  Problem q owns the keyframes first_kf .. first_kf + n_kf - 1 and the
+ * edges first_edge .. first_edge + n_edges - 1, whose endpoints are keyframes of the problem, i != j; a pair listed twice is two
+ * edges.  Neither range overlaps another problem's.  Upstream's vertex and edge sets (spanning tree, loop edges, covisibility >=
+ * 100, the new loop connections) are the caller's to choose.  WHICH KEYFRAMES TO FIX: every measurement is formed from the
+ * non-corrected Sim3s (step 1), so the measurements alone are a consistent graph whose zero-cost states are S_v = N_v . D for one
+ * common D.  A loop correction therefore enters through the fixed keyframes: fix the loop keyframe at its non-corrected pose AND the
+ * current keyframe (or its corrected group) at the corrected Sim3s; the edges spread the disagreement over the free keyframes in
+ * between.  With the loop keyframe alone fixed at N_m (upstream's choice, which works there because it measures the loop
+ * connections from the corrected Sim3s) the optimum is the non-corrected map and the points do not move.
+ * 1. Start.  A problem whose N_v or S_v has an entry that is not finite, or s not > 0: state 2.  No free keyframe or no edge: state
+ *    1.  The state starts as the S_v as they stand (no orthonormalisation).  M_e = N_j . N_i^-1, formed once.
+ * 2. Error of an edge: E = (M_e . S_i) . S_j^-1, e = (omega, upsilon, sigma).  v = (E21 - E12, E02 - E20, E10 - E01) / 2 (each
+ *    0.5 * difference), c = 0.5 * (((E00 + E11) + E22) - 1.0), n = sqrt((v0*v0 + v1*v1) + v2*v2), theta = atan2(n, c).  omega =
+ *    v * (theta / n); if n < 2^-26: omega = v; if c < 0 and n < 2^-20 (next to pi, where v vanishes): with B = (E + E^T) / 2
+ *    entry by entry, d = 1.0 - c and k the largest diagonal entry of E (the first among equals), a_k = sqrt((E_kk - c) / d), a_j =
+ *    B_kj / (d * a_k), negated when (a0*v0 + a1*v1) + a2*v2 < 0; omega = a * theta: defined, with no NaN, at theta = pi.  upsilon =
+ *    t_E AS IT STANDS, without g2o's W^-1: the counterpart of the retraction below; second order in the error, zero at a consistent
+ *    graph.  sigma = ln(s_E).  The information matrix is the identity, as upstream sets it.
+ * 3. Retraction by delta = (omega, upsilon, sigma), the Sim3 refinement's: dR of ss_pose_exp, ds its scale series; R <- dR.R, t <-
+ *    ds * (dR.t) + upsilon, s <- ds * s.  Refused (state 4, nothing moves): q > pi*pi or |delta_6| > 1.  fix_scale (upstream's
+ *    bFixScale for stereo) holds delta_6 = 0 and s as it is.
+ * 4. Jacobians are g2o's own for EdgeSim3, which defines none: central differences through the retraction, column a of endpoint
+ *    `side` = (e(+h) - e(-h)) / 2h with h = 1e-9 (2h the double next to 2e-9).  Columns of a fixed endpoint, and the scale column
+ *    under fix_scale, are +0.0.
+ * 5. Per free keyframe v: H_vv = sum J^T.J and g_v = sum J^T.e over its incident (edge, side) pairs in ascending edge number from
+ *    +0.0, each entry a seven-term dot product added left to right.  d_a = lambda * (1.0 + H_aa); the preconditioner is the Cholesky
+ *    factor (ss_gn_chol_n) of H_vv with H_aa + d_a on its diagonal, order 7 (6 under fix_scale).  A pivot not > 0: state 2.
+ * 6. The step solves (H + diag d) delta = -g by preconditioned conjugate gradients, matrix-free: u_e = J_ei.p_i + J_ej.p_j (fourteen
+ *    products left to right), q_v = sum J_side^T.u_e in the order of 5, then + d_a * p_a.  x = 0, r = -g, z = M^-1.r, p = z, rho =
+ *    r.z, stop = (pcg_tol * pcg_tol) * rho.  Each iteration: q = A.p; pq = p.q; if not pq > 0 the solve ends and keeps x; alpha =
+ *    rho / pq; x += alpha * p; r -= alpha * q; z = M^-1.r; rho' = r.z; the solve ends after pcg_iterations iterations or once
+ *    rho' <= stop; else beta = rho' / rho, p = z + beta * p.  Every dot product is the tree of the pose-only optimisation over the
+ *    7 * n_kf entries in keyframe-major order (slot k mod 256), entries of fixed keyframes and of the held scale being +0.0.
+ * 7. Accept or reject, as in the local bundle adjustment: the cost is the tree sum over the edges (slot e mod 256) of e^T.e (seven
+ *    squares added left to right).  A step is accepted iff every trial entry is finite and the trial cost is finite and <= the
+ *    cost before; then lambda <- max(lambda / lambda_factor, lambda_min), else nothing moves and lambda <- lambda * lambda_factor.
+ *    `iterations` steps are taken.  A start cost that is not finite: state 2.
+ * Outputs.  Per problem an ss_graph_result, 48 bytes.  Per keyframe of the call thirteen doubles, the Sim3, and twelve doubles, R
+ * and t / s (upstream's SetPose), which feed ss_proj_view_init unchanged.  A fixed keyframe, a keyframe of no problem and every
+ * keyframe of a problem that ends in state 1, 2 or 4 before its first accepted step return their start bit for bit.
+ * Deviations from upstream: upsilon without W^-1; g2o's Levenberg-Marquardt scales lambda by its gain ratio and seeds it from the
+ * diagonal, here it is multiplied or divided by lambda_factor from the given start; the linear solve is block-Jacobi PCG to a loose
+ * tolerance (a sparse Cholesky there); the exponentials, atan2 and ln by series; the order of every sum is fixed; every edge is
+ * measured from the non-corrected Sim3s (upstream measures the loop connections from the corrected ones), so the corrected
+ * keyframes are fixed where upstream fixes the loop keyframe alone. */
+#define SS_GRAPH_MAX_KF 16384     /* keyframes of a problem */
+#define SS_GRAPH_MAX_EDGES 131072 /* edges of a problem */
+typedef struct {            /* 16 bytes, one per problem (a HOST table) */
+    int32_t first_kf, n_kf, first_edge, n_edges;
+} ss_graph_problem;
+typedef struct {            /* 48 bytes */
+    double lambda;          /* the first step's; finite and >= 0; upstream: 1e-16.  0 is plain Gauss-Newton: the block of a free
+                             * keyframe without an edge is then all zero and its pivot ends the problem in state 2 (step 5); with
+                             * any lambda > 0 that keyframe stays where it is */
+    double lambda_factor;   /* finite and > 1; default 10 */
+    double lambda_min;      /* finite and >= 0; default 0 */
+    double pcg_tol;         /* finite and >= 0; default 1e-2 */
+    int32_t iterations;     /* 1 .. 64; upstream: 20 */
+    int32_t pcg_iterations; /* 1 .. 4096; default 128 */
+    int32_t fix_scale;      /* non-zero: delta_6 = 0, blocks of order 6 */
+    int32_t reserved;       /* must be 0 */
+} ss_graph_params;
+typedef struct {            /* 48 bytes, one per problem */
+    double lambda;          /* after the last step */
+    double cost_before, cost_after;
+    int32_t state;          /* 0 ok, 1 nothing to optimise, 2 not finite or a pivot not > 0, 4 step too large */
+    int32_t n_edges, n_free;
+    int32_t steps, accepted; /* steps taken, rejected ones included; steps accepted */
+    int32_t pcg_iterations; /* of all steps */
+} ss_graph_result;
+/* The whole rule on the host from the text the kernels compile (csrc/ss_graph_steps.h), one problem; needs no device.  nc, start:
+ * n_kf x 13 doubles; fixed: n_kf bytes; edges: n_edges pairs; sim3 n_kf x 13 and poses n_kf x 12 doubles out.  Arguments are checked
+ * as the device calls check them (SS_ERR_INVALID_ARG). */
+int ss_pose_graph_host(const double *nc, const double *start, const uint8_t *fixed, int n_kf, const int32_t *edges, int n_edges,
+                       const ss_graph_params *p, double *sim3, double *poses, ss_graph_result *result);
+/* One edge on the host: its error e (7) under (N_i, N_j, S_i, S_j) and both Jacobian blocks, J [14][7]: column c of endpoint i at
+ * J + 7c, of endpoint j at J + 7(7 + c); fixed_i / fixed_j and fix_scale zero columns as step 4 says. */
+int ss_pose_graph_edge_host(const double *nc_i, const double *nc_j, const double *s_i, const double *s_j, int fixed_i, int fixed_j,
+                            int fix_scale, double *e, double *J);
+/* The two series on the host, n values each: out[k] = atan2(y[k], x[k]) for finite y >= 0 and finite x, ln(x[k]) for finite x > 0;
+ * NaN outside. */
+int ss_graph_atan2_host(const double *y, const double *x, int n, double *out);
+int ss_graph_ln_host(const double *x, int n, double *out);
+/* n_problems problems on device arrays: d_nc and d_start double [n_kf][13], d_fixed uint8 [n_kf]; problems (n_problems) and edges
+ * (int32 [n_edges][2]) are HOST tables, copied (with the incidence lists the host builds from them) before the call returns.
+ * Outputs: d_sim3 double [n_kf][13], d_poses double [n_kf][12], d_result [n_problems] ss_graph_result; every byte is written.
+ * SS_ERR_INVALID_ARG, with a message: an endpoint outside its problem, i == j, n_kf outside 1 .. SS_GRAPH_MAX_KF or n_edges outside
+ * 0 .. SS_GRAPH_MAX_EDGES, a keyframe or edge range outside the call or overlapping another problem's, a parameter out of its
+ * range, a reserved field that is not 0, a NULL buffer.  Without a keyframe the call returns SS_OK and writes nothing.  The fixed
+ * schedule of every step is enqueued at once; a problem that has ended costs empty launches.  The workspace is dominated by the
+ * edges' Jacobians, 784 bytes each.  Asynchronous on the context's stream. */
+int ss_pose_graph_device(ss_ctx *ctx, const void *d_nc, const void *d_start, const void *d_fixed, int n_kf,
+                         const ss_graph_problem *problems, int n_problems, const int32_t *edges, int n_edges, const ss_graph_params *p,
+                         void *d_sim3, void *d_poses, void *d_result);
+/* One problem with host pointers in and out (copy in, the device form, copy out), synchronous; the arguments of
+ * ss_pose_graph_host. */
+int ss_pose_graph(ss_ctx *ctx, const double *nc, const double *start, const uint8_t *fixed, int n_kf, const int32_t *edges,
+                  int n_edges, const ss_graph_params *p, double *sim3, double *poses, ss_graph_result *result);
+/* The map-point correction of OptimizeEssentialGraph: row i of block b of d_points ([n_blocks][point_rows] ss_map_point) whose
+ * d_ref entry (int32 [n_blocks][point_rows]) names keyframe r of the call, 0 <= r < n_kf, gets x <- S_r^-1(N_r(x)) in double from
+ * its floats widened: y = s_N * ((R_N.x)) + t_N, x' = (1 / s_S) * (R_S^T.(y - t_S)), rounded to the block's floats; the other 20 bytes
+ * of the ss_map_point are left alone (UpdateNormalAndDepth stays with the caller).  Any other r (-1) skips the row.  d_nc and d_sim3
+ * are double [n_kf][13]: the call's input and ss_pose_graph_device's output.  SS_ERR_INVALID_ARG: a bad count, point_rows above
+ * SS_GUIDED_MAX_ROWS, a NULL buffer.  Asynchronous. */
+int ss_pose_graph_points_device(ss_ctx *ctx, void *d_points, const void *d_ref, int n_blocks, int point_rows, const void *d_nc,
+                                const void *d_sim3, int n_kf);
+
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device
  * (hipStream_t; NULL = the legacy default stream): for callers that produce the inputs of a *_device call on their own

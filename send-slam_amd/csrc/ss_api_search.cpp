@@ -15,7 +15,10 @@
 #include <vector>
 
 #include "ss_ctx.h"
+#include <new>
+
 #include "ss_ba_steps.h"
+#include "ss_graph_steps.h"
 #include "ss_epi_steps.h"
 #include "ss_fuse_steps.h"
 #include "ss_pnp_steps.h"
@@ -2326,6 +2329,252 @@ int ss_local_ba_points_to_block(ss_ctx *c, const void *d_xyz, const void *d_poin
     {
         stage_timer t(c, "ba_points_to_block", (int64_t)n_problems * point_rows * (1 + 24 + 12));
         ssk_ba_points_to_block(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+/* ---- essential-graph optimisation (csrc/ss_graph.hip, csrc/ss_graph_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *graph_params_error(const ss_graph_params *p)
+{
+    if (!p) return "pose graph: params is NULL";
+    if (!(p->lambda >= 0.0) || !std::isfinite(p->lambda)) return "pose graph: lambda must be finite and >= 0";
+    if (!(p->lambda_factor > 1.0) || !std::isfinite(p->lambda_factor)) return "pose graph: lambda_factor must be finite and > 1";
+    if (!(p->lambda_min >= 0.0) || !std::isfinite(p->lambda_min)) return "pose graph: lambda_min must be finite and >= 0";
+    if (!(p->pcg_tol >= 0.0) || !std::isfinite(p->pcg_tol)) return "pose graph: pcg_tol must be finite and >= 0";
+    if (p->iterations < 1 || p->iterations > 64) return "pose graph: iterations must be 1 .. 64";
+    if (p->pcg_iterations < 1 || p->pcg_iterations > 4096) return "pose graph: pcg_iterations must be 1 .. 4096";
+    if (p->reserved != 0) return "pose graph: the reserved field must be 0";
+    return nullptr;
+}
+
+/* the message of the rule problem q of a call of n_kf keyframes and n_edges edges breaks (overlaps apart), or empty */
+static std::string graph_problem_error(const ss_graph_problem &b, int q, int n_kf, int n_edges, const int32_t *edges)
+{
+    const std::string head = "pose graph: problem " + std::to_string(q) + ": ";
+    if (b.n_kf < 1 || b.n_kf > SS_GRAPH_MAX_KF)
+        return head + "n_kf " + std::to_string(b.n_kf) + " outside 1 .. SS_GRAPH_MAX_KF (" + std::to_string(SS_GRAPH_MAX_KF) + ")";
+    if (b.n_edges < 0 || b.n_edges > SS_GRAPH_MAX_EDGES)
+        return head + "n_edges " + std::to_string(b.n_edges) + " outside 0 .. SS_GRAPH_MAX_EDGES (" + std::to_string(SS_GRAPH_MAX_EDGES) + ")";
+    if (b.first_kf < 0 || b.first_kf > n_kf - b.n_kf)
+        return head + "keyframes " + std::to_string(b.first_kf) + " .. + " + std::to_string(b.n_kf) + " lie outside the call's " + std::to_string(n_kf);
+    if (b.first_edge < 0 || b.first_edge > n_edges - b.n_edges)
+        return head + "edges " + std::to_string(b.first_edge) + " .. + " + std::to_string(b.n_edges) + " lie outside the call's " + std::to_string(n_edges);
+    for (int e = b.first_edge; e < b.first_edge + b.n_edges; e++) {
+        const int i = edges[2 * (size_t)e], j = edges[2 * (size_t)e + 1];
+        if (i < b.first_kf || i >= b.first_kf + b.n_kf || j < b.first_kf || j >= b.first_kf + b.n_kf)
+            return head + "edge " + std::to_string(e) + " (" + std::to_string(i) + ", " + std::to_string(j) + ") names a keyframe outside the problem";
+        if (i == j) return head + "edge " + std::to_string(e) + " joins keyframe " + std::to_string(i) + " to itself";
+    }
+    return std::string();
+}
+
+int ss_graph_atan2_host(const double *y, const double *x, int n, double *out)
+{
+    if (n < 0 || (n > 0 && (!y || !x || !out))) return SS_ERR_INVALID_ARG;
+    for (int k = 0; k < n; k++) out[k] = ss_graph_atan2(y[k], x[k]);
+    return SS_OK;
+}
+
+int ss_graph_ln_host(const double *x, int n, double *out)
+{
+    if (n < 0 || (n > 0 && (!x || !out))) return SS_ERR_INVALID_ARG;
+    for (int k = 0; k < n; k++) out[k] = ss_graph_ln(x[k]);
+    return SS_OK;
+}
+
+int ss_pose_graph_edge_host(const double *nc_i, const double *nc_j, const double *s_i, const double *s_j, int fixed_i, int fixed_j, int fix_scale, double *e,
+                            double *J)
+{
+    if (!nc_i || !nc_j || !s_i || !s_j || !e || !J) return SS_ERR_INVALID_ARG;
+    double M[SS_GRAPH_SIM3];
+    ss_graph_measure(nc_i, nc_j, M);
+    ss_graph_error(M, s_i, s_j, e);
+    const bool fix = fix_scale != 0;
+    for (int c = 0; c < 14; c++) ss_graph_column(M, s_i, s_j, c / 7, c % 7, fix, (c < 7 ? fixed_i : fixed_j) != 0 || (fix && c % 7 == 6), J + 7 * c);
+    return SS_OK;
+}
+
+int ss_pose_graph_host(const double *nc, const double *start, const uint8_t *fixed, int n_kf, const int32_t *edges, int n_edges, const ss_graph_params *p,
+                       double *sim3, double *poses, ss_graph_result *result)
+{
+    if (graph_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!nc || !start || !fixed || !sim3 || !poses || !result || n_edges < 0 || (n_edges > 0 && !edges)) return SS_ERR_INVALID_ARG;
+    const ss_graph_problem shape = {0, n_kf, 0, n_edges};
+    if (!graph_problem_error(shape, 0, n_kf, n_edges, edges).empty()) return SS_ERR_INVALID_ARG;
+    try {
+        ss_graph_problem_host(n_kf, n_edges, nc, start, fixed, edges, *p, sim3, result);
+    } catch (const std::bad_alloc &) { /* its workspace grows with the caller's counts */
+        return SS_ERR_NO_MEMORY;
+    }
+    for (int v = 0; v < n_kf; v++) ss_graph_pose(sim3 + 13 * (size_t)v, poses + 12 * (size_t)v);
+    return SS_OK;
+}
+
+/* the checks, the tables and the schedule of ss_pose_graph_device; its host tables grow with the caller's counts and may throw */
+static int graph_run(ss_ctx *c, const void *d_nc, const void *d_start, const void *d_fixed, int n_kf, const ss_graph_problem *problems, int n_problems,
+                     const int32_t *edges, int n_edges, const ss_graph_params *p, void *d_sim3, void *d_poses, void *d_result)
+{
+    if (const char *msg = graph_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_kf < 0 || n_problems < 0 || n_edges < 0) return fail(c, SS_ERR_INVALID_ARG, "pose graph: bad keyframe, problem or edge count");
+    const int rc0 = call_count_ok(c, "pose graph", n_problems, "problems");
+    if (rc0 != SS_OK) return rc0;
+    if (n_kf == 0) return SS_OK;
+    if ((n_problems > 0 && !problems) || (n_edges > 0 && !edges)) return fail(c, SS_ERR_INVALID_ARG, "pose graph: problems or edges is NULL");
+    ssk_graph_call g;
+    g.n_kf = n_kf, g.n_problems = n_problems, g.n_edges = n_edges;
+    std::vector<int32_t> kf_prob((size_t)n_kf, -1), edge_prob((size_t)n_edges, -1), off((size_t)n_kf, 0), cnt((size_t)n_kf, 0), inc(2 * (size_t)n_edges + 1);
+    int inc_at = 0;
+    for (int q = 0; q < n_problems; q++) {
+        const ss_graph_problem &b = problems[q];
+        const std::string msg = graph_problem_error(b, q, n_kf, n_edges, edges);
+        if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+        const std::string head = "pose graph: problem " + std::to_string(q) + ": ";
+        for (int k = b.first_kf; k < b.first_kf + b.n_kf; k++) {
+            if (kf_prob[(size_t)k] >= 0)
+                return fail(c, SS_ERR_INVALID_ARG, head + "keyframe " + std::to_string(k) + " belongs to problem " + std::to_string(kf_prob[(size_t)k]) + " already");
+            kf_prob[(size_t)k] = q;
+        }
+        for (int e = b.first_edge; e < b.first_edge + b.n_edges; e++) {
+            if (edge_prob[(size_t)e] >= 0)
+                return fail(c, SS_ERR_INVALID_ARG, head + "edge " + std::to_string(e) + " belongs to problem " + std::to_string(edge_prob[(size_t)e]) + " already");
+            edge_prob[(size_t)e] = q;
+        }
+        /* the problem's incidence lists in the call's numbers: its run of inc starts at inc_at */
+        std::vector<int32_t> local(2 * (size_t)b.n_edges + 1), l_off((size_t)b.n_kf), l_cnt((size_t)b.n_kf), l_inc(2 * (size_t)b.n_edges + 1);
+        for (int e = 0; e < 2 * b.n_edges; e++) local[(size_t)e] = edges[2 * (size_t)b.first_edge + e] - b.first_kf;
+        ss_graph_incidence(b.n_kf, b.n_edges, local.data(), l_off.data(), l_cnt.data(), l_inc.data());
+        for (int k = 0; k < b.n_kf; k++) off[(size_t)(b.first_kf + k)] = inc_at + l_off[(size_t)k], cnt[(size_t)(b.first_kf + k)] = l_cnt[(size_t)k];
+        for (int m = 0; m < 2 * b.n_edges; m++) inc[(size_t)(inc_at + m)] = l_inc[(size_t)m] + 2 * b.first_edge;
+        inc_at += 2 * b.n_edges;
+        g.max_kf = std::max(g.max_kf, (int)b.n_kf), g.max_edges = std::max(g.max_edges, (int)b.n_edges);
+    }
+    if (!d_nc || !d_start || !d_fixed || !d_sim3 || !d_poses || (n_problems > 0 && !d_result)) return fail(c, SS_ERR_INVALID_ARG, "pose graph: NULL buffer");
+    g.nc = (const double *)d_nc, g.start = (const double *)d_start, g.fixed = (const uint8_t *)d_fixed;
+    g.out_sim3 = (double *)d_sim3, g.out_pose = (double *)d_poses, g.result = (ss_graph_result *)d_result;
+    g.p = *p;
+    const size_t K = (size_t)n_kf, E = (size_t)n_edges, nq = (size_t)n_problems;
+    int rc = carve_from(c, c->d_graph_ws, [&](carve &w) {
+        g.S = w.take<double>(2 * K * 13 * sizeof(double));
+        g.M = w.take<double>(E * 13 * sizeof(double));
+        g.err = w.take<double>(E * 7 * sizeof(double));
+        g.J = w.take<double>(E * 98 * sizeof(double));
+        g.u = w.take<double>(E * 7 * sizeof(double));
+        g.L = w.take<double>(K * 49 * sizeof(double));
+        g.dd = w.take<double>(K * 7 * sizeof(double));
+        g.g = w.take<double>(K * 7 * sizeof(double));
+        g.x = w.take<double>(K * 7 * sizeof(double));
+        g.r = w.take<double>(K * 7 * sizeof(double));
+        g.z = w.take<double>(K * 7 * sizeof(double));
+        g.pv = w.take<double>(K * 7 * sizeof(double));
+        g.q = w.take<double>(K * 7 * sizeof(double));
+        g.flag = w.take<uint8_t>(K);
+        g.st = w.take<ssk_graph_state>(nq * sizeof(ssk_graph_state));
+    });
+    if (rc != SS_OK) return rc;
+    /* the host tables of the call: the problems, the edges, the keyframes' problems, the incidence lists */
+    const size_t pb = (nq * sizeof(ss_graph_problem) + 15) & ~(size_t)15, eb = E * 8, kb = K * 4, ib = 2 * E * 4;
+    rc = staged_upload(c, c->graph_tab, pb + eb + 3 * kb + ib + 16, [&](uint8_t *h) {
+        if (nq) memcpy(h, problems, nq * sizeof(ss_graph_problem));
+        if (E) memcpy(h + pb, edges, eb);
+        memcpy(h + pb + eb, kf_prob.data(), kb);
+        memcpy(h + pb + eb + kb, off.data(), kb);
+        memcpy(h + pb + eb + 2 * kb, cnt.data(), kb);
+        if (E) memcpy(h + pb + eb + 3 * kb, inc.data(), ib);
+    });
+    if (rc != SS_OK) return rc;
+    g.prob = c->graph_tab.as<ss_graph_problem>();
+    g.edges = c->graph_tab.as<int32_t>(pb);
+    g.kf_prob = c->graph_tab.as<int32_t>(pb + eb);
+    g.inc_off = c->graph_tab.as<int32_t>(pb + eb + kb);
+    g.inc_cnt = c->graph_tab.as<int32_t>(pb + eb + 2 * kb);
+    g.inc = c->graph_tab.as<int32_t>(pb + eb + 3 * kb);
+    /* the stages' bytes: what a launch reads and writes when every problem runs (an upper bound) */
+    const int64_t iK = (int64_t)K, iE = (int64_t)E, iq = (int64_t)nq;
+    {
+        stage_timer t(c, "graph_gather", iK * (2 * 104 + 2 * 104 + 2) + iE * (8 + 3 * 104) + iq * (int64_t)sizeof(ssk_graph_state));
+        ssk_graph_gather(c->stream, g);
+    }
+    if (n_problems > 0 && g.max_edges > 0) {
+        for (int it = -1; it < p->iterations; it++) {
+            if (it >= 0) {
+                {
+                    stage_timer t(c, "graph_lin", iE * 16 * (8 + 3 * 104) + iE * (56 + 784));
+                    ssk_graph_lin(c->stream, g);
+                }
+                {
+                    stage_timer t(c, "graph_blocks", 2 * iE * (4 + 392 + 56) + iK * (392 + 112 + 1));
+                    ssk_graph_blocks(c->stream, g);
+                }
+                {
+                    stage_timer t(c, "graph_solve", (int64_t)p->pcg_iterations * (iE * (784 + 112 + 56 + 2 * (392 + 56 + 4)) + iK * (392 + 10 * 56)) + iK * (2 * 104 + 56));
+                    ssk_graph_solve(c->stream, g);
+                }
+            }
+            stage_timer t(c, "graph_cost", iE * (8 + 3 * 104) + iq * (int64_t)sizeof(ssk_graph_state));
+            ssk_graph_cost(c->stream, g, it >= 0 ? 0 : 1);
+        }
+    }
+    {
+        stage_timer t(c, "graph_finish", iK * (4 + 104 + 104 + 96) + iq * (int64_t)(sizeof(ssk_graph_state) + sizeof(ss_graph_result)));
+        ssk_graph_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_pose_graph_device(ss_ctx *c, const void *d_nc, const void *d_start, const void *d_fixed, int n_kf, const ss_graph_problem *problems, int n_problems,
+                         const int32_t *edges, int n_edges, const ss_graph_params *p, void *d_sim3, void *d_poses, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    try {
+        return graph_run(c, d_nc, d_start, d_fixed, n_kf, problems, n_problems, edges, n_edges, p, d_sim3, d_poses, d_result);
+    } catch (const std::bad_alloc &) {
+        return fail(c, SS_ERR_NO_MEMORY, "pose graph: no host memory for the tables of the call");
+    }
+}
+
+int ss_pose_graph(ss_ctx *c, const double *nc, const double *start, const uint8_t *fixed, int n_kf, const int32_t *edges, int n_edges, const ss_graph_params *p,
+                  double *sim3, double *poses, ss_graph_result *result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = graph_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (!nc || !start || !fixed || !sim3 || !poses || !result || n_edges < 0 || (n_edges > 0 && !edges)) return fail(c, SS_ERR_INVALID_ARG, "pose graph: NULL buffer");
+    const ss_graph_problem problem = {0, n_kf, 0, n_edges};
+    const std::string msg = graph_problem_error(problem, 0, n_kf, n_edges, edges);
+    if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+    const size_t K = (size_t)n_kf;
+    enum { NC, ST, FX, S3, PO, RES, PIECES };
+    io_piece io[PIECES] = {{nc, nullptr, K * 104, K * 104},      {start, nullptr, K * 104, K * 104}, {fixed, nullptr, K, K},
+                           {nullptr, sim3, K * 104, K * 104},    {nullptr, poses, K * 96, K * 96},   {nullptr, result, sizeof(ss_graph_result), sizeof(ss_graph_result)}};
+    int rc = io_send(c, c->d_graph_io, io, PIECES);
+    if (rc == SS_OK) rc = ss_pose_graph_device(c, io[NC].d, io[ST].d, io[FX].d, n_kf, &problem, 1, edges, n_edges, p, io[S3].d, io[PO].d, io[RES].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
+}
+
+int ss_pose_graph_points_device(ss_ctx *c, void *d_points, const void *d_ref, int n_blocks, int point_rows, const void *d_nc, const void *d_sim3, int n_kf)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (n_blocks < 0 || n_kf < 0 || point_rows < 1 || point_rows > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "pose graph points: bad block, row or keyframe count");
+    const int rc0 = call_count_ok(c, "pose graph points", n_blocks, "blocks");
+    if (rc0 != SS_OK) return rc0;
+    if (n_blocks == 0 || n_kf == 0) return SS_OK;
+    if (!d_points || !d_ref || !d_nc || !d_sim3) return fail(c, SS_ERR_INVALID_ARG, "pose graph points: NULL buffer");
+    ssk_graph_points_call g;
+    g.n_blocks = n_blocks, g.point_rows = point_rows, g.n_kf = n_kf;
+    g.points = (ss_map_point *)d_points, g.ref = (const int32_t *)d_ref, g.nc = (const double *)d_nc, g.sim3 = (const double *)d_sim3;
+    {
+        stage_timer t(c, "graph_points", (int64_t)n_blocks * point_rows * (4 + 24 + 208));
+        ssk_graph_points(c->stream, g);
     }
     HIP_TRY(c, hipGetLastError());
     return SS_OK;

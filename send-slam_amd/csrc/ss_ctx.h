@@ -160,6 +160,10 @@ struct ss_ctx {
      * problems, views, start poses; the block numbers of ss_local_ba_points_to_block) */
     dev_buf<uint8_t> d_ba_ws, d_ba_io;
     staged_table ba_tab, ba_block_tab;
+    /* essential-graph optimisation: the workspace of a call, the host form's device copies, the tables of a call (problems, edges,
+     * the keyframes' problems, the incidence lists) */
+    dev_buf<uint8_t> d_graph_ws, d_graph_io;
+    staged_table graph_tab;
     /* PnP RANSAC: the workspace of a call (correspondences, models, poses, counts), the host form's device copies, the tables of a
      * call (views, then frame numbers, then block numbers) */
     dev_buf<uint8_t> d_pnp_ws, d_pnp_io;

@@ -545,6 +545,53 @@ struct ssk_ba_block_call {
     ss_map_point *points = nullptr;
 };
 void ssk_ba_points_to_block(hipStream_t s, const ssk_ba_block_call &g);
+/* ss_graph.hip: essential-graph optimisation (DESIGN.md "Essential-graph optimisation").  Problem q owns the keyframes
+ * prob[q].first_kf .. and the edges prob[q].first_edge .. of the call; keyframe and edge numbers are the call's everywhere.  Every
+ * kernel of the fixed schedule reads its problem's ssk_graph_state and returns at once when the problem has ended.  The Sim3s are
+ * double-buffered: st.cur names the buffer of the current state, the other one takes the trial state, an accepted step flips cur */
+struct ssk_graph_state {
+    double lambda, cost0, cost_before;
+    int32_t state, ended, cur, n_free, steps, accepted, pcg, trial_finite;
+};
+struct ssk_graph_call {
+    int n_kf = 0, n_problems = 0, n_edges = 0;
+    int max_kf = 0, max_edges = 0;           /* the largest of the call's problems */
+    const double *nc = nullptr;             /* [n_kf][13] */
+    const double *start = nullptr;          /* [n_kf][13] */
+    const uint8_t *fixed = nullptr;         /* [n_kf] */
+    const ss_graph_problem *prob = nullptr; /* device [n_problems] */
+    const int32_t *edges = nullptr;         /* device [n_edges][2] */
+    const int32_t *kf_prob = nullptr;       /* device [n_kf]: the keyframe's problem, or -1 */
+    const int32_t *inc_off = nullptr, *inc_cnt = nullptr; /* device [n_kf]: the keyframe's run of inc */
+    const int32_t *inc = nullptr;           /* device [2 n_edges]: 2 * edge + side, ascending per keyframe */
+    ss_graph_params p = {};
+    /* workspace */
+    double *S = nullptr;       /* [2][n_kf][13] */
+    double *M = nullptr;       /* [n_edges][13] */
+    double *err = nullptr;     /* [n_edges][7] */
+    double *J = nullptr;       /* [n_edges][14][7]: column c of endpoint `side` at 7 (7 side + c) */
+    double *u = nullptr;       /* [n_edges][7] */
+    double *L = nullptr;       /* [n_kf][49]: the factor of a free keyframe's damped block */
+    double *dd = nullptr, *g = nullptr, *x = nullptr, *r = nullptr, *z = nullptr, *pv = nullptr, *q = nullptr; /* [n_kf][7] each */
+    uint8_t *flag = nullptr;   /* [n_kf]: gather: the Sim3s are usable; blocks: every pivot > 0 */
+    ssk_graph_state *st = nullptr; /* [n_problems] */
+    /* outputs */
+    double *out_sim3 = nullptr, *out_pose = nullptr;
+    ss_graph_result *result = nullptr;
+};
+void ssk_graph_gather(hipStream_t s, const ssk_graph_call &g); /* three launches; two without a problem */
+void ssk_graph_lin(hipStream_t s, const ssk_graph_call &g);
+void ssk_graph_blocks(hipStream_t s, const ssk_graph_call &g);
+void ssk_graph_solve(hipStream_t s, const ssk_graph_call &g);
+void ssk_graph_cost(hipStream_t s, const ssk_graph_call &g, int begin);
+void ssk_graph_finish(hipStream_t s, const ssk_graph_call &g);
+struct ssk_graph_points_call {
+    int n_blocks = 0, point_rows = 0, n_kf = 0;
+    ss_map_point *points = nullptr;
+    const int32_t *ref = nullptr;
+    const double *nc = nullptr, *sim3 = nullptr;
+};
+void ssk_graph_points(hipStream_t s, const ssk_graph_points_call &g);
 /* The bookkeeping of SearchBySim3 (the rule: include/sendslam_orb.h).  One workgroup per pair: a base pass over the rows, a barrier,
  * a scatter pass in which every store to one address writes the same value.  marks writes skip1 and skip2; mutual marks the train
  * rows that carry a prior match in taken (workspace, [n_frames][rows]) and writes idx_out and the summary */

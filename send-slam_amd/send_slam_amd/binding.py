@@ -52,7 +52,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_sim3_opt", "ss_sim3_marks_pairs_device", "ss_sim3_mutual_pairs_device", "ss_sim3_marks_batch_device",
            "ss_sim3_mutual_batch_device", "ss_sim3_to_view21", "ss_local_ba_host", "ss_local_ba_pairs_device",
            "ss_local_ba_batch_device", "ss_local_ba", "ss_local_ba_points_to_block", "ss_pnp_host", "ss_pnp_model_host", "ss_pnp_check_host",
-           "ss_pnp_pairs_device", "ss_pnp_batch_device", "ss_pnp"]
+           "ss_pnp_pairs_device", "ss_pnp_batch_device", "ss_pnp", "ss_pose_graph_host", "ss_pose_graph_edge_host", "ss_graph_atan2_host",
+           "ss_graph_ln_host", "ss_pose_graph_device", "ss_pose_graph", "ss_pose_graph_points_device"]
 
 
 class OrbParams(C.Structure):
@@ -646,6 +647,85 @@ def local_ba_host(views, start, n_free: int, scale, points: np.ndarray, kp: np.n
     return poses, xyz, pf, of, res[0]
 
 
+# ---- essential-graph optimisation (the rule: include/sendslam_orb.h) ----
+SS_GRAPH_MAX_KF, SS_GRAPH_MAX_EDGES = 16384, 131072
+
+
+class GraphParams(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("lambda_factor", C.c_double), ("lambda_min", C.c_double), ("pcg_tol", C.c_double),
+                ("iterations", C.c_int32), ("pcg_iterations", C.c_int32), ("fix_scale", C.c_int32), ("reserved", C.c_int32)]
+
+
+# ss_graph_problem: one per problem (a host table); ss_graph_result: one per problem
+GRAPH_PROBLEM_DTYPE = np.dtype([(n, "<i4") for n in ("first_kf", "n_kf", "first_edge", "n_edges")])
+GRAPH_RESULT_DTYPE = np.dtype([("lambda_", "<f8"), ("cost_before", "<f8"), ("cost_after", "<f8")] +
+                              [(n, "<i4") for n in ("state", "n_edges", "n_free", "steps", "accepted", "pcg_iterations")])
+
+
+def graph_params(lambda_: float = 1e-16, lambda_factor: float = 10.0, lambda_min: float = 0.0, pcg_tol: float = 1e-2, iterations: int = 20,
+                 pcg_iterations: int = 128, fix_scale: bool = False, reserved: int = 0) -> GraphParams:
+    """upstream's OptimizeEssentialGraph: 20 Levenberg-Marquardt iterations from lambda 1e-16; fix_scale is its bFixScale (stereo, RGB-D)"""
+    return GraphParams(lambda_=lambda_, lambda_factor=lambda_factor, lambda_min=lambda_min, pcg_tol=pcg_tol, iterations=iterations,
+                       pcg_iterations=pcg_iterations, fix_scale=int(fix_scale), reserved=reserved)
+
+
+def _graph_host_arrays(nc, start, fixed, edges):
+    """the arrays of one problem, checked against each other: nc, start [n_kf][13], fixed [n_kf], edges [n_edges][2]"""
+    nc = np.ascontiguousarray(nc, np.float64).reshape(-1, 13)
+    st = np.ascontiguousarray(start, np.float64).reshape(-1, 13)
+    fx = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    ed = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+    if len(st) != len(nc) or len(fx) != len(nc):
+        raise ValueError("one non-corrected Sim3, one start and one fixed byte per keyframe")
+    return nc, st, fx, ed
+
+
+def pose_graph_host(nc, start, fixed, edges, params: GraphParams):
+    """ss_pose_graph_host: the whole rule on the host for one problem -> (sim3 float64 [n_kf][13], poses float64 [n_kf][12], one
+    GRAPH_RESULT_DTYPE record); needs no device"""
+    nc, st, fx, ed = _graph_host_arrays(nc, start, fixed, edges)
+    n_kf = len(nc)
+    sim3, poses, res = np.empty((n_kf, 13), np.float64), np.empty((n_kf, 12), np.float64), np.zeros(1, GRAPH_RESULT_DTYPE)
+    rc = load().ss_pose_graph_host(nc.ctypes.data, st.ctypes.data, fx.ctypes.data, n_kf, ed.ctypes.data if len(ed) else None, len(ed),
+                                   C.byref(params), sim3.ctypes.data, poses.ctypes.data, res.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_pose_graph_host refused its arguments")
+    return sim3, poses, res[0]
+
+
+def pose_graph_edge_host(nc_i, nc_j, s_i, s_j, fixed_i: bool = False, fixed_j: bool = False, fix_scale: bool = False):
+    """ss_pose_graph_edge_host: one edge -> (e float64 [7], J float64 [14][7]: row c is column c of the 7 x 14 block)"""
+    a = [np.ascontiguousarray(v, np.float64).reshape(13) for v in (nc_i, nc_j, s_i, s_j)]
+    e, J = np.empty(7, np.float64), np.empty((14, 7), np.float64)
+    rc = load().ss_pose_graph_edge_host(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, int(fixed_i), int(fixed_j),
+                                        int(fix_scale), e.ctypes.data, J.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_pose_graph_edge_host refused its arguments")
+    return e, J
+
+
+def graph_atan2_host(y, x) -> np.ndarray:
+    """ss_graph_atan2_host: the library's series for atan2(y, x), y >= 0, elementwise"""
+    y, x = np.ascontiguousarray(y, np.float64).reshape(-1), np.ascontiguousarray(x, np.float64).reshape(-1)
+    if len(y) != len(x):
+        raise ValueError("one x per y")
+    out = np.empty(len(y), np.float64)
+    rc = load().ss_graph_atan2_host(y.ctypes.data, x.ctypes.data, len(y), out.ctypes.data) if len(y) else SS_OK
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_graph_atan2_host refused its arguments")
+    return out
+
+
+def graph_ln_host(x) -> np.ndarray:
+    """ss_graph_ln_host: the library's series for ln(x), x > 0, elementwise"""
+    x = np.ascontiguousarray(x, np.float64).reshape(-1)
+    out = np.empty(len(x), np.float64)
+    rc = load().ss_graph_ln_host(x.ctypes.data, len(x), out.ctypes.data) if len(x) else SS_OK
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_graph_ln_host refused its arguments")
+    return out
+
+
 class EpiPair(C.Structure):
     """ss_epi_pair: a (keyframe 1 = query, keyframe 2 = train) pair; float32 for the search, double for the triangulation"""
     _fields_ = [("f12", C.c_float * 9), ("ex", C.c_float), ("ey", C.c_float), ("epipole_test", C.c_int32)] + \
@@ -930,6 +1010,14 @@ def load():
     lib.ss_local_ba.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int, C.c_void_p, C.POINTER(BaParams)] + [C.c_void_p] * 5
     lib.ss_local_ba_points_to_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    lib.ss_pose_graph_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(GraphParams)] + [C.c_void_p] * 3
+    lib.ss_pose_graph_edge_host.argtypes = [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 2
+    lib.ss_graph_atan2_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.ss_graph_ln_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.ss_pose_graph_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(GraphParams)] + \
+                                        [C.c_void_p] * 3
+    lib.ss_pose_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(GraphParams)] + [C.c_void_p] * 3
+    lib.ss_pose_graph_points_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     lib.ss_pnp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                 C.POINTER(PnpParams), C.c_int, C.c_void_p, C.c_void_p]
     lib.ss_pnp_model_host.argtypes = [C.POINTER(PnpParams)] + [C.c_void_p] * 6
@@ -1724,6 +1812,33 @@ class OrbContext:
             raise ValueError("one block number per problem")
         self._check(self._lib.ss_local_ba_points_to_block(self._h, C.c_void_p(d_xyz), C.c_void_p(d_point_flags), n_problems, point_rows,
                                                           None if bo is None else bo.ctypes.data, C.c_void_p(d_points), n_blocks))
+
+    # ---- essential-graph optimisation: the Sim3 pose graph of a closed loop (the rule: include/sendslam_orb.h) ----
+    def pose_graph_device(self, d_nc: int, d_start: int, d_fixed: int, n_kf: int, problems, edges, params: GraphParams, d_sim3: int, d_poses: int,
+                          d_result: int):
+        """the problems (GRAPH_PROBLEM_DTYPE, a host table) of one call on device arrays: d_nc and d_start float64 [n_kf][13], d_fixed uint8
+        [n_kf]; edges a host table int32 [n_edges][2] of the call's keyframe numbers; d_sim3 float64 [n_kf][13], d_poses float64 [n_kf][12],
+        d_result GRAPH_RESULT_DTYPE [n_problems]; asynchronous."""
+        pr = np.ascontiguousarray(problems, GRAPH_PROBLEM_DTYPE).reshape(-1)
+        ed = np.ascontiguousarray(edges, np.int32).reshape(-1, 2)
+        self._check(self._lib.ss_pose_graph_device(self._h, C.c_void_p(d_nc), C.c_void_p(d_start), C.c_void_p(d_fixed), n_kf,
+                                                   pr.ctypes.data if len(pr) else None, len(pr), ed.ctypes.data if len(ed) else None, len(ed),
+                                                   C.byref(params), C.c_void_p(d_sim3), C.c_void_p(d_poses), C.c_void_p(d_result)))
+
+    def pose_graph(self, nc, start, fixed, edges, params: GraphParams):
+        """One problem, host arrays in and out -> what pose_graph_host returns."""
+        nc, st, fx, ed = _graph_host_arrays(nc, start, fixed, edges)
+        n_kf = len(nc)
+        sim3, poses, res = np.empty((n_kf, 13), np.float64), np.empty((n_kf, 12), np.float64), np.zeros(1, GRAPH_RESULT_DTYPE)
+        self._check(self._lib.ss_pose_graph(self._h, nc.ctypes.data, st.ctypes.data, fx.ctypes.data, n_kf, ed.ctypes.data if len(ed) else None,
+                                            len(ed), C.byref(params), sim3.ctypes.data, poses.ctypes.data, res.ctypes.data))
+        return sim3, poses, res[0]
+
+    def pose_graph_points_device(self, d_points: int, d_ref: int, n_blocks: int, point_rows: int, d_nc: int, d_sim3: int, n_kf: int):
+        """x, y, z of every row of the blocks of MAP_POINT_DTYPE whose d_ref entry (int32 [n_blocks][point_rows]) names a keyframe of the call
+        move with that keyframe: x <- S^-1(N(x)); the other fields and the rows with another entry (-1) stay; asynchronous."""
+        self._check(self._lib.ss_pose_graph_points_device(self._h, C.c_void_p(d_points), C.c_void_p(d_ref), n_blocks, point_rows, C.c_void_p(d_nc),
+                                                          C.c_void_p(d_sim3), n_kf))
 
     # ---- PnP RANSAC: a pose for every relocalisation candidate (the rule: include/sendslam_orb.h) ----
     @staticmethod

@@ -1759,6 +1759,154 @@ int ss_pose_graph(ss_ctx *ctx, const double *nc, const double *start, const uint
 int ss_pose_graph_points_device(ss_ctx *ctx, void *d_points, const void *d_ref, int n_blocks, int point_rows, const void *d_nc,
                                 const void *d_sim3, int n_kf);
 
+/* ---- Global bundle adjustment: Optimizer::GlobalBundleAdjustemnt / BundleAdjustment (the edges of the local bundle adjustment
+ * over every keyframe and point of a map, under one Levenberg-Marquardt loop with the points marginalised) as
+ * LoopClosing::RunGlobalBundleAdjustment starts it after a loop correction and CreateInitialMapMonocular after the initialisation,
+ * for several maps (problems) of a call at once.  tests/gba_ref.py is its normative statement; DESIGN.md section 29.  An addition
+ * to ABI 5: nothing existing changes.  The g2o and ORB-SLAM3 sources are not in the reference tree: parity with the real binary is
+ * unpinned, as for the Sim3 refinement, the local bundle adjustment and the essential-graph optimisation --------------------------
+ * - All arithmetic is double.  Every step is one IEEE operation, left to right as written, with no contraction.  The only library
+ *   functions are sqrt and division.  Every test is written in its accepting form, so a NaN fails it (the step-size test of
+ *   ss_pose_exp excepted).
+ * - Every sum has one fixed order, so ss_global_ba_host and the kernels agree bit for bit, for any number of problems of a call
+ *   and whatever the order of the observation records.
+ * A call has n_kf keyframes (a start pose and a fixed byte each on the device, a view each in a HOST table: only the camera and bf
+ * of a view are read, as in the local bundle adjustment), blocks of map points (only x, y, z are read) with an optional skip byte
+ * each, a HOST table of observation records (ss_gba_obs, any order) and a HOST table of problems.  Problem q owns the keyframes
+ * first_kf .. first_kf + n_kf - 1, the blocks first_block .. first_block + n_blocks - 1 (its points: P = n_blocks * point_rows,
+ * point i = block * point_rows + row relative to first_block) and the records first_obs .. first_obs + n_obs - 1, whose kf and point
+ * are relative to the problem.  No two problems share a keyframe, a block or a record.  The host sorts a problem's records by
+ * (point, kf) with two stable counting passes and builds both incidence lists from the sorted table: a point's list in ascending
+ * kf, a keyframe's list in ascending point.  "List order" below is that order; j is an item's place in its keyframe's list.
+ * 1. Observations and points, as step 1 of the local bundle adjustment with the record in the place of the keypoint row.  Point row
+ *    i of a block is a point iff i < n_points of the block, its skip byte (if given) is 0 and x, y, z are finite.  A record is an
+ *    observation iff its point is a point and its octave lies in 0 .. n_levels-1; u, v are the record's floats widened, w = 1.0 /
+ *    (s*s) with s = (double)scale[octave]; stereo iff check_right is set and right > 0.  A point is active iff it has at least
+ *    min_point_obs observations; the others are flagged 1 and never move.  Start poses go through step 2 of the pose-only
+ *    optimisation (Gram-Schmidt); one that is not finite gives the problem state 2 at once.  Keyframe k is free iff fixed[k] == 0;
+ *    no fixed keyframe is required (the damping keeps the system definite, the gauge is the caller's choice; upstream fixes the
+ *    first keyframe).  No active point or no free keyframe: state 1.
+ * 2. Linearisation: step 2 of the local bundle adjustment, term by term (ss_ba_lin, ss_pose_terms).
+ * 3. Per active point: step 3 of the local bundle adjustment over the point's list (ascending kf from +0.0, fixed keyframes
+ *    included): V_i, b_i, the damping V_aa += lambda*(1.0 + V_aa), the factor, frozen points.  W_ki is kept for every free k.
+ * 4. Per free keyframe k, over its list in list order.  The 26 sums of U_k and g_k (every contributing observation), the 21 of the
+ *    upper triangle of C_kk = sum_i Y_ki.W_ki^T and the 6 of sum_i Y_ki.b_i (the contributing observations of solved points; Y_ki =
+ *    W_ki.V_i^-1 row by row by the two triangular solves, the entries as in step 4 of the local bundle adjustment) are each a tree
+ *    of 256 slots: slot s adds the items j = s, s + 256, ... in ascending j from +0.0, skipping those that do not contribute; each
+ *    group of 64 slots folds by halving; the four results combine as (r0 + r1) + (r2 + r3).  U_aa += lambda*(1.0 + U_aa); M_k = U_k
+ *    - C_kk, one subtraction per entry, is factored by Cholesky by columns of order 6 (ss_gn_chol_n); r_k = -(g_k - sum Y.b).  A
+ *    pivot that is not > 0 in any free keyframe: state 2, the problem ends, nothing moves.  A free keyframe without a contributing
+ *    observation has M_k = lambda on the diagonal: it stays where it is for any lambda > 0, and ends the problem under lambda 0.
+ * 5. Solve S.dc = r, S = U - W.V^-1.W^T over the free keyframes, by preconditioned conjugate gradients; S is never formed.
+ *    The operator q = S.p: per solved point a_i = sum_k W_ki^T.p_k over its free contributing observations in ascending kf from
+ *    +0.0 (a_b = a_b + (((((W[0][b]*p[0] + W[1][b]*p[1]) + W[2][b]*p[2]) + W[3][b]*p[3]) + W[4][b]*p[4]) + W[5][b]*p[5])), c_i =
+ *    V_i^-1.a_i by the two triangular solves; per free keyframe q_k = U_k.p_k - T_k, entry by entry, with (U.p)_a the six products
+ *    of row a added left to right and T_k the tree over the keyframe's list of W_ki.c_i (entry a: (W[a][0]*c[0] + W[a][1]*c[1]) +
+ *    W[a][2]*c[2]; the items of solved points that contribute).  So Y.x is W.(V^-1.x) in the operator and (W.V^-1).x in step 4,
+ *    on the host and on the device alike.  The loop is that of the essential-graph optimisation: x = 0, z = M^-1.r block by
+ *    block, p = z, rho = r.z, stop = (pcg_tol*pcg_tol)*rho; while fewer than pcg_iterations are done: q = S.p, pq = p.q, leave
+ *    unless pq > 0 (x kept); alpha = rho / pq; x += alpha*p, r -= alpha*q; one more is done; z = M^-1.r; rho1 = r.z; leave if rho1
+ *    <= stop; beta = rho1 / rho; p = z + beta*p; rho = rho1.  Every dot product is the tree over the 6*n_kf entries in
+ *    keyframe-major order (entry e in slot e % 256); the entries of fixed keyframes are +0.0.  dc = x.
+ * 6. Back-substitution and update: step 6 of the local bundle adjustment over the point's list (v = -b_i, the free contributing
+ *    observations in ascending kf, dp_i = V_i^-1.v), the trial poses by exp(dc_k), and q > pi*pi in any free keyframe: state 4.
+ * 7. Accept or reject, the lambda schedule and the end of a round: step 7 of the local bundle adjustment.  The cost of a state is
+ *    the tree over the keyframes (keyframe k in slot k % 256, ascending) of the tree over each keyframe's list, in list order, of
+ *    the chi-terms of the inlier observations of active points.
+ * 8. Rounds and classification: step 8 of the local bundle adjustment.  The defaults are upstream's global schedule: one robust
+ *    round of 10 iterations.
+ * 9. No NaN bits reach a result, as in step 9 of the local bundle adjustment.
+ * Outputs.  Per problem one ss_gba_result, 104 bytes.  Per keyframe of the call twelve doubles: fixed keyframes and those of no
+ * problem get their orthonormalised start.  Per block and point row three doubles and one flag byte with the local bundle
+ * adjustment's meaning (0 optimised, 1 too few observations or inliers, 2 not a point, its doubles +0.0; every row of a block of
+ * no problem is flagged 2), in its layout with one block in the place of one problem, so that ss_local_ba_points_to_block with
+ * n_problems = n_blocks and block_of = NULL rounds the result back into the map.  Per record, in the caller's order, one byte: 0
+ * inlier, 1 outlier, 2 not an observation (every record of no problem).  Every output byte is written exactly once per call.
+ * Deviations from upstream: those of the local bundle adjustment; the linear solve is block-Jacobi PCG on the reduced system to a
+ * loose tolerance (a sparse Cholesky there); no map bookkeeping and no stop flag. */
+#define SS_GBA_MAX_KF 16384       /* keyframes of a problem: SS_GRAPH_MAX_KF, one call's output feeds the other */
+#define SS_GBA_MAX_POINTS 1048576 /* n_blocks * point_rows of a problem */
+#define SS_GBA_MAX_OBS 4194304    /* observation records of a problem */
+typedef struct {            /* 24 bytes, one per observation (a HOST table, any order) */
+    int32_t kf;             /* 0 .. n_kf-1, relative to the problem */
+    int32_t point;          /* block * point_rows + row, relative to the problem's first block */
+    float u, v;             /* the undistorted keypoint */
+    float right;            /* > 0: a stereo observation when check_right is set */
+    int32_t octave;
+} ss_gba_obs;
+typedef struct {            /* 32 bytes, one per problem (a HOST table) */
+    int32_t first_kf, n_kf, first_block, n_blocks, first_obs, n_obs;
+    int32_t reserved[2];    /* must be 0 */
+} ss_gba_problem;
+typedef struct {            /* 104 bytes */
+    double chi2_mono;       /* finite and > 0; upstream: 5.991 */
+    double chi2_stereo;     /* finite and > 0; upstream: 7.815 */
+    double lambda;          /* the first step's; finite and >= 0; default 1e-4 */
+    double lambda_factor;   /* finite and > 1; default 10 */
+    double lambda_min;      /* finite and >= 0; default 1e-9 */
+    double step_eps;        /* finite and >= 0; default 1e-10; 0 runs every step */
+    double pcg_tol;         /* finite and >= 0; default 1e-2 (DESIGN.md section 29 holds the table it was chosen on) */
+    int32_t n_rounds;       /* 1 .. SS_BA_MAX_ROUNDS; default 1 */
+    int32_t iterations[4];  /* each 1 .. 32 for r < n_rounds; default 10 */
+    int32_t robust_rounds;  /* 0 .. SS_BA_MAX_ROUNDS; default 1 */
+    int32_t min_point_obs;  /* >= 1; default 2 */
+    int32_t check_right;    /* non-zero: a record with right > 0 is a stereo observation */
+    int32_t pcg_iterations; /* 1 .. 256 per step; default 64.  Each one is three launches of the fixed schedule */
+    int32_t reserved[3];    /* must be 0 */
+} ss_gba_params;
+typedef struct {            /* 104 bytes, one per problem */
+    double lambda;          /* after the last step */
+    double cost_before;     /* the cost ahead of the first step of round 0 */
+    double cost_after;      /* the cost of the state returned, under the inliers and robustness of the last round that ran */
+    int32_t state;          /* 0 ok, 1 no active point or no free keyframe, 2 not positive definite, or a start pose or a cost that is not finite, 4 step too large */
+    int32_t status;         /* SS_OK */
+    int32_t n_obs, n_stereo; /* observations of points, active or not; the stereo ones among them */
+    int32_t n_inliers;      /* observation bytes that are 0 on return */
+    int32_t n_points_active; /* point flags that are 0 on return */
+    int32_t n_frozen_max;   /* the most points frozen in one step */
+    int32_t steps[4];       /* steps taken in round r, rejected ones included */
+    int32_t accepted[4];    /* steps accepted in round r */
+    int32_t pcg_iterations; /* of all steps */
+    int32_t n_free, n_fixed; /* keyframes of the problem */
+    int32_t reserved[2];    /* 0 */
+} ss_gba_result;
+/* The whole rule on the host from the text the kernels compile (csrc/ss_gba_steps.h), one problem of n_kf keyframes, n_points point
+ * rows (one block) and n_obs records; needs no device.  views, start (n_kf x 12 doubles) and fixed are per keyframe; poses n_kf x
+ * 12 doubles, xyz n_points x 3 doubles, point_flags n_points bytes, obs_flags n_obs bytes in the order of obs.  Arguments are
+ * checked as the device call checks them: SS_ERR_INVALID_ARG, and the message in err (err_bytes of it; NULL: none). */
+int ss_global_ba_host(const ss_proj_view *views, const double *start, const uint8_t *fixed, int n_kf, const float *scale, int n_levels,
+                      const ss_map_point *points, const uint8_t *point_skip, int n_points, const ss_gba_obs *obs, int n_obs,
+                      const ss_gba_params *p, double *poses, double *xyz, uint8_t *point_flags, uint8_t *obs_flags,
+                      ss_gba_result *result, char *err, int err_bytes);
+/* The records of the stack the projection searches leave, in ascending (point, kf) order: one for every idx[k][i] (int32
+ * [n_kf][n_points]) with 0 <= idx < n_kp[k] clamped to 0 .. rows_per_frame, with the keypoint's x, y and octave and right[k][row]
+ * (right NULL: -1).  kp and right are [n_kf][rows_per_frame], downloaded.  Returns the count and writes at most capacity records
+ * (out NULL: counts only); SS_ERR_INVALID_ARG (negative) for a NULL table or a bad count.  Pure host code. */
+int ss_global_ba_obs_from_idx_host(const ss_keypoint *kp, const float *right, const int32_t *n_kp, int n_kf, int rows_per_frame,
+                                   const int32_t *idx, int n_points, ss_gba_obs *out, int capacity);
+/* n_problems problems on device arrays: d_points [n_blocks][point_rows] ss_map_point, d_point_skip uint8 [n_blocks][point_rows] or
+ * NULL, d_n_points int32 [n_blocks] (clamped to 0 .. point_rows), d_start double [n_kf][12] (ss_pose_graph_device's d_poses feeds
+ * it without a round trip), d_fixed uint8 [n_kf].  problems (n_problems), obs (n_obs) and views (n_kf) are HOST tables, copied
+ * (sorted, with both incidence lists) before the call returns.  The scale table and n_levels are the context's.  Outputs: d_poses
+ * double [n_kf][12], d_xyz double [n_blocks][point_rows][3], d_point_flags uint8 [n_blocks][point_rows], d_obs_flags uint8
+ * [n_obs], d_result [n_problems] ss_gba_result.  SS_ERR_INVALID_ARG, with a message: a kf or point outside its problem, a (kf,
+ * point) pair twice, n_kf outside 1 .. SS_GBA_MAX_KF, n_blocks * point_rows outside 0 .. SS_GBA_MAX_POINTS or n_obs outside 0 ..
+ * SS_GBA_MAX_OBS, a keyframe, block or record range outside the call or overlapping another problem's, a parameter out of its
+ * range, a reserved field that is not 0, a NULL buffer, point_rows above SS_GUIDED_MAX_ROWS.  Without a keyframe or without a
+ * problem the call returns SS_OK and writes nothing.  The fixed schedule of every round, step and PCG iteration is enqueued at
+ * once (7 + 3 * pcg_iterations launches per step); a problem that has ended, or whose PCG has left, costs empty launches.  The
+ * context's workspace for a call is dominated by the W blocks, 144 bytes per record (4 194 304 records: 604 MB);
+ * SS_ERR_NO_MEMORY when it cannot be had.  Asynchronous on the context's stream. */
+int ss_global_ba_device(ss_ctx *ctx, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks,
+                        int point_rows, const void *d_start, const void *d_fixed, int n_kf, const ss_gba_problem *problems,
+                        int n_problems, const ss_gba_obs *obs, int n_obs, const ss_proj_view *views, const ss_gba_params *p,
+                        void *d_poses, void *d_xyz, void *d_point_flags, void *d_obs_flags, void *d_result);
+/* One problem with host pointers in and out (copy in, the device form, copy out), synchronous; the arguments of
+ * ss_global_ba_host without the message buffer (the message is the context's last error). */
+int ss_global_ba(ss_ctx *ctx, const ss_proj_view *views, const double *start, const uint8_t *fixed, int n_kf,
+                 const ss_map_point *points, const uint8_t *point_skip, int n_points, const ss_gba_obs *obs, int n_obs,
+                 const ss_gba_params *p, double *poses, double *xyz, uint8_t *point_flags, uint8_t *obs_flags, ss_gba_result *result);
+
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device
  * (hipStream_t; NULL = the legacy default stream): for callers that produce the inputs of a *_device call on their own

@@ -461,6 +461,9 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_graph_ws);
     dev_free(c->d_graph_io);
     staged_free(c->graph_tab);
+    dev_free(c->d_gba_ws);
+    dev_free(c->d_gba_io);
+    staged_free(c->gba_tab);
     dev_free(c->d_sim3opt_ws);
     dev_free(c->d_sim3opt_io);
     staged_free(c->sim3opt_tab);

@@ -19,6 +19,7 @@
 
 #include "ss_ba_steps.h"
 #include "ss_graph_steps.h"
+#include "ss_gba_steps.h"
 #include "ss_epi_steps.h"
 #include "ss_fuse_steps.h"
 #include "ss_pnp_steps.h"
@@ -2578,6 +2579,337 @@ int ss_pose_graph_points_device(ss_ctx *c, void *d_points, const void *d_ref, in
     }
     HIP_TRY(c, hipGetLastError());
     return SS_OK;
+}
+
+/* ---- global bundle adjustment (csrc/ss_gba.hip, csrc/ss_gba_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *gba_params_error(const ss_gba_params *p)
+{
+    if (!p) return "global BA: params is NULL";
+    if (!(p->chi2_mono > 0.0) || !std::isfinite(p->chi2_mono)) return "global BA: chi2_mono must be finite and > 0";
+    if (!(p->chi2_stereo > 0.0) || !std::isfinite(p->chi2_stereo)) return "global BA: chi2_stereo must be finite and > 0";
+    if (!(p->lambda >= 0.0) || !std::isfinite(p->lambda)) return "global BA: lambda must be finite and >= 0";
+    if (!(p->lambda_factor > 1.0) || !std::isfinite(p->lambda_factor)) return "global BA: lambda_factor must be finite and > 1";
+    if (!(p->lambda_min >= 0.0) || !std::isfinite(p->lambda_min)) return "global BA: lambda_min must be finite and >= 0";
+    if (!(p->step_eps >= 0.0) || !std::isfinite(p->step_eps)) return "global BA: step_eps must be finite and >= 0";
+    if (!(p->pcg_tol >= 0.0) || !std::isfinite(p->pcg_tol)) return "global BA: pcg_tol must be finite and >= 0";
+    if (p->n_rounds < 1 || p->n_rounds > SS_BA_MAX_ROUNDS) return "global BA: n_rounds must be 1 .. 4";
+    for (int r = 0; r < p->n_rounds; r++)
+        if (p->iterations[r] < 1 || p->iterations[r] > 32) return "global BA: iterations must be 1 .. 32 in every round";
+    if (p->robust_rounds < 0 || p->robust_rounds > SS_BA_MAX_ROUNDS) return "global BA: robust_rounds must be 0 .. 4";
+    if (p->min_point_obs < 1) return "global BA: min_point_obs must be >= 1";
+    if (p->pcg_iterations < 1 || p->pcg_iterations > 256) return "global BA: pcg_iterations must be 1 .. 256";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0) return "global BA: the reserved fields must be 0";
+    return nullptr;
+}
+
+/* the host tables of a call: what the kernels read besides the caller's device arrays */
+struct gba_host_tables {
+    std::vector<int32_t> kf_prob, blk_prob, pt_off, pt_cnt, kf_off, kf_cnt, kf_list;
+    std::vector<ss_gba_rec> rec;
+    int max_kf = 0;
+};
+
+/* The shapes and ranges of the problems of a call, then the records of each sorted and both its incidence lists into t.  The message
+ * of the first rule that is broken, or empty.  May throw std::bad_alloc: the tables grow with the caller's counts */
+static std::string gba_build(int n_kf, int n_blocks, int point_rows, const ss_gba_problem *problems, int n_problems, const ss_gba_obs *obs, int n_obs,
+                             const float *scale, int n_levels, bool check_right, gba_host_tables &t)
+{
+    const size_t NP = (size_t)n_blocks * point_rows;
+    t.kf_prob.assign((size_t)n_kf, -1), t.blk_prob.assign((size_t)n_blocks, -1);
+    t.pt_off.assign(NP, 0), t.pt_cnt.assign(NP, 0), t.kf_off.assign((size_t)n_kf, 0), t.kf_cnt.assign((size_t)n_kf, 0);
+    t.kf_list.assign((size_t)n_obs, 0);
+    t.rec.resize((size_t)n_obs);
+    for (int m = 0; m < n_obs; m++) t.rec[(size_t)m] = ss_gba_rec{-1, -1, 0.0f, 0.0f, -1.0f, 1.0f, m, 0};
+    std::vector<int32_t> rec_prob((size_t)n_obs, -1);
+    for (int q = 0; q < n_problems; q++) {
+        const ss_gba_problem &b = problems[q];
+        const std::string head = "global BA: problem " + std::to_string(q) + ": ";
+        if (b.n_kf < 1 || b.n_kf > SS_GBA_MAX_KF) return head + "n_kf " + std::to_string(b.n_kf) + " outside 1 .. SS_GBA_MAX_KF (" + std::to_string(SS_GBA_MAX_KF) + ")";
+        if (b.n_blocks < 0 || (int64_t)b.n_blocks * point_rows > SS_GBA_MAX_POINTS)
+            return head + "n_blocks " + std::to_string(b.n_blocks) + " of " + std::to_string(point_rows) + " rows outside 0 .. SS_GBA_MAX_POINTS (" +
+                   std::to_string(SS_GBA_MAX_POINTS) + ") points";
+        if (b.n_obs < 0 || b.n_obs > SS_GBA_MAX_OBS) return head + "n_obs " + std::to_string(b.n_obs) + " outside 0 .. SS_GBA_MAX_OBS (" + std::to_string(SS_GBA_MAX_OBS) + ")";
+        if (b.reserved[0] != 0 || b.reserved[1] != 0) return head + "the reserved fields must be 0";
+        if (b.first_kf < 0 || b.first_kf > n_kf - b.n_kf)
+            return head + "keyframes " + std::to_string(b.first_kf) + " .. + " + std::to_string(b.n_kf) + " lie outside the call's " + std::to_string(n_kf);
+        if (b.first_block < 0 || b.first_block > n_blocks - b.n_blocks)
+            return head + "blocks " + std::to_string(b.first_block) + " .. + " + std::to_string(b.n_blocks) + " lie outside the call's " + std::to_string(n_blocks);
+        if (b.first_obs < 0 || b.first_obs > n_obs - b.n_obs)
+            return head + "records " + std::to_string(b.first_obs) + " .. + " + std::to_string(b.n_obs) + " lie outside the call's " + std::to_string(n_obs);
+        for (int k = b.first_kf; k < b.first_kf + b.n_kf; k++) {
+            if (t.kf_prob[(size_t)k] >= 0) return head + "keyframe " + std::to_string(k) + " belongs to problem " + std::to_string(t.kf_prob[(size_t)k]) + " already";
+            t.kf_prob[(size_t)k] = q;
+        }
+        for (int k = b.first_block; k < b.first_block + b.n_blocks; k++) {
+            if (t.blk_prob[(size_t)k] >= 0) return head + "block " + std::to_string(k) + " belongs to problem " + std::to_string(t.blk_prob[(size_t)k]) + " already";
+            t.blk_prob[(size_t)k] = q;
+        }
+        for (int m = b.first_obs; m < b.first_obs + b.n_obs; m++) {
+            if (rec_prob[(size_t)m] >= 0) return head + "record " + std::to_string(m) + " belongs to problem " + std::to_string(rec_prob[(size_t)m]) + " already";
+            rec_prob[(size_t)m] = q;
+        }
+        t.max_kf = std::max(t.max_kf, (int)b.n_kf);
+    }
+    /* the ranges stand: now the records of every problem */
+    for (int q = 0; q < n_problems; q++) {
+        const ss_gba_problem &b = problems[q];
+        const std::string head = "global BA: problem " + std::to_string(q) + ": ";
+        if (b.n_obs > 0 && !obs) return "global BA: obs is NULL";
+        const int P = b.n_blocks * point_rows;
+        const size_t p0 = (size_t)b.first_block * point_rows;
+        int bad = 0;
+        const int why = ss_gba_tables(b.n_kf, P, obs + b.first_obs, b.n_obs, scale, n_levels, check_right, b.first_obs, t.rec.data() + b.first_obs, t.pt_off.data() + p0,
+                                      t.pt_cnt.data() + p0, t.kf_off.data() + b.first_kf, t.kf_cnt.data() + b.first_kf, t.kf_list.data() + b.first_obs, &bad);
+        if (why != 0) {
+            const ss_gba_obs &o = obs[b.first_obs + bad];
+            const std::string rec = head + "record " + std::to_string(b.first_obs + bad) + ": ";
+            if (why == 1) return rec + "kf " + std::to_string(o.kf) + " outside 0 .. " + std::to_string(b.n_kf - 1);
+            if (why == 2) return rec + "point " + std::to_string(o.point) + " outside 0 .. " + std::to_string(P - 1);
+            return rec + "the pair (kf " + std::to_string(o.kf) + ", point " + std::to_string(o.point) + ") has a record already";
+        }
+    }
+    return std::string();
+}
+
+static int gba_refuse(char *err, int err_bytes, const std::string &msg)
+{
+    if (err && err_bytes > 0) snprintf(err, (size_t)err_bytes, "%s", msg.c_str());
+    return SS_ERR_INVALID_ARG;
+}
+
+int ss_global_ba_obs_from_idx_host(const ss_keypoint *kp, const float *right, const int32_t *n_kp, int n_kf, int rows_per_frame, const int32_t *idx, int n_points,
+                                   ss_gba_obs *out, int capacity)
+{
+    if (n_kf < 0 || n_points < 0 || rows_per_frame < 1 || capacity < 0) return SS_ERR_INVALID_ARG;
+    if (n_kf > 0 && n_points > 0 && (!kp || !n_kp || !idx)) return SS_ERR_INVALID_ARG;
+    int64_t n = 0;
+    for (int i = 0; i < n_points; i++)
+        for (int k = 0; k < n_kf; k++) {
+            const int nk = std::min(std::max(n_kp[k], 0), rows_per_frame), row = idx[(size_t)k * n_points + i];
+            if (row < 0 || row >= nk) continue;
+            if (out && n < capacity) {
+                const ss_keypoint &kk = kp[(size_t)k * rows_per_frame + row];
+                out[n] = ss_gba_obs{k, i, kk.x, kk.y, right ? right[(size_t)k * rows_per_frame + row] : -1.0f, kk.octave};
+            }
+            n++;
+        }
+    return n > INT32_MAX ? SS_ERR_INVALID_ARG : (int)n;
+}
+
+int ss_global_ba_host(const ss_proj_view *views, const double *start, const uint8_t *fixed, int n_kf, const float *scale, int n_levels, const ss_map_point *points,
+                      const uint8_t *point_skip, int n_points, const ss_gba_obs *obs, int n_obs, const ss_gba_params *p, double *poses, double *xyz,
+                      uint8_t *point_flags, uint8_t *obs_flags, ss_gba_result *result, char *err, int err_bytes)
+{
+    if (const char *msg = gba_params_error(p)) return gba_refuse(err, err_bytes, msg);
+    if (n_points < 0 || n_obs < 0 || n_kf < 0) return gba_refuse(err, err_bytes, "global BA: bad keyframe, point or record count");
+    if (!scale || n_levels < 1 || n_levels > SS_MAX_LEVELS) return gba_refuse(err, err_bytes, "global BA: no pyramid table of 1 .. SS_MAX_LEVELS levels");
+    if (!views || !start || !fixed || !poses || !result || (n_points > 0 && (!points || !xyz || !point_flags)) || (n_obs > 0 && (!obs || !obs_flags)))
+        return gba_refuse(err, err_bytes, "global BA: NULL buffer");
+    try {
+        const ss_gba_problem shape = {0, n_kf, 0, n_points > 0 ? 1 : 0, 0, n_obs, {0, 0}};
+        gba_host_tables t;
+        const std::string msg = gba_build(n_kf, shape.n_blocks, std::max(n_points, 1), &shape, 1, obs, n_obs, scale, n_levels, p->check_right != 0, t);
+        if (!msg.empty()) return gba_refuse(err, err_bytes, msg);
+        const size_t P = (size_t)n_points;
+        std::vector<ss_pose_cam> cam((size_t)n_kf);
+        for (int k = 0; k < n_kf; k++) cam[(size_t)k] = ss_pose_cam_of(views[k], p->chi2_mono, p->chi2_stereo);
+        std::vector<double> X(P * 3 + 1);
+        std::vector<uint8_t> pflag(P + 1), ob((size_t)n_obs + 1);
+        for (size_t i = 0; i < P; i++) {
+            const ss_map_point &pt = points[i];
+            const bool is_point = !(point_skip && point_skip[i] != 0) && ss_gn_is_finite((double)pt.x) && ss_gn_is_finite((double)pt.y) && ss_gn_is_finite((double)pt.z);
+            pflag[i] = is_point ? 0 : 2;
+            X[3 * i] = is_point ? (double)pt.x : 0.0, X[3 * i + 1] = is_point ? (double)pt.y : 0.0, X[3 * i + 2] = is_point ? (double)pt.z : 0.0;
+        }
+        ss_gba_problem_host(n_kf, n_points, n_obs, cam.data(), start, fixed, t.rec.data(), t.pt_off.data(), t.pt_cnt.data(), t.kf_off.data(), t.kf_cnt.data(),
+                            t.kf_list.data(), *p, ob.data(), X.data(), pflag.data(), poses, result);
+        for (size_t i = 0; i < P; i++) {
+            point_flags[i] = pflag[i];
+            for (int e = 0; e < 3; e++) xyz[3 * i + e] = pflag[i] == 2 ? 0.0 : X[3 * i + e];
+        }
+        for (int s = 0; s < n_obs; s++) obs_flags[t.rec[(size_t)s].orig] = ob[(size_t)s];
+    } catch (const std::bad_alloc &) { /* the tables and the workspace grow with the caller's counts */
+        return SS_ERR_NO_MEMORY;
+    }
+    return SS_OK;
+}
+
+/* the checks, the tables and the schedule of ss_global_ba_device; its host tables grow with the caller's counts and may throw */
+static int gba_run(ss_ctx *c, ssk_gba_call &g, const ss_gba_problem *problems, const ss_gba_obs *obs, const ss_proj_view *views, const ss_gba_params *p)
+{
+    if (const char *msg = gba_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (g.n_kf < 0 || g.n_problems < 0 || g.n_blocks < 0 || g.n_obs < 0 || g.point_rows < 1)
+        return fail(c, SS_ERR_INVALID_ARG, "global BA: bad keyframe, problem, block, row or record count");
+    if (g.point_rows > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "global BA: point_rows " + std::to_string(g.point_rows) + " exceeds SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")");
+    if ((int64_t)g.n_blocks * g.point_rows > INT32_MAX / 4) return fail(c, SS_ERR_INVALID_ARG, "global BA: more than 2^29 point rows in one call");
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS];
+    int rc = call_count_ok(c, "global BA", g.n_problems, "problems");
+    if (rc == SS_OK) rc = context_pyramid(c, "global BA", &n_levels, scale);
+    if (rc != SS_OK) return rc;
+    if (g.n_kf == 0 || g.n_problems == 0) return SS_OK;
+    if (!problems || !views) return fail(c, SS_ERR_INVALID_ARG, "global BA: problems or views is NULL");
+    gba_host_tables t;
+    const std::string msg = gba_build(g.n_kf, g.n_blocks, g.point_rows, problems, g.n_problems, obs, g.n_obs, scale, n_levels, p->check_right != 0, t);
+    if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (!g.start || !g.fixed || !g.out_pose || !g.result || (g.n_blocks > 0 && (!g.points || !g.np || !g.out_xyz || !g.out_pflag)) || (g.n_obs > 0 && !g.out_obs))
+        return fail(c, SS_ERR_INVALID_ARG, "global BA: NULL buffer");
+    g.p = *p;
+    g.max_kf = t.max_kf;
+    const size_t K = (size_t)g.n_kf, NP = (size_t)g.n_blocks * g.point_rows, S = (size_t)g.n_obs, nq = (size_t)g.n_problems, B = (size_t)g.n_blocks;
+    const size_t groups = B * (((size_t)g.point_rows + SS_GN_SLOTS - 1) / SS_GN_SLOTS);
+    rc = carve_from(c, c->d_gba_ws, [&](carve &w) {
+        g.pose = w.take<double>(2 * K * 12 * sizeof(double));
+        g.X = w.take<double>(2 * NP * 3 * sizeof(double));
+        g.pflag = w.take<uint8_t>(NP);
+        g.solved = w.take<uint8_t>(NP);
+        g.ob = w.take<uint8_t>(S);
+        g.lin = w.take<uint8_t>(S);
+        g.W = w.take<double>(S * SS_BA_W * sizeof(double));
+        g.Lb = w.take<double>(NP * 12 * sizeof(double));
+        g.U = w.take<double>(K * SS_BA_DIAG * sizeof(double));
+        g.M = w.take<double>(K * 36 * sizeof(double));
+        g.x = w.take<double>(K * 6 * sizeof(double));
+        g.r = w.take<double>(K * 6 * sizeof(double));
+        g.z = w.take<double>(K * 6 * sizeof(double));
+        g.pv = w.take<double>(K * 6 * sizeof(double));
+        g.q = w.take<double>(K * 6 * sizeof(double));
+        g.cost_k = w.take<double>(K * sizeof(double));
+        g.kf_flag = w.take<uint8_t>(K);
+        g.part = w.take<int32_t>(groups * 4 * sizeof(int32_t));
+        g.st = w.take<ssk_gba_state>(nq * sizeof(ssk_gba_state));
+    });
+    if (rc != SS_OK) return rc;
+    /* the host tables of the call, each on a 16-byte boundary: the problems, the views, the keyframes' and the blocks' problems, the
+     * keyframes' and the points' runs, the sorted records, the keyframes' lists */
+    size_t at = 0;
+    auto place = [&](size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 15) & ~(size_t)15;
+        return o;
+    };
+    const size_t o_prob = place(nq * sizeof(ss_gba_problem)), o_view = place(K * sizeof(ss_proj_view)), o_kfp = place(K * 4), o_blp = place(B * 4), o_kfo = place(K * 4),
+                 o_kfc = place(K * 4), o_pto = place(NP * 4), o_ptc = place(NP * 4), o_rec = place(S * sizeof(ss_gba_rec)), o_lst = place(S * 4);
+    rc = staged_upload(c, c->gba_tab, at + 16, [&](uint8_t *h) {
+        memcpy(h + o_prob, problems, nq * sizeof(ss_gba_problem));
+        memcpy(h + o_view, views, K * sizeof(ss_proj_view));
+        memcpy(h + o_kfp, t.kf_prob.data(), K * 4);
+        if (B) memcpy(h + o_blp, t.blk_prob.data(), B * 4);
+        memcpy(h + o_kfo, t.kf_off.data(), K * 4);
+        memcpy(h + o_kfc, t.kf_cnt.data(), K * 4);
+        if (NP) memcpy(h + o_pto, t.pt_off.data(), NP * 4), memcpy(h + o_ptc, t.pt_cnt.data(), NP * 4);
+        if (S) memcpy(h + o_rec, t.rec.data(), S * sizeof(ss_gba_rec)), memcpy(h + o_lst, t.kf_list.data(), S * 4);
+    });
+    if (rc != SS_OK) return rc;
+    g.prob = c->gba_tab.as<ss_gba_problem>(o_prob);
+    g.views = c->gba_tab.as<ss_proj_view>(o_view);
+    g.kf_prob = c->gba_tab.as<int32_t>(o_kfp), g.blk_prob = c->gba_tab.as<int32_t>(o_blp);
+    g.kf_off = c->gba_tab.as<int32_t>(o_kfo), g.kf_cnt = c->gba_tab.as<int32_t>(o_kfc);
+    g.pt_off = c->gba_tab.as<int32_t>(o_pto), g.pt_cnt = c->gba_tab.as<int32_t>(o_ptc);
+    g.rec = c->gba_tab.as<ss_gba_rec>(o_rec);
+    g.kf_list = c->gba_tab.as<int32_t>(o_lst);
+    /* the stages' bytes: what a launch reads and writes when every record is an observation of a free keyframe (an upper bound) */
+    const int64_t iK = (int64_t)K, iP = (int64_t)NP, iS = (int64_t)S, iq = (int64_t)nq, iG = (int64_t)groups;
+    const int64_t state_bytes = iq * (int64_t)sizeof(ssk_gba_state);
+    {
+        stage_timer tm(c, "gba_gather", iK * (96 + 192 + 1) + iP * (32 + 8 + 48 + 2 + (g.p_skip ? 1 : 0)) + iS * 33 + iG * 32 + state_bytes);
+        ssk_gba_gather(c->stream, g);
+    }
+    for (int r = 0; r < p->n_rounds; r++) {
+        for (int it = -1; it < p->iterations[r]; it++) {
+            if (it >= 0) {
+                {
+                    stage_timer tm(c, "gba_points", iP * (8 + 1 + 24 + 72 + 1) + iS * (1 + 32 + 96 + 48 + 1 + 144 + 1) + iG * 4);
+                    ssk_gba_points(c->stream, g, r);
+                }
+                {
+                    stage_timer tm(c, "gba_blocks", iS * (4 + 1 + 32 + 1 + 24 + 144 + 72) + iK * (8 + 96 + 48 + 168 + 288 + 5 * 48 + 1 + 48 + 1) + iG * 4 + 2 * state_bytes);
+                    ssk_gba_blocks(c->stream, g, r);
+                }
+                for (int m = 0; m < p->pcg_iterations; m++) {
+                    stage_timer tm(c, "gba_pcg", iS * (1 + 32 + 1 + 144 + 48) + iP * (8 + 1 + 48 + 24) + iS * (4 + 1 + 32 + 1 + 144 + 24) + iK * (8 + 168 + 48 + 48) +
+                                                     iK * (6 * 48 + 288 + 1) + 2 * state_bytes);
+                    ssk_gba_pcg(c->stream, g);
+                }
+                {
+                    stage_timer tm(c, "gba_update", iK * (96 + 48 + 96 + 2) + iP * (8 + 2 + 24 + 72 + 24) + iS * (1 + 32 + 1 + 144 + 48) + iG * 8);
+                    ssk_gba_update(c->stream, g);
+                }
+            }
+            stage_timer tm(c, "gba_cost", iK * (8 + 96 + 48 + 8) + iS * (4 + 1 + 32 + 1 + 24) + iK * 9 + iG * 8 + 2 * state_bytes);
+            ssk_gba_cost(c->stream, g, r, it >= 0 ? 0 : 1);
+        }
+        stage_timer tm(c, "gba_classify", iP * (8 + 1 + 24 + 1) + iS * (1 + 32 + 96 + 48 + 1));
+        ssk_gba_classify(c->stream, g);
+    }
+    {
+        stage_timer tm(c, "gba_finish", iP * (8 + 1 + 24 + 24 + 1) + iS * (1 + 32 + 1 + 1) + iK * (4 + 96 + 96) + iG * 16 + iq * (int64_t)sizeof(ss_gba_result) + state_bytes);
+        ssk_gba_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_global_ba_device(ss_ctx *c, const void *d_points, const void *d_point_skip, const void *d_n_points, int n_blocks, int point_rows, const void *d_start,
+                        const void *d_fixed, int n_kf, const ss_gba_problem *problems, int n_problems, const ss_gba_obs *obs, int n_obs, const ss_proj_view *views,
+                        const ss_gba_params *p, void *d_poses, void *d_xyz, void *d_point_flags, void *d_obs_flags, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    ssk_gba_call g;
+    g.n_kf = n_kf, g.n_problems = n_problems, g.n_blocks = n_blocks, g.point_rows = point_rows, g.n_obs = n_obs;
+    g.points = (const ss_map_point *)d_points, g.p_skip = (const uint8_t *)d_point_skip, g.np = (const int32_t *)d_n_points;
+    g.start = (const double *)d_start, g.fixed = (const uint8_t *)d_fixed;
+    g.out_pose = (double *)d_poses, g.out_xyz = (double *)d_xyz, g.out_pflag = (uint8_t *)d_point_flags, g.out_obs = (uint8_t *)d_obs_flags;
+    g.result = (ss_gba_result *)d_result;
+    try {
+        return gba_run(c, g, problems, obs, views, p);
+    } catch (const std::bad_alloc &) {
+        return fail(c, SS_ERR_NO_MEMORY, "global BA: no host memory for the tables of the call");
+    }
+}
+
+int ss_global_ba(ss_ctx *c, const ss_proj_view *views, const double *start, const uint8_t *fixed, int n_kf, const ss_map_point *points, const uint8_t *point_skip,
+                 int n_points, const ss_gba_obs *obs, int n_obs, const ss_gba_params *p, double *poses, double *xyz, uint8_t *point_flags, uint8_t *obs_flags,
+                 ss_gba_result *result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = gba_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_kf < 1 || n_kf > SS_GBA_MAX_KF) return fail(c, SS_ERR_INVALID_ARG, "global BA: problem 0: n_kf " + std::to_string(n_kf) + " outside 1 .. SS_GBA_MAX_KF (" + std::to_string(SS_GBA_MAX_KF) + ")");
+    if (n_points < 0 || n_points > SS_GBA_MAX_POINTS || n_obs < 0 || n_obs > SS_GBA_MAX_OBS)
+        return fail(c, SS_ERR_INVALID_ARG, "global BA: n_points must be 0 .. SS_GBA_MAX_POINTS and n_obs 0 .. SS_GBA_MAX_OBS");
+    if (!views || !start || !fixed || !poses || !result || (n_points > 0 && (!points || !xyz || !point_flags)) || (n_obs > 0 && (!obs || !obs_flags)))
+        return fail(c, SS_ERR_INVALID_ARG, "global BA: NULL buffer");
+    /* the points as blocks of `pr` rows, the last one short: point i is row i % pr of block i / pr.  `count` is on this stack: no
+     * return before the stream has read it */
+    const int pr = std::min(std::max(n_points, 1), SS_GUIDED_MAX_ROWS), nb = n_points > 0 ? (n_points + pr - 1) / pr : 0;
+    const size_t np = (size_t)n_points, room = (size_t)std::max(nb, 1) * pr, kf = (size_t)n_kf, ns = (size_t)n_obs;
+    std::vector<int32_t> count((size_t)std::max(nb, 1), 0);
+    for (int b = 0; b < nb; b++) count[(size_t)b] = std::min(pr, n_points - b * pr);
+    const ss_gba_problem problem = {0, n_kf, 0, nb, 0, n_obs, {0, 0}};
+    enum { PT, PS, NP, ST, FX, POSE, XYZ, PF, OF, RES, PIECES };
+    io_piece io[PIECES] = {{points, nullptr, room * sizeof(ss_map_point), np * sizeof(ss_map_point)},
+                           {point_skip, nullptr, room, np},
+                           {count.data(), nullptr, count.size() * 4, count.size() * 4},
+                           {start, nullptr, kf * 96, kf * 96},
+                           {fixed, nullptr, kf, kf},
+                           {nullptr, poses, kf * 96, kf * 96},
+                           {nullptr, xyz, room * 24, np * 24},
+                           {nullptr, point_flags, room, np},
+                           {nullptr, obs_flags, std::max(ns, (size_t)1), ns},
+                           {nullptr, result, sizeof(ss_gba_result), sizeof(ss_gba_result)}};
+    int rc = io_send(c, c->d_gba_io, io, PIECES);
+    if (rc == SS_OK)
+        rc = ss_global_ba_device(c, io[PT].d, point_skip ? io[PS].d : nullptr, io[NP].d, nb, pr, io[ST].d, io[FX].d, n_kf, &problem, 1, obs, n_obs, views, p, io[POSE].d,
+                                 io[XYZ].d, io[PF].d, io[OF].d, io[RES].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
 }
 
 /* ---- PnP RANSAC (csrc/ss_pnp.hip, csrc/ss_pnp_steps.h) ---- */

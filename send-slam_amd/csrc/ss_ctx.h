@@ -164,6 +164,10 @@ struct ss_ctx {
      * the keyframes' problems, the incidence lists) */
     dev_buf<uint8_t> d_graph_ws, d_graph_io;
     staged_table graph_tab;
+    /* global bundle adjustment: the workspace of a call, the host form's device copies, the tables of a call (problems, views, the
+     * keyframes' and blocks' problems, the sorted records and both incidence lists) */
+    dev_buf<uint8_t> d_gba_ws, d_gba_io;
+    staged_table gba_tab;
     /* PnP RANSAC: the workspace of a call (correspondences, models, poses, counts), the host form's device copies, the tables of a
      * call (views, then frame numbers, then block numbers) */
     dev_buf<uint8_t> d_pnp_ws, d_pnp_io;

@@ -592,6 +592,66 @@ struct ssk_graph_points_call {
     const double *nc = nullptr, *sim3 = nullptr;
 };
 void ssk_graph_points(hipStream_t s, const ssk_graph_points_call &g);
+/* ss_gba.hip: global bundle adjustment (DESIGN.md "Global bundle adjustment").  Problem q owns the keyframes prob[q].first_kf ..,
+ * the blocks prob[q].first_block .. and the sorted records prob[q].first_obs .. of the call.  Keyframe, point (block * point_rows +
+ * row) and record numbers index the call's arrays; what the tables hold (rec.kf, rec.point, the offsets and kf_list) is relative
+ * to the problem, as ss_gba_tables builds it.  Every kernel of the fixed schedule reads its problem's ssk_gba_state and returns at
+ * once when the problem has ended, its round is over or (the three kernels of a PCG iteration) its PCG has left.  Poses and
+ * points are double-buffered as in ss_ba.hip */
+struct ss_gba_rec; /* ss_gba_steps.h */
+struct ssk_gba_state {
+    double lambda, cost0, cost_before, rho, stop;
+    int32_t state, ended, round_over, cur, n_free;
+    int32_t pcg_live, pcg_done, pcg_total;
+    int32_t n_obs, n_stereo, n_frozen_max, trial_ok;
+    int32_t steps[4], accepted[4];
+};
+struct ssk_gba_call {
+    int n_kf = 0, n_problems = 0, n_blocks = 0, point_rows = 0, n_obs = 0;
+    int max_kf = 0;                        /* the largest of the call's problems */
+    const ss_map_point *points = nullptr; /* [n_blocks][point_rows] */
+    const uint8_t *p_skip = nullptr;      /* [n_blocks][point_rows], or NULL */
+    const int32_t *np = nullptr;          /* [n_blocks] */
+    const double *start = nullptr;        /* [n_kf][12] */
+    const uint8_t *fixed = nullptr;       /* [n_kf] */
+    const ss_gba_problem *prob = nullptr; /* device [n_problems] */
+    const int32_t *kf_prob = nullptr;     /* device [n_kf]: the keyframe's problem, or -1 */
+    const int32_t *blk_prob = nullptr;    /* device [n_blocks]: the block's problem, or -1 */
+    const ss_proj_view *views = nullptr;  /* device [n_kf] */
+    const ss_gba_rec *rec = nullptr;      /* device [n_obs]: a problem's records sorted; kf < 0: a record of no problem */
+    const int32_t *pt_off = nullptr, *pt_cnt = nullptr; /* device [n_blocks * point_rows]: the point's run of rec */
+    const int32_t *kf_off = nullptr, *kf_cnt = nullptr; /* device [n_kf]: the keyframe's run of kf_list */
+    const int32_t *kf_list = nullptr;     /* device [n_obs] */
+    ss_gba_params p = {};
+    /* workspace */
+    double *pose = nullptr;    /* [2][n_kf][12] */
+    double *X = nullptr;       /* [2][points][3] */
+    uint8_t *pflag = nullptr;  /* [points] */
+    uint8_t *solved = nullptr; /* [points] */
+    uint8_t *ob = nullptr;     /* [n_obs]: the rule's byte of every sorted record */
+    uint8_t *lin = nullptr;    /* [n_obs]: the record took part in this step's linearisation */
+    double *W = nullptr;       /* [n_obs][18]: the records of free keyframes */
+    double *Lb = nullptr;      /* [points][12]: a point's factor (6), b (3), c of the operator (3) */
+    double *U = nullptr;       /* [n_kf][21] */
+    double *M = nullptr;       /* [n_kf][36]: the factor of a free keyframe's block */
+    double *x = nullptr, *r = nullptr, *z = nullptr, *pv = nullptr, *q = nullptr; /* [n_kf][6] each */
+    double *cost_k = nullptr;  /* [n_kf] */
+    uint8_t *kf_flag = nullptr; /* [n_kf]: gather: the start is finite; blocks: every pivot > 0; update: bit 0 finite, 1 small, 2 too large */
+    int32_t *part = nullptr;   /* [n_blocks * pblocks][4]: per workgroup of points, what a kernel hands to the next */
+    ssk_gba_state *st = nullptr; /* [n_problems] */
+    /* outputs */
+    double *out_pose = nullptr, *out_xyz = nullptr;
+    uint8_t *out_pflag = nullptr, *out_obs = nullptr;
+    ss_gba_result *result = nullptr;
+};
+void ssk_gba_gather(hipStream_t s, const ssk_gba_call &g);  /* three launches */
+void ssk_gba_cost(hipStream_t s, const ssk_gba_call &g, int round, int begin); /* two launches: the keyframes' trees, then the decision */
+void ssk_gba_points(hipStream_t s, const ssk_gba_call &g, int round);
+void ssk_gba_blocks(hipStream_t s, const ssk_gba_call &g, int round);          /* two launches: the blocks, then the start of the PCG */
+void ssk_gba_pcg(hipStream_t s, const ssk_gba_call &g);                        /* one iteration: three launches */
+void ssk_gba_update(hipStream_t s, const ssk_gba_call &g);                     /* two launches */
+void ssk_gba_classify(hipStream_t s, const ssk_gba_call &g);
+void ssk_gba_finish(hipStream_t s, const ssk_gba_call &g);                     /* three launches */
 /* The bookkeeping of SearchBySim3 (the rule: include/sendslam_orb.h).  One workgroup per pair: a base pass over the rows, a barrier,
  * a scatter pass in which every store to one address writes the same value.  marks writes skip1 and skip2; mutual marks the train
  * rows that carry a prior match in taken (workspace, [n_frames][rows]) and writes idx_out and the summary */

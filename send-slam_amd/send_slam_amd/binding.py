@@ -53,7 +53,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_sim3_mutual_batch_device", "ss_sim3_to_view21", "ss_local_ba_host", "ss_local_ba_pairs_device",
            "ss_local_ba_batch_device", "ss_local_ba", "ss_local_ba_points_to_block", "ss_pnp_host", "ss_pnp_model_host", "ss_pnp_check_host",
            "ss_pnp_pairs_device", "ss_pnp_batch_device", "ss_pnp", "ss_pose_graph_host", "ss_pose_graph_edge_host", "ss_graph_atan2_host",
-           "ss_graph_ln_host", "ss_pose_graph_device", "ss_pose_graph", "ss_pose_graph_points_device"]
+           "ss_graph_ln_host", "ss_pose_graph_device", "ss_pose_graph", "ss_pose_graph_points_device", "ss_global_ba_host",
+           "ss_global_ba_obs_from_idx_host", "ss_global_ba_device", "ss_global_ba"]
 
 
 class OrbParams(C.Structure):
@@ -852,6 +853,93 @@ def rectify_model(fx, fy, cx, cy, k1, k2, p1, p2, k3, R, fx_new, fy_new, cx_new,
     return m
 
 
+# ---- global bundle adjustment (the rule: include/sendslam_orb.h) ----
+SS_GBA_MAX_KF, SS_GBA_MAX_POINTS, SS_GBA_MAX_OBS = 16384, 1048576, 4194304
+
+
+class GbaParams(C.Structure):
+    _fields_ = [("chi2_mono", C.c_double), ("chi2_stereo", C.c_double), ("lambda_", C.c_double), ("lambda_factor", C.c_double),
+                ("lambda_min", C.c_double), ("step_eps", C.c_double), ("pcg_tol", C.c_double), ("n_rounds", C.c_int32),
+                ("iterations", C.c_int32 * 4), ("robust_rounds", C.c_int32), ("min_point_obs", C.c_int32), ("check_right", C.c_int32),
+                ("pcg_iterations", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+# ss_gba_obs: one per observation record; ss_gba_problem: one per problem (host tables); ss_gba_result: one per problem
+GBA_OBS_DTYPE = np.dtype([("kf", "<i4"), ("point", "<i4"), ("u", "<f4"), ("v", "<f4"), ("right", "<f4"), ("octave", "<i4")])
+GBA_PROBLEM_DTYPE = np.dtype([(n, "<i4") for n in ("first_kf", "n_kf", "first_block", "n_blocks", "first_obs", "n_obs")] + [("reserved", "<i4", (2,))])
+GBA_RESULT_DTYPE = np.dtype([("lambda_", "<f8"), ("cost_before", "<f8"), ("cost_after", "<f8")] +
+                            [(n, "<i4") for n in ("state", "status", "n_obs", "n_stereo", "n_inliers", "n_points_active", "n_frozen_max")] +
+                            [("steps", "<i4", (4,)), ("accepted", "<i4", (4,))] + [(n, "<i4") for n in ("pcg_iterations", "n_free", "n_fixed")] +
+                            [("reserved", "<i4", (2,))])
+
+
+def gba_params(chi2_mono: float = 5.991, chi2_stereo: float = 7.815, lambda_: float = 1e-4, lambda_factor: float = 10.0, lambda_min: float = 1e-9,
+               step_eps: float = 1e-10, pcg_tol: float = 1e-2, n_rounds: int = 1, iterations=(10, 0, 0, 0), robust_rounds: int = 1,
+               min_point_obs: int = 2, check_right: bool = False, pcg_iterations: int = 64, reserved=(0, 0, 0)) -> GbaParams:
+    """upstream's GlobalBundleAdjustemnt schedule: one robust round of 10 iterations"""
+    its = tuple(iterations) + (0,) * (4 - len(tuple(iterations)))
+    return GbaParams(chi2_mono=chi2_mono, chi2_stereo=chi2_stereo, lambda_=lambda_, lambda_factor=lambda_factor, lambda_min=lambda_min,
+                     step_eps=step_eps, pcg_tol=pcg_tol, n_rounds=n_rounds, iterations=(C.c_int32 * 4)(*its), robust_rounds=robust_rounds,
+                     min_point_obs=min_point_obs, check_right=int(check_right), pcg_iterations=pcg_iterations,
+                     reserved=(C.c_int32 * 3)(*reserved))
+
+
+def _gba_host_arrays(views, start, fixed, points, obs, skip):
+    """the arrays of one problem, checked against each other"""
+    v = _views_array(views)
+    n_kf = len(v)
+    st = _start_array(start, n_kf)
+    fx = np.ascontiguousarray(fixed, np.uint8).reshape(-1)
+    pts = np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1)
+    ob = np.ascontiguousarray(obs, GBA_OBS_DTYPE).reshape(-1)
+    skip = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    if len(fx) != n_kf or (skip is not None and len(skip) != len(pts)):
+        raise ValueError("views, start poses, fixed bytes, map points and skip bytes differ in length")
+    return v, st, fx, pts, ob, skip
+
+
+def global_ba_host(views, start, fixed, scale, points: np.ndarray, obs: np.ndarray, params: GbaParams, skip=None):
+    """ss_global_ba_host: the whole rule on the host for one problem -> (poses float64 [n_kf][12], xyz float64 [n_points][3], uint8 point
+    flags, uint8 observation flags [n_obs] in the order of obs, one GBA_RESULT_DTYPE record); needs no device.  A refusal raises
+    OrbError with the library's message"""
+    v, st, fx, pts, ob, skip = _gba_host_arrays(views, start, fixed, points, obs, skip)
+    sc = np.ascontiguousarray(scale, np.float32)
+    n_kf, n_p, n_o = len(v), len(pts), len(ob)
+    poses, xyz = np.empty((n_kf, 12), np.float64), np.empty((n_p, 3), np.float64)
+    pf, of, res = np.empty(n_p, np.uint8), np.empty(n_o, np.uint8), np.zeros(1, GBA_RESULT_DTYPE)
+    err = C.create_string_buffer(512)
+    ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+    rc = load().ss_global_ba_host(ptr(v, n_kf), ptr(st, n_kf), ptr(fx, n_kf), n_kf, ptr(sc, len(sc)), len(sc), ptr(pts, n_p), ptr(skip, n_p), n_p,
+                                  ptr(ob, n_o), n_o, C.byref(params), poses.ctypes.data, ptr(xyz, n_p), ptr(pf, n_p), ptr(of, n_o), res.ctypes.data,
+                                  err, len(err))
+    if rc != SS_OK:
+        raise OrbError(rc, err.value.decode() or "ss_global_ba_host refused its arguments")
+    return poses, xyz, pf, of, res[0]
+
+
+def global_ba_obs_from_idx(kp: np.ndarray, idx: np.ndarray, n_kp=None, right=None) -> np.ndarray:
+    """ss_global_ba_obs_from_idx_host: kp [n_kf][rows], idx int32 [n_kf][n_points] (a stack of projection-search outputs), right
+    [n_kf][rows] or None -> the GBA_OBS_DTYPE records in ascending (point, kf) order"""
+    k = np.ascontiguousarray(kp, KP_DTYPE)
+    if k.ndim != 2 or k.shape[1] < 1:
+        raise ValueError("keypoints are [n_kf][rows_per_frame]")
+    n_kf = len(k)
+    ix = np.ascontiguousarray(idx, np.int32).reshape(n_kf, -1)
+    nk = np.full(n_kf, k.shape[1], np.int32) if n_kp is None else np.ascontiguousarray(n_kp, np.int32)
+    right = None if right is None else np.ascontiguousarray(right, np.float32)
+    if len(nk) != n_kf or (right is not None and right.shape != k.shape):
+        raise ValueError("keypoints, counts and right coordinates differ in length")
+    fn = load().ss_global_ba_obs_from_idx_host
+    args = (k.ctypes.data, None if right is None else right.ctypes.data, nk.ctypes.data, n_kf, k.shape[1], ix.ctypes.data, ix.shape[1])
+    n = fn(*args, None, 0)
+    if n < 0:
+        raise OrbError(n, "ss_global_ba_obs_from_idx_host refused its arguments")
+    out = np.zeros(n, GBA_OBS_DTYPE)
+    if n and fn(*args, out.ctypes.data, n) != n:
+        raise OrbError(SS_ERR_STATE, "ss_global_ba_obs_from_idx_host: the count changed between two calls")
+    return out
+
+
 class OrbError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libsendslam_orb: {message} (status {code})")
@@ -1018,6 +1106,13 @@ def load():
                                         [C.c_void_p] * 3
     lib.ss_pose_graph.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(GraphParams)] + [C.c_void_p] * 3
     lib.ss_pose_graph_points_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    lib.ss_global_ba_host.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                         C.POINTER(GbaParams)] + [C.c_void_p] * 5 + [C.c_char_p, C.c_int]
+    lib.ss_global_ba_obs_from_idx_host.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.ss_global_ba_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                                          C.c_void_p, C.c_int, C.c_void_p, C.POINTER(GbaParams)] + [C.c_void_p] * 5
+    lib.ss_global_ba.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                                   C.POINTER(GbaParams)] + [C.c_void_p] * 5
     lib.ss_pnp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                 C.POINTER(PnpParams), C.c_int, C.c_void_p, C.c_void_p]
     lib.ss_pnp_model_host.argtypes = [C.POINTER(PnpParams)] + [C.c_void_p] * 6
@@ -1839,6 +1934,36 @@ class OrbContext:
         move with that keyframe: x <- S^-1(N(x)); the other fields and the rows with another entry (-1) stay; asynchronous."""
         self._check(self._lib.ss_pose_graph_points_device(self._h, C.c_void_p(d_points), C.c_void_p(d_ref), n_blocks, point_rows, C.c_void_p(d_nc),
                                                           C.c_void_p(d_sim3), n_kf))
+
+    # ---- global bundle adjustment: Schur PCG over a whole map (the rule: include/sendslam_orb.h) ----
+    def global_ba_device(self, d_points: int, d_n_points: int, n_blocks: int, point_rows: int, d_start: int, d_fixed: int, n_kf: int, problems, obs,
+                         views, params: GbaParams, d_poses: int, d_xyz: int, d_point_flags: int, d_obs_flags: int, d_result: int,
+                         d_point_skip: int = 0):
+        """the problems (GBA_PROBLEM_DTYPE), the observation records (GBA_OBS_DTYPE, any order) and the views (one per keyframe) are host
+        tables; d_start float64 [n_kf][12] (pose_graph_device's d_poses feeds it), d_fixed uint8 [n_kf], map points as for
+        local_ba_pairs_device; d_poses float64 [n_kf][12], d_xyz float64 [n_blocks][point_rows][3], d_point_flags uint8
+        [n_blocks][point_rows], d_obs_flags uint8 [n_obs] in the order of obs, d_result GBA_RESULT_DTYPE [n_problems]; asynchronous."""
+        pr = np.ascontiguousarray(problems, GBA_PROBLEM_DTYPE).reshape(-1)
+        ob = np.ascontiguousarray(obs, GBA_OBS_DTYPE).reshape(-1)
+        v = _views_array(views)
+        if len(v) != n_kf:
+            raise ValueError("one view per keyframe")
+        self._check(self._lib.ss_global_ba_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_skip), C.c_void_p(d_n_points), n_blocks, point_rows,
+                                                  C.c_void_p(d_start), C.c_void_p(d_fixed), n_kf, pr.ctypes.data if len(pr) else None, len(pr),
+                                                  ob.ctypes.data if len(ob) else None, len(ob), v.ctypes.data if n_kf else None, C.byref(params),
+                                                  C.c_void_p(d_poses), C.c_void_p(d_xyz), C.c_void_p(d_point_flags), C.c_void_p(d_obs_flags),
+                                                  C.c_void_p(d_result)))
+
+    def global_ba(self, views, start, fixed, points: np.ndarray, obs: np.ndarray, params: GbaParams, skip=None):
+        """One problem, host arrays in and out -> what global_ba_host returns."""
+        v, st, fx, pts, ob, skip = _gba_host_arrays(views, start, fixed, points, obs, skip)
+        n_kf, n_p, n_o = len(v), len(pts), len(ob)
+        poses, xyz = np.empty((n_kf, 12), np.float64), np.empty((n_p, 3), np.float64)
+        pf, of, res = np.empty(n_p, np.uint8), np.empty(n_o, np.uint8), np.zeros(1, GBA_RESULT_DTYPE)
+        ptr = lambda a, n: None if a is None or not n else a.ctypes.data  # noqa: E731
+        self._check(self._lib.ss_global_ba(self._h, ptr(v, n_kf), ptr(st, n_kf), ptr(fx, n_kf), n_kf, ptr(pts, n_p), ptr(skip, n_p), n_p, ptr(ob, n_o), n_o,
+                                           C.byref(params), poses.ctypes.data, ptr(xyz, n_p), ptr(pf, n_p), ptr(of, n_o), res.ctypes.data))
+        return poses, xyz, pf, of, res[0]
 
     # ---- PnP RANSAC: a pose for every relocalisation candidate (the rule: include/sendslam_orb.h) ----
     @staticmethod

@@ -1641,6 +1641,154 @@ int ss_pnp_batch_device(ss_ctx *ctx, const void *d_points, const void *d_point_s
 int ss_pnp(ss_ctx *ctx, const ss_proj_view *view, const ss_map_point *points, const uint8_t *point_skip, int n_points,
            const ss_keypoint *kp, int n_kp, const int32_t *idx, const ss_pnp_params *p, uint8_t *inlier, ss_pnp_result *result);
 
+/* ---- Two-view initialisation: TwoViewReconstruction::Reconstruct as Tracking::MonocularInitialization runs it on the matches of
+ * SearchForInitialization (ss_match_guided_*): homography and fundamental-matrix RANSAC, the model choice, the decomposition and
+ * CheckRT, for every initialising pair of a call at once.  The upstream source is not in the reference tree.  This is the library's
+ * own restatement from the published algorithm and from the host form inside the bounded tracker (sst_two_view, which keeps its own
+ * draw stream and is not replaced); parity with the real binary stays unpinned, as for the Sim3 and PnP RANSAC.  tests/two_view_ref.py is
+ * its normative statement; csrc/ss_two_view_steps.h is the text kernels and host twins compile; DESIGN.md section 30.  An addition to ABI 5: nothing
+ * existing changes -------------------------------------------------------------------------------------------------------------
+ * - All arithmetic is double on the float32 coordinates widened.  Every step is one IEEE operation, left to right as written, with
+ *   no contraction.  Every test is written in its accepting form, so a NaN fails it.  Division and sqrt are the only library
+ *   operations (no acos: the parallax tests are on cosines).
+ * - Host and device agree bit for bit, for any number of problems in a call and in any order.
+ * One problem q: the keypoints of two frames (ss_keypoint; x, y of both and the octave of frame 1 are read; taken as undistorted),
+ * idx[i], the row of frame 2 matched to row i of frame 1, or < 0 (what ss_match_guided_* writes), and one camera for both frames
+ * (fx, fy, cx, cy of an ss_proj_view; nothing else of it is read).
+ * 1. Correspondences.  Rows i < n1 in ascending order; (i, j = idx[i]) is kept iff 0 <= j < n2 and 0 <= octave_i < n_levels (the
+ *    map point's distance range reads that scale).  The kept ones are numbered 0 .. N-1 in that order; each is four float32 values
+ *    u1 v1 u2 v2.  N < 8: state 1.
+ * 2. Normalisation, per coordinate c of the four: m_c = sum(x) / N, d_c = sum(|x - m_c|) / N.  A sum over the correspondences is
+ *    THE TREE: chunks of 256 consecutive correspondences (absent terms +0.0); in a chunk each group of 64 is folded by halving
+ *    (a[l] += a[l + h], h = 32 .. 1) and the four group results are combined as (g0 + g1) + (g2 + g3) (ss_gn_tree); the chunk sums
+ *    are added in ascending order starting from the first.  A d_c that is not > 0, or a d_c or m_c that is not finite: state 2.
+ *    s_c = 1.0 / d_c, the normalised coordinate is (x - m_c) * s_c, T = [[sx, 0, -mx*sx], [0, sy, -my*sy], [0, 0, 1]] per image and
+ *    T2^-1 = [[dx, 0, mx], [0, dy, my], [0, 0, 1]] in closed form.
+ * 3. Hypothesis t, 0 <= t < max_iterations: eight draws without replacement by the swap-with-last rule of ss_sim3_* step 3a with
+ *    eight values of the stream per hypothesis (ss_sim3_draw_k<8>(seed, q, t, N)); H and F share them.
+ *    H: each draw gives the rows ra = (0, 0, 0, -u1, -v1, -1, v2*u1, v2*v1, v2) and rb = (u1, v1, 1, 0, 0, 0, -(u2*u1), -(u2*v1),
+ *    -u2); entry (i, j), i >= j, of the 9 x 9 normal matrix is the sum over the draws, in draw order from the first term, of
+ *    ra_i*ra_j + rb_i*rb_j.  F: one row (u2*u1, u2*v1, u2, v2*u1, v2*v1, v2, u1, v1, 1) per draw, entry (i, j) the sum of r_i*r_j.
+ *    The null vector of either as ss_pnp_* step 3b finds its own at order 12: trace in ascending order, 1e-13 * trace added to the
+ *    diagonal, one Cholesky by columns, x = nine times 1.0 / 3.0, six inverse iterations each followed by x / sqrt(the sequential
+ *    sum of squares); no convergence test.  F is then projected to rank 2: G = F^T.F (entry (i, j) = (F0i*F0j + F1i*F1j) +
+ *    F2i*F2j), eight sweeps of cyclic Jacobi over (0,1) (0,2) (1,2) with the rotation of ss_triangulate_* step 2, v the column of
+ *    the smallest diagonal entry (the first among equals), F[r][c] -= ((F[r][0]*v0 + F[r][1]*v1) + F[r][2]*v2) * v[c].  H21 =
+ *    (T2^-1.Hn).T1, H12 = adj(H21) * (1.0 / det), F21 = (T2^T.Fn).T1, every product entry (a0*b0 + a1*b1) + a2*b2.  A model is the
+ *    zero model, of score -1, when an entry is not finite, a pivot was not > 0, |det H21| is not > 1e-300 (H only) or two of the
+ *    eight draws coincide.
+ * 4. Score over all N correspondences, sigma = 1.  H: with x2 carried into image 1 by H12 and x1 into image 2 by H21 (w = 1.0 /
+ *    ((h6*u + h7*v) + h8), then each coordinate times w), chi_a and chi_b the two squared distances; F: chi_a = num^2 / (a^2 + b^2)
+ *    of x2 against the line F.x1, chi_b of x1 against F^T.x2.  A term is accepted iff chi <= chi2_h (chi2_f); the correspondence
+ *    contributes (chi_a accepted ? th - chi_a : 0.0) + (chi_b accepted ? th - chi_b : 0.0) with th = chi2_h for H and chi2_score
+ *    for F, and is an inlier iff both are accepted.  The score is the tree of step 2 over these contributions.
+ * 5. Selection, per model: the LARGEST score, the smallest t among equals.  Neither score > 0: state 2.
+ * 6. Model choice.  RH = h / (h + f), h and f the two scores, one that is not > 0 taken as 0.0; the homography iff RH >
+ *    rh_threshold.  The winner's inlier flags are computed once more; N_in is their count.  N_in < 8: state 3, reason 2.
+ * 7. Decomposition in double.  The 3 x 3 SVD: the eigenvalues of A^T.A by the Jacobi of step 3, sorted descending (among equals the
+ *    smaller index first), sigma = sqrt (0.0 when the eigenvalue is not > 0); columns 0 and 1 of U are A.v over its length,
+ *    column 2 their cross product, negated when its product with A.v2 is < 0.  F: E = (K^T.F).K, t = column 2 of U over its
+ *    length, R1 = (U.W).V^T, R2 = (U.W^T).V^T, each negated when its determinant is < 0; the four hypotheses (R1, t) (R2, t)
+ *    (R1, -t) (R2, -t).  H: A = (K^-1.H).K, refused (state 3, reason 1) unless d1/d2 >= 1.00001 and d2/d3 >= 1.00001; Faugeras and
+ *    Lustman's eight in the order of ReconstructH, R = s.(U.R').V^T with s = det U * det V^T, t = U.t' over its length.
+ * 8. CheckRT of every hypothesis over the winner's inliers.  a = (u - cx) / fx, b = (v - cy) / fy for both images; the DLT rows
+ *    (-1, 0, a1, 0), (0, -1, b1, 0), a2*P2[2] - P2[0], b2*P2[2] - P2[1] with P2 = [R | t]; the smallest eigenvector of the 4 x 4
+ *    exactly as ss_triangulate_* step 2; X = v / v3.  The point is good iff v3 is finite and not 0, X is finite, cos = (X.n2) /
+ *    (|X| * |n2|) with n2 = X + R^T.t is finite, (X.z > 0 or cos >= 0.99998), (Y.z > 0 or cos >= 0.99998) with Y = R.X + t, and
+ *    both squared reprojection errors ((fx*X.x) / X.z + cx) - u ... are <= 4.0.  n_good counts them; a good point is triangulated
+ *    iff cos < 0.99998.  The best hypothesis is the first with the largest n_good; its parallax cosine is the element at index
+ *    min(50, n_good - 1) of its good points' cosines in ascending order (an order statistic: -0.0 orders below +0.0).
+ * 9. Acceptance, in this order.  F: n_good >= max((int)(0.9 * N_in), min_triangulated), else reason 2; at most one hypothesis with
+ *    n_good > 0.7 * best, else reason 3; cos < cos_min_parallax, else reason 4.  H: n_good > min_triangulated and n_good > 0.9 *
+ *    N_in, else reason 2; second < 0.75 * best, else reason 3; cos <= cos_min_parallax, else reason 4.  Anything refused: state 3.
+ * 10. Outputs.  ss_two_view_result per problem; flag uint8 per row of frame 1 (every row < rows is written): 0 not a
+ *    correspondence, 1 an outlier of the chosen model, 2 an inlier that is not triangulated, 3 triangulated.  The triangulated
+ *    points in ascending query row as ss_map_point (frame 1 the world; x y z; the normal (X/|X| + n2/|n2|) / 2.0; max_dist = |X| *
+ *    scale[octave_i], min_dist = max_dist / scale[n_levels - 1]; each rounded to float32 once), their rows (int32 i, j) and their
+ *    count, in the layout ss_triangulate_* writes; rows from n_points on are not written.  In states 1 - 3 r21 and t21 are all
+ *    0.0, no flag exceeds 1 and there are no points; the scores, iterations, model, N_in, n_good and cos_parallax keep what the
+ *    rule reached.
+ * Deviations from upstream: the draw stream (DUtils::Random there); a match whose reference keypoint has an octave outside the
+ * pyramid table is no correspondence (upstream takes every match: N can be below the count of valid idx entries);
+ * inverse iteration and Jacobi where upstream calls cv::SVD;
+ * triangulation in normalised coordinates; cosines instead of degrees (cos_min_parallax is cos 1 degree); rh_threshold is a
+ * parameter (upstream's source has 0.50, ss_track 0.45); every hypothesis is scored, as upstream does; a NaN fails every test. */
+#define SS_TWO_VIEW_MAX_ITERATIONS 1024
+#define SS_TWO_VIEW_COS_1DEG 0.9998476951563913 /* cos(1 degree) */
+typedef struct {               /* 64 bytes */
+    double chi2_h;             /* finite and > 0; upstream: 5.991 */
+    double chi2_f;             /* finite and > 0; upstream: 3.841 */
+    double chi2_score;         /* finite and > 0; upstream: 5.991 */
+    double rh_threshold;       /* 0 .. 1; upstream: 0.50, ss_track: 0.45 */
+    double cos_min_parallax;   /* -1 .. 1; upstream: SS_TWO_VIEW_COS_1DEG */
+    int32_t min_triangulated;  /* >= 0; upstream: 50 */
+    int32_t max_iterations;    /* 1 .. SS_TWO_VIEW_MAX_ITERATIONS; upstream: 200 */
+    uint32_t seed;
+    int32_t reserved[3];       /* must be 0 */
+} ss_two_view_params;
+typedef struct {               /* 192 bytes, one per problem */
+    double r21[9], t21[3];     /* all 0.0 unless state == 0; X2 = r21.X1 + t21, |t21| = 1; feed ss_proj_view_init unchanged */
+    double score_h, score_f;   /* the best scores; -1.0 when every model was the zero model; 0.0 in state 1 and when step 2 fails */
+    double cos_parallax;       /* of the best hypothesis; 0.0 when there was none */
+    int32_t state;             /* 0 a map, 1 too few correspondences, 2 no model, 3 the reconstruction was refused */
+    int32_t reason;            /* state 3: 1 singular values, 2 too few good points, 3 ambiguous, 4 low parallax; else 0 */
+    int32_t status;            /* SS_OK, or the frame_error that voided the problem */
+    int32_t model;             /* 1 F, 2 H, 0 none */
+    int32_t iteration_h, iteration_f; /* the winners' t, or -1 */
+    int32_t n_corr;            /* N */
+    int32_t n_inliers;         /* N_in of the chosen model */
+    int32_t n_good;            /* of the best hypothesis */
+    int32_t n_triangulated;    /* state 0: the points written */
+    int32_t reserved[8];       /* 0 */
+} ss_two_view_result;
+/* Host twins (the text the kernels compile); none needs a device.  p is checked as the device calls check it (SS_ERR_INVALID_ARG).
+ * ss_two_view_host: the whole rule for one problem whose number in the call is `problem`; scale: n_levels entries; idx and flag
+ * have n_kp1 entries; points and point_rows (2 int32 each) have room for n_kp1 entries; *n_points is written.
+ * ss_two_view_model_host: steps 2 and 3 for one octuple: uv 8 x 4 floats (u1 v1 u2 v2) in draw order, normalised by their own mean
+ * and deviation (N = 8, the draws 0 .. 7); h21, h12, f21: nine doubles each, all 0.0 for a zero model; ok[2]: H, F.
+ * ss_two_view_check_host: steps 4 and 8 of n correspondences (uv n x 4 floats).  Any of h21 + h12, f21, r21 + t21 may be NULL with
+ * its outputs: chi_h / chi_f (2 doubles each per correspondence) and in_h / in_f (uint8), score_h / score_f (the tree); good
+ * (uint8: 0 not good, 1 good, 2 triangulated), cosv and xyz (3 doubles) under (r21, t21) and the camera of `view`.
+ * ss_two_view_accept_host: steps 8 and 9 on counts: good[n_hyp] (n_hyp 1 .. 8) the hypotheses' n_good, model 1 or 2, N_in and the best
+ * hypothesis' parallax cosine -> out[0] the reason (0: accepted), out[1] the best hypothesis (-1: none), out[2] its count, out[3] the
+ * second count.  ss_two_view_beats_host: step 5's order, 1 iff (score, t) beats (best, best_t).  ss_two_view_point_tests_host: the
+ * three tests of step 8 on given numbers: out[0] cos < 0.99998 (triangulated), out[1] cos >= 0.99998 (exempt from the depth tests),
+ * out[2] err_sq <= 4.0. */
+int ss_two_view_host(const ss_proj_view *view, const float *scale, int n_levels, const ss_keypoint *kp1, int n_kp1, const ss_keypoint *kp2,
+                     int n_kp2, const int32_t *idx, const ss_two_view_params *p, int problem, uint8_t *flag, ss_map_point *points,
+                     int32_t *point_rows, int32_t *n_points, ss_two_view_result *result);
+int ss_two_view_model_host(const float *uv, double *h21, double *h12, double *f21, int32_t *ok);
+int ss_two_view_check_host(const ss_two_view_params *p, const ss_proj_view *view, const float *uv, int n, const double *h21, const double *h12,
+                           const double *f21, const double *r21, const double *t21, double *chi_h, uint8_t *in_h, double *score_h,
+                           double *chi_f, uint8_t *in_f, double *score_f, uint8_t *good, double *cosv, double *xyz);
+int ss_two_view_accept_host(const ss_two_view_params *p, int model, const int32_t *good, int n_hyp, int n_in, double cos_parallax,
+                            int32_t *out);
+int ss_two_view_beats_host(double score, int t, double best, int best_t);
+int ss_two_view_point_tests_host(double cos_parallax, double err_sq, int32_t *out);
+/* n_problems problems on caller-supplied device arrays.  d_kp1 [n_frames1][rows_per_frame] and d_kp2 [n_frames2][rows_per_frame]
+ * ss_keypoint with their device int32 counts (clamped to 0 .. rows); kp1_src and kp2_src: HOST tables [n_problems] of frame
+ * numbers, or NULL (problem q reads frame q): one reference frame tried against several current frames is several problems that
+ * share it, with no copies.  d_idx int32 and d_flag uint8 are [n_problems][rows_per_frame]; views (n_problems) is a HOST table,
+ * copied before the call returns.  d_points (ss_map_point) and d_point_rows (2 int32) are [n_problems][rows_per_frame], d_n_points
+ * int32 [n_problems], d_result [n_problems] ss_two_view_result.  SS_ERR_INVALID_ARG: rows above SS_GUIDED_MAX_ROWS, a parameter out
+ * of its range, a reserved field that is not 0, a source entry out of range, a NULL buffer.  Asynchronous on the context's stream. */
+int ss_two_view_pairs_device(ss_ctx *ctx, const void *d_kp1, const void *d_n_kp1, int n_frames1, const void *d_kp2, const void *d_n_kp2,
+                             int n_frames2, int rows_per_frame, const void *d_idx, int n_problems, const ss_proj_view *views,
+                             const int32_t *kp1_src, const int32_t *kp2_src, const ss_two_view_params *p, void *d_flag, void *d_points,
+                             void *d_point_rows, void *d_n_points, void *d_result);
+/* The same, both sides being frames of the last ss_extract_batch_device batch (SS_ERR_STATE without one; n_problems is the batch's
+ * frame count and rows_per_frame its kp_capacity): problem q has frame q as its frame 1 and frame train_src[q] as its frame 2
+ * (train_src: a HOST table, or NULL: frame q - 1; -1, and frame 0 under NULL: no frame 2, so no correspondences and state 1), as in
+ * ss_match_guided_batch_device, whose d_idx it reads.  A problem with a frame whose frame_error is set gets that status, state 1 and
+ * no correspondences. */
+int ss_two_view_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_idx, int n_problems, const ss_proj_view *views,
+                             const ss_two_view_params *p, void *d_flag, void *d_points, void *d_point_rows, void *d_n_points, void *d_result);
+/* One problem (number 0) with host pointers in and out (copy in, the pairs form, copy out), synchronous; the arguments of
+ * ss_two_view_host.  n_kp1, n_kp2 <= SS_GUIDED_MAX_ROWS. */
+int ss_two_view(ss_ctx *ctx, const ss_proj_view *view, const ss_keypoint *kp1, int n_kp1, const ss_keypoint *kp2, int n_kp2, const int32_t *idx,
+                const ss_two_view_params *p, uint8_t *flag, ss_map_point *points, int32_t *point_rows, int32_t *n_points,
+                ss_two_view_result *result);
+
 /* ---- Essential-graph optimisation: Optimizer::OptimizeEssentialGraph (g2o VertexSim3Expmap and EdgeSim3 under Levenberg-Marquardt)
  * as LoopClosing::CorrectLoop calls it once a loop is accepted, for several loops (problems) of a call at once, and the map-point
  * correction that follows it there.  tests/graph_ref.py is its normative statement; DESIGN.md section 28.  An addition to ABI 5:

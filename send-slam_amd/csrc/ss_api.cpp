@@ -451,6 +451,9 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_pnp_ws);
     dev_free(c->d_pnp_io);
     staged_free(c->pnp_tab);
+    dev_free(c->d_tv_ws);
+    dev_free(c->d_tv_io);
+    staged_free(c->tv_tab);
     dev_free(c->d_pose_ws);
     dev_free(c->d_pose_io);
     staged_free(c->pose_tab);

@@ -27,6 +27,7 @@
 #include "ss_proj_steps.h"
 #include "ss_sim3_steps.h"
 #include "ss_sim3opt_steps.h"
+#include "ss_two_view_steps.h"
 
 extern "C" {
 
@@ -3129,6 +3130,277 @@ int ss_pnp(ss_ctx *c, const ss_proj_view *view, const ss_map_point *points, cons
         return rc;
     }
     return io_fetch(c, io, PIECES);
+}
+
+/* ---- two-view initialisation (csrc/ss_two_view.hip, csrc/ss_two_view_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *tv_params_error(const ss_two_view_params *p)
+{
+    if (!p) return "two_view: params is NULL";
+    if (!(p->chi2_h > 0.0) || !std::isfinite(p->chi2_h)) return "two_view: chi2_h must be finite and > 0";
+    if (!(p->chi2_f > 0.0) || !std::isfinite(p->chi2_f)) return "two_view: chi2_f must be finite and > 0";
+    if (!(p->chi2_score > 0.0) || !std::isfinite(p->chi2_score)) return "two_view: chi2_score must be finite and > 0";
+    if (!(p->rh_threshold >= 0.0 && p->rh_threshold <= 1.0)) return "two_view: rh_threshold must be 0 .. 1";
+    if (!(p->cos_min_parallax >= -1.0 && p->cos_min_parallax <= 1.0)) return "two_view: cos_min_parallax must be -1 .. 1";
+    if (p->min_triangulated < 0) return "two_view: min_triangulated must be >= 0";
+    if (p->max_iterations < 1 || p->max_iterations > SS_TWO_VIEW_MAX_ITERATIONS) return "two_view: max_iterations must be 1 .. SS_TWO_VIEW_MAX_ITERATIONS";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0) return "two_view: the reserved fields must be 0";
+    return nullptr;
+}
+
+int ss_two_view_host(const ss_proj_view *view, const float *scale, int n_levels, const ss_keypoint *kp1, int n_kp1, const ss_keypoint *kp2, int n_kp2,
+                     const int32_t *idx, const ss_two_view_params *p, int problem, uint8_t *flag, ss_map_point *points, int32_t *point_rows,
+                     int32_t *n_points, ss_two_view_result *result)
+{
+    if (tv_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!view || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n_kp1 < 0 || n_kp2 < 0 || problem < 0 || !result || !n_points) return SS_ERR_INVALID_ARG;
+    if ((n_kp1 > 0 && (!kp1 || !idx || !flag || !points || !point_rows)) || (n_kp2 > 0 && !kp2)) return SS_ERR_INVALID_ARG;
+    /* step 1 */
+    std::vector<float> corr, s1;
+    std::vector<int32_t> row_of;
+    for (int i = 0; i < n_kp1; i++) {
+        const int j = idx[i], octave = kp1[i].octave;
+        flag[i] = 0;
+        if (!(j >= 0 && j < n_kp2) || !(octave >= 0 && octave < n_levels)) continue;
+        corr.push_back(kp1[i].x), corr.push_back(kp1[i].y), corr.push_back(kp2[j].x), corr.push_back(kp2[j].y);
+        s1.push_back(scale[octave]), row_of.push_back(i);
+    }
+    const int n = (int)row_of.size();
+    std::vector<uint8_t> fl((size_t)n + 1);
+    std::vector<ss_map_point> pts((size_t)n + 1);
+    ss_tv_problem_host(corr.data(), s1.data(), n, ss_tv_cam_of(*view), scale[n_levels - 1], *p, (uint32_t)problem, fl.data(), pts.data(), result);
+    int np = 0;
+    for (int k = 0; k < n; k++) {
+        const int i = row_of[(size_t)k];
+        flag[i] = fl[(size_t)k];
+        if (fl[(size_t)k] == 3) points[np] = pts[(size_t)k], point_rows[2 * np] = i, point_rows[2 * np + 1] = idx[i], np++;
+    }
+    *n_points = np;
+    return SS_OK;
+}
+
+int ss_two_view_model_host(const float *uv, double *h21, double *h12, double *f21, int32_t *ok)
+{
+    if (!uv || !h21 || !h12 || !f21 || !ok) return SS_ERR_INVALID_ARG;
+    const ss_tv_norm nm = ss_tv_normalise_host(uv, SS_TV_DRAWS);
+    ss_tv_model m;
+    memset(&m, 0, sizeof(m));
+    if (ss_tv_norm_ok(nm)) {
+        const int pick[SS_TV_DRAWS] = {0, 1, 2, 3, 4, 5, 6, 7};
+        ss_tv_work_host w;
+        ss_tv_model_of(uv, pick, nm, w, m);
+    }
+    memcpy(h21, m.h21, sizeof(m.h21)), memcpy(h12, m.h12, sizeof(m.h12)), memcpy(f21, m.f21, sizeof(m.f21));
+    ok[0] = m.ok_h, ok[1] = m.ok_f;
+    return SS_OK;
+}
+
+int ss_two_view_check_host(const ss_two_view_params *p, const ss_proj_view *view, const float *uv, int n, const double *h21, const double *h12,
+                           const double *f21, const double *r21, const double *t21, double *chi_h, uint8_t *in_h, double *score_h, double *chi_f,
+                           uint8_t *in_f, double *score_f, uint8_t *good, double *cosv, double *xyz)
+{
+    if (tv_params_error(p)) return SS_ERR_INVALID_ARG;
+    if (!view || n < 0 || (n > 0 && !uv)) return SS_ERR_INVALID_ARG;
+    const bool do_h = h21 && h12, do_f = f21 != nullptr, do_rt = r21 && t21;
+    if ((do_h && (!chi_h || !in_h || !score_h)) || (do_f && (!chi_f || !in_f || !score_f)) || (do_rt && (!good || !cosv || !xyz))) return SS_ERR_INVALID_ARG;
+    auto at = [&](int k, int c) { return (double)uv[4 * k + c]; };
+    if (do_h)
+        *score_h = ss_tv_tree_sum(n, [&](int k) {
+            bool in;
+            const double v = ss_tv_term_h(h21, h12, at(k, 0), at(k, 1), at(k, 2), at(k, 3), p->chi2_h, &in, chi_h + 2 * k);
+            in_h[k] = in ? 1 : 0;
+            return v;
+        });
+    if (do_f)
+        *score_f = ss_tv_tree_sum(n, [&](int k) {
+            bool in;
+            const double v = ss_tv_term_f(f21, at(k, 0), at(k, 1), at(k, 2), at(k, 3), p->chi2_f, p->chi2_score, &in, chi_f + 2 * k);
+            in_f[k] = in ? 1 : 0;
+            return v;
+        });
+    const ss_tv_cam cam = ss_tv_cam_of(*view);
+    for (int k = 0; do_rt && k < n; k++) {
+        ss_tv_point q;
+        const bool g = ss_tv_check_rt(r21, t21, cam, at(k, 0), at(k, 1), at(k, 2), at(k, 3), &q);
+        good[k] = g ? (ss_tv_triangulated(q.cosp) ? 2 : 1) : 0;
+        cosv[k] = q.cosp, xyz[3 * k] = q.X[0], xyz[3 * k + 1] = q.X[1], xyz[3 * k + 2] = q.X[2];
+    }
+    return SS_OK;
+}
+
+int ss_two_view_accept_host(const ss_two_view_params *p, int model, const int32_t *good, int n_hyp, int n_in, double cos_parallax, int32_t *out)
+{
+    if (tv_params_error(p) || !good || !out || (model != 1 && model != 2) || n_hyp < 1 || n_hyp > SS_TV_MAX_HYP || n_in < 0) return SS_ERR_INVALID_ARG;
+    int g[SS_TV_MAX_HYP] = {0}, best, best_good, second_good;
+    for (int k = 0; k < n_hyp; k++) g[k] = good[k];
+    ss_tv_pick(g, n_hyp, &best, &best_good, &second_good);
+    out[0] = ss_tv_accept(model, g, n_hyp, best_good, second_good, n_in, cos_parallax, *p);
+    out[1] = best, out[2] = best_good, out[3] = second_good;
+    return SS_OK;
+}
+
+int ss_two_view_point_tests_host(double cos_parallax, double err_sq, int32_t *out)
+{
+    if (!out) return SS_ERR_INVALID_ARG;
+    out[0] = ss_tv_triangulated(cos_parallax) ? 1 : 0, out[1] = ss_tv_exempt(cos_parallax) ? 1 : 0, out[2] = ss_tv_reprojects(err_sq) ? 1 : 0;
+    return SS_OK;
+}
+
+int ss_two_view_beats_host(double score, int t, double best, int best_t) { return ss_tv_beats(score, t, best, best_t) ? 1 : 0; }
+
+/* The checks the device forms share, the workspace, the host tables (views, then both sides' frame numbers; src2 entries may be -1
+ * when `none_ok`: no frame 2), then the six launches of a call whose device operands and outputs are filled in */
+static int tv_run(ss_ctx *c, ssk_tv_call &g, int n_frames1, int n_frames2, const ss_proj_view *views, const int32_t *src1, const int32_t *src2,
+                  int default2_shift, bool none_ok, const ss_two_view_params *p)
+{
+    if (const char *msg = tv_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_frames1 < 0 || n_frames2 < 0) return fail(c, SS_ERR_INVALID_ARG, "two_view: bad frame count");
+    int rc = pairs_shape(c, "two_view", "problem", g.n_frames, g.rows);
+    if (rc == SS_OK) rc = call_count_ok(c, "two_view", g.n_frames, "problems");
+    if (rc == SS_OK) rc = context_pyramid(c, "two_view", &g.n_levels, g.scale);
+    if (rc != SS_OK) return rc;
+    if (g.n_frames == 0) return SS_OK;
+    if (!views) return fail(c, SS_ERR_INVALID_ARG, "two_view: views is NULL");
+    for (int q = 0; q < g.n_frames; q++) {
+        const int f1 = src1 ? src1[q] : q, f2 = src2 ? src2[q] : q - default2_shift;
+        if (f1 < 0 || f1 >= n_frames1)
+            return fail(c, SS_ERR_INVALID_ARG, std::string(src1 ? "kp1_src[" : "problem [") + std::to_string(q) + "] = " + std::to_string(f1) +
+                                                   " names no frame of side 1 (" + std::to_string(n_frames1) + ")");
+        if ((f2 < (none_ok ? -1 : 0)) || f2 >= n_frames2)
+            return fail(c, SS_ERR_INVALID_ARG, std::string(src2 ? "kp2_src[" : "problem [") + std::to_string(q) + "] = " + std::to_string(f2) +
+                                                   " names no frame of side 2 (" + std::to_string(n_frames2) + ")");
+    }
+    if (!g.kp1 || !g.n1 || !g.kp2 || !g.n2 || !g.idx || !g.flag || !g.points || !g.point_rows || !g.n_points || !g.result)
+        return fail(c, SS_ERR_INVALID_ARG, "two_view: NULL buffer");
+    g.p = *p;
+    const size_t np = (size_t)g.n_frames, nr = np * g.rows, nh = np * g.p.max_iterations;
+    const size_t chunks = ((size_t)g.rows + SS_TV_CHUNK - 1) / SS_TV_CHUNK;
+    rc = carve_from(c, c->d_tv_ws, [&](carve &w) {
+        g.models = w.take<ssk_tv_model>(nh * sizeof(ssk_tv_model));
+        g.partial = w.take<double>(nh * chunks * 2 * sizeof(double));
+        g.choice = w.take<ssk_tv_choice>(np * sizeof(ssk_tv_choice));
+        g.corr = w.take<float>(4 * nr * sizeof(float));
+        g.corr_of_row = w.take<int32_t>(nr * sizeof(int32_t));
+        g.n_corr = w.take<int32_t>(np * sizeof(int32_t));
+        g.corr_flag = w.take<uint8_t>(nr);
+    });
+    if (rc != SS_OK) return rc;
+    const size_t vb = np * sizeof(ss_proj_view), sb = np * sizeof(int32_t);
+    rc = staged_upload(c, c->tv_tab, vb + 2 * sb, [&](uint8_t *h) {
+        memcpy(h, views, vb);
+        int32_t *s1 = (int32_t *)(h + vb), *s2 = (int32_t *)(h + vb + sb);
+        for (int q = 0; q < g.n_frames; q++) s1[q] = src1 ? src1[q] : q, s2[q] = src2 ? src2[q] : q - default2_shift;
+    });
+    if (rc != SS_OK) return rc;
+    g.views = c->tv_tab.as<ss_proj_view>();
+    g.kp1_src = c->tv_tab.as<int32_t>(vb), g.kp2_src = c->tv_tab.as<int32_t>(vb + sb);
+    const int64_t T = g.p.max_iterations, hb = (T + SSK_TV_HYP_BLOCK - 1) / SSK_TV_HYP_BLOCK;
+    {
+        /* per row: its match and the number written; a correspondence reads two keypoints and writes its four floats, which the two
+         * sums of the normalisation then read twice */
+        stage_timer t(c, "tv_gather", (int64_t)nr * (4 + 4 + 2 * (int64_t)sizeof(ss_keypoint) + 16 + 32) + (int64_t)np * (int64_t)sizeof(ssk_tv_choice));
+        ssk_tv_gather(c->stream, g);
+    }
+    {
+        /* per hypothesis: eight correspondences' four floats read, one record written */
+        stage_timer t(c, "tv_model", (int64_t)nh * (SS_TV_DRAWS * 16 + (int64_t)sizeof(ssk_tv_model)));
+        ssk_tv_model_launch(c->stream, g);
+    }
+    {
+        /* every block of hypotheses reads the four floats of every correspondence once and its own records per chunk; two partial
+         * sums per chunk and hypothesis are written */
+        stage_timer t(c, "tv_score", (int64_t)nr * 16 * hb + (int64_t)nh * (int64_t)chunks * ((int64_t)sizeof(ssk_tv_model) + 16));
+        ssk_tv_score(c->stream, g);
+    }
+    {
+        /* the partial sums and the records' flags read; per correspondence its four floats read and its flag written */
+        stage_timer t(c, "tv_select", (int64_t)nh * ((int64_t)chunks * 16 + 8) + (int64_t)nr * (16 + 1) + (int64_t)np * (int64_t)(sizeof(ssk_tv_model) + sizeof(ssk_tv_choice)));
+        ssk_tv_select(c->stream, g);
+    }
+    {
+        /* per correspondence its flag and four floats; the hypotheses and counts per workgroup */
+        stage_timer t(c, "tv_check", (int64_t)nr * (16 + 1) + (int64_t)np * (int64_t)chunks * (int64_t)sizeof(ssk_tv_choice));
+        ssk_tv_check(c->stream, g);
+    }
+    {
+        /* twice per correspondence its flag and four floats; per row its number, match and octave read, its flag written, and up to
+         * one point and its two rows */
+        stage_timer t(c, "tv_finish", (int64_t)nr * (2 * (16 + 1) + 4 + 4 + (int64_t)sizeof(ss_keypoint) + 1 + (int64_t)sizeof(ss_map_point) + 8) +
+                                          (int64_t)np * (int64_t)(sizeof(ssk_tv_choice) + sizeof(ss_two_view_result) + 4));
+        ssk_tv_finish(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_two_view_pairs_device(ss_ctx *c, const void *d_kp1, const void *d_n_kp1, int n_frames1, const void *d_kp2, const void *d_n_kp2, int n_frames2,
+                             int rows_per_frame, const void *d_idx, int n_problems, const ss_proj_view *views, const int32_t *kp1_src,
+                             const int32_t *kp2_src, const ss_two_view_params *p, void *d_flag, void *d_points, void *d_point_rows, void *d_n_points,
+                             void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    ssk_tv_call g;
+    g.n_frames = n_problems, g.rows = rows_per_frame;
+    g.kp1 = (const ss_keypoint *)d_kp1, g.n1 = (const int32_t *)d_n_kp1, g.kp2 = (const ss_keypoint *)d_kp2, g.n2 = (const int32_t *)d_n_kp2;
+    g.idx = (const int32_t *)d_idx;
+    g.flag = (uint8_t *)d_flag, g.points = (ss_map_point *)d_points, g.point_rows = (int32_t *)d_point_rows, g.n_points = (int32_t *)d_n_points;
+    g.result = (ss_two_view_result *)d_result;
+    return tv_run(c, g, n_frames1, n_frames2, views, kp1_src, kp2_src, 0, false, p);
+}
+
+int ss_two_view_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_idx, int n_problems, const ss_proj_view *views,
+                             const ss_two_view_params *p, void *d_flag, void *d_points, void *d_point_rows, void *d_n_points, void *d_result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_two_view_batch_device")) return SS_ERR_STATE;
+    if (n_problems != c->last_n_frames) return fail(c, SS_ERR_INVALID_ARG, "two_view: n_problems must be the batch's frame count");
+    ssk_tv_call g;
+    g.n_frames = n_problems, g.rows = c->hg.kcap;
+    g.kp1 = g.kp2 = c->ws.kps, g.n1 = g.n2 = c->ws.n_kp;
+    const int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
+    g.idx = (const int32_t *)d_idx;
+    g.flag = (uint8_t *)d_flag, g.points = (ss_map_point *)d_points, g.point_rows = (int32_t *)d_point_rows, g.n_points = (int32_t *)d_n_points;
+    g.result = (ss_two_view_result *)d_result;
+    return tv_run(c, g, c->last_n_frames, c->last_n_frames, views, nullptr, train_src, 1, true, p);
+}
+
+int ss_two_view(ss_ctx *c, const ss_proj_view *view, const ss_keypoint *kp1, int n_kp1, const ss_keypoint *kp2, int n_kp2, const int32_t *idx,
+                const ss_two_view_params *p, uint8_t *flag, ss_map_point *points, int32_t *point_rows, int32_t *n_points, ss_two_view_result *result)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = tv_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_kp1 < 0 || n_kp2 < 0 || n_kp1 > SS_GUIDED_MAX_ROWS || n_kp2 > SS_GUIDED_MAX_ROWS)
+        return fail(c, SS_ERR_INVALID_ARG, "two_view: n_kp1 and n_kp2 must be 0 .. SS_GUIDED_MAX_ROWS");
+    if (!view || !result || !n_points || (n_kp1 > 0 && (!kp1 || !idx || !flag || !points || !point_rows)) || (n_kp2 > 0 && !kp2))
+        return fail(c, SS_ERR_INVALID_ARG, "two_view: NULL buffer");
+    /* one frame of `rows` rows on each side; `counts` is on this stack: no return before the stream has read it.  The points and
+     * their rows come back whole: rows from n_points on hold what the device buffer held */
+    const size_t rows = (size_t)std::max(std::max(n_kp1, n_kp2), 1), n1 = (size_t)n_kp1, n2 = (size_t)n_kp2, kb = sizeof(ss_keypoint);
+    const int32_t counts[2] = {n_kp1, n_kp2};
+    std::vector<ss_map_point> pts(rows);
+    std::vector<int32_t> prow(2 * rows);
+    enum { K1, K2, IDX, N, FL, PT, PR, NP, RES, PIECES };
+    io_piece io[PIECES] = {{kp1, nullptr, rows * kb, n1 * kb}, {kp2, nullptr, rows * kb, n2 * kb}, {idx, nullptr, rows * 4, n1 * 4},
+                           {counts, nullptr, sizeof(counts), sizeof(counts)}, {nullptr, flag, rows, n1},
+                           {nullptr, pts.data(), rows * sizeof(ss_map_point), rows * sizeof(ss_map_point)}, {nullptr, prow.data(), rows * 8, rows * 8},
+                           {nullptr, n_points, 4, 4}, {nullptr, result, sizeof(ss_two_view_result), sizeof(ss_two_view_result)}};
+    int rc = io_send(c, c->d_tv_io, io, PIECES);
+    if (rc == SS_OK)
+        rc = ss_two_view_pairs_device(c, io[K1].d, io[N].d, 1, io[K2].d, io[N].d + 4, 1, (int)rows, io[IDX].d, 1, view, nullptr, nullptr, p, io[FL].d,
+                                      io[PT].d, io[PR].d, io[NP].d, io[RES].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    rc = io_fetch(c, io, PIECES);
+    if (rc != SS_OK) return rc;
+    const int np = std::min(std::max(*n_points, 0), n_kp1);
+    for (int k = 0; k < np; k++) points[k] = pts[(size_t)k], point_rows[2 * k] = prow[2 * (size_t)k], point_rows[2 * k + 1] = prow[2 * (size_t)k + 1];
+    return SS_OK;
 }
 
 } /* extern "C" */

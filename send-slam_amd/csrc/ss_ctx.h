@@ -172,6 +172,10 @@ struct ss_ctx {
      * call (views, then frame numbers, then block numbers) */
     dev_buf<uint8_t> d_pnp_ws, d_pnp_io;
     staged_table pnp_tab;
+    /* two-view initialisation: the workspace of a call (correspondences, models, partial sums, choices), the host form's device
+     * copies, the tables of a call (views, then both sides' frame numbers) */
+    dev_buf<uint8_t> d_tv_ws, d_tv_io;
+    staged_table tv_tab;
     /* rectification: map map_id in its fixed-point form (one allocation each: the xy array, then ab; d == NULL: unset) and the
      * 16-byte aligned buffer ss_extract_stereo_raw remaps both eyes into */
     struct rect_map {

@@ -89,6 +89,41 @@ template <int P, int Q> SS_HD void ss_tri_rotate(double (&M)[4][4], double (&V)[
     }
 }
 
+/* the smallest eigenvector of A^T A for the four rows of A: the upper triangle of M, each entry the sum of its four products in
+ * row order, mirrored; SS_TRI_SWEEPS sweeps of cyclic Jacobi; the column of the smallest diagonal entry, the first among equals.
+ * ss_tri_eval and the two-view CheckRT (ss_two_view_steps.h) triangulate with it */
+SS_HD void ss_tri_null4(const double (&A)[4][4], double v[4])
+{
+    double M[4][4], V[4][4];
+    SS_EPI_UNROLL
+    for (int i = 0; i < 4; i++) {
+        SS_EPI_UNROLL
+        for (int j = 0; j < 4; j++) {
+            if (j >= i) M[i][j] = ((A[0][i] * A[0][j] + A[1][i] * A[1][j]) + A[2][i] * A[2][j]) + A[3][i] * A[3][j];
+            V[i][j] = i == j ? 1.0 : 0.0;
+        }
+    }
+    M[1][0] = M[0][1], M[2][0] = M[0][2], M[3][0] = M[0][3], M[2][1] = M[1][2], M[3][1] = M[1][3], M[3][2] = M[2][3];
+    SS_EPI_ROLLED
+    for (int sweep = 0; sweep < SS_TRI_SWEEPS; sweep++) {
+        ss_tri_rotate<0, 1>(M, V);
+        ss_tri_rotate<0, 2>(M, V);
+        ss_tri_rotate<0, 3>(M, V);
+        ss_tri_rotate<1, 2>(M, V);
+        ss_tri_rotate<1, 3>(M, V);
+        ss_tri_rotate<2, 3>(M, V);
+    }
+    int best = 0;
+    double low = M[0][0];
+    if (M[1][1] < low) best = 1, low = M[1][1];
+    if (M[2][2] < low) best = 2, low = M[2][2];
+    if (M[3][3] < low) best = 3, low = M[3][3];
+    v[0] = best == 0 ? V[0][0] : best == 1 ? V[0][1] : best == 2 ? V[0][2] : V[0][3];
+    v[1] = best == 0 ? V[1][0] : best == 1 ? V[1][1] : best == 2 ? V[1][2] : V[1][3];
+    v[2] = best == 0 ? V[2][0] : best == 1 ? V[2][1] : best == 2 ? V[2][2] : V[2][3];
+    v[3] = best == 0 ? V[3][0] : best == 1 ? V[3][1] : best == 2 ? V[3][2] : V[3][3];
+}
+
 SS_HD ss_tri_out ss_tri_rejected(int state, double cosp, double e1, double e2)
 {
     ss_tri_out o;
@@ -118,7 +153,7 @@ SS_HD ss_tri_out ss_tri_eval(const ss_epi_pair &w, const ss_tri_params &tp, cons
     const double cosp = dot / (l1 * l2);
     if (!(cosp > 0.0 && cosp < tp.cos_parallax_max)) return ss_tri_rejected(1, cosp, 0.0, 0.0);
     /* 2 */
-    double A[4][4], M[4][4], V[4][4];
+    double A[4][4], v[4];
     SS_EPI_UNROLL
     for (int c = 0; c < 4; c++) {
         const double p10 = c < 3 ? R1[c] : t1[0], p11 = c < 3 ? R1[3 + c] : t1[1], p12 = c < 3 ? R1[6 + c] : t1[2];
@@ -128,33 +163,8 @@ SS_HD ss_tri_out ss_tri_eval(const ss_epi_pair &w, const ss_tri_params &tp, cons
         A[2][c] = a2 * p22 - p20;
         A[3][c] = b2 * p22 - p21;
     }
-    SS_EPI_UNROLL
-    for (int i = 0; i < 4; i++) {
-        SS_EPI_UNROLL
-        for (int j = 0; j < 4; j++) {
-            if (j >= i) M[i][j] = ((A[0][i] * A[0][j] + A[1][i] * A[1][j]) + A[2][i] * A[2][j]) + A[3][i] * A[3][j];
-            V[i][j] = i == j ? 1.0 : 0.0;
-        }
-    }
-    M[1][0] = M[0][1], M[2][0] = M[0][2], M[3][0] = M[0][3], M[2][1] = M[1][2], M[3][1] = M[1][3], M[3][2] = M[2][3];
-    SS_EPI_ROLLED
-    for (int sweep = 0; sweep < SS_TRI_SWEEPS; sweep++) {
-        ss_tri_rotate<0, 1>(M, V);
-        ss_tri_rotate<0, 2>(M, V);
-        ss_tri_rotate<0, 3>(M, V);
-        ss_tri_rotate<1, 2>(M, V);
-        ss_tri_rotate<1, 3>(M, V);
-        ss_tri_rotate<2, 3>(M, V);
-    }
-    int best = 0;
-    double low = M[0][0];
-    if (M[1][1] < low) best = 1, low = M[1][1];
-    if (M[2][2] < low) best = 2, low = M[2][2];
-    if (M[3][3] < low) best = 3, low = M[3][3];
-    const double v0 = best == 0 ? V[0][0] : best == 1 ? V[0][1] : best == 2 ? V[0][2] : V[0][3];
-    const double v1 = best == 0 ? V[1][0] : best == 1 ? V[1][1] : best == 2 ? V[1][2] : V[1][3];
-    const double v2 = best == 0 ? V[2][0] : best == 1 ? V[2][1] : best == 2 ? V[2][2] : V[2][3];
-    const double v3 = best == 0 ? V[3][0] : best == 1 ? V[3][1] : best == 2 ? V[3][2] : V[3][3];
+    ss_tri_null4(A, v);
+    const double v0 = v[0], v1 = v[1], v2 = v[2], v3 = v[3];
     if (!(fabs(v3) <= 1.7976931348623157e308 && v3 != 0.0)) return ss_tri_rejected(2, cosp, 0.0, 0.0);
     const double X0 = v0 / v3, X1 = v1 / v3, X2 = v2 / v3;
     /* 3, 4 */

@@ -457,6 +457,60 @@ void ssk_pnp_gather(hipStream_t s, const ssk_pnp_call &g);
 void ssk_pnp_model_launch(hipStream_t s, const ssk_pnp_call &g);
 void ssk_pnp_count(hipStream_t s, const ssk_pnp_call &g);
 void ssk_pnp_finish(hipStream_t s, const ssk_pnp_call &g);
+/* ss_two_view.hip: two-view initialisation (DESIGN.md "Two-view initialisation").  Problem q solves the matches idx[q][i] of the rows
+ * of frame kp1_src[q] with the rows of frame kp2_src[q] (< 0: no frame 2).  gather (one workgroup per problem, SSK_TV_GATHER_ROWS rows at a
+ * time in ascending order) numbers the correspondences, writes their four floats as a structure of arrays (corr: 4 planes of
+ * [n_frames][rows]: u1 v1 u2 v2), the number of every row's correspondence (corr_of_row, -1: none), N and the normalisation; model
+ * (one lane per problem and hypothesis) writes one ssk_tv_model; score (a lane per correspondence, SS_TV_CHUNK of them and
+ * SSK_TV_HYP_BLOCK hypotheses per workgroup) writes both scores' partial sums per (chunk, hypothesis); select (one workgroup per
+ * problem) adds them, picks both winners and the model, flags its inliers and decomposes it; check (a lane per correspondence)
+ * counts the good points of every motion hypothesis; finish (one workgroup per problem) accepts and writes flags, points and result */
+#define SSK_TV_GATHER_ROWS 1024
+#define SSK_TV_HYP_BLOCK 32
+struct alignas(16) ssk_tv_model { /* 256 bytes */
+    double h21[9], h12[9], f21[9];
+    int32_t ok_h, ok_f;
+    double pad[4];
+};
+struct alignas(8) ssk_tv_choice { /* per problem, select -> check and finish */
+    double hyp[12 * 8];
+    double norm[8];       /* m[4], d[4] */
+    double score_h, score_f;
+    int32_t norm_ok, model, n_hyp, reason, n_in, t_h, t_f, pad;
+    int32_t good[8];
+};
+struct ssk_tv_call {
+    int n_frames = 0, rows = 0; /* n_frames: the problems of the call */
+    const ss_keypoint *kp1 = nullptr, *kp2 = nullptr; /* [frames][rows] */
+    const int32_t *n1 = nullptr, *n2 = nullptr;
+    const int32_t *frame_error = nullptr; /* per frame of either side (the batch form), or NULL */
+    const int32_t *kp1_src = nullptr, *kp2_src = nullptr; /* device int32 [n_frames] each */
+    const ss_proj_view *views = nullptr;  /* device [n_frames] */
+    const int32_t *idx = nullptr;         /* [n_frames][rows] */
+    ss_two_view_params p = {};
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    /* workspace */
+    float *corr = nullptr;          /* 4 planes */
+    int32_t *corr_of_row = nullptr; /* [n_frames][rows] */
+    uint8_t *corr_flag = nullptr;   /* [n_frames][rows], by correspondence: 1 an inlier of the chosen model */
+    int32_t *n_corr = nullptr;      /* [n_frames] */
+    ssk_tv_model *models = nullptr; /* [n_frames][max_iterations] */
+    double *partial = nullptr;      /* [n_frames][chunks][max_iterations][2] */
+    ssk_tv_choice *choice = nullptr; /* [n_frames] */
+    /* outputs */
+    uint8_t *flag = nullptr;        /* [n_frames][rows] */
+    ss_map_point *points = nullptr; /* [n_frames][rows] */
+    int32_t *point_rows = nullptr;  /* [n_frames][rows][2] */
+    int32_t *n_points = nullptr;
+    ss_two_view_result *result = nullptr;
+};
+void ssk_tv_gather(hipStream_t s, const ssk_tv_call &g);
+void ssk_tv_model_launch(hipStream_t s, const ssk_tv_call &g);
+void ssk_tv_score(hipStream_t s, const ssk_tv_call &g);
+void ssk_tv_select(hipStream_t s, const ssk_tv_call &g);
+void ssk_tv_check(hipStream_t s, const ssk_tv_call &g);
+void ssk_tv_finish(hipStream_t s, const ssk_tv_call &g);
 /* ss_sim3opt.hip: Sim3 refinement (DESIGN.md "Sim3 refinement").  Pair b as for ssk_sim3_call, and start[b], the model it starts
  * from.  gather (one workgroup per pair, SSK_SIM3OPT_CHUNK rows at a time in ascending order) numbers the correspondences, writes
  * their twelve floats as a structure of arrays (planes: 12 of [n_frames][rows]: X1, X2, both keypoints, both scales), the query row

@@ -63,18 +63,18 @@ SS_HD void ss_pnp_bearing(float u, float v, const ss_pnp_cam &c, double b[3])
 
 SS_HD int ss_pnp_tri(int i, int j) { return i * (i + 1) / 2 + j; }
 
-/* Cholesky by columns over the packed lower triangle, every inner sum subtracting in ascending k (ss_gn_chol_n's order).  False
- * when a pivot is not > 0 */
-template <class W> SS_HD bool ss_pnp_chol(W &w)
+/* Cholesky by columns over the packed lower triangle of order N, every inner sum subtracting in ascending k (ss_gn_chol_n's order).
+ * False when a pivot is not > 0.  The two-view models (ss_two_view_steps.h) run it at order 9 */
+template <int N, class W> SS_HD bool ss_tri_chol(W &w)
 {
     bool ok = true;
-    for (int j = 0; j < SS_PNP_UNKNOWNS; j++) {
+    for (int j = 0; j < N; j++) {
         double s = w.at(ss_pnp_tri(j, j));
         for (int k = 0; k < j; k++) s = s - w.at(ss_pnp_tri(j, k)) * w.at(ss_pnp_tri(j, k));
         ok = ok && s > 0.0;
         const double d = sqrt(s);
         w.at(ss_pnp_tri(j, j)) = d;
-        for (int i = j + 1; i < SS_PNP_UNKNOWNS; i++) {
+        for (int i = j + 1; i < N; i++) {
             double v = w.at(ss_pnp_tri(i, j));
             for (int k = 0; k < j; k++) v = v - w.at(ss_pnp_tri(i, k)) * w.at(ss_pnp_tri(j, k));
             w.at(ss_pnp_tri(i, j)) = v / d;
@@ -83,25 +83,29 @@ template <class W> SS_HD bool ss_pnp_chol(W &w)
     return ok;
 }
 
-/* one inverse iteration on the factor: x <- L^-T L^-1 x (ss_gn_subst_n's order), then x / sqrt(the sequential sum of squares) */
-template <class W> SS_HD void ss_pnp_inverse_step(W &w)
+/* one inverse iteration on the factor of order N, the vector behind the triangle: x <- L^-T L^-1 x (ss_gn_subst_n's order), then
+ * x / sqrt(the sequential sum of squares) */
+template <int N, class W> SS_HD void ss_tri_inverse_step(W &w)
 {
-    const int X = SS_PNP_TRI;
-    for (int i = 0; i < SS_PNP_UNKNOWNS; i++) {
+    const int X = N * (N + 1) / 2;
+    for (int i = 0; i < N; i++) {
         double v = w.at(X + i);
         for (int k = 0; k < i; k++) v = v - w.at(ss_pnp_tri(i, k)) * w.at(X + k);
         w.at(X + i) = v / w.at(ss_pnp_tri(i, i));
     }
-    for (int i = SS_PNP_UNKNOWNS - 1; i >= 0; i--) {
+    for (int i = N - 1; i >= 0; i--) {
         double v = w.at(X + i);
-        for (int k = i + 1; k < SS_PNP_UNKNOWNS; k++) v = v - w.at(ss_pnp_tri(k, i)) * w.at(X + k);
+        for (int k = i + 1; k < N; k++) v = v - w.at(ss_pnp_tri(k, i)) * w.at(X + k);
         w.at(X + i) = v / w.at(ss_pnp_tri(i, i));
     }
     double s = w.at(X) * w.at(X);
-    for (int k = 1; k < SS_PNP_UNKNOWNS; k++) s = s + w.at(X + k) * w.at(X + k);
+    for (int k = 1; k < N; k++) s = s + w.at(X + k) * w.at(X + k);
     const double n = sqrt(s);
-    for (int k = 0; k < SS_PNP_UNKNOWNS; k++) w.at(X + k) = w.at(X + k) / n;
+    for (int k = 0; k < N; k++) w.at(X + k) = w.at(X + k) / n;
 }
+
+template <class W> SS_HD bool ss_pnp_chol(W &w) { return ss_tri_chol<SS_PNP_UNKNOWNS>(w); }
+template <class W> SS_HD void ss_pnp_inverse_step(W &w) { ss_tri_inverse_step<SS_PNP_UNKNOWNS>(w); }
 
 /* Step 3b.  X[3i ..], uv[2i ..]: draw i.  The unknowns are the columns c1 c2 c3 of R^ and t^: unknown 3a + r is component r of
  * column a (a = 3: t^).  With d_i = (X_i - O, 1) and P_i = I - b_i b_i^T, entry (3a + r, 3b + c) of H is the sum over the draws, in

@@ -54,7 +54,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_local_ba_batch_device", "ss_local_ba", "ss_local_ba_points_to_block", "ss_pnp_host", "ss_pnp_model_host", "ss_pnp_check_host",
            "ss_pnp_pairs_device", "ss_pnp_batch_device", "ss_pnp", "ss_pose_graph_host", "ss_pose_graph_edge_host", "ss_graph_atan2_host",
            "ss_graph_ln_host", "ss_pose_graph_device", "ss_pose_graph", "ss_pose_graph_points_device", "ss_global_ba_host",
-           "ss_global_ba_obs_from_idx_host", "ss_global_ba_device", "ss_global_ba"]
+           "ss_global_ba_obs_from_idx_host", "ss_global_ba_device", "ss_global_ba", "ss_two_view_host", "ss_two_view_model_host",
+           "ss_two_view_check_host", "ss_two_view_accept_host", "ss_two_view_beats_host", "ss_two_view_point_tests_host", "ss_two_view_pairs_device", "ss_two_view_batch_device", "ss_two_view"]
 
 
 class OrbParams(C.Structure):
@@ -582,6 +583,116 @@ def pnp_check_host(params: PnpParams, view, scale, points, kp, model):
     if rc != SS_OK:
         raise OrbError(rc, "ss_pnp_check_host refused its arguments")
     return out, err
+
+
+# ---- two-view initialisation (the rule: include/sendslam_orb.h) ----
+SS_TWO_VIEW_MAX_ITERATIONS = 1024
+SS_TWO_VIEW_COS_1DEG = 0.9998476951563913
+
+
+class TwoViewParams(C.Structure):
+    _fields_ = [("chi2_h", C.c_double), ("chi2_f", C.c_double), ("chi2_score", C.c_double), ("rh_threshold", C.c_double),
+                ("cos_min_parallax", C.c_double), ("min_triangulated", C.c_int32), ("max_iterations", C.c_int32), ("seed", C.c_uint32),
+                ("reserved", C.c_int32 * 3)]
+
+
+# ss_two_view_result: one per problem
+TWO_VIEW_RESULT_DTYPE = np.dtype([("r21", "<f8", (9,)), ("t21", "<f8", (3,)), ("score_h", "<f8"), ("score_f", "<f8"), ("cos_parallax", "<f8")] +
+                                 [(n, "<i4") for n in ("state", "reason", "status", "model", "iteration_h", "iteration_f", "n_corr", "n_inliers",
+                                                       "n_good", "n_triangulated")] + [("reserved", "<i4", (8,))])
+
+
+def two_view_params(chi2_h: float = 5.991, chi2_f: float = 3.841, chi2_score: float = 5.991, rh_threshold: float = 0.45,
+                    cos_min_parallax: float = SS_TWO_VIEW_COS_1DEG, min_triangulated: int = 50, max_iterations: int = 200, seed: int = 0,
+                    reserved=(0, 0, 0)) -> TwoViewParams:
+    """upstream's TwoViewReconstruction(K, 1.0, 200) with its thresholds; rh_threshold is ss_track's 0.45 (upstream's source: 0.50)"""
+    return TwoViewParams(chi2_h=chi2_h, chi2_f=chi2_f, chi2_score=chi2_score, rh_threshold=rh_threshold, cos_min_parallax=cos_min_parallax,
+                         min_triangulated=min_triangulated, max_iterations=max_iterations, seed=seed & 0xFFFFFFFF,
+                         reserved=(C.c_int32 * 3)(*reserved))
+
+
+def _two_view_arrays(view, kp1, kp2, idx):
+    """the host arrays of one problem, checked -> (v, k1, k2, ix, n1, n2)"""
+    v = _views_array(view)
+    k1, k2 = np.ascontiguousarray(kp1, KP_DTYPE), np.ascontiguousarray(kp2, KP_DTYPE)
+    ix = np.ascontiguousarray(idx, np.int32)
+    if len(v) != 1 or len(ix) != len(k1):
+        raise ValueError("one view; one match per row of frame 1")
+    return v, k1, k2, ix, len(k1), len(k2)
+
+
+def _two_view_outputs(n1):
+    return (np.empty(n1, np.uint8), np.zeros(n1, MAP_POINT_DTYPE), np.full((n1, 2), -1, np.int32), np.zeros(1, np.int32),
+            np.zeros(1, TWO_VIEW_RESULT_DTYPE))
+
+
+def two_view_host(view, scale, kp1: np.ndarray, kp2: np.ndarray, idx: np.ndarray, params: TwoViewParams, problem: int = 0):
+    """ss_two_view_host: the whole rule on the host for one problem -> (uint8 flag per row of frame 1, the triangulated MAP_POINT_DTYPE
+    points, their int32 rows (i, j), one TWO_VIEW_RESULT_DTYPE record); needs no device"""
+    v, k1, k2, ix, n1, n2 = _two_view_arrays(view, kp1, kp2, idx)
+    sc = np.ascontiguousarray(scale, np.float32)
+    flag, pts, rows, n_pts, res = _two_view_outputs(n1)
+    ptr = lambda a, n: a.ctypes.data if n else None  # noqa: E731
+    rc = load().ss_two_view_host(v.ctypes.data, sc.ctypes.data, len(sc), ptr(k1, n1), n1, ptr(k2, n2), n2, ptr(ix, n1), C.byref(params), problem,
+                                 ptr(flag, n1), ptr(pts, n1), ptr(rows, n1), n_pts.ctypes.data, res.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_two_view_host refused its arguments")
+    return flag, pts[:n_pts[0]], rows[:n_pts[0]], res[0]
+
+
+def two_view_model_host(uv):
+    """ss_two_view_model_host: steps 2 and 3 of one octuple (8 x 4 float32: u1 v1 u2 v2) normalised by itself -> (H21, H12, F21 as 3 x 3
+    float64, (ok_h, ok_f)); needs no device"""
+    a = np.ascontiguousarray(uv, np.float32).reshape(32)
+    h21, h12, f21, ok = np.zeros(9), np.zeros(9), np.zeros(9), np.zeros(2, np.int32)
+    rc = load().ss_two_view_model_host(a.ctypes.data, h21.ctypes.data, h12.ctypes.data, f21.ctypes.data, ok.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_two_view_model_host refused its arguments")
+    return h21.reshape(3, 3), h12.reshape(3, 3), f21.reshape(3, 3), (int(ok[0]), int(ok[1]))
+
+
+def two_view_check_host(params: TwoViewParams, view, uv, h21=None, h12=None, f21=None, r21=None, t21=None) -> dict:
+    """ss_two_view_check_host: steps 4 and 8 of n correspondences (n x 4 float32) under the models and the motion given -> a dict of
+    chi_h / in_h / score_h, chi_f / in_f / score_f, good / cos / xyz for whichever were given; needs no device"""
+    v = _views_array(view)
+    a = np.ascontiguousarray(uv, np.float32).reshape(-1, 4)
+    n = len(a)
+    f8 = lambda m, k: None if m is None else np.ascontiguousarray(m, np.float64).reshape(k)  # noqa: E731
+    h21, h12, f21, r21, t21 = f8(h21, 9), f8(h12, 9), f8(f21, 9), f8(r21, 9), f8(t21, 3)
+    out = {"chi_h": np.zeros((n, 2)), "in_h": np.zeros(n, np.uint8), "score_h": np.zeros(1), "chi_f": np.zeros((n, 2)),
+           "in_f": np.zeros(n, np.uint8), "score_f": np.zeros(1), "good": np.zeros(n, np.uint8), "cos": np.zeros(n), "xyz": np.zeros((n, 3))}
+    ptr = lambda m: None if m is None else m.ctypes.data  # noqa: E731
+    rc = load().ss_two_view_check_host(C.byref(params), v.ctypes.data, a.ctypes.data if n else None, n, ptr(h21), ptr(h12), ptr(f21), ptr(r21),
+                                       ptr(t21), *[out[k].ctypes.data for k in ("chi_h", "in_h", "score_h", "chi_f", "in_f", "score_f", "good",
+                                                                                 "cos", "xyz")])
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_two_view_check_host refused its arguments")
+    out["score_h"], out["score_f"] = float(out["score_h"][0]), float(out["score_f"][0])
+    return out
+
+
+def two_view_accept_host(params: TwoViewParams, model: int, good, n_in: int, cos_parallax: float):
+    """ss_two_view_accept_host: steps 8 and 9 on the hypotheses' counts -> (reason, best hypothesis, its count, the second count)"""
+    g = np.ascontiguousarray(good, np.int32)
+    out = np.zeros(4, np.int32)
+    rc = load().ss_two_view_accept_host(C.byref(params), model, g.ctypes.data, len(g), n_in, C.c_double(cos_parallax), out.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_two_view_accept_host refused its arguments")
+    return tuple(int(v) for v in out)
+
+
+def two_view_beats_host(score: float, t: int, best: float, best_t: int) -> bool:
+    """ss_two_view_beats_host: step 5's order"""
+    return bool(load().ss_two_view_beats_host(C.c_double(score), t, C.c_double(best), best_t))
+
+
+def two_view_point_tests_host(cos_parallax: float, err_sq: float):
+    """ss_two_view_point_tests_host: step 8's tests on numbers -> (triangulated, exempt from the depth tests, within 4 sigma^2)"""
+    out = np.zeros(3, np.int32)
+    rc = load().ss_two_view_point_tests_host(C.c_double(cos_parallax), C.c_double(err_sq), out.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_two_view_point_tests_host refused its arguments")
+    return tuple(bool(v) for v in out)
 
 
 # ---- local bundle adjustment (the rule: include/sendslam_orb.h) ----
@@ -1122,6 +1233,18 @@ def load():
     lib.ss_pnp_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + \
                                        [C.POINTER(PnpParams)] + [C.c_void_p] * 2
     lib.ss_pnp.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PnpParams), C.c_void_p, C.c_void_p]
+    lib.ss_two_view_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                     C.POINTER(TwoViewParams), C.c_int] + [C.c_void_p] * 5
+    lib.ss_two_view_model_host.argtypes = [C.c_void_p] * 5
+    lib.ss_two_view_check_host.argtypes = [C.POINTER(TwoViewParams), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 14
+    lib.ss_two_view_accept_host.argtypes = [C.POINTER(TwoViewParams), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]
+    lib.ss_two_view_point_tests_host.argtypes = [C.c_double, C.c_double, C.c_void_p]
+    lib.ss_two_view_beats_host.argtypes = [C.c_double, C.c_int, C.c_double, C.c_int]
+    lib.ss_two_view_pairs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TwoViewParams)] + [C.c_void_p] * 5
+    lib.ss_two_view_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TwoViewParams)] + [C.c_void_p] * 5
+    lib.ss_two_view.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(TwoViewParams)] + \
+        [C.c_void_p] * 5
     lib.ss_pose_opt_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                      C.c_void_p, C.POINTER(PoseOptParams), C.c_void_p, C.c_void_p]
     lib.ss_pose_opt_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int] + \
@@ -2008,6 +2131,45 @@ class OrbContext:
         self._check(self._lib.ss_pnp(self._h, v.ctypes.data, ptr(pts, n_p), ptr(skip, n_p), n_p, ptr(k, n_k), n_k, ptr(ix, n_k), C.byref(params),
                                      ptr(inlier, n_k), res.ctypes.data))
         return inlier, res[0]
+
+    # ---- two-view initialisation: a pose and points from two frames' matches (the rule: include/sendslam_orb.h) ----
+    def two_view_pairs_device(self, d_kp1: int, d_n_kp1: int, n_frames1: int, d_kp2: int, d_n_kp2: int, n_frames2: int, rows_per_frame: int,
+                              d_idx: int, n_problems: int, views, params: TwoViewParams, d_flag: int, d_points: int, d_point_rows: int,
+                              d_n_points: int, d_result: int, kp1_src=None, kp2_src=None):
+        """n_problems problems on device arrays: keypoints KP_DTYPE [n_frames][rows_per_frame] with counts on both sides, d_idx as
+        match_guided_pairs_device wrote it; views one per problem, kp1_src and kp2_src host tables or None (problem q reads frame q); d_flag
+        uint8 [n_problems][rows_per_frame], d_points MAP_POINT_DTYPE and d_point_rows int32 x 2 of the same shape, d_n_points int32
+        [n_problems], d_result TWO_VIEW_RESULT_DTYPE [n_problems]; asynchronous."""
+        v = _views_array(views)
+        s1 = None if kp1_src is None else np.ascontiguousarray(kp1_src, np.int32)
+        s2 = None if kp2_src is None else np.ascontiguousarray(kp2_src, np.int32)
+        if len(v) != n_problems or (s1 is not None and len(s1) != n_problems) or (s2 is not None and len(s2) != n_problems):
+            raise ValueError("one view and one frame number of each side per problem")
+        self._check(self._lib.ss_two_view_pairs_device(self._h, C.c_void_p(d_kp1), C.c_void_p(d_n_kp1), n_frames1, C.c_void_p(d_kp2),
+                                                       C.c_void_p(d_n_kp2), n_frames2, rows_per_frame, C.c_void_p(d_idx), n_problems,
+                                                       v.ctypes.data if n_problems else None, None if s1 is None else s1.ctypes.data,
+                                                       None if s2 is None else s2.ctypes.data, C.byref(params), C.c_void_p(d_flag),
+                                                       C.c_void_p(d_points), C.c_void_p(d_point_rows), C.c_void_p(d_n_points), C.c_void_p(d_result)))
+
+    def two_view_batch_device(self, d_idx: int, n_problems: int, views, params: TwoViewParams, d_flag: int, d_points: int, d_point_rows: int,
+                              d_n_points: int, d_result: int, train_src=None):
+        """the same, frame q of the last batch against frame train_src[q] of it (None: q - 1; -1: none); asynchronous."""
+        v = _views_array(views)
+        ts = None if train_src is None else np.ascontiguousarray(train_src, np.int32)
+        if len(v) != n_problems or (ts is not None and len(ts) != n_problems):
+            raise ValueError("one view and one train frame per problem")
+        self._check(self._lib.ss_two_view_batch_device(self._h, None if ts is None else ts.ctypes.data, C.c_void_p(d_idx), n_problems,
+                                                       v.ctypes.data if n_problems else None, C.byref(params), C.c_void_p(d_flag),
+                                                       C.c_void_p(d_points), C.c_void_p(d_point_rows), C.c_void_p(d_n_points), C.c_void_p(d_result)))
+
+    def two_view(self, view, kp1: np.ndarray, kp2: np.ndarray, idx: np.ndarray, params: TwoViewParams):
+        """One problem, host arrays in and out -> what two_view_host returns."""
+        v, k1, k2, ix, n1, n2 = _two_view_arrays(view, kp1, kp2, idx)
+        flag, pts, rows, n_pts, res = _two_view_outputs(n1)
+        ptr = lambda a, n: a.ctypes.data if n else None  # noqa: E731
+        self._check(self._lib.ss_two_view(self._h, v.ctypes.data, ptr(k1, n1), n1, ptr(k2, n2), n2, ptr(ix, n1), C.byref(params), ptr(flag, n1),
+                                          ptr(pts, n1), ptr(rows, n1), n_pts.ctypes.data, res.ctypes.data))
+        return flag, pts[:n_pts[0]], rows[:n_pts[0]], res[0]
 
     # ---- Sim3 refinement: SearchBySim3's bookkeeping and OptimizeSim3 per loop candidate (the rule: include/sendslam_orb.h) ----
     def sim3_opt_pairs_device(self, d_query_xyz: int, d_query_kp: int, d_n_query: int, d_train_xyz: int, d_train_kp: int, d_n_train: int,

@@ -568,9 +568,9 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
     /* stage rows y0-4 .. y0+hrows+3, bytes x0-4 .. x0+67 (inside 96-byte rows that start at x0-16).  Pixels outside
      * the image are filled by BORDER_REFLECT_101 (what the blur needs; FAST never evaluates a
      * pixel whose ring leaves the image, so it does not care): only the regions at the image rim
-     * take that path (block-uniform).  One at the top or the bottom rim only differs from an interior
-     * one in the row index; one at the left or the right rim is staged as dwords: thread (tx, ty) takes
-     * column tx of rows ty, ty+16, ...; the two rightmost columns go to tx < 2. */
+     * take that path (block-uniform).  Every region is staged by two rounds of one 16-byte load per thread; a rim
+     * region differs from an interior one in the row index (reflected) and in the pieces of a staged row that lie
+     * outside the image's row (not loaded); one at the left or the right rim then mirrors three columns on that side. */
     const bool inner_x = x0 >= 4 && x0 + 68 <= w;
     const bool interior = inner_x && y0 >= 4 && y0 + hrows + 4 <= h;
     /* FAST's own bound is 3 px; the cell windows (cinfo's SS_CI_VALID entries) lie inside SS_EDGE_THRESHOLD px of the level's
@@ -595,49 +595,48 @@ __global__ __launch_bounds__(FT_THREADS) void k_fast_score(const uint8_t *__rest
         if (r1 < (uint32_t)rows) v1 = *(const uint4 *)(tile0 + (__umul24(r1, (uint32_t)ipitch) + 16u * c1));
         if (r0 < (uint32_t)rows) *(uint4 *)&lds[r0][4 * c0] = v0;
         if (r1 < (uint32_t)rows) *(uint4 *)&lds[r1][4 * c1] = v1;
-    } else if (inner_x && x0 >= FT_XB && x0 - FT_XB + 4 * FT_WORDS <= ipitch) {
-        /* a region at the top or the bottom rim only, its aligned window inside the row: the interior's two rounds of
-         * 16-byte loads, the row taken through BORDER_REFLECT_101 once per thread and round */
-        const uint8_t *col0 = img + (x0 - FT_XB);
+    } else {
+        /* a region at the image rim: the interior's two rounds, the row taken through BORDER_REFLECT_101 once per thread
+         * and round.  Of the six 16-byte pieces of a staged row the ones that lie inside the image's row -- bytes
+         * [0, ipitch) of it: rows start 16-byte aligned and pitches are multiples of 16, so a piece is inside or outside
+         * as a whole -- are loaded, the others (the first at the left rim, up to four where the row ends inside the last
+         * tile column) are staged as zeros: nothing is read at or behind row + ipitch.  One unsigned comparison per piece
+         * says both (a negative gx wraps). */
+        const int xw = x0 - FT_XB;
         const uint32_t t1 = (uint32_t)threadIdx.x + FT_THREADS;
         const uint32_t r0 = __umulhi((uint32_t)threadIdx.x, 0xAAAAAAABu) >> 2, c0 = (uint32_t)threadIdx.x - 6u * r0; /* t / 6 */
         const uint32_t r1 = __umulhi(t1, 0xAAAAAAABu) >> 2, c1 = t1 - 6u * r1;
+        const uint32_t gx0 = (uint32_t)(xw + 16 * (int)c0), gx1 = (uint32_t)(xw + 16 * (int)c1), gx_last = (uint32_t)(ipitch - 16);
         uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0;
-        if (r0 < (uint32_t)rows) v0 = *(const uint4 *)(col0 + (__umul24((uint32_t)reflect101(y0 - 4 + (int)r0, h), (uint32_t)ipitch) + 16u * c0));
-        if (r1 < (uint32_t)rows) v1 = *(const uint4 *)(col0 + (__umul24((uint32_t)reflect101(y0 - 4 + (int)r1, h), (uint32_t)ipitch) + 16u * c1));
+        if (r0 < (uint32_t)rows && gx0 <= gx_last) v0 = *(const uint4 *)(img + (__umul24((uint32_t)reflect101(y0 - 4 + (int)r0, h), (uint32_t)ipitch) + gx0));
+        if (r1 < (uint32_t)rows && gx1 <= gx_last) v1 = *(const uint4 *)(img + (__umul24((uint32_t)reflect101(y0 - 4 + (int)r1, h), (uint32_t)ipitch) + gx1));
         if (r0 < (uint32_t)rows) *(uint4 *)&lds[r0][4 * c0] = v0;
         if (r1 < (uint32_t)rows) *(uint4 *)&lds[r1][4 * c1] = v1;
-    } else {
-        /* a region at the image rim: rows by reflected row index; columns as the same aligned dwords wherever their
-         * first byte is inside the row (a level's rows are padded to the pitch, the caller's rows to 16 bytes), and a
-         * fix-up pass below for the few bytes BORDER_REFLECT_101 defines outside [0, w) */
-#pragma unroll
-        for (int rr = 0; rr < (FT_ROWS + FT_THREADS / 16 - 1) / (FT_THREADS / 16); rr++) {
-            const int r = ty + (FT_THREADS / 16) * rr;
-            if (r < rows) {
-                const uint8_t *row = img + (size_t)reflect101(y0 - 4 + r, h) * ipitch;
-                const int gx = x0 - 4 + 4 * tx;
-                lds[r][FT_XW - 1 + tx] = (gx >= 0 && gx < w) ? *(const uint32_t *)(row + gx) : 0u;
-                if (tx < 2) lds[r][FT_XW + 15 + tx] = (gx + 64 < w) ? *(const uint32_t *)(row + gx + 64) : 0u;
-            }
-        }
         if (!inner_x) {
-            /* the blur reads up to 3 px outside the row (x = -3 .. -1 mirror 3 .. 1, x = w .. w+2 mirror w-2 .. w-4); FAST
-             * never evaluates a pixel whose ring leaves the image.  Sources and destinations are inside the staged window. */
+            /* a region at the left or the right rim: a fix-up pass for the few bytes BORDER_REFLECT_101 defines outside
+             * [0, w).  The blur reads up to 3 px outside the row (x = -3 .. -1 mirror 3 .. 1, x = w .. w+2 mirror w-2 .. w-4); FAST
+             * never evaluates a pixel whose ring leaves the image.  Sources and destinations are inside the staged window,
+             * the sources (columns of the image) in pieces that were loaded.  What a row holds in its padding (columns
+             * w + 3 .. pitch - 1) reaches no result: only the blurred level's own padding columns depend on it. */
             __syncthreads();
-            uint8_t *t8 = (uint8_t *)&lds[0][0];
-            /* thread (tx, ty), tx < 6, takes byte tx of the six in rows ty, ty + 16, ...: all reads, then all writes */
-            static_assert((FT_ROWS + FT_THREADS / 16 - 1) / (FT_THREADS / 16) == 5, "five rows per thread");
-            const int k = tx;
-            const int x = k < 3 ? -1 - k : w + (k - 3), sx = k < 3 ? 1 + k : w - 2 - (k - 3);
-            const int bx = x - (x0 - FT_XB), bs = sx - (x0 - FT_XB);
-            if (tx < 6 && bx >= 0 && bx < 4 * FT_WORDS && bs >= 0 && bs < 4 * FT_WORDS) {
-                uint8_t v[5];
-#pragma unroll
-                for (int rr = 0; rr < 5; rr++) v[rr] = t8[imin(ty + 16 * rr, rows - 1) * (4 * FT_WORDS) + bs];
-#pragma unroll
-                for (int rr = 0; rr < 5; rr++)
-                    if (ty + 16 * rr < rows) t8[(ty + 16 * rr) * (4 * FT_WORDS) + bx] = v[rr];
+            /* a thread per staged row (waves 0 and 1), whole dwords, the byte selectors block-uniform */
+            static_assert(FT_ROWS <= FT_THREADS && SS_TILE_W % 4 == 0 && FT_XB % 4 == 0, "a thread per row; x0 and the window dword aligned");
+            if ((int)threadIdx.x < rows) {
+                uint32_t *lrow = &lds[threadIdx.x][0];
+                /* left rim: x0 < 4 is x0 == 0 (a multiple of SS_TILE_W).  The dword of x = -4 .. -1 from the one of x = 0 .. 3;
+                 * x = -4 is no one's and stays 0 */
+                if (x0 < 4) lrow[FT_XW - 1] = __builtin_amdgcn_perm(0u, lrow[FT_XW], 0x0102030Cu);
+                if (x0 + 68 > w) {
+                    /* right rim: 1 <= w - x0 <= 67.  q[0], q[1], q[2]: the aligned dwords from the one that holds column w - 4
+                     * (window byte w - x0 + 12 = 4 (q - lrow) + s, words 3 .. 21 of the row's 24); columns w, w + 1, w + 2 are
+                     * bytes s + 4, s + 5, s + 6 of the twelve and take bytes s + 2, s + 1, s: the rest of q[1] keeps its bytes */
+                    const int rel = w - x0 + FT_XB - 4, s = rel & 3;
+                    uint32_t *q = lrow + (rel >> 2);
+                    const uint32_t d0 = q[0], d1 = q[1];
+                    q[1] = __builtin_amdgcn_perm(d1, d0, s == 0 ? 0x07000102u : s == 1 ? 0x01020304u : s == 2 ? 0x03040504u : 0x05060504u);
+                    if (s == 2) *(uint8_t *)(q + 2) = (uint8_t)(d0 >> 16);                                             /* w + 2 */
+                    else if (s == 3) *(uint16_t *)(q + 2) = (uint16_t)__builtin_amdgcn_perm(d1, d0, 0x0C0C0304u); /* w + 1, w + 2 */
+                }
             }
         }
     }

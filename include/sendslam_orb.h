@@ -2055,6 +2055,103 @@ int ss_global_ba(ss_ctx *ctx, const ss_proj_view *views, const double *start, co
                  const ss_map_point *points, const uint8_t *point_skip, int n_points, const ss_gba_obs *obs, int n_obs,
                  const ss_gba_params *p, double *poses, double *xyz, uint8_t *point_flags, uint8_t *obs_flags, ss_gba_result *result);
 
+/* ---- Covisibility: how many map points two keyframes share, as KeyFrame::UpdateConnections counts it for a keyframe,
+ * Tracking::UpdateLocalKeyFrames for a tracked frame and LocalMapping::KeyFrameCulling walks the same two incidence lists for the
+ * redundant observations of a keyframe.  tests/covis_ref.py is its normative statement; DESIGN.md section 31.  An addition to ABI
+ * 5: nothing existing changes.  All of it is integer counting, so it is order-free and exact; one float comparison closes the
+ * culling vote -----------------------------------------------------------------------------------------------------------------
+ * The map.  ss_covis_set_map takes the tables ss_global_ba_device takes: problems (ss_gba_problem, HOST) and observation records
+ * (ss_gba_obs, HOST, any order; only kf, point, octave and right are read), and optionally one skip byte per record (cull_skip, in
+ * the order of obs).  Per problem the host sorts the records by (point, kf) with two stable counting passes and keeps compact
+ * lists, 12 bytes per record: a point's list is its run of (kf, octave, stereo bit, skip bit) in ascending kf; a keyframe's list
+ * is its run of point numbers in ascending point, each with the record's place in the point's run.  A record is an observation
+ * iff its octave lies in 0 .. n_levels-1 of the context; it is stereo iff check_right is set and right > 0.  The context keeps the
+ * tables on the device until the next ss_covis_set_map or ss_destroy (the map changes at keyframe rate, frames query it at frame
+ * rate); n_problems == 0 clears the map.
+ * Weights.  A keyframe row k of problem q: for j != k of the same problem, w(j) is the number of points i for which both (k, i)
+ * and (j, i) are observations.  A frame row b: w(j) is the number of hits i whose point (j, i) is an observation; a hit is a row i
+ * of d_idx[b] with idx >= 0 (only the sign is read) and i < clamp(d_n_points[point_src[b]], 0, point_rows), its point is
+ * (point_src[b] - first_block) * point_rows + i of the block's problem; there is no self exclusion.  A frame whose block, or a
+ * keyframe row whose keyframe, belongs to no problem has an empty row.
+ * Row summary (ss_covis_row).  n_shared: the j with w > 0.  max_weight, max_kf: the largest w and the lowest j that attains it; 0
+ * and -1 with nothing shared.  The listed set is every j with w >= min_weight; if it is empty, fallback is set and max_kf >= 0, it
+ * is {max_kf} (UpdateConnections' "no keyframe over the threshold: connect to the best").  n_listed is its size, n_written =
+ * min(n_listed, cap).
+ * Neighbour list.  d_nb is int32 [n_rows][cap][2]: (kf relative to the problem, weight), weight descending, then kf ascending (a
+ * rule of ours: upstream's sort of pair<int, KeyFrame*> breaks ties by pointer); truncation keeps the first cap entries of that
+ * order; entries from n_written on are (-1, 0).
+ * Culling counts (keyframe rows; a frame row gets zeros): LocalMapping::KeyFrameCulling for keyframe k.  An item (k, i) that is an
+ * observation and whose skip bit is 0 is examined and adds 1 to n_mps (the skip bit stands for upstream's depth test, which
+ * passes over the point before it is counted).  count(i) is the observations of i plus its stereo ones once more
+ * (MapPoint::Observations()); near is the number of observations (j, i), j != k, with octave_j <= octave_k + cull_slack.  An
+ * examined item adds 1 to n_redundant iff count(i) > cull_obs and near > cull_obs.  redundant = ((float)n_redundant > redundant_th
+ * * (float)n_mps): one float multiply and one compare, uncontracted.  Skip bits do not affect the weights.
+ * Deviations from upstream.  A row is what UpdateConnections itself leaves in mvpOrderedConnectedKeyFrames, on a snapshot of the
+ * map; its history-dependent side effects on the other keyframes (AddConnection -> UpdateBestCovisibles, which re-sorts every
+ * counted keyframe, those under the threshold too) are not modelled: min_weight 1 gives that superset.  The fallback is
+ * one-directional.  The culling counts are order-free on the snapshot (upstream removes a culled keyframe's observations before it
+ * examines the next; its early break does not change a count's verdict and is not modelled).  With the caller stay: the spanning
+ * tree (a new keyframe's parent is entry 0 of its row), children, parents and temporal neighbours in UpdateLocalKeyFrames,
+ * applying a culling decision, and bad flags (leave those records out). */
+/* records of one keyframe: a weight then fits 18 bits, and (weight << 14) | (16383 - kf) is one exact 32-bit sort key */
+#define SS_COVIS_MAX_ROW_ITEMS 262143
+#define SS_COVIS_MAX_NEIGHBOURS 1024 /* cap */
+#define SS_COVIS_MAX_MAP_KF 1048576  /* keyframes of one ss_covis_set_map call, all its problems and the gaps between them */
+typedef struct {            /* 32 bytes */
+    int32_t min_weight;     /* >= 1; upstream: 15, and 1 for UpdateLocalKeyFrames */
+    int32_t fallback;       /* 0 / 1; default 1 */
+    int32_t cull_obs;       /* >= 0; upstream: 3 */
+    int32_t cull_slack;     /* 0 .. SS_MAX_LEVELS; upstream: 1 */
+    float redundant_th;     /* finite, 0 .. 1; upstream: 0.9 */
+    int32_t reserved[3];    /* must be 0 */
+} ss_covis_params;
+typedef struct {            /* 32 bytes, one per row */
+    int32_t n_shared, max_weight, max_kf, n_listed, n_written;
+    int32_t n_mps, n_redundant, redundant;
+} ss_covis_row;
+int ss_covis_params_default(ss_covis_params *p);
+/* The map of the context (above).  n_kf keyframes, n_blocks blocks of point_rows point rows and n_obs records in the call; the
+ * problems own ranges of each as in ss_global_ba_device, and records of no problem are not read.  SS_ERR_INVALID_ARG, with a
+ * message: a kf or point outside its problem, a (kf, point) pair twice, a problem's n_kf outside 1 .. SS_GBA_MAX_KF, its n_blocks *
+ * point_rows outside 0 .. SS_GBA_MAX_POINTS or its n_obs outside 0 .. SS_GBA_MAX_OBS, the call's n_kf above SS_COVIS_MAX_MAP_KF or its
+ * point rows above 2^29, a range outside the call or overlapping another problem's,
+ * a reserved field that is not 0, point_rows above SS_GUIDED_MAX_ROWS, a keyframe with more than SS_COVIS_MAX_ROW_ITEMS records.  A
+ * refused call leaves the map it found. */
+int ss_covis_set_map(ss_ctx *ctx, const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows,
+                     const ss_gba_obs *obs, int n_obs, const uint8_t *cull_skip, int check_right);
+/* n_rows keyframe rows: rows is a HOST table of call keyframe numbers in any order, duplicates allowed; NULL: every keyframe of
+ * the map in order (n_rows must be the map's n_kf).  d_nb int32 [n_rows][cap][2], d_row ss_covis_row [n_rows]; every output byte
+ * is written exactly once.  n_rows == 0: SS_OK, nothing written.  SS_ERR_STATE: no map is set.  SS_ERR_INVALID_ARG, with a message:
+ * a row outside the map, cap outside 1 .. SS_COVIS_MAX_NEIGHBOURS, a parameter out of its range, a NULL buffer, more than 65535
+ * rows.  Asynchronous on the context's stream. */
+int ss_covis_kf_device(ss_ctx *ctx, const int32_t *rows, int n_rows, const ss_covis_params *p, int cap, void *d_nb, void *d_row);
+/* n_frames frame rows: d_idx int32 [n_frames][point_rows] exactly as ss_match_proj_batch_device writes it, d_n_points int32
+ * [n_blocks] of the map's blocks, point_src a HOST table of block numbers.  Otherwise as ss_covis_kf_device. */
+int ss_covis_frames_device(ss_ctx *ctx, const void *d_idx, const void *d_n_points, const int32_t *point_src, int n_frames,
+                           const ss_covis_params *p, int cap, void *d_nb, void *d_row);
+/* One problem of n_kf keyframes and n_points points with host pointers in and out, synchronous: sets the context's map to it
+ * (ss_covis_set_map) and returns every keyframe's row: nb int32 [n_kf][cap][2], row [n_kf]. */
+int ss_covis(ss_ctx *ctx, int n_kf, int n_points, const ss_gba_obs *obs, int n_obs, const uint8_t *cull_skip, int check_right,
+             const ss_covis_params *p, int cap, int32_t *nb, ss_covis_row *row);
+/* The whole rule on the host from the text the kernels compile (csrc/ss_covis_steps.h); needs no device.  The map's arguments are
+ * ss_covis_set_map's, with the pyramid's n_levels in the place of the context; the query's are the device forms' with host
+ * arrays.  Arguments are checked as the device calls check them: SS_ERR_INVALID_ARG, and the message in err (err_bytes of it;
+ * NULL: none). */
+int ss_covis_kf_host(const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs,
+                     int n_obs, const uint8_t *cull_skip, int check_right, int n_levels, const int32_t *rows, int n_rows,
+                     const ss_covis_params *p, int cap, int32_t *nb, ss_covis_row *row, char *err, int err_bytes);
+int ss_covis_frames_host(const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs,
+                         int n_obs, const uint8_t *cull_skip, int check_right, int n_levels, const int32_t *idx, const int32_t *n_points,
+                         const int32_t *point_src, int n_frames, const ss_covis_params *p, int cap, int32_t *nb, ss_covis_row *row,
+                         char *err, int err_bytes);
+/* The covisibility edges of the table ss_pose_graph_device takes, from downloaded rows: nb [n_rows][cap][2] and row [n_rows] as
+ * written above, row_kf [n_rows] the keyframe of each row relative to its problem.  For every row r in ascending r and every entry
+ * (j, w) of its list in list order with j > row_kf[r] and w >= min_weight, the pair (row_kf[r], j).  Writes at most capacity pairs
+ * (edges int32 [capacity][2]; NULL: counts only) and returns the count of pairs that qualify; SS_ERR_INVALID_ARG (negative) for a
+ * NULL table or a bad count.  Pure host code. */
+int ss_covis_edges_host(const int32_t *nb, const ss_covis_row *row, const int32_t *row_kf, int n_rows, int cap, int min_weight,
+                        int32_t *edges, int capacity);
+
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device
  * (hipStream_t; NULL = the legacy default stream): for callers that produce the inputs of a *_device call on their own

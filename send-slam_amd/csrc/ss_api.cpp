@@ -467,6 +467,9 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_gba_ws);
     dev_free(c->d_gba_io);
     staged_free(c->gba_tab);
+    staged_free(c->covis_tab);
+    staged_free(c->covis_call_tab);
+    dev_free(c->d_covis_io);
     dev_free(c->d_sim3opt_ws);
     dev_free(c->d_sim3opt_io);
     staged_free(c->sim3opt_tab);

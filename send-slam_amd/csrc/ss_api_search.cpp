@@ -2611,21 +2611,16 @@ struct gba_host_tables {
     int max_kf = 0;
 };
 
-/* The shapes and ranges of the problems of a call, then the records of each sorted and both its incidence lists into t.  The message
- * of the first rule that is broken, or empty.  May throw std::bad_alloc: the tables grow with the caller's counts */
-static std::string gba_build(int n_kf, int n_blocks, int point_rows, const ss_gba_problem *problems, int n_problems, const ss_gba_obs *obs, int n_obs,
-                             const float *scale, int n_levels, bool check_right, gba_host_tables &t)
+/* The shapes and ranges of the problems of a call (`what` heads the messages): the keyframes' and the blocks' problems into kf_prob and
+ * blk_prob, the largest n_kf into *max_kf.  The message of the first rule that is broken, or empty */
+static std::string problem_ranges(const std::string &what, int n_kf, int n_blocks, int point_rows, const ss_gba_problem *problems, int n_problems, int n_obs,
+                                  std::vector<int32_t> &kf_prob, std::vector<int32_t> &blk_prob, int *max_kf)
 {
-    const size_t NP = (size_t)n_blocks * point_rows;
-    t.kf_prob.assign((size_t)n_kf, -1), t.blk_prob.assign((size_t)n_blocks, -1);
-    t.pt_off.assign(NP, 0), t.pt_cnt.assign(NP, 0), t.kf_off.assign((size_t)n_kf, 0), t.kf_cnt.assign((size_t)n_kf, 0);
-    t.kf_list.assign((size_t)n_obs, 0);
-    t.rec.resize((size_t)n_obs);
-    for (int m = 0; m < n_obs; m++) t.rec[(size_t)m] = ss_gba_rec{-1, -1, 0.0f, 0.0f, -1.0f, 1.0f, m, 0};
+    kf_prob.assign((size_t)n_kf, -1), blk_prob.assign((size_t)n_blocks, -1);
     std::vector<int32_t> rec_prob((size_t)n_obs, -1);
     for (int q = 0; q < n_problems; q++) {
         const ss_gba_problem &b = problems[q];
-        const std::string head = "global BA: problem " + std::to_string(q) + ": ";
+        const std::string head = what + ": problem " + std::to_string(q) + ": ";
         if (b.n_kf < 1 || b.n_kf > SS_GBA_MAX_KF) return head + "n_kf " + std::to_string(b.n_kf) + " outside 1 .. SS_GBA_MAX_KF (" + std::to_string(SS_GBA_MAX_KF) + ")";
         if (b.n_blocks < 0 || (int64_t)b.n_blocks * point_rows > SS_GBA_MAX_POINTS)
             return head + "n_blocks " + std::to_string(b.n_blocks) + " of " + std::to_string(point_rows) + " rows outside 0 .. SS_GBA_MAX_POINTS (" +
@@ -2639,19 +2634,34 @@ static std::string gba_build(int n_kf, int n_blocks, int point_rows, const ss_gb
         if (b.first_obs < 0 || b.first_obs > n_obs - b.n_obs)
             return head + "records " + std::to_string(b.first_obs) + " .. + " + std::to_string(b.n_obs) + " lie outside the call's " + std::to_string(n_obs);
         for (int k = b.first_kf; k < b.first_kf + b.n_kf; k++) {
-            if (t.kf_prob[(size_t)k] >= 0) return head + "keyframe " + std::to_string(k) + " belongs to problem " + std::to_string(t.kf_prob[(size_t)k]) + " already";
-            t.kf_prob[(size_t)k] = q;
+            if (kf_prob[(size_t)k] >= 0) return head + "keyframe " + std::to_string(k) + " belongs to problem " + std::to_string(kf_prob[(size_t)k]) + " already";
+            kf_prob[(size_t)k] = q;
         }
         for (int k = b.first_block; k < b.first_block + b.n_blocks; k++) {
-            if (t.blk_prob[(size_t)k] >= 0) return head + "block " + std::to_string(k) + " belongs to problem " + std::to_string(t.blk_prob[(size_t)k]) + " already";
-            t.blk_prob[(size_t)k] = q;
+            if (blk_prob[(size_t)k] >= 0) return head + "block " + std::to_string(k) + " belongs to problem " + std::to_string(blk_prob[(size_t)k]) + " already";
+            blk_prob[(size_t)k] = q;
         }
         for (int m = b.first_obs; m < b.first_obs + b.n_obs; m++) {
             if (rec_prob[(size_t)m] >= 0) return head + "record " + std::to_string(m) + " belongs to problem " + std::to_string(rec_prob[(size_t)m]) + " already";
             rec_prob[(size_t)m] = q;
         }
-        t.max_kf = std::max(t.max_kf, (int)b.n_kf);
+        *max_kf = std::max(*max_kf, (int)b.n_kf);
     }
+    return std::string();
+}
+
+/* The shapes and ranges of the problems of a call, then the records of each sorted and both its incidence lists into t.  The message
+ * of the first rule that is broken, or empty.  May throw std::bad_alloc: the tables grow with the caller's counts */
+static std::string gba_build(int n_kf, int n_blocks, int point_rows, const ss_gba_problem *problems, int n_problems, const ss_gba_obs *obs, int n_obs,
+                             const float *scale, int n_levels, bool check_right, gba_host_tables &t)
+{
+    const size_t NP = (size_t)n_blocks * point_rows;
+    t.pt_off.assign(NP, 0), t.pt_cnt.assign(NP, 0), t.kf_off.assign((size_t)n_kf, 0), t.kf_cnt.assign((size_t)n_kf, 0);
+    t.kf_list.assign((size_t)n_obs, 0);
+    t.rec.resize((size_t)n_obs);
+    for (int m = 0; m < n_obs; m++) t.rec[(size_t)m] = ss_gba_rec{-1, -1, 0.0f, 0.0f, -1.0f, 1.0f, m, 0};
+    const std::string ranges = problem_ranges("global BA", n_kf, n_blocks, point_rows, problems, n_problems, n_obs, t.kf_prob, t.blk_prob, &t.max_kf);
+    if (!ranges.empty()) return ranges;
     /* the ranges stand: now the records of every problem */
     for (int q = 0; q < n_problems; q++) {
         const ss_gba_problem &b = problems[q];
@@ -2906,6 +2916,305 @@ int ss_global_ba(ss_ctx *c, const ss_proj_view *views, const double *start, cons
     if (rc == SS_OK)
         rc = ss_global_ba_device(c, io[PT].d, point_skip ? io[PS].d : nullptr, io[NP].d, nb, pr, io[ST].d, io[FX].d, n_kf, &problem, 1, obs, n_obs, views, p, io[POSE].d,
                                  io[XYZ].d, io[PF].d, io[OF].d, io[RES].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
+}
+
+/* ---- covisibility (csrc/ss_covis.hip, csrc/ss_covis_steps.h) ---- */
+/* the message of the first rule p or cap breaks, or NULL; needs no context */
+static const char *covis_params_error(const ss_covis_params *p, int cap)
+{
+    if (!p) return "covis: params is NULL";
+    if (p->min_weight < 1) return "covis: min_weight must be >= 1";
+    if (p->fallback != 0 && p->fallback != 1) return "covis: fallback must be 0 or 1";
+    if (p->cull_obs < 0) return "covis: cull_obs must be >= 0";
+    if (p->cull_slack < 0 || p->cull_slack > SS_MAX_LEVELS) return "covis: cull_slack must be 0 .. SS_MAX_LEVELS";
+    if (!(p->redundant_th >= 0.0f && p->redundant_th <= 1.0f)) return "covis: redundant_th must be finite and 0 .. 1";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0) return "covis: the reserved fields must be 0";
+    if (cap < 1 || cap > SS_COVIS_MAX_NEIGHBOURS) return "covis: cap must be 1 .. SS_COVIS_MAX_NEIGHBOURS (1024)";
+    return nullptr;
+}
+
+int ss_covis_params_default(ss_covis_params *p)
+{
+    if (!p) return SS_ERR_INVALID_ARG;
+    *p = ss_covis_params{15, 1, 3, 1, 0.9f, {0, 0, 0}};
+    return SS_OK;
+}
+
+/* the map's tables on the host */
+struct covis_host_tables {
+    std::vector<ss_covis_prob> prob;
+    std::vector<int32_t> kf_prob, blk_prob, pt_off, pt_cnt, kf_off, kf_cnt, kf_item;
+    std::vector<uint32_t> pt_item;
+    int n_kf = 0, n_blocks = 0, point_rows = 0, max_kf = 0;
+    size_t items = 0;
+    ss_covis_tab view() const
+    {
+        ss_covis_tab m;
+        m.n_kf = n_kf, m.n_blocks = n_blocks, m.point_rows = point_rows, m.n_problems = (int)prob.size(), m.max_kf = max_kf;
+        m.prob = prob.data(), m.kf_prob = kf_prob.data(), m.blk_prob = blk_prob.data();
+        m.kf_off = kf_off.data(), m.kf_cnt = kf_cnt.data(), m.pt_off = pt_off.data(), m.pt_cnt = pt_cnt.data();
+        m.pt_item = pt_item.data(), m.kf_item = kf_item.data();
+        return m;
+    }
+};
+
+/* The checks of ss_covis_set_map and the lists of every problem into t.  The message of the first rule that is broken, or empty.  May
+ * throw std::bad_alloc: the tables grow with the caller's counts */
+static std::string covis_build(const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs,
+                               const uint8_t *cull_skip, bool check_right, int n_levels, covis_host_tables &t)
+{
+    if (n_kf < 0 || n_problems < 0 || n_blocks < 0 || n_obs < 0 || point_rows < 1) return "covis: bad keyframe, problem, block, row or record count";
+    if (point_rows > SS_GUIDED_MAX_ROWS)
+        return "covis: point_rows " + std::to_string(point_rows) + " exceeds SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")";
+    if ((int64_t)n_blocks * point_rows > INT32_MAX / 4) return "covis: more than 2^29 point rows in one call";
+    if (n_kf > SS_COVIS_MAX_MAP_KF) return "covis: n_kf " + std::to_string(n_kf) + " exceeds SS_COVIS_MAX_MAP_KF (" + std::to_string(SS_COVIS_MAX_MAP_KF) + ") keyframes in one call";
+    if (n_levels < 1 || n_levels > SS_MAX_LEVELS) return "covis: no pyramid of 1 .. SS_MAX_LEVELS levels";
+    if (n_problems > 0 && !problems) return "covis: problems is NULL";
+    const std::string ranges = problem_ranges("covis", n_kf, n_blocks, point_rows, problems, n_problems, n_obs, t.kf_prob, t.blk_prob, &t.max_kf);
+    if (!ranges.empty()) return ranges;
+    const size_t NP = (size_t)n_blocks * point_rows;
+    t.n_kf = n_kf, t.n_blocks = n_blocks, t.point_rows = point_rows;
+    t.pt_off.assign(NP + 1, 0), t.pt_cnt.assign(NP + 1, 0), t.kf_off.assign((size_t)n_kf + 1, 0), t.kf_cnt.assign((size_t)n_kf + 1, 0);
+    t.items = 0;
+    for (int q = 0; q < n_problems; q++) t.items += (size_t)problems[q].n_obs;
+    t.pt_item.assign(t.items + 1, 0u), t.kf_item.assign(2 * t.items + 2, 0);
+    t.prob.resize((size_t)n_problems);
+    size_t base = 0;
+    for (int q = 0; q < n_problems; q++) {
+        const ss_gba_problem &b = problems[q];
+        t.prob[(size_t)q] = ss_covis_prob{b.first_kf, b.n_kf, b.first_block, b.n_blocks};
+        if (b.n_obs > 0 && !obs) return "covis: obs is NULL";
+        const int P = b.n_blocks * point_rows;
+        const size_t p0 = (size_t)b.first_block * point_rows;
+        int bad = 0;
+        const int why = ss_covis_tables(b.n_kf, P, obs + b.first_obs, cull_skip ? cull_skip + b.first_obs : nullptr, b.n_obs, n_levels, check_right, (int)base, (int)p0,
+                                        t.pt_off.data() + p0, t.pt_cnt.data() + p0, t.kf_off.data() + b.first_kf, t.kf_cnt.data() + b.first_kf, t.pt_item.data() + base,
+                                        t.kf_item.data() + 2 * base, &bad);
+        if (why != 0) {
+            const ss_gba_obs &o = obs[b.first_obs + bad];
+            const std::string rec = "covis: problem " + std::to_string(q) + ": record " + std::to_string(b.first_obs + bad) + ": ";
+            if (why == 1) return rec + "kf " + std::to_string(o.kf) + " outside 0 .. " + std::to_string(b.n_kf - 1);
+            if (why == 2) return rec + "point " + std::to_string(o.point) + " outside 0 .. " + std::to_string(P - 1);
+            if (why == 3) return rec + "the pair (kf " + std::to_string(o.kf) + ", point " + std::to_string(o.point) + ") has a record already";
+            return rec + "keyframe " + std::to_string(o.kf) + " has more than SS_COVIS_MAX_ROW_ITEMS (" + std::to_string(SS_COVIS_MAX_ROW_ITEMS) + ") records";
+        }
+        base += (size_t)b.n_obs;
+    }
+    return std::string();
+}
+
+/* the checks of a query against the map m (`what` heads the messages); table: the keyframe numbers or, frames, the block numbers */
+static std::string covis_query_error(const std::string &what, const ss_covis_tab &m, bool frames, const int32_t *table, int n_rows, const ss_covis_params *p, int cap)
+{
+    if (const char *msg = covis_params_error(p, cap)) return msg;
+    if (n_rows < 0) return what + ": bad row count";
+    if (n_rows > 65535) return what + ": more than 65535 rows in one call";
+    if (frames && n_rows > 0 && !table) return what + ": point_src is NULL";
+    if (!frames && !table && n_rows != 0 && n_rows != m.n_kf)
+        return what + ": rows is NULL, so n_rows must be the map's " + std::to_string(m.n_kf) + " keyframes, not " + std::to_string(n_rows);
+    const int limit = frames ? m.n_blocks : m.n_kf;
+    for (int r = 0; table && r < n_rows; r++)
+        if (table[r] < 0 || table[r] >= limit)
+            return what + ": row " + std::to_string(r) + ": " + (frames ? "block " : "keyframe ") + std::to_string(table[r]) + " lies outside the map's " + std::to_string(limit);
+    return std::string();
+}
+
+static int covis_host(bool frames, const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs,
+                      const uint8_t *cull_skip, int check_right, int n_levels, const int32_t *table, const int32_t *idx, const int32_t *n_points, int n_rows,
+                      const ss_covis_params *p, int cap, int32_t *nb, ss_covis_row *row, char *err, int err_bytes)
+{
+    const std::string what = frames ? "ss_covis_frames_host" : "ss_covis_kf_host";
+    try {
+        covis_host_tables t;
+        std::string msg = covis_build(problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, cull_skip, check_right != 0, n_levels, t);
+        if (msg.empty() && n_problems == 0) msg = what + ": no map";
+        const ss_covis_tab m = t.view();
+        if (msg.empty()) msg = covis_query_error(what, m, frames, table, n_rows, p, cap);
+        if (msg.empty() && n_rows > 0 && (!nb || !row || (frames && (!idx || !n_points)))) msg = what + ": NULL buffer";
+        if (!msg.empty()) return gba_refuse(err, err_bytes, msg);
+        std::vector<int32_t> w;
+        for (int r = 0; r < n_rows; r++) {
+            const int at = table ? table[r] : r;
+            ss_covis_row_host(m, frames ? -1 : at, frames ? at : 0, frames ? idx + (size_t)r * point_rows : nullptr, frames ? n_points[at] : 0, *p, cap,
+                              nb + (size_t)r * cap * 2, row + r, w);
+        }
+    } catch (const std::bad_alloc &) {
+        return SS_ERR_NO_MEMORY;
+    }
+    return SS_OK;
+}
+
+int ss_covis_kf_host(const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs, const uint8_t *cull_skip,
+                     int check_right, int n_levels, const int32_t *rows, int n_rows, const ss_covis_params *p, int cap, int32_t *nb, ss_covis_row *row, char *err,
+                     int err_bytes)
+{
+    return covis_host(false, problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, cull_skip, check_right, n_levels, rows, nullptr, nullptr, n_rows, p, cap, nb, row,
+                      err, err_bytes);
+}
+
+int ss_covis_frames_host(const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs,
+                         const uint8_t *cull_skip, int check_right, int n_levels, const int32_t *idx, const int32_t *n_points, const int32_t *point_src, int n_frames,
+                         const ss_covis_params *p, int cap, int32_t *nb, ss_covis_row *row, char *err, int err_bytes)
+{
+    return covis_host(true, problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, cull_skip, check_right, n_levels, point_src, idx, n_points, n_frames, p, cap, nb,
+                      row, err, err_bytes);
+}
+
+int ss_covis_edges_host(const int32_t *nb, const ss_covis_row *row, const int32_t *row_kf, int n_rows, int cap, int min_weight, int32_t *edges, int capacity)
+{
+    if (n_rows < 0 || cap < 1 || capacity < 0 || (n_rows > 0 && (!nb || !row || !row_kf))) return SS_ERR_INVALID_ARG;
+    int64_t n = 0;
+    for (int r = 0; r < n_rows; r++) {
+        const int listed = std::min(std::max(row[r].n_written, 0), cap);
+        for (int e = 0; e < listed; e++) {
+            const int32_t j = nb[((size_t)r * cap + e) * 2], w = nb[((size_t)r * cap + e) * 2 + 1];
+            if (j <= row_kf[r] || w < min_weight) continue;
+            if (edges && n < capacity) edges[2 * n] = row_kf[r], edges[2 * n + 1] = j;
+            n++;
+        }
+    }
+    return n > INT32_MAX ? SS_ERR_INVALID_ARG : (int)n;
+}
+
+static int covis_set_map(ss_ctx *c, const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs,
+                         const uint8_t *cull_skip, int check_right)
+{
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS];
+    const int rc = context_pyramid(c, "covis", &n_levels, scale);
+    if (rc != SS_OK) return rc;
+    covis_host_tables t;
+    const std::string msg = covis_build(problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, cull_skip, check_right != 0, n_levels, t);
+    if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_problems == 0) {
+        c->covis_map = ss_covis_tab();
+        c->covis_items = 0;
+        return SS_OK;
+    }
+    /* the tables, each on a 16-byte boundary */
+    const size_t K = (size_t)n_kf, B = (size_t)n_blocks, NP = B * point_rows, S = t.items, nq = (size_t)n_problems;
+    size_t at = 0;
+    auto place = [&](size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 15) & ~(size_t)15;
+        return o;
+    };
+    const size_t o_prob = place(nq * sizeof(ss_covis_prob)), o_kfp = place(K * 4), o_blp = place(B * 4), o_kfo = place(K * 4), o_kfc = place(K * 4), o_pto = place(NP * 4),
+                 o_ptc = place(NP * 4), o_pti = place(S * 4), o_kfi = place(S * 8);
+    {
+        stage_timer tm(c, "covis_upload", (int64_t)at);
+        const int up = staged_upload(c, c->covis_tab, at + 16, [&](uint8_t *h) {
+            memcpy(h + o_prob, t.prob.data(), nq * sizeof(ss_covis_prob));
+            memcpy(h + o_kfp, t.kf_prob.data(), K * 4);
+            if (B) memcpy(h + o_blp, t.blk_prob.data(), B * 4);
+            memcpy(h + o_kfo, t.kf_off.data(), K * 4);
+            memcpy(h + o_kfc, t.kf_cnt.data(), K * 4);
+            if (NP) memcpy(h + o_pto, t.pt_off.data(), NP * 4), memcpy(h + o_ptc, t.pt_cnt.data(), NP * 4);
+            if (S) memcpy(h + o_pti, t.pt_item.data(), S * 4), memcpy(h + o_kfi, t.kf_item.data(), S * 8);
+        });
+        if (up != SS_OK) {
+            c->covis_map = ss_covis_tab(); /* the buffer may have moved */
+            return up;
+        }
+    }
+    ss_covis_tab m;
+    m.n_kf = n_kf, m.n_blocks = n_blocks, m.point_rows = point_rows, m.n_problems = n_problems, m.max_kf = t.max_kf;
+    m.prob = c->covis_tab.as<ss_covis_prob>(o_prob);
+    m.kf_prob = c->covis_tab.as<int32_t>(o_kfp), m.blk_prob = c->covis_tab.as<int32_t>(o_blp);
+    m.kf_off = c->covis_tab.as<int32_t>(o_kfo), m.kf_cnt = c->covis_tab.as<int32_t>(o_kfc);
+    m.pt_off = c->covis_tab.as<int32_t>(o_pto), m.pt_cnt = c->covis_tab.as<int32_t>(o_ptc);
+    m.pt_item = c->covis_tab.as<uint32_t>(o_pti), m.kf_item = c->covis_tab.as<int32_t>(o_kfi);
+    c->covis_map = m;
+    c->covis_items = (int64_t)S;
+    return SS_OK;
+}
+
+int ss_covis_set_map(ss_ctx *c, const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs,
+                     const uint8_t *cull_skip, int check_right)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    try {
+        return covis_set_map(c, problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, cull_skip, check_right);
+    } catch (const std::bad_alloc &) {
+        return fail(c, SS_ERR_NO_MEMORY, "covis: no host memory for the tables of the map");
+    }
+}
+
+/* the checks, the table and the launch of both device forms */
+static int covis_query(ss_ctx *c, const std::string &what, bool frames, const int32_t *table, int n_rows, const ss_covis_params *p, int cap, const void *d_idx,
+                       const void *d_n_points, void *d_nb, void *d_row)
+{
+    const ss_covis_tab &m = c->covis_map;
+    if (const char *msg = covis_params_error(p, cap)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (m.n_kf == 0) return fail(c, SS_ERR_STATE, what + ": no map (ss_covis_set_map)");
+    const std::string msg = covis_query_error(what, m, frames, table, n_rows, p, cap);
+    if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_rows == 0) return SS_OK;
+    if (!d_nb || !d_row || (frames && (!d_idx || !d_n_points))) return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
+    ssk_covis_call g;
+    g.tab = &m, g.n_rows = n_rows, g.cap = cap, g.p = *p;
+    g.idx = (const int32_t *)d_idx, g.np = (const int32_t *)d_n_points;
+    g.nb = (int32_t *)d_nb, g.row = (ss_covis_row *)d_row;
+    if (table) {
+        const int rc = staged_upload(c, c->covis_call_tab, (size_t)n_rows * 4, [&](uint8_t *h) { memcpy(h, table, (size_t)n_rows * 4); });
+        if (rc != SS_OK) return rc;
+        (frames ? g.src : g.rows) = c->covis_call_tab.as<int32_t>();
+    }
+    /* the stage's bytes: the row's share of the map's lists (a mean row's; 12 bytes per record, its point's list once more and the
+     * point's run), the frame's idx, and the outputs */
+    const int64_t out = (int64_t)n_rows * (cap * 8 + 32 + 4);
+    hipError_t e;
+    if (frames) {
+        stage_timer tm(c, "covis_frames", (int64_t)n_rows * m.point_rows * (4 + 8) + out);
+        e = (hipError_t)ssk_covis_frames(c->stream, g);
+    } else {
+        stage_timer tm(c, "covis_kf", c->covis_items * (12 + 8) * n_rows / m.n_kf + out);
+        e = (hipError_t)ssk_covis_kf(c->stream, g);
+    }
+    HIP_TRY(c, e);
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_covis_kf_device(ss_ctx *c, const int32_t *rows, int n_rows, const ss_covis_params *p, int cap, void *d_nb, void *d_row)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    return covis_query(c, "ss_covis_kf_device", false, rows, n_rows, p, cap, nullptr, nullptr, d_nb, d_row);
+}
+
+int ss_covis_frames_device(ss_ctx *c, const void *d_idx, const void *d_n_points, const int32_t *point_src, int n_frames, const ss_covis_params *p, int cap, void *d_nb,
+                           void *d_row)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    return covis_query(c, "ss_covis_frames_device", true, point_src, n_frames, p, cap, d_idx, d_n_points, d_nb, d_row);
+}
+
+int ss_covis(ss_ctx *c, int n_kf, int n_points, const ss_gba_obs *obs, int n_obs, const uint8_t *cull_skip, int check_right, const ss_covis_params *p, int cap,
+             int32_t *nb, ss_covis_row *row)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = covis_params_error(p, cap)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_points < 0 || n_points > SS_GBA_MAX_POINTS || n_obs < 0) return fail(c, SS_ERR_INVALID_ARG, "covis: n_points must be 0 .. SS_GBA_MAX_POINTS and n_obs >= 0");
+    if (!nb || !row) return fail(c, SS_ERR_INVALID_ARG, "ss_covis: NULL buffer");
+    /* the points as blocks of `pr` rows, the last one short, as ss_global_ba lays them out */
+    const int pr = std::min(std::max(n_points, 1), SS_GUIDED_MAX_ROWS), nblk = n_points > 0 ? (n_points + pr - 1) / pr : 0;
+    const ss_gba_problem problem = {0, n_kf, 0, nblk, 0, n_obs, {0, 0}};
+    int rc = ss_covis_set_map(c, &problem, 1, n_kf, nblk, pr, obs, n_obs, cull_skip, check_right);
+    if (rc != SS_OK) return rc;
+    const size_t kf = (size_t)n_kf;
+    enum { NB, ROW, PIECES };
+    io_piece io[PIECES] = {{nullptr, nb, kf * cap * 8, kf * cap * 8}, {nullptr, row, kf * sizeof(ss_covis_row), kf * sizeof(ss_covis_row)}};
+    rc = io_send(c, c->d_covis_io, io, PIECES);
+    if (rc == SS_OK) rc = ss_covis_kf_device(c, nullptr, n_kf, p, cap, io[NB].d, io[ROW].d);
     if (rc != SS_OK) {
         (void)hipStreamSynchronize(c->stream);
         return rc;

@@ -13,6 +13,7 @@
 
 #include "../../include/sendslam_orb.h"
 #include "ss_constants.h"
+#include "ss_covis_steps.h"
 #include "ss_geometry.h"
 #include "ss_kernels.h"
 #include "ss_layout.h"
@@ -168,6 +169,12 @@ struct ss_ctx {
      * keyframes' and blocks' problems, the sorted records and both incidence lists) */
     dev_buf<uint8_t> d_gba_ws, d_gba_io;
     staged_table gba_tab;
+    /* covisibility: the map's tables, kept from ss_covis_set_map until the next one (covis_map points into covis_tab; n_kf == 0: no
+     * map), the tables of a query (row or block numbers), the host form's device copies */
+    staged_table covis_tab, covis_call_tab;
+    ss_covis_tab covis_map;
+    int64_t covis_items = 0; /* the records of the map's problems */
+    dev_buf<uint8_t> d_covis_io;
     /* PnP RANSAC: the workspace of a call (correspondences, models, poses, counts), the host form's device copies, the tables of a
      * call (views, then frame numbers, then block numbers) */
     dev_buf<uint8_t> d_pnp_ws, d_pnp_io;

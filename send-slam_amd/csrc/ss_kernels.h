@@ -706,6 +706,23 @@ void ssk_gba_pcg(hipStream_t s, const ssk_gba_call &g);                        /
 void ssk_gba_update(hipStream_t s, const ssk_gba_call &g);                     /* two launches */
 void ssk_gba_classify(hipStream_t s, const ssk_gba_call &g);
 void ssk_gba_finish(hipStream_t s, const ssk_gba_call &g);                     /* three launches */
+/* ss_covis.hip: covisibility (DESIGN.md "Covisibility").  One workgroup per row: a keyframe row names a keyframe of the map (rows
+ * NULL: row r is keyframe r), a frame row the block its hits index (src) and its row of idx.  max_kf, the largest problem of the map,
+ * sizes the weight counters in dynamic LDS */
+struct ss_covis_tab; /* ss_covis_steps.h */
+struct ssk_covis_call {
+    const ss_covis_tab *tab = nullptr; /* HOST: the map's tables on the device */
+    int n_rows = 0, cap = 0;
+    const int32_t *rows = nullptr;     /* device [n_rows] or NULL: keyframe rows */
+    const int32_t *src = nullptr;      /* device [n_rows]: the block of a frame row */
+    const int32_t *idx = nullptr;      /* device [n_rows][point_rows] */
+    const int32_t *np = nullptr;       /* device [n_blocks] */
+    ss_covis_params p = {};
+    int32_t *nb = nullptr;             /* device [n_rows][cap][2] */
+    ss_covis_row *row = nullptr;       /* device [n_rows] */
+};
+int ssk_covis_kf(hipStream_t s, const ssk_covis_call &g);     /* a hipError_t: the LDS attribute may be refused */
+int ssk_covis_frames(hipStream_t s, const ssk_covis_call &g);
 /* The bookkeeping of SearchBySim3 (the rule: include/sendslam_orb.h).  One workgroup per pair: a base pass over the rows, a barrier,
  * a scatter pass in which every store to one address writes the same value.  marks writes skip1 and skip2; mutual marks the train
  * rows that carry a prior match in taken (workspace, [n_frames][rows]) and writes idx_out and the summary */

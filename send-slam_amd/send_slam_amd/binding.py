@@ -55,7 +55,9 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_pnp_pairs_device", "ss_pnp_batch_device", "ss_pnp", "ss_pose_graph_host", "ss_pose_graph_edge_host", "ss_graph_atan2_host",
            "ss_graph_ln_host", "ss_pose_graph_device", "ss_pose_graph", "ss_pose_graph_points_device", "ss_global_ba_host",
            "ss_global_ba_obs_from_idx_host", "ss_global_ba_device", "ss_global_ba", "ss_two_view_host", "ss_two_view_model_host",
-           "ss_two_view_check_host", "ss_two_view_accept_host", "ss_two_view_beats_host", "ss_two_view_point_tests_host", "ss_two_view_pairs_device", "ss_two_view_batch_device", "ss_two_view"]
+           "ss_two_view_check_host", "ss_two_view_accept_host", "ss_two_view_beats_host", "ss_two_view_point_tests_host", "ss_two_view_pairs_device", "ss_two_view_batch_device", "ss_two_view",
+           "ss_covis_params_default", "ss_covis_set_map", "ss_covis_kf_device", "ss_covis_frames_device", "ss_covis", "ss_covis_kf_host",
+           "ss_covis_frames_host", "ss_covis_edges_host"]
 
 
 class OrbParams(C.Structure):
@@ -1051,6 +1053,89 @@ def global_ba_obs_from_idx(kp: np.ndarray, idx: np.ndarray, n_kp=None, right=Non
     return out
 
 
+# ---- covisibility (the rule: include/sendslam_orb.h) ----
+SS_COVIS_MAX_ROW_ITEMS, SS_COVIS_MAX_NEIGHBOURS, SS_COVIS_MAX_MAP_KF = 262143, 1024, 1048576
+
+
+class CovisParams(C.Structure):
+    _fields_ = [("min_weight", C.c_int32), ("fallback", C.c_int32), ("cull_obs", C.c_int32), ("cull_slack", C.c_int32),
+                ("redundant_th", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+# ss_covis_row: one per row
+COVIS_ROW_DTYPE = np.dtype([(n, "<i4") for n in ("n_shared", "max_weight", "max_kf", "n_listed", "n_written", "n_mps", "n_redundant", "redundant")])
+
+
+def covis_params(min_weight: int = 15, fallback: int = 1, cull_obs: int = 3, cull_slack: int = 1, redundant_th: float = 0.9,
+                 reserved=(0, 0, 0)) -> CovisParams:
+    """upstream's values: UpdateConnections' threshold of 15 (UpdateLocalKeyFrames: min_weight 1), KeyFrameCulling's thObs 3, one octave
+    of slack and 0.9 of the points"""
+    return CovisParams(min_weight=min_weight, fallback=int(fallback), cull_obs=cull_obs, cull_slack=cull_slack, redundant_th=redundant_th,
+                       reserved=(C.c_int32 * 3)(*reserved))
+
+
+def _covis_map_arrays(problems, obs, cull_skip):
+    pr = np.ascontiguousarray(problems, GBA_PROBLEM_DTYPE).reshape(-1)
+    ob = np.ascontiguousarray(obs, GBA_OBS_DTYPE).reshape(-1)
+    sk = None if cull_skip is None else np.ascontiguousarray(cull_skip, np.uint8).reshape(-1)
+    if sk is not None and len(sk) != len(ob):
+        raise ValueError("one skip byte per observation record")
+    return pr, ob, sk
+
+
+def _covis_host(frames, problems, n_kf, n_blocks, point_rows, obs, n_levels, table, idx, n_points, n_rows, params, cap, cull_skip, check_right):
+    pr, ob, sk = _covis_map_arrays(problems, obs, cull_skip)
+    tb = None if table is None else np.ascontiguousarray(table, np.int32).reshape(-1)
+    n_rows = len(tb) if tb is not None else n_rows
+    nb, row = np.full((max(n_rows, 0), max(cap, 1), 2), 0x5A5A5A5A, np.int32), np.zeros(max(n_rows, 0), COVIS_ROW_DTYPE)
+    err = C.create_string_buffer(512)
+    ptr = lambda a: None if a is None or not len(a) else a.ctypes.data  # noqa: E731
+    map_args = (ptr(pr), len(pr), n_kf, n_blocks, point_rows, ptr(ob), len(ob), ptr(sk), int(check_right), n_levels)
+    if frames:
+        ix = np.ascontiguousarray(idx, np.int32).reshape(n_rows, -1)
+        npts = np.ascontiguousarray(n_points, np.int32).reshape(-1)
+        if n_rows and ix.shape[1] != point_rows:
+            raise ValueError("idx is [n_frames][point_rows]")
+        rc = load().ss_covis_frames_host(*map_args, ptr(ix.reshape(-1)), ptr(npts), ptr(tb), n_rows, C.byref(params), cap, ptr(nb.reshape(-1)), ptr(row), err, len(err))
+    else:
+        rc = load().ss_covis_kf_host(*map_args, ptr(tb), n_rows, C.byref(params), cap, ptr(nb.reshape(-1)), ptr(row), err, len(err))
+    if rc != SS_OK:
+        raise OrbError(rc, err.value.decode() or "the covisibility host twin refused its arguments")
+    return nb, row
+
+
+def covis_kf_host(problems, n_kf: int, n_blocks: int, point_rows: int, obs, n_levels: int, params: CovisParams, cap: int, rows=None, cull_skip=None,
+                  check_right: bool = False):
+    """ss_covis_kf_host: the whole rule on the host -> (nb int32 [n_rows][cap][2], COVIS_ROW_DTYPE [n_rows]); rows None: every keyframe of
+    the map.  A refusal raises OrbError with the library's message"""
+    return _covis_host(False, problems, n_kf, n_blocks, point_rows, obs, n_levels, rows, None, None, n_kf, params, cap, cull_skip, check_right)
+
+
+def covis_frames_host(problems, n_kf: int, n_blocks: int, point_rows: int, obs, n_levels: int, idx, n_points, point_src, params: CovisParams, cap: int,
+                      cull_skip=None, check_right: bool = False):
+    """ss_covis_frames_host: idx int32 [n_frames][point_rows], n_points int32 [n_blocks], point_src [n_frames] -> as covis_kf_host"""
+    return _covis_host(True, problems, n_kf, n_blocks, point_rows, obs, n_levels, point_src, idx, n_points, 0, params, cap, cull_skip, check_right)
+
+
+def covis_edges(nb: np.ndarray, row: np.ndarray, row_kf, min_weight: int) -> np.ndarray:
+    """ss_covis_edges_host: the pairs (k, j), j > k, of weight >= min_weight in the downloaded rows -> int32 [n][2]"""
+    nb = np.ascontiguousarray(nb, np.int32)
+    rw = np.ascontiguousarray(row, COVIS_ROW_DTYPE).reshape(-1)
+    rk = np.ascontiguousarray(row_kf, np.int32).reshape(-1)
+    if nb.ndim != 3 or nb.shape[0] != len(rw) or len(rk) != len(rw) or nb.shape[2] != 2:
+        raise ValueError("nb is [n_rows][cap][2], with one row record and one keyframe number per row")
+    fn = load().ss_covis_edges_host
+    ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
+    args = (ptr(nb), ptr(rw), ptr(rk), len(rw), max(nb.shape[1], 1), min_weight)
+    n = fn(*args, None, 0)
+    if n < 0:
+        raise OrbError(n, "ss_covis_edges_host refused its arguments")
+    out = np.zeros((n, 2), np.int32)
+    if n and fn(*args, out.ctypes.data, n) != n:
+        raise OrbError(SS_ERR_STATE, "ss_covis_edges_host: the count changed between two calls")
+    return out
+
+
 class OrbError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libsendslam_orb: {message} (status {code})")
@@ -1224,6 +1309,16 @@ def load():
                                                                           C.c_void_p, C.c_int, C.c_void_p, C.POINTER(GbaParams)] + [C.c_void_p] * 5
     lib.ss_global_ba.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                                    C.POINTER(GbaParams)] + [C.c_void_p] * 5
+    covis_map = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.ss_covis_params_default.argtypes = [C.POINTER(CovisParams)]
+    lib.ss_covis_set_map.argtypes = [C.c_void_p] + covis_map
+    lib.ss_covis_kf_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CovisParams), C.c_int, C.c_void_p, C.c_void_p]
+    lib.ss_covis_frames_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CovisParams), C.c_int, C.c_void_p, C.c_void_p]
+    lib.ss_covis.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(CovisParams), C.c_int, C.c_void_p, C.c_void_p]
+    lib.ss_covis_kf_host.argtypes = covis_map + [C.c_int, C.c_void_p, C.c_int, C.POINTER(CovisParams), C.c_int, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    lib.ss_covis_frames_host.argtypes = covis_map + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CovisParams), C.c_int, C.c_void_p,
+                                                     C.c_void_p, C.c_char_p, C.c_int]
+    lib.ss_covis_edges_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     lib.ss_pnp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                 C.POINTER(PnpParams), C.c_int, C.c_void_p, C.c_void_p]
     lib.ss_pnp_model_host.argtypes = [C.POINTER(PnpParams)] + [C.c_void_p] * 6
@@ -2087,6 +2182,40 @@ class OrbContext:
         self._check(self._lib.ss_global_ba(self._h, ptr(v, n_kf), ptr(st, n_kf), ptr(fx, n_kf), n_kf, ptr(pts, n_p), ptr(skip, n_p), n_p, ptr(ob, n_o), n_o,
                                            C.byref(params), poses.ctypes.data, ptr(xyz, n_p), ptr(pf, n_p), ptr(of, n_o), res.ctypes.data))
         return poses, xyz, pf, of, res[0]
+
+    # ---- covisibility: neighbour lists and culling counts from the map's incidence lists (the rule: include/sendslam_orb.h) ----
+    def covis_set_map(self, problems, n_kf: int, n_blocks: int, point_rows: int, obs, cull_skip=None, check_right: bool = False):
+        """the problems (GBA_PROBLEM_DTYPE) and the observation records (GBA_OBS_DTYPE, any order) global_ba_device takes, and optionally
+        one skip byte per record; the context keeps the map until the next call.  No problem clears it."""
+        pr, ob, sk = _covis_map_arrays(problems, obs, cull_skip)
+        self._check(self._lib.ss_covis_set_map(self._h, pr.ctypes.data if len(pr) else None, len(pr), n_kf, n_blocks, point_rows,
+                                               ob.ctypes.data if len(ob) else None, len(ob), None if sk is None or not len(sk) else sk.ctypes.data,
+                                               int(check_right)))
+
+    def covis_kf_device(self, rows, n_rows: int, params: CovisParams, cap: int, d_nb: int, d_row: int):
+        """rows: call keyframe numbers (any order, duplicates allowed) or None: every keyframe of the map; d_nb int32 [n_rows][cap][2],
+        d_row COVIS_ROW_DTYPE [n_rows]; asynchronous."""
+        rw = None if rows is None else np.ascontiguousarray(rows, np.int32).reshape(-1)
+        if rw is not None and len(rw) != n_rows:
+            raise ValueError("one keyframe number per row")
+        self._check(self._lib.ss_covis_kf_device(self._h, None if rw is None or not n_rows else rw.ctypes.data, n_rows, C.byref(params), cap,
+                                                 C.c_void_p(d_nb), C.c_void_p(d_row)))
+
+    def covis_frames_device(self, d_idx: int, d_n_points: int, point_src, params: CovisParams, cap: int, d_nb: int, d_row: int):
+        """d_idx int32 [n_frames][point_rows] as match_proj_batch_device wrote it, d_n_points int32 [n_blocks] of the map's blocks, point_src
+        the block of each frame; outputs as covis_kf_device; asynchronous."""
+        ps = np.ascontiguousarray(point_src, np.int32).reshape(-1)
+        self._check(self._lib.ss_covis_frames_device(self._h, C.c_void_p(d_idx), C.c_void_p(d_n_points), ps.ctypes.data if len(ps) else None, len(ps),
+                                                     C.byref(params), cap, C.c_void_p(d_nb), C.c_void_p(d_row)))
+
+    def covis(self, n_kf: int, n_points: int, obs, params: CovisParams, cap: int, cull_skip=None, check_right: bool = False):
+        """One problem, host arrays in and out -> what covis_kf_host returns for every keyframe; the map of the context becomes this one."""
+        _, ob, sk = _covis_map_arrays(np.zeros(0, GBA_PROBLEM_DTYPE), obs, cull_skip)
+        nb, row = np.full((max(n_kf, 0), max(cap, 1), 2), 0x5A5A5A5A, np.int32), np.zeros(max(n_kf, 0), COVIS_ROW_DTYPE)
+        self._check(self._lib.ss_covis(self._h, n_kf, n_points, ob.ctypes.data if len(ob) else None, len(ob),
+                                       None if sk is None or not len(sk) else sk.ctypes.data, int(check_right), C.byref(params), cap,
+                                       nb.ctypes.data if nb.size else None, row.ctypes.data if len(row) else None))
+        return nb, row
 
     # ---- PnP RANSAC: a pose for every relocalisation candidate (the rule: include/sendslam_orb.h) ----
     @staticmethod

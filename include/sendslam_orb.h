@@ -49,6 +49,8 @@
  *   ss_sim3_mutual_*           the result ss_sim3_* left in device memory
  *   ss_pnp_*                   MLPnPsolver's RANSAC of Tracking::Relocalization: a pose from the 2D-3D matches of SearchByBoW against
  *                              each relocalisation candidate, with no prior
+ *   ss_refresh_*               MapPoint::UpdateNormalAndDepth, MapPoint::ComputeDistinctiveDescriptors and MapPoint::Observations()
+ *                              over the map ss_covis_set_map_rows keeps: after a fusion, a bundle adjustment or a loop correction
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
  *   ss_last_error              the cerr diagnostics of the shim (:457-469, :523-551)
  *
@@ -2032,6 +2034,11 @@ int ss_global_ba_host(const ss_proj_view *views, const double *start, const uint
  * (out NULL: counts only); SS_ERR_INVALID_ARG (negative) for a NULL table or a bad count.  Pure host code. */
 int ss_global_ba_obs_from_idx_host(const ss_keypoint *kp, const float *right, const int32_t *n_kp, int n_kf, int rows_per_frame,
                                    const int32_t *idx, int n_points, ss_gba_obs *out, int capacity);
+/* The keypoint row of each of those records: the same enumeration, the same ascending (point, kf) order, the same clamp and the
+ * same return convention, so out[m] is the row of record m of ss_global_ba_obs_from_idx_host's table (the obs_row of
+ * ss_covis_set_map_rows).  Pure host code. */
+int ss_global_ba_rows_from_idx_host(const int32_t *n_kp, int n_kf, int rows_per_frame, const int32_t *idx, int n_points,
+                                    int32_t *out, int capacity);
 /* n_problems problems on device arrays: d_points [n_blocks][point_rows] ss_map_point, d_point_skip uint8 [n_blocks][point_rows] or
  * NULL, d_n_points int32 [n_blocks] (clamped to 0 .. point_rows), d_start double [n_kf][12] (ss_pose_graph_device's d_poses feeds
  * it without a round trip), d_fixed uint8 [n_kf].  problems (n_problems), obs (n_obs) and views (n_kf) are HOST tables, copied
@@ -2119,6 +2126,12 @@ int ss_covis_params_default(ss_covis_params *p);
  * refused call leaves the map it found. */
 int ss_covis_set_map(ss_ctx *ctx, const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows,
                      const ss_gba_obs *obs, int n_obs, const uint8_t *cull_skip, int check_right);
+/* The same, and which keypoint row of its keyframe each record is: obs_row is a HOST int32 [n_obs] in the order of obs, or NULL
+ * (then this is ss_covis_set_map).  With rows the context keeps one int32 per record next to the points' lists, in their order, and
+ * the largest row of the map: what ss_refresh_device needs to find an observation's descriptor.  The covisibility queries do not
+ * read them.  One more refusal, SS_ERR_INVALID_ARG with a message that names the record: a row < 0 or >= SS_GUIDED_MAX_ROWS. */
+int ss_covis_set_map_rows(ss_ctx *ctx, const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows,
+                          const ss_gba_obs *obs, int n_obs, const uint8_t *cull_skip, int check_right, const int32_t *obs_row);
 /* n_rows keyframe rows: rows is a HOST table of call keyframe numbers in any order, duplicates allowed; NULL: every keyframe of
  * the map in order (n_rows must be the map's n_kf).  d_nb int32 [n_rows][cap][2], d_row ss_covis_row [n_rows]; every output byte
  * is written exactly once.  n_rows == 0: SS_OK, nothing written.  SS_ERR_STATE: no map is set.  SS_ERR_INVALID_ARG, with a message:
@@ -2151,6 +2164,90 @@ int ss_covis_frames_host(const ss_gba_problem *problems, int n_problems, int n_k
  * NULL table or a bad count.  Pure host code. */
 int ss_covis_edges_host(const int32_t *nb, const ss_covis_row *row, const int32_t *row_kf, int n_rows, int cap, int min_weight,
                         int32_t *edges, int capacity);
+
+/* ---- Map-point refresh: MapPoint::UpdateNormalAndDepth and MapPoint::ComputeDistinctiveDescriptors for every selected point of
+ * the context's map in one call, with MapPoint::Observations() reported per point: what a triangulation, a fusion, a bundle
+ * adjustment or a loop correction leaves stale in the fields the projection search reads (nx, ny, nz, min_dist, max_dist of an
+ * ss_map_point and the point's row of d_point_desc).  tests/refresh_ref.py is its normative statement; DESIGN.md section 32.  An
+ * addition to ABI 5: nothing existing changes --------------------------------------------------------------------------------------
+ * The map is the context's (ss_covis_set_map_rows: the points' lists in ascending kf, and each record's keypoint row).
+ * Inputs.  Per block b of a problem q of the map: d_points[b][i] and d_n_points[b] clamped to 0 .. point_rows; views[k].ow of every
+ * keyframe of the call (a HOST ss_proj_view table; only ow is read); scale[] and n_levels of the context; optionally d_ref_kf
+ * (int32 [n_blocks][point_rows]: the point's reference keyframe relative to its problem) and d_select (uint8
+ * [n_blocks][point_rows]); d_desc, uint8 [n_kf][rows_per_frame][32]: the descriptors of the map's keyframes by call keyframe number.
+ * Selection.  Row i of block b is refreshed iff the block belongs to a problem, i < n_points, its select byte (if given) is 0 and
+ * x, y, z are finite; so the d_point_flags of ss_local_ba_* and ss_global_ba_* (0 = optimised) serve as d_select as they lie.  Any
+ * other row has state -1.
+ * Observations.  The records of the point's list whose octave lies in 0 .. n_levels-1, in ascending kf, numbered a = 0 .. n-1;
+ * count = n + (the stereo ones), MapPoint::Observations().  n == 0: state 1.
+ * Geometry (UpdateNormalAndDepth; all in double from the float32 inputs widened, one IEEE operation per step, no contraction).
+ * Per observation d = P - ow_k, len = sqrt((dx*dx + dy*dy) + dz*dz); any len that is not > 0 or not finite: state 2.  Per component
+ * the sum of the terms d[c] / len is a tree of 64 slots: slot s adds the terms a = s, s + 64, ... in ascending a from +0.0, and the
+ * slots fold by halving (one 64-slot group of the global bundle adjustment's trees).  normal[c] = sum[c] / (double)n; upstream does
+ * not renormalise.  The reference keyframe is d_ref_kf's entry if it is given and names an observation of the list, otherwise
+ * observation 0 (upstream's EraseObservation falls back to mObservations.begin(); our order is kf order, its is pointer order).
+ * level = the octave of the reference's record, dist = its len, max_dist = dist * (double)scale[level], min_dist = max_dist /
+ * (double)scale[n_levels-1].  Each of the five numbers is rounded to float32 once.  Deviation: upstream runs Eigen float32; this
+ * is the triangulation's deviation, so a refreshed point and a triangulated one follow one text.
+ * Descriptor (ComputeDistinctiveDescriptors).  Observation a's descriptor is row obs_row of keyframe first_kf + kf of d_desc.
+ * D[a][b] is the Hamming distance over all 256 bits, D[a][a] = 0.  median_a is the element of rank (n-1)/2 (integer division;
+ * upstream's 0.5*(N-1) truncated) of row a in ascending order, the self distance included.  The winner is the lowest median, the
+ * lowest a on a tie: the minimum of median << 14 | a (a < 16384 = SS_GBA_MAX_KF).  Upstream's tie is the first in pointer order: the
+ * only deviation.  All of it is integer and order-free.
+ * Outputs.  For a state-0 row: nx, ny, nz, min_dist, max_dist of d_points[b][i] if geometry is set, the 32 bytes of
+ * d_point_desc[b][i] if descriptor is set.  x, y, z are never written, nor anything of a row whose state is not 0.  d_info
+ * [n_blocks][point_rows] ss_refresh_info: ref_kf is the one used, best_kf the winner's keyframe (both relative to the problem);
+ * states 1 and 2 carry n_obs and count, state -1 zero counts; ref_kf, level, best_kf and best_median are -1 in a row whose state is
+ * not 0, ref_kf and level also with geometry 0 (then state 2 cannot occur), best_* also with descriptor 0.  d_summary [n_blocks]
+ * ss_refresh_summary: n_rows is the clamped n_points of a block of a problem (0 for a block of none), n_selected the rows whose
+ * state is not -1, then the rows of state 0, 1 and 2, and the largest n_obs.  Every byte of both is written exactly once per call.
+ * With the caller stay mnFound / mnVisible, applying a culling decision and bad flags; the fisheye right-eye observations of
+ * UpdateNormalAndDepth are not modelled. */
+typedef struct {            /* 32 bytes */
+    int32_t geometry;       /* 0 / 1; default 1: UpdateNormalAndDepth */
+    int32_t descriptor;     /* 0 / 1; default 1: ComputeDistinctiveDescriptors.  At least one must be set */
+    int32_t reserved[6];    /* must be 0 */
+} ss_refresh_params;
+typedef struct {            /* 32 bytes, one per point row */
+    int32_t state;          /* 0 refreshed, 1 no observation, 2 a camera centre on the point (or a distance not finite), -1 not selected */
+    int32_t n_obs, count;   /* the observations; with the stereo ones once more: MapPoint::Observations() */
+    int32_t ref_kf, level;
+    int32_t best_kf, best_median;
+    int32_t reserved;       /* 0 */
+} ss_refresh_info;
+typedef struct {            /* 32 bytes, one per block */
+    int32_t status;         /* SS_OK */
+    int32_t n_rows, n_selected, n_refreshed, n_no_obs, n_degenerate, max_obs;
+    int32_t reserved;       /* 0 */
+} ss_refresh_summary;
+int ss_refresh_params_default(ss_refresh_params *p);
+/* Replaces MapPoint::UpdateNormalAndDepth and MapPoint::ComputeDistinctiveDescriptors over the context's map (its n_kf, n_blocks
+ * and point_rows).  d_points [n_blocks][point_rows] ss_map_point (read and written), d_point_desc [n_blocks][point_rows][32]
+ * (written), d_n_points int32 [n_blocks], d_ref_kf / d_select as above or NULL, d_desc as above, views a HOST table of the map's
+ * n_kf views, copied before the call returns; d_info and d_summary as above.  With descriptor 0, d_desc and d_point_desc may be
+ * NULL.  Descriptors and points on 16-byte boundaries, as everywhere.  SS_ERR_STATE: no map, or a map set without rows while
+ * descriptor is set (a geometry-only call needs no rows).  SS_ERR_INVALID_ARG, with a message: rows_per_frame not above the map's
+ * largest row or above SS_GUIDED_MAX_ROWS, n_kf * rows_per_frame above 2^31 - 1, a parameter out of range, a reserved field that is
+ * not 0, a NULL buffer that the flags require.  Asynchronous on the context's stream. */
+int ss_refresh_device(ss_ctx *ctx, void *d_points, void *d_point_desc, const void *d_n_points, const void *d_ref_kf,
+                      const void *d_select, const void *d_desc, int rows_per_frame, const ss_proj_view *views,
+                      const ss_refresh_params *p, void *d_info, void *d_summary);
+/* One problem of n_kf keyframes and n_points points with host pointers in and out, synchronous: sets the context's map to it with
+ * its rows (ss_covis_set_map_rows, the points as blocks of min(n_points, SS_GUIDED_MAX_ROWS) rows, as ss_covis lays them out),
+ * refreshes points and point_desc in place and returns info [n_points] and one summary per block.  ref_kf and select [n_points] or
+ * NULL; desc [n_kf][rows_per_frame][32]; obs_row [n_obs] (NULL only with descriptor 0). */
+int ss_refresh(ss_ctx *ctx, const ss_proj_view *views, int n_kf, ss_map_point *points, uint8_t *point_desc, int n_points,
+               const int32_t *ref_kf, const uint8_t *select, const ss_gba_obs *obs, const int32_t *obs_row, int n_obs, int check_right,
+               const uint8_t *desc, int rows_per_frame, const ss_refresh_params *p, ss_refresh_info *info, ss_refresh_summary *summary);
+/* The whole rule on the host from the text the kernels compile (csrc/ss_refresh_steps.h); needs no device.  The map's arguments
+ * are ss_covis_set_map_rows', with the pyramid's table in the place of the context; the rest are ss_refresh_device's with host
+ * arrays.  Arguments are checked as the device calls check them: SS_ERR_INVALID_ARG (a map without rows under descriptor:
+ * SS_ERR_STATE), and the message in err (err_bytes of it; NULL: none). */
+int ss_refresh_host(const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs,
+                    int n_obs, int check_right, const int32_t *obs_row, const float *scale, int n_levels, ss_map_point *points,
+                    uint8_t *point_desc, const int32_t *n_points, const int32_t *ref_kf, const uint8_t *select, const uint8_t *desc,
+                    int rows_per_frame, const ss_proj_view *views, const ss_refresh_params *p, ss_refresh_info *info,
+                    ss_refresh_summary *summary, char *err, int err_bytes);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

@@ -470,6 +470,8 @@ int ss_destroy(ss_ctx *c)
     staged_free(c->covis_tab);
     staged_free(c->covis_call_tab);
     dev_free(c->d_covis_io);
+    staged_free(c->refresh_tab);
+    dev_free(c->d_refresh_io);
     dev_free(c->d_sim3opt_ws);
     dev_free(c->d_sim3opt_io);
     staged_free(c->sim3opt_tab);

@@ -25,6 +25,7 @@
 #include "ss_pnp_steps.h"
 #include "ss_pose_steps.h"
 #include "ss_proj_steps.h"
+#include "ss_refresh_steps.h"
 #include "ss_sim3_steps.h"
 #include "ss_sim3opt_steps.h"
 #include "ss_two_view_steps.h"
@@ -2708,6 +2709,21 @@ int ss_global_ba_obs_from_idx_host(const ss_keypoint *kp, const float *right, co
     return n > INT32_MAX ? SS_ERR_INVALID_ARG : (int)n;
 }
 
+int ss_global_ba_rows_from_idx_host(const int32_t *n_kp, int n_kf, int rows_per_frame, const int32_t *idx, int n_points, int32_t *out, int capacity)
+{
+    if (n_kf < 0 || n_points < 0 || rows_per_frame < 1 || capacity < 0) return SS_ERR_INVALID_ARG;
+    if (n_kf > 0 && n_points > 0 && (!n_kp || !idx)) return SS_ERR_INVALID_ARG;
+    int64_t n = 0;
+    for (int i = 0; i < n_points; i++)
+        for (int k = 0; k < n_kf; k++) {
+            const int nk = std::min(std::max(n_kp[k], 0), rows_per_frame), row = idx[(size_t)k * n_points + i];
+            if (row < 0 || row >= nk) continue;
+            if (out && n < capacity) out[n] = row;
+            n++;
+        }
+    return n > INT32_MAX ? SS_ERR_INVALID_ARG : (int)n;
+}
+
 int ss_global_ba_host(const ss_proj_view *views, const double *start, const uint8_t *fixed, int n_kf, const float *scale, int n_levels, const ss_map_point *points,
                       const uint8_t *point_skip, int n_points, const ss_gba_obs *obs, int n_obs, const ss_gba_params *p, double *poses, double *xyz,
                       uint8_t *point_flags, uint8_t *obs_flags, ss_gba_result *result, char *err, int err_bytes)
@@ -2950,7 +2966,9 @@ struct covis_host_tables {
     std::vector<ss_covis_prob> prob;
     std::vector<int32_t> kf_prob, blk_prob, pt_off, pt_cnt, kf_off, kf_cnt, kf_item;
     std::vector<uint32_t> pt_item;
-    int n_kf = 0, n_blocks = 0, point_rows = 0, max_kf = 0;
+    std::vector<int32_t> pt_row, long_pts; /* with rows: each record's keypoint row, in the order of pt_item; the points of a list above one wave's */
+    int n_kf = 0, n_blocks = 0, point_rows = 0, max_kf = 0, max_row = -1, max_cnt = 0;
+    bool has_rows = false;
     size_t items = 0;
     ss_covis_tab view() const
     {
@@ -2966,7 +2984,7 @@ struct covis_host_tables {
 /* The checks of ss_covis_set_map and the lists of every problem into t.  The message of the first rule that is broken, or empty.  May
  * throw std::bad_alloc: the tables grow with the caller's counts */
 static std::string covis_build(const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs,
-                               const uint8_t *cull_skip, bool check_right, int n_levels, covis_host_tables &t)
+                               const uint8_t *cull_skip, bool check_right, int n_levels, covis_host_tables &t, const int32_t *obs_row = nullptr)
 {
     if (n_kf < 0 || n_problems < 0 || n_blocks < 0 || n_obs < 0 || point_rows < 1) return "covis: bad keyframe, problem, block, row or record count";
     if (point_rows > SS_GUIDED_MAX_ROWS)
@@ -2984,6 +3002,9 @@ static std::string covis_build(const ss_gba_problem *problems, int n_problems, i
     for (int q = 0; q < n_problems; q++) t.items += (size_t)problems[q].n_obs;
     t.pt_item.assign(t.items + 1, 0u), t.kf_item.assign(2 * t.items + 2, 0);
     t.prob.resize((size_t)n_problems);
+    t.has_rows = obs_row != nullptr;
+    t.pt_row.assign(obs_row ? t.items + 1 : 0, 0);
+    std::vector<int32_t> from;
     size_t base = 0;
     for (int q = 0; q < n_problems; q++) {
         const ss_gba_problem &b = problems[q];
@@ -2992,9 +3013,10 @@ static std::string covis_build(const ss_gba_problem *problems, int n_problems, i
         const int P = b.n_blocks * point_rows;
         const size_t p0 = (size_t)b.first_block * point_rows;
         int bad = 0;
+        if (obs_row) from.assign((size_t)b.n_obs + 1, 0);
         const int why = ss_covis_tables(b.n_kf, P, obs + b.first_obs, cull_skip ? cull_skip + b.first_obs : nullptr, b.n_obs, n_levels, check_right, (int)base, (int)p0,
                                         t.pt_off.data() + p0, t.pt_cnt.data() + p0, t.kf_off.data() + b.first_kf, t.kf_cnt.data() + b.first_kf, t.pt_item.data() + base,
-                                        t.kf_item.data() + 2 * base, &bad);
+                                        t.kf_item.data() + 2 * base, &bad, obs_row ? from.data() : nullptr);
         if (why != 0) {
             const ss_gba_obs &o = obs[b.first_obs + bad];
             const std::string rec = "covis: problem " + std::to_string(q) + ": record " + std::to_string(b.first_obs + bad) + ": ";
@@ -3003,7 +3025,19 @@ static std::string covis_build(const ss_gba_problem *problems, int n_problems, i
             if (why == 3) return rec + "the pair (kf " + std::to_string(o.kf) + ", point " + std::to_string(o.point) + ") has a record already";
             return rec + "keyframe " + std::to_string(o.kf) + " has more than SS_COVIS_MAX_ROW_ITEMS (" + std::to_string(SS_COVIS_MAX_ROW_ITEMS) + ") records";
         }
+        for (int s = 0; obs_row && s < b.n_obs; s++) {
+            const int m = b.first_obs + from[(size_t)s], row = obs_row[m];
+            if (row < 0 || row >= SS_GUIDED_MAX_ROWS)
+                return "covis: problem " + std::to_string(q) + ": record " + std::to_string(m) + ": row " + std::to_string(row) + " outside 0 .. SS_GUIDED_MAX_ROWS - 1 (" +
+                       std::to_string(SS_GUIDED_MAX_ROWS - 1) + ")";
+            t.pt_row[base + (size_t)s] = row;
+            t.max_row = std::max(t.max_row, row);
+        }
         base += (size_t)b.n_obs;
+    }
+    for (size_t gp = 0; gp < NP; gp++) {
+        t.max_cnt = std::max(t.max_cnt, (int)t.pt_cnt[gp]);
+        if (t.pt_cnt[gp] > SS_REFRESH_SHORT) t.long_pts.push_back((int32_t)gp);
     }
     return std::string();
 }
@@ -3082,18 +3116,23 @@ int ss_covis_edges_host(const int32_t *nb, const ss_covis_row *row, const int32_
 }
 
 static int covis_set_map(ss_ctx *c, const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs,
-                         const uint8_t *cull_skip, int check_right)
+                         const uint8_t *cull_skip, int check_right, const int32_t *obs_row)
 {
     int n_levels = 1;
     float scale[SS_MAX_LEVELS];
     const int rc = context_pyramid(c, "covis", &n_levels, scale);
     if (rc != SS_OK) return rc;
     covis_host_tables t;
-    const std::string msg = covis_build(problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, cull_skip, check_right != 0, n_levels, t);
+    const std::string msg = covis_build(problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, cull_skip, check_right != 0, n_levels, t, obs_row);
     if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
-    if (n_problems == 0) {
+    auto no_map = [&]() {
         c->covis_map = ss_covis_tab();
         c->covis_items = 0;
+        c->covis_pt_row = c->covis_long = nullptr;
+        c->covis_max_row = -1, c->covis_n_long = c->covis_max_cnt = 0;
+    };
+    if (n_problems == 0) {
+        no_map();
         return SS_OK;
     }
     /* the tables, each on a 16-byte boundary */
@@ -3105,7 +3144,7 @@ static int covis_set_map(ss_ctx *c, const ss_gba_problem *problems, int n_proble
         return o;
     };
     const size_t o_prob = place(nq * sizeof(ss_covis_prob)), o_kfp = place(K * 4), o_blp = place(B * 4), o_kfo = place(K * 4), o_kfc = place(K * 4), o_pto = place(NP * 4),
-                 o_ptc = place(NP * 4), o_pti = place(S * 4), o_kfi = place(S * 8);
+                 o_ptc = place(NP * 4), o_pti = place(S * 4), o_kfi = place(S * 8), o_row = place(t.has_rows ? S * 4 : 0), o_long = place(t.long_pts.size() * 4);
     {
         stage_timer tm(c, "covis_upload", (int64_t)at);
         const int up = staged_upload(c, c->covis_tab, at + 16, [&](uint8_t *h) {
@@ -3116,9 +3155,11 @@ static int covis_set_map(ss_ctx *c, const ss_gba_problem *problems, int n_proble
             memcpy(h + o_kfc, t.kf_cnt.data(), K * 4);
             if (NP) memcpy(h + o_pto, t.pt_off.data(), NP * 4), memcpy(h + o_ptc, t.pt_cnt.data(), NP * 4);
             if (S) memcpy(h + o_pti, t.pt_item.data(), S * 4), memcpy(h + o_kfi, t.kf_item.data(), S * 8);
+            if (S && t.has_rows) memcpy(h + o_row, t.pt_row.data(), S * 4);
+            if (!t.long_pts.empty()) memcpy(h + o_long, t.long_pts.data(), t.long_pts.size() * 4);
         });
         if (up != SS_OK) {
-            c->covis_map = ss_covis_tab(); /* the buffer may have moved */
+            no_map(); /* the buffer may have moved */
             return up;
         }
     }
@@ -3131,19 +3172,28 @@ static int covis_set_map(ss_ctx *c, const ss_gba_problem *problems, int n_proble
     m.pt_item = c->covis_tab.as<uint32_t>(o_pti), m.kf_item = c->covis_tab.as<int32_t>(o_kfi);
     c->covis_map = m;
     c->covis_items = (int64_t)S;
+    c->covis_pt_row = t.has_rows ? c->covis_tab.as<int32_t>(o_row) : nullptr;
+    c->covis_long = c->covis_tab.as<int32_t>(o_long);
+    c->covis_max_row = t.max_row, c->covis_n_long = (int)t.long_pts.size(), c->covis_max_cnt = t.max_cnt;
     return SS_OK;
+}
+
+int ss_covis_set_map_rows(ss_ctx *c, const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs,
+                          const uint8_t *cull_skip, int check_right, const int32_t *obs_row)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    try {
+        return covis_set_map(c, problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, cull_skip, check_right, obs_row);
+    } catch (const std::bad_alloc &) {
+        return fail(c, SS_ERR_NO_MEMORY, "covis: no host memory for the tables of the map");
+    }
 }
 
 int ss_covis_set_map(ss_ctx *c, const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs,
                      const uint8_t *cull_skip, int check_right)
 {
-    if (!c) return SS_ERR_INVALID_ARG;
-    (void)hipSetDevice(c->device);
-    try {
-        return covis_set_map(c, problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, cull_skip, check_right);
-    } catch (const std::bad_alloc &) {
-        return fail(c, SS_ERR_NO_MEMORY, "covis: no host memory for the tables of the map");
-    }
+    return ss_covis_set_map_rows(c, problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, cull_skip, check_right, nullptr);
 }
 
 /* the checks, the table and the launch of both device forms */
@@ -3220,6 +3270,166 @@ int ss_covis(ss_ctx *c, int n_kf, int n_points, const ss_gba_obs *obs, int n_obs
         return rc;
     }
     return io_fetch(c, io, PIECES);
+}
+
+/* ---- map-point refresh (csrc/ss_refresh.hip, csrc/ss_refresh_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *refresh_params_error(const ss_refresh_params *p)
+{
+    if (!p) return "refresh: params is NULL";
+    if (p->geometry != 0 && p->geometry != 1) return "refresh: geometry must be 0 or 1";
+    if (p->descriptor != 0 && p->descriptor != 1) return "refresh: descriptor must be 0 or 1";
+    if (p->geometry == 0 && p->descriptor == 0) return "refresh: geometry or descriptor must be set";
+    for (int k = 0; k < 6; k++)
+        if (p->reserved[k] != 0) return "refresh: the reserved fields must be 0";
+    return nullptr;
+}
+
+int ss_refresh_params_default(ss_refresh_params *p)
+{
+    if (!p) return SS_ERR_INVALID_ARG;
+    *p = ss_refresh_params{1, 1, {0, 0, 0, 0, 0, 0}};
+    return SS_OK;
+}
+
+/* the checks of a call against a map of n_kf keyframes whose largest row is max_row (`what` heads the messages), or empty */
+static std::string refresh_call_error(const std::string &what, int n_kf, int max_row, int rows_per_frame, const ss_refresh_params *p)
+{
+    if (p->descriptor == 0) return std::string();
+    if (rows_per_frame > SS_GUIDED_MAX_ROWS)
+        return what + ": rows_per_frame " + std::to_string(rows_per_frame) + " exceeds SS_GUIDED_MAX_ROWS (" + std::to_string(SS_GUIDED_MAX_ROWS) + ")";
+    if (rows_per_frame <= max_row || rows_per_frame < 1)
+        return what + ": rows_per_frame " + std::to_string(rows_per_frame) + " is not above the map's largest row " + std::to_string(max_row);
+    if ((int64_t)n_kf * rows_per_frame > INT32_MAX) return what + ": n_kf * rows_per_frame exceeds 2^31 - 1 descriptor rows";
+    return std::string();
+}
+
+int ss_refresh_device(ss_ctx *c, void *d_points, void *d_point_desc, const void *d_n_points, const void *d_ref_kf, const void *d_select, const void *d_desc,
+                      int rows_per_frame, const ss_proj_view *views, const ss_refresh_params *p, void *d_info, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const std::string what = "ss_refresh_device";
+    if (const char *msg = refresh_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    const ss_covis_tab &m = c->covis_map;
+    if (m.n_kf == 0) return fail(c, SS_ERR_STATE, what + ": no map (ss_covis_set_map_rows)");
+    if (p->descriptor != 0 && !c->covis_pt_row) return fail(c, SS_ERR_STATE, what + ": the map was set without rows (ss_covis_set_map_rows), which descriptor needs");
+    const std::string msg = refresh_call_error(what, m.n_kf, c->covis_max_row, rows_per_frame, p);
+    if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (!d_points || !d_n_points || !views || !d_info || !d_summary || (p->descriptor != 0 && (!d_desc || !d_point_desc))) return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
+    if (m.n_blocks == 0) return SS_OK;
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS];
+    int rc = context_pyramid(c, "refresh", &n_levels, scale);
+    if (rc != SS_OK) return rc;
+    /* the tables of the call: every keyframe's ow, then the pyramid's table */
+    const size_t K = (size_t)m.n_kf, o_scale = (K * 12 + 15) & ~(size_t)15;
+    rc = staged_upload(c, c->refresh_tab, o_scale + SS_MAX_LEVELS * 4, [&](uint8_t *h) {
+        for (size_t k = 0; k < K; k++) memcpy(h + 12 * k, views[k].ow, 12);
+        memcpy(h + o_scale, scale, sizeof(scale[0]) * (size_t)n_levels);
+    });
+    if (rc != SS_OK) return rc;
+    ssk_refresh_call g;
+    g.tab = &m, g.pt_row = c->covis_pt_row, g.long_pts = c->covis_long, g.n_long = c->covis_n_long, g.max_cnt = c->covis_max_cnt;
+    g.points = (ss_map_point *)d_points, g.point_desc = (uint8_t *)d_point_desc, g.np = (const int32_t *)d_n_points;
+    g.ref_kf = (const int32_t *)d_ref_kf, g.select = (const uint8_t *)d_select, g.desc = (const uint8_t *)d_desc, g.rows_per_frame = rows_per_frame;
+    g.ow = c->refresh_tab.as<float>(), g.scale = c->refresh_tab.as<float>(o_scale), g.n_levels = n_levels;
+    g.geometry = p->geometry, g.descriptor = p->descriptor;
+    g.info = (ss_refresh_info *)d_info, g.summary = (ss_refresh_summary *)d_summary;
+    /* the stage's bytes: per record its word of the list, the keyframe's ow (geometry), its row and its descriptor (descriptor); per
+     * point row its run, the point and its info, the fields (geometry) or the descriptor (descriptor) written; per block its count
+     * and its summary */
+    const int64_t NP = (int64_t)m.n_blocks * m.point_rows;
+    const int64_t bytes = c->covis_items * (4 + 12 * p->geometry + 36 * p->descriptor) + NP * (8 + 32 + 32 + 20 * p->geometry + 32 * p->descriptor) + (int64_t)m.n_blocks * 36;
+    hipError_t e;
+    {
+        stage_timer tm(c, "refresh", bytes);
+        e = (hipError_t)ssk_refresh(c->stream, g);
+    }
+    HIP_TRY(c, e);
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+/* the blocks ss_covis and ss_refresh lay n_points points out in: rows per block, blocks */
+static void single_problem_blocks(int n_points, int *pr, int *nblk)
+{
+    *pr = std::min(std::max(n_points, 1), SS_GUIDED_MAX_ROWS);
+    *nblk = n_points > 0 ? (n_points + *pr - 1) / *pr : 0;
+}
+
+int ss_refresh(ss_ctx *c, const ss_proj_view *views, int n_kf, ss_map_point *points, uint8_t *point_desc, int n_points, const int32_t *ref_kf, const uint8_t *select,
+               const ss_gba_obs *obs, const int32_t *obs_row, int n_obs, int check_right, const uint8_t *desc, int rows_per_frame, const ss_refresh_params *p,
+               ss_refresh_info *info, ss_refresh_summary *summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (const char *msg = refresh_params_error(p)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_points < 1 || n_points > SS_GBA_MAX_POINTS || n_obs < 0 || n_kf < 1) return fail(c, SS_ERR_INVALID_ARG, "refresh: n_points must be 1 .. SS_GBA_MAX_POINTS, n_kf >= 1 and n_obs >= 0");
+    if (!views || !points || !info || !summary || (p->descriptor != 0 && (!desc || !point_desc || (n_obs > 0 && !obs_row)))) return fail(c, SS_ERR_INVALID_ARG, "ss_refresh: NULL buffer");
+    int pr, nblk;
+    single_problem_blocks(n_points, &pr, &nblk);
+    const ss_gba_problem problem = {0, n_kf, 0, nblk, 0, n_obs, {0, 0}};
+    int rc = ss_covis_set_map_rows(c, &problem, 1, n_kf, nblk, pr, obs, n_obs, nullptr, check_right, p->descriptor != 0 ? obs_row : nullptr);
+    if (rc != SS_OK) return rc;
+    const std::string msg = refresh_call_error("ss_refresh", n_kf, c->covis_max_row, rows_per_frame, p);
+    if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+    std::vector<int32_t> np((size_t)nblk);
+    for (int b = 0; b < nblk; b++) np[(size_t)b] = std::min(pr, n_points - b * pr);
+    const size_t N = (size_t)n_points, R = (size_t)nblk * pr, D = p->descriptor != 0 ? (size_t)n_kf * rows_per_frame * 32 : 0;
+    enum { PTS, PDESC, NPTS, REF, SEL, DESC, INFO, SUM, PIECES };
+    io_piece io[PIECES] = {{points, points, R * 32, N * 32},
+                           {p->descriptor != 0 ? point_desc : nullptr, p->descriptor != 0 ? point_desc : nullptr, R * 32, N * 32},
+                           {np.data(), nullptr, (size_t)nblk * 4, (size_t)nblk * 4},
+                           {ref_kf, nullptr, ref_kf ? R * 4 : 0, ref_kf ? N * 4 : 0},
+                           {select, nullptr, select ? R : 0, select ? N : 0},
+                           {desc, nullptr, D, D},
+                           {nullptr, info, R * 32, N * 32},
+                           {nullptr, summary, (size_t)nblk * 32, (size_t)nblk * 32}};
+    rc = io_send(c, c->d_refresh_io, io, PIECES);
+    if (rc == SS_OK)
+        rc = ss_refresh_device(c, io[PTS].d, p->descriptor != 0 ? io[PDESC].d : nullptr, io[NPTS].d, ref_kf ? io[REF].d : nullptr, select ? io[SEL].d : nullptr,
+                               p->descriptor != 0 ? io[DESC].d : nullptr, rows_per_frame, views, p, io[INFO].d, io[SUM].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    return io_fetch(c, io, PIECES);
+}
+
+int ss_refresh_host(const ss_gba_problem *problems, int n_problems, int n_kf, int n_blocks, int point_rows, const ss_gba_obs *obs, int n_obs, int check_right,
+                    const int32_t *obs_row, const float *scale, int n_levels, ss_map_point *points, uint8_t *point_desc, const int32_t *n_points, const int32_t *ref_kf,
+                    const uint8_t *select, const uint8_t *desc, int rows_per_frame, const ss_proj_view *views, const ss_refresh_params *p, ss_refresh_info *info,
+                    ss_refresh_summary *summary, char *err, int err_bytes)
+{
+    const std::string what = "ss_refresh_host";
+    if (const char *msg = refresh_params_error(p)) return gba_refuse(err, err_bytes, msg);
+    if (!scale || n_levels < 1 || n_levels > SS_MAX_LEVELS) return gba_refuse(err, err_bytes, "refresh: no pyramid table of 1 .. SS_MAX_LEVELS levels");
+    try {
+        covis_host_tables t;
+        std::string msg = covis_build(problems, n_problems, n_kf, n_blocks, point_rows, obs, n_obs, nullptr, check_right != 0, n_levels, t, obs_row);
+        if (!msg.empty()) return gba_refuse(err, err_bytes, msg);
+        if (n_problems == 0 || (p->descriptor != 0 && !obs_row)) {
+            (void)gba_refuse(err, err_bytes, n_problems == 0 ? what + ": no map" : what + ": the map has no rows, which descriptor needs");
+            return SS_ERR_STATE;
+        }
+        msg = refresh_call_error(what, n_kf, t.max_row, rows_per_frame, p);
+        if (msg.empty() && (!points || !n_points || !views || !info || !summary || (p->descriptor != 0 && (!desc || !point_desc)))) msg = what + ": NULL buffer";
+        if (!msg.empty()) return gba_refuse(err, err_bytes, msg);
+        const ss_covis_tab m = t.view();
+        std::vector<float> ow((size_t)n_kf * 3 + 1);
+        for (int k = 0; k < n_kf; k++) memcpy(&ow[(size_t)k * 3], views[k].ow, 12);
+        ss_refresh_host_in in;
+        in.pt_row = t.pt_row.data(), in.n_points = n_points, in.ref_kf = ref_kf, in.select = select, in.desc = desc, in.rows_per_frame = rows_per_frame;
+        in.ow = ow.data(), in.scale = scale, in.n_levels = n_levels, in.geometry = p->geometry, in.descriptor = p->descriptor;
+        for (int b = 0; b < n_blocks; b++) {
+            for (int i = 0; i < point_rows; i++) ss_refresh_row_host(m, in, b, i, points, point_desc, info);
+            ss_refresh_summary_host(m, b, n_points[b], info, summary + b);
+        }
+    } catch (const std::bad_alloc &) {
+        return SS_ERR_NO_MEMORY;
+    }
+    return SS_OK;
 }
 
 /* ---- PnP RANSAC (csrc/ss_pnp.hip, csrc/ss_pnp_steps.h) ---- */

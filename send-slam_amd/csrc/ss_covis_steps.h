@@ -92,9 +92,10 @@ struct ss_covis_tab {
  * pt_off, pt_cnt [P], kf_off, kf_cnt [n_kf], pt_item [n], kf_item [n][2]; the offsets stored start at item_base, the points at
  * point_base.  Two stable counting passes, first by kf, then by point, as ss_gba_tables.  Returns 0, or 1: a kf outside the problem,
  * 2: a point outside it, 3: a (kf, point) pair twice, 4: a keyframe with more than SS_COVIS_MAX_ROW_ITEMS records; *bad is then the
- * offending record's number in obs */
+ * offending record's number in obs.  from (NULL: not wanted) [n]: the record of obs that stands at each place of pt_item */
 static inline int ss_covis_tables(int n_kf, int P, const ss_gba_obs *obs, const uint8_t *skip, int n, int n_levels, bool check_right, int item_base, int point_base,
-                                  int32_t *pt_off, int32_t *pt_cnt, int32_t *kf_off, int32_t *kf_cnt, uint32_t *pt_item, int32_t *kf_item, int *bad)
+                                  int32_t *pt_off, int32_t *pt_cnt, int32_t *kf_off, int32_t *kf_cnt, uint32_t *pt_item, int32_t *kf_item, int *bad,
+                                  int32_t *from = nullptr)
 {
     for (int k = 0; k < n_kf; k++) kf_cnt[k] = 0;
     for (int i = 0; i < P; i++) pt_cnt[i] = 0;
@@ -117,6 +118,7 @@ static inline int ss_covis_tables(int n_kf, int P, const ss_gba_obs *obs, const 
         const int s = pt_off[o.point] + pt_cnt[o.point]++;
         pt_item[s] = ss_covis_pack(o.kf, o.octave, n_levels, check_right && o.right > 0.0f, skip && skip[m] != 0);
         orig[(size_t)s] = m;
+        if (from) from[s] = m;
     }
     for (int k = 0; k < n_kf; k++) kf_cnt[k] = 0;
     for (int i = 0; i < P; i++)

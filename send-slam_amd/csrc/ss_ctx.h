@@ -174,6 +174,13 @@ struct ss_ctx {
     staged_table covis_tab, covis_call_tab;
     ss_covis_tab covis_map;
     int64_t covis_items = 0; /* the records of the map's problems */
+    /* the map-point refresh: next to the map's lists, each record's keypoint row in the order of pt_item (NULL: the map was set
+     * without rows) with the largest of them, and the points whose list is longer than one wave's (their numbers, their longest
+     * list); the tables of a call (every keyframe's ow, then the pyramid's scale table); the host form's device copies */
+    const int32_t *covis_pt_row = nullptr, *covis_long = nullptr;
+    int covis_max_row = -1, covis_n_long = 0, covis_max_cnt = 0;
+    staged_table refresh_tab;
+    dev_buf<uint8_t> d_refresh_io;
     dev_buf<uint8_t> d_covis_io;
     /* PnP RANSAC: the workspace of a call (correspondences, models, poses, counts), the host form's device copies, the tables of a
      * call (views, then frame numbers, then block numbers) */

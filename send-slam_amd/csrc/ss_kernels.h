@@ -723,6 +723,27 @@ struct ssk_covis_call {
 };
 int ssk_covis_kf(hipStream_t s, const ssk_covis_call &g);     /* a hipError_t: the LDS attribute may be refused */
 int ssk_covis_frames(hipStream_t s, const ssk_covis_call &g);
+/* ss_refresh.hip: the map-point refresh (DESIGN.md "Map-point refresh").  One wave per point row whose list has at most 64 records,
+ * one workgroup per longer one (long_pts names them), then one workgroup per block for the summary: three launches */
+struct ssk_refresh_call {
+    const ss_covis_tab *tab = nullptr; /* HOST: the map's tables on the device */
+    const int32_t *pt_row = nullptr;   /* device [records] in the order of pt_item, or NULL (descriptor 0) */
+    const int32_t *long_pts = nullptr; /* device [n_long]: block * point_rows + row */
+    int n_long = 0, max_cnt = 0;       /* max_cnt: the longest list, which sizes the long kernel's dynamic LDS */
+    ss_map_point *points = nullptr;    /* device [n_blocks][point_rows] */
+    uint8_t *point_desc = nullptr;     /* device [n_blocks][point_rows][32] */
+    const int32_t *np = nullptr;       /* device [n_blocks] */
+    const int32_t *ref_kf = nullptr;   /* device [n_blocks][point_rows] or NULL */
+    const uint8_t *select = nullptr;   /* device [n_blocks][point_rows] or NULL */
+    const uint8_t *desc = nullptr;     /* device [n_kf][rows_per_frame][32] */
+    int rows_per_frame = 0;
+    const float *ow = nullptr;         /* device [n_kf][3] */
+    const float *scale = nullptr;      /* device [n_levels] */
+    int n_levels = 0, geometry = 0, descriptor = 0;
+    ss_refresh_info *info = nullptr;       /* device [n_blocks][point_rows] */
+    ss_refresh_summary *summary = nullptr; /* device [n_blocks] */
+};
+int ssk_refresh(hipStream_t s, const ssk_refresh_call &g); /* a hipError_t: the LDS attribute may be refused */
 /* The bookkeeping of SearchBySim3 (the rule: include/sendslam_orb.h).  One workgroup per pair: a base pass over the rows, a barrier,
  * a scatter pass in which every store to one address writes the same value.  marks writes skip1 and skip2; mutual marks the train
  * rows that carry a prior match in taken (workspace, [n_frames][rows]) and writes idx_out and the summary */

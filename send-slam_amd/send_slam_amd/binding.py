@@ -57,7 +57,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_global_ba_obs_from_idx_host", "ss_global_ba_device", "ss_global_ba", "ss_two_view_host", "ss_two_view_model_host",
            "ss_two_view_check_host", "ss_two_view_accept_host", "ss_two_view_beats_host", "ss_two_view_point_tests_host", "ss_two_view_pairs_device", "ss_two_view_batch_device", "ss_two_view",
            "ss_covis_params_default", "ss_covis_set_map", "ss_covis_kf_device", "ss_covis_frames_device", "ss_covis", "ss_covis_kf_host",
-           "ss_covis_frames_host", "ss_covis_edges_host"]
+           "ss_covis_frames_host", "ss_covis_edges_host", "ss_covis_set_map_rows", "ss_global_ba_rows_from_idx_host", "ss_refresh_params_default",
+           "ss_refresh_device", "ss_refresh", "ss_refresh_host"]
 
 
 class OrbParams(C.Structure):
@@ -1136,6 +1137,75 @@ def covis_edges(nb: np.ndarray, row: np.ndarray, row_kf, min_weight: int) -> np.
     return out
 
 
+def global_ba_rows_from_idx(idx: np.ndarray, n_kp, rows_per_frame: int) -> np.ndarray:
+    """ss_global_ba_rows_from_idx_host: the keypoint row of each record of global_ba_obs_from_idx(kp, idx, n_kp), kp being
+    [n_kf][rows_per_frame] -> int32, parallel to its table"""
+    nk = np.ascontiguousarray(n_kp, np.int32).reshape(-1)
+    ix = np.ascontiguousarray(idx, np.int32).reshape(len(nk), -1)
+    fn = load().ss_global_ba_rows_from_idx_host
+    args = (nk.ctypes.data if len(nk) else None, len(nk), rows_per_frame, ix.ctypes.data if ix.size else None, ix.shape[1])
+    n = fn(*args, None, 0)
+    if n < 0:
+        raise OrbError(n, "ss_global_ba_rows_from_idx_host refused its arguments")
+    out = np.zeros(n, np.int32)
+    if n and fn(*args, out.ctypes.data, n) != n:
+        raise OrbError(SS_ERR_STATE, "ss_global_ba_rows_from_idx_host: the count changed between two calls")
+    return out
+
+
+# ---- map-point refresh (the rule: include/sendslam_orb.h) ----
+class RefreshParams(C.Structure):
+    _fields_ = [("geometry", C.c_int32), ("descriptor", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+# ss_refresh_info: one per point row; ss_refresh_summary: one per block
+REFRESH_INFO_DTYPE = np.dtype([(n, "<i4") for n in ("state", "n_obs", "count", "ref_kf", "level", "best_kf", "best_median", "reserved")])
+REFRESH_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_rows", "n_selected", "n_refreshed", "n_no_obs", "n_degenerate", "max_obs", "reserved")])
+
+
+def refresh_params(geometry: int = 1, descriptor: int = 1, reserved=(0, 0, 0, 0, 0, 0)) -> RefreshParams:
+    """geometry: UpdateNormalAndDepth; descriptor: ComputeDistinctiveDescriptors; upstream calls the first alone after a bundle adjustment
+    or a loop correction, both after a fusion and a creation"""
+    return RefreshParams(geometry=int(geometry), descriptor=int(descriptor), reserved=(C.c_int32 * 6)(*reserved))
+
+
+def _refresh_rows(desc, n_kf, rows_per_frame):
+    if rows_per_frame is not None:
+        return int(rows_per_frame)
+    return 0 if desc is None else desc.reshape(max(n_kf, 1), -1, 32).shape[1]
+
+
+def refresh_host(problems, n_kf: int, n_blocks: int, point_rows: int, obs, obs_row, scale, points, point_desc, n_points, desc, views,
+                 params: RefreshParams, ref_kf=None, select=None, check_right: bool = False, rows_per_frame=None):
+    """ss_refresh_host: the whole rule on the host.  points MAP_POINT_DTYPE [n_blocks][point_rows] and point_desc uint8
+    [n_blocks][point_rows][32] are copied, refreshed and returned with REFRESH_INFO_DTYPE [n_blocks][point_rows] and REFRESH_SUMMARY_DTYPE
+    [n_blocks]; desc uint8 [n_kf][rows_per_frame][32] or None; obs_row int32 [n_obs] or None.  A refusal raises OrbError with the
+    library's message"""
+    pr, ob, _ = _covis_map_arrays(problems, obs, None)
+    rows = None if obs_row is None else np.ascontiguousarray(obs_row, np.int32).reshape(-1)
+    if rows is not None and len(rows) != len(ob):
+        raise ValueError("one keypoint row per observation record")
+    sc = np.ascontiguousarray(scale, np.float32).reshape(-1)
+    pts = np.array(points, MAP_POINT_DTYPE).reshape(max(n_blocks, 0), -1)
+    pd = None if point_desc is None else np.array(point_desc, np.uint8).reshape(max(n_blocks, 0), -1, 32)
+    npts = np.ascontiguousarray(n_points, np.int32).reshape(-1)
+    rk = None if ref_kf is None else np.ascontiguousarray(ref_kf, np.int32).reshape(-1)
+    sel = None if select is None else np.ascontiguousarray(select, np.uint8).reshape(-1)
+    ds = None if desc is None else np.ascontiguousarray(desc, np.uint8)
+    v = _views_array(views)
+    if len(v) != n_kf or len(npts) != n_blocks:
+        raise ValueError("one view per keyframe and one count per block")
+    info, summary = np.zeros((max(n_blocks, 0), max(point_rows, 0)), REFRESH_INFO_DTYPE), np.zeros(max(n_blocks, 0), REFRESH_SUMMARY_DTYPE)
+    err = C.create_string_buffer(512)
+    ptr = lambda a: None if a is None or not a.size else a.ctypes.data  # noqa: E731
+    rc = load().ss_refresh_host(ptr(pr), len(pr), n_kf, n_blocks, point_rows, ptr(ob), len(ob), int(check_right), ptr(rows), ptr(sc), len(sc), ptr(pts), ptr(pd),
+                                ptr(npts), ptr(rk), ptr(sel), ptr(ds), _refresh_rows(ds, n_kf, rows_per_frame), ptr(v), C.byref(params),
+                                ptr(info), ptr(summary), err, len(err))
+    if rc != SS_OK:
+        raise OrbError(rc, err.value.decode() or "the refresh host twin refused its arguments")
+    return pts, pd, info, summary
+
+
 class OrbError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libsendslam_orb: {message} (status {code})")
@@ -1319,6 +1389,14 @@ def load():
     lib.ss_covis_frames_host.argtypes = covis_map + [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CovisParams), C.c_int, C.c_void_p,
                                                      C.c_void_p, C.c_char_p, C.c_int]
     lib.ss_covis_edges_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.ss_covis_set_map_rows.argtypes = [C.c_void_p] + covis_map + [C.c_void_p]
+    lib.ss_global_ba_rows_from_idx_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.ss_refresh_params_default.argtypes = [C.POINTER(RefreshParams)]
+    lib.ss_refresh_device.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_void_p, C.POINTER(RefreshParams), C.c_void_p, C.c_void_p]
+    lib.ss_refresh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                               C.c_void_p, C.c_int, C.POINTER(RefreshParams), C.c_void_p, C.c_void_p]
+    lib.ss_refresh_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + \
+                                   [C.c_int, C.c_void_p, C.POINTER(RefreshParams), C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
     lib.ss_pnp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                 C.POINTER(PnpParams), C.c_int, C.c_void_p, C.c_void_p]
     lib.ss_pnp_model_host.argtypes = [C.POINTER(PnpParams)] + [C.c_void_p] * 6
@@ -2184,13 +2262,52 @@ class OrbContext:
         return poses, xyz, pf, of, res[0]
 
     # ---- covisibility: neighbour lists and culling counts from the map's incidence lists (the rule: include/sendslam_orb.h) ----
-    def covis_set_map(self, problems, n_kf: int, n_blocks: int, point_rows: int, obs, cull_skip=None, check_right: bool = False):
+    def covis_set_map(self, problems, n_kf: int, n_blocks: int, point_rows: int, obs, cull_skip=None, check_right: bool = False, obs_row=None):
         """the problems (GBA_PROBLEM_DTYPE) and the observation records (GBA_OBS_DTYPE, any order) global_ba_device takes, and optionally
-        one skip byte per record; the context keeps the map until the next call.  No problem clears it."""
+        one skip byte per record; the context keeps the map until the next call.  No problem clears it.  obs_row (int32, one per record:
+        its keypoint row in its keyframe) goes through ss_covis_set_map_rows: refresh_device needs it for the descriptors."""
         pr, ob, sk = _covis_map_arrays(problems, obs, cull_skip)
-        self._check(self._lib.ss_covis_set_map(self._h, pr.ctypes.data if len(pr) else None, len(pr), n_kf, n_blocks, point_rows,
-                                               ob.ctypes.data if len(ob) else None, len(ob), None if sk is None or not len(sk) else sk.ctypes.data,
-                                               int(check_right)))
+        args = (self._h, pr.ctypes.data if len(pr) else None, len(pr), n_kf, n_blocks, point_rows, ob.ctypes.data if len(ob) else None, len(ob),
+                None if sk is None or not len(sk) else sk.ctypes.data, int(check_right))
+        if obs_row is None:
+            self._check(self._lib.ss_covis_set_map(*args))
+            return
+        rows = np.ascontiguousarray(obs_row, np.int32).reshape(-1)
+        if len(rows) != len(ob):
+            raise ValueError("one keypoint row per observation record")
+        self._check(self._lib.ss_covis_set_map_rows(*args, rows.ctypes.data if len(rows) else np.zeros(1, np.int32).ctypes.data))
+
+    def refresh_device(self, d_points: int, d_point_desc: int, d_n_points: int, d_desc: int, rows_per_frame: int, views, params: RefreshParams,
+                       d_info: int, d_summary: int, d_ref_kf: int = 0, d_select: int = 0):
+        """UpdateNormalAndDepth and ComputeDistinctiveDescriptors over the context's map (covis_set_map with obs_row): d_points MAP_POINT_DTYPE
+        [n_blocks][point_rows] and d_point_desc uint8 [n_blocks][point_rows][32] are refreshed in place; d_desc uint8
+        [n_kf][rows_per_frame][32]; views one per keyframe of the map (only ow is read); d_ref_kf int32 and d_select uint8
+        [n_blocks][point_rows] or 0 (the d_point_flags of local_ba / global_ba serve as d_select); d_info REFRESH_INFO_DTYPE
+        [n_blocks][point_rows], d_summary REFRESH_SUMMARY_DTYPE [n_blocks]; asynchronous."""
+        v = _views_array(views)
+        self._check(self._lib.ss_refresh_device(self._h, C.c_void_p(d_points), C.c_void_p(d_point_desc), C.c_void_p(d_n_points), C.c_void_p(d_ref_kf),
+                                                C.c_void_p(d_select), C.c_void_p(d_desc), rows_per_frame, v.ctypes.data if len(v) else None, C.byref(params),
+                                                C.c_void_p(d_info), C.c_void_p(d_summary)))
+
+    def refresh(self, views, points, point_desc, obs, obs_row, desc, params: RefreshParams, ref_kf=None, select=None, check_right: bool = False):
+        """One problem, host arrays in and out -> (points, point_desc, info, summary) as refresh_host returns them for one block of
+        len(points) rows (more than 16384 points: blocks of 16384); the map of the context becomes this one."""
+        v = _views_array(views)
+        pts = np.array(points, MAP_POINT_DTYPE).reshape(-1)
+        n = len(pts)
+        pd = None if point_desc is None else np.array(point_desc, np.uint8).reshape(n, 32)
+        _, ob, _ = _covis_map_arrays(np.zeros(0, GBA_PROBLEM_DTYPE), obs, None)
+        rows = None if obs_row is None else np.ascontiguousarray(obs_row, np.int32).reshape(-1)
+        rk = None if ref_kf is None else np.ascontiguousarray(ref_kf, np.int32).reshape(-1)
+        sel = None if select is None else np.ascontiguousarray(select, np.uint8).reshape(-1)
+        ds = None if desc is None else np.ascontiguousarray(desc, np.uint8)
+        pr = min(max(n, 1), SS_GUIDED_MAX_ROWS)
+        info, summary = np.zeros(n, REFRESH_INFO_DTYPE), np.zeros((n + pr - 1) // pr, REFRESH_SUMMARY_DTYPE)
+        ptr = lambda a: None if a is None or not a.size else a.ctypes.data  # noqa: E731
+        self._check(self._lib.ss_refresh(self._h, ptr(v), len(v), ptr(pts), ptr(pd), n, ptr(rk), ptr(sel), ptr(ob), ptr(rows), len(ob), int(check_right), ptr(ds),
+                                         _refresh_rows(ds, len(v), None), C.byref(params), ptr(info), ptr(summary)))
+        return pts, pd, info, summary
+
 
     def covis_kf_device(self, rows, n_rows: int, params: CovisParams, cap: int, d_nb: int, d_row: int):
         """rows: call keyframe numbers (any order, duplicates allowed) or None: every keyframe of the map; d_nb int32 [n_rows][cap][2],

@@ -51,6 +51,8 @@
  *                              each relocalisation candidate, with no prior
  *   ss_refresh_*               MapPoint::UpdateNormalAndDepth, MapPoint::ComputeDistinctiveDescriptors and MapPoint::Observations()
  *                              over the map ss_covis_set_map_rows keeps: after a fusion, a bundle adjustment or a loop correction
+ *   ss_place_*                 KeyFrameDatabase: add / erase, DetectLoopCandidates, DetectNBestCandidates and
+ *                              DetectRelocalizationCandidates over an inverted file kept on the device
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
  *   ss_last_error              the cerr diagnostics of the shim (:457-469, :523-551)
  *
@@ -2248,6 +2250,114 @@ int ss_refresh_host(const ss_gba_problem *problems, int n_problems, int n_kf, in
                     uint8_t *point_desc, const int32_t *n_points, const int32_t *ref_kf, const uint8_t *select, const uint8_t *desc,
                     int rows_per_frame, const ss_proj_view *views, const ss_refresh_params *p, ss_refresh_info *info,
                     ss_refresh_summary *summary, char *err, int err_bytes);
+
+/* ---- Place recognition: KeyFrameDatabase (add / erase / DetectLoopCandidates / DetectNBestCandidates /
+ * DetectRelocalizationCandidates): from a new keyframe or a lost frame and a database of keyframes' BoW vectors, the few keyframes
+ * worth handing to the Sim3 or the PnP stage.  No ORB-SLAM3 source is in the reference tree: this is the library's own restatement,
+ * tests/place_ref.py is its normative statement, and parity with the real binary stays unpinned.  DESIGN.md section 33.  An
+ * addition to ABI 5: nothing existing changes -----------------------------------------------------------------------------------
+ * Database.  n_db BoW vectors as ss_bow_transform_* writes them: d_db_word int32 (ascending, distinct), d_db_value double, both
+ * [n_db][stride], d_db_count int32 [n_db] clamped to 0 .. stride: the arrays ss_bow_score_device takes, kept by the caller.  Row r
+ * is keyframe r of the call, numbered as ss_covis_set_map numbers them; problems is a HOST table of ss_gba_problem of which only
+ * first_kf and n_kf are read (n_kf in 1 .. SS_GBA_MAX_KF, the range inside the call, no keyframe in two problems).  A row's map is
+ * its problem; a row of no problem takes part in nothing.  d_db_skip, uint8 [n_db] or NULL, is upstream's erase / isBad: it is read
+ * at query time, so erasing a keyframe rebuilds nothing.  The inverted file: for every word 0 .. n_words-1 the rows whose vector
+ * holds it within its count; an entry whose word lies outside that range is in no list.  The order inside a list is free:
+ * everything that reads a list counts.
+ * Query q of n_q: its vector (a row of d_q_word / d_q_value [n_q][q_stride] with d_q_count [n_q]); q_kf[q], HOST: its own database
+ * row, or -1 for a frame; q_problem[q], HOST: its map (for q_kf >= 0 that row's problem); optionally its covisibility row as
+ * ss_covis_kf_device writes it (d_q_nb int32 [n_q][q_cap][2], d_q_row ss_covis_row [n_q]): the first n_written (clamped to 0 ..
+ * q_cap) entries, relative to q_problem, are the connected keyframes; an entry that names no keyframe of that problem is passed
+ * over.  NULL covisibility arrays: nothing is connected (the relocalisation form).
+ * 1. Shared words.  Row r is excluded iff it is skipped, belongs to no problem, r == q_kf, or it is connected.  words(r) is the
+ *    number of the query's words, within its count and in range, whose list holds r.  The sharing set is the non-excluded r with
+ *    words(r) > 0; empty: no candidates.
+ * 2. Word threshold.  max_common is the largest words(r) of the sharing set, min_common = (int)((float)max_common * common_ratio):
+ *    one float multiply, then truncation.  Survivors are the sharing rows with words > min_common.
+ * 3. Score.  s(r) = (float) of ss_bow_score_device's double for (query, r), rounded once.  The minimum score: mode 0, min_score;
+ *    mode 1 (LoopClosing::DetectLoop), start at 1.0f and, for each connected entry in list order whose row is not skipped, if
+ *    s(j) < m then m = s(j).  Seeds are the survivors with s >= the minimum score; none: no candidates.
+ * 4. Groups.  d_nb is int32 [n_db][nb_cap][2]: row r holds (kf relative to r's problem, weight), what ss_covis_kf_device writes
+ *    with rows == NULL (upstream: cap 10, min_weight 15); an entry with kf < 0 ends the row.  For seed i: acc = s(i), best = i,
+ *    best_s = s(i); for each entry j in list order that is a survivor of this query (seed or not): acc += s(j), one float add, and if
+ *    s(j) > best_s, strictly, best = j, best_s = s(j).  A listed j that is no survivor contributes nothing (the one deviation:
+ *    upstream's DetectNBestCandidates reads a stale score there).
+ * 5. Candidates.  acc*(b) is the maximum of acc(i) over the seeds with best(i) == b, best_acc the maximum over all seeds; both
+ *    maxima are taken in the IEEE total order (-0.0 below +0.0, a NaN at its fixed place), so they do not depend on a schedule.  The
+ *    order is acc* descending in that order, then row ascending (a tie rule of ours: upstream ties by list position).  Threshold
+ *    form (n_best == 0): every b with acc*(b) > retain_ratio * best_acc, one float multiply and a strict compare.  N-best form
+ *    (n_best > 0): walk the order; the first n_best of the query's own problem are loop candidates (class 0), the first n_best of
+ *    other problems merge candidates (class 1).  scope is applied last: 0 keeps only the query's own problem, 1 all; rows of other
+ *    maps still count towards max_common and the groups.
+ * Outputs per query.  d_cand [n_q][cand_cap] ss_place_cand in the candidate order, entries from n_written on (-1, -1, 0, 0, 0, 0);
+ * d_summary [n_q] ss_place_summary (min_score as used, best_acc 0.0 without a seed, n_candidates the size of the set, n_written =
+ * min(n_candidates, cand_cap), status SS_OK); optionally d_words int32 [n_q][n_db] (words(r), 0 for excluded rows) and d_score
+ * float [n_q][n_db] (s, -1.0f for a row never scored; the connected rows of mode 1 are scored).  Every output byte is written
+ * exactly once per call.  Values are expected finite, as the transform writes them; a NaN is ordered, never read as an index. */
+#define SS_PLACE_MAX_DB 262144         /* n_db: a query's tables are [n_q][n_db]; below SS_COVIS_MAX_MAP_KF, whose numbering the rows share */
+#define SS_PLACE_MAX_QUERIES 256       /* n_q: with SS_PLACE_MAX_DB four 256 MiB tables and one of 64 MiB in the workspace */
+#define SS_PLACE_MAX_CANDIDATES 256    /* cand_cap and n_best: each written candidate is one pass of a workgroup over the survivors */
+#define SS_PLACE_MAX_NEIGHBOURS 1024   /* nb_cap and q_cap: SS_COVIS_MAX_NEIGHBOURS, the rows ss_covis_kf_device can write */
+typedef struct {            /* 32 bytes */
+    int32_t min_score_mode; /* 0: min_score; 1: the lowest score of the connected keyframes.  Default 1 */
+    float min_score;        /* mode 0; finite */
+    int32_t n_best;         /* 0: the threshold form; 1 .. SS_PLACE_MAX_CANDIDATES: the N-best form.  Default 0 */
+    int32_t scope;          /* 0: the query's own problem only; 1: all.  Default 1 */
+    float common_ratio;     /* 0 .. 1; upstream: 0.8f */
+    float retain_ratio;     /* 0 .. 1; upstream: 0.75f */
+    int32_t reserved[2];    /* must be 0 */
+} ss_place_params;
+typedef struct {            /* 24 bytes */
+    int32_t kf;             /* the call row */
+    int32_t problem;
+    int32_t words;
+    int32_t cls;            /* the class: 0 own map, 1 other map */
+    float score, acc;       /* s and acc* */
+} ss_place_cand;
+typedef struct {            /* 48 bytes, one per query */
+    int32_t n_sharing, max_common, min_common, n_survivors, n_seeds;
+    float min_score, best_acc;
+    int32_t n_candidates, n_written, status;
+    int32_t reserved[2];    /* 0 */
+} ss_place_summary;
+/* upstream's loop detection: mode 1, the threshold form, every map, 0.8f and 0.75f */
+int ss_place_params_default(ss_place_params *p);
+/* Builds the inverted file on the device from the caller's device arrays, which are never downloaded: a count of every word with
+ * integer atomics, an exclusive scan, a fill through per-word cursors.  The lists are sized by their upper bound n_db * stride,
+ * which the host knows, so the whole call is asynchronous on the context's stream: nothing waits for the device (only a workspace
+ * that has to grow synchronises, as everywhere).  The context keeps the lists and the caller's pointers until the next call or
+ * ss_destroy, so the arrays must stay allocated; their contents are read again by every query (the skip bytes, the vectors of the
+ * scored rows).  n_db == 0 clears the database.  SS_ERR_INVALID_ARG, with a message: n_db outside 0 .. SS_PLACE_MAX_DB, stride < 1,
+ * n_db * stride not below 2^31, n_words outside 1 .. SS_VOCAB_MAX_NODES, a NULL required buffer, a bad problem table.  A refused call
+ * leaves the database it found. */
+int ss_place_set_database(ss_ctx *ctx, const void *d_db_word, const void *d_db_value, const void *d_db_count, const void *d_db_skip,
+                          int n_db, int stride, int n_words, const ss_gba_problem *problems, int n_problems);
+/* The whole rule for n_q queries, enqueued at once on the context's stream with no host synchronisation inside (q_kf and q_problem
+ * are HOST tables, copied before the call returns).  d_q_nb and d_q_row both NULL: no covisibility rows (q_cap is ignored); d_words /
+ * d_score may be NULL.  n_q == 0: SS_OK, nothing written.  SS_ERR_STATE without a database.  SS_ERR_INVALID_ARG, with a message:
+ * n_q outside 0 .. SS_PLACE_MAX_QUERIES, q_stride < 1, cand_cap outside 1 .. SS_PLACE_MAX_CANDIDATES, nb_cap or q_cap outside 1 ..
+ * SS_PLACE_MAX_NEIGHBOURS, a NULL required buffer, a q_kf outside -1 .. n_db-1 or a q_problem outside the table, a q_problem that
+ * contradicts q_kf, a parameter out of range, a reserved field that is not 0. */
+int ss_place_query_device(ss_ctx *ctx, const void *d_q_word, const void *d_q_value, const void *d_q_count, int q_stride, int n_q,
+                          const int32_t *q_kf, const int32_t *q_problem, const void *d_q_nb, const void *d_q_row, int q_cap,
+                          const void *d_nb, int nb_cap, const ss_place_params *params, int cand_cap, void *d_cand, void *d_summary,
+                          void *d_words, void *d_score);
+/* One database and its queries with host pointers in and out, synchronous: uploads, ss_place_set_database, ss_place_query_device,
+ * downloads.  The context's database is left cleared (its arrays were the call's own copies).  words / score may be NULL. */
+int ss_place(ss_ctx *ctx, const int32_t *db_word, const double *db_value, const int32_t *db_count, const uint8_t *db_skip, int n_db,
+             int stride, int n_words, const ss_gba_problem *problems, int n_problems, const int32_t *q_word, const double *q_value,
+             const int32_t *q_count, int q_stride, int n_q, const int32_t *q_kf, const int32_t *q_problem, const int32_t *q_nb,
+             const ss_covis_row *q_row, int q_cap, const int32_t *nb, int nb_cap, const ss_place_params *params, int cand_cap,
+             ss_place_cand *cand, ss_place_summary *summary, int32_t *words, float *score);
+/* The whole rule on the host from the text the kernels compile (csrc/ss_place_steps.h, csrc/ss_bow_merge.h); needs no device.
+ * Arguments are ss_place's and are checked as the device calls check them: SS_ERR_INVALID_ARG, and the message in err (err_bytes
+ * of it; NULL: none). */
+int ss_place_query_host(const int32_t *db_word, const double *db_value, const int32_t *db_count, const uint8_t *db_skip, int n_db,
+                        int stride, int n_words, const ss_gba_problem *problems, int n_problems, const int32_t *q_word,
+                        const double *q_value, const int32_t *q_count, int q_stride, int n_q, const int32_t *q_kf,
+                        const int32_t *q_problem, const int32_t *q_nb, const ss_covis_row *q_row, int q_cap, const int32_t *nb,
+                        int nb_cap, const ss_place_params *params, int cand_cap, ss_place_cand *cand, ss_place_summary *summary,
+                        int32_t *words, float *score, char *err, int err_bytes);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

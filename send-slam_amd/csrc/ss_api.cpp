@@ -472,6 +472,11 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_covis_io);
     staged_free(c->refresh_tab);
     dev_free(c->d_refresh_io);
+    staged_free(c->place_tab);
+    staged_free(c->place_call_tab);
+    dev_free(c->d_place_lists);
+    dev_free(c->d_place_ws);
+    dev_free(c->d_place_io);
     dev_free(c->d_sim3opt_ws);
     dev_free(c->d_sim3opt_io);
     staged_free(c->sim3opt_tab);

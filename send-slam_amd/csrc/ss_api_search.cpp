@@ -3432,6 +3432,278 @@ int ss_refresh_host(const ss_gba_problem *problems, int n_problems, int n_kf, in
     return SS_OK;
 }
 
+/* ---- place recognition (csrc/ss_place.hip, csrc/ss_place_steps.h) ---- */
+/* the message of the first rule p breaks, or NULL; needs no context */
+static const char *place_params_error(const ss_place_params *p)
+{
+    if (!p) return "place: params is NULL";
+    if (p->min_score_mode != 0 && p->min_score_mode != 1) return "place: min_score_mode must be 0 or 1";
+    if (!std::isfinite(p->min_score)) return "place: min_score must be finite";
+    if (p->n_best < 0 || p->n_best > SS_PLACE_MAX_CANDIDATES) return "place: n_best must be 0 .. SS_PLACE_MAX_CANDIDATES";
+    if (p->scope != 0 && p->scope != 1) return "place: scope must be 0 or 1";
+    if (!(p->common_ratio >= 0.0f && p->common_ratio <= 1.0f)) return "place: common_ratio must be 0 .. 1";
+    if (!(p->retain_ratio >= 0.0f && p->retain_ratio <= 1.0f)) return "place: retain_ratio must be 0 .. 1";
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return "place: the reserved fields must be 0";
+    return nullptr;
+}
+
+int ss_place_params_default(ss_place_params *p)
+{
+    if (!p) return SS_ERR_INVALID_ARG;
+    *p = ss_place_params{1, 0.0f, 0, 1, 0.8f, 0.75f, {0, 0}};
+    return SS_OK;
+}
+
+/* The checks of a database (`what` heads the messages), the rows' problems into row_prob and the problems' (first_kf, n_kf) into
+ * prob.  The message of the first rule that is broken, or empty */
+static std::string place_db_error(const std::string &what, bool arrays, int n_db, int stride, int n_words, const ss_gba_problem *problems, int n_problems,
+                                  std::vector<int32_t> &row_prob, std::vector<int32_t> &prob)
+{
+    if (n_db < 0 || n_db > SS_PLACE_MAX_DB) return what + ": n_db " + std::to_string(n_db) + " outside 0 .. SS_PLACE_MAX_DB (" + std::to_string(SS_PLACE_MAX_DB) + ")";
+    if (stride < 1) return what + ": stride " + std::to_string(stride) + " must be >= 1";
+    if ((int64_t)n_db * stride > INT32_MAX) return what + ": n_db * stride must be below 2^31";
+    if (n_words < 1 || n_words > SS_VOCAB_MAX_NODES) return what + ": n_words " + std::to_string(n_words) + " outside 1 .. SS_VOCAB_MAX_NODES (" + std::to_string(SS_VOCAB_MAX_NODES) + ")";
+    if (n_problems < 0) return what + ": n_problems must be >= 0";
+    if (n_problems > 0 && !problems) return what + ": problems is NULL";
+    if (n_db > 0 && !arrays) return what + ": db_word, db_value or db_count is NULL";
+    row_prob.assign((size_t)n_db, -1), prob.assign((size_t)n_problems * 2 + 2, 0);
+    for (int q = 0; q < n_problems; q++) {
+        const ss_gba_problem &b = problems[q];
+        const std::string head = what + ": problems[" + std::to_string(q) + "]: ";
+        if (b.n_kf < 1 || b.n_kf > SS_GBA_MAX_KF) return head + "n_kf " + std::to_string(b.n_kf) + " outside 1 .. SS_GBA_MAX_KF (" + std::to_string(SS_GBA_MAX_KF) + ")";
+        if (b.first_kf < 0 || b.first_kf > n_db - b.n_kf)
+            return head + "keyframes " + std::to_string(b.first_kf) + " .. + " + std::to_string(b.n_kf) + " lie outside the call's n_db " + std::to_string(n_db);
+        for (int k = b.first_kf; k < b.first_kf + b.n_kf; k++) {
+            if (row_prob[(size_t)k] >= 0) return head + "keyframe " + std::to_string(k) + " belongs to problem " + std::to_string(row_prob[(size_t)k]) + " already";
+            row_prob[(size_t)k] = q;
+        }
+        prob[(size_t)q * 2] = b.first_kf, prob[(size_t)q * 2 + 1] = b.n_kf;
+    }
+    return std::string();
+}
+
+/* the checks of a call's queries against a database of n_db rows whose problems are row_prob, or empty */
+static std::string place_query_error(const std::string &what, int n_db, int n_problems, const int32_t *row_prob, bool vectors, int q_stride, int n_q, const int32_t *q_kf,
+                                     const int32_t *q_problem, bool have_q_nb, bool have_q_row, int q_cap, bool have_nb, int nb_cap, const ss_place_params *p, int cand_cap,
+                                     bool outputs)
+{
+    if (const char *msg = place_params_error(p)) return msg;
+    if (n_q < 0 || n_q > SS_PLACE_MAX_QUERIES) return what + ": n_q " + std::to_string(n_q) + " outside 0 .. SS_PLACE_MAX_QUERIES (" + std::to_string(SS_PLACE_MAX_QUERIES) + ")";
+    if (q_stride < 1) return what + ": q_stride " + std::to_string(q_stride) + " must be >= 1";
+    if (cand_cap < 1 || cand_cap > SS_PLACE_MAX_CANDIDATES)
+        return what + ": cand_cap " + std::to_string(cand_cap) + " outside 1 .. SS_PLACE_MAX_CANDIDATES (" + std::to_string(SS_PLACE_MAX_CANDIDATES) + ")";
+    if (nb_cap < 1 || nb_cap > SS_PLACE_MAX_NEIGHBOURS)
+        return what + ": nb_cap " + std::to_string(nb_cap) + " outside 1 .. SS_PLACE_MAX_NEIGHBOURS (" + std::to_string(SS_PLACE_MAX_NEIGHBOURS) + ")";
+    if (have_q_nb != have_q_row) return what + ": q_nb and q_row must both be given or both be NULL";
+    if (have_q_nb && (q_cap < 1 || q_cap > SS_PLACE_MAX_NEIGHBOURS))
+        return what + ": q_cap " + std::to_string(q_cap) + " outside 1 .. SS_PLACE_MAX_NEIGHBOURS (" + std::to_string(SS_PLACE_MAX_NEIGHBOURS) + ")";
+    if (n_q == 0) return std::string();
+    if (!vectors) return what + ": q_word, q_value or q_count is NULL";
+    if (!q_kf) return what + ": q_kf is NULL";
+    if (!q_problem) return what + ": q_problem is NULL";
+    if (!have_nb) return what + ": nb is NULL";
+    if (!outputs) return what + ": cand or summary is NULL";
+    for (int q = 0; q < n_q; q++) {
+        const std::string head = what + ": query " + std::to_string(q) + ": ";
+        if (q_kf[q] < -1 || q_kf[q] >= n_db) return head + "q_kf " + std::to_string(q_kf[q]) + " outside -1 .. n_db - 1 (" + std::to_string(n_db - 1) + ")";
+        if (q_problem[q] < 0 || q_problem[q] >= n_problems)
+            return head + "q_problem " + std::to_string(q_problem[q]) + " outside the table's " + std::to_string(n_problems) + " problems";
+        if (q_kf[q] >= 0 && row_prob[q_kf[q]] != q_problem[q])
+            return head + "q_problem " + std::to_string(q_problem[q]) + " contradicts q_kf " + std::to_string(q_kf[q]) + ", a row of problem " + std::to_string(row_prob[q_kf[q]]);
+    }
+    return std::string();
+}
+
+static void place_clear(ss_ctx *c)
+{
+    c->place_db = ss_place_db();
+    c->place_row_prob.clear();
+}
+
+static int place_set_database(ss_ctx *c, const void *d_db_word, const void *d_db_value, const void *d_db_count, const void *d_db_skip, int n_db, int stride, int n_words,
+                              const ss_gba_problem *problems, int n_problems)
+{
+    const std::string what = "ss_place_set_database";
+    std::vector<int32_t> row_prob, prob;
+    const std::string msg = place_db_error(what, d_db_word && d_db_value && d_db_count, n_db, stride, n_words, problems, n_problems, row_prob, prob);
+    if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_db == 0) {
+        place_clear(c);
+        return SS_OK;
+    }
+    place_clear(c); /* from here on the buffers of the database it found may move */
+    const size_t o_prob = ((size_t)n_db * 4 + 15) & ~(size_t)15;
+    int rc = staged_upload(c, c->place_tab, o_prob + prob.size() * 4, [&](uint8_t *h) {
+        memcpy(h, row_prob.data(), (size_t)n_db * 4);
+        memcpy(h + o_prob, prob.data(), prob.size() * 4);
+    });
+    if (rc != SS_OK) return rc;
+    ssk_place_lists b;
+    b.word = (const int32_t *)d_db_word, b.count = (const int32_t *)d_db_count, b.n_db = n_db, b.stride = stride, b.n_words = n_words;
+    const size_t entries = (size_t)n_db * stride, W = (size_t)n_words + 1;
+    rc = carve_from(c, c->d_place_lists, [&](carve &w) {
+        b.off = w.take<int32_t>(W * 4), b.cursor = w.take<int32_t>(W * 4), b.list = w.take<int32_t>((entries + 1) * 4);
+        b.sums = w.take<int32_t>(ssk_place_scan_sums(n_words) * 4);
+    });
+    if (rc != SS_OK) return rc;
+    hipError_t e;
+    {
+        /* the stage's bytes: every entry's word twice, its row written once, the counts three times and the cursors twice */
+        stage_timer tm(c, "place_build", (int64_t)entries * 12 + (int64_t)W * 20);
+        e = (hipError_t)ssk_place_build(c->stream, b);
+    }
+    HIP_TRY(c, e);
+    HIP_TRY(c, hipGetLastError());
+    ss_place_db &db = c->place_db;
+    db.word = b.word, db.value = (const double *)d_db_value, db.count = b.count, db.skip = (const uint8_t *)d_db_skip;
+    db.n_db = n_db, db.stride = stride, db.n_words = n_words, db.n_problems = n_problems;
+    db.row_prob = c->place_tab.as<int32_t>(), db.prob = c->place_tab.as<int32_t>(o_prob);
+    db.off = b.off, db.list = b.list;
+    c->place_row_prob.swap(row_prob);
+    return SS_OK;
+}
+
+int ss_place_set_database(ss_ctx *c, const void *d_db_word, const void *d_db_value, const void *d_db_count, const void *d_db_skip, int n_db, int stride, int n_words,
+                          const ss_gba_problem *problems, int n_problems)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    try {
+        return place_set_database(c, d_db_word, d_db_value, d_db_count, d_db_skip, n_db, stride, n_words, problems, n_problems);
+    } catch (const std::bad_alloc &) {
+        return fail(c, SS_ERR_NO_MEMORY, "place: no host memory for the tables of the database");
+    }
+}
+
+int ss_place_query_device(ss_ctx *c, const void *d_q_word, const void *d_q_value, const void *d_q_count, int q_stride, int n_q, const int32_t *q_kf, const int32_t *q_problem,
+                          const void *d_q_nb, const void *d_q_row, int q_cap, const void *d_nb, int nb_cap, const ss_place_params *params, int cand_cap, void *d_cand,
+                          void *d_summary, void *d_words, void *d_score)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const std::string what = "ss_place_query_device";
+    if (const char *msg = place_params_error(params)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    const ss_place_db &db = c->place_db;
+    if (db.n_db == 0) return fail(c, SS_ERR_STATE, what + ": no database (ss_place_set_database)");
+    const std::string msg = place_query_error(what, db.n_db, db.n_problems, c->place_row_prob.data(), d_q_word && d_q_value && d_q_count, q_stride, n_q, q_kf, q_problem,
+                                              d_q_nb != nullptr, d_q_row != nullptr, q_cap, d_nb != nullptr, nb_cap, params, cand_cap, d_cand && d_summary);
+    if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (n_q == 0) return SS_OK;
+    const size_t Q = (size_t)n_q, T = Q * (size_t)db.n_db;
+    int rc = staged_upload(c, c->place_call_tab, Q * 8, [&](uint8_t *h) {
+        memcpy(h, q_kf, Q * 4);
+        memcpy(h + Q * 4, q_problem, Q * 4);
+    });
+    if (rc != SS_OK) return rc;
+    ssk_place_call g;
+    g.db = db;
+    g.q_word = (const int32_t *)d_q_word, g.q_value = (const double *)d_q_value, g.q_count = (const int32_t *)d_q_count;
+    g.q_stride = q_stride, g.n_q = n_q, g.q_cap = d_q_nb ? q_cap : 0, g.nb_cap = nb_cap, g.cand_cap = cand_cap;
+    g.q_kf = c->place_call_tab.as<int32_t>(), g.q_problem = c->place_call_tab.as<int32_t>(Q * 4);
+    g.q_nb = (const int32_t *)d_q_nb, g.q_row = (const ss_covis_row *)d_q_row, g.nb = (const int32_t *)d_nb;
+    g.p = *params, g.cand = (ss_place_cand *)d_cand, g.summary = (ss_place_summary *)d_summary;
+    g.words = (int32_t *)d_words, g.score = (float *)d_score;
+    rc = carve_from(c, c->d_place_ws, [&](carve &w) {
+        g.flags = w.take<uint8_t>(T), g.star = w.take<uint32_t>(T * 4), g.surv = w.take<int32_t>(T * 4), g.state = w.take<int32_t>(Q * 32);
+        if (!d_words) g.words = w.take<int32_t>(T * 4);
+        if (!d_score) g.score = w.take<float>(T * 4);
+    });
+    if (rc != SS_OK) return rc;
+    /* the stages' bytes: the tables each writes or reads whole; the lists and vectors it follows are the data's */
+    static const char *const stage_name[6] = {"place_flags", "place_vote", "place_reduce", "place_score", "place_seeds", "place_final"};
+    const int64_t table_bytes[6] = {13, 5, 9, 4, 8, 8};
+    for (int stage = 0; stage < 6; stage++) {
+        stage_timer tm(c, stage_name[stage], (int64_t)T * table_bytes[stage]);
+        ssk_place_query(c->stream, g, stage);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_place(ss_ctx *c, const int32_t *db_word, const double *db_value, const int32_t *db_count, const uint8_t *db_skip, int n_db, int stride, int n_words,
+             const ss_gba_problem *problems, int n_problems, const int32_t *q_word, const double *q_value, const int32_t *q_count, int q_stride, int n_q,
+             const int32_t *q_kf, const int32_t *q_problem, const int32_t *q_nb, const ss_covis_row *q_row, int q_cap, const int32_t *nb, int nb_cap,
+             const ss_place_params *params, int cand_cap, ss_place_cand *cand, ss_place_summary *summary, int32_t *words, float *score)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const std::string what = "ss_place";
+    try {
+        std::vector<int32_t> row_prob, prob;
+        std::string msg = place_db_error(what, db_word && db_value && db_count, n_db, stride, n_words, problems, n_problems, row_prob, prob);
+        if (msg.empty() && n_db == 0) msg = what + ": n_db must be >= 1";
+        if (msg.empty())
+            msg = place_query_error(what, n_db, n_problems, row_prob.data(), q_word && q_value && q_count, q_stride, n_q, q_kf, q_problem, q_nb != nullptr, q_row != nullptr, q_cap,
+                                    nb != nullptr, nb_cap, params, cand_cap, cand && summary);
+        if (!msg.empty()) return fail(c, SS_ERR_INVALID_ARG, msg);
+        if (n_q == 0) return SS_OK;
+        const size_t D = (size_t)n_db * stride, Q = (size_t)n_q, QV = Q * q_stride, T = Q * n_db, QN = q_nb ? Q * q_cap * 8 : 0;
+        enum { DW, DV, DC, DS, QW, QVAL, QC, QNB, QROW, NB, CAND, SUM, WORDS, SCORE, PIECES };
+        io_piece io[PIECES] = {{db_word, nullptr, D * 4, D * 4},
+                               {db_value, nullptr, D * 8, D * 8},
+                               {db_count, nullptr, (size_t)n_db * 4, (size_t)n_db * 4},
+                               {db_skip, nullptr, db_skip ? (size_t)n_db : 0, db_skip ? (size_t)n_db : 0},
+                               {q_word, nullptr, QV * 4, QV * 4},
+                               {q_value, nullptr, QV * 8, QV * 8},
+                               {q_count, nullptr, Q * 4, Q * 4},
+                               {q_nb, nullptr, QN, QN},
+                               {q_row, nullptr, q_nb ? Q * sizeof(ss_covis_row) : 0, q_nb ? Q * sizeof(ss_covis_row) : 0},
+                               {nb, nullptr, (size_t)n_db * nb_cap * 8, (size_t)n_db * nb_cap * 8},
+                               {nullptr, cand, Q * cand_cap * sizeof(ss_place_cand), Q * cand_cap * sizeof(ss_place_cand)},
+                               {nullptr, summary, Q * sizeof(ss_place_summary), Q * sizeof(ss_place_summary)},
+                               {nullptr, words, words ? T * 4 : 0, words ? T * 4 : 0},
+                               {nullptr, score, score ? T * 4 : 0, score ? T * 4 : 0}};
+        int rc = io_send(c, c->d_place_io, io, PIECES);
+        if (rc == SS_OK) rc = place_set_database(c, io[DW].d, io[DV].d, io[DC].d, db_skip ? io[DS].d : nullptr, n_db, stride, n_words, problems, n_problems);
+        if (rc == SS_OK)
+            rc = ss_place_query_device(c, io[QW].d, io[QVAL].d, io[QC].d, q_stride, n_q, q_kf, q_problem, q_nb ? io[QNB].d : nullptr, q_nb ? io[QROW].d : nullptr, q_cap, io[NB].d,
+                                       nb_cap, params, cand_cap, io[CAND].d, io[SUM].d, words ? io[WORDS].d : nullptr, score ? io[SCORE].d : nullptr);
+        if (rc != SS_OK) {
+            (void)hipStreamSynchronize(c->stream);
+            place_clear(c);
+            return rc;
+        }
+        rc = io_fetch(c, io, PIECES);
+        place_clear(c); /* the database's arrays were this call's copies */
+        return rc;
+    } catch (const std::bad_alloc &) {
+        return fail(c, SS_ERR_NO_MEMORY, "place: no host memory for the tables of the database");
+    }
+}
+
+int ss_place_query_host(const int32_t *db_word, const double *db_value, const int32_t *db_count, const uint8_t *db_skip, int n_db, int stride, int n_words,
+                        const ss_gba_problem *problems, int n_problems, const int32_t *q_word, const double *q_value, const int32_t *q_count, int q_stride, int n_q,
+                        const int32_t *q_kf, const int32_t *q_problem, const int32_t *q_nb, const ss_covis_row *q_row, int q_cap, const int32_t *nb, int nb_cap,
+                        const ss_place_params *params, int cand_cap, ss_place_cand *cand, ss_place_summary *summary, int32_t *words, float *score, char *err, int err_bytes)
+{
+    const std::string what = "ss_place_query_host";
+    try {
+        ss_place_host_db h;
+        std::string msg = place_db_error(what, db_word && db_value && db_count, n_db, stride, n_words, problems, n_problems, h.row_prob, h.prob);
+        if (msg.empty() && n_db == 0) msg = what + ": n_db must be >= 1";
+        if (msg.empty())
+            msg = place_query_error(what, n_db, n_problems, h.row_prob.data(), q_word && q_value && q_count, q_stride, n_q, q_kf, q_problem, q_nb != nullptr, q_row != nullptr,
+                                    q_cap, nb != nullptr, nb_cap, params, cand_cap, cand && summary);
+        if (!msg.empty()) return gba_refuse(err, err_bytes, msg);
+        ss_place_db &db = h.view;
+        db.word = db_word, db.value = db_value, db.count = db_count, db.skip = db_skip;
+        db.n_db = n_db, db.stride = stride, db.n_words = n_words, db.n_problems = n_problems;
+        db.row_prob = h.row_prob.data(), db.prob = h.prob.data();
+        ss_place_build_host(h);
+        std::vector<int32_t> w((size_t)n_db);
+        std::vector<float> s((size_t)n_db);
+        for (int q = 0; q < n_q; q++) {
+            const size_t row0 = (size_t)q * n_db;
+            ss_place_query_one_host(db, q_word + (size_t)q * q_stride, q_value + (size_t)q * q_stride, ss_place_clamp(q_count[q], q_stride), q_kf[q], q_problem[q],
+                                    q_nb ? q_nb + (size_t)q * q_cap * 2 : nullptr, q_nb ? ss_place_clamp(q_row[q].n_written, q_cap) : 0, nb, nb_cap, *params, cand_cap,
+                                    cand + (size_t)q * cand_cap, summary + q, words ? words + row0 : w.data(), score ? score + row0 : s.data());
+        }
+    } catch (const std::bad_alloc &) {
+        return SS_ERR_NO_MEMORY;
+    }
+    return SS_OK;
+}
+
 /* ---- PnP RANSAC (csrc/ss_pnp.hip, csrc/ss_pnp_steps.h) ---- */
 /* the message of the first rule p breaks, or NULL; needs no context */
 static const char *pnp_params_error(const ss_pnp_params *p)

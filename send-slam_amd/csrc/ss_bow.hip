@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ss_bow_merge.h"
 #include "ss_constants.h"
 #include "ss_kernels.h"
 #include "ss_quad.h"
@@ -286,33 +287,8 @@ __global__ __launch_bounds__(256) void k_bow_score(const int32_t *q_word, const 
     const int nq = min(max(q_count[0], 0), q_rows), nd = min(max(db_count[d], 0), stride);
     const int32_t *dw = db_word + (size_t)d * stride;
     const double *dv = db_value + (size_t)d * stride;
-    double s = 0.0;
-    for (int base = 0; base < nd && nq > 0; base += 64) {
-        const int j = base + lane;
-        bool common = false;
-        double term = 0.0;
-        if (j < nd) {
-            const int32_t wd = dw[j];
-            int lo = 0, hi = nq;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (q_word[mid] < wd) lo = mid + 1;
-                else hi = mid;
-            }
-            if (lo < nq && q_word[lo] == wd) {
-                const double x = q_value[lo], y = dv[j];
-                term = fabs(x - y) - fabs(x) - fabs(y);
-                common = true;
-            }
-        }
-        unsigned long long mask = __ballot(common);
-        while (mask) { /* ascending lanes = ascending words */
-            const int l = __ffsll((long long)mask) - 1;
-            s += __shfl(term, l);
-            mask &= mask - 1;
-        }
-    }
-    if (lane == 0) score[d] = (nq == 0 || nd == 0) ? 0.0 : -s / 2.0;
+    const double s = ss_bow_score_wave(q_word, q_value, nq, dw, dv, nd, lane); /* ss_bow_merge.h: the place recognition scores with it too */
+    if (lane == 0) score[d] = s;
 }
 
 } // namespace

@@ -182,6 +182,13 @@ struct ss_ctx {
     staged_table refresh_tab;
     dev_buf<uint8_t> d_refresh_io;
     dev_buf<uint8_t> d_covis_io;
+    /* place recognition: the database ss_place_set_database keeps (place_db points at the caller's arrays, into place_tab, the
+     * rows' problems and the problems' ranges, and into d_place_lists, the inverted file; n_db == 0: none), the tables of a query
+     * (q_kf, then q_problem), the workspace of a query, the host form's device copies */
+    ss_place_db place_db;
+    std::vector<int32_t> place_row_prob; /* the host's copy of the rows' problems: a query's q_kf and q_problem are checked on it */
+    staged_table place_tab, place_call_tab;
+    dev_buf<uint8_t> d_place_lists, d_place_ws, d_place_io;
     /* PnP RANSAC: the workspace of a call (correspondences, models, poses, counts), the host form's device copies, the tables of a
      * call (views, then frame numbers, then block numbers) */
     dev_buf<uint8_t> d_pnp_ws, d_pnp_io;

@@ -7,6 +7,7 @@
 
 #include "../../include/sendslam_orb.h"
 #include "ss_layout.h"
+#include "ss_place_steps.h" /* ss_place_db, a member of ssk_place_call */
 
 /* level 0 read in place from the caller's buffer (ptr != NULL: 1-channel image, 16-byte aligned base, row and frame
  * strides; no k_ingest pass), or from the pyramid block (ptr == NULL) */
@@ -744,6 +745,40 @@ struct ssk_refresh_call {
     ss_refresh_summary *summary = nullptr; /* device [n_blocks] */
 };
 int ssk_refresh(hipStream_t s, const ssk_refresh_call &g); /* a hipError_t: the LDS attribute may be refused */
+/* ss_place.hip: place recognition (DESIGN.md "Place recognition").  The inverted file of a database: count, scan, fill (one memset
+ * and five launches); the queries of a call in six stages, so that the caller can time each (stage 0 .. 5: flags, votes, survivors,
+ * scores and the minimum score, groups, candidates; ten launches in all) */
+struct ssk_place_lists {
+    const int32_t *word = nullptr, *count = nullptr; /* device [n_db][stride], [n_db] */
+    int n_db = 0, stride = 0, n_words = 0;
+    int32_t *off = nullptr;    /* device [n_words + 1]: the counts, then the lists' starts */
+    int32_t *cursor = nullptr; /* device [n_words + 1] */
+    int32_t *list = nullptr;   /* device [n_db * stride] */
+    int32_t *sums = nullptr;   /* device [ssk_place_scan_sums(n_words)] */
+};
+size_t ssk_place_scan_sums(int n_words);
+int ssk_place_build(hipStream_t s, const ssk_place_lists &b); /* a hipError_t */
+struct ssk_place_call {
+    ss_place_db db; /* device pointers */
+    const int32_t *q_word = nullptr, *q_count = nullptr;
+    const double *q_value = nullptr;
+    int q_stride = 0, n_q = 0, q_cap = 0, nb_cap = 0, cand_cap = 0;
+    const int32_t *q_kf = nullptr, *q_problem = nullptr; /* device [n_q] */
+    const int32_t *q_nb = nullptr;                       /* device [n_q][q_cap][2] or NULL */
+    const ss_covis_row *q_row = nullptr;
+    const int32_t *nb = nullptr; /* device [n_db][nb_cap][2] */
+    ss_place_params p = {};
+    ss_place_cand *cand = nullptr;
+    ss_place_summary *summary = nullptr;
+    /* [n_q][n_db] each: the caller's d_words / d_score or the workspace's */
+    int32_t *words = nullptr;
+    float *score = nullptr;
+    uint8_t *flags = nullptr;
+    uint32_t *star = nullptr; /* acc* as keys of the total order; 0: none */
+    int32_t *surv = nullptr;  /* the survivors, ascending */
+    int32_t *state = nullptr; /* [n_q][8] */
+};
+void ssk_place_query(hipStream_t s, const ssk_place_call &c, int stage);
 /* The bookkeeping of SearchBySim3 (the rule: include/sendslam_orb.h).  One workgroup per pair: a base pass over the rows, a barrier,
  * a scatter pass in which every store to one address writes the same value.  marks writes skip1 and skip2; mutual marks the train
  * rows that carry a prior match in taken (workspace, [n_frames][rows]) and writes idx_out and the summary */

@@ -58,7 +58,8 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_two_view_check_host", "ss_two_view_accept_host", "ss_two_view_beats_host", "ss_two_view_point_tests_host", "ss_two_view_pairs_device", "ss_two_view_batch_device", "ss_two_view",
            "ss_covis_params_default", "ss_covis_set_map", "ss_covis_kf_device", "ss_covis_frames_device", "ss_covis", "ss_covis_kf_host",
            "ss_covis_frames_host", "ss_covis_edges_host", "ss_covis_set_map_rows", "ss_global_ba_rows_from_idx_host", "ss_refresh_params_default",
-           "ss_refresh_device", "ss_refresh", "ss_refresh_host"]
+           "ss_refresh_device", "ss_refresh", "ss_refresh_host", "ss_place_params_default", "ss_place_set_database", "ss_place_query_device",
+           "ss_place", "ss_place_query_host"]
 
 
 class OrbParams(C.Structure):
@@ -1054,6 +1055,90 @@ def global_ba_obs_from_idx(kp: np.ndarray, idx: np.ndarray, n_kp=None, right=Non
     return out
 
 
+# ---- place recognition (the rule: include/sendslam_orb.h) ----
+SS_PLACE_MAX_DB, SS_PLACE_MAX_QUERIES, SS_PLACE_MAX_CANDIDATES, SS_PLACE_MAX_NEIGHBOURS = 262144, 256, 256, 1024
+
+
+class PlaceParams(C.Structure):
+    _fields_ = [("min_score_mode", C.c_int32), ("min_score", C.c_float), ("n_best", C.c_int32), ("scope", C.c_int32),
+                ("common_ratio", C.c_float), ("retain_ratio", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+# ss_place_cand: one per candidate slot; ss_place_summary: one per query
+PLACE_CAND_DTYPE = np.dtype([("kf", "<i4"), ("problem", "<i4"), ("words", "<i4"), ("class", "<i4"), ("score", "<f4"), ("acc", "<f4")])
+PLACE_SUMMARY_DTYPE = np.dtype([("n_sharing", "<i4"), ("max_common", "<i4"), ("min_common", "<i4"), ("n_survivors", "<i4"), ("n_seeds", "<i4"),
+                                ("min_score", "<f4"), ("best_acc", "<f4"), ("n_candidates", "<i4"), ("n_written", "<i4"), ("status", "<i4"),
+                                ("reserved", "<i4", (2,))])
+
+
+def place_params(min_score_mode: int = 1, min_score: float = 0.0, n_best: int = 0, scope: int = 1, common_ratio: float = 0.8,
+                 retain_ratio: float = 0.75, reserved=(0, 0)) -> PlaceParams:
+    """upstream's loop detection: the minimum score from the connected keyframes, the 0.75 cut, every map"""
+    return PlaceParams(min_score_mode=min_score_mode, min_score=min_score, n_best=n_best, scope=scope, common_ratio=common_ratio,
+                       retain_ratio=retain_ratio, reserved=(C.c_int32 * 2)(*reserved))
+
+
+def _place_arrays(db_word, db_value, db_count, db_skip, problems, q_word, q_value, q_count, q_kf, q_problem, q_nb, q_row, nb):
+    """the host arrays of a place call in their C types and the counts they imply"""
+    dw = np.ascontiguousarray(db_word, np.int32)
+    dv = np.ascontiguousarray(db_value, np.float64)
+    dc = np.ascontiguousarray(db_count, np.int32).reshape(-1)
+    if dw.ndim != 2 or dv.shape != dw.shape or len(dc) != dw.shape[0]:
+        raise ValueError("db_word and db_value are [n_db][stride], db_count [n_db]")
+    sk = None if db_skip is None else np.ascontiguousarray(db_skip, np.uint8).reshape(-1)
+    if sk is not None and len(sk) != len(dc):
+        raise ValueError("one skip byte per database row")
+    pr = np.ascontiguousarray(problems, GBA_PROBLEM_DTYPE).reshape(-1)
+    qw = np.ascontiguousarray(q_word, np.int32)
+    qv = np.ascontiguousarray(q_value, np.float64)
+    qc = np.ascontiguousarray(q_count, np.int32).reshape(-1)
+    if qw.ndim != 2 or qv.shape != qw.shape or len(qc) != qw.shape[0]:
+        raise ValueError("q_word and q_value are [n_q][q_stride], q_count [n_q]")
+    n_q = len(qc)
+    qk = np.ascontiguousarray(q_kf, np.int32).reshape(-1)
+    qp = np.ascontiguousarray(q_problem, np.int32).reshape(-1)
+    if len(qk) != n_q or len(qp) != n_q:
+        raise ValueError("one q_kf and q_problem per query")
+    qn = qr = None
+    q_cap = 0
+    if q_nb is not None:
+        qn = np.ascontiguousarray(q_nb, np.int32)
+        qr = np.ascontiguousarray(q_row, COVIS_ROW_DTYPE).reshape(-1)
+        if qn.ndim != 3 or qn.shape[0] != n_q or qn.shape[2] != 2 or len(qr) != n_q:
+            raise ValueError("q_nb is [n_q][q_cap][2], q_row [n_q]")
+        q_cap = qn.shape[1]
+    nbr = np.ascontiguousarray(nb, np.int32)
+    if nbr.ndim != 3 or nbr.shape[0] != len(dc) or nbr.shape[2] != 2:
+        raise ValueError("nb is [n_db][nb_cap][2]")
+    return dw, dv, dc, sk, pr, qw, qv, qc, qk, qp, qn, qr, q_cap, nbr
+
+
+def _place_outputs(n_q, n_db, cand_cap):
+    cand = np.zeros((n_q, max(cand_cap, 1)), PLACE_CAND_DTYPE)
+    cand.view(np.uint8)[...] = 0x5A
+    summary = np.zeros(n_q, PLACE_SUMMARY_DTYPE)
+    summary.view(np.uint8)[...] = 0x5A
+    return cand, summary, np.full((n_q, n_db), 0x5A5A5A5A, np.int32), np.full((n_q, n_db), np.nan, np.float32)
+
+
+def place_query_host(db_word, db_value, db_count, n_words: int, problems, q_word, q_value, q_count, q_kf, q_problem, nb, params: PlaceParams,
+                     cand_cap: int, db_skip=None, q_nb=None, q_row=None):
+    """ss_place_query_host: the whole rule on the host -> (cand PLACE_CAND_DTYPE [n_q][cand_cap], summary PLACE_SUMMARY_DTYPE [n_q], words
+    int32 [n_q][n_db], score float32 [n_q][n_db])"""
+    dw, dv, dc, sk, pr, qw, qv, qc, qk, qp, qn, qr, q_cap, nbr = _place_arrays(db_word, db_value, db_count, db_skip, problems, q_word, q_value, q_count,
+                                                                               q_kf, q_problem, q_nb, q_row, nb)
+    n_db, n_q = len(dc), len(qc)
+    cand, summary, words, score = _place_outputs(n_q, n_db, cand_cap)
+    err = C.create_string_buffer(512)
+    ptr = lambda a: None if a is None or not a.size else a.ctypes.data  # noqa: E731
+    rc = load().ss_place_query_host(ptr(dw), ptr(dv), ptr(dc), ptr(sk), n_db, dw.shape[1], n_words, ptr(pr), len(pr), ptr(qw), ptr(qv), ptr(qc), qw.shape[1], n_q,
+                                    ptr(qk), ptr(qp), ptr(qn), ptr(qr), q_cap, ptr(nbr), nbr.shape[1], C.byref(params), cand_cap, ptr(cand), ptr(summary),
+                                    ptr(words), ptr(score), err, len(err))
+    if rc != SS_OK:
+        raise OrbError(rc, err.value.decode() or "the place recognition host twin refused its arguments")
+    return cand, summary, words, score
+
+
 # ---- covisibility (the rule: include/sendslam_orb.h) ----
 SS_COVIS_MAX_ROW_ITEMS, SS_COVIS_MAX_NEIGHBOURS, SS_COVIS_MAX_MAP_KF = 262143, 1024, 1048576
 
@@ -1397,6 +1482,13 @@ def load():
                                C.c_void_p, C.c_int, C.POINTER(RefreshParams), C.c_void_p, C.c_void_p]
     lib.ss_refresh_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + \
                                    [C.c_int, C.c_void_p, C.POINTER(RefreshParams), C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
+    lib.ss_place_params_default.argtypes = [C.POINTER(PlaceParams)]
+    lib.ss_place_set_database.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    place_query = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.POINTER(PlaceParams), C.c_int] + [C.c_void_p] * 4
+    place_db = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.ss_place_query_device.argtypes = [C.c_void_p] + place_query
+    lib.ss_place.argtypes = [C.c_void_p] + place_db + place_query
+    lib.ss_place_query_host.argtypes = place_db + place_query + [C.c_char_p, C.c_int]
     lib.ss_pnp_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                 C.POINTER(PnpParams), C.c_int, C.c_void_p, C.c_void_p]
     lib.ss_pnp_model_host.argtypes = [C.POINTER(PnpParams)] + [C.c_void_p] * 6
@@ -2333,6 +2425,42 @@ class OrbContext:
                                        None if sk is None or not len(sk) else sk.ctypes.data, int(check_right), C.byref(params), cap,
                                        nb.ctypes.data if nb.size else None, row.ctypes.data if len(row) else None))
         return nb, row
+
+    # ---- place recognition: loop and relocalisation candidates from an inverted file (the rule: include/sendslam_orb.h) ----
+    def place_set_database(self, d_db_word: int, d_db_value: int, d_db_count: int, n_db: int, stride: int, n_words: int, problems, d_db_skip: int = 0):
+        """d_db_word int32 / d_db_value float64 [n_db][stride], d_db_count int32 [n_db], d_db_skip uint8 [n_db] or 0: the caller's device
+        arrays, which the context reads again at every query; problems GBA_PROBLEM_DTYPE (only first_kf and n_kf are read).  Builds the
+        inverted file on the device; asynchronous.  n_db 0 clears the database."""
+        pr = np.ascontiguousarray(problems, GBA_PROBLEM_DTYPE).reshape(-1)
+        self._check(self._lib.ss_place_set_database(self._h, C.c_void_p(d_db_word), C.c_void_p(d_db_value), C.c_void_p(d_db_count), C.c_void_p(d_db_skip), n_db,
+                                                    stride, n_words, pr.ctypes.data if len(pr) else None, len(pr)))
+
+    def place_query_device(self, d_q_word: int, d_q_value: int, d_q_count: int, q_stride: int, q_kf, q_problem, d_nb: int, nb_cap: int, params: PlaceParams,
+                           cand_cap: int, d_cand: int, d_summary: int, d_words: int = 0, d_score: int = 0, d_q_nb: int = 0, d_q_row: int = 0, q_cap: int = 0):
+        """len(q_kf) queries: d_q_word / d_q_value [n_q][q_stride], d_q_count [n_q]; q_kf, q_problem host tables; d_q_nb int32 [n_q][q_cap][2]
+        and d_q_row COVIS_ROW_DTYPE [n_q] as covis_kf_device wrote them, or 0; d_nb int32 [n_db][nb_cap][2]; d_cand PLACE_CAND_DTYPE
+        [n_q][cand_cap], d_summary PLACE_SUMMARY_DTYPE [n_q], d_words int32 / d_score float32 [n_q][n_db] or 0; asynchronous."""
+        qk = np.ascontiguousarray(q_kf, np.int32).reshape(-1)
+        qp = np.ascontiguousarray(q_problem, np.int32).reshape(-1)
+        if len(qk) != len(qp):
+            raise ValueError("one q_kf and q_problem per query")
+        self._check(self._lib.ss_place_query_device(self._h, C.c_void_p(d_q_word), C.c_void_p(d_q_value), C.c_void_p(d_q_count), q_stride, len(qk),
+                                                    qk.ctypes.data if len(qk) else None, qp.ctypes.data if len(qp) else None, C.c_void_p(d_q_nb),
+                                                    C.c_void_p(d_q_row), q_cap, C.c_void_p(d_nb), nb_cap, C.byref(params), cand_cap, C.c_void_p(d_cand),
+                                                    C.c_void_p(d_summary), C.c_void_p(d_words), C.c_void_p(d_score)))
+
+    def place(self, db_word, db_value, db_count, n_words: int, problems, q_word, q_value, q_count, q_kf, q_problem, nb, params: PlaceParams, cand_cap: int,
+              db_skip=None, q_nb=None, q_row=None):
+        """One database and its queries, host arrays in and out -> what place_query_host returns; the context's database is left cleared."""
+        dw, dv, dc, sk, pr, qw, qv, qc, qk, qp, qn, qr, q_cap, nbr = _place_arrays(db_word, db_value, db_count, db_skip, problems, q_word, q_value, q_count,
+                                                                                   q_kf, q_problem, q_nb, q_row, nb)
+        n_db, n_q = len(dc), len(qc)
+        cand, summary, words, score = _place_outputs(n_q, n_db, cand_cap)
+        ptr = lambda a: None if a is None or not a.size else a.ctypes.data  # noqa: E731
+        self._check(self._lib.ss_place(self._h, ptr(dw), ptr(dv), ptr(dc), ptr(sk), n_db, dw.shape[1], n_words, ptr(pr), len(pr), ptr(qw), ptr(qv), ptr(qc),
+                                       qw.shape[1], n_q, ptr(qk), ptr(qp), ptr(qn), ptr(qr), q_cap, ptr(nbr), nbr.shape[1], C.byref(params), cand_cap, ptr(cand),
+                                       ptr(summary), ptr(words), ptr(score)))
+        return cand, summary, words, score
 
     # ---- PnP RANSAC: a pose for every relocalisation candidate (the rule: include/sendslam_orb.h) ----
     @staticmethod

@@ -53,6 +53,9 @@
  *                              over the map ss_covis_set_map_rows keeps: after a fusion, a bundle adjustment or a loop correction
  *   ss_place_*                 KeyFrameDatabase: add / erase, DetectLoopCandidates, DetectNBestCandidates and
  *                              DetectRelocalizationCandidates over an inverted file kept on the device
+ *   ss_undistort_* /           the keypoint post-processing of Frame's constructor: UndistortKeyPoints (mvKeysUn; k1 k2 p1 p2 of the
+ *   ss_proj_view_set_bounds /  calibration message :125-128), ComputeImageBounds and ComputeStereoFromRGBD (the first reader of
+ *   ss_depth_*                 depth_map_factor), so that every family above that takes undistorted keypoints gets them on the device
  *   ss_stats                   vTimesTrack median/mean summary :615-616, :656-664
  *   ss_last_error              the cerr diagnostics of the shim (:457-469, :523-551)
  *
@@ -2358,6 +2361,102 @@ int ss_place_query_host(const int32_t *db_word, const double *db_value, const in
                         const int32_t *q_problem, const int32_t *q_nb, const ss_covis_row *q_row, int q_cap, const int32_t *nb,
                         int nb_cap, const ss_place_params *params, int cand_cap, ss_place_cand *cand, ss_place_summary *summary,
                         int32_t *words, float *score, char *err, int err_bytes);
+
+/* ---- undistorted keypoints, image bounds, RGB-D depth: what Frame's constructor does to the extractor's keypoints --
+ * Frame::UndistortKeyPoints (mvKeysUn), Frame::ComputeImageBounds (mnMinX .. mnMaxY) and Frame::ComputeStereoFromRGBD (mvuRight,
+ * mvDepth).  Every search and optimiser above takes its keypoints as undistorted; this family makes them so on the device, so that
+ * the batch of a distorted camera stays in HBM from pixels to poses.  No ORB-SLAM3 source is in the reference tree: this is the
+ * library's own restatement, oracle/vo_oracle.py::undistort and tests/undistort_ref.py are its normative statement, and parity with
+ * the real binary stays unpinned.  DESIGN.md section 34.  An addition to ABI 5: nothing existing changes; ss_track keeps its own
+ * host routine, which states the same rule.
+ * 1. Undistortion.  Of a camera only fx fy cx cy k1 k2 p1 p2 are read.  If k1 == 0 && k2 == 0 && p1 == 0 && p2 == 0, x and y are
+ *    copied bit for bit.  Otherwise, in double, one IEEE operation per step, left to right, no contraction:
+ *      x0 = ((double)x - cx) / fx;  y0 = ((double)y - cy) / fy;  x = x0;  y = y0;
+ *      five times:  r2 = x*x + y*y;  icdist = 1.0 / (1.0 + (k2*r2 + k1)*r2);
+ *                   dx = 2*p1*x*y + p2*(r2 + 2*x*x);  dy = p1*(r2 + 2*y*y) + 2*p2*x*y;
+ *                   x = (x0 - dx)*icdist;  y = (y0 - dy)*icdist;
+ *      out.x = (float)(x*fx + cx);  out.y = (float)(y*fy + cy);      one rounding each: mvKeysUn is float32
+ *    Host and device agree bit for bit on finite input; a non-finite coordinate goes through the same operations.  size, angle,
+ *    response and octave are never touched.  Known differences from cv::undistortPoints as published: the rule divides by fx where
+ *    OpenCV multiplies by 1/fx; OpenCV's bail-out for icdist < 0 is absent (tests/test_undistort_ref.py shows the denominator
+ *    positive over the whole image for its cameras); K is taken in double where upstream holds it in float.
+ * 2. Bounds.  All four coefficients zero: 0, width, 0, height.  Otherwise the corners c0 = (0,0), c1 = (w,0), c2 = (0,h),
+ *    c3 = (w,h), as floats, go through rule 1, and min_x = min(c0.x, c2.x), max_x = max(c1.x, c3.x), min_y = min(c0.y, c1.y),
+ *    max_y = max(c2.y, c3.y).
+ * 3. RGB-D depth (Tracking::GrabImageRGBD, then ComputeStereoFromRGBD), all float32, one operation per step:
+ *    1. inv = fabsf(depth_map_factor) < 1e-5f ? 1.0f : 1.0f / depth_map_factor.
+ *    2. A uint16 sample becomes (float)raw * inv.  A float32 sample is multiplied by inv only when fabsf(inv - 1.0f) > 1e-5f.
+ *    3. The sample is taken at column (int)x_raw, row (int)y_raw: truncation of the RAW position, as at<float>(v, u) does.  A
+ *       position whose pixel lies outside the frame, or a NaN, has no sample.
+ *    4. If d > 0 (a NaN fails): depth = d and right = x_undistorted - bf / d, one division and one subtraction.  Otherwise both
+ *       are -1.0f.  Rows at or past a frame's count get -1.0f in both planes.
+ *    right is the plane ss_pose_opt_*, ss_local_ba_* and ss_match_proj_* take as d_right / d_train_right. */
+typedef struct {            /* 16 bytes */
+    float bf;               /* baseline times fx (upstream's mbf); finite */
+    float depth_map_factor; /* the calibration's; finite */
+    float close_limit;      /* upstream's mThDepth: a depth in (0, close_limit) counts as close; summary only */
+    int32_t depth_type;     /* 0: float32 samples, 1: uint16 samples */
+} ss_depth_params;
+typedef struct {            /* 16 bytes, one per frame */
+    int32_t status;         /* SS_OK, or the frame_error that voided the frame (batch form: n_kp 0, every row -1.0f) */
+    int32_t n_kp;           /* the count as used, clamped to 0 .. rows_per_frame */
+    int32_t n_depth;        /* rows with depth > 0 */
+    int32_t n_close;        /* rows with 0 < depth < close_limit */
+} ss_depth_summary;
+/* Rule 2; needs no device.  SS_ERR_INVALID_ARG: a NULL pointer, width <= 0, height <= 0, a non-finite one of the eight numbers
+ * rule 1 reads, fx or fy equal to 0. */
+int ss_undistort_bounds_host(const ss_camera *cam, float out[4] /* min_x, max_x, min_y, max_y */);
+/* Overwrites the four bound fields of a view, and nothing else of it, with rule 2 of cam: for a view from ss_proj_view_init,
+ * ss_fuse_view_sim3, ss_sim3_to_view or ss_sim3_to_view21, all of which set 0 .. width, 0 .. height.  Refusals as above. */
+int ss_proj_view_set_bounds(ss_proj_view *view, const ss_camera *cam);
+/* Rule 1 for n keypoints on the host from the text the kernel compiles; out may alias kp; other fields are copied.  Needs no
+ * device.  SS_ERR_INVALID_ARG: a NULL pointer (n == 0 needs no arrays), n < 0, fx or fy not finite or equal to 0. */
+int ss_undistort_host(const ss_camera *cam, const ss_keypoint *kp, int n, ss_keypoint *out);
+/* Rule 1 on caller arrays: d_kp [n_frames][rows_per_frame] ss_keypoint, counts d_n_kp (device int32 [n_frames], clamped to 0 ..
+ * rows_per_frame).  cams: a HOST table of n_cams cameras, n_cams == 1 (all frames) or n_cams == n_frames, copied before the call
+ * returns.  d_kp_out [n_frames][rows_per_frame] may equal d_kp; otherwise whole records are written, every other field copied.
+ * Rows at or past a frame's count are not written.  One launch, asynchronous on the context's stream.  SS_ERR_INVALID_ARG: a bad
+ * frame or row count, n_cams neither 1 nor n_frames, a NULL buffer or table, fx or fy of a camera not finite or equal to 0. */
+int ss_undistort_pairs_device(ss_ctx *ctx, const void *d_kp, const void *d_n_kp, int n_frames, int rows_per_frame,
+                              const ss_camera *cams, int n_cams, void *d_kp_out);
+/* The same on the frames of the last ss_extract_batch_device batch (SS_ERR_STATE without one; n_frames and kp_capacity are the
+ * batch's); a frame whose frame_error is set counts as 0 rows.  cams == NULL: the calibration set last (n_cams is ignored;
+ * SS_ERR_NOT_CALIBRATED without one).
+ * d_kp_out != NULL: out of place, the batch is left as it is.
+ * d_kp_out == NULL: IN PLACE.  The raw (x, y) pairs are first saved into an array of the context ([n_frames][kp_capacity][2]
+ * float, allocated on first use, handed out by ss_get_batch_raw_xy), then x and y of the batch's own keypoints are overwritten.
+ * From then on every *_batch_device call on that batch, ss_get_batch_view and ss_fetch_frame read mvKeysUn.  A second in-place call
+ * on the same batch is SS_ERR_STATE and writes nothing; every new extraction clears the state.
+ * ss_stereo_batch_device reads the positions as they are: its row bands and its disparity are those of rectified pairs, whose
+ * coefficients are zero, and for zero coefficients the in-place form is a bit copy. */
+int ss_undistort_batch_device(ss_ctx *ctx, const ss_camera *cams, int n_cams, void *d_kp_out /* NULL = in place */);
+/* The raw pairs the in-place form saved, device [n_frames][kp_capacity][2] float (rows past a frame's count are unspecified);
+ * valid until the next extraction.  SS_ERR_STATE while the current batch has not been undistorted in place. */
+int ss_get_batch_raw_xy(ss_ctx *ctx, const float **d_xy);
+/* bf = (float)(baseline * fx), depth_map_factor = (float) of the calibration's, close_limit = (float)(baseline * fx * th_depth / fx)
+ * (upstream's mThDepth = mbf * ThDepth / fx, in double, left to right).  Needs no device.  SS_ERR_INVALID_ARG: a NULL pointer,
+ * depth_type not 0 or 1. */
+int ss_depth_params_from_camera(const ss_camera *cam, int depth_type, ss_depth_params *out);
+/* Rule 3 for the n keypoints of one frame on the host from the text the kernel compiles.  depth: height rows of row_stride bytes,
+ * width samples each.  kp_un == NULL: kp_raw serves as both.  right and depth_out are float [n]; summary may be NULL.  Needs no
+ * device.  Refusals as for the device forms. */
+int ss_depth_host(const ss_depth_params *p, const void *depth, int width, int height, int64_t row_stride, const ss_keypoint *kp_raw,
+                  const ss_keypoint *kp_un, int n, float *right, float *depth_out, ss_depth_summary *summary);
+/* Rule 3 on caller arrays.  d_depth: n_frames depth frames in device memory, frame b at d_depth + b * frame_stride, its rows
+ * row_stride bytes apart (both in bytes, multiples of the sample size, as the base is).  d_kp_raw / d_kp_un
+ * [n_frames][rows_per_frame] ss_keypoint, the raw and the undistorted keypoints (d_kp_un == NULL: d_kp_raw serves as both), counts
+ * d_n_kp.  Outputs d_right / d_depth_out float [n_frames][rows_per_frame], every row written; d_summary [n_frames]
+ * ss_depth_summary, its two counters by integer atomics (exact and order-free).  Two launches, asynchronous on the context's
+ * stream.  SS_ERR_INVALID_ARG: a bad frame or row count, width or height outside 1 .. 16777216, strides smaller than the frame or
+ * misaligned, depth_type not 0 or 1, bf, depth_map_factor or close_limit not finite, a NULL buffer. */
+int ss_depth_pairs_device(ss_ctx *ctx, const ss_depth_params *p, const void *d_depth, int width, int height, int64_t row_stride,
+                          int64_t frame_stride, const void *d_kp_raw, const void *d_kp_un, const void *d_n_kp, int n_frames,
+                          int rows_per_frame, void *d_right, void *d_depth_out, void *d_summary);
+/* The same on the frames of the last ss_extract_batch_device batch (SS_ERR_STATE without one; planes [n_frames][kp_capacity]).  A
+ * batch that was undistorted in place: the saved raw pairs give the pixel, the batch's keypoints x_undistorted.  Otherwise the
+ * batch's keypoints serve as both.  A frame whose frame_error is set gets that status and no depth. */
+int ss_depth_batch_device(ss_ctx *ctx, const ss_depth_params *p, const void *d_depth, int width, int height, int64_t row_stride,
+                          int64_t frame_stride, void *d_right, void *d_depth_out, void *d_summary);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

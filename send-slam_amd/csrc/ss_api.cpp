@@ -81,8 +81,8 @@ void collect_events(ss_ctx *c)
 /* The buffers of c->ws in allocation order: the one place where their sizes live.  ensure_geometry, free_geometry_buffers and
  * the first ss_debug_fetch(2) walk it (ws_alloc: one hipMalloc per buffer). */
 /* a group is allocated and uploaded in table order, then cleared: with the geometry; desc_x, after that group's clears; score, when
- * ss_debug_fetch(2) first asks for it */
-enum ws_when { WS_GEOMETRY, WS_OPERANDS, WS_FIRST_USE };
+ * ss_debug_fetch(2) first asks for it; raw_xy, when the first in-place undistortion asks for it */
+enum ws_when { WS_GEOMETRY, WS_OPERANDS, WS_FIRST_USE, WS_RAW_XY };
 struct ws_buf {
     void **p;
     size_t bytes;      /* from the geometry and max_batch; 0: not allocated */
@@ -91,7 +91,7 @@ struct ws_buf {
     bool zero;         /* cleared once */
     ws_when when;
 };
-std::array<ws_buf, 28> ws_table(ss_ctx *c)
+std::array<ws_buf, 29> ws_table(ss_ctx *c)
 {
     ssk_extract_ws &w = c->ws;
     const ss_geom &g = c->hg;
@@ -131,6 +131,7 @@ std::array<ws_buf, 28> ws_table(ss_ctx *c)
         {WS(kps), K * sizeof(ss_keypoint), nullptr, 0, true},
         {WS(desc), K * SS_DESC_BYTES, nullptr, 0, true},
         {WS(desc_x), operands ? K * SSK_X_ROW : 0, nullptr, 0, true, WS_OPERANDS},
+        {(void **)&c->d_raw_xy, K * sizeof(float2), nullptr, 0, false, WS_RAW_XY},
     }};
 #undef WS
 }
@@ -153,6 +154,20 @@ void free_geometry_buffers(ss_ctx *c)
     for (const ws_buf &b : ws_table(c)) dev_free(*b.p);
     c->have_geom = false;
 }
+
+} // namespace
+
+namespace ss_detail {
+
+int raw_xy_buffer(ss_ctx *c)
+{
+    if (c->d_raw_xy) return SS_OK;
+    return ws_alloc(c, WS_RAW_XY);
+}
+
+} // namespace ss_detail
+
+namespace {
 
 int ensure_geometry(ss_ctx *c, int w, int h)
 {
@@ -182,6 +197,7 @@ int ensure_geometry(ss_ctx *c, int w, int h)
     c->have_geom = true;
     c->last_n_frames = 0;
     c->bow_frames = 0;
+    c->batch_undistorted = false;
     return SS_OK;
 }
 
@@ -252,6 +268,7 @@ int run_extract(ss_ctx *c, const void *d_pix, int n, int channels, int64_t row_s
     HIP_TRY(c, hipGetLastError());
     c->last_n_frames = n;
     c->bow_frames = 0; /* the nodes a BoW transform kept belong to the batch before */
+    c->batch_undistorted = false; /* ... and so do the raw pairs an in-place undistortion saved */
     return SS_OK;
 }
 
@@ -472,6 +489,7 @@ int ss_destroy(ss_ctx *c)
     dev_free(c->d_covis_io);
     staged_free(c->refresh_tab);
     dev_free(c->d_refresh_io);
+    staged_free(c->undist_tab);
     staged_free(c->place_tab);
     staged_free(c->place_call_tab);
     dev_free(c->d_place_lists);

@@ -1,7 +1,7 @@
 /*
  * ss_api_search.cpp -- the search family of the C ABI (include/sendslam_orb.h): guided matching, map-point projection search,
  * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation, the Sim3 RANSAC, the pose-only optimisation, the Sim3 refinement,
- * the local bundle adjustment, the PnP RANSAC.  Each has a pairs form on caller arrays, a batch form on the
+ * the local bundle adjustment, the PnP RANSAC, the undistortion of keypoints with the image bounds and the RGB-D depth.  Each has a pairs form on caller arrays, a batch form on the
  * frames of the last extraction and, for some, a host form.  The context and the helpers they share: ss_ctx.h.
  */
 #include <algorithm>
@@ -29,6 +29,7 @@
 #include "ss_sim3_steps.h"
 #include "ss_sim3opt_steps.h"
 #include "ss_two_view_steps.h"
+#include "ss_undistort_steps.h"
 
 extern "C" {
 
@@ -3702,6 +3703,219 @@ int ss_place_query_host(const int32_t *db_word, const double *db_value, const in
         return SS_ERR_NO_MEMORY;
     }
     return SS_OK;
+}
+
+/* ---- undistorted keypoints, image bounds, RGB-D depth (csrc/ss_undistort.hip, csrc/ss_undistort_steps.h) ---- */
+int ss_undistort_bounds_host(const ss_camera *cam, float out[4])
+{
+    if (!cam || !out || cam->width <= 0 || cam->height <= 0) return SS_ERR_INVALID_ARG;
+    const ss_undist_cam u = ss_undist_cam_of(*cam);
+    if (!ss_undist_cam_finite(u)) return SS_ERR_INVALID_ARG;
+    ss_undist_bounds(u, cam->width, cam->height, out);
+    return SS_OK;
+}
+
+int ss_proj_view_set_bounds(ss_proj_view *view, const ss_camera *cam)
+{
+    if (!view) return SS_ERR_INVALID_ARG;
+    float b[4];
+    const int rc = ss_undistort_bounds_host(cam, b);
+    if (rc != SS_OK) return rc;
+    view->min_x = b[0], view->max_x = b[1], view->min_y = b[2], view->max_y = b[3];
+    return SS_OK;
+}
+
+int ss_undistort_host(const ss_camera *cam, const ss_keypoint *kp, int n, ss_keypoint *out)
+{
+    if (!cam || n < 0 || (n > 0 && (!kp || !out))) return SS_ERR_INVALID_ARG;
+    if (!ss_undist_focal_ok(cam->fx, cam->fy)) return SS_ERR_INVALID_ARG;
+    const ss_undist_cam u = ss_undist_cam_of(*cam);
+    for (int i = 0; i < n; i++) {
+        ss_keypoint k = kp[i]; /* out may be kp */
+        ss_undist_point(u, k.x, k.y, &k.x, &k.y);
+        out[i] = k;
+    }
+    return SS_OK;
+}
+
+/* The launch of an undistortion call whose device operands are filled in: the cameras checked and staged, one per frame */
+static int undistort_run(ss_ctx *c, ssk_undistort_call &g, const std::string &what, const ss_camera *cams, int n_cams)
+{
+    if (!cams) return fail(c, SS_ERR_INVALID_ARG, what + ": cams is NULL");
+    if (n_cams != 1 && n_cams != g.n_frames) return fail(c, SS_ERR_INVALID_ARG, what + ": n_cams " + std::to_string(n_cams) + " is neither 1 nor n_frames (" + std::to_string(g.n_frames) + ")");
+    for (int k = 0; k < n_cams; k++)
+        if (!ss_undist_focal_ok(cams[k].fx, cams[k].fy)) return fail(c, SS_ERR_INVALID_ARG, what + ": cams[" + std::to_string(k) + "]: fx and fy must be finite and not 0");
+    int rc = call_count_ok(c, what, g.n_frames, "frames");
+    if (rc != SS_OK) return rc;
+    rc = staged_upload(c, c->undist_tab, (size_t)g.n_frames * sizeof(ss_undist_cam), [&](uint8_t *h) {
+        ss_undist_cam *t = (ss_undist_cam *)h;
+        for (int b = 0; b < g.n_frames; b++) t[b] = ss_undist_cam_of(cams[n_cams == 1 ? 0 : b]);
+    });
+    if (rc != SS_OK) return rc;
+    g.cams = c->undist_tab.as<ss_undist_cam>();
+    {
+        /* per row: x and y read and written, the raw save or the rest of the record on top; the counts and the cameras */
+        const int64_t per_row = 16 + (g.raw_xy ? 8 : 0) + ((const void *)g.kp_out != (const void *)g.kp ? 32 : 0);
+        stage_timer t(c, g.raw_xy ? "undistort_in_place" : "undistort", (int64_t)g.n_frames * g.rows * per_row + g.n_frames * (int64_t)(4 + sizeof(ss_undist_cam)));
+        ssk_undistort(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_undistort_pairs_device(ss_ctx *c, const void *d_kp, const void *d_n_kp, int n_frames, int rows_per_frame, const ss_camera *cams, int n_cams,
+                              void *d_kp_out)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const std::string what = "ss_undistort_pairs_device";
+    const int rc = pairs_shape(c, what, "frame", n_frames, rows_per_frame);
+    if (rc != SS_OK) return rc;
+    if (n_frames == 0) return SS_OK;
+    if (!d_kp || !d_n_kp || !d_kp_out) return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
+    ssk_undistort_call g;
+    g.n_frames = n_frames, g.rows = rows_per_frame;
+    g.kp = (const ss_keypoint *)d_kp, g.n_kp = (const int32_t *)d_n_kp, g.kp_out = (ss_keypoint *)d_kp_out;
+    return undistort_run(c, g, what, cams, n_cams);
+}
+
+int ss_undistort_batch_device(ss_ctx *c, const ss_camera *cams, int n_cams, void *d_kp_out)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const std::string what = "ss_undistort_batch_device";
+    if (!have_batch(c, what.c_str())) return SS_ERR_STATE;
+    if (!cams) {
+        if (!c->calibrated) return fail(c, SS_ERR_NOT_CALIBRATED, what + ": cams is NULL and no calibration has been set");
+        cams = &c->cam, n_cams = 1;
+    }
+    const bool in_place = d_kp_out == nullptr;
+    if (in_place && c->batch_undistorted) return fail(c, SS_ERR_STATE, what + ": this batch has been undistorted in place already");
+    ssk_undistort_call g;
+    g.n_frames = c->last_n_frames, g.rows = c->hg.kcap;
+    g.kp = c->ws.kps, g.n_kp = c->ws.n_kp;
+    int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
+    if (in_place) {
+        rc = raw_xy_buffer(c);
+        if (rc != SS_OK) return rc;
+        g.kp_out = c->ws.kps, g.raw_xy = c->d_raw_xy;
+    } else {
+        g.kp_out = (ss_keypoint *)d_kp_out;
+    }
+    rc = undistort_run(c, g, what, cams, n_cams);
+    if (rc == SS_OK && in_place) c->batch_undistorted = true;
+    return rc;
+}
+
+int ss_get_batch_raw_xy(ss_ctx *c, const float **d_xy)
+{
+    if (!c || !d_xy) return SS_ERR_INVALID_ARG;
+    if (!c->have_geom || c->last_n_frames <= 0 || !c->batch_undistorted)
+        return fail(c, SS_ERR_STATE, "ss_get_batch_raw_xy: the current batch has not been undistorted in place");
+    *d_xy = (const float *)c->d_raw_xy;
+    return SS_OK;
+}
+
+int ss_depth_params_from_camera(const ss_camera *cam, int depth_type, ss_depth_params *out)
+{
+    if (!cam || !out || (depth_type != 0 && depth_type != 1)) return SS_ERR_INVALID_ARG;
+    const double bf = cam->baseline * cam->fx;
+    out->bf = (float)bf;
+    out->depth_map_factor = (float)cam->depth_map_factor;
+    out->close_limit = (float)(bf * cam->th_depth / cam->fx);
+    out->depth_type = depth_type;
+    return SS_OK;
+}
+
+/* the message of the first rule the shape of a depth call breaks, or NULL; needs no context */
+static const char *depth_shape_error(const ss_depth_params *p, const void *depth, int width, int height, int64_t row_stride, int64_t frame_stride, int n_frames)
+{
+    if (!p) return "depth: params is NULL";
+    if (p->depth_type != 0 && p->depth_type != 1) return "depth: depth_type must be 0 (float32) or 1 (uint16)";
+    if (!std::isfinite(p->bf) || !std::isfinite(p->depth_map_factor) || !std::isfinite(p->close_limit)) return "depth: bf, depth_map_factor and close_limit must be finite";
+    if (width < 1 || height < 1 || width > (1 << 24) || height > (1 << 24)) return "depth: width and height must be 1 .. 16777216";
+    const int64_t sample = p->depth_type == 1 ? 2 : 4;
+    if (row_stride < width * sample || (n_frames > 1 && frame_stride < row_stride * (height - 1) + width * sample)) return "depth: strides smaller than the frame";
+    if (row_stride > ((int64_t)1 << 40) || frame_stride > ((int64_t)1 << 40)) return "depth: strides above 2^40";
+    if (row_stride % sample != 0 || (n_frames > 1 && frame_stride % sample != 0) || (uintptr_t)depth % (uintptr_t)sample != 0)
+        return "depth: the base and the strides must be multiples of the sample size";
+    return nullptr;
+}
+
+int ss_depth_host(const ss_depth_params *p, const void *depth, int width, int height, int64_t row_stride, const ss_keypoint *kp_raw, const ss_keypoint *kp_un,
+                  int n, float *right, float *depth_out, ss_depth_summary *summary)
+{
+    if (!depth || n < 0 || (n > 0 && (!kp_raw || !right || !depth_out))) return SS_ERR_INVALID_ARG;
+    if (depth_shape_error(p, depth, width, height, row_stride, 0, 1)) return SS_ERR_INVALID_ARG;
+    const float inv = ss_depth_inv(p->depth_map_factor);
+    const bool scale_float = ss_depth_scales_float(inv);
+    ss_depth_summary s = {SS_OK, n, 0, 0};
+    for (int i = 0; i < n; i++) {
+        float d = 0.0f;
+        const bool have = ss_depth_sample((const uint8_t *)depth, width, height, row_stride, p->depth_type, inv, scale_float, kp_raw[i].x, kp_raw[i].y, &d);
+        ss_depth_row(have, d, (kp_un ? kp_un : kp_raw)[i].x, p->bf, &right[i], &depth_out[i]);
+        s.n_depth += depth_out[i] > 0.0f;
+        s.n_close += depth_out[i] > 0.0f && depth_out[i] < p->close_limit;
+    }
+    if (summary) *summary = s;
+    return SS_OK;
+}
+
+/* The two launches of a depth call whose keypoint side is filled in */
+static int depth_run(ss_ctx *c, ssk_depth_call &g, const std::string &what, const ss_depth_params *p, const void *d_depth, int width, int height, int64_t row_stride,
+                     int64_t frame_stride, void *d_right, void *d_depth_out, void *d_summary)
+{
+    if (!d_depth || !d_right || !d_depth_out || !d_summary) return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
+    if (const char *msg = depth_shape_error(p, d_depth, width, height, row_stride, frame_stride, g.n_frames)) return fail(c, SS_ERR_INVALID_ARG, what + ": " + msg);
+    const int rc = call_count_ok(c, what, g.n_frames, "frames");
+    if (rc != SS_OK) return rc;
+    g.width = width, g.height = height;
+    g.depth = (const uint8_t *)d_depth, g.row_stride = row_stride, g.frame_stride = g.n_frames > 1 ? frame_stride : 0;
+    g.p = *p;
+    g.inv = ss_depth_inv(p->depth_map_factor), g.scale_float = ss_depth_scales_float(g.inv);
+    g.right = (float *)d_right, g.depth_out = (float *)d_depth_out, g.summary = (ss_depth_summary *)d_summary;
+    {
+        /* per row: the raw pair, the undistorted x, one sample, the two planes; per frame its count and summary */
+        const int64_t sample = p->depth_type == 1 ? 2 : 4;
+        stage_timer t(c, "depth_lookup", (int64_t)g.n_frames * g.rows * (8 + 4 + sample + 8) + g.n_frames * (int64_t)(4 + sizeof(ss_depth_summary)));
+        ssk_depth(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_depth_pairs_device(ss_ctx *c, const ss_depth_params *p, const void *d_depth, int width, int height, int64_t row_stride, int64_t frame_stride,
+                          const void *d_kp_raw, const void *d_kp_un, const void *d_n_kp, int n_frames, int rows_per_frame, void *d_right, void *d_depth_out,
+                          void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const std::string what = "ss_depth_pairs_device";
+    const int rc = pairs_shape(c, what, "frame", n_frames, rows_per_frame);
+    if (rc != SS_OK) return rc;
+    if (n_frames == 0) return SS_OK;
+    if (!d_kp_raw || !d_n_kp) return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
+    ssk_depth_call g;
+    g.n_frames = n_frames, g.rows = rows_per_frame;
+    g.kp_raw = (const ss_keypoint *)d_kp_raw, g.kp_un = d_kp_un ? (const ss_keypoint *)d_kp_un : g.kp_raw, g.n_kp = (const int32_t *)d_n_kp;
+    return depth_run(c, g, what, p, d_depth, width, height, row_stride, frame_stride, d_right, d_depth_out, d_summary);
+}
+
+int ss_depth_batch_device(ss_ctx *c, const ss_depth_params *p, const void *d_depth, int width, int height, int64_t row_stride, int64_t frame_stride, void *d_right,
+                          void *d_depth_out, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const std::string what = "ss_depth_batch_device";
+    if (!have_batch(c, what.c_str())) return SS_ERR_STATE;
+    ssk_depth_call g;
+    g.n_frames = c->last_n_frames, g.rows = c->hg.kcap;
+    g.kp_raw = g.kp_un = c->ws.kps, g.n_kp = c->ws.n_kp;
+    if (c->batch_undistorted) g.raw_xy = c->d_raw_xy;
+    const int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
+    return depth_run(c, g, what, p, d_depth, width, height, row_stride, frame_stride, d_right, d_depth_out, d_summary);
 }
 
 /* ---- PnP RANSAC (csrc/ss_pnp.hip, csrc/ss_pnp_steps.h) ---- */

@@ -205,6 +205,13 @@ struct ss_ctx {
     } rect_maps[SS_MAX_RECTIFY_MAPS];
     dev_buf<uint8_t> d_rect;
 
+    /* undistortion: the raw (x, y) pairs of the batch, [max_batch][kcap] (a buffer of ws_table, allocated by raw_xy_buffer on first
+     * use, freed with the geometry); whether the current batch was undistorted in place (cleared where last_n_frames is set); the
+     * cameras of a call */
+    float2 *d_raw_xy = nullptr;
+    bool batch_undistorted = false;
+    staged_table undist_tab;
+
     int last_n_frames = 0;
     ss_lvl0 last_lvl0; /* where level 0 of the last batch lives (ptr == NULL: in the pyramid block) */
 
@@ -327,6 +334,9 @@ int upload_train_src(ss_ctx *c, const int32_t *train_src, int n);
 /* The frame_error array a stage of the last batch reads: the extraction's own, or, where a test hook names frames, a copy of it
  * on c->stream in which those frames carry SS_ERR_OVERFLOW. */
 int flagged_frame_error(ss_ctx *c, const std::vector<int> &frames, const int32_t **out);
+
+/* c->d_raw_xy, allocated through the workspace's buffer table when it is not there yet (needs the geometry) */
+int raw_xy_buffer(ss_ctx *c);
 
 /* Hands out the pieces of one buffer in order, each on a 256-byte boundary.  With a null base it only measures. */
 struct carve {

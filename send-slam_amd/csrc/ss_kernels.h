@@ -8,6 +8,7 @@
 #include "../../include/sendslam_orb.h"
 #include "ss_layout.h"
 #include "ss_place_steps.h" /* ss_place_db, a member of ssk_place_call */
+#include "ss_undistort_steps.h" /* ss_undist_cam, the table of ssk_undistort_call */
 
 /* level 0 read in place from the caller's buffer (ptr != NULL: 1-channel image, 16-byte aligned base, row and frame
  * strides; no k_ingest pass), or from the pyramid block (ptr == NULL) */
@@ -779,6 +780,35 @@ struct ssk_place_call {
     int32_t *state = nullptr; /* [n_q][8] */
 };
 void ssk_place_query(hipStream_t s, const ssk_place_call &c, int stage);
+/* ss_undistort.hip: Frame's keypoint post-processing (DESIGN.md "Undistorted keypoints").  One launch: mvKeysUn of every row below
+ * its frame's count.  kp_out == kp: only x and y are written; raw_xy != NULL (the in-place form of a batch, kp_out == kp): the raw
+ * pairs are saved there first */
+struct ssk_undistort_call {
+    int n_frames = 0, rows = 0;
+    const ss_keypoint *kp = nullptr;       /* device [n_frames][rows] */
+    const int32_t *n_kp = nullptr;         /* device [n_frames] */
+    const int32_t *frame_error = nullptr;  /* device [n_frames] or NULL */
+    const ss_undist_cam *cams = nullptr;   /* device [n_frames] */
+    ss_keypoint *kp_out = nullptr;         /* device [n_frames][rows] */
+    float2 *raw_xy = nullptr;              /* device [n_frames][rows] or NULL */
+};
+void ssk_undistort(hipStream_t s, const ssk_undistort_call &g);
+/* Two launches: the summaries' heads, then depth and right coordinate of every row.  raw_xy != NULL: the raw positions are read
+ * there instead of kp_raw */
+struct ssk_depth_call {
+    int n_frames = 0, rows = 0, width = 0, height = 0;
+    const uint8_t *depth = nullptr; /* device: n_frames frames of frame_stride bytes, rows of row_stride bytes */
+    int64_t row_stride = 0, frame_stride = 0;
+    ss_depth_params p = {};
+    float inv = 1.0f;         /* ss_depth_inv(p.depth_map_factor) */
+    bool scale_float = false; /* ss_depth_scales_float(inv) */
+    const ss_keypoint *kp_raw = nullptr, *kp_un = nullptr; /* device [n_frames][rows] */
+    const float2 *raw_xy = nullptr;
+    const int32_t *n_kp = nullptr, *frame_error = nullptr;
+    float *right = nullptr, *depth_out = nullptr; /* device [n_frames][rows] */
+    ss_depth_summary *summary = nullptr;          /* device [n_frames] */
+};
+void ssk_depth(hipStream_t s, const ssk_depth_call &g);
 /* The bookkeeping of SearchBySim3 (the rule: include/sendslam_orb.h).  One workgroup per pair: a base pass over the rows, a barrier,
  * a scatter pass in which every store to one address writes the same value.  marks writes skip1 and skip2; mutual marks the train
  * rows that carry a prior match in taken (workspace, [n_frames][rows]) and writes idx_out and the summary */

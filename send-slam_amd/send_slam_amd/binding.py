@@ -59,7 +59,9 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_covis_params_default", "ss_covis_set_map", "ss_covis_kf_device", "ss_covis_frames_device", "ss_covis", "ss_covis_kf_host",
            "ss_covis_frames_host", "ss_covis_edges_host", "ss_covis_set_map_rows", "ss_global_ba_rows_from_idx_host", "ss_refresh_params_default",
            "ss_refresh_device", "ss_refresh", "ss_refresh_host", "ss_place_params_default", "ss_place_set_database", "ss_place_query_device",
-           "ss_place", "ss_place_query_host"]
+           "ss_place", "ss_place_query_host", "ss_undistort_bounds_host", "ss_proj_view_set_bounds", "ss_undistort_host",
+           "ss_undistort_pairs_device", "ss_undistort_batch_device", "ss_get_batch_raw_xy", "ss_depth_params_from_camera", "ss_depth_host",
+           "ss_depth_pairs_device", "ss_depth_batch_device"]
 
 
 class OrbParams(C.Structure):
@@ -1291,6 +1293,84 @@ def refresh_host(problems, n_kf: int, n_blocks: int, point_rows: int, obs, obs_r
     return pts, pd, info, summary
 
 
+class DepthParams(C.Structure):
+    """ss_depth_params: depth_type 0 float32 samples, 1 uint16 samples"""
+    _fields_ = [("bf", C.c_float), ("depth_map_factor", C.c_float), ("close_limit", C.c_float), ("depth_type", C.c_int32)]
+
+
+DEPTH_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_kp", "n_depth", "n_close")])
+
+
+def depth_params(bf: float, depth_map_factor: float = 1.0, close_limit: float = 0.0, depth_type: int = 0) -> DepthParams:
+    return DepthParams(bf=bf, depth_map_factor=depth_map_factor, close_limit=close_limit, depth_type=depth_type)
+
+
+def depth_params_from_camera(camera: Camera, depth_type: int = 0) -> DepthParams:
+    """ss_depth_params_from_camera: bf, depth_map_factor and close_limit (mThDepth) of a calibration; needs no device"""
+    p = DepthParams()
+    rc = load().ss_depth_params_from_camera(C.byref(camera), int(depth_type), C.byref(p))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_depth_params_from_camera refused its arguments")
+    return p
+
+
+def _cameras_array(cams):
+    """one Camera or a sequence of them -> (a ctypes array, its length); None -> (None, 0)"""
+    if cams is None:
+        return None, 0
+    if isinstance(cams, Camera):
+        cams = [cams]
+    return (Camera * len(cams))(*cams), len(cams)
+
+
+def undistort_bounds_host(camera: Camera) -> np.ndarray:
+    """ss_undistort_bounds_host: Frame::ComputeImageBounds -> float32 (min_x, max_x, min_y, max_y); needs no device"""
+    out = np.empty(4, np.float32)
+    rc = load().ss_undistort_bounds_host(C.byref(camera), out.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_undistort_bounds_host refused its arguments")
+    return out
+
+
+def proj_view_set_bounds(view: ProjView, camera: Camera) -> ProjView:
+    """ss_proj_view_set_bounds: overwrites the four bounds of `view` with those of `camera` and returns it; needs no device"""
+    rc = load().ss_proj_view_set_bounds(C.byref(view), C.byref(camera))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_proj_view_set_bounds refused its arguments")
+    return view
+
+
+def undistort_host(camera: Camera, kp: np.ndarray, in_place: bool = False) -> np.ndarray:
+    """ss_undistort_host: mvKeysUn of KP_DTYPE rows on the host (the text the kernel compiles); in_place: out aliases kp, which
+    must then be a contiguous KP_DTYPE array.  Needs no device"""
+    k = kp if in_place else np.ascontiguousarray(kp, KP_DTYPE).reshape(-1)
+    if in_place and (k.dtype != KP_DTYPE or not k.flags.c_contiguous):
+        raise ValueError("in_place needs a contiguous KP_DTYPE array")
+    out = k if in_place else np.empty(len(k), KP_DTYPE)
+    rc = load().ss_undistort_host(C.byref(camera), k.ctypes.data if len(k) else None, len(k), out.ctypes.data if len(k) else None)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_undistort_host refused its arguments")
+    return out
+
+
+def depth_host(params: DepthParams, depth: np.ndarray, kp_raw: np.ndarray, kp_un=None, width=None):
+    """ss_depth_host: ComputeStereoFromRGBD of one frame on the host.  depth: a 2-D float32 or uint16 array whose rows may be
+    longer than `width` samples (a pitch) -> (right float32 [n], depth float32 [n], summary DEPTH_SUMMARY_DTYPE scalar)"""
+    if depth.ndim != 2 or depth.strides[1] != depth.itemsize:
+        raise ValueError("depth: a 2-D array with contiguous rows")
+    raw = np.ascontiguousarray(kp_raw, KP_DTYPE).reshape(-1)
+    un = None if kp_un is None else np.ascontiguousarray(kp_un, KP_DTYPE).reshape(-1)
+    n = len(raw)
+    right, out = np.empty(n, np.float32), np.empty(n, np.float32)
+    summary = np.zeros(1, DEPTH_SUMMARY_DTYPE)
+    rc = load().ss_depth_host(C.byref(params), depth.ctypes.data, depth.shape[1] if width is None else int(width), depth.shape[0], depth.strides[0],
+                              raw.ctypes.data if n else None, un.ctypes.data if un is not None and n else None, n, right.ctypes.data if n else None,
+                              out.ctypes.data if n else None, summary.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_depth_host refused its arguments")
+    return right, out, summary[0]
+
+
 class OrbError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libsendslam_orb: {message} (status {code})")
@@ -1530,6 +1610,19 @@ def load():
     lib.ss_sim3_marks_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5
     lib.ss_sim3_mutual_batch_device.argtypes = [C.c_void_p] + [C.c_void_p] * 6
     lib.ss_sim3_to_view21.argtypes = [C.POINTER(Camera), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(ProjView)]
+    lib.ss_undistort_bounds_host.argtypes = [C.POINTER(Camera), C.c_void_p]
+    lib.ss_proj_view_set_bounds.argtypes = [C.POINTER(ProjView), C.POINTER(Camera)]
+    lib.ss_undistort_host.argtypes = [C.POINTER(Camera), C.c_void_p, C.c_int, C.c_void_p]
+    lib.ss_undistort_pairs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.ss_undistort_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.ss_get_batch_raw_xy.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    lib.ss_depth_params_from_camera.argtypes = [C.POINTER(Camera), C.c_int, C.POINTER(DepthParams)]
+    lib.ss_depth_host.argtypes = [C.POINTER(DepthParams), C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]
+    lib.ss_depth_pairs_device.argtypes = [C.c_void_p, C.POINTER(DepthParams), C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ss_depth_batch_device.argtypes = [C.c_void_p, C.POINTER(DepthParams), C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -2463,6 +2556,33 @@ class OrbContext:
         return cand, summary, words, score
 
     # ---- PnP RANSAC: a pose for every relocalisation candidate (the rule: include/sendslam_orb.h) ----
+    # ---- undistorted keypoints and RGB-D depth ----
+    def undistort_pairs_device(self, d_kp: int, d_n_kp: int, n_frames: int, rows_per_frame: int, cams, d_kp_out: int):
+        """cams: one Camera (all frames) or n_frames of them; d_kp_out may equal d_kp"""
+        arr, n = _cameras_array(cams)
+        self._check(self._lib.ss_undistort_pairs_device(self._h, d_kp, d_n_kp, int(n_frames), int(rows_per_frame), arr, n, d_kp_out))
+
+    def undistort_batch_device(self, cams=None, d_kp_out: int = 0):
+        """cams None: the calibration set last; d_kp_out 0: in place (the raw pairs are saved first: batch_raw_xy)"""
+        arr, n = _cameras_array(cams)
+        self._check(self._lib.ss_undistort_batch_device(self._h, arr, n, d_kp_out or None))
+
+    def batch_raw_xy(self) -> int:
+        """the device address of the raw pairs the in-place undistortion saved, float32 [n_frames][kp_capacity][2]"""
+        p = C.c_void_p()
+        self._check(self._lib.ss_get_batch_raw_xy(self._h, C.byref(p)))
+        return p.value
+
+    def depth_pairs_device(self, params: DepthParams, d_depth: int, width: int, height: int, row_stride: int, frame_stride: int, d_kp_raw: int,
+                           d_n_kp: int, n_frames: int, rows_per_frame: int, d_right: int, d_depth_out: int, d_summary: int, d_kp_un: int = 0):
+        self._check(self._lib.ss_depth_pairs_device(self._h, C.byref(params), d_depth, int(width), int(height), int(row_stride), int(frame_stride), d_kp_raw,
+                                                    d_kp_un or None, d_n_kp, int(n_frames), int(rows_per_frame), d_right, d_depth_out, d_summary))
+
+    def depth_batch_device(self, params: DepthParams, d_depth: int, width: int, height: int, row_stride: int, frame_stride: int, d_right: int,
+                           d_depth_out: int, d_summary: int):
+        self._check(self._lib.ss_depth_batch_device(self._h, C.byref(params), d_depth, int(width), int(height), int(row_stride), int(frame_stride), d_right,
+                                                    d_depth_out, d_summary))
+
     @staticmethod
     def _pnp_tables(views, kp_src, point_src, n_problems):
         v = _views_array(views)

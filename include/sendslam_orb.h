@@ -2477,8 +2477,10 @@ int ss_stats(ss_ctx *ctx, ss_stage_stats *out, int max_stages);
  * is not kept in normal operation: the first request allocates it, re-runs the FAST kernel on the last
  * batch's pyramid, and the context keeps it from then on); 3 candidates,
  * 4 quadtree-selected keypoints of a level (int32 triples x, y, response; candidates are
- * relative to the (16,16) border origin, selected are level coordinates).  Returns the
- * number of bytes written to dst (<= dst_bytes) or < 0. */
+ * relative to the (16,16) border origin, selected are level coordinates); 5 two int32: the kernel that
+ * built the level in the last batch (0 level 0, 1 k_resize, 2 / 5 k_resize_walk with bands of 32 / 16 rows,
+ * 3 k_resize_pair, 4 k_resize_lds) and whether the batch's level 0 was read in place from the caller's buffer.  Returns the number
+ * of bytes written to dst (<= dst_bytes) or < 0. */
 int ss_debug_fetch(ss_ctx *ctx, int what, int frame, int level, void *dst, int64_t dst_bytes);
 /* Test hook: sorts n <= 2048 items in place with the device's restatement of libstdc++
  * std::sort for ORB-SLAM3's compareNodes.  Item = size << 32 | UL.x << 20 | id (20 bits); the

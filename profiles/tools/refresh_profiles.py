@@ -1,5 +1,5 @@
 """Turns the rocprofv3 output directories of the commands in profiles/README.md into the committed summaries.
-Only full-batch launches are counted (largest grid of each kernel; for k_resize_lds the seven largest = the seven
+Only full-batch launches are counted (largest grid of each kernel; for k_resize_walk (k_resize_lds before it) the seven largest = the seven
 levels): the same bench run also launches smaller batches for its latency fields.
 usage: refresh_profiles.py <gpurun_out dir> [round tag, default r02] [batch, default 64]"""
 import collections
@@ -15,7 +15,7 @@ tag = sys.argv[2] if len(sys.argv) > 2 else "r03"
 batch = int(sys.argv[3]) if len(sys.argv) > 3 else 128
 shape = "1280x720_n2000"
 here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STAGE = {"k_ingest_gray16": "ingest", "k_ingest": "ingest", "k_resize_lds": "resize", "k_fast_score": "fast_blur_nms",
+STAGE = {"k_ingest_gray16": "ingest", "k_ingest": "ingest", "k_resize_lds": "resize", "k_resize_walk": "resize", "k_fast_score": "fast_blur_nms",
          "k_bucket_gather": "bucket_gather", "k_cells_emit": "cells_emit", "k_quadtree": "quadtree", "k_slots": "slots",
          "k_orient_describe": "orient_describe", "k_orient_moments": "orient_describe", "k_keypoint_finish": "orient_describe",
          "k_describe": "orient_describe", "k_match": "match", "k_match_mfma": "match", "k_match_mfma_x": "match",
@@ -43,7 +43,7 @@ def per_kernel(d):
         by[n][int(r["Grid_Size"])][r["Counter_Name"]].append(float(r["Counter_Value"]))
     res = {}
     for n, g in by.items():
-        take = sorted(g, reverse=True)[:7 if n == "k_resize_lds" else 1]
+        take = sorted(g, reverse=True)[:7 if n in ("k_resize_lds", "k_resize_walk") else 1]
         acc = collections.defaultdict(float)
         for x in take:
             for c, v in g[x].items():

@@ -11,7 +11,7 @@ for r in csv.DictReader(open(f)):
     by[n][int(r["Grid_Size"])][r["Counter_Name"]].append(float(r["Counter_Value"]))
 tot = 0
 for n, g in by.items():
-    take = sorted(g, reverse=True)[:7 if n == "k_resize_lds" else 1]
+    take = sorted(g, reverse=True)[:7 if n in ("k_resize_lds", "k_resize_walk") else 1]
     acc = collections.defaultdict(float)
     for x in take:
         for c, v in g[x].items():

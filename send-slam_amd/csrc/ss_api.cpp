@@ -191,6 +191,8 @@ int ensure_geometry(ss_ctx *c, int w, int h)
         for (int l = 1; l + 1 < g.n_levels && e && atoi(e);)
             if (ssk_resize_pair_fits(g, c->tabs.rtab.data(), l)) { c->resize_pair[l] = true; l += 2; } else l += 1;
     }
+    std::fill(std::begin(c->resize_walk), std::end(c->resize_walk), false);
+    for (int l = 1; l < g.n_levels; l++) c->resize_walk[l] = ssk_resize_walk_fits(g, c->tabs.rtab.data(), l);
     rc = ws_alloc(c, WS_GEOMETRY);
     if (rc == SS_OK) rc = ws_alloc(c, WS_OPERANDS);
     if (rc != SS_OK) return rc;
@@ -239,10 +241,11 @@ int run_extract(ss_ctx *c, const void *d_pix, int n, int channels, int64_t row_s
         if (c->resize_pair[l]) { /* two pyramid steps, the middle level never read back */
             stage_timer t(c, "resize", n * (level_px(g, l - 1) + level_px(g, l) + level_px(g, l + 1)));
             ssk_resize_pair(s, c->ws, g, n, l, l0);
+            c->resize_kernel[l] = c->resize_kernel[l + 1] = SSK_RESIZE_PAIR;
             l += 2;
         } else {
             stage_timer t(c, "resize", n * (level_px(g, l - 1) + level_px(g, l)));
-            ssk_resize(s, c->ws, g, n, l, l0);
+            c->resize_kernel[l] = ssk_resize(s, c->ws, g, n, l, l0, c->resize_walk[l], c->wave_slots);
             l += 1;
         }
     }
@@ -404,6 +407,9 @@ int ss_create(int device_ordinal, const ss_orb_params *params, ss_ctx **out)
     if (device_ordinal < 0 || device_ordinal >= n_dev)
         return fail(nullptr, SS_ERR_NO_DEVICE, "device ordinal " + std::to_string(device_ordinal) + " out of range");
     HIP_TRY((ss_ctx *)nullptr, hipSetDevice(device_ordinal));
+    int n_cus = 0;
+    HIP_TRY((ss_ctx *)nullptr, hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, device_ordinal));
+    if (n_cus <= 0) return fail(nullptr, SS_ERR_HIP, "device reports no compute units");
     {
         /* validate the parameters on a nominal size now, so a bad parameter fails here */
         ss_geom g;
@@ -414,6 +420,7 @@ int ss_create(int device_ordinal, const ss_orb_params *params, ss_ctx **out)
     }
     ss_ctx *c = new ss_ctx();
     c->device = device_ordinal;
+    c->wave_slots = (int64_t)SSK_WAVE_SLOTS_PER_CU * n_cus;
     c->params = p;
     if (const char *e = getenv("SENDSLAM_FORCE_INGEST")) c->force_ingest = atoi(e) != 0;
     if (const char *e = getenv("SENDSLAM_TRACK_TIMING")) c->track_timing = atoi(e) != 0;
@@ -1616,6 +1623,12 @@ int ss_debug_fetch(ss_ctx *c, int what, int frame, int level, void *dst, int64_t
             o[3 * i + 2] = SS_PR(packed[i]);
         }
         return n * 12;
+    }
+    if (what == 5) { /* which kernel built this level of the last batch, and where its level 0 lives */
+        if (dst_bytes < 8) return fail(c, SS_ERR_INVALID_ARG, "ss_debug_fetch: dst too small");
+        ((int32_t *)dst)[0] = level == 0 ? 0 : c->resize_kernel[level];
+        ((int32_t *)dst)[1] = c->last_lvl0.ptr != nullptr;
+        return 8;
     }
     return fail(c, SS_ERR_INVALID_ARG, "ss_debug_fetch: unknown selector");
 }

@@ -98,6 +98,9 @@ struct ss_ctx {
     bool calibrated = false;
     bool force_ingest = false; /* SENDSLAM_FORCE_INGEST=1: always copy level 0 into the pyramid block (tests) */
     bool resize_pair[SS_MAX_LEVELS] = {}; /* levels l, l + 1 built by one k_resize_pair launch (checked on the tap tables) */
+    bool resize_walk[SS_MAX_LEVELS] = {}; /* level l may be built by k_resize_walk (checked on the tap tables) */
+    int64_t wave_slots = 0;    /* resident waves of this context's device at k_resize_walk's occupancy (ss_create): ssk_resize */
+    int resize_kernel[SS_MAX_LEVELS] = {}; /* SSK_RESIZE_*: what built level l of the last batch (ss_debug_fetch 5) */
     bool no_desc_x = false;    /* SENDSLAM_MATCH_PACKED=1: batch matches run k_match_mfma on the packed descriptors (A/B tests) */
     ss_camera cam{};
     int cam_id = 0;

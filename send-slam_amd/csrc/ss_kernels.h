@@ -53,7 +53,14 @@ struct ssk_extract_ws {
 /* src -> level 0 in ws.pyr: the gray weights c0, c1, c2 of its channels, its row and frame strides */
 void ssk_ingest(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, const void *src, int channels,
                 int64_t row_stride, int64_t frame_stride, int c0, int c1, int c2);
-void ssk_resize(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, int level, const ss_lvl0 &l0);
+/* one pyramid step, by the kernel the launch's size asks for: k_resize_walk (bands of 32 rows, else of 16) where `walk`
+ * (= ssk_resize_walk_fits(host geometry, HOST tap tables, level), asked once per geometry) and the launch has at least
+ * `wave_slots` waves (SSK_WAVE_SLOTS_PER_CU x the compute units of the context's device: the waves k_resize_walk keeps
+ * resident, eight per SIMD), else k_resize_lds, else k_resize; returns which */
+enum { SSK_WAVE_SLOTS_PER_CU = 32 };
+enum { SSK_RESIZE_DIRECT = 1, SSK_RESIZE_WALK32 = 2, SSK_RESIZE_PAIR = 3, SSK_RESIZE_LDS = 4, SSK_RESIZE_WALK16 = 5 };
+bool ssk_resize_walk_fits(const ss_geom &hg, const ss_rtab *host_rtab, int level);
+int ssk_resize(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, int level, const ss_lvl0 &l0, bool walk, int64_t wave_slots);
 /* levels `level` and `level + 1` in one launch (k_resize_pair), where ssk_resize_pair_fits(host geometry, HOST tap tables)
  * said so */
 bool ssk_resize_pair_fits(const ss_geom &hg, const ss_rtab *host_rtab, int level);

@@ -5,7 +5,7 @@
  * unvendored ORB-SLAM3 library entered at
  * /root/reference/slam_backends/orb_slam_3/orbslam3_mono_networked.cc:594:
  *   K0  k_ingest / k_ingest_gray16   cvtColor RGB/BGR -> gray (or pitched copy) into pyramid level 0
- *   K1  k_resize_lds / k_resize      ORBextractor::ComputePyramid: cv::resize INTER_LINEAR, level by level
+ *   K1  k_resize_walk / k_resize_lds / k_resize   ORBextractor::ComputePyramid: cv::resize INTER_LINEAR, level by level
  *   K2 + K3a + K6a  k_fast_score     cv::FAST-9-16 corner response R-1 (threshold-free), the NMS cv::FAST runs
  *                       inside each 35-px cell window, and GaussianBlur 7x7 sigma 2 (8-bit fixed-point
  *                       path) -- one staged tile feeds all three; survivors go to per-tile sub-lists
@@ -176,6 +176,160 @@ __global__ __launch_bounds__(256) void k_resize(uint8_t *__restrict__ pyr, const
     *(uint32_t *)(base + D.off + (size_t)dy * D.pitch + dx4) = out;
 }
 
+/* The same step for the pyramid's usual scale factors, separable and without LDS: a wave walks a band of RW_BAND
+ * consecutive destination rows top to bottom, 64 lanes x four destination columns.  cv::resize's 8-bit linear path is two
+ * passes with a rounding in between: h = S[s0] * a0 + S[s1] * a1 per source row, then
+ * ((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2 >> 2.  Every lane of the wave is on the same destination row, so the
+ * row taps, the source row pointers and the store pointer are wave-uniform: scalar loads of the y table, scalar registers,
+ * scalar branches.  Neighbouring destination rows share a source row, so the horizontal sums are formed ONCE per source row of
+ * the band and the sums of the last two source rows stay in registers (hx, hy: rows at an even / odd distance from the band's
+ * first, so nothing is copied when the walk advances); a destination row is emitted as soon as the sums of its second row
+ * exist.
+ *   per source row   one 12-byte load from the dword of the first column's s0 on (the four columns need <= 8 bytes from
+ *                    byte s0[0] on), funnelled to 8 bytes (two v_alignbyte); one v_perm_b32 per column puts its two taps'
+ *                    bytes into the HIGH bytes of the two 16-bit halves (256 S) and one v_dot2_u32_u16 multiplies them by
+ *                    16 x (a0, a1): the sum is 4096 h < 2^31 and h >> 4 is its upper half-word, which the vertical pass
+ *                    reads as an SDWA operand -- no shift, no packing.  s1 = s0 + 1 wherever a1 != 0 (ss_geometry.cpp
+ *                    build_axis_table).
+ *   per destination row   products on the 24-bit multiplier, one dword store.  The y table clips indices and keeps weights,
+ *                    so s1 == s0 is possible: both operands are then the same sums.
+ * The source rows of a band are consecutive: RW_AHEAD of them are in flight at any time (a ring of registers, a slot loaded
+ * again as soon as its row's sums are formed), so a wave pays one memory latency per band and not one per row.
+ * No byte outside [row start, row start + pitch) is read: the loads go through a buffer descriptor of the one row, so the
+ * dwords of a 12-byte window that crosses the pitch (the last live lane of a row; every byte it needs is below the width)
+ * come back 0 without a memory access, by one unconditional instruction; lanes at or beyond the width leave.  This rests on
+ * the range check of gfx9 raw buffers (stride 0, no swizzle): num_records counts bytes, and a multi-dword load is checked per
+ * component, each dword against num_records on its own.
+ * The host launches this for the levels whose tap tables it has checked (ssk_resize_walk_fits). */
+#define RW_AHEAD 8 /* source rows in flight; even: hx / hy keep their roles from round to round */
+typedef uint32_t rw_window __attribute__((ext_vector_type(3))); /* one 12-byte load from a dword boundary */
+typedef uint32_t rw_entry __attribute__((ext_vector_type(2)));              /* an ss_rtab entry: s0 | s1 << 16, a0 | a1 << 16 */
+typedef const __attribute__((address_space(4))) rw_entry *rw_scalar_tab;    /* the y table read with scalar loads */
+
+/* b * (h >> 16) on the 24-bit multiplier, the half-word picked by the operand's SDWA selector (the compiler folds the shift
+ * only where it sits in the multiplication's own block) */
+__device__ __forceinline__ int mul24_hi(int b, uint32_t h)
+{
+    int r;
+    asm("v_mul_i32_i24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "=v"(r) : "s"(b), "v"(h));
+    return r;
+}
+
+/* what the kernel needs of the geometry, by value: a wave starts without a dependent load of the level records */
+struct rw_level {
+    int32_t w, h, pitch;      /* destination level */
+    uint32_t off, src_off;    /* both levels in the pyramid block */
+    int32_t src_pitch;        /* of the source rows: the level's, or the caller's level 0 */
+    int32_t xtab_off, ytab_off;
+    uint32_t block_bytes;
+};
+
+/* RW_BAND: destination rows of a band, 32 or 16 (ssk_resize chooses by the launch's size); RW_ROWS: source rows unrolled, a
+ * band's at a scale factor of 1.2 (RW_BAND * 1.2 + 2), a multiple of RW_AHEAD */
+template <int RW_BAND, int RW_ROWS>
+__global__ __launch_bounds__(256) void k_resize_walk(uint8_t *__restrict__ pyr, const ss_rtab *__restrict__ rtab, const rw_level D,
+                                                     const uint8_t *__restrict__ lvl0, int64_t lvl0_fs)
+{
+    /* work items: (band, group of 256 columns), the groups of a band next to each other; four per block */
+    const int groups_x = (D.w + 255) >> 8, n_items = groups_x * ((D.h + RW_BAND - 1) / RW_BAND);
+    const int item = xcd_remap((int)blockIdx.x, (int)gridDim.x) * 4 + rfl((int)(threadIdx.x >> 6));
+    if (item >= n_items) return;
+    const int band = item / groups_x;
+    const int dx4 = ((item - band * groups_x) * 64 + lane_id()) * 4;
+    if (dx4 >= D.w) return;
+    uint8_t *base = pyr + (size_t)blockIdx.y * D.block_bytes;
+    /* lvl0: level 0 lives in the caller's buffer and this is level 1 */
+    const uint8_t *src = lvl0 ? lvl0 + (int64_t)blockIdx.y * lvl0_fs : base + D.src_off;
+    const int spitch = D.src_pitch;
+    uint8_t *dst = base + D.off;
+    const int dpitch = D.pitch;
+    ss_rtab rx[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) rx[i] = rtab[D.xtab_off + dx4 + i]; /* x table is padded past w */
+    /* the window: 12 bytes from the dword of s0[0] on (rows are 16-byte aligned); the funnel {fb:fa} = 8 bytes from byte
+     * s0[0] on; column i reads funnel bytes k, k + 1 (k = s0[i] - s0[0] <= 6) into bytes 1 and 3 */
+    const uint32_t wx = (uint32_t)rx[0].s0 & ~3u, fsh = (uint32_t)rx[0].s0 & 3u;
+    uint32_t sel[4], taps[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const uint32_t k = (uint32_t)((int)rx[i].s0 - (int)rx[0].s0);
+        sel[i] = 0x000C000Cu | (k << 8) | ((k + 1) << 24);
+        taps[i] = ((uint32_t)(uint16_t)rx[i].a0 << 4) | ((uint32_t)(uint16_t)rx[i].a1 << 20); /* 16 x the 11-bit weights: <= 2^15 */
+    }
+    const rw_scalar_tab yt = (rw_scalar_tab)(rtab + D.ytab_off);
+    const int d_last = imin(band * RW_BAND + RW_BAND, D.h) - 1;
+    int d = band * RW_BAND;                      /* the next destination row */
+    rw_entry e = yt[d], en = yt[imin(d + 1, d_last)]; /* its entry and the following row's */
+    const int r_first = (int)(e.x & 0xFFFFu), r_last = (int)(yt[d_last].x >> 16); /* the band's source rows */
+
+    /* the window of one source row through a buffer descriptor of that row alone: [row start, row start + pitch), so the dwords
+     * of a window that crosses the pitch (the last live lane of a row) come back 0 without a memory access -- one unconditional
+     * instruction for every lane.  A row past the band's last gets an empty descriptor: nothing is read. */
+    auto load_row = [&](int row) -> rw_window {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(src + (size_t)imin(row, r_last) * (size_t)spitch), 0,
+                                                                            row <= r_last ? spitch : 0, 0x00020000);
+        return __builtin_amdgcn_raw_buffer_load_b96(rs, (int)wx, 0, 0);
+    };
+    /* horizontal sums of one source row: h >> 4 of the four columns in the upper half-words */
+    auto h_row = [&](const rw_window &w, uint32_t (&hs)[4]) {
+        const uint32_t fa = __builtin_amdgcn_alignbyte(w.y, w.x, fsh), fb = __builtin_amdgcn_alignbyte(w.z, w.y, fsh);
+#pragma unroll
+        for (int i = 0; i < 4; i++) hs[i] = dot2_u16(__builtin_amdgcn_perm(fb, fa, sel[i]), taps[i], 0u);
+    };
+    /* the destination rows whose second source row is `row`: hc its sums, hp those of the row above */
+    auto emit_rows = [&](int row, uint32_t (&hp)[4], const uint32_t (&hc)[4]) {
+        while (d <= d_last && (int)(e.x >> 16) == row) {
+            if ((e.x & 0xFFFFu) == (e.x >> 16)) {
+                /* a clipped row: both operands are this row's sums.  hp is dead after this source row (the next one's sums
+                 * replace it, and s0 does not decrease), so it takes them; kept a branch, the case is rare */
+                asm volatile(""); /* keeps this block a branch: without it the compiler turns the copy into four selects on every row */
+#pragma unroll
+                for (int i = 0; i < 4; i++) hp[i] = hc[i];
+            }
+            const rw_entry en2 = yt[imin(d + 2, d_last)]; /* two rows ahead: the arithmetic below covers the scalar load */
+            const int b0 = (int)(int16_t)(e.y & 0xFFFFu), b1 = (int)e.y >> 16;
+            uint32_t o = (uint32_t)dx4;
+            asm volatile("" : "+v"(o)); /* the lane offset defined in the store's own block: the store then takes the scalar row pointer and a 32-bit offset, with no 64-bit address add */
+            uint32_t out = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                /* every factor is below 2^12 (taps) or 2^16 (h >> 4): the 24-bit multiplier gives the 32-bit products */
+                const int v = ((mul24_hi(b0, hp[i]) >> 16) + (mul24_hi(b1, hc[i]) >> 16) + 2) >> 2;
+                out |= ((uint32_t)v & 0xFFu) << (8 * i);
+            }
+            *(uint32_t *)(dst + (size_t)d * (size_t)dpitch + o) = out;
+            d++;
+            e = en;
+            en = en2;
+        }
+    };
+    uint32_t hx[4] = {0, 0, 0, 0}, hy[4] = {0, 0, 0, 0};
+    /* RW_AHEAD rows in flight: a slot is loaded again, RW_AHEAD rows further down, as soon as its row's sums are formed */
+    rw_window ring[RW_AHEAD];
+#pragma unroll
+    for (int j = 0; j < RW_AHEAD; j++) ring[j] = load_row(r_first + j);
+    /* RW_ROWS rows unrolled (the band's, up to a scale factor of 1.2): inside them the compiler counts the waits on the ring
+     * exactly (vmcnt(RW_AHEAD - 1)).  At the loop's head it waits for everything in flight (vmcnt(0)): the first RW_AHEAD loads
+     * before the band's first row -- they were issued together, one latency -- and the ring again wherever the loop goes round,
+     * for larger scale factors */
+    for (int first = r_first; first <= r_last; first += RW_ROWS) {
+#pragma unroll
+        for (int i = 0; i < RW_ROWS; i++) {
+            const int row = first + i, j = i % RW_AHEAD;
+            if (row > r_last) break;
+            if (i & 1) {
+                h_row(ring[j], hy);
+                ring[j] = load_row(row + RW_AHEAD);
+                emit_rows(row, hx, hy);
+            } else {
+                h_row(ring[j], hx);
+                ring[j] = load_row(row + RW_AHEAD);
+                emit_rows(row, hy, hx);
+            }
+        }
+    }
+}
+
 /* LDS-staged, separable form of the same step for pyramid scale factors <= 1.4 (the source window of a 64x64
  * destination tile then fits 112 B x 80 rows, from a 16-byte aligned column on).  cv::resize's 8-bit linear path is two passes with a rounding in between:
  * h = S[s0] * a0 + S[s1] * a1 per source row, then ((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2 >> 2.  Every
@@ -286,7 +440,7 @@ __global__ __launch_bounds__(256) void k_resize_lds(uint8_t *__restrict__ pyr, c
 }
 
 /* Two pyramid steps in one launch: a block builds a 48x64 tile of level l+1 AND, first, the part of level l it is
- * resized from -- 64 columns x <= 80 rows, computed from level l-1 into LDS by the same two passes as k_resize_lds, never
+ * resized from -- 64 columns x <= 80 rows, computed from level l-1 into LDS by two passes (horizontal sums once per source row, kept in LDS as h >> 4; then the rows), never
  * read back from memory.  Level l is still written (every block stores the columns / rows from its own window origin up to
  * its right / lower neighbour's: each pixel by exactly one block), level l+1 reads level l's ROUNDED bytes from LDS, so
  * both levels are bit for bit what two launches produce.  The windows overlap by 1-2 pixels: 14 % more pixels of level l
@@ -353,7 +507,8 @@ __global__ __launch_bounds__(256) void k_resize_pair(uint8_t *__restrict__ pyr, 
         }
     }
     /* horizontal pass of one step: source rows [0, n_rows) of a window with `pitch` dwords per row whose byte 0 is source
-     * column `origin`; four destination columns per thread with taps t[4] (k_resize_lds pass 1) */
+     * column `origin`; four destination columns per thread with taps t[4]: the window's 12 bytes funnelled to 8, one v_perm_b32 and one
+     * v_dot2_u32_u16 per column as in k_resize_walk, the sums packed two per dword for the LDS store */
     auto h_pass = [&](const uint32_t *win, int pitch, int origin, const ss_rtab (&t)[4], int n_rows, int max_rounds) {
         const int o0 = (int)t[0].s0 - origin, bword = o0 >> 2;
         const uint32_t fsh = (uint32_t)o0 & 3u;
@@ -376,7 +531,7 @@ __global__ __launch_bounds__(256) void k_resize_pair(uint8_t *__restrict__ pyr, 
             *(uint2 *)&hbuf[r][4 * tx] = make_uint2(__builtin_amdgcn_perm(hs[1], hs[0], 0x06050201u), __builtin_amdgcn_perm(hs[3], hs[2], 0x06050201u));
         }
     };
-    /* vertical pass: four pixels of destination row `ry` from the sums of its two source rows (k_resize_lds pass 2) */
+    /* vertical pass: four pixels of destination row `ry` from the sums of its two source rows */
     auto v_dword = [&](const ss_rtab ry, int row0) -> uint32_t {
         const uint2 h0 = *(const uint2 *)&hbuf[ry.s0 - row0][4 * tx], h1 = *(const uint2 *)&hbuf[ry.s1 - row0][4 * tx];
         const int b0 = ry.a0, b1 = ry.a1;
@@ -3136,17 +3291,66 @@ void ssk_ingest(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int 
                        c0, c1, c2, ws.pyr, ws.dg);
 }
 
-void ssk_resize(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, int level, const ss_lvl0 &l0)
+/* May k_resize_walk build `level`?  Checked on the real tap tables: the rows of a band must walk down the source one
+ * row at a time with each destination row on the last row reached or on the last two, and the four columns of every lane must
+ * fit the 8 bytes its funnel forms out of the 12-byte window.  Very large scale factors fail and take k_resize. */
+bool ssk_resize_walk_fits(const ss_geom &hg, const ss_rtab *t, int level)
 {
-    /* source window of a 64x64 tile: (64 * scale + 1 + 15 alignment) bytes x (64 * scale + 2) rows */
-    const float sx = (float)hg.lv[level - 1].w / (float)hg.lv[level].w, sy = (float)hg.lv[level - 1].h / (float)hg.lv[level].h;
-    if (64.f * sx + 18.f <= 4.f * RS_WORDS && (float)RS_TILE_H * sy + 3.f <= (float)RS_ROWS) {
-        dim3 grid(((hg.lv[level].w + SS_TILE_W - 1) / SS_TILE_W) * ((hg.lv[level].h + RS_TILE_H - 1) / RS_TILE_H), n_frames);
-        hipLaunchKernelGGL(k_resize_lds, grid, dim3(256), 0, s, ws.pyr, ws.dg, ws.rtab, level, l0.ptr, l0.pitch, l0.frame_stride);
-    } else {
-        dim3 grid((hg.lv[level].w + 255) / 256, (hg.lv[level].h + 3) / 4, n_frames);
-        hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, s, ws.pyr, ws.dg, ws.rtab, level, l0.ptr, l0.pitch, l0.frame_stride);
+    if (level < 1 || level >= hg.n_levels) return false;
+    const ss_level &S = hg.lv[level - 1], &D = hg.lv[level];
+    for (int y = 0; y < D.h; y++) {
+        const ss_rtab &e = t[D.ytab_off + y];
+        if (e.s1 < e.s0 || e.s1 > e.s0 + 1 || (int)e.s1 >= S.h) return false;
+        if (y > 0 && (e.s0 < t[D.ytab_off + y - 1].s0 || e.s1 < t[D.ytab_off + y - 1].s1)) return false;
     }
+    for (int c = 0; c < D.w; c += 4) {
+        const ss_rtab &f = t[D.xtab_off + c];
+        if ((int)f.s0 >= S.w) return false;
+        for (int i = 0; i < 4; i++) { /* the table is padded past w */
+            const ss_rtab &e = t[D.xtab_off + c + i];
+            if (e.s0 < f.s0 || e.s0 - f.s0 > 6 || (e.a1 != 0 && e.s1 != e.s0 + 1)) return false;
+        }
+    }
+    return true;
+}
+
+template <int BAND, int ROWS>
+static void launch_resize_walk(hipStream_t s, const ssk_extract_ws &ws, const rw_level &L, int n_frames, const uint8_t *lvl0, int64_t lvl0_fs)
+{
+    const int items = ((L.w + 255) / 256) * ((L.h + BAND - 1) / BAND);
+    hipLaunchKernelGGL((k_resize_walk<BAND, ROWS>), dim3((items + 3) / 4, n_frames), dim3(256), 0, s, ws.pyr, ws.rtab, L, lvl0, lvl0_fs);
+}
+
+/* One pyramid step.  k_resize_walk issues 40 % fewer instructions than the tile form, and each of its waves is eight (bands of
+ * 32 rows) or four times (16) as long as a wave of a 64x64 tile.  That pays where the launch fills every wave slot of the chip
+ * (eight per SIMD) at least once: its time is then the sum of its waves' work.  A launch below that -- a single frame, a stereo
+ * pair, the small levels of a short batch -- lasts as long as its longest wave and takes the tile form (k_resize_lds), as
+ * ssk_fast_blur_nms chooses its blocks.  Same results from every form; returns the SSK_RESIZE_* it launched. */
+int ssk_resize(hipStream_t s, const ssk_extract_ws &ws, const ss_geom &hg, int n_frames, int level, const ss_lvl0 &l0, bool walk, int64_t wave_slots)
+{
+    const ss_level &D = hg.lv[level], &S = hg.lv[level - 1];
+    const int64_t groups = (int64_t)((D.w + 255) / 256) * n_frames;
+    const int band = !walk ? 0 : groups * ((D.h + 31) / 32) >= wave_slots ? 32 : groups * ((D.h + 15) / 16) >= wave_slots ? 16 : 0;
+    if (band) {
+        const bool inplace = level == 1 && l0.ptr != nullptr; /* level 0 lives in the caller's buffer */
+        rw_level L;
+        L.w = D.w, L.h = D.h, L.pitch = D.pitch, L.off = D.off, L.src_off = S.off;
+        L.src_pitch = inplace ? l0.pitch : S.pitch;
+        L.xtab_off = D.xtab_off, L.ytab_off = D.ytab_off, L.block_bytes = hg.block_bytes;
+        if (band == 32) launch_resize_walk<32, 40>(s, ws, L, n_frames, inplace ? l0.ptr : nullptr, l0.frame_stride);
+        else launch_resize_walk<16, 24>(s, ws, L, n_frames, inplace ? l0.ptr : nullptr, l0.frame_stride);
+        return band == 32 ? SSK_RESIZE_WALK32 : SSK_RESIZE_WALK16;
+    }
+    /* source window of a 64x64 tile: (64 * scale + 1 + 15 alignment) bytes x (64 * scale + 2) rows */
+    const float sx = (float)S.w / (float)D.w, sy = (float)S.h / (float)D.h;
+    if (64.f * sx + 18.f <= 4.f * RS_WORDS && (float)RS_TILE_H * sy + 3.f <= (float)RS_ROWS) {
+        dim3 grid(((D.w + SS_TILE_W - 1) / SS_TILE_W) * ((D.h + RS_TILE_H - 1) / RS_TILE_H), n_frames);
+        hipLaunchKernelGGL(k_resize_lds, grid, dim3(256), 0, s, ws.pyr, ws.dg, ws.rtab, level, l0.ptr, l0.pitch, l0.frame_stride);
+        return SSK_RESIZE_LDS;
+    }
+    dim3 grid((D.w + 255) / 256, (D.h + 3) / 4, n_frames);
+    hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, s, ws.pyr, ws.dg, ws.rtab, level, l0.ptr, l0.pitch, l0.frame_stride);
+    return SSK_RESIZE_DIRECT;
 }
 
 /* May levels `level` and `level + 1` be built by one k_resize_pair launch?  Checked on the real tap tables, tile by

@@ -746,7 +746,8 @@ int ss_match_proj(ss_ctx *ctx, const ss_proj_view *view, const ss_map_point *poi
  * train) pairs.  Neither upstream source is in the reference tree.  This is the library's own restatement and parity with the real
  * binary stays unpinned, as for the guided, bag-of-words and projection stages.  tests/epi_ref.py is its normative statement;
  * DESIGN.md section 18.  An addition to ABI 5: nothing existing changes ---------------------------------------------------------
- * Out of scope: stereo rows (bOnlyStereo, stereo parallax, unprojectStereo: a row with a right coordinate is treated as monocular),
+ * Out of scope: stereo rows in ss_triangulate_* (a row with a right coordinate is treated as monocular there; the stereo parallax,
+ * unprojectStereo and the three-term error are ss_triangulate_stereo_*, below),
  * fisheye models (pinhole only; keypoints are taken as undistorted, upstream's mvKeysUn: k1 k2 p1 p2 are not read), the per-pair
  * baseline / median-depth gate of CreateNewMapPoints (the caller decides which pairs to submit), Fuse, culling, the observations
  * bookkeeping and any wiring into ss_track.
@@ -899,6 +900,64 @@ int ss_triangulate_pairs_device(ss_ctx *ctx, const void *d_query, const void *d_
  * train_src[b] (ss_match_guided_batch_device's table; -1: no train, every row -1).  A flagged frame on either side voids the pair. */
 int ss_triangulate_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_idx, const ss_epi_pair *pairs, const ss_tri_params *tp,
                                 void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points, void *d_summary);
+/* The stereo form of the triangulation: LocalMapping::CreateNewMapPoints with its stereo branch.  ss_triangulate_* above are
+ * unchanged and keep treating every row as monocular.  The library's own restatement, as the rest of this family: tests/tri_stereo_ref.py
+ * is its normative statement and parity with the real binary stays unpinned; DESIGN.md section 35.  An addition to ABI 5.
+ * Per side a depth plane and a right-coordinate plane (float32, each a pointer and a byte stride per row, so ss_stereo_point is read in
+ * place with stride 16 at &points[0].depth and &points[0].u_right) and, per pair, one ss_tri_stereo_rig on the HOST: bf1, b1, bf2, b2
+ * in double, b upstream's mb in metres and bf = b*fx.  ss_tri_stereo_params holds ss_tri_params as it is and chi2_stereo (upstream:
+ * 7.8); ss_tri_params itself stays 32 bytes (deviation from "one new number joins it": the existing struct may not change).
+ * The rule of a match, in double like steps 1 - 9 above, one IEEE operation per step:
+ *   stereo1 = right1 >= 0 (a NaN is mono), stereo2 likewise.  cos_rays is step 1's cos.  cs1 = cs2 = cos_rays + 1.0; if stereo1:
+ *   cs1 = (d*d - h*h)/(d*d + h*h) with d = (double)depth1, h = b1/2.0; ELSE IF stereo2: the same for side 2 (upstream's else is kept:
+ *   with both sides stereo only cs1 is formed).  cs = min(cs1, cs2).  Deviation: upstream evaluates cos(2*atan2(mb/2, depth)) in float
+ *   through libm; the closed form is the same number in exact arithmetic (tests/test_tri_stereo_ref.py sweeps 2 M pairs).
+ *   Mode 0, triangulated: iff cos_rays < cs && cos_rays > 0 && (stereo1 || stereo2 || cos_rays < cos_parallax_max); step 2's DLT
+ *   unchanged.  Mode 1: else iff stereo1 && cs1 < cs2; X is the unprojection of the row of keyframe 1 (ss_unproject's step 5 position,
+ *   the very function).  Mode 2: else iff stereo2 && cs2 < cs1; the same from keyframe 2.  Else state 1, mode -1.
+ *   Steps 3 - 9 as above, except that on a stereo side steps 5 / 6 become ur = u - bf*(1.0/z), er = ur - right,
+ *   err = (eu*eu + ev*ev) + er*er, accepted iff err <= chi2_stereo * sigma2.  The map point and its descriptor are the mono form's.
+ * With both right planes all -1.0f the states, points and compact blocks are those of ss_triangulate_*, byte for byte.
+ * ss_tri_stereo_info per query row: state (as above), mode (-1 .. 2; -1 where no mode was chosen), cos_rays, cs1, cs2, err1_sq,
+ * err2_sq as floats (0.0f before their step, a NaN as 0.0f).  ss_tri_stereo_summary: ss_tri_summary, then the state-0 rows per mode. */
+typedef struct {          /* 32 bytes, one per pair (a HOST table) */
+    double bf1, b1, bf2, b2;
+} ss_tri_stereo_rig;
+typedef struct {          /* 40 bytes */
+    ss_tri_params tri;
+    double chi2_stereo;   /* upstream: 7.8 */
+} ss_tri_stereo_params;
+typedef struct {          /* 32 bytes, one per query row */
+    int32_t state, mode;
+    float cos_rays, cs1, cs2, err1_sq, err2_sq;
+    int32_t reserved;     /* 0 */
+} ss_tri_stereo_info;
+typedef struct {          /* 80 bytes, one per pair */
+    ss_tri_summary tri;
+    int32_t n_mode[3];    /* rows of state 0 per mode */
+    int32_t reserved;     /* 0 */
+} ss_tri_stereo_summary;
+/* The n couples (kp1[k], kp2[k]) on the host from the text the kernel compiles; depth and right of each side are float [n], or all
+ * four NULL (every row mono).  Needs no device.  Refusals as ss_triangulate_host. */
+int ss_triangulate_stereo_host(const ss_epi_pair *pair, const ss_tri_stereo_rig *rig, const ss_tri_stereo_params *tp, const float *scale,
+                               int n_levels, const ss_keypoint *kp1, const ss_keypoint *kp2, const float *depth1, const float *right1,
+                               const float *depth2, const float *right2, int n, ss_map_point *points, ss_tri_stereo_info *info);
+/* ss_triangulate_pairs_device with the planes of both sides: the value of query row i of pair b at d_x1 + (b * rows_per_frame + i) *
+ * stride, of train row j at d_x2 + (b * rows_per_frame + j) * stride (strides positive multiples of 4, pointers multiples of 4: else
+ * SS_ERR_INVALID_ARG, as for a NULL buffer or table).  rigs: a HOST table of n_frames.  d_info [n_frames][rows_per_frame]
+ * ss_tri_stereo_info, d_summary [n_frames] ss_tri_stereo_summary; the compact blocks as ss_triangulate_pairs_device.  Asynchronous. */
+int ss_triangulate_stereo_pairs_device(ss_ctx *ctx, const void *d_query, const void *d_query_kp, const void *d_n_query, const void *d_train_kp,
+                                       const void *d_n_train, const void *d_idx, int n_frames, int rows_per_frame, const ss_epi_pair *pairs,
+                                       const ss_tri_stereo_rig *rigs, const void *d_depth1, int64_t depth1_stride, const void *d_right1,
+                                       int64_t right1_stride, const void *d_depth2, int64_t depth2_stride, const void *d_right2,
+                                       int64_t right2_stride, const ss_tri_stereo_params *tp, void *d_info, void *d_points, void *d_point_desc,
+                                       void *d_point_rows, void *d_n_points, void *d_summary);
+/* ss_triangulate_batch_device with one pair of planes [n_frames][kp_capacity] that both sides read: row i of frame f at
+ * d_x + (f * kp_capacity + i) * stride. */
+int ss_triangulate_stereo_batch_device(ss_ctx *ctx, const int32_t *train_src, const void *d_idx, const ss_epi_pair *pairs,
+                                       const ss_tri_stereo_rig *rigs, const void *d_depth, int64_t depth_stride, const void *d_right,
+                                       int64_t right_stride, const ss_tri_stereo_params *tp, void *d_info, void *d_points, void *d_point_desc,
+                                       void *d_point_rows, void *d_n_points, void *d_summary);
 
 /* ---- map-point fusion: ORBmatcher::Fuse(pKF, vpMapPoints, th) of LocalMapping::SearchInNeighbors, Fuse(pKF, Scw, ...) of
  * LoopClosing::SearchAndFuse and SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) of the loop and merge
@@ -2457,6 +2516,116 @@ int ss_depth_pairs_device(ss_ctx *ctx, const ss_depth_params *p, const void *d_d
  * batch's keypoints serve as both.  A frame whose frame_error is set gets that status and no depth. */
 int ss_depth_batch_device(ss_ctx *ctx, const ss_depth_params *p, const void *d_depth, int width, int height, int64_t row_stride,
                           int64_t frame_stride, void *d_right, void *d_depth_out, void *d_summary);
+
+/* ---- map points from depth: Frame::UnprojectStereo / KeyFrame::UnprojectStereo, Tracking::StereoInitialization, the close-point
+ * rule of Tracking::CreateNewKeyFrame and Tracking::UpdateLastFrame and the close counts of Tracking::NeedNewKeyFrame: from the
+ * depth per keypoint that ss_stereo_batch_device and ss_depth_*_device leave on the device to a block of ss_map_point that
+ * ss_match_proj_* reads, without a round trip through the host.  No ORB-SLAM3 source is in the reference tree: this is the
+ * library's own restatement, tests/unproject_ref.py is its normative statement, and parity with the real binary stays unpinned.
+ * DESIGN.md section 35.  An addition to ABI 5: nothing existing changes; ss_triangulate_* keep treating every row as monocular, the
+ * stereo form of the triangulation is ss_triangulate_stereo_* (with the epipolar family above).
+ * Not built: the inertial 0.9996 parallax variant of the stereo triangulation (ss_triangulate_stereo_* are the plain rule), the order in which upstream numbers the created points (depth order; it affects ids only: a caller sorts the
+ * few hundred created rows by depth if it needs that), inserting the points into a map, mnFound / mnVisible, wiring into ss_track
+ * or the pipe, fisheye stereo.
+ * Inputs per frame: undistorted keypoints and descriptors, a count clamped to 0 .. rows_per_frame, a depth plane (a pointer and
+ * a byte stride per row: stride 4 reads the float plane ss_depth_*_device writes, stride 16 with the pointer at &points[0].depth
+ * reads ss_stereo_point in place), has_point (uint8 per row, upstream's mvpMapPoints[i] && Observations() >= 1; NULL: no row has a
+ * point), outlier (uint8 per row, or NULL) and one ss_unproject_view, made on the host by ss_unproject_view_init and handed to the
+ * device calls as a HOST table that is copied before the call returns.  The view holds, in double, rcw and tcw as given, fx fy cx
+ * cy, 1.0/fx, 1.0/fy and ow[k] = -((r[k]*t[0] + r[3+k]*t[1]) + r[6+k]*t[2]), as ss_epi_pair_init forms it.
+ * The rule.  All arithmetic is in double, one IEEE operation per step, left to right, no contraction, no library function beyond
+ * sqrt; every test is in its accepting form, so a NaN fails it.  scale[] is the pyramid table, n_levels entries.
+ * 1. Row i is live iff i < n and depth_i > 0; otherwise its state is 3 (a row at or past the count: -1).  A live row whose octave
+ *    is outside 0 .. n_levels - 1 has state 4 and takes no part in steps 2 - 6: it has no key and only n_depth counts it.
+ * 2. The key of a live row is (uint64)bits(depth_i) << 32 | i: positive floats order as their bits, so this is std::sort on
+ *    pair<float, int>.  rank_i is the number of live rows with a lower key; n_not_far the number with depth <= close_limit
+ *    (upstream's break test is first > mThDepth); n_close the number with depth < close_limit (NeedNewKeyFrame, ss_depth_summary).
+ * 3. SS_UNPROJECT_ALL (StereoInitialization): every live row is processed.  SS_UNPROJECT_CLOSE (CreateNewKeyFrame,
+ *    UpdateLastFrame): row i iff rank_i <= max(n_not_far, max_points); upstream's max_points is 100.  This is the closed form of
+ *    upstream's loop "nPoints++; if (depth > mThDepth && nPoints > maxPoint) break;" over the sorted pairs
+ *    (tests/test_unproject_ref.py compares the two).  A live row that is not processed has state 2.
+ * 4. A processed row is created (state 0) iff has_point is NULL or has_point[i] == 0; otherwise it is kept (state 1).
+ * 5. The map point of a created row, (x, y) the keypoint and z = (double)depth: xc = ((x - cx)*z)*invfx, yc = ((y - cy)*z)*invfy;
+ *    X[k] = ((rcw[k]*xc + rcw[3+k]*yc) + rcw[6+k]*z) + ow[k] (Rwc.xc + Ow); n = X - ow; d = sqrt((n0*n0 + n1*n1) + n2*n2).  The row
+ *    has state 5, and no point, unless d > 0 and d is finite.  Normal n/d; max_dist = d*scale[octave]; min_dist = max_dist /
+ *    scale[n_levels - 1]; the eight numbers rounded to float32 once each (MapPoint::UpdateNormalAndDepth with one observation).
+ *    The descriptor is the row's own.
+ * 6. Over the live rows with depth < close_limit: tracked iff has_point[i] != 0 and the row is no outlier (outlier NULL or
+ *    outlier[i] == 0), untracked otherwise (NeedNewKeyFrame's nTrackedClose and nNonTrackedClose).
+ * Outputs: one ss_unproject_info per row; the compact d_points / d_point_desc / d_point_rows (int32 (i, -1)) / d_n_points of the
+ * state-0 rows in ascending row order, byte for byte the layout ss_triangulate_* write and ss_match_proj_pairs_device reads, with
+ * the same alignment rules (the depth plane: 4 bytes); rows from n_points on are not written; the compaction is deterministic
+ * whatever the schedule.  One ss_unproject_summary per frame; its counters are exact and order-free. */
+#define SS_UNPROJECT_ALL 0
+#define SS_UNPROJECT_CLOSE 1
+#define SS_UNPROJECT_CREATED 0
+#define SS_UNPROJECT_KEPT 1
+#define SS_UNPROJECT_FAR 2
+#define SS_UNPROJECT_NO_DEPTH 3
+#define SS_UNPROJECT_OCTAVE 4
+#define SS_UNPROJECT_DEGENERATE 5
+typedef struct {            /* 168 bytes, one per frame (a HOST table) */
+    double rcw[9], tcw[3];
+    double fx, fy, cx, cy, invfx, invfy;
+    double ow[3];
+} ss_unproject_view;
+typedef struct {            /* 16 bytes */
+    int32_t mode;           /* SS_UNPROJECT_ALL or SS_UNPROJECT_CLOSE */
+    int32_t max_points;     /* >= 0; upstream: 100; SS_UNPROJECT_CLOSE only */
+    float close_limit;      /* upstream's mThDepth (ss_depth_params_from_camera's close_limit); finite */
+    int32_t reserved;       /* 0 */
+} ss_unproject_params;
+typedef struct {            /* 4 bytes, one per row */
+    int32_t state;          /* -1 at or past the count, else SS_UNPROJECT_CREATED .. SS_UNPROJECT_DEGENERATE */
+} ss_unproject_info;
+typedef struct {            /* 40 bytes, one per frame */
+    int32_t status;         /* SS_OK, or the frame_error that voided the frame (batch form: n_kp 0, every row -1, no point) */
+    int32_t n_kp;           /* the count as used, clamped to 0 .. rows_per_frame */
+    int32_t n_depth;        /* rows with depth > 0 */
+    int32_t n_close;        /* live rows with depth < close_limit */
+    int32_t n_not_far;      /* live rows with depth <= close_limit */
+    int32_t n_processed;    /* states 0, 1 and 5 */
+    int32_t n_created;      /* state 0 = n_points */
+    int32_t n_kept;         /* state 1 */
+    int32_t n_tracked_close, n_untracked_close; /* step 6 */
+} ss_unproject_summary;
+/* Needs no device.  NULL pointer: SS_ERR_INVALID_ARG.  A pose or camera that is not finite gives state 5 for every created row. */
+int ss_unproject_view_init(const ss_camera *cam, const double rcw[9], const double tcw[3], ss_unproject_view *out);
+/* The whole rule for one frame on the host from the text the kernel compiles; needs no device.  The arrays have `rows` rows
+ * (0 <= rows <= SS_GUIDED_MAX_ROWS), n is the told count (clamped); depth is row 0's, depth_stride bytes to the next.  info gets
+ * rows entries, points / point_desc / point_rows their first *n_points.  SS_ERR_INVALID_ARG: as the device forms; 1 <= n_levels <=
+ * SS_MAX_LEVELS. */
+int ss_unproject_host(const ss_unproject_view *view, const ss_unproject_params *p, const float *scale, int n_levels, const ss_keypoint *kp,
+                      const uint8_t *desc, int n, int rows, const void *depth, int64_t depth_stride, const uint8_t *has_point,
+                      const uint8_t *outlier, ss_unproject_info *info, ss_map_point *points, uint8_t *point_desc, int32_t *point_rows,
+                      int32_t *n_points, ss_unproject_summary *summary);
+/* The rule on caller arrays of n_frames frames: d_kp / d_desc [n_frames][rows_per_frame], counts d_n_kp (device int32 [n_frames]),
+ * d_has_point / d_outlier uint8 [n_frames][rows_per_frame] or NULL, views a HOST table of n_frames.  The depth planes are
+ * n_depth_blocks blocks of rows_per_frame rows: frame b reads block depth_src[b] (a HOST table of n_frames, copied before the call
+ * returns; NULL: block b, and n_depth_blocks >= n_frames), the depth of its row i at d_depth + (depth_src[b] * rows_per_frame + i) *
+ * depth_stride; depth_src[b] == -1: the frame has no depth plane, nothing is read for it and none of its rows has a depth (the
+ * right-eye frames of a stereo batch, whose left eye 2p reads block p of ss_stereo_batch_device's points).  n_depth_blocks and
+ * depth_src are this library's addition to the interface first planned for the family (a pointer and a stride alone): without them
+ * the batch form would read past the [pairs][kp_capacity] points of a stereo batch for its last right eye.
+ * Outputs: d_info [n_frames][rows_per_frame] ss_unproject_info (every row written), the compact blocks [n_frames][rows_per_frame] with d_n_points int32 [n_frames], d_summary [n_frames].  The
+ * pyramid table is the context's.  One launch, asynchronous on the context's stream.  SS_ERR_INVALID_ARG: a bad frame or row count
+ * (rows_per_frame above SS_GUIDED_MAX_ROWS), a bad mode, max_points < 0, a close_limit that is not finite, reserved not 0, a
+ * depth_stride that is not a positive multiple of 4, a depth pointer that is no multiple of 4, n_depth_blocks < 1, a depth_src entry
+ * outside -1 .. n_depth_blocks - 1, a NULL required buffer or table; the context stays usable. */
+int ss_unproject_pairs_device(ss_ctx *ctx, const void *d_kp, const void *d_desc, const void *d_n_kp, const void *d_depth, int64_t depth_stride,
+                              int n_depth_blocks, const int32_t *depth_src, const void *d_has_point, const void *d_outlier, int n_frames, int rows_per_frame, const ss_unproject_view *views,
+                              const ss_unproject_params *p, void *d_info, void *d_points, void *d_point_desc, void *d_point_rows,
+                              void *d_n_points, void *d_summary);
+/* The same on the frames of the last ss_extract_batch_device batch (SS_ERR_STATE without one; rows_per_frame = kp_capacity, which
+ * must not exceed SS_GUIDED_MAX_ROWS).  It reads the batch's keypoints as they are: after an in-place ss_undistort_batch_device
+ * that is mvKeysUn.  A frame whose frame_error is set gets that status and no rows. */
+int ss_unproject_batch_device(ss_ctx *ctx, const void *d_depth, int64_t depth_stride, int n_depth_blocks, const int32_t *depth_src,
+                              const void *d_has_point, const void *d_outlier, const ss_unproject_view *views, const ss_unproject_params *p, void *d_info, void *d_points, void *d_point_desc,
+                              void *d_point_rows, void *d_n_points, void *d_summary);
+/* One frame of n rows (0 .. SS_GUIDED_MAX_ROWS) in host memory, synchronous; outputs as ss_unproject_host's with rows = n. */
+int ss_unproject(ss_ctx *ctx, const ss_unproject_view *view, const ss_unproject_params *p, const ss_keypoint *kp, const uint8_t *desc, int n,
+                 const void *depth, int64_t depth_stride, const uint8_t *has_point, const uint8_t *outlier, ss_unproject_info *info,
+                 ss_map_point *points, uint8_t *point_desc, int32_t *point_rows, int32_t *n_points, ss_unproject_summary *summary);
 
 int ss_synchronize(ss_ctx *ctx);
 /* Orders the context's stream after everything enqueued so far on another stream of the same device

@@ -497,6 +497,8 @@ int ss_destroy(ss_ctx *c)
     staged_free(c->refresh_tab);
     dev_free(c->d_refresh_io);
     staged_free(c->undist_tab);
+    staged_free(c->unproject_tab);
+    dev_free(c->d_unproject_io);
     staged_free(c->place_tab);
     staged_free(c->place_call_tab);
     dev_free(c->d_place_lists);

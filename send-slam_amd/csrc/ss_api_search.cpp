@@ -1,7 +1,7 @@
 /*
  * ss_api_search.cpp -- the search family of the C ABI (include/sendslam_orb.h): guided matching, map-point projection search,
  * map-point fusion, the vocabulary and bag of words, epipolar search and triangulation, the Sim3 RANSAC, the pose-only optimisation, the Sim3 refinement,
- * the local bundle adjustment, the PnP RANSAC, the undistortion of keypoints with the image bounds and the RGB-D depth.  Each has a pairs form on caller arrays, a batch form on the
+ * the local bundle adjustment, the PnP RANSAC, the undistortion of keypoints with the image bounds and the RGB-D depth, the map points from depth.  Each has a pairs form on caller arrays, a batch form on the
  * frames of the last extraction and, for some, a host form.  The context and the helpers they share: ss_ctx.h.
  */
 #include <algorithm>
@@ -30,6 +30,7 @@
 #include "ss_sim3opt_steps.h"
 #include "ss_two_view_steps.h"
 #include "ss_undistort_steps.h"
+#include "ss_unproject_steps.h"
 
 extern "C" {
 
@@ -1450,6 +1451,146 @@ int ss_triangulate_batch_device(ss_ctx *c, const int32_t *train_src, const void 
     t.idx = (const int32_t *)d_idx;
     tri_outputs(t, d_info, d_points, d_point_desc, d_point_rows, d_n_points, d_summary);
     return tri_run(c, t, pairs, tp);
+}
+
+/* ---- the stereo form of the triangulation (k_tri_stereo_eval, ss_tri_stereo_eval) ---- */
+int ss_triangulate_stereo_host(const ss_epi_pair *pair, const ss_tri_stereo_rig *rig, const ss_tri_stereo_params *tp, const float *scale, int n_levels,
+                               const ss_keypoint *kp1, const ss_keypoint *kp2, const float *depth1, const float *right1, const float *depth2,
+                               const float *right2, int n, ss_map_point *points, ss_tri_stereo_info *info)
+{
+    if (!pair || !rig || !tp || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || n < 0 || (n > 0 && (!kp1 || !kp2 || !points || !info))) return SS_ERR_INVALID_ARG;
+    const bool planes = depth1 && right1 && depth2 && right2;
+    if (!planes && (depth1 || right1 || depth2 || right2)) return SS_ERR_INVALID_ARG; /* all four or none */
+    for (int k = 0; k < n; k++) {
+        const ss_tri_stereo_out r = ss_tri_stereo_eval(*pair, *rig, *tp, scale, n_levels, kp1[k].x, kp1[k].y, kp1[k].octave, planes ? depth1[k] : -1.0f,
+                                                       planes ? right1[k] : -1.0f, kp2[k].x, kp2[k].y, kp2[k].octave, planes ? depth2[k] : -1.0f,
+                                                       planes ? right2[k] : -1.0f);
+        points[k] = r.point;
+        info[k] = r.info;
+    }
+    return SS_OK;
+}
+
+/* the message of the first rule a plane of the stereo form breaks, or NULL */
+static const char *tri_plane_error(const void *p, int64_t stride)
+{
+    if (!p) return "triangulation, stereo form: NULL plane";
+    if (stride < 4 || stride % 4 != 0 || stride > ((int64_t)1 << 30)) return "triangulation, stereo form: a plane's stride must be a positive multiple of 4";
+    if ((uintptr_t)p % 4 != 0) return "triangulation, stereo form: a plane's pointer must be a multiple of 4";
+    return nullptr;
+}
+
+/* the three launches of a stereo triangulation whose sides, planes and outputs are filled in */
+static int tri_stereo_run(ss_ctx *c, ssk_tri_stereo_call &sc, const ss_epi_pair *pairs, const ss_tri_stereo_rig *rigs, const ss_tri_stereo_params *tp)
+{
+    ssk_tri_call &t = sc.t;
+    t.tp = tp->tri, sc.chi2_stereo = tp->chi2_stereo;
+    int rc = context_pyramid(c, "epipolar search", &t.n_levels, t.scale);
+    if (rc != SS_OK) return rc;
+    const size_t nr = (size_t)t.n_frames * t.rows, n = (size_t)t.n_frames;
+    rc = carve_from(c, c->d_tri_ws, [&](carve &w) {
+        t.tmp = w.take<ss_map_point>(nr * sizeof(ss_map_point));
+        t.info = w.take<ss_tri_info>(nr * sizeof(ss_tri_info));
+        t.summary = w.take<ss_tri_summary>(n * sizeof(ss_tri_summary));
+    });
+    if (rc != SS_OK) return rc;
+    /* the pairs, then the rigs */
+    const size_t pb = n * sizeof(ss_epi_pair), rb = n * sizeof(ss_tri_stereo_rig);
+    rc = staged_upload(c, c->epi_tab, pb + rb, [&](uint8_t *h) {
+        memcpy(h, pairs, pb);
+        memcpy(h + pb, rigs, rb);
+    });
+    if (rc != SS_OK) return rc;
+    t.pairs = c->epi_tab.as<ss_epi_pair>(), sc.rigs = c->epi_tab.as<ss_tri_stereo_rig>(pb);
+    {
+        /* per row: its match, its keypoint, both records; a matched row reads the other keypoint and the four plane values on top */
+        stage_timer s(c, "tri_stereo_eval", (int64_t)nr * (4 + (int64_t)sizeof(ss_keypoint) + (int64_t)sizeof(ss_tri_info) + (int64_t)sizeof(ss_tri_stereo_info)));
+        ssk_tri_stereo_eval(c->stream, sc);
+    }
+    {
+        stage_timer s(c, "tri_compact", (int64_t)nr * 4 + t.n_frames * (int64_t)(sizeof(ss_tri_summary) + 4));
+        ssk_tri_compact(c->stream, t);
+    }
+    {
+        stage_timer s(c, "tri_stereo_summary", (int64_t)nr * 8 + t.n_frames * (int64_t)(sizeof(ss_tri_summary) + sizeof(ss_tri_stereo_summary)));
+        ssk_tri_stereo_summary(c->stream, sc);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+static void tri_stereo_outputs(ssk_tri_stereo_call &sc, void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points, void *d_summary)
+{
+    sc.sinfo = (ss_tri_stereo_info *)d_info;
+    sc.t.points = (ss_map_point *)d_points, sc.t.point_desc = (uint8_t *)d_point_desc, sc.t.point_rows = (int32_t *)d_point_rows;
+    sc.t.n_points = (int32_t *)d_n_points;
+    sc.ssummary = (ss_tri_stereo_summary *)d_summary;
+}
+
+int ss_triangulate_stereo_pairs_device(ss_ctx *c, const void *d_query, const void *d_query_kp, const void *d_n_query, const void *d_train_kp,
+                                       const void *d_n_train, const void *d_idx, int n_frames, int rows_per_frame, const ss_epi_pair *pairs,
+                                       const ss_tri_stereo_rig *rigs, const void *d_depth1, int64_t depth1_stride, const void *d_right1,
+                                       int64_t right1_stride, const void *d_depth2, int64_t depth2_stride, const void *d_right2, int64_t right2_stride,
+                                       const ss_tri_stereo_params *tp, void *d_info, void *d_points, void *d_point_desc, void *d_point_rows,
+                                       void *d_n_points, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!tp) return fail(c, SS_ERR_INVALID_ARG, "triangulation, stereo form: params is NULL");
+    const int rc = pairs_shape(c, "triangulation, stereo form", "pair", n_frames, rows_per_frame);
+    if (rc != SS_OK) return rc;
+    if (n_frames == 0) return SS_OK;
+    if (!d_query || !d_query_kp || !d_n_query || !d_train_kp || !d_n_train || !d_idx || !pairs || !rigs || !d_info || !d_points || !d_point_desc ||
+        !d_point_rows || !d_n_points || !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "triangulation, stereo form: NULL buffer");
+    const void *planes[4] = {d_depth1, d_right1, d_depth2, d_right2};
+    const int64_t strides[4] = {depth1_stride, right1_stride, depth2_stride, right2_stride};
+    for (int k = 0; k < 4; k++)
+        if (const char *msg = tri_plane_error(planes[k], strides[k])) return fail(c, SS_ERR_INVALID_ARG, msg);
+    ssk_tri_stereo_call sc;
+    ssk_tri_call &t = sc.t;
+    t.n_frames = n_frames;
+    t.rows = rows_per_frame;
+    t.q_kp = (const ss_keypoint *)d_query_kp, t.t_kp = (const ss_keypoint *)d_train_kp;
+    t.q_desc = (const uint8_t *)d_query;
+    t.nq = (const int32_t *)d_n_query, t.nt = (const int32_t *)d_n_train;
+    t.idx = (const int32_t *)d_idx;
+    sc.depth1 = (const uint8_t *)d_depth1, sc.right1 = (const uint8_t *)d_right1, sc.depth2 = (const uint8_t *)d_depth2, sc.right2 = (const uint8_t *)d_right2;
+    sc.depth1_stride = depth1_stride, sc.right1_stride = right1_stride, sc.depth2_stride = depth2_stride, sc.right2_stride = right2_stride;
+    tri_stereo_outputs(sc, d_info, d_points, d_point_desc, d_point_rows, d_n_points, d_summary);
+    return tri_stereo_run(c, sc, pairs, rigs, tp);
+}
+
+int ss_triangulate_stereo_batch_device(ss_ctx *c, const int32_t *train_src, const void *d_idx, const ss_epi_pair *pairs, const ss_tri_stereo_rig *rigs,
+                                       const void *d_depth, int64_t depth_stride, const void *d_right, int64_t right_stride,
+                                       const ss_tri_stereo_params *tp, void *d_info, void *d_points, void *d_point_desc, void *d_point_rows,
+                                       void *d_n_points, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    if (!have_batch(c, "ss_triangulate_stereo_batch_device")) return SS_ERR_STATE;
+    if (!tp) return fail(c, SS_ERR_INVALID_ARG, "triangulation, stereo form: params is NULL");
+    if (!d_idx || !pairs || !rigs || !d_info || !d_points || !d_point_desc || !d_point_rows || !d_n_points || !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, "triangulation, stereo form: NULL buffer");
+    if (const char *msg = tri_plane_error(d_depth, depth_stride)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    if (const char *msg = tri_plane_error(d_right, right_stride)) return fail(c, SS_ERR_INVALID_ARG, msg);
+    batch_operands o;
+    const int rc = batch_operands_of(c, "triangulation, stereo form", train_src, o);
+    if (rc != SS_OK) return rc;
+    ssk_tri_stereo_call sc;
+    ssk_tri_call &t = sc.t;
+    t.n_frames = o.n_frames;
+    t.rows = o.kcap;
+    t.q_kp = t.t_kp = o.kps;
+    t.q_desc = o.desc;
+    t.nq = t.nt = o.n_kp;
+    t.src = o.src;
+    t.frame_error = o.frame_error;
+    t.idx = (const int32_t *)d_idx;
+    sc.depth1 = sc.depth2 = (const uint8_t *)d_depth, sc.right1 = sc.right2 = (const uint8_t *)d_right;
+    sc.depth1_stride = sc.depth2_stride = depth_stride, sc.right1_stride = sc.right2_stride = right_stride;
+    tri_stereo_outputs(sc, d_info, d_points, d_point_desc, d_point_rows, d_n_points, d_summary);
+    return tri_stereo_run(c, sc, pairs, rigs, tp);
 }
 
 /* ---- Sim3 from matched map points (csrc/ss_sim3.hip, csrc/ss_sim3_steps.h) ---- */
@@ -3916,6 +4057,220 @@ int ss_depth_batch_device(ss_ctx *c, const ss_depth_params *p, const void *d_dep
     const int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
     if (rc != SS_OK) return rc;
     return depth_run(c, g, what, p, d_depth, width, height, row_stride, frame_stride, d_right, d_depth_out, d_summary);
+}
+
+/* ---- map points from depth (csrc/ss_unproject.hip, csrc/ss_unproject_steps.h) ---- */
+int ss_unproject_view_init(const ss_camera *cam, const double rcw[9], const double tcw[3], ss_unproject_view *out)
+{
+    if (!cam || !rcw || !tcw || !out) return SS_ERR_INVALID_ARG;
+    ss_unproject_view &v = *out;
+    for (int k = 0; k < 9; k++) v.rcw[k] = rcw[k];
+    for (int k = 0; k < 3; k++) {
+        v.tcw[k] = tcw[k];
+        v.ow[k] = -((rcw[k] * tcw[0] + rcw[3 + k] * tcw[1]) + rcw[6 + k] * tcw[2]);
+    }
+    v.fx = cam->fx, v.fy = cam->fy, v.cx = cam->cx, v.cy = cam->cy, v.invfx = 1.0 / cam->fx, v.invfy = 1.0 / cam->fy;
+    return SS_OK;
+}
+
+/* the message of the first rule the parameters or the depth plane break, or NULL; needs no context */
+static const char *unproject_error(const ss_unproject_params *p, const void *depth, int64_t depth_stride)
+{
+    if (!p) return "unproject: params is NULL";
+    if (p->mode != SS_UNPROJECT_ALL && p->mode != SS_UNPROJECT_CLOSE) return "unproject: mode must be SS_UNPROJECT_ALL or SS_UNPROJECT_CLOSE";
+    if (p->max_points < 0) return "unproject: max_points must be >= 0";
+    if (!std::isfinite(p->close_limit)) return "unproject: close_limit must be finite";
+    if (p->reserved != 0) return "unproject: the reserved field must be 0";
+    if (depth_stride < 4 || depth_stride % 4 != 0 || depth_stride > ((int64_t)1 << 30)) return "unproject: depth_stride must be a positive multiple of 4";
+    if ((uintptr_t)depth % 4 != 0) return "unproject: the depth pointer must be a multiple of 4";
+    return nullptr;
+}
+
+int ss_unproject_host(const ss_unproject_view *view, const ss_unproject_params *p, const float *scale, int n_levels, const ss_keypoint *kp,
+                      const uint8_t *desc, int n, int rows, const void *depth, int64_t depth_stride, const uint8_t *has_point, const uint8_t *outlier,
+                      ss_unproject_info *info, ss_map_point *points, uint8_t *point_desc, int32_t *point_rows, int32_t *n_points,
+                      ss_unproject_summary *summary)
+{
+    if (!view || !scale || n_levels < 1 || n_levels > SS_MAX_LEVELS || rows < 0 || rows > SS_GUIDED_MAX_ROWS || !n_points || !summary) return SS_ERR_INVALID_ARG;
+    if (rows > 0 && (!kp || !desc || !depth || !info || !points || !point_desc || !point_rows)) return SS_ERR_INVALID_ARG;
+    if (unproject_error(p, depth, depth_stride)) return SS_ERR_INVALID_ARG;
+    const int nk = ss_unproject_clamp(n, rows);
+    ss_unproject_summary s = {SS_OK, nk, 0, 0, 0, 0, 0, 0, 0, 0};
+    try {
+        std::vector<uint64_t> keys;
+        std::vector<int> cls((size_t)nk);
+        for (int i = 0; i < nk; i++) {
+            const float d = ss_unproject_depth_at((const uint8_t *)depth, depth_stride, i);
+            cls[i] = ss_unproject_class(d, kp[i].octave, n_levels);
+            s.n_depth += d > 0.0f;
+            if (cls[i] != 0) continue;
+            keys.push_back(ss_unproject_key(d, i));
+            s.n_not_far += d <= p->close_limit;
+            if (d < p->close_limit) {
+                s.n_close++;
+                const bool t = has_point && has_point[i] != 0 && !(outlier && outlier[i] != 0);
+                s.n_tracked_close += t, s.n_untracked_close += !t;
+            }
+        }
+        std::sort(keys.begin(), keys.end());
+        const int quota = ss_unproject_quota(p->mode, p->max_points, s.n_not_far, (int)keys.size());
+        const uint64_t last = quota > 0 ? keys[(size_t)quota - 1] : 0; /* a row is processed iff its key is <= last */
+        for (int i = 0; i < rows; i++) {
+            int state = -1;
+            if (i < nk) {
+                const float d = ss_unproject_depth_at((const uint8_t *)depth, depth_stride, i);
+                if (cls[i] != 0) state = cls[i];
+                else if (!(quota > 0 && ss_unproject_key(d, i) <= last)) state = SS_UNPROJECT_FAR;
+                else {
+                    s.n_processed++;
+                    if (has_point && has_point[i] != 0) {
+                        state = SS_UNPROJECT_KEPT;
+                        s.n_kept++;
+                    } else {
+                        const ss_unproject_out r = ss_unproject_point(*view, scale, n_levels, kp[i].x, kp[i].y, kp[i].octave, d);
+                        if (r.ok) {
+                            state = SS_UNPROJECT_CREATED;
+                            points[s.n_created] = r.point;
+                            memcpy(point_desc + (size_t)s.n_created * SS_DESC_BYTES, desc + (size_t)i * SS_DESC_BYTES, SS_DESC_BYTES);
+                            point_rows[2 * s.n_created] = i, point_rows[2 * s.n_created + 1] = -1;
+                            s.n_created++;
+                        } else {
+                            state = SS_UNPROJECT_DEGENERATE;
+                        }
+                    }
+                }
+            }
+            info[i].state = state;
+        }
+    } catch (const std::bad_alloc &) {
+        return SS_ERR_NO_MEMORY;
+    }
+    *n_points = s.n_created;
+    *summary = s;
+    return SS_OK;
+}
+
+/* The launch of an unprojection whose keypoint side is filled in and whose parameters and depth plane the form has checked
+ * (unproject_error): the buffers and the depth blocks checked, the views staged, the outputs */
+static int unproject_run(ss_ctx *c, ssk_unproject_call &g, const std::string &what, const void *d_depth, int64_t depth_stride, int n_depth_blocks,
+                         const int32_t *depth_src, const void *d_has_point, const void *d_outlier, const ss_unproject_view *views, const ss_unproject_params *p, void *d_info, void *d_points,
+                         void *d_point_desc, void *d_point_rows, void *d_n_points, void *d_summary)
+{
+    if (!d_depth || !views || !d_info || !d_points || !d_point_desc || !d_point_rows || !d_n_points || !d_summary)
+        return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
+    if (n_depth_blocks < 1) return fail(c, SS_ERR_INVALID_ARG, what + ": n_depth_blocks must be >= 1");
+    if (!depth_src && n_depth_blocks < g.n_frames) return fail(c, SS_ERR_INVALID_ARG, what + ": depth_src is NULL and n_depth_blocks is below the frames");
+    for (int b = 0; depth_src && b < g.n_frames; b++)
+        if (depth_src[b] < -1 || depth_src[b] >= n_depth_blocks)
+            return fail(c, SS_ERR_INVALID_ARG, what + ": depth_src[" + std::to_string(b) + "] = " + std::to_string(depth_src[b]) + " names no depth block (" +
+                                                   std::to_string(n_depth_blocks) + ")");
+    int rc = call_count_ok(c, what, g.n_frames, "frames");
+    if (rc != SS_OK) return rc;
+    rc = context_pyramid(c, what, &g.n_levels, g.scale);
+    if (rc != SS_OK) return rc;
+    /* the views, then the depth blocks of the frames */
+    const size_t vb = (size_t)g.n_frames * sizeof(ss_unproject_view);
+    rc = staged_upload(c, c->unproject_tab, vb + (size_t)g.n_frames * sizeof(int32_t), [&](uint8_t *h) {
+        memcpy(h, views, vb);
+        int32_t *src = (int32_t *)(h + vb);
+        for (int b = 0; b < g.n_frames; b++) src[b] = depth_src ? depth_src[b] : b;
+    });
+    if (rc != SS_OK) return rc;
+    g.views = c->unproject_tab.as<ss_unproject_view>(), g.depth_src = c->unproject_tab.as<int32_t>(vb);
+    g.depth = (const uint8_t *)d_depth, g.depth_stride = depth_stride;
+    g.has_point = (const uint8_t *)d_has_point, g.outlier = (const uint8_t *)d_outlier;
+    g.p = *p;
+    g.info = (ss_unproject_info *)d_info;
+    g.points = (ss_map_point *)d_points, g.point_desc = (uint8_t *)d_point_desc, g.point_rows = (int32_t *)d_point_rows;
+    g.n_points = (int32_t *)d_n_points;
+    g.summary = (ss_unproject_summary *)d_summary;
+    {
+        /* per row: its depth, its octave and its state; what a created row moves (its keypoint, 32 bytes of point, its descriptor
+         * twice, its rows) depends on the content; per frame its count, view, point count and summary */
+        stage_timer t(c, "unproject", (int64_t)g.n_frames * g.rows * (4 + 4 + 4) +
+                                          g.n_frames * (int64_t)(4 + sizeof(ss_unproject_view) + 4 + sizeof(ss_unproject_summary)));
+        ssk_unproject(c->stream, g);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return SS_OK;
+}
+
+int ss_unproject_pairs_device(ss_ctx *c, const void *d_kp, const void *d_desc, const void *d_n_kp, const void *d_depth, int64_t depth_stride,
+                              int n_depth_blocks, const int32_t *depth_src, const void *d_has_point, const void *d_outlier, int n_frames, int rows_per_frame, const ss_unproject_view *views,
+                              const ss_unproject_params *p, void *d_info, void *d_points, void *d_point_desc, void *d_point_rows, void *d_n_points,
+                              void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const std::string what = "ss_unproject_pairs_device";
+    const int rc = pairs_shape(c, what, "frame", n_frames, rows_per_frame);
+    if (rc != SS_OK) return rc;
+    if (const char *msg = unproject_error(p, d_depth, depth_stride)) return fail(c, SS_ERR_INVALID_ARG, what + ": " + msg);
+    if (n_frames == 0) return SS_OK;
+    if (!d_kp || !d_desc || !d_n_kp) return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
+    ssk_unproject_call g;
+    g.n_frames = n_frames, g.rows = rows_per_frame;
+    g.kp = (const ss_keypoint *)d_kp, g.desc = (const uint8_t *)d_desc, g.n_kp = (const int32_t *)d_n_kp;
+    return unproject_run(c, g, what, d_depth, depth_stride, n_depth_blocks, depth_src, d_has_point, d_outlier, views, p, d_info, d_points, d_point_desc, d_point_rows, d_n_points,
+                         d_summary);
+}
+
+int ss_unproject_batch_device(ss_ctx *c, const void *d_depth, int64_t depth_stride, int n_depth_blocks, const int32_t *depth_src,
+                              const void *d_has_point, const void *d_outlier,
+                              const ss_unproject_view *views, const ss_unproject_params *p, void *d_info, void *d_points, void *d_point_desc,
+                              void *d_point_rows, void *d_n_points, void *d_summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const std::string what = "ss_unproject_batch_device";
+    if (!have_batch(c, what.c_str())) return SS_ERR_STATE;
+    if (c->hg.kcap > SS_GUIDED_MAX_ROWS) return fail(c, SS_ERR_INVALID_ARG, what + ": kp_capacity " + std::to_string(c->hg.kcap) + " exceeds SS_GUIDED_MAX_ROWS");
+    if (const char *msg = unproject_error(p, d_depth, depth_stride)) return fail(c, SS_ERR_INVALID_ARG, what + ": " + msg);
+    ssk_unproject_call g;
+    g.n_frames = c->last_n_frames, g.rows = c->hg.kcap;
+    g.kp = c->ws.kps, g.desc = c->ws.desc, g.n_kp = c->ws.n_kp;
+    const int rc = flagged_frame_error(c, c->batch_test_flagged, &g.frame_error);
+    if (rc != SS_OK) return rc;
+    return unproject_run(c, g, what, d_depth, depth_stride, n_depth_blocks, depth_src, d_has_point, d_outlier, views, p, d_info, d_points, d_point_desc, d_point_rows, d_n_points,
+                         d_summary);
+}
+
+int ss_unproject(ss_ctx *c, const ss_unproject_view *view, const ss_unproject_params *p, const ss_keypoint *kp, const uint8_t *desc, int n,
+                 const void *depth, int64_t depth_stride, const uint8_t *has_point, const uint8_t *outlier, ss_unproject_info *info,
+                 ss_map_point *points, uint8_t *point_desc, int32_t *point_rows, int32_t *n_points, ss_unproject_summary *summary)
+{
+    if (!c) return SS_ERR_INVALID_ARG;
+    (void)hipSetDevice(c->device);
+    const std::string what = "ss_unproject";
+    if (n < 0 || n > SS_GUIDED_MAX_ROWS) return fail(c, SS_ERR_INVALID_ARG, what + ": n must be 0 .. SS_GUIDED_MAX_ROWS");
+    if (const char *msg = unproject_error(p, depth, depth_stride)) return fail(c, SS_ERR_INVALID_ARG, what + ": " + msg);
+    if (!view || !n_points || !summary || (n > 0 && (!kp || !desc || !depth || !info || !points || !point_desc || !point_rows)))
+        return fail(c, SS_ERR_INVALID_ARG, what + ": NULL buffer");
+    /* one frame of `rows` rows; the depth plane goes up as the caller strides it, so that the device reads what the host would */
+    const size_t rows = (size_t)std::max(n, 1), nn = (size_t)n, kb = sizeof(ss_keypoint), stride = (size_t)depth_stride;
+    const size_t depth_bytes = nn ? (nn - 1) * stride + 4 : 0;
+    const int32_t count = n;
+    enum { KP, DESC, DEPTH, HAS, OUT, N, INFO, PTS, PDESC, PROWS, NPTS, SUM, PIECES };
+    io_piece io[PIECES] = {{kp, nullptr, rows * kb, nn * kb}, {desc, nullptr, rows * 32, nn * 32}, {depth, nullptr, rows * stride, depth_bytes},
+                           {has_point, nullptr, rows, nn}, {outlier, nullptr, rows, nn}, {&count, nullptr, 4, 4},
+                           {nullptr, info, rows * sizeof(ss_unproject_info), nn * sizeof(ss_unproject_info)},
+                           {nullptr, points, rows * sizeof(ss_map_point), 0}, {nullptr, point_desc, rows * 32, 0}, {nullptr, point_rows, rows * 8, 0},
+                           {nullptr, n_points, 4, 4}, {nullptr, summary, sizeof(ss_unproject_summary), sizeof(ss_unproject_summary)}};
+    int rc = io_send(c, c->d_unproject_io, io, PIECES);
+    if (rc == SS_OK)
+        rc = ss_unproject_pairs_device(c, io[KP].d, io[DESC].d, io[N].d, io[DEPTH].d, depth_stride, 1, nullptr, has_point ? io[HAS].d : nullptr,
+                                       outlier ? io[OUT].d : nullptr, 1, (int)rows, view, p, io[INFO].d, io[PTS].d, io[PDESC].d, io[PROWS].d, io[NPTS].d,
+                                       io[SUM].d);
+    if (rc != SS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    rc = io_fetch(c, io, PIECES); /* the count first: it sizes the copies of the compact blocks */
+    if (rc != SS_OK) return rc;
+    const size_t np = (size_t)std::min(std::max(*n_points, 0), n);
+    io_piece blocks[3] = {io[PTS], io[PDESC], io[PROWS]};
+    blocks[0].bytes = np * sizeof(ss_map_point), blocks[1].bytes = np * 32, blocks[2].bytes = np * 8;
+    return io_fetch(c, blocks, 3);
 }
 
 /* ---- PnP RANSAC (csrc/ss_pnp.hip, csrc/ss_pnp_steps.h) ---- */

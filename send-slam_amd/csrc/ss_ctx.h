@@ -214,6 +214,9 @@ struct ss_ctx {
     float2 *d_raw_xy = nullptr;
     bool batch_undistorted = false;
     staged_table undist_tab;
+    /* map points from depth: the views of a call, the host form's device copies */
+    staged_table unproject_tab;
+    dev_buf<uint8_t> d_unproject_io;
 
     int last_n_frames = 0;
     ss_lvl0 last_lvl0; /* where level 0 of the last batch lives (ptr == NULL: in the pyramid block) */

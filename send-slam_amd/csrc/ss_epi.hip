@@ -12,6 +12,8 @@
  *   E-B  k_epi_summary  one workgroup per pair: the sums of the per-row counters next to what k_guided_finish counted
  *   T-A  k_tri_eval     one thread per query row: steps 1 - 9 in double with the 4 x 4 arrays in registers, the info record, the
  *                       map point of the row into a workspace
+ *   T-A' k_tri_stereo_eval     the stereo form of T-A (ss_tri_stereo_eval): depth and right coordinate of both rows from strided planes;
+ *                       T-B runs on the mono records it leaves in the workspace; k_tri_stereo_summary adds the rows per mode
  *   T-B  k_tri_compact  one workgroup per pair walks the rows in chunks of SSK_TRI_CHUNK in ascending order: ballot and prefix
  *                       sums place the state-0 rows, so the compact block is in query-row order whatever the schedule
  *
@@ -139,6 +141,66 @@ __global__ __launch_bounds__(256) void k_tri_eval(ssk_tri_call a)
     }
 }
 
+/* T-A, stereo form.  As k_tri_eval, with the depth and right coordinate of both rows; the mono record goes to the workspace for T-B */
+__global__ __launch_bounds__(256) void k_tri_stereo_eval(ssk_tri_stereo_call c)
+{
+    const ssk_tri_call &a = c.t;
+    const int b = (int)blockIdx.y, rows = a.rows;
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= rows) return;
+    const gd_frame f = gd_frame_of(a.src, a.frame_error, a.nq, a.nt, rows, b);
+    const int n_levels = min(max(a.n_levels, 1), SS_MAX_LEVELS);
+    const size_t o = (size_t)b * rows + i;
+    const int j = i < f.nq ? a.idx[o] : -1;
+    ss_tri_stereo_out r = ss_tri_stereo_rejected(-1, -1, 0.0, 0.0, 0.0, 0.0, 0.0);
+    if (j >= 0 && j < f.nt) {
+        const size_t t = (size_t)f.t * rows + j;
+        const ss_keypoint *k1 = a.q_kp + o, *k2 = a.t_kp + t;
+        const float2 p1 = *(const float2 *)k1, p2 = *(const float2 *)k2;
+        ss_tri_stereo_params sp;
+        sp.tri = a.tp, sp.chi2_stereo = c.chi2_stereo;
+        const float d1 = *(const float *)(c.depth1 + (int64_t)o * c.depth1_stride), u1 = *(const float *)(c.right1 + (int64_t)o * c.right1_stride);
+        const float d2 = *(const float *)(c.depth2 + (int64_t)t * c.depth2_stride), u2 = *(const float *)(c.right2 + (int64_t)t * c.right2_stride);
+        r = ss_tri_stereo_eval(a.pairs[b], c.rigs[b], sp, a.scale, n_levels, p1.x, p1.y, k1->octave, d1, u1, p2.x, p2.y, k2->octave, d2, u2);
+    }
+    c.sinfo[o] = r.info;
+    ss_tri_info m;
+    m.state = r.info.state, m.cos_parallax = r.info.cos_rays, m.err1_sq = r.info.err1_sq, m.err2_sq = r.info.err2_sq;
+    a.info[o] = m;
+    if (r.info.state == 0) {
+        float4 *po = (float4 *)(a.tmp + o);
+        po[0] = make_float4(r.point.x, r.point.y, r.point.z, r.point.nx);
+        po[1] = make_float4(r.point.ny, r.point.nz, r.point.min_dist, r.point.max_dist);
+    }
+}
+
+/* T-C, stereo form.  grid (pairs), 256 threads, after T-B: its summary and the state-0 rows per mode */
+__global__ __launch_bounds__(256) void k_tri_stereo_summary(ssk_tri_stereo_call c)
+{
+    __shared__ int cnt[3];
+    const int b = (int)blockIdx.x, tid = (int)threadIdx.x, rows = c.t.rows;
+    const ss_tri_summary s = c.t.summary[b];
+    const int nq = min(max(s.n_query, 0), rows);
+    if (tid < 3) cnt[tid] = 0;
+    __syncthreads();
+    int n0 = 0, n1 = 0, n2 = 0;
+    for (int i = tid; i < nq; i += 256) {
+        const ss_tri_stereo_info v = c.sinfo[(size_t)b * rows + i];
+        if (v.state == 0) n0 += v.mode == 0, n1 += v.mode == 1, n2 += v.mode == 2;
+    }
+    if (n0) atomicAdd(&cnt[0], n0);
+    if (n1) atomicAdd(&cnt[1], n1);
+    if (n2) atomicAdd(&cnt[2], n2);
+    __syncthreads();
+    if (tid == 0) {
+        ss_tri_stereo_summary out;
+        out.tri = s;
+        out.n_mode[0] = cnt[0], out.n_mode[1] = cnt[1], out.n_mode[2] = cnt[2];
+        out.reserved = 0;
+        c.ssummary[b] = out;
+    }
+}
+
 /* T-B.  grid (pairs), SSK_TRI_CHUNK threads */
 __global__ __launch_bounds__(SSK_TRI_CHUNK) void k_tri_compact(ssk_tri_call a)
 {
@@ -209,6 +271,16 @@ void ssk_epi_summary(hipStream_t s, const ssk_guided_call &g, const ssk_epi_call
 void ssk_tri_eval(hipStream_t s, const ssk_tri_call &t)
 {
     hipLaunchKernelGGL(k_tri_eval, dim3((unsigned)((t.rows + 255) / 256), (unsigned)t.n_frames), dim3(256), 0, s, t);
+}
+
+void ssk_tri_stereo_eval(hipStream_t s, const ssk_tri_stereo_call &c)
+{
+    hipLaunchKernelGGL(k_tri_stereo_eval, dim3((unsigned)((c.t.rows + 255) / 256), (unsigned)c.t.n_frames), dim3(256), 0, s, c);
+}
+
+void ssk_tri_stereo_summary(hipStream_t s, const ssk_tri_stereo_call &c)
+{
+    hipLaunchKernelGGL(k_tri_stereo_summary, dim3((unsigned)c.t.n_frames), dim3(256), 0, s, c);
 }
 
 void ssk_tri_compact(hipStream_t s, const ssk_tri_call &t)

@@ -342,6 +342,20 @@ struct ssk_tri_call {
 };
 void ssk_tri_eval(hipStream_t s, const ssk_tri_call &t);
 void ssk_tri_compact(hipStream_t s, const ssk_tri_call &t);
+/* The stereo form: eval reads the planes of both sides (query row i of pair b at x1 + (b * rows + i) * stride, train row j of frame
+ * f = src[b] (NULL: b) at x2 + (f * rows + j) * stride), writes sinfo and, for ssk_tri_compact as it is, the mono record t.info
+ * (workspace) and the point into t.tmp; compact writes t.summary (workspace); summary adds the state-0 rows per mode */
+struct ssk_tri_stereo_call {
+    ssk_tri_call t;
+    const uint8_t *depth1 = nullptr, *right1 = nullptr, *depth2 = nullptr, *right2 = nullptr;
+    int64_t depth1_stride = 4, right1_stride = 4, depth2_stride = 4, right2_stride = 4;
+    const ss_tri_stereo_rig *rigs = nullptr; /* device [n_frames] */
+    double chi2_stereo = 0.0;
+    ss_tri_stereo_info *sinfo = nullptr;
+    ss_tri_stereo_summary *ssummary = nullptr;
+};
+void ssk_tri_stereo_eval(hipStream_t s, const ssk_tri_stereo_call &c);
+void ssk_tri_stereo_summary(hipStream_t s, const ssk_tri_stereo_call &c);
 /* ss_sim3.hip: Sim3 from matched map points (DESIGN.md "Sim3 RANSAC").  Pair b solves the matches idx[b][i] of its query rows with
  * the rows of train frame src[b] (NULL: b).  gather (one workgroup per pair, SSK_SIM3_CHUNK rows at a time in ascending order)
  * numbers the correspondences and writes their twelve floats as a structure of arrays (corr: 12 planes of [n_frames][rows]), the
@@ -816,6 +830,32 @@ struct ssk_depth_call {
     ss_depth_summary *summary = nullptr;          /* device [n_frames] */
 };
 void ssk_depth(hipStream_t s, const ssk_depth_call &g);
+/* ss_unproject.hip: map points from depth (DESIGN.md "Map points from depth").  One launch, one workgroup per frame: the counts, the
+ * radix select of the threshold key, then the rows in ascending chunks of SSK_UNPROJECT_CHUNK: state, map point and the ordered
+ * compaction.  The depth of row i of frame b is at depth + (depth_src[b] * rows + i) * depth_stride (depth_src NULL: block b); a
+ * frame whose depth_src is negative reads no depth and has none */
+#define SSK_UNPROJECT_CHUNK 1024
+struct ssk_unproject_call {
+    int n_frames = 0, rows = 0;
+    const ss_keypoint *kp = nullptr;          /* device [n_frames][rows] */
+    const uint8_t *desc = nullptr;
+    const int32_t *n_kp = nullptr, *frame_error = nullptr;
+    const uint8_t *depth = nullptr;
+    int64_t depth_stride = 4;
+    const int32_t *depth_src = nullptr;       /* device [n_frames] or NULL */
+    const uint8_t *has_point = nullptr, *outlier = nullptr; /* device [n_frames][rows] or NULL */
+    const ss_unproject_view *views = nullptr; /* device [n_frames] */
+    ss_unproject_params p = {};
+    int n_levels = 1;
+    float scale[SS_MAX_LEVELS] = {};
+    ss_unproject_info *info = nullptr;
+    ss_map_point *points = nullptr;
+    uint8_t *point_desc = nullptr;
+    int32_t *point_rows = nullptr;
+    int32_t *n_points = nullptr;
+    ss_unproject_summary *summary = nullptr;
+};
+void ssk_unproject(hipStream_t s, const ssk_unproject_call &g);
 /* The bookkeeping of SearchBySim3 (the rule: include/sendslam_orb.h).  One workgroup per pair: a base pass over the rows, a barrier,
  * a scatter pass in which every store to one address writes the same value.  marks writes skip1 and skip2; mutual marks the train
  * rows that carry a prior match in taken (workspace, [n_frames][rows]) and writes idx_out and the summary */

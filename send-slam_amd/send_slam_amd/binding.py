@@ -61,7 +61,9 @@ EXPORTS = ["ss_abi_version", "ss_orb_params_default", "ss_create", "ss_destroy",
            "ss_refresh_device", "ss_refresh", "ss_refresh_host", "ss_place_params_default", "ss_place_set_database", "ss_place_query_device",
            "ss_place", "ss_place_query_host", "ss_undistort_bounds_host", "ss_proj_view_set_bounds", "ss_undistort_host",
            "ss_undistort_pairs_device", "ss_undistort_batch_device", "ss_get_batch_raw_xy", "ss_depth_params_from_camera", "ss_depth_host",
-           "ss_depth_pairs_device", "ss_depth_batch_device"]
+           "ss_depth_pairs_device", "ss_depth_batch_device", "ss_unproject_view_init", "ss_unproject_host", "ss_unproject_pairs_device",
+           "ss_unproject_batch_device", "ss_unproject", "ss_triangulate_stereo_host", "ss_triangulate_stereo_pairs_device",
+           "ss_triangulate_stereo_batch_device"]
 
 
 class OrbParams(C.Structure):
@@ -945,6 +947,52 @@ def triangulate_host(pair, params: TriParams, scale, kp1: np.ndarray, kp2: np.nd
     return pts, info
 
 
+class TriStereoRig(C.Structure):
+    """ss_tri_stereo_rig: b the baseline in metres (upstream's mb), bf = b * fx, of both sides of a pair"""
+    _fields_ = [("bf1", C.c_double), ("b1", C.c_double), ("bf2", C.c_double), ("b2", C.c_double)]
+
+
+class TriStereoParams(C.Structure):
+    _fields_ = [("tri", TriParams), ("chi2_stereo", C.c_double)]
+
+
+TRI_STEREO_RIG_DTYPE = np.dtype([(n, "<f8") for n in ("bf1", "b1", "bf2", "b2")])
+TRI_STEREO_INFO_DTYPE = np.dtype([("state", "<i4"), ("mode", "<i4"), ("cos_rays", "<f4"), ("cs1", "<f4"), ("cs2", "<f4"), ("err1_sq", "<f4"),
+                                  ("err2_sq", "<f4"), ("reserved", "<i4")])
+TRI_STEREO_SUMMARY_DTYPE = np.dtype(TRI_SUMMARY_DTYPE.descr + [("n_mode", "<i4", (3,)), ("reserved", "<i4")])
+
+
+def tri_stereo_params(chi2_stereo: float = 7.8, **tri) -> TriStereoParams:
+    """upstream's CreateNewMapPoints: tri_params() and 7.8 for a stereo side"""
+    return TriStereoParams(tri=tri_params(**tri), chi2_stereo=chi2_stereo)
+
+
+def _rigs_array(rigs):
+    """one TriStereoRig, a sequence of them or a TRI_STEREO_RIG_DTYPE array -> a contiguous TRI_STEREO_RIG_DTYPE array"""
+    if isinstance(rigs, TriStereoRig):
+        rigs = [rigs]
+    if isinstance(rigs, np.ndarray):
+        return np.ascontiguousarray(rigs, TRI_STEREO_RIG_DTYPE).reshape(-1)
+    return np.frombuffer(b"".join(bytes(v) for v in rigs), TRI_STEREO_RIG_DTYPE).copy()
+
+
+def triangulate_stereo_host(pair, rig: TriStereoRig, params: TriStereoParams, scale, kp1, kp2, depth1=None, right1=None, depth2=None, right2=None):
+    """ss_triangulate_stereo_host: the couples (kp1[k], kp2[k]) with the depth and right coordinate of each side (float32 [n]; all None:
+    every row mono) -> (MAP_POINT_DTYPE rows, TRI_STEREO_INFO_DTYPE rows); needs no device"""
+    w, sc, k1, k2 = _one_pair_couples(pair, scale, kp1, kp2)
+    n = len(k1)
+    planes = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1) for a in (depth1, right1, depth2, right2)]
+    if any(a is not None and len(a) != n for a in planes):
+        raise ValueError("one depth and right coordinate per couple")
+    pts, info = np.empty(n, MAP_POINT_DTYPE), np.empty(n, TRI_STEREO_INFO_DTYPE)
+    ptr = lambda a: a.ctypes.data if a is not None and n else None  # noqa: E731
+    rc = load().ss_triangulate_stereo_host(w.ctypes.data, C.byref(rig), C.byref(params), sc.ctypes.data, len(sc), ptr(k1), ptr(k2), *[ptr(a) for a in planes],
+                                           n, ptr(pts), ptr(info))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_triangulate_stereo_host refused its arguments")
+    return pts, info
+
+
 class VocabShape(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("n_nodes", C.c_int32), ("n_words", C.c_int32), ("max_depth", C.c_int32)]
 
@@ -1371,6 +1419,112 @@ def depth_host(params: DepthParams, depth: np.ndarray, kp_raw: np.ndarray, kp_un
     return right, out, summary[0]
 
 
+# ---- map points from depth (the rule: include/sendslam_orb.h) ----
+SS_UNPROJECT_ALL, SS_UNPROJECT_CLOSE = 0, 1
+SS_UNPROJECT_CREATED, SS_UNPROJECT_KEPT, SS_UNPROJECT_FAR, SS_UNPROJECT_NO_DEPTH, SS_UNPROJECT_OCTAVE, SS_UNPROJECT_DEGENERATE = range(6)
+
+
+class UnprojectView(C.Structure):
+    """ss_unproject_view: the pose and camera of one frame, in double"""
+    _fields_ = [("rcw", C.c_double * 9), ("tcw", C.c_double * 3)] + [(n, C.c_double) for n in ("fx", "fy", "cx", "cy", "invfx", "invfy")] + \
+               [("ow", C.c_double * 3)]
+
+
+class UnprojectParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("max_points", C.c_int32), ("close_limit", C.c_float), ("reserved", C.c_int32)]
+
+
+UNPROJECT_VIEW_DTYPE = np.dtype([("rcw", "<f8", (9,)), ("tcw", "<f8", (3,))] + [(n, "<f8") for n in ("fx", "fy", "cx", "cy", "invfx", "invfy")] +
+                                [("ow", "<f8", (3,))])
+UNPROJECT_INFO_DTYPE = np.dtype([("state", "<i4")])
+UNPROJECT_SUMMARY_DTYPE = np.dtype([(n, "<i4") for n in ("status", "n_kp", "n_depth", "n_close", "n_not_far", "n_processed", "n_created", "n_kept",
+                                                         "n_tracked_close", "n_untracked_close")])
+
+
+def unproject_params(mode: int = SS_UNPROJECT_CLOSE, max_points: int = 100, close_limit: float = 0.0) -> UnprojectParams:
+    """upstream's CreateNewKeyFrame / UpdateLastFrame: the close rule with 100 points; close_limit is mThDepth"""
+    return UnprojectParams(mode=mode, max_points=max_points, close_limit=close_limit, reserved=0)
+
+
+def unproject_view(camera: Camera, rcw, tcw) -> UnprojectView:
+    """ss_unproject_view_init: the view of `camera` at the pose (rcw, tcw); needs no device"""
+    r, t = np.ascontiguousarray(rcw, np.float64).reshape(9), np.ascontiguousarray(tcw, np.float64).reshape(3)
+    v = UnprojectView()
+    rc = load().ss_unproject_view_init(C.byref(camera), r.ctypes.data, t.ctypes.data, C.byref(v))
+    if rc != SS_OK:
+        raise OrbError(rc, "ss_unproject_view_init refused its arguments")
+    return v
+
+
+def _unproject_views_array(views):
+    """one UnprojectView, a sequence of them or an UNPROJECT_VIEW_DTYPE array -> a contiguous UNPROJECT_VIEW_DTYPE array"""
+    if isinstance(views, UnprojectView):
+        views = [views]
+    if isinstance(views, np.ndarray):
+        return np.ascontiguousarray(views, UNPROJECT_VIEW_DTYPE).reshape(-1)
+    return np.frombuffer(b"".join(bytes(v) for v in views), UNPROJECT_VIEW_DTYPE).copy()
+
+
+def _depth_plane(depth, rows):
+    """a float32 array of `rows` depths, or an array of records with a float32 field "depth" (STEREO_POINT_DTYPE), read in place ->
+    (the array kept alive, the address of row 0's depth, the byte stride)"""
+    d = np.asarray(depth)
+    if d.dtype.fields:
+        d = np.ascontiguousarray(d).reshape(-1)
+        if d.dtype.fields["depth"][0] != np.dtype("<f4"):
+            raise ValueError("depth: the field must be float32")
+        at, stride = d.ctypes.data + d.dtype.fields["depth"][1], d.dtype.itemsize
+    else:
+        d = np.ascontiguousarray(d, np.float32).reshape(-1)
+        at, stride = d.ctypes.data, 4
+    if len(d) != rows:
+        raise ValueError("one depth per keypoint row")
+    return d, at, stride
+
+
+def _row_flags(flags, rows, name):
+    if flags is None:
+        return None
+    f = np.ascontiguousarray(flags, np.uint8).reshape(-1)
+    if len(f) != rows:
+        raise ValueError(f"{name}: one byte per keypoint row")
+    return f
+
+
+def _unproject_one(call, what, kp, desc, depth, n, has_point, outlier):
+    """the arrays of one frame for ss_unproject_host / ss_unproject -> (info, points, point_desc, point_rows, summary)"""
+    k = np.ascontiguousarray(kp, KP_DTYPE).reshape(-1)
+    rows = len(k)
+    de = np.ascontiguousarray(desc, np.uint8).reshape(rows, 32)
+    d, d_at, stride = _depth_plane(depth, rows)
+    hp, ol = _row_flags(has_point, rows, "has_point"), _row_flags(outlier, rows, "outlier")
+    info = np.empty(rows, UNPROJECT_INFO_DTYPE)
+    pts, pd, pr = np.zeros(rows, MAP_POINT_DTYPE), np.zeros((rows, 32), np.uint8), np.zeros((rows, 2), np.int32)
+    n_pts, summary = np.zeros(1, np.int32), np.zeros(1, UNPROJECT_SUMMARY_DTYPE)
+
+    def ptr(a):
+        return a.ctypes.data if a is not None and a.size else None
+    rc = call(rows if n is None else int(n), rows, ptr(k), ptr(de), d_at if rows else None, stride, ptr(hp), ptr(ol), ptr(info), ptr(pts), ptr(pd), ptr(pr),
+              n_pts.ctypes.data, summary.ctypes.data)
+    if rc != SS_OK:
+        raise OrbError(rc, what + " refused its arguments")
+    m = int(n_pts[0])
+    return info, pts[:m], pd[:m], pr[:m], summary[0]
+
+
+def unproject_host(view: UnprojectView, params: UnprojectParams, scale, kp, desc, depth, n=None, has_point=None, outlier=None):
+    """ss_unproject_host: the whole rule for one frame on the host (the text the kernel compiles).  depth: float32 [rows], or records
+    with a "depth" field read in place; n: the told count (None: every row) -> (UNPROJECT_INFO_DTYPE [rows], MAP_POINT_DTYPE
+    [n_points], uint8 [n_points][32], int32 [n_points][2], UNPROJECT_SUMMARY_DTYPE scalar); needs no device"""
+    sc = np.ascontiguousarray(scale, np.float32)
+    lib = load()
+
+    def call(n_, rows, k, de, d_at, stride, hp, ol, info, pts, pd, pr, n_pts, summary):
+        return lib.ss_unproject_host(C.byref(view), C.byref(params), sc.ctypes.data, len(sc), k, de, n_, rows, d_at, stride, hp, ol, info, pts, pd, pr,
+                                     n_pts, summary)
+    return _unproject_one(call, "ss_unproject_host", kp, desc, depth, n, has_point, outlier)
+
+
 class OrbError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"libsendslam_orb: {message} (status {code})")
@@ -1623,6 +1777,22 @@ def load():
                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ss_depth_batch_device.argtypes = [C.c_void_p, C.POINTER(DepthParams), C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_void_p]
+    lib.ss_triangulate_stereo_host.argtypes = [C.c_void_p, C.POINTER(TriStereoRig), C.POINTER(TriStereoParams), C.c_void_p, C.c_int] + [C.c_void_p] * 6 + \
+                                               [C.c_int, C.c_void_p, C.c_void_p]
+    lib.ss_triangulate_stereo_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p] + \
+                                                       [C.c_void_p, C.c_int64] * 4 + [C.POINTER(TriStereoParams)] + [C.c_void_p] * 6
+    lib.ss_triangulate_stereo_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_void_p, C.c_int64] * 2 + \
+                                                       [C.POINTER(TriStereoParams)] + [C.c_void_p] * 6
+    lib.ss_unproject_view_init.argtypes = [C.POINTER(Camera), C.c_void_p, C.c_void_p, C.POINTER(UnprojectView)]
+    lib.ss_unproject_host.argtypes = [C.POINTER(UnprojectView), C.POINTER(UnprojectParams), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_int64] + [C.c_void_p] * 8
+    lib.ss_unproject_pairs_device.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                                                 C.POINTER(UnprojectParams)] + [C.c_void_p] * 6
+    lib.ss_unproject_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(UnprojectParams)] + \
+                                             [C.c_void_p] * 6
+    lib.ss_unproject.argtypes = [C.c_void_p, C.POINTER(UnprojectView), C.POINTER(UnprojectParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                 C.c_int64] + [C.c_void_p] * 8
     lib.ss_pipe_create.argtypes = [C.c_int, C.POINTER(OrbParams), C.POINTER(Camera), C.POINTER(PipeConfig),
                                    C.POINTER(C.c_void_p)]
     lib.ss_pipe_destroy.argtypes = [C.c_void_p]
@@ -2582,6 +2752,82 @@ class OrbContext:
                            d_depth_out: int, d_summary: int):
         self._check(self._lib.ss_depth_batch_device(self._h, C.byref(params), d_depth, int(width), int(height), int(row_stride), int(frame_stride), d_right,
                                                     d_depth_out, d_summary))
+
+    # ---- the stereo form of the triangulation ----
+    def triangulate_stereo_pairs_device(self, d_q: int, d_q_kp: int, d_nq: int, d_t_kp: int, d_nt: int, d_idx: int, n_frames: int, rows_per_frame: int,
+                                        pairs, rigs, planes, params: TriStereoParams, d_info: int, d_points: int, d_point_desc: int, d_point_rows: int,
+                                        d_n_points: int, d_summary: int):
+        """triangulate_pairs_device with planes = ((d_depth1, stride), (d_right1, stride), (d_depth2, stride), (d_right2, stride)) and
+        rigs: n_frames TriStereoRig (host); d_info TRI_STEREO_INFO_DTYPE, d_summary TRI_STEREO_SUMMARY_DTYPE; asynchronous."""
+        w, r = _pairs_array(pairs), _rigs_array(rigs)
+        if len(w) != n_frames or len(r) != n_frames or len(planes) != 4:
+            raise ValueError("one pair and one rig per pair of frames, four planes")
+        flat = [int(v) for pl in planes for v in pl]
+        self._check(self._lib.ss_triangulate_stereo_pairs_device(self._h, d_q, d_q_kp, d_nq, d_t_kp, d_nt, d_idx, int(n_frames), int(rows_per_frame),
+                                                                 w.ctypes.data if n_frames else None, r.ctypes.data if n_frames else None, *flat,
+                                                                 C.byref(params), d_info, d_points, d_point_desc, d_point_rows, d_n_points, d_summary))
+
+    def triangulate_stereo_batch_device(self, d_idx: int, pairs, rigs, d_depth: int, depth_stride: int, d_right: int, right_stride: int,
+                                        params: TriStereoParams, d_info: int, d_points: int, d_point_desc: int, d_point_rows: int, d_n_points: int,
+                                        d_summary: int, train_src=None):
+        """the same on the frames of the last batch, frame b against train_src[b] (None: b - 1); the planes are [n_frames][kp_capacity]"""
+        w, r = _pairs_array(pairs), _rigs_array(rigs)
+        n_frames = self.batch_view().n_frames
+        if len(w) != n_frames or len(r) != n_frames:
+            raise ValueError("one pair and one rig per frame of the batch")
+        src = None if train_src is None else np.ascontiguousarray(train_src, np.int32)
+        self._check(self._lib.ss_triangulate_stereo_batch_device(self._h, None if src is None else src.ctypes.data, d_idx, w.ctypes.data, r.ctypes.data,
+                                                                 d_depth, int(depth_stride), d_right, int(right_stride), C.byref(params), d_info, d_points,
+                                                                 d_point_desc, d_point_rows, d_n_points, d_summary))
+
+    # ---- map points from depth: unprojection and the close-point rule (the rule: include/sendslam_orb.h) ----
+    @staticmethod
+    def _depth_blocks(depth_src, n_depth_blocks, n_frames):
+        src = None if depth_src is None else np.ascontiguousarray(depth_src, np.int32).reshape(-1)
+        if src is not None and len(src) != n_frames:
+            raise ValueError("one depth_src entry per frame")
+        if n_depth_blocks is None:
+            n_depth_blocks = n_frames if src is None else max(int(src.max(initial=-1)) + 1, 1)
+        return src, int(n_depth_blocks)
+
+    def unproject_pairs_device(self, d_kp: int, d_desc: int, d_n_kp: int, d_depth: int, depth_stride: int, n_frames: int, rows_per_frame: int, views,
+                               params: UnprojectParams, d_info: int, d_points: int, d_point_desc: int, d_point_rows: int, d_n_points: int,
+                               d_summary: int, d_has_point: int = 0, d_outlier: int = 0, depth_src=None, n_depth_blocks=None):
+        """views: n_frames UnprojectView (host).  d_depth: the depth of row 0 of block 0, depth_stride bytes to the next row (4: a
+        float plane; 16 at &points[0].depth: STEREO_POINT_DTYPE in place); depth_src: host ints, frame b reads block depth_src[b] of
+        n_depth_blocks (-1: the frame has no depth; None: block b).  d_info UNPROJECT_INFO_DTYPE [n_frames][rows_per_frame]; the
+        compact d_points / d_point_desc / d_point_rows with d_n_points are the blocks match_proj_pairs_device reads; d_summary
+        UNPROJECT_SUMMARY_DTYPE [n_frames]; asynchronous."""
+        v = _unproject_views_array(views)
+        if len(v) != n_frames:
+            raise ValueError("one view per frame")
+        src, blocks = self._depth_blocks(depth_src, n_depth_blocks, n_frames)
+        self._check(self._lib.ss_unproject_pairs_device(self._h, d_kp, d_desc, d_n_kp, d_depth, int(depth_stride), blocks,
+                                                        None if src is None else src.ctypes.data, d_has_point or None, d_outlier or None,
+                                                        int(n_frames), int(rows_per_frame), v.ctypes.data if n_frames else None, C.byref(params), d_info,
+                                                        d_points, d_point_desc, d_point_rows, d_n_points, d_summary))
+
+    def unproject_batch_device(self, d_depth: int, depth_stride: int, views, params: UnprojectParams, d_info: int, d_points: int, d_point_desc: int,
+                               d_point_rows: int, d_n_points: int, d_summary: int, d_has_point: int = 0, d_outlier: int = 0, depth_src=None,
+                               n_depth_blocks=None):
+        """the same on the frames of the last batch (rows_per_frame = kp_capacity); views: one per frame of the batch.  After
+        stereo_batch_device: d_depth at the depth field of its points, depth_stride 16, depth_src [0, -1, 1, -1, ...]"""
+        v = _unproject_views_array(views)
+        n_frames = self.batch_view().n_frames  # OrbError SS_ERR_STATE without a batch
+        if len(v) != n_frames:
+            raise ValueError("one view per frame of the batch")
+        src, blocks = self._depth_blocks(depth_src, n_depth_blocks, n_frames)
+        self._check(self._lib.ss_unproject_batch_device(self._h, d_depth, int(depth_stride), blocks, None if src is None else src.ctypes.data,
+                                                        d_has_point or None, d_outlier or None, v.ctypes.data,
+                                                        C.byref(params), d_info, d_points, d_point_desc, d_point_rows, d_n_points, d_summary))
+
+    def unproject(self, view: UnprojectView, params: UnprojectParams, kp, desc, depth, has_point=None, outlier=None):
+        """ss_unproject: one frame in host memory, synchronous; the arguments and the result of unproject_host with n = the rows"""
+        def call(n_, rows, k, de, d_at, stride, hp, ol, info, pts, pd, pr, n_pts, summary):
+            rc = self._lib.ss_unproject(self._h, C.byref(view), C.byref(params), k, de, rows, d_at, stride, hp, ol, info, pts, pd, pr, n_pts, summary)
+            self._check(rc)
+            return rc
+        return _unproject_one(call, "ss_unproject", kp, desc, depth, None, has_point, outlier)
 
     @staticmethod
     def _pnp_tables(views, kp_src, point_src, n_problems):
